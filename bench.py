@@ -268,6 +268,41 @@ def check_rollout(env, fused):
             E.rollout_status()
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, env, B, s):
+    """What the last timed rollout step computed, as a caller of the path receives it: the rollout-buffer slot ``s`` it filled
+    (observations acted on, actions, rewards, values, log-probabilities, done flags, episode stats) and the env state it left
+    (next observations / done flags / info rows, qpos / qvel).  One <name>.npy per array, float32 (float64 where the source is
+    float64 or an integer wider than float32's mantissa).  Above DUMP_LIMIT_BYTES a fixed, seeded sample of envs is written,
+    with its indices in env_index.npy."""
+    f32, f64 = np.float32, np.float64
+    out = {"obs": (B["obs"][:, s], f32), "actions": (B["act"][:, s], f32), "rewards": (B["rew"][:, s], f32),
+           "values": (B["val"][:, s], f32), "neglogp": (B["nlp"][:, s], f32), "opponent_neglogp": (B["onlp"][:, s], f32),
+           "dones": (B["done"][:, s], f32), "episode_done": (B["ep_done"][s], f32), "episode_reward": (B["ep_r"][s], f64),
+           "episode_length": (B["ep_l"][s], f64), "next_obs": (env.obs_dev, f32), "next_dones": (env.done_dev, f32),
+           "info": (env.info_dev, f64)}
+    out = {k: (v.cpu().numpy(), dt) for k, (v, dt) in out.items()}
+    states = [E.get_state() for E in env.engines]
+    out["qpos"] = (np.concatenate([st[0] for st in states]), f64)
+    out["qvel"] = (np.concatenate([st[1] for st in states]), f64)
+    # env axis: axis 1 of the [agent, env, ...] rollout-buffer slices, axis 0 of the env-side arrays
+    env_axis = {k: 1 if k in ("obs", "actions", "rewards", "values", "neglogp", "opponent_neglogp", "dones") else 0 for k in out}
+    N = env.num_envs
+    per_env = sum(a.size * np.dtype(dt).itemsize for a, dt in out.values()) / N
+    idx = None
+    if per_env * N > DUMP_LIMIT_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(N, int((DUMP_LIMIT_BYTES - 4096) // (per_env + 8)), replace=False))   # 8: env_index
+    os.makedirs(path, exist_ok=True)
+    for k, (a, dt) in out.items():
+        if idx is not None:
+            a = np.take(a, idx, axis=env_axis[k])
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a, dtype=dt))
+    if idx is not None:
+        np.save(os.path.join(path, "env_index.npy"), idx.astype(f64))
+
+
 def cpu_baseline(model, states, actions, steps, threads):
     """Times the CPU oracle (the float64 restatement; the reference's MuJoCo path cannot run here) on a bounded
     sample of the same workload: the first len(states[0]) envs of the GPU batch, same states, same action law."""
@@ -306,7 +341,11 @@ def main():
     ap.add_argument("--recurrent-steps", type=int, default=64, help="timed rollout steps of the secondary recurrent line (config-5 shard: 1024 envs, LSTM(128), pool of 16; 0 = skip)")
     ap.add_argument("--state-warmup", type=int, default=100,
                     help="untimed rollout steps that bring the env states from the reset law to the steady workload (SURVEY.md 8(d): >= 100)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0; at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # self-launch: one rank per GPU through torch.distributed.run, started BEFORE this process touches a GPU (a process that
@@ -424,6 +463,8 @@ def main():
     dt = time.perf_counter() - t0
     thr1 = hostcfg.throttle_stats()
     check_rollout(env, fused)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, env, B, (k0 + args.steps - 1) % ring)
     if fused:
         timed = [0]
     kern_ms = float(np.mean([ev0[k].elapsed_time(ev1[k]) for k in timed])) if timed else float("nan")   # fused: the K-step launch

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, has_gpu
+from fake_rollout import CASES, make_case
 
 pytestmark = pytest.mark.gpu
 
@@ -15,7 +16,6 @@ if has_gpu():
     from robosumo_selfplay_amd.runner import Runner
     from robosumo_selfplay_amd.vec_env import SumoVecEnv
     from oracle import ppo_oracle as po
-    from fake_rollout import CASES, make_case
 
     DEV = torch.device("cuda:0")
 
@@ -61,7 +61,7 @@ def test_forward_matches_oracle(ob, ac, n):
     assert np.array_equal(m.step(obs)[0], a)
 
 
-@pytest.mark.parametrize("case", CASES if has_gpu() else [], ids=[c[0] for c in CASES] if has_gpu() else [])
+@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
 def test_runner_host_mode_matches_reference_golden(case):
     """Our Runner (reward mix + IS ratios + V-trace on the GPU) driven by the same fake env/models as the reference
     Runner.  Everything that does not pass through exp() is bit-exact; ratios / agent-1 returns to 2e-6 relative

@@ -8,7 +8,8 @@ import pytest
 
 from robosumo_selfplay_amd import mjcf
 
-REF_ASSETS = "/root/reference/robosumo/robosumo/envs/assets"
+# copies of the reference's MJCF scene files (robosumo/robosumo/envs/assets/{tatami,ant,bug,spider}.xml), kept as test data
+REF_ASSETS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "robosumo_assets")
 
 # (nq, nv, nu, nbody, njnt, ngeom, obs, act) per agent type: SURVEY.md Appendix B table
 PER_AGENT = {"ant": (15, 14, 8, 13, 9, 13, 121, 8), "bug": (19, 18, 12, 19, 13, 19, 165, 12),
@@ -114,7 +115,6 @@ def test_blob_roundtrip(ant_model, oracle_lib):
     assert m2.to_blob() == ant_model.to_blob()
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_ASSETS), reason="reference checkout not present")
 @pytest.mark.parametrize("env_id", ["RoboSumo-Ant-vs-Ant-v0", "RoboSumo-Bug-vs-Spider-v0"])
 def test_packaged_tables_match_fresh_compile(env_id):
     fresh = mjcf.compile_env(env_id, REF_ASSETS)

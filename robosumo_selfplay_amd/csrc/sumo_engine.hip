@@ -925,27 +925,37 @@ __device__ __forceinline__ void collision(C& c) {
   int* plist = (int*)S(jar);
   int* prlist = (int*)S(aref);
   int ncon = 0, dropped = 0;
-  const int WR = c.P->aux.wrounds, AR = c.P->aux.arounds, nwp = c.P->aux.nwp, maxcand = c.L.maxcand;
+  const auto& ax = aux_view(c);   // static-Layout variants: round counts are literals, the round loop unrolls completely
+  const int WR = ax.wrounds, AR = ax.arounds, nwp = ax.nwp, maxcand = c.L.maxcand;
   const unsigned long long lt_mask = (1ull << lane) - 1ull;
   // The pair table lists the pairs with a static world geom first (WR rounds of 64, padded), then the pairs between
-  // moving geoms (AR rounds).  Rounds are tested four at a time, loads first, so their latencies overlap; a candidate
-  // with queue position in [base, base + maxcand) is stored, and the (rare) overflow is handled by running the tests
-  // again for the next window.
+  // moving geoms (AR rounds), contiguously.  The test is a chain of dependent loads (pair record -> centres in LDS / the
+  // world geom's extent), so the rounds of both kinds are taken as ONE sequence, eight at a time, every record and bound of
+  // a batch requested before the first test: Ant's 8 rounds are one batch (were three: 4-round batches, world and moving
+  // pairs in separate loops).  A candidate with queue position in [base, base + maxcand) is stored, and the (rare)
+  // overflow is handled by running the tests again for the next window.
   int base = 0, total = 0;
   do {
     int run = 0;
     const int PT_GAS* prp = pt_global(launder_ptr(c.prp));
     const float PT_GAS* pbp = pt_global(launder_ptr(c.pbp));
-    // ---- world pairs: distance from the moving geom's centre to the static geom's extent (box / segment / half space)
-    for (int r0 = 0; r0 < WR; r0 += 4) {
-      int rec[4], pass[4];
+    constexpr int RB = 8;
+    for (int r0 = 0; r0 < WR + AR; r0 += RB) {
+      int rec[RB], pass[RB];
+      float bnd[RB];
 #pragma unroll
-      for (int q = 0; q < 4; q++) {
+      for (int q = 0; q < RB; q++) {
         const int r = r0 + q;
-        rec[q] = 0; pass[q] = 0;
+        rec[q] = 0; bnd[q] = 0.f;
+        if (r < WR + AR) { rec[q] = prp[WAVE * r]; bnd[q] = pbp[WAVE * r]; }
+      }
+#pragma unroll
+      for (int q = 0; q < RB; q++) {
+        const int r = r0 + q;
+        pass[q] = 0;
+        const double bound = (double)bnd[q];
         if (r < WR) {
-          rec[q] = prp[WAVE * r];
-          const double bound = (double)pbp[WAVE * r];
+          // world pair: distance from the moving geom's centre to the static geom's extent (box / segment / half space)
           const int ca = rec[q] & 0xFF, cw = (rec[q] >> 8) & 0xFF, w = cw >= nb ? cw - nb : 0;
           const double* pa = S(xipos) + 3 * ca;
           const double* pw = S(xipos) + 3 * cw;
@@ -957,34 +967,8 @@ __device__ __forceinline__ void collision(C& c) {
 #pragma unroll
           for (int k = 0; k < 3; k++) { double e = fmax(fmax(ctr[k] - wl[k], wl[3 + k] - ctr[k]), 0.0); d2 += e * e; }
           pass[q] = ((rec[q] >> 17) & 1) && !(d2 > bound * bound);
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < 4; q++) {
-        const int r = r0 + q;
-        if (r < WR) {
-          const unsigned long long bal = __ballot(pass[q]);
-          const int pos = run + __popcll(bal & lt_mask) - base;
-          if (pass[q] && pos >= 0 && pos < maxcand) {
-            const int ca = rec[q] & 0xFF, cw = (rec[q] >> 8) & 0xFF;
-            plist[pos] = lane + WAVE * r;
-            prlist[pos] = (rec[q] & (1 << 16)) ? (cw | (ca << 8)) : (ca | (cw << 8));   // bit 16: the world geom is geom1
-          }
-          run += __popcll(bal);
-        }
-      }
-    }
-    // ---- pairs of moving geoms: bounding spheres
-    prp += WAVE * WR; pbp += WAVE * WR;
-    for (int r0 = 0; r0 < AR; r0 += 4) {
-      int rec[4], pass[4];
-#pragma unroll
-      for (int q = 0; q < 4; q++) {
-        const int r = r0 + q;
-        rec[q] = 0; pass[q] = 0;
-        if (r < AR) {
-          rec[q] = prp[WAVE * r];
-          const double bound = (double)pbp[WAVE * r];
+        } else if (r < WR + AR) {
+          // pair of moving geoms: bounding spheres
           const double* p1 = S(xipos) + 3 * (rec[q] & 0xFF);
           const double* p2 = S(xipos) + 3 * ((rec[q] >> 8) & 0xFF);
           const double t[3] = {p2[0] - p1[0], p2[1] - p1[1], p2[2] - p1[2]};
@@ -992,12 +976,21 @@ __device__ __forceinline__ void collision(C& c) {
         }
       }
 #pragma unroll
-      for (int q = 0; q < 4; q++) {
+      for (int q = 0; q < RB; q++) {
         const int r = r0 + q;
-        if (r < AR) {
+        if (r < WR + AR) {
           const unsigned long long bal = __ballot(pass[q]);
           const int pos = run + __popcll(bal & lt_mask) - base;
-          if (pass[q] && pos >= 0 && pos < maxcand) { plist[pos] = nwp + lane + WAVE * r; prlist[pos] = rec[q] & 0xFFFF; }
+          if (pass[q] && pos >= 0 && pos < maxcand) {
+            const int ca = rec[q] & 0xFF, cw = (rec[q] >> 8) & 0xFF;
+            if (r < WR) {
+              plist[pos] = lane + WAVE * r;
+              prlist[pos] = (rec[q] & (1 << 16)) ? (cw | (ca << 8)) : (ca | (cw << 8));   // bit 16: the world geom is geom1
+            } else {
+              plist[pos] = nwp + lane + WAVE * (r - WR);
+              prlist[pos] = rec[q] & 0xFFFF;
+            }
+          }
           run += __popcll(bal);
         }
       }

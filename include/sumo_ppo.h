@@ -14,6 +14,7 @@
  *   ppo_adv_moments/_normalize  PPOModel.train advantage normalisation (model.py:180-185); split in two so a
  *                               multi-GPU run can all-reduce the three moments in between
  *   ppo_grad                    loss + gradients of model.py:65-132 (sums, not means: divide by the global count)
+ *   ppo_a2c_grad / _loss_stats  loss + gradients and statistics of ActorCriticModel (model.py:257-310)
  *   ppo_clip_adam               tf.clip_by_global_norm + tf.train.AdamOptimizer(epsilon=1e-5).apply_gradients
  *                               (model.py:121-139)
  *
@@ -198,6 +199,21 @@ int ppo_grad(const float* params, const float* obs, int obs_stride, int ob_dim, 
  * entropy, approxkl, clipfrac}; entropy = sum(logstd + 0.5 log(2 pi e)) of the policy the loss was evaluated with
  * (baselines distributions.py:246-247).  logstd float32 [ac_dim] (inside the flat parameter vector), stats double[PPO_NSTATS]. */
 int ppo_loss_stats(const double* stats, const float* logstd, int ac_dim, double* out5, void* stream);
+
+/* --- A2C (the reference's ActorCriticModel, model.py:216-372) -------------------------------------------------------------------
+ * ppo_a2c_grad: gradient of the A2C loss over rows idx[0..n) (idx may be NULL = identity), on the same MFMA kernel as ppo_grad with
+ * the per-row loss swapped at compile time:
+ *   sum-loss = sum_i w_i adv_i neglogp_i + vf_coef * sum_i 0.5 w_i (v_i - R_i)^2 - n_local * ent_coef * entropy
+ * with every per-row term pre-divided by inv_count = 1 / global_count, as ppo_grad.  No ratio, no clipping; unlike ppo_grad the
+ * IS weight multiplies the value term too (model.py:275).  adv [n] is in minibatch order (ppo_adv_normalize's output); obs,
+ * actions, returns, is_weight are data rows.  stats double[PPO_NSTATS] accumulate: 0 sum w adv neglogp, 1 sum 0.5 w (v-R)^2,
+ * 5 sum w, 6 count; slots 3 and 4 receive 0.  workspace: ppo_grad_workspace_bytes(ob_dim, ac_dim) bytes, ZERO-INITIALISED once by
+ * the caller, same contract as ppo_grad (one gradient launch in flight per workspace; ppo_grad and ppo_a2c_grad may share one).
+ * ppo_a2c_loss_stats: out3 = {policy_loss, value_loss, policy_entropy} (model.py:296-297) from those sums and logstd [ac_dim]. */
+int ppo_a2c_grad(const float* params, const float* obs, int obs_stride, int ob_dim, int ac_dim, const float* actions,
+                 const float* adv, const float* returns, const float* is_weight, const int32_t* idx, int n, double inv_count,
+                 float ent_coef, float vf_coef, float* grads, double* stats, void* workspace, void* stream);
+int ppo_a2c_loss_stats(const double* stats, const float* logstd, int ac_dim, double* out3, void* stream);
 
 /* params -= Adam(clip_by_global_norm(grads, max_grad_norm)); m, v float32 [P]; step t >= 1 (TF1 bias correction).
  * max_grad_norm <= 0 disables clipping.  stats[7] receives the global gradient norm. */

@@ -1,0 +1,187 @@
+"""A2C self-play driver: counterpart of the reference's ``alg_ac.learn`` (alg_ac.py:25-341).
+
+Per update: opponent selection from the checkpoint directory, one rollout of ``nsteps`` steps (``runner.run(update)``: the fused
+``sumo_rollout_steps`` launch with MLP policies), optional reuse of the opponent's samples, then ONE optimiser step of
+``ActorCriticModel`` on the whole batch (no minibatches, no epochs: nbatch_train = nbatch, alg_ac.py:110-111).  Rollout buffers
+stay in HBM.  Not reproduced: TF summaries, the eval runner, matplotlib histograms.
+
+Decisions on the reference's A2C path:
+  1. alg_ac.py:153 builds its Runner without ``rho_bar`` / ``c_bar``, which runner.py:36 requires (TypeError before the first step).
+     Here they are ``learn`` keywords with PPO's RoboSumo defaults, 10.0 / 1.0.  They enter only agent 1's V-trace returns -- agent
+     0's clips are 1 (runner.py:175-177), so the learner's own returns are plain GAE(lambda) -- i.e. they matter only with
+     opponent-data reuse.
+  2. ``use_opponent_data='off_policy'`` / ``'both'`` use ratios the reference computes in commented-out code (alg_ac.py:285-290,
+     NameError).  Supported: None and ``'direct'`` (weights 1); the other two raise NotImplementedError.
+  3. ``opponent_mode='ours'`` has no selection block in alg_ac.py:200-213: the opponent stays checkpoint 00000 for the whole run (and
+     the reference's log line reads an unset ``idx``).  That v0-forever behaviour is what the reference trains against and is kept;
+     the log line reports version 0.
+Single GPU, MLP policies only (``comm`` / ``network='lstm'`` raise NotImplementedError)."""
+import os
+import os.path as osp
+import time
+from collections import deque
+
+import numpy as np
+
+from .alg_ppo import assemble_update_batch, constfn, explained_variance, safemean
+
+NEGLOGP_THRESHOLD = 50.0      # alg_ac.py:241-243, hard-coded there
+
+
+def check_config(network, use_opponent_data, comm):
+    """The scope of this learner, checked before anything touches the GPU."""
+    if network == "lstm":
+        raise NotImplementedError("the A2C learner (--algo ac) supports MLP policies only; recurrent (lstm) policies train with --algo ppo")
+    if use_opponent_data in ("off_policy", "both"):
+        raise NotImplementedError("use_opponent_data=%r: the reference's A2C computes these importance ratios in commented-out code "
+                                  "(alg_ac.py:285-290) and fails with NameError; supported here: None and 'direct'" % (use_opponent_data,))
+    if use_opponent_data not in (None, "direct"):
+        raise ValueError("use_opponent_data %r" % (use_opponent_data,))
+    if comm is not None:
+        raise NotImplementedError("the A2C learner (--algo ac) runs on a single GPU (no comm)")
+
+
+def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_data=None, eval_env=None, seed=None, nsteps=2048,
+          ent_coef=0.0, lr=3e-4, vf_coef=0.5, max_grad_norm=0.5, gamma=0.99, lam=0.95, log_interval=10, save_interval=1,
+          load_path=None, model_fn=None, update_fn=None, init_fn=None, mpi_rank_weight=1, comm=None, nagent=1, anneal_bound=500,
+          fix_opponent_path=None, rho_bar=10.0, c_bar=1.0, log_dir=None, verbose=True, opponent_pool=1, **network_kwargs):
+    check_config(network, use_opponent_data, comm)
+    if opponent_mode not in ("ours", "random", "latest", "fix"):
+        raise ValueError("opponent_mode %r" % (opponent_mode,))
+    import torch
+    from .a2c_model import ActorCriticModel
+    from .policies import build_policy
+    from .runner import Runner
+    if seed is not None:                                                # set_global_seeds (misc_util.py:48-62)
+        np.random.seed(seed)
+        torch.manual_seed(seed)
+    lr = constfn(lr) if isinstance(lr, float) else lr
+    total_timesteps = int(total_timesteps)
+    policy = build_policy(env, network, **network_kwargs)
+    nenvs = env.num_envs
+    ob_space, ac_space = env.observation_space[0], env.action_space[0]
+    nbatch = nenvs * nsteps
+    model_fn = model_fn or ActorCriticModel
+    dev = getattr(env, "device", torch.device("cuda", 0))
+    mk = lambda scope, trainable: model_fn(policy=policy, ob_space=ob_space, ac_space=ac_space, nbatch_act=nenvs, nbatch_train=nbatch,
+                                           nsteps=nsteps, ent_coef=ent_coef, vf_coef=vf_coef, max_grad_norm=max_grad_norm,
+                                           trainable=trainable, model_scope=scope, device=dev.index or 0)
+    model = mk("model_0", True)
+    models = [model] + [mk("model_%d" % i, False) for i in range(1, nagent)]
+    log_dir = log_dir or os.environ.get("OPENAI_LOGDIR") or "/tmp/robosumo_selfplay_amd"
+    checkdir = osp.join(log_dir, "checkpoints")
+    model.save(osp.join(checkdir, "00000"))                              # alg_ac.py:117-118
+    if load_path is not None:
+        for m in models:
+            m.load(load_path)
+    for i, m in enumerate(models):
+        m.act_model.seed((seed or 0) * 1000 + 17 * i)
+    runner = Runner(env=env, models=models, nsteps=nsteps, nagent=nagent, gamma=gamma, lam=lam, rho_bar=rho_bar, c_bar=c_bar,
+                    anneal_bound=anneal_bound)
+    # opponent_pool = K > 1 (extension, as in alg_ppo): K snapshots resident in HBM, one per env tile, drawn by the selection law of
+    # opponent_mode; K = 1 is the reference's single opponent for all envs
+    pool = None
+    if int(opponent_pool) > 1:
+        if opponent_mode == "fix":
+            raise ValueError("opponent_pool > 1 makes no sense with a fixed opponent")
+        if not runner.fused_ok():
+            raise NotImplementedError("opponent_pool > 1 runs inside the fused rollout launch (SUMO_FUSED_ROLLOUT != 0)")
+        from .opponent_pool import OpponentPool
+        pool = runner.opponent_pool = OpponentPool(policy, int(opponent_pool), nenvs, dev)
+    epinfobuf = deque(maxlen=100)
+    if init_fn is not None:
+        init_fn()
+    tfirststart = time.perf_counter()
+    history = dict(opponent_versions=[], useful_ratio=[], lossvals=[], fps=[], select_s=[], rollout_s=[], update_s=[],
+                   env_diverged=[], env_dropped_contacts=[], env_rollout_aborts=[])     # per update, from the engine's counters
+    env_stats_prev = env.stats() if hasattr(env, "stats") else None
+    nupdates = total_timesteps // nbatch
+    loaded = None        # the checkpoint(s) the opponent holds: re-read from disk only when the selection changes
+    for update in range(1, nupdates + 1):
+        tstart = time.perf_counter()
+        frac = 1.0 - (update - 1.0) / nupdates
+        lrnow = lr(frac)
+        # ---- opponent selection (alg_ac.py:172-213)
+        if opponent_mode == "fix":
+            if update == 1:                                              # a policy-zoo MLP net (alg_ac.py:175-189)
+                from .policy_zoo import FixedOpponentModel, load_zoo_policy
+                if fix_opponent_path is None:
+                    raise ValueError("opponent_mode='fix' needs fix_opponent_path=<policy_zoo .npy> (reference default: "
+                                     "robosumo/robosumo/policy_zoo/assets/ant/mlp/agent-params-v3.npy)")
+                zoo = load_zoo_policy(fix_opponent_path, ac_space.shape[0], device=dev)
+                zoo.seed((seed or 0) * 1000 + 17)
+                runner.models[1] = FixedOpponentModel(zoo)
+            history["opponent_versions"].append([])
+        else:
+            if update == 1 or opponent_mode == "ours":                   # 'ours': v0 for the whole run (decision 3 above)
+                paths, choices = [osp.join(checkdir, "00000")], [0]
+            else:
+                paths = sorted(osp.join(checkdir, f) for f in os.listdir(checkdir))
+                K = pool.capacity if pool is not None else 1
+                if opponent_mode == "random":                            # alg_ac.py:203-205
+                    choices = [int(x) for x in np.random.choice(len(paths), K)]
+                else:                                                    # 'latest', alg_ac.py:206-208
+                    choices = list(range(len(paths) - 1, max(-1, len(paths) - 1 - K), -1))
+            sel = tuple(paths[c] for c in choices)
+            if sel != loaded:
+                runner.models[1].load(sel[0])
+                if pool is not None:
+                    for k, p in enumerate(sel):
+                        pool.set_snapshot(k, p)
+                    pool.assign_round_robin(range(len(sel)))
+                loaded = sel
+            history["opponent_versions"].append([int(osp.basename(p)) for p in sel])
+        tsel = time.perf_counter()
+        # ---- rollout
+        obs, returns, masks, actions, values, neglogpacs, rewards, _onlp, _oobs, _oact, _states, epinfos, _opr, _oer, _tr = runner.run(update)
+        torch.cuda.synchronize(dev)
+        t_roll = time.perf_counter() - tsel
+        if isinstance(obs, np.ndarray):       # host-mode Runner: continue on the device
+            up = lambda x: torch.as_tensor(np.ascontiguousarray(x)).to(dev)
+            obs, returns, masks, actions, values, neglogpacs, rewards = map(up, (obs, returns, masks, actions, values, neglogpacs, rewards))
+        # ---- batch: the learner's rows, plus the opponent's usable rows under 'direct' (alg_ac.py:241-262)
+        if use_opponent_data is None:
+            b_obs, b_ret, b_act, b_val = obs[0], returns[0], actions[0], values[0]
+            weights = torch.ones(nbatch, dtype=torch.float32, device=dev)
+            history["useful_ratio"].append(None)
+        else:
+            ub = assemble_update_batch(obs, returns, masks, actions, values, neglogpacs, rewards, None, None, nbatch=nbatch,
+                                       neglogp_threshold=NEGLOGP_THRESHOLD, use_opponent_data=use_opponent_data)
+            b_obs, b_ret, b_act, b_val, weights = ub["obs"], ub["returns"], ub["actions"], ub["values"], ub["weights"]
+            history["useful_ratio"].append(ub["useful_ratio"])
+        epinfobuf.extend(epinfos[-epinfobuf.maxlen:])
+        # ---- one optimiser step on the whole batch (alg_ac.py:273-276)
+        out3 = model.train_device(lrnow, b_obs.contiguous(), b_ret.contiguous(), b_act.contiguous(), b_val.contiguous(), weights)
+        lossvals = out3.cpu().numpy().astype(np.float64)                # (waits for the step)
+        tnow = time.perf_counter()
+        history["lossvals"].append(lossvals)
+        history["select_s"].append(tsel - tstart)                      # opponent selection (checkpoint reads)
+        history["rollout_s"].append(t_roll)
+        history["update_s"].append(tnow - tsel - t_roll)
+        history["fps"].append(nbatch / (tnow - tstart))
+        env_note = ""
+        if env_stats_prev is not None:                                  # the engine's fault counters of this update (as alg_ppo)
+            st_now = env.stats()
+            dv, dc = st_now["diverged"] - env_stats_prev["diverged"], st_now["dropped"] - env_stats_prev["dropped"]
+            ab = (st_now["rollout_aborts"] + st_now.get("handover_mismatches", 0)
+                  - env_stats_prev["rollout_aborts"] - env_stats_prev.get("handover_mismatches", 0))
+            env_stats_prev = st_now
+            history["env_diverged"].append(int(dv)); history["env_dropped_contacts"].append(int(dc)); history["env_rollout_aborts"].append(int(ab))
+            if dv or dc or ab:
+                env_note = "  [env: %d diverged steps, %d dropped contacts, %d rollout aborts]" % (dv, dc, ab)
+        if update_fn is not None:
+            update_fn(update)
+        if verbose and (update % log_interval == 0 or update == 1):
+            ev = explained_variance(b_val.cpu().numpy(), b_ret.cpu().numpy())
+            opp = history["opponent_versions"][-1]
+            print("update %d/%d  opponent %s  fps %.0f  rollout %.2fms  update %.2fms  ev %.3f  eprewmean %.2f  eplenmean %.1f  %s" % (
+                update, nupdates, opp[0] if opp else "fix", history["fps"][-1], 1e3 * t_roll, 1e3 * history["update_s"][-1], ev,
+                safemean([e["r"] for e in epinfobuf]), safemean([e["l"] for e in epinfobuf]),
+                " ".join("%s %.4g" % (n, v) for n, v in zip(model.loss_names, lossvals))) + env_note, flush=True)
+        elif env_note:
+            print("update %d/%d%s" % (update, nupdates, env_note), flush=True)
+        if save_interval and (update % save_interval == 0 or update == 1):
+            model.save(osp.join(checkdir, "%.5i" % update))               # alg_ac.py:333-339
+    model.history = history
+    model.time_elapsed = time.perf_counter() - tfirststart
+    return model

@@ -1456,7 +1456,12 @@ __device__ __forceinline__ float quad_bcast(float v) {   // the value of lane R 
   return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), R * 0x55, 0xf, 0xf, false));
 }
 #define GRAD_HS 68   /* activation-tile row stride of the gradient kernel (floats): 16-byte aligned rows, 128-bit reads conflict free */
-template <int KT, bool PI>
+// The objective the kernel differentiates (a compile-time parameter: each instantiation holds only its own per-row loss code).
+//   GRAD_PPO  clipped surrogate of model.py:65-111 (ppo_grad)
+//   GRAD_A2C  ActorCriticModel's loss, model.py:257-310 (ppo_a2c_grad): pg = w adv neglogp, no ratio / clip; the value term is
+//             0.5 w (v - R)^2, i.e. weighted too; stats slot 5 receives sum w, slots 3 / 4 (approxkl, clipfrac) stay 0
+enum GradObjective { GRAD_PPO = 0, GRAD_A2C = 1 };
+template <int KT, bool PI, int OBJ>
 __device__ __forceinline__ void grad_net_coop(const GradArgs& a, float* lds, int lane, int w) {
   const ParamLayout& L = a.L;
   const int XS = a.XS, D = L.D, A = L.A;
@@ -1483,6 +1488,7 @@ __device__ __forceinline__ void grad_net_coop(const GradArgs& a, float* lds, int
   const int xr = tid >> 4, xc = tid & 15;
   constexpr int NXJ = KT;   // 16 * KT columns cover D
   constexpr int RDS = 20;   // side-tile row: actions 0..15 | 16 old neglogp (policy) / return (value) | 17 advantage | 18 weight
+                            // (value net: 17 repeats the return; 18 is the weight under GRAD_A2C, the return under GRAD_PPO)
   float xv[NXJ], xact = 0.0f, xsc = 0.0f;
   auto fetch_src = [&](int tile) -> int {
     const int row = tile * 16 + xr;
@@ -1500,10 +1506,12 @@ __device__ __forceinline__ void grad_net_coop(const GradArgs& a, float* lds, int
     for (int j = 0; j < NXJ; j++) { const int c = xc + 16 * j; xv[j] = orow[c < D ? c : D - 1]; }
     if (PI) {
       xact = a.actions[(size_t)src * A + (xc < A ? xc : 0)];
-      const float* sp = xc == 0 ? a.oldnlp + src : (xc == 1 ? a.adv + row : a.weight + src);
+      // (GRAD_A2C has no old neglogp: slot 16 is loaded from the return of the row, a data-row array like it, and never read)
+      const float* sp = xc == 0 ? (OBJ == GRAD_A2C ? a.returns : a.oldnlp) + src : (xc == 1 ? a.adv + row : a.weight + src);
       xsc = sp[0];
     } else {
-      xsc = a.returns[src];
+      const float* sp = (OBJ == GRAD_A2C && xc == 2) ? a.weight + src : a.returns + src;
+      xsc = sp[0];
     }
   };
   auto commit = [&](float* xb, float* rd) {   // columns D .. 16 KT - 1 are written as zeros (the launch sizes the row stride for the variant: XS >= 16 KT)
@@ -1542,7 +1550,7 @@ __device__ __forceinline__ void grad_net_coop(const GradArgs& a, float* lds, int
 #pragma unroll
   for (int ft = 0; ft < 4; ft++) gW1[ft] = (f32x4){0, 0, 0, 0};
   float gb0 = 0, gb1 = 0, gb2 = 0, glogstd = 0;
-  double st_pg = 0, st_vf = 0, st_kl = 0, st_clip = 0, st_cnt = 0;
+  double st_pg = 0, st_vf = 0, st_kl = 0, st_clip = 0, st_cnt = 0, st_w = 0;
   const float logstd = (PI && col) ? a.params[L.logstd + i] : 0.0f;
   const float inv_std = 1.0f / expf(logstd);
   const float sum_logstd = row16_sum(logstd);
@@ -1616,7 +1624,19 @@ __device__ __forceinline__ void grad_net_coop(const GradArgs& a, float* lds, int
         ssm = rm == r ? ss : ssm;
       }
       float dnlp_m;
-      {
+      if (OBJ == GRAD_A2C) {   // loss row = inv_count * w * adv * neglogp: d / d neglogp is a constant of the row
+        const int row = r0 + 4 * kq + rm;
+        const bool rok = row < a.n;
+        const float* rdr = rd + (4 * kq + rm) * RDS;
+        const float nlp = 0.5f * ssm + 0.5f * LOG2PI_F * (float)A + sum_logstd;
+        const float adv = rok ? rdr[17] : 0.0f, wt = rok ? rdr[18] : 0.0f;
+        dnlp_m = wt * adv * a.inv_count;
+        if (w == 0 && rok && i < 4) {
+          st_pg += (double)wt * (double)adv * (double)nlp;
+          st_w += (double)wt;
+          st_cnt += 1.0;
+        }
+      } else {
         const int row = r0 + 4 * kq + rm;
         const bool rok = row < a.n;
         const float* rdr = rd + (4 * kq + rm) * RDS;
@@ -1660,6 +1680,14 @@ __device__ __forceinline__ void grad_net_coop(const GradArgs& a, float* lds, int
         const float v = out[r] + bias2;
         const float R = rok ? rd[(4 * kq + r) * RDS + 16] : v;
         const float dv = v - R;
+        if (OBJ == GRAD_A2C) {   // weighted value loss (model.py:275): the weight rides in side-tile slot 18
+          const float wt = rok ? rd[(4 * kq + r) * RDS + 18] : 0.0f;
+          const float dhead = (rok && col) ? a.vf_coef * a.inv_count * (wt * dv) : 0.0f;
+          if (w == 0 && rok && i == 0) { st_vf += 0.5 * (double)wt * (double)dv * (double)dv; st_cnt += 1.0; }
+          mydout[(4 * kq + r) * 18 + i] = dhead;
+          gb2 += dhead;
+          continue;
+        }
         const float dhead = (rok && col) ? a.vf_coef * a.inv_count * dv : 0.0f;
         if (w == 0 && rok && i == 0) { st_vf += 0.5 * (double)dv * (double)dv; st_cnt += 1.0; }
         mydout[(4 * kq + r) * 18 + i] = dhead;
@@ -1750,13 +1778,19 @@ __device__ __forceinline__ void grad_net_coop(const GradArgs& a, float* lds, int
         t_pg += __shfl_xor(t_pg, o, WAVE); t_kl += __shfl_xor(t_kl, o, WAVE); t_clip += __shfl_xor(t_clip, o, WAVE); t_cnt += __shfl_xor(t_cnt, o, WAVE);
       }
     }
+    double t_w = st_w;
+    if (OBJ == GRAD_A2C) {
+      if (PI)
+        for (int o = 1; o < 4; o <<= 1) t_w += __shfl_xor(t_w, o, WAVE);
+      for (int o = 16; o < 64; o <<= 1) t_w += __shfl_xor(t_w, o, WAVE);
+    }
     for (int o = 16; o < 64; o <<= 1) {
       t_pg += __shfl_xor(t_pg, o, WAVE); t_vf += __shfl_xor(t_vf, o, WAVE); t_kl += __shfl_xor(t_kl, o, WAVE);
       t_clip += __shfl_xor(t_clip, o, WAVE); t_cnt += __shfl_xor(t_cnt, o, WAVE);
     }
     if (lane == 0) {
       double* ws = a.wstats + ((size_t)(PI ? 0 : 1) * a.nwaves + blockIdx.x) * 8;
-      ws[0] = t_pg; ws[1] = t_vf; ws[2] = 0; ws[3] = t_kl; ws[4] = t_clip; ws[5] = 0; ws[6] = PI ? t_cnt : 0.0; ws[7] = 0;
+      ws[0] = t_pg; ws[1] = t_vf; ws[2] = 0; ws[3] = t_kl; ws[4] = t_clip; ws[5] = OBJ == GRAD_A2C ? t_w : 0.0; ws[6] = PI ? t_cnt : 0.0; ws[7] = 0;
     }
   }
   GP_DRAIN();
@@ -1767,11 +1801,11 @@ __device__ __forceinline__ void grad_net_coop(const GradArgs& a, float* lds, int
 #define GRAD_LDS_FLOATS(XS) (2 * 16 * (XS) + 4 * 16 * GRAD_HS + 4 * 16 * 18 + 2 * 16 * 20 + 4 * 64 * 4)
 // Ant (KT = 8): 255 registers, two workgroups per CU.  The wider first layers of the Bug / Spider nets (KT = 11 / 14: 44 / 56 resident
 // B operands and as many accumulators) get the whole register file of a SIMD instead of spilling: one workgroup per CU.
-template <int KT>
+template <int KT, int OBJ>
 __global__ void __launch_bounds__(256, (KT <= 8 ? 2 : 1)) ppo_grad_kernel(GradArgs a) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (blockIdx.y == 0) grad_net_coop<KT, true>(a, smem_f, lane, wid);
-  else grad_net_coop<KT, false>(a, smem_f, lane, wid);
+  if (blockIdx.y == 0) grad_net_coop<KT, true, OBJ>(a, smem_f, lane, wid);
+  else grad_net_coop<KT, false, OBJ>(a, smem_f, lane, wid);
 }
 
 // grads[p] = sum over workgroups of the slab of the net that owns p; stats += per-workgroup stats.  ONE launch, two levels, fixed
@@ -1842,12 +1876,12 @@ extern "C" size_t ppo_grad_workspace_bytes(int ob_dim, int ac_dim) {
          (size_t)((L.P + 255) / 256) * sizeof(unsigned int);              // | arrival counter per 256-parameter chunk (zero between calls)
 }
 
-extern "C" int ppo_grad(const float* params, const float* obs, int obs_stride, int ob_dim, int ac_dim, const float* actions,
-                        const float* adv_mb, const float* returns, const float* old_neglogp, const float* is_weight, const int32_t* idx,
-                        int n, double inv_count, float cliprange, float ent_coef, float vf_coef, float* grads, double* stats,
-                        float* log_ratio_out, void* workspace, void* stream) {
-  if (!params || !obs || !actions || !adv_mb || !returns || !old_neglogp || !is_weight || !grads || !stats || !workspace || n <= 0)
-    FAIL(-1, "bad arguments");
+// ppo_grad and ppo_a2c_grad: the same launches (gradient kernel of objective OBJ, then the slab reduction) on the same workspace layout
+template <int OBJ>
+static int grad_launch(const float* params, const float* obs, int obs_stride, int ob_dim, int ac_dim, const float* actions,
+                       const float* adv_mb, const float* returns, const float* old_neglogp, const float* is_weight, const int32_t* idx,
+                       int n, double inv_count, float cliprange, float ent_coef, float vf_coef, float* grads, double* stats,
+                       float* log_ratio_out, void* workspace, void* stream) {
   if (ac_dim < 1 || ac_dim > MAXA) FAIL(-2, "ac_dim %d not in [1,%d]", ac_dim, MAXA);
   int KT = (ob_dim + 15) / 16;
   if (KT > 14) FAIL(-3, "ob_dim %d too large (max 224)", ob_dim);
@@ -1876,10 +1910,10 @@ extern "C" int ppo_grad(const float* params, const float* obs, int obs_stride, i
   do {                                                                                                                  \
     static thread_local size_t lds_set_##KTV = 0;                                                                       \
     if (lds > 64 * 1024 && lds > lds_set_##KTV) {                                                                       \
-      HIPCHK(hipFuncSetAttribute((const void*)ppo_grad_kernel<KTV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+      HIPCHK(hipFuncSetAttribute((const void*)ppo_grad_kernel<KTV, OBJ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
       lds_set_##KTV = lds;                                                                                              \
     }                                                                                                                   \
-    hipLaunchKernelGGL(ppo_grad_kernel<KTV>, dim3(nblocks, 2), dim3(256), lds, s, a);                                  \
+    hipLaunchKernelGGL((ppo_grad_kernel<KTV, OBJ>), dim3(nblocks, 2), dim3(256), lds, s, a);                           \
   } while (0)
   if (KT <= 8) LAUNCH(8);
   else if (KT <= 11) LAUNCH(11);
@@ -1895,6 +1929,27 @@ extern "C" int ppo_grad(const float* params, const float* obs, int obs_stride, i
   }
   HIPCHK(hipGetLastError());
   return 0;
+}
+
+extern "C" int ppo_grad(const float* params, const float* obs, int obs_stride, int ob_dim, int ac_dim, const float* actions,
+                        const float* adv_mb, const float* returns, const float* old_neglogp, const float* is_weight, const int32_t* idx,
+                        int n, double inv_count, float cliprange, float ent_coef, float vf_coef, float* grads, double* stats,
+                        float* log_ratio_out, void* workspace, void* stream) {
+  if (!params || !obs || !actions || !adv_mb || !returns || !old_neglogp || !is_weight || !grads || !stats || !workspace || n <= 0)
+    FAIL(-1, "bad arguments");
+  return grad_launch<GRAD_PPO>(params, obs, obs_stride, ob_dim, ac_dim, actions, adv_mb, returns, old_neglogp, is_weight, idx, n, inv_count,
+                               cliprange, ent_coef, vf_coef, grads, stats, log_ratio_out, workspace, stream);
+}
+
+// A2C: under GRAD_A2C the gradient kernel neither reads an old neglogp nor writes log-ratios (the return array, indexed by data row
+// like the old neglogp, fills the unused pointer)
+extern "C" int ppo_a2c_grad(const float* params, const float* obs, int obs_stride, int ob_dim, int ac_dim, const float* actions,
+                            const float* adv, const float* returns, const float* is_weight, const int32_t* idx, int n, double inv_count,
+                            float ent_coef, float vf_coef, float* grads, double* stats, void* workspace, void* stream) {
+  if (!params || !obs || !actions || !adv || !returns || !is_weight || !grads || !stats || !workspace || n <= 0)
+    FAIL(-1, "bad arguments");
+  return grad_launch<GRAD_A2C>(params, obs, obs_stride, ob_dim, ac_dim, actions, adv, returns, returns, is_weight, idx, n, inv_count, 0.0f,
+                               ent_coef, vf_coef, grads, stats, nullptr, workspace, stream);
 }
 
 #ifdef PPO_GRAD_PROBE
@@ -1951,6 +2006,21 @@ __global__ void ppo_loss_stats_kernel(const double* stats, const float* logstd, 
 extern "C" int ppo_loss_stats(const double* stats, const float* logstd, int ac_dim, double* out5, void* stream) {
   if (!stats || !logstd || !out5 || ac_dim < 1) FAIL(-1, "bad arguments");
   hipLaunchKernelGGL(ppo_loss_stats_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, stats, logstd, ac_dim, out5);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// ActorCriticModel's three statistics (model.py:296-297: policy loss, value loss, entropy) from the sums ppo_a2c_grad accumulated
+__global__ void ppo_a2c_loss_stats_kernel(const double* stats, const float* logstd, int A, double* out3) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  double ent = 0.0;
+  for (int i = 0; i < A; i++) ent += (double)logstd[i] + 0.5 * 2.8378770664093453;   // log(2 pi e)
+  const double cnt = stats[6];
+  out3[0] = stats[0] / cnt; out3[1] = stats[1] / cnt; out3[2] = ent;
+}
+extern "C" int ppo_a2c_loss_stats(const double* stats, const float* logstd, int ac_dim, double* out3, void* stream) {
+  if (!stats || !logstd || !out3 || ac_dim < 1) FAIL(-1, "bad arguments");
+  hipLaunchKernelGGL(ppo_a2c_loss_stats_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, stats, logstd, ac_dim, out3);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """CLI counterpart of the reference's run.py (run.py:211-251) for the hot path:
     python run.py --env RoboSumo-Ant-vs-Ant-v0 --num_env 4096 --num_timesteps 2097152 --nsteps=128
+    python run.py --env RoboSumo-Ant-vs-Ant-v0 --algo ac --num_env 1024 --num_timesteps 512000      (A2C learner, one GPU)
 Unknown ``--key=value`` flags are forwarded to ``learn`` like the reference does (run.py:29-63), but parsed with
 ``ast.literal_eval`` instead of ``eval``.  Under ``torchrun`` every rank takes an equal shard of ``--num_env``.
 """
@@ -34,7 +35,7 @@ def main(argv):
     ap.add_argument("--num_timesteps", type=float, default=1e8)
     ap.add_argument("--network", default="mlp")
     ap.add_argument("--num_env", type=int, default=1)
-    ap.add_argument("--algo", default="ppo")
+    ap.add_argument("--algo", default="ppo", help="ppo (PPO2, alg_ppo.learn) or ac (A2C, alg_ac.learn); the reference's td3 is not ported")
     ap.add_argument("--log_path", default="results")
     ap.add_argument("--suffix", default="0")
     ap.add_argument("--env_groups", type=int, default=0, help="env groups per GPU (vec_env.SumoVecEnv): 0 = 1 when the whole rollout is one fused "
@@ -46,8 +47,15 @@ def main(argv):
                     "evaluation / play scripts use -0.5, which is what the policy-zoo nets expect")
     args, unknown = ap.parse_known_args(argv)
     extra = parse_unknown(unknown)
-    from robosumo_selfplay_amd import alg_ppo, defaults, dist as sdist
+    from robosumo_selfplay_amd import alg_ac, alg_ppo, defaults, dist as sdist
     from robosumo_selfplay_amd.vec_env import make_vec_env
+    learn = {"ppo": alg_ppo.learn, "ac": alg_ac.learn}.get(args.algo)
+    kw = defaults.get_default_params(args.env, args.algo)       # (td3 / unknown algorithms stop here)
+    kw.update(extra)
+    if args.algo == "ac":             # the A2C learner's scope, checked before anything touches the GPU
+        if sdist.env_rank_world()[2] > 1:
+            raise SystemExit("--algo ac runs on a single GPU: launch it without torchrun / with WORLD_SIZE=1")
+        alg_ac.check_config(args.network, kw.get("use_opponent_data"), None)
     comm = sdist.init_process_group()
     rank, local_rank, world = sdist.env_rank_world()
     log_path = os.path.join(args.log_path, "%s-%s" % (args.env, args.suffix))
@@ -63,16 +71,14 @@ def main(argv):
     import torch
     local_rank = local_rank % max(1, torch.cuda.device_count())        # gloo rehearsal of N ranks on fewer GPUs
     env = make_vec_env(args.env, per, args.seed + start, device=local_rank, groups=groups, cfrc_mode=args.cfrc_mode, adjust_z=args.adjust_z)  # run.py:144: env i gets seed + i
-    kw = defaults.get_default_params(args.env, args.algo)
-    kw.update(extra)
     if args.network == "lstm":       # the RoboSumo defaults describe the MLP (defaults.py:8-26); recurrent nets share the latent
         for k in ("value_network", "num_hidden", "num_layers", "activation"):
             kw.pop(k, None)
     if rank == 0:
         with open(os.path.join(log_path, "config.pkl"), "wb") as f:        # run.py:176-177
             pickle.dump(dict(vars(args), **kw), f)
-    model = alg_ppo.learn(network=args.network, env=env, seed=args.seed, total_timesteps=int(args.num_timesteps) // world,
-                          nagent=len(env.agents), log_dir=log_path, comm=comm, **kw)
+    model = learn(network=args.network, env=env, seed=args.seed, total_timesteps=int(args.num_timesteps) // world,
+                  nagent=len(env.agents), log_dir=log_path, comm=comm, **kw)
     env.close()
     return model
 

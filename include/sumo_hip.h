@@ -114,6 +114,31 @@ typedef struct sumo_rollout_lstm {
 } sumo_rollout_lstm;
 int sumo_rollout_steps_lstm(sumo_handle_t h, const sumo_rollout_lstm* r, float* actions_dev, float* obs_dev, double* info_dev,
                             uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream);
+/* K consecutive steps of checkpoint-vs-checkpoint MATCHES of every env of the engine in ONE launch: replaces the step loop of the
+ * reference's compare_history_version.py:16-47 / play_evaluation.py (model[0].step on obs 0, model[1].step on obs 1, env.step, the
+ * winner bookkeeping) for MLP(64,64) policies, on the fused launch of sumo_rollout_steps (same scheduler, hand-over and env step).
+ * The wavefront that owns env e evaluates two policy trunks: snapshot idx0[e] acts for agent 0 on obs 0, snapshot idx1[e] for
+ * agent 1 on obs 1 (idx0[e] == idx1[e] is allowed); no value net, no cross-scoring, no rollout buffer.
+ *   params    float32 [nsnap][P] flat parameter vectors in the sumo_ppo.h layout; idx0 / idx1 int32 [E] (DEVICE) select each env's
+ *             snapshots -- an index outside [0, nsnap) raises the launch's abort flag (sumo_rollout_status returns -20)
+ *   noise0 / noise1  float32 [T][E][ac_dim] standard-normal draws: action = mean + exp(logstd) * noise (PPOModel.step); both NULL =
+ *             deterministic play, action = mean (PPOModel.step(deterministic=True)); steps s0 .. s0 + K - 1 are read
+ *   score     int32 [E][3] = {agent-0 wins, agent-1 wins, draws}, read and updated in place: where agent 0's episode ends in a step, a
+ *             win if agent 0 carries the winner flag (info[.][0][7] bit 0), a loss if only agent 1 does, a draw otherwise; counted
+ *             while wins + losses + draws < quota (compare_history_version.py:33-41, eval_robosumo_against_fix.py's rule)
+ * The env-side buffers are those of sumo_step (actions receives both actions), left as after the last step.  Ordering contract as
+ * sumo_rollout_steps; the outcome is read with sumo_rollout_status.  Refused: cfrc_mode rne_post, mixed match-ups (ob_dim / ac_dim
+ * differing between the sides), nsnap < 1, ob_dim / ac_dim other than the scene's. */
+typedef struct sumo_match {
+  const float* params;
+  const int32_t *idx0, *idx1;
+  int nsnap, ob_dim, ac_dim;
+  int T, s0, K, quota;
+  const float *noise0, *noise1;
+  int32_t* score;
+} sumo_match;
+int sumo_match_steps(sumo_handle_t h, const sumo_match* m, float* actions_dev, float* obs_dev, double* info_dev, uint8_t* done_dev,
+                     double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream);
 /* cfrc_mode (reference agents.py:190-214 reads sim.data.cfrc_ext into 84 of the 121 observation entries):
  *   0 = zero (default): what the reference produces -- its MuJoCo 2.1 scenes declare no force / torque / accelerometer sensor, so
  *       mj_rnePostConstraint never runs and cfrc_ext stays at its reset value 0;

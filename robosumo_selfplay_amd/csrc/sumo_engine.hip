@@ -2553,6 +2553,15 @@ struct RolloutArgs {
   const ppo_lstm_net* onets;
   const int32_t* tile_net;
   float *st0, *st1;
+  // checkpoint-vs-checkpoint matches (sumo_match_steps, POLICY 2): agent 0 acts with snapshot idx0[e], agent 1 with idx1[e] of
+  // snaps [nsnap][P]; noise0 / noise1 NULL = deterministic play.  score [N][3] = {agent-0 wins, agent-1 wins, draws} of the env,
+  // counted while their sum is below quota.  An env's counters cross waves between its tickets like its record: lane 0 of the
+  // owning wave reads them with hand_load<true> and writes them with hand_store<true> before the s_waitcnt vmcnt(0) that precedes
+  // the progress store, so the next owner (which polls prog[e] first) sees them.
+  const float* snaps;
+  const int32_t *idx0, *idx1;
+  int* score;
+  int nsnap, quota;
 };
 
 template <class C, class SA, class RA>
@@ -2741,6 +2750,66 @@ __device__ __forceinline__ void rollout_policy_phase_lstm(C& c, const SA& a, con
   wave_sync();
 }
 
+// Match policy phase (sumo_match_steps): two policy trunks, snapshot idx0[e] on the tile (its row 0 = agent 0's observation acts)
+// and snapshot idx1[e] (its row 1 = agent 1's observation acts); no value net, no cross-scoring, nothing recorded.  The action is
+// the mean (noise NULL, PPOModel.step(deterministic=True)) or mean + exp(logstd) * noise through gauss_row as ppo_forward samples.
+// A snapshot index outside [0, nsnap) raises the launch's abort flag (sumo_rollout_status fails) and plays snapshot 0 instead.
+template <class C, class SA, class RA>
+__device__ __forceinline__ void rollout_policy_phase_match(C& c, const SA& a, const RA& r, int e, int s) {
+  const int lane = c.lane, i = lane & 15, kq = lane >> 4;
+  const int D = r.L.D, A = r.L.A, XS = r.XS;
+  float* xbuf = (float*)(c.sm + r.lds_off);        // [2][XS] | h1 [2][PT_HS] | h2 [2][PT_HS]
+  float* h1 = xbuf + 2 * XS;
+  float* h2 = h1 + 2 * PT_HS;
+  const float* ob = a.obs + (size_t)e * 2 * a.obs_stride;
+  for (int k = lane; k < D; k += WAVE) { xbuf[k] = hand_load<true>(ob + k); xbuf[XS + k] = hand_load<true>(ob + a.obs_stride + k); }
+  wave_sync();
+  int j0 = pt_global(r.idx0)[e], j1 = pt_global(r.idx1)[e];
+  if ((unsigned)j0 >= (unsigned)r.nsnap || (unsigned)j1 >= (unsigned)r.nsnap) {
+    if (lane == 0) __hip_atomic_store(pt_global(a.abort_flag), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    j0 = (unsigned)j0 < (unsigned)r.nsnap ? j0 : 0; j1 = (unsigned)j1 < (unsigned)r.nsnap ? j1 : 0;
+  }
+  const float PT_GAS* p0 = pt_global(r.snaps) + (size_t)j0 * r.L.P;
+  const float PT_GAS* p1 = pt_global(r.snaps) + (size_t)j1 * r.L.P;
+  const f32x4 m0 = trunk_forward<false, 2>(pi_net((const float*)p0, r.L), xbuf, XS, D, h1, h2, lane);
+  wave_sync();
+  const f32x4 m1 = trunk_forward<false, 2>(pi_net((const float*)p1, r.L), xbuf, XS, D, h1, h2, lane);
+  const bool ok = i < A && kq == 0;                 // rows 0 and 1 live in the first 16 lanes (D layout: rows 4 kq + r)
+  float act0 = m0[0], act1 = m1[1];
+  if (r.noise0) {
+    const float ls0 = ok ? p0[r.L.logstd + i] : 0.0f, ls1 = ok ? p1[r.L.logstd + i] : 0.0f;
+    const size_t nz = ((size_t)s * a.N + e) * A + i;
+    const float n0 = ok ? pt_global(r.noise0)[nz] : 0.0f, n1 = ok ? pt_global(r.noise1)[nz] : 0.0f;
+    (void)gauss_row(m0[0], expf(ls0), 0.0f, ok, true, n0, act0, A);
+    (void)gauss_row(m1[1], expf(ls1), 0.0f, ok, true, n1, act1, A);
+  }
+  if (ok) {
+    float* ae = const_cast<float*>(a.actions) + (size_t)e * 2 * a.act_stride;
+    hand_store<true>(ae + i, act0); hand_store<true>(ae + a.act_stride + i, act1);     // the env's action buffer (output only)
+    const auto& mdl = model_view(c);
+    S(ctrl)[MI(agent_uadr)[0] + i] = (double)act0; S(ctrl)[MI(agent_uadr)[1] + i] = (double)act1;   // the step's control vector
+  }
+  wave_sync();   // the action buffer is read back by the env step (other lanes), the scratch region becomes the mass matrix again
+}
+
+// Match post phase: where agent 0's episode ended in the step, score it from the step's winner flags (info[.][7] bit 0, just
+// written by this lane): a win if agent 0 carries the flag, a loss if only agent 1 does, a draw otherwise (timeouts, diverged states)
+// -- policy_zoo._evaluate_against's rule.  Counted while wins + losses + draws < quota.
+template <class C, class SA, class RA>
+__device__ __forceinline__ void rollout_post_phase_match(C& c, const SA& a, const RA& r, int e) {
+  SYNC();   // the step's episode record was parked in LDS by lane 0 of the epilogue
+  if (c.lane == 0 && ((const int*)(S(stash) + 10))[1]) {
+    const double* io = a.info + (size_t)e * 2 * SUMO_INFO_STRIDE;
+    const int f0 = (int)hand_load<true>(io + 7), f1 = (int)hand_load<true>(io + SUMO_INFO_STRIDE + 7);
+    int* sc = r.score + 3 * e;
+    const int w = hand_load<true>(sc), l = hand_load<true>(sc + 1), d = hand_load<true>(sc + 2);
+    if (w + l + d < r.quota) {
+      const int slot = (f0 & 1) ? 0 : ((f1 & 1) ? 1 : 2);
+      hand_store<true>(sc + slot, (slot == 0 ? w : slot == 1 ? l : d) + 1);
+    }
+  }
+}
+
 template <class C, class SA, class RA>
 __device__ __forceinline__ void rollout_post_phase(C& c, const SA& a, const RA& r, int e, int s) {
   SYNC();   // the step's reward inputs and episode record were parked in LDS by lane 0 of the epilogue
@@ -2776,7 +2845,8 @@ struct RolloutLaunch { StepArgs a; RolloutArgs r; };
 // launch's abort flag (counted in sumo_stats[9]) and every wave drains.
 #define ROLLOUT_SPIN_LIMIT (1u << 22)   /* polls of ~0.5 us each */
 
-template <int NV, int POLICY, int SL = 0>   // POLICY 0: MLP(64,64) policy / value nets; 1: LSTM(128) with shared value head; SL 1: static Layout
+template <int NV, int POLICY, int SL = 0>   // POLICY 0: MLP(64,64) policy / value nets; 1: LSTM(128) with shared value head; 2: MLP matches
+                                            // (sumo_match_steps: score counters instead of rollout buffers); SL 1: static Layout
 __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(SUMO_WPE_OF(NV), SUMO_WPE_OF(NV))))
 sumo_rollout_kernel(const Params* P, RolloutLaunch launch_args) {
   // `launch_args` is read in place from the kernel-argument segment (second argument, 8-byte aligned right behind P) through a
@@ -2830,6 +2900,7 @@ sumo_rollout_kernel(const Params* P, RolloutLaunch launch_args) {
     if (c.dbg) c.st_forward = 0;
 #endif
     if constexpr (POLICY == 1) rollout_policy_phase_lstm<128>(c, lp->a, lp->r, e, s);
+    else if constexpr (POLICY == 2) rollout_policy_phase_match(c, lp->a, lp->r, e, s);
     else rollout_policy_phase(c, lp->a, lp->r, e, s);
 #ifdef SUMO_DBG_HARD_BARRIER
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -2842,7 +2913,8 @@ sumo_rollout_kernel(const Params* P, RolloutLaunch launch_args) {
     asm volatile("" : "+s"(e), "+s"(k));
     lp = launder_sptr(LP);
     s = lp->r.s0 + k;
-    rollout_post_phase(c, lp->a, lp->r, e, s);
+    if constexpr (POLICY == 2) rollout_post_phase_match(c, lp->a, lp->r, e);
+    else rollout_post_phase(c, lp->a, lp->r, e, s);
     prof = lp->r.prof;
     if (prof && c.lane == 0) {
       const unsigned long long t2 = wall_clock64(), t1 = (unsigned long long)__double_as_longlong(S(stash)[11]);
@@ -3670,12 +3742,15 @@ static int rollout_launch(sumo_engine* E, const RolloutArgs& r, int policy, floa
   size_t lds_ = (size_t)E->L.total_bytes;
   if (E->static_layout == 1) {
     if (policy == 1) hipLaunchKernelGGL((sumo_rollout_kernel<28, 1, 1>), g_, b_, lds_, st_, E->d_params, rl);
+    else if (policy == 2) hipLaunchKernelGGL((sumo_rollout_kernel<28, 2, 1>), g_, b_, lds_, st_, E->d_params, rl);
     else hipLaunchKernelGGL((sumo_rollout_kernel<28, 0, 1>), g_, b_, lds_, st_, E->d_params, rl);
   } else if (E->static_layout == 2) {
     if (policy == 1) hipLaunchKernelGGL((sumo_rollout_kernel<44, 1, 2>), g_, b_, lds_, st_, E->d_params, rl);
+    else if (policy == 2) hipLaunchKernelGGL((sumo_rollout_kernel<44, 2, 2>), g_, b_, lds_, st_, E->d_params, rl);
     else hipLaunchKernelGGL((sumo_rollout_kernel<44, 0, 2>), g_, b_, lds_, st_, E->d_params, rl);
   } else if (!for_kernel_variant(E->hm.nv, [&](auto nvc_) {
         if (policy == 1) hipLaunchKernelGGL((sumo_rollout_kernel<decltype(nvc_)::value, 1>), g_, b_, lds_, st_, E->d_params, rl);
+        else if (policy == 2) hipLaunchKernelGGL((sumo_rollout_kernel<decltype(nvc_)::value, 2>), g_, b_, lds_, st_, E->d_params, rl);
         else hipLaunchKernelGGL((sumo_rollout_kernel<decltype(nvc_)::value, 0>), g_, b_, lds_, st_, E->d_params, rl);
       }))
     FAIL(-19, "no kernel variant for nv=%d", E->hm.nv);
@@ -3752,6 +3827,28 @@ extern "C" int sumo_rollout_steps_lstm(sumo_handle_t E, const sumo_rollout_lstm*
   const size_t need = (size_t)(2 * r.XS + 7 * 128) * sizeof(float), have = (size_t)(E->L.i_base - r.lds_off) * sizeof(double);
   if (E->L.ctrl >= E->L.M || E->L.stash >= E->L.M || need > have) FAIL(-8, "policy scratch (%zu B) does not fit the per-step LDS area (%zu B)", need, have);
   return rollout_launch(E, r, 1, actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev, stream);
+}
+
+extern "C" int sumo_match_steps(sumo_handle_t E, const sumo_match* mo, float* actions_dev, float* obs_dev, double* info_dev,
+                                uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
+  if (!E || !mo || !actions_dev || !obs_dev || !info_dev || !done_dev || !ep_r_dev || !ep_dr_dev || !ep_l_dev) FAIL(-1, "bad arguments");
+  if (!mo->params || !mo->idx0 || !mo->idx1 || !mo->score) FAIL(-2, "sumo_match: missing buffer");
+  if (!mo->noise0 != !mo->noise1) FAIL(-2, "sumo_match: noise0 and noise1 are both given (stochastic play) or both NULL (deterministic)");
+  int od = 0, ad = 0;
+  if (int rc = rollout_scene(E, mo->T, E->N, 0, mo->s0, mo->K, &od, &ad)) return rc;
+  if (mo->ob_dim != od || mo->ac_dim != ad || mo->ac_dim > PT_MAXA) FAIL(-4, "ob_dim %d / ac_dim %d do not match the scene (%d / %d)", mo->ob_dim, mo->ac_dim, od, ad);
+  if (mo->nsnap < 1) FAIL(-7, "nsnap %d: the snapshot table needs at least one entry", mo->nsnap);
+  if (mo->quota < 0) FAIL(-9, "quota %d", mo->quota);
+  HIPCHK(hipSetDevice(E->device));
+  RolloutArgs r;
+  memset(&r, 0, sizeof r);
+  r.snaps = mo->params; r.idx0 = mo->idx0; r.idx1 = mo->idx1; r.score = mo->score; r.nsnap = mo->nsnap; r.quota = mo->quota;
+  r.noise0 = mo->noise0; r.noise1 = mo->noise1;
+  r.T = mo->T; r.Ntot = E->N; r.s0 = mo->s0; r.K = mo->K;
+  r.XS = x_stride(mo->ob_dim); r.L = make_layout(mo->ob_dim, mo->ac_dim); r.lds_off = E->L.M;
+  if ((size_t)(2 * r.XS + 4 * PT_HS) * sizeof(float) > (size_t)E->L.msize * sizeof(double))
+    FAIL(-8, "policy scratch (%zu B) does not fit the mass-matrix region (%zu B)", (size_t)(2 * r.XS + 4 * PT_HS) * sizeof(float), (size_t)E->L.msize * sizeof(double));
+  return rollout_launch(E, r, 2, actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev, stream);
 }
 
 #ifdef SUMO_POLICY_PROBE

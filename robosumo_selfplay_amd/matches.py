@@ -1,0 +1,363 @@
+"""Checkpoint-vs-checkpoint matches on the GPU: the reference's compare_history_version.py / play_evaluation.py, plus a
+round-robin over the versions of one run.
+
+The reference loads version *i* of run P1 and version *i* of run P2 into two models and plays ``--trials`` games between them
+on one env (stochastic ``model.step`` for both sides, ``agent._adjust_z = -0.5`` on every agent, compare_history_version.py:16-47,
+:73-74), writing P1's win rate per version.  Here the snapshots of every match-up live as rows of one device table
+(:class:`SnapshotTable`), each env plays one match-up (``idx0[e]`` for agent 0, ``idx1[e]`` for agent 1), and the fused match
+launch (include/sumo_hip.h ``sumo_match_steps``) runs ``chunk`` whole env steps of every env with both policies evaluated inside
+the owning wave, keeping each env's score {agent-0 wins, agent-1 wins, draws} on the device.  The host reads that small counter
+tensor once per launch.
+
+An episode is a win if agent 0 carries the 'winner' flag when it ends, a loss if only agent 1 does, a draw otherwise
+(compare_history_version.py:33-41; policy_zoo._evaluate_against).  ``fused=False`` plays the same games step by step: two
+``ppo_forward`` launches (what ``PPOModel.step`` runs) per match-up and side, then ``step_device``; with the same seed it draws
+the same noise and yields bit-identical envs and scores.  Recurrent (LSTM) checkpoints are refused.
+"""
+import os
+import warnings
+
+import numpy as np
+
+from . import policies
+
+EVAL_ADJUST_Z = -0.5      # compare_history_version.py:73-74
+
+
+# ---- checkpoints ---------------------------------------------------------------------------------------------------------
+def param_count(ob_dim, ac_dim):
+    return sum(int(np.prod(s)) for s in policies.param_shapes(ob_dim, ac_dim))
+
+
+def snapshot_vector(spec, src):
+    """Flat float32 parameter vector (numpy) of an MLP(64,64) policy of ``spec`` from a ``PPOModel`` / ``ActorCriticModel``, a
+    flat vector, the 13-array list of a checkpoint (model.py:153-177) or a checkpoint path written by ``PPOModel.save``.
+    LSTM models and checkpoints are refused (recurrent matches are not supported)."""
+    D, A = spec.ob_dim, spec.ac_dim
+    label = None
+    if getattr(src, "recurrent", False):
+        raise ValueError("recurrent (LSTM) models cannot play fused matches: only MLP(64,64) policies are supported")
+    if isinstance(src, (str, os.PathLike)):
+        import joblib
+        label = str(src)
+        src = joblib.load(os.path.expanduser(str(src)))            # only files written by PPOModel.save()
+    if hasattr(src, "params") and hasattr(src, "spec"):            # PPOModel / ActorCriticModel
+        if (src.spec.ob_dim, src.spec.ac_dim) != (D, A):
+            raise ValueError("model's policy (%d, %d) does not match the table's (%d, %d)" % (src.spec.ob_dim, src.spec.ac_dim, D, A))
+        return src.params.detach().cpu().numpy().astype(np.float32).reshape(-1)
+    if hasattr(src, "detach"):                                     # torch tensor
+        src = src.detach().cpu().numpy()
+    if isinstance(src, dict):
+        raise ValueError("dict checkpoints are not supported here; load them into a PPOModel first")
+    if isinstance(src, (list, tuple)):
+        shapes = policies.param_shapes(D, A)
+        lshapes = policies.lstm_param_shapes(D, A)
+        got = [tuple(np.shape(p)) for p in src]
+        if len(src) == len(lshapes) and got == [tuple(s) for s in lshapes]:
+            raise ValueError("%s is an LSTM checkpoint: recurrent matches are not supported (MLP(64,64) checkpoints only)"
+                             % (label or "checkpoint"))
+        if len(src) != len(shapes) or got != [tuple(s) for s in shapes]:
+            raise ValueError("%s does not match the MLP(64,64) policy of ob_dim %d / ac_dim %d" % (label or "checkpoint", D, A))
+        return policies.flatten_params(list(src))
+    v = np.ascontiguousarray(src, np.float32).reshape(-1)
+    P = param_count(D, A)
+    if v.size != P:
+        raise ValueError("snapshot has %d parameters, the policy %d" % (v.size, P))
+    return v
+
+
+class SnapshotTable(object):
+    """Device table ``params [capacity][P]`` of frozen MLP(64,64) policies in checkpoint order (the layout of sumo_ppo.h)."""
+
+    def __init__(self, spec, capacity, device=0):
+        import torch
+        self.spec = spec
+        self.capacity = int(capacity)
+        if self.capacity < 1:
+            raise ValueError("capacity must be >= 1")
+        self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        self.P = param_count(spec.ob_dim, spec.ac_dim)
+        self.params = torch.zeros((self.capacity, self.P), dtype=torch.float32, device=self.device)
+        self.filled = np.zeros(self.capacity, bool)
+        self.labels = [None] * self.capacity
+
+    def set(self, k, src, label=None):
+        """Fill row ``k`` (see :func:`snapshot_vector` for what ``src`` may be)."""
+        import torch
+        if not 0 <= k < self.capacity:
+            raise IndexError("row %d outside the table of %d" % (k, self.capacity))
+        v = snapshot_vector(self.spec, src)
+        self.params[k].copy_(torch.from_numpy(v).to(self.device))
+        self.filled[k] = True
+        self.labels[k] = label if label is not None else (str(src) if isinstance(src, (str, os.PathLike)) else None)
+
+    @classmethod
+    def from_checkpoints(cls, spec, paths, device=0):
+        t = cls(spec, len(paths), device)
+        for k, p in enumerate(paths):
+            t.set(k, p)
+        return t
+
+
+def checkpoint_dir(path):
+    """``path`` may be a run directory (holding ``checkpoints/``) or the checkpoint directory itself."""
+    ck = os.path.join(path, "checkpoints")
+    return ck if os.path.isdir(ck) else path
+
+
+def list_checkpoints(path):
+    """Checkpoint ids of a run, sorted, ``00000`` (the untrained initial version) excluded (compare_history_version.py:63-69)."""
+    ck = checkpoint_dir(path)
+    ids = [f for f in os.listdir(ck) if f.isdigit() and f != "00000" and os.path.isfile(os.path.join(ck, f))]
+    return sorted(ids, key=lambda f: (int(f), f))
+
+
+def pair_versions(ids1, ids2):
+    """Version i of P1 with version i of P2, up to the shorter list (the reference indexes P2 with P1's positions and fails
+    where P2 is shorter; here the extra versions are dropped with a warning)."""
+    n = min(len(ids1), len(ids2))
+    if len(ids1) != len(ids2):
+        warnings.warn("P1 has %d versions and P2 %d: comparing the first %d" % (len(ids1), len(ids2), n))
+    return list(zip(ids1[:n], ids2[:n]))
+
+
+def split_trials(trials, num_env):
+    """(envs_per_pair, rounds_per_env) with envs_per_pair * rounds_per_env == trials: the largest divisor of ``trials`` that
+    fits ``num_env`` envs, so a match-up's ``trials`` games run on as many envs in parallel as possible."""
+    trials, num_env = int(trials), int(num_env)
+    if trials < 1 or num_env < 1:
+        raise ValueError("trials and num_env must be >= 1")
+    epp = max(d for d in range(1, min(trials, num_env) + 1) if trials % d == 0)
+    return epp, trials // epp
+
+
+def plan_batches(npairs, envs_per_pair, num_envs):
+    """Match-ups per launch batch: each batch gives pair b of the batch the CONTIGUOUS env block [b * envs_per_pair,
+    (b + 1) * envs_per_pair), so waves running at the same time mostly read the same snapshots (L2 reuse)."""
+    if envs_per_pair < 1 or envs_per_pair > num_envs:
+        raise ValueError("envs_per_pair %d must be in [1, %d]" % (envs_per_pair, num_envs))
+    per = num_envs // envs_per_pair
+    return [list(range(b, min(b + per, npairs))) for b in range(0, npairs, per)]
+
+
+def env_assignment(pairs, batch, envs_per_pair, num_envs):
+    """Host arrays (idx0, idx1, active) of one batch: env e of block b plays pairs[batch[b]]; envs past the last block play
+    snapshot 0 against itself and are not counted (active False)."""
+    idx0 = np.zeros(num_envs, np.int32)
+    idx1 = np.zeros(num_envs, np.int32)
+    active = np.zeros(num_envs, bool)
+    for b, p in enumerate(batch):
+        sl = slice(b * envs_per_pair, (b + 1) * envs_per_pair)
+        idx0[sl], idx1[sl] = pairs[p]
+        active[sl] = True
+    return idx0, idx1, active
+
+
+# ---- one chunk of steps ----------------------------------------------------------------------------------------------------
+def _check_env(env, table):
+    D0, D1 = env.model.obs_dims
+    A0, A1 = env.model.act_dims
+    if D0 != D1 or A0 != A1:
+        raise ValueError("matches need a homogeneous match-up (one observation / action space for both sides); got ob_dim %d / %d, "
+                         "ac_dim %d / %d" % (D0, D1, A0, A1))
+    if (table.spec.ob_dim, table.spec.ac_dim) != (D0, A0):
+        raise ValueError("snapshot table's policy (%d, %d) does not match the env (%d, %d)" % (table.spec.ob_dim, table.spec.ac_dim, D0, A0))
+    if getattr(env, "cfrc_mode", "zero") != "zero":
+        raise ValueError("matches run on the fused launch, which refuses cfrc_mode 'rne_post'")
+
+
+def match_steps_fused(env, table, idx0, idx1, score, quota, K, noise=None):
+    """K match steps of every env in one ``sumo_match_steps`` launch per env group.  idx0 / idx1 int32 CUDA tensors [N],
+    score int32 CUDA [N][3] (updated in place), noise None (deterministic) or a pair of float32 CUDA [K][N][A] tensors.  Raises
+    if the launch was cut short (``rollout_status``)."""
+    from . import capi
+    _check_env(env, table)
+    A = table.spec.ac_dim
+    for g in range(env.groups):
+        sl = env._gs(g)
+        mo = capi.Match()
+        mo.params = table.params.data_ptr()
+        mo.idx0, mo.idx1 = idx0[sl].data_ptr(), idx1[sl].data_ptr()
+        mo.nsnap, mo.ob_dim, mo.ac_dim = table.capacity, table.spec.ob_dim, A
+        mo.T, mo.s0, mo.K, mo.quota = int(K), 0, int(K), int(quota)
+        keep = None
+        if noise is not None:
+            keep = [n[:, sl].contiguous() if env.groups > 1 else n for n in noise]
+            mo.noise0, mo.noise1 = keep[0].data_ptr(), keep[1].data_ptr()
+        mo.score = score[sl].data_ptr()
+        E = env.engines[g]
+        E.match_steps(mo, env.act_dev[sl].data_ptr(), env.obs_dev[sl].data_ptr(), env.info_dev[sl].data_ptr(), env.done_dev[sl].data_ptr(),
+                      env.ep_r_dev[sl].data_ptr(), env.ep_dr_dev[sl].data_ptr(), env.ep_l_dev[sl].data_ptr(), stream=env._stream())
+        E.rollout_status()
+        del keep
+
+
+def _runs(idx):
+    """(start, end, value) of the runs of equal consecutive entries of a host array."""
+    cut = np.flatnonzero(np.diff(idx)) + 1
+    starts = np.concatenate([[0], cut])
+    ends = np.concatenate([cut, [len(idx)]])
+    return [(int(s), int(e), int(idx[s])) for s, e in zip(starts, ends)]
+
+
+def match_steps_stepwise(env, table, idx0, idx1, score, quota, K, noise=None):
+    """The same K steps on the step-by-step path: per step and side one ``ppo_forward`` launch (``PPOModel.step``'s kernel) for
+    every run of envs that share a snapshot, then ``step_device`` and the score update.  idx0 / idx1 are host arrays."""
+    import torch
+    from . import ppo_capi
+    _check_env(env, table)
+    idx0, idx1 = np.asarray(idx0, np.int64), np.asarray(idx1, np.int64)
+    if min(idx0.min(), idx1.min()) < 0 or max(idx0.max(), idx1.max()) >= table.capacity:
+        raise ValueError("snapshot index outside [0, %d)" % table.capacity)
+    D, A = table.spec.ob_dim, table.spec.ac_dim
+    N = env.num_envs
+    L = ppo_capi.lib()
+    st = env._stream()
+    acts = env.act_dev                          # the env's action buffer receives both actions, as in the fused launch
+    act = [torch.empty((N, A), dtype=torch.float32, device=env.device) for _ in range(2)]
+    nlp = torch.empty(N, dtype=torch.float32, device=env.device)
+    runs = [_runs(idx0), _runs(idx1)]
+    obs = env.obs_dev
+    for t in range(int(K)):
+        for side in range(2):
+            for s, e, k in runs[side]:
+                nz = None if noise is None else noise[side][t, s:e]
+                ppo_capi.chk(L.ppo_forward(table.params[k].data_ptr(), obs[s:e, side].data_ptr(), e - s, obs.stride(0), D, A, ppo_capi.FWD_PI,
+                                           ppo_capi.ptr(nz), None, act[side][s:e].data_ptr(), nlp[s:e].data_ptr(), None, None, st))
+            acts[:, side, :A] = act[side]
+        obs, info, done, _, _, _ = env.step_device(acts)
+        _score_step(score, info, done, quota)
+
+
+def _score_step(score, info, done, quota):
+    import torch
+    fin = done[:, 0] != 0
+    f = info[:, :, 7].to(torch.int64)
+    w0 = (f[:, 0] & 1) != 0
+    w1 = ((f[:, 1] & 1) != 0) & ~w0
+    slot = torch.where(w0, 0, torch.where(w1, 1, 2))
+    inc = (fin & (score.sum(1) < quota)).to(score.dtype)
+    score.scatter_add_(1, slot[:, None], inc[:, None])
+
+
+# ---- match-ups -------------------------------------------------------------------------------------------------------------
+def play_matches(env, table, pairs, rounds_per_env, envs_per_pair, deterministic=False, seed=0, adjust_z=EVAL_ADJUST_Z, chunk=64,
+                 fused=True):
+    """Plays every match-up ``pairs[p] = (i, j)`` (snapshot i as agent 0 against snapshot j as agent 1 of ``table``) on
+    ``envs_per_pair`` envs, ``rounds_per_env`` finished episodes per env.  Pairs are played in batches of contiguous env blocks;
+    each batch resets the envs seeded (``seed`` + batch number * N + env) and runs ``chunk``-step launches until every env of the
+    batch has its quota.  ``adjust_z`` is imposed on every agent for the games and the env's value restored afterwards (None:
+    leave it).  Returns one dict per pair: wins, losses, draws, rounds (== envs_per_pair * rounds_per_env), env_steps."""
+    import torch
+    _check_env(env, table)
+    pairs = [(int(i), int(j)) for i, j in pairs]
+    for i, j in pairs:
+        if not (0 <= i < table.capacity and 0 <= j < table.capacity) or not (table.filled[i] and table.filled[j]):
+            raise ValueError("pair (%d, %d) refers to an empty or non-existent snapshot row" % (i, j))
+    rounds_per_env, envs_per_pair, chunk = int(rounds_per_env), int(envs_per_pair), int(chunk)
+    if rounds_per_env < 1 or chunk < 1:
+        raise ValueError("rounds_per_env and chunk must be >= 1")
+    N, A = env.num_envs, table.spec.ac_dim
+    batches = plan_batches(len(pairs), envs_per_pair, N)
+    max_launches = -(-rounds_per_env * (env.model.timestep_limit + 1) // chunk) + 1   # every episode ends by the time limit
+    gen = torch.Generator(device=env.device)
+    gen.manual_seed(int(seed))
+    out = [None] * len(pairs)
+    prev_adjust, prev_seeds = getattr(env, "adjust_z", 0.0), env.seeds.copy()
+    change_z = adjust_z is not None and float(adjust_z) != prev_adjust
+    if change_z:
+        env.set_adjust_z(adjust_z)
+    try:
+        for bn, batch in enumerate(batches):
+            idx0_h, idx1_h, active = env_assignment(pairs, batch, envs_per_pair, N)
+            idx0 = torch.from_numpy(idx0_h).to(env.device)
+            idx1 = torch.from_numpy(idx1_h).to(env.device)
+            act_t = torch.from_numpy(active).to(env.device)
+            score = torch.zeros((N, 3), dtype=torch.int32, device=env.device)
+            env.seeds = np.uint64(seed) + np.uint64(bn * N) + np.arange(N, dtype=np.uint64)
+            env._needs_seed = True
+            env.reset_device()
+            launches = 0
+            while True:
+                noise = None if deterministic else tuple(torch.randn((chunk, N, A), generator=gen, device=env.device) for _ in range(2))
+                if fused:
+                    match_steps_fused(env, table, idx0, idx1, score, rounds_per_env, chunk, noise)
+                else:
+                    match_steps_stepwise(env, table, idx0_h, idx1_h, score, rounds_per_env, chunk, noise)
+                launches += 1
+                if not bool((score.sum(1)[act_t] < rounds_per_env).any()):
+                    break
+                if launches >= max_launches:
+                    raise RuntimeError("matches did not finish within %d launches of %d steps" % (launches, chunk))
+            sc = score.cpu().numpy().astype(np.int64)
+            for b, p in enumerate(batch):
+                s = sc[b * envs_per_pair:(b + 1) * envs_per_pair].sum(0)
+                out[p] = dict(wins=int(s[0]), losses=int(s[1]), draws=int(s[2]), rounds=int(s.sum()),
+                              env_steps=launches * chunk * envs_per_pair)
+    finally:
+        env.seeds = prev_seeds
+        if change_z:
+            torch.cuda.synchronize(env.device)
+            env.set_adjust_z(prev_adjust)
+    return out
+
+
+def _make_env(env_id, num_env, seed, env):
+    if env is not None:
+        return env, False
+    from .vec_env import make_vec_env
+    return make_vec_env(env_id, num_env, seed), True
+
+
+def _spec_of(env):
+    return policies.PolicySpec(env.observation_space[0].shape[0], env.action_space[0].shape[0], value_network="copy", activation="relu")
+
+
+def compare_history_versions(path1, path2, trials, num_env=256, deterministic=False, seed=0, adjust_z=EVAL_ADJUST_Z,
+                             env_id="RoboSumo-Ant-vs-Ant-v0", chunk=64, env=None, fused=True):
+    """compare_history_version.py on the GPU: version i of run ``path1`` (agent 0) against version i of ``path2`` (agent 1),
+    ``trials`` games each.  Returns dict(versions=[(id1, id2)], win_rate=[P1 wins / trials], results=[play_matches dicts])."""
+    pv = pair_versions(list_checkpoints(path1), list_checkpoints(path2))
+    if not pv:
+        raise ValueError("no checkpoints to compare")
+    env, own = _make_env(env_id, num_env, seed, env)
+    try:
+        spec = _spec_of(env)
+        paths = [os.path.join(checkpoint_dir(path1), a) for a, _ in pv] + [os.path.join(checkpoint_dir(path2), b) for _, b in pv]
+        table = SnapshotTable.from_checkpoints(spec, paths, env.device)
+        n = len(pv)
+        epp, rpe = split_trials(trials, env.num_envs)
+        res = play_matches(env, table, [(k, n + k) for k in range(n)], rpe, epp, deterministic=deterministic, seed=seed,
+                           adjust_z=adjust_z, chunk=chunk, fused=fused)
+    finally:
+        if own:
+            env.close()
+    return dict(versions=pv, win_rate=[r["wins"] / float(trials) for r in res], results=res)
+
+
+def round_robin(path, interval, trials, num_env=256, deterministic=False, seed=0, adjust_z=EVAL_ADJUST_Z,
+                env_id="RoboSumo-Ant-vs-Ant-v0", chunk=64, env=None, fused=True):
+    """Every ``interval``-th version of one run (sorted, ``00000`` excluded) against every other, both seatings, ``trials``
+    games per ordered pair.  Returns dict(versions, win, draw, loss): [V][V] rates of version i as agent 0 against version j
+    as agent 1 (NaN on the diagonal), and results (play_matches dicts by (i, j))."""
+    interval = int(interval)
+    if interval < 1:
+        raise ValueError("interval must be >= 1")
+    ids = list_checkpoints(path)[::interval]
+    if len(ids) < 2:
+        raise ValueError("a round robin needs at least two versions (got %d)" % len(ids))
+    env, own = _make_env(env_id, num_env, seed, env)
+    try:
+        table = SnapshotTable.from_checkpoints(_spec_of(env), [os.path.join(checkpoint_dir(path), c) for c in ids], env.device)
+        V = len(ids)
+        pairs = [(i, j) for i in range(V) for j in range(V) if i != j]
+        epp, rpe = split_trials(trials, env.num_envs)
+        res = play_matches(env, table, pairs, rpe, epp, deterministic=deterministic, seed=seed, adjust_z=adjust_z, chunk=chunk,
+                           fused=fused)
+    finally:
+        if own:
+            env.close()
+    M = {k: np.full((V, V), np.nan) for k in ("win", "draw", "loss")}
+    for (i, j), r in zip(pairs, res):
+        M["win"][i, j], M["draw"][i, j], M["loss"][i, j] = r["wins"] / trials, r["draws"] / trials, r["losses"] / trials
+    return dict(versions=ids, results={p: r for p, r in zip(pairs, res)}, **M)

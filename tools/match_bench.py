@@ -1,0 +1,80 @@
+#!/usr/bin/env python3
+"""Throughput of checkpoint-vs-checkpoint matches: the fused match launch (sumo_match_steps) against the step-by-step path
+(ppo_forward for both sides of every match-up -- PPOModel.step's kernel -- plus step_device), same match-ups, same noise.
+
+    python tools/match_bench.py --num_env 4096 --pairs 16 --steps 256 --chunk 64
+
+Prints one JSON line: env-steps/s and finished matches per second of both paths (stochastic play, Ant-vs-Ant by default)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main(argv):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--env", default="RoboSumo-Ant-vs-Ant-v0")
+    ap.add_argument("--num_env", type=int, default=4096)
+    ap.add_argument("--pairs", type=int, default=16, help="match-ups; each gets a contiguous block of num_env / pairs envs")
+    ap.add_argument("--steps", type=int, default=256, help="timed env steps per path")
+    ap.add_argument("--chunk", type=int, default=64, help="steps per fused launch (and per counter read on both paths)")
+    ap.add_argument("--warmup", type=int, default=64)
+    ap.add_argument("--skip_stepwise", action="store_true")
+    args = ap.parse_args(argv)
+    import numpy as np
+    import torch
+    from robosumo_selfplay_amd import matches, policies
+    from robosumo_selfplay_amd.vec_env import SumoVecEnv
+    N, K = args.num_env, args.chunk
+    env = SumoVecEnv(args.env, num_envs=N, seed=0, adjust_z=-0.5)
+    spec = policies.PolicySpec(env.observation_space[0].shape[0], env.action_space[0].shape[0], value_network="copy", activation="relu")
+    nsnap = 2 * args.pairs
+    table = matches.SnapshotTable(spec, nsnap, env.device)
+    rng = np.random.default_rng(0)
+    for j in range(nsnap):
+        table.set(j, policies.flatten_params([p + 0.1 * rng.standard_normal(p.shape).astype(np.float32)
+                                              for p in policies.init_param_list(spec.ob_dim, spec.ac_dim)]))
+    epp = N // args.pairs
+    idx0_h, idx1_h, _ = matches.env_assignment([(2 * p, 2 * p + 1) for p in range(args.pairs)], list(range(args.pairs)), epp, N)
+    idx0, idx1 = torch.from_numpy(idx0_h).cuda(), torch.from_numpy(idx1_h).cuda()
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(0)
+    A = spec.ac_dim
+    noise = tuple(torch.randn((K, N, A), generator=gen, device="cuda") for _ in range(2))
+    out = dict(env=args.env, num_env=N, pairs=args.pairs, chunk=K)
+    quota = 1 << 30
+
+    def run(fused, steps):
+        score = torch.zeros((N, 3), dtype=torch.int32, device="cuda")
+        env._needs_seed = True
+        env.reset_device()
+        for _ in range(-(-args.warmup // K)):
+            (matches.match_steps_fused if fused else matches.match_steps_stepwise)(env, table, idx0 if fused else idx0_h,
+                                                                                     idx1 if fused else idx1_h, score, quota, K, noise)
+        score.zero_()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        n = 0
+        while n < steps:
+            (matches.match_steps_fused if fused else matches.match_steps_stepwise)(env, table, idx0 if fused else idx0_h,
+                                                                                     idx1 if fused else idx1_h, score, quota, K, noise)
+            score.sum().item()                    # the per-launch counter read of play_matches
+            n += K
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        return n * N / dt, int(score.sum().item()) / dt
+
+    out["fused_env_steps_per_s"], out["fused_matches_per_s"] = run(True, args.steps)
+    if not args.skip_stepwise:
+        out["stepwise_env_steps_per_s"], out["stepwise_matches_per_s"] = run(False, args.steps)
+        out["speedup"] = out["fused_env_steps_per_s"] / out["stepwise_env_steps_per_s"]
+    env.close()
+    print(json.dumps(out))
+    return out
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

@@ -7,7 +7,8 @@
     python compare_versions.py --path results/RoboSumo-Ant-vs-Ant-v0-0 --round_robin --interval 10 --trials 100
 
 Play is stochastic (model.step samples, as in the reference script) unless --deterministic is given; every agent reports its
-height with adjust_z = -0.5 (compare_history_version.py:73-74).
+height with adjust_z = -0.5 (compare_history_version.py:73-74).  MLP(64,64) and LSTM runs (learn(network='lstm')) are both
+accepted: the network is read from the checkpoints and recorded in the JSON output; both runs must use the same one.
 """
 import argparse
 import json
@@ -56,7 +57,8 @@ def main(argv):
                 if i != j:
                     print("-----%s vs %s win: %.2f, draw: %.2f, lose: %.2f-----" % (r["versions"][i], r["versions"][j], r["win"][i, j],
                                                                                   r["draw"][i, j], r["loss"][i, j]))
-        rec = dict(mode="round_robin", path=args.path, trials=args.trials, deterministic=args.deterministic, versions=r["versions"],
+        rec = dict(mode="round_robin", path=args.path, trials=args.trials, deterministic=args.deterministic, network=r["network"],
+                   nlstm=r["nlstm"], versions=r["versions"],
                    win=[[None if i == j else float(r["win"][i, j]) for j in range(V)] for i in range(V)],
                    draw=[[None if i == j else float(r["draw"][i, j]) for j in range(V)] for i in range(V)],
                    loss=[[None if i == j else float(r["loss"][i, j]) for j in range(V)] for i in range(V)])
@@ -67,7 +69,8 @@ def main(argv):
             print("-----P1 %s vs P2 %s: P1 win rate %.2f (%d wins, %d losses, %d draws)-----" % (a, b, w, res["wins"], res["losses"],
                                                                                              res["draws"]))
         rec = dict(mode="paired", p1=args.p1, p2=args.p2, trials=args.trials, deterministic=args.deterministic,
-                   versions=[list(v) for v in r["versions"]], win_rate=r["win_rate"], results=r["results"])
+                   network=r["network"], nlstm=r["nlstm"], versions=[list(v) for v in r["versions"]], win_rate=r["win_rate"],
+                   results=r["results"])
         out = args.out or os.path.join(args.p1, "compare_versions_vs_%s.json" % os.path.basename(os.path.normpath(args.p2)))
     with open(out, "w") as f:
         json.dump(rec, f, indent=1)

@@ -139,6 +139,29 @@ typedef struct sumo_match {
 } sumo_match;
 int sumo_match_steps(sumo_handle_t h, const sumo_match* m, float* actions_dev, float* obs_dev, double* info_dev, uint8_t* done_dev,
                      double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream);
+/* The same matches for RECURRENT checkpoints (LstmPPOModel.save, learn(network='lstm')): agent g in {0, 1} acts with net
+ * nets_dev[idx_g[e]] on (obs g, its own state state_g[e]), the state row zeroed first where agent g's done flag of the previous step
+ * is set -- LstmPPOModel.step(obs, S, M) on one row, bit for bit.  No value head is read.
+ *   proto      HOST struct: the dimensions / gate order every net of the table shares; checked as sumo_rollout_lstm's learner (hidden
+ *              128, gate order i,f,o,u, no embedding / observation filter, wx / wh / b / head_w / head_b / logstd present)
+ *   nets_dev   DEVICE array of nsnap ppo_lstm_net structs of that shape; idx0 / idx1 int32 [E] (DEVICE) select each env's nets -- an
+ *              index outside [0, nsnap) raises the launch's abort flag (sumo_rollout_status returns -20)
+ *   state0/state1  DEVICE float32 [E][256] (c | h) per agent, read at step s0 and left at the state after step s0 + K - 1 (the
+ *              caller zeroes them where a match-up starts)
+ *   noise0 / noise1, score, quota, T / s0 / K  as sumo_match (action = mean + exp(logstd) * noise, or the mean when both are NULL)
+ * Refused: whatever sumo_match_steps refuses, a proto sumo_rollout_steps_lstm would refuse, missing state buffers. */
+typedef struct sumo_match_lstm {
+  const ppo_lstm_net* proto;
+  const ppo_lstm_net* nets_dev;
+  const int32_t *idx0, *idx1;
+  int nsnap;
+  float *state0, *state1;
+  int T, s0, K, quota;
+  const float *noise0, *noise1;
+  int32_t* score;
+} sumo_match_lstm;
+int sumo_match_steps_lstm(sumo_handle_t h, const sumo_match_lstm* m, float* actions_dev, float* obs_dev, double* info_dev,
+                          uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream);
 /* cfrc_mode (reference agents.py:190-214 reads sim.data.cfrc_ext into 84 of the 121 observation entries):
  *   0 = zero (default): what the reference produces -- its MuJoCo 2.1 scenes declare no force / torque / accelerometer sensor, so
  *       mj_rnePostConstraint never runs and cfrc_ext stays at its reset value 0;

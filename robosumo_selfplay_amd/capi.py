@@ -48,6 +48,13 @@ class Match(C.Structure):
                 ("noise0", C.c_void_p), ("noise1", C.c_void_p), ("score", C.c_void_p)]
 
 
+class MatchLstm(C.Structure):
+    """``sumo_match_lstm`` of include/sumo_hip.h (``proto`` a host pointer to a ``ppo_capi.LstmNet``, the rest device pointers)."""
+    _fields_ = [("proto", C.c_void_p), ("nets_dev", C.c_void_p), ("idx0", C.c_void_p), ("idx1", C.c_void_p), ("nsnap", C.c_int),
+                ("state0", C.c_void_p), ("state1", C.c_void_p), ("T", C.c_int), ("s0", C.c_int), ("K", C.c_int), ("quota", C.c_int),
+                ("noise0", C.c_void_p), ("noise1", C.c_void_p), ("score", C.c_void_p)]
+
+
 def lib():
     global _LIB
     if _LIB is None:
@@ -66,6 +73,7 @@ def lib():
         L.sumo_rollout_steps.argtypes = [vp, C.POINTER(Rollout)] + [vp] * 8
         L.sumo_rollout_steps_lstm.argtypes = [vp, C.POINTER(RolloutLstm)] + [vp] * 8
         L.sumo_match_steps.argtypes = [vp, C.POINTER(Match)] + [vp] * 8
+        L.sumo_match_steps_lstm.argtypes = [vp, C.POINTER(MatchLstm)] + [vp] * 8
         L.sumo_get_state.argtypes = [vp] * 5
         L.sumo_set_cfrc_mode.argtypes = [vp, i32]
         L.sumo_get_cfrc_ext.argtypes = [vp, vp]
@@ -83,15 +91,15 @@ def lib():
         L.sumo_static_layout.argtypes = [vp]
         L.sumo_static_layout.restype = i32
         L.sumo_profile.restype = i32
-        for n in ("sumo_create", "sumo_destroy", "sumo_dims", "sumo_reset", "sumo_step", "sumo_rollout_steps", "sumo_rollout_steps_lstm", "sumo_match_steps", "sumo_get_state",
-                  "sumo_set_cfrc_mode", "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_set_state", "sumo_debug_forward", "sumo_stats"):
+        for n in ("sumo_create", "sumo_destroy", "sumo_dims", "sumo_reset", "sumo_step", "sumo_rollout_steps", "sumo_rollout_steps_lstm", "sumo_match_steps", "sumo_match_steps_lstm",
+                  "sumo_get_state", "sumo_set_cfrc_mode", "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_set_state", "sumo_debug_forward", "sumo_stats"):
             getattr(L, n).restype = i32
         _LIB = L
     return _LIB
 
 
 EXPORTS = ("sumo_last_error", "sumo_create", "sumo_destroy", "sumo_dims", "sumo_reset", "sumo_step", "sumo_rollout_steps",
-           "sumo_rollout_steps_lstm", "sumo_match_steps", "sumo_set_cfrc_mode", "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_get_state", "sumo_set_state", "sumo_debug_forward", "sumo_stats", "sumo_profile", "sumo_debug_trace",
+           "sumo_rollout_steps_lstm", "sumo_match_steps", "sumo_match_steps_lstm", "sumo_set_cfrc_mode", "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_get_state", "sumo_set_state", "sumo_debug_forward", "sumo_stats", "sumo_profile", "sumo_debug_trace",
            "sumo_rollout_status", "sumo_debug_fault", "sumo_static_layout", "sumo_debug_layout", "sumo_debug_model_ints", "sumo_debug_dump")
 
 
@@ -152,6 +160,10 @@ class Engine:
         """K fused checkpoint-vs-checkpoint match steps (``sumo_match_steps``); ``mo`` is a filled :class:`Match`.  The outcome is
         read with :meth:`rollout_status`."""
         _chk(lib().sumo_match_steps(self.h, C.byref(mo), actions_ptr, obs_ptr, info_ptr, done_ptr, ep_r_ptr, ep_dr_ptr, ep_l_ptr, stream))
+
+    def match_steps_lstm(self, mo, actions_ptr, obs_ptr, info_ptr, done_ptr, ep_r_ptr, ep_dr_ptr, ep_l_ptr, stream=None):
+        """The same for recurrent checkpoints (``sumo_match_steps_lstm``); ``mo`` is a filled :class:`MatchLstm`."""
+        _chk(lib().sumo_match_steps_lstm(self.h, C.byref(mo), actions_ptr, obs_ptr, info_ptr, done_ptr, ep_r_ptr, ep_dr_ptr, ep_l_ptr, stream))
 
     def set_cfrc_mode(self, mode):
         """'zero' (default, the reference's behaviour) or 'rne_post' (include/sumo_hip.h: cfrc_mode)."""

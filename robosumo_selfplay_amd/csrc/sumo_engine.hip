@@ -2792,6 +2792,82 @@ __device__ __forceinline__ void rollout_policy_phase_match(C& c, const SA& a, co
   wave_sync();   // the action buffer is read back by the env step (other lanes), the scratch region becomes the mass matrix again
 }
 
+// LSTM match policy phase (sumo_match_steps_lstm, POLICY 3): agent g in {0, 1} acts with net idx_g[e] of the device table onets on
+// (obs g, its own state st_g[e] masked by the previous step's done flag) -- LstmPPOModel.step on one row, the S / M feeds of
+// models.py:163-170.  One row per net: gate sums on the vector ALU in the MFMA tiles' order (lstm_gates_valu), cell update and
+// Gaussian head through the functions ppo_lstm_step_kernel uses, so every number equals that kernel bit for bit.  No value head,
+// no cross-scoring, nothing recorded; the new state crosses waves like the LSTM rollout's.  An index outside [0, nsnap) raises the
+// abort flag and plays net 0 instead.  LDS (floats, from lds_off): x [2][XS] | previous latent [NH] | new latent [NH].
+template <int NH, class C, class SA, class RA>
+__device__ __forceinline__ void rollout_policy_phase_match_lstm(C& c, const SA& a, const RA& r, int e, int s) {
+  const int lane = c.lane;
+  const int D = r.lnet.ob_dim, A = r.lnet.ac_dim, XS = r.XS;
+  float* xo = (float*)(c.sm + r.lds_off);
+  float* hp = xo + 2 * XS;
+  float* hn = hp + NH;
+  const float* ob = a.obs + (size_t)e * 2 * a.obs_stride;
+  for (int k = lane; k < XS; k += WAVE) {
+    float o0 = 0.0f, o1 = 0.0f;
+    if (k < D) { o0 = hand_load<true>(ob + k); o1 = hand_load<true>(ob + a.obs_stride + k); }
+    xo[k] = o0; xo[XS + k] = o1;
+  }
+  const unsigned dn = hand_load<true>((const uint16_t*)(a.done + 2 * e));   // done flags of the previous step = the masks M
+  int jn[2] = {pt_global(r.idx0)[e], pt_global(r.idx1)[e]};
+  if ((unsigned)jn[0] >= (unsigned)r.nsnap || (unsigned)jn[1] >= (unsigned)r.nsnap) {
+    if (lane == 0) __hip_atomic_store(pt_global(a.abort_flag), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    jn[0] = (unsigned)jn[0] < (unsigned)r.nsnap ? jn[0] : 0; jn[1] = (unsigned)jn[1] < (unsigned)r.nsnap ? jn[1] : 0;
+  }
+  const bool ok = lane < A;
+  const int j0 = 2 * lane;                           // lane owns the units 2 lane, 2 lane + 1
+  float act[2];
+#pragma unroll
+  for (int g = 0; g < 2; g++) {
+    const ppo_lstm_net PT_GAS* NT = pt_global(r.onets) + jn[g];
+    const float keep = 1.0f - (float)((dn >> (8 * g)) & 0xff);
+    float* sp = (g ? r.st1 : r.st0) + (size_t)e * 2 * NH;
+    float cp[2];
+    {
+      union { unsigned long long u; float f[2]; } q;
+      q.u = hand_load<true>((const unsigned long long*)(sp + j0)); cp[0] = q.f[0] * keep; cp[1] = q.f[1] * keep;
+      q.u = hand_load<true>((const unsigned long long*)(sp + NH + j0)); hp[j0] = q.f[0] * keep; hp[j0 + 1] = q.f[1] * keep;
+    }
+    const float PT_GAS* b_ = pt_global(NT->b);
+    const float fb = NT->forget_bias;
+    float z[4][2][1], bz[4][2];
+#pragma unroll
+    for (int q = 0; q < 4; q++) { bz[q][0] = b_[q * NH + j0]; bz[q][1] = b_[q * NH + j0 + 1]; }
+    wave_sync();
+    const float* const xr[1] = {xo + g * XS};
+    const float* const hr[1] = {hp};
+    lstm_gates_valu<NH, 1>(NT->wx, NT->wh, D, xr, hr, lane, z);
+#pragma unroll
+    for (int u = 0; u < 2; u++) {
+      const int j = j0 + u;
+      const LstmCell cl = lstm_cell(z[0][u][0], z[1][u][0], z[2][u][0], z[3][u][0], bz[0][u], bz[1][u] + fb, bz[2][u], bz[3][u], cp[u]);
+      hand_store<true>(sp + j, cl.cn); hand_store<true>(sp + NH + j, cl.hn);        // agent g's state after its step
+      hn[j] = cl.hn;
+    }
+    wave_sync();
+    float m[1];
+    lstm_heads_valu<NH, 1>(NT->head_w, NT->head_w, A, hn, lane, m);   // (lane 16's value sum reads head_w: the value head stays unread)
+    const float mean = m[0] + (ok ? pt_global(NT->head_b)[lane] : 0.0f);
+    act[g] = mean;
+    if (r.noise0) {
+      const float ls = ok ? pt_global(NT->logstd)[lane] : 0.0f;
+      const float nz = ok ? pt_global(g ? r.noise1 : r.noise0)[((size_t)s * a.N + e) * A + lane] : 0.0f;
+      (void)gauss_row(mean, expf(ls), 0.0f, ok, true, nz, act[g], A);
+    }
+    wave_sync();   // the latent rows are rewritten by the next side
+  }
+  if (ok) {
+    float* ae = const_cast<float*>(a.actions) + (size_t)e * 2 * a.act_stride;
+    hand_store<true>(ae + lane, act[0]); hand_store<true>(ae + a.act_stride + lane, act[1]);   // the env's action buffer (output only)
+    const auto& mdl = model_view(c);
+    S(ctrl)[MI(agent_uadr)[0] + lane] = (double)act[0]; S(ctrl)[MI(agent_uadr)[1] + lane] = (double)act[1];   // the step's control vector
+  }
+  wave_sync();
+}
+
 // Match post phase: where agent 0's episode ended in the step, score it from the step's winner flags (info[.][7] bit 0, just
 // written by this lane): a win if agent 0 carries the flag, a loss if only agent 1 does, a draw otherwise (timeouts, diverged states)
 // -- policy_zoo._evaluate_against's rule.  Counted while wins + losses + draws < quota.
@@ -2846,7 +2922,8 @@ struct RolloutLaunch { StepArgs a; RolloutArgs r; };
 #define ROLLOUT_SPIN_LIMIT (1u << 22)   /* polls of ~0.5 us each */
 
 template <int NV, int POLICY, int SL = 0>   // POLICY 0: MLP(64,64) policy / value nets; 1: LSTM(128) with shared value head; 2: MLP matches
-                                            // (sumo_match_steps: score counters instead of rollout buffers); SL 1: static Layout
+                                            // (sumo_match_steps: score counters instead of rollout buffers); 3: LSTM(128) matches
+                                            // (sumo_match_steps_lstm); SL 1: static Layout
 __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(SUMO_WPE_OF(NV), SUMO_WPE_OF(NV))))
 sumo_rollout_kernel(const Params* P, RolloutLaunch launch_args) {
   // `launch_args` is read in place from the kernel-argument segment (second argument, 8-byte aligned right behind P) through a
@@ -2901,6 +2978,7 @@ sumo_rollout_kernel(const Params* P, RolloutLaunch launch_args) {
 #endif
     if constexpr (POLICY == 1) rollout_policy_phase_lstm<128>(c, lp->a, lp->r, e, s);
     else if constexpr (POLICY == 2) rollout_policy_phase_match(c, lp->a, lp->r, e, s);
+    else if constexpr (POLICY == 3) rollout_policy_phase_match_lstm<128>(c, lp->a, lp->r, e, s);
     else rollout_policy_phase(c, lp->a, lp->r, e, s);
 #ifdef SUMO_DBG_HARD_BARRIER
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -2913,7 +2991,7 @@ sumo_rollout_kernel(const Params* P, RolloutLaunch launch_args) {
     asm volatile("" : "+s"(e), "+s"(k));
     lp = launder_sptr(LP);
     s = lp->r.s0 + k;
-    if constexpr (POLICY == 2) rollout_post_phase_match(c, lp->a, lp->r, e);
+    if constexpr (POLICY >= 2) rollout_post_phase_match(c, lp->a, lp->r, e);
     else rollout_post_phase(c, lp->a, lp->r, e, s);
     prof = lp->r.prof;
     if (prof && c.lane == 0) {
@@ -3743,14 +3821,17 @@ static int rollout_launch(sumo_engine* E, const RolloutArgs& r, int policy, floa
   if (E->static_layout == 1) {
     if (policy == 1) hipLaunchKernelGGL((sumo_rollout_kernel<28, 1, 1>), g_, b_, lds_, st_, E->d_params, rl);
     else if (policy == 2) hipLaunchKernelGGL((sumo_rollout_kernel<28, 2, 1>), g_, b_, lds_, st_, E->d_params, rl);
+    else if (policy == 3) hipLaunchKernelGGL((sumo_rollout_kernel<28, 3, 1>), g_, b_, lds_, st_, E->d_params, rl);
     else hipLaunchKernelGGL((sumo_rollout_kernel<28, 0, 1>), g_, b_, lds_, st_, E->d_params, rl);
   } else if (E->static_layout == 2) {
     if (policy == 1) hipLaunchKernelGGL((sumo_rollout_kernel<44, 1, 2>), g_, b_, lds_, st_, E->d_params, rl);
     else if (policy == 2) hipLaunchKernelGGL((sumo_rollout_kernel<44, 2, 2>), g_, b_, lds_, st_, E->d_params, rl);
+    else if (policy == 3) hipLaunchKernelGGL((sumo_rollout_kernel<44, 3, 2>), g_, b_, lds_, st_, E->d_params, rl);
     else hipLaunchKernelGGL((sumo_rollout_kernel<44, 0, 2>), g_, b_, lds_, st_, E->d_params, rl);
   } else if (!for_kernel_variant(E->hm.nv, [&](auto nvc_) {
         if (policy == 1) hipLaunchKernelGGL((sumo_rollout_kernel<decltype(nvc_)::value, 1>), g_, b_, lds_, st_, E->d_params, rl);
         else if (policy == 2) hipLaunchKernelGGL((sumo_rollout_kernel<decltype(nvc_)::value, 2>), g_, b_, lds_, st_, E->d_params, rl);
+        else if (policy == 3) hipLaunchKernelGGL((sumo_rollout_kernel<decltype(nvc_)::value, 3>), g_, b_, lds_, st_, E->d_params, rl);
         else hipLaunchKernelGGL((sumo_rollout_kernel<decltype(nvc_)::value, 0>), g_, b_, lds_, st_, E->d_params, rl);
       }))
     FAIL(-19, "no kernel variant for nv=%d", E->hm.nv);
@@ -3849,6 +3930,36 @@ extern "C" int sumo_match_steps(sumo_handle_t E, const sumo_match* mo, float* ac
   if ((size_t)(2 * r.XS + 4 * PT_HS) * sizeof(float) > (size_t)E->L.msize * sizeof(double))
     FAIL(-8, "policy scratch (%zu B) does not fit the mass-matrix region (%zu B)", (size_t)(2 * r.XS + 4 * PT_HS) * sizeof(float), (size_t)E->L.msize * sizeof(double));
   return rollout_launch(E, r, 2, actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev, stream);
+}
+
+extern "C" int sumo_match_steps_lstm(sumo_handle_t E, const sumo_match_lstm* mo, float* actions_dev, float* obs_dev, double* info_dev,
+                                     uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
+  if (!E || !mo || !actions_dev || !obs_dev || !info_dev || !done_dev || !ep_r_dev || !ep_dr_dev || !ep_l_dev) FAIL(-1, "bad arguments");
+  if (!mo->proto || !mo->nets_dev || !mo->idx0 || !mo->idx1 || !mo->score) FAIL(-2, "sumo_match_lstm: missing buffer");
+  if (!mo->state0 || !mo->state1) FAIL(-2, "sumo_match_lstm: missing state buffer (state0 / state1)");
+  if (!mo->noise0 != !mo->noise1) FAIL(-2, "sumo_match_lstm: noise0 and noise1 are both given (stochastic play) or both NULL (deterministic)");
+  int od = 0, ad = 0;
+  if (int rc = rollout_scene(E, mo->T, E->N, 0, mo->s0, mo->K, &od, &ad)) return rc;
+  const ppo_lstm_net& n = *mo->proto;
+  if (n.ob_dim != od || n.ac_dim != ad || n.ac_dim > PT_MAXA) FAIL(-4, "ob_dim %d / ac_dim %d do not match the scene (%d / %d)", n.ob_dim, n.ac_dim, od, ad);
+  // the nets sumo_rollout_steps_lstm plays (what `learn(network='lstm')` trains)
+  if (n.hidden != 128 || n.gate_order != PPO_LSTM_GATES_IFOU || n.emb_w || n.emb_dim != 0 || n.obs_mean || n.obs_invstd)
+    FAIL(-9, "fused recurrent matches: hidden 128, gate order i,f,o,u, no embedding, no observation filter (got hidden %d, order %d, emb %d)", n.hidden, n.gate_order, n.emb_dim);
+  if (!n.wx || !n.wh || !n.b || !n.head_w || !n.head_b || !n.logstd) FAIL(-10, "prototype net: missing weights");
+  if (mo->nsnap < 1) FAIL(-7, "nsnap %d: the snapshot table needs at least one entry", mo->nsnap);
+  if (mo->quota < 0) FAIL(-9, "quota %d", mo->quota);
+  HIPCHK(hipSetDevice(E->device));
+  RolloutArgs r;
+  memset(&r, 0, sizeof r);
+  r.lnet = n; r.onets = mo->nets_dev; r.st0 = mo->state0; r.st1 = mo->state1;
+  r.idx0 = mo->idx0; r.idx1 = mo->idx1; r.score = mo->score; r.nsnap = mo->nsnap; r.quota = mo->quota;
+  r.noise0 = mo->noise0; r.noise1 = mo->noise1;
+  r.T = mo->T; r.Ntot = E->N; r.s0 = mo->s0; r.K = mo->K;
+  r.XS = (od + 3) & ~3;
+  r.lds_off = (E->L.M + 1) & ~1;   // where the LSTM rollout's rows go (see sumo_rollout_steps_lstm)
+  const size_t need = (size_t)(2 * r.XS + 2 * 128) * sizeof(float), have = (size_t)(E->L.i_base - r.lds_off) * sizeof(double);
+  if (E->L.ctrl >= E->L.M || E->L.stash >= E->L.M || need > have) FAIL(-8, "policy scratch (%zu B) does not fit the per-step LDS area (%zu B)", need, have);
+  return rollout_launch(E, r, 3, actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev, stream);
 }
 
 #ifdef SUMO_POLICY_PROBE

@@ -12,8 +12,15 @@ tensor once per launch.
 An episode is a win if agent 0 carries the 'winner' flag when it ends, a loss if only agent 1 does, a draw otherwise
 (compare_history_version.py:33-41; policy_zoo._evaluate_against).  ``fused=False`` plays the same games step by step: two
 ``ppo_forward`` launches (what ``PPOModel.step`` runs) per match-up and side, then ``step_device``; with the same seed it draws
-the same noise and yields bit-identical envs and scores.  Recurrent (LSTM) checkpoints are refused.
+the same noise and yields bit-identical envs and scores.
+
+Recurrent checkpoints (``LstmPPOModel.save``, ``learn(network='lstm')``) go into an :class:`LstmSnapshotTable` instead: the
+same drivers detect the kind from the checkpoint files (:func:`checkpoint_kind`), and each side carries its own recurrent state
+per env, zeroed where a batch starts and masked by that side's done flag of the previous step (``LstmPPOModel.step(obs, S, M)``).
+The fused path is ``sumo_match_steps_lstm`` (LSTM(128)); ``fused=False`` makes one ``ppo_lstm_step`` launch per side and run of
+envs sharing a snapshot, bit-identical again.  MLP-vs-LSTM match-ups are refused.
 """
+import ctypes as C
 import os
 import warnings
 
@@ -32,7 +39,7 @@ def param_count(ob_dim, ac_dim):
 def snapshot_vector(spec, src):
     """Flat float32 parameter vector (numpy) of an MLP(64,64) policy of ``spec`` from a ``PPOModel`` / ``ActorCriticModel``, a
     flat vector, the 13-array list of a checkpoint (model.py:153-177) or a checkpoint path written by ``PPOModel.save``.
-    LSTM models and checkpoints are refused (recurrent matches are not supported)."""
+    LSTM models and checkpoints are refused here: they play in an :class:`LstmSnapshotTable`."""
     D, A = spec.ob_dim, spec.ac_dim
     label = None
     if getattr(src, "recurrent", False):
@@ -87,6 +94,112 @@ class SnapshotTable(object):
         if not 0 <= k < self.capacity:
             raise IndexError("row %d outside the table of %d" % (k, self.capacity))
         v = snapshot_vector(self.spec, src)
+        self.params[k].copy_(torch.from_numpy(v).to(self.device))
+        self.filled[k] = True
+        self.labels[k] = label if label is not None else (str(src) if isinstance(src, (str, os.PathLike)) else None)
+
+    @classmethod
+    def from_checkpoints(cls, spec, paths, device=0):
+        t = cls(spec, len(paths), device)
+        for k, p in enumerate(paths):
+            t.set(k, p)
+        return t
+
+
+def checkpoint_kind(path):
+    """('mlp', None) for a checkpoint written by ``PPOModel.save`` (the 13 arrays of MLP(64,64)), ('lstm', nlstm) for one written by
+    ``LstmPPOModel.save`` (the 8 arrays of ``lstm_param_shapes``), read from the array shapes."""
+    import joblib
+    plist = joblib.load(os.path.expanduser(str(path)))            # only files written by PPOModel.save() / LstmPPOModel.save()
+    return _list_kind(plist, str(path))
+
+
+def _list_kind(plist, label):
+    if isinstance(plist, (list, tuple)):
+        sh = [tuple(np.shape(p)) for p in plist]
+        if len(sh) == 13 and len(sh[0]) == 2:
+            D, A = sh[0][0], sh[8][1] if len(sh[8]) == 2 else -1
+            if sh == [tuple(x) for x in policies.param_shapes(D, A)]:
+                return "mlp", None
+        if len(sh) == 8 and len(sh[0]) == 2 and len(sh[3]) == 2:
+            D, H, A = sh[0][0], sh[3][0], sh[3][1]
+            if sh == [tuple(x) for x in policies.lstm_param_shapes(D, A, H)]:
+                return "lstm", H
+    raise ValueError("%s is neither an MLP(64,64) nor an LSTM checkpoint" % label)
+
+
+def lstm_snapshot_vector(spec, src):
+    """Flat float32 parameter vector (numpy) of an LSTM policy of ``spec`` (``LstmSpec``) from an ``LstmPPOModel``, a flat vector,
+    the 8-array list of ``lstm_param_shapes`` or a checkpoint path written by ``LstmPPOModel.save``.  MLP models and checkpoints,
+    and LSTM policies of another width, are refused."""
+    D, A, H = spec.ob_dim, spec.ac_dim, spec.nlstm
+    label = None
+    if isinstance(src, (str, os.PathLike)):
+        import joblib
+        label = str(src)
+        src = joblib.load(os.path.expanduser(str(src)))            # only files written by LstmPPOModel.save()
+    if hasattr(src, "params") and hasattr(src, "spec"):            # LstmPPOModel (or an MLP model: refused)
+        if not getattr(src, "recurrent", False):
+            raise ValueError("MLP models cannot play in an LSTM snapshot table: use SnapshotTable")
+        got = (src.spec.ob_dim, src.spec.ac_dim, src.spec.nlstm)
+        if got != (D, A, H):
+            raise ValueError("model's policy (%d, %d, LSTM(%d)) does not match the table's (%d, %d, LSTM(%d))" % (got + (D, A, H)))
+        return src.params.detach().cpu().numpy().astype(np.float32).reshape(-1)
+    if hasattr(src, "detach"):                                     # torch tensor
+        src = src.detach().cpu().numpy()
+    if isinstance(src, dict):
+        raise ValueError("dict checkpoints are not supported here; load them into an LstmPPOModel first")
+    if isinstance(src, (list, tuple)):
+        name = label or "checkpoint"
+        try:
+            kind, h = _list_kind(src, name)
+        except ValueError:
+            kind, h = None, None
+        if kind == "mlp":
+            raise ValueError("%s is an MLP(64,64) checkpoint: it plays in a SnapshotTable, not in an LSTM table" % name)
+        if kind == "lstm" and h != H:
+            raise ValueError("%s is an LSTM(%d) checkpoint, the table holds LSTM(%d) policies" % (name, h, H))
+        shapes = [tuple(x) for x in policies.lstm_param_shapes(D, A, H)]
+        if [tuple(np.shape(p)) for p in src] != shapes:
+            raise ValueError("%s does not match the LSTM(%d) policy of ob_dim %d / ac_dim %d" % (name, H, D, A))
+        return np.concatenate([np.asarray(p, np.float32).ravel() for p in src])
+    v = np.ascontiguousarray(src, np.float32).reshape(-1)
+    P = sum(int(np.prod(x)) for x in policies.lstm_param_shapes(D, A, H))
+    if v.size != P:
+        raise ValueError("snapshot has %d parameters, the LSTM policy %d" % (v.size, P))
+    return v
+
+
+class LstmSnapshotTable(object):
+    """Device table ``params [capacity][P]`` of frozen LSTM policies (``lstm_param_shapes`` order, what ``LstmPPOModel.save``
+    writes) plus the device array of their ``ppo_lstm_net`` structs (``nets_dev``) and a host prototype (``proto``)."""
+    recurrent = True
+
+    def __init__(self, spec, capacity, device=0):
+        import torch
+        from . import ppo_capi
+        from .opponent_pool import fill_lstm_net
+        self.spec = spec
+        self.capacity = int(capacity)
+        if self.capacity < 1:
+            raise ValueError("capacity must be >= 1")
+        self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        self.P = sum(int(np.prod(x)) for x in policies.lstm_param_shapes(spec.ob_dim, spec.ac_dim, spec.nlstm))
+        self.params = torch.zeros((self.capacity, self.P), dtype=torch.float32, device=self.device)
+        self.nets = (ppo_capi.LstmNet * self.capacity)()
+        for k in range(self.capacity):
+            fill_lstm_net(self.nets[k], self.params[k].data_ptr(), spec)
+        self.proto = fill_lstm_net(ppo_capi.LstmNet(), self.params[0].data_ptr(), spec)
+        self.nets_dev = torch.from_numpy(np.frombuffer(bytes(self.nets), dtype=np.uint8).copy()).to(self.device)
+        self.filled = np.zeros(self.capacity, bool)
+        self.labels = [None] * self.capacity
+
+    def set(self, k, src, label=None):
+        """Fill row ``k`` (see :func:`lstm_snapshot_vector` for what ``src`` may be)."""
+        import torch
+        if not 0 <= k < self.capacity:
+            raise IndexError("row %d outside the table of %d" % (k, self.capacity))
+        v = lstm_snapshot_vector(self.spec, src)
         self.params[k].copy_(torch.from_numpy(v).to(self.device))
         self.filled[k] = True
         self.labels[k] = label if label is not None else (str(src) if isinstance(src, (str, os.PathLike)) else None)
@@ -229,6 +342,76 @@ def match_steps_stepwise(env, table, idx0, idx1, score, quota, K, noise=None):
         _score_step(score, info, done, quota)
 
 
+def _check_lstm(table, states, N):
+    H = table.spec.nlstm
+    for st in states:
+        if tuple(st.shape) != (N, 2 * H) or not st.is_contiguous():
+            raise ValueError("recurrent states must be two contiguous float32 [%d][%d] tensors (c | h)" % (N, 2 * H))
+
+
+def match_steps_fused_lstm(env, table, idx0, idx1, states, score, quota, K, noise=None):
+    """:func:`match_steps_fused` for an :class:`LstmSnapshotTable`: one ``sumo_match_steps_lstm`` launch per env group.  ``states``
+    is a pair of float32 CUDA [N][2 nlstm] tensors (c | h) per agent, read and updated in place.  LSTM(128) only."""
+    from . import capi
+    _check_env(env, table)
+    _check_lstm(table, states, env.num_envs)
+    if table.spec.nlstm != 128:
+        raise ValueError("the fused match launch plays LSTM(128) policies only (got LSTM(%d)): use fused=False" % table.spec.nlstm)
+    for g in range(env.groups):
+        sl = env._gs(g)
+        mo = capi.MatchLstm()
+        mo.proto = C.addressof(table.proto)
+        mo.nets_dev = table.nets_dev.data_ptr()
+        mo.idx0, mo.idx1 = idx0[sl].data_ptr(), idx1[sl].data_ptr()
+        mo.nsnap = table.capacity
+        mo.state0, mo.state1 = states[0][sl].data_ptr(), states[1][sl].data_ptr()
+        mo.T, mo.s0, mo.K, mo.quota = int(K), 0, int(K), int(quota)
+        keep = None
+        if noise is not None:
+            keep = [n[:, sl].contiguous() if env.groups > 1 else n for n in noise]
+            mo.noise0, mo.noise1 = keep[0].data_ptr(), keep[1].data_ptr()
+        mo.score = score[sl].data_ptr()
+        E = env.engines[g]
+        E.match_steps_lstm(mo, env.act_dev[sl].data_ptr(), env.obs_dev[sl].data_ptr(), env.info_dev[sl].data_ptr(),
+                           env.done_dev[sl].data_ptr(), env.ep_r_dev[sl].data_ptr(), env.ep_dr_dev[sl].data_ptr(),
+                           env.ep_l_dev[sl].data_ptr(), stream=env._stream())
+        E.rollout_status()
+        del keep
+
+
+def match_steps_stepwise_lstm(env, table, idx0, idx1, states, score, quota, K, noise=None):
+    """The same K steps of an :class:`LstmSnapshotTable` step by step: per step and side one ``ppo_lstm_step`` launch (the kernel
+    ``LstmPPOModel.step`` runs) for every run of envs that share a snapshot, masked by that side's done flags of the previous step,
+    then ``step_device`` and the score update.  idx0 / idx1 are host arrays; any LSTM width the step kernel is built for."""
+    import torch
+    from . import ppo_capi
+    _check_env(env, table)
+    _check_lstm(table, states, env.num_envs)
+    idx0, idx1 = np.asarray(idx0, np.int64), np.asarray(idx1, np.int64)
+    if min(idx0.min(), idx1.min()) < 0 or max(idx0.max(), idx1.max()) >= table.capacity:
+        raise ValueError("snapshot index outside [0, %d)" % table.capacity)
+    A, H = table.spec.ac_dim, table.spec.nlstm
+    N = env.num_envs
+    L = ppo_capi.lib()
+    st = env._stream()
+    acts = env.act_dev
+    act = [torch.empty((N, A), dtype=torch.float32, device=env.device) for _ in range(2)]
+    runs = [_runs(idx0), _runs(idx1)]
+    obs = env.obs_dev
+    for t in range(int(K)):
+        masks = [env.done_dev[:, side].to(torch.float32) for side in range(2)]   # done flags of the previous step = the masks M
+        for side in range(2):
+            S = states[side]
+            for s, e, k in runs[side]:
+                nz = None if noise is None else noise[side][t, s:e]
+                ppo_capi.chk(L.ppo_lstm_step(C.byref(table.nets[k]), obs[s:e, side].data_ptr(), e - s, obs.stride(0), masks[side][s:e].data_ptr(),
+                                             S[s:e].data_ptr(), S[s:e].data_ptr() + 4 * H, 2 * H, ppo_capi.ptr(nz), None,
+                                             act[side][s:e].data_ptr(), None, None, None, st))
+            acts[:, side, :A] = act[side]
+        obs, info, done, _, _, _ = env.step_device(acts)
+        _score_step(score, info, done, quota)
+
+
 def _score_step(score, info, done, quota):
     import torch
     fin = done[:, 0] != 0
@@ -243,10 +426,11 @@ def _score_step(score, info, done, quota):
 # ---- match-ups -------------------------------------------------------------------------------------------------------------
 def play_matches(env, table, pairs, rounds_per_env, envs_per_pair, deterministic=False, seed=0, adjust_z=EVAL_ADJUST_Z, chunk=64,
                  fused=True):
-    """Plays every match-up ``pairs[p] = (i, j)`` (snapshot i as agent 0 against snapshot j as agent 1 of ``table``) on
-    ``envs_per_pair`` envs, ``rounds_per_env`` finished episodes per env.  Pairs are played in batches of contiguous env blocks;
-    each batch resets the envs seeded (``seed`` + batch number * N + env) and runs ``chunk``-step launches until every env of the
-    batch has its quota.  ``adjust_z`` is imposed on every agent for the games and the env's value restored afterwards (None:
+    """Plays every match-up ``pairs[p] = (i, j)`` (snapshot i as agent 0 against snapshot j as agent 1 of ``table``, a
+    :class:`SnapshotTable` or an :class:`LstmSnapshotTable`) on ``envs_per_pair`` envs, ``rounds_per_env`` finished episodes per
+    env.  Pairs are played in batches of contiguous env blocks; each batch resets the envs seeded (``seed`` + batch number * N +
+    env), zeroes both sides' recurrent states (LSTM tables) and runs ``chunk``-step launches until every env of the batch has its
+    quota.  ``adjust_z`` is imposed on every agent for the games and the env's value restored afterwards (None:
     leave it).  Returns one dict per pair: wins, losses, draws, rounds (== envs_per_pair * rounds_per_env), env_steps."""
     import torch
     _check_env(env, table)
@@ -258,6 +442,9 @@ def play_matches(env, table, pairs, rounds_per_env, envs_per_pair, deterministic
     if rounds_per_env < 1 or chunk < 1:
         raise ValueError("rounds_per_env and chunk must be >= 1")
     N, A = env.num_envs, table.spec.ac_dim
+    recurrent = bool(getattr(table, "recurrent", False))
+    if recurrent and fused and table.spec.nlstm != 128:
+        raise ValueError("the fused match launch plays LSTM(128) policies only (got LSTM(%d)): use fused=False" % table.spec.nlstm)
     batches = plan_batches(len(pairs), envs_per_pair, N)
     max_launches = -(-rounds_per_env * (env.model.timestep_limit + 1) // chunk) + 1   # every episode ends by the time limit
     gen = torch.Generator(device=env.device)
@@ -277,10 +464,16 @@ def play_matches(env, table, pairs, rounds_per_env, envs_per_pair, deterministic
             env.seeds = np.uint64(seed) + np.uint64(bn * N) + np.arange(N, dtype=np.uint64)
             env._needs_seed = True
             env.reset_device()
+            if recurrent:                     # every match-up starts from the zero state (LstmPPOModel.initial_state)
+                states = tuple(torch.zeros((N, 2 * table.spec.nlstm), dtype=torch.float32, device=env.device) for _ in range(2))
             launches = 0
             while True:
                 noise = None if deterministic else tuple(torch.randn((chunk, N, A), generator=gen, device=env.device) for _ in range(2))
-                if fused:
+                if recurrent and fused:
+                    match_steps_fused_lstm(env, table, idx0, idx1, states, score, rounds_per_env, chunk, noise)
+                elif recurrent:
+                    match_steps_stepwise_lstm(env, table, idx0_h, idx1_h, states, score, rounds_per_env, chunk, noise)
+                elif fused:
                     match_steps_fused(env, table, idx0, idx1, score, rounds_per_env, chunk, noise)
                 else:
                     match_steps_stepwise(env, table, idx0_h, idx1_h, score, rounds_per_env, chunk, noise)
@@ -313,18 +506,40 @@ def _spec_of(env):
     return policies.PolicySpec(env.observation_space[0].shape[0], env.action_space[0].shape[0], value_network="copy", activation="relu")
 
 
+def _kind_name(kind):
+    return "MLP(64,64)" if kind[0] == "mlp" else "LSTM(%d)" % kind[1]
+
+
+def _table_of(kind, env, paths):
+    """The snapshot table of a checkpoint kind (:func:`checkpoint_kind`) filled from ``paths``."""
+    if kind[0] == "lstm":
+        from .lstm_model import LstmSpec
+        spec = LstmSpec(env.observation_space[0].shape[0], env.action_space[0].shape[0], kind[1])
+        return LstmSnapshotTable.from_checkpoints(spec, paths, env.device)
+    return SnapshotTable.from_checkpoints(_spec_of(env), paths, env.device)
+
+
+def _network(kind):
+    return dict(network=kind[0], nlstm=kind[1])
+
+
 def compare_history_versions(path1, path2, trials, num_env=256, deterministic=False, seed=0, adjust_z=EVAL_ADJUST_Z,
                              env_id="RoboSumo-Ant-vs-Ant-v0", chunk=64, env=None, fused=True):
     """compare_history_version.py on the GPU: version i of run ``path1`` (agent 0) against version i of ``path2`` (agent 1),
-    ``trials`` games each.  Returns dict(versions=[(id1, id2)], win_rate=[P1 wins / trials], results=[play_matches dicts])."""
+    ``trials`` games each.  MLP and LSTM runs are told apart by their first checkpoint; both runs must hold the same kind.
+    Returns dict(versions=[(id1, id2)], win_rate=[P1 wins / trials], results=[play_matches dicts], network='mlp' | 'lstm',
+    nlstm=LSTM width or None)."""
     pv = pair_versions(list_checkpoints(path1), list_checkpoints(path2))
     if not pv:
         raise ValueError("no checkpoints to compare")
+    paths = [os.path.join(checkpoint_dir(path1), a) for a, _ in pv] + [os.path.join(checkpoint_dir(path2), b) for _, b in pv]
+    k1, k2 = checkpoint_kind(paths[0]), checkpoint_kind(paths[len(pv)])
+    if k1 != k2:
+        raise ValueError("P1 holds %s checkpoints and P2 %s checkpoints: both runs must use the same network (MLP-vs-LSTM and "
+                         "mixed LSTM widths are not supported)" % (_kind_name(k1), _kind_name(k2)))
     env, own = _make_env(env_id, num_env, seed, env)
     try:
-        spec = _spec_of(env)
-        paths = [os.path.join(checkpoint_dir(path1), a) for a, _ in pv] + [os.path.join(checkpoint_dir(path2), b) for _, b in pv]
-        table = SnapshotTable.from_checkpoints(spec, paths, env.device)
+        table = _table_of(k1, env, paths)
         n = len(pv)
         epp, rpe = split_trials(trials, env.num_envs)
         res = play_matches(env, table, [(k, n + k) for k in range(n)], rpe, epp, deterministic=deterministic, seed=seed,
@@ -332,23 +547,26 @@ def compare_history_versions(path1, path2, trials, num_env=256, deterministic=Fa
     finally:
         if own:
             env.close()
-    return dict(versions=pv, win_rate=[r["wins"] / float(trials) for r in res], results=res)
+    return dict(versions=pv, win_rate=[r["wins"] / float(trials) for r in res], results=res, **_network(k1))
 
 
 def round_robin(path, interval, trials, num_env=256, deterministic=False, seed=0, adjust_z=EVAL_ADJUST_Z,
                 env_id="RoboSumo-Ant-vs-Ant-v0", chunk=64, env=None, fused=True):
     """Every ``interval``-th version of one run (sorted, ``00000`` excluded) against every other, both seatings, ``trials``
     games per ordered pair.  Returns dict(versions, win, draw, loss): [V][V] rates of version i as agent 0 against version j
-    as agent 1 (NaN on the diagonal), and results (play_matches dicts by (i, j))."""
+    as agent 1 (NaN on the diagonal), results (play_matches dicts by (i, j)) and network / nlstm as
+    :func:`compare_history_versions`."""
     interval = int(interval)
     if interval < 1:
         raise ValueError("interval must be >= 1")
     ids = list_checkpoints(path)[::interval]
     if len(ids) < 2:
         raise ValueError("a round robin needs at least two versions (got %d)" % len(ids))
+    paths = [os.path.join(checkpoint_dir(path), c) for c in ids]
+    kind = checkpoint_kind(paths[0])
     env, own = _make_env(env_id, num_env, seed, env)
     try:
-        table = SnapshotTable.from_checkpoints(_spec_of(env), [os.path.join(checkpoint_dir(path), c) for c in ids], env.device)
+        table = _table_of(kind, env, paths)
         V = len(ids)
         pairs = [(i, j) for i in range(V) for j in range(V) if i != j]
         epp, rpe = split_trials(trials, env.num_envs)
@@ -360,4 +578,4 @@ def round_robin(path, interval, trials, num_env=256, deterministic=False, seed=0
     M = {k: np.full((V, V), np.nan) for k in ("win", "draw", "loss")}
     for (i, j), r in zip(pairs, res):
         M["win"][i, j], M["draw"][i, j], M["loss"][i, j] = r["wins"] / trials, r["draws"] / trials, r["losses"] / trials
-    return dict(versions=ids, results={p: r for p, r in zip(pairs, res)}, **M)
+    return dict(versions=ids, results={p: r for p, r in zip(pairs, res)}, **M, **_network(kind))

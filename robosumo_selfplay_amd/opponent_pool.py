@@ -12,6 +12,20 @@ import numpy as np
 from . import policies
 
 
+def fill_lstm_net(n, base, spec):
+    """Fill the ``ppo_capi.LstmNet`` ``n`` for the flat parameter vector of an ``lstm_param_shapes`` policy of ``spec`` (ob_dim,
+    ac_dim, nlstm) at device address ``base``: gate order i,f,o,u, no forget-bias offset, no embedding / observation filter --
+    the nets ``learn(network='lstm')`` trains."""
+    from . import ppo_capi
+    D, A, H = spec.ob_dim, spec.ac_dim, spec.nlstm
+    o = np.concatenate([[0], np.cumsum([int(np.prod(s)) for s in policies.lstm_param_shapes(D, A, H)])]) * 4
+    n.ob_dim, n.emb_dim, n.hidden, n.ac_dim = D, 0, H, A
+    n.gate_order, n.forget_bias = ppo_capi.LSTM_GATES_IFOU, 0.0
+    n.wx, n.wh, n.b = base + int(o[0]), base + int(o[1]), base + int(o[2])
+    n.head_w, n.head_b, n.logstd, n.vf_w, n.vf_b = base + int(o[3]), base + int(o[4]), base + int(o[5]), base + int(o[6]), base + int(o[7])
+    return n
+
+
 class OpponentPool(object):
     def __init__(self, spec, capacity, num_envs, device):
         import torch
@@ -93,9 +107,8 @@ class LstmOpponentPool(object):
         self.params = torch.zeros((self.capacity, self.P), dtype=torch.float32, device=device)
         nets = (ppo_capi.LstmNet * self.capacity)()
         for k in range(self.capacity):
-            self._fill_net(nets[k], self.params[k].data_ptr())
-        self._proto = ppo_capi.LstmNet()
-        self._fill_net(self._proto, self.params[0].data_ptr())
+            fill_lstm_net(nets[k], self.params[k].data_ptr(), spec)
+        self._proto = fill_lstm_net(ppo_capi.LstmNet(), self.params[0].data_ptr(), spec)
         self._nets_dev = torch.from_numpy(np.frombuffer(bytes(nets), dtype=np.uint8).copy()).to(device)
         self.tile_net = torch.zeros(self.num_envs // 16, dtype=torch.int32, device=device)
         self.filled = np.zeros(self.capacity, bool)
@@ -103,14 +116,6 @@ class LstmOpponentPool(object):
         self.gen = torch.Generator(device=device)
         self.act_model = self.train_model = self
         self.initial_state = np.zeros((self.num_envs, 2 * H), np.float32)            # models.py:176
-
-    def _fill_net(self, n, base):
-        D, A, H = self.spec.ob_dim, self.spec.ac_dim, self.spec.nlstm
-        o = np.concatenate([[0], np.cumsum(self.sizes)]) * 4
-        n.ob_dim, n.emb_dim, n.hidden, n.ac_dim = D, 0, H, A
-        n.gate_order, n.forget_bias = self._capi.LSTM_GATES_IFOU, 0.0
-        n.wx, n.wh, n.b = base + int(o[0]), base + int(o[1]), base + int(o[2])
-        n.head_w, n.head_b, n.logstd, n.vf_w, n.vf_b = base + int(o[3]), base + int(o[4]), base + int(o[5]), base + int(o[6]), base + int(o[7])
 
     @property
     def index(self):

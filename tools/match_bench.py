@@ -3,6 +3,7 @@
 (ppo_forward for both sides of every match-up -- PPOModel.step's kernel -- plus step_device), same match-ups, same noise.
 
     python tools/match_bench.py --num_env 4096 --pairs 16 --steps 256 --chunk 64
+    python tools/match_bench.py --network lstm     # LSTM(128) checkpoints: sumo_match_steps_lstm against ppo_lstm_step per side
 
 Prints one JSON line: env-steps/s and finished matches per second of both paths (stochastic play, Ant-vs-Ant by default)."""
 import argparse
@@ -23,6 +24,7 @@ def main(argv):
     ap.add_argument("--chunk", type=int, default=64, help="steps per fused launch (and per counter read on both paths)")
     ap.add_argument("--warmup", type=int, default=64)
     ap.add_argument("--skip_stepwise", action="store_true")
+    ap.add_argument("--network", choices=("mlp", "lstm"), default="mlp", help="MLP(64,64) or LSTM(128) snapshots")
     args = ap.parse_args(argv)
     import numpy as np
     import torch
@@ -30,37 +32,51 @@ def main(argv):
     from robosumo_selfplay_amd.vec_env import SumoVecEnv
     N, K = args.num_env, args.chunk
     env = SumoVecEnv(args.env, num_envs=N, seed=0, adjust_z=-0.5)
-    spec = policies.PolicySpec(env.observation_space[0].shape[0], env.action_space[0].shape[0], value_network="copy", activation="relu")
+    D, A = env.observation_space[0].shape[0], env.action_space[0].shape[0]
     nsnap = 2 * args.pairs
-    table = matches.SnapshotTable(spec, nsnap, env.device)
     rng = np.random.default_rng(0)
-    for j in range(nsnap):
-        table.set(j, policies.flatten_params([p + 0.1 * rng.standard_normal(p.shape).astype(np.float32)
-                                              for p in policies.init_param_list(spec.ob_dim, spec.ac_dim)]))
+    if args.network == "lstm":
+        from robosumo_selfplay_amd.lstm_model import LstmSpec
+        table = matches.LstmSnapshotTable(LstmSpec(D, A, 128), nsnap, env.device)
+        for j in range(nsnap):
+            table.set(j, [p + 0.1 * rng.standard_normal(p.shape).astype(np.float32)
+                          for p in policies.init_lstm_param_list(D, A, 128, np.random.RandomState(j))])
+    else:
+        table = matches.SnapshotTable(policies.PolicySpec(D, A, value_network="copy", activation="relu"), nsnap, env.device)
+        for j in range(nsnap):
+            table.set(j, policies.flatten_params([p + 0.1 * rng.standard_normal(p.shape).astype(np.float32)
+                                                  for p in policies.init_param_list(D, A)]))
     epp = N // args.pairs
     idx0_h, idx1_h, _ = matches.env_assignment([(2 * p, 2 * p + 1) for p in range(args.pairs)], list(range(args.pairs)), epp, N)
     idx0, idx1 = torch.from_numpy(idx0_h).cuda(), torch.from_numpy(idx1_h).cuda()
     gen = torch.Generator(device="cuda")
     gen.manual_seed(0)
-    A = spec.ac_dim
     noise = tuple(torch.randn((K, N, A), generator=gen, device="cuda") for _ in range(2))
-    out = dict(env=args.env, num_env=N, pairs=args.pairs, chunk=K)
+    out = dict(env=args.env, network=args.network, num_env=N, pairs=args.pairs, chunk=K)
     quota = 1 << 30
+    states = tuple(torch.zeros((N, 256), dtype=torch.float32, device="cuda") for _ in range(2))
+
+    def launch(fused, score):
+        i0, i1 = (idx0, idx1) if fused else (idx0_h, idx1_h)
+        if args.network == "lstm":
+            (matches.match_steps_fused_lstm if fused else matches.match_steps_stepwise_lstm)(env, table, i0, i1, states, score, quota, K, noise)
+        else:
+            (matches.match_steps_fused if fused else matches.match_steps_stepwise)(env, table, i0, i1, score, quota, K, noise)
 
     def run(fused, steps):
         score = torch.zeros((N, 3), dtype=torch.int32, device="cuda")
         env._needs_seed = True
         env.reset_device()
+        for st in states:
+            st.zero_()
         for _ in range(-(-args.warmup // K)):
-            (matches.match_steps_fused if fused else matches.match_steps_stepwise)(env, table, idx0 if fused else idx0_h,
-                                                                                     idx1 if fused else idx1_h, score, quota, K, noise)
+            launch(fused, score)
         score.zero_()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         n = 0
         while n < steps:
-            (matches.match_steps_fused if fused else matches.match_steps_stepwise)(env, table, idx0 if fused else idx0_h,
-                                                                                     idx1 if fused else idx1_h, score, quota, K, noise)
+            launch(fused, score)
             score.sum().item()                    # the per-launch counter read of play_matches
             n += K
         torch.cuda.synchronize()

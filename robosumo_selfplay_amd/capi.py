@@ -20,39 +20,33 @@ class SumoHipError(RuntimeError):
     pass
 
 
+_I, _P = C.c_int, C.c_void_p
+# the field tails the MLP and the LSTM struct of a launch share (include/sumo_hip.h)
+_ROLLOUT_TAIL = [("T", _I), ("Ntot", _I), ("env_offset", _I), ("s0", _I), ("K", _I), ("alpha", C.c_double), ("noise0", _P), ("noise1", _P),
+                 ("obs", _P), ("act", _P), ("rew", _P), ("val", _P), ("nlp", _P), ("onlp", _P),
+                 ("done", _P), ("ep_done", _P), ("ep_r", _P), ("ep_l", _P)]
+_MATCH_TAIL = [("T", _I), ("s0", _I), ("K", _I), ("quota", _I), ("noise0", _P), ("noise1", _P), ("score", _P)]
+
+
 class Rollout(C.Structure):
     """``sumo_rollout`` of include/sumo_hip.h (device pointers as integers)."""
-    _fields_ = [("learner_params", C.c_void_p), ("opponent_params", C.c_void_p), ("opponent_index", C.c_void_p),
-                ("npool", C.c_int), ("ob_dim", C.c_int), ("ac_dim", C.c_int),
-                ("T", C.c_int), ("Ntot", C.c_int), ("env_offset", C.c_int), ("s0", C.c_int), ("K", C.c_int),
-                ("alpha", C.c_double), ("noise0", C.c_void_p), ("noise1", C.c_void_p),
-                ("obs", C.c_void_p), ("act", C.c_void_p), ("rew", C.c_void_p), ("val", C.c_void_p), ("nlp", C.c_void_p), ("onlp", C.c_void_p),
-                ("done", C.c_void_p), ("ep_done", C.c_void_p), ("ep_r", C.c_void_p), ("ep_l", C.c_void_p)]
+    _fields_ = [("learner_params", _P), ("opponent_params", _P), ("opponent_index", _P),
+                ("npool", _I), ("ob_dim", _I), ("ac_dim", _I)] + _ROLLOUT_TAIL
 
 
 class RolloutLstm(C.Structure):
     """``sumo_rollout_lstm`` of include/sumo_hip.h (``learner``: pointer to a host ``ppo_capi.LstmNet``; the rest device pointers)."""
-    _fields_ = [("learner", C.c_void_p), ("opponents_dev", C.c_void_p), ("tile_net_dev", C.c_void_p), ("npool", C.c_int),
-                ("state0", C.c_void_p), ("state1", C.c_void_p),
-                ("T", C.c_int), ("Ntot", C.c_int), ("env_offset", C.c_int), ("s0", C.c_int), ("K", C.c_int),
-                ("alpha", C.c_double), ("noise0", C.c_void_p), ("noise1", C.c_void_p),
-                ("obs", C.c_void_p), ("act", C.c_void_p), ("rew", C.c_void_p), ("val", C.c_void_p), ("nlp", C.c_void_p), ("onlp", C.c_void_p),
-                ("done", C.c_void_p), ("ep_done", C.c_void_p), ("ep_r", C.c_void_p), ("ep_l", C.c_void_p)]
+    _fields_ = [("learner", _P), ("opponents_dev", _P), ("tile_net_dev", _P), ("npool", _I), ("state0", _P), ("state1", _P)] + _ROLLOUT_TAIL
 
 
 class Match(C.Structure):
     """``sumo_match`` of include/sumo_hip.h (device pointers as integers)."""
-    _fields_ = [("params", C.c_void_p), ("idx0", C.c_void_p), ("idx1", C.c_void_p),
-                ("nsnap", C.c_int), ("ob_dim", C.c_int), ("ac_dim", C.c_int),
-                ("T", C.c_int), ("s0", C.c_int), ("K", C.c_int), ("quota", C.c_int),
-                ("noise0", C.c_void_p), ("noise1", C.c_void_p), ("score", C.c_void_p)]
+    _fields_ = [("params", _P), ("idx0", _P), ("idx1", _P), ("nsnap", _I), ("ob_dim", _I), ("ac_dim", _I)] + _MATCH_TAIL
 
 
 class MatchLstm(C.Structure):
     """``sumo_match_lstm`` of include/sumo_hip.h (``proto`` a host pointer to a ``ppo_capi.LstmNet``, the rest device pointers)."""
-    _fields_ = [("proto", C.c_void_p), ("nets_dev", C.c_void_p), ("idx0", C.c_void_p), ("idx1", C.c_void_p), ("nsnap", C.c_int),
-                ("state0", C.c_void_p), ("state1", C.c_void_p), ("T", C.c_int), ("s0", C.c_int), ("K", C.c_int), ("quota", C.c_int),
-                ("noise0", C.c_void_p), ("noise1", C.c_void_p), ("score", C.c_void_p)]
+    _fields_ = [("proto", _P), ("nets_dev", _P), ("idx0", _P), ("idx1", _P), ("nsnap", _I), ("state0", _P), ("state1", _P)] + _MATCH_TAIL
 
 
 def lib():
@@ -148,22 +142,27 @@ class Engine:
     def step(self, actions_ptr, obs_ptr, info_ptr, done_ptr, ep_r_ptr, ep_dr_ptr, ep_l_ptr, stream=None):
         _chk(lib().sumo_step(self.h, actions_ptr, obs_ptr, info_ptr, done_ptr, ep_r_ptr, ep_dr_ptr, ep_l_ptr, stream))
 
-    def rollout_steps(self, ro, actions_ptr, obs_ptr, info_ptr, done_ptr, ep_r_ptr, ep_dr_ptr, ep_l_ptr, stream=None):
+    def _fused(self, entry, launch, env_ptrs, stream):
+        """One fused launch: ``env_ptrs`` are the seven env-side pointers of :meth:`step`, in its order."""
+        actions_ptr, obs_ptr, info_ptr, done_ptr, ep_r_ptr, ep_dr_ptr, ep_l_ptr = env_ptrs
+        _chk(getattr(lib(), entry)(self.h, C.byref(launch), *env_ptrs, stream))
+
+    def rollout_steps(self, ro, *env_ptrs, stream=None):
         """K fused self-play rollout steps (``sumo_rollout_steps``); ``ro`` is a filled :class:`Rollout`."""
-        _chk(lib().sumo_rollout_steps(self.h, C.byref(ro), actions_ptr, obs_ptr, info_ptr, done_ptr, ep_r_ptr, ep_dr_ptr, ep_l_ptr, stream))
+        self._fused("sumo_rollout_steps", ro, env_ptrs, stream)
 
-    def rollout_steps_lstm(self, ro, actions_ptr, obs_ptr, info_ptr, done_ptr, ep_r_ptr, ep_dr_ptr, ep_l_ptr, stream=None):
+    def rollout_steps_lstm(self, ro, *env_ptrs, stream=None):
         """The same for recurrent policies (``sumo_rollout_steps_lstm``); ``ro`` is a filled :class:`RolloutLstm`."""
-        _chk(lib().sumo_rollout_steps_lstm(self.h, C.byref(ro), actions_ptr, obs_ptr, info_ptr, done_ptr, ep_r_ptr, ep_dr_ptr, ep_l_ptr, stream))
+        self._fused("sumo_rollout_steps_lstm", ro, env_ptrs, stream)
 
-    def match_steps(self, mo, actions_ptr, obs_ptr, info_ptr, done_ptr, ep_r_ptr, ep_dr_ptr, ep_l_ptr, stream=None):
+    def match_steps(self, mo, *env_ptrs, stream=None):
         """K fused checkpoint-vs-checkpoint match steps (``sumo_match_steps``); ``mo`` is a filled :class:`Match`.  The outcome is
         read with :meth:`rollout_status`."""
-        _chk(lib().sumo_match_steps(self.h, C.byref(mo), actions_ptr, obs_ptr, info_ptr, done_ptr, ep_r_ptr, ep_dr_ptr, ep_l_ptr, stream))
+        self._fused("sumo_match_steps", mo, env_ptrs, stream)
 
-    def match_steps_lstm(self, mo, actions_ptr, obs_ptr, info_ptr, done_ptr, ep_r_ptr, ep_dr_ptr, ep_l_ptr, stream=None):
+    def match_steps_lstm(self, mo, *env_ptrs, stream=None):
         """The same for recurrent checkpoints (``sumo_match_steps_lstm``); ``mo`` is a filled :class:`MatchLstm`."""
-        _chk(lib().sumo_match_steps_lstm(self.h, C.byref(mo), actions_ptr, obs_ptr, info_ptr, done_ptr, ep_r_ptr, ep_dr_ptr, ep_l_ptr, stream))
+        self._fused("sumo_match_steps_lstm", mo, env_ptrs, stream)
 
     def set_cfrc_mode(self, mode):
         """'zero' (default, the reference's behaviour) or 'rne_post' (include/sumo_hip.h: cfrc_mode)."""

@@ -2564,6 +2564,81 @@ struct RolloutArgs {
   int nsnap, quota;
 };
 
+// ---- pieces shared by the four policy phases (each reads a / r through the references its phase received) ----
+// The env's two observations through the hand-over loads into rows 0 / 1 of the LDS tile x [2][XS].  PAD: columns D .. XS are
+// zero-filled; REC: the observations also go into the rollout record (runner.py:98-101).
+template <bool PAD, bool REC, class SA, class RA>
+__device__ __forceinline__ void policy_load_obs(const SA& a, const RA& r, int e, int lane, float* x, int D, int XS, size_t slot0 = 0, size_t slot1 = 0) {
+  const float* ob = a.obs + (size_t)e * 2 * a.obs_stride;
+  for (int k = lane; k < (PAD ? XS : D); k += WAVE) {
+    float o0 = 0.0f, o1 = 0.0f;
+    if (!PAD || k < D) {
+      o0 = hand_load<true>(ob + k); o1 = hand_load<true>(ob + a.obs_stride + k);
+      if (REC && PAD) { pt_global(r.obs)[slot0 * D + k] = o0; pt_global(r.obs)[slot1 * D + k] = o1; }   // (one predicated region)
+    }
+    x[k] = o0; x[XS + k] = o1;
+    if (REC && !PAD) { pt_global(r.obs)[slot0 * D + k] = o0; pt_global(r.obs)[slot1 * D + k] = o1; }
+  }
+}
+
+// Done flags of the previous step (agent 0 in the low byte, agent 1 in the next): the masks M of the recurrent nets; lanes 0 / 1
+// append agent 0's / agent 1's flag to the rollout record.
+template <class SA>
+__device__ __forceinline__ unsigned policy_prev_done(const SA& a, int e) { return hand_load<true>((const uint16_t*)(a.done + 2 * e)); }
+template <class RA>
+__device__ __forceinline__ void policy_record_done(const RA& r, int lane, size_t slot0, size_t slot1, unsigned dn) {
+  pt_global(r.done)[lane == 0 ? slot0 : slot1] = (uint8_t)(dn >> (8 * lane));
+}
+
+// Snapshot rows of env e's two sides (matches).  An index outside [0, nsnap) raises the launch's abort flag and plays row 0.
+template <class SA, class RA>
+__device__ __forceinline__ void policy_snapshot_rows(const SA& a, const RA& r, int e, int lane, int& j0, int& j1) {
+  j0 = pt_global(r.idx0)[e]; j1 = pt_global(r.idx1)[e];
+  if ((unsigned)j0 >= (unsigned)r.nsnap || (unsigned)j1 >= (unsigned)r.nsnap) {
+    if (lane == 0) __hip_atomic_store(pt_global(a.abort_flag), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    j0 = (unsigned)j0 < (unsigned)r.nsnap ? j0 : 0; j1 = (unsigned)j1 < (unsigned)r.nsnap ? j1 : 0;
+  }
+}
+
+// Column i of both actions (lanes i < A): REC into the rollout record; into the env's action buffer (output only, read back by
+// the next owner of the env) and into the step's control vector.
+template <bool REC, class C, class SA, class RA>
+__device__ __forceinline__ void policy_commit_actions(C& c, const SA& a, const RA& r, int e, int i, float act0, float act1, int A = 0, size_t slot0 = 0, size_t slot1 = 0) {
+  if (REC) { pt_global(r.act)[slot0 * A + i] = act0; pt_global(r.act)[slot1 * A + i] = act1; }
+  float* ae = const_cast<float*>(a.actions) + (size_t)e * 2 * a.act_stride;
+  hand_store<true>(ae + i, act0); hand_store<true>(ae + a.act_stride + i, act1);
+  const auto& mdl = model_view(c);
+  S(ctrl)[MI(agent_uadr)[0] + i] = (double)act0; S(ctrl)[MI(agent_uadr)[1] + i] = (double)act1;
+}
+
+// Index of column i of env e's draw at step s in noise0 / noise1 [T][N][A]
+template <class SA>
+__device__ __forceinline__ size_t policy_noise_index(const SA& a, int e, int s, int A, int i) { return ((size_t)s * a.N + e) * A + i; }
+
+// The step's scalars of the rollout record (lane 0): the learner's / the opponent's neglogp of both actions, the learner's values
+template <class RA>
+__device__ __forceinline__ void policy_record_scalars(const RA& r, size_t slot0, size_t slot1, float nlp0, float nlp1, float onlp0, float onlp1, float v0, float v1) {
+  pt_global(r.nlp)[slot0] = nlp0; pt_global(r.nlp)[slot1] = nlp1; pt_global(r.onlp)[slot0] = onlp0; pt_global(r.onlp)[slot1] = onlp1;
+  pt_global(r.val)[slot0] = v0; pt_global(r.val)[slot1] = v1;
+}
+
+// Recurrent state rows [2 NH] (c | h) cross waves like the env's record.  A lane owns the units j0 = 2 lane and j0 + 1:
+// lstm_state_pair loads their entries at p (one 8-byte hand-over load) masked by `keep` into out[0..1] (registers or LDS),
+// lstm_bias_pair prefetches their four gate biases, lstm_state_store writes unit j's new (c, h) back.
+__device__ __forceinline__ void lstm_state_pair(const float* p, float keep, float* out) {
+  union { unsigned long long u; float f[2]; } q;
+  q.u = hand_load<true>((const unsigned long long*)p); out[0] = q.f[0] * keep; out[1] = q.f[1] * keep;
+}
+template <int NH>
+__device__ __forceinline__ void lstm_bias_pair(const float PT_GAS* b, int j0, float (&bz)[4][2]) {
+#pragma unroll
+  for (int g = 0; g < 4; g++) { bz[g][0] = b[g * NH + j0]; bz[g][1] = b[g * NH + j0 + 1]; }
+}
+template <int NH>
+__device__ __forceinline__ void lstm_state_store(float* sp, int j, const LstmCell& cell) {
+  hand_store<true>(sp + j, cell.cn); hand_store<true>(sp + NH + j, cell.hn);
+}
+
 template <class C, class SA, class RA>
 __device__ __forceinline__ void rollout_policy_phase(C& c, const SA& a, const RA& r, int e, int s) {
   const int lane = c.lane, i = lane & 15, kq = lane >> 4;
@@ -2573,17 +2648,11 @@ __device__ __forceinline__ void rollout_policy_phase(C& c, const SA& a, const RA
   float* h2 = h1 + 2 * PT_HS;
   const size_t col = (size_t)r.env_offset + e;
   const size_t slot0 = ((size_t)0 * r.T + s) * r.Ntot + col, slot1 = ((size_t)1 * r.T + s) * r.Ntot + col;
-  // the env's two observations: into the tile and into the rollout record (runner.py:98-101)
-  const float* ob = a.obs + (size_t)e * 2 * a.obs_stride;
 #ifdef SUMO_POLICY_PROBE
   unsigned long long tp_ = wall_clock64();
 #endif
-  for (int k = lane; k < D; k += WAVE) {
-    const float o0 = hand_load<true>(ob + k), o1 = hand_load<true>(ob + a.obs_stride + k);
-    xbuf[k] = o0; xbuf[XS + k] = o1;
-    pt_global(r.obs)[slot0 * D + k] = o0; pt_global(r.obs)[slot1 * D + k] = o1;
-  }
-  if (lane < 2) pt_global(r.done)[lane == 0 ? slot0 : slot1] = (uint8_t)(hand_load<true>((const uint16_t*)(a.done + 2 * e)) >> (8 * lane));
+  policy_load_obs<false, true>(a, r, e, lane, xbuf, D, XS, slot0, slot1);
+  if (lane < 2) policy_record_done(r, lane, slot0, slot1, policy_prev_done(a, e));
   wave_sync();
   const float PT_GAS* lp = pt_global(r.learner);
   const float PT_GAS* op = pt_global(r.opponent) + (size_t)(r.opp_idx ? pt_global(r.opp_idx)[e] : 0) * r.L.P;
@@ -2602,24 +2671,15 @@ __device__ __forceinline__ void rollout_policy_phase(C& c, const SA& a, const RA
   const float stdL = expf(lsL), stdO = expf(lsO);
   const float sumL = row16_sum(lsL), sumO = row16_sum(lsO);
   const bool ok = colk && kq == 0;                  // rows 0 and 1 live in the first 16 lanes (D layout: rows 4 kq + r)
-  const size_t nz = ((size_t)s * a.N + e) * A + i;
+  const size_t nz = policy_noise_index(a, e, s, A, i);
   const float n0 = ok ? pt_global(r.noise0)[nz] : 0.0f, n1 = ok ? pt_global(r.noise1)[nz] : 0.0f;
   float act0 = 0.0f, act1 = 0.0f;
   const float nlp0 = gauss_row(mL[0], stdL, sumL, ok, true, n0, act0, A);      // learner samples for agent 0 ...
   const float onlp0 = gauss_row(mO[0], stdO, sumO, ok, false, 0.0f, act0, A);  // ... the opponent net scores that action
   const float onlp1 = gauss_row(mO[1], stdO, sumO, ok, true, n1, act1, A);     // opponent samples for agent 1 ...
   const float nlp1 = gauss_row(mL[1], stdL, sumL, ok, false, 0.0f, act1, A);   // ... the learner scores it
-  if (ok) {
-    pt_global(r.act)[slot0 * A + i] = act0; pt_global(r.act)[slot1 * A + i] = act1;
-    float* ae = const_cast<float*>(a.actions) + (size_t)e * 2 * a.act_stride;
-    hand_store<true>(ae + i, act0); hand_store<true>(ae + a.act_stride + i, act1);     // the env's action buffer (output only)
-    const auto& mdl = model_view(c);
-    S(ctrl)[MI(agent_uadr)[0] + i] = (double)act0; S(ctrl)[MI(agent_uadr)[1] + i] = (double)act1;   // the step's control vector
-  }
-  if (lane == 0) {
-    pt_global(r.nlp)[slot0] = nlp0; pt_global(r.nlp)[slot1] = nlp1; pt_global(r.onlp)[slot0] = onlp0; pt_global(r.onlp)[slot1] = onlp1;
-    pt_global(r.val)[slot0] = vL[0]; pt_global(r.val)[slot1] = vL[1];
-  }
+  if (ok) policy_commit_actions<true>(c, a, r, e, i, act0, act1, A, slot0, slot1);
+  if (lane == 0) policy_record_scalars(r, slot0, slot1, nlp0, nlp1, onlp0, onlp1, vL[0], vL[1]);
   PPROBE(8);
   wave_sync();   // the action buffer is read back by the env step (other lanes), the scratch region becomes the mass matrix again
 }
@@ -2645,43 +2705,31 @@ __device__ __forceinline__ void rollout_policy_phase_lstm(C& c, const SA& a, con
   float* hn = hp + 3 * NH;
   const size_t col = (size_t)r.env_offset + e;
   const size_t slot0 = ((size_t)0 * r.T + s) * r.Ntot + col, slot1 = ((size_t)1 * r.T + s) * r.Ntot + col;
-  const float* ob = a.obs + (size_t)e * 2 * a.obs_stride;
-  for (int k = lane; k < XS; k += WAVE) {
-    float o0 = 0.0f, o1 = 0.0f;
-    if (k < D) {
-      o0 = hand_load<true>(ob + k); o1 = hand_load<true>(ob + a.obs_stride + k);
-      pt_global(r.obs)[slot0 * D + k] = o0; pt_global(r.obs)[slot1 * D + k] = o1;
-    }
-    xo[k] = o0; xo[XS + k] = o1;
-  }
-  const unsigned dn = hand_load<true>((const uint16_t*)(a.done + 2 * e));   // done flags of the previous step = the masks M
-  if (lane < 2) pt_global(r.done)[lane == 0 ? slot0 : slot1] = (uint8_t)(dn >> (8 * lane));
+  policy_load_obs<true, true>(a, r, e, lane, xo, D, XS, slot0, slot1);
+  const unsigned dn = policy_prev_done(a, e);
+  if (lane < 2) policy_record_done(r, lane, slot0, slot1, dn);
   const float keep0 = 1.0f - (float)(dn & 0xff), keep1 = 1.0f - (float)((dn >> 8) & 0xff);
   // the acting nets' states: lane owns the units 2 lane, 2 lane + 1
   float* s0p = r.st0 + (size_t)e * 2 * NH;
   float* s1p = r.st1 + (size_t)e * 2 * NH;
   const int j0 = 2 * lane;
   float c0[2], c1[2], cD[2];
-  {
-    union { unsigned long long u; float f[2]; } q;
-    q.u = hand_load<true>((const unsigned long long*)(s0p + j0)); c0[0] = q.f[0] * keep0; c0[1] = q.f[1] * keep0;
-    q.u = hand_load<true>((const unsigned long long*)(s1p + j0)); c1[0] = q.f[0] * keep1; c1[1] = q.f[1] * keep1;
-    q.u = hand_load<true>((const unsigned long long*)(s0p + NH + j0)); hp[NH + j0] = q.f[0] * keep0; hp[NH + j0 + 1] = q.f[1] * keep0;
-    q.u = hand_load<true>((const unsigned long long*)(s1p + NH + j0)); hp[j0] = q.f[0] * keep1; hp[j0 + 1] = q.f[1] * keep1;
-    hz[j0] = 0.0f; hz[j0 + 1] = 0.0f;
-  }
+  lstm_state_pair(s0p + j0, keep0, c0);
+  lstm_state_pair(s1p + j0, keep1, c1);
+  lstm_state_pair(s0p + NH + j0, keep0, hp + NH + j0);
+  lstm_state_pair(s1p + NH + j0, keep1, hp + j0);
+  hz[j0] = 0.0f; hz[j0 + 1] = 0.0f;
   wave_sync();
   const ppo_lstm_net PT_GAS* NOp = pt_global(r.onets) + (r.tile_net ? pt_global(r.tile_net)[col >> 4] : 0);
   const bool ok = lane < A;
-  const size_t nz = ((size_t)s * a.N + e) * A + lane;
+  const size_t nz = policy_noise_index(a, e, s, A, lane);
   float act0 = 0.0f, act1 = 0.0f, onlp1, mOB, stdO, sumO;
   {  // ---- opponent net: rows A, B
     const float *owx = NOp->wx, *owh = NOp->wh;
     const float PT_GAS* ob_ = pt_global(NOp->b);
     const float fb = NOp->forget_bias;
     float z[4][2][2], bz[4][2];
-#pragma unroll
-    for (int g = 0; g < 4; g++) { bz[g][0] = ob_[g * NH + j0]; bz[g][1] = ob_[g * NH + j0 + 1]; }   // (in flight during the gate sums)
+    lstm_bias_pair<NH>(ob_, j0, bz);   // (in flight during the gate sums)
     const float* const xr[2] = {xo + XS, xo};
     const float* const hr[2] = {hp, hz};
     lstm_gates_valu<NH, 2>(owx, owh, D, xr, hr, lane, z);
@@ -2691,7 +2739,7 @@ __device__ __forceinline__ void rollout_policy_phase_lstm(C& c, const SA& a, con
       const float bi = bz[0][u], bf = bz[1][u] + fb, bo = bz[2][u], bu = bz[3][u];   // gate order i, f, o, u
       const LstmCell ca = lstm_cell(z[0][u][0], z[1][u][0], z[2][u][0], z[3][u][0], bi, bf, bo, bu, c1[u]);
       const LstmCell cb = lstm_cell(z[0][u][1], z[1][u][1], z[2][u][1], z[3][u][1], bi, bf, bo, bu, hz[j]);
-      hand_store<true>(s1p + j, ca.cn); hand_store<true>(s1p + NH + j, ca.hn);      // agent 1's state after the opponent's step
+      lstm_state_store<NH>(s1p, j, ca);                                              // agent 1's state after the opponent's step
       hn[j] = ca.hn; hn[NH + j] = cb.hn;
       cD[u] = ca.cn * keep1; hp[2 * NH + j] = ca.hn * keep1;                         // row D: masked once more by the same flag
     }
@@ -2709,8 +2757,7 @@ __device__ __forceinline__ void rollout_policy_phase_lstm(C& c, const SA& a, con
   {  // ---- learner net: rows C, D, E
     const float fb = NL.forget_bias;
     float z[4][2][3], bz[4][2];
-#pragma unroll
-    for (int g = 0; g < 4; g++) { bz[g][0] = pt_global(NL.b)[g * NH + j0]; bz[g][1] = pt_global(NL.b)[g * NH + j0 + 1]; }
+    lstm_bias_pair<NH>(pt_global(NL.b), j0, bz);
     const float* const xr[3] = {xo, xo + XS, xo + XS};
     const float* const hr[3] = {hp + NH, hp + 2 * NH, hz};
     lstm_gates_valu<NH, 3>(NL.wx, NL.wh, D, xr, hr, lane, z);
@@ -2721,7 +2768,7 @@ __device__ __forceinline__ void rollout_policy_phase_lstm(C& c, const SA& a, con
       const LstmCell cc = lstm_cell(z[0][u][0], z[1][u][0], z[2][u][0], z[3][u][0], bi, bf, bo, bu, c0[u]);
       const LstmCell cd = lstm_cell(z[0][u][1], z[1][u][1], z[2][u][1], z[3][u][1], bi, bf, bo, bu, cD[u]);
       const LstmCell ce = lstm_cell(z[0][u][2], z[1][u][2], z[2][u][2], z[3][u][2], bi, bf, bo, bu, hz[j]);
-      hand_store<true>(s0p + j, cc.cn); hand_store<true>(s0p + NH + j, cc.hn);      // agent 0's state after the learner's step
+      lstm_state_store<NH>(s0p, j, cc);                                              // agent 0's state after the learner's step
       hn[j] = cc.hn; hn[NH + j] = cd.hn; hn[2 * NH + j] = ce.hn;
     }
     wave_sync();
@@ -2736,17 +2783,8 @@ __device__ __forceinline__ void rollout_policy_phase_lstm(C& c, const SA& a, con
     onlp0 = gauss_row(mOB, stdO, sumO, ok, false, 0.0f, act0, A);        // ... the opponent net (zero state) scores that action
     nlp1 = gauss_row(m[2] + hb, stdL, sumL, ok, false, 0.0f, act1, A);   // the learner (zero state) scores the opponent's action
   }
-  if (ok) {
-    pt_global(r.act)[slot0 * A + lane] = act0; pt_global(r.act)[slot1 * A + lane] = act1;
-    float* ae = const_cast<float*>(a.actions) + (size_t)e * 2 * a.act_stride;
-    hand_store<true>(ae + lane, act0); hand_store<true>(ae + a.act_stride + lane, act1);
-    const auto& mdl = model_view(c);
-    S(ctrl)[MI(agent_uadr)[0] + lane] = (double)act0; S(ctrl)[MI(agent_uadr)[1] + lane] = (double)act1;
-  }
-  if (lane == 0) {
-    pt_global(r.nlp)[slot0] = nlp0; pt_global(r.nlp)[slot1] = nlp1; pt_global(r.onlp)[slot0] = onlp0; pt_global(r.onlp)[slot1] = onlp1;
-    pt_global(r.val)[slot0] = v0; pt_global(r.val)[slot1] = v1;
-  }
+  if (ok) policy_commit_actions<true>(c, a, r, e, lane, act0, act1, A, slot0, slot1);
+  if (lane == 0) policy_record_scalars(r, slot0, slot1, nlp0, nlp1, onlp0, onlp1, v0, v1);
   wave_sync();
 }
 
@@ -2761,14 +2799,10 @@ __device__ __forceinline__ void rollout_policy_phase_match(C& c, const SA& a, co
   float* xbuf = (float*)(c.sm + r.lds_off);        // [2][XS] | h1 [2][PT_HS] | h2 [2][PT_HS]
   float* h1 = xbuf + 2 * XS;
   float* h2 = h1 + 2 * PT_HS;
-  const float* ob = a.obs + (size_t)e * 2 * a.obs_stride;
-  for (int k = lane; k < D; k += WAVE) { xbuf[k] = hand_load<true>(ob + k); xbuf[XS + k] = hand_load<true>(ob + a.obs_stride + k); }
+  policy_load_obs<false, false>(a, r, e, lane, xbuf, D, XS);
   wave_sync();
-  int j0 = pt_global(r.idx0)[e], j1 = pt_global(r.idx1)[e];
-  if ((unsigned)j0 >= (unsigned)r.nsnap || (unsigned)j1 >= (unsigned)r.nsnap) {
-    if (lane == 0) __hip_atomic_store(pt_global(a.abort_flag), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    j0 = (unsigned)j0 < (unsigned)r.nsnap ? j0 : 0; j1 = (unsigned)j1 < (unsigned)r.nsnap ? j1 : 0;
-  }
+  int j0, j1;
+  policy_snapshot_rows(a, r, e, lane, j0, j1);
   const float PT_GAS* p0 = pt_global(r.snaps) + (size_t)j0 * r.L.P;
   const float PT_GAS* p1 = pt_global(r.snaps) + (size_t)j1 * r.L.P;
   const f32x4 m0 = trunk_forward<false, 2>(pi_net((const float*)p0, r.L), xbuf, XS, D, h1, h2, lane);
@@ -2778,17 +2812,12 @@ __device__ __forceinline__ void rollout_policy_phase_match(C& c, const SA& a, co
   float act0 = m0[0], act1 = m1[1];
   if (r.noise0) {
     const float ls0 = ok ? p0[r.L.logstd + i] : 0.0f, ls1 = ok ? p1[r.L.logstd + i] : 0.0f;
-    const size_t nz = ((size_t)s * a.N + e) * A + i;
+    const size_t nz = policy_noise_index(a, e, s, A, i);
     const float n0 = ok ? pt_global(r.noise0)[nz] : 0.0f, n1 = ok ? pt_global(r.noise1)[nz] : 0.0f;
     (void)gauss_row(m0[0], expf(ls0), 0.0f, ok, true, n0, act0, A);
     (void)gauss_row(m1[1], expf(ls1), 0.0f, ok, true, n1, act1, A);
   }
-  if (ok) {
-    float* ae = const_cast<float*>(a.actions) + (size_t)e * 2 * a.act_stride;
-    hand_store<true>(ae + i, act0); hand_store<true>(ae + a.act_stride + i, act1);     // the env's action buffer (output only)
-    const auto& mdl = model_view(c);
-    S(ctrl)[MI(agent_uadr)[0] + i] = (double)act0; S(ctrl)[MI(agent_uadr)[1] + i] = (double)act1;   // the step's control vector
-  }
+  if (ok) policy_commit_actions<false>(c, a, r, e, i, act0, act1);
   wave_sync();   // the action buffer is read back by the env step (other lanes), the scratch region becomes the mass matrix again
 }
 
@@ -2805,18 +2834,10 @@ __device__ __forceinline__ void rollout_policy_phase_match_lstm(C& c, const SA& 
   float* xo = (float*)(c.sm + r.lds_off);
   float* hp = xo + 2 * XS;
   float* hn = hp + NH;
-  const float* ob = a.obs + (size_t)e * 2 * a.obs_stride;
-  for (int k = lane; k < XS; k += WAVE) {
-    float o0 = 0.0f, o1 = 0.0f;
-    if (k < D) { o0 = hand_load<true>(ob + k); o1 = hand_load<true>(ob + a.obs_stride + k); }
-    xo[k] = o0; xo[XS + k] = o1;
-  }
-  const unsigned dn = hand_load<true>((const uint16_t*)(a.done + 2 * e));   // done flags of the previous step = the masks M
-  int jn[2] = {pt_global(r.idx0)[e], pt_global(r.idx1)[e]};
-  if ((unsigned)jn[0] >= (unsigned)r.nsnap || (unsigned)jn[1] >= (unsigned)r.nsnap) {
-    if (lane == 0) __hip_atomic_store(pt_global(a.abort_flag), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    jn[0] = (unsigned)jn[0] < (unsigned)r.nsnap ? jn[0] : 0; jn[1] = (unsigned)jn[1] < (unsigned)r.nsnap ? jn[1] : 0;
-  }
+  policy_load_obs<true, false>(a, r, e, lane, xo, D, XS);
+  const unsigned dn = policy_prev_done(a, e);
+  int jn[2];
+  policy_snapshot_rows(a, r, e, lane, jn[0], jn[1]);
   const bool ok = lane < A;
   const int j0 = 2 * lane;                           // lane owns the units 2 lane, 2 lane + 1
   float act[2];
@@ -2826,16 +2847,12 @@ __device__ __forceinline__ void rollout_policy_phase_match_lstm(C& c, const SA& 
     const float keep = 1.0f - (float)((dn >> (8 * g)) & 0xff);
     float* sp = (g ? r.st1 : r.st0) + (size_t)e * 2 * NH;
     float cp[2];
-    {
-      union { unsigned long long u; float f[2]; } q;
-      q.u = hand_load<true>((const unsigned long long*)(sp + j0)); cp[0] = q.f[0] * keep; cp[1] = q.f[1] * keep;
-      q.u = hand_load<true>((const unsigned long long*)(sp + NH + j0)); hp[j0] = q.f[0] * keep; hp[j0 + 1] = q.f[1] * keep;
-    }
+    lstm_state_pair(sp + j0, keep, cp);
+    lstm_state_pair(sp + NH + j0, keep, hp + j0);
     const float PT_GAS* b_ = pt_global(NT->b);
     const float fb = NT->forget_bias;
     float z[4][2][1], bz[4][2];
-#pragma unroll
-    for (int q = 0; q < 4; q++) { bz[q][0] = b_[q * NH + j0]; bz[q][1] = b_[q * NH + j0 + 1]; }
+    lstm_bias_pair<NH>(b_, j0, bz);
     wave_sync();
     const float* const xr[1] = {xo + g * XS};
     const float* const hr[1] = {hp};
@@ -2844,7 +2861,7 @@ __device__ __forceinline__ void rollout_policy_phase_match_lstm(C& c, const SA& 
     for (int u = 0; u < 2; u++) {
       const int j = j0 + u;
       const LstmCell cl = lstm_cell(z[0][u][0], z[1][u][0], z[2][u][0], z[3][u][0], bz[0][u], bz[1][u] + fb, bz[2][u], bz[3][u], cp[u]);
-      hand_store<true>(sp + j, cl.cn); hand_store<true>(sp + NH + j, cl.hn);        // agent g's state after its step
+      lstm_state_store<NH>(sp, j, cl);                                              // agent g's state after its step
       hn[j] = cl.hn;
     }
     wave_sync();
@@ -2854,17 +2871,12 @@ __device__ __forceinline__ void rollout_policy_phase_match_lstm(C& c, const SA& 
     act[g] = mean;
     if (r.noise0) {
       const float ls = ok ? pt_global(NT->logstd)[lane] : 0.0f;
-      const float nz = ok ? pt_global(g ? r.noise1 : r.noise0)[((size_t)s * a.N + e) * A + lane] : 0.0f;
+      const float nz = ok ? pt_global(g ? r.noise1 : r.noise0)[policy_noise_index(a, e, s, A, lane)] : 0.0f;
       (void)gauss_row(mean, expf(ls), 0.0f, ok, true, nz, act[g], A);
     }
     wave_sync();   // the latent rows are rewritten by the next side
   }
-  if (ok) {
-    float* ae = const_cast<float*>(a.actions) + (size_t)e * 2 * a.act_stride;
-    hand_store<true>(ae + lane, act[0]); hand_store<true>(ae + a.act_stride + lane, act[1]);   // the env's action buffer (output only)
-    const auto& mdl = model_view(c);
-    S(ctrl)[MI(agent_uadr)[0] + lane] = (double)act[0]; S(ctrl)[MI(agent_uadr)[1] + lane] = (double)act[1];   // the step's control vector
-  }
+  if (ok) policy_commit_actions<false>(c, a, r, e, lane, act[0], act[1]);
   wave_sync();
 }
 
@@ -3688,6 +3700,14 @@ static bool for_kernel_variant(int nv, F&& f) {
 #undef X
   return false;
 }
+// the variant an engine's step / rollout kernels run: f(NV, SL) with the static layouts <28, 1> (Ant vs Ant) and <44, 2> (Spider
+// vs Spider) where sumo_create found one, else <nv, 0>
+template <class F>
+static bool for_engine_variant(const sumo_engine* E, F&& f) {
+  if (E->static_layout == 1) { f(std::integral_constant<int, 28>(), std::integral_constant<int, 1>()); return true; }
+  if (E->static_layout == 2) { f(std::integral_constant<int, 44>(), std::integral_constant<int, 2>()); return true; }
+  return for_kernel_variant(E->hm.nv, [&](auto nvc_) { f(nvc_, std::integral_constant<int, 0>()); });
+}
 #define SUMO_DISPATCH(KERNEL, E, stream, args) SUMO_DISPATCH_N(KERNEL, E, stream, args, (E)->N)
 #define SUMO_DISPATCH_N(KERNEL, E, stream, args, nblocks)                                                   \
   do {                                                                                                       \
@@ -3754,14 +3774,11 @@ extern "C" int sumo_step(sumo_handle_t E, const float* actions_dev, float* obs_d
   }
   if (E->cfrc_mode)   // rne_post: the state this step starts from, for the second launch below
     HIPCHK(hipMemcpyAsync(E->d_state_prev, E->d_state, (size_t)E->N * E->state_stride * sizeof(double), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  if (E->static_layout == 1) {
-    dim3 g_(nblocks), b_(WAVE);
-    hipLaunchKernelGGL((sumo_step_kernel<28, 1>), g_, b_, (size_t)E->L.total_bytes, (hipStream_t)stream, E->d_params, a);
-  } else if (E->static_layout == 2) {
-    dim3 g_(nblocks), b_(WAVE);
-    hipLaunchKernelGGL((sumo_step_kernel<44, 2>), g_, b_, (size_t)E->L.total_bytes, (hipStream_t)stream, E->d_params, a);
-  } else
-    SUMO_DISPATCH_N(sumo_step_kernel, E, (hipStream_t)stream, a, nblocks);
+  if (!for_engine_variant(E, [&](auto nvc_, auto slc_) {
+        hipLaunchKernelGGL((sumo_step_kernel<decltype(nvc_)::value, decltype(slc_)::value>), dim3(nblocks), dim3(WAVE), (size_t)E->L.total_bytes,
+                           (hipStream_t)stream, E->d_params, a);
+      }))
+    FAIL(-19, "no kernel variant for nv=%d", E->hm.nv);
   HIPCHK(hipGetLastError());
   if (E->cfrc_mode) {
     CfrcArgs q;
@@ -3785,13 +3802,25 @@ extern "C" int sumo_step(sumo_handle_t E, const float* actions_dev, float* obs_d
   return 0;
 }
 
-// common tail of the two fused-rollout entry points: scheduler state, persistent grid, launch
-static int rollout_launch(sumo_engine* E, const RolloutArgs& r, int policy, float* actions_dev, float* obs_dev, double* info_dev,
-                          uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
+// the env-side buffers of sumo_step, as every fused entry point receives them
+struct EnvBuffers {
+  float *actions, *obs;
+  double* info;
+  uint8_t* done;
+  double *ep_r, *ep_dr;
+  int32_t* ep_l;
+};
+static int check_launch_args(sumo_engine* E, const void* launch, const EnvBuffers& b) {
+  if (!E || !launch || !b.actions || !b.obs || !b.info || !b.done || !b.ep_r || !b.ep_dr || !b.ep_l) FAIL(-1, "bad arguments");
+  return 0;
+}
+
+// common tail of the fused entry points: scheduler state, persistent grid, launch
+static int rollout_launch(sumo_engine* E, const RolloutArgs& r, int policy, const EnvBuffers& b, void* stream) {
   RolloutLaunch rl;
   rl.a = base_args(E);
   StepArgs& a = rl.a;
-  a.actions = actions_dev; a.obs = obs_dev; a.info = info_dev; a.done = done_dev; a.ep_r = ep_r_dev; a.ep_dr = ep_dr_dev; a.ep_l = ep_l_dev;
+  a.actions = b.actions; a.obs = b.obs; a.info = b.info; a.done = b.done; a.ep_r = b.ep_r; a.ep_dr = b.ep_dr; a.ep_l = b.ep_l;
   rl.r = r;
   rl.r.prof = E->d_trace;   // development: sumo_debug_trace(stamps) switches the per-wave phase clock on
   hipStream_t st_ = (hipStream_t)stream;
@@ -3818,28 +3847,20 @@ static int rollout_launch(sumo_engine* E, const RolloutArgs& r, int policy, floa
   if (nw > (long long)E->N) nw = E->N;   // more waves than envs would only wait on each other's steps
   dim3 g_((unsigned)nw), b_(WAVE);
   size_t lds_ = (size_t)E->L.total_bytes;
-  if (E->static_layout == 1) {
-    if (policy == 1) hipLaunchKernelGGL((sumo_rollout_kernel<28, 1, 1>), g_, b_, lds_, st_, E->d_params, rl);
-    else if (policy == 2) hipLaunchKernelGGL((sumo_rollout_kernel<28, 2, 1>), g_, b_, lds_, st_, E->d_params, rl);
-    else if (policy == 3) hipLaunchKernelGGL((sumo_rollout_kernel<28, 3, 1>), g_, b_, lds_, st_, E->d_params, rl);
-    else hipLaunchKernelGGL((sumo_rollout_kernel<28, 0, 1>), g_, b_, lds_, st_, E->d_params, rl);
-  } else if (E->static_layout == 2) {
-    if (policy == 1) hipLaunchKernelGGL((sumo_rollout_kernel<44, 1, 2>), g_, b_, lds_, st_, E->d_params, rl);
-    else if (policy == 2) hipLaunchKernelGGL((sumo_rollout_kernel<44, 2, 2>), g_, b_, lds_, st_, E->d_params, rl);
-    else if (policy == 3) hipLaunchKernelGGL((sumo_rollout_kernel<44, 3, 2>), g_, b_, lds_, st_, E->d_params, rl);
-    else hipLaunchKernelGGL((sumo_rollout_kernel<44, 0, 2>), g_, b_, lds_, st_, E->d_params, rl);
-  } else if (!for_kernel_variant(E->hm.nv, [&](auto nvc_) {
-        if (policy == 1) hipLaunchKernelGGL((sumo_rollout_kernel<decltype(nvc_)::value, 1>), g_, b_, lds_, st_, E->d_params, rl);
-        else if (policy == 2) hipLaunchKernelGGL((sumo_rollout_kernel<decltype(nvc_)::value, 2>), g_, b_, lds_, st_, E->d_params, rl);
-        else if (policy == 3) hipLaunchKernelGGL((sumo_rollout_kernel<decltype(nvc_)::value, 3>), g_, b_, lds_, st_, E->d_params, rl);
-        else hipLaunchKernelGGL((sumo_rollout_kernel<decltype(nvc_)::value, 0>), g_, b_, lds_, st_, E->d_params, rl);
+  if (!for_engine_variant(E, [&](auto nvc_, auto slc_) {
+        constexpr int NV = decltype(nvc_)::value, SL = decltype(slc_)::value;
+        void (*kernel)(const Params*, RolloutLaunch) = policy == 1   ? sumo_rollout_kernel<NV, 1, SL>
+                                                       : policy == 2 ? sumo_rollout_kernel<NV, 2, SL>
+                                                       : policy == 3 ? sumo_rollout_kernel<NV, 3, SL>
+                                                                     : sumo_rollout_kernel<NV, 0, SL>;
+        hipLaunchKernelGGL(kernel, g_, b_, lds_, st_, E->d_params, rl);
       }))
     FAIL(-19, "no kernel variant for nv=%d", E->hm.nv);
   HIPCHK(hipGetLastError());
   return 0;
 }
 
-// scene checks shared by the two entry points; returns the observation / action width through od / ad
+// scene checks shared by the entry points; returns the observation / action width through od / ad
 static int rollout_scene(sumo_engine* E, int T, int Ntot, int env_offset, int s0, int K, int* od, int* ad) {
   const sumo_model_t* m = &E->hm;
   if (E->cfrc_mode) FAIL(-12, "cfrc_mode rne_post fills the observations in a second launch per step: use sumo_step (the fused rollout evaluates the policies inside its launch)");
@@ -3853,43 +3874,100 @@ static int rollout_scene(sumo_engine* E, int T, int Ntot, int env_offset, int s0
   return 0;
 }
 
+static int check_dims(int ob_dim, int ac_dim, int od, int ad) {
+  if (ob_dim != od || ac_dim != ad || ac_dim > PT_MAXA) FAIL(-4, "ob_dim %d / ac_dim %d do not match the scene (%d / %d)", ob_dim, ac_dim, od, ad);
+  return 0;
+}
+
+// what the in-wave recurrent evaluation is built for: the nets `learn(network='lstm')` trains (policy-zoo LSTM nets carry an
+// observation filter, an embedding and the other gate order: they go through ppo_lstm_step)
+static int check_lstm_shape(const ppo_lstm_net& n, const char* what) {
+  if (n.hidden != 128 || n.gate_order != PPO_LSTM_GATES_IFOU || n.emb_w || n.emb_dim != 0 || n.obs_mean || n.obs_invstd)
+    FAIL(-9, "fused recurrent %s: hidden 128, gate order i,f,o,u, no embedding, no observation filter (got hidden %d, order %d, emb %d)", what, n.hidden, n.gate_order, n.emb_dim);
+  return 0;
+}
+
+// MLP phases: x [2][XS] and the two hidden tiles go where the mass matrix lives between two steps
+static int place_mlp_scratch(sumo_engine* E, int ob_dim, int ac_dim, RolloutArgs& r) {
+  r.XS = x_stride(ob_dim); r.L = make_layout(ob_dim, ac_dim); r.lds_off = E->L.M;
+  const size_t need = (size_t)(2 * r.XS + 4 * PT_HS) * sizeof(float), have = (size_t)E->L.msize * sizeof(double);
+  if (need > have) FAIL(-8, "policy scratch (%zu B) does not fit the mass-matrix region (%zu B)", need, have);
+  return 0;
+}
+
+// LSTM phases: x [2][XS] and `rows` rows of 128 floats.  Between two steps of an env nothing from the mass matrix to the end of the
+// float64 area is live (contact records, Jacobian pool and row arrays are rebuilt by every forward): the rows go there, 16-byte
+// aligned for the 128-bit LDS reads
+static int place_lstm_scratch(sumo_engine* E, int od, int rows, RolloutArgs& r) {
+  r.XS = (od + 3) & ~3;
+  r.lds_off = (E->L.M + 1) & ~1;
+  const size_t need = (size_t)(2 * r.XS + rows * 128) * sizeof(float), have = (size_t)(E->L.i_base - r.lds_off) * sizeof(double);
+  if (E->L.ctrl >= E->L.M || E->L.stash >= E->L.M || need > have) FAIL(-8, "policy scratch (%zu B) does not fit the per-step LDS area (%zu B)", need, have);
+  return 0;
+}
+
+// the fields sumo_rollout and sumo_rollout_lstm share
+template <class RO>
+static bool rollout_buffer_missing(const RO* ro) {
+  return !ro->noise0 || !ro->noise1 || !ro->obs || !ro->act || !ro->rew || !ro->val || !ro->nlp || !ro->onlp || !ro->done || !ro->ep_done ||
+         !ro->ep_r || !ro->ep_l;
+}
+template <class RO>
+static void copy_rollout_fields(RolloutArgs& r, const RO* ro) {
+  r.noise0 = ro->noise0; r.noise1 = ro->noise1;
+  r.obs = ro->obs; r.act = ro->act; r.rew = ro->rew; r.val = ro->val; r.nlp = ro->nlp; r.onlp = ro->onlp; r.done = ro->done;
+  r.ep_done = ro->ep_done; r.ep_r = ro->ep_r; r.ep_l = ro->ep_l; r.alpha = ro->alpha;
+  r.T = ro->T; r.Ntot = ro->Ntot; r.env_offset = ro->env_offset; r.s0 = ro->s0; r.K = ro->K;
+}
+
+// the fields sumo_match and sumo_match_lstm share: their checks (`name`: the struct in the messages) and the copy
+template <class MO>
+static int check_match_buffers(const MO* mo, const char* name) {
+  if (!mo->idx0 || !mo->idx1 || !mo->score) FAIL(-2, "%s: missing buffer", name);
+  if (!mo->noise0 != !mo->noise1) FAIL(-2, "%s: noise0 and noise1 are both given (stochastic play) or both NULL (deterministic)", name);
+  return 0;
+}
+template <class MO>
+static int check_match_counts(const MO* mo) {
+  if (mo->nsnap < 1) FAIL(-7, "nsnap %d: the snapshot table needs at least one entry", mo->nsnap);
+  if (mo->quota < 0) FAIL(-9, "quota %d", mo->quota);
+  return 0;
+}
+template <class MO>
+static void copy_match_fields(RolloutArgs& r, const MO* mo, int N) {
+  r.idx0 = mo->idx0; r.idx1 = mo->idx1; r.score = mo->score; r.nsnap = mo->nsnap; r.quota = mo->quota;
+  r.noise0 = mo->noise0; r.noise1 = mo->noise1;
+  r.T = mo->T; r.Ntot = N; r.s0 = mo->s0; r.K = mo->K;
+}
+
 extern "C" int sumo_rollout_steps(sumo_handle_t E, const sumo_rollout* ro, float* actions_dev, float* obs_dev, double* info_dev,
                                   uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
-  if (!E || !ro || !actions_dev || !obs_dev || !info_dev || !done_dev || !ep_r_dev || !ep_dr_dev || !ep_l_dev) FAIL(-1, "bad arguments");
-  if (!ro->learner_params || !ro->opponent_params || !ro->noise0 || !ro->noise1 || !ro->obs || !ro->act || !ro->rew || !ro->val ||
-      !ro->nlp || !ro->onlp || !ro->done || !ro->ep_done || !ro->ep_r || !ro->ep_l)
-    FAIL(-2, "sumo_rollout: missing buffer");
+  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
+  if (int rc = check_launch_args(E, ro, b)) return rc;
+  if (!ro->learner_params || !ro->opponent_params || rollout_buffer_missing(ro)) FAIL(-2, "sumo_rollout: missing buffer");
   int od = 0, ad = 0;
   if (int rc = rollout_scene(E, ro->T, ro->Ntot, ro->env_offset, ro->s0, ro->K, &od, &ad)) return rc;
-  if (ro->ob_dim != od || ro->ac_dim != ad || ro->ac_dim > PT_MAXA) FAIL(-4, "ob_dim %d / ac_dim %d do not match the scene (%d / %d)", ro->ob_dim, ro->ac_dim, od, ad);
+  if (int rc = check_dims(ro->ob_dim, ro->ac_dim, od, ad)) return rc;
   if (ro->npool < 1) FAIL(-7, "npool %d", ro->npool);
   HIPCHK(hipSetDevice(E->device));
   RolloutArgs r;
   memset(&r, 0, sizeof r);
-  r.learner = ro->learner_params; r.opponent = ro->opponent_params; r.opp_idx = ro->opponent_index; r.noise0 = ro->noise0; r.noise1 = ro->noise1;
-  r.obs = ro->obs; r.act = ro->act; r.rew = ro->rew; r.val = ro->val; r.nlp = ro->nlp; r.onlp = ro->onlp; r.done = ro->done;
-  r.ep_done = ro->ep_done; r.ep_r = ro->ep_r; r.ep_l = ro->ep_l; r.alpha = ro->alpha;
-  r.T = ro->T; r.Ntot = ro->Ntot; r.env_offset = ro->env_offset; r.s0 = ro->s0; r.K = ro->K;
-  r.XS = x_stride(ro->ob_dim); r.L = make_layout(ro->ob_dim, ro->ac_dim); r.lds_off = E->L.M;
-  if ((size_t)(2 * r.XS + 4 * PT_HS) * sizeof(float) > (size_t)E->L.msize * sizeof(double))
-    FAIL(-8, "policy scratch (%zu B) does not fit the mass-matrix region (%zu B)", (size_t)(2 * r.XS + 4 * PT_HS) * sizeof(float), (size_t)E->L.msize * sizeof(double));
-  return rollout_launch(E, r, 0, actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev, stream);
+  r.learner = ro->learner_params; r.opponent = ro->opponent_params; r.opp_idx = ro->opponent_index;
+  copy_rollout_fields(r, ro);
+  if (int rc = place_mlp_scratch(E, ro->ob_dim, ro->ac_dim, r)) return rc;
+  return rollout_launch(E, r, 0, b, stream);
 }
 
 extern "C" int sumo_rollout_steps_lstm(sumo_handle_t E, const sumo_rollout_lstm* ro, float* actions_dev, float* obs_dev, double* info_dev,
                                        uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
-  if (!E || !ro || !actions_dev || !obs_dev || !info_dev || !done_dev || !ep_r_dev || !ep_dr_dev || !ep_l_dev) FAIL(-1, "bad arguments");
-  if (!ro->learner || !ro->opponents_dev || !ro->state0 || !ro->state1 || !ro->noise0 || !ro->noise1 || !ro->obs || !ro->act || !ro->rew ||
-      !ro->val || !ro->nlp || !ro->onlp || !ro->done || !ro->ep_done || !ro->ep_r || !ro->ep_l)
-    FAIL(-2, "sumo_rollout_lstm: missing buffer");
+  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
+  if (int rc = check_launch_args(E, ro, b)) return rc;
+  if (!ro->learner || !ro->opponents_dev || !ro->state0 || !ro->state1 || rollout_buffer_missing(ro)) FAIL(-2, "sumo_rollout_lstm: missing buffer");
   int od = 0, ad = 0;
   if (int rc = rollout_scene(E, ro->T, ro->Ntot, ro->env_offset, ro->s0, ro->K, &od, &ad)) return rc;
   const ppo_lstm_net& n = *ro->learner;
-  if (n.ob_dim != od || n.ac_dim != ad || n.ac_dim > PT_MAXA) FAIL(-4, "ob_dim %d / ac_dim %d do not match the scene (%d / %d)", n.ob_dim, n.ac_dim, od, ad);
-  // what the in-wave evaluation is built for: the nets `learn(network='lstm')` trains (policy-zoo LSTM nets carry an observation
-  // filter, an embedding and the other gate order: they go through ppo_lstm_step)
-  if (n.hidden != 128 || n.gate_order != PPO_LSTM_GATES_IFOU || n.emb_w || n.emb_dim != 0 || n.obs_mean || n.obs_invstd)
-    FAIL(-9, "fused recurrent rollout: hidden 128, gate order i,f,o,u, no embedding, no observation filter (got hidden %d, order %d, emb %d)", n.hidden, n.gate_order, n.emb_dim);
+  if (int rc = check_dims(n.ob_dim, n.ac_dim, od, ad)) return rc;
+  if (int rc = check_lstm_shape(n, "rollout")) return rc;
   if (!n.wx || !n.wh || !n.b || !n.head_w || !n.head_b || !n.logstd || !n.vf_w || !n.vf_b) FAIL(-10, "learner net: missing weights");
   if (ro->npool < 1) FAIL(-7, "npool %d", ro->npool);
   if (ro->tile_net_dev && ((ro->env_offset & 15) || (E->N & 15))) FAIL(-11, "a snapshot per 16-env tile needs env_offset (%d) and the env count (%d) to be multiples of 16", ro->env_offset, E->N);
@@ -3897,69 +3975,51 @@ extern "C" int sumo_rollout_steps_lstm(sumo_handle_t E, const sumo_rollout_lstm*
   RolloutArgs r;
   memset(&r, 0, sizeof r);
   r.lnet = n; r.onets = ro->opponents_dev; r.tile_net = ro->tile_net_dev; r.st0 = ro->state0; r.st1 = ro->state1;
-  r.noise0 = ro->noise0; r.noise1 = ro->noise1;
-  r.obs = ro->obs; r.act = ro->act; r.rew = ro->rew; r.val = ro->val; r.nlp = ro->nlp; r.onlp = ro->onlp; r.done = ro->done;
-  r.ep_done = ro->ep_done; r.ep_r = ro->ep_r; r.ep_l = ro->ep_l; r.alpha = ro->alpha;
-  r.T = ro->T; r.Ntot = ro->Ntot; r.env_offset = ro->env_offset; r.s0 = ro->s0; r.K = ro->K;
-  r.XS = (od + 3) & ~3;
-  // between two steps of an env nothing from the mass matrix to the end of the float64 area is live (contact records, Jacobian
-  // pool and row arrays are rebuilt by every forward): the phase's rows go there, 16-byte aligned for the 128-bit LDS reads
-  r.lds_off = (E->L.M + 1) & ~1;
-  const size_t need = (size_t)(2 * r.XS + 7 * 128) * sizeof(float), have = (size_t)(E->L.i_base - r.lds_off) * sizeof(double);
-  if (E->L.ctrl >= E->L.M || E->L.stash >= E->L.M || need > have) FAIL(-8, "policy scratch (%zu B) does not fit the per-step LDS area (%zu B)", need, have);
-  return rollout_launch(E, r, 1, actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev, stream);
+  copy_rollout_fields(r, ro);
+  if (int rc = place_lstm_scratch(E, od, 7, r)) return rc;   // zero row, previous latents [3], new latents [3]
+  return rollout_launch(E, r, 1, b, stream);
 }
 
 extern "C" int sumo_match_steps(sumo_handle_t E, const sumo_match* mo, float* actions_dev, float* obs_dev, double* info_dev,
                                 uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
-  if (!E || !mo || !actions_dev || !obs_dev || !info_dev || !done_dev || !ep_r_dev || !ep_dr_dev || !ep_l_dev) FAIL(-1, "bad arguments");
-  if (!mo->params || !mo->idx0 || !mo->idx1 || !mo->score) FAIL(-2, "sumo_match: missing buffer");
-  if (!mo->noise0 != !mo->noise1) FAIL(-2, "sumo_match: noise0 and noise1 are both given (stochastic play) or both NULL (deterministic)");
+  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
+  if (int rc = check_launch_args(E, mo, b)) return rc;
+  if (!mo->params) FAIL(-2, "sumo_match: missing buffer");
+  if (int rc = check_match_buffers(mo, "sumo_match")) return rc;
   int od = 0, ad = 0;
   if (int rc = rollout_scene(E, mo->T, E->N, 0, mo->s0, mo->K, &od, &ad)) return rc;
-  if (mo->ob_dim != od || mo->ac_dim != ad || mo->ac_dim > PT_MAXA) FAIL(-4, "ob_dim %d / ac_dim %d do not match the scene (%d / %d)", mo->ob_dim, mo->ac_dim, od, ad);
-  if (mo->nsnap < 1) FAIL(-7, "nsnap %d: the snapshot table needs at least one entry", mo->nsnap);
-  if (mo->quota < 0) FAIL(-9, "quota %d", mo->quota);
+  if (int rc = check_dims(mo->ob_dim, mo->ac_dim, od, ad)) return rc;
+  if (int rc = check_match_counts(mo)) return rc;
   HIPCHK(hipSetDevice(E->device));
   RolloutArgs r;
   memset(&r, 0, sizeof r);
-  r.snaps = mo->params; r.idx0 = mo->idx0; r.idx1 = mo->idx1; r.score = mo->score; r.nsnap = mo->nsnap; r.quota = mo->quota;
-  r.noise0 = mo->noise0; r.noise1 = mo->noise1;
-  r.T = mo->T; r.Ntot = E->N; r.s0 = mo->s0; r.K = mo->K;
-  r.XS = x_stride(mo->ob_dim); r.L = make_layout(mo->ob_dim, mo->ac_dim); r.lds_off = E->L.M;
-  if ((size_t)(2 * r.XS + 4 * PT_HS) * sizeof(float) > (size_t)E->L.msize * sizeof(double))
-    FAIL(-8, "policy scratch (%zu B) does not fit the mass-matrix region (%zu B)", (size_t)(2 * r.XS + 4 * PT_HS) * sizeof(float), (size_t)E->L.msize * sizeof(double));
-  return rollout_launch(E, r, 2, actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev, stream);
+  r.snaps = mo->params;
+  copy_match_fields(r, mo, E->N);
+  if (int rc = place_mlp_scratch(E, mo->ob_dim, mo->ac_dim, r)) return rc;
+  return rollout_launch(E, r, 2, b, stream);
 }
 
 extern "C" int sumo_match_steps_lstm(sumo_handle_t E, const sumo_match_lstm* mo, float* actions_dev, float* obs_dev, double* info_dev,
                                      uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
-  if (!E || !mo || !actions_dev || !obs_dev || !info_dev || !done_dev || !ep_r_dev || !ep_dr_dev || !ep_l_dev) FAIL(-1, "bad arguments");
-  if (!mo->proto || !mo->nets_dev || !mo->idx0 || !mo->idx1 || !mo->score) FAIL(-2, "sumo_match_lstm: missing buffer");
+  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
+  if (int rc = check_launch_args(E, mo, b)) return rc;
+  if (!mo->proto || !mo->nets_dev) FAIL(-2, "sumo_match_lstm: missing buffer");
   if (!mo->state0 || !mo->state1) FAIL(-2, "sumo_match_lstm: missing state buffer (state0 / state1)");
-  if (!mo->noise0 != !mo->noise1) FAIL(-2, "sumo_match_lstm: noise0 and noise1 are both given (stochastic play) or both NULL (deterministic)");
+  if (int rc = check_match_buffers(mo, "sumo_match_lstm")) return rc;
   int od = 0, ad = 0;
   if (int rc = rollout_scene(E, mo->T, E->N, 0, mo->s0, mo->K, &od, &ad)) return rc;
   const ppo_lstm_net& n = *mo->proto;
-  if (n.ob_dim != od || n.ac_dim != ad || n.ac_dim > PT_MAXA) FAIL(-4, "ob_dim %d / ac_dim %d do not match the scene (%d / %d)", n.ob_dim, n.ac_dim, od, ad);
-  // the nets sumo_rollout_steps_lstm plays (what `learn(network='lstm')` trains)
-  if (n.hidden != 128 || n.gate_order != PPO_LSTM_GATES_IFOU || n.emb_w || n.emb_dim != 0 || n.obs_mean || n.obs_invstd)
-    FAIL(-9, "fused recurrent matches: hidden 128, gate order i,f,o,u, no embedding, no observation filter (got hidden %d, order %d, emb %d)", n.hidden, n.gate_order, n.emb_dim);
+  if (int rc = check_dims(n.ob_dim, n.ac_dim, od, ad)) return rc;
+  if (int rc = check_lstm_shape(n, "matches")) return rc;   // the nets sumo_rollout_steps_lstm plays
   if (!n.wx || !n.wh || !n.b || !n.head_w || !n.head_b || !n.logstd) FAIL(-10, "prototype net: missing weights");
-  if (mo->nsnap < 1) FAIL(-7, "nsnap %d: the snapshot table needs at least one entry", mo->nsnap);
-  if (mo->quota < 0) FAIL(-9, "quota %d", mo->quota);
+  if (int rc = check_match_counts(mo)) return rc;
   HIPCHK(hipSetDevice(E->device));
   RolloutArgs r;
   memset(&r, 0, sizeof r);
   r.lnet = n; r.onets = mo->nets_dev; r.st0 = mo->state0; r.st1 = mo->state1;
-  r.idx0 = mo->idx0; r.idx1 = mo->idx1; r.score = mo->score; r.nsnap = mo->nsnap; r.quota = mo->quota;
-  r.noise0 = mo->noise0; r.noise1 = mo->noise1;
-  r.T = mo->T; r.Ntot = E->N; r.s0 = mo->s0; r.K = mo->K;
-  r.XS = (od + 3) & ~3;
-  r.lds_off = (E->L.M + 1) & ~1;   // where the LSTM rollout's rows go (see sumo_rollout_steps_lstm)
-  const size_t need = (size_t)(2 * r.XS + 2 * 128) * sizeof(float), have = (size_t)(E->L.i_base - r.lds_off) * sizeof(double);
-  if (E->L.ctrl >= E->L.M || E->L.stash >= E->L.M || need > have) FAIL(-8, "policy scratch (%zu B) does not fit the per-step LDS area (%zu B)", need, have);
-  return rollout_launch(E, r, 3, actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev, stream);
+  copy_match_fields(r, mo, E->N);
+  if (int rc = place_lstm_scratch(E, od, 2, r)) return rc;   // previous latent, new latent
+  return rollout_launch(E, r, 3, b, stream);
 }
 
 #ifdef SUMO_POLICY_PROBE

@@ -36,74 +36,52 @@ def param_count(ob_dim, ac_dim):
     return sum(int(np.prod(s)) for s in policies.param_shapes(ob_dim, ac_dim))
 
 
+def _source_vector(src, check_model, dict_hint, from_list, P, policy_name):
+    """The source-type ladder behind :func:`snapshot_vector` / :func:`lstm_snapshot_vector`: a checkpoint path is loaded into
+    its array list, a model yields its flat ``params`` (after ``check_model(src)``, which raises on the wrong kind or shape), a
+    tensor becomes an array, dicts are refused, an array list goes through ``from_list(list, label)``, anything else must be a
+    flat vector of ``P`` entries."""
+    label = None
+    if isinstance(src, (str, os.PathLike)):
+        import joblib
+        label = str(src)
+        src = joblib.load(os.path.expanduser(str(src)))            # only files written by the models' save()
+    if hasattr(src, "params") and hasattr(src, "spec"):            # PPOModel / ActorCriticModel / LstmPPOModel
+        check_model(src)
+        return src.params.detach().cpu().numpy().astype(np.float32).reshape(-1)
+    if hasattr(src, "detach"):                                     # torch tensor
+        src = src.detach().cpu().numpy()
+    if isinstance(src, dict):
+        raise ValueError("dict checkpoints are not supported here; load them into %s first" % dict_hint)
+    if isinstance(src, (list, tuple)):
+        return from_list(src, label or "checkpoint")
+    v = np.ascontiguousarray(src, np.float32).reshape(-1)
+    if v.size != P:
+        raise ValueError("snapshot has %d parameters, the %s %d" % (v.size, policy_name, P))
+    return v
+
+
 def snapshot_vector(spec, src):
     """Flat float32 parameter vector (numpy) of an MLP(64,64) policy of ``spec`` from a ``PPOModel`` / ``ActorCriticModel``, a
     flat vector, the 13-array list of a checkpoint (model.py:153-177) or a checkpoint path written by ``PPOModel.save``.
     LSTM models and checkpoints are refused here: they play in an :class:`LstmSnapshotTable`."""
     D, A = spec.ob_dim, spec.ac_dim
-    label = None
     if getattr(src, "recurrent", False):
-        raise ValueError("recurrent (LSTM) models cannot play fused matches: only MLP(64,64) policies are supported")
-    if isinstance(src, (str, os.PathLike)):
-        import joblib
-        label = str(src)
-        src = joblib.load(os.path.expanduser(str(src)))            # only files written by PPOModel.save()
-    if hasattr(src, "params") and hasattr(src, "spec"):            # PPOModel / ActorCriticModel
-        if (src.spec.ob_dim, src.spec.ac_dim) != (D, A):
-            raise ValueError("model's policy (%d, %d) does not match the table's (%d, %d)" % (src.spec.ob_dim, src.spec.ac_dim, D, A))
-        return src.params.detach().cpu().numpy().astype(np.float32).reshape(-1)
-    if hasattr(src, "detach"):                                     # torch tensor
-        src = src.detach().cpu().numpy()
-    if isinstance(src, dict):
-        raise ValueError("dict checkpoints are not supported here; load them into a PPOModel first")
-    if isinstance(src, (list, tuple)):
-        shapes = policies.param_shapes(D, A)
-        lshapes = policies.lstm_param_shapes(D, A)
-        got = [tuple(np.shape(p)) for p in src]
-        if len(src) == len(lshapes) and got == [tuple(s) for s in lshapes]:
-            raise ValueError("%s is an LSTM checkpoint: recurrent matches are not supported (MLP(64,64) checkpoints only)"
-                             % (label or "checkpoint"))
-        if len(src) != len(shapes) or got != [tuple(s) for s in shapes]:
-            raise ValueError("%s does not match the MLP(64,64) policy of ob_dim %d / ac_dim %d" % (label or "checkpoint", D, A))
-        return policies.flatten_params(list(src))
-    v = np.ascontiguousarray(src, np.float32).reshape(-1)
-    P = param_count(D, A)
-    if v.size != P:
-        raise ValueError("snapshot has %d parameters, the policy %d" % (v.size, P))
-    return v
+        raise ValueError("recurrent (LSTM) models do not play in a SnapshotTable (MLP(64,64) policies): use LstmSnapshotTable")
 
+    def check_model(m):
+        if (m.spec.ob_dim, m.spec.ac_dim) != (D, A):
+            raise ValueError("model's policy (%d, %d) does not match the table's (%d, %d)" % (m.spec.ob_dim, m.spec.ac_dim, D, A))
 
-class SnapshotTable(object):
-    """Device table ``params [capacity][P]`` of frozen MLP(64,64) policies in checkpoint order (the layout of sumo_ppo.h)."""
+    def from_list(plist, name):
+        got = [tuple(np.shape(p)) for p in plist]
+        if got == [tuple(x) for x in policies.lstm_param_shapes(D, A)]:
+            raise ValueError("%s is an LSTM checkpoint: it plays in an LstmSnapshotTable, not in a SnapshotTable" % name)
+        if got != [tuple(x) for x in policies.param_shapes(D, A)]:
+            raise ValueError("%s does not match the MLP(64,64) policy of ob_dim %d / ac_dim %d" % (name, D, A))
+        return policies.flatten_params(list(plist))
 
-    def __init__(self, spec, capacity, device=0):
-        import torch
-        self.spec = spec
-        self.capacity = int(capacity)
-        if self.capacity < 1:
-            raise ValueError("capacity must be >= 1")
-        self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-        self.P = param_count(spec.ob_dim, spec.ac_dim)
-        self.params = torch.zeros((self.capacity, self.P), dtype=torch.float32, device=self.device)
-        self.filled = np.zeros(self.capacity, bool)
-        self.labels = [None] * self.capacity
-
-    def set(self, k, src, label=None):
-        """Fill row ``k`` (see :func:`snapshot_vector` for what ``src`` may be)."""
-        import torch
-        if not 0 <= k < self.capacity:
-            raise IndexError("row %d outside the table of %d" % (k, self.capacity))
-        v = snapshot_vector(self.spec, src)
-        self.params[k].copy_(torch.from_numpy(v).to(self.device))
-        self.filled[k] = True
-        self.labels[k] = label if label is not None else (str(src) if isinstance(src, (str, os.PathLike)) else None)
-
-    @classmethod
-    def from_checkpoints(cls, spec, paths, device=0):
-        t = cls(spec, len(paths), device)
-        for k, p in enumerate(paths):
-            t.set(k, p)
-        return t
+    return _source_vector(src, check_model, "a PPOModel", from_list, param_count(D, A), "policy")
 
 
 def checkpoint_kind(path):
@@ -128,78 +106,62 @@ def _list_kind(plist, label):
     raise ValueError("%s is neither an MLP(64,64) nor an LSTM checkpoint" % label)
 
 
+def _lstm_param_count(spec):
+    return sum(int(np.prod(x)) for x in policies.lstm_param_shapes(spec.ob_dim, spec.ac_dim, spec.nlstm))
+
+
 def lstm_snapshot_vector(spec, src):
     """Flat float32 parameter vector (numpy) of an LSTM policy of ``spec`` (``LstmSpec``) from an ``LstmPPOModel``, a flat vector,
     the 8-array list of ``lstm_param_shapes`` or a checkpoint path written by ``LstmPPOModel.save``.  MLP models and checkpoints,
     and LSTM policies of another width, are refused."""
     D, A, H = spec.ob_dim, spec.ac_dim, spec.nlstm
-    label = None
-    if isinstance(src, (str, os.PathLike)):
-        import joblib
-        label = str(src)
-        src = joblib.load(os.path.expanduser(str(src)))            # only files written by LstmPPOModel.save()
-    if hasattr(src, "params") and hasattr(src, "spec"):            # LstmPPOModel (or an MLP model: refused)
-        if not getattr(src, "recurrent", False):
+
+    def check_model(m):
+        if not getattr(m, "recurrent", False):
             raise ValueError("MLP models cannot play in an LSTM snapshot table: use SnapshotTable")
-        got = (src.spec.ob_dim, src.spec.ac_dim, src.spec.nlstm)
+        got = (m.spec.ob_dim, m.spec.ac_dim, m.spec.nlstm)
         if got != (D, A, H):
             raise ValueError("model's policy (%d, %d, LSTM(%d)) does not match the table's (%d, %d, LSTM(%d))" % (got + (D, A, H)))
-        return src.params.detach().cpu().numpy().astype(np.float32).reshape(-1)
-    if hasattr(src, "detach"):                                     # torch tensor
-        src = src.detach().cpu().numpy()
-    if isinstance(src, dict):
-        raise ValueError("dict checkpoints are not supported here; load them into an LstmPPOModel first")
-    if isinstance(src, (list, tuple)):
-        name = label or "checkpoint"
+
+    def from_list(plist, name):
         try:
-            kind, h = _list_kind(src, name)
+            kind, h = _list_kind(plist, name)
         except ValueError:
             kind, h = None, None
         if kind == "mlp":
             raise ValueError("%s is an MLP(64,64) checkpoint: it plays in a SnapshotTable, not in an LSTM table" % name)
         if kind == "lstm" and h != H:
             raise ValueError("%s is an LSTM(%d) checkpoint, the table holds LSTM(%d) policies" % (name, h, H))
-        shapes = [tuple(x) for x in policies.lstm_param_shapes(D, A, H)]
-        if [tuple(np.shape(p)) for p in src] != shapes:
+        if [tuple(np.shape(p)) for p in plist] != [tuple(x) for x in policies.lstm_param_shapes(D, A, H)]:
             raise ValueError("%s does not match the LSTM(%d) policy of ob_dim %d / ac_dim %d" % (name, H, D, A))
-        return np.concatenate([np.asarray(p, np.float32).ravel() for p in src])
-    v = np.ascontiguousarray(src, np.float32).reshape(-1)
-    P = sum(int(np.prod(x)) for x in policies.lstm_param_shapes(D, A, H))
-    if v.size != P:
-        raise ValueError("snapshot has %d parameters, the LSTM policy %d" % (v.size, P))
-    return v
+        return np.concatenate([np.asarray(p, np.float32).ravel() for p in plist])
+
+    return _source_vector(src, check_model, "an LstmPPOModel", from_list, _lstm_param_count(spec), "LSTM policy")
 
 
-class LstmSnapshotTable(object):
-    """Device table ``params [capacity][P]`` of frozen LSTM policies (``lstm_param_shapes`` order, what ``LstmPPOModel.save``
-    writes) plus the device array of their ``ppo_lstm_net`` structs (``nets_dev``) and a host prototype (``proto``)."""
-    recurrent = True
+class _SnapshotTableBase(object):
+    """Device table ``params [capacity][P]`` of frozen policies of one ``spec``, with the rows' fill state and labels.  A
+    subclass names its parameter count (``param_count_of``) and its vector loader (``vector_of``)."""
+    recurrent = False
 
     def __init__(self, spec, capacity, device=0):
         import torch
-        from . import ppo_capi
-        from .opponent_pool import fill_lstm_net
         self.spec = spec
         self.capacity = int(capacity)
         if self.capacity < 1:
             raise ValueError("capacity must be >= 1")
         self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-        self.P = sum(int(np.prod(x)) for x in policies.lstm_param_shapes(spec.ob_dim, spec.ac_dim, spec.nlstm))
+        self.P = self.param_count_of(spec)
         self.params = torch.zeros((self.capacity, self.P), dtype=torch.float32, device=self.device)
-        self.nets = (ppo_capi.LstmNet * self.capacity)()
-        for k in range(self.capacity):
-            fill_lstm_net(self.nets[k], self.params[k].data_ptr(), spec)
-        self.proto = fill_lstm_net(ppo_capi.LstmNet(), self.params[0].data_ptr(), spec)
-        self.nets_dev = torch.from_numpy(np.frombuffer(bytes(self.nets), dtype=np.uint8).copy()).to(self.device)
         self.filled = np.zeros(self.capacity, bool)
         self.labels = [None] * self.capacity
 
     def set(self, k, src, label=None):
-        """Fill row ``k`` (see :func:`lstm_snapshot_vector` for what ``src`` may be)."""
+        """Fill row ``k`` (see the table's ``vector_of`` for what ``src`` may be)."""
         import torch
         if not 0 <= k < self.capacity:
             raise IndexError("row %d outside the table of %d" % (k, self.capacity))
-        v = lstm_snapshot_vector(self.spec, src)
+        v = self.vector_of(self.spec, src)
         self.params[k].copy_(torch.from_numpy(v).to(self.device))
         self.filled[k] = True
         self.labels[k] = label if label is not None else (str(src) if isinstance(src, (str, os.PathLike)) else None)
@@ -210,6 +172,33 @@ class LstmSnapshotTable(object):
         for k, p in enumerate(paths):
             t.set(k, p)
         return t
+
+
+class SnapshotTable(_SnapshotTableBase):
+    """Device table ``params [capacity][P]`` of frozen MLP(64,64) policies in checkpoint order (the layout of sumo_ppo.h); rows
+    are filled from what :func:`snapshot_vector` accepts."""
+    param_count_of = staticmethod(lambda spec: param_count(spec.ob_dim, spec.ac_dim))
+    vector_of = staticmethod(snapshot_vector)
+
+
+class LstmSnapshotTable(_SnapshotTableBase):
+    """Device table ``params [capacity][P]`` of frozen LSTM policies (``lstm_param_shapes`` order, what ``LstmPPOModel.save``
+    writes; rows are filled from what :func:`lstm_snapshot_vector` accepts) plus the device array of their ``ppo_lstm_net``
+    structs (``nets_dev``) and a host prototype (``proto``)."""
+    recurrent = True
+    param_count_of = staticmethod(_lstm_param_count)
+    vector_of = staticmethod(lstm_snapshot_vector)
+
+    def __init__(self, spec, capacity, device=0):
+        from . import ppo_capi
+        from .opponent_pool import fill_lstm_net
+        super(LstmSnapshotTable, self).__init__(spec, capacity, device)
+        import torch
+        self.nets = (ppo_capi.LstmNet * self.capacity)()
+        for k in range(self.capacity):
+            fill_lstm_net(self.nets[k], self.params[k].data_ptr(), spec)
+        self.proto = fill_lstm_net(ppo_capi.LstmNet(), self.params[0].data_ptr(), spec)
+        self.nets_dev = torch.from_numpy(np.frombuffer(bytes(self.nets), dtype=np.uint8).copy()).to(self.device)
 
 
 def checkpoint_dir(path):
@@ -279,19 +268,15 @@ def _check_env(env, table):
         raise ValueError("matches run on the fused launch, which refuses cfrc_mode 'rne_post'")
 
 
-def match_steps_fused(env, table, idx0, idx1, score, quota, K, noise=None):
-    """K match steps of every env in one ``sumo_match_steps`` launch per env group.  idx0 / idx1 int32 CUDA tensors [N],
-    score int32 CUDA [N][3] (updated in place), noise None (deterministic) or a pair of float32 CUDA [K][N][A] tensors.  Raises
-    if the launch was cut short (``rollout_status``)."""
-    from . import capi
-    _check_env(env, table)
-    A = table.spec.ac_dim
+def _fused_groups(env, entry, struct, fill, idx0, idx1, score, quota, K, noise):
+    """The per-group loop of the two fused match launches: a ``struct`` (capi.Match / capi.MatchLstm) whose own fields
+    ``fill(mo, sl)`` sets and whose shared fields (indices, window, quota, noise, score) are set here, passed to the engine's
+    ``entry`` method with the group's env-side pointers; raises if the launch was cut short (``rollout_status``)."""
     for g in range(env.groups):
         sl = env._gs(g)
-        mo = capi.Match()
-        mo.params = table.params.data_ptr()
+        mo = struct()
+        fill(mo, sl)
         mo.idx0, mo.idx1 = idx0[sl].data_ptr(), idx1[sl].data_ptr()
-        mo.nsnap, mo.ob_dim, mo.ac_dim = table.capacity, table.spec.ob_dim, A
         mo.T, mo.s0, mo.K, mo.quota = int(K), 0, int(K), int(quota)
         keep = None
         if noise is not None:
@@ -299,10 +284,23 @@ def match_steps_fused(env, table, idx0, idx1, score, quota, K, noise=None):
             mo.noise0, mo.noise1 = keep[0].data_ptr(), keep[1].data_ptr()
         mo.score = score[sl].data_ptr()
         E = env.engines[g]
-        E.match_steps(mo, env.act_dev[sl].data_ptr(), env.obs_dev[sl].data_ptr(), env.info_dev[sl].data_ptr(), env.done_dev[sl].data_ptr(),
-                      env.ep_r_dev[sl].data_ptr(), env.ep_dr_dev[sl].data_ptr(), env.ep_l_dev[sl].data_ptr(), stream=env._stream())
+        getattr(E, entry)(mo, *env.env_ptrs(g), stream=env._stream())
         E.rollout_status()
         del keep
+
+
+def match_steps_fused(env, table, idx0, idx1, score, quota, K, noise=None):
+    """K match steps of every env in one ``sumo_match_steps`` launch per env group.  idx0 / idx1 int32 CUDA tensors [N],
+    score int32 CUDA [N][3] (updated in place), noise None (deterministic) or a pair of float32 CUDA [K][N][A] tensors.  Raises
+    if the launch was cut short (``rollout_status``)."""
+    from . import capi
+    _check_env(env, table)
+
+    def fill(mo, sl):
+        mo.params = table.params.data_ptr()
+        mo.nsnap, mo.ob_dim, mo.ac_dim = table.capacity, table.spec.ob_dim, table.spec.ac_dim
+
+    _fused_groups(env, "match_steps", capi.Match, fill, idx0, idx1, score, quota, K, noise)
 
 
 def _runs(idx):
@@ -313,33 +311,45 @@ def _runs(idx):
     return [(int(s), int(e), int(idx[s])) for s, e in zip(starts, ends)]
 
 
+def _stepwise(env, table, idx0, idx1, score, quota, K, noise, forward, masked):
+    """The step-by-step loop of both kinds: per step and side, ``forward(k, side, rows, noise rows or None, action rows, mask
+    rows or None)`` for every run ``rows = slice(s, e)`` of envs that share snapshot ``k``, then ``step_device`` and the score
+    update.  ``masked``: the previous step's done flags of each side are passed as float32 masks.  idx0 / idx1 are host arrays."""
+    import torch
+    idx0, idx1 = np.asarray(idx0, np.int64), np.asarray(idx1, np.int64)
+    if min(idx0.min(), idx1.min()) < 0 or max(idx0.max(), idx1.max()) >= table.capacity:
+        raise ValueError("snapshot index outside [0, %d)" % table.capacity)
+    A, N = table.spec.ac_dim, env.num_envs
+    acts = env.act_dev                          # the env's action buffer receives both actions, as in the fused launch
+    act = [torch.empty((N, A), dtype=torch.float32, device=env.device) for _ in range(2)]
+    runs = [_runs(idx0), _runs(idx1)]
+    for t in range(int(K)):
+        masks = [env.done_dev[:, side].to(torch.float32) if masked else None for side in range(2)]
+        for side in range(2):
+            for s, e, k in runs[side]:
+                rows = slice(s, e)
+                forward(k, side, rows, None if noise is None else noise[side][t, rows], act[side][rows],
+                        masks[side][rows] if masked else None)
+            acts[:, side, :A] = act[side]
+        _, info, done, _, _, _ = env.step_device(acts)
+        _score_step(score, info, done, quota)
+
+
 def match_steps_stepwise(env, table, idx0, idx1, score, quota, K, noise=None):
     """The same K steps on the step-by-step path: per step and side one ``ppo_forward`` launch (``PPOModel.step``'s kernel) for
     every run of envs that share a snapshot, then ``step_device`` and the score update.  idx0 / idx1 are host arrays."""
     import torch
     from . import ppo_capi
     _check_env(env, table)
-    idx0, idx1 = np.asarray(idx0, np.int64), np.asarray(idx1, np.int64)
-    if min(idx0.min(), idx1.min()) < 0 or max(idx0.max(), idx1.max()) >= table.capacity:
-        raise ValueError("snapshot index outside [0, %d)" % table.capacity)
     D, A = table.spec.ob_dim, table.spec.ac_dim
-    N = env.num_envs
-    L = ppo_capi.lib()
-    st = env._stream()
-    acts = env.act_dev                          # the env's action buffer receives both actions, as in the fused launch
-    act = [torch.empty((N, A), dtype=torch.float32, device=env.device) for _ in range(2)]
-    nlp = torch.empty(N, dtype=torch.float32, device=env.device)
-    runs = [_runs(idx0), _runs(idx1)]
-    obs = env.obs_dev
-    for t in range(int(K)):
-        for side in range(2):
-            for s, e, k in runs[side]:
-                nz = None if noise is None else noise[side][t, s:e]
-                ppo_capi.chk(L.ppo_forward(table.params[k].data_ptr(), obs[s:e, side].data_ptr(), e - s, obs.stride(0), D, A, ppo_capi.FWD_PI,
-                                           ppo_capi.ptr(nz), None, act[side][s:e].data_ptr(), nlp[s:e].data_ptr(), None, None, st))
-            acts[:, side, :A] = act[side]
-        obs, info, done, _, _, _ = env.step_device(acts)
-        _score_step(score, info, done, quota)
+    L, st, obs = ppo_capi.lib(), env._stream(), env.obs_dev
+    nlp = torch.empty(env.num_envs, dtype=torch.float32, device=env.device)
+
+    def forward(k, side, rows, nz, out, _mask):
+        ppo_capi.chk(L.ppo_forward(table.params[k].data_ptr(), obs[rows, side].data_ptr(), rows.stop - rows.start, obs.stride(0), D, A,
+                                   ppo_capi.FWD_PI, ppo_capi.ptr(nz), None, out.data_ptr(), nlp[rows].data_ptr(), None, None, st))
+
+    _stepwise(env, table, idx0, idx1, score, quota, K, noise, forward, masked=False)
 
 
 def _check_lstm(table, states, N):
@@ -357,59 +367,42 @@ def match_steps_fused_lstm(env, table, idx0, idx1, states, score, quota, K, nois
     _check_lstm(table, states, env.num_envs)
     if table.spec.nlstm != 128:
         raise ValueError("the fused match launch plays LSTM(128) policies only (got LSTM(%d)): use fused=False" % table.spec.nlstm)
-    for g in range(env.groups):
-        sl = env._gs(g)
-        mo = capi.MatchLstm()
+
+    def fill(mo, sl):
         mo.proto = C.addressof(table.proto)
         mo.nets_dev = table.nets_dev.data_ptr()
-        mo.idx0, mo.idx1 = idx0[sl].data_ptr(), idx1[sl].data_ptr()
         mo.nsnap = table.capacity
         mo.state0, mo.state1 = states[0][sl].data_ptr(), states[1][sl].data_ptr()
-        mo.T, mo.s0, mo.K, mo.quota = int(K), 0, int(K), int(quota)
-        keep = None
-        if noise is not None:
-            keep = [n[:, sl].contiguous() if env.groups > 1 else n for n in noise]
-            mo.noise0, mo.noise1 = keep[0].data_ptr(), keep[1].data_ptr()
-        mo.score = score[sl].data_ptr()
-        E = env.engines[g]
-        E.match_steps_lstm(mo, env.act_dev[sl].data_ptr(), env.obs_dev[sl].data_ptr(), env.info_dev[sl].data_ptr(),
-                           env.done_dev[sl].data_ptr(), env.ep_r_dev[sl].data_ptr(), env.ep_dr_dev[sl].data_ptr(),
-                           env.ep_l_dev[sl].data_ptr(), stream=env._stream())
-        E.rollout_status()
-        del keep
+
+    _fused_groups(env, "match_steps_lstm", capi.MatchLstm, fill, idx0, idx1, score, quota, K, noise)
 
 
 def match_steps_stepwise_lstm(env, table, idx0, idx1, states, score, quota, K, noise=None):
     """The same K steps of an :class:`LstmSnapshotTable` step by step: per step and side one ``ppo_lstm_step`` launch (the kernel
     ``LstmPPOModel.step`` runs) for every run of envs that share a snapshot, masked by that side's done flags of the previous step,
     then ``step_device`` and the score update.  idx0 / idx1 are host arrays; any LSTM width the step kernel is built for."""
-    import torch
     from . import ppo_capi
     _check_env(env, table)
     _check_lstm(table, states, env.num_envs)
-    idx0, idx1 = np.asarray(idx0, np.int64), np.asarray(idx1, np.int64)
-    if min(idx0.min(), idx1.min()) < 0 or max(idx0.max(), idx1.max()) >= table.capacity:
-        raise ValueError("snapshot index outside [0, %d)" % table.capacity)
-    A, H = table.spec.ac_dim, table.spec.nlstm
-    N = env.num_envs
-    L = ppo_capi.lib()
-    st = env._stream()
-    acts = env.act_dev
-    act = [torch.empty((N, A), dtype=torch.float32, device=env.device) for _ in range(2)]
-    runs = [_runs(idx0), _runs(idx1)]
-    obs = env.obs_dev
-    for t in range(int(K)):
-        masks = [env.done_dev[:, side].to(torch.float32) for side in range(2)]   # done flags of the previous step = the masks M
-        for side in range(2):
-            S = states[side]
-            for s, e, k in runs[side]:
-                nz = None if noise is None else noise[side][t, s:e]
-                ppo_capi.chk(L.ppo_lstm_step(C.byref(table.nets[k]), obs[s:e, side].data_ptr(), e - s, obs.stride(0), masks[side][s:e].data_ptr(),
-                                             S[s:e].data_ptr(), S[s:e].data_ptr() + 4 * H, 2 * H, ppo_capi.ptr(nz), None,
-                                             act[side][s:e].data_ptr(), None, None, None, st))
-            acts[:, side, :A] = act[side]
-        obs, info, done, _, _, _ = env.step_device(acts)
-        _score_step(score, info, done, quota)
+    H = table.spec.nlstm
+    L, st, obs = ppo_capi.lib(), env._stream(), env.obs_dev
+
+    def forward(k, side, rows, nz, out, mask):
+        S = states[side][rows]
+        ppo_capi.chk(L.ppo_lstm_step(C.byref(table.nets[k]), obs[rows, side].data_ptr(), rows.stop - rows.start, obs.stride(0),
+                                     mask.data_ptr(), S.data_ptr(), S.data_ptr() + 4 * H, 2 * H, ppo_capi.ptr(nz), None,
+                                     out.data_ptr(), None, None, None, st))
+
+    _stepwise(env, table, idx0, idx1, score, quota, K, noise, forward, masked=True)
+
+
+def match_steps(env, table, idx0, idx1, states, score, quota, K, noise=None, fused=True):
+    """K match steps of either table kind on either path: ``states`` is the pair of recurrent state tensors of an
+    :class:`LstmSnapshotTable` (ignored for MLP tables); idx0 / idx1 are CUDA tensors (fused) or host arrays (step by step)."""
+    if getattr(table, "recurrent", False):
+        (match_steps_fused_lstm if fused else match_steps_stepwise_lstm)(env, table, idx0, idx1, states, score, quota, K, noise)
+    else:
+        (match_steps_fused if fused else match_steps_stepwise)(env, table, idx0, idx1, score, quota, K, noise)
 
 
 def _score_step(score, info, done, quota):
@@ -464,19 +457,14 @@ def play_matches(env, table, pairs, rounds_per_env, envs_per_pair, deterministic
             env.seeds = np.uint64(seed) + np.uint64(bn * N) + np.arange(N, dtype=np.uint64)
             env._needs_seed = True
             env.reset_device()
+            states = None
             if recurrent:                     # every match-up starts from the zero state (LstmPPOModel.initial_state)
                 states = tuple(torch.zeros((N, 2 * table.spec.nlstm), dtype=torch.float32, device=env.device) for _ in range(2))
             launches = 0
             while True:
                 noise = None if deterministic else tuple(torch.randn((chunk, N, A), generator=gen, device=env.device) for _ in range(2))
-                if recurrent and fused:
-                    match_steps_fused_lstm(env, table, idx0, idx1, states, score, rounds_per_env, chunk, noise)
-                elif recurrent:
-                    match_steps_stepwise_lstm(env, table, idx0_h, idx1_h, states, score, rounds_per_env, chunk, noise)
-                elif fused:
-                    match_steps_fused(env, table, idx0, idx1, score, rounds_per_env, chunk, noise)
-                else:
-                    match_steps_stepwise(env, table, idx0_h, idx1_h, score, rounds_per_env, chunk, noise)
+                match_steps(env, table, idx0 if fused else idx0_h, idx1 if fused else idx1_h, states, score, rounds_per_env, chunk, noise,
+                            fused=fused)
                 launches += 1
                 if not bool((score.sum(1)[act_t] < rounds_per_env).any()):
                     break

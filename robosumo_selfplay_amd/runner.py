@@ -222,39 +222,49 @@ class Runner(AbstractEnvRunner):
         return (sp0.nlstm == sp1.nlstm == 128 and sp0.ob_dim == sp1.ob_dim == self.ob_dim and sp0.ac_dim == sp1.ac_dim
                 and env.act_dev.shape[2] == sp0.ac_dim and env.obs_dev.stride(2) == 1)
 
-    def _steps_fused_lstm(self, B, s0, K, alpha):
-        """``_steps_fused`` for recurrent policies: one ``sumo_rollout_steps_lstm`` launch per env group; the recurrent states
-        ``self.states`` are advanced in place.  Same numbers as the step-by-step recurrent branch of ``_step_group``."""
-        import ctypes as C
-        from . import capi
-        from .opponent_pool import LstmOpponentPool
-        t = self._t
-        env = self.env
-        m0, m1 = self.models
+    def _fused_groups(self, B, s0, K, alpha, ro_type, draw, fill, launch):
+        """The per-group loop of the two fused rollouts.  On group g's stream: the group's noise pair, drawn by ``draw(n)`` for the
+        whole buffer when its first step is written and cached as ``B[("noise", first env)]``; a ``ro_type`` launch struct whose
+        own fields ``fill(ro, sl)`` sets and whose shared fields (window, noise, rollout buffers) are set here; ``launch(g, ro)``."""
+        t, env = self._t, self.env
         G = getattr(env, "groups", 1)
         streams = self._group_streams() if G > 1 else [None]
-        A, T, N = m0.spec.ac_dim, B["T"], self.nenv
         for g in range(G):
             sl = env._gs(g)
-            n = sl.stop - sl.start
             ctx = t.cuda.stream(streams[g]) if streams[g] is not None else _nullctx()
             with ctx:
                 key = ("noise", sl.start)
                 if s0 == 0 or key not in B:
-                    B[key] = (self._draw_steps(m0.gen, T, n, A), self._draw_steps(m1.gen, T, n, A))
-                ro = capi.RolloutLstm()
-                ro.learner = C.addressof(m0._net)
-                if isinstance(m1, LstmOpponentPool):
-                    ro.opponents_dev, ro.tile_net_dev, ro.npool = m1._nets_dev.data_ptr(), m1.tile_net.data_ptr(), m1.capacity
-                else:
-                    ro.opponents_dev, ro.tile_net_dev, ro.npool = m1.net_dev().data_ptr(), None, 1
-                ro.state0, ro.state1 = self.states[0][sl].data_ptr(), self.states[1][sl].data_ptr()
-                ro.T, ro.Ntot, ro.env_offset, ro.s0, ro.K, ro.alpha = T, N, sl.start, int(s0), int(K), float(alpha)
+                    B[key] = draw(sl.stop - sl.start)
+                ro = ro_type()
+                fill(ro, sl)
+                ro.T, ro.Ntot, ro.env_offset, ro.s0, ro.K, ro.alpha = B["T"], self.nenv, sl.start, int(s0), int(K), float(alpha)
                 ro.noise0, ro.noise1 = B[key][0].data_ptr(), B[key][1].data_ptr()
                 for f in ("obs", "act", "rew", "val", "nlp", "onlp", "done", "ep_done", "ep_r", "ep_l"):
                     setattr(ro, f, B[f].data_ptr())
-                env.rollout_steps_lstm_group(g, ro)
+                launch(g, ro)
         self.obs, self.dones = env.obs_dev, env.done_dev
+
+    def _steps_fused_lstm(self, B, s0, K, alpha):
+        """``_steps_fused`` for recurrent policies: one ``sumo_rollout_steps_lstm`` launch per env group; the recurrent states
+        ``self.states`` are advanced in place.  Same numbers as the step-by-step recurrent branch of ``_step_group``: the noise is
+        drawn step by step (``_draw_steps``), as that branch consumes the generators."""
+        import ctypes as C
+        from . import capi
+        from .opponent_pool import LstmOpponentPool
+        m0, m1 = self.models
+        A, T = m0.spec.ac_dim, B["T"]
+
+        def fill(ro, sl):
+            ro.learner = C.addressof(m0._net)
+            if isinstance(m1, LstmOpponentPool):
+                ro.opponents_dev, ro.tile_net_dev, ro.npool = m1._nets_dev.data_ptr(), m1.tile_net.data_ptr(), m1.capacity
+            else:
+                ro.opponents_dev, ro.tile_net_dev, ro.npool = m1.net_dev().data_ptr(), None, 1
+            ro.state0, ro.state1 = self.states[0][sl].data_ptr(), self.states[1][sl].data_ptr()
+
+        self._fused_groups(B, s0, K, alpha, capi.RolloutLstm, lambda n: (self._draw_steps(m0.gen, T, n, A), self._draw_steps(m1.gen, T, n, A)),
+                           fill, self.env.rollout_steps_lstm_group)
 
     def fused_ok(self):
         """The fused rollout launch applies to device mode with two plain MLP policies of the env's own observation / action shape."""
@@ -274,33 +284,23 @@ class Runner(AbstractEnvRunner):
         draws as the step-by-step path, hence the same rollout bit for bit."""
         from . import capi
         t = self._t
-        env = self.env
         learner, opp = self.models[0].act_model, self.models[1].act_model
-        G = getattr(env, "groups", 1)
-        streams = self._group_streams() if G > 1 else [None]
         pool = self.opponent_pool
-        D, A, T, N = learner.spec.ob_dim, learner.spec.ac_dim, B["T"], self.nenv
-        for g in range(G):
-            sl = env._gs(g)
-            n = sl.stop - sl.start
-            ctx = t.cuda.stream(streams[g]) if streams[g] is not None else _nullctx()
-            with ctx:
-                key = ("noise", sl.start)
-                if s0 == 0 or key not in B:
-                    B[key] = (t.randn((T, n, A), generator=learner.gen, device=self.device, dtype=t.float32),
-                              t.randn((T, n, A), generator=opp.gen, device=self.device, dtype=t.float32))
-                ro = capi.Rollout()
-                ro.learner_params = learner.params.data_ptr()
-                if pool is None:
-                    ro.opponent_params, ro.opponent_index, ro.npool = opp.params.data_ptr(), None, 1
-                else:
-                    ro.opponent_params, ro.opponent_index, ro.npool = pool.params.data_ptr(), pool.index[sl].data_ptr(), pool.capacity
-                ro.ob_dim, ro.ac_dim, ro.T, ro.Ntot, ro.env_offset, ro.s0, ro.K, ro.alpha = D, A, T, N, sl.start, int(s0), int(K), float(alpha)
-                ro.noise0, ro.noise1 = B[key][0].data_ptr(), B[key][1].data_ptr()
-                for f in ("obs", "act", "rew", "val", "nlp", "onlp", "done", "ep_done", "ep_r", "ep_l"):
-                    setattr(ro, f, B[f].data_ptr())
-                env.rollout_steps_group(g, ro)
-        self.obs, self.dones = env.obs_dev, env.done_dev
+        D, A, T = learner.spec.ob_dim, learner.spec.ac_dim, B["T"]
+
+        def draw(n):   # one call per generator for the whole buffer, as the step-by-step MLP path draws
+            return (t.randn((T, n, A), generator=learner.gen, device=self.device, dtype=t.float32),
+                    t.randn((T, n, A), generator=opp.gen, device=self.device, dtype=t.float32))
+
+        def fill(ro, sl):
+            ro.learner_params = learner.params.data_ptr()
+            if pool is None:
+                ro.opponent_params, ro.opponent_index, ro.npool = opp.params.data_ptr(), None, 1
+            else:
+                ro.opponent_params, ro.opponent_index, ro.npool = pool.params.data_ptr(), pool.index[sl].data_ptr(), pool.capacity
+            ro.ob_dim, ro.ac_dim = D, A
+
+        self._fused_groups(B, s0, K, alpha, capi.Rollout, draw, fill, self.env.rollout_steps_group)
 
     def join_groups(self):
         """Make the current stream wait for every env group's stream (no-op without groups)."""

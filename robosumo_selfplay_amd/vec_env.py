@@ -137,29 +137,28 @@ class SumoVecEnv(VecEnv):
         self._needs_seed = False
         return self.obs_dev
 
+    def env_ptrs(self, g, actions=None):
+        """The seven env-side pointers of group ``g`` in the order ``sumo_step`` and the fused launches take them: its rows of the
+        action tensor (``actions``, default the env's own action buffer), obs, info, done, ep_r, ep_dr, ep_l."""
+        sl = self._gs(g)
+        bufs = (self.act_dev if actions is None else actions, self.obs_dev, self.info_dev, self.done_dev, self.ep_r_dev, self.ep_dr_dev,
+                self.ep_l_dev)
+        return tuple(b[sl].data_ptr() for b in bufs)
+
     def step_device_group(self, g, actions):
         """Advance group ``g`` only (its slice of every buffer), on the current stream.  ``actions`` is the FULL [N, 2, A]
         action tensor; the group's rows are read."""
-        sl = self._gs(g)
-        self.engines[g].step(actions[sl].data_ptr(), self.obs_dev[sl].data_ptr(), self.info_dev[sl].data_ptr(),
-                             self.done_dev[sl].data_ptr(), self.ep_r_dev[sl].data_ptr(), self.ep_dr_dev[sl].data_ptr(),
-                             self.ep_l_dev[sl].data_ptr(), stream=self._stream())
+        self.engines[g].step(*self.env_ptrs(g, actions), stream=self._stream())
 
     def rollout_steps_group(self, g, ro):
         """K fused self-play rollout steps of group ``g`` on the current stream (``capi.Engine.rollout_steps``): policies, env
         steps and the appends to the rollout buffers in one launch.  ``ro`` is a ``capi.Rollout`` whose ``env_offset`` is the
         group's first env."""
-        sl = self._gs(g)
-        self.engines[g].rollout_steps(ro, self.act_dev[sl].data_ptr(), self.obs_dev[sl].data_ptr(), self.info_dev[sl].data_ptr(),
-                                      self.done_dev[sl].data_ptr(), self.ep_r_dev[sl].data_ptr(), self.ep_dr_dev[sl].data_ptr(),
-                                      self.ep_l_dev[sl].data_ptr(), stream=self._stream())
+        self.engines[g].rollout_steps(ro, *self.env_ptrs(g), stream=self._stream())
 
     def rollout_steps_lstm_group(self, g, ro):
         """The same for recurrent policies (``capi.Engine.rollout_steps_lstm``, ``ro`` a ``capi.RolloutLstm``)."""
-        sl = self._gs(g)
-        self.engines[g].rollout_steps_lstm(ro, self.act_dev[sl].data_ptr(), self.obs_dev[sl].data_ptr(), self.info_dev[sl].data_ptr(),
-                                           self.done_dev[sl].data_ptr(), self.ep_r_dev[sl].data_ptr(), self.ep_dr_dev[sl].data_ptr(),
-                                           self.ep_l_dev[sl].data_ptr(), stream=self._stream())
+        self.engines[g].rollout_steps_lstm(ro, *self.env_ptrs(g), stream=self._stream())
 
     def step_device(self, actions):
         """actions: float32 CUDA tensor [N, 2, act_stride]. Returns (obs, info, done, ep_r, ep_dr, ep_l) tensors that

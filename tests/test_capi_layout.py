@@ -1,4 +1,4 @@
-"""The ctypes mirrors of the C-ABI structs (capi.Rollout, capi.RolloutLstm, ppo_capi.LstmNet) against the layout the C compiler gives
+"""The ctypes mirrors of the C-ABI structs (capi.Rollout, capi.RolloutLstm, capi.Match, capi.MatchLstm, ppo_capi.LstmNet) against the layout the C compiler gives
 the structs of include/*.h: sizes and field offsets, from a small program compiled with gcc.  (A hand-written mirror that drifts from
 its header passes garbage pointers to a kernel.)"""
 import ctypes as C
@@ -13,7 +13,9 @@ sys.path.insert(0, ROOT)
 
 from robosumo_selfplay_amd import capi, ppo_capi  # noqa: E402
 
-STRUCTS = [("sumo_rollout", capi.Rollout), ("sumo_rollout_lstm", capi.RolloutLstm), ("ppo_lstm_net", ppo_capi.LstmNet)]
+STRUCTS = [("sumo_rollout", capi.Rollout), ("sumo_rollout_lstm", capi.RolloutLstm), ("sumo_match", capi.Match),
+           ("sumo_match_lstm", capi.MatchLstm), ("ppo_lstm_net", ppo_capi.LstmNet)]
+NO_TAIL_PADDING = ("sumo_match", "sumo_match_lstm")   # these end in a pointer: the last mirrored field ends exactly at sizeof
 
 
 def _c_layout(tmp_path):
@@ -44,6 +46,8 @@ def test_ctypes_mirrors_match_the_headers(tmp_path):
         # every field of the header is mirrored: the last mirrored field ends where the struct (up to tail padding) ends
         last = st._fields_[-1][0]
         assert getattr(st, last).offset + getattr(st, last).size + 8 > table[(cname, "size")], cname
+        if cname in NO_TAIL_PADDING:
+            assert getattr(st, last).offset + getattr(st, last).size == table[(cname, "size")], cname
 
 
 def test_headers_are_plain_c(tmp_path):

@@ -12,12 +12,13 @@ both terms.  One ``train`` call is one optimiser step on the whole batch:
 Out of scope: recurrent policies and multi-GPU (``comm``) -- both raise ``NotImplementedError``."""
 import numpy as np
 
-from . import hostcfg, policies, ppo_capi
+from . import policies, ppo_capi
 from .model import PPOModel
 
 
 class ActorCriticModel(PPOModel):
     loss_names = ["policy_loss", "value_loss", "policy_entropy"]   # model.py:296
+    graph_noun = "A2C"
 
     def __init__(self, *, policy, ob_space=None, ac_space=None, nbatch_act=None, nbatch_train=None, nsteps=None,
                  ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, microbatch_size=None, trainable=True, model_scope="",
@@ -30,7 +31,7 @@ class ActorCriticModel(PPOModel):
                          nsteps=nsteps, ent_coef=ent_coef, vf_coef=vf_coef, max_grad_norm=max_grad_norm,
                          microbatch_size=microbatch_size, trainable=trainable, model_scope=model_scope, device=device, comm=None)
         if trainable:
-            self._a2c = dict(graphs={}, last_n=None)
+            self._last_n = None       # batch size of the previous step (a size is captured the second time in a row it is seen)
 
     # ---- one optimiser step (model.py:348-372) -----------------------------------------------------------------
     def train(self, lr, obs, returns, masks, actions, values, neglogpacs, rewards, IS_weight, states=None):
@@ -69,11 +70,7 @@ class ActorCriticModel(PPOModel):
             out3 = t.empty(3, dtype=t.float64, device=self.device)
             adv = t.empty(n, dtype=t.float32, device=self.device)
             self._launch_chain(obs, returns, actions, values, IS_weight, n, adv, out3, st)
-        self.t += 1
-        ppo_capi.chk(ppo_capi.lib().ppo_clip_adam(self.params.data_ptr(), self.grads.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
-                                                   self.P, self.t, float(lr), 0.9, 0.999, 1e-5,
-                                                   float(self.max_grad_norm) if self.max_grad_norm is not None else 0.0,
-                                                   self.stats.data_ptr(), st))
+        self._adam_step(lr, st)
         return out3.clone()
 
     def _launch_chain(self, obs, returns, actions, values, weights, n, adv, out3, st):
@@ -95,35 +92,22 @@ class ActorCriticModel(PPOModel):
         update (opponent-data reuse) stays on the eager launches instead of capturing per update.  Returns None = use the eager
         path."""
         t = self._t
-        S = self._a2c
-        seen_before, S["last_n"] = S["last_n"] == n, n
-        g = S["graphs"].get(n)
+        seen_before, self._last_n = self._last_n == n, n
+        g = self._graphs.get(n)
         if g is None:
             if not seen_before:
                 return None
-            if len(S["graphs"]) >= 2:
-                hostcfg.drop_graphs(S["graphs"])
-            try:
+
+            def make_record():
                 bufs = [t.empty((n, obs.shape[1]), dtype=t.float32, device=self.device)] + [t.empty_like(x) for x in (returns, actions, values, weights)]
-                g = dict(bufs=bufs, adv=t.empty(n, dtype=t.float32, device=self.device), out3=t.zeros(3, dtype=t.float64, device=self.device))
                 for dst, x in zip(bufs, (obs, returns, actions, values, weights)):
                     dst.copy_(x)
-                side = t.cuda.Stream(device=self.device)
-                side.wait_stream(t.cuda.current_stream(self.device))
-                with t.cuda.stream(side):       # warm-up outside the capture (kernel attributes, allocator)
-                    self._launch_chain(*bufs, n, g["adv"], g["out3"], side.cuda_stream)
-                t.cuda.current_stream(self.device).wait_stream(side)
-                t.cuda.synchronize(self.device)
-                graph = t.cuda.CUDAGraph()
-                with hostcfg.gc_paused(), t.cuda.graph(graph):
-                    self._launch_chain(*bufs, n, g["adv"], g["out3"], t.cuda.current_stream(self.device).cuda_stream)
-                g["graph"] = graph
-                S["graphs"][n] = g
-            except Exception as e:                     # capture unsupported here: stay on the eager path for good
-                type(self).use_graph = False
-                hostcfg.drop_graphs(S["graphs"])
-                import warnings
-                warnings.warn("HIP graph capture of the A2C step failed (%r); using eager launches" % (e,))
+                return dict(bufs=bufs, adv=t.empty(n, dtype=t.float32, device=self.device), out3=t.zeros(3, dtype=t.float64, device=self.device))
+
+            def body(g):
+                self._launch_chain(*g["bufs"], n, g["adv"], g["out3"], t.cuda.current_stream(self.device).cuda_stream)
+            g = self._graphs.capture(n, make_record, body, lambda: setattr(type(self), "use_graph", False))
+            if g is None:
                 return None
         for dst, x in zip(g["bufs"], (obs, returns, actions, values, weights)):
             dst.copy_(x)

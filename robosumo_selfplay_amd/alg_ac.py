@@ -23,7 +23,8 @@ from collections import deque
 
 import numpy as np
 
-from .alg_ppo import assemble_update_batch, constfn, explained_variance, safemean
+from .alg_ppo import (assemble_update_batch, check_opponent_pool, constfn, env_fault_delta, explained_variance, install_fixed_opponent,
+                      safemean, upload)
 
 NEGLOGP_THRESHOLD = 50.0      # alg_ac.py:241-243, hard-coded there
 
@@ -82,10 +83,7 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
     # opponent_mode; K = 1 is the reference's single opponent for all envs
     pool = None
     if int(opponent_pool) > 1:
-        if opponent_mode == "fix":
-            raise ValueError("opponent_pool > 1 makes no sense with a fixed opponent")
-        if not runner.fused_ok():
-            raise NotImplementedError("opponent_pool > 1 runs inside the fused rollout launch (SUMO_FUSED_ROLLOUT != 0)")
+        check_opponent_pool(opponent_mode, runner, fused=True)
         from .opponent_pool import OpponentPool
         pool = runner.opponent_pool = OpponentPool(policy, int(opponent_pool), nenvs, dev)
     epinfobuf = deque(maxlen=100)
@@ -103,14 +101,8 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
         lrnow = lr(frac)
         # ---- opponent selection (alg_ac.py:172-213)
         if opponent_mode == "fix":
-            if update == 1:                                              # a policy-zoo MLP net (alg_ac.py:175-189)
-                from .policy_zoo import FixedOpponentModel, load_zoo_policy
-                if fix_opponent_path is None:
-                    raise ValueError("opponent_mode='fix' needs fix_opponent_path=<policy_zoo .npy> (reference default: "
-                                     "robosumo/robosumo/policy_zoo/assets/ant/mlp/agent-params-v3.npy)")
-                zoo = load_zoo_policy(fix_opponent_path, ac_space.shape[0], device=dev)
-                zoo.seed((seed or 0) * 1000 + 17)
-                runner.models[1] = FixedOpponentModel(zoo)
+            if update == 1:
+                install_fixed_opponent(runner, fix_opponent_path, ac_space.shape[0], dev, (seed or 0) * 1000 + 17)
             history["opponent_versions"].append([])
         else:
             if update == 1 or opponent_mode == "ours":                   # 'ours': v0 for the whole run (decision 3 above)
@@ -137,8 +129,7 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
         torch.cuda.synchronize(dev)
         t_roll = time.perf_counter() - tsel
         if isinstance(obs, np.ndarray):       # host-mode Runner: continue on the device
-            up = lambda x: torch.as_tensor(np.ascontiguousarray(x)).to(dev)
-            obs, returns, masks, actions, values, neglogpacs, rewards = map(up, (obs, returns, masks, actions, values, neglogpacs, rewards))
+            obs, returns, masks, actions, values, neglogpacs, rewards = upload(dev, obs, returns, masks, actions, values, neglogpacs, rewards)
         # ---- batch: the learner's rows, plus the opponent's usable rows under 'direct' (alg_ac.py:241-262)
         if use_opponent_data is None:
             b_obs, b_ret, b_act, b_val = obs[0], returns[0], actions[0], values[0]
@@ -159,16 +150,7 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
         history["rollout_s"].append(t_roll)
         history["update_s"].append(tnow - tsel - t_roll)
         history["fps"].append(nbatch / (tnow - tstart))
-        env_note = ""
-        if env_stats_prev is not None:                                  # the engine's fault counters of this update (as alg_ppo)
-            st_now = env.stats()
-            dv, dc = st_now["diverged"] - env_stats_prev["diverged"], st_now["dropped"] - env_stats_prev["dropped"]
-            ab = (st_now["rollout_aborts"] + st_now.get("handover_mismatches", 0)
-                  - env_stats_prev["rollout_aborts"] - env_stats_prev.get("handover_mismatches", 0))
-            env_stats_prev = st_now
-            history["env_diverged"].append(int(dv)); history["env_dropped_contacts"].append(int(dc)); history["env_rollout_aborts"].append(int(ab))
-            if dv or dc or ab:
-                env_note = "  [env: %d diverged steps, %d dropped contacts, %d rollout aborts]" % (dv, dc, ab)
+        env_stats_prev, env_note = env_fault_delta(env, env_stats_prev, history)
         if update_fn is not None:
             update_fn(update)
         if verbose and (update % log_interval == 0 or update == 1):

@@ -91,6 +91,46 @@ def selection_probs(action_prob, new_action_probs):
     return rd / tot if np.isfinite(tot) and tot > 0 else np.full(len(rd), 1.0 / len(rd))
 
 
+def install_fixed_opponent(runner, fix_opponent_path, ac_dim, dev, seed):
+    """``opponent_mode='fix'`` (alg_ppo.py:194-206, alg_ac.py:175-189): a policy-zoo MLP net plays agent 1 for the whole run."""
+    from .policy_zoo import FixedOpponentModel, load_zoo_policy
+    if fix_opponent_path is None:
+        raise ValueError("opponent_mode='fix' needs fix_opponent_path=<policy_zoo .npy> (reference default: "
+                         "robosumo/robosumo/policy_zoo/assets/ant/mlp/agent-params-v3.npy)")
+    zoo = load_zoo_policy(fix_opponent_path, ac_dim, device=dev)
+    zoo.seed(seed)
+    runner.models[1] = FixedOpponentModel(zoo)
+
+
+def check_opponent_pool(opponent_mode, runner, fused):
+    """What ``opponent_pool`` > 1 refuses; ``fused``: the pool is read by the fused rollout launch (MLP policies)."""
+    if opponent_mode == "fix":
+        raise ValueError("opponent_pool > 1 makes no sense with a fixed opponent")
+    if fused and not runner.fused_ok():
+        raise NotImplementedError("opponent_pool > 1 with MLP policies runs inside the fused rollout launch (SUMO_FUSED_ROLLOUT != 0)")
+
+
+def upload(dev, *arrays):
+    """The arrays of a host-mode Runner (recurrent models), moved to the device so that the update continues there like the MLP path."""
+    import torch
+    return [torch.as_tensor(np.ascontiguousarray(x)).to(dev) for x in arrays]
+
+
+def env_fault_delta(env, prev, history):
+    """The engine's fault counters of one update (the reference is loud here: a MuJoCo warning raises MujocoException, mujoco-py
+    builder.py:351-369; the fused launch's abort already raised in Runner.run): diverged env steps (episodes ended by the bad-value
+    guard), contacts dropped for lack of room, aborted hand-over waits.  ``prev``: ``env.stats()`` at the end of the previous update
+    (None: the env keeps no counters).  Appends the three deltas to ``history``; returns (stats now, note for the log line or "")."""
+    if prev is None:
+        return None, ""
+    now = env.stats()
+    dv, dc = now["diverged"] - prev["diverged"], now["dropped"] - prev["dropped"]
+    ab = now["rollout_aborts"] + now.get("handover_mismatches", 0) - prev["rollout_aborts"] - prev.get("handover_mismatches", 0)
+    history["env_diverged"].append(int(dv)); history["env_dropped_contacts"].append(int(dc)); history["env_rollout_aborts"].append(int(ab))
+    note = "  [env: %d diverged steps, %d dropped contacts, %d rollout aborts]" % (dv, dc, ab) if dv or dc or ab else ""
+    return now, note
+
+
 def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_data=None, eval_env=None, seed=None, nsteps=2048,
           ent_coef=0.0, lr=3e-4, vf_coef=0.5, max_grad_norm=0.5, gamma=0.99, lam=0.95, rho_bar=1.0, c_bar=1.0, log_interval=10,
           nminibatches=4, noptepochs=4, cliprange=0.2, save_interval=1, load_path=None, model_fn=None, update_fn=None, init_fn=None,
@@ -128,7 +168,7 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
     models = [model] + [mk("model_%d" % i, False) for i in range(1, nagent)]
     model_util = mk("model_util", False)
     log_dir = log_dir or os.environ.get("OPENAI_LOGDIR") or "/tmp/robosumo_selfplay_amd"
-    checkdir = osp.join(log_dir, "checkpoints") if world == 1 else osp.join(log_dir, "checkpoints")
+    checkdir = osp.join(log_dir, "checkpoints")
     if rank == 0:
         model.save(osp.join(checkdir, "00000"))                          # alg_ppo.py:122-123
     if comm is not None:
@@ -146,16 +186,13 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
     pool = None
     opp_ref = models[1] if nagent > 1 else None      # the single-snapshot opponent model (reference of the 'ours' selector under a pool)
     if int(opponent_pool) > 1:
-        if opponent_mode == "fix":
-            raise ValueError("opponent_pool > 1 makes no sense with a fixed opponent")
+        check_opponent_pool(opponent_mode, runner, fused=not recurrent)
         from .opponent_pool import LstmOpponentPool, OpponentPool
         pool = (LstmOpponentPool if recurrent else OpponentPool)(policy, int(opponent_pool), nenvs, dev)
         if recurrent:
             pool.seed((seed or 0) * 1000 + 17 + rank)
             runner.models[1] = pool           # acts for agent 1 and scores agent 0's actions, each env tile with its own snapshot
         else:
-            if not runner.fused_ok():
-                raise NotImplementedError("opponent_pool > 1 with MLP policies runs inside the fused rollout launch (SUMO_FUSED_ROLLOUT != 0)")
             runner.opponent_pool = pool
     epinfobuf = deque(maxlen=100)
     shuffle_gen = torch.Generator(device=dev)
@@ -179,13 +216,7 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
         # ---- opponent selection (alg_ppo.py:191-247); rank 0 decides, everyone loads the same file
         if opponent_mode == "fix":                                       # alg_ppo.py:194-206: a policy-zoo MLP net
             if update == 1:
-                from .policy_zoo import FixedOpponentModel, load_zoo_policy
-                if fix_opponent_path is None:
-                    raise ValueError("opponent_mode='fix' needs fix_opponent_path=<policy_zoo .npy> (reference default: "
-                                     "robosumo/robosumo/policy_zoo/assets/ant/mlp/agent-params-v3.npy)")
-                zoo = load_zoo_policy(fix_opponent_path, ac_space.shape[0], device=dev)
-                zoo.seed((seed or 0) * 1000 + 17 + rank)
-                runner.models[1] = FixedOpponentModel(zoo)
+                install_fixed_opponent(runner, fix_opponent_path, ac_space.shape[0], dev, (seed or 0) * 1000 + 17 + rank)
         elif update == 1:
             if not (recurrent and pool is not None):
                 runner.models[1].load(osp.join(checkdir, "00000"))
@@ -236,10 +267,8 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
         torch.cuda.synchronize(dev)
         t_roll = time.perf_counter() - tstart
         if isinstance(obs, np.ndarray):       # host-mode Runner (recurrent models): continue on the device like the MLP path
-            up = lambda x: torch.as_tensor(np.ascontiguousarray(x)).to(dev)
-            obs, returns, masks, actions, values, neglogpacs, rewards, opponent_neglogpacs = map(
-                up, (obs, returns, masks, actions, values, neglogpacs, rewards, opponent_neglogpacs))
-            off_policy_ratio, off_env_ratio, total_ratio = map(up, (off_policy_ratio, off_env_ratio, total_ratio))
+            obs, returns, masks, actions, values, neglogpacs, rewards, opponent_neglogpacs, off_policy_ratio, off_env_ratio, total_ratio = upload(
+                dev, obs, returns, masks, actions, values, neglogpacs, rewards, opponent_neglogpacs, off_policy_ratio, off_env_ratio, total_ratio)
         # un-scrambled opponent data for the 'ours' selector: rows = agent 1's (obs, action), env-major
         opponent_obs, opponent_actions = obs[1], actions[1]
         # ---- ratio hygiene (alg_ppo.py:258-280)
@@ -313,19 +342,7 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
         history["rollout_s"].append(t_roll)
         history["update_s"].append(tnow - tstart - t_roll)
         history["fps"].append(nbatch * world / (tnow - tstart))
-        # the engine's fault counters of this update (the reference is loud here: a MuJoCo warning raises MujocoException,
-        # mujoco-py builder.py:351-369; the fused launch's abort already raised in Runner.run): diverged env steps (episodes ended
-        # by the bad-value guard), contacts dropped for lack of room, aborted hand-over waits
-        env_note = ""
-        if env_stats_prev is not None:
-            st_now = env.stats()
-            dv, dc = st_now["diverged"] - env_stats_prev["diverged"], st_now["dropped"] - env_stats_prev["dropped"]
-            ab = (st_now["rollout_aborts"] + st_now.get("handover_mismatches", 0)
-                  - env_stats_prev["rollout_aborts"] - env_stats_prev.get("handover_mismatches", 0))
-            env_stats_prev = st_now
-            history["env_diverged"].append(int(dv)); history["env_dropped_contacts"].append(int(dc)); history["env_rollout_aborts"].append(int(ab))
-            if dv or dc or ab:
-                env_note = "  [env: %d diverged steps, %d dropped contacts, %d rollout aborts]" % (dv, dc, ab)
+        env_stats_prev, env_note = env_fault_delta(env, env_stats_prev, history)
         if update_fn is not None:
             update_fn(update)
         if verbose and rank == 0 and (update % log_interval == 0 or update == 1):

@@ -1,6 +1,7 @@
-"""Host-side thread budget.
+"""Host-side rules of the process: the thread budget (``apply`` and the cgroup probes below) and the lifetime of captured HIP
+graphs (``gc_paused``, ``drop_graphs``, ``GraphCache`` at the end of the file).
 
-A GPU box hands a job a CPU *quota* (cgroup ``cpu.max``, e.g. 16 cores' worth of a 256-core host) while ``os.cpu_count()``
+Thread budget.  A GPU box hands a job a CPU *quota* (cgroup ``cpu.max``, e.g. 16 cores' worth of a 256-core host) while ``os.cpu_count()``
 still reports every core of the host.  numpy's BLAS, torch's intra-op pool and OpenMP then start one spinning worker per
 reported core; their spin-waits burn the quota and the kernel throttles the WHOLE process group until the next 100 ms
 scheduler period -- including the thread that enqueues kernels and the one that waits for them.  Measured on an MI355X box
@@ -11,6 +12,12 @@ hazard in mirror image (one OS process per env, subproc_vec_env.py:35-58) and si
 ``apply()`` caps the pools at the quota.  It must run before numpy / torch are imported to catch the pools at creation;
 pools that already exist are narrowed through threadpoolctl / torch.set_num_threads.  SUMO_HOST_THREADS=<n> overrides the
 count, SUMO_HOST_THREADS=0 leaves everything alone.
+
+Graph lifetime.  Destroying a captured graph (or a stream / event of an earlier model) while any stream of the process is capturing
+aborts the process, and so does a one-time set-up call (kernel attributes, allocator growth, communicator set-up) issued inside a
+capture.  Hence: graphs are released in one place that refuses while a capture is open (``drop_graphs``), the cyclic collector is off
+during a capture (``gc_paused``), and every capture is preceded by a warm-up of the same launches outside it (``GraphCache.capture``,
+the one copy of that protocol; the learners keep only what differs between them: key, static buffers, captured launches).
 """
 import os
 import sys
@@ -102,13 +109,13 @@ def capturing():
 
 
 def drop_graphs(graphs):
-    """The ONE place captured HIP graphs are released (``graphs``: a dict of capture records).  Destroying a graph while a stream of
-    the process is capturing aborts the process; the cyclic collector is held off by ``gc_paused``, and this guard covers the other
-    route -- a reference count reaching zero inside a capture block."""
+    """The ONE place captured HIP graphs are released (``graphs``: a dict of capture records or a ``GraphCache``).  Destroying a graph
+    while a stream of the process is capturing aborts the process; the cyclic collector is held off by ``gc_paused``, and this guard
+    covers the other route -- a reference count reaching zero inside a capture block."""
     if _captures_open:
         raise RuntimeError("a captured HIP graph would be destroyed while a graph capture is open (hostcfg.gc_paused): "
                            "release graphs before entering the capture block")
-    graphs.clear()
+    dict.clear(graphs)
 
 
 class gc_paused(object):
@@ -133,3 +140,50 @@ class gc_paused(object):
         if self._was:
             gc.enable()
         return False
+
+
+class GraphCache(dict):
+    """key -> capture record (a dict with the step's static buffers and its ``graph``) of one learner, at most ``LIMIT`` of them: a
+    further key releases ALL records first.  A hit costs the caller one ``get``; it then copies its inputs into the record's buffers and
+    calls ``record["graph"].replay()``.  ``noun`` names the step in the failure warning; ``cuda`` (default ``torch.cuda``) is the
+    stream / graph API, replaceable by a stand-in so that the policy is testable without a device."""
+    LIMIT = 2
+
+    def __init__(self, noun, device, cuda=None):
+        dict.__init__(self)
+        self.noun, self.device, self._cuda = noun, device, cuda
+
+    def clear(self):
+        drop_graphs(self)
+
+    def capture(self, key, make_record, body, on_fail, **graph_kwargs):
+        """``make_record()`` allocates (and fills) the static buffers; ``body(record)`` issues the step's launches on the CURRENT
+        stream and runs twice: as the warm-up on a side stream, outside the capture, and under the capture with the collector paused.
+        Returns the stored record, or None after a failure: the records are dropped, ``on_fail()`` switches the caller's graph path off
+        for good and a warning names the cause."""
+        if len(self) >= self.LIMIT:
+            self.clear()
+        cuda = self._cuda
+        if cuda is None:
+            import torch
+            cuda = torch.cuda
+        try:
+            rec = make_record()
+            side = cuda.Stream(device=self.device)
+            side.wait_stream(cuda.current_stream(self.device))
+            with cuda.stream(side):       # warm-up outside the capture (one-time kernel attributes, allocator, GEMM workspaces, communicator)
+                body(rec)
+            cuda.current_stream(self.device).wait_stream(side)
+            cuda.synchronize(self.device)
+            graph = cuda.CUDAGraph()
+            with gc_paused(), cuda.graph(graph, **graph_kwargs):
+                body(rec)
+            rec["graph"] = graph
+            self[key] = rec
+            return rec
+        except Exception as e:                     # capture unsupported here: the caller stays on the eager path for good
+            on_fail()
+            self.clear()
+            import warnings
+            warnings.warn("HIP graph capture of the %s step failed (%r); using eager launches" % (self.noun, e))
+            return None

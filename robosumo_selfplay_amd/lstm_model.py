@@ -18,6 +18,7 @@ import os
 import numpy as np
 
 from . import dist as sdist, hostcfg, policies, ppo_capi
+from .learner import Learner
 
 
 class LstmSpec(object):
@@ -27,7 +28,7 @@ class LstmSpec(object):
         self.ob_dim, self.ac_dim, self.nlstm = int(ob_dim), int(ac_dim), int(nlstm)
 
 
-class LstmPPOModel(object):
+class LstmPPOModel(Learner):
     loss_names = ["policy_loss", "value_loss", "policy_entropy", "approxkl", "clipfrac"]
     recurrent = True
     accepts_noise = True  # step(..., noise=rows) takes the action noise from the caller (device-mode Runner: one draw per rollout)
@@ -51,7 +52,7 @@ class LstmPPOModel(object):
         flat = np.concatenate([np.asarray(p, np.float32).ravel() for p in policies.init_lstm_param_list(D, A, H)])
         self.params = torch.from_numpy(flat).to(self.device)
         self.views = self._split(self.params)
-        self._net = self._make_net(self.views)
+        self._net = ppo_capi.fill_lstm_net_ifou(ppo_capi.LstmNet(), D, A, H, [v.data_ptr() for v in self.views])
         self.gen = torch.Generator(device=self.device)
         self.act_model = self.train_model = self
         self.initial_state = None if nbatch_act is None else np.zeros((int(nbatch_act), 2 * H), np.float32)   # models.py:176
@@ -63,7 +64,7 @@ class LstmPPOModel(object):
             self.gviews = self._split(self.grads)
             self.stats = torch.zeros(ppo_capi.NSTATS, dtype=torch.float64, device=self.device)
             self.moments = torch.zeros(3, dtype=torch.float64, device=self.device)
-            self._graphs = {}
+            self._graphs = hostcfg.GraphCache("recurrent PPO", self.device)
             self.wgrad_native = os.environ.get("SUMO_LSTM_WGRAD", "native") != "blas"
             self.seq_kernels = os.environ.get("SUMO_LSTM_SEQ", "1") != "0"    # whole-sequence forward / BPTT launches (nlstm 128)
             self.xproj = os.environ.get("SUMO_LSTM_XPROJ", "1") != "0"      # input block of the training forward hoisted out of the recurrence
@@ -82,15 +83,6 @@ class LstmPPOModel(object):
             o += n
         return out
 
-    def _make_net(self, v):
-        wx, wh, b, pw, pb, logstd, vw, vb = v
-        n = ppo_capi.LstmNet()
-        n.ob_dim, n.emb_dim, n.hidden, n.ac_dim = self.spec.ob_dim, 0, self.spec.nlstm, self.spec.ac_dim
-        n.gate_order, n.forget_bias = ppo_capi.LSTM_GATES_IFOU, 0.0
-        n.wx, n.wh, n.b = wx.data_ptr(), wh.data_ptr(), b.data_ptr()
-        n.head_w, n.head_b, n.logstd, n.vf_w, n.vf_b = pw.data_ptr(), pb.data_ptr(), logstd.data_ptr(), vw.data_ptr(), vb.data_ptr()
-        return n
-
     def seed(self, s):
         self.gen.manual_seed(int(s))
 
@@ -105,22 +97,7 @@ class LstmPPOModel(object):
                 raise ValueError("parameter shape %s does not match %s" % (np.shape(p), s))
         self.params.copy_(self._t.from_numpy(np.concatenate([np.asarray(p, np.float32).ravel() for p in plist])))
 
-    def save(self, save_path):
-        import joblib
-        d = os.path.dirname(save_path)
-        if d:
-            os.makedirs(d, exist_ok=True)
-        joblib.dump(self.get_param_list(), save_path)
-
-    def load(self, load_path):
-        import joblib
-        self.set_param_list(joblib.load(os.path.expanduser(load_path)))      # only files written by save()
-
     # ---- acting (policies.py:84-128 with the S / M feeds of models.py:163-170) --------------------------------------
-    def _dev(self, x, dtype=np.float32):
-        t = self._t
-        return x if t.is_tensor(x) else t.from_numpy(np.ascontiguousarray(x, dtype)).to(self.device)
-
     def net_dev(self):
         """Device copy of this model's ``ppo_lstm_net`` (its pointers address ``self.params``, whose storage never moves): what the
         fused recurrent rollout reads when this model is the opponent."""
@@ -256,32 +233,17 @@ class LstmPPOModel(object):
         key = (tuple(tuple(x.shape) for x in tensors), tuple(x.dtype for x in tensors), int(T), float(cliprange))
         ent = self._graphs.get(key)
         if ent is None:
-            if len(self._graphs) >= 2:
-                hostcfg.drop_graphs(self._graphs)
-            try:
+            def make_record():
                 static = [t.empty(x.shape, dtype=x.dtype, device=self.device) for x in tensors]
                 for d, x in zip(static, tensors):
                     d.copy_(x)
+                return dict(static=static)
 
-                def body():
-                    obs, returns, masks, actions, values, neglogpacs, IS_weight, states = static
-                    self._loss_step(cliprange, obs, returns.contiguous(), values.contiguous(), masks, actions, neglogpacs, IS_weight,
-                                    states, T, 1)
-                side = t.cuda.Stream(device=self.device)
-                side.wait_stream(t.cuda.current_stream(self.device))
-                with t.cuda.stream(side):          # warm-up outside the capture (GEMM workspaces, kernel attributes, allocator)
-                    body()
-                t.cuda.current_stream(self.device).wait_stream(side)
-                t.cuda.synchronize(self.device)
-                graph = t.cuda.CUDAGraph()
-                with hostcfg.gc_paused(), t.cuda.graph(graph):
-                    body()
-                ent = self._graphs[key] = dict(graph=graph, static=static)
-            except Exception as e:                 # capture unsupported here: eager launches from now on
-                type(self).use_graph = False
-                hostcfg.drop_graphs(self._graphs)
-                import warnings
-                warnings.warn("HIP graph capture of the recurrent PPO step failed (%r); using eager launches" % (e,))
+            def body(ent):
+                obs, returns, masks, actions, values, neglogpacs, IS_weight, states = ent["static"]
+                self._loss_step(cliprange, obs, returns.contiguous(), values.contiguous(), masks, actions, neglogpacs, IS_weight, states, T, 1)
+            ent = self._graphs.capture(key, make_record, body, lambda: setattr(type(self), "use_graph", False))
+            if ent is None:
                 return False
         else:
             for d, x in zip(ent["static"], tensors):
@@ -295,7 +257,6 @@ class LstmPPOModel(object):
         if states is None:
             raise ValueError("a recurrent model trains on whole sequences: pass the start states of the minibatch envs")
         t = self._t
-        L = ppo_capi.lib()
         np_in = not t.is_tensor(obs)
         T = int(nsteps or self.nsteps)
         world = 1 if self.comm is None else t.distributed.get_world_size(self.comm)
@@ -305,15 +266,10 @@ class LstmPPOModel(object):
             ret, val = self._dev(returns).contiguous(), self._dev(values).contiguous()
             self._loss_step(cliprange, obs, ret, val, masks, actions, neglogpacs, IS_weight, states, T, world)
         st = t.cuda.current_stream(self.device).cuda_stream
-        if self.comm is not None:            # ONE fused collective per optimiser step: [flat grad | loss sums] (equal shards per rank)
-            self.grads[self.P:] = self.stats.to(t.float32)
-            sdist.allreduce_fused(self.grads, self.comm)
-            self.stats.copy_(self.grads[self.P:].to(t.float64))
+        if self.comm is not None:            # equal shards per rank
+            self._allreduce_grad_and_stats()
         entropy = float((self.views[5].double() + 0.5 * np.log(2.0 * np.pi * np.e)).sum().item())
-        self.t += 1
-        ppo_capi.chk(L.ppo_clip_adam(self.params.data_ptr(), self.grads.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.P, self.t,
-                                     float(lr), 0.9, 0.999, 1e-5, float(self.max_grad_norm) if self.max_grad_norm is not None else 0.0,
-                                     self.stats.data_ptr(), st))
+        self._adam_step(lr, st)
         s = self.stats.cpu().numpy()
         cnt = s[6]
         out = [s[0] / cnt, s[1] / cnt, entropy, s[3] / cnt, s[4] / cnt]

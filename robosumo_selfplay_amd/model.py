@@ -5,9 +5,10 @@ import os
 import numpy as np
 
 from . import dist as sdist, hostcfg, policies, ppo_capi
+from .learner import Learner
 
 
-class PPOModel(object):
+class PPOModel(Learner):
     loss_names = ["policy_loss", "value_loss", "policy_entropy", "approxkl", "clipfrac"]   # model.py:138
 
     def __init__(self, *, policy, ob_space=None, ac_space=None, nbatch_act=None, nbatch_train=None, nsteps=None,
@@ -44,7 +45,7 @@ class PPOModel(object):
             self.moments = torch.zeros(3, dtype=torch.float64, device=self.device)
             self.workspace = torch.zeros(ppo_capi.lib().ppo_grad_workspace_bytes(D, A), dtype=torch.uint8, device=self.device)   # zeroed once: sumo_ppo.h
             self.adv_ws = torch.zeros(ppo_capi.lib().ppo_adv_moments_workspace_bytes(), dtype=torch.uint8, device=self.device)   # this model's own (sumo_ppo.h)
-            self._graphs = {}
+            self._graphs = hostcfg.GraphCache(self.graph_noun, self.device)
             self._static = None
             self._epoch_moments = None
 
@@ -63,24 +64,7 @@ class PPOModel(object):
                 raise ValueError("checkpoint tensor shape %s does not match %s" % (np.shape(p), s))
         self.params.copy_(self._t.from_numpy(policies.flatten_params(plist)))
 
-    def save(self, save_path):
-        dirname = os.path.dirname(save_path)
-        if dirname:
-            os.makedirs(dirname, exist_ok=True)
-        import joblib
-        joblib.dump(self.get_param_list(), save_path)                  # same on-disk format as model.py:161
-
-    def load(self, load_path):
-        import joblib
-        self.set_param_list(joblib.load(os.path.expanduser(load_path)))   # only files written by save()
-
     # ---- training (model.py:179-213) ---------------------------------------------------------------------------
-    def _dev(self, x, dtype):
-        t = self._t
-        if t.is_tensor(x):
-            return x
-        return t.as_tensor(np.ascontiguousarray(x, dtype=dtype)).to(self.device)
-
     def train(self, lr, cliprange, obs, returns, masks, actions, values, neglogpacs, rewards, IS_weight, states=None):
         t = self._t
         np_in = not t.is_tensor(obs)
@@ -97,37 +81,35 @@ class PPOModel(object):
     # is captured once per (batch arrays, minibatch size, cliprange) into a HIP graph and replayed with a fresh index
     # vector; only the Adam step stays outside (its step count is a host scalar).  Single-GPU, asynchronous path only.
     use_graph = os.environ.get("SUMO_PPO_GRAPH", "1") != "0"
+    graph_noun = "PPO"    # names the step in the warning of a failed capture
     equal_counts = True   # multi-GPU: minibatches have the same size on every rank (learn() clears it for opponent-data reuse)
 
     def _launch_loss_grad(self, obs, returns, actions, values, neglogpacs, weights, idx, n, cliprange, adv, log_ratio, st, mom=None):
-        """The launches of one optimiser step up to the gradient.  ``mom`` None: single GPU, the minibatch's own advantage moments.
-        ``mom`` = device [3] float64 holding the GLOBAL moments of this minibatch (``prepare_epoch``): multi-GPU form -- normalise with
-        them, scale by the global count, then ONE all-reduce of [flat grad | loss sums | count]."""
+        """The launches of one optimiser step up to the gradient, eager or under capture.  ``mom`` None: the minibatch's own advantage
+        moments (all-reduced when there is a communicator).  ``mom`` = device [3] float64 holding the GLOBAL moments of this minibatch
+        (``prepare_epoch``): normalise with them, scale by the global count, then ONE all-reduce of [flat grad | loss sums | count]
+        (SURVEY.md 8(e)(ii)).  A step is captured only without a communicator or with ``mom`` (equal shards), so the host read-back of
+        the count below never happens inside a capture."""
         L = ppo_capi.lib()
-        D, A = self.spec.ob_dim, self.spec.ac_dim
-        ip = idx.data_ptr()
+        ip = ppo_capi.ptr(idx)
         if mom is None:
             mom = self.moments
             ppo_capi.chk(L.ppo_adv_moments_ws(returns.data_ptr(), values.data_ptr(), ip, n, mom.data_ptr(), self.adv_ws.data_ptr(), st))
+            sdist.allreduce_moments(mom, self.comm)
+        if self.comm is None:
             count = float(n)
+        elif self.equal_counts:       # every rank contributes the same number of rows: no host read-back of the all-reduced count
+            count = float(n) * self._t.distributed.get_world_size(self.comm)
         else:
-            count = float(n) * self._t.distributed.get_world_size(self.comm)       # equal shards: no host read-back of the reduced count
+            count = float(mom[2].item())
         ppo_capi.chk(L.ppo_adv_normalize(returns.data_ptr(), values.data_ptr(), ip, n, mom.data_ptr(), adv.data_ptr(), st))
         self.stats.zero_()
-        ppo_capi.chk(L.ppo_grad(self.params.data_ptr(), obs.data_ptr(), obs.stride(0), D, A, actions.data_ptr(), adv.data_ptr(),
-                                returns.data_ptr(), neglogpacs.data_ptr(), weights.data_ptr(), ip, n, 1.0 / count,
+        ppo_capi.chk(L.ppo_grad(self.params.data_ptr(), obs.data_ptr(), obs.stride(0), self.spec.ob_dim, self.spec.ac_dim, actions.data_ptr(),
+                                adv.data_ptr(), returns.data_ptr(), neglogpacs.data_ptr(), weights.data_ptr(), ip, n, 1.0 / count,
                                 float(cliprange), self.ent_coef, self.vf_coef, self.grads.data_ptr(), self.stats.data_ptr(),
                                 log_ratio.data_ptr(), self.workspace.data_ptr(), st))
         if self.comm is not None:
             self._allreduce_grad_and_stats()
-
-    def _allreduce_grad_and_stats(self):
-        """ONE fused collective per optimiser step: [flat grad | 8 loss sums] (the reference's only gradient collective,
-        mpi_adam_optimizer.py:39, all-reduces the flat gradient alone)."""
-        t = self._t
-        self.grads[self.P:self.P + ppo_capi.NSTATS] = self.stats.to(t.float32)
-        sdist.allreduce_fused(self.grads, self.comm)
-        self.stats.copy_(self.grads[self.P:self.P + ppo_capi.NSTATS].to(t.float64))
 
     def prepare_epoch(self, inds, nbatch_train, returns=None, values=None):
         """Multi-GPU with equal shards: the advantage moments of ALL minibatches of the coming epoch -- rows
@@ -171,7 +153,7 @@ class PPOModel(object):
         shp = (tuple(obs.shape), obs.stride(0), tuple(weights.shape))
         if self._static is None or self._static["shape"] != shp:
             self._static = dict(shape=shp, bufs=[t.empty_like(x, memory_format=t.contiguous_format) for x in arrs])
-            hostcfg.drop_graphs(self._graphs)
+            self._graphs.clear()
         for dst, x in zip(self._static["bufs"], arrs):
             dst.copy_(x)
         self._static["open"] = True
@@ -185,57 +167,36 @@ class PPOModel(object):
     def _graph_step(self, lr, cliprange, idx, n, mom=None):
         """``mom`` (multi-GPU: the minibatch's global advantage moments from ``prepare_epoch``): the captured step then holds
         adv_normalize -> ppo_grad -> fused all-reduce (RCCL calls capture on the stream) -> loss statistics, and the moments are copied
-        into the graph's own buffer before every replay, like the index vector."""
+        into the graph's own buffer before every replay, like the index vector.  Returns None = use the eager path."""
         t = self._t
-        A = self.spec.ac_dim
-        obs, returns, actions, values, neglogpacs, weights = self._static["bufs"]
         key = (int(n), float(cliprange), mom is not None)
         g = self._graphs.get(key)
         if g is None:
-            if len(self._graphs) >= 2:
-                hostcfg.drop_graphs(self._graphs)
-            try:
-                ent = dict(idx=t.zeros(n, dtype=t.int32, device=self.device), adv=t.empty(n, dtype=t.float32, device=self.device),
-                           log_ratio=t.empty(n, dtype=t.float32, device=self.device), keep=(obs, returns, actions, values, neglogpacs, weights),
-                           mom=None if mom is None else t.zeros(3, dtype=t.float64, device=self.device))
-                side = t.cuda.Stream(device=self.device)
-                side.wait_stream(t.cuda.current_stream(self.device))
-                with t.cuda.stream(side):       # warm-up outside the capture (one-time kernel attributes, allocator, communicator set-up)
-                    ent["idx"].copy_(idx)
-                    if mom is not None:
-                        ent["mom"].copy_(mom)
-                    self._launch_loss_grad(obs, returns, actions, values, neglogpacs, weights, ent["idx"], n, cliprange, ent["adv"],
-                                           ent["log_ratio"], side.cuda_stream, mom=ent["mom"])
-                t.cuda.current_stream(self.device).wait_stream(side)
-                t.cuda.synchronize(self.device)
-                graph = t.cuda.CUDAGraph()
-                # with a collective inside, only this thread's calls belong to the capture (the process group's watchdog thread polls events)
-                gkw = dict(capture_error_mode="thread_local") if mom is not None else {}
-                with hostcfg.gc_paused(), t.cuda.graph(graph, **gkw):
-                    cst = t.cuda.current_stream(self.device).cuda_stream
-                    self._launch_loss_grad(obs, returns, actions, values, neglogpacs, weights, ent["idx"], n, cliprange, ent["adv"],
-                                           ent["log_ratio"], cst, mom=ent["mom"])
-                    ent["out"] = self._loss_stats(cst)
-                ent["graph"] = graph
-                g = self._graphs[key] = ent
-            except Exception as e:                     # capture unsupported here: stay on the eager path for good
+            def make_record():
+                g = dict(idx=t.zeros(n, dtype=t.int32, device=self.device), adv=t.empty(n, dtype=t.float32, device=self.device),
+                         log_ratio=t.empty(n, dtype=t.float32, device=self.device), keep=tuple(self._static["bufs"]),
+                         mom=None if mom is None else t.zeros(3, dtype=t.float64, device=self.device))
+                g["idx"].copy_(idx)
                 if mom is not None:
-                    type(self).use_comm_graph = False
-                else:
-                    type(self).use_graph = False
-                hostcfg.drop_graphs(self._graphs)
-                import warnings
-                warnings.warn("HIP graph capture of the PPO step failed (%r); using eager launches" % (e,))
+                    g["mom"].copy_(mom)
+                return g
+
+            def body(g):
+                st = t.cuda.current_stream(self.device).cuda_stream
+                self._launch_loss_grad(*g["keep"], g["idx"], n, cliprange, g["adv"], g["log_ratio"], st, mom=g["mom"])
+                g["out"] = self._loss_stats(st)
+
+            # with a collective inside, only this thread's calls belong to the capture (the process group's watchdog thread polls events)
+            gkw = dict(capture_error_mode="thread_local") if mom is not None else {}
+            g = self._graphs.capture(key, make_record, body, lambda: setattr(type(self), "use_graph" if mom is None else "use_comm_graph", False),
+                                     **gkw)
+            if g is None:
                 return None
         g["idx"].copy_(idx)
         if mom is not None:
             g["mom"].copy_(mom)
         g["graph"].replay()
-        self.t += 1
-        ppo_capi.chk(ppo_capi.lib().ppo_clip_adam(self.params.data_ptr(), self.grads.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
-                                                   self.P, self.t, float(lr), 0.9, 0.999, 1e-5,
-                                                   float(self.max_grad_norm) if self.max_grad_norm is not None else 0.0,
-                                                   self.stats.data_ptr(), t.cuda.current_stream(self.device).cuda_stream))
+        self._adam_step(lr, t.cuda.current_stream(self.device).cuda_stream)
         return g["out"].clone()
 
     # multi-GPU step graph (needs RCCL: gloo's collectives run on the host and cannot be captured)
@@ -254,8 +215,6 @@ class PPOModel(object):
         if not self.trainable:
             raise RuntimeError("model built with trainable=False")
         t = self._t
-        L = ppo_capi.lib()
-        D, A = self.spec.ob_dim, self.spec.ac_dim
         if obs.stride(1) != 1:
             raise ValueError("obs rows must have unit inner stride")
         em = self._epoch_moments if (self.comm is not None and self.equal_counts and mb_index is not None) else None
@@ -270,7 +229,6 @@ class PPOModel(object):
                 if out is not None:
                     return out
         st = t.cuda.current_stream(self.device).cuda_stream
-        ip = ppo_capi.ptr(idx)
         if n == 0:
             # a rank whose shard ran out of rows (opponent-data reuse gives ranks different batch sizes) still takes part in
             # both collectives of the step with an empty contribution, so every rank issues the same sequence of all-reduces
@@ -279,31 +237,13 @@ class PPOModel(object):
             self.moments.zero_()
             sdist.allreduce_moments(self.moments, self.comm)
             self.grads.zero_()
-            sdist.allreduce_fused(self.grads, self.comm)
-            self.stats.copy_(self.grads[self.P:self.P + ppo_capi.NSTATS].to(t.float64))
-            return self._finish_step(lr, sync, t.empty(0, dtype=t.float32, device=self.device), st)
-        # advantages: returns - values, normalised over the (global) minibatch (model.py:180-185)
-        if mom_k is not None:          # the epoch's moments were all-reduced in one collective (prepare_epoch): nothing to exchange here
-            self.moments.copy_(mom_k)
-        else:
-            ppo_capi.chk(L.ppo_adv_moments_ws(returns.data_ptr(), values.data_ptr(), ip, n, self.moments.data_ptr(), self.adv_ws.data_ptr(), st))
-            sdist.allreduce_moments(self.moments, self.comm)
-        adv = t.empty(n, dtype=t.float32, device=self.device)
-        ppo_capi.chk(L.ppo_adv_normalize(returns.data_ptr(), values.data_ptr(), ip, n, self.moments.data_ptr(), adv.data_ptr(), st))
-        if self.comm is None:
-            count = float(n)
-        elif self.equal_counts:       # every rank contributes the same number of rows: no host read-back of the all-reduced count
-            count = float(n) * self._t.distributed.get_world_size(self.comm)
-        else:
-            count = float(self.moments[2].item())
-        self.stats.zero_()
-        log_ratio = t.empty(n, dtype=t.float32, device=self.device)
-        ppo_capi.chk(L.ppo_grad(self.params.data_ptr(), obs.data_ptr(), obs.stride(0), D, A, actions.data_ptr(), adv.data_ptr(),
-                                returns.data_ptr(), neglogpacs.data_ptr(), weights.data_ptr(), ip, n, 1.0 / count,
-                                float(cliprange), self.ent_coef, self.vf_coef, self.grads.data_ptr(), self.stats.data_ptr(),
-                                log_ratio.data_ptr(), self.workspace.data_ptr(), st))
-        if self.comm is not None:
+            self.stats.zero_()
             self._allreduce_grad_and_stats()
+            return self._finish_step(lr, sync, t.empty(0, dtype=t.float32, device=self.device), st)
+        # advantages: returns - values, normalised over the (global) minibatch (model.py:180-185); with ``mom_k`` the epoch's moments were
+        # all-reduced in one collective (prepare_epoch) and there is nothing to exchange here
+        adv, log_ratio = (t.empty(n, dtype=t.float32, device=self.device) for _ in range(2))
+        self._launch_loss_grad(obs, returns, actions, values, neglogpacs, weights, idx, n, cliprange, adv, log_ratio, st, mom=mom_k)
         return self._finish_step(lr, sync, log_ratio, st)
 
     def _loss_stats(self, st):
@@ -316,15 +256,9 @@ class PPOModel(object):
         return out5
 
     def _finish_step(self, lr, sync, log_ratio, st):
-        t = self._t
-        A = self.spec.ac_dim
         # loss means + entropy of the distribution the loss was evaluated with (before the parameter update), model.py:69
         out5 = self._loss_stats(st)
-        self.t += 1
-        ppo_capi.chk(ppo_capi.lib().ppo_clip_adam(self.params.data_ptr(), self.grads.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.P,
-                                                   self.t, float(lr), 0.9, 0.999, 1e-5,
-                                                   float(self.max_grad_norm) if self.max_grad_norm is not None else 0.0,
-                                                   self.stats.data_ptr(), st))
+        self._adam_step(lr, st)
         if not sync:
             return out5
         o = out5.cpu().numpy()

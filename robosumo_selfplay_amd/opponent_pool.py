@@ -14,16 +14,11 @@ from . import policies
 
 def fill_lstm_net(n, base, spec):
     """Fill the ``ppo_capi.LstmNet`` ``n`` for the flat parameter vector of an ``lstm_param_shapes`` policy of ``spec`` (ob_dim,
-    ac_dim, nlstm) at device address ``base``: gate order i,f,o,u, no forget-bias offset, no embedding / observation filter --
-    the nets ``learn(network='lstm')`` trains."""
+    ac_dim, nlstm) at device address ``base``."""
     from . import ppo_capi
     D, A, H = spec.ob_dim, spec.ac_dim, spec.nlstm
-    o = np.concatenate([[0], np.cumsum([int(np.prod(s)) for s in policies.lstm_param_shapes(D, A, H)])]) * 4
-    n.ob_dim, n.emb_dim, n.hidden, n.ac_dim = D, 0, H, A
-    n.gate_order, n.forget_bias = ppo_capi.LSTM_GATES_IFOU, 0.0
-    n.wx, n.wh, n.b = base + int(o[0]), base + int(o[1]), base + int(o[2])
-    n.head_w, n.head_b, n.logstd, n.vf_w, n.vf_b = base + int(o[3]), base + int(o[4]), base + int(o[5]), base + int(o[6]), base + int(o[7])
-    return n
+    o = np.cumsum([0] + [int(np.prod(s)) for s in policies.lstm_param_shapes(D, A, H)[:-1]]) * 4
+    return ppo_capi.fill_lstm_net_ifou(n, D, A, H, base + o)
 
 
 class OpponentPool(object):

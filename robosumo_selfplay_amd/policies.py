@@ -198,13 +198,7 @@ class LstmPolicyWithValue(object):
         shapes = lstm_param_shapes(ob_dim, ac_dim, nlstm)
         assert len(param_list) == len(shapes) and all(tuple(np.shape(p)) == s for p, s in zip(param_list, shapes))
         self.tensors = [torch.from_numpy(np.ascontiguousarray(p, np.float32)).to(self.device) for p in param_list]
-        wx, wh, b, pw, pb, logstd, vw, vb = self.tensors
-        n = ppo_capi.LstmNet()
-        n.ob_dim, n.emb_dim, n.hidden, n.ac_dim = self.ob_dim, 0, self.nlstm, self.ac_dim
-        n.gate_order, n.forget_bias = ppo_capi.LSTM_GATES_IFOU, 0.0
-        n.wx, n.wh, n.b = wx.data_ptr(), wh.data_ptr(), b.data_ptr()
-        n.head_w, n.head_b, n.logstd, n.vf_w, n.vf_b = pw.data_ptr(), pb.data_ptr(), logstd.data_ptr(), vw.data_ptr(), vb.data_ptr()
-        self._net = n
+        self._net = ppo_capi.fill_lstm_net_ifou(ppo_capi.LstmNet(), ob_dim, ac_dim, nlstm, [x.data_ptr() for x in self.tensors])
         self.gen = torch.Generator(device=self.device)
 
     def initial_state(self, nenv):

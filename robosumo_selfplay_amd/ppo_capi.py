@@ -26,6 +26,15 @@ class LstmNet(C.Structure):
                 ("head_w", C.c_void_p), ("head_b", C.c_void_p), ("logstd", C.c_void_p), ("vf_w", C.c_void_p), ("vf_b", C.c_void_p)]
 
 
+def fill_lstm_net_ifou(n, ob_dim, ac_dim, nlstm, addrs):
+    """Fill ``n`` for a net of the layout ``learn(network='lstm')`` trains -- gate order i,f,o,u, no forget-bias offset, no embedding /
+    observation filter -- from the device addresses of its eight tensors in ``policies.lstm_param_shapes`` order."""
+    n.ob_dim, n.emb_dim, n.hidden, n.ac_dim = int(ob_dim), 0, int(nlstm), int(ac_dim)
+    n.gate_order, n.forget_bias = LSTM_GATES_IFOU, 0.0
+    n.wx, n.wh, n.b, n.head_w, n.head_b, n.logstd, n.vf_w, n.vf_b = (int(a) for a in addrs)
+    return n
+
+
 def lib():
     global _LIB
     if _LIB is None:

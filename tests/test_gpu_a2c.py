@@ -123,7 +123,7 @@ def test_a2c_graph_replay_matches_eager():
         oa = ma.train_device(3e-4, obs, ret, act, val, w)
         ob_ = mb.train_device(3e-4, obs, ret, act, val, w)
         assert torch.equal(oa, ob_) and torch.equal(ma.params, mb.params), step
-    assert len(ma._a2c["graphs"]) == 2
+    assert len(ma._graphs) == 2
 
 
 def test_ppo_checkpoint_loads_into_a2c_and_back(tmp_path):

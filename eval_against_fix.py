@@ -4,6 +4,8 @@ fixed policy-zoo MLP opponent on the GPU and print / save win, draw and lose rat
 
     python eval_against_fix.py --path results/RoboSumo-Ant-vs-Ant-v0-0 --opponent_path <zoo>/ant/mlp/agent-params-v3.npy \\
         --num_env 256 --rounds 512 --interval 10
+    python eval_against_fix.py --path results/RoboSumo-Ant-vs-Ant-v0-0 --opponent_path <zoo v1>.npy --opponent_path <zoo v3>.npy \
+        --fused --trials 512 --interval 10      (all checkpoints x opponents batched over the envs, one fused launch per 64 steps)
 """
 import argparse
 import json
@@ -16,7 +18,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 def main(argv):
     ap = argparse.ArgumentParser()
     ap.add_argument("--path", required=True, help="run directory holding checkpoints/NNNNN (run.py --log_path/<env>-<suffix>)")
-    ap.add_argument("--opponent_path", required=True, help="policy-zoo .npy (robosumo/robosumo/policy_zoo/assets/<agent>/mlp/...)")
+    ap.add_argument("--opponent_path", required=True, action="append",
+                    help="policy-zoo .npy (robosumo/robosumo/policy_zoo/assets/<agent>/mlp/...); with --fused it may be given several times")
     ap.add_argument("--env", default="RoboSumo-Ant-vs-Ant-v0")
     ap.add_argument("--num_env", type=int, default=256)
     ap.add_argument("--rounds", type=int, default=500)
@@ -27,8 +30,16 @@ def main(argv):
     ap.add_argument("--adjust_z", type=float, default=-0.5, help="Agent._adjust_z of every agent; the reference's evaluator sets -0.5 "
                     "(eval_robosumo_against_fix.py:108-115): the zoo nets were trained with the tatami surface at z = 0")
     ap.add_argument("--cfrc_mode", default="zero", choices=["zero", "rne_post"])
+    ap.add_argument("--fused", action="store_true", help="play every selected checkpoint against every opponent in fused match launches "
+                    "(matches.evaluate_history_against_zoo): zoo MLP opponents, exactly --trials games per checkpoint and opponent")
+    ap.add_argument("--trials", type=int, default=None, help="games per checkpoint and opponent with --fused (default: --rounds)")
     args = ap.parse_args(argv)
     import numpy as np
+    if args.fused:
+        return main_fused(args)
+    if len(args.opponent_path) != 1:
+        raise SystemExit("several --opponent_path need --fused")
+    args.opponent_path = args.opponent_path[0]
     from robosumo_selfplay_amd import policy_zoo
     from robosumo_selfplay_amd.model import PPOModel
     from robosumo_selfplay_amd.policies import build_policy
@@ -52,6 +63,29 @@ def main(argv):
     with open(os.path.join(args.path, "eval_against_fix.json"), "w") as f:
         json.dump(table, f)
     env.close()
+    return np.array(table)
+
+
+def main_fused(args):
+    import numpy as np
+    from robosumo_selfplay_amd import matches
+    if args.cfrc_mode != "zero":
+        raise SystemExit("--fused runs on the fused match launch, which refuses --cfrc_mode rne_post")
+    trials = args.trials if args.trials is not None else args.rounds
+    r = matches.evaluate_history_against_zoo(args.path, args.opponent_path, trials, start=args.start, interval=args.interval,
+                                             num_env=args.num_env, deterministic=not args.stochastic, fused=True, seed=args.seed,
+                                             adjust_z=args.adjust_z, env_id=args.env)
+    table = []
+    for cid in r["checkpoints"]:
+        row = [cid]
+        for k in range(len(r["opponents"])):       # one (win, draw, lose) triple per opponent, in --opponent_path order
+            x = r["results"][(cid, k)]
+            row += [x["win"], x["draw"], x["lose"]]
+            print("-----Episode %d win: %.2f, draw: %.2f, lose: %.2f (%d rounds, %d steps)-----" % (cid, x["win"], x["draw"], x["lose"],
+                                                                                               x["rounds"], x["env_steps"]))
+        table.append(row)
+    with open(os.path.join(args.path, "eval_against_fix.json"), "w") as f:
+        json.dump(table, f)
     return np.array(table)
 
 

@@ -162,6 +162,36 @@ typedef struct sumo_match_lstm {
 } sumo_match_lstm;
 int sumo_match_steps_lstm(sumo_handle_t h, const sumo_match_lstm* m, float* actions_dev, float* obs_dev, double* info_dev,
                           uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream);
+/* The fused launches against POLICY-ZOO MLP nets (the reference's robosumo/policy_zoo MLPPolicy(normalize=True), policy.py:23-91:
+ * tanh 64-64 trunks, running-mean observation filter clipped to +-obs_clip, input = the first ob_dim observation columns -- the
+ * observation without the time feature, eval_robosumo_against_fix.py:206).  A table of nzoo frozen nets of one ob_dim:
+ *   params  float32 [nzoo][Pz] flat vectors in the sumo_ppo.h layout for (ob_dim, the scene's ac_dim), Pz = ppo_param_count(ob_dim,
+ *           ac_dim): pi trunk, vf trunk (never read here), pi head, logstd, vf head
+ *   filt    float32 [nzoo][2][ob_dim]: the observation filter's mean | 1 / std (std = sqrt(max(var, 1e-2)), utils.py:30-32)
+ * The owning wave evaluates a zoo net as ppo_forward_filtered does (clip((x - mean) / std, +-obs_clip), tanh trunk, Gaussian head),
+ * bit for bit.  Zoo LSTM nets (policy.py:94-199) are not played here: they go through ppo_lstm_step.
+ *
+ * sumo_rollout_steps_zoo: sumo_rollout_steps with agent 1 played by a zoo net (learn(opponent_mode='fix'), reference
+ *   alg_ppo.py:194-206): per step and env the learner's policy and value nets on both observations, zoo net opponent_index[e]
+ *   (NULL = net 0) on both; the learner samples action 0 and the zoo net scores it, the zoo net samples action 1 (mean + exp(logstd)
+ *   * noise1) and the learner scores and values it; the zoo net's value trunk is not evaluated.  r->opponent_params must be NULL and
+ *   r->npool == z->nzoo; an opponent_index outside [0, nzoo) raises the launch's abort flag (sumo_rollout_status returns -20).
+ *   Everything else as sumo_rollout_steps.
+ * sumo_match_steps_zoo: sumo_match_steps with agent 1 played by zoo nets (eval_robosumo_against_fix.py:196-230): agent 0 acts with
+ *   checkpoint m->idx0[e] of m->params [m->nsnap][P], agent 1 with zoo net m->idx1[e] of z; noise, score, quota and the abort on a
+ *   bad index (idx0 against nsnap, idx1 against nzoo) as sumo_match_steps.
+ * Refused: whatever the sibling entry point refuses, ob_dim outside [1, the scene's ob_dim], nzoo < 1, missing params / filt,
+ * obs_clip <= 0. */
+typedef struct sumo_zoo_mlp {
+  const float* params;
+  const float* filt;
+  float obs_clip;   /* 5 for the zoo nets */
+  int nzoo, ob_dim;
+} sumo_zoo_mlp;
+int sumo_rollout_steps_zoo(sumo_handle_t h, const sumo_rollout* r, const sumo_zoo_mlp* z, float* actions_dev, float* obs_dev,
+                           double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream);
+int sumo_match_steps_zoo(sumo_handle_t h, const sumo_match* m, const sumo_zoo_mlp* z, float* actions_dev, float* obs_dev,
+                         double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream);
 /* cfrc_mode (reference agents.py:190-214 reads sim.data.cfrc_ext into 84 of the 121 observation entries):
  *   0 = zero (default): what the reference produces -- its MuJoCo 2.1 scenes declare no force / torque / accelerometer sensor, so
  *       mj_rnePostConstraint never runs and cfrc_ext stays at its reset value 0;

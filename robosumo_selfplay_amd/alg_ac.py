@@ -45,7 +45,7 @@ def check_config(network, use_opponent_data, comm):
 def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_data=None, eval_env=None, seed=None, nsteps=2048,
           ent_coef=0.0, lr=3e-4, vf_coef=0.5, max_grad_norm=0.5, gamma=0.99, lam=0.95, log_interval=10, save_interval=1,
           load_path=None, model_fn=None, update_fn=None, init_fn=None, mpi_rank_weight=1, comm=None, nagent=1, anneal_bound=500,
-          fix_opponent_path=None, rho_bar=10.0, c_bar=1.0, log_dir=None, verbose=True, opponent_pool=1, **network_kwargs):
+          fix_opponent_path=None, rho_bar=10.0, c_bar=1.0, log_dir=None, verbose=True, opponent_pool=1, fused_fix_opponent=False, **network_kwargs):
     check_config(network, use_opponent_data, comm)
     if opponent_mode not in ("ours", "random", "latest", "fix"):
         raise ValueError("opponent_mode %r" % (opponent_mode,))
@@ -79,6 +79,7 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
         m.act_model.seed((seed or 0) * 1000 + 17 * i)
     runner = Runner(env=env, models=models, nsteps=nsteps, nagent=nagent, gamma=gamma, lam=lam, rho_bar=rho_bar, c_bar=c_bar,
                     anneal_bound=anneal_bound)
+    runner.fused_fix_opponent = bool(fused_fix_opponent)     # opt-in, as in alg_ppo: the fix-mode zoo net inside the fused launch
     # opponent_pool = K > 1 (extension, as in alg_ppo): K snapshots resident in HBM, one per env tile, drawn by the selection law of
     # opponent_mode; K = 1 is the reference's single opponent for all envs
     pool = None

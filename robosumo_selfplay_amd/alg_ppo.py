@@ -135,7 +135,7 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
           ent_coef=0.0, lr=3e-4, vf_coef=0.5, max_grad_norm=0.5, gamma=0.99, lam=0.95, rho_bar=1.0, c_bar=1.0, log_interval=10,
           nminibatches=4, noptepochs=4, cliprange=0.2, save_interval=1, load_path=None, model_fn=None, update_fn=None, init_fn=None,
           nagent=1, anneal_bound=500, vgap=None, kl_threshold=None, neglogp_threshold=10000.0, log_dir=None, comm=None,
-          verbose=True, fix_opponent_path=None, opponent_pool=1, **network_kwargs):
+          verbose=True, fix_opponent_path=None, opponent_pool=1, fused_fix_opponent=False, **network_kwargs):
     import torch
     if seed is not None:                                                # set_global_seeds (misc_util.py:48-62)
         np.random.seed(seed)
@@ -180,6 +180,8 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
         m.act_model.seed((seed or 0) * 1000 + 17 * i + rank)
     runner = Runner(env=env, models=models, nsteps=nsteps, nagent=nagent, gamma=gamma, lam=lam, rho_bar=rho_bar, c_bar=c_bar,
                     anneal_bound=anneal_bound)
+    # opt-in: in opponent_mode='fix' the zoo MLP net plays inside the fused rollout launch (Runner.fused_fix_opponent: another noise stream)
+    runner.fused_fix_opponent = bool(fused_fix_opponent)
     # opponent_pool = K > 1 (extension, BASELINE config 5): K frozen snapshots stay resident in HBM and every env plays against its own
     # one (opponent_pool.py); each update draws K snapshots by the selection law of ``opponent_mode`` instead of one.  K = 1 is the
     # reference: one snapshot for all parallel envs (alg_ppo.py:213-214).

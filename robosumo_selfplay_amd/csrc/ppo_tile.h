@@ -192,6 +192,24 @@ __device__ __forceinline__ Net vf_net(const float* p_, const PL& L) {
   return n;
 }
 
+// Policy trunk of a policy-zoo MLP net (policy_zoo MLPPolicy(normalize=True), policy.py:23-91) on ROWS staged rows of x [ROWS][XS]:
+// the rows are filtered IN PLACE -- clip((x - mean) * invstd, +-clip) on the first Dz columns, the expression and order of stage_x
+// in ppo_kernels.hip; columns Dz .. XS are zeroed -- then the tanh trunk of input width Dz runs on them.  filt: mean [Dz] | 1 / std
+// [Dz].  The caller has finished every read of the raw rows (wave_sync before the call); the raw tile is gone afterwards.
+template <int ROWS>
+__device__ __forceinline__ f32x4 zoo_trunk_forward(const Net& net, const float* filt_, float clip, float* xbuf, int XS, int Dz, float* h1buf,
+                                                   float* h2buf, int lane) {
+  const float PT_GAS* filt = pt_global(filt_);
+  for (int k = lane; k < XS; k += PT_WAVE) {
+    const bool cok = k < Dz;
+    const float fm = cok ? filt[k] : 0.0f, fi = cok ? filt[Dz + k] : 0.0f;
+#pragma unroll
+    for (int r = 0; r < ROWS; r++) xbuf[r * XS + k] = cok ? fminf(fmaxf((xbuf[r * XS + k] - fm) * fi, -clip), clip) : 0.0f;
+  }
+  wave_sync();
+  return trunk_forward<true, ROWS>(net, xbuf, XS, Dz, h1buf, h2buf, lane);
+}
+
 // One row of the diagonal-Gaussian head (baselines distributions.py:227-251) in the tile's D layout: lane i < A of the row's
 // 16-lane group holds the mean m of action dimension i.  sample: act = m + std * noise, else `act` is given.
 // Returns -log pi(act | obs) of the row (every lane of the group).

@@ -2534,6 +2534,14 @@ sumo_cfrc_kernel(const Params* P, StepArgs a, CfrcArgs q) {
 #define PROF_STRIDE 4
 #define PPROBE(slot) do { } while (0)
 #endif
+// Policy-zoo MLP opponents (sumo_rollout_steps_zoo / sumo_match_steps_zoo, POLICY 4 / 5): the table's filter rows, clip, size,
+// input width and parameter layout.  The table's parameter rows [nzoo][Lz.P] travel in RolloutArgs::opponent.
+struct ZooArgs {
+  const float* filt;                 // [nzoo][2][Dz]: mean | 1 / std
+  float clip;
+  int nzoo, Dz;
+  ParamLayout Lz;                    // make_layout(Dz, A)
+};
 struct RolloutArgs {
   const float *learner, *opponent;   // flat parameter vectors; opponent: [npool][P]
   const int32_t* opp_idx;            // [N] snapshot per env or NULL
@@ -2549,7 +2557,9 @@ struct RolloutArgs {
   ParamLayout L;
   // recurrent policies (sumo_rollout_steps_lstm): the learner's net, the opponent snapshots (device array) with the snapshot of
   // every 16-env tile of the whole env set (NULL: snapshot 0), and the acting nets' states [N][2 hidden] (c | h) per agent
-  ppo_lstm_net lnet;
+  // (the zoo modes evaluate no recurrent net: their fields overlay lnet, so the struct -- and with it the kernel-argument
+  // segment every instantiation reads -- keeps its size and offsets)
+  union { ppo_lstm_net lnet; ZooArgs zoo; };
   const ppo_lstm_net* onets;
   const int32_t* tile_net;
   float *st0, *st1;
@@ -2880,6 +2890,92 @@ __device__ __forceinline__ void rollout_policy_phase_match_lstm(C& c, const SA& 
   wave_sync();
 }
 
+// ---- policy-zoo MLP opponents (POLICY 4 / 5) ----
+// Row j of a table of n entries, checked: an index outside [0, n) raises the launch's abort flag and plays row 0.
+template <class SA>
+__device__ __forceinline__ int policy_checked_row(const SA& a, int lane, int j, int n) {
+  if ((unsigned)j >= (unsigned)n) {
+    if (lane == 0) __hip_atomic_store(pt_global(a.abort_flag), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    j = 0;
+  }
+  return j;
+}
+
+// Rollout against a policy-zoo MLP net (sumo_rollout_steps_zoo, POLICY 4; learn(opponent_mode='fix'), reference alg_ppo.py:194-206):
+// rollout_policy_phase with the opponent's policy trunk replaced by zoo net opp_idx[e]: the learner's policy and value trunks run
+// on the raw tile first (the raw observations are in the rollout record by then), the tile is then filtered in place and the zoo
+// net's tanh trunk of input width Dz runs on it (zoo_trunk_forward: no second tile).  Heads and record as rollout_policy_phase;
+// the zoo net's value trunk is not evaluated.  Every number equals ppo_forward (learner) / ppo_forward_filtered (zoo net) bit for bit.
+template <class C, class SA, class RA>
+__device__ __forceinline__ void rollout_policy_phase_zoo(C& c, const SA& a, const RA& r, int e, int s) {
+  const int lane = c.lane, i = lane & 15, kq = lane >> 4;
+  const int D = r.L.D, A = r.L.A, XS = r.XS, Dz = r.zoo.Dz;
+  float* xbuf = (float*)(c.sm + r.lds_off);        // [2][XS] | h1 [2][PT_HS] | h2 [2][PT_HS]
+  float* h1 = xbuf + 2 * XS;
+  float* h2 = h1 + 2 * PT_HS;
+  const size_t col = (size_t)r.env_offset + e;
+  const size_t slot0 = ((size_t)0 * r.T + s) * r.Ntot + col, slot1 = ((size_t)1 * r.T + s) * r.Ntot + col;
+  policy_load_obs<false, true>(a, r, e, lane, xbuf, D, XS, slot0, slot1);
+  if (lane < 2) policy_record_done(r, lane, slot0, slot1, policy_prev_done(a, e));
+  wave_sync();
+  const int jz = policy_checked_row(a, lane, r.opp_idx ? pt_global(r.opp_idx)[e] : 0, r.zoo.nzoo);
+  const float PT_GAS* lp = pt_global(r.learner);
+  const float PT_GAS* op = pt_global(r.opponent) + (size_t)jz * r.zoo.Lz.P;
+  const f32x4 mL = trunk_forward<false, 2>(pi_net((const float*)lp, r.L), xbuf, XS, D, h1, h2, lane);
+  wave_sync();
+  const f32x4 vL = trunk_forward<false, 2>(vf_net((const float*)lp, r.L), xbuf, XS, D, h1, h2, lane);
+  wave_sync();
+  const f32x4 mO = zoo_trunk_forward<2>(pi_net((const float*)op, r.zoo.Lz), r.zoo.filt + (size_t)jz * 2 * Dz, r.zoo.clip, xbuf, XS, Dz, h1, h2, lane);
+  // heads: row 0 = agent 0 (learner acts, zoo net scores), row 1 = agent 1 (zoo net acts, learner scores and values)
+  const bool colk = i < A;
+  const float lsL = colk ? lp[r.L.logstd + i] : 0.0f, lsO = colk ? op[r.zoo.Lz.logstd + i] : 0.0f;
+  const float stdL = expf(lsL), stdO = expf(lsO);
+  const float sumL = row16_sum(lsL), sumO = row16_sum(lsO);
+  const bool ok = colk && kq == 0;                  // rows 0 and 1 live in the first 16 lanes (D layout: rows 4 kq + r)
+  const size_t nz = policy_noise_index(a, e, s, A, i);
+  const float n0 = ok ? pt_global(r.noise0)[nz] : 0.0f, n1 = ok ? pt_global(r.noise1)[nz] : 0.0f;
+  float act0 = 0.0f, act1 = 0.0f;
+  const float nlp0 = gauss_row(mL[0], stdL, sumL, ok, true, n0, act0, A);      // learner samples for agent 0 ...
+  const float onlp0 = gauss_row(mO[0], stdO, sumO, ok, false, 0.0f, act0, A);  // ... the zoo net scores that action
+  const float onlp1 = gauss_row(mO[1], stdO, sumO, ok, true, n1, act1, A);     // zoo net samples for agent 1 ...
+  const float nlp1 = gauss_row(mL[1], stdL, sumL, ok, false, 0.0f, act1, A);   // ... the learner scores it
+  if (ok) policy_commit_actions<true>(c, a, r, e, i, act0, act1, A, slot0, slot1);
+  if (lane == 0) policy_record_scalars(r, slot0, slot1, nlp0, nlp1, onlp0, onlp1, vL[0], vL[1]);
+  wave_sync();   // the action buffer is read back by the env step (other lanes), the scratch region becomes the mass matrix again
+}
+
+// Matches against policy-zoo MLP nets (sumo_match_steps_zoo, POLICY 5; the reference's eval_robosumo_against_fix.py:196-230):
+// agent 0 acts with checkpoint idx0[e] of snaps [nsnap][P] on the raw tile (as rollout_policy_phase_match), agent 1 with zoo net
+// idx1[e] on the tile filtered in place afterwards.  Noise, score counters and quota as sumo_match_steps.
+template <class C, class SA, class RA>
+__device__ __forceinline__ void rollout_policy_phase_match_zoo(C& c, const SA& a, const RA& r, int e, int s) {
+  const int lane = c.lane, i = lane & 15, kq = lane >> 4;
+  const int D = r.L.D, A = r.L.A, XS = r.XS, Dz = r.zoo.Dz;
+  float* xbuf = (float*)(c.sm + r.lds_off);        // [2][XS] | h1 [2][PT_HS] | h2 [2][PT_HS]
+  float* h1 = xbuf + 2 * XS;
+  float* h2 = h1 + 2 * PT_HS;
+  policy_load_obs<false, false>(a, r, e, lane, xbuf, D, XS);
+  wave_sync();
+  const int j0 = policy_checked_row(a, lane, pt_global(r.idx0)[e], r.nsnap);
+  const int j1 = policy_checked_row(a, lane, pt_global(r.idx1)[e], r.zoo.nzoo);
+  const float PT_GAS* p0 = pt_global(r.snaps) + (size_t)j0 * r.L.P;
+  const float PT_GAS* p1 = pt_global(r.opponent) + (size_t)j1 * r.zoo.Lz.P;
+  const f32x4 m0 = trunk_forward<false, 2>(pi_net((const float*)p0, r.L), xbuf, XS, D, h1, h2, lane);
+  wave_sync();
+  const f32x4 m1 = zoo_trunk_forward<2>(pi_net((const float*)p1, r.zoo.Lz), r.zoo.filt + (size_t)j1 * 2 * Dz, r.zoo.clip, xbuf, XS, Dz, h1, h2, lane);
+  const bool ok = i < A && kq == 0;                 // rows 0 and 1 live in the first 16 lanes (D layout: rows 4 kq + r)
+  float act0 = m0[0], act1 = m1[1];
+  if (r.noise0) {
+    const float ls0 = ok ? p0[r.L.logstd + i] : 0.0f, ls1 = ok ? p1[r.zoo.Lz.logstd + i] : 0.0f;
+    const size_t nz = policy_noise_index(a, e, s, A, i);
+    const float n0 = ok ? pt_global(r.noise0)[nz] : 0.0f, n1 = ok ? pt_global(r.noise1)[nz] : 0.0f;
+    (void)gauss_row(m0[0], expf(ls0), 0.0f, ok, true, n0, act0, A);
+    (void)gauss_row(m1[1], expf(ls1), 0.0f, ok, true, n1, act1, A);
+  }
+  if (ok) policy_commit_actions<false>(c, a, r, e, i, act0, act1);
+  wave_sync();   // the action buffer is read back by the env step (other lanes), the scratch region becomes the mass matrix again
+}
+
 // Match post phase: where agent 0's episode ended in the step, score it from the step's winner flags (info[.][7] bit 0, just
 // written by this lane): a win if agent 0 carries the flag, a loss if only agent 1 does, a draw otherwise (timeouts, diverged states)
 // -- policy_zoo._evaluate_against's rule.  Counted while wins + losses + draws < quota.
@@ -2919,6 +3015,7 @@ __device__ __forceinline__ void rollout_post_phase(C& c, const SA& a, const RA& 
 // evaluations of every step (the kernel sits exactly at its 256-register budget).  The pointer addresses the kernel-argument
 // segment itself, where the runtime has placed the struct at launch (no separate copy to keep alive).
 struct RolloutLaunch { StepArgs a; RolloutArgs r; };
+static_assert(sizeof(ZooArgs) <= sizeof(ppo_lstm_net), "ZooArgs overlays RolloutArgs::lnet");
 
 // Scheduling: the launch is a set of persistent waves (one per wave slot of the chip) that draw TICKETS from a global counter;
 // ticket t is step t / N of env t % N.  Env steps differ in cost by 3x (contacts, Newton iterations, agents wrestling), so
@@ -2935,7 +3032,9 @@ struct RolloutLaunch { StepArgs a; RolloutArgs r; };
 
 template <int NV, int POLICY, int SL = 0>   // POLICY 0: MLP(64,64) policy / value nets; 1: LSTM(128) with shared value head; 2: MLP matches
                                             // (sumo_match_steps: score counters instead of rollout buffers); 3: LSTM(128) matches
-                                            // (sumo_match_steps_lstm); SL 1: static Layout
+                                            // (sumo_match_steps_lstm); 4: MLP learner against policy-zoo MLP nets
+                                            // (sumo_rollout_steps_zoo); 5: MLP checkpoints against policy-zoo MLP nets
+                                            // (sumo_match_steps_zoo); SL 1: static Layout
 __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(SUMO_WPE_OF(NV), SUMO_WPE_OF(NV))))
 sumo_rollout_kernel(const Params* P, RolloutLaunch launch_args) {
   // `launch_args` is read in place from the kernel-argument segment (second argument, 8-byte aligned right behind P) through a
@@ -2991,6 +3090,8 @@ sumo_rollout_kernel(const Params* P, RolloutLaunch launch_args) {
     if constexpr (POLICY == 1) rollout_policy_phase_lstm<128>(c, lp->a, lp->r, e, s);
     else if constexpr (POLICY == 2) rollout_policy_phase_match(c, lp->a, lp->r, e, s);
     else if constexpr (POLICY == 3) rollout_policy_phase_match_lstm<128>(c, lp->a, lp->r, e, s);
+    else if constexpr (POLICY == 4) rollout_policy_phase_zoo(c, lp->a, lp->r, e, s);
+    else if constexpr (POLICY == 5) rollout_policy_phase_match_zoo(c, lp->a, lp->r, e, s);
     else rollout_policy_phase(c, lp->a, lp->r, e, s);
 #ifdef SUMO_DBG_HARD_BARRIER
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -3003,7 +3104,7 @@ sumo_rollout_kernel(const Params* P, RolloutLaunch launch_args) {
     asm volatile("" : "+s"(e), "+s"(k));
     lp = launder_sptr(LP);
     s = lp->r.s0 + k;
-    if constexpr (POLICY >= 2) rollout_post_phase_match(c, lp->a, lp->r, e);
+    if constexpr (POLICY == 2 || POLICY == 3 || POLICY == 5) rollout_post_phase_match(c, lp->a, lp->r, e);
     else rollout_post_phase(c, lp->a, lp->r, e, s);
     prof = lp->r.prof;
     if (prof && c.lane == 0) {
@@ -3852,6 +3953,8 @@ static int rollout_launch(sumo_engine* E, const RolloutArgs& r, int policy, cons
         void (*kernel)(const Params*, RolloutLaunch) = policy == 1   ? sumo_rollout_kernel<NV, 1, SL>
                                                        : policy == 2 ? sumo_rollout_kernel<NV, 2, SL>
                                                        : policy == 3 ? sumo_rollout_kernel<NV, 3, SL>
+                                                       : policy == 4 ? sumo_rollout_kernel<NV, 4, SL>
+                                                       : policy == 5 ? sumo_rollout_kernel<NV, 5, SL>
                                                                      : sumo_rollout_kernel<NV, 0, SL>;
         hipLaunchKernelGGL(kernel, g_, b_, lds_, st_, E->d_params, rl);
       }))
@@ -4020,6 +4123,60 @@ extern "C" int sumo_match_steps_lstm(sumo_handle_t E, const sumo_match_lstm* mo,
   copy_match_fields(r, mo, E->N);
   if (int rc = place_lstm_scratch(E, od, 2, r)) return rc;   // previous latent, new latent
   return rollout_launch(E, r, 3, b, stream);
+}
+
+// the zoo table of sumo_rollout_steps_zoo / sumo_match_steps_zoo: checks, then the fields of RolloutArgs it fills
+static int place_zoo_table(RolloutArgs& r, const sumo_zoo_mlp* z, int od, int ad) {
+  if (!z->params || !z->filt) FAIL(-2, "sumo_zoo_mlp: missing buffer (params / filt)");
+  if (z->nzoo < 1) FAIL(-7, "nzoo %d: the zoo table needs at least one entry", z->nzoo);
+  if (z->ob_dim < 1 || z->ob_dim > od)
+    FAIL(-4, "zoo ob_dim %d outside [1, %d]: a policy-zoo MLP net reads the first ob_dim columns of the scene's observation", z->ob_dim, od);
+  if (!(z->obs_clip > 0.0f)) FAIL(-9, "obs_clip %g must be positive", (double)z->obs_clip);
+  r.opponent = z->params;
+  r.zoo.filt = z->filt; r.zoo.clip = z->obs_clip; r.zoo.nzoo = z->nzoo; r.zoo.Dz = z->ob_dim; r.zoo.Lz = make_layout(z->ob_dim, ad);
+  return 0;
+}
+
+extern "C" int sumo_rollout_steps_zoo(sumo_handle_t E, const sumo_rollout* ro, const sumo_zoo_mlp* z, float* actions_dev, float* obs_dev,
+                                      double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
+  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
+  if (int rc = check_launch_args(E, ro, b)) return rc;
+  if (!z) FAIL(-1, "bad arguments");
+  if (!ro->learner_params || rollout_buffer_missing(ro)) FAIL(-2, "sumo_rollout: missing buffer");
+  if (ro->opponent_params) FAIL(-2, "sumo_rollout_steps_zoo: opponent_params must be NULL (the opponents are the zoo table's nets)");
+  int od = 0, ad = 0;
+  if (int rc = rollout_scene(E, ro->T, ro->Ntot, ro->env_offset, ro->s0, ro->K, &od, &ad)) return rc;
+  if (int rc = check_dims(ro->ob_dim, ro->ac_dim, od, ad)) return rc;
+  if (ro->npool != z->nzoo) FAIL(-7, "npool %d must equal the zoo table's nzoo %d", ro->npool, z->nzoo);
+  HIPCHK(hipSetDevice(E->device));
+  RolloutArgs r;
+  memset(&r, 0, sizeof r);
+  if (int rc = place_zoo_table(r, z, od, ad)) return rc;
+  r.learner = ro->learner_params; r.opp_idx = ro->opponent_index;
+  copy_rollout_fields(r, ro);
+  if (int rc = place_mlp_scratch(E, ro->ob_dim, ro->ac_dim, r)) return rc;
+  return rollout_launch(E, r, 4, b, stream);
+}
+
+extern "C" int sumo_match_steps_zoo(sumo_handle_t E, const sumo_match* mo, const sumo_zoo_mlp* z, float* actions_dev, float* obs_dev,
+                                    double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
+  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
+  if (int rc = check_launch_args(E, mo, b)) return rc;
+  if (!z) FAIL(-1, "bad arguments");
+  if (!mo->params) FAIL(-2, "sumo_match: missing buffer");
+  if (int rc = check_match_buffers(mo, "sumo_match")) return rc;
+  int od = 0, ad = 0;
+  if (int rc = rollout_scene(E, mo->T, E->N, 0, mo->s0, mo->K, &od, &ad)) return rc;
+  if (int rc = check_dims(mo->ob_dim, mo->ac_dim, od, ad)) return rc;
+  if (int rc = check_match_counts(mo)) return rc;
+  HIPCHK(hipSetDevice(E->device));
+  RolloutArgs r;
+  memset(&r, 0, sizeof r);
+  if (int rc = place_zoo_table(r, z, od, ad)) return rc;
+  r.snaps = mo->params;
+  copy_match_fields(r, mo, E->N);
+  if (int rc = place_mlp_scratch(E, mo->ob_dim, mo->ac_dim, r)) return rc;
+  return rollout_launch(E, r, 5, b, stream);
 }
 
 #ifdef SUMO_POLICY_PROBE

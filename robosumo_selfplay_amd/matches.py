@@ -268,10 +268,11 @@ def _check_env(env, table):
         raise ValueError("matches run on the fused launch, which refuses cfrc_mode 'rne_post'")
 
 
-def _fused_groups(env, entry, struct, fill, idx0, idx1, score, quota, K, noise):
-    """The per-group loop of the two fused match launches: a ``struct`` (capi.Match / capi.MatchLstm) whose own fields
+def _fused_groups(env, entry, struct, fill, idx0, idx1, score, quota, K, noise, extra=()):
+    """The per-group loop of the fused match launches: a ``struct`` (capi.Match / capi.MatchLstm) whose own fields
     ``fill(mo, sl)`` sets and whose shared fields (indices, window, quota, noise, score) are set here, passed to the engine's
-    ``entry`` method with the group's env-side pointers; raises if the launch was cut short (``rollout_status``)."""
+    ``entry`` method (followed by ``extra``: the zoo table's struct) with the group's env-side pointers; raises if the launch
+    was cut short (``rollout_status``)."""
     for g in range(env.groups):
         sl = env._gs(g)
         mo = struct()
@@ -284,7 +285,7 @@ def _fused_groups(env, entry, struct, fill, idx0, idx1, score, quota, K, noise):
             mo.noise0, mo.noise1 = keep[0].data_ptr(), keep[1].data_ptr()
         mo.score = score[sl].data_ptr()
         E = env.engines[g]
-        getattr(E, entry)(mo, *env.env_ptrs(g), stream=env._stream())
+        getattr(E, entry)(mo, *extra, *env.env_ptrs(g), stream=env._stream())
         E.rollout_status()
         del keep
 
@@ -311,14 +312,16 @@ def _runs(idx):
     return [(int(s), int(e), int(idx[s])) for s, e in zip(starts, ends)]
 
 
-def _stepwise(env, table, idx0, idx1, score, quota, K, noise, forward, masked):
-    """The step-by-step loop of both kinds: per step and side, ``forward(k, side, rows, noise rows or None, action rows, mask
+def _stepwise(env, table, idx0, idx1, score, quota, K, noise, forward, masked, capacity1=None):
+    """The step-by-step loop of every kind: per step and side, ``forward(k, side, rows, noise rows or None, action rows, mask
     rows or None)`` for every run ``rows = slice(s, e)`` of envs that share snapshot ``k``, then ``step_device`` and the score
-    update.  ``masked``: the previous step's done flags of each side are passed as float32 masks.  idx0 / idx1 are host arrays."""
+    update.  ``masked``: the previous step's done flags of each side are passed as float32 masks.  idx0 / idx1 are host arrays;
+    ``capacity1``: size of the table idx1 indexes where that is not ``table`` (zoo opponents)."""
     import torch
     idx0, idx1 = np.asarray(idx0, np.int64), np.asarray(idx1, np.int64)
-    if min(idx0.min(), idx1.min()) < 0 or max(idx0.max(), idx1.max()) >= table.capacity:
-        raise ValueError("snapshot index outside [0, %d)" % table.capacity)
+    cap1 = table.capacity if capacity1 is None else int(capacity1)
+    if min(idx0.min(), idx1.min()) < 0 or idx0.max() >= table.capacity or idx1.max() >= cap1:
+        raise ValueError("snapshot index outside [0, %d) / [0, %d)" % (table.capacity, cap1))
     A, N = table.spec.ac_dim, env.num_envs
     acts = env.act_dev                          # the env's action buffer receives both actions, as in the fused launch
     act = [torch.empty((N, A), dtype=torch.float32, device=env.device) for _ in range(2)]
@@ -396,6 +399,54 @@ def match_steps_stepwise_lstm(env, table, idx0, idx1, states, score, quota, K, n
     _stepwise(env, table, idx0, idx1, score, quota, K, noise, forward, masked=True)
 
 
+def _check_zoo(env, table, zoo_table):
+    _check_env(env, table)
+    if getattr(table, "recurrent", False):
+        raise ValueError("LSTM checkpoints do not play against zoo nets in the fused launch (MLP(64,64) checkpoints only)")
+    if zoo_table.ac_dim != table.spec.ac_dim or not 1 <= zoo_table.ob_dim <= table.spec.ob_dim:
+        raise ValueError("zoo table (ob_dim %d, ac_dim %d) does not fit the env (%d, %d): a zoo MLP net reads the first ob_dim "
+                         "observation columns" % (zoo_table.ob_dim, zoo_table.ac_dim, table.spec.ob_dim, table.spec.ac_dim))
+
+
+def zoo_match_steps_fused(env, table, zoo_table, idx0, idx1, score, quota, K, noise=None):
+    """K match steps of MLP checkpoints (agent 0: row idx0[e] of ``table``) against policy-zoo MLP nets (agent 1: row idx1[e] of
+    ``zoo_table``, a :class:`policy_zoo.ZooTable`) in one ``sumo_match_steps_zoo`` launch per env group; arguments as
+    :func:`match_steps_fused`."""
+    from . import capi
+    _check_zoo(env, table, zoo_table)
+
+    def fill(mo, sl):
+        mo.params = table.params.data_ptr()
+        mo.nsnap, mo.ob_dim, mo.ac_dim = table.capacity, table.spec.ob_dim, table.spec.ac_dim
+
+    _fused_groups(env, "match_steps_zoo", capi.Match, fill, idx0, idx1, score, quota, K, noise, extra=(zoo_table.struct(),))
+
+
+def zoo_match_steps_stepwise(env, table, zoo_table, idx0, idx1, score, quota, K, noise=None):
+    """The same K steps step by step: per step one ``ppo_forward`` launch for every run of envs that share a checkpoint, one
+    ``ppo_forward_filtered`` launch (what ``ZooMLPPolicy.act`` runs) for every run that shares a zoo net, then ``step_device`` and
+    the score update.  idx0 / idx1 are host arrays."""
+    import torch
+    from . import ppo_capi
+    _check_zoo(env, table, zoo_table)
+    D, A, Dz = table.spec.ob_dim, table.spec.ac_dim, zoo_table.ob_dim
+    L, st, obs = ppo_capi.lib(), env._stream(), env.obs_dev
+    nlp = torch.empty(env.num_envs, dtype=torch.float32, device=env.device)
+
+    def forward(k, side, rows, nz, out, _mask):
+        n, ob = rows.stop - rows.start, obs[rows, side].data_ptr()
+        if side == 0:
+            ppo_capi.chk(L.ppo_forward(table.params[k].data_ptr(), ob, n, obs.stride(0), D, A, ppo_capi.FWD_PI, ppo_capi.ptr(nz), None,
+                                       out.data_ptr(), nlp[rows].data_ptr(), None, None, st))
+        else:
+            f = zoo_table.filt[k]
+            ppo_capi.chk(L.ppo_forward_filtered(zoo_table.params[k].data_ptr(), ob, n, obs.stride(0), Dz, A,
+                                                ppo_capi.FWD_PI | ppo_capi.FWD_TANH, f[0].data_ptr(), f[1].data_ptr(), zoo_table.obs_clip,
+                                                ppo_capi.ptr(nz), None, out.data_ptr(), nlp[rows].data_ptr(), None, None, st))
+
+    _stepwise(env, table, idx0, idx1, score, quota, K, noise, forward, masked=False, capacity1=zoo_table.capacity)
+
+
 def match_steps(env, table, idx0, idx1, states, score, quota, K, noise=None, fused=True):
     """K match steps of either table kind on either path: ``states`` is the pair of recurrent state tensors of an
     :class:`LstmSnapshotTable` (ignored for MLP tables); idx0 / idx1 are CUDA tensors (fused) or host arrays (step by step)."""
@@ -434,10 +485,26 @@ def play_matches(env, table, pairs, rounds_per_env, envs_per_pair, deterministic
     rounds_per_env, envs_per_pair, chunk = int(rounds_per_env), int(envs_per_pair), int(chunk)
     if rounds_per_env < 1 or chunk < 1:
         raise ValueError("rounds_per_env and chunk must be >= 1")
-    N, A = env.num_envs, table.spec.ac_dim
     recurrent = bool(getattr(table, "recurrent", False))
     if recurrent and fused and table.spec.nlstm != 128:
         raise ValueError("the fused match launch plays LSTM(128) policies only (got LSTM(%d)): use fused=False" % table.spec.nlstm)
+    new_states = None
+    if recurrent:                     # every match-up starts from the zero state (LstmPPOModel.initial_state)
+        import torch
+        new_states = lambda: tuple(torch.zeros((env.num_envs, 2 * table.spec.nlstm), dtype=torch.float32, device=env.device) for _ in range(2))
+    steps = lambda idx0, idx1, states, score, noise: match_steps(env, table, idx0, idx1, states, score, rounds_per_env, chunk, noise,
+                                                                 fused=fused)
+    return _play_batches(env, table.spec.ac_dim, pairs, rounds_per_env, envs_per_pair, deterministic, seed, adjust_z, chunk, fused,
+                         new_states, steps)
+
+
+def _play_batches(env, A, pairs, rounds_per_env, envs_per_pair, deterministic, seed, adjust_z, chunk, fused, new_states, steps):
+    """The batching behind :func:`play_matches` / :func:`play_against_zoo`: pairs in batches of contiguous env blocks
+    (:func:`plan_batches`, :func:`env_assignment`); per batch a seeded reset, fresh recurrent states (``new_states()`` or None) and
+    ``steps(idx0, idx1, states, score, noise)`` launches of ``chunk`` steps -- indices as CUDA tensors when ``fused``, else host
+    arrays -- until every env of the batch has its quota."""
+    import torch
+    N = env.num_envs
     batches = plan_batches(len(pairs), envs_per_pair, N)
     max_launches = -(-rounds_per_env * (env.model.timestep_limit + 1) // chunk) + 1   # every episode ends by the time limit
     gen = torch.Generator(device=env.device)
@@ -457,14 +524,11 @@ def play_matches(env, table, pairs, rounds_per_env, envs_per_pair, deterministic
             env.seeds = np.uint64(seed) + np.uint64(bn * N) + np.arange(N, dtype=np.uint64)
             env._needs_seed = True
             env.reset_device()
-            states = None
-            if recurrent:                     # every match-up starts from the zero state (LstmPPOModel.initial_state)
-                states = tuple(torch.zeros((N, 2 * table.spec.nlstm), dtype=torch.float32, device=env.device) for _ in range(2))
+            states = new_states() if new_states is not None else None
             launches = 0
             while True:
                 noise = None if deterministic else tuple(torch.randn((chunk, N, A), generator=gen, device=env.device) for _ in range(2))
-                match_steps(env, table, idx0 if fused else idx0_h, idx1 if fused else idx1_h, states, score, rounds_per_env, chunk, noise,
-                            fused=fused)
+                steps(idx0 if fused else idx0_h, idx1 if fused else idx1_h, states, score, noise)
                 launches += 1
                 if not bool((score.sum(1)[act_t] < rounds_per_env).any()):
                     break
@@ -481,6 +545,26 @@ def play_matches(env, table, pairs, rounds_per_env, envs_per_pair, deterministic
             torch.cuda.synchronize(env.device)
             env.set_adjust_z(prev_adjust)
     return out
+
+
+def play_against_zoo(env, table, zoo_table, pairs, rounds_per_env, envs_per_pair, deterministic=True, seed=0, adjust_z=EVAL_ADJUST_Z,
+                     chunk=64, fused=True):
+    """:func:`play_matches` with agent 1 played by policy-zoo MLP nets: ``pairs[p] = (i, j)`` is checkpoint row i of ``table`` (a
+    :class:`SnapshotTable`) as agent 0 against net j of ``zoo_table`` (a :class:`policy_zoo.ZooTable`) as agent 1 -- the games of
+    the reference's eval_robosumo_against_fix.py:196-230 (deterministic by default, as there).  Same batching, seeding, quota and
+    return value as :func:`play_matches`; ``fused=False`` plays the same games step by step (bit-identical envs and scores)."""
+    _check_zoo(env, table, zoo_table)
+    pairs = [(int(i), int(j)) for i, j in pairs]
+    for i, j in pairs:
+        if not (0 <= i < table.capacity and table.filled[i]) or not 0 <= j < zoo_table.capacity:
+            raise ValueError("pair (%d, %d) refers to an empty or non-existent checkpoint / zoo row" % (i, j))
+    rounds_per_env, envs_per_pair, chunk = int(rounds_per_env), int(envs_per_pair), int(chunk)
+    if rounds_per_env < 1 or chunk < 1:
+        raise ValueError("rounds_per_env and chunk must be >= 1")
+    fn = zoo_match_steps_fused if fused else zoo_match_steps_stepwise
+    steps = lambda idx0, idx1, _states, score, noise: fn(env, table, zoo_table, idx0, idx1, score, rounds_per_env, chunk, noise)
+    return _play_batches(env, table.spec.ac_dim, pairs, rounds_per_env, envs_per_pair, deterministic, seed, adjust_z, chunk, fused, None,
+                         steps)
 
 
 def _make_env(env_id, num_env, seed, env):
@@ -567,3 +651,59 @@ def round_robin(path, interval, trials, num_env=256, deterministic=False, seed=0
     for (i, j), r in zip(pairs, res):
         M["win"][i, j], M["draw"][i, j], M["loss"][i, j] = r["wins"] / trials, r["draws"] / trials, r["losses"] / trials
     return dict(versions=ids, results={p: r for p, r in zip(pairs, res)}, **M, **_network(kind))
+
+
+def select_checkpoints(ids, start=0, interval=1):
+    """The checkpoint ids eval_robosumo_against_fix.py evaluates: sorted, from ``start`` on, every ``interval``-th number."""
+    start, interval = int(start), int(interval)
+    if interval < 1:
+        raise ValueError("interval must be >= 1")
+    return [c for c in sorted(int(i) for i in ids) if c >= start and (c - start) % interval == 0]
+
+
+def plan_zoo_evaluation(n_checkpoints, n_opponents, trials, num_env):
+    """The pure part of :func:`evaluate_history_against_zoo`: every (checkpoint c, opponent o) pair, checkpoint-major, gets
+    ``envs_per_pair`` contiguous envs that play ``rounds_per_env`` games each (:func:`split_trials`: their product is ``trials``);
+    pairs fill the envs batch by batch (:func:`plan_batches`).  Returns dict(pairs, envs_per_pair, rounds_per_env, blocks) with
+    ``blocks[p] = (batch number, first env, end env)`` of pair p."""
+    if n_checkpoints < 1 or n_opponents < 1:
+        raise ValueError("need at least one checkpoint and one opponent")
+    epp, rpe = split_trials(trials, num_env)
+    pairs = [(c, o) for c in range(n_checkpoints) for o in range(n_opponents)]
+    blocks = [None] * len(pairs)
+    for bn, batch in enumerate(plan_batches(len(pairs), epp, num_env)):
+        for b, p in enumerate(batch):
+            blocks[p] = (bn, b * epp, (b + 1) * epp)
+    return dict(pairs=pairs, envs_per_pair=epp, rounds_per_env=rpe, blocks=blocks)
+
+
+def evaluate_history_against_zoo(path, opponent_paths, trials, start=0, interval=1, num_env=256, deterministic=True, fused=True, seed=0,
+                                 adjust_z=EVAL_ADJUST_Z, env_id="RoboSumo-Ant-vs-Ant-v0", chunk=64, env=None):
+    """eval_robosumo_against_fix.py on the fused launch: every selected checkpoint of run ``path`` (:func:`select_checkpoints` of
+    all of its saved versions) as agent 0 against every policy-zoo MLP file of ``opponent_paths`` as agent 1, exactly ``trials``
+    games per (checkpoint, opponent), all match-ups batched over the envs (:func:`plan_zoo_evaluation`) instead of one checkpoint
+    after the other.  Returns dict(checkpoints=[ids], opponents=[paths], results={(id, k): dict(win, draw, lose, rounds,
+    env_steps)}) with rates over ``rounds == trials`` games against opponent k."""
+    from .policy_zoo import ZooTable
+    if isinstance(opponent_paths, (str, os.PathLike)):
+        opponent_paths = [opponent_paths]
+    opponent_paths = [str(p) for p in opponent_paths]
+    ck = checkpoint_dir(path)
+    ids = select_checkpoints([f for f in os.listdir(ck) if f.isdigit() and os.path.isfile(os.path.join(ck, f))], start, interval)
+    if not ids:
+        raise ValueError("no checkpoints to evaluate in %s" % ck)
+    env, own = _make_env(env_id, num_env, seed, env)
+    try:
+        table = SnapshotTable.from_checkpoints(_spec_of(env), [os.path.join(ck, "%.5i" % c) for c in ids], env.device)
+        zoo_table = ZooTable(opponent_paths, table.spec.ac_dim, env.device)
+        plan = plan_zoo_evaluation(len(ids), len(opponent_paths), trials, env.num_envs)
+        res = play_against_zoo(env, table, zoo_table, plan["pairs"], plan["rounds_per_env"], plan["envs_per_pair"],
+                               deterministic=deterministic, seed=seed, adjust_z=adjust_z, chunk=chunk, fused=fused)
+    finally:
+        if own:
+            env.close()
+    out = {}
+    for (c, o), r in zip(plan["pairs"], res):
+        n = float(r["rounds"])
+        out[(ids[c], o)] = dict(win=r["wins"] / n, draw=r["draws"] / n, lose=r["losses"] / n, rounds=r["rounds"], env_steps=r["env_steps"])
+    return dict(checkpoints=ids, opponents=opponent_paths, results=out)

@@ -109,10 +109,12 @@ class PolicyWithValue(object):
             raise ValueError("expected a float32 CUDA matrix with unit inner stride")
         return x, False
 
-    def evaluate(self, obs, flags, given_action=None, deterministic=False, out=None):
-        """Returns dict(action, neglogp, value).  ``out`` may hold preallocated output tensors."""
+    def evaluate(self, obs, flags, given_action=None, deterministic=False, out=None, noise=None):
+        """Returns dict(action, neglogp, value).  ``out`` may hold preallocated output tensors; ``noise``: explicit standard-normal
+        rows (contiguous float32 CUDA [n, ac_dim]) for the sampled action instead of a draw from ``self.gen``."""
         t = self._t
         D, A = self.spec.ob_dim, self.spec.ac_dim
+        noise_in = noise
         ob, _ = self._prep(obs, D)
         n = ob.shape[0]
         out = out or {}
@@ -129,6 +131,10 @@ class PolicyWithValue(object):
                 given, _ = self._prep(given_action, A)
                 if not given.is_contiguous():
                     given = given.contiguous()
+            elif not deterministic and noise_in is not None:
+                if tuple(noise_in.shape) != (n, A) or noise_in.dtype != t.float32 or not noise_in.is_cuda or not noise_in.is_contiguous():
+                    raise ValueError("noise must be a contiguous float32 CUDA tensor of shape (%d, %d)" % (n, A))
+                noise = noise_in
             elif not deterministic:
                 noise = t.randn((n, A), generator=self.gen, device=self.device, dtype=t.float32)
         if flags & ppo_capi.FWD_VF:

@@ -67,6 +67,78 @@ def filter_stats(p, prefix):
     return mean, std
 
 
+def zoo_kernel_flat(p):
+    """The kernel's flat layout (sumo_ppo.h) of a split zoo MLP net: pi trunk, vf trunk, pi head, logstd, vf head."""
+    return flatten_params([p["polfc1/w"], p["polfc1/b"], p["polfc2/w"], p["polfc2/b"], p["vffc1/w"], p["vffc1/b"],
+                           p["vffc2/w"], p["vffc2/b"], p["polfinal/w"], p["polfinal/b"], p["logstd"], p["vffinal/w"],
+                           p["vffinal/b"]])
+
+
+def zoo_table_rows(flats, ac_dim):
+    """Host rows of a device table of zoo MLP nets (include/sumo_hip.h ``sumo_zoo_mlp``) from flat ``.npy`` vectors:
+    ``(params [n][Pz], filt [n][2][Dz])`` float32 -- each net in the kernel's flat layout, and its observation filter's
+    mean | 1 / std.  Zoo LSTM vectors and vectors of different ``ob_dim`` raise ``ValueError``."""
+    flats = [np.asarray(f, np.float32).ravel() for f in flats]
+    if not flats:
+        raise ValueError("a zoo table needs at least one net")
+    params, filt, dims = [], [], []
+    for k, f in enumerate(flats):
+        try:
+            ob_dim, p = split_zoo_mlp(f, ac_dim)
+        except ValueError:
+            try:
+                split_zoo_lstm(f, ac_dim)
+            except ValueError:
+                raise ValueError("net %d: %d parameters fit neither zoo policy with %d actions" % (k, f.size, ac_dim))
+            raise ValueError("net %d is a zoo LSTM policy: the fused launches play zoo MLP nets only (zoo LSTM nets run step by "
+                             "step, ZooLSTMPolicy)" % k)
+        mean, std = filter_stats(p, "obsfilter")
+        params.append(zoo_kernel_flat(p))
+        filt.append(np.stack([mean, (np.float32(1.0) / std).astype(np.float32)]))
+        dims.append(ob_dim)
+    if len(set(dims)) != 1:
+        raise ValueError("the nets of one zoo table share ob_dim; got %s" % sorted(set(dims)))
+    return np.stack(params).astype(np.float32), np.stack(filt).astype(np.float32)
+
+
+class ZooTable(object):
+    """Device table of frozen zoo MLP nets for the fused launches (``sumo_rollout_steps_zoo`` / ``sumo_match_steps_zoo``):
+    ``params [n][Pz]`` and ``filt [n][2][ob_dim]`` CUDA tensors.  ``sources``: ``.npy`` paths, flat vectors or
+    :class:`ZooMLPPolicy` objects (a :class:`ZooLSTMPolicy` or an LSTM-shaped vector is refused)."""
+
+    obs_clip = 5.0
+
+    def __init__(self, sources, ac_dim, device=0):
+        import os
+        import torch
+        self.device = torch.device("cuda", int(device)) if not isinstance(device, torch.device) else device
+        self.ac_dim = int(ac_dim)
+        flats, self.labels = [], []
+        for src in sources:
+            if isinstance(src, ZooLSTMPolicy):
+                raise ValueError("a ZooLSTMPolicy does not play in a ZooTable: the fused launches play zoo MLP nets only")
+            self.labels.append(str(src) if isinstance(src, (str, os.PathLike)) else None)
+            if isinstance(src, ZooMLPPolicy):
+                if src.ac_dim != self.ac_dim:
+                    raise ValueError("zoo policy has %d actions, the table %d" % (src.ac_dim, self.ac_dim))
+                flats.append(src.flat)
+            elif isinstance(src, (str, os.PathLike)):
+                flats.append(np.load(os.path.expanduser(str(src)), allow_pickle=False))
+            else:
+                flats.append(src)
+        params, filt = zoo_table_rows(flats, self.ac_dim)
+        self.capacity, self.ob_dim = int(params.shape[0]), int(filt.shape[2])
+        self.params = torch.from_numpy(params).to(self.device)
+        self.filt = torch.from_numpy(filt).to(self.device)
+
+    def struct(self):
+        """The ``capi.ZooMlp`` launch struct of this table (the tensors stay owned by the table)."""
+        from . import capi
+        z = capi.ZooMlp()
+        z.params, z.filt, z.obs_clip, z.nzoo, z.ob_dim = self.params.data_ptr(), self.filt.data_ptr(), self.obs_clip, self.capacity, self.ob_dim
+        return z
+
+
 class ZooMLPPolicy(object):
     """One zoo MLP net resident on the GPU.  ``act`` follows policy.py:72-79; ``step`` / ``value`` /
     ``action_probability`` follow the PolicyWithValue surface so the object can sit in ``Runner.models[1]``
@@ -81,14 +153,12 @@ class ZooMLPPolicy(object):
         self._t = torch
         self.device = torch.device("cuda", int(device)) if not isinstance(device, torch.device) else device
         self.ac_dim = int(ac_dim)
-        self.ob_dim, p = split_zoo_mlp(flat_params, ac_dim)
+        self.flat = np.asarray(flat_params, np.float32).ravel().copy()     # the zoo's own vector (ZooTable reads it)
+        self.ob_dim, p = split_zoo_mlp(self.flat, ac_dim)
         self.tensors = p
         mean, std = filter_stats(p, "obsfilter")
         self.ret_mean, self.ret_std = [float(x) for x in filter_stats(p, "retfilter")]
-        # the kernel's flat layout (sumo_ppo.h): pi trunk, vf trunk, pi head, logstd, vf head
-        flat = flatten_params([p["polfc1/w"], p["polfc1/b"], p["polfc2/w"], p["polfc2/b"], p["vffc1/w"], p["vffc1/b"],
-                               p["vffc2/w"], p["vffc2/b"], p["polfinal/w"], p["polfinal/b"], p["logstd"], p["vffinal/w"],
-                               p["vffinal/b"]])
+        flat = zoo_kernel_flat(p)
         self.params = torch.from_numpy(flat).to(self.device)
         self.obs_mean = torch.from_numpy(mean).to(self.device)
         self.obs_invstd = torch.from_numpy((np.float32(1.0) / std).astype(np.float32)).to(self.device)
@@ -112,14 +182,15 @@ class ZooMLPPolicy(object):
             raise ValueError("expected float32 [n, >=%d] observations with unit inner stride" % min_cols)
         return x, np_in
 
-    def evaluate(self, obs, flags, given_action=None, deterministic=False, out=None):
+    def evaluate(self, obs, flags, given_action=None, deterministic=False, out=None, noise=None):
         """Same contract as ``PolicyWithValue.evaluate`` (device tensors in, dict of device tensors out; ``out`` may hold
-        preallocated outputs), so the device-mode Runner can drive a zoo opponent."""
+        preallocated outputs), so the device-mode Runner can drive a zoo opponent.  ``noise``: explicit standard-normal rows
+        (contiguous float32 CUDA [n, ac_dim]) for the sampled action instead of a draw from ``self.gen``."""
         t = self._t
         ob, _ = self._prep(obs, self.ob_dim)
         n, A = ob.shape[0], self.ac_dim
         out = out or {}
-        action = neglogp = value = noise = given = None
+        action = neglogp = value = given = None
         if flags & ppo_capi.FWD_PI:
             action = out.get("action")
             if action is None:
@@ -130,8 +201,15 @@ class ZooMLPPolicy(object):
             if given_action is not None:
                 given, _ = self._prep(given_action, A)
                 given = given.contiguous()
-            elif not deterministic:
+                noise = None
+            elif deterministic:
+                noise = None
+            elif noise is None:
                 noise = t.randn((n, A), generator=self.gen, device=self.device, dtype=t.float32)
+            elif tuple(noise.shape) != (n, A) or noise.dtype != t.float32 or not noise.is_cuda or not noise.is_contiguous():
+                raise ValueError("noise must be a contiguous float32 CUDA tensor of shape (%d, %d)" % (n, A))
+        else:
+            noise = None
         if flags & ppo_capi.FWD_VF:
             value = out.get("value")
             if value is None:

@@ -101,6 +101,12 @@ class Runner(AbstractEnvRunner):
         self.fused_rollout = os.environ.get("SUMO_FUSED_ROLLOUT", "1") != "0"
         self.rollout_chunk = int(os.environ.get("SUMO_ROLLOUT_CHUNK", "0"))   # steps per launch (0 = the whole rollout)
         self.opponent_pool = None     # opponent_pool.OpponentPool: frozen snapshots + per-env snapshot index (fused path)
+        # opt-in (learn(fused_fix_opponent=True)): a policy-zoo MLP opponent (opponent_mode='fix') plays inside the fused launch
+        # (sumo_rollout_steps_zoo).  The action noise is then drawn per group and generator for the whole buffer, as the MLP
+        # self-play path draws it -- another, equally valid stream than the per-step draws of the default fix-mode path; with
+        # SUMO_FUSED_ROLLOUT=0 the step-by-step launches play that same stream (bit-identical rollouts).
+        self.fused_fix_opponent = False
+        self._zoo_table = None
         self.recurrent = all(getattr(m, "recurrent", False) for m in models)
         self.device_mode = hasattr(env, "step_device") and (self.recurrent or all(
             hasattr(m, "act_model") and hasattr(m.act_model, "evaluate") for m in models))
@@ -223,7 +229,7 @@ class Runner(AbstractEnvRunner):
                 and env.act_dev.shape[2] == sp0.ac_dim and env.obs_dev.stride(2) == 1)
 
     def _fused_groups(self, B, s0, K, alpha, ro_type, draw, fill, launch):
-        """The per-group loop of the two fused rollouts.  On group g's stream: the group's noise pair, drawn by ``draw(n)`` for the
+        """The per-group loop of the fused rollouts.  On group g's stream: the group's noise pair, drawn by ``draw(n)`` for the
         whole buffer when its first step is written and cached as ``B[("noise", first env)]``; a ``ro_type`` launch struct whose
         own fields ``fill(ro, sl)`` sets and whose shared fields (window, noise, rollout buffers) are set here; ``launch(g, ro)``."""
         t, env = self._t, self.env
@@ -302,6 +308,58 @@ class Runner(AbstractEnvRunner):
 
         self._fused_groups(B, s0, K, alpha, capi.Rollout, draw, fill, self.env.rollout_steps_group)
 
+    def zoo_opponent(self):
+        """The ``ZooMLPPolicy`` behind ``models[1]`` when the run opted into the fused fix-mode rollout (``fused_fix_opponent``)
+        and the launch applies -- device mode, a plain MLP learner of the env's shape, a zoo MLP net (zoo LSTM nets stay on the
+        step-by-step path), cfrc_mode 'zero' -- else None."""
+        env = self.env
+        if not (self.fused_fix_opponent and self.device_mode and not self.recurrent and hasattr(env, "rollout_steps_zoo_group")):
+            return None
+        from .policies import PolicyWithValue
+        from .policy_zoo import FixedOpponentModel, ZooMLPPolicy
+        if getattr(env, "cfrc_mode", "zero") != "zero" or self.opponent_pool is not None:
+            return None
+        m0, m1 = self.models[0], self.models[1]
+        if not isinstance(m1, FixedOpponentModel) or type(m1.act_model) is not ZooMLPPolicy or not hasattr(m0, "act_model"):
+            return None
+        learner, zoo = m0.act_model, m1.act_model
+        if not (type(learner) is PolicyWithValue and learner.spec.ob_dim == self.ob_dim and zoo.ob_dim <= self.ob_dim
+                and learner.spec.ac_dim == zoo.ac_dim == env.act_dev.shape[2] and env.obs_dev.stride(2) == 1):
+            return None
+        return zoo
+
+    def fused_zoo_ok(self):
+        """The fused launch against a policy-zoo MLP net (``sumo_rollout_steps_zoo``) applies: see :meth:`zoo_opponent`."""
+        return self.fused_rollout and self.zoo_opponent() is not None
+
+    def _draw_zoo(self, B, n, learner, zoo):
+        """A group's noise pair for the whole buffer: one call per generator, as the MLP self-play path draws."""
+        t = self._t
+        A, T = learner.spec.ac_dim, B["T"]
+        return (t.randn((T, n, A), generator=learner.gen, device=self.device, dtype=t.float32),
+                t.randn((T, n, A), generator=zoo.gen, device=self.device, dtype=t.float32))
+
+    def _steps_fused_zoo(self, B, s0, K, alpha):
+        """``_steps_fused`` against a policy-zoo MLP net: one ``sumo_rollout_steps_zoo`` launch per env group.  The zoo net sits in a
+        one-row :class:`policy_zoo.ZooTable`; same numbers as the step-by-step launches under the opt-in (``_policy_evals`` with the
+        same noise rows), bit for bit."""
+        from . import capi
+        from .policy_zoo import ZooTable
+        learner, zoo = self.models[0].act_model, self.zoo_opponent()
+        if self._zoo_table is None or self._zoo_table[0] is not zoo:
+            self._zoo_table = (zoo, ZooTable([zoo], zoo.ac_dim, self.device))
+        table = self._zoo_table[1]
+        zs = table.struct()
+        D, A = learner.spec.ob_dim, learner.spec.ac_dim
+
+        def fill(ro, sl):
+            ro.learner_params = learner.params.data_ptr()
+            ro.opponent_params, ro.opponent_index, ro.npool = None, None, table.capacity
+            ro.ob_dim, ro.ac_dim = D, A
+
+        self._fused_groups(B, s0, K, alpha, capi.Rollout, lambda n: self._draw_zoo(B, n, learner, zoo), fill,
+                           lambda g, ro: self.env.rollout_steps_zoo_group(g, ro, zs))
+
     def join_groups(self):
         """Make the current stream wait for every env group's stream (no-op without groups)."""
         if self._gstreams is not None:
@@ -347,6 +405,12 @@ class Runner(AbstractEnvRunner):
             act1.copy_(a1); B["onlp"][1, s, sl].copy_(on1)
             B["val"][1, s, sl].copy_(m0.value(o1, S=S1, M=dn[:, 1]))
             B["nlp"][1, s, sl].copy_(m0.act_model.action_probability(o1, given_action=a1))
+        elif self.zoo_opponent() is not None:
+            # opt-in fix mode, step by step: the noise rows the fused launch (``_steps_fused_zoo``) would read
+            key = ("noise", sl.start)
+            if s == 0 or key not in B:
+                B[key] = self._draw_zoo(B, n, learner, opp)
+            self._policy_evals(B, s, learner, opp, o0, o1, sl, g, dict(noise=B[key][0][s]), dict(noise=B[key][1][s]))
         else:
             self._policy_evals(B, s, learner, opp, o0, o1, sl, g)
         act = env.act_dev
@@ -400,17 +464,19 @@ class Runner(AbstractEnvRunner):
                                                          self.env.act_dev[sl].data_ptr(), fp, dp,
                                                          t.cuda.current_stream(self.device).cuda_stream))
 
-    def _policy_evals(self, B, s, learner, opp, o0, o1, sl, g):
+    def _policy_evals(self, B, s, learner, opp, o0, o1, sl, g, nk0=None, nk1=None):
         """The two chains (learner acts on agent 0's stream and the opponent scores it; the opponent acts on agent 1's stream
-        and the learner evaluates it) are independent: they run on two HIP streams and join before the env step."""
+        and the learner evaluates it) are independent: they run on two HIP streams and join before the env step.  ``nk0`` /
+        ``nk1``: ``dict(noise=rows)`` for the two sampling evaluations (default: each net draws from its own generator)."""
         t = self._t
         PI, VF = ppo_capi.FWD_PI, ppo_capi.FWD_VF
+        nk0, nk1 = nk0 or {}, nk1 or {}
         sa, sb = B["scratch_a"][sl], B["scratch_b"][sl]
         if g is not None:
             # env groups already overlap with each other; more streams than hardware queues (4 by default) only serialise
-            learner.evaluate(o0, PI | VF, out=dict(action=B["act"][0, s, sl], neglogp=B["nlp"][0, s, sl], value=B["val"][0, s, sl]))
+            learner.evaluate(o0, PI | VF, out=dict(action=B["act"][0, s, sl], neglogp=B["nlp"][0, s, sl], value=B["val"][0, s, sl]), **nk0)
             opp.evaluate(o0, PI, given_action=B["act"][0, s, sl], out=dict(neglogp=B["onlp"][0, s, sl], action=sa))
-            opp.evaluate(o1, PI, out=dict(action=B["act"][1, s, sl], neglogp=B["onlp"][1, s, sl]))
+            opp.evaluate(o1, PI, out=dict(action=B["act"][1, s, sl], neglogp=B["onlp"][1, s, sl]), **nk1)
             learner.evaluate(o1, PI | VF, given_action=B["act"][1, s, sl],
                              out=dict(neglogp=B["nlp"][1, s, sl], value=B["val"][1, s, sl], action=sb))
             return
@@ -420,11 +486,11 @@ class Runner(AbstractEnvRunner):
         side = self._side
         side.wait_stream(cur)
         # agent 0 acts with the learner; the opponent net scores that action (runner.py:67-85)
-        learner.evaluate(o0, PI | VF, out=dict(action=B["act"][0, s, sl], neglogp=B["nlp"][0, s, sl], value=B["val"][0, s, sl]))
+        learner.evaluate(o0, PI | VF, out=dict(action=B["act"][0, s, sl], neglogp=B["nlp"][0, s, sl], value=B["val"][0, s, sl]), **nk0)
         opp.evaluate(o0, PI, given_action=B["act"][0, s, sl], out=dict(neglogp=B["onlp"][0, s, sl], action=sa))
         with t.cuda.stream(side):
             # agent 1 acts with the opponent; the learner net evaluates value and neglogp there (runner.py:86-96)
-            opp.evaluate(o1, PI, out=dict(action=B["act"][1, s, sl], neglogp=B["onlp"][1, s, sl]))
+            opp.evaluate(o1, PI, out=dict(action=B["act"][1, s, sl], neglogp=B["onlp"][1, s, sl]), **nk1)
             learner.evaluate(o1, PI | VF, given_action=B["act"][1, s, sl],
                              out=dict(neglogp=B["nlp"][1, s, sl], value=B["val"][1, s, sl], action=sb))
         cur.wait_stream(side)
@@ -439,8 +505,9 @@ class Runner(AbstractEnvRunner):
             cur = t.cuda.current_stream(self.device)
             for st in self._gstreams:
                 st.wait_stream(cur)
-        if self.fused_ok() or self.fused_lstm_ok():
-            steps = self._steps_fused_lstm if self.recurrent else self._steps_fused
+        fused = self.fused_ok() or self.fused_lstm_ok() or self.fused_zoo_ok()
+        if fused:
+            steps = self._steps_fused_lstm if self.recurrent else self._steps_fused_zoo if self.fused_zoo_ok() else self._steps_fused
             chunk = self.rollout_chunk if self.rollout_chunk > 0 else T
             for s0 in range(0, T, chunk):
                 steps(B, s0, min(chunk, T - s0), alpha)
@@ -462,7 +529,7 @@ class Runner(AbstractEnvRunner):
         # A fused launch that was cut short (expired hand-over wait, hand-over tag / checksum mismatch) leaves unwritten rollout rows:
         # fail as loudly as a MuJoCo fault does in the reference (mujoco-py builder.py:351-369 raises out of env.step) instead of
         # training on them.  The call waits for the launch; this function synchronises right below anyway.
-        if self.fused_ok() or self.fused_lstm_ok():
+        if fused:
             for E in self.env.engines:
                 E.rollout_status()
         # episode infos of agent 0 (monitor.py:63-78), harvested with one host sync per rollout

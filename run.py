@@ -45,6 +45,9 @@ def main(argv):
     ap.add_argument("--adjust_z", type=float, default=0.0, help="Agent._adjust_z (agents.py:33): offset of the torso height the agents report "
                     "(observations, lose test).  0 = the reference's training setting (its run.py:76-77 leaves the -0.5 commented out); its "
                     "evaluation / play scripts use -0.5, which is what the policy-zoo nets expect")
+    ap.add_argument("--fused_fix_opponent", action="store_true", help="opponent_mode=fix: play the policy-zoo MLP net inside the fused "
+                    "rollout launch (sumo_rollout_steps_zoo).  Opt-in: the action noise is drawn per rollout buffer instead of per step, "
+                    "so the same seed gives another, equally valid random stream")
     args, unknown = ap.parse_known_args(argv)
     extra = parse_unknown(unknown)
     from robosumo_selfplay_amd import alg_ac, alg_ppo, defaults, dist as sdist
@@ -52,6 +55,8 @@ def main(argv):
     learn = {"ppo": alg_ppo.learn, "ac": alg_ac.learn}.get(args.algo)
     kw = defaults.get_default_params(args.env, args.algo)       # (td3 / unknown algorithms stop here)
     kw.update(extra)
+    if args.fused_fix_opponent:
+        kw["fused_fix_opponent"] = True
     if args.algo == "ac":             # the A2C learner's scope, checked before anything touches the GPU
         if sdist.env_rank_world()[2] > 1:
             raise SystemExit("--algo ac runs on a single GPU: launch it without torchrun / with WORLD_SIZE=1")

@@ -4,6 +4,8 @@
 
     python tools/match_bench.py --num_env 4096 --pairs 16 --steps 256 --chunk 64
     python tools/match_bench.py --network lstm     # LSTM(128) checkpoints: sumo_match_steps_lstm against ppo_lstm_step per side
+    python tools/match_bench.py --opponent zoo --repeats 3   # MLP checkpoints against policy-zoo MLP nets: sumo_match_steps_zoo
+                                                   # against ppo_forward + ppo_forward_filtered per step, repeats interleaved
 
 Prints one JSON line: env-steps/s and finished matches per second of both paths (stochastic play, Ant-vs-Ant by default)."""
 import argparse
@@ -13,6 +15,20 @@ import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def _zoo_flat(policy_zoo, D, A, rng):
+    """A synthetic policy-zoo MLP vector: unit-count filter sums, O(1) weights."""
+    import numpy as np
+    sh = policy_zoo.zoo_mlp_shapes(D, A)
+    parts = []
+    for k in policy_zoo._ZOO_MLP_ORDER:
+        s = sh[k]
+        v = {"count": 1000.0, "sum": 1000.0 * rng.normal(0, 0.5, s), "sumsq": 1000.0 * (0.25 + rng.uniform(0.0, 2.0, s))}.get(k.split("/")[-1])
+        if v is None:
+            v = rng.normal(-1.0, 0.3, s) if k == "logstd" else rng.normal(0, 1.0 / max(1.0, float(s[0])) ** 0.5 if k.endswith("/w") else 0.1, s)
+        parts.append(np.asarray(v, np.float32).ravel())
+    return np.concatenate(parts)
 
 
 def main(argv):
@@ -25,7 +41,13 @@ def main(argv):
     ap.add_argument("--warmup", type=int, default=64)
     ap.add_argument("--skip_stepwise", action="store_true")
     ap.add_argument("--network", choices=("mlp", "lstm"), default="mlp", help="MLP(64,64) or LSTM(128) snapshots")
+    ap.add_argument("--opponent", choices=("checkpoint", "zoo"), default="checkpoint", help="agent 1: checkpoints of the same table, or "
+                    "synthetic policy-zoo MLP nets (one per pair) in a ZooTable")
+    ap.add_argument("--repeats", type=int, default=1, help="timed runs per path, interleaved fused / step by step; the JSON line then "
+                    "carries every run and the spread (max - min) of each path")
     args = ap.parse_args(argv)
+    if args.opponent == "zoo" and args.network != "mlp":
+        raise SystemExit("--opponent zoo plays MLP(64,64) checkpoints against zoo MLP nets")
     import numpy as np
     import torch
     from robosumo_selfplay_amd import matches, policies
@@ -47,18 +69,25 @@ def main(argv):
             table.set(j, policies.flatten_params([p + 0.1 * rng.standard_normal(p.shape).astype(np.float32)
                                                   for p in policies.init_param_list(D, A)]))
     epp = N // args.pairs
-    idx0_h, idx1_h, _ = matches.env_assignment([(2 * p, 2 * p + 1) for p in range(args.pairs)], list(range(args.pairs)), epp, N)
+    zoo_table = None
+    if args.opponent == "zoo":
+        from robosumo_selfplay_amd import policy_zoo
+        zoo_table = policy_zoo.ZooTable([_zoo_flat(policy_zoo, D - 1, A, rng) for _ in range(args.pairs)], A, env.device)
+    idx0_h, idx1_h, _ = matches.env_assignment([(2 * p, p if zoo_table is not None else 2 * p + 1) for p in range(args.pairs)],
+                                               list(range(args.pairs)), epp, N)
     idx0, idx1 = torch.from_numpy(idx0_h).cuda(), torch.from_numpy(idx1_h).cuda()
     gen = torch.Generator(device="cuda")
     gen.manual_seed(0)
     noise = tuple(torch.randn((K, N, A), generator=gen, device="cuda") for _ in range(2))
-    out = dict(env=args.env, network=args.network, num_env=N, pairs=args.pairs, chunk=K)
+    out = dict(env=args.env, network=args.network, opponent=args.opponent, num_env=N, pairs=args.pairs, chunk=K)
     quota = 1 << 30
     states = tuple(torch.zeros((N, 256), dtype=torch.float32, device="cuda") for _ in range(2))
 
     def launch(fused, score):
         i0, i1 = (idx0, idx1) if fused else (idx0_h, idx1_h)
-        if args.network == "lstm":
+        if zoo_table is not None:
+            (matches.zoo_match_steps_fused if fused else matches.zoo_match_steps_stepwise)(env, table, zoo_table, i0, i1, score, quota, K, noise)
+        elif args.network == "lstm":
             (matches.match_steps_fused_lstm if fused else matches.match_steps_stepwise_lstm)(env, table, i0, i1, states, score, quota, K, noise)
         else:
             (matches.match_steps_fused if fused else matches.match_steps_stepwise)(env, table, i0, i1, score, quota, K, noise)
@@ -83,9 +112,17 @@ def main(argv):
         dt = time.perf_counter() - t0
         return n * N / dt, int(score.sum().item()) / dt
 
-    out["fused_env_steps_per_s"], out["fused_matches_per_s"] = run(True, args.steps)
-    if not args.skip_stepwise:
-        out["stepwise_env_steps_per_s"], out["stepwise_matches_per_s"] = run(False, args.steps)
+    runs = {True: [], False: []}
+    for _ in range(max(1, args.repeats)):              # interleaved: drift of the machine hits both paths alike
+        for fused in (True,) if args.skip_stepwise else (True, False):
+            runs[fused].append(run(fused, args.steps))
+    for fused, name in ((True, "fused"), (False, "stepwise")):
+        if runs[fused]:
+            eps = sorted(r[0] for r in runs[fused])
+            out[name + "_env_steps_per_s"], out[name + "_matches_per_s"] = eps[len(eps) // 2], sorted(r[1] for r in runs[fused])[len(eps) // 2]
+            if args.repeats > 1:
+                out[name + "_runs"], out[name + "_spread"] = [r[0] for r in runs[fused]], eps[-1] - eps[0]
+    if runs[False]:
         out["speedup"] = out["fused_env_steps_per_s"] / out["stepwise_env_steps_per_s"]
     env.close()
     print(json.dumps(out))

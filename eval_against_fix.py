@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """CLI counterpart of the reference's eval_robosumo_against_fix.py (:121-262): play saved checkpoints of a run against a
-fixed policy-zoo MLP opponent on the GPU and print / save win, draw and lose rates per checkpoint.
+fixed policy-zoo opponent (MLP or LSTM net) on the GPU and print / save win, draw and lose rates per checkpoint.
 
     python eval_against_fix.py --path results/RoboSumo-Ant-vs-Ant-v0-0 --opponent_path <zoo>/ant/mlp/agent-params-v3.npy \\
         --num_env 256 --rounds 512 --interval 10
     python eval_against_fix.py --path results/RoboSumo-Ant-vs-Ant-v0-0 --opponent_path <zoo v1>.npy --opponent_path <zoo v3>.npy \
-        --fused --trials 512 --interval 10      (all checkpoints x opponents batched over the envs, one fused launch per 64 steps)
+        --fused --trials 512 --interval 10      (all checkpoints x opponents batched over the envs, one fused launch per 64 steps;
+                                                 MLP and LSTM opponent files may be mixed: each family plays in launches of its own)
 """
 import argparse
 import json
@@ -19,7 +20,7 @@ def main(argv):
     ap = argparse.ArgumentParser()
     ap.add_argument("--path", required=True, help="run directory holding checkpoints/NNNNN (run.py --log_path/<env>-<suffix>)")
     ap.add_argument("--opponent_path", required=True, action="append",
-                    help="policy-zoo .npy (robosumo/robosumo/policy_zoo/assets/<agent>/mlp/...); with --fused it may be given several times")
+                    help="policy-zoo .npy (robosumo/robosumo/policy_zoo/assets/<agent>/{mlp,lstm}/...); with --fused it may be given several times")
     ap.add_argument("--env", default="RoboSumo-Ant-vs-Ant-v0")
     ap.add_argument("--num_env", type=int, default=256)
     ap.add_argument("--rounds", type=int, default=500)
@@ -31,7 +32,7 @@ def main(argv):
                     "(eval_robosumo_against_fix.py:108-115): the zoo nets were trained with the tatami surface at z = 0")
     ap.add_argument("--cfrc_mode", default="zero", choices=["zero", "rne_post"])
     ap.add_argument("--fused", action="store_true", help="play every selected checkpoint against every opponent in fused match launches "
-                    "(matches.evaluate_history_against_zoo): zoo MLP opponents, exactly --trials games per checkpoint and opponent")
+                    "(matches.evaluate_history_against_zoo): zoo MLP and LSTM opponents, exactly --trials games per checkpoint and opponent")
     ap.add_argument("--trials", type=int, default=None, help="games per checkpoint and opponent with --fused (default: --rounds)")
     args = ap.parse_args(argv)
     import numpy as np

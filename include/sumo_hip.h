@@ -169,7 +169,7 @@ int sumo_match_steps_lstm(sumo_handle_t h, const sumo_match_lstm* m, float* acti
  *           ac_dim): pi trunk, vf trunk (never read here), pi head, logstd, vf head
  *   filt    float32 [nzoo][2][ob_dim]: the observation filter's mean | 1 / std (std = sqrt(max(var, 1e-2)), utils.py:30-32)
  * The owning wave evaluates a zoo net as ppo_forward_filtered does (clip((x - mean) / std, +-obs_clip), tanh trunk, Gaussian head),
- * bit for bit.  Zoo LSTM nets (policy.py:94-199) are not played here: they go through ppo_lstm_step.
+ * bit for bit.  Zoo LSTM nets (policy.py:94-199) are not played by these two entry points: see sumo_zoo_lstm below.
  *
  * sumo_rollout_steps_zoo: sumo_rollout_steps with agent 1 played by a zoo net (learn(opponent_mode='fix'), reference
  *   alg_ppo.py:194-206): per step and env the learner's policy and value nets on both observations, zoo net opponent_index[e]
@@ -192,6 +192,48 @@ int sumo_rollout_steps_zoo(sumo_handle_t h, const sumo_rollout* r, const sumo_zo
                            double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream);
 int sumo_match_steps_zoo(sumo_handle_t h, const sumo_match* m, const sumo_zoo_mlp* z, float* actions_dev, float* obs_dev,
                          double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream);
+/* The fused match launches against POLICY-ZOO LSTM nets (the reference's robosumo/policy_zoo LSTMPolicy(normalize=True),
+ * policy.py:94-199: observation filter clipped to +-obs_clip on the first ob_dim observation columns, relu embedding of emb_dim,
+ * BasicLSTMCell(hidden) in gate order i,j,f,o with forget_bias, Gaussian head; two such branches, of which only the POLICY branch
+ * -- p/emb, lstmp, p/out, logstd -- is evaluated, as ZooLSTMPolicy.act does without want_value).  A table of nzoo frozen nets of one
+ * ob_dim, emb_dim = hidden = 64:
+ *   params  float32 [nzoo][Pz], each row in this order (A = the scene's ac_dim):
+ *             emb_w  [ob_dim][64]      p/emb/w
+ *             emb_b  [64]              p/emb/b
+ *             kernel [64 + 64][256]    lstmp/kernel: the 64 input rows, then the 64 recurrent rows; columns gate-major i | j | f | o
+ *             bias   [256]             lstmp/bias (forget_bias is added to the f block inside)
+ *             head_w [64][A]           p/out/w
+ *             head_b [A]               p/out/b
+ *             logstd [A]
+ *           Pz = 64 ob_dim + 64 + 128 * 256 + 256 + 64 A + 2 A
+ *   filt    float32 [nzoo][2][ob_dim]: the observation filter's mean | 1 / std, as sumo_zoo_mlp
+ *   state   float32 [E][2 * 64] (c | h): agent 1's recurrent state, rows of THIS engine's envs; read at step s0, left at the state
+ *           after step s0 + K - 1 (the caller zeroes it where a match-up starts).  Inside the launch a row is zeroed before the cell
+ *           runs where AGENT 0's done flag of the previous step is set (policy_zoo._evaluate_against resets the opponent on it).
+ * The owning wave evaluates the net as ppo_lstm_step does with a ppo_lstm_net filled like ZooLSTMPolicy's policy branch, bit for bit.
+ *
+ * sumo_match_steps_zoo_lstm: sumo_match_steps_zoo with agent 1 played by zoo LSTM nets: agent 0 acts with MLP(64,64) checkpoint
+ *   m->idx0[e] of m->params [m->nsnap][P], agent 1 with net m->idx1[e] of z.
+ * sumo_match_steps_lstm_zoo_lstm: the same for RECURRENT checkpoints: agent 0 is agent 0 of sumo_match_steps_lstm (net m->idx0[e] of
+ *   m->nets_dev on its state m->state0, LSTM(128)); m->state1 must be NULL (agent 1's state is z->state).
+ * Two entry points rather than a mode field, like the MLP / LSTM pair of sumo_match_steps: each takes its sibling's launch struct.
+ * Noise (m->noise0 for agent 0, m->noise1 for agent 1; both NULL = deterministic), score, quota and the abort on a bad index (idx0
+ * against nsnap, idx1 against nzoo: sumo_rollout_status returns -20, row 0 plays) as sumo_match_steps.  Refused: whatever the sibling
+ * entry point refuses, ob_dim outside [1, the scene's ob_dim], nzoo < 1, missing params / filt / state, obs_clip <= 0, emb_dim /
+ * hidden other than 64, a scene whose policy scratch cannot hold the observation tile plus the embedding and latent rows. */
+typedef struct sumo_zoo_lstm {
+  const float* params;
+  const float* filt;
+  float* state;
+  float obs_clip;      /* 5 for the zoo nets */
+  float forget_bias;   /* 1 for the zoo nets (tf BasicLSTMCell) */
+  int nzoo, ob_dim, emb_dim, hidden;
+} sumo_zoo_lstm;
+int sumo_match_steps_zoo_lstm(sumo_handle_t h, const sumo_match* m, const sumo_zoo_lstm* z, float* actions_dev, float* obs_dev,
+                              double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream);
+int sumo_match_steps_lstm_zoo_lstm(sumo_handle_t h, const sumo_match_lstm* m, const sumo_zoo_lstm* z, float* actions_dev, float* obs_dev,
+                                   double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev,
+                                   void* stream);
 /* cfrc_mode (reference agents.py:190-214 reads sim.data.cfrc_ext into 84 of the 121 observation entries):
  *   0 = zero (default): what the reference produces -- its MuJoCo 2.1 scenes declare no force / torque / accelerometer sensor, so
  *       mj_rnePostConstraint never runs and cfrc_ext stays at its reset value 0;

@@ -54,6 +54,13 @@ class ZooMlp(C.Structure):
     _fields_ = [("params", _P), ("filt", _P), ("obs_clip", C.c_float), ("nzoo", _I), ("ob_dim", _I)]
 
 
+class ZooLstm(C.Structure):
+    """``sumo_zoo_lstm`` of include/sumo_hip.h: a device table of frozen policy-zoo LSTM nets plus agent 1's recurrent state of the
+    launch's envs (device pointers as integers)."""
+    _fields_ = [("params", _P), ("filt", _P), ("state", _P), ("obs_clip", C.c_float), ("forget_bias", C.c_float), ("nzoo", _I),
+                ("ob_dim", _I), ("emb_dim", _I), ("hidden", _I)]
+
+
 def lib():
     global _LIB
     if _LIB is None:
@@ -75,6 +82,8 @@ def lib():
         L.sumo_match_steps_lstm.argtypes = [vp, C.POINTER(MatchLstm)] + [vp] * 8
         L.sumo_rollout_steps_zoo.argtypes = [vp, C.POINTER(Rollout), C.POINTER(ZooMlp)] + [vp] * 8
         L.sumo_match_steps_zoo.argtypes = [vp, C.POINTER(Match), C.POINTER(ZooMlp)] + [vp] * 8
+        L.sumo_match_steps_zoo_lstm.argtypes = [vp, C.POINTER(Match), C.POINTER(ZooLstm)] + [vp] * 8
+        L.sumo_match_steps_lstm_zoo_lstm.argtypes = [vp, C.POINTER(MatchLstm), C.POINTER(ZooLstm)] + [vp] * 8
         L.sumo_get_state.argtypes = [vp] * 5
         L.sumo_set_cfrc_mode.argtypes = [vp, i32]
         L.sumo_get_cfrc_ext.argtypes = [vp, vp]
@@ -93,14 +102,14 @@ def lib():
         L.sumo_static_layout.restype = i32
         L.sumo_profile.restype = i32
         for n in ("sumo_create", "sumo_destroy", "sumo_dims", "sumo_reset", "sumo_step", "sumo_rollout_steps", "sumo_rollout_steps_lstm", "sumo_match_steps", "sumo_match_steps_lstm",
-                  "sumo_rollout_steps_zoo", "sumo_match_steps_zoo", "sumo_get_state", "sumo_set_cfrc_mode", "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_set_state", "sumo_debug_forward", "sumo_stats"):
+                  "sumo_rollout_steps_zoo", "sumo_match_steps_zoo", "sumo_match_steps_zoo_lstm", "sumo_match_steps_lstm_zoo_lstm", "sumo_get_state", "sumo_set_cfrc_mode", "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_set_state", "sumo_debug_forward", "sumo_stats"):
             getattr(L, n).restype = i32
         _LIB = L
     return _LIB
 
 
 EXPORTS = ("sumo_last_error", "sumo_create", "sumo_destroy", "sumo_dims", "sumo_reset", "sumo_step", "sumo_rollout_steps",
-           "sumo_rollout_steps_lstm", "sumo_match_steps", "sumo_match_steps_lstm", "sumo_rollout_steps_zoo", "sumo_match_steps_zoo", "sumo_set_cfrc_mode", "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_get_state", "sumo_set_state", "sumo_debug_forward", "sumo_stats", "sumo_profile", "sumo_debug_trace",
+           "sumo_rollout_steps_lstm", "sumo_match_steps", "sumo_match_steps_lstm", "sumo_rollout_steps_zoo", "sumo_match_steps_zoo", "sumo_match_steps_zoo_lstm", "sumo_match_steps_lstm_zoo_lstm", "sumo_set_cfrc_mode", "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_get_state", "sumo_set_state", "sumo_debug_forward", "sumo_stats", "sumo_profile", "sumo_debug_trace",
            "sumo_rollout_status", "sumo_debug_fault", "sumo_static_layout", "sumo_debug_layout", "sumo_debug_model_ints", "sumo_debug_dump")
 
 
@@ -151,7 +160,7 @@ class Engine:
 
     def _fused(self, entry, launch, env_ptrs, stream, zoo=None):
         """One fused launch: ``env_ptrs`` are the seven env-side pointers of :meth:`step`, in its order; ``zoo``: the
-        :class:`ZooMlp` table the ``*_zoo`` entry points take after the launch struct."""
+        :class:`ZooMlp` / :class:`ZooLstm` table the ``*_zoo`` / ``*_zoo_lstm`` entry points take after the launch struct."""
         actions_ptr, obs_ptr, info_ptr, done_ptr, ep_r_ptr, ep_dr_ptr, ep_l_ptr = env_ptrs
         structs = (C.byref(launch),) if zoo is None else (C.byref(launch), C.byref(zoo))
         _chk(getattr(lib(), entry)(self.h, *structs, *env_ptrs, stream))
@@ -182,6 +191,16 @@ class Engine:
         """K fused match steps of checkpoints (agent 0) against policy-zoo MLP nets (agent 1) (``sumo_match_steps_zoo``); ``mo`` is
         a filled :class:`Match` whose ``idx1`` indexes ``zoo``, a filled :class:`ZooMlp`."""
         self._fused("sumo_match_steps_zoo", mo, env_ptrs, stream, zoo)
+
+    def match_steps_zoo_lstm(self, mo, zoo, *env_ptrs, stream=None):
+        """K fused match steps of MLP checkpoints (agent 0) against policy-zoo LSTM nets (agent 1) (``sumo_match_steps_zoo_lstm``);
+        ``mo`` is a filled :class:`Match` whose ``idx1`` indexes ``zoo``, a filled :class:`ZooLstm` (``state``: agent 1's rows)."""
+        self._fused("sumo_match_steps_zoo_lstm", mo, env_ptrs, stream, zoo)
+
+    def match_steps_lstm_zoo_lstm(self, mo, zoo, *env_ptrs, stream=None):
+        """The same for LSTM(128) checkpoints (``sumo_match_steps_lstm_zoo_lstm``); ``mo`` is a filled :class:`MatchLstm` with
+        ``state1`` left None (agent 1's state is ``zoo.state``)."""
+        self._fused("sumo_match_steps_lstm_zoo_lstm", mo, env_ptrs, stream, zoo)
 
     def set_cfrc_mode(self, mode):
         """'zero' (default, the reference's behaviour) or 'rne_post' (include/sumo_hip.h: cfrc_mode)."""

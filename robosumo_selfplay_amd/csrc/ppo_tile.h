@@ -268,17 +268,19 @@ typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));   // two f
 // runs fmaf over the input block (k = 0 .. D-1) and then the recurrent block (k = 0 .. NH-1) reproduces that column of the
 // tile.  One env has 2-3 rows per net: on a 16-row tile 13 of 16 rows would be idle and every B operand a 256-byte load; here a
 // lane owns the units 2 lane, 2 lane + 1 -- all four gates of them, columns g NH + 2 lane + {0, 1} -- and a k-step costs four
-// 512-byte loads for the whole wave.  xr[r] / hr[r]: LDS rows (16-byte aligned; x rows zero-padded to a multiple of four).
+// 512-byte loads for the whole wave (NH = 64: the unit `lane`, four 256-byte loads).  xr[r] / hr[r]: LDS rows (16-byte aligned; x
+// rows zero-padded to a multiple of four).
 template <int NH, int R>
 __device__ __forceinline__ void lstm_gates_valu(const float* wx, const float* wh, int D, const float* const (&xr)[R], const float* const (&hr)[R],
-                                                int lane, float (&z)[4][2][R]) {
-  static_assert(NH == 128, "two units per lane");
+                                                int lane, float (&z)[4][NH / 64][R]) {
+  static_assert(NH == 128 || NH == 64, "two units per lane, or one (NH = 64: the policy-zoo LSTM cell)");
+  constexpr int U = NH / 64;   // units per lane; U == 1 keeps the .x half of every weight pair only
   const int nx = (D + 3) >> 2, nch = nx + NH / 4;
-  const int col = 2 * lane;
+  const int col = U * lane;
 #pragma unroll
   for (int g = 0; g < 4; g++)
 #pragma unroll
-    for (int r = 0; r < R; r++) { z[g][0][r] = 0.0f; z[g][1][r] = 0.0f; }
+    for (int r = 0; r < R; r++) { z[g][0][r] = 0.0f; if constexpr (U == 2) z[g][1][r] = 0.0f; }
   auto fetch = [&](int ch, f32x2u (&w)[4][4]) {
     const bool in_x = ch < nx;
     const float PT_GAS* base = pt_global(in_x ? wx : wh);
@@ -289,7 +291,10 @@ __device__ __forceinline__ void lstm_gates_valu(const float* wx, const float* wh
       if (k >= kmax) k = kmax - 1;   // the x rows are zero there: fma(0, w, z) == z for any finite weight
       const float PT_GAS* wrow = base + (size_t)k * 4 * NH + col;
 #pragma unroll
-      for (int g = 0; g < 4; g++) w[kk][g] = *(const f32x2u PT_GAS*)(wrow + g * NH);
+      for (int g = 0; g < 4; g++) {
+        if constexpr (U == 2) w[kk][g] = *(const f32x2u PT_GAS*)(wrow + g * NH);
+        else w[kk][g].x = wrow[g * NH];
+      }
     }
   };
   auto consume = [&](int ch, const f32x2u (&w)[4][4]) {
@@ -304,7 +309,7 @@ __device__ __forceinline__ void lstm_gates_valu(const float* wx, const float* wh
 #pragma unroll
         for (int g = 0; g < 4; g++) {
           z[g][0][r] = __builtin_fmaf(xs[kk], w[kk][g].x, z[g][0][r]);
-          z[g][1][r] = __builtin_fmaf(xs[kk], w[kk][g].y, z[g][1][r]);
+          if constexpr (U == 2) z[g][1][r] = __builtin_fmaf(xs[kk], w[kk][g].y, z[g][1][r]);
         }
     }
   };
@@ -324,6 +329,30 @@ __device__ __forceinline__ void lstm_gates_valu(const float* wx, const float* wh
 #pragma unroll
   for (int b = 0; b < 3; b++)   // the last nch % 4 chunks are in flight in buffers 0 .. 2
     if (ch + b < nch) consume(ch + b, w[b]);
+}
+
+// Input stage of a policy-zoo LSTM net (policy_zoo LSTMPolicy(normalize=True), policy.py:94-199) on ONE staged observation row:
+// the row is filtered IN PLACE -- clip((x - mean) * invstd, +-clip) on its first Dz columns, the expression and order of stage_x in
+// ppo_kernels.hip -- and the relu embedding (Dz -> 64) goes to erow [64]: lane owns column `lane` and runs fmaf over k = 0 .. Dz - 1
+// from zero, the order in which the embedding tiles of ppo_lstm_step_kernel accumulate (an f32 MFMA adds its k-products as
+// sequential FMAs in ascending k; its padded k-steps add 0 * 0), then relu(sum + bias).  filt: mean [Dz] |
+// 1 / std [Dz]; emb_w [Dz][64], emb_b [64].  The caller orders erow against its readers (wave_sync).
+__device__ __forceinline__ void zoo_lstm_embed(const float PT_GAS* emb_w, const float PT_GAS* emb_b, const float* filt_, float clip, float* xrow,
+                                               int Dz, float* erow, int lane) {
+  const float PT_GAS* filt = pt_global(filt_);
+  const float bias = emb_b[lane];
+  for (int k = lane; k < Dz; k += PT_WAVE) xrow[k] = fminf(fmaxf((xrow[k] - filt[k]) * filt[Dz + k], -clip), clip);
+  wave_sync();
+  float acc = 0.0f;
+  for (int k0 = 0; k0 < Dz; k0 += 16) {   // sixteen 256-byte weight rows in flight per trip to the L2
+    float w[16];
+#pragma unroll
+    for (int u = 0; u < 16; u++) { const int k = k0 + u; w[u] = emb_w[(size_t)(k < Dz ? k : Dz - 1) * PT_H + lane]; }
+#pragma unroll
+    for (int u = 0; u < 16; u++)
+      if (k0 + u < Dz) acc = __builtin_fmaf(xrow[k0 + u], w[u], acc);
+  }
+  erow[lane] = fmaxf(acc + bias, 0.0f);
 }
 
 // Heads on R latent rows in LDS (hn [R][NH]): lane i < A accumulates column i of the Gaussian mean, lane 16 the value, over the

@@ -2542,11 +2542,32 @@ struct ZooArgs {
   int nzoo, Dz;
   ParamLayout Lz;                    // make_layout(Dz, A)
 };
+// Policy-zoo LSTM opponents (sumo_match_steps_zoo_lstm / sumo_match_steps_lstm_zoo_lstm, POLICY 6 / 7): the table (parameter rows
+// [nzoo][Pz] in the order of sumo_zoo_lstm, filter rows), clip, forget bias, size, input / action width, and where the cell's
+// rows (embedding [64] | previous latent [64] | new latent [64], 16-byte aligned) start in the policy scratch.  Agent 1's
+// recurrent state [N][128] (c | h) travels in RolloutArgs::st1.
+struct ZooLstmArgs {
+  const float* params;
+  const float* filt;                 // [nzoo][2][Dz]: mean | 1 / std
+  float clip, forget_bias;
+  int nzoo, Dz, A, Pz;
+  int sc_off;                        // floats from the scratch base (lds_off)
+  int emb;                           // embedding width (the table's emb_dim, 64).  Deliberately a launch field and not a literal:
+                                     // lstm_gates_valu's chunk loop runs (emb + 64) / 4 trips, and it keeps its ring of four
+                                     // chunk buffers only while that count is a run-time value, as it is for the LSTM(128)
+                                     // nets (their D is a launch field too).  The loop is shared with modes 1 and 3, whose
+                                     // code objects must not change, so it carries no unroll pragma of its own.
+};
 struct RolloutArgs {
   const float *learner, *opponent;   // flat parameter vectors; opponent: [npool][P]
   const int32_t* opp_idx;            // [N] snapshot per env or NULL
   const float *noise0, *noise1;      // [T][N][A]
-  float *obs, *act, *rew, *val, *nlp, *onlp;   // [2][T][Ntot][...]
+  // (the match modes write no rollout record: the zoo LSTM modes' fields overlay its six pointers, so the struct -- and with it
+  // the kernel-argument segment every instantiation reads -- keeps its size and offsets; static_asserts below RolloutLaunch)
+  union {
+    struct { float *obs, *act, *rew, *val, *nlp, *onlp; };   // [2][T][Ntot][...]
+    ZooLstmArgs zl;
+  };
   uint8_t *done, *ep_done;           // [2][T][Ntot], [T][Ntot]
   double* ep_r;                      // [T][Ntot]
   int32_t* ep_l;                     // [T][Ntot]
@@ -2976,6 +2997,149 @@ __device__ __forceinline__ void rollout_policy_phase_match_zoo(C& c, const SA& a
   wave_sync();   // the action buffer is read back by the env step (other lanes), the scratch region becomes the mass matrix again
 }
 
+// ---- policy-zoo LSTM opponents (POLICY 6 / 7) ----
+// Agent 1's action from zoo LSTM net idx1[e] (policy_zoo LSTMPolicy, policy.py:94-199; ZooLSTMPolicy.act's policy branch -- the value
+// branch v/emb, lstmv is never evaluated): observation filter on the first Dz columns of xrow (agent 1's staged observation, filtered
+// in place), relu embedding (Dz -> 64), BasicLSTMCell(64) in gate order i,j,f,o with the table's forget bias, Gaussian head, noise1
+// (or the mean where noise0 is NULL).  The state row st1[e] (c | h) is zeroed first where AGENT 0's done flag of the previous step is
+// set (policy_zoo._evaluate_against resets the opponent on done[:, 0]) and crosses waves like the LSTM matches' states.  Embedding,
+// gate sums, cell and head run through zoo_lstm_embed / lstm_gates_valu / lstm_cell / lstm_heads_valu in the accumulation order of
+// ppo_lstm_step_kernel<64, PPO_LSTM_GATES_IJFO>: every number equals that kernel bit for bit.  sc: embedding [64] | previous latent
+// [64] | new latent [64] (16-byte aligned LDS).  Lanes < A return their column of the action.
+template <class SA, class RA>
+__device__ __forceinline__ float zoo_lstm_act(const SA& a, const RA& r, int e, int s, int lane, unsigned dn, float* xrow, float* sc) {
+  constexpr int NH = 64, EM = PT_H;
+  const int Dz = r.zl.Dz, A = r.zl.A;
+  const int j1 = policy_checked_row(a, lane, pt_global(r.idx1)[e], r.zl.nzoo);
+  // parameter row: emb_w [Dz][64] | emb_b [64] | kernel [64 + 64][256] (input rows, then recurrent rows) | bias [256] | head_w
+  // [64][A] | head_b [A] | logstd [A]
+  const float PT_GAS* p = pt_global(r.zl.params) + (size_t)j1 * r.zl.Pz;
+  const float PT_GAS* emb_b = p + Dz * EM;
+  const float PT_GAS* wx = emb_b + EM;
+  const float PT_GAS* wh = wx + EM * 4 * NH;
+  const float PT_GAS* b_ = wh + NH * 4 * NH;
+  const float PT_GAS* head_w = b_ + 4 * NH;
+  const float PT_GAS* head_b = head_w + NH * A;
+  float *eb = sc, *hp = sc + EM, *hn = hp + NH;
+  const float keep = 1.0f - (float)(dn & 0xff);
+  float* sp = r.st1 + (size_t)e * 2 * NH;
+  const float cp = hand_load<true>(sp + lane) * keep;          // lane owns the unit `lane`
+  hp[lane] = hand_load<true>(sp + NH + lane) * keep;
+  float bz[4];
+#pragma unroll
+  for (int g = 0; g < 4; g++) bz[g] = b_[g * NH + lane];       // (in flight during the embedding and the gate sums)
+  zoo_lstm_embed(p, emb_b, r.zl.filt + (size_t)j1 * 2 * Dz, r.zl.clip, xrow, Dz, eb, lane);
+  wave_sync();
+  float z[4][1][1];
+  const float* const xr[1] = {eb};
+  const float* const hr[1] = {hp};
+  lstm_gates_valu<NH, 1>((const float*)wx, (const float*)wh, r.zl.emb, xr, hr, lane, z);
+  // gate order i, j, f, o: z[1] is the candidate, z[2] the forget gate
+  const LstmCell cl = lstm_cell(z[0][0][0], z[2][0][0], z[3][0][0], z[1][0][0], bz[0], bz[2] + r.zl.forget_bias, bz[3], bz[1], cp);
+  lstm_state_store<NH>(sp, lane, cl);
+  hn[lane] = cl.hn;
+  wave_sync();
+  float m[1];
+  lstm_heads_valu<NH, 1>((const float*)head_w, (const float*)head_w, A, hn, lane, m);   // (lane 16's value sum reads head_w: no value head here)
+  const bool ok = lane < A;
+  const float mean = m[0] + (ok ? head_b[lane] : 0.0f);
+  float act = mean;
+  if (r.noise0) {
+    const float ls = ok ? head_b[A + lane] : 0.0f;
+    const float nz = ok ? pt_global(r.noise1)[policy_noise_index(a, e, s, A, lane)] : 0.0f;
+    (void)gauss_row(mean, expf(ls), 0.0f, ok, true, nz, act, A);
+  }
+  return act;
+}
+
+// MLP(64,64) checkpoints against policy-zoo LSTM nets (sumo_match_steps_zoo_lstm, POLICY 6): agent 0 acts with checkpoint idx0[e] of
+// snaps [nsnap][P] on the raw tile, exactly as in rollout_policy_phase_match_zoo; agent 1 through zoo_lstm_act on row 1 of the tile,
+// its rows in the hidden tiles' place once agent 0's trunk is done (no extra LDS).
+template <class C, class SA, class RA>
+__device__ __forceinline__ void rollout_policy_phase_match_zoo_lstm(C& c, const SA& a, const RA& r, int e, int s) {
+  const int lane = c.lane, i = lane & 15, kq = lane >> 4;
+  const int D = r.L.D, A = r.L.A, XS = r.XS;
+  float* xbuf = (float*)(c.sm + r.lds_off);        // [2][XS] | h1 [2][PT_HS] | h2 [2][PT_HS]
+  float* h1 = xbuf + 2 * XS;
+  float* h2 = h1 + 2 * PT_HS;
+  policy_load_obs<false, false>(a, r, e, lane, xbuf, D, XS);
+  const unsigned dn = policy_prev_done(a, e);
+  wave_sync();
+  const int j0 = policy_checked_row(a, lane, pt_global(r.idx0)[e], r.nsnap);
+  const float PT_GAS* p0 = pt_global(r.snaps) + (size_t)j0 * r.L.P;
+  const f32x4 m0 = trunk_forward<false, 2>(pi_net((const float*)p0, r.L), xbuf, XS, D, h1, h2, lane);
+  const bool ok = i < A && kq == 0;                 // row 0 lives in the first 16 lanes (D layout: rows 4 kq + r)
+  float act0 = m0[0];
+  if (r.noise0) {
+    const float ls0 = ok ? p0[r.L.logstd + i] : 0.0f;
+    const float n0 = ok ? pt_global(r.noise0)[policy_noise_index(a, e, s, A, i)] : 0.0f;
+    (void)gauss_row(m0[0], expf(ls0), 0.0f, ok, true, n0, act0, A);
+  }
+  wave_sync();   // the hidden tiles become the cell's rows
+  const float act1 = zoo_lstm_act(a, r, e, s, lane, dn, xbuf + XS, xbuf + r.zl.sc_off);
+  if (ok) policy_commit_actions<false>(c, a, r, e, i, act0, act1);
+  wave_sync();   // the action buffer is read back by the env step (other lanes), the scratch region becomes the mass matrix again
+}
+
+// LSTM(128) checkpoints against policy-zoo LSTM nets (sumo_match_steps_lstm_zoo_lstm, POLICY 7): agent 0 is side 0 of
+// rollout_policy_phase_match_lstm<128> (net idx0[e] of onets on (obs 0, st0[e] masked by its done flag)); agent 1 through
+// zoo_lstm_act on row 1 of the tile, its rows in the latent rows' place once agent 0's head is done.  Agent 0's block below is the
+// g = 0 pass of that function's side loop written out, not a helper both call: the loop there is unrolled over both sides with
+// shared index checks, and moving its body into a function is a source change to mode 3, whose code objects have to stay as
+// they are.  Any change to one of the two goes into the other; tests/test_gpu_zoo_lstm_fused.py compares mode 7 with the same
+// ppo_lstm_step launches that tests/test_gpu_matches_lstm.py compares mode 3 with.
+template <int NH, class C, class SA, class RA>
+__device__ __forceinline__ void rollout_policy_phase_match_lstm_zoo_lstm(C& c, const SA& a, const RA& r, int e, int s) {
+  const int lane = c.lane;
+  const int D = r.lnet.ob_dim, A = r.lnet.ac_dim, XS = r.XS;
+  float* xo = (float*)(c.sm + r.lds_off);
+  float* hp = xo + 2 * XS;
+  float* hn = hp + NH;
+  policy_load_obs<true, false>(a, r, e, lane, xo, D, XS);
+  const unsigned dn = policy_prev_done(a, e);
+  const int jn = policy_checked_row(a, lane, pt_global(r.idx0)[e], r.nsnap);
+  const bool ok = lane < A;
+  const int j0 = 2 * lane;                           // lane owns the units 2 lane, 2 lane + 1
+  float act0;
+  {
+    const ppo_lstm_net PT_GAS* NT = pt_global(r.onets) + jn;
+    const float keep = 1.0f - (float)(dn & 0xff);
+    float* sp = r.st0 + (size_t)e * 2 * NH;
+    float cp[2];
+    lstm_state_pair(sp + j0, keep, cp);
+    lstm_state_pair(sp + NH + j0, keep, hp + j0);
+    const float PT_GAS* b_ = pt_global(NT->b);
+    const float fb = NT->forget_bias;
+    float z[4][2][1], bz[4][2];
+    lstm_bias_pair<NH>(b_, j0, bz);
+    wave_sync();
+    const float* const xr[1] = {xo};
+    const float* const hr[1] = {hp};
+    lstm_gates_valu<NH, 1>(NT->wx, NT->wh, D, xr, hr, lane, z);
+#pragma unroll
+    for (int u = 0; u < 2; u++) {
+      const int j = j0 + u;
+      const LstmCell cl = lstm_cell(z[0][u][0], z[1][u][0], z[2][u][0], z[3][u][0], bz[0][u], bz[1][u] + fb, bz[2][u], bz[3][u], cp[u]);
+      lstm_state_store<NH>(sp, j, cl);                                              // agent 0's state after its step
+      hn[j] = cl.hn;
+    }
+    wave_sync();
+    float m[1];
+    lstm_heads_valu<NH, 1>(NT->head_w, NT->head_w, A, hn, lane, m);   // (lane 16's value sum reads head_w: the value head stays unread)
+    const float mean = m[0] + (ok ? pt_global(NT->head_b)[lane] : 0.0f);
+    act0 = mean;
+    if (r.noise0) {
+      const float ls = ok ? pt_global(NT->logstd)[lane] : 0.0f;
+      const float nz = ok ? pt_global(r.noise0)[policy_noise_index(a, e, s, A, lane)] : 0.0f;
+      (void)gauss_row(mean, expf(ls), 0.0f, ok, true, nz, act0, A);
+    }
+    wave_sync();   // the latent rows become the zoo cell's rows
+  }
+  const float act1 = zoo_lstm_act(a, r, e, s, lane, dn, xo + XS, xo + r.zl.sc_off);
+  if (ok) policy_commit_actions<false>(c, a, r, e, lane, act0, act1);
+  wave_sync();
+}
+
 // Match post phase: where agent 0's episode ended in the step, score it from the step's winner flags (info[.][7] bit 0, just
 // written by this lane): a win if agent 0 carries the flag, a loss if only agent 1 does, a draw otherwise (timeouts, diverged states)
 // -- policy_zoo._evaluate_against's rule.  Counted while wins + losses + draws < quota.
@@ -3016,6 +3180,11 @@ __device__ __forceinline__ void rollout_post_phase(C& c, const SA& a, const RA& 
 // segment itself, where the runtime has placed the struct at launch (no separate copy to keep alive).
 struct RolloutLaunch { StepArgs a; RolloutArgs r; };
 static_assert(sizeof(ZooArgs) <= sizeof(ppo_lstm_net), "ZooArgs overlays RolloutArgs::lnet");
+static_assert(sizeof(ZooLstmArgs) <= 6 * sizeof(float*) && offsetof(RolloutArgs, obs) == offsetof(RolloutArgs, zl) &&
+                  offsetof(RolloutArgs, obs) == offsetof(RolloutArgs, noise1) + sizeof(float*) &&
+                  offsetof(RolloutArgs, onlp) == offsetof(RolloutArgs, obs) + 5 * sizeof(float*) &&
+                  offsetof(RolloutArgs, done) == offsetof(RolloutArgs, obs) + 6 * sizeof(float*),
+              "ZooLstmArgs overlays the six rollout-record pointers of RolloutArgs: no field moves");
 
 // Scheduling: the launch is a set of persistent waves (one per wave slot of the chip) that draw TICKETS from a global counter;
 // ticket t is step t / N of env t % N.  Env steps differ in cost by 3x (contacts, Newton iterations, agents wrestling), so
@@ -3034,7 +3203,9 @@ template <int NV, int POLICY, int SL = 0>   // POLICY 0: MLP(64,64) policy / val
                                             // (sumo_match_steps: score counters instead of rollout buffers); 3: LSTM(128) matches
                                             // (sumo_match_steps_lstm); 4: MLP learner against policy-zoo MLP nets
                                             // (sumo_rollout_steps_zoo); 5: MLP checkpoints against policy-zoo MLP nets
-                                            // (sumo_match_steps_zoo); SL 1: static Layout
+                                            // (sumo_match_steps_zoo); 6: MLP checkpoints against policy-zoo LSTM nets
+                                            // (sumo_match_steps_zoo_lstm); 7: LSTM(128) checkpoints against policy-zoo LSTM
+                                            // nets (sumo_match_steps_lstm_zoo_lstm); SL 1: static Layout
 __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(SUMO_WPE_OF(NV), SUMO_WPE_OF(NV))))
 sumo_rollout_kernel(const Params* P, RolloutLaunch launch_args) {
   // `launch_args` is read in place from the kernel-argument segment (second argument, 8-byte aligned right behind P) through a
@@ -3092,6 +3263,8 @@ sumo_rollout_kernel(const Params* P, RolloutLaunch launch_args) {
     else if constexpr (POLICY == 3) rollout_policy_phase_match_lstm<128>(c, lp->a, lp->r, e, s);
     else if constexpr (POLICY == 4) rollout_policy_phase_zoo(c, lp->a, lp->r, e, s);
     else if constexpr (POLICY == 5) rollout_policy_phase_match_zoo(c, lp->a, lp->r, e, s);
+    else if constexpr (POLICY == 6) rollout_policy_phase_match_zoo_lstm(c, lp->a, lp->r, e, s);
+    else if constexpr (POLICY == 7) rollout_policy_phase_match_lstm_zoo_lstm<128>(c, lp->a, lp->r, e, s);
     else rollout_policy_phase(c, lp->a, lp->r, e, s);
 #ifdef SUMO_DBG_HARD_BARRIER
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -3104,7 +3277,7 @@ sumo_rollout_kernel(const Params* P, RolloutLaunch launch_args) {
     asm volatile("" : "+s"(e), "+s"(k));
     lp = launder_sptr(LP);
     s = lp->r.s0 + k;
-    if constexpr (POLICY == 2 || POLICY == 3 || POLICY == 5) rollout_post_phase_match(c, lp->a, lp->r, e);
+    if constexpr (POLICY == 2 || POLICY == 3 || POLICY >= 5) rollout_post_phase_match(c, lp->a, lp->r, e);
     else rollout_post_phase(c, lp->a, lp->r, e, s);
     prof = lp->r.prof;
     if (prof && c.lane == 0) {
@@ -3955,6 +4128,8 @@ static int rollout_launch(sumo_engine* E, const RolloutArgs& r, int policy, cons
                                                        : policy == 3 ? sumo_rollout_kernel<NV, 3, SL>
                                                        : policy == 4 ? sumo_rollout_kernel<NV, 4, SL>
                                                        : policy == 5 ? sumo_rollout_kernel<NV, 5, SL>
+                                                       : policy == 6 ? sumo_rollout_kernel<NV, 6, SL>
+                                                       : policy == 7 ? sumo_rollout_kernel<NV, 7, SL>
                                                                      : sumo_rollout_kernel<NV, 0, SL>;
         hipLaunchKernelGGL(kernel, g_, b_, lds_, st_, E->d_params, rl);
       }))
@@ -3983,7 +4158,7 @@ static int check_dims(int ob_dim, int ac_dim, int od, int ad) {
 }
 
 // what the in-wave recurrent evaluation is built for: the nets `learn(network='lstm')` trains (policy-zoo LSTM nets carry an
-// observation filter, an embedding and the other gate order: they go through ppo_lstm_step)
+// observation filter, an embedding and the other gate order: they play as agent 1 of the match modes 6 / 7, zoo_lstm_act)
 static int check_lstm_shape(const ppo_lstm_net& n, const char* what) {
   if (n.hidden != 128 || n.gate_order != PPO_LSTM_GATES_IFOU || n.emb_w || n.emb_dim != 0 || n.obs_mean || n.obs_invstd)
     FAIL(-9, "fused recurrent %s: hidden 128, gate order i,f,o,u, no embedding, no observation filter (got hidden %d, order %d, emb %d)", what, n.hidden, n.gate_order, n.emb_dim);
@@ -4177,6 +4352,78 @@ extern "C" int sumo_match_steps_zoo(sumo_handle_t E, const sumo_match* mo, const
   copy_match_fields(r, mo, E->N);
   if (int rc = place_mlp_scratch(E, mo->ob_dim, mo->ac_dim, r)) return rc;
   return rollout_launch(E, r, 5, b, stream);
+}
+
+// the zoo LSTM table of sumo_match_steps_zoo_lstm / sumo_match_steps_lstm_zoo_lstm: checks, then the fields of RolloutArgs it fills
+// (after place_*_scratch: the cell's rows -- embedding | previous latent | new latent, 64 floats each -- go behind the observation
+// tile, 16-byte aligned, into the `rows_floats` floats the placed scratch holds there)
+static int place_zoo_lstm_table(RolloutArgs& r, const sumo_zoo_lstm* z, int od, int ad, int rows_floats) {
+  if (!z->params || !z->filt) FAIL(-2, "sumo_zoo_lstm: missing buffer (params / filt)");
+  if (!z->state) FAIL(-2, "sumo_zoo_lstm: missing state buffer (state)");
+  if (z->nzoo < 1) FAIL(-7, "nzoo %d: the zoo table needs at least one entry", z->nzoo);
+  if (z->ob_dim < 1 || z->ob_dim > od)
+    FAIL(-4, "zoo ob_dim %d outside [1, %d]: a policy-zoo LSTM net reads the first ob_dim columns of the scene's observation", z->ob_dim, od);
+  if (z->emb_dim != PT_H || z->hidden != 64) FAIL(-4, "zoo LSTM emb_dim %d / hidden %d: the fused launch is built for 64 / 64", z->emb_dim, z->hidden);
+  if (!(z->obs_clip > 0.0f)) FAIL(-9, "obs_clip %g must be positive", (double)z->obs_clip);
+  ZooLstmArgs& q = r.zl;
+  q.params = z->params; q.filt = z->filt; q.clip = z->obs_clip; q.forget_bias = z->forget_bias; q.nzoo = z->nzoo; q.Dz = z->ob_dim; q.A = ad; q.emb = z->emb_dim;
+  q.Pz = z->ob_dim * PT_H + PT_H + 2 * 64 * 256 + 256 + 64 * ad + 2 * ad;
+  r.st1 = z->state;
+  const int tile = 2 * r.XS;
+  q.sc_off = tile;
+  while ((2 * r.lds_off + q.sc_off) & 3) q.sc_off++;   // lds_off counts doubles from the 16-byte aligned LDS base
+  if (q.sc_off + 3 * 64 > tile + rows_floats)
+    FAIL(-8, "zoo LSTM scratch (observation tile + embedding and latent rows, %zu B) does not fit the policy scratch (%zu B)",
+         (size_t)(q.sc_off + 3 * 64) * sizeof(float), (size_t)(tile + rows_floats) * sizeof(float));
+  return 0;
+}
+
+extern "C" int sumo_match_steps_zoo_lstm(sumo_handle_t E, const sumo_match* mo, const sumo_zoo_lstm* z, float* actions_dev, float* obs_dev,
+                                         double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
+  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
+  if (int rc = check_launch_args(E, mo, b)) return rc;
+  if (!z) FAIL(-1, "bad arguments");
+  if (!mo->params) FAIL(-2, "sumo_match: missing buffer");
+  if (int rc = check_match_buffers(mo, "sumo_match")) return rc;
+  int od = 0, ad = 0;
+  if (int rc = rollout_scene(E, mo->T, E->N, 0, mo->s0, mo->K, &od, &ad)) return rc;
+  if (int rc = check_dims(mo->ob_dim, mo->ac_dim, od, ad)) return rc;
+  if (int rc = check_match_counts(mo)) return rc;
+  HIPCHK(hipSetDevice(E->device));
+  RolloutArgs r;
+  memset(&r, 0, sizeof r);
+  r.snaps = mo->params;
+  copy_match_fields(r, mo, E->N);
+  if (int rc = place_mlp_scratch(E, mo->ob_dim, mo->ac_dim, r)) return rc;
+  if (int rc = place_zoo_lstm_table(r, z, od, ad, 4 * PT_HS)) return rc;   // the two hidden tiles of agent 0's trunk
+  return rollout_launch(E, r, 6, b, stream);
+}
+
+extern "C" int sumo_match_steps_lstm_zoo_lstm(sumo_handle_t E, const sumo_match_lstm* mo, const sumo_zoo_lstm* z, float* actions_dev,
+                                              float* obs_dev, double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev,
+                                              int32_t* ep_l_dev, void* stream) {
+  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
+  if (int rc = check_launch_args(E, mo, b)) return rc;
+  if (!z) FAIL(-1, "bad arguments");
+  if (!mo->proto || !mo->nets_dev) FAIL(-2, "sumo_match_lstm: missing buffer");
+  if (!mo->state0) FAIL(-2, "sumo_match_lstm: missing state buffer (state0)");
+  if (mo->state1) FAIL(-2, "sumo_match_steps_lstm_zoo_lstm: state1 must be NULL (agent 1's state is the zoo table's state)");
+  if (int rc = check_match_buffers(mo, "sumo_match_lstm")) return rc;
+  int od = 0, ad = 0;
+  if (int rc = rollout_scene(E, mo->T, E->N, 0, mo->s0, mo->K, &od, &ad)) return rc;
+  const ppo_lstm_net& n = *mo->proto;
+  if (int rc = check_dims(n.ob_dim, n.ac_dim, od, ad)) return rc;
+  if (int rc = check_lstm_shape(n, "matches")) return rc;
+  if (!n.wx || !n.wh || !n.b || !n.head_w || !n.head_b || !n.logstd) FAIL(-10, "prototype net: missing weights");
+  if (int rc = check_match_counts(mo)) return rc;
+  HIPCHK(hipSetDevice(E->device));
+  RolloutArgs r;
+  memset(&r, 0, sizeof r);
+  r.lnet = n; r.onets = mo->nets_dev; r.st0 = mo->state0;
+  copy_match_fields(r, mo, E->N);
+  if (int rc = place_lstm_scratch(E, od, 2, r)) return rc;   // agent 0's previous and new latent
+  if (int rc = place_zoo_lstm_table(r, z, od, ad, 2 * 128)) return rc;
+  return rollout_launch(E, r, 7, b, stream);
 }
 
 #ifdef SUMO_POLICY_PROBE

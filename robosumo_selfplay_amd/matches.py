@@ -19,6 +19,11 @@ same drivers detect the kind from the checkpoint files (:func:`checkpoint_kind`)
 per env, zeroed where a batch starts and masked by that side's done flag of the previous step (``LstmPPOModel.step(obs, S, M)``).
 The fused path is ``sumo_match_steps_lstm`` (LSTM(128)); ``fused=False`` makes one ``ppo_lstm_step`` launch per side and run of
 envs sharing a snapshot, bit-identical again.  MLP-vs-LSTM match-ups are refused.
+
+Policy-zoo opponents sit in a :class:`policy_zoo.ZooTable` (MLP nets) or a :class:`policy_zoo.ZooLstmTable` (LSTM nets) and play
+agent 1 (:func:`play_against_zoo`, :func:`evaluate_history_against_zoo`): MLP checkpoints face either family, LSTM(128)
+checkpoints face zoo LSTM nets (``sumo_match_steps_zoo`` / ``sumo_match_steps_zoo_lstm`` / ``sumo_match_steps_lstm_zoo_lstm``);
+LSTM checkpoints against zoo MLP nets are refused.
 """
 import ctypes as C
 import os
@@ -271,8 +276,8 @@ def _check_env(env, table):
 def _fused_groups(env, entry, struct, fill, idx0, idx1, score, quota, K, noise, extra=()):
     """The per-group loop of the fused match launches: a ``struct`` (capi.Match / capi.MatchLstm) whose own fields
     ``fill(mo, sl)`` sets and whose shared fields (indices, window, quota, noise, score) are set here, passed to the engine's
-    ``entry`` method (followed by ``extra``: the zoo table's struct) with the group's env-side pointers; raises if the launch
-    was cut short (``rollout_status``)."""
+    ``entry`` method (followed by ``extra``: the zoo table's struct, or a function of the group's env slice that returns it) with
+    the group's env-side pointers; raises if the launch was cut short (``rollout_status``)."""
     for g in range(env.groups):
         sl = env._gs(g)
         mo = struct()
@@ -285,7 +290,7 @@ def _fused_groups(env, entry, struct, fill, idx0, idx1, score, quota, K, noise, 
             mo.noise0, mo.noise1 = keep[0].data_ptr(), keep[1].data_ptr()
         mo.score = score[sl].data_ptr()
         E = env.engines[g]
-        getattr(E, entry)(mo, *extra, *env.env_ptrs(g), stream=env._stream())
+        getattr(E, entry)(mo, *(extra(sl) if callable(extra) else extra), *env.env_ptrs(g), stream=env._stream())
         E.rollout_status()
         del keep
 
@@ -401,8 +406,9 @@ def match_steps_stepwise_lstm(env, table, idx0, idx1, states, score, quota, K, n
 
 def _check_zoo(env, table, zoo_table):
     _check_env(env, table)
-    if getattr(table, "recurrent", False):
-        raise ValueError("LSTM checkpoints do not play against zoo nets in the fused launch (MLP(64,64) checkpoints only)")
+    if getattr(table, "recurrent", False) and not getattr(zoo_table, "recurrent", False):
+        raise ValueError("LSTM checkpoints do not play against zoo MLP nets in the fused launch (MLP(64,64) checkpoints only; LSTM "
+                         "checkpoints play against zoo LSTM nets, a ZooLstmTable)")
     if zoo_table.ac_dim != table.spec.ac_dim or not 1 <= zoo_table.ob_dim <= table.spec.ob_dim:
         raise ValueError("zoo table (ob_dim %d, ac_dim %d) does not fit the env (%d, %d): a zoo MLP net reads the first ob_dim "
                          "observation columns" % (zoo_table.ob_dim, zoo_table.ac_dim, table.spec.ob_dim, table.spec.ac_dim))
@@ -445,6 +451,80 @@ def zoo_match_steps_stepwise(env, table, zoo_table, idx0, idx1, score, quota, K,
                                                 ppo_capi.ptr(nz), None, out.data_ptr(), nlp[rows].data_ptr(), None, None, st))
 
     _stepwise(env, table, idx0, idx1, score, quota, K, noise, forward, masked=False, capacity1=zoo_table.capacity)
+
+
+def _check_zoo_lstm(env, table, zoo_table, states):
+    """Checks of the zoo LSTM match steps; returns (agent 0's state or None, agent 1's state) from ``states``: agent 1's tensor
+    [N][2 * 64] for an MLP table, the pair (agent 0 [N][2 nlstm], agent 1 [N][2 * 64]) for an :class:`LstmSnapshotTable`."""
+    _check_zoo(env, table, zoo_table)
+    if not getattr(zoo_table, "recurrent", False):
+        raise ValueError("zoo_lstm_match_steps_* need a policy_zoo.ZooLstmTable (zoo MLP nets play through zoo_match_steps_*)")
+    N, Hz = env.num_envs, zoo_table.hidden
+    st0, st1 = states if getattr(table, "recurrent", False) else (None, states)
+    if st0 is not None:
+        _check_lstm(table, (st0,), N)
+    if tuple(st1.shape) != (N, 2 * Hz) or not st1.is_contiguous():
+        raise ValueError("the zoo nets' recurrent state must be a contiguous float32 [%d][%d] tensor (c | h)" % (N, 2 * Hz))
+    return st0, st1
+
+
+def zoo_lstm_match_steps_fused(env, table, zoo_table, idx0, idx1, states, score, quota, K, noise=None):
+    """K match steps of checkpoints (agent 0: row idx0[e] of ``table``) against policy-zoo LSTM nets (agent 1: row idx1[e] of
+    ``zoo_table``, a :class:`policy_zoo.ZooLstmTable`) in one launch per env group: ``sumo_match_steps_zoo_lstm`` for a
+    :class:`SnapshotTable` (``states``: agent 1's float32 CUDA [N][128] tensor, c | h), ``sumo_match_steps_lstm_zoo_lstm`` for an
+    :class:`LstmSnapshotTable` of LSTM(128) policies (``states``: the pair agent 0 [N][256], agent 1 [N][128]).  The states are
+    read and updated in place; the other arguments as :func:`match_steps_fused`."""
+    from . import capi
+    st0, st1 = _check_zoo_lstm(env, table, zoo_table, states)
+    extra = lambda sl: (zoo_table.struct(st1[sl]),)
+    if st0 is None:
+        def fill(mo, sl):
+            mo.params = table.params.data_ptr()
+            mo.nsnap, mo.ob_dim, mo.ac_dim = table.capacity, table.spec.ob_dim, table.spec.ac_dim
+
+        _fused_groups(env, "match_steps_zoo_lstm", capi.Match, fill, idx0, idx1, score, quota, K, noise, extra=extra)
+        return
+    if table.spec.nlstm != 128:
+        raise ValueError("the fused match launch plays LSTM(128) policies only (got LSTM(%d)): use fused=False" % table.spec.nlstm)
+
+    def fill(mo, sl):
+        mo.proto = C.addressof(table.proto)
+        mo.nets_dev = table.nets_dev.data_ptr()
+        mo.nsnap = table.capacity
+        mo.state0 = st0[sl].data_ptr()
+
+    _fused_groups(env, "match_steps_lstm_zoo_lstm", capi.MatchLstm, fill, idx0, idx1, score, quota, K, noise, extra=extra)
+
+
+def zoo_lstm_match_steps_stepwise(env, table, zoo_table, idx0, idx1, states, score, quota, K, noise=None):
+    """The same K steps step by step: per step, for every run of envs that share a checkpoint, one ``ppo_forward`` launch (MLP
+    table) or one ``ppo_lstm_step`` launch masked by agent 0's done flags (LSTM table); for every run that shares a zoo net one
+    ``ppo_lstm_step`` launch on its policy branch (what ``ZooLSTMPolicy.act`` runs), its state rows masked by AGENT 0's done flags
+    of the previous step (``policy_zoo._evaluate_against`` resets the opponent on them); then ``step_device`` and the score
+    update.  idx0 / idx1 are host arrays."""
+    import torch
+    from . import ppo_capi
+    st0, st1 = _check_zoo_lstm(env, table, zoo_table, states)
+    D, A, Hz = table.spec.ob_dim, table.spec.ac_dim, zoo_table.hidden
+    L, st, obs = ppo_capi.lib(), env._stream(), env.obs_dev
+    nlp = torch.empty(env.num_envs, dtype=torch.float32, device=env.device)
+
+    def lstm_step(net, ob, n, mask, S, H, nz, out):
+        ppo_capi.chk(L.ppo_lstm_step(C.byref(net), ob, n, obs.stride(0), mask.data_ptr(), S.data_ptr(), S.data_ptr() + 4 * H, 2 * H,
+                                     ppo_capi.ptr(nz), None, out.data_ptr(), None, None, None, st))
+
+    def forward(k, side, rows, nz, out, mask):
+        n, ob = rows.stop - rows.start, obs[rows, side].data_ptr()
+        if side == 0:
+            if st0 is None:
+                ppo_capi.chk(L.ppo_forward(table.params[k].data_ptr(), ob, n, obs.stride(0), D, A, ppo_capi.FWD_PI, ppo_capi.ptr(nz), None,
+                                           out.data_ptr(), nlp[rows].data_ptr(), None, None, st))
+            else:
+                lstm_step(table.nets[k], ob, n, mask, st0[rows], table.spec.nlstm, nz, out)
+        else:
+            lstm_step(zoo_table.nets[k], ob, n, env.done_dev[rows, 0].to(torch.float32), st1[rows], Hz, nz, out)
+
+    _stepwise(env, table, idx0, idx1, score, quota, K, noise, forward, masked=True, capacity1=zoo_table.capacity)
 
 
 def match_steps(env, table, idx0, idx1, states, score, quota, K, noise=None, fused=True):
@@ -549,10 +629,12 @@ def _play_batches(env, A, pairs, rounds_per_env, envs_per_pair, deterministic, s
 
 def play_against_zoo(env, table, zoo_table, pairs, rounds_per_env, envs_per_pair, deterministic=True, seed=0, adjust_z=EVAL_ADJUST_Z,
                      chunk=64, fused=True):
-    """:func:`play_matches` with agent 1 played by policy-zoo MLP nets: ``pairs[p] = (i, j)`` is checkpoint row i of ``table`` (a
-    :class:`SnapshotTable`) as agent 0 against net j of ``zoo_table`` (a :class:`policy_zoo.ZooTable`) as agent 1 -- the games of
-    the reference's eval_robosumo_against_fix.py:196-230 (deterministic by default, as there).  Same batching, seeding, quota and
-    return value as :func:`play_matches`; ``fused=False`` plays the same games step by step (bit-identical envs and scores)."""
+    """:func:`play_matches` with agent 1 played by policy-zoo nets: ``pairs[p] = (i, j)`` is checkpoint row i of ``table`` (a
+    :class:`SnapshotTable`, or an :class:`LstmSnapshotTable` against zoo LSTM nets) as agent 0 against net j of ``zoo_table`` (a
+    :class:`policy_zoo.ZooTable` or :class:`policy_zoo.ZooLstmTable`) as agent 1 -- the games of the reference's
+    eval_robosumo_against_fix.py:196-230 (deterministic by default, as there).  Recurrent states (the zoo LSTM nets', the LSTM
+    checkpoints') are allocated and zeroed per batch.  Same batching, seeding, quota and return value as :func:`play_matches`;
+    ``fused=False`` plays the same games step by step (bit-identical envs and scores)."""
     _check_zoo(env, table, zoo_table)
     pairs = [(int(i), int(j)) for i, j in pairs]
     for i, j in pairs:
@@ -561,10 +643,21 @@ def play_against_zoo(env, table, zoo_table, pairs, rounds_per_env, envs_per_pair
     rounds_per_env, envs_per_pair, chunk = int(rounds_per_env), int(envs_per_pair), int(chunk)
     if rounds_per_env < 1 or chunk < 1:
         raise ValueError("rounds_per_env and chunk must be >= 1")
-    fn = zoo_match_steps_fused if fused else zoo_match_steps_stepwise
-    steps = lambda idx0, idx1, _states, score, noise: fn(env, table, zoo_table, idx0, idx1, score, rounds_per_env, chunk, noise)
-    return _play_batches(env, table.spec.ac_dim, pairs, rounds_per_env, envs_per_pair, deterministic, seed, adjust_z, chunk, fused, None,
-                         steps)
+    new_states = None
+    if getattr(zoo_table, "recurrent", False):
+        import torch
+        rec0 = bool(getattr(table, "recurrent", False))
+        if rec0 and fused and table.spec.nlstm != 128:
+            raise ValueError("the fused match launch plays LSTM(128) policies only (got LSTM(%d)): use fused=False" % table.spec.nlstm)
+        zeros = lambda width: torch.zeros((env.num_envs, width), dtype=torch.float32, device=env.device)
+        new_states = (lambda: (zeros(2 * table.spec.nlstm), zeros(2 * zoo_table.hidden))) if rec0 else (lambda: zeros(2 * zoo_table.hidden))
+        fn = zoo_lstm_match_steps_fused if fused else zoo_lstm_match_steps_stepwise
+        steps = lambda idx0, idx1, states, score, noise: fn(env, table, zoo_table, idx0, idx1, states, score, rounds_per_env, chunk, noise)
+    else:
+        fn = zoo_match_steps_fused if fused else zoo_match_steps_stepwise
+        steps = lambda idx0, idx1, _states, score, noise: fn(env, table, zoo_table, idx0, idx1, score, rounds_per_env, chunk, noise)
+    return _play_batches(env, table.spec.ac_dim, pairs, rounds_per_env, envs_per_pair, deterministic, seed, adjust_z, chunk, fused,
+                         new_states, steps)
 
 
 def _make_env(env_id, num_env, seed, env):
@@ -677,14 +770,47 @@ def plan_zoo_evaluation(n_checkpoints, n_opponents, trials, num_env):
     return dict(pairs=pairs, envs_per_pair=epp, rounds_per_env=rpe, blocks=blocks)
 
 
+def group_zoo_opponents(kinds):
+    """The pure grouping of :func:`evaluate_history_against_zoo`: ``kinds[k]`` in {'mlp', 'lstm'} is the family of opponent file k.
+    Returns the non-empty groups in the order MLP, LSTM as ``[(kind, [positions in the input])]`` -- each group plays in launches
+    of its own, its opponents numbered 0 .. in its own zoo table."""
+    bad = [k for k in kinds if k not in ("mlp", "lstm")]
+    if bad:
+        raise ValueError("unknown zoo opponent kind %r" % bad[0])
+    return [(kind, pos) for kind, pos in (("mlp", [i for i, k in enumerate(kinds) if k == "mlp"]),
+                                          ("lstm", [i for i, k in enumerate(kinds) if k == "lstm"])) if pos]
+
+
+def plan_mixed_zoo_evaluation(n_checkpoints, kinds, trials, num_env):
+    """:func:`plan_zoo_evaluation` per opponent family: ``[dict(kind, opponents=[input positions], plan)]`` for the groups of
+    :func:`group_zoo_opponents`."""
+    return [dict(kind=kind, opponents=pos, plan=plan_zoo_evaluation(n_checkpoints, len(pos), trials, num_env))
+            for kind, pos in group_zoo_opponents(kinds)]
+
+
+def merge_zoo_results(ids, groups, group_results):
+    """One result table ``{(checkpoint id, opponent position in the caller's list): dict}`` from the per-group results
+    (``group_results[g][p]`` belongs to pair ``groups[g]['plan']['pairs'][p]`` = (checkpoint c, opponent o of the group))."""
+    out = {}
+    for grp, res in zip(groups, group_results):
+        for (c, o), r in zip(grp["plan"]["pairs"], res):
+            n = float(r["rounds"])
+            out[(ids[c], grp["opponents"][o])] = dict(win=r["wins"] / n, draw=r["draws"] / n, lose=r["losses"] / n, rounds=r["rounds"],
+                                                      env_steps=r["env_steps"])
+    return {key: out[key] for key in sorted(out, key=lambda key: (ids.index(key[0]), key[1]))}
+
+
 def evaluate_history_against_zoo(path, opponent_paths, trials, start=0, interval=1, num_env=256, deterministic=True, fused=True, seed=0,
                                  adjust_z=EVAL_ADJUST_Z, env_id="RoboSumo-Ant-vs-Ant-v0", chunk=64, env=None):
     """eval_robosumo_against_fix.py on the fused launch: every selected checkpoint of run ``path`` (:func:`select_checkpoints` of
-    all of its saved versions) as agent 0 against every policy-zoo MLP file of ``opponent_paths`` as agent 1, exactly ``trials``
+    all of its saved versions) as agent 0 against every policy-zoo file of ``opponent_paths`` as agent 1, exactly ``trials``
     games per (checkpoint, opponent), all match-ups batched over the envs (:func:`plan_zoo_evaluation`) instead of one checkpoint
-    after the other.  Returns dict(checkpoints=[ids], opponents=[paths], results={(id, k): dict(win, draw, lose, rounds,
-    env_steps)}) with rates over ``rounds == trials`` games against opponent k."""
-    from .policy_zoo import ZooTable
+    after the other.  Each opponent file's family (MLP / LSTM) is read from its length; the MLP files and the LSTM files play in
+    launches of their own (:func:`plan_mixed_zoo_evaluation`) and the results come back in the caller's opponent order.  The run's
+    checkpoint kind is read with :func:`checkpoint_kind`: MLP(64,64) runs face both families, LSTM runs zoo LSTM files only.
+    Returns dict(checkpoints=[ids], opponents=[paths], results={(id, k): dict(win, draw, lose, rounds, env_steps)}) with rates
+    over ``rounds == trials`` games against opponent k."""
+    from .policy_zoo import ZooLstmTable, ZooTable, zoo_file_kind
     if isinstance(opponent_paths, (str, os.PathLike)):
         opponent_paths = [opponent_paths]
     opponent_paths = [str(p) for p in opponent_paths]
@@ -692,18 +818,21 @@ def evaluate_history_against_zoo(path, opponent_paths, trials, start=0, interval
     ids = select_checkpoints([f for f in os.listdir(ck) if f.isdigit() and os.path.isfile(os.path.join(ck, f))], start, interval)
     if not ids:
         raise ValueError("no checkpoints to evaluate in %s" % ck)
+    ck_paths = [os.path.join(ck, "%.5i" % c) for c in ids]
+    kind = checkpoint_kind(ck_paths[0])
     env, own = _make_env(env_id, num_env, seed, env)
     try:
-        table = SnapshotTable.from_checkpoints(_spec_of(env), [os.path.join(ck, "%.5i" % c) for c in ids], env.device)
-        zoo_table = ZooTable(opponent_paths, table.spec.ac_dim, env.device)
-        plan = plan_zoo_evaluation(len(ids), len(opponent_paths), trials, env.num_envs)
-        res = play_against_zoo(env, table, zoo_table, plan["pairs"], plan["rounds_per_env"], plan["envs_per_pair"],
-                               deterministic=deterministic, seed=seed, adjust_z=adjust_z, chunk=chunk, fused=fused)
+        table = _table_of(kind, env, ck_paths)
+        A = table.spec.ac_dim
+        flats = [np.load(os.path.expanduser(p), allow_pickle=False) for p in opponent_paths]
+        groups = plan_mixed_zoo_evaluation(len(ids), [zoo_file_kind(f.size, A) for f in flats], trials, env.num_envs)
+        res = []
+        for grp in groups:
+            zoo_table = (ZooLstmTable if grp["kind"] == "lstm" else ZooTable)([flats[k] for k in grp["opponents"]], A, env.device)
+            plan = grp["plan"]
+            res.append(play_against_zoo(env, table, zoo_table, plan["pairs"], plan["rounds_per_env"], plan["envs_per_pair"],
+                                        deterministic=deterministic, seed=seed, adjust_z=adjust_z, chunk=chunk, fused=fused))
     finally:
         if own:
             env.close()
-    out = {}
-    for (c, o), r in zip(plan["pairs"], res):
-        n = float(r["rounds"])
-        out[(ids[c], o)] = dict(win=r["wins"] / n, draw=r["draws"] / n, lose=r["losses"] / n, rounds=r["rounds"], env_steps=r["env_steps"])
-    return dict(checkpoints=ids, opponents=opponent_paths, results=out)
+    return dict(checkpoints=ids, opponents=opponent_paths, results=merge_zoo_results(ids, groups, res))

@@ -10,6 +10,8 @@ Reference:
   * alg_ppo.py:194-206                             ``opponent_mode='fix'``
 
 MLP and LSTM zoo nets are built (policy.py:23-91 and :94-199); the LSTM one keeps a per-env recurrent state on the device.
+Both families also play inside the fused match launches from device tables: :class:`ZooTable` (MLP nets) and
+:class:`ZooLstmTable` (LSTM nets, policy branch only).
 The ``.npy`` files are loaded with ``numpy.load(allow_pickle=False)``.
 """
 import numpy as np
@@ -90,8 +92,8 @@ def zoo_table_rows(flats, ac_dim):
                 split_zoo_lstm(f, ac_dim)
             except ValueError:
                 raise ValueError("net %d: %d parameters fit neither zoo policy with %d actions" % (k, f.size, ac_dim))
-            raise ValueError("net %d is a zoo LSTM policy: the fused launches play zoo MLP nets only (zoo LSTM nets run step by "
-                             "step, ZooLSTMPolicy)" % k)
+            raise ValueError("net %d is a zoo LSTM policy: a ZooTable holds zoo MLP nets only (zoo LSTM nets play from a "
+                             "ZooLstmTable, or step by step as ZooLSTMPolicy)" % k)
         mean, std = filter_stats(p, "obsfilter")
         params.append(zoo_kernel_flat(p))
         filt.append(np.stack([mean, (np.float32(1.0) / std).astype(np.float32)]))
@@ -116,7 +118,7 @@ class ZooTable(object):
         flats, self.labels = [], []
         for src in sources:
             if isinstance(src, ZooLSTMPolicy):
-                raise ValueError("a ZooLSTMPolicy does not play in a ZooTable: the fused launches play zoo MLP nets only")
+                raise ValueError("a ZooLSTMPolicy does not play in a ZooTable (zoo MLP nets only): use ZooLstmTable")
             self.labels.append(str(src) if isinstance(src, (str, os.PathLike)) else None)
             if isinstance(src, ZooMLPPolicy):
                 if src.ac_dim != self.ac_dim:
@@ -136,6 +138,114 @@ class ZooTable(object):
         from . import capi
         z = capi.ZooMlp()
         z.params, z.filt, z.obs_clip, z.nzoo, z.ob_dim = self.params.data_ptr(), self.filt.data_ptr(), self.obs_clip, self.capacity, self.ob_dim
+        return z
+
+
+# order of a zoo LSTM net's row in the fused launches' table (include/sumo_hip.h ``sumo_zoo_lstm``): the policy branch only
+_ZOO_LSTM_ROW = ("p/emb/w", "p/emb/b", "lstmp/kernel", "lstmp/bias", "p/out/w", "p/out/b", "logstd")
+
+
+def zoo_lstm_table_rows(flats, ac_dim):
+    """Host rows of a device table of zoo LSTM nets (include/sumo_hip.h ``sumo_zoo_lstm``) from flat ``.npy`` vectors:
+    ``(params [n][Pz], filt [n][2][Dz])`` float32 -- each net's policy branch in the order ``p/emb/w | p/emb/b | lstmp/kernel |
+    lstmp/bias | p/out/w | p/out/b | logstd`` (row-major slices of :func:`split_zoo_lstm`), and its observation filter's
+    mean | 1 / std.  Zoo MLP vectors, vectors that fit neither family and vectors of different ``ob_dim`` raise ``ValueError``."""
+    flats = [np.asarray(f, np.float32).ravel() for f in flats]
+    if not flats:
+        raise ValueError("a zoo table needs at least one net")
+    params, filt, dims = [], [], []
+    for k, f in enumerate(flats):
+        try:
+            ob_dim, p = split_zoo_lstm(f, ac_dim)
+        except ValueError:
+            try:
+                infer_ob_dim(f.size, ac_dim)
+            except ValueError:
+                raise ValueError("net %d: %d parameters fit neither zoo policy with %d actions" % (k, f.size, ac_dim))
+            raise ValueError("net %d is a zoo MLP policy: a ZooLstmTable holds zoo LSTM nets only (zoo MLP nets play from a "
+                             "ZooTable)" % k)
+        mean, std = filter_stats(p, "obsfilter")
+        params.append(np.concatenate([np.asarray(p[n], np.float32).ravel() for n in _ZOO_LSTM_ROW]))
+        filt.append(np.stack([mean, (np.float32(1.0) / std).astype(np.float32)]))
+        dims.append(ob_dim)
+    if len(set(dims)) != 1:
+        raise ValueError("the nets of one zoo table share ob_dim; got %s" % sorted(set(dims)))
+    return np.stack(params).astype(np.float32), np.stack(filt).astype(np.float32)
+
+
+def zoo_file_kind(nparams, ac_dim):
+    """'mlp' or 'lstm': the zoo family whose layout a flat vector of ``nparams`` entries fits; ``ValueError`` if it fits neither.
+    Both counts grow by 130 per observation column (two filter sums plus two 64-wide input layers) and their offsets differ by 8
+    modulo 130 for every ``ac_dim``, so no length fits both families; should other widths ever make one fit both, it is refused
+    rather than guessed."""
+    def fits(c0, c1):
+        d, r = divmod(int(nparams) - c0, c1 - c0)
+        return r == 0 and d > 0
+
+    mlp = fits(zoo_mlp_param_count(0, ac_dim), zoo_mlp_param_count(1, ac_dim))
+    lstm = fits(zoo_lstm_param_count(0, ac_dim), zoo_lstm_param_count(1, ac_dim))
+    if mlp and lstm:
+        raise ValueError("%d parameters fit a zoo MLP and a zoo LSTM policy with %d actions: the family cannot be read from the "
+                         "length" % (nparams, ac_dim))
+    if not mlp and not lstm:
+        raise ValueError("%d parameters fit neither zoo policy with %d actions" % (nparams, ac_dim))
+    return "mlp" if mlp else "lstm"
+
+
+class ZooLstmTable(object):
+    """Device table of frozen zoo LSTM nets for the fused match launches (``sumo_match_steps_zoo_lstm`` /
+    ``sumo_match_steps_lstm_zoo_lstm``): ``params [n][Pz]`` and ``filt [n][2][ob_dim]`` CUDA tensors, plus one ``ppo_lstm_net``
+    per row (``nets``, filled as ``ZooLSTMPolicy._nets["p"]``) for the step-by-step path.  ``sources``: ``.npy`` paths, flat
+    vectors or :class:`ZooLSTMPolicy` objects (a :class:`ZooMLPPolicy` or an MLP-shaped vector is refused)."""
+
+    recurrent = True
+    obs_clip = 5.0
+    forget_bias = 1.0        # tf BasicLSTMCell
+    emb = hidden = HIDDEN
+
+    def __init__(self, sources, ac_dim, device=0):
+        import os
+        import torch
+        self.device = torch.device("cuda", int(device)) if not isinstance(device, torch.device) else device
+        self.ac_dim = int(ac_dim)
+        flats, self.labels = [], []
+        for src in sources:
+            if isinstance(src, ZooMLPPolicy):
+                raise ValueError("a ZooMLPPolicy does not play in a ZooLstmTable (zoo LSTM nets only): use ZooTable")
+            self.labels.append(str(src) if isinstance(src, (str, os.PathLike)) else None)
+            if isinstance(src, ZooLSTMPolicy):
+                if src.ac_dim != self.ac_dim:
+                    raise ValueError("zoo policy has %d actions, the table %d" % (src.ac_dim, self.ac_dim))
+                flats.append(src.flat)
+            elif isinstance(src, (str, os.PathLike)):
+                flats.append(np.load(os.path.expanduser(str(src)), allow_pickle=False))
+            else:
+                flats.append(src)
+        params, filt = zoo_lstm_table_rows(flats, self.ac_dim)
+        self.capacity, self.ob_dim = int(params.shape[0]), int(filt.shape[2])
+        self.params = torch.from_numpy(params).to(self.device)
+        self.filt = torch.from_numpy(filt).to(self.device)
+        D, E, H, A = self.ob_dim, self.emb, self.hidden, self.ac_dim
+        self.nets = (ppo_capi.LstmNet * self.capacity)()
+        for k in range(self.capacity):
+            n, base = self.nets[k], self.params[k].data_ptr()
+            n.ob_dim, n.emb_dim, n.hidden, n.ac_dim = D, E, H, A
+            n.gate_order, n.forget_bias = ppo_capi.LSTM_GATES_IJFO, self.forget_bias
+            n.obs_mean, n.obs_invstd, n.obs_clip = self.filt[k, 0].data_ptr(), self.filt[k, 1].data_ptr(), self.obs_clip
+            o = 0
+            for name, size in (("emb_w", D * E), ("emb_b", E), ("wx", E * 4 * H), ("wh", H * 4 * H), ("b", 4 * H), ("head_w", H * A),
+                               ("head_b", A), ("logstd", A)):
+                setattr(n, name, base + 4 * o)
+                o += size
+            assert o == self.params.shape[1]
+
+    def struct(self, state):
+        """The ``capi.ZooLstm`` launch struct of this table with agent 1's state rows ``state`` (contiguous float32 CUDA
+        [n][2 * 64], c | h); the tensors stay owned by their holders."""
+        from . import capi
+        z = capi.ZooLstm()
+        z.params, z.filt, z.state = self.params.data_ptr(), self.filt.data_ptr(), state.data_ptr()
+        z.obs_clip, z.forget_bias, z.nzoo, z.ob_dim, z.emb_dim, z.hidden = self.obs_clip, self.forget_bias, self.capacity, self.ob_dim, self.emb, self.hidden
         return z
 
 
@@ -298,7 +408,8 @@ class ZooLSTMPolicy(object):
         self._t = torch
         self.device = torch.device("cuda", int(device)) if not isinstance(device, torch.device) else device
         self.ac_dim, self.emb, self.hidden = int(ac_dim), int(emb), int(hidden)
-        self.ob_dim, p = split_zoo_lstm(flat_params, ac_dim, emb, hidden)
+        self.flat = np.asarray(flat_params, np.float32).ravel().copy()     # the zoo's own vector (ZooLstmTable reads it)
+        self.ob_dim, p = split_zoo_lstm(self.flat, ac_dim, emb, hidden)
         self.tensors = p
         mean, std = filter_stats(p, "obsfilter")
         self.ret_mean, self.ret_std = [float(x) for x in filter_stats(p, "retfilter")]

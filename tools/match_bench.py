@@ -6,6 +6,9 @@
     python tools/match_bench.py --network lstm     # LSTM(128) checkpoints: sumo_match_steps_lstm against ppo_lstm_step per side
     python tools/match_bench.py --opponent zoo --repeats 3   # MLP checkpoints against policy-zoo MLP nets: sumo_match_steps_zoo
                                                    # against ppo_forward + ppo_forward_filtered per step, repeats interleaved
+    python tools/match_bench.py --opponent zoo_lstm [--network lstm]   # checkpoints against policy-zoo LSTM nets:
+                                                   # sumo_match_steps_zoo_lstm / sumo_match_steps_lstm_zoo_lstm against ppo_forward
+                                                   # (or ppo_lstm_step) + ppo_lstm_step per step
 
 Prints one JSON line: env-steps/s and finished matches per second of both paths (stochastic play, Ant-vs-Ant by default)."""
 import argparse
@@ -31,6 +34,20 @@ def _zoo_flat(policy_zoo, D, A, rng):
     return np.concatenate(parts)
 
 
+def _zoo_lstm_flat(policy_zoo, D, A, rng):
+    """A synthetic policy-zoo LSTM vector: unit-count filter sums, O(1) weights."""
+    import numpy as np
+    sh = policy_zoo.zoo_lstm_shapes(D, A)
+    parts = []
+    for k in policy_zoo._ZOO_LSTM_ORDER:
+        s = sh[k]
+        v = {"count": 1000.0, "sum": 1000.0 * rng.normal(0, 0.5, s), "sumsq": 1000.0 * (0.25 + rng.uniform(0.0, 2.0, s))}.get(k.split("/")[-1])
+        if v is None:
+            v = rng.normal(-1.0, 0.3, s) if k == "logstd" else rng.normal(0, 1.0 / max(1.0, float(s[0])) ** 0.5 if len(s) == 2 else 0.1, s)
+        parts.append(np.asarray(v, np.float32).ravel())
+    return np.concatenate(parts)
+
+
 def main(argv):
     ap = argparse.ArgumentParser()
     ap.add_argument("--env", default="RoboSumo-Ant-vs-Ant-v0")
@@ -41,8 +58,8 @@ def main(argv):
     ap.add_argument("--warmup", type=int, default=64)
     ap.add_argument("--skip_stepwise", action="store_true")
     ap.add_argument("--network", choices=("mlp", "lstm"), default="mlp", help="MLP(64,64) or LSTM(128) snapshots")
-    ap.add_argument("--opponent", choices=("checkpoint", "zoo"), default="checkpoint", help="agent 1: checkpoints of the same table, or "
-                    "synthetic policy-zoo MLP nets (one per pair) in a ZooTable")
+    ap.add_argument("--opponent", choices=("checkpoint", "zoo", "zoo_lstm"), default="checkpoint", help="agent 1: checkpoints of the same "
+                    "table, synthetic policy-zoo MLP nets (one per pair) in a ZooTable, or synthetic policy-zoo LSTM nets in a ZooLstmTable")
     ap.add_argument("--repeats", type=int, default=1, help="timed runs per path, interleaved fused / step by step; the JSON line then "
                     "carries every run and the spread (max - min) of each path")
     args = ap.parse_args(argv)
@@ -73,6 +90,9 @@ def main(argv):
     if args.opponent == "zoo":
         from robosumo_selfplay_amd import policy_zoo
         zoo_table = policy_zoo.ZooTable([_zoo_flat(policy_zoo, D - 1, A, rng) for _ in range(args.pairs)], A, env.device)
+    elif args.opponent == "zoo_lstm":
+        from robosumo_selfplay_amd import policy_zoo
+        zoo_table = policy_zoo.ZooLstmTable([_zoo_lstm_flat(policy_zoo, D - 1, A, rng) for _ in range(args.pairs)], A, env.device)
     idx0_h, idx1_h, _ = matches.env_assignment([(2 * p, p if zoo_table is not None else 2 * p + 1) for p in range(args.pairs)],
                                                list(range(args.pairs)), epp, N)
     idx0, idx1 = torch.from_numpy(idx0_h).cuda(), torch.from_numpy(idx1_h).cuda()
@@ -81,11 +101,14 @@ def main(argv):
     noise = tuple(torch.randn((K, N, A), generator=gen, device="cuda") for _ in range(2))
     out = dict(env=args.env, network=args.network, opponent=args.opponent, num_env=N, pairs=args.pairs, chunk=K)
     quota = 1 << 30
-    states = tuple(torch.zeros((N, 256), dtype=torch.float32, device="cuda") for _ in range(2))
+    states = tuple(torch.zeros((N, 128 if args.opponent == "zoo_lstm" and g == 1 else 256), dtype=torch.float32, device="cuda") for g in range(2))
 
     def launch(fused, score):
         i0, i1 = (idx0, idx1) if fused else (idx0_h, idx1_h)
-        if zoo_table is not None:
+        if args.opponent == "zoo_lstm":
+            (matches.zoo_lstm_match_steps_fused if fused else matches.zoo_lstm_match_steps_stepwise)(
+                env, table, zoo_table, i0, i1, states if args.network == "lstm" else states[1], score, quota, K, noise)
+        elif zoo_table is not None:
             (matches.zoo_match_steps_fused if fused else matches.zoo_match_steps_stepwise)(env, table, zoo_table, i0, i1, score, quota, K, noise)
         elif args.network == "lstm":
             (matches.match_steps_fused_lstm if fused else matches.match_steps_stepwise_lstm)(env, table, i0, i1, states, score, quota, K, noise)

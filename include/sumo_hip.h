@@ -234,6 +234,20 @@ int sumo_match_steps_zoo_lstm(sumo_handle_t h, const sumo_match* m, const sumo_z
 int sumo_match_steps_lstm_zoo_lstm(sumo_handle_t h, const sumo_match_lstm* m, const sumo_zoo_lstm* z, float* actions_dev, float* obs_dev,
                                    double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev,
                                    void* stream);
+/* sumo_rollout_steps_zoo_lstm: sumo_rollout_steps_zoo with agent 1 played by a zoo LSTM net (learn(opponent_mode='fix') with an
+ *   LSTM file): per step and env the learner's MLP(64,64) policy and value nets on both observations; the learner samples action 0;
+ *   zoo net r->opponent_index[e] of z (NULL = net 0) acts on agent 1's observation from the env's row of z->state, which is zeroed
+ *   first where AGENT 1's done flag of the previous step is set (the Runner's M = dones[:, 1]) and left at the new state; its action
+ *   is mean + exp(logstd) * noise1 and its neglogp goes to onlp[1].  The same net then scores action 0 on agent 0's observation
+ *   from a ZERO state (one cell evaluation, no state written) for onlp[0], as the Runner's scoring calls feed no state; the learner
+ *   scores and values action 1.  The record holds the raw observations.  z->state: [E][2 * 64] rows of this engine's envs.
+ *   Every recorded number equals ppo_forward (learner) / ppo_lstm_step (zoo net) bit for bit.
+ *   Refused: r->opponent_params != NULL, r->npool != z->nzoo, and whatever sumo_rollout_steps (cfrc_mode rne_post, mixed match-ups,
+ *   ...) and the zoo LSTM match launches (ob_dim outside [1, the scene's ob_dim], nzoo < 1, missing params / filt / state,
+ *   obs_clip <= 0, emb_dim / hidden other than 64) refuse.  An opponent_index outside [0, nzoo) raises the launch's abort flag
+ *   (sumo_rollout_status returns -20) and plays row 0. */
+int sumo_rollout_steps_zoo_lstm(sumo_handle_t h, const sumo_rollout* r, const sumo_zoo_lstm* z, float* actions_dev, float* obs_dev,
+                                double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream);
 /* cfrc_mode (reference agents.py:190-214 reads sim.data.cfrc_ext into 84 of the 121 observation entries):
  *   0 = zero (default): what the reference produces -- its MuJoCo 2.1 scenes declare no force / torque / accelerometer sensor, so
  *       mj_rnePostConstraint never runs and cfrc_ext stays at its reset value 0;

@@ -92,7 +92,8 @@ def selection_probs(action_prob, new_action_probs):
 
 
 def install_fixed_opponent(runner, fix_opponent_path, ac_dim, dev, seed):
-    """``opponent_mode='fix'`` (alg_ppo.py:194-206, alg_ac.py:175-189): a policy-zoo MLP net plays agent 1 for the whole run."""
+    """``opponent_mode='fix'`` (alg_ppo.py:194-206, alg_ac.py:175-189): a policy-zoo net (MLP or LSTM: the file's length selects
+    the family) plays agent 1 for the whole run."""
     from .policy_zoo import FixedOpponentModel, load_zoo_policy
     if fix_opponent_path is None:
         raise ValueError("opponent_mode='fix' needs fix_opponent_path=<policy_zoo .npy> (reference default: "
@@ -180,7 +181,7 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
         m.act_model.seed((seed or 0) * 1000 + 17 * i + rank)
     runner = Runner(env=env, models=models, nsteps=nsteps, nagent=nagent, gamma=gamma, lam=lam, rho_bar=rho_bar, c_bar=c_bar,
                     anneal_bound=anneal_bound)
-    # opt-in: in opponent_mode='fix' the zoo MLP net plays inside the fused rollout launch (Runner.fused_fix_opponent: another noise stream)
+    # opt-in: in opponent_mode='fix' the zoo net (MLP or LSTM) plays inside the fused rollout launch (Runner.fused_fix_opponent: another noise stream)
     runner.fused_fix_opponent = bool(fused_fix_opponent)
     # opponent_pool = K > 1 (extension, BASELINE config 5): K frozen snapshots stay resident in HBM and every env plays against its own
     # one (opponent_pool.py); each update draws K snapshots by the selection law of ``opponent_mode`` instead of one.  K = 1 is the
@@ -216,7 +217,7 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
         frac = 1.0 - (update - 1.0) / nupdates
         lrnow, cliprangenow = lr(frac), cliprange(frac)
         # ---- opponent selection (alg_ppo.py:191-247); rank 0 decides, everyone loads the same file
-        if opponent_mode == "fix":                                       # alg_ppo.py:194-206: a policy-zoo MLP net
+        if opponent_mode == "fix":                                       # alg_ppo.py:194-206: a policy-zoo net
             if update == 1:
                 install_fixed_opponent(runner, fix_opponent_path, ac_space.shape[0], dev, (seed or 0) * 1000 + 17 + rank)
         elif update == 1:

@@ -84,6 +84,7 @@ def lib():
         L.sumo_match_steps_zoo.argtypes = [vp, C.POINTER(Match), C.POINTER(ZooMlp)] + [vp] * 8
         L.sumo_match_steps_zoo_lstm.argtypes = [vp, C.POINTER(Match), C.POINTER(ZooLstm)] + [vp] * 8
         L.sumo_match_steps_lstm_zoo_lstm.argtypes = [vp, C.POINTER(MatchLstm), C.POINTER(ZooLstm)] + [vp] * 8
+        L.sumo_rollout_steps_zoo_lstm.argtypes = [vp, C.POINTER(Rollout), C.POINTER(ZooLstm)] + [vp] * 8
         L.sumo_get_state.argtypes = [vp] * 5
         L.sumo_set_cfrc_mode.argtypes = [vp, i32]
         L.sumo_get_cfrc_ext.argtypes = [vp, vp]
@@ -102,14 +103,14 @@ def lib():
         L.sumo_static_layout.restype = i32
         L.sumo_profile.restype = i32
         for n in ("sumo_create", "sumo_destroy", "sumo_dims", "sumo_reset", "sumo_step", "sumo_rollout_steps", "sumo_rollout_steps_lstm", "sumo_match_steps", "sumo_match_steps_lstm",
-                  "sumo_rollout_steps_zoo", "sumo_match_steps_zoo", "sumo_match_steps_zoo_lstm", "sumo_match_steps_lstm_zoo_lstm", "sumo_get_state", "sumo_set_cfrc_mode", "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_set_state", "sumo_debug_forward", "sumo_stats"):
+                  "sumo_rollout_steps_zoo", "sumo_match_steps_zoo", "sumo_match_steps_zoo_lstm", "sumo_match_steps_lstm_zoo_lstm", "sumo_rollout_steps_zoo_lstm", "sumo_get_state", "sumo_set_cfrc_mode", "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_set_state", "sumo_debug_forward", "sumo_stats"):
             getattr(L, n).restype = i32
         _LIB = L
     return _LIB
 
 
 EXPORTS = ("sumo_last_error", "sumo_create", "sumo_destroy", "sumo_dims", "sumo_reset", "sumo_step", "sumo_rollout_steps",
-           "sumo_rollout_steps_lstm", "sumo_match_steps", "sumo_match_steps_lstm", "sumo_rollout_steps_zoo", "sumo_match_steps_zoo", "sumo_match_steps_zoo_lstm", "sumo_match_steps_lstm_zoo_lstm", "sumo_set_cfrc_mode", "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_get_state", "sumo_set_state", "sumo_debug_forward", "sumo_stats", "sumo_profile", "sumo_debug_trace",
+           "sumo_rollout_steps_lstm", "sumo_match_steps", "sumo_match_steps_lstm", "sumo_rollout_steps_zoo", "sumo_match_steps_zoo", "sumo_match_steps_zoo_lstm", "sumo_match_steps_lstm_zoo_lstm", "sumo_rollout_steps_zoo_lstm", "sumo_set_cfrc_mode", "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_get_state", "sumo_set_state", "sumo_debug_forward", "sumo_stats", "sumo_profile", "sumo_debug_trace",
            "sumo_rollout_status", "sumo_debug_fault", "sumo_static_layout", "sumo_debug_layout", "sumo_debug_model_ints", "sumo_debug_dump")
 
 
@@ -201,6 +202,12 @@ class Engine:
         """The same for LSTM(128) checkpoints (``sumo_match_steps_lstm_zoo_lstm``); ``mo`` is a filled :class:`MatchLstm` with
         ``state1`` left None (agent 1's state is ``zoo.state``)."""
         self._fused("sumo_match_steps_lstm_zoo_lstm", mo, env_ptrs, stream, zoo)
+
+    def rollout_steps_zoo_lstm(self, ro, zoo, *env_ptrs, stream=None):
+        """K fused rollout steps against policy-zoo LSTM nets (``sumo_rollout_steps_zoo_lstm``); ``ro`` is a filled :class:`Rollout`
+        (``opponent_params`` None, ``npool`` = ``zoo.nzoo``), ``zoo`` a filled :class:`ZooLstm` (``state``: agent 1's rows of the
+        launch's envs, read and updated in place)."""
+        self._fused("sumo_rollout_steps_zoo_lstm", ro, env_ptrs, stream, zoo)
 
     def set_cfrc_mode(self, mode):
         """'zero' (default, the reference's behaviour) or 'rne_post' (include/sumo_hip.h: cfrc_mode)."""

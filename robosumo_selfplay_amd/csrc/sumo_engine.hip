@@ -2580,7 +2580,9 @@ struct RolloutArgs {
   // every 16-env tile of the whole env set (NULL: snapshot 0), and the acting nets' states [N][2 hidden] (c | h) per agent
   // (the zoo modes evaluate no recurrent net: their fields overlay lnet, so the struct -- and with it the kernel-argument
   // segment every instantiation reads -- keeps its size and offsets)
-  union { ppo_lstm_net lnet; ZooArgs zoo; };
+  // (sumo_rollout_steps_zoo_lstm, POLICY 8, writes the rollout record, so its zoo LSTM fields cannot sit in zl: they travel
+  // here as zlr -- its learner is an MLP and reads no lnet)
+  union { ppo_lstm_net lnet; ZooArgs zoo; ZooLstmArgs zlr; };
   const ppo_lstm_net* onets;
   const int32_t* tile_net;
   float *st0, *st1;
@@ -3140,6 +3142,104 @@ __device__ __forceinline__ void rollout_policy_phase_match_lstm_zoo_lstm(C& c, c
   wave_sync();
 }
 
+// ---- rollout against policy-zoo LSTM nets (POLICY 8) ----
+// Mean of the Gaussian head of zoo LSTM net row p (the row layout of zoo_lstm_act) on ONE staged observation row: xrow is filtered in
+// place, then embedding, gate sums, cell and head as in zoo_lstm_act -- the accumulation order of
+// ppo_lstm_step_kernel<64, PPO_LSTM_GATES_IJFO>.  STATE: the previous state is the row sp (c | h) masked by `keep`, and the new state
+// is written back to it (hand-over accesses: the row crosses waves); otherwise the cell starts from zeros and nothing is written --
+// the recurrent half of the gate sum still runs, over a zero row, so the additions stay the step kernel's.  q: the launch's
+// ZooLstmArgs, sc as in zoo_lstm_act.  Lanes < A return their column.  (zoo_lstm_act is not rebuilt on top of this function: modes
+// 6 / 7 keep their code objects.)
+template <bool STATE, class ZA>
+__device__ __forceinline__ float zoo_lstm_mean(const ZA& q, const float PT_GAS* p, const float* filt, float* sp, float keep, float* xrow,
+                                               float* sc, int lane) {
+  constexpr int NH = 64, EM = PT_H;
+  const int Dz = q.Dz, A = q.A;
+  const float PT_GAS* emb_b = p + Dz * EM;
+  const float PT_GAS* wx = emb_b + EM;
+  const float PT_GAS* wh = wx + EM * 4 * NH;
+  const float PT_GAS* b_ = wh + NH * 4 * NH;
+  const float PT_GAS* head_w = b_ + 4 * NH;
+  const float PT_GAS* head_b = head_w + NH * A;
+  float *eb = sc, *hp = sc + EM, *hn = hp + NH;
+  float cp = 0.0f, hv = 0.0f;
+  if constexpr (STATE) { cp = hand_load<true>(sp + lane) * keep; hv = hand_load<true>(sp + NH + lane) * keep; }   // lane owns the unit `lane`
+  hp[lane] = hv;
+  float bz[4];
+#pragma unroll
+  for (int g = 0; g < 4; g++) bz[g] = b_[g * NH + lane];       // (in flight during the embedding and the gate sums)
+  zoo_lstm_embed(p, emb_b, filt, q.clip, xrow, Dz, eb, lane);
+  wave_sync();
+  float z[4][1][1];
+  const float* const xr[1] = {eb};
+  const float* const hr[1] = {hp};
+  lstm_gates_valu<NH, 1>((const float*)wx, (const float*)wh, q.emb, xr, hr, lane, z);
+  // gate order i, j, f, o: z[1] is the candidate, z[2] the forget gate
+  const LstmCell cl = lstm_cell(z[0][0][0], z[2][0][0], z[3][0][0], z[1][0][0], bz[0], bz[2] + q.forget_bias, bz[3], bz[1], cp);
+  if constexpr (STATE) lstm_state_store<NH>(sp, lane, cl);
+  hn[lane] = cl.hn;
+  wave_sync();
+  float m[1];
+  lstm_heads_valu<NH, 1>((const float*)head_w, (const float*)head_w, A, hn, lane, m);   // (lane 16's value sum reads head_w: no value head here)
+  return m[0] + (lane < A ? head_b[lane] : 0.0f);
+}
+
+// Rollout against a policy-zoo LSTM net (sumo_rollout_steps_zoo_lstm, POLICY 8; learn(opponent_mode='fix') with an LSTM file):
+// rollout_policy_phase_zoo with the zoo MLP trunk replaced by the policy branch of zoo LSTM net opp_idx[e].  The learner's policy and
+// value trunks run on the raw tile, both rows (the raw observations are in the rollout record by then) and agent 0's action is
+// sampled; the hidden tiles then become the cell's rows (r.zlr.sc_off, as in mode 6: no extra LDS).  The zoo net acts on row 1 from
+// the env's state row st1[e], masked by AGENT 1's done flag of the previous step (the Runner's M = dones[:, 1]) and updated in place;
+// it then scores agent 0's action on row 0 from a zero state, writing no state (the Runner's scoring calls feed no state).  Both rows
+// are filtered in place; the record holds the raw ones.  The launch fields travel in RolloutArgs::zlr (the lnet union: the learner
+// is an MLP), since this mode needs the six record pointers r.zl overlays.  Every recorded number equals ppo_forward (learner) /
+// ppo_lstm_step (zoo net) bit for bit.
+template <class C, class SA, class RA>
+__device__ __forceinline__ void rollout_policy_phase_zoo_lstm(C& c, const SA& a, const RA& r, int e, int s) {
+  const int lane = c.lane, i = lane & 15, kq = lane >> 4;
+  const int D = r.L.D, A = r.L.A, XS = r.XS;
+  const auto& q = r.zlr;
+  float* xbuf = (float*)(c.sm + r.lds_off);        // [2][XS] | h1 [2][PT_HS] | h2 [2][PT_HS]
+  float* h1 = xbuf + 2 * XS;
+  float* h2 = h1 + 2 * PT_HS;
+  const size_t col = (size_t)r.env_offset + e;
+  const size_t slot0 = ((size_t)0 * r.T + s) * r.Ntot + col, slot1 = ((size_t)1 * r.T + s) * r.Ntot + col;
+  policy_load_obs<false, true>(a, r, e, lane, xbuf, D, XS, slot0, slot1);
+  const unsigned dn = policy_prev_done(a, e);
+  if (lane < 2) policy_record_done(r, lane, slot0, slot1, dn);
+  wave_sync();
+  const int jz = policy_checked_row(a, lane, r.opp_idx ? pt_global(r.opp_idx)[e] : 0, q.nzoo);
+  const float PT_GAS* lp = pt_global(r.learner);
+  const f32x4 mL4 = trunk_forward<false, 2>(pi_net((const float*)lp, r.L), xbuf, XS, D, h1, h2, lane);
+  const float mL0 = mL4[0], mL1 = mL4[1];
+  wave_sync();
+  const f32x4 vL4 = trunk_forward<false, 2>(vf_net((const float*)lp, r.L), xbuf, XS, D, h1, h2, lane);
+  const float vL0 = vL4[0], vL1 = vL4[1];
+  // heads: row 0 = agent 0 (learner acts, zoo net scores), row 1 = agent 1 (zoo net acts, learner scores and values)
+  const bool colk = i < A;
+  const bool ok = colk && kq == 0;                  // rows 0 and 1 live in the first 16 lanes (D layout: rows 4 kq + r)
+  const float lsL = colk ? lp[r.L.logstd + i] : 0.0f;
+  const float stdL = expf(lsL), sumL = row16_sum(lsL);
+  const size_t nz = policy_noise_index(a, e, s, A, i);
+  float act0 = 0.0f, act1 = 0.0f;
+  const float nlp0 = gauss_row(mL0, stdL, sumL, ok, true, ok ? pt_global(r.noise0)[nz] : 0.0f, act0, A);   // learner samples for agent 0
+  wave_sync();   // the hidden tiles become the cell's rows
+  const float PT_GAS* zp = pt_global(q.params) + (size_t)jz * q.Pz;
+  const float* zf = q.filt + (size_t)jz * 2 * q.Dz;
+  float* sc = xbuf + q.sc_off;
+  const float lsO = ok ? zp[q.Pz - A + i] : 0.0f;   // the row ends with logstd [A]
+  const float stdO = expf(lsO), sumO = row16_sum(lsO);
+  const float keep1 = 1.0f - (float)((dn >> 8) & 0xff);
+  const float mO1 = zoo_lstm_mean<true>(q, zp, zf, r.st1 + (size_t)e * 128, keep1, xbuf + XS, sc, lane);
+  const float onlp1 = gauss_row(mO1, stdO, sumO, ok, true, ok ? pt_global(r.noise1)[nz] : 0.0f, act1, A);   // zoo net samples for agent 1 ...
+  const float nlp1 = gauss_row(mL1, stdL, sumL, ok, false, 0.0f, act1, A);                                  // ... the learner scores it
+  wave_sync();   // the cell's rows are rewritten by the scoring pass
+  const float mO0 = zoo_lstm_mean<false>(q, zp, zf, nullptr, 0.0f, xbuf, sc, lane);
+  const float onlp0 = gauss_row(mO0, stdO, sumO, ok, false, 0.0f, act0, A);                                 // the zoo net scores agent 0's action
+  if (ok) policy_commit_actions<true>(c, a, r, e, i, act0, act1, A, slot0, slot1);
+  if (lane == 0) policy_record_scalars(r, slot0, slot1, nlp0, nlp1, onlp0, onlp1, vL0, vL1);
+  wave_sync();   // the action buffer is read back by the env step (other lanes), the scratch region becomes the mass matrix again
+}
+
 // Match post phase: where agent 0's episode ended in the step, score it from the step's winner flags (info[.][7] bit 0, just
 // written by this lane): a win if agent 0 carries the flag, a loss if only agent 1 does, a draw otherwise (timeouts, diverged states)
 // -- policy_zoo._evaluate_against's rule.  Counted while wins + losses + draws < quota.
@@ -3180,6 +3280,8 @@ __device__ __forceinline__ void rollout_post_phase(C& c, const SA& a, const RA& 
 // segment itself, where the runtime has placed the struct at launch (no separate copy to keep alive).
 struct RolloutLaunch { StepArgs a; RolloutArgs r; };
 static_assert(sizeof(ZooArgs) <= sizeof(ppo_lstm_net), "ZooArgs overlays RolloutArgs::lnet");
+static_assert(sizeof(ZooLstmArgs) <= sizeof(ppo_lstm_net) && offsetof(RolloutArgs, zlr) == offsetof(RolloutArgs, lnet),
+              "ZooLstmArgs (POLICY 8) overlays RolloutArgs::lnet");
 static_assert(sizeof(ZooLstmArgs) <= 6 * sizeof(float*) && offsetof(RolloutArgs, obs) == offsetof(RolloutArgs, zl) &&
                   offsetof(RolloutArgs, obs) == offsetof(RolloutArgs, noise1) + sizeof(float*) &&
                   offsetof(RolloutArgs, onlp) == offsetof(RolloutArgs, obs) + 5 * sizeof(float*) &&
@@ -3205,7 +3307,8 @@ template <int NV, int POLICY, int SL = 0>   // POLICY 0: MLP(64,64) policy / val
                                             // (sumo_rollout_steps_zoo); 5: MLP checkpoints against policy-zoo MLP nets
                                             // (sumo_match_steps_zoo); 6: MLP checkpoints against policy-zoo LSTM nets
                                             // (sumo_match_steps_zoo_lstm); 7: LSTM(128) checkpoints against policy-zoo LSTM
-                                            // nets (sumo_match_steps_lstm_zoo_lstm); SL 1: static Layout
+                                            // nets (sumo_match_steps_lstm_zoo_lstm); 8: MLP learner against policy-zoo LSTM
+                                            // nets (sumo_rollout_steps_zoo_lstm); SL 1: static Layout
 __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(SUMO_WPE_OF(NV), SUMO_WPE_OF(NV))))
 sumo_rollout_kernel(const Params* P, RolloutLaunch launch_args) {
   // `launch_args` is read in place from the kernel-argument segment (second argument, 8-byte aligned right behind P) through a
@@ -3265,6 +3368,7 @@ sumo_rollout_kernel(const Params* P, RolloutLaunch launch_args) {
     else if constexpr (POLICY == 5) rollout_policy_phase_match_zoo(c, lp->a, lp->r, e, s);
     else if constexpr (POLICY == 6) rollout_policy_phase_match_zoo_lstm(c, lp->a, lp->r, e, s);
     else if constexpr (POLICY == 7) rollout_policy_phase_match_lstm_zoo_lstm<128>(c, lp->a, lp->r, e, s);
+    else if constexpr (POLICY == 8) rollout_policy_phase_zoo_lstm(c, lp->a, lp->r, e, s);
     else rollout_policy_phase(c, lp->a, lp->r, e, s);
 #ifdef SUMO_DBG_HARD_BARRIER
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -3277,7 +3381,7 @@ sumo_rollout_kernel(const Params* P, RolloutLaunch launch_args) {
     asm volatile("" : "+s"(e), "+s"(k));
     lp = launder_sptr(LP);
     s = lp->r.s0 + k;
-    if constexpr (POLICY == 2 || POLICY == 3 || POLICY >= 5) rollout_post_phase_match(c, lp->a, lp->r, e);
+    if constexpr (POLICY == 2 || POLICY == 3 || (POLICY >= 5 && POLICY <= 7)) rollout_post_phase_match(c, lp->a, lp->r, e);
     else rollout_post_phase(c, lp->a, lp->r, e, s);
     prof = lp->r.prof;
     if (prof && c.lane == 0) {
@@ -4130,6 +4234,7 @@ static int rollout_launch(sumo_engine* E, const RolloutArgs& r, int policy, cons
                                                        : policy == 5 ? sumo_rollout_kernel<NV, 5, SL>
                                                        : policy == 6 ? sumo_rollout_kernel<NV, 6, SL>
                                                        : policy == 7 ? sumo_rollout_kernel<NV, 7, SL>
+                                                       : policy == 8 ? sumo_rollout_kernel<NV, 8, SL>
                                                                      : sumo_rollout_kernel<NV, 0, SL>;
         hipLaunchKernelGGL(kernel, g_, b_, lds_, st_, E->d_params, rl);
       }))
@@ -4354,10 +4459,11 @@ extern "C" int sumo_match_steps_zoo(sumo_handle_t E, const sumo_match* mo, const
   return rollout_launch(E, r, 5, b, stream);
 }
 
-// the zoo LSTM table of sumo_match_steps_zoo_lstm / sumo_match_steps_lstm_zoo_lstm: checks, then the fields of RolloutArgs it fills
+// the zoo LSTM table of sumo_match_steps_zoo_lstm / sumo_match_steps_lstm_zoo_lstm / sumo_rollout_steps_zoo_lstm: checks, then the
+// fields of RolloutArgs it fills -- st1 and the launch's ZooLstmArgs q (r.zl in the match modes, r.zlr in the rollout mode)
 // (after place_*_scratch: the cell's rows -- embedding | previous latent | new latent, 64 floats each -- go behind the observation
 // tile, 16-byte aligned, into the `rows_floats` floats the placed scratch holds there)
-static int place_zoo_lstm_table(RolloutArgs& r, const sumo_zoo_lstm* z, int od, int ad, int rows_floats) {
+static int place_zoo_lstm_table(RolloutArgs& r, ZooLstmArgs& q, const sumo_zoo_lstm* z, int od, int ad, int rows_floats) {
   if (!z->params || !z->filt) FAIL(-2, "sumo_zoo_lstm: missing buffer (params / filt)");
   if (!z->state) FAIL(-2, "sumo_zoo_lstm: missing state buffer (state)");
   if (z->nzoo < 1) FAIL(-7, "nzoo %d: the zoo table needs at least one entry", z->nzoo);
@@ -4365,7 +4471,6 @@ static int place_zoo_lstm_table(RolloutArgs& r, const sumo_zoo_lstm* z, int od, 
     FAIL(-4, "zoo ob_dim %d outside [1, %d]: a policy-zoo LSTM net reads the first ob_dim columns of the scene's observation", z->ob_dim, od);
   if (z->emb_dim != PT_H || z->hidden != 64) FAIL(-4, "zoo LSTM emb_dim %d / hidden %d: the fused launch is built for 64 / 64", z->emb_dim, z->hidden);
   if (!(z->obs_clip > 0.0f)) FAIL(-9, "obs_clip %g must be positive", (double)z->obs_clip);
-  ZooLstmArgs& q = r.zl;
   q.params = z->params; q.filt = z->filt; q.clip = z->obs_clip; q.forget_bias = z->forget_bias; q.nzoo = z->nzoo; q.Dz = z->ob_dim; q.A = ad; q.emb = z->emb_dim;
   q.Pz = z->ob_dim * PT_H + PT_H + 2 * 64 * 256 + 256 + 64 * ad + 2 * ad;
   r.st1 = z->state;
@@ -4395,7 +4500,7 @@ extern "C" int sumo_match_steps_zoo_lstm(sumo_handle_t E, const sumo_match* mo, 
   r.snaps = mo->params;
   copy_match_fields(r, mo, E->N);
   if (int rc = place_mlp_scratch(E, mo->ob_dim, mo->ac_dim, r)) return rc;
-  if (int rc = place_zoo_lstm_table(r, z, od, ad, 4 * PT_HS)) return rc;   // the two hidden tiles of agent 0's trunk
+  if (int rc = place_zoo_lstm_table(r, r.zl, z, od, ad, 4 * PT_HS)) return rc;   // the two hidden tiles of agent 0's trunk
   return rollout_launch(E, r, 6, b, stream);
 }
 
@@ -4422,8 +4527,29 @@ extern "C" int sumo_match_steps_lstm_zoo_lstm(sumo_handle_t E, const sumo_match_
   r.lnet = n; r.onets = mo->nets_dev; r.st0 = mo->state0;
   copy_match_fields(r, mo, E->N);
   if (int rc = place_lstm_scratch(E, od, 2, r)) return rc;   // agent 0's previous and new latent
-  if (int rc = place_zoo_lstm_table(r, z, od, ad, 2 * 128)) return rc;
+  if (int rc = place_zoo_lstm_table(r, r.zl, z, od, ad, 2 * 128)) return rc;
   return rollout_launch(E, r, 7, b, stream);
+}
+
+extern "C" int sumo_rollout_steps_zoo_lstm(sumo_handle_t E, const sumo_rollout* ro, const sumo_zoo_lstm* z, float* actions_dev, float* obs_dev,
+                                           double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
+  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
+  if (int rc = check_launch_args(E, ro, b)) return rc;
+  if (!z) FAIL(-1, "bad arguments");
+  if (!ro->learner_params || rollout_buffer_missing(ro)) FAIL(-2, "sumo_rollout: missing buffer");
+  if (ro->opponent_params) FAIL(-2, "sumo_rollout_steps_zoo_lstm: opponent_params must be NULL (the opponents are the zoo table's nets)");
+  int od = 0, ad = 0;
+  if (int rc = rollout_scene(E, ro->T, ro->Ntot, ro->env_offset, ro->s0, ro->K, &od, &ad)) return rc;
+  if (int rc = check_dims(ro->ob_dim, ro->ac_dim, od, ad)) return rc;
+  if (ro->npool != z->nzoo) FAIL(-7, "npool %d must equal the zoo table's nzoo %d", ro->npool, z->nzoo);
+  HIPCHK(hipSetDevice(E->device));
+  RolloutArgs r;
+  memset(&r, 0, sizeof r);
+  r.learner = ro->learner_params; r.opp_idx = ro->opponent_index;
+  copy_rollout_fields(r, ro);
+  if (int rc = place_mlp_scratch(E, ro->ob_dim, ro->ac_dim, r)) return rc;
+  if (int rc = place_zoo_lstm_table(r, r.zlr, z, od, ad, 4 * PT_HS)) return rc;   // the two hidden tiles of the learner's trunks
+  return rollout_launch(E, r, 8, b, stream);
 }
 
 #ifdef SUMO_POLICY_PROBE

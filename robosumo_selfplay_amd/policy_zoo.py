@@ -10,7 +10,7 @@ Reference:
   * alg_ppo.py:194-206                             ``opponent_mode='fix'``
 
 MLP and LSTM zoo nets are built (policy.py:23-91 and :94-199); the LSTM one keeps a per-env recurrent state on the device.
-Both families also play inside the fused match launches from device tables: :class:`ZooTable` (MLP nets) and
+Both families also play inside the fused rollout and match launches from device tables: :class:`ZooTable` (MLP nets) and
 :class:`ZooLstmTable` (LSTM nets, policy branch only).
 The ``.npy`` files are loaded with ``numpy.load(allow_pickle=False)``.
 """
@@ -193,8 +193,8 @@ def zoo_file_kind(nparams, ac_dim):
 
 
 class ZooLstmTable(object):
-    """Device table of frozen zoo LSTM nets for the fused match launches (``sumo_match_steps_zoo_lstm`` /
-    ``sumo_match_steps_lstm_zoo_lstm``): ``params [n][Pz]`` and ``filt [n][2][ob_dim]`` CUDA tensors, plus one ``ppo_lstm_net``
+    """Device table of frozen zoo LSTM nets for the fused launches (``sumo_match_steps_zoo_lstm`` /
+    ``sumo_match_steps_lstm_zoo_lstm`` / ``sumo_rollout_steps_zoo_lstm``): ``params [n][Pz]`` and ``filt [n][2][ob_dim]`` CUDA tensors, plus one ``ppo_lstm_net``
     per row (``nets``, filled as ``ZooLSTMPolicy._nets["p"]``) for the step-by-step path.  ``sources``: ``.npy`` paths, flat
     vectors or :class:`ZooLSTMPolicy` objects (a :class:`ZooMLPPolicy` or an MLP-shaped vector is refused)."""
 
@@ -399,9 +399,16 @@ class ZooLSTMPolicy(object):
     """policy.py:94-199 on the device: observation filter -> relu embedding (64) -> BasicLSTMCell(64) -> head, separately
     for the value and the policy (two cells).  The recurrent state of every env lives in ``self.state`` ([4][n][64]:
     value c, value h, policy c, policy h -- the reference's ``zero_state`` order); ``reset(mask)`` zeroes the rows of
-    finished episodes (the reference calls ``policy.reset()`` when an episode starts)."""
+    finished episodes (the reference calls ``policy.reset()`` when an episode starts).
+
+    ``step`` / ``value`` / ``action_probability`` are the surface ``FixedOpponentModel`` and the ``Runner`` call
+    (``opponent_mode='fix'``), with the Runner's rules for recurrent opponents: the acting call masks the state rows by the done
+    flags ``M`` of the previous step and advances them, the scoring call (``given_action``) is one cell evaluation from a zero
+    state that writes no state.  :meth:`evaluate` is the same on explicit noise rows and an explicit state.  All of them are
+    ``ppo_lstm_step`` launches on the policy branch (``value``: on the value branch)."""
 
     recurrent = True
+    initial_state = None     # the acting state lives in the policy (``S=None``) or in the caller's tensor
 
     def __init__(self, flat_params, ac_dim, device=0, emb=HIDDEN, hidden=HIDDEN):
         import torch
@@ -482,6 +489,108 @@ class ZooLSTMPolicy(object):
         return (a[0] if single else a), info
 
 
+    # ---- PolicyWithValue surface (policies.py:84-128 of the reference) with the S / M feeds of models.py:163-170 ---------------
+    def _obs(self, x):
+        t = self._t
+        np_in = isinstance(x, np.ndarray) or not t.is_tensor(x)
+        if np_in:
+            x = np.asarray(x, np.float32)
+            x = t.from_numpy(np.ascontiguousarray(x[None] if x.ndim == 1 else x)).to(self.device)
+        if x.dtype != t.float32 or not x.is_cuda or x.dim() != 2 or x.stride(1) != 1 or x.shape[1] < self.ob_dim:
+            raise ValueError("expected float32 [n, >=%d] observations with unit inner stride" % self.ob_dim)
+        return x, np_in
+
+    def _own_state(self, n):
+        if self.state is None or self.state.shape[1] != n:
+            self.state = self._t.zeros((4, n, self.hidden), dtype=self._t.float32, device=self.device)
+        return self.state
+
+    def _mask(self, M, n):
+        t = self._t
+        if M is None:
+            return None
+        m = (M if t.is_tensor(M) else t.from_numpy(np.ascontiguousarray(np.asarray(M).reshape(-1), np.float32))).to(self.device, t.float32)
+        if tuple(m.shape) != (n,):
+            raise ValueError("the done mask must have shape (%d,)" % n)
+        return m.contiguous()
+
+    def evaluate(self, obs, state=None, mask=None, given_action=None, deterministic=False, noise=None, out=None):
+        """One ``ppo_lstm_step`` launch of the policy branch on device tensors.  ``given_action`` None: the net ACTS -- ``state`` is
+        a contiguous float32 CUDA [n, 2 * hidden] tensor (c | h), or None for the policy's own state; its rows are zeroed where
+        ``mask`` (the done flags of the previous step) is set and then advanced IN PLACE; the action is the mean
+        (``deterministic``) or mean + exp(logstd) * ``noise`` (explicit contiguous float32 CUDA [n, ac_dim] rows; None: drawn from
+        ``self.gen``).  With ``given_action`` the net SCORES it: one cell evaluation from a zero state (a scratch buffer zeroed
+        for every call), no state is written, ``state`` / ``mask`` / ``noise`` are not read.  Returns dict(action, neglogp);
+        ``out`` may hold preallocated outputs."""
+        import ctypes as C
+        t = self._t
+        x, _ = self._obs(obs)
+        n, A, H = x.shape[0], self.ac_dim, self.hidden
+        out = out or {}
+        action, neglogp = out.get("action"), out.get("neglogp")
+        if action is None:
+            action = t.empty((n, A), dtype=t.float32, device=self.device)
+        if neglogp is None:
+            neglogp = t.empty(n, dtype=t.float32, device=self.device)
+        given = None
+        if given_action is not None:
+            given = given_action if t.is_tensor(given_action) else t.from_numpy(np.ascontiguousarray(given_action, np.float32))
+            given = given.to(self.device, t.float32).reshape(n, A).contiguous()
+            # a fresh zero state per call, allocated on the current stream: the kernel writes its new state there, and the env
+            # groups of a Runner score on streams of their own (one cached buffer would be shared between them)
+            zero = t.zeros((n, 2 * H), dtype=t.float32, device=self.device)
+            cptr, hptr, stride, mask, noise = zero.data_ptr(), zero.data_ptr() + 4 * H, 2 * H, None, None
+        else:
+            if state is None:
+                st = self._own_state(n)
+                cptr, hptr, stride = st[2].data_ptr(), st[3].data_ptr(), H
+            else:
+                if tuple(state.shape) != (n, 2 * H) or state.dtype != t.float32 or not state.is_cuda or not state.is_contiguous():
+                    raise ValueError("state must be a contiguous float32 CUDA tensor of shape (%d, %d)" % (n, 2 * H))
+                cptr, hptr, stride = state.data_ptr(), state.data_ptr() + 4 * H, 2 * H
+            mask = self._mask(mask, n)
+            if deterministic:
+                noise = None
+            elif noise is None:
+                noise = t.randn((n, A), generator=self.gen, device=self.device, dtype=t.float32)
+            elif tuple(noise.shape) != (n, A) or noise.dtype != t.float32 or not noise.is_cuda or not noise.is_contiguous():
+                raise ValueError("noise must be a contiguous float32 CUDA tensor of shape (%d, %d)" % (n, A))
+        ppo_capi.chk(ppo_capi.lib().ppo_lstm_step(C.byref(self._nets["p"]), x.data_ptr(), n, x.stride(0) if n > 1 else x.shape[1],
+                                                  ppo_capi.ptr(mask), cptr, hptr, stride, ppo_capi.ptr(noise), ppo_capi.ptr(given),
+                                                  action.data_ptr(), neglogp.data_ptr(), None, None,
+                                                  t.cuda.current_stream(self.device).cuda_stream))
+        return dict(action=action, neglogp=neglogp)
+
+    def step(self, observation, S=None, M=None, deterministic=False, noise=None, **extra_feed):
+        """(action, None, S, neglogp): the net acts on ``observation`` from the state ``S`` (None: its own) masked by ``M``.  The value
+        slot is None -- fix mode values agent 1 with the learner, and the value branch is a second cell (:meth:`value`)."""
+        x, np_in = self._obs(observation)
+        r = self.evaluate(x, state=S, mask=M, deterministic=deterministic, noise=noise)
+        ret = (lambda z: z.cpu().numpy()) if np_in else (lambda z: z)
+        return ret(r["action"]), None, S, ret(r["neglogp"])
+
+    def value(self, ob, S=None, M=None, **kwargs):
+        """The value branch on the policy's own value state (masked by ``M``, advanced), de-normalised with the return filter, as
+        ``act(want_value=True)`` computes it.  Kept for the model interface: fix mode never reads it."""
+        import ctypes as C
+        t = self._t
+        x, np_in = self._obs(ob)
+        n, H = x.shape[0], self.hidden
+        st = self._own_state(n)
+        value = t.empty(n, dtype=t.float32, device=self.device)
+        ppo_capi.chk(ppo_capi.lib().ppo_lstm_step(C.byref(self._nets["v"]), x.data_ptr(), n, x.stride(0) if n > 1 else x.shape[1],
+                                                  ppo_capi.ptr(self._mask(M, n)), st[0].data_ptr(), st[1].data_ptr(), H, None, None, None,
+                                                  None, value.data_ptr(), None, t.cuda.current_stream(self.device).cuda_stream))
+        value = value * self.ret_std + self.ret_mean
+        return value.cpu().numpy() if np_in else value
+
+    def action_probability(self, observation, given_action=None, **extra_feed):
+        """-log pi(given_action | observation) from a zero state (the Runner's scoring calls feed no state)."""
+        x, np_in = self._obs(observation)
+        nlp = self.evaluate(x, given_action=given_action)["neglogp"]
+        return nlp.cpu().numpy() if np_in else nlp
+
+
 def load_zoo_policy(path, ac_dim, device=0, kind=None):
     """utils.py:66-67 ``load_params`` + policy construction; ``kind`` 'mlp' / 'lstm' (default: whichever layout fits the
     vector length)."""
@@ -503,7 +612,7 @@ def load_zoo_policy_from_flat(flat, ac_dim, device=0, kind=None):
 
 class FixedOpponentModel(object):
     """What alg_ppo.py:194-206 puts into ``runner.models[1]`` in ``opponent_mode='fix'``: a non-trainable model whose
-    ``step`` / ``value`` / ``act_model.action_probability`` come from the zoo net."""
+    ``step`` / ``value`` / ``act_model.action_probability`` come from the zoo net (either family)."""
 
     trainable = False
 

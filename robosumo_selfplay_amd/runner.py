@@ -101,12 +101,14 @@ class Runner(AbstractEnvRunner):
         self.fused_rollout = os.environ.get("SUMO_FUSED_ROLLOUT", "1") != "0"
         self.rollout_chunk = int(os.environ.get("SUMO_ROLLOUT_CHUNK", "0"))   # steps per launch (0 = the whole rollout)
         self.opponent_pool = None     # opponent_pool.OpponentPool: frozen snapshots + per-env snapshot index (fused path)
-        # opt-in (learn(fused_fix_opponent=True)): a policy-zoo MLP opponent (opponent_mode='fix') plays inside the fused launch
-        # (sumo_rollout_steps_zoo).  The action noise is then drawn per group and generator for the whole buffer, as the MLP
-        # self-play path draws it -- another, equally valid stream than the per-step draws of the default fix-mode path; with
-        # SUMO_FUSED_ROLLOUT=0 the step-by-step launches play that same stream (bit-identical rollouts).
+        # opt-in (learn(fused_fix_opponent=True)): a policy-zoo opponent (opponent_mode='fix') plays inside the fused launch
+        # (sumo_rollout_steps_zoo for an MLP net, sumo_rollout_steps_zoo_lstm for an LSTM net).  The action noise is then drawn per
+        # group and generator for the whole buffer, as the MLP self-play path draws it -- another, equally valid stream than the
+        # per-step draws of the default fix-mode path; with SUMO_FUSED_ROLLOUT=0 the step-by-step launches play that same stream
+        # (bit-identical rollouts).
         self.fused_fix_opponent = False
         self._zoo_table = None
+        self.zoo_state = None         # device mode: agent 1's recurrent state [nenv][128] (c | h) when a zoo LSTM net plays it
         self.recurrent = all(getattr(m, "recurrent", False) for m in models)
         self.device_mode = hasattr(env, "step_device") and (self.recurrent or all(
             hasattr(m, "act_model") and hasattr(m.act_model, "evaluate") for m in models))
@@ -124,6 +126,9 @@ class Runner(AbstractEnvRunner):
             self.dones = torch.zeros((self.nenv, 2), dtype=torch.uint8, device=self.device)
             if self.recurrent:                                          # recurrent states live on the device as well
                 self.states = [torch.as_tensor(np.asarray(st, np.float32)).to(self.device) for st in self.states]
+            # a zoo LSTM opponent (installed after construction, opponent_mode='fix') acts from these rows on either path; they
+            # persist across run() calls and across the K-step launches of one rollout
+            self.zoo_state = torch.zeros((self.nenv, 128), dtype=torch.float32, device=self.device)
         else:
             self.obs = np.zeros((self.nenv, len(env.observation_space)) + ob_shape,
                                 dtype=models[0].train_model.X.dtype.name)
@@ -309,27 +314,30 @@ class Runner(AbstractEnvRunner):
         self._fused_groups(B, s0, K, alpha, capi.Rollout, draw, fill, self.env.rollout_steps_group)
 
     def zoo_opponent(self):
-        """The ``ZooMLPPolicy`` behind ``models[1]`` when the run opted into the fused fix-mode rollout (``fused_fix_opponent``)
-        and the launch applies -- device mode, a plain MLP learner of the env's shape, a zoo MLP net (zoo LSTM nets stay on the
-        step-by-step path), cfrc_mode 'zero' -- else None."""
+        """The ``ZooMLPPolicy`` or ``ZooLSTMPolicy`` behind ``models[1]`` when the run opted into the fused fix-mode rollout
+        (``fused_fix_opponent``) and the launch applies -- device mode, a plain MLP learner of the env's shape, a zoo net of either
+        family (an LSTM net: embedding and cell of 64), cfrc_mode 'zero', no opponent pool -- else None."""
         env = self.env
         if not (self.fused_fix_opponent and self.device_mode and not self.recurrent and hasattr(env, "rollout_steps_zoo_group")):
             return None
         from .policies import PolicyWithValue
-        from .policy_zoo import FixedOpponentModel, ZooMLPPolicy
+        from .policy_zoo import FixedOpponentModel, ZooLSTMPolicy, ZooMLPPolicy
         if getattr(env, "cfrc_mode", "zero") != "zero" or self.opponent_pool is not None:
             return None
         m0, m1 = self.models[0], self.models[1]
-        if not isinstance(m1, FixedOpponentModel) or type(m1.act_model) is not ZooMLPPolicy or not hasattr(m0, "act_model"):
+        if not isinstance(m1, FixedOpponentModel) or type(m1.act_model) not in (ZooMLPPolicy, ZooLSTMPolicy) or not hasattr(m0, "act_model"):
             return None
         learner, zoo = m0.act_model, m1.act_model
+        if type(zoo) is ZooLSTMPolicy and not (zoo.emb == zoo.hidden == 64 and hasattr(env, "rollout_steps_zoo_lstm_group")):
+            return None
         if not (type(learner) is PolicyWithValue and learner.spec.ob_dim == self.ob_dim and zoo.ob_dim <= self.ob_dim
                 and learner.spec.ac_dim == zoo.ac_dim == env.act_dev.shape[2] and env.obs_dev.stride(2) == 1):
             return None
         return zoo
 
     def fused_zoo_ok(self):
-        """The fused launch against a policy-zoo MLP net (``sumo_rollout_steps_zoo``) applies: see :meth:`zoo_opponent`."""
+        """The fused launch against a policy-zoo net (``sumo_rollout_steps_zoo`` / ``sumo_rollout_steps_zoo_lstm``) applies: see
+        :meth:`zoo_opponent`."""
         return self.fused_rollout and self.zoo_opponent() is not None
 
     def _draw_zoo(self, B, n, learner, zoo):
@@ -359,6 +367,38 @@ class Runner(AbstractEnvRunner):
 
         self._fused_groups(B, s0, K, alpha, capi.Rollout, lambda n: self._draw_zoo(B, n, learner, zoo), fill,
                            lambda g, ro: self.env.rollout_steps_zoo_group(g, ro, zs))
+
+    def _steps_fused_zoo_lstm(self, B, s0, K, alpha):
+        """``_steps_fused_zoo`` against a policy-zoo LSTM net: one ``sumo_rollout_steps_zoo_lstm`` launch per env group.  The net
+        sits in a one-row :class:`policy_zoo.ZooLstmTable`; agent 1's state rows ``self.zoo_state`` are advanced in place.  Same
+        numbers as the step-by-step launches under the opt-in (``_zoo_lstm_evals`` with the same noise rows), bit for bit."""
+        from . import capi
+        from .policy_zoo import ZooLstmTable
+        learner, zoo = self.models[0].act_model, self.zoo_opponent()
+        if self._zoo_table is None or self._zoo_table[0] is not zoo:
+            self._zoo_table = (zoo, ZooLstmTable([zoo], zoo.ac_dim, self.device))
+        table = self._zoo_table[1]
+        D, A = learner.spec.ob_dim, learner.spec.ac_dim
+
+        def fill(ro, sl):
+            ro.learner_params = learner.params.data_ptr()
+            ro.opponent_params, ro.opponent_index, ro.npool = None, None, table.capacity
+            ro.ob_dim, ro.ac_dim = D, A
+
+        self._fused_groups(B, s0, K, alpha, capi.Rollout, lambda n: self._draw_zoo(B, n, learner, zoo), fill,
+                           lambda g, ro: self.env.rollout_steps_zoo_lstm_group(g, ro, table.struct(self.zoo_state[self.env._gs(g)])))
+
+    def _zoo_lstm_evals(self, B, s, learner, zoo, o0, o1, dn, sl, nk0=None, nk1=None):
+        """The step's evaluations against a zoo LSTM net, step by step: the learner acts on agent 0 and the zoo net scores that
+        action from a zero state; the zoo net acts on agent 1 from its rows of ``self.zoo_state`` (masked by agent 1's done flags
+        of the previous step, advanced in place) and the learner scores and values that action.  ``nk0`` / ``nk1`` as in
+        ``_policy_evals``."""
+        PI, VF = ppo_capi.FWD_PI, ppo_capi.FWD_VF
+        act0, act1 = B["act"][0, s, sl], B["act"][1, s, sl]
+        learner.evaluate(o0, PI | VF, out=dict(action=act0, neglogp=B["nlp"][0, s, sl], value=B["val"][0, s, sl]), **(nk0 or {}))
+        zoo.evaluate(o0, given_action=act0, out=dict(neglogp=B["onlp"][0, s, sl], action=B["scratch_a"][sl]))
+        zoo.evaluate(o1, state=self.zoo_state[sl], mask=dn[:, 1], out=dict(action=act1, neglogp=B["onlp"][1, s, sl]), **(nk1 or {}))
+        learner.evaluate(o1, PI | VF, given_action=act1, out=dict(neglogp=B["nlp"][1, s, sl], value=B["val"][1, s, sl], action=B["scratch_b"][sl]))
 
     def join_groups(self):
         """Make the current stream wait for every env group's stream (no-op without groups)."""
@@ -406,11 +446,17 @@ class Runner(AbstractEnvRunner):
             B["val"][1, s, sl].copy_(m0.value(o1, S=S1, M=dn[:, 1]))
             B["nlp"][1, s, sl].copy_(m0.act_model.action_probability(o1, given_action=a1))
         elif self.zoo_opponent() is not None:
-            # opt-in fix mode, step by step: the noise rows the fused launch (``_steps_fused_zoo``) would read
+            # opt-in fix mode, step by step: the noise rows the fused launch (``_steps_fused_zoo`` / ``_steps_fused_zoo_lstm``) would read
             key = ("noise", sl.start)
             if s == 0 or key not in B:
                 B[key] = self._draw_zoo(B, n, learner, opp)
-            self._policy_evals(B, s, learner, opp, o0, o1, sl, g, dict(noise=B[key][0][s]), dict(noise=B[key][1][s]))
+            if getattr(opp, "recurrent", False):
+                self._zoo_lstm_evals(B, s, learner, opp, o0, o1, dn, sl, dict(noise=B[key][0][s]), dict(noise=B[key][1][s]))
+            else:
+                self._policy_evals(B, s, learner, opp, o0, o1, sl, g, dict(noise=B[key][0][s]), dict(noise=B[key][1][s]))
+        elif getattr(opp, "recurrent", False):
+            # fix mode against a zoo LSTM net without the opt-in: each net draws its noise per step from its own generator
+            self._zoo_lstm_evals(B, s, learner, opp, o0, o1, dn, sl)
         else:
             self._policy_evals(B, s, learner, opp, o0, o1, sl, g)
         act = env.act_dev
@@ -507,7 +553,11 @@ class Runner(AbstractEnvRunner):
                 st.wait_stream(cur)
         fused = self.fused_ok() or self.fused_lstm_ok() or self.fused_zoo_ok()
         if fused:
-            steps = self._steps_fused_lstm if self.recurrent else self._steps_fused_zoo if self.fused_zoo_ok() else self._steps_fused
+            steps = self._steps_fused
+            if self.recurrent:
+                steps = self._steps_fused_lstm
+            elif self.fused_zoo_ok():
+                steps = self._steps_fused_zoo_lstm if getattr(self.zoo_opponent(), "recurrent", False) else self._steps_fused_zoo
             chunk = self.rollout_chunk if self.rollout_chunk > 0 else T
             for s0 in range(0, T, chunk):
                 steps(B, s0, min(chunk, T - s0), alpha)

@@ -45,8 +45,8 @@ def main(argv):
     ap.add_argument("--adjust_z", type=float, default=0.0, help="Agent._adjust_z (agents.py:33): offset of the torso height the agents report "
                     "(observations, lose test).  0 = the reference's training setting (its run.py:76-77 leaves the -0.5 commented out); its "
                     "evaluation / play scripts use -0.5, which is what the policy-zoo nets expect")
-    ap.add_argument("--fused_fix_opponent", action="store_true", help="opponent_mode=fix: play the policy-zoo MLP net inside the fused "
-                    "rollout launch (sumo_rollout_steps_zoo).  Opt-in: the action noise is drawn per rollout buffer instead of per step, "
+    ap.add_argument("--fused_fix_opponent", action="store_true", help="opponent_mode=fix: play the policy-zoo net (MLP or LSTM file) inside the fused "
+                    "rollout launch (sumo_rollout_steps_zoo / sumo_rollout_steps_zoo_lstm).  Opt-in: the action noise is drawn per rollout buffer instead of per step, "
                     "so the same seed gives another, equally valid random stream")
     args, unknown = ap.parse_known_args(argv)
     extra = parse_unknown(unknown)

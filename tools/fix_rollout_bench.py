@@ -1,0 +1,100 @@
+#!/usr/bin/env python3
+"""Throughput of the rollout launches of learn(opponent_mode='fix') against a policy-zoo net, next to plain self-play: K rollout steps
+per launch through the Runner's own drivers (noise draws included), the fused launch against the step-by-step launches.
+
+    python tools/fix_rollout_bench.py --opponent zoo_lstm   # sumo_rollout_steps_zoo_lstm against ppo_forward + ppo_lstm_step per step
+    python tools/fix_rollout_bench.py --opponent zoo        # sumo_rollout_steps_zoo against ppo_forward + ppo_forward_filtered
+    python tools/fix_rollout_bench.py --opponent self       # sumo_rollout_steps (MLP self-play) against ppo_selfplay_forward
+
+Every repeat times `launches` windows of K steps on each path, fused and step by step interleaved, after `warmup` windows; the envs
+keep running from window to window.  Prints one JSON line: env-steps/s per repeat and the median of both paths."""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main(argv):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--env", default="RoboSumo-Ant-vs-Ant-v0")
+    ap.add_argument("--num_env", type=int, default=4096)
+    ap.add_argument("--K", type=int, default=20, help="rollout steps per launch (the rollout buffer's length)")
+    ap.add_argument("--launches", type=int, default=10, help="timed K-step windows per repeat and path")
+    ap.add_argument("--warmup", type=int, default=5, help="untimed K-step windows per path")
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--opponent", choices=("self", "zoo", "zoo_lstm"), default="zoo_lstm")
+    ap.add_argument("--skip_stepwise", action="store_true")
+    args = ap.parse_args(argv)
+    import numpy as np
+    import torch
+    from tools.match_bench import _zoo_flat, _zoo_lstm_flat
+    from robosumo_selfplay_amd import policies, policy_zoo
+    from robosumo_selfplay_amd.model import PPOModel
+    from robosumo_selfplay_amd.runner import Runner
+    from robosumo_selfplay_amd.vec_env import SumoVecEnv
+
+    def runner():
+        env = SumoVecEnv(args.env, num_envs=args.num_env, seed=3)
+        D, A = env.observation_space[0].shape[0], env.action_space[0].shape[0]
+        spec = policies.PolicySpec(D, A, value_network="copy", activation="relu")
+        models = [PPOModel(policy=spec, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, trainable=False) for _ in range(2)]
+        rng = np.random.default_rng(1)
+        if args.opponent == "zoo":
+            models[1] = policy_zoo.FixedOpponentModel(policy_zoo.ZooMLPPolicy(_zoo_flat(policy_zoo, D - 1, A, rng), A))
+        elif args.opponent == "zoo_lstm":
+            models[1] = policy_zoo.FixedOpponentModel(policy_zoo.ZooLSTMPolicy(_zoo_lstm_flat(policy_zoo, D - 1, A, rng), A))
+        for k, m in enumerate(models):
+            m.act_model.seed(100 + k)
+        r = Runner(env=env, models=models, nsteps=args.K, nagent=2, gamma=0.995, lam=0.95, rho_bar=1.0, c_bar=1.0)
+        r.fused_fix_opponent = True
+        return r
+
+    def window(r, B, fused):
+        if fused:
+            steps = r._steps_fused
+            if r.fused_zoo_ok():
+                steps = r._steps_fused_zoo_lstm if args.opponent == "zoo_lstm" else r._steps_fused_zoo
+            steps(B, 0, args.K, 0.5)
+        else:
+            for s in range(args.K):
+                r._step_device(B, s, 0.5)
+
+    paths = [True] if args.skip_stepwise else [True, False]
+    rs = {f: runner() for f in paths}
+    for f, r in rs.items():
+        r.fused_rollout = f
+        assert (r.fused_ok() or r.fused_zoo_ok()) == f, "the fused launch does not apply"
+    Bs = {f: r._alloc_device(args.K) for f, r in rs.items()}
+    rates = {f: [] for f in paths}
+    for rep in range(args.repeats + 1):                      # repeat 0 is the warm-up
+        for f in paths:
+            n = args.warmup if rep == 0 else args.launches
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(n):
+                window(rs[f], Bs[f], f)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            if rep:
+                rates[f].append(args.num_env * args.K * n / dt)
+    for f, r in rs.items():
+        if f:
+            for E in r.env.engines:
+                E.rollout_status()
+        assert r.env.stats()["rollout_aborts"] == 0
+    out = dict(opponent=args.opponent, env=args.env, num_env=args.num_env, K=args.K, launches=args.launches, repeats=args.repeats)
+    for f in paths:
+        name = "fused" if f else "stepwise"
+        out[name + "_env_steps_per_s"] = [round(x) for x in rates[f]]
+        out[name + "_median"] = round(float(np.median(rates[f])))
+    print(json.dumps(out))
+    for r in rs.values():
+        r.env.close()
+    return out
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

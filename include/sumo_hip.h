@@ -248,6 +248,38 @@ int sumo_match_steps_lstm_zoo_lstm(sumo_handle_t h, const sumo_match_lstm* m, co
  *   (sumo_rollout_status returns -20) and plays row 0. */
 int sumo_rollout_steps_zoo_lstm(sumo_handle_t h, const sumo_rollout* r, const sumo_zoo_lstm* z, float* actions_dev, float* obs_dev,
                                 double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream);
+/* The rollout launches of a RECURRENT learner against policy-zoo nets (learn(network='lstm', opponent_mode='fix')): the launch
+ * struct of sumo_rollout_steps_lstm with agent 1 played by a zoo net of the table z.  Per step and env the owning wave evaluates
+ *   learner(obs 0, state0)    -> action 0 (mean + exp(logstd) * noise0) / neglogp / value / new state0; the state row is zeroed
+ *                                first where AGENT 0's done flag of the previous step is set
+ *   zoo net on obs 0          -> its likelihood of action 0 (onlp[0]); an LSTM net: one cell evaluation from a ZERO state, no state
+ *                                written
+ *   zoo net on obs 1          -> action 1 (mean + exp(logstd) * noise1) and its neglogp (onlp[1]); an LSTM net acts from the env's
+ *                                row of z->state, zeroed first where AGENT 1's done flag of the previous step is set, and leaves
+ *                                the new state there
+ *   learner(obs 1, ZERO state) -> its likelihood (nlp[1]) AND the value (val[1]) of action 1, ONE cell evaluation: a zoo net's
+ *                                state is not the learner's, so the rule of sumo_rollout_steps_lstm (value from agent 1's new
+ *                                state) has nothing to feed
+ * The record holds the raw observations.  Every recorded number equals the ppo_lstm_step (learner, zoo LSTM net) /
+ * ppo_forward_filtered (zoo MLP net) launches of the step-by-step path bit for bit.
+ *   r->learner, r->state0   as sumo_rollout_steps_lstm (hidden 128, gate order i,f,o,u; [E][256] rows of THIS engine's envs)
+ *   r->opponents_dev, r->state1   must be NULL; r->npool == z->nzoo
+ *   r->tile_net_dev   DEVICE int32 [Ntot / 16]: the table row every 16-env tile of the WHOLE env set faces, exactly as it selects
+ *                     the snapshot in sumo_rollout_steps_lstm (NULL = row 0); a row outside [0, nzoo) raises the launch's abort flag
+ *                     (sumo_rollout_status returns -20) and row 0 plays
+ *   z                 sumo_rollout_steps_lstm_zoo: a sumo_zoo_mlp table; sumo_rollout_steps_lstm_zoo_lstm: a sumo_zoo_lstm table
+ *                     whose state ([E][2 * 64], rows of this engine's envs) is read at step s0 and left at the state after step
+ *                     s0 + K - 1
+ * Refused before any launch: whatever sumo_rollout_steps_lstm refuses (cfrc_mode rne_post, mixed match-ups, a learner of another
+ * shape, missing buffers, a scene whose per-step LDS area cannot hold the policy scratch, ...), opponents_dev / state1 given,
+ * npool != nzoo, and whatever sumo_rollout_steps_zoo / sumo_rollout_steps_zoo_lstm refuse of the table (ob_dim outside [1, the
+ * scene's ob_dim], nzoo < 1, missing params / filt / state, obs_clip <= 0, emb_dim / hidden other than 64, cell rows that do not
+ * fit the policy scratch).  Ordering contract as sumo_rollout_steps. */
+int sumo_rollout_steps_lstm_zoo(sumo_handle_t h, const sumo_rollout_lstm* r, const sumo_zoo_mlp* z, float* actions_dev, float* obs_dev,
+                                double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream);
+int sumo_rollout_steps_lstm_zoo_lstm(sumo_handle_t h, const sumo_rollout_lstm* r, const sumo_zoo_lstm* z, float* actions_dev, float* obs_dev,
+                                     double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev,
+                                     void* stream);
 /* cfrc_mode (reference agents.py:190-214 reads sim.data.cfrc_ext into 84 of the 121 observation entries):
  *   0 = zero (default): what the reference produces -- its MuJoCo 2.1 scenes declare no force / torque / accelerometer sensor, so
  *       mj_rnePostConstraint never runs and cfrc_ext stays at its reset value 0;

@@ -85,6 +85,8 @@ def lib():
         L.sumo_match_steps_zoo_lstm.argtypes = [vp, C.POINTER(Match), C.POINTER(ZooLstm)] + [vp] * 8
         L.sumo_match_steps_lstm_zoo_lstm.argtypes = [vp, C.POINTER(MatchLstm), C.POINTER(ZooLstm)] + [vp] * 8
         L.sumo_rollout_steps_zoo_lstm.argtypes = [vp, C.POINTER(Rollout), C.POINTER(ZooLstm)] + [vp] * 8
+        L.sumo_rollout_steps_lstm_zoo.argtypes = [vp, C.POINTER(RolloutLstm), C.POINTER(ZooMlp)] + [vp] * 8
+        L.sumo_rollout_steps_lstm_zoo_lstm.argtypes = [vp, C.POINTER(RolloutLstm), C.POINTER(ZooLstm)] + [vp] * 8
         L.sumo_get_state.argtypes = [vp] * 5
         L.sumo_set_cfrc_mode.argtypes = [vp, i32]
         L.sumo_get_cfrc_ext.argtypes = [vp, vp]
@@ -103,14 +105,14 @@ def lib():
         L.sumo_static_layout.restype = i32
         L.sumo_profile.restype = i32
         for n in ("sumo_create", "sumo_destroy", "sumo_dims", "sumo_reset", "sumo_step", "sumo_rollout_steps", "sumo_rollout_steps_lstm", "sumo_match_steps", "sumo_match_steps_lstm",
-                  "sumo_rollout_steps_zoo", "sumo_match_steps_zoo", "sumo_match_steps_zoo_lstm", "sumo_match_steps_lstm_zoo_lstm", "sumo_rollout_steps_zoo_lstm", "sumo_get_state", "sumo_set_cfrc_mode", "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_set_state", "sumo_debug_forward", "sumo_stats"):
+                  "sumo_rollout_steps_zoo", "sumo_match_steps_zoo", "sumo_match_steps_zoo_lstm", "sumo_match_steps_lstm_zoo_lstm", "sumo_rollout_steps_zoo_lstm", "sumo_rollout_steps_lstm_zoo", "sumo_rollout_steps_lstm_zoo_lstm", "sumo_get_state", "sumo_set_cfrc_mode", "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_set_state", "sumo_debug_forward", "sumo_stats"):
             getattr(L, n).restype = i32
         _LIB = L
     return _LIB
 
 
 EXPORTS = ("sumo_last_error", "sumo_create", "sumo_destroy", "sumo_dims", "sumo_reset", "sumo_step", "sumo_rollout_steps",
-           "sumo_rollout_steps_lstm", "sumo_match_steps", "sumo_match_steps_lstm", "sumo_rollout_steps_zoo", "sumo_match_steps_zoo", "sumo_match_steps_zoo_lstm", "sumo_match_steps_lstm_zoo_lstm", "sumo_rollout_steps_zoo_lstm", "sumo_set_cfrc_mode", "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_get_state", "sumo_set_state", "sumo_debug_forward", "sumo_stats", "sumo_profile", "sumo_debug_trace",
+           "sumo_rollout_steps_lstm", "sumo_match_steps", "sumo_match_steps_lstm", "sumo_rollout_steps_zoo", "sumo_match_steps_zoo", "sumo_match_steps_zoo_lstm", "sumo_match_steps_lstm_zoo_lstm", "sumo_rollout_steps_zoo_lstm", "sumo_rollout_steps_lstm_zoo", "sumo_rollout_steps_lstm_zoo_lstm", "sumo_set_cfrc_mode", "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_get_state", "sumo_set_state", "sumo_debug_forward", "sumo_stats", "sumo_profile", "sumo_debug_trace",
            "sumo_rollout_status", "sumo_debug_fault", "sumo_static_layout", "sumo_debug_layout", "sumo_debug_model_ints", "sumo_debug_dump")
 
 
@@ -208,6 +210,17 @@ class Engine:
         (``opponent_params`` None, ``npool`` = ``zoo.nzoo``), ``zoo`` a filled :class:`ZooLstm` (``state``: agent 1's rows of the
         launch's envs, read and updated in place)."""
         self._fused("sumo_rollout_steps_zoo_lstm", ro, env_ptrs, stream, zoo)
+
+    def rollout_steps_lstm_zoo(self, ro, zoo, *env_ptrs, stream=None):
+        """K fused rollout steps of a recurrent learner against policy-zoo MLP nets (``sumo_rollout_steps_lstm_zoo``); ``ro`` is a
+        filled :class:`RolloutLstm` (``opponents_dev`` / ``state1`` None, ``npool`` = ``zoo.nzoo``, ``tile_net_dev`` the table row
+        per 16-env tile or None), ``zoo`` a filled :class:`ZooMlp`."""
+        self._fused("sumo_rollout_steps_lstm_zoo", ro, env_ptrs, stream, zoo)
+
+    def rollout_steps_lstm_zoo_lstm(self, ro, zoo, *env_ptrs, stream=None):
+        """The same against policy-zoo LSTM nets (``sumo_rollout_steps_lstm_zoo_lstm``); ``zoo`` a filled :class:`ZooLstm`
+        (``state``: agent 1's rows of the launch's envs, read and updated in place)."""
+        self._fused("sumo_rollout_steps_lstm_zoo_lstm", ro, env_ptrs, stream, zoo)
 
     def set_cfrc_mode(self, mode):
         """'zero' (default, the reference's behaviour) or 'rne_post' (include/sumo_hip.h: cfrc_mode)."""

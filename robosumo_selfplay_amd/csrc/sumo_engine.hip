@@ -2558,6 +2558,19 @@ struct ZooLstmArgs {
                                      // nets (their D is a launch field too).  The loop is shared with modes 1 and 3, whose
                                      // code objects must not change, so it carries no unroll pragma of its own.
 };
+// Policy-zoo opponents of a RECURRENT learner (sumo_rollout_steps_lstm_zoo / sumo_rollout_steps_lstm_zoo_lstm, POLICY 9 / 10).  The
+// learner's net fills RolloutArgs::lnet and the launch writes the rollout record, so neither overlay above is free: these fields
+// overlay the match fields at the end of RolloutArgs, which a rollout never reads.  The table's parameter rows [nzoo][Pz] travel in
+// RolloutArgs::opponent (as in mode 4); a zoo MLP table's layout make_layout(Dz, A) in RolloutArgs::L, which the recurrent learner
+// does not read (Pz == L.P then); a zoo LSTM table's state rows in RolloutArgs::st1.  forget_bias, A, sc_off and emb are read by
+// mode 10 only, with the meaning they have in ZooLstmArgs.
+struct ZooTailArgs {
+  const float* filt;                 // [nzoo][2][Dz]: mean | 1 / std
+  float clip, forget_bias;
+  int nzoo, Dz, A, Pz;
+  int sc_off;
+  int emb;
+};
 struct RolloutArgs {
   const float *learner, *opponent;   // flat parameter vectors; opponent: [npool][P]
   const int32_t* opp_idx;            // [N] snapshot per env or NULL
@@ -2591,10 +2604,17 @@ struct RolloutArgs {
   // counted while their sum is below quota.  An env's counters cross waves between its tickets like its record: lane 0 of the
   // owning wave reads them with hand_load<true> and writes them with hand_store<true> before the s_waitcnt vmcnt(0) that precedes
   // the progress store, so the next owner (which polls prog[e] first) sees them.
-  const float* snaps;
-  const int32_t *idx0, *idx1;
-  int* score;
-  int nsnap, quota;
+  // (the rollouts of a recurrent learner against policy-zoo nets, POLICY 9 / 10, play no match: their zoo fields overlay these,
+  // so the struct keeps its size and offsets; static_assert below RolloutLaunch)
+  union {
+    struct {
+      const float* snaps;
+      const int32_t *idx0, *idx1;
+      int* score;
+      int nsnap, quota;
+    };
+    ZooTailArgs zt;
+  };
 };
 
 // ---- pieces shared by the four policy phases (each reads a / r through the references its phase received) ----
@@ -3240,6 +3260,106 @@ __device__ __forceinline__ void rollout_policy_phase_zoo_lstm(C& c, const SA& a,
   wave_sync();   // the action buffer is read back by the env step (other lanes), the scratch region becomes the mass matrix again
 }
 
+// ---- rollout of a recurrent learner against policy-zoo nets (POLICY 9 / 10) ----
+// learn(network='lstm', opponent_mode='fix') inside the launch (sumo_rollout_steps_lstm_zoo: ZLSTM false, a zoo MLP net;
+// sumo_rollout_steps_lstm_zoo_lstm: ZLSTM true, a zoo LSTM net).  Four evaluations per step, the learner's two in one pass over its
+// weights:
+//   learner: row C = (obs 0, agent 0's state)  -> action 0, neglogp, value, agent 0's new state   (row C of rollout_policy_phase_lstm)
+//            row E = (obs 1, zero state)       -> the learner's likelihood AND value of action 1  (its row E; there is no row D: a
+//                                                 zoo net's state is not the learner's, so the zero-state evaluation also values)
+//   zoo net: on obs 0 scores action 0 (LSTM: from a zero state, nothing written); on obs 1 acts (LSTM: from its row of st1, masked by
+//            AGENT 1's done flag of the previous step and advanced in place), as modes 4 / 8.
+// The learner reads the raw tile first (it is in the record by then); only then the zoo net filters the rows in place, its hidden
+// tiles (MLP: [2][PT_HS] twice) or cell rows (LSTM: zt.sc_off, three rows of 64) in the place of the learner's latent rows.  The
+// zoo row comes from tile_net per 16-env tile of the whole env set, as the snapshot of mode 1.  Every number equals the
+// ppo_lstm_step (learner, zoo LSTM net) / ppo_forward_filtered (zoo MLP net) launches of the step-by-step path bit for bit.
+// LDS (floats, from lds_off): x [2][XS] | zero row [NH] | agent 0's previous latent [NH] | new latents [2][NH].
+template <int NH, bool ZLSTM, class C, class SA, class RA>
+__device__ __forceinline__ void rollout_policy_phase_lstm_zoo(C& c, const SA& a, const RA& r, int e, int s) {
+  const int lane = c.lane;
+  const auto& NL = r.lnet;
+  const auto& q = r.zt;
+  const int D = NL.ob_dim, A = NL.ac_dim, XS = r.XS;
+  float* xo = (float*)(c.sm + r.lds_off);
+  float* hz = xo + 2 * XS;
+  float* hp = hz + NH;
+  float* hn = hp + NH;
+  const size_t col = (size_t)r.env_offset + e;
+  const size_t slot0 = ((size_t)0 * r.T + s) * r.Ntot + col, slot1 = ((size_t)1 * r.T + s) * r.Ntot + col;
+  policy_load_obs<true, true>(a, r, e, lane, xo, D, XS, slot0, slot1);
+  const unsigned dn = policy_prev_done(a, e);
+  if (lane < 2) policy_record_done(r, lane, slot0, slot1, dn);
+  const float keep0 = 1.0f - (float)(dn & 0xff);
+  float* s0p = r.st0 + (size_t)e * 2 * NH;
+  const int j0 = 2 * lane;                           // lane owns the units 2 lane, 2 lane + 1
+  float c0[2];
+  lstm_state_pair(s0p + j0, keep0, c0);
+  lstm_state_pair(s0p + NH + j0, keep0, hp + j0);
+  hz[j0] = 0.0f; hz[j0 + 1] = 0.0f;
+  wave_sync();
+  const int jz = policy_checked_row(a, lane, r.tile_net ? pt_global(r.tile_net)[col >> 4] : 0, q.nzoo);
+  const bool ok = lane < A;
+  const size_t nz = policy_noise_index(a, e, s, A, lane);
+  float act0 = 0.0f, act1 = 0.0f;
+  float nlp0, mL1, stdL, sumL, v0, v1;
+  {  // ---- learner net: rows C, E
+    const float fb = NL.forget_bias;
+    float z[4][2][2], bz[4][2];
+    lstm_bias_pair<NH>(pt_global(NL.b), j0, bz);   // (in flight during the gate sums)
+    const float* const xr[2] = {xo, xo + XS};
+    const float* const hr[2] = {hp, hz};
+    lstm_gates_valu<NH, 2>(NL.wx, NL.wh, D, xr, hr, lane, z);
+#pragma unroll
+    for (int u = 0; u < 2; u++) {
+      const int j = j0 + u;
+      const float bi = bz[0][u], bf = bz[1][u] + fb, bo = bz[2][u], bu = bz[3][u];   // gate order i, f, o, u
+      const LstmCell cc = lstm_cell(z[0][u][0], z[1][u][0], z[2][u][0], z[3][u][0], bi, bf, bo, bu, c0[u]);
+      const LstmCell ce = lstm_cell(z[0][u][1], z[1][u][1], z[2][u][1], z[3][u][1], bi, bf, bo, bu, hz[j]);
+      lstm_state_store<NH>(s0p, j, cc);                                              // agent 0's state after the learner's step
+      hn[j] = cc.hn; hn[NH + j] = ce.hn;
+    }
+    wave_sync();
+    float m[2];
+    lstm_heads_valu<NH, 2>(NL.head_w, NL.vf_w, A, hn, lane, m);
+    const float hb = ok ? pt_global(NL.head_b)[lane] : 0.0f, ls = ok ? pt_global(NL.logstd)[lane] : 0.0f;
+    stdL = expf(ls); sumL = row16_sum(ls);
+    const float vb = pt_global(NL.vf_b)[0];
+    v0 = __shfl(m[0], 16) + vb; v1 = __shfl(m[1], 16) + vb;
+    mL1 = m[1] + hb;
+    const float n0 = ok ? pt_global(r.noise0)[nz] : 0.0f;
+    nlp0 = gauss_row(m[0] + hb, stdL, sumL, ok, true, n0, act0, A);      // the learner samples for agent 0
+    wave_sync();   // the raw tile is filtered in place and the latent rows are rewritten by the zoo net's pass
+  }
+  const float n1 = ok ? pt_global(r.noise1)[nz] : 0.0f;
+  const float PT_GAS* zp = pt_global(r.opponent) + (size_t)jz * q.Pz;
+  const float* zf = q.filt + (size_t)jz * 2 * q.Dz;
+  float onlp0, onlp1, nlp1;
+  if constexpr (ZLSTM) {
+    float* sc = xo + q.sc_off;
+    const float lsO = ok ? zp[q.Pz - A + lane] : 0.0f;   // the row ends with logstd [A]
+    const float stdO = expf(lsO), sumO = row16_sum(lsO);
+    const float keep1 = 1.0f - (float)((dn >> 8) & 0xff);
+    const float mO1 = zoo_lstm_mean<true>(q, zp, zf, r.st1 + (size_t)e * 128, keep1, xo + XS, sc, lane);
+    onlp1 = gauss_row(mO1, stdO, sumO, ok, true, n1, act1, A);           // the zoo net samples for agent 1 ...
+    nlp1 = gauss_row(mL1, stdL, sumL, ok, false, 0.0f, act1, A);         // ... the learner (zero state) scores it
+    wave_sync();   // the cell's rows are rewritten by the scoring pass
+    const float mO0 = zoo_lstm_mean<false>(q, zp, zf, nullptr, 0.0f, xo, sc, lane);
+    onlp0 = gauss_row(mO0, stdO, sumO, ok, false, 0.0f, act0, A);        // the zoo net (zero state) scores agent 0's action
+  } else {
+    float* h1 = xo + 2 * XS;                         // [2][PT_HS] | h2 [2][PT_HS]
+    float* h2 = h1 + 2 * PT_HS;
+    const f32x4 mO = zoo_trunk_forward<2>(pi_net((const float*)zp, r.L), zf, q.clip, xo, XS, q.Dz, h1, h2, lane);
+    const float lsO = ok ? zp[r.L.logstd + lane] : 0.0f;
+    const float stdO = expf(lsO), sumO = row16_sum(lsO);
+    onlp0 = gauss_row(mO[0], stdO, sumO, ok, false, 0.0f, act0, A);      // the zoo net scores agent 0's action
+    onlp1 = gauss_row(mO[1], stdO, sumO, ok, true, n1, act1, A);         // the zoo net samples for agent 1 ...
+    nlp1 = gauss_row(mL1, stdL, sumL, ok, false, 0.0f, act1, A);         // ... the learner (zero state) scores it
+  }
+  if (ok) policy_commit_actions<true>(c, a, r, e, lane, act0, act1, A, slot0, slot1);
+  if (lane == 0) policy_record_scalars(r, slot0, slot1, nlp0, nlp1, onlp0, onlp1, v0, v1);
+  wave_sync();   // the action buffer is read back by the env step (other lanes), the scratch region is the step's again
+}
+
 // Match post phase: where agent 0's episode ended in the step, score it from the step's winner flags (info[.][7] bit 0, just
 // written by this lane): a win if agent 0 carries the flag, a loss if only agent 1 does, a draw otherwise (timeouts, diverged states)
 // -- policy_zoo._evaluate_against's rule.  Counted while wins + losses + draws < quota.
@@ -3287,6 +3407,9 @@ static_assert(sizeof(ZooLstmArgs) <= 6 * sizeof(float*) && offsetof(RolloutArgs,
                   offsetof(RolloutArgs, onlp) == offsetof(RolloutArgs, obs) + 5 * sizeof(float*) &&
                   offsetof(RolloutArgs, done) == offsetof(RolloutArgs, obs) + 6 * sizeof(float*),
               "ZooLstmArgs overlays the six rollout-record pointers of RolloutArgs: no field moves");
+static_assert(sizeof(ZooTailArgs) <= 4 * sizeof(void*) + 2 * sizeof(int) && offsetof(RolloutArgs, zt) == offsetof(RolloutArgs, snaps) &&
+                  offsetof(RolloutArgs, quota) + sizeof(int) == sizeof(RolloutArgs),
+              "ZooTailArgs (POLICY 9 / 10) overlays the match fields that end RolloutArgs: the struct keeps its size");
 
 // Scheduling: the launch is a set of persistent waves (one per wave slot of the chip) that draw TICKETS from a global counter;
 // ticket t is step t / N of env t % N.  Env steps differ in cost by 3x (contacts, Newton iterations, agents wrestling), so
@@ -3308,7 +3431,9 @@ template <int NV, int POLICY, int SL = 0>   // POLICY 0: MLP(64,64) policy / val
                                             // (sumo_match_steps_zoo); 6: MLP checkpoints against policy-zoo LSTM nets
                                             // (sumo_match_steps_zoo_lstm); 7: LSTM(128) checkpoints against policy-zoo LSTM
                                             // nets (sumo_match_steps_lstm_zoo_lstm); 8: MLP learner against policy-zoo LSTM
-                                            // nets (sumo_rollout_steps_zoo_lstm); SL 1: static Layout
+                                            // nets (sumo_rollout_steps_zoo_lstm); 9 / 10: LSTM(128) learner against policy-zoo
+                                            // MLP / LSTM nets (sumo_rollout_steps_lstm_zoo / sumo_rollout_steps_lstm_zoo_lstm);
+                                            // SL 1: static Layout
 __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(SUMO_WPE_OF(NV), SUMO_WPE_OF(NV))))
 sumo_rollout_kernel(const Params* P, RolloutLaunch launch_args) {
   // `launch_args` is read in place from the kernel-argument segment (second argument, 8-byte aligned right behind P) through a
@@ -3369,6 +3494,8 @@ sumo_rollout_kernel(const Params* P, RolloutLaunch launch_args) {
     else if constexpr (POLICY == 6) rollout_policy_phase_match_zoo_lstm(c, lp->a, lp->r, e, s);
     else if constexpr (POLICY == 7) rollout_policy_phase_match_lstm_zoo_lstm<128>(c, lp->a, lp->r, e, s);
     else if constexpr (POLICY == 8) rollout_policy_phase_zoo_lstm(c, lp->a, lp->r, e, s);
+    else if constexpr (POLICY == 9) rollout_policy_phase_lstm_zoo<128, false>(c, lp->a, lp->r, e, s);
+    else if constexpr (POLICY == 10) rollout_policy_phase_lstm_zoo<128, true>(c, lp->a, lp->r, e, s);
     else rollout_policy_phase(c, lp->a, lp->r, e, s);
 #ifdef SUMO_DBG_HARD_BARRIER
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -4235,6 +4362,8 @@ static int rollout_launch(sumo_engine* E, const RolloutArgs& r, int policy, cons
                                                        : policy == 6 ? sumo_rollout_kernel<NV, 6, SL>
                                                        : policy == 7 ? sumo_rollout_kernel<NV, 7, SL>
                                                        : policy == 8 ? sumo_rollout_kernel<NV, 8, SL>
+                                                       : policy == 9 ? sumo_rollout_kernel<NV, 9, SL>
+                                                       : policy == 10 ? sumo_rollout_kernel<NV, 10, SL>
                                                                      : sumo_rollout_kernel<NV, 0, SL>;
         hipLaunchKernelGGL(kernel, g_, b_, lds_, st_, E->d_params, rl);
       }))
@@ -4406,12 +4535,16 @@ extern "C" int sumo_match_steps_lstm(sumo_handle_t E, const sumo_match_lstm* mo,
 }
 
 // the zoo table of sumo_rollout_steps_zoo / sumo_match_steps_zoo: checks, then the fields of RolloutArgs it fills
-static int place_zoo_table(RolloutArgs& r, const sumo_zoo_mlp* z, int od, int ad) {
+static int check_zoo_table(const sumo_zoo_mlp* z, int od) {
   if (!z->params || !z->filt) FAIL(-2, "sumo_zoo_mlp: missing buffer (params / filt)");
   if (z->nzoo < 1) FAIL(-7, "nzoo %d: the zoo table needs at least one entry", z->nzoo);
   if (z->ob_dim < 1 || z->ob_dim > od)
     FAIL(-4, "zoo ob_dim %d outside [1, %d]: a policy-zoo MLP net reads the first ob_dim columns of the scene's observation", z->ob_dim, od);
   if (!(z->obs_clip > 0.0f)) FAIL(-9, "obs_clip %g must be positive", (double)z->obs_clip);
+  return 0;
+}
+static int place_zoo_table(RolloutArgs& r, const sumo_zoo_mlp* z, int od, int ad) {
+  if (int rc = check_zoo_table(z, od)) return rc;
   r.opponent = z->params;
   r.zoo.filt = z->filt; r.zoo.clip = z->obs_clip; r.zoo.nzoo = z->nzoo; r.zoo.Dz = z->ob_dim; r.zoo.Lz = make_layout(z->ob_dim, ad);
   return 0;
@@ -4463,7 +4596,11 @@ extern "C" int sumo_match_steps_zoo(sumo_handle_t E, const sumo_match* mo, const
 // fields of RolloutArgs it fills -- st1 and the launch's ZooLstmArgs q (r.zl in the match modes, r.zlr in the rollout mode)
 // (after place_*_scratch: the cell's rows -- embedding | previous latent | new latent, 64 floats each -- go behind the observation
 // tile, 16-byte aligned, into the `rows_floats` floats the placed scratch holds there)
-static int place_zoo_lstm_table(RolloutArgs& r, ZooLstmArgs& q, const sumo_zoo_lstm* z, int od, int ad, int rows_floats) {
+// (Q: ZooLstmArgs, or the ZooTailArgs of mode 10, whose parameter rows travel in r.opponent)
+static void zoo_lstm_params(RolloutArgs&, ZooLstmArgs& q, const float* p) { q.params = p; }
+static void zoo_lstm_params(RolloutArgs& r, ZooTailArgs&, const float* p) { r.opponent = p; }
+template <class Q>
+static int place_zoo_lstm_table(RolloutArgs& r, Q& q, const sumo_zoo_lstm* z, int od, int ad, int rows_floats) {
   if (!z->params || !z->filt) FAIL(-2, "sumo_zoo_lstm: missing buffer (params / filt)");
   if (!z->state) FAIL(-2, "sumo_zoo_lstm: missing state buffer (state)");
   if (z->nzoo < 1) FAIL(-7, "nzoo %d: the zoo table needs at least one entry", z->nzoo);
@@ -4471,7 +4608,8 @@ static int place_zoo_lstm_table(RolloutArgs& r, ZooLstmArgs& q, const sumo_zoo_l
     FAIL(-4, "zoo ob_dim %d outside [1, %d]: a policy-zoo LSTM net reads the first ob_dim columns of the scene's observation", z->ob_dim, od);
   if (z->emb_dim != PT_H || z->hidden != 64) FAIL(-4, "zoo LSTM emb_dim %d / hidden %d: the fused launch is built for 64 / 64", z->emb_dim, z->hidden);
   if (!(z->obs_clip > 0.0f)) FAIL(-9, "obs_clip %g must be positive", (double)z->obs_clip);
-  q.params = z->params; q.filt = z->filt; q.clip = z->obs_clip; q.forget_bias = z->forget_bias; q.nzoo = z->nzoo; q.Dz = z->ob_dim; q.A = ad; q.emb = z->emb_dim;
+  zoo_lstm_params(r, q, z->params);
+  q.filt = z->filt; q.clip = z->obs_clip; q.forget_bias = z->forget_bias; q.nzoo = z->nzoo; q.Dz = z->ob_dim; q.A = ad; q.emb = z->emb_dim;
   q.Pz = z->ob_dim * PT_H + PT_H + 2 * 64 * 256 + 256 + 64 * ad + 2 * ad;
   r.st1 = z->state;
   const int tile = 2 * r.XS;
@@ -4550,6 +4688,63 @@ extern "C" int sumo_rollout_steps_zoo_lstm(sumo_handle_t E, const sumo_rollout* 
   if (int rc = place_mlp_scratch(E, ro->ob_dim, ro->ac_dim, r)) return rc;
   if (int rc = place_zoo_lstm_table(r, r.zlr, z, od, ad, 4 * PT_HS)) return rc;   // the two hidden tiles of the learner's trunks
   return rollout_launch(E, r, 8, b, stream);
+}
+
+// what sumo_rollout_steps_lstm_zoo and sumo_rollout_steps_lstm_zoo_lstm share.  check_lstm_zoo_rollout: the checks of
+// sumo_rollout_steps_lstm on a launch without opponent nets; place_lstm_zoo_rollout: the learner's fields and the scratch -- x [2][XS]
+// and LSTM_ZOO_ROWS rows of 128 floats (zero row, agent 0's previous latent, two new latents), which the zoo net's hidden tiles /
+// cell rows reuse
+constexpr int LSTM_ZOO_ROWS = 4;
+static_assert(4 * PT_HS <= LSTM_ZOO_ROWS * 128, "mode 9: the zoo trunk's two hidden tiles [2][PT_HS] go where the learner's latent rows were");
+static int check_lstm_zoo_rollout(sumo_engine* E, const sumo_rollout_lstm* ro, int nzoo, const char* name, int* od, int* ad) {
+  if (!ro->learner || !ro->state0 || rollout_buffer_missing(ro)) FAIL(-2, "sumo_rollout_lstm: missing buffer");
+  if (ro->opponents_dev || ro->state1)
+    FAIL(-2, "%s: opponents_dev and state1 must be NULL (the opponents are the zoo table's nets, agent 1's state is the table's)", name);
+  if (int rc = rollout_scene(E, ro->T, ro->Ntot, ro->env_offset, ro->s0, ro->K, od, ad)) return rc;
+  const ppo_lstm_net& n = *ro->learner;
+  if (int rc = check_dims(n.ob_dim, n.ac_dim, *od, *ad)) return rc;
+  if (int rc = check_lstm_shape(n, "rollout")) return rc;
+  if (!n.wx || !n.wh || !n.b || !n.head_w || !n.head_b || !n.logstd || !n.vf_w || !n.vf_b) FAIL(-10, "learner net: missing weights");
+  if (ro->npool != nzoo) FAIL(-7, "npool %d must equal the zoo table's nzoo %d", ro->npool, nzoo);
+  if (ro->tile_net_dev && ((ro->env_offset & 15) || (E->N & 15))) FAIL(-11, "a zoo net per 16-env tile needs env_offset (%d) and the env count (%d) to be multiples of 16", ro->env_offset, E->N);
+  return 0;
+}
+static int place_lstm_zoo_rollout(sumo_engine* E, const sumo_rollout_lstm* ro, int od, RolloutArgs& r) {
+  HIPCHK(hipSetDevice(E->device));
+  memset(&r, 0, sizeof r);
+  r.lnet = *ro->learner; r.tile_net = ro->tile_net_dev; r.st0 = ro->state0;
+  copy_rollout_fields(r, ro);
+  return place_lstm_scratch(E, od, LSTM_ZOO_ROWS, r);
+}
+
+extern "C" int sumo_rollout_steps_lstm_zoo(sumo_handle_t E, const sumo_rollout_lstm* ro, const sumo_zoo_mlp* z, float* actions_dev, float* obs_dev,
+                                           double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
+  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
+  if (int rc = check_launch_args(E, ro, b)) return rc;
+  if (!z) FAIL(-1, "bad arguments");
+  RolloutArgs r;
+  int od = 0, ad = 0;
+  if (int rc = check_lstm_zoo_rollout(E, ro, z->nzoo, "sumo_rollout_steps_lstm_zoo", &od, &ad)) return rc;
+  if (int rc = check_zoo_table(z, od)) return rc;
+  if (int rc = place_lstm_zoo_rollout(E, ro, od, r)) return rc;
+  r.opponent = z->params;
+  r.L = make_layout(z->ob_dim, ad);
+  r.zt.filt = z->filt; r.zt.clip = z->obs_clip; r.zt.nzoo = z->nzoo; r.zt.Dz = z->ob_dim; r.zt.A = ad; r.zt.Pz = r.L.P;
+  return rollout_launch(E, r, 9, b, stream);
+}
+
+extern "C" int sumo_rollout_steps_lstm_zoo_lstm(sumo_handle_t E, const sumo_rollout_lstm* ro, const sumo_zoo_lstm* z, float* actions_dev,
+                                                float* obs_dev, double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev,
+                                                int32_t* ep_l_dev, void* stream) {
+  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
+  if (int rc = check_launch_args(E, ro, b)) return rc;
+  if (!z) FAIL(-1, "bad arguments");
+  RolloutArgs r;
+  int od = 0, ad = 0;
+  if (int rc = check_lstm_zoo_rollout(E, ro, z->nzoo, "sumo_rollout_steps_lstm_zoo_lstm", &od, &ad)) return rc;
+  if (int rc = place_lstm_zoo_rollout(E, ro, od, r)) return rc;   // (the table's checks need the placed scratch: as modes 6-8)
+  if (int rc = place_zoo_lstm_table(r, r.zt, z, od, ad, LSTM_ZOO_ROWS * 128)) return rc;   // the cell's rows go where the learner's latent rows were
+  return rollout_launch(E, r, 10, b, stream);
 }
 
 #ifdef SUMO_POLICY_PROBE

@@ -139,6 +139,12 @@ class LstmPPOModel(Learner):
         likelihood of the learner's action (runner.py:85 passes no state)."""
         return self._run(observation, S, M, given_action=given_action)[3]
 
+    def score_and_value(self, observation, given_action):
+        """(value, neglogp) of ``given_action`` from the sequence start state (zeros) in ONE evaluation: how the Runner scores and
+        values agent 1's action when a policy-zoo net plays it (its state is not this net's)."""
+        r = self._run(observation, None, None, given_action=given_action)
+        return r[1], r[3]
+
     # ---- training ---------------------------------------------------------------------------------------------------
     def loss_and_grads(self, cliprange, obs, returns, masks, actions, advs, neglogpacs, IS_weight, states, nsteps, world=1):
         """Forward over ``nsteps`` + BPTT for a minibatch of whole env sequences.  Flat inputs are env-major

@@ -102,7 +102,8 @@ class Runner(AbstractEnvRunner):
         self.rollout_chunk = int(os.environ.get("SUMO_ROLLOUT_CHUNK", "0"))   # steps per launch (0 = the whole rollout)
         self.opponent_pool = None     # opponent_pool.OpponentPool: frozen snapshots + per-env snapshot index (fused path)
         # opt-in (learn(fused_fix_opponent=True)): a policy-zoo opponent (opponent_mode='fix') plays inside the fused launch
-        # (sumo_rollout_steps_zoo for an MLP net, sumo_rollout_steps_zoo_lstm for an LSTM net).  The action noise is then drawn per
+        # (sumo_rollout_steps_zoo for an MLP net, sumo_rollout_steps_zoo_lstm for an LSTM net; sumo_rollout_steps_lstm_zoo /
+        # sumo_rollout_steps_lstm_zoo_lstm where the learner is an LSTM(128)).  The action noise is then drawn per
         # group and generator for the whole buffer, as the MLP self-play path draws it -- another, equally valid stream than the
         # per-step draws of the default fix-mode path; with SUMO_FUSED_ROLLOUT=0 the step-by-step launches play that same stream
         # (bit-identical rollouts).
@@ -400,6 +401,98 @@ class Runner(AbstractEnvRunner):
         zoo.evaluate(o1, state=self.zoo_state[sl], mask=dn[:, 1], out=dict(action=act1, neglogp=B["onlp"][1, s, sl]), **(nk1 or {}))
         learner.evaluate(o1, PI | VF, given_action=act1, out=dict(neglogp=B["nlp"][1, s, sl], value=B["val"][1, s, sl], action=B["scratch_b"][sl]))
 
+    # ---- a recurrent learner against a policy-zoo net (learn(network='lstm', opponent_mode='fix')) ----------------------------
+    def _lstm_vs_zoo(self):
+        """``models[1]`` is a fixed policy-zoo opponent of a recurrent learner (``recurrent`` is computed at construction, before
+        ``install_fixed_opponent`` swaps the second model)."""
+        from .policy_zoo import FixedOpponentModel
+        return self.recurrent and isinstance(self.models[1], FixedOpponentModel)
+
+    def lstm_zoo_opponent(self):
+        """:meth:`zoo_opponent` for a recurrent learner: the ``ZooMLPPolicy`` or ``ZooLSTMPolicy`` behind ``models[1]`` when the run
+        opted into the fused fix-mode rollout (``fused_fix_opponent``) and the launch applies -- device mode, cfrc_mode 'zero', an
+        ``LstmPPOModel`` learner with nlstm = 128 of the env's shape, a zoo net of either family (an LSTM net: embedding and cell
+        of 64), env groups that start and end on multiples of 16 (the launch indexes the table per 16-env tile) -- else None."""
+        env = self.env
+        if not (self.fused_fix_opponent and self.device_mode and self._lstm_vs_zoo() and hasattr(env, "rollout_steps_lstm_zoo_group")):
+            return None
+        from .lstm_model import LstmPPOModel
+        from .policy_zoo import ZooLSTMPolicy, ZooMLPPolicy
+        if getattr(env, "cfrc_mode", "zero") != "zero" or self.opponent_pool is not None:
+            return None
+        m0, zoo = self.models[0], self.models[1].act_model
+        if type(m0) is not LstmPPOModel or type(zoo) not in (ZooMLPPolicy, ZooLSTMPolicy):
+            return None
+        if type(zoo) is ZooLSTMPolicy and not (zoo.emb == zoo.hidden == 64 and hasattr(env, "rollout_steps_lstm_zoo_lstm_group")):
+            return None
+        if any((env._gs(g).start % 16 or env._gs(g).stop % 16) for g in range(getattr(env, "groups", 1))):
+            return None
+        sp = m0.spec
+        if not (sp.nlstm == 128 and sp.ob_dim == self.ob_dim and zoo.ob_dim <= self.ob_dim
+                and sp.ac_dim == zoo.ac_dim == env.act_dev.shape[2] and env.obs_dev.stride(2) == 1):
+            return None
+        return zoo
+
+    def fused_lstm_zoo_ok(self):
+        """The fused launch of a recurrent learner against a policy-zoo net (``sumo_rollout_steps_lstm_zoo`` /
+        ``sumo_rollout_steps_lstm_zoo_lstm``) applies: see :meth:`lstm_zoo_opponent`."""
+        return self.fused_rollout and self.lstm_zoo_opponent() is not None
+
+    def _draw_lstm_zoo(self, B, n, m0, zoo):
+        """A group's noise pair for the whole buffer under the opt-in: the learner's rows step by step (``_draw_steps``, as the
+        recurrent self-play path draws), the zoo net's in one call (as ``_draw_zoo`` draws)."""
+        t = self._t
+        A, T = m0.spec.ac_dim, B["T"]
+        return (self._draw_steps(m0.gen, T, n, A), t.randn((T, n, A), generator=zoo.gen, device=self.device, dtype=t.float32))
+
+    def _steps_fused_lstm_zoo(self, B, s0, K, alpha):
+        """``_steps_fused_lstm`` against a policy-zoo net: one ``sumo_rollout_steps_lstm_zoo`` (MLP net) or
+        ``sumo_rollout_steps_lstm_zoo_lstm`` (LSTM net) launch per env group.  The net sits in a cached one-row
+        :class:`policy_zoo.ZooTable` / :class:`policy_zoo.ZooLstmTable`; ``self.states[0]`` and, for an LSTM net, ``self.zoo_state``
+        are advanced in place.  Same numbers as ``_lstm_zoo_evals`` on the same noise rows, bit for bit."""
+        import ctypes as C
+        from . import capi
+        from .policy_zoo import ZooLstmTable, ZooTable
+        m0, zoo = self.models[0], self.lstm_zoo_opponent()
+        rec = getattr(zoo, "recurrent", False)
+        if self._zoo_table is None or self._zoo_table[0] is not zoo:
+            self._zoo_table = (zoo, (ZooLstmTable if rec else ZooTable)([zoo], zoo.ac_dim, self.device))
+        table = self._zoo_table[1]
+        env = self.env
+
+        def fill(ro, sl):
+            ro.learner = C.addressof(m0._net)
+            ro.opponents_dev, ro.tile_net_dev, ro.npool = None, None, table.capacity
+            ro.state0, ro.state1 = self.states[0][sl].data_ptr(), None
+
+        if rec:
+            launch = lambda g, ro: env.rollout_steps_lstm_zoo_lstm_group(g, ro, table.struct(self.zoo_state[env._gs(g)]))
+        else:
+            zs = table.struct()
+            launch = lambda g, ro: env.rollout_steps_lstm_zoo_group(g, ro, zs)
+        self._fused_groups(B, s0, K, alpha, capi.RolloutLstm, lambda n: self._draw_lstm_zoo(B, n, m0, zoo), fill, launch)
+
+    def _lstm_zoo_evals(self, B, s, m0, zoo, o0, o1, dn, sl, nk0=None, nk1=None):
+        """The step's four evaluations of a recurrent learner against a zoo net, step by step: the learner acts on agent 0 from its
+        rows of ``self.states[0]`` (masked by agent 0's done flags of the previous step, advanced); the zoo net scores that action
+        (an LSTM net: from a zero state); the zoo net acts on agent 1 (an LSTM net: from its rows of ``self.zoo_state``, masked by
+        agent 1's done flags, advanced in place); the learner scores AND values that action in one evaluation from a zero state --
+        a zoo net's state is not the learner's, so the self-play rule (value from agent 1's new state) has nothing to feed.
+        ``self.states[1]`` is neither read nor advanced.  ``nk0`` / ``nk1`` as in ``_policy_evals``."""
+        act0, act1 = B["act"][0, s, sl], B["act"][1, s, sl]
+        a0, v0, S0, n0 = m0.step(o0, S=self.states[0][sl], M=dn[:, 0], **(nk0 or {}))
+        self.states[0][sl] = S0
+        act0.copy_(a0); B["val"][0, s, sl].copy_(v0); B["nlp"][0, s, sl].copy_(n0)
+        if getattr(zoo, "recurrent", False):
+            zoo.evaluate(o0, given_action=act0, out=dict(neglogp=B["onlp"][0, s, sl], action=B["scratch_a"][sl]))
+            zoo.evaluate(o1, state=self.zoo_state[sl], mask=dn[:, 1], out=dict(action=act1, neglogp=B["onlp"][1, s, sl]), **(nk1 or {}))
+        else:
+            PI = ppo_capi.FWD_PI
+            zoo.evaluate(o0, PI, given_action=act0, out=dict(neglogp=B["onlp"][0, s, sl], action=B["scratch_a"][sl]))
+            zoo.evaluate(o1, PI, out=dict(action=act1, neglogp=B["onlp"][1, s, sl]), **(nk1 or {}))
+        v1, n1 = m0.score_and_value(o1, act1)
+        B["val"][1, s, sl].copy_(v1); B["nlp"][1, s, sl].copy_(n1)
+
     def join_groups(self):
         """Make the current stream wait for every env group's stream (no-op without groups)."""
         if self._gstreams is not None:
@@ -423,6 +516,16 @@ class Runner(AbstractEnvRunner):
         act0, act1 = B["act"][0, s, sl], B["act"][1, s, sl]
         if fused:
             pass
+        elif self._lstm_vs_zoo():
+            # a recurrent learner in fix mode.  Under the opt-in: the noise rows the fused launch (``_steps_fused_lstm_zoo``) would
+            # read, drawn for the whole buffer at the group's first step; otherwise each net draws per step from its own generator
+            nk0 = nk1 = None
+            if self.lstm_zoo_opponent() is not None:
+                key = ("noise", sl.start)
+                if s == 0 or key not in B:
+                    B[key] = self._draw_lstm_zoo(B, n, self.models[0], opp)
+                nk0, nk1 = dict(noise=B[key][0][s]), dict(noise=B[key][1][s])
+            self._lstm_zoo_evals(B, s, self.models[0], opp, o0, o1, dn, sl, nk0, nk1)
         elif self.recurrent:
             # same five evaluations through the recurrent nets (runner.py:62-96 with the S / M feeds): each stream carries its
             # acting model's state; the scoring calls without a state feed start from zeros, as the reference's calls do
@@ -551,10 +654,12 @@ class Runner(AbstractEnvRunner):
             cur = t.cuda.current_stream(self.device)
             for st in self._gstreams:
                 st.wait_stream(cur)
-        fused = self.fused_ok() or self.fused_lstm_ok() or self.fused_zoo_ok()
+        fused = self.fused_ok() or self.fused_lstm_ok() or self.fused_zoo_ok() or self.fused_lstm_zoo_ok()
         if fused:
             steps = self._steps_fused
-            if self.recurrent:
+            if self.fused_lstm_zoo_ok():
+                steps = self._steps_fused_lstm_zoo
+            elif self.recurrent:
                 steps = self._steps_fused_lstm
             elif self.fused_zoo_ok():
                 steps = self._steps_fused_zoo_lstm if getattr(self.zoo_opponent(), "recurrent", False) else self._steps_fused_zoo
@@ -569,7 +674,11 @@ class Runner(AbstractEnvRunner):
         self.join_groups()
         learner = self.models[0].act_model
         last_values = t.empty((2, N), dtype=t.float32, device=self.device)
-        if self.recurrent:
+        if self._lstm_vs_zoo():
+            # agent 1 carries no state of the learner's (``_lstm_zoo_evals``): its last value is the learner's from a zero state
+            last_values[0].copy_(self.models[0].value(self.obs[:, 0, :], S=self.states[0], M=self.dones[:, 0]))
+            last_values[1].copy_(self.models[0].value(self.obs[:, 1, :]))
+        elif self.recurrent:
             for g in range(2):
                 last_values[g].copy_(self.models[0].value(self.obs[:, g, :], S=self.states[g], M=self.dones[:, g]))
         else:

@@ -169,6 +169,16 @@ class SumoVecEnv(VecEnv):
         ``state`` holds agent 1's rows of the group's envs)."""
         self.engines[g].rollout_steps_zoo_lstm(ro, zoo, *self.env_ptrs(g), stream=self._stream())
 
+    def rollout_steps_lstm_zoo_group(self, g, ro, zoo):
+        """The recurrent launch against policy-zoo MLP nets (``capi.Engine.rollout_steps_lstm_zoo``, ``ro`` a ``capi.RolloutLstm``,
+        ``zoo`` a ``capi.ZooMlp``)."""
+        self.engines[g].rollout_steps_lstm_zoo(ro, zoo, *self.env_ptrs(g), stream=self._stream())
+
+    def rollout_steps_lstm_zoo_lstm_group(self, g, ro, zoo):
+        """The recurrent launch against policy-zoo LSTM nets (``capi.Engine.rollout_steps_lstm_zoo_lstm``, ``zoo`` a
+        ``capi.ZooLstm`` whose ``state`` holds agent 1's rows of the group's envs)."""
+        self.engines[g].rollout_steps_lstm_zoo_lstm(ro, zoo, *self.env_ptrs(g), stream=self._stream())
+
     def step_device(self, actions):
         """actions: float32 CUDA tensor [N, 2, act_stride]. Returns (obs, info, done, ep_r, ep_dr, ep_l) tensors that
         are overwritten by the next call."""

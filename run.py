@@ -46,7 +46,7 @@ def main(argv):
                     "(observations, lose test).  0 = the reference's training setting (its run.py:76-77 leaves the -0.5 commented out); its "
                     "evaluation / play scripts use -0.5, which is what the policy-zoo nets expect")
     ap.add_argument("--fused_fix_opponent", action="store_true", help="opponent_mode=fix: play the policy-zoo net (MLP or LSTM file) inside the fused "
-                    "rollout launch (sumo_rollout_steps_zoo / sumo_rollout_steps_zoo_lstm).  Opt-in: the action noise is drawn per rollout buffer instead of per step, "
+                    "rollout launch (sumo_rollout_steps_zoo / sumo_rollout_steps_zoo_lstm; --network lstm: sumo_rollout_steps_lstm_zoo / sumo_rollout_steps_lstm_zoo_lstm).  Opt-in: the action noise is drawn per rollout buffer instead of per step, "
                     "so the same seed gives another, equally valid random stream")
     args, unknown = ap.parse_known_args(argv)
     extra = parse_unknown(unknown)

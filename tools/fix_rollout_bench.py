@@ -5,6 +5,8 @@ per launch through the Runner's own drivers (noise draws included), the fused la
     python tools/fix_rollout_bench.py --opponent zoo_lstm   # sumo_rollout_steps_zoo_lstm against ppo_forward + ppo_lstm_step per step
     python tools/fix_rollout_bench.py --opponent zoo        # sumo_rollout_steps_zoo against ppo_forward + ppo_forward_filtered
     python tools/fix_rollout_bench.py --opponent self       # sumo_rollout_steps (MLP self-play) against ppo_selfplay_forward
+    python tools/fix_rollout_bench.py --network lstm --opponent zoo        # sumo_rollout_steps_lstm_zoo: an LSTM(128) learner
+    python tools/fix_rollout_bench.py --network lstm --opponent zoo_lstm   # sumo_rollout_steps_lstm_zoo_lstm
 
 Every repeat times `launches` windows of K steps on each path, fused and step by step interleaved, after `warmup` windows; the envs
 keep running from window to window.  Prints one JSON line: env-steps/s per repeat and the median of both paths."""
@@ -26,12 +28,16 @@ def main(argv):
     ap.add_argument("--warmup", type=int, default=5, help="untimed K-step windows per path")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--opponent", choices=("self", "zoo", "zoo_lstm"), default="zoo_lstm")
+    ap.add_argument("--network", choices=("mlp", "lstm"), default="mlp", help="the learner: MLP(64,64) nets or an LSTM(128) (LstmPPOModel; "
+                    "--opponent zoo / zoo_lstm)")
     ap.add_argument("--skip_stepwise", action="store_true")
     args = ap.parse_args(argv)
+    if args.network == "lstm" and args.opponent == "self":
+        ap.error("--network lstm measures the fix-mode launches: --opponent zoo or zoo_lstm (tools/lstm_bench.py times recurrent self-play)")
     import numpy as np
     import torch
     from tools.match_bench import _zoo_flat, _zoo_lstm_flat
-    from robosumo_selfplay_amd import policies, policy_zoo
+    from robosumo_selfplay_amd import lstm_model, policies, policy_zoo
     from robosumo_selfplay_amd.model import PPOModel
     from robosumo_selfplay_amd.runner import Runner
     from robosumo_selfplay_amd.vec_env import SumoVecEnv
@@ -39,23 +45,35 @@ def main(argv):
     def runner():
         env = SumoVecEnv(args.env, num_envs=args.num_env, seed=3)
         D, A = env.observation_space[0].shape[0], env.action_space[0].shape[0]
-        spec = policies.PolicySpec(D, A, value_network="copy", activation="relu")
-        models = [PPOModel(policy=spec, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, trainable=False) for _ in range(2)]
+        if args.network == "lstm":
+            spec = lstm_model.LstmSpec(D, A, 128)
+            models = [lstm_model.LstmPPOModel(policy=spec, nbatch_act=args.num_env, nsteps=args.K, trainable=False) for _ in range(2)]
+        else:
+            spec = policies.PolicySpec(D, A, value_network="copy", activation="relu")
+            models = [PPOModel(policy=spec, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, trainable=False) for _ in range(2)]
         rng = np.random.default_rng(1)
+        fixed = None
         if args.opponent == "zoo":
-            models[1] = policy_zoo.FixedOpponentModel(policy_zoo.ZooMLPPolicy(_zoo_flat(policy_zoo, D - 1, A, rng), A))
+            fixed = policy_zoo.FixedOpponentModel(policy_zoo.ZooMLPPolicy(_zoo_flat(policy_zoo, D - 1, A, rng), A))
         elif args.opponent == "zoo_lstm":
-            models[1] = policy_zoo.FixedOpponentModel(policy_zoo.ZooLSTMPolicy(_zoo_lstm_flat(policy_zoo, D - 1, A, rng), A))
+            fixed = policy_zoo.FixedOpponentModel(policy_zoo.ZooLSTMPolicy(_zoo_lstm_flat(policy_zoo, D - 1, A, rng), A))
+        if fixed is not None and args.network == "mlp":
+            models[1] = fixed
         for k, m in enumerate(models):
             m.act_model.seed(100 + k)
         r = Runner(env=env, models=models, nsteps=args.K, nagent=2, gamma=0.995, lam=0.95, rho_bar=1.0, c_bar=1.0)
+        if fixed is not None and args.network == "lstm":      # as learn() does: the Runner is built on two recurrent models first
+            fixed.act_model.seed(101)
+            r.models[1] = fixed
         r.fused_fix_opponent = True
         return r
 
     def window(r, B, fused):
         if fused:
             steps = r._steps_fused
-            if r.fused_zoo_ok():
+            if r.fused_lstm_zoo_ok():
+                steps = r._steps_fused_lstm_zoo
+            elif r.fused_zoo_ok():
                 steps = r._steps_fused_zoo_lstm if args.opponent == "zoo_lstm" else r._steps_fused_zoo
             steps(B, 0, args.K, 0.5)
         else:
@@ -66,7 +84,7 @@ def main(argv):
     rs = {f: runner() for f in paths}
     for f, r in rs.items():
         r.fused_rollout = f
-        assert (r.fused_ok() or r.fused_zoo_ok()) == f, "the fused launch does not apply"
+        assert (r.fused_ok() or r.fused_zoo_ok() or r.fused_lstm_zoo_ok()) == f, "the fused launch does not apply"
     Bs = {f: r._alloc_device(args.K) for f, r in rs.items()}
     rates = {f: [] for f in paths}
     for rep in range(args.repeats + 1):                      # repeat 0 is the warm-up
@@ -85,7 +103,7 @@ def main(argv):
             for E in r.env.engines:
                 E.rollout_status()
         assert r.env.stats()["rollout_aborts"] == 0
-    out = dict(opponent=args.opponent, env=args.env, num_env=args.num_env, K=args.K, launches=args.launches, repeats=args.repeats)
+    out = dict(network=args.network, opponent=args.opponent, env=args.env, num_env=args.num_env, K=args.K, launches=args.launches, repeats=args.repeats)
     for f in paths:
         name = "fused" if f else "stepwise"
         out[name + "_env_steps_per_s"] = [round(x) for x in rates[f]]

@@ -5,6 +5,8 @@ comparison of two builds (the gate of a change that must leave the existing kern
     python tools/isa_table.py robosumo_selfplay_amd/csrc/libsumo_hip.so                       # table of one library
     python tools/isa_table.py <parent>/libsumo_hip.so robosumo_selfplay_amd/csrc/libsumo_hip.so    # + comparison, exit 1 on a difference
 
+    python tools/isa_table.py --only sumo_ <parent>/libsumo_hip.so robosumo_selfplay_amd/csrc/libsumo_hip.so   # the project's own kernels
+
 Kernels present in both libraries must agree in every figure; kernels only in the second one are listed as new."""
 import os
 import re
@@ -46,8 +48,14 @@ def fmt(t):
 
 
 def main(argv):
+    only = None
+    if "--only" in argv:                                  # --only sumo_ : the kernels whose demangled name contains the text
+        k = argv.index("--only")
+        only, argv = argv[k + 1], argv[:k] + argv[k + 2:]
     head = "%-110s %s" % ("kernel", " ".join(f.strip(".").replace("_count", "").replace("private_segment_fixed_size", "scratch") for f in FIELDS))
     tabs = [table(p) for p in argv]
+    if only:
+        tabs = [{k: v for k, v in t.items() if only in k} for t in tabs]
     for p, t in zip(argv, tabs):
         print("== %s (%d kernels)\n%s\n%s\n" % (p, len(t), head, fmt(t)))
     if len(tabs) == 2:

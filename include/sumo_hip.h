@@ -280,6 +280,34 @@ int sumo_rollout_steps_lstm_zoo(sumo_handle_t h, const sumo_rollout_lstm* r, con
 int sumo_rollout_steps_lstm_zoo_lstm(sumo_handle_t h, const sumo_rollout_lstm* r, const sumo_zoo_lstm* z, float* actions_dev, float* obs_dev,
                                      double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev,
                                      void* stream);
+/* The rollout launches against a LEAGUE of policy-zoo nets of both families (learn(opponent_mode='fix', fix_opponent_path=[files])
+ * with MLP and LSTM files mixed): every 16-env tile of the whole env set faces one member, MLP tiles and LSTM tiles in one launch.
+ *   mlp             a sumo_zoo_mlp table (nzoo >= 1)
+ *   lstm            a sumo_zoo_lstm table (nzoo >= 1) whose state ([E][2 * 64]) holds rows of THIS engine's envs; only the envs of
+ *                   tiles that face an LSTM member read and write their rows
+ *   tile_entry_dev  DEVICE int32 [Ntot / 16], indexed (env_offset + e) / 16 like tile_net_dev (NULL = entry 0): an entry in
+ *                   [0, mlp.nzoo) is that row of the MLP table, an entry in [mlp.nzoo, mlp.nzoo + lstm.nzoo) is row
+ *                   entry - mlp.nzoo of the LSTM table; any other entry raises the launch's abort flag (sumo_rollout_status returns
+ *                   -20) and entry 0 plays
+ * The owning wave reads its tile's entry once per step and takes a wave-uniform branch: the zoo pass of sumo_rollout_steps_zoo /
+ * sumo_rollout_steps_lstm_zoo (MLP member) or of sumo_rollout_steps_zoo_lstm / sumo_rollout_steps_lstm_zoo_lstm (LSTM member), so
+ * every recorded number of a tile equals the single-table launch against its member bit for bit.
+ * sumo_rollout_steps_zoo_league: an MLP(64,64) learner (the launch struct of sumo_rollout_steps_zoo; opponent_params and
+ *   opponent_index must be NULL).  sumo_rollout_steps_lstm_zoo_league: an LSTM(128) learner (the launch struct of
+ *   sumo_rollout_steps_lstm_zoo; opponents_dev, tile_net_dev and state1 must be NULL).  r->npool == mlp.nzoo + lstm.nzoo.
+ * Refused before any launch: whatever the sibling launches refuse of the launch struct and of either table (a table with no net
+ * included: a league of one family plays through that family's launch), npool other than the league's size, tile_entry_dev with an
+ * env range off the 16-env grid, a scene whose policy scratch cannot hold the larger of the two zoo passes. */
+typedef struct sumo_zoo_league {
+  sumo_zoo_mlp mlp;
+  sumo_zoo_lstm lstm;
+  const int32_t* tile_entry_dev;
+} sumo_zoo_league;
+int sumo_rollout_steps_zoo_league(sumo_handle_t h, const sumo_rollout* r, const sumo_zoo_league* z, float* actions_dev, float* obs_dev,
+                                  double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream);
+int sumo_rollout_steps_lstm_zoo_league(sumo_handle_t h, const sumo_rollout_lstm* r, const sumo_zoo_league* z, float* actions_dev,
+                                       float* obs_dev, double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev,
+                                       int32_t* ep_l_dev, void* stream);
 /* cfrc_mode (reference agents.py:190-214 reads sim.data.cfrc_ext into 84 of the 121 observation entries):
  *   0 = zero (default): what the reference produces -- its MuJoCo 2.1 scenes declare no force / torque / accelerometer sensor, so
  *       mj_rnePostConstraint never runs and cfrc_ext stays at its reset value 0;

@@ -23,8 +23,8 @@ from collections import deque
 
 import numpy as np
 
-from .alg_ppo import (assemble_update_batch, check_opponent_pool, constfn, env_fault_delta, explained_variance, install_fixed_opponent,
-                      safemean, upload)
+from .alg_ppo import (assemble_update_batch, assign_league, check_opponent_pool, constfn, env_fault_delta, explained_variance,
+                      install_fixed_opponent, league_note, safemean, upload)
 
 NEGLOGP_THRESHOLD = 50.0      # alg_ac.py:241-243, hard-coded there
 
@@ -92,10 +92,12 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
         init_fn()
     tfirststart = time.perf_counter()
     history = dict(opponent_versions=[], useful_ratio=[], lossvals=[], fps=[], select_s=[], rollout_s=[], update_s=[],
-                   env_diverged=[], env_dropped_contacts=[], env_rollout_aborts=[])     # per update, from the engine's counters
+                   env_diverged=[], env_dropped_contacts=[], env_rollout_aborts=[],     # per update, from the engine's counters
+                   league_scores=[], league_tiles=[])       # fix mode with a list of files: per update and member (alg_ppo.league_note)
     env_stats_prev = env.stats() if hasattr(env, "stats") else None
     nupdates = total_timesteps // nbatch
     loaded = None        # the checkpoint(s) the opponent holds: re-read from disk only when the selection changes
+    league = None        # fix mode with a list of files: the policy_zoo.ZooLeague on agent 1
     for update in range(1, nupdates + 1):
         tstart = time.perf_counter()
         frac = 1.0 - (update - 1.0) / nupdates
@@ -104,6 +106,7 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
         if opponent_mode == "fix":
             if update == 1:
                 install_fixed_opponent(runner, fix_opponent_path, ac_space.shape[0], dev, (seed or 0) * 1000 + 17)
+            league = assign_league(runner, update)
             history["opponent_versions"].append([])
         else:
             if update == 1 or opponent_mode == "ours":                   # 'ours': v0 for the whole run (decision 3 above)
@@ -152,6 +155,7 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
         history["update_s"].append(tnow - tsel - t_roll)
         history["fps"].append(nbatch / (tnow - tstart))
         env_stats_prev, env_note = env_fault_delta(env, env_stats_prev, history)
+        lg_note = league_note(history, runner, league)
         if update_fn is not None:
             update_fn(update)
         if verbose and (update % log_interval == 0 or update == 1):
@@ -160,7 +164,7 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
             print("update %d/%d  opponent %s  fps %.0f  rollout %.2fms  update %.2fms  ev %.3f  eprewmean %.2f  eplenmean %.1f  %s" % (
                 update, nupdates, opp[0] if opp else "fix", history["fps"][-1], 1e3 * t_roll, 1e3 * history["update_s"][-1], ev,
                 safemean([e["r"] for e in epinfobuf]), safemean([e["l"] for e in epinfobuf]),
-                " ".join("%s %.4g" % (n, v) for n, v in zip(model.loss_names, lossvals))) + env_note, flush=True)
+                " ".join("%s %.4g" % (n, v) for n, v in zip(model.loss_names, lossvals))) + lg_note + env_note, flush=True)
         elif env_note:
             print("update %d/%d%s" % (update, nupdates, env_note), flush=True)
         if save_interval and (update % save_interval == 0 or update == 1):

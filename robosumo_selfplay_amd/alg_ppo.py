@@ -93,14 +93,46 @@ def selection_probs(action_prob, new_action_probs):
 
 def install_fixed_opponent(runner, fix_opponent_path, ac_dim, dev, seed):
     """``opponent_mode='fix'`` (alg_ppo.py:194-206, alg_ac.py:175-189): a policy-zoo net (MLP or LSTM: the file's length selects
-    the family) plays agent 1 for the whole run."""
-    from .policy_zoo import FixedOpponentModel, load_zoo_policy
+    the family) plays agent 1 for the whole run.  A list or tuple of files is a LEAGUE (``policy_zoo.ZooLeague``): every 16-env
+    tile faces one of them, re-dealt per update by :func:`assign_league`; its one noise generator is seeded as the single net's."""
+    from .policy_zoo import FixedOpponentModel, load_zoo_league, load_zoo_policy
     if fix_opponent_path is None:
         raise ValueError("opponent_mode='fix' needs fix_opponent_path=<policy_zoo .npy> (reference default: "
                          "robosumo/robosumo/policy_zoo/assets/ant/mlp/agent-params-v3.npy)")
-    zoo = load_zoo_policy(fix_opponent_path, ac_dim, device=dev)
+    if isinstance(fix_opponent_path, (list, tuple)):
+        env = runner.env
+        if hasattr(env, "_gs") and any((env._gs(g).start % 16 or env._gs(g).stop % 16) for g in range(getattr(env, "groups", 1))):
+            raise ValueError("a league deals its members over 16-env tiles: the env groups must start and end on multiples of 16")
+        zoo = load_zoo_league(fix_opponent_path, ac_dim, runner.nenv, device=dev)
+    else:
+        zoo = load_zoo_policy(fix_opponent_path, ac_dim, device=dev)
     zoo.seed(seed)
     runner.models[1] = FixedOpponentModel(zoo)
+
+
+def assign_league(runner, update):
+    """Start of an update in fix mode: a league re-deals its members over the env tiles, rotated by one tile per update (no-op for
+    a single zoo net).  Returns the league or None."""
+    from .policy_zoo import ZooLeague
+    zoo = getattr(runner.models[1], "act_model", None)
+    if type(zoo) is not ZooLeague:
+        return None
+    zoo.assign(update - 1)
+    return zoo
+
+
+def league_note(history, runner, league):
+    """After a rollout against a league: append the update's per-member tally (episodes, learner wins, losses, draws as
+    ``policy_zoo.league_scores`` estimates them from the episode returns) and the tile assignment to ``history``; returns the learner's win rate per member for the log line."""
+    if league is None:
+        return ""
+    sc = runner.league_scores          # None where the Runner kept no tally (host mode: the episode records are the env's dicts)
+    history["league_scores"].append(None if sc is None else sc.tolist())
+    history["league_tiles"].append([int(x) for x in league.tile_member])
+    if sc is None:
+        return ""
+    rates = ["%d:%s" % (k, "%.2f" % (row[1] / row[0]) if row[0] else "-") for k, row in enumerate(sc)]
+    return "  [league win rate, estimated from returns, %s]" % " ".join(rates)
 
 
 def check_opponent_pool(opponent_mode, runner, fused):
@@ -206,11 +238,13 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
     history = dict(version_gap=[], off_policy_ratio_mean=[], off_env_ratio_mean=[], total_ratio_mean=[], off_policy_ratio_clip_frac=[],
                    off_env_ratio_clip_frac=[], total_ratio_clip_frac=[], useful_ratio=[], opponent_versions=[], ppo_clip_frac=[],
                    approxkl=[], early_stop_info=[], lossvals=[], fps=[], rollout_s=[], update_s=[],
-                   env_diverged=[], env_dropped_contacts=[], env_rollout_aborts=[])     # per update, from the engine's counters
+                   env_diverged=[], env_dropped_contacts=[], env_rollout_aborts=[],     # per update, from the engine's counters
+                   league_scores=[], league_tiles=[])       # fix mode with a list of files: per update and member (league_note)
     env_stats_prev = env.stats() if hasattr(env, "stats") else None
     nupdates = total_timesteps // nbatch
     idx_choice = 0
     opponent_obs = opponent_actions = None
+    league = None
     for update in range(1, nupdates + 1):
         assert nbatch % nminibatches == 0
         tstart = time.perf_counter()
@@ -220,6 +254,7 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
         if opponent_mode == "fix":                                       # alg_ppo.py:194-206: a policy-zoo net
             if update == 1:
                 install_fixed_opponent(runner, fix_opponent_path, ac_space.shape[0], dev, (seed or 0) * 1000 + 17 + rank)
+            league = assign_league(runner, update)
         elif update == 1:
             if not (recurrent and pool is not None):
                 runner.models[1].load(osp.join(checkdir, "00000"))
@@ -346,13 +381,14 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
         history["update_s"].append(tnow - tstart - t_roll)
         history["fps"].append(nbatch * world / (tnow - tstart))
         env_stats_prev, env_note = env_fault_delta(env, env_stats_prev, history)
+        lg_note = league_note(history, runner, league)
         if update_fn is not None:
             update_fn(update)
         if verbose and rank == 0 and (update % log_interval == 0 or update == 1):
             ev = explained_variance(b_val.cpu().numpy(), b_ret.cpu().numpy())
             print("update %d/%d  fps %.0f  rollout %.2fs  sgd %.2fs  ev %.3f  eprewmean %.2f  eplenmean %.1f  %s" % (
                 update, nupdates, history["fps"][-1], t_roll, tnow - tstart - t_roll, ev, safemean([e["r"] for e in epinfobuf]),
-                safemean([e["l"] for e in epinfobuf]), " ".join("%s %.4g" % (n, v) for n, v in zip(model.loss_names, lossvals))) + env_note,
+                safemean([e["l"] for e in epinfobuf]), " ".join("%s %.4g" % (n, v) for n, v in zip(model.loss_names, lossvals))) + lg_note + env_note,
                 flush=True)
         elif env_note and rank == 0:
             print("update %d/%d%s" % (update, nupdates, env_note), flush=True)

@@ -61,6 +61,12 @@ class ZooLstm(C.Structure):
                 ("ob_dim", _I), ("emb_dim", _I), ("hidden", _I)]
 
 
+class ZooLeague(C.Structure):
+    """``sumo_zoo_league`` of include/sumo_hip.h: a zoo MLP table, a zoo LSTM table and the league entry of every 16-env tile of the
+    whole env set (``tile_entry_dev``: device int32 [Ntot / 16]; [0, mlp.nzoo) = MLP row, then the LSTM rows)."""
+    _fields_ = [("mlp", ZooMlp), ("lstm", ZooLstm), ("tile_entry_dev", _P)]
+
+
 def lib():
     global _LIB
     if _LIB is None:
@@ -87,6 +93,8 @@ def lib():
         L.sumo_rollout_steps_zoo_lstm.argtypes = [vp, C.POINTER(Rollout), C.POINTER(ZooLstm)] + [vp] * 8
         L.sumo_rollout_steps_lstm_zoo.argtypes = [vp, C.POINTER(RolloutLstm), C.POINTER(ZooMlp)] + [vp] * 8
         L.sumo_rollout_steps_lstm_zoo_lstm.argtypes = [vp, C.POINTER(RolloutLstm), C.POINTER(ZooLstm)] + [vp] * 8
+        L.sumo_rollout_steps_zoo_league.argtypes = [vp, C.POINTER(Rollout), C.POINTER(ZooLeague)] + [vp] * 8
+        L.sumo_rollout_steps_lstm_zoo_league.argtypes = [vp, C.POINTER(RolloutLstm), C.POINTER(ZooLeague)] + [vp] * 8
         L.sumo_get_state.argtypes = [vp] * 5
         L.sumo_set_cfrc_mode.argtypes = [vp, i32]
         L.sumo_get_cfrc_ext.argtypes = [vp, vp]
@@ -105,14 +113,16 @@ def lib():
         L.sumo_static_layout.restype = i32
         L.sumo_profile.restype = i32
         for n in ("sumo_create", "sumo_destroy", "sumo_dims", "sumo_reset", "sumo_step", "sumo_rollout_steps", "sumo_rollout_steps_lstm", "sumo_match_steps", "sumo_match_steps_lstm",
-                  "sumo_rollout_steps_zoo", "sumo_match_steps_zoo", "sumo_match_steps_zoo_lstm", "sumo_match_steps_lstm_zoo_lstm", "sumo_rollout_steps_zoo_lstm", "sumo_rollout_steps_lstm_zoo", "sumo_rollout_steps_lstm_zoo_lstm", "sumo_get_state", "sumo_set_cfrc_mode", "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_set_state", "sumo_debug_forward", "sumo_stats"):
+                  "sumo_rollout_steps_zoo", "sumo_match_steps_zoo", "sumo_match_steps_zoo_lstm", "sumo_match_steps_lstm_zoo_lstm", "sumo_rollout_steps_zoo_lstm", "sumo_rollout_steps_lstm_zoo", "sumo_rollout_steps_lstm_zoo_lstm",
+                  "sumo_rollout_steps_zoo_league", "sumo_rollout_steps_lstm_zoo_league", "sumo_get_state", "sumo_set_cfrc_mode", "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_set_state", "sumo_debug_forward", "sumo_stats"):
             getattr(L, n).restype = i32
         _LIB = L
     return _LIB
 
 
 EXPORTS = ("sumo_last_error", "sumo_create", "sumo_destroy", "sumo_dims", "sumo_reset", "sumo_step", "sumo_rollout_steps",
-           "sumo_rollout_steps_lstm", "sumo_match_steps", "sumo_match_steps_lstm", "sumo_rollout_steps_zoo", "sumo_match_steps_zoo", "sumo_match_steps_zoo_lstm", "sumo_match_steps_lstm_zoo_lstm", "sumo_rollout_steps_zoo_lstm", "sumo_rollout_steps_lstm_zoo", "sumo_rollout_steps_lstm_zoo_lstm", "sumo_set_cfrc_mode", "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_get_state", "sumo_set_state", "sumo_debug_forward", "sumo_stats", "sumo_profile", "sumo_debug_trace",
+           "sumo_rollout_steps_lstm", "sumo_match_steps", "sumo_match_steps_lstm", "sumo_rollout_steps_zoo", "sumo_match_steps_zoo", "sumo_match_steps_zoo_lstm", "sumo_match_steps_lstm_zoo_lstm", "sumo_rollout_steps_zoo_lstm", "sumo_rollout_steps_lstm_zoo", "sumo_rollout_steps_lstm_zoo_lstm",
+           "sumo_rollout_steps_zoo_league", "sumo_rollout_steps_lstm_zoo_league", "sumo_set_cfrc_mode", "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_get_state", "sumo_set_state", "sumo_debug_forward", "sumo_stats", "sumo_profile", "sumo_debug_trace",
            "sumo_rollout_status", "sumo_debug_fault", "sumo_static_layout", "sumo_debug_layout", "sumo_debug_model_ints", "sumo_debug_dump")
 
 
@@ -163,7 +173,8 @@ class Engine:
 
     def _fused(self, entry, launch, env_ptrs, stream, zoo=None):
         """One fused launch: ``env_ptrs`` are the seven env-side pointers of :meth:`step`, in its order; ``zoo``: the
-        :class:`ZooMlp` / :class:`ZooLstm` table the ``*_zoo`` / ``*_zoo_lstm`` entry points take after the launch struct."""
+        :class:`ZooMlp` / :class:`ZooLstm` table (or :class:`ZooLeague`) the ``*_zoo`` / ``*_zoo_lstm`` / ``*_zoo_league`` entry points take after
+        the launch struct."""
         actions_ptr, obs_ptr, info_ptr, done_ptr, ep_r_ptr, ep_dr_ptr, ep_l_ptr = env_ptrs
         structs = (C.byref(launch),) if zoo is None else (C.byref(launch), C.byref(zoo))
         _chk(getattr(lib(), entry)(self.h, *structs, *env_ptrs, stream))
@@ -221,6 +232,17 @@ class Engine:
         """The same against policy-zoo LSTM nets (``sumo_rollout_steps_lstm_zoo_lstm``); ``zoo`` a filled :class:`ZooLstm`
         (``state``: agent 1's rows of the launch's envs, read and updated in place)."""
         self._fused("sumo_rollout_steps_lstm_zoo_lstm", ro, env_ptrs, stream, zoo)
+
+    def rollout_steps_zoo_league(self, ro, league, *env_ptrs, stream=None):
+        """K fused rollout steps of an MLP learner against a league of policy-zoo nets of both families
+        (``sumo_rollout_steps_zoo_league``); ``ro`` is a filled :class:`Rollout` (``opponent_params`` / ``opponent_index`` None,
+        ``npool`` = the league's size), ``league`` a filled :class:`ZooLeague`."""
+        self._fused("sumo_rollout_steps_zoo_league", ro, env_ptrs, stream, league)
+
+    def rollout_steps_lstm_zoo_league(self, ro, league, *env_ptrs, stream=None):
+        """The same for a recurrent learner (``sumo_rollout_steps_lstm_zoo_league``); ``ro`` is a filled :class:`RolloutLstm`
+        (``opponents_dev`` / ``tile_net_dev`` / ``state1`` None, ``npool`` = the league's size)."""
+        self._fused("sumo_rollout_steps_lstm_zoo_league", ro, env_ptrs, stream, league)
 
     def set_cfrc_mode(self, mode):
         """'zero' (default, the reference's behaviour) or 'rne_post' (include/sumo_hip.h: cfrc_mode)."""

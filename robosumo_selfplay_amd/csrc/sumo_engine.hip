@@ -2571,6 +2571,21 @@ struct ZooTailArgs {
   int sc_off;
   int emb;
 };
+// Leagues of policy-zoo nets of BOTH families (sumo_rollout_steps_zoo_league / sumo_rollout_steps_lstm_zoo_league, POLICY 11 / 12).
+// The launch writes the rollout record, mode 12's learner fills RolloutArgs::lnet and the tail overlay holds one table's fields, so
+// nothing is left to overlay for a second table: these fields are APPENDED to RolloutArgs (no existing field moves, static_assert
+// below RolloutLaunch; the earlier modes never read them).  The LSTM table travels as in mode 10 -- its fields in `l`, its parameter
+// rows in RolloutArgs::opponent, its state rows in RolloutArgs::st1 -- the MLP table here; the entry of every 16-env tile of the
+// whole env set in RolloutArgs::tile_net: [0, nmlp) = that row of the MLP table, [nmlp, nmlp + l.nzoo) = row entry - nmlp of the
+// LSTM table.
+struct ZooLeagueArgs {
+  ZooTailArgs l;
+  const float* mparams;              // [nmlp][Lz.P]
+  const float* mfilt;                // [nmlp][2][Dm]: mean | 1 / std
+  float mclip;
+  int nmlp, Dm;
+  ParamLayout Lz;                    // make_layout(Dm, A)
+};
 struct RolloutArgs {
   const float *learner, *opponent;   // flat parameter vectors; opponent: [npool][P]
   const int32_t* opp_idx;            // [N] snapshot per env or NULL
@@ -2615,6 +2630,7 @@ struct RolloutArgs {
     };
     ZooTailArgs zt;
   };
+  ZooLeagueArgs lg;                  // POLICY 11 / 12 only
 };
 
 // ---- pieces shared by the four policy phases (each reads a / r through the references its phase received) ----
@@ -3360,6 +3376,160 @@ __device__ __forceinline__ void rollout_policy_phase_lstm_zoo(C& c, const SA& a,
   wave_sync();   // the action buffer is read back by the env step (other lanes), the scratch region is the step's again
 }
 
+// ---- rollout against a league of policy-zoo nets, MLP and LSTM mixed (POLICY 11 / 12) ----
+// The league entry of env column `col` (r.tile_net per 16-env tile of the whole env set, NULL = entry 0), checked against the two
+// tables' sizes like every table row (policy_checked_row).  One value per wave: the branch on it is a scalar branch.
+template <class SA, class RA>
+__device__ __forceinline__ int league_entry(const SA& a, const RA& r, int lane, size_t col) {
+  const int je = policy_checked_row(a, lane, r.tile_net ? pt_global(r.tile_net)[col >> 4] : 0, r.lg.nmlp + r.lg.l.nzoo);
+  return __builtin_amdgcn_readfirstlane(je);
+}
+
+// The zoo side of a league step, once the learner has read the raw tile and sampled act0: entry je < nmlp plays the zoo pass of
+// modes 4 / 9 (zoo_trunk_forward on both rows of the tile, filtered in place, hidden tiles behind it), any other entry the zoo pass
+// of modes 8 / 10 (zoo_lstm_mean on row 1 from the env's state row masked by AGENT 1's done flag, then on row 0 from a zero state;
+// cell rows at l.sc_off).  xbuf: x [2][XS] followed by the scratch either pass needs; mL1 / stdL / sumL: the learner's head on row 1.
+// Lanes < A hold their action column.  Every number equals ppo_forward_filtered / ppo_lstm_step, as in those modes.
+template <class SA, class RA>
+__device__ __forceinline__ void league_zoo_pass(const SA& a, const RA& r, int e, int lane, int je, unsigned dn, float* xbuf, int XS, int A,
+                                                float n1, float mL1, float stdL, float sumL, float act0, float& act1, float& onlp0,
+                                                float& onlp1, float& nlp1) {
+  const auto& g = r.lg;
+  const bool ok = lane < A;
+  if (je < g.nmlp) {
+    float* h1 = xbuf + 2 * XS;                       // [2][PT_HS] | h2 [2][PT_HS]
+    float* h2 = h1 + 2 * PT_HS;
+    const float PT_GAS* zp = pt_global(g.mparams) + (size_t)je * g.Lz.P;
+    const f32x4 mO = zoo_trunk_forward<2>(pi_net((const float*)zp, g.Lz), g.mfilt + (size_t)je * 2 * g.Dm, g.mclip, xbuf, XS, g.Dm, h1, h2, lane);
+    const float lsO = ok ? zp[g.Lz.logstd + lane] : 0.0f;
+    const float stdO = expf(lsO), sumO = row16_sum(lsO);
+    onlp0 = gauss_row(mO[0], stdO, sumO, ok, false, 0.0f, act0, A);      // the zoo net scores agent 0's action
+    onlp1 = gauss_row(mO[1], stdO, sumO, ok, true, n1, act1, A);         // the zoo net samples for agent 1 ...
+    nlp1 = gauss_row(mL1, stdL, sumL, ok, false, 0.0f, act1, A);         // ... the learner scores it
+  } else {
+    const auto& q = g.l;
+    const int jz = je - g.nmlp;
+    const float PT_GAS* zp = pt_global(r.opponent) + (size_t)jz * q.Pz;
+    const float* zf = q.filt + (size_t)jz * 2 * q.Dz;
+    float* sc = xbuf + q.sc_off;
+    const float lsO = ok ? zp[q.Pz - A + lane] : 0.0f;   // the row ends with logstd [A]
+    const float stdO = expf(lsO), sumO = row16_sum(lsO);
+    const float keep1 = 1.0f - (float)((dn >> 8) & 0xff);
+    const float mO1 = zoo_lstm_mean<true>(q, zp, zf, r.st1 + (size_t)e * 128, keep1, xbuf + XS, sc, lane);
+    onlp1 = gauss_row(mO1, stdO, sumO, ok, true, n1, act1, A);           // the zoo net samples for agent 1 ...
+    nlp1 = gauss_row(mL1, stdL, sumL, ok, false, 0.0f, act1, A);         // ... the learner scores it
+    wave_sync();   // the cell's rows are rewritten by the scoring pass
+    const float mO0 = zoo_lstm_mean<false>(q, zp, zf, nullptr, 0.0f, xbuf, sc, lane);
+    onlp0 = gauss_row(mO0, stdO, sumO, ok, false, 0.0f, act0, A);        // the zoo net (zero state) scores agent 0's action
+  }
+}
+
+// MLP(64,64) learner against a league (sumo_rollout_steps_zoo_league, POLICY 11): the learner's part of modes 4 / 8 -- policy and
+// value trunks on the raw tile, agent 0's action sampled -- then league_zoo_pass for the tile's entry.
+template <class C, class SA, class RA>
+__device__ __forceinline__ void rollout_policy_phase_zoo_league(C& c, const SA& a, const RA& r, int e, int s) {
+  const int lane = c.lane, i = lane & 15, kq = lane >> 4;
+  const int D = r.L.D, A = r.L.A, XS = r.XS;
+  float* xbuf = (float*)(c.sm + r.lds_off);        // [2][XS] | h1 [2][PT_HS] | h2 [2][PT_HS]
+  float* h1 = xbuf + 2 * XS;
+  float* h2 = h1 + 2 * PT_HS;
+  const size_t col = (size_t)r.env_offset + e;
+  const size_t slot0 = ((size_t)0 * r.T + s) * r.Ntot + col, slot1 = ((size_t)1 * r.T + s) * r.Ntot + col;
+  policy_load_obs<false, true>(a, r, e, lane, xbuf, D, XS, slot0, slot1);
+  const unsigned dn = policy_prev_done(a, e);
+  if (lane < 2) policy_record_done(r, lane, slot0, slot1, dn);
+  wave_sync();
+  const int je = league_entry(a, r, lane, col);
+  const float PT_GAS* lp = pt_global(r.learner);
+  const f32x4 mL4 = trunk_forward<false, 2>(pi_net((const float*)lp, r.L), xbuf, XS, D, h1, h2, lane);
+  const float mL0 = mL4[0], mL1 = mL4[1];
+  wave_sync();
+  const f32x4 vL4 = trunk_forward<false, 2>(vf_net((const float*)lp, r.L), xbuf, XS, D, h1, h2, lane);
+  const float vL0 = vL4[0], vL1 = vL4[1];
+  const bool colk = i < A;
+  const bool ok = colk && kq == 0;                  // rows 0 and 1 live in the first 16 lanes (D layout: rows 4 kq + r)
+  const float lsL = colk ? lp[r.L.logstd + i] : 0.0f;
+  const float stdL = expf(lsL), sumL = row16_sum(lsL);
+  const size_t nz = policy_noise_index(a, e, s, A, i);
+  const float n1 = ok ? pt_global(r.noise1)[nz] : 0.0f;
+  float act0 = 0.0f, act1 = 0.0f;
+  const float nlp0 = gauss_row(mL0, stdL, sumL, ok, true, ok ? pt_global(r.noise0)[nz] : 0.0f, act0, A);   // learner samples for agent 0
+  wave_sync();   // the tile is filtered in place, the hidden tiles are the zoo net's
+  float onlp0, onlp1, nlp1;
+  league_zoo_pass(a, r, e, lane, je, dn, xbuf, XS, A, n1, mL1, stdL, sumL, act0, act1, onlp0, onlp1, nlp1);
+  if (ok) policy_commit_actions<true>(c, a, r, e, i, act0, act1, A, slot0, slot1);
+  if (lane == 0) policy_record_scalars(r, slot0, slot1, nlp0, nlp1, onlp0, onlp1, vL0, vL1);
+  wave_sync();   // the action buffer is read back by the env step (other lanes), the scratch region becomes the mass matrix again
+}
+
+// LSTM(128) learner against a league (sumo_rollout_steps_lstm_zoo_league, POLICY 12): the learner's rows C and E of
+// rollout_policy_phase_lstm_zoo, then league_zoo_pass for the tile's entry.  The learner's block is that function's written out, not
+// a helper both call: moving it into a function is a source change to modes 9 / 10, whose code objects have to stay as they are.
+// Any change to one of the two goes into the other; tests/test_gpu_zoo_league.py compares this mode with the launches
+// tests/test_gpu_lstm_zoo_rollout.py compares modes 9 / 10 with.
+template <int NH, class C, class SA, class RA>
+__device__ __forceinline__ void rollout_policy_phase_lstm_zoo_league(C& c, const SA& a, const RA& r, int e, int s) {
+  const int lane = c.lane;
+  const auto& NL = r.lnet;
+  const int D = NL.ob_dim, A = NL.ac_dim, XS = r.XS;
+  float* xo = (float*)(c.sm + r.lds_off);
+  float* hz = xo + 2 * XS;
+  float* hp = hz + NH;
+  float* hn = hp + NH;
+  const size_t col = (size_t)r.env_offset + e;
+  const size_t slot0 = ((size_t)0 * r.T + s) * r.Ntot + col, slot1 = ((size_t)1 * r.T + s) * r.Ntot + col;
+  policy_load_obs<true, true>(a, r, e, lane, xo, D, XS, slot0, slot1);
+  const unsigned dn = policy_prev_done(a, e);
+  if (lane < 2) policy_record_done(r, lane, slot0, slot1, dn);
+  const float keep0 = 1.0f - (float)(dn & 0xff);
+  float* s0p = r.st0 + (size_t)e * 2 * NH;
+  const int j0 = 2 * lane;                           // lane owns the units 2 lane, 2 lane + 1
+  float c0[2];
+  lstm_state_pair(s0p + j0, keep0, c0);
+  lstm_state_pair(s0p + NH + j0, keep0, hp + j0);
+  hz[j0] = 0.0f; hz[j0 + 1] = 0.0f;
+  wave_sync();
+  const int je = league_entry(a, r, lane, col);
+  const bool ok = lane < A;
+  const size_t nz = policy_noise_index(a, e, s, A, lane);
+  float act0 = 0.0f, act1 = 0.0f;
+  float nlp0, mL1, stdL, sumL, v0, v1;
+  {  // ---- learner net: rows C, E
+    const float fb = NL.forget_bias;
+    float z[4][2][2], bz[4][2];
+    lstm_bias_pair<NH>(pt_global(NL.b), j0, bz);   // (in flight during the gate sums)
+    const float* const xr[2] = {xo, xo + XS};
+    const float* const hr[2] = {hp, hz};
+    lstm_gates_valu<NH, 2>(NL.wx, NL.wh, D, xr, hr, lane, z);
+#pragma unroll
+    for (int u = 0; u < 2; u++) {
+      const int j = j0 + u;
+      const float bi = bz[0][u], bf = bz[1][u] + fb, bo = bz[2][u], bu = bz[3][u];   // gate order i, f, o, u
+      const LstmCell cc = lstm_cell(z[0][u][0], z[1][u][0], z[2][u][0], z[3][u][0], bi, bf, bo, bu, c0[u]);
+      const LstmCell ce = lstm_cell(z[0][u][1], z[1][u][1], z[2][u][1], z[3][u][1], bi, bf, bo, bu, hz[j]);
+      lstm_state_store<NH>(s0p, j, cc);                                              // agent 0's state after the learner's step
+      hn[j] = cc.hn; hn[NH + j] = ce.hn;
+    }
+    wave_sync();
+    float m[2];
+    lstm_heads_valu<NH, 2>(NL.head_w, NL.vf_w, A, hn, lane, m);
+    const float hb = ok ? pt_global(NL.head_b)[lane] : 0.0f, ls = ok ? pt_global(NL.logstd)[lane] : 0.0f;
+    stdL = expf(ls); sumL = row16_sum(ls);
+    const float vb = pt_global(NL.vf_b)[0];
+    v0 = __shfl(m[0], 16) + vb; v1 = __shfl(m[1], 16) + vb;
+    mL1 = m[1] + hb;
+    const float n0 = ok ? pt_global(r.noise0)[nz] : 0.0f;
+    nlp0 = gauss_row(m[0] + hb, stdL, sumL, ok, true, n0, act0, A);      // the learner samples for agent 0
+    wave_sync();   // the raw tile is filtered in place and the latent rows are rewritten by the zoo net's pass
+  }
+  const float n1 = ok ? pt_global(r.noise1)[nz] : 0.0f;
+  float onlp0, onlp1, nlp1;
+  league_zoo_pass(a, r, e, lane, je, dn, xo, XS, A, n1, mL1, stdL, sumL, act0, act1, onlp0, onlp1, nlp1);
+  if (ok) policy_commit_actions<true>(c, a, r, e, lane, act0, act1, A, slot0, slot1);
+  if (lane == 0) policy_record_scalars(r, slot0, slot1, nlp0, nlp1, onlp0, onlp1, v0, v1);
+  wave_sync();   // the action buffer is read back by the env step (other lanes), the scratch region is the step's again
+}
+
 // Match post phase: where agent 0's episode ended in the step, score it from the step's winner flags (info[.][7] bit 0, just
 // written by this lane): a win if agent 0 carries the flag, a loss if only agent 1 does, a draw otherwise (timeouts, diverged states)
 // -- policy_zoo._evaluate_against's rule.  Counted while wins + losses + draws < quota.
@@ -3408,8 +3578,8 @@ static_assert(sizeof(ZooLstmArgs) <= 6 * sizeof(float*) && offsetof(RolloutArgs,
                   offsetof(RolloutArgs, done) == offsetof(RolloutArgs, obs) + 6 * sizeof(float*),
               "ZooLstmArgs overlays the six rollout-record pointers of RolloutArgs: no field moves");
 static_assert(sizeof(ZooTailArgs) <= 4 * sizeof(void*) + 2 * sizeof(int) && offsetof(RolloutArgs, zt) == offsetof(RolloutArgs, snaps) &&
-                  offsetof(RolloutArgs, quota) + sizeof(int) == sizeof(RolloutArgs),
-              "ZooTailArgs (POLICY 9 / 10) overlays the match fields that end RolloutArgs: the struct keeps its size");
+                  offsetof(RolloutArgs, quota) + sizeof(int) == offsetof(RolloutArgs, lg),
+              "ZooTailArgs (POLICY 9 / 10) overlays the match fields of RolloutArgs; the league fields (POLICY 11 / 12) follow them");
 
 // Scheduling: the launch is a set of persistent waves (one per wave slot of the chip) that draw TICKETS from a global counter;
 // ticket t is step t / N of env t % N.  Env steps differ in cost by 3x (contacts, Newton iterations, agents wrestling), so
@@ -3433,6 +3603,8 @@ template <int NV, int POLICY, int SL = 0>   // POLICY 0: MLP(64,64) policy / val
                                             // nets (sumo_match_steps_lstm_zoo_lstm); 8: MLP learner against policy-zoo LSTM
                                             // nets (sumo_rollout_steps_zoo_lstm); 9 / 10: LSTM(128) learner against policy-zoo
                                             // MLP / LSTM nets (sumo_rollout_steps_lstm_zoo / sumo_rollout_steps_lstm_zoo_lstm);
+                                            // 11 / 12: MLP(64,64) / LSTM(128) learner against a league of policy-zoo nets of
+                                            // both families (sumo_rollout_steps_zoo_league / sumo_rollout_steps_lstm_zoo_league);
                                             // SL 1: static Layout
 __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(SUMO_WPE_OF(NV), SUMO_WPE_OF(NV))))
 sumo_rollout_kernel(const Params* P, RolloutLaunch launch_args) {
@@ -3496,6 +3668,8 @@ sumo_rollout_kernel(const Params* P, RolloutLaunch launch_args) {
     else if constexpr (POLICY == 8) rollout_policy_phase_zoo_lstm(c, lp->a, lp->r, e, s);
     else if constexpr (POLICY == 9) rollout_policy_phase_lstm_zoo<128, false>(c, lp->a, lp->r, e, s);
     else if constexpr (POLICY == 10) rollout_policy_phase_lstm_zoo<128, true>(c, lp->a, lp->r, e, s);
+    else if constexpr (POLICY == 11) rollout_policy_phase_zoo_league(c, lp->a, lp->r, e, s);
+    else if constexpr (POLICY == 12) rollout_policy_phase_lstm_zoo_league<128>(c, lp->a, lp->r, e, s);
     else rollout_policy_phase(c, lp->a, lp->r, e, s);
 #ifdef SUMO_DBG_HARD_BARRIER
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -4364,6 +4538,8 @@ static int rollout_launch(sumo_engine* E, const RolloutArgs& r, int policy, cons
                                                        : policy == 8 ? sumo_rollout_kernel<NV, 8, SL>
                                                        : policy == 9 ? sumo_rollout_kernel<NV, 9, SL>
                                                        : policy == 10 ? sumo_rollout_kernel<NV, 10, SL>
+                                                       : policy == 11 ? sumo_rollout_kernel<NV, 11, SL>
+                                                       : policy == 12 ? sumo_rollout_kernel<NV, 12, SL>
                                                                      : sumo_rollout_kernel<NV, 0, SL>;
         hipLaunchKernelGGL(kernel, g_, b_, lds_, st_, E->d_params, rl);
       }))
@@ -4745,6 +4921,62 @@ extern "C" int sumo_rollout_steps_lstm_zoo_lstm(sumo_handle_t E, const sumo_roll
   if (int rc = place_lstm_zoo_rollout(E, ro, od, r)) return rc;   // (the table's checks need the placed scratch: as modes 6-8)
   if (int rc = place_zoo_lstm_table(r, r.zt, z, od, ad, LSTM_ZOO_ROWS * 128)) return rc;   // the cell's rows go where the learner's latent rows were
   return rollout_launch(E, r, 10, b, stream);
+}
+
+// the league of sumo_rollout_steps_zoo_league / sumo_rollout_steps_lstm_zoo_league: the launch's checks of the struct, then -- after
+// the scratch is placed -- both tables into r.lg (the LSTM table as mode 10 travels: place_zoo_lstm_table with the ZooTailArgs)
+static int check_zoo_league(sumo_engine* E, const sumo_zoo_league* z, int npool, int env_offset) {
+  if (z->mlp.nzoo < 1 || z->lstm.nzoo < 1)
+    FAIL(-7, "sumo_zoo_league: nzoo %d (MLP table) / %d (LSTM table): a mixed league needs at least one net of each family (a league of one family plays through that family's launch)", z->mlp.nzoo, z->lstm.nzoo);
+  if (npool != z->mlp.nzoo + z->lstm.nzoo) FAIL(-7, "npool %d must equal the league's size %d + %d", npool, z->mlp.nzoo, z->lstm.nzoo);
+  if (z->tile_entry_dev && ((env_offset & 15) || (E->N & 15))) FAIL(-11, "a league entry per 16-env tile needs env_offset (%d) and the env count (%d) to be multiples of 16", env_offset, E->N);
+  return 0;
+}
+static int place_zoo_league(RolloutArgs& r, const sumo_zoo_league* z, int od, int ad, int rows_floats) {
+  if (int rc = check_zoo_table(&z->mlp, od)) return rc;
+  if (int rc = place_zoo_lstm_table(r, r.lg.l, &z->lstm, od, ad, rows_floats)) return rc;
+  r.lg.mparams = z->mlp.params; r.lg.mfilt = z->mlp.filt; r.lg.mclip = z->mlp.obs_clip; r.lg.nmlp = z->mlp.nzoo; r.lg.Dm = z->mlp.ob_dim;
+  r.lg.Lz = make_layout(z->mlp.ob_dim, ad);
+  r.tile_net = z->tile_entry_dev;
+  return 0;
+}
+
+extern "C" int sumo_rollout_steps_zoo_league(sumo_handle_t E, const sumo_rollout* ro, const sumo_zoo_league* z, float* actions_dev, float* obs_dev,
+                                             double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
+  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
+  if (int rc = check_launch_args(E, ro, b)) return rc;
+  if (!z) FAIL(-1, "bad arguments");
+  if (!ro->learner_params || rollout_buffer_missing(ro)) FAIL(-2, "sumo_rollout: missing buffer");
+  if (ro->opponent_params || ro->opponent_index)
+    FAIL(-2, "sumo_rollout_steps_zoo_league: opponent_params and opponent_index must be NULL (the opponents are the league's nets, selected per tile by tile_entry_dev)");
+  int od = 0, ad = 0;
+  if (int rc = rollout_scene(E, ro->T, ro->Ntot, ro->env_offset, ro->s0, ro->K, &od, &ad)) return rc;
+  if (int rc = check_dims(ro->ob_dim, ro->ac_dim, od, ad)) return rc;
+  if (int rc = check_zoo_league(E, z, ro->npool, ro->env_offset)) return rc;
+  HIPCHK(hipSetDevice(E->device));
+  RolloutArgs r;
+  memset(&r, 0, sizeof r);
+  r.learner = ro->learner_params;
+  copy_rollout_fields(r, ro);
+  if (int rc = place_mlp_scratch(E, ro->ob_dim, ro->ac_dim, r)) return rc;   // the zoo trunk's hidden tiles are the learner's ...
+  if (int rc = place_zoo_league(r, z, od, ad, 4 * PT_HS)) return rc;         // ... and the cell's rows go there too, as in mode 8
+  return rollout_launch(E, r, 11, b, stream);
+}
+
+extern "C" int sumo_rollout_steps_lstm_zoo_league(sumo_handle_t E, const sumo_rollout_lstm* ro, const sumo_zoo_league* z, float* actions_dev,
+                                                  float* obs_dev, double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev,
+                                                  int32_t* ep_l_dev, void* stream) {
+  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
+  if (int rc = check_launch_args(E, ro, b)) return rc;
+  if (!z) FAIL(-1, "bad arguments");
+  RolloutArgs r;
+  int od = 0, ad = 0;
+  if (ro->tile_net_dev) FAIL(-2, "sumo_rollout_steps_lstm_zoo_league: tile_net_dev must be NULL (the league's tile_entry_dev selects the nets)");
+  if (int rc = check_lstm_zoo_rollout(E, ro, z->mlp.nzoo + z->lstm.nzoo, "sumo_rollout_steps_lstm_zoo_league", &od, &ad)) return rc;
+  if (int rc = check_zoo_league(E, z, ro->npool, ro->env_offset)) return rc;
+  if (int rc = place_lstm_zoo_rollout(E, ro, od, r)) return rc;   // LSTM_ZOO_ROWS rows hold the larger of the two zoo passes (static_assert above)
+  if (int rc = place_zoo_league(r, z, od, ad, LSTM_ZOO_ROWS * 128)) return rc;
+  return rollout_launch(E, r, 12, b, stream);
 }
 
 #ifdef SUMO_POLICY_PROBE

@@ -11,7 +11,8 @@ Reference:
 
 MLP and LSTM zoo nets are built (policy.py:23-91 and :94-199); the LSTM one keeps a per-env recurrent state on the device.
 Both families also play inside the fused rollout and match launches from device tables: :class:`ZooTable` (MLP nets) and
-:class:`ZooLstmTable` (LSTM nets, policy branch only).
+:class:`ZooLstmTable` (LSTM nets, policy branch only).  :class:`ZooLeague` deals several nets of either family over the 16-env
+tiles of a training run.
 The ``.npy`` files are loaded with ``numpy.load(allow_pickle=False)``.
 """
 import numpy as np
@@ -608,6 +609,239 @@ def load_zoo_policy_from_flat(flat, ac_dim, device=0, kind=None):
     if kind == "lstm":
         return ZooLSTMPolicy(flat, ac_dim, device=device)
     return ZooMLPPolicy(flat, ac_dim, device=device)
+
+
+# ---- leagues of zoo nets (learn(opponent_mode='fix', fix_opponent_path=[files])) ------------------------------------------------
+LEAGUE_TILE = 16    # envs per tile: the granularity at which the fused launches select a table row (tile_net_dev / tile_entry_dev)
+
+
+def league_plan(nmembers, nenvs, offset=0):
+    """The member every 16-env tile of ``nenvs`` envs faces: int32 [nenvs / 16], tile t -> member (t + offset) % nmembers -- round
+    robin over the tiles, ``offset`` the rotation (``learn`` passes update - 1: every member meets every env region over time).
+    ``ValueError`` for an empty league, ``nenvs`` off the tile grid and fewer tiles than members (some member would not play)."""
+    nmembers, nenvs = int(nmembers), int(nenvs)
+    if nmembers < 1:
+        raise ValueError("a league needs at least one zoo net (got %d)" % nmembers)
+    if nenvs < LEAGUE_TILE or nenvs % LEAGUE_TILE:
+        raise ValueError("a league deals its %d members over tiles of %d envs: nenvs = %d is not a multiple of %d"
+                         % (nmembers, LEAGUE_TILE, nenvs, LEAGUE_TILE))
+    ntiles = nenvs // LEAGUE_TILE
+    if ntiles < nmembers:
+        raise ValueError("a league of %d members needs at least as many 16-env tiles: nenvs = %d gives %d" % (nmembers, nenvs, ntiles))
+    return ((np.arange(ntiles, dtype=np.int64) + int(offset)) % nmembers).astype(np.int32)
+
+
+def league_entries(kinds):
+    """Table entry of every member of a league whose families are ``kinds`` ('mlp' / 'lstm', in file order), in the encoding of
+    include/sumo_hip.h ``sumo_zoo_league``: the MLP members take [0, nmlp) in their order, the LSTM members [nmlp, nmlp + nlstm) in
+    theirs.  Returns (entries int32 [n], nmlp, nlstm)."""
+    kinds = list(kinds)
+    if any(k not in ("mlp", "lstm") for k in kinds):
+        raise ValueError("league families are 'mlp' / 'lstm', got %r" % (kinds,))
+    nmlp = sum(k == "mlp" for k in kinds)
+    seen = {"mlp": 0, "lstm": 0}
+    out = []
+    for k in kinds:
+        out.append(seen[k] + (nmlp if k == "lstm" else 0))
+        seen[k] += 1
+    return np.asarray(out, np.int32), nmlp, len(kinds) - nmlp
+
+
+def league_scores(ep_done, ep_r, ep_l, tile_member, nmembers, timestep_limit=500):
+    """Per-member tally of agent 0's finished episodes of one rollout, from the episode records ``Runner.run`` reads back
+    (``ep_done`` bool / ``ep_r`` / ``ep_l`` [T][N], numpy) and the update's tile assignment (``tile_member`` [N / 16]): int64
+    [nmembers][4] = episodes, learner wins, losses, draws -- an ESTIMATE, a training diagnostic and no evaluator (eval_against_fix.py
+    reads the winner flags).  The record carries no winner flag, so the outcome is read from the
+    episode itself (sumo.py:147-186): longer than ``timestep_limit`` steps = the -1000 timeout, a draw; otherwise the return holds
+    the +2000 / -2000 main reward next to the dense shaping sum (about -1 to -5 per step), and the episode counts as a win if the
+    return is above -1000 and as a loss otherwise.  Known misreadings: a double fall or a diverged episode (main reward 0) counts as
+    a win, a win after hundreds of steps of strongly negative shaping can fall below -1000 and count as a loss, a fall in the very
+    step after the time limit counts as a draw."""
+    d = np.asarray(ep_done).astype(bool)
+    r, l = np.asarray(ep_r, np.float64), np.asarray(ep_l)
+    member = np.repeat(np.asarray(tile_member, np.int64), LEAGUE_TILE)
+    if d.ndim != 2 or member.shape[0] != d.shape[1]:
+        raise ValueError("episode records [T][N] and %d tiles of %d envs do not match" % (len(tile_member), LEAGUE_TILE))
+    out = np.zeros((int(nmembers), 4), np.int64)
+    _, env = np.nonzero(d)
+    m = member[env]
+    draw = l[d] > timestep_limit
+    win = ~draw & (r[d] > -1000.0)
+    for k, sel in enumerate((np.ones_like(draw), win, ~draw & ~win, draw)):
+        np.add.at(out[:, k], m[sel], 1)
+    return out
+
+
+class ZooLeague(object):
+    """A league of zoo nets, MLP and LSTM mixed, as agent 1 of a device-mode ``Runner`` (inside a :class:`FixedOpponentModel`):
+    every 16-env tile of the whole env set faces one member (:func:`league_plan`, re-dealt by :meth:`assign`).  Holds the members
+    (:class:`ZooMLPPolicy` / :class:`ZooLSTMPolicy`, file order), a :class:`ZooTable` of the MLP members and a
+    :class:`ZooLstmTable` of the LSTM members (None where the league has none of that family), each member's table entry
+    (:func:`league_entries`), the per-tile entries on the device (``tile_entry`` int32 [N / 16], and ``env_entry`` [N], the same
+    per env), ONE noise generator for agent 1's action noise of the whole league and the zoo LSTM state ``state`` [N][128] (c | h;
+    only envs on LSTM tiles use their rows; a row is zeroed when its tile changes member).
+
+    :meth:`act` / :meth:`score` are the step-by-step definition of what the fused league launches compute: each member's rows are
+    gathered, evaluated exactly as a single zoo net is, and scattered back."""
+
+    recurrent = False
+    initial_state = None
+
+    def __init__(self, members, nenvs, device=0):
+        import torch
+        self._t = torch
+        self.device = torch.device("cuda", int(device)) if not isinstance(device, torch.device) else device
+        self.members = list(members)
+        if any(type(m) not in (ZooMLPPolicy, ZooLSTMPolicy) for m in self.members):
+            raise ValueError("league members are ZooMLPPolicy / ZooLSTMPolicy objects")
+        if any(type(m) is ZooLSTMPolicy and not (m.emb == m.hidden == HIDDEN) for m in self.members):
+            raise ValueError("the LSTM members of a league have embedding and cell of %d (the league keeps one [N][%d] state for all of them)"
+                             % (HIDDEN, 2 * HIDDEN))
+        self.num_envs = int(nenvs)
+        league_plan(len(self.members), self.num_envs)                 # the size checks, before anything is uploaded
+        self.kinds = ["lstm" if type(m) is ZooLSTMPolicy else "mlp" for m in self.members]
+        self.entries, self.nmlp, self.nlstm = league_entries(self.kinds)
+        self.ac_dim = self.members[0].ac_dim
+        if len({m.ac_dim for m in self.members}) != 1 or len({m.ob_dim for m in self.members}) != 1:
+            raise ValueError("the members of a league share ob_dim and ac_dim")
+        self.ob_dim = self.members[0].ob_dim
+        mlp = [m for m in self.members if type(m) is ZooMLPPolicy]
+        lstm = [m for m in self.members if type(m) is ZooLSTMPolicy]
+        self.mlp_table = ZooTable(mlp, self.ac_dim, self.device) if mlp else None
+        self.lstm_table = ZooLstmTable(lstm, self.ac_dim, self.device) if lstm else None
+        self.gen = torch.Generator(device=self.device)
+        self.state = torch.zeros((self.num_envs, 2 * HIDDEN), dtype=torch.float32, device=self.device)
+        self.tile_member = None
+        self.assign(0)
+
+    def seed(self, s):
+        self.gen.manual_seed(int(s))
+
+    def reset(self, **kwargs):
+        self.state.zero_()
+
+    def assign(self, offset):
+        """Deal the members over the tiles with rotation ``offset`` (:func:`league_plan`); the state rows of tiles that change
+        member are zeroed."""
+        t = self._t
+        plan = league_plan(len(self.members), self.num_envs, offset)
+        if self.tile_member is not None:
+            changed = np.repeat(plan != self.tile_member, LEAGUE_TILE)
+            if changed.any():
+                self.state[t.from_numpy(changed).to(self.device)] = 0.0
+        self.tile_member = plan
+        self.tile_entry = t.from_numpy(self.entries[plan]).to(self.device)
+        self.env_entry = self.tile_entry.repeat_interleave(LEAGUE_TILE).contiguous()
+        env_member = np.repeat(plan, LEAGUE_TILE)
+        self._member_envs = [np.nonzero(env_member == k)[0] for k in range(len(self.members))]
+        self._rows = {}
+
+    def member_rows(self, first_env, n):
+        """[(member, device int64 rows relative to ``first_env``)] for the members that play envs [first_env, first_env + n)."""
+        key = (int(first_env), int(n))
+        if key not in self._rows:
+            out = []
+            for k, envs in enumerate(self._member_envs):
+                sel = envs[(envs >= key[0]) & (envs < key[0] + key[1])] - key[0]
+                if sel.size:
+                    out.append((self.members[k], self._t.from_numpy(sel.astype(np.int64)).to(self.device)))
+            self._rows[key] = out
+        return self._rows[key]
+
+    def struct(self, state):
+        """The ``capi.ZooLeague`` launch struct of a mixed league with the state rows ``state`` of the launch's envs."""
+        from . import capi
+        if self.mlp_table is None or self.lstm_table is None:
+            raise ValueError("the league launch plays MLP and LSTM members side by side; a league of one family plays through that "
+                             "family's launch")
+        z = capi.ZooLeague()
+        z.mlp, z.lstm, z.tile_entry_dev = self.mlp_table.struct(), self.lstm_table.struct(state), self.tile_entry.data_ptr()
+        return z
+
+    def act(self, obs, done, first_env, noise, action, neglogp):
+        """Agent 1's step of envs [first_env, first_env + n): every member acts on its rows of ``obs`` [n, >= ob_dim] with its rows
+        of ``noise`` [n, A] -- an MLP member through ``ppo_forward_filtered`` with the tanh trunk, an LSTM member from its rows of
+        ``self.state``, masked by ``done`` [n] (agent 1's flags of the previous step) and advanced -- into ``action`` / ``neglogp``."""
+        n = obs.shape[0]
+        for m, rows in self.member_rows(first_env, n):
+            o, nz = obs[rows], noise[rows].contiguous()
+            if type(m) is ZooLSTMPolicy:
+                st = self.state[first_env + rows]
+                r = m.evaluate(o, state=st, mask=done[rows], noise=nz)
+                self.state[first_env + rows] = st
+            else:
+                r = m.evaluate(o, ppo_capi.FWD_PI, noise=nz)
+            action[rows] = r["action"]
+            neglogp[rows] = r["neglogp"]
+
+    def score(self, obs, given_action, first_env, neglogp):
+        """Every member's -log pi(given_action | obs) on its rows (an LSTM member: from a zero state, nothing written)."""
+        n = obs.shape[0]
+        for m, rows in self.member_rows(first_env, n):
+            if type(m) is ZooLSTMPolicy:
+                r = m.evaluate(obs[rows], given_action=given_action[rows])
+            else:
+                r = m.evaluate(obs[rows], ppo_capi.FWD_PI, given_action=given_action[rows])
+            neglogp[rows] = r["neglogp"]
+
+    def evaluate(self, obs, flags=None, given_action=None, noise=None, out=None, first_env=0, mask=None):
+        """The policies' ``evaluate`` on device rows of envs [first_env, first_env + n) (what makes a device-mode ``Runner`` of an MLP
+        learner accept the league): :meth:`score` with ``given_action``, else :meth:`act` (``noise`` None: drawn from ``self.gen``;
+        ``mask`` None: no state row is zeroed).  Returns dict(action, neglogp); ``out`` may hold preallocated outputs."""
+        t = self._t
+        n, out = obs.shape[0], out or {}
+        neglogp = out.get("neglogp")
+        if neglogp is None:
+            neglogp = t.empty(n, dtype=t.float32, device=self.device)
+        if given_action is not None:
+            self.score(obs, given_action, first_env, neglogp)
+            return dict(action=given_action, neglogp=neglogp)
+        action = out.get("action")
+        if action is None:
+            action = t.empty((n, self.ac_dim), dtype=t.float32, device=self.device)
+        if noise is None:
+            noise = t.randn((n, self.ac_dim), generator=self.gen, device=self.device, dtype=t.float32)
+        if mask is None:
+            mask = t.zeros(n, dtype=t.uint8, device=self.device)
+        self.act(obs, mask, first_env, noise, action, neglogp)
+        return dict(action=action, neglogp=neglogp)
+
+    # ---- model surface (FixedOpponentModel): whole env set, host or device arrays -----------------------------------------------
+    def _dev(self, x):
+        t = self._t
+        np_in = not t.is_tensor(x)
+        if np_in:
+            x = t.from_numpy(np.ascontiguousarray(np.asarray(x, np.float32))).to(self.device)
+        return x, np_in
+
+    def step(self, observation, S=None, M=None, **extra_feed):
+        """(action, None, None, neglogp) for the whole env set: every member acts on its tiles (host arrays in, host arrays out)."""
+        t = self._t
+        x, np_in = self._dev(observation)
+        if x.shape[0] != self.num_envs:
+            raise ValueError("a league steps its whole env set (%d envs), got %d rows" % (self.num_envs, x.shape[0]))
+        mask = None if M is None else (M if t.is_tensor(M) else t.from_numpy(np.ascontiguousarray(np.asarray(M).reshape(-1), np.uint8)).to(self.device))
+        r = self.evaluate(x, mask=mask)
+        ret = (lambda z: z.cpu().numpy()) if np_in else (lambda z: z)
+        return ret(r["action"]), None, None, ret(r["neglogp"])
+
+    def value(self, ob, *args, **kwargs):
+        raise NotImplementedError("fix mode values agent 1 with the learner; a league has no value of its own")
+
+    def action_probability(self, observation, given_action=None, **extra_feed):
+        x, np_in = self._dev(observation)
+        nlp = self.evaluate(x, given_action=self._dev(given_action)[0].reshape(x.shape[0], self.ac_dim))["neglogp"]
+        return nlp.cpu().numpy() if np_in else nlp
+
+
+def load_zoo_league(paths, ac_dim, nenvs, device=0):
+    """A :class:`ZooLeague` from a sequence of ``.npy`` files (the family of each is read from its length, as :func:`load_zoo_policy`
+    reads it)."""
+    paths = list(paths)
+    if not paths:
+        raise ValueError("a league needs at least one zoo net (got 0 files)")
+    league_plan(len(paths), nenvs)
+    return ZooLeague([load_zoo_policy(p, ac_dim, device=device) for p in paths], nenvs, device=device)
 
 
 class FixedOpponentModel(object):

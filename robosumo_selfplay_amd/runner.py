@@ -110,6 +110,7 @@ class Runner(AbstractEnvRunner):
         self.fused_fix_opponent = False
         self._zoo_table = None
         self.zoo_state = None         # device mode: agent 1's recurrent state [nenv][128] (c | h) when a zoo LSTM net plays it
+        self.league_scores = None     # a league on agent 1: int64 [members][4] of the last rollout (policy_zoo.league_scores)
         self.recurrent = all(getattr(m, "recurrent", False) for m in models)
         self.device_mode = hasattr(env, "step_device") and (self.recurrent or all(
             hasattr(m, "act_model") and hasattr(m.act_model, "evaluate") for m in models))
@@ -493,6 +494,121 @@ class Runner(AbstractEnvRunner):
         v1, n1 = m0.score_and_value(o1, act1)
         B["val"][1, s, sl].copy_(v1); B["nlp"][1, s, sl].copy_(n1)
 
+    # ---- a league of policy-zoo nets on agent 1 (learn(opponent_mode='fix', fix_opponent_path=[files])) -------------------------
+    def league_opponent(self):
+        """The :class:`policy_zoo.ZooLeague` behind ``models[1]`` (device mode), else None.  A league always plays on noise rows
+        drawn for the whole buffer -- one stream per generator, the learner's and the league's -- with or without the opt-in."""
+        from .policy_zoo import FixedOpponentModel, ZooLeague
+        m1 = self.models[1]
+        if self.device_mode and isinstance(m1, FixedOpponentModel) and type(m1.act_model) is ZooLeague:
+            return m1.act_model
+        return None
+
+    def fused_league_ok(self):
+        """The league plays inside the fused launches: the opt-in (``fused_fix_opponent``), ``fused_rollout``, cfrc_mode 'zero', no
+        opponent pool, a plain MLP learner or an ``LstmPPOModel`` with nlstm = 128 of the env's shape, the league dealt over this env set, env groups that start and end on multiples of 16.  A league of one
+        family goes through that family's launch with the index arrays filled, a mixed one through ``sumo_rollout_steps_zoo_league``
+        / ``sumo_rollout_steps_lstm_zoo_league``.  Otherwise the step-by-step league path plays the same noise rows."""
+        league, env = self.league_opponent(), self.env
+        if league is None or not (self.fused_fix_opponent and self.fused_rollout and hasattr(env, "rollout_steps_zoo_league_group")):
+            return False
+        if getattr(env, "cfrc_mode", "zero") != "zero" or self.opponent_pool is not None:
+            return False
+        if league.num_envs != self.nenv:
+            return False
+        if any((env._gs(g).start % 16 or env._gs(g).stop % 16) for g in range(getattr(env, "groups", 1))):
+            return False
+        m0 = self.models[0]
+        if self.recurrent:
+            from .lstm_model import LstmPPOModel
+            sp = m0.spec if type(m0) is LstmPPOModel else None
+            if sp is None or sp.nlstm != 128:
+                return False
+        else:
+            from .policies import PolicyWithValue
+            sp = m0.act_model.spec if type(getattr(m0, "act_model", None)) is PolicyWithValue else None
+            if sp is None:
+                return False
+        return (sp.ob_dim == self.ob_dim and league.ob_dim <= self.ob_dim and sp.ac_dim == league.ac_dim == env.act_dev.shape[2]
+                and env.obs_dev.stride(2) == 1)
+
+    def _draw_league(self, B, n, league):
+        """A group's noise pair for the whole buffer: the learner's rows as its opt-in single-net path draws them (``_draw_zoo`` /
+        ``_draw_lstm_zoo``), agent 1's in one call from the league's generator."""
+        if self.recurrent:
+            return self._draw_lstm_zoo(B, n, self.models[0], league)
+        return self._draw_zoo(B, n, self.models[0].act_model, league)
+
+    def _league_evals(self, B, s, learner, league, o0, o1, dn, sl, nk0, nk1):
+        """The step's evaluations of an MLP learner against a league, step by step: the learner's as in ``_policy_evals`` /
+        ``_zoo_lstm_evals``; every member acts on and scores its own tiles' rows (``ZooLeague.act`` / ``score``)."""
+        PI, VF = ppo_capi.FWD_PI, ppo_capi.FWD_VF
+        act0, act1 = B["act"][0, s, sl], B["act"][1, s, sl]
+        learner.evaluate(o0, PI | VF, out=dict(action=act0, neglogp=B["nlp"][0, s, sl], value=B["val"][0, s, sl]), **nk0)
+        league.score(o0, act0, sl.start, B["onlp"][0, s, sl])
+        league.act(o1, dn[:, 1], sl.start, nk1["noise"], act1, B["onlp"][1, s, sl])
+        learner.evaluate(o1, PI | VF, given_action=act1, out=dict(neglogp=B["nlp"][1, s, sl], value=B["val"][1, s, sl], action=B["scratch_b"][sl]))
+
+    def _lstm_league_evals(self, B, s, m0, league, o0, o1, dn, sl, nk0, nk1):
+        """The same for a recurrent learner: its two evaluations as in ``_lstm_zoo_evals`` (acts from ``self.states[0]``; scores
+        and values agent 1's action from a zero state)."""
+        act0, act1 = B["act"][0, s, sl], B["act"][1, s, sl]
+        a0, v0, S0, n0 = m0.step(o0, S=self.states[0][sl], M=dn[:, 0], **nk0)
+        self.states[0][sl] = S0
+        act0.copy_(a0); B["val"][0, s, sl].copy_(v0); B["nlp"][0, s, sl].copy_(n0)
+        league.score(o0, act0, sl.start, B["onlp"][0, s, sl])
+        league.act(o1, dn[:, 1], sl.start, nk1["noise"], act1, B["onlp"][1, s, sl])
+        v1, n1 = m0.score_and_value(o1, act1)
+        B["val"][1, s, sl].copy_(v1); B["nlp"][1, s, sl].copy_(n1)
+
+    def _steps_fused_league(self, B, s0, K, alpha):
+        """``_steps_fused_zoo`` against a league, MLP learner: one launch per env group -- ``sumo_rollout_steps_zoo_league`` for a
+        mixed league, ``sumo_rollout_steps_zoo`` / ``sumo_rollout_steps_zoo_lstm`` with the per-env ``opponent_index`` for a league
+        of one family.  Same numbers as ``_league_evals`` on the same noise rows, bit for bit."""
+        from . import capi
+        learner, league, env = self.models[0].act_model, self.league_opponent(), self.env
+        D, A = learner.spec.ob_dim, learner.spec.ac_dim
+        mixed = league.nmlp > 0 and league.nlstm > 0
+
+        def fill(ro, sl):
+            ro.learner_params = learner.params.data_ptr()
+            ro.opponent_params, ro.npool = None, len(league.members)
+            ro.opponent_index = None if mixed else league.env_entry[sl].data_ptr()
+            ro.ob_dim, ro.ac_dim = D, A
+
+        if mixed:
+            launch = lambda g, ro: env.rollout_steps_zoo_league_group(g, ro, league.struct(league.state[env._gs(g)]))
+        elif league.nlstm:
+            launch = lambda g, ro: env.rollout_steps_zoo_lstm_group(g, ro, league.lstm_table.struct(league.state[env._gs(g)]))
+        else:
+            zs = league.mlp_table.struct()
+            launch = lambda g, ro: env.rollout_steps_zoo_group(g, ro, zs)
+        self._fused_groups(B, s0, K, alpha, capi.Rollout, lambda n: self._draw_league(B, n, league), fill, launch)
+
+    def _steps_fused_lstm_league(self, B, s0, K, alpha):
+        """``_steps_fused_lstm_zoo`` against a league: ``sumo_rollout_steps_lstm_zoo_league`` for a mixed league,
+        ``sumo_rollout_steps_lstm_zoo`` / ``sumo_rollout_steps_lstm_zoo_lstm`` with ``tile_net_dev`` for a league of one family.
+        Same numbers as ``_lstm_league_evals`` on the same noise rows, bit for bit."""
+        import ctypes as C
+        from . import capi
+        m0, league, env = self.models[0], self.league_opponent(), self.env
+        mixed = league.nmlp > 0 and league.nlstm > 0
+
+        def fill(ro, sl):
+            ro.learner = C.addressof(m0._net)
+            ro.opponents_dev, ro.npool = None, len(league.members)
+            ro.tile_net_dev = None if mixed else league.tile_entry.data_ptr()
+            ro.state0, ro.state1 = self.states[0][sl].data_ptr(), None
+
+        if mixed:
+            launch = lambda g, ro: env.rollout_steps_lstm_zoo_league_group(g, ro, league.struct(league.state[env._gs(g)]))
+        elif league.nlstm:
+            launch = lambda g, ro: env.rollout_steps_lstm_zoo_lstm_group(g, ro, league.lstm_table.struct(league.state[env._gs(g)]))
+        else:
+            zs = league.mlp_table.struct()
+            launch = lambda g, ro: env.rollout_steps_lstm_zoo_group(g, ro, zs)
+        self._fused_groups(B, s0, K, alpha, capi.RolloutLstm, lambda n: self._draw_league(B, n, league), fill, launch)
+
     def join_groups(self):
         """Make the current stream wait for every env group's stream (no-op without groups)."""
         if self._gstreams is not None:
@@ -514,8 +630,20 @@ class Runner(AbstractEnvRunner):
             B["done"][:, s, sl].copy_(dn.t())
         o0, o1 = B["obs"][0, s, sl], B["obs"][1, s, sl]
         act0, act1 = B["act"][0, s, sl], B["act"][1, s, sl]
+        league = self.league_opponent()
         if fused:
             pass
+        elif league is not None:
+            # a league of zoo nets: the noise rows the fused launches (``_steps_fused_league`` / ``_steps_fused_lstm_league``) would
+            # read, drawn for the whole buffer at the group's first step
+            key = ("noise", sl.start)
+            if s == 0 or key not in B:
+                B[key] = self._draw_league(B, n, league)
+            nk0, nk1 = dict(noise=B[key][0][s]), dict(noise=B[key][1][s])
+            if self.recurrent:
+                self._lstm_league_evals(B, s, self.models[0], league, o0, o1, dn, sl, nk0, nk1)
+            else:
+                self._league_evals(B, s, learner, league, o0, o1, dn, sl, nk0, nk1)
         elif self._lstm_vs_zoo():
             # a recurrent learner in fix mode.  Under the opt-in: the noise rows the fused launch (``_steps_fused_lstm_zoo``) would
             # read, drawn for the whole buffer at the group's first step; otherwise each net draws per step from its own generator
@@ -654,10 +782,12 @@ class Runner(AbstractEnvRunner):
             cur = t.cuda.current_stream(self.device)
             for st in self._gstreams:
                 st.wait_stream(cur)
-        fused = self.fused_ok() or self.fused_lstm_ok() or self.fused_zoo_ok() or self.fused_lstm_zoo_ok()
+        fused = self.fused_ok() or self.fused_lstm_ok() or self.fused_zoo_ok() or self.fused_lstm_zoo_ok() or self.fused_league_ok()
         if fused:
             steps = self._steps_fused
-            if self.fused_lstm_zoo_ok():
+            if self.fused_league_ok():
+                steps = self._steps_fused_lstm_league if self.recurrent else self._steps_fused_league
+            elif self.fused_lstm_zoo_ok():
                 steps = self._steps_fused_lstm_zoo
             elif self.recurrent:
                 steps = self._steps_fused_lstm
@@ -695,6 +825,11 @@ class Runner(AbstractEnvRunner):
         d = B["ep_done"].cpu().numpy().astype(bool)
         rr, ll = B["ep_r"].cpu().numpy(), B["ep_l"].cpu().numpy()
         epinfos = EpInfoList(rr[d], ll[d])          # (step, env) order of np.nonzero, dicts built on demand
+        league = self.league_opponent()
+        if league is not None:                      # per member: episodes, learner wins, losses, draws (policy_zoo.league_scores)
+            from .policy_zoo import league_scores
+            self.league_scores = league_scores(d, rr, ll, league.tile_member, len(league.members),
+                                               getattr(getattr(self.env, "model", None), "timestep_limit", 500))
         return (sf01(B["obs"]), sf01(returns), sf01(B["done"].bool()), sf01(B["act"]), sf01(B["val"]), sf01(B["nlp"]), sf01(B["rew"]),
                 sf01(B["onlp"]), sf01(B["obs"][1]), sf01(B["act"][1]), states0, epinfos, sf0(opr), sf0(oer), sf0(ratio))
 

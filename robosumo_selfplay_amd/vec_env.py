@@ -179,6 +179,16 @@ class SumoVecEnv(VecEnv):
         ``capi.ZooLstm`` whose ``state`` holds agent 1's rows of the group's envs)."""
         self.engines[g].rollout_steps_lstm_zoo_lstm(ro, zoo, *self.env_ptrs(g), stream=self._stream())
 
+    def rollout_steps_zoo_league_group(self, g, ro, league):
+        """The MLP learner's launch against a league of policy-zoo nets of both families (``capi.Engine.rollout_steps_zoo_league``,
+        ``league`` a ``capi.ZooLeague`` whose LSTM table's ``state`` holds agent 1's rows of the group's envs)."""
+        self.engines[g].rollout_steps_zoo_league(ro, league, *self.env_ptrs(g), stream=self._stream())
+
+    def rollout_steps_lstm_zoo_league_group(self, g, ro, league):
+        """The recurrent learner's launch against such a league (``capi.Engine.rollout_steps_lstm_zoo_league``, ``ro`` a
+        ``capi.RolloutLstm``)."""
+        self.engines[g].rollout_steps_lstm_zoo_league(ro, league, *self.env_ptrs(g), stream=self._stream())
+
     def step_device(self, actions):
         """actions: float32 CUDA tensor [N, 2, act_stride]. Returns (obs, info, done, ep_r, ep_dr, ep_l) tensors that
         are overwritten by the next call."""

@@ -22,8 +22,12 @@ def parse_unknown(args):
             raise SystemExit("cannot parse extra argument %r (expected --key=value)" % a)
         k, v = a[2:].split("=", 1)
         try:
-            out[k] = ast.literal_eval(v)
+            v = ast.literal_eval(v)
         except (ValueError, SyntaxError):
+            pass
+        if k == "fix_opponent_path" and k in out:      # given several times: a league of policy-zoo nets (one occurrence: a single net)
+            out[k] = (out[k] if isinstance(out[k], list) else [out[k]]) + [v]
+        else:
             out[k] = v
     return out
 

@@ -7,6 +7,9 @@ per launch through the Runner's own drivers (noise draws included), the fused la
     python tools/fix_rollout_bench.py --opponent self       # sumo_rollout_steps (MLP self-play) against ppo_selfplay_forward
     python tools/fix_rollout_bench.py --network lstm --opponent zoo        # sumo_rollout_steps_lstm_zoo: an LSTM(128) learner
     python tools/fix_rollout_bench.py --network lstm --opponent zoo_lstm   # sumo_rollout_steps_lstm_zoo_lstm
+    python tools/fix_rollout_bench.py --opponent league --league-mlp 3 --league-lstm 3   # sumo_rollout_steps_zoo_league against the
+                                                                   # step-by-step league path (--network lstm: sumo_rollout_steps_lstm_zoo_league;
+                                                                   # one of the two counts 0: that family's launch with its index array filled)
 
 Every repeat times `launches` windows of K steps on each path, fused and step by step interleaved, after `warmup` windows; the envs
 keep running from window to window.  Prints one JSON line: env-steps/s per repeat and the median of both paths."""
@@ -27,13 +30,15 @@ def main(argv):
     ap.add_argument("--launches", type=int, default=10, help="timed K-step windows per repeat and path")
     ap.add_argument("--warmup", type=int, default=5, help="untimed K-step windows per path")
     ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--opponent", choices=("self", "zoo", "zoo_lstm"), default="zoo_lstm")
+    ap.add_argument("--opponent", choices=("self", "zoo", "zoo_lstm", "league"), default="zoo_lstm")
+    ap.add_argument("--league-mlp", default="0", help="--opponent league: its zoo MLP members, a count of synthetic nets or a comma-separated list of .npy files")
+    ap.add_argument("--league-lstm", default="0", help="--opponent league: its zoo LSTM members, likewise")
     ap.add_argument("--network", choices=("mlp", "lstm"), default="mlp", help="the learner: MLP(64,64) nets or an LSTM(128) (LstmPPOModel; "
                     "--opponent zoo / zoo_lstm)")
     ap.add_argument("--skip_stepwise", action="store_true")
     args = ap.parse_args(argv)
     if args.network == "lstm" and args.opponent == "self":
-        ap.error("--network lstm measures the fix-mode launches: --opponent zoo or zoo_lstm (tools/lstm_bench.py times recurrent self-play)")
+        ap.error("--network lstm measures the fix-mode launches: --opponent zoo, zoo_lstm or league (tools/lstm_bench.py times recurrent self-play)")
     import numpy as np
     import torch
     from tools.match_bench import _zoo_flat, _zoo_lstm_flat
@@ -57,6 +62,13 @@ def main(argv):
             fixed = policy_zoo.FixedOpponentModel(policy_zoo.ZooMLPPolicy(_zoo_flat(policy_zoo, D - 1, A, rng), A))
         elif args.opponent == "zoo_lstm":
             fixed = policy_zoo.FixedOpponentModel(policy_zoo.ZooLSTMPolicy(_zoo_lstm_flat(policy_zoo, D - 1, A, rng), A))
+        elif args.opponent == "league":
+            def members(arg, synth, load_kind):
+                if arg.isdigit():
+                    return [policy_zoo.load_zoo_policy_from_flat(synth(policy_zoo, D - 1, A, rng), A, kind=load_kind) for _ in range(int(arg))]
+                return [policy_zoo.load_zoo_policy(f, A, kind=load_kind) for f in arg.split(",")]
+            nets = members(args.league_mlp, _zoo_flat, "mlp") + members(args.league_lstm, _zoo_lstm_flat, "lstm")
+            fixed = policy_zoo.FixedOpponentModel(policy_zoo.ZooLeague(nets, args.num_env, env.device))
         if fixed is not None and args.network == "mlp":
             models[1] = fixed
         for k, m in enumerate(models):
@@ -71,7 +83,9 @@ def main(argv):
     def window(r, B, fused):
         if fused:
             steps = r._steps_fused
-            if r.fused_lstm_zoo_ok():
+            if r.fused_league_ok():
+                steps = r._steps_fused_lstm_league if args.network == "lstm" else r._steps_fused_league
+            elif r.fused_lstm_zoo_ok():
                 steps = r._steps_fused_lstm_zoo
             elif r.fused_zoo_ok():
                 steps = r._steps_fused_zoo_lstm if args.opponent == "zoo_lstm" else r._steps_fused_zoo
@@ -84,7 +98,7 @@ def main(argv):
     rs = {f: runner() for f in paths}
     for f, r in rs.items():
         r.fused_rollout = f
-        assert (r.fused_ok() or r.fused_zoo_ok() or r.fused_lstm_zoo_ok()) == f, "the fused launch does not apply"
+        assert (r.fused_ok() or r.fused_zoo_ok() or r.fused_lstm_zoo_ok() or r.fused_league_ok()) == f, "the fused launch does not apply"
     Bs = {f: r._alloc_device(args.K) for f, r in rs.items()}
     rates = {f: [] for f in paths}
     for rep in range(args.repeats + 1):                      # repeat 0 is the warm-up
@@ -104,6 +118,8 @@ def main(argv):
                 E.rollout_status()
         assert r.env.stats()["rollout_aborts"] == 0
     out = dict(network=args.network, opponent=args.opponent, env=args.env, num_env=args.num_env, K=args.K, launches=args.launches, repeats=args.repeats)
+    if args.opponent == "league":
+        out.update(league_mlp=args.league_mlp, league_lstm=args.league_lstm)
     for f in paths:
         name = "fused" if f else "stepwise"
         out[name + "_env_steps_per_s"] = [round(x) for x in rates[f]]

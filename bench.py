@@ -6,10 +6,13 @@ value evaluations of reference runner.py:66-97 (4 fused MFMA launches), one vect
 rules, rewards, done, auto-reset, observation write) and the reward curriculum -- for `--envs` environments per GPU
 (BASELINE configs[1]: RoboSumo Ant-vs-Ant, 4096 envs, MLP(64,64), 1 MI355X).  Inputs are synthetic and resident in HBM:
 random-init networks of the reference architecture (zero-init logstd => N(0,1)-scale actions, the initial policy's law)
-and env states warmed up from the env's own reset distribution.  After the timed region one full PPO2
-update (rollout of --ppo-nsteps + noptepochs x nminibatches optimiser steps) is timed for the "+ PPO2 iters/sec" half
-of the metric and reported under config.  Multi-GPU: one process per GPU (torch.distributed / RCCL), envs sharded with
-no data-path collective -> weak scaling; value = total env-steps of all ranks / max-over-ranks time.
+and env states warmed up from the env's own reset distribution.  A plain run does only that: set up, state
+warm-up, --warmup, the timed --steps, --dump-outputs, the result line.  With --full the run goes on after the timed region:
+one full PPO2 update (rollout of --ppo-nsteps + noptepochs x nminibatches optimiser steps) is timed for the "+ PPO2
+iters/sec" half of the metric and reported under config, then the matrix-core probe, the secondary Spider and recurrent
+lines, the code-object scan and the CPU baselines.  The timed region is the same either way.  Multi-GPU: one process per GPU
+(torch.distributed / RCCL), envs sharded with no data-path collective -> weak scaling; value = total env-steps of all
+ranks / max-over-ranks time.
 
 Prints ONE JSON line (rank 0).
 """
@@ -331,10 +334,13 @@ def main():
                     "each group is stepped on its own stream there)")
     ap.add_argument("--stepwise", action="store_true", help="time the step-by-step launches (ppo_selfplay_forward + sumo_step + ppo_post_step per "
                     "rollout step) instead of the fused rollout launch (sumo_rollout_steps: all timed steps in one launch)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run everything else the benchmark measures or checks: the PPO2 "
+                    "update, the MFMA probe, the Spider and recurrent lines, the code-object scan and the CPU baselines (the options below "
+                    "that name them select among these and act only with --full)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-envs", type=int, default=1024)
     ap.add_argument("--cpu-sample-steps", type=int, default=300)
-    ap.add_argument("--ppo-nsteps", type=int, default=128, help="rollout length of the PPO2 update timed after the main region (0 = skip)")
+    ap.add_argument("--ppo-nsteps", type=int, default=128, help="rollout length of the PPO2 update timed after the main region with --full (0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = the cgroup CPU quota of this job (hostcfg.cpu_quota)")
     ap.add_argument("--no-mfma-probe", action="store_true")
     ap.add_argument("--spider-steps", type=int, default=30, help="timed rollout steps of the secondary Spider-vs-Spider 4096-env line (0 = skip)")
@@ -444,7 +450,7 @@ def main():
     torch.cuda.synchronize(dev)
     st0 = env.stats()
     states = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         q, v, w, c = env.engine.get_state()
         ns = min(args.cpu_sample_envs, env.group_size)
         states = (q[:ns].copy(), v[:ns].copy(), w[:ns].copy(), c[:ns].copy())
@@ -469,11 +475,11 @@ def main():
         timed = [0]
     kern_ms = float(np.mean([ev0[k].elapsed_time(ev1[k]) for k in timed])) if timed else float("nan")   # fused: the K-step launch
     st1 = env.stats()
-    sample_acts = [B["act"][:, k].permute(1, 0, 2).contiguous() for k in range(8)]   # [N, 2, A] per step
+    sample_acts = None if states is None else [B["act"][:, k].permute(1, 0, 2).contiguous() for k in range(8)]   # [N, 2, A] per step
 
-    # ---- "+ PPO2 iters/sec": one full update, outside the timed region above
+    # ---- "+ PPO2 iters/sec": one full update, outside the timed region above (--full)
     ppo = None
-    if args.ppo_nsteps > 0:
+    if args.full and args.ppo_nsteps > 0:
         T, nmb, nep = args.ppo_nsteps, hp["nminibatches"], hp["noptepochs"]
         for timed_update in (False, True):     # the first update pays one-time costs (graph capture, lazy initialisation): untimed
             barrier()
@@ -503,13 +509,13 @@ def main():
                    "samples_per_iter": nb * world}
 
     mfma = None
-    if args.ppo_nsteps > 0 and rank == 0 and not args.no_mfma_probe:
+    if ppo is not None and rank == 0 and not args.no_mfma_probe:
         mfma = mfma_probe(torch, dev, learner, opponent, env, obs_b, ret_b, act_b, val_b, nlp_b, nb // nmb)
     spider = None
-    if args.spider_steps > 0 and rank == 0 and "Ant-vs-Ant" in args.env_id:
+    if args.full and args.spider_steps > 0 and rank == 0 and "Ant-vs-Ant" in args.env_id:
         spider = spider_segment(torch, dev, local_rank, args, hp)
     recurrent = None
-    if args.recurrent_steps > 0 and rank == 0 and "Ant-vs-Ant" in args.env_id:
+    if args.full and args.recurrent_steps > 0 and rank == 0 and "Ant-vs-Ant" in args.env_id:
         recurrent = recurrent_segment(torch, dev, local_rank, args, hp)
     tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
     if dist is not None:
@@ -558,7 +564,7 @@ def main():
                        "rollout_path": "fused: the timed steps are one sumo_rollout_steps launch per env group" if fused else
                                        "stepwise: ppo_selfplay_forward + sumo_step + ppo_post_step launches per step",
                        "ppo2": ppo,
-                       "state_warmup_steps": args.state_warmup,
+                       "full": args.full, "state_warmup_steps": args.state_warmup,
                        "envs_per_gpu": N, "env_groups_per_gpu": env.groups, "total_envs": N * world, "parallelism": "env-shard x%d" % world,
                        "mean_contacts_per_forward": (st1["contacts"] - st0["contacts"]) / nfwd,
                        "mean_newton_iters_per_forward": (st1["newton"] - st0["newton"]) / nfwd,
@@ -598,12 +604,13 @@ def main():
             out["config"]["recurrent"] = recurrent
         # static scan of the code objects this run loaded for the register-allocator defect of DESIGN.md section 4 ("code-generation
         # hazard"): suspicious copies per library (0 = clean), None if the tools are missing
-        try:
-            from robosumo_selfplay_amd import build as _build, codegen_check as _cc
-            out["config"]["codegen_check"] = {name: sum(len(v) for v in _cc.scan_library(_build.lib_path(name)).values())
-                                              for name in ("libsumo_hip.so", "libsumo_ppo.so")}
-        except Exception:
-            out["config"]["codegen_check"] = None
+        if args.full:
+            try:
+                from robosumo_selfplay_amd import build as _build, codegen_check as _cc
+                out["config"]["codegen_check"] = {name: sum(len(v) for v in _cc.scan_library(_build.lib_path(name)).values())
+                                                  for name in ("libsumo_hip.so", "libsumo_ppo.so")}
+            except Exception:
+                out["config"]["codegen_check"] = None
         out["host"] = {"cpu_model": hostcfg.cpu_model(), "os_cpu_count": os.cpu_count(), "cgroup_cpu_quota": hostcfg.cpu_quota(),
                        "pool_threads": hostcfg.apply(),
                        "throttled_periods_in_timed_region": None if thr0 is None or thr1 is None else thr1[0] - thr0[0]}

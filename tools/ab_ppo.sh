@@ -8,7 +8,7 @@ for L in "$@"; do
 done
 for r in $(seq $REPS); do
   for L in "$@"; do
-    SUMO_PPO_LIB=$PWD/$L python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --spider-steps 0 --recurrent-steps 0 2>/dev/null | python3 -c "
+    SUMO_PPO_LIB=$PWD/$L python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --spider-steps 0 --recurrent-steps 0 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 p=d['config']['ppo2']; m=d.get('roofline_mfma',{})

@@ -13,6 +13,7 @@
  *   ppo_vtrace                  Runner.run IS ratios + V-trace targets (runner.py:166-196)
  *   ppo_adv_moments/_normalize  PPOModel.train advantage normalisation (model.py:180-185); split in two so a
  *                               multi-GPU run can all-reduce the three moments in between
+ *   ppo_selection_scores        the 'ours' opponent selector's candidate scores (alg_ppo.py:227-244), all candidates in one launch
  *   ppo_grad                    loss + gradients of model.py:65-132 (sums, not means: divide by the global count)
  *   ppo_a2c_grad / _loss_stats  loss + gradients and statistics of ActorCriticModel (model.py:257-310)
  *   ppo_clip_adam               tf.clip_by_global_norm + tf.train.AdamOptimizer(epsilon=1e-5).apply_gradients
@@ -182,6 +183,22 @@ int ppo_adv_moments_ws(const float* returns, const float* values, const int32_t*
 int ppo_adv_moments(const float* returns, const float* values, const int32_t* idx, int n, double* moments, void* stream);
 int ppo_adv_normalize(const float* returns, const float* values, const int32_t* idx, int n, const double* moments,
                       float* adv_out, void* stream);
+
+/* Scores of the 'ours' opponent selector (alg_ppo.py:227-244) for ncand (1..32) candidates in ONE launch.  obs [n][obs_stride] and
+ * actions [n][ac_dim] are the opponent's samples of the last rollout; ref_params is the net that produced them, table holds frozen
+ * nets as rows of table_stride floats in the layout of `params` (matches.SnapshotTable), cand_rows DEVICE int32 [ncand] the rows to
+ * score (any order, repeats allowed).  With ap / nap the reference's / a candidate's neglogp of the given action -- the same trunk
+ * and the same neglogp expression as ppo_forward, equal to its values bit for bit as tests/test_gpu_selector.py verifies, not by
+ * shared code alone -- r = nap / ap - 1 in float32 per row; rows where r is not finite, or whose observation holds a NaN,
+ * are left out; score_sum double [ncand] receives the sum of |r| over the others and finite_count int32 [ncand] their number (the
+ * selector's score is their quotient).  neglogp_dbg (may be NULL) float32 [ncand + 1][n]: every neglogp, row 0 = the reference net.
+ * Deterministic: a fixed summation order for a given n and grid; max_blocks > 0 caps the grid (0 = sized from the device).
+ * workspace: ppo_selection_scores_workspace_bytes() bytes, ZERO-INITIALISED once by the caller, one call in flight per workspace.
+ * Argument errors (ncand outside 1..32, n < 1, ob_dim / ac_dim outside ppo_forward's range) return before anything is launched. */
+size_t ppo_selection_scores_workspace_bytes(void);
+int ppo_selection_scores(const float* ref_params, const float* table, int table_stride, const int32_t* cand_rows, int ncand,
+                         const float* obs, int n, int obs_stride, int ob_dim, int ac_dim, const float* actions,
+                         double* score_sum, int32_t* finite_count, float* neglogp_dbg, int max_blocks, void* workspace, void* stream);
 
 /* Gradient of the PPO loss over minibatch rows idx[0..n): grads float32 [P] receives d(sum-loss)/d(theta) with
  * sum-loss = sum_i w_i*pg_i + vf_coef * sum_i 0.5 (v_i-R_i)^2 - n_local*ent_coef*entropy, where every per-row term

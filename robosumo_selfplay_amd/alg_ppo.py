@@ -17,7 +17,8 @@ import numpy as np
 
 from . import dist as sdist
 from .model import PPOModel
-from .policies import build_policy
+from .policies import build_policy, init_param_list
+from .policy_selector import selection_probs_from_scores
 from .runner import Runner
 
 
@@ -86,9 +87,7 @@ def selection_probs(action_prob, new_action_probs):
         r = nap / action_prob - 1.0
         r = r[torch.isfinite(r)]           # a probability that underflowed to 0 in float32 (sharp late-training policies) gives inf / NaN here;
         return float(r.abs().mean().item()) if r.numel() else 0.0      # the reference would pass NaN to np.random.choice and stop -- those samples are left out
-    rd = np.array([score(nap) for nap in new_action_probs])
-    tot = rd.sum()
-    return rd / tot if np.isfinite(tot) and tot > 0 else np.full(len(rd), 1.0 / len(rd))
+    return selection_probs_from_scores(np.array([score(nap) for nap in new_action_probs]))
 
 
 def install_fixed_opponent(runner, fix_opponent_path, ac_dim, dev, seed):
@@ -143,6 +142,17 @@ def check_opponent_pool(opponent_mode, runner, fused):
         raise NotImplementedError("opponent_pool > 1 with MLP policies runs inside the fused rollout launch (SUMO_FUSED_ROLLOUT != 0)")
 
 
+def check_fused_selector(network, opponent_mode, model_fn):
+    """What ``fused_selector=True`` refuses, before anything touches the env or the device: the selector's table holds MLP(64,64)
+    policies as flat parameter vectors and serves the 'ours' mode, the only one that scores candidates."""
+    if network == "lstm":
+        raise ValueError("fused_selector scores MLP(64,64) checkpoints: not available with network='lstm'")
+    if opponent_mode != "ours":
+        raise ValueError("fused_selector serves opponent_mode='ours' (the other modes score no candidates); got %r" % (opponent_mode,))
+    if model_fn is not None and not (isinstance(model_fn, type) and issubclass(model_fn, PPOModel)):
+        raise ValueError("fused_selector needs models with a flat ``params`` vector (PPOModel and its subclasses), not a custom model_fn")
+
+
 def upload(dev, *arrays):
     """The arrays of a host-mode Runner (recurrent models), moved to the device so that the update continues there like the MLP path."""
     import torch
@@ -168,7 +178,10 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
           ent_coef=0.0, lr=3e-4, vf_coef=0.5, max_grad_norm=0.5, gamma=0.99, lam=0.95, rho_bar=1.0, c_bar=1.0, log_interval=10,
           nminibatches=4, noptepochs=4, cliprange=0.2, save_interval=1, load_path=None, model_fn=None, update_fn=None, init_fn=None,
           nagent=1, anneal_bound=500, vgap=None, kl_threshold=None, neglogp_threshold=10000.0, log_dir=None, comm=None,
-          verbose=True, fix_opponent_path=None, opponent_pool=1, fused_fix_opponent=False, **network_kwargs):
+          verbose=True, fix_opponent_path=None, opponent_pool=1, fused_fix_opponent=False, fused_selector=False, selector_table_mb=1024,
+          **network_kwargs):
+    if fused_selector:
+        check_fused_selector(network, opponent_mode, model_fn)
     import torch
     if seed is not None:                                                # set_global_seeds (misc_util.py:48-62)
         np.random.seed(seed)
@@ -199,11 +212,31 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
     model.equal_counts = use_opponent_data is None      # opponent-data reuse makes per-rank minibatch sizes differ
     sdist.broadcast_params(model.params, comm)                          # sync_from_root (ppo2/model.py:129-131)
     models = [model] + [mk("model_%d" % i, False) for i in range(1, nagent)]
-    model_util = mk("model_util", False)
     log_dir = log_dir or os.environ.get("OPENAI_LOGDIR") or "/tmp/robosumo_selfplay_amd"
     checkdir = osp.join(log_dir, "checkpoints")
+    nupdates = total_timesteps // nbatch
+    selector = None
+    if not fused_selector:
+        model_util = mk("model_util", False)
+    else:
+        # the candidates live in a device table and are scored in one launch (policy_selector.py); no scratch model is built, but the
+        # initial-weight draws that PPOModel's own constructor makes (one init_param_list) are still taken from numpy's global stream,
+        # so with PPOModel both settings make the same opponent draws.  A subclass whose constructor draws more than that passes
+        # check_fused_selector but loses this alignment: its fused run is a valid run on another random stream.
+        from .policy_selector import FusedSelector
+        init_param_list(policy.ob_dim, policy.ac_dim)
+        names = set(os.listdir(checkdir)) if osp.isdir(checkdir) else set()      # a run directory may already hold checkpoints
+        # history mode takes its whole table (one row per checkpoint of the run, at most selector_table_mb) here, before the first update
+        selector = FusedSelector(policy, dev, len(names | set("%.5i" % u for u in range(nupdates + 1))), table_mb=selector_table_mb)
+
+    def save_checkpoint(name):
+        path = osp.join(checkdir, name)
+        model.save(path)
+        if selector is not None:
+            selector.note_saved(sorted(os.listdir(checkdir)).index(name), model, path)
+
     if rank == 0:
-        model.save(osp.join(checkdir, "00000"))                          # alg_ppo.py:122-123
+        save_checkpoint("00000")                                         # alg_ppo.py:122-123
     if comm is not None:
         torch.distributed.barrier(comm)
     if load_path is not None:
@@ -241,7 +274,6 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
                    env_diverged=[], env_dropped_contacts=[], env_rollout_aborts=[],     # per update, from the engine's counters
                    league_scores=[], league_tiles=[])       # fix mode with a list of files: per update and member (league_note)
     env_stats_prev = env.stats() if hasattr(env, "stats") else None
-    nupdates = total_timesteps // nbatch
     idx_choice = 0
     opponent_obs = opponent_actions = None
     league = None
@@ -275,13 +307,17 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
                 choices = list(range(len(paths) - 1, max(-1, len(paths) - 1 - K), -1))
             elif opponent_mode == "ours":                                # ratio-divergence sampling (:227-244)
                 ref = opp_ref if (recurrent and pool is not None) else runner.models[1]
-                ap = ref.act_model.action_probability(opponent_obs, given_action=opponent_actions)
                 sub = np.sort(np.random.choice(len(paths), 30, replace=False)) if len(paths) > 30 else np.arange(len(paths))
-                naps = []
-                for i in sub:
-                    model_util.load(paths[i])
-                    naps.append(model_util.act_model.action_probability(opponent_obs, given_action=opponent_actions))
-                rd = selection_probs(ap, naps)
+                if selector is not None:
+                    selector.ensure(paths, sub)
+                    rd = selection_probs_from_scores(selector.scores(ref.params, sub, opponent_obs, opponent_actions))
+                else:
+                    ap = ref.act_model.action_probability(opponent_obs, given_action=opponent_actions)
+                    naps = []
+                    for i in sub:
+                        model_util.load(paths[i])
+                        naps.append(model_util.act_model.action_probability(opponent_obs, given_action=opponent_actions))
+                    rd = selection_probs(ap, naps)
                 choices = [int(sub[j]) for j in np.random.choice(len(rd), K, p=rd)]
             else:
                 raise ValueError("opponent_mode %r" % (opponent_mode,))
@@ -393,7 +429,7 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
         elif env_note and rank == 0:
             print("update %d/%d%s" % (update, nupdates, env_note), flush=True)
         if save_interval and (update % save_interval == 0 or update == 1) and rank == 0:
-            model.save(osp.join(checkdir, "%.5i" % update))               # alg_ppo.py:459-464
+            save_checkpoint("%.5i" % update)                              # alg_ppo.py:459-464
         if comm is not None:
             sdist.assert_synced(model.params, comm)                       # MpiAdamOptimizer.check_synced (mpi_adam_optimizer.py:54-67)
             torch.distributed.barrier(comm)

@@ -12,6 +12,7 @@
 // model.py:65-139 (loss, gradient clipping, Adam), model.py:180-185 (advantage normalisation), runner.py:127-143,166-196
 // (reward curriculum, IS ratios, V-trace).
 #include <hip/hip_runtime.h>
+#include <float.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -1407,6 +1408,179 @@ extern "C" int ppo_adv_normalize(const float* returns, const float* values, cons
   if (!returns || !values || !moments || !adv_out || n <= 0) FAIL(-1, "bad arguments");
   hipLaunchKernelGGL(ppo_adv_normalize_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, returns, values, idx, n, moments,
                      adv_out);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Scores of the 'ours' opponent selector (alg_ppo.py:227-244) for up to 32 candidates in ONE launch: a persistent grid of waves strides
+// over the 16-row tiles of the opponent's (obs, action) samples; a wave stages its tile once (stage_x, the row stride of
+// ppo_forward_kernel), evaluates the reference net and then every candidate row of the snapshot table on it -- trunk_forward, which
+// ppo_forward_kernel calls too, then gauss_row, which holds the same neglogp expression as ppo_forward_kernel's inline copy (shared
+// code does not make the two contract alike: tests/test_gpu_selector.py compares every neglogp with that launch's as bit patterns)
+// -- and adds |nap / ap - 1| of the rows where that
+// is finite to its per-candidate float64 sum and int32 count (in LDS: the candidate index is a loop variable).  A workgroup adds its
+// waves' partials in wave order into its slot of the caller's workspace; the last workgroup to arrive adds the slots in slot order
+// (ppo_adv_moments_kernel's scheme), so the result depends on the grid alone, not on which workgroup finishes last.
+// A row whose observation holds a NaN counts as not finite for every net: relu is fmaxf, which returns 0 for a NaN, so the trunk
+// would hand such a row a finite, meaningless neglogp.
+// ---------------------------------------------------------------------------------------------------------
+#define SEL_MAX_CAND 32
+#define SEL_MAX_BLOCKS 1024
+struct SelWs { double sum[SEL_MAX_BLOCKS * SEL_MAX_CAND]; int32_t cnt[SEL_MAX_BLOCKS * SEL_MAX_CAND]; unsigned int arrived; unsigned int pad[3]; };
+struct SelArgs {
+  const float *ref, *table, *obs, *actions;
+  const int32_t* cand_rows;
+  double* score_sum;
+  int32_t* finite_count;
+  float* dbg;
+  SelWs* ws;
+  int table_stride, ncand, n, obs_stride, XS;
+  ParamLayout L;
+};
+
+__global__ void __launch_bounds__(256) ppo_selection_scores_kernel(SelArgs a) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const int XS = a.XS, D = a.L.D, A = a.L.A, n = a.n, ncand = a.ncand;
+  const int tile_floats = 16 * XS + 2 * 16 * HS;
+  float* base = smem_f + wid * tile_floats;
+  float *xbuf = base, *h1 = base + 16 * XS, *h2 = h1 + 16 * HS;
+  double* acc_sum = (double*)(smem_f + nw * tile_floats);          // [nw][SEL_MAX_CAND]; the tile buffers are a multiple of 16 bytes
+  int32_t* acc_cnt = (int32_t*)(acc_sum + nw * SEL_MAX_CAND);      // [nw][SEL_MAX_CAND]
+  double* my_sum = acc_sum + wid * SEL_MAX_CAND;
+  int32_t* my_cnt = acc_cnt + wid * SEL_MAX_CAND;
+  const int i = lane & 15, kq = lane >> 4;
+  const bool col = i < A;
+  if (lane < SEL_MAX_CAND) { my_sum[lane] = 0.0; my_cnt[lane] = 0; }
+  const int tiles = (n + 15) / 16;
+  for (int tile = blockIdx.x * nw + wid; tile < tiles; tile += gridDim.x * nw) {
+    const int r0 = tile * 16;
+    wave_sync();   // the previous tile's trunks have read xbuf
+    stage_x(xbuf, XS, a.obs, a.obs_stride, D, nullptr, r0, n, lane);
+    wave_sync();
+    int nan_row = 0;   // row i of the tile holds a NaN (lanes kq = 0 .. 3 look at every fourth column)
+    for (int k = kq; k < D; k += 4) { const float v = xbuf[i * XS + k]; nan_row |= (v != v); }
+    nan_row |= __shfl_xor(nan_row, 16, WAVE); nan_row |= __shfl_xor(nan_row, 32, WAVE);
+    float act[4], ap[4];
+    bool rowok[4];
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int row = r0 + 4 * kq + r;
+      rowok[r] = row < n && !__shfl(nan_row, 4 * kq + r, WAVE);
+      act[r] = (col && row < n) ? a.actions[(size_t)row * A + i] : 0.0f;
+      ap[r] = 0.0f;
+    }
+#pragma nounroll
+    for (int c = -1; c < ncand; c++) {   // -1: the reference net
+      const float* p = c < 0 ? a.ref : a.table + (size_t)a.cand_rows[c] * a.table_stride;
+      const Net net = pi_net(p, a.L);
+      const f32x4 mean = trunk_forward<false>(net, xbuf, XS, D, h1, h2, lane);
+      const float logstd = col ? pt_global(p)[a.L.logstd + i] : 0.0f;
+      const float std = expf(logstd);
+      const float sum_logstd = row16_sum(logstd);
+      double s = 0.0;
+      int cnt = 0;
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const int row = r0 + 4 * kq + r;
+        const float nlp = gauss_row(mean[r], std, sum_logstd, col && row < n, false, 0.0f, act[r], A);
+        if (a.dbg && i == 0 && row < n) a.dbg[(size_t)(c + 1) * n + row] = nlp;
+        if (c < 0) ap[r] = nlp;
+        else {
+          const float ratio = nlp / ap[r] - 1.0f;
+          if (rowok[r] && fabsf(ratio) <= FLT_MAX) { s += (double)fabsf(ratio); cnt++; }   // (false for NaN and inf)
+        }
+      }
+      if (c >= 0) {   // the tile's 16 rows: r ascending inside a lane group, then the four groups by a butterfly (a fixed tree)
+        s += __shfl_xor(s, 16, WAVE); s += __shfl_xor(s, 32, WAVE);
+        cnt += __shfl_xor(cnt, 16, WAVE); cnt += __shfl_xor(cnt, 32, WAVE);
+        if (lane == 0) { my_sum[c] += s; my_cnt[c] += cnt; }
+      }
+      wave_sync();   // h1 / h2 are free for the next net
+    }
+  }
+  __syncthreads();
+  if (wid != 0) return;
+  // wave 0: the workgroup's partial per candidate (waves in order) -> its workspace slot (sc1: visible to every XCD), then count in
+  const int c = lane;
+  if (c < ncand) {
+    double s = 0.0;
+    int cnt = 0;
+    for (int w = 0; w < nw; w++) { s += acc_sum[w * SEL_MAX_CAND + c]; cnt += acc_cnt[w * SEL_MAX_CAND + c]; }
+    __hip_atomic_store(&a.ws->sum[blockIdx.x * SEL_MAX_CAND + c], s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&a.ws->cnt[blockIdx.x * SEL_MAX_CAND + c], cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  unsigned int arrived = 0;
+  if (lane == 0) arrived = __hip_atomic_fetch_add(&a.ws->arrived, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  arrived = __shfl(arrived, 0, WAVE);
+  if (arrived != gridDim.x - 1) return;
+  if (c < ncand) {
+    double s = 0.0;
+    int cnt = 0;
+    for (unsigned int b0 = 0; b0 < gridDim.x; b0 += 8) {   // eight slots in flight at a time, added in slot order
+      double vs[8];
+      int vc[8];
+#pragma unroll
+      for (unsigned int k = 0; k < 8; k++) {
+        const unsigned int b = b0 + k < gridDim.x ? b0 + k : b0;
+        vs[k] = __hip_atomic_load(&a.ws->sum[b * SEL_MAX_CAND + c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        vc[k] = __hip_atomic_load(&a.ws->cnt[b * SEL_MAX_CAND + c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+#pragma unroll
+      for (unsigned int k = 0; k < 8; k++)
+        if (b0 + k < gridDim.x) { s += vs[k]; cnt += vc[k]; }
+    }
+    a.score_sum[c] = s;
+    a.finite_count[c] = cnt;
+  }
+  if (lane == 0) __hip_atomic_store(&a.ws->arrived, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next call
+}
+
+extern "C" size_t ppo_selection_scores_workspace_bytes(void) { return sizeof(SelWs); }
+extern "C" int ppo_selection_scores(const float* ref_params, const float* table, int table_stride, const int32_t* cand_rows, int ncand,
+                                    const float* obs, int n, int obs_stride, int ob_dim, int ac_dim, const float* actions,
+                                    double* score_sum, int32_t* finite_count, float* neglogp_dbg, int max_blocks, void* workspace,
+                                    void* stream) {
+  if (!ref_params || !table || !cand_rows || !obs || !actions || !score_sum || !finite_count || !workspace) FAIL(-1, "bad arguments");
+  if (ncand < 1 || ncand > SEL_MAX_CAND) FAIL(-5, "ncand %d not in [1,%d]", ncand, SEL_MAX_CAND);
+  if (n < 1) FAIL(-1, "n %d < 1", n);
+  if (ac_dim < 1 || ac_dim > MAXA) FAIL(-2, "ac_dim %d not in [1,%d]", ac_dim, MAXA);
+  if (ob_dim < 1 || ob_dim > 512 || obs_stride < ob_dim) FAIL(-3, "bad ob_dim/obs_stride");
+  if (max_blocks < 0) FAIL(-1, "max_blocks %d < 0", max_blocks);
+  SelArgs a;
+  a.L = make_layout(ob_dim, ac_dim);
+  if (table_stride < a.L.P) FAIL(-6, "table_stride %d below the %d parameters of a row", table_stride, a.L.P);
+  a.ref = ref_params; a.table = table; a.obs = obs; a.actions = actions; a.cand_rows = cand_rows; a.score_sum = score_sum;
+  a.finite_count = finite_count; a.dbg = neglogp_dbg; a.ws = (SelWs*)workspace; a.table_stride = table_stride; a.ncand = ncand; a.n = n;
+  a.obs_stride = obs_stride; a.XS = x_stride(ob_dim);
+  // waves per workgroup: four where two such workgroups fit the CU's 160 KB of LDS (ob_dim <= 160), else two (<= 480), else one
+  const size_t wave_lds = (size_t)(16 * a.XS + 2 * 16 * HS) * sizeof(float), acc_lds = SEL_MAX_CAND * (sizeof(double) + sizeof(int32_t));
+  int wpb = 4;
+  while (wpb > 1 && 2 * wpb * (wave_lds + acc_lds) > 160 * 1024) wpb >>= 1;
+  const size_t lds = wpb * (wave_lds + acc_lds);
+  // the CU count and the raised dynamic-LDS limit belong to a device: both are looked up again when the thread's device changes
+  static thread_local int cached_dev = -1, cus = 0;
+  static thread_local size_t lds_set = 0;
+  int dev = 0;
+  HIPCHK(hipGetDevice(&dev));
+  if (dev != cached_dev) {
+    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    cached_dev = dev;
+    lds_set = 0;
+  }
+  const int tiles = (n + 15) / 16;
+  int per_cu = (int)((160 * 1024) / lds);                       // resident workgroups per CU by LDS, at most eight waves
+  if (per_cu * wpb > 8) per_cu = 8 / wpb;
+  int grid = (tiles + wpb - 1) / wpb;
+  if (grid > cus * per_cu) grid = cus * per_cu;
+  if (grid > SEL_MAX_BLOCKS) grid = SEL_MAX_BLOCKS;
+  if (max_blocks > 0 && grid > max_blocks) grid = max_blocks;
+  if (lds > 64 * 1024 && lds > lds_set) {
+    HIPCHK(hipFuncSetAttribute((const void*)ppo_selection_scores_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    lds_set = lds;
+  }
+  hipLaunchKernelGGL(ppo_selection_scores_kernel, dim3(grid), dim3(64 * wpb), lds, (hipStream_t)stream, a);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -11,7 +11,7 @@ _LIB = None
 
 EXPORTS = ("ppo_last_error", "ppo_param_count", "ppo_forward", "ppo_forward_filtered", "ppo_lstm_step", "ppo_lstm_step_pool", "ppo_lstm_step_save", "ppo_lstm_xproj", "ppo_lstm_step_save_z", "ppo_lstm_seq_forward", "ppo_lstm_seq_backward", "ppo_lstm_head_grad", "ppo_lstm_bwd_step", "ppo_lstm_wgrad_workspace_bytes", "ppo_lstm_wgrad", "ppo_selfplay_forward", "ppo_post_step", "ppo_reward_mix", "ppo_vtrace", "ppo_adv_moments", "ppo_adv_moments_ws", "ppo_adv_moments_workspace_bytes",
            "ppo_adv_normalize", "ppo_grad_workspace_bytes", "ppo_grad", "ppo_loss_stats", "ppo_clip_adam",
-           "ppo_a2c_grad", "ppo_a2c_loss_stats")
+           "ppo_a2c_grad", "ppo_a2c_loss_stats", "ppo_selection_scores_workspace_bytes", "ppo_selection_scores")
 
 
 class PpoHipError(RuntimeError):
@@ -74,9 +74,13 @@ def lib():
         L.ppo_loss_stats.argtypes = [vp, vp, i32, vp, vp]
         L.ppo_a2c_grad.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, f64, f32, f32, vp, vp, vp, vp]
         L.ppo_a2c_loss_stats.argtypes = [vp, vp, i32, vp, vp]
+        L.ppo_selection_scores_workspace_bytes.argtypes = []
+        L.ppo_selection_scores_workspace_bytes.restype = C.c_size_t
+        L.ppo_selection_scores.argtypes = [vp, vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp]
         L.ppo_clip_adam.argtypes = [vp, vp, vp, vp, i32, i32, f64, f64, f64, f64, f64, vp, vp]
         for n in EXPORTS:
-            if n not in ("ppo_last_error", "ppo_grad_workspace_bytes", "ppo_lstm_wgrad_workspace_bytes", "ppo_adv_moments_workspace_bytes"):
+            if n not in ("ppo_last_error", "ppo_grad_workspace_bytes", "ppo_lstm_wgrad_workspace_bytes", "ppo_adv_moments_workspace_bytes",
+                         "ppo_selection_scores_workspace_bytes"):
                 getattr(L, n).restype = i32
         _LIB = L
     return _LIB

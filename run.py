@@ -32,7 +32,7 @@ def parse_unknown(args):
     return out
 
 
-def main(argv):
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--env", default="RoboSumo-Ant-vs-Ant-v0")
     ap.add_argument("--seed", type=int, default=42)
@@ -52,7 +52,17 @@ def main(argv):
     ap.add_argument("--fused_fix_opponent", action="store_true", help="opponent_mode=fix: play the policy-zoo net (MLP or LSTM file) inside the fused "
                     "rollout launch (sumo_rollout_steps_zoo / sumo_rollout_steps_zoo_lstm; --network lstm: sumo_rollout_steps_lstm_zoo / sumo_rollout_steps_lstm_zoo_lstm).  Opt-in: the action noise is drawn per rollout buffer instead of per step, "
                     "so the same seed gives another, equally valid random stream")
-    args, unknown = ap.parse_known_args(argv)
+    ap.add_argument("--fused_selector", action="store_true", help="opponent_mode=ours with MLP policies: keep the run's checkpoints in a device table "
+                    "and score the selector's candidates in one launch per update (policy_selector.FusedSelector) instead of one file read and one "
+                    "forward launch per candidate.  Opt-in; --algo ppo only")
+    ap.add_argument("--selector_table_mb", type=float, default=None, help="--fused_selector: device memory the checkpoint table may take, in MiB "
+                    "(default 1024).  A run whose checkpoints fit gets one row per checkpoint, allocated before the first update; a longer run, "
+                    "or a smaller value here, gets the 32-row staging table (3 MiB on Ant) refilled from the sampled files each update")
+    return ap
+
+
+def main(argv):
+    args, unknown = build_parser().parse_known_args(argv)
     extra = parse_unknown(unknown)
     from robosumo_selfplay_amd import alg_ac, alg_ppo, defaults, dist as sdist
     from robosumo_selfplay_amd.vec_env import make_vec_env
@@ -61,6 +71,14 @@ def main(argv):
     kw.update(extra)
     if args.fused_fix_opponent:
         kw["fused_fix_opponent"] = True
+    if args.fused_selector:
+        if args.algo != "ppo":
+            raise SystemExit("--fused_selector belongs to --algo ppo (the A2C learner's 'ours' mode scores no candidates)")
+        kw["fused_selector"] = True
+    if args.selector_table_mb is not None:
+        if not args.fused_selector or not args.selector_table_mb > 0:
+            raise SystemExit("--selector_table_mb is a positive size in MiB and belongs to --fused_selector")
+        kw["selector_table_mb"] = args.selector_table_mb
     if args.algo == "ac":             # the A2C learner's scope, checked before anything touches the GPU
         if sdist.env_rank_world()[2] > 1:
             raise SystemExit("--algo ac runs on a single GPU: launch it without torchrun / with WORLD_SIZE=1")

@@ -513,23 +513,22 @@ static void collision(const so_sim* s, env_t* d) {
       else if (u1 == SUMO_GEOM_CAPSULE && u2 == SUMO_GEOM_BOX) n = capsule_box(tmp, margin, p1, m1, s1, p2, m2, s2);
       else n = 0; /* plane-box etc.: static-static, filtered at compile time */
     }
-    if ((d->n_forward - 1) % 20 == 0) { /* sampled like the engine: the forward evaluation that opens an env step (1 in 20) */
-      int nact = 0;
-      for (int i = 0; i < n; i++) nact += tmp[i].dist < margin;
-      if (nact == 3) d->n_cb3++;
-      if (t2 == SUMO_GEOM_CYLINDER) { /* the rod's axis is the z axis of its frame, half length size[1] */
-        for (int i = 0; i < n; i++) {
-          if (!(tmp[i].dist < margin)) continue;
-          double d3[3] = {tmp[i].pos[0] - p2[0], tmp[i].pos[1] - p2[1], tmp[i].pos[2] - p2[2]}, ax[3] = {m2[2], m2[5], m2[8]};
-          if (fabs(dot3(d3, ax)) > s2[1]) d->n_rodcap++;
-        }
-      }
-    }
+    /* contact-generation fidelity accounting, sampled like the engine: the forward evaluation that opens an env step (1 in 20), and
+     * like the engine over the contacts that are KEPT (those that fit under maxcon; the Jacobian-pool cap below comes later) */
+    const int sampled = (d->n_forward - 1) % 20 == 0;
+    int kept = 0;
     for (int i = 0; i < n; i++) {
       if (!(tmp[i].dist < margin)) continue; /* active iff dist < includemargin (gap = 0) */
       if (d->ncon >= s->maxcon) { d->ncon_dropped++; continue; }
       contact_t* c = d->con + d->ncon++;
       *c = tmp[i];
+      if (sampled) {
+        if (++kept == 3) d->n_cb3++;
+        if (t2 == SUMO_GEOM_CYLINDER) { /* the rod's axis is the z axis of its frame, half length size[1] */
+          double d3[3] = {tmp[i].pos[0] - p2[0], tmp[i].pos[1] - p2[1], tmp[i].pos[2] - p2[2]}, ax[3] = {m2[2], m2[5], m2[8]};
+          if (fabs(dot3(d3, ax)) > s2[1]) d->n_rodcap++;
+        }
+      }
       make_frame(c->frame);
       c->includemargin = margin - SUMO_F(m, pair_gap)[p];
       c->mu = SUMO_F(m, pair_friction)[3 * p];

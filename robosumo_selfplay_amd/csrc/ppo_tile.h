@@ -192,6 +192,141 @@ __device__ __forceinline__ Net vf_net(const float* p_, const PL& L) {
   return n;
 }
 
+// The trunks of NT relu nets on R staged rows x [R][XS] on the vector ALU, all nets in one pass, equal bit for bit to NT calls of
+// trunk_forward<false, R>: an f32 MFMA adds its four k-products to C as sequential FMAs in ascending k, so a
+// lane that owns hidden unit `lane` of every net and runs fmaf over k = 0 .. D-1 from +0 reproduces that column of the tile.  An env
+// of the fused rollout has two rows: on a 16-row tile 14 of 16 rows are zero, and the three trunks of a step wait for their weight
+// batches one after the other.  Here a k-step is one 256-byte weight row per net (w[k * 64 + lane]), every address is known before
+// any data arrives, and ONE ring of four chunks (a chunk = four k-rows of every net; three chunks, 12 NT rows, in flight ahead of
+// the products) runs through layer 0 and on through layer 1 of all nets: the layer-1 rows are requested while layer 0 still
+// accumulates, the head weights at the hand-over between the layers.
+//   x: rows 16-byte aligned (XS a multiple of four, >= (D + 3) & ~3) and ZERO in columns D .. (D + 3) & ~3.  trunk_forward runs
+//   its padded k-steps as 0 * 0 products; here the padded steps of the last chunk are 0 * (the clamped row D - 1), which for finite
+//   weights adds +-0: that leaves every accumulator alone except -0 (reachable from +0 only through a product that underflows),
+//   which 0 * 0 turns into +0 and -0 * w need not.  The `+ 0.0f` behind the loop (only where trunk_forward pads: D & 3) makes
+//   both cases +0.  Chunks past (D + 3) / 4 of the last group of four are fetched (clamped rows) and not multiplied.
+//   hbuf [NT][R][PT_VS]: the relu activations of layer 0, then of layer 1, cross lanes through it.
+//   Heads: the 16-lane group t < NT runs net t's head as lstm_heads_valu does, lane i < nout over the 64 units in ascending order
+//   (the k order of trunk_forward's head tile), plus bias; out[t][r] then holds, in EVERY 16-lane group, column i = lane & 15 of
+//   row r of net t's head: where trunk_forward's tile has it for the lanes with lane >> 4 == 0 (rows 0, 1 = registers 0, 1).
+#define PT_VS 68          /* row stride of hbuf: rows 16-byte aligned, == 4 mod 32 (the head pass reads NT rows at once) */
+template <int NT, int R>
+__device__ __forceinline__ void mlp_rows_valu(const Net (&net)[NT], const float* x, int XS, int D, float* hbuf, int lane, float (&out)[NT][R]) {
+  static_assert(NT >= 1 && NT <= 4, "one 16-lane group per head");
+  const int nx = (D + 3) >> 2;        // layer-0 chunks that carry data
+  const int g0 = (nx + 3) >> 2;       // groups of four chunks: layer 0, then PT_H / 16 of layer 1
+  const int nch = 4 * g0 + PT_H / 4;
+  const int i = lane & 15, hg = lane >> 4;
+  const float PT_GAS *w0p[NT], *w1p[NT];
+  float b0[NT], b1[NT];
+#pragma unroll
+  for (int t = 0; t < NT; t++) { w0p[t] = net[t].w0; w1p[t] = net[t].w1; b0[t] = net[t].b0[lane]; b1[t] = net[t].b1[lane]; }
+  const float PT_GAS *w2p[NT], *b2p[NT];
+  int noutp[NT];
+#pragma unroll
+  for (int t = 0; t < NT; t++) { w2p[t] = net[t].w2; b2p[t] = net[t].b2; noutp[t] = net[t].nout; }
+  const float PT_GAS* w2 = w2p[0];
+  const float PT_GAS* b2 = b2p[0];
+  int nout = noutp[0];
+#pragma unroll
+  for (int t = 1; t < NT; t++) { const bool mine = hg == t; w2 = mine ? w2p[t] : w2; b2 = mine ? b2p[t] : b2; nout = mine ? noutp[t] : nout; }
+  const bool col_ok = hg < NT && i < nout;
+  const int hcol = col_ok ? i : 0;
+  const float bias2 = b2[hcol];
+  float acc[NT][R];
+#pragma unroll
+  for (int t = 0; t < NT; t++)
+#pragma unroll
+    for (int r = 0; r < R; r++) acc[t][r] = 0.0f;
+  auto fetch = [&](int ch, float (&w)[4][NT]) {
+    const bool l0 = ch < 4 * g0;
+    const int k0 = 4 * (l0 ? ch : ch - 4 * g0), kmax = l0 ? D : PT_H;
+#pragma unroll
+    for (int kk = 0; kk < 4; kk++) {
+      int k = k0 + kk;
+      if (k >= kmax) k = kmax - 1;   // unconditional loads from a clamped row
+#pragma unroll
+      for (int t = 0; t < NT; t++) w[kk][t] = (l0 ? w0p[t] : w1p[t])[k * PT_H + lane];
+    }
+  };
+  auto consume0 = [&](int ch, const float (&w)[4][NT]) {   // layer 0: the nets share the x rows (wave-uniform 128-bit LDS reads)
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+      const float4 xv = *(const float4*)(x + r * XS + 4 * ch);
+      const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
+#pragma unroll
+      for (int kk = 0; kk < 4; kk++)
+#pragma unroll
+        for (int t = 0; t < NT; t++) acc[t][r] = __builtin_fmaf(xs[kk], w[kk][t], acc[t][r]);
+    }
+  };
+  auto consume1 = [&](int ch, const float (&w)[4][NT]) {   // layer 1: every net on its own activation rows
+#pragma unroll
+    for (int t = 0; t < NT; t++)
+#pragma unroll
+      for (int r = 0; r < R; r++) {
+        const float4 xv = *(const float4*)(hbuf + (t * R + r) * PT_VS + 4 * ch);
+        const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
+#pragma unroll
+        for (int kk = 0; kk < 4; kk++) acc[t][r] = __builtin_fmaf(xs[kk], w[kk][t], acc[t][r]);
+      }
+  };
+  float w[4][4][NT], w2v[PT_H];
+  fetch(0, w[0]); fetch(1, w[1]); fetch(2, w[2]);
+  for (int g = 0; g < g0; g++) {
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+      const int ch = 4 * g + b;
+      fetch(ch + 3, w[(b + 3) & 3]);
+      if (ch < nx) consume0(ch, w[b]);
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < PT_H; u++) { const float wv = w2[u * nout + hcol]; w2v[u] = col_ok ? wv : 0.0f; }
+#pragma unroll
+  for (int t = 0; t < NT; t++)
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+      const float a = (D & 3) ? acc[t][r] + 0.0f : acc[t][r];
+      hbuf[(t * R + r) * PT_VS + lane] = fmaxf(a + b0[t], 0.0f);
+      acc[t][r] = 0.0f;
+    }
+  wave_sync();
+#pragma unroll
+  for (int g = 0; g < PT_H / 16; g++) {
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+      const int c1 = 4 * g + b, nxt = 4 * g0 + c1 + 3;
+      fetch(nxt < nch ? nxt : nch - 1, w[(b + 3) & 3]);   // (no branch around the loads: past the end the last chunk is fetched again)
+      consume1(c1, w[b]);
+    }
+  }
+  wave_sync();   // every lane has read the layer-0 rows
+#pragma unroll
+  for (int t = 0; t < NT; t++)
+#pragma unroll
+    for (int r = 0; r < R; r++) hbuf[(t * R + r) * PT_VS + lane] = fmaxf(acc[t][r] + b1[t], 0.0f);
+  wave_sync();
+  const float* hrow = hbuf + (hg < NT ? hg : 0) * R * PT_VS;
+  const float bias = col_ok ? bias2 : 0.0f;
+  float o[R];
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    o[r] = 0.0f;
+#pragma unroll
+    for (int q = 0; q < PT_H / 4; q++) {
+      const float4 hv = *(const float4*)(hrow + r * PT_VS + 4 * q);
+      o[r] = __builtin_fmaf(hv.x, w2v[4 * q], o[r]); o[r] = __builtin_fmaf(hv.y, w2v[4 * q + 1], o[r]);
+      o[r] = __builtin_fmaf(hv.z, w2v[4 * q + 2], o[r]); o[r] = __builtin_fmaf(hv.w, w2v[4 * q + 3], o[r]);
+    }
+    o[r] += bias;
+  }
+#pragma unroll
+  for (int t = 0; t < NT; t++)
+#pragma unroll
+    for (int r = 0; r < R; r++) out[t][r] = __shfl(o[r], 16 * t + i, PT_WAVE);
+}
+
 // Policy trunk of a policy-zoo MLP net (policy_zoo MLPPolicy(normalize=True), policy.py:23-91) on ROWS staged rows of x [ROWS][XS]:
 // the rows are filtered IN PLACE -- clip((x - mean) * invstd, +-clip) on the first Dz columns, the expression and order of stage_x
 // in ppo_kernels.hip; columns Dz .. XS are zeroed -- then the tanh trunk of input width Dz runs on them.  filt: mean [Dz] | 1 / std

@@ -2708,47 +2708,49 @@ __device__ __forceinline__ void lstm_state_store(float* sp, int j, const LstmCel
   hand_store<true>(sp + j, cell.cn); hand_store<true>(sp + NH + j, cell.hn);
 }
 
+// MLP policy phase (POLICY 0).  The three trunks of a step -- learner policy, opponent policy (snapshot opp_idx[e]), learner value --
+// run in ONE pass on the vector ALU (ppo_tile.h mlp_rows_valu<3, 2>: lane j owns hidden unit j of all three nets, one ring of weight
+// rows through both layers), in the accumulation order of the MFMA tiles of ppo_selfplay_kernel, so every number equals the
+// step-by-step path bit for bit.  LDS (floats, from lds_off; place_mlp_scratch(valu_nets = 3)): x [2][XS], zero in columns
+// D .. XS | activation rows [3][2][PT_VS].
 template <class C, class SA, class RA>
 __device__ __forceinline__ void rollout_policy_phase(C& c, const SA& a, const RA& r, int e, int s) {
   const int lane = c.lane, i = lane & 15, kq = lane >> 4;
   const int D = r.L.D, A = r.L.A, XS = r.XS;
-  float* xbuf = (float*)(c.sm + r.lds_off);        // [2][XS] | h1 [2][PT_HS] | h2 [2][PT_HS]
-  float* h1 = xbuf + 2 * XS;
-  float* h2 = h1 + 2 * PT_HS;
+  float* xbuf = (float*)(c.sm + r.lds_off);
+  float* hb = xbuf + 2 * XS;
   const size_t col = (size_t)r.env_offset + e;
   const size_t slot0 = ((size_t)0 * r.T + s) * r.Ntot + col, slot1 = ((size_t)1 * r.T + s) * r.Ntot + col;
 #ifdef SUMO_POLICY_PROBE
   unsigned long long tp_ = wall_clock64();
 #endif
-  policy_load_obs<false, true>(a, r, e, lane, xbuf, D, XS, slot0, slot1);
+  const int oiv = r.opp_idx ? pt_global(r.opp_idx)[e] : 0;   // (in flight during the observation loads)
+  policy_load_obs<true, true>(a, r, e, lane, xbuf, D, XS, slot0, slot1);
   if (lane < 2) policy_record_done(r, lane, slot0, slot1, policy_prev_done(a, e));
-  wave_sync();
   const float PT_GAS* lp = pt_global(r.learner);
-  const float PT_GAS* op = pt_global(r.opponent) + (size_t)(r.opp_idx ? pt_global(r.opp_idx)[e] : 0) * r.L.P;
-  PPROBE(4);
-  const f32x4 mL = trunk_forward<false, 2>(pi_net((const float*)lp, r.L), xbuf, XS, D, h1, h2, lane);
-  wave_sync();
-  PPROBE(5);
-  const f32x4 mO = trunk_forward<false, 2>(pi_net((const float*)op, r.L), xbuf, XS, D, h1, h2, lane);
-  wave_sync();
-  PPROBE(6);
-  const f32x4 vL = trunk_forward<false, 2>(vf_net((const float*)lp, r.L), xbuf, XS, D, h1, h2, lane);
-  PPROBE(7);
-  // heads: row 0 = agent 0 (learner acts, opponent scores), row 1 = agent 1 (opponent acts, learner scores and values)
+  const float PT_GAS* op = pt_global(r.opponent) + (size_t)__builtin_amdgcn_readfirstlane(oiv) * r.L.P;
+  // what the heads need is requested with the first weight rows, not behind the trunks
   const bool colk = i < A;
   const float lsL = colk ? lp[r.L.logstd + i] : 0.0f, lsO = colk ? op[r.L.logstd + i] : 0.0f;
-  const float stdL = expf(lsL), stdO = expf(lsO);
-  const float sumL = row16_sum(lsL), sumO = row16_sum(lsO);
-  const bool ok = colk && kq == 0;                  // rows 0 and 1 live in the first 16 lanes (D layout: rows 4 kq + r)
+  const bool ok = colk && kq == 0;                  // rows 0 and 1 of a head live in the first 16 lanes
   const size_t nz = policy_noise_index(a, e, s, A, i);
   const float n0 = ok ? pt_global(r.noise0)[nz] : 0.0f, n1 = ok ? pt_global(r.noise1)[nz] : 0.0f;
+  wave_sync();
+  PPROBE(4);
+  const Net nets[3] = {pi_net((const float*)lp, r.L), pi_net((const float*)op, r.L), vf_net((const float*)lp, r.L)};
+  float m[3][2];                                    // [learner mean | opponent mean | learner value][row]
+  mlp_rows_valu<3, 2>(nets, xbuf, XS, D, hb, lane, m);
+  PPROBE(7);
+  // heads: row 0 = agent 0 (learner acts, opponent scores), row 1 = agent 1 (opponent acts, learner scores and values)
+  const float stdL = expf(lsL), stdO = expf(lsO);
+  const float sumL = row16_sum(lsL), sumO = row16_sum(lsO);
   float act0 = 0.0f, act1 = 0.0f;
-  const float nlp0 = gauss_row(mL[0], stdL, sumL, ok, true, n0, act0, A);      // learner samples for agent 0 ...
-  const float onlp0 = gauss_row(mO[0], stdO, sumO, ok, false, 0.0f, act0, A);  // ... the opponent net scores that action
-  const float onlp1 = gauss_row(mO[1], stdO, sumO, ok, true, n1, act1, A);     // opponent samples for agent 1 ...
-  const float nlp1 = gauss_row(mL[1], stdL, sumL, ok, false, 0.0f, act1, A);   // ... the learner scores it
+  const float nlp0 = gauss_row(m[0][0], stdL, sumL, ok, true, n0, act0, A);      // learner samples for agent 0 ...
+  const float onlp0 = gauss_row(m[1][0], stdO, sumO, ok, false, 0.0f, act0, A);  // ... the opponent net scores that action
+  const float onlp1 = gauss_row(m[1][1], stdO, sumO, ok, true, n1, act1, A);     // opponent samples for agent 1 ...
+  const float nlp1 = gauss_row(m[0][1], stdL, sumL, ok, false, 0.0f, act1, A);   // ... the learner scores it
   if (ok) policy_commit_actions<true>(c, a, r, e, i, act0, act1, A, slot0, slot1);
-  if (lane == 0) policy_record_scalars(r, slot0, slot1, nlp0, nlp1, onlp0, onlp1, vL[0], vL[1]);
+  if (lane == 0) policy_record_scalars(r, slot0, slot1, nlp0, nlp1, onlp0, onlp1, m[2][0], m[2][1]);
   PPROBE(8);
   wave_sync();   // the action buffer is read back by the env step (other lanes), the scratch region becomes the mass matrix again
 }
@@ -2865,26 +2867,28 @@ template <class C, class SA, class RA>
 __device__ __forceinline__ void rollout_policy_phase_match(C& c, const SA& a, const RA& r, int e, int s) {
   const int lane = c.lane, i = lane & 15, kq = lane >> 4;
   const int D = r.L.D, A = r.L.A, XS = r.XS;
-  float* xbuf = (float*)(c.sm + r.lds_off);        // [2][XS] | h1 [2][PT_HS] | h2 [2][PT_HS]
-  float* h1 = xbuf + 2 * XS;
-  float* h2 = h1 + 2 * PT_HS;
-  policy_load_obs<false, false>(a, r, e, lane, xbuf, D, XS);
-  wave_sync();
+  float* xbuf = (float*)(c.sm + r.lds_off);        // x [2][XS], zero in columns D .. XS | activation rows [2][2][PT_VS]
+  float* hb = xbuf + 2 * XS;
   int j0, j1;
   policy_snapshot_rows(a, r, e, lane, j0, j1);
-  const float PT_GAS* p0 = pt_global(r.snaps) + (size_t)j0 * r.L.P;
-  const float PT_GAS* p1 = pt_global(r.snaps) + (size_t)j1 * r.L.P;
-  const f32x4 m0 = trunk_forward<false, 2>(pi_net((const float*)p0, r.L), xbuf, XS, D, h1, h2, lane);
-  wave_sync();
-  const f32x4 m1 = trunk_forward<false, 2>(pi_net((const float*)p1, r.L), xbuf, XS, D, h1, h2, lane);
-  const bool ok = i < A && kq == 0;                 // rows 0 and 1 live in the first 16 lanes (D layout: rows 4 kq + r)
-  float act0 = m0[0], act1 = m1[1];
-  if (r.noise0) {
-    const float ls0 = ok ? p0[r.L.logstd + i] : 0.0f, ls1 = ok ? p1[r.L.logstd + i] : 0.0f;
+  policy_load_obs<true, false>(a, r, e, lane, xbuf, D, XS);
+  const float PT_GAS* p0 = pt_global(r.snaps) + (size_t)__builtin_amdgcn_readfirstlane(j0) * r.L.P;
+  const float PT_GAS* p1 = pt_global(r.snaps) + (size_t)__builtin_amdgcn_readfirstlane(j1) * r.L.P;
+  const bool ok = i < A && kq == 0;                 // rows 0 and 1 of a head live in the first 16 lanes
+  float ls0 = 0.0f, ls1 = 0.0f, n0 = 0.0f, n1 = 0.0f;
+  if (r.noise0) {   // (requested with the first weight rows)
+    ls0 = ok ? p0[r.L.logstd + i] : 0.0f; ls1 = ok ? p1[r.L.logstd + i] : 0.0f;
     const size_t nz = policy_noise_index(a, e, s, A, i);
-    const float n0 = ok ? pt_global(r.noise0)[nz] : 0.0f, n1 = ok ? pt_global(r.noise1)[nz] : 0.0f;
-    (void)gauss_row(m0[0], expf(ls0), 0.0f, ok, true, n0, act0, A);
-    (void)gauss_row(m1[1], expf(ls1), 0.0f, ok, true, n1, act1, A);
+    n0 = ok ? pt_global(r.noise0)[nz] : 0.0f; n1 = ok ? pt_global(r.noise1)[nz] : 0.0f;
+  }
+  wave_sync();
+  const Net nets[2] = {pi_net((const float*)p0, r.L), pi_net((const float*)p1, r.L)};
+  float m[2][2];                                    // both trunks in one pass on the vector ALU (mlp_rows_valu), as rollout_policy_phase
+  mlp_rows_valu<2, 2>(nets, xbuf, XS, D, hb, lane, m);
+  float act0 = m[0][0], act1 = m[1][1];
+  if (r.noise0) {
+    (void)gauss_row(m[0][0], expf(ls0), 0.0f, ok, true, n0, act0, A);
+    (void)gauss_row(m[1][1], expf(ls1), 0.0f, ok, true, n1, act1, A);
   }
   if (ok) policy_commit_actions<false>(c, a, r, e, i, act0, act1);
   wave_sync();   // the action buffer is read back by the env step (other lanes), the scratch region becomes the mass matrix again
@@ -4575,10 +4579,14 @@ static int check_lstm_shape(const ppo_lstm_net& n, const char* what) {
   return 0;
 }
 
-// MLP phases: x [2][XS] and the two hidden tiles go where the mass matrix lives between two steps
-static int place_mlp_scratch(sumo_engine* E, int ob_dim, int ac_dim, RolloutArgs& r) {
-  r.XS = x_stride(ob_dim); r.L = make_layout(ob_dim, ac_dim); r.lds_off = E->L.M;
-  const size_t need = (size_t)(2 * r.XS + 4 * PT_HS) * sizeof(float), have = (size_t)E->L.msize * sizeof(double);
+// MLP phases: x [2][XS] and the two hidden tiles go where the mass matrix lives between two steps.  valu_nets > 0 (modes 0 and 2:
+// that many trunks in one pass of mlp_rows_valu): x rows and the activation rows [valu_nets][2][PT_VS] 16-byte aligned for the
+// 128-bit LDS reads, the x rows zero-padded to a multiple of four columns
+static int place_mlp_scratch(sumo_engine* E, int ob_dim, int ac_dim, RolloutArgs& r, int valu_nets = 0) {
+  r.XS = valu_nets ? (ob_dim + 3) & ~3 : x_stride(ob_dim); r.L = make_layout(ob_dim, ac_dim);
+  r.lds_off = valu_nets ? (E->L.M + 1) & ~1 : E->L.M;
+  const size_t need = (size_t)(2 * r.XS + (valu_nets ? valu_nets * 2 * PT_VS : 4 * PT_HS)) * sizeof(float);
+  const size_t have = (size_t)(E->L.M + E->L.msize - r.lds_off) * sizeof(double);
   if (need > have) FAIL(-8, "policy scratch (%zu B) does not fit the mass-matrix region (%zu B)", need, have);
   return 0;
 }
@@ -4642,7 +4650,7 @@ extern "C" int sumo_rollout_steps(sumo_handle_t E, const sumo_rollout* ro, float
   memset(&r, 0, sizeof r);
   r.learner = ro->learner_params; r.opponent = ro->opponent_params; r.opp_idx = ro->opponent_index;
   copy_rollout_fields(r, ro);
-  if (int rc = place_mlp_scratch(E, ro->ob_dim, ro->ac_dim, r)) return rc;
+  if (int rc = place_mlp_scratch(E, ro->ob_dim, ro->ac_dim, r, 3)) return rc;
   return rollout_launch(E, r, 0, b, stream);
 }
 
@@ -4683,7 +4691,7 @@ extern "C" int sumo_match_steps(sumo_handle_t E, const sumo_match* mo, float* ac
   memset(&r, 0, sizeof r);
   r.snaps = mo->params;
   copy_match_fields(r, mo, E->N);
-  if (int rc = place_mlp_scratch(E, mo->ob_dim, mo->ac_dim, r)) return rc;
+  if (int rc = place_mlp_scratch(E, mo->ob_dim, mo->ac_dim, r, 2)) return rc;
   return rollout_launch(E, r, 2, b, stream);
 }
 

@@ -71,9 +71,12 @@ for cfg in a.configs.split(","):
             L.sumo_debug_tprobe(buf, 1)
             run(); torch.cuda.synchronize()
             L.sumo_debug_tprobe(buf, 1)
+            # (the MLP rollout's three trunks run in one pass of mlp_rows_valu, which carries no hooks: the trunk_forward hooks
+            # count in the zoo modes only, and the one pass is the phase clock's slot 7)
             per = [buf[k] / 1e5 / (a.envs * a.steps * 3) * 1e3 for k in range(5)]      # us per trunk
-            print("  inside a trunk (us, mean of the three): layer-1 loads + products %.2f | bias / relu / LDS write %.2f | layer-2 %.2f | "
+            print("  inside a trunk_forward (us, mean of three per step): layer-1 loads + products %.2f | bias / relu / LDS write %.2f | layer-2 %.2f | "
                   "bias / relu / LDS write %.2f | head %.2f" % tuple(per), flush=True)
-            print("  policy phase split (us per env step): obs staging %.1f | learner policy trunk %.1f | opponent policy trunk %.1f | learner value trunk %.1f | heads + records %.1f"
-                  % tuple(st[:, 4 + q].mean() / 1e5 / a.steps * 1e3 for q in range(5)), flush=True)
+            sp = [st[:, 4 + q].mean() / 1e5 / a.steps * 1e3 for q in range(5)]
+            print("  policy phase split (us per env step): obs staging + head operands %.1f | three trunks, one pass %.1f | heads + records %.1f"
+                  % (sp[0], sp[3], sp[4]), flush=True)
     env.close()

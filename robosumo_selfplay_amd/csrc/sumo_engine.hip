@@ -20,6 +20,7 @@
 #include <string.h>
 
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include <rocprim/rocprim.hpp>
@@ -2534,68 +2535,37 @@ sumo_cfrc_kernel(const Params* P, StepArgs a, CfrcArgs q) {
 #define PROF_STRIDE 4
 #define PPROBE(slot) do { } while (0)
 #endif
-// Policy-zoo MLP opponents (sumo_rollout_steps_zoo / sumo_match_steps_zoo, POLICY 4 / 5): the table's filter rows, clip, size,
-// input width and parameter layout.  The table's parameter rows [nzoo][Lz.P] travel in RolloutArgs::opponent.
-struct ZooArgs {
-  const float* filt;                 // [nzoo][2][Dz]: mean | 1 / std
+// The policy-zoo tables of a launch (POLICY 4 .. 12), one struct per family.  Every zoo mode reads its table(s) from the two members
+// RolloutArgs::zm / zl, which no other mode reads; a league (POLICY 11 / 12) fills both, and RolloutArgs::tile_net then holds the
+// entry of every 16-env tile of the whole env set: [0, zm.n) = that row of the MLP table, [zm.n, zm.n + zl.n) = row entry - zm.n of
+// the LSTM table.
+struct ZooMlpTable {
+  const float* params;               // [n][L.P]
+  const float* filt;                 // [n][2][D]: mean | 1 / std
   float clip;
-  int nzoo, Dz;
-  ParamLayout Lz;                    // make_layout(Dz, A)
+  int n, D;                          // entries, input width (the first D columns of the scene's observation)
+  ParamLayout L;                     // make_layout(D, A)
 };
-// Policy-zoo LSTM opponents (sumo_match_steps_zoo_lstm / sumo_match_steps_lstm_zoo_lstm, POLICY 6 / 7): the table (parameter rows
-// [nzoo][Pz] in the order of sumo_zoo_lstm, filter rows), clip, forget bias, size, input / action width, and where the cell's
-// rows (embedding [64] | previous latent [64] | new latent [64], 16-byte aligned) start in the policy scratch.  Agent 1's
-// recurrent state [N][128] (c | h) travels in RolloutArgs::st1.
-struct ZooLstmArgs {
-  const float* params;
-  const float* filt;                 // [nzoo][2][Dz]: mean | 1 / std
+// A zoo LSTM net's parameter row follows the order of sumo_zoo_lstm.  Its cell's rows (embedding [64] | previous latent [64] | new
+// latent [64], 16-byte aligned) start sc_off floats from the scratch base (lds_off); agent 1's recurrent state [N][128] (c | h)
+// travels in RolloutArgs::st1.
+struct ZooLstmTable {
+  const float* params;               // [n][P]
+  const float* filt;                 // [n][2][D]: mean | 1 / std
   float clip, forget_bias;
-  int nzoo, Dz, A, Pz;
-  int sc_off;                        // floats from the scratch base (lds_off)
+  int n, D, A, P;
+  int sc_off;
   int emb;                           // embedding width (the table's emb_dim, 64).  Deliberately a launch field and not a literal:
                                      // lstm_gates_valu's chunk loop runs (emb + 64) / 4 trips, and it keeps its ring of four
                                      // chunk buffers only while that count is a run-time value, as it is for the LSTM(128)
-                                     // nets (their D is a launch field too).  The loop is shared with modes 1 and 3, whose
-                                     // code objects must not change, so it carries no unroll pragma of its own.
-};
-// Policy-zoo opponents of a RECURRENT learner (sumo_rollout_steps_lstm_zoo / sumo_rollout_steps_lstm_zoo_lstm, POLICY 9 / 10).  The
-// learner's net fills RolloutArgs::lnet and the launch writes the rollout record, so neither overlay above is free: these fields
-// overlay the match fields at the end of RolloutArgs, which a rollout never reads.  The table's parameter rows [nzoo][Pz] travel in
-// RolloutArgs::opponent (as in mode 4); a zoo MLP table's layout make_layout(Dz, A) in RolloutArgs::L, which the recurrent learner
-// does not read (Pz == L.P then); a zoo LSTM table's state rows in RolloutArgs::st1.  forget_bias, A, sc_off and emb are read by
-// mode 10 only, with the meaning they have in ZooLstmArgs.
-struct ZooTailArgs {
-  const float* filt;                 // [nzoo][2][Dz]: mean | 1 / std
-  float clip, forget_bias;
-  int nzoo, Dz, A, Pz;
-  int sc_off;
-  int emb;
-};
-// Leagues of policy-zoo nets of BOTH families (sumo_rollout_steps_zoo_league / sumo_rollout_steps_lstm_zoo_league, POLICY 11 / 12).
-// The launch writes the rollout record, mode 12's learner fills RolloutArgs::lnet and the tail overlay holds one table's fields, so
-// nothing is left to overlay for a second table: these fields are APPENDED to RolloutArgs (no existing field moves, static_assert
-// below RolloutLaunch; the earlier modes never read them).  The LSTM table travels as in mode 10 -- its fields in `l`, its parameter
-// rows in RolloutArgs::opponent, its state rows in RolloutArgs::st1 -- the MLP table here; the entry of every 16-env tile of the
-// whole env set in RolloutArgs::tile_net: [0, nmlp) = that row of the MLP table, [nmlp, nmlp + l.nzoo) = row entry - nmlp of the
-// LSTM table.
-struct ZooLeagueArgs {
-  ZooTailArgs l;
-  const float* mparams;              // [nmlp][Lz.P]
-  const float* mfilt;                // [nmlp][2][Dm]: mean | 1 / std
-  float mclip;
-  int nmlp, Dm;
-  ParamLayout Lz;                    // make_layout(Dm, A)
+                                     // nets (their D is a launch field too).  The loop is shared with modes 1 and 3, so it
+                                     // carries no unroll pragma of its own.
 };
 struct RolloutArgs {
-  const float *learner, *opponent;   // flat parameter vectors; opponent: [npool][P]
-  const int32_t* opp_idx;            // [N] snapshot per env or NULL
+  const float *learner, *opponent;   // flat parameter vectors; opponent: the self-play snapshot pool [npool][P]
+  const int32_t* opp_idx;            // [N] snapshot (zoo modes: table row) per env or NULL
   const float *noise0, *noise1;      // [T][N][A]
-  // (the match modes write no rollout record: the zoo LSTM modes' fields overlay its six pointers, so the struct -- and with it
-  // the kernel-argument segment every instantiation reads -- keeps its size and offsets; static_asserts below RolloutLaunch)
-  union {
-    struct { float *obs, *act, *rew, *val, *nlp, *onlp; };   // [2][T][Ntot][...]
-    ZooLstmArgs zl;
-  };
+  float *obs, *act, *rew, *val, *nlp, *onlp;   // the rollout record [2][T][Ntot][...] (the match modes write none)
   uint8_t *done, *ep_done;           // [2][T][Ntot], [T][Ntot]
   double* ep_r;                      // [T][Ntot]
   int32_t* ep_l;                     // [T][Ntot]
@@ -2603,14 +2573,11 @@ struct RolloutArgs {
   int T, Ntot, env_offset, s0, K, XS, lds_off;   // lds_off: LDS offset (doubles) of the policy scratch (the mass-matrix region)
   int* sched;                        // ticket counter | abort flag | finished steps per env [N] (zeroed by the host per launch)
   unsigned long long* prof;          // development (sumo_debug_trace): [N][4] wave start, end, ticks in the policy phases, ticks in the env steps (100 MHz)
-  ParamLayout L;
-  // recurrent policies (sumo_rollout_steps_lstm): the learner's net, the opponent snapshots (device array) with the snapshot of
-  // every 16-env tile of the whole env set (NULL: snapshot 0), and the acting nets' states [N][2 hidden] (c | h) per agent
-  // (the zoo modes evaluate no recurrent net: their fields overlay lnet, so the struct -- and with it the kernel-argument
-  // segment every instantiation reads -- keeps its size and offsets)
-  // (sumo_rollout_steps_zoo_lstm, POLICY 8, writes the rollout record, so its zoo LSTM fields cannot sit in zl: they travel
-  // here as zlr -- its learner is an MLP and reads no lnet)
-  union { ppo_lstm_net lnet; ZooArgs zoo; ZooLstmArgs zlr; };
+  ParamLayout L;                     // the MLP learner's / checkpoints' layout
+  // recurrent policies (sumo_rollout_steps_lstm): the learner's net (matches: the prototype), the opponent snapshots (device array)
+  // with the snapshot of every 16-env tile of the whole env set (NULL: snapshot 0; zoo modes: the table row / league entry of the
+  // tile), and the acting nets' states [N][2 hidden] (c | h) per agent
+  ppo_lstm_net lnet;
   const ppo_lstm_net* onets;
   const int32_t* tile_net;
   float *st0, *st1;
@@ -2619,18 +2586,13 @@ struct RolloutArgs {
   // counted while their sum is below quota.  An env's counters cross waves between its tickets like its record: lane 0 of the
   // owning wave reads them with hand_load<true> and writes them with hand_store<true> before the s_waitcnt vmcnt(0) that precedes
   // the progress store, so the next owner (which polls prog[e] first) sees them.
-  // (the rollouts of a recurrent learner against policy-zoo nets, POLICY 9 / 10, play no match: their zoo fields overlay these,
-  // so the struct keeps its size and offsets; static_assert below RolloutLaunch)
-  union {
-    struct {
-      const float* snaps;
-      const int32_t *idx0, *idx1;
-      int* score;
-      int nsnap, quota;
-    };
-    ZooTailArgs zt;
-  };
-  ZooLeagueArgs lg;                  // POLICY 11 / 12 only
+  const float* snaps;
+  const int32_t *idx0, *idx1;
+  int* score;
+  int nsnap, quota;
+  // policy-zoo opponents (POLICY 4 .. 12); appended, so every field above keeps the offset the modes 0 .. 3 read it at
+  ZooMlpTable zm;
+  ZooLstmTable zl;
 };
 
 // ---- pieces shared by the four policy phases (each reads a / r through the references its phase received) ----
@@ -2894,66 +2856,7 @@ __device__ __forceinline__ void rollout_policy_phase_match(C& c, const SA& a, co
   wave_sync();   // the action buffer is read back by the env step (other lanes), the scratch region becomes the mass matrix again
 }
 
-// LSTM match policy phase (sumo_match_steps_lstm, POLICY 3): agent g in {0, 1} acts with net idx_g[e] of the device table onets on
-// (obs g, its own state st_g[e] masked by the previous step's done flag) -- LstmPPOModel.step on one row, the S / M feeds of
-// models.py:163-170.  One row per net: gate sums on the vector ALU in the MFMA tiles' order (lstm_gates_valu), cell update and
-// Gaussian head through the functions ppo_lstm_step_kernel uses, so every number equals that kernel bit for bit.  No value head,
-// no cross-scoring, nothing recorded; the new state crosses waves like the LSTM rollout's.  An index outside [0, nsnap) raises the
-// abort flag and plays net 0 instead.  LDS (floats, from lds_off): x [2][XS] | previous latent [NH] | new latent [NH].
-template <int NH, class C, class SA, class RA>
-__device__ __forceinline__ void rollout_policy_phase_match_lstm(C& c, const SA& a, const RA& r, int e, int s) {
-  const int lane = c.lane;
-  const int D = r.lnet.ob_dim, A = r.lnet.ac_dim, XS = r.XS;
-  float* xo = (float*)(c.sm + r.lds_off);
-  float* hp = xo + 2 * XS;
-  float* hn = hp + NH;
-  policy_load_obs<true, false>(a, r, e, lane, xo, D, XS);
-  const unsigned dn = policy_prev_done(a, e);
-  int jn[2];
-  policy_snapshot_rows(a, r, e, lane, jn[0], jn[1]);
-  const bool ok = lane < A;
-  const int j0 = 2 * lane;                           // lane owns the units 2 lane, 2 lane + 1
-  float act[2];
-#pragma unroll
-  for (int g = 0; g < 2; g++) {
-    const ppo_lstm_net PT_GAS* NT = pt_global(r.onets) + jn[g];
-    const float keep = 1.0f - (float)((dn >> (8 * g)) & 0xff);
-    float* sp = (g ? r.st1 : r.st0) + (size_t)e * 2 * NH;
-    float cp[2];
-    lstm_state_pair(sp + j0, keep, cp);
-    lstm_state_pair(sp + NH + j0, keep, hp + j0);
-    const float PT_GAS* b_ = pt_global(NT->b);
-    const float fb = NT->forget_bias;
-    float z[4][2][1], bz[4][2];
-    lstm_bias_pair<NH>(b_, j0, bz);
-    wave_sync();
-    const float* const xr[1] = {xo + g * XS};
-    const float* const hr[1] = {hp};
-    lstm_gates_valu<NH, 1>(NT->wx, NT->wh, D, xr, hr, lane, z);
-#pragma unroll
-    for (int u = 0; u < 2; u++) {
-      const int j = j0 + u;
-      const LstmCell cl = lstm_cell(z[0][u][0], z[1][u][0], z[2][u][0], z[3][u][0], bz[0][u], bz[1][u] + fb, bz[2][u], bz[3][u], cp[u]);
-      lstm_state_store<NH>(sp, j, cl);                                              // agent g's state after its step
-      hn[j] = cl.hn;
-    }
-    wave_sync();
-    float m[1];
-    lstm_heads_valu<NH, 1>(NT->head_w, NT->head_w, A, hn, lane, m);   // (lane 16's value sum reads head_w: the value head stays unread)
-    const float mean = m[0] + (ok ? pt_global(NT->head_b)[lane] : 0.0f);
-    act[g] = mean;
-    if (r.noise0) {
-      const float ls = ok ? pt_global(NT->logstd)[lane] : 0.0f;
-      const float nz = ok ? pt_global(g ? r.noise1 : r.noise0)[policy_noise_index(a, e, s, A, lane)] : 0.0f;
-      (void)gauss_row(mean, expf(ls), 0.0f, ok, true, nz, act[g], A);
-    }
-    wave_sync();   // the latent rows are rewritten by the next side
-  }
-  if (ok) policy_commit_actions<false>(c, a, r, e, lane, act[0], act[1]);
-  wave_sync();
-}
-
-// ---- policy-zoo MLP opponents (POLICY 4 / 5) ----
+// ---- pieces of the match modes 3, 5, 6, 7 and of the zoo rollouts 4, 8 .. 12 (each exists once; the phases below compose them) ----
 // Row j of a table of n entries, checked: an index outside [0, n) raises the launch's abort flag and plays row 0.
 template <class SA>
 __device__ __forceinline__ int policy_checked_row(const SA& a, int lane, int j, int n) {
@@ -2964,237 +2867,135 @@ __device__ __forceinline__ int policy_checked_row(const SA& a, int lane, int j, 
   return j;
 }
 
-// Rollout against a policy-zoo MLP net (sumo_rollout_steps_zoo, POLICY 4; learn(opponent_mode='fix'), reference alg_ppo.py:194-206):
-// rollout_policy_phase with the opponent's policy trunk replaced by zoo net opp_idx[e]: the learner's policy and value trunks run
-// on the raw tile first (the raw observations are in the rollout record by then), the tile is then filtered in place and the zoo
-// net's tanh trunk of input width Dz runs on it (zoo_trunk_forward: no second tile).  Heads and record as rollout_policy_phase;
-// the zoo net's value trunk is not evaluated.  Every number equals ppo_forward (learner) / ppo_forward_filtered (zoo net) bit for bit.
-template <class C, class SA, class RA>
-__device__ __forceinline__ void rollout_policy_phase_zoo(C& c, const SA& a, const RA& r, int e, int s) {
-  const int lane = c.lane, i = lane & 15, kq = lane >> 4;
-  const int D = r.L.D, A = r.L.A, XS = r.XS, Dz = r.zoo.Dz;
-  float* xbuf = (float*)(c.sm + r.lds_off);        // [2][XS] | h1 [2][PT_HS] | h2 [2][PT_HS]
-  float* h1 = xbuf + 2 * XS;
-  float* h2 = h1 + 2 * PT_HS;
-  const size_t col = (size_t)r.env_offset + e;
-  const size_t slot0 = ((size_t)0 * r.T + s) * r.Ntot + col, slot1 = ((size_t)1 * r.T + s) * r.Ntot + col;
-  policy_load_obs<false, true>(a, r, e, lane, xbuf, D, XS, slot0, slot1);
-  if (lane < 2) policy_record_done(r, lane, slot0, slot1, policy_prev_done(a, e));
+// One side of an LSTM(128) match: agent g in {0, 1} acts with net jn of the device table onets on (obs g, its own state st_g[e] masked
+// by the previous step's done flag) -- LstmPPOModel.step on one row, the S / M feeds of models.py:163-170.  Gate sums on the vector
+// ALU in the MFMA tiles' order (lstm_gates_valu), cell update and Gaussian head through the functions ppo_lstm_step_kernel uses, so
+// every number equals that kernel bit for bit.  No value head; the new state crosses waves like the LSTM rollout's.  xo: x [2][XS],
+// zero-padded; hp / hn: previous / new latent [NH], free for the next side when the function returns.  act: the action's column in
+// lanes < A -- by reference, not returned: returned, mode 3 on the 28-DoF dynamic layout spills three more vector registers.
+template <int NH, class SA, class RA>
+__device__ __forceinline__ void match_lstm_side(const SA& a, const RA& r, int e, int s, int lane, int g, int jn, unsigned dn, float* xo,
+                                                float* hp, float* hn, float& act) {
+  const int D = r.lnet.ob_dim, A = r.lnet.ac_dim;
+  const bool ok = lane < A;
+  const int j0 = 2 * lane;                           // lane owns the units 2 lane, 2 lane + 1
+  const ppo_lstm_net PT_GAS* NT = pt_global(r.onets) + jn;
+  const float keep = 1.0f - (float)((dn >> (8 * g)) & 0xff);
+  float* sp = (g ? r.st1 : r.st0) + (size_t)e * 2 * NH;
+  float cp[2];
+  lstm_state_pair(sp + j0, keep, cp);
+  lstm_state_pair(sp + NH + j0, keep, hp + j0);
+  const float PT_GAS* b_ = pt_global(NT->b);
+  const float fb = NT->forget_bias;
+  float z[4][2][1], bz[4][2];
+  lstm_bias_pair<NH>(b_, j0, bz);
   wave_sync();
-  const int jz = policy_checked_row(a, lane, r.opp_idx ? pt_global(r.opp_idx)[e] : 0, r.zoo.nzoo);
-  const float PT_GAS* lp = pt_global(r.learner);
-  const float PT_GAS* op = pt_global(r.opponent) + (size_t)jz * r.zoo.Lz.P;
-  const f32x4 mL = trunk_forward<false, 2>(pi_net((const float*)lp, r.L), xbuf, XS, D, h1, h2, lane);
-  wave_sync();
-  const f32x4 vL = trunk_forward<false, 2>(vf_net((const float*)lp, r.L), xbuf, XS, D, h1, h2, lane);
-  wave_sync();
-  const f32x4 mO = zoo_trunk_forward<2>(pi_net((const float*)op, r.zoo.Lz), r.zoo.filt + (size_t)jz * 2 * Dz, r.zoo.clip, xbuf, XS, Dz, h1, h2, lane);
-  // heads: row 0 = agent 0 (learner acts, zoo net scores), row 1 = agent 1 (zoo net acts, learner scores and values)
-  const bool colk = i < A;
-  const float lsL = colk ? lp[r.L.logstd + i] : 0.0f, lsO = colk ? op[r.zoo.Lz.logstd + i] : 0.0f;
-  const float stdL = expf(lsL), stdO = expf(lsO);
-  const float sumL = row16_sum(lsL), sumO = row16_sum(lsO);
-  const bool ok = colk && kq == 0;                  // rows 0 and 1 live in the first 16 lanes (D layout: rows 4 kq + r)
-  const size_t nz = policy_noise_index(a, e, s, A, i);
-  const float n0 = ok ? pt_global(r.noise0)[nz] : 0.0f, n1 = ok ? pt_global(r.noise1)[nz] : 0.0f;
-  float act0 = 0.0f, act1 = 0.0f;
-  const float nlp0 = gauss_row(mL[0], stdL, sumL, ok, true, n0, act0, A);      // learner samples for agent 0 ...
-  const float onlp0 = gauss_row(mO[0], stdO, sumO, ok, false, 0.0f, act0, A);  // ... the zoo net scores that action
-  const float onlp1 = gauss_row(mO[1], stdO, sumO, ok, true, n1, act1, A);     // zoo net samples for agent 1 ...
-  const float nlp1 = gauss_row(mL[1], stdL, sumL, ok, false, 0.0f, act1, A);   // ... the learner scores it
-  if (ok) policy_commit_actions<true>(c, a, r, e, i, act0, act1, A, slot0, slot1);
-  if (lane == 0) policy_record_scalars(r, slot0, slot1, nlp0, nlp1, onlp0, onlp1, vL[0], vL[1]);
-  wave_sync();   // the action buffer is read back by the env step (other lanes), the scratch region becomes the mass matrix again
-}
-
-// Matches against policy-zoo MLP nets (sumo_match_steps_zoo, POLICY 5; the reference's eval_robosumo_against_fix.py:196-230):
-// agent 0 acts with checkpoint idx0[e] of snaps [nsnap][P] on the raw tile (as rollout_policy_phase_match), agent 1 with zoo net
-// idx1[e] on the tile filtered in place afterwards.  Noise, score counters and quota as sumo_match_steps.
-template <class C, class SA, class RA>
-__device__ __forceinline__ void rollout_policy_phase_match_zoo(C& c, const SA& a, const RA& r, int e, int s) {
-  const int lane = c.lane, i = lane & 15, kq = lane >> 4;
-  const int D = r.L.D, A = r.L.A, XS = r.XS, Dz = r.zoo.Dz;
-  float* xbuf = (float*)(c.sm + r.lds_off);        // [2][XS] | h1 [2][PT_HS] | h2 [2][PT_HS]
-  float* h1 = xbuf + 2 * XS;
-  float* h2 = h1 + 2 * PT_HS;
-  policy_load_obs<false, false>(a, r, e, lane, xbuf, D, XS);
-  wave_sync();
-  const int j0 = policy_checked_row(a, lane, pt_global(r.idx0)[e], r.nsnap);
-  const int j1 = policy_checked_row(a, lane, pt_global(r.idx1)[e], r.zoo.nzoo);
-  const float PT_GAS* p0 = pt_global(r.snaps) + (size_t)j0 * r.L.P;
-  const float PT_GAS* p1 = pt_global(r.opponent) + (size_t)j1 * r.zoo.Lz.P;
-  const f32x4 m0 = trunk_forward<false, 2>(pi_net((const float*)p0, r.L), xbuf, XS, D, h1, h2, lane);
-  wave_sync();
-  const f32x4 m1 = zoo_trunk_forward<2>(pi_net((const float*)p1, r.zoo.Lz), r.zoo.filt + (size_t)j1 * 2 * Dz, r.zoo.clip, xbuf, XS, Dz, h1, h2, lane);
-  const bool ok = i < A && kq == 0;                 // rows 0 and 1 live in the first 16 lanes (D layout: rows 4 kq + r)
-  float act0 = m0[0], act1 = m1[1];
-  if (r.noise0) {
-    const float ls0 = ok ? p0[r.L.logstd + i] : 0.0f, ls1 = ok ? p1[r.zoo.Lz.logstd + i] : 0.0f;
-    const size_t nz = policy_noise_index(a, e, s, A, i);
-    const float n0 = ok ? pt_global(r.noise0)[nz] : 0.0f, n1 = ok ? pt_global(r.noise1)[nz] : 0.0f;
-    (void)gauss_row(m0[0], expf(ls0), 0.0f, ok, true, n0, act0, A);
-    (void)gauss_row(m1[1], expf(ls1), 0.0f, ok, true, n1, act1, A);
-  }
-  if (ok) policy_commit_actions<false>(c, a, r, e, i, act0, act1);
-  wave_sync();   // the action buffer is read back by the env step (other lanes), the scratch region becomes the mass matrix again
-}
-
-// ---- policy-zoo LSTM opponents (POLICY 6 / 7) ----
-// Agent 1's action from zoo LSTM net idx1[e] (policy_zoo LSTMPolicy, policy.py:94-199; ZooLSTMPolicy.act's policy branch -- the value
-// branch v/emb, lstmv is never evaluated): observation filter on the first Dz columns of xrow (agent 1's staged observation, filtered
-// in place), relu embedding (Dz -> 64), BasicLSTMCell(64) in gate order i,j,f,o with the table's forget bias, Gaussian head, noise1
-// (or the mean where noise0 is NULL).  The state row st1[e] (c | h) is zeroed first where AGENT 0's done flag of the previous step is
-// set (policy_zoo._evaluate_against resets the opponent on done[:, 0]) and crosses waves like the LSTM matches' states.  Embedding,
-// gate sums, cell and head run through zoo_lstm_embed / lstm_gates_valu / lstm_cell / lstm_heads_valu in the accumulation order of
-// ppo_lstm_step_kernel<64, PPO_LSTM_GATES_IJFO>: every number equals that kernel bit for bit.  sc: embedding [64] | previous latent
-// [64] | new latent [64] (16-byte aligned LDS).  Lanes < A return their column of the action.
-template <class SA, class RA>
-__device__ __forceinline__ float zoo_lstm_act(const SA& a, const RA& r, int e, int s, int lane, unsigned dn, float* xrow, float* sc) {
-  constexpr int NH = 64, EM = PT_H;
-  const int Dz = r.zl.Dz, A = r.zl.A;
-  const int j1 = policy_checked_row(a, lane, pt_global(r.idx1)[e], r.zl.nzoo);
-  // parameter row: emb_w [Dz][64] | emb_b [64] | kernel [64 + 64][256] (input rows, then recurrent rows) | bias [256] | head_w
-  // [64][A] | head_b [A] | logstd [A]
-  const float PT_GAS* p = pt_global(r.zl.params) + (size_t)j1 * r.zl.Pz;
-  const float PT_GAS* emb_b = p + Dz * EM;
-  const float PT_GAS* wx = emb_b + EM;
-  const float PT_GAS* wh = wx + EM * 4 * NH;
-  const float PT_GAS* b_ = wh + NH * 4 * NH;
-  const float PT_GAS* head_w = b_ + 4 * NH;
-  const float PT_GAS* head_b = head_w + NH * A;
-  float *eb = sc, *hp = sc + EM, *hn = hp + NH;
-  const float keep = 1.0f - (float)(dn & 0xff);
-  float* sp = r.st1 + (size_t)e * 2 * NH;
-  const float cp = hand_load<true>(sp + lane) * keep;          // lane owns the unit `lane`
-  hp[lane] = hand_load<true>(sp + NH + lane) * keep;
-  float bz[4];
-#pragma unroll
-  for (int g = 0; g < 4; g++) bz[g] = b_[g * NH + lane];       // (in flight during the embedding and the gate sums)
-  zoo_lstm_embed(p, emb_b, r.zl.filt + (size_t)j1 * 2 * Dz, r.zl.clip, xrow, Dz, eb, lane);
-  wave_sync();
-  float z[4][1][1];
-  const float* const xr[1] = {eb};
+  const float* const xr[1] = {xo + g * r.XS};
   const float* const hr[1] = {hp};
-  lstm_gates_valu<NH, 1>((const float*)wx, (const float*)wh, r.zl.emb, xr, hr, lane, z);
-  // gate order i, j, f, o: z[1] is the candidate, z[2] the forget gate
-  const LstmCell cl = lstm_cell(z[0][0][0], z[2][0][0], z[3][0][0], z[1][0][0], bz[0], bz[2] + r.zl.forget_bias, bz[3], bz[1], cp);
-  lstm_state_store<NH>(sp, lane, cl);
-  hn[lane] = cl.hn;
+  lstm_gates_valu<NH, 1>(NT->wx, NT->wh, D, xr, hr, lane, z);
+#pragma unroll
+  for (int u = 0; u < 2; u++) {
+    const int j = j0 + u;
+    const LstmCell cl = lstm_cell(z[0][u][0], z[1][u][0], z[2][u][0], z[3][u][0], bz[0][u], bz[1][u] + fb, bz[2][u], bz[3][u], cp[u]);
+    lstm_state_store<NH>(sp, j, cl);                                                // agent g's state after its step
+    hn[j] = cl.hn;
+  }
   wave_sync();
   float m[1];
-  lstm_heads_valu<NH, 1>((const float*)head_w, (const float*)head_w, A, hn, lane, m);   // (lane 16's value sum reads head_w: no value head here)
-  const bool ok = lane < A;
-  const float mean = m[0] + (ok ? head_b[lane] : 0.0f);
-  float act = mean;
+  lstm_heads_valu<NH, 1>(NT->head_w, NT->head_w, A, hn, lane, m);   // (lane 16's value sum reads head_w: the value head stays unread)
+  const float mean = m[0] + (ok ? pt_global(NT->head_b)[lane] : 0.0f);
+  act = mean;
   if (r.noise0) {
-    const float ls = ok ? head_b[A + lane] : 0.0f;
-    const float nz = ok ? pt_global(r.noise1)[policy_noise_index(a, e, s, A, lane)] : 0.0f;
+    const float ls = ok ? pt_global(NT->logstd)[lane] : 0.0f;
+    const float nz = ok ? pt_global(g ? r.noise1 : r.noise0)[policy_noise_index(a, e, s, A, lane)] : 0.0f;
     (void)gauss_row(mean, expf(ls), 0.0f, ok, true, nz, act, A);
   }
-  return act;
+  wave_sync();   // the latent rows are rewritten by whatever acts next
 }
 
-// MLP(64,64) checkpoints against policy-zoo LSTM nets (sumo_match_steps_zoo_lstm, POLICY 6): agent 0 acts with checkpoint idx0[e] of
-// snaps [nsnap][P] on the raw tile, exactly as in rollout_policy_phase_match_zoo; agent 1 through zoo_lstm_act on row 1 of the tile,
-// its rows in the hidden tiles' place once agent 0's trunk is done (no extra LDS).
-template <class C, class SA, class RA>
-__device__ __forceinline__ void rollout_policy_phase_match_zoo_lstm(C& c, const SA& a, const RA& r, int e, int s) {
-  const int lane = c.lane, i = lane & 15, kq = lane >> 4;
+// LSTM match policy phase (sumo_match_steps_lstm, POLICY 3): match_lstm_side for both agents, nets idx0[e] / idx1[e] (an index outside
+// [0, nsnap) raises the abort flag and plays net 0 instead).  No cross-scoring, nothing recorded.
+// LDS (floats, from lds_off): x [2][XS] | previous latent [NH] | new latent [NH].
+template <int NH, class C, class SA, class RA>
+__device__ __forceinline__ void rollout_policy_phase_match_lstm(C& c, const SA& a, const RA& r, int e, int s) {
+  const int lane = c.lane;
+  float* xo = (float*)(c.sm + r.lds_off);
+  float* hp = xo + 2 * r.XS;
+  policy_load_obs<true, false>(a, r, e, lane, xo, r.lnet.ob_dim, r.XS);
+  const unsigned dn = policy_prev_done(a, e);
+  int jn[2];
+  policy_snapshot_rows(a, r, e, lane, jn[0], jn[1]);
+  float act[2];
+#pragma unroll
+  for (int g = 0; g < 2; g++) match_lstm_side<NH>(a, r, e, s, lane, g, jn[g], dn, xo, hp, hp + NH, act[g]);
+  if (lane < r.lnet.ac_dim) policy_commit_actions<false>(c, a, r, e, lane, act[0], act[1]);
+  wave_sync();
+}
+
+// Agent 0 of the MLP matches against policy-zoo nets (POLICY 5 / 6): checkpoint idx0[e] of snaps [nsnap][P] on the raw tile (row 0
+// acts), mean or mean + exp(logstd) * noise0 as rollout_policy_phase_match.  xbuf: [2][XS] | h1 [2][PT_HS] | h2 [2][PT_HS]; column i
+// where ok.
+template <class SA, class RA>
+__device__ __forceinline__ float match_mlp_side0(const SA& a, const RA& r, int e, int s, int lane, int i, bool ok, float* xbuf) {
   const int D = r.L.D, A = r.L.A, XS = r.XS;
-  float* xbuf = (float*)(c.sm + r.lds_off);        // [2][XS] | h1 [2][PT_HS] | h2 [2][PT_HS]
   float* h1 = xbuf + 2 * XS;
   float* h2 = h1 + 2 * PT_HS;
-  policy_load_obs<false, false>(a, r, e, lane, xbuf, D, XS);
-  const unsigned dn = policy_prev_done(a, e);
-  wave_sync();
   const int j0 = policy_checked_row(a, lane, pt_global(r.idx0)[e], r.nsnap);
   const float PT_GAS* p0 = pt_global(r.snaps) + (size_t)j0 * r.L.P;
   const f32x4 m0 = trunk_forward<false, 2>(pi_net((const float*)p0, r.L), xbuf, XS, D, h1, h2, lane);
-  const bool ok = i < A && kq == 0;                 // row 0 lives in the first 16 lanes (D layout: rows 4 kq + r)
   float act0 = m0[0];
   if (r.noise0) {
     const float ls0 = ok ? p0[r.L.logstd + i] : 0.0f;
     const float n0 = ok ? pt_global(r.noise0)[policy_noise_index(a, e, s, A, i)] : 0.0f;
     (void)gauss_row(m0[0], expf(ls0), 0.0f, ok, true, n0, act0, A);
   }
-  wave_sync();   // the hidden tiles become the cell's rows
-  const float act1 = zoo_lstm_act(a, r, e, s, lane, dn, xbuf + XS, xbuf + r.zl.sc_off);
+  return act0;
+}
+
+// Matches against policy-zoo MLP nets (sumo_match_steps_zoo, POLICY 5; the reference's eval_robosumo_against_fix.py:196-230):
+// agent 0 through match_mlp_side0, agent 1 with zoo net idx1[e] on the tile filtered in place afterwards.  Noise, score counters and
+// quota as sumo_match_steps.
+template <class C, class SA, class RA>
+__device__ __forceinline__ void rollout_policy_phase_match_zoo(C& c, const SA& a, const RA& r, int e, int s) {
+  const int lane = c.lane, i = lane & 15, kq = lane >> 4;
+  const int D = r.L.D, A = r.L.A, XS = r.XS;
+  const auto& t = r.zm;
+  float* xbuf = (float*)(c.sm + r.lds_off);        // [2][XS] | h1 [2][PT_HS] | h2 [2][PT_HS]
+  float* h1 = xbuf + 2 * XS;
+  float* h2 = h1 + 2 * PT_HS;
+  policy_load_obs<false, false>(a, r, e, lane, xbuf, D, XS);
+  wave_sync();
+  const bool ok = i < A && kq == 0;                 // rows 0 and 1 live in the first 16 lanes (D layout: rows 4 kq + r)
+  const float act0 = match_mlp_side0(a, r, e, s, lane, i, ok, xbuf);
+  wave_sync();   // the raw tile is filtered in place
+  const int j1 = policy_checked_row(a, lane, pt_global(r.idx1)[e], t.n);
+  const float PT_GAS* p1 = pt_global(t.params) + (size_t)j1 * t.L.P;
+  const f32x4 m1 = zoo_trunk_forward<2>(pi_net((const float*)p1, t.L), t.filt + (size_t)j1 * 2 * t.D, t.clip, xbuf, XS, t.D, h1, h2, lane);
+  float act1 = m1[1];
+  if (r.noise0) {
+    const float ls1 = ok ? p1[t.L.logstd + i] : 0.0f;
+    const float n1 = ok ? pt_global(r.noise1)[policy_noise_index(a, e, s, A, i)] : 0.0f;
+    (void)gauss_row(m1[1], expf(ls1), 0.0f, ok, true, n1, act1, A);
+  }
   if (ok) policy_commit_actions<false>(c, a, r, e, i, act0, act1);
   wave_sync();   // the action buffer is read back by the env step (other lanes), the scratch region becomes the mass matrix again
 }
 
-// LSTM(128) checkpoints against policy-zoo LSTM nets (sumo_match_steps_lstm_zoo_lstm, POLICY 7): agent 0 is side 0 of
-// rollout_policy_phase_match_lstm<128> (net idx0[e] of onets on (obs 0, st0[e] masked by its done flag)); agent 1 through
-// zoo_lstm_act on row 1 of the tile, its rows in the latent rows' place once agent 0's head is done.  Agent 0's block below is the
-// g = 0 pass of that function's side loop written out, not a helper both call: the loop there is unrolled over both sides with
-// shared index checks, and moving its body into a function is a source change to mode 3, whose code objects have to stay as
-// they are.  Any change to one of the two goes into the other; tests/test_gpu_zoo_lstm_fused.py compares mode 7 with the same
-// ppo_lstm_step launches that tests/test_gpu_matches_lstm.py compares mode 3 with.
-template <int NH, class C, class SA, class RA>
-__device__ __forceinline__ void rollout_policy_phase_match_lstm_zoo_lstm(C& c, const SA& a, const RA& r, int e, int s) {
-  const int lane = c.lane;
-  const int D = r.lnet.ob_dim, A = r.lnet.ac_dim, XS = r.XS;
-  float* xo = (float*)(c.sm + r.lds_off);
-  float* hp = xo + 2 * XS;
-  float* hn = hp + NH;
-  policy_load_obs<true, false>(a, r, e, lane, xo, D, XS);
-  const unsigned dn = policy_prev_done(a, e);
-  const int jn = policy_checked_row(a, lane, pt_global(r.idx0)[e], r.nsnap);
-  const bool ok = lane < A;
-  const int j0 = 2 * lane;                           // lane owns the units 2 lane, 2 lane + 1
-  float act0;
-  {
-    const ppo_lstm_net PT_GAS* NT = pt_global(r.onets) + jn;
-    const float keep = 1.0f - (float)(dn & 0xff);
-    float* sp = r.st0 + (size_t)e * 2 * NH;
-    float cp[2];
-    lstm_state_pair(sp + j0, keep, cp);
-    lstm_state_pair(sp + NH + j0, keep, hp + j0);
-    const float PT_GAS* b_ = pt_global(NT->b);
-    const float fb = NT->forget_bias;
-    float z[4][2][1], bz[4][2];
-    lstm_bias_pair<NH>(b_, j0, bz);
-    wave_sync();
-    const float* const xr[1] = {xo};
-    const float* const hr[1] = {hp};
-    lstm_gates_valu<NH, 1>(NT->wx, NT->wh, D, xr, hr, lane, z);
-#pragma unroll
-    for (int u = 0; u < 2; u++) {
-      const int j = j0 + u;
-      const LstmCell cl = lstm_cell(z[0][u][0], z[1][u][0], z[2][u][0], z[3][u][0], bz[0][u], bz[1][u] + fb, bz[2][u], bz[3][u], cp[u]);
-      lstm_state_store<NH>(sp, j, cl);                                              // agent 0's state after its step
-      hn[j] = cl.hn;
-    }
-    wave_sync();
-    float m[1];
-    lstm_heads_valu<NH, 1>(NT->head_w, NT->head_w, A, hn, lane, m);   // (lane 16's value sum reads head_w: the value head stays unread)
-    const float mean = m[0] + (ok ? pt_global(NT->head_b)[lane] : 0.0f);
-    act0 = mean;
-    if (r.noise0) {
-      const float ls = ok ? pt_global(NT->logstd)[lane] : 0.0f;
-      const float nz = ok ? pt_global(r.noise0)[policy_noise_index(a, e, s, A, lane)] : 0.0f;
-      (void)gauss_row(mean, expf(ls), 0.0f, ok, true, nz, act0, A);
-    }
-    wave_sync();   // the latent rows become the zoo cell's rows
-  }
-  const float act1 = zoo_lstm_act(a, r, e, s, lane, dn, xo + XS, xo + r.zl.sc_off);
-  if (ok) policy_commit_actions<false>(c, a, r, e, lane, act0, act1);
-  wave_sync();
-}
-
-// ---- rollout against policy-zoo LSTM nets (POLICY 8) ----
-// Mean of the Gaussian head of zoo LSTM net row p (the row layout of zoo_lstm_act) on ONE staged observation row: xrow is filtered in
-// place, then embedding, gate sums, cell and head as in zoo_lstm_act -- the accumulation order of
-// ppo_lstm_step_kernel<64, PPO_LSTM_GATES_IJFO>.  STATE: the previous state is the row sp (c | h) masked by `keep`, and the new state
-// is written back to it (hand-over accesses: the row crosses waves); otherwise the cell starts from zeros and nothing is written --
-// the recurrent half of the gate sum still runs, over a zero row, so the additions stay the step kernel's.  q: the launch's
-// ZooLstmArgs, sc as in zoo_lstm_act.  Lanes < A return their column.  (zoo_lstm_act is not rebuilt on top of this function: modes
-// 6 / 7 keep their code objects.)
-template <bool STATE, class ZA>
-__device__ __forceinline__ float zoo_lstm_mean(const ZA& q, const float PT_GAS* p, const float* filt, float* sp, float keep, float* xrow,
-                                               float* sc, int lane) {
+// Mean of the Gaussian head of zoo LSTM net row p of table t (policy_zoo LSTMPolicy, policy.py:94-199; ZooLSTMPolicy.act's policy
+// branch -- the value branch v/emb, lstmv is never evaluated) on ONE staged observation row: observation filter on the first t.D
+// columns of xrow (filtered in place), relu embedding (t.D -> 64), BasicLSTMCell(64) in gate order i,j,f,o with the table's forget
+// bias, head.  Embedding, gate sums, cell and head run through zoo_lstm_embed / lstm_gates_valu / lstm_cell / lstm_heads_valu in the
+// accumulation order of ppo_lstm_step_kernel<64, PPO_LSTM_GATES_IJFO>: every number equals that kernel bit for bit.  Parameter row:
+// emb_w [D][64] | emb_b [64] | kernel [64 + 64][256] (input rows, then recurrent rows) | bias [256] | head_w [64][A] | head_b [A] |
+// logstd [A].  STATE: the previous state is the row sp (c | h) masked by `keep`, and the new state is written back to it (hand-over
+// accesses: the row crosses waves); otherwise the cell starts from zeros and nothing is written -- the recurrent half of the gate
+// sum still runs, over a zero row, so the additions stay the step kernel's.  sc: embedding [64] | previous latent [64] | new latent
+// [64] (16-byte aligned LDS).  Lanes < A return their column.
+template <bool STATE, class ZT>   // ZT: ZooLstmTable as the launch arguments hold it (constant address space)
+__device__ __forceinline__ float zoo_lstm_mean(const ZT& t, const float PT_GAS* p, const float* filt, float* sp, float keep,
+                                               float* xrow, float* sc, int lane) {
   constexpr int NH = 64, EM = PT_H;
-  const int Dz = q.Dz, A = q.A;
+  const int Dz = t.D, A = t.A;
   const float PT_GAS* emb_b = p + Dz * EM;
   const float PT_GAS* wx = emb_b + EM;
   const float PT_GAS* wh = wx + EM * 4 * NH;
@@ -3208,14 +3009,14 @@ __device__ __forceinline__ float zoo_lstm_mean(const ZA& q, const float PT_GAS* 
   float bz[4];
 #pragma unroll
   for (int g = 0; g < 4; g++) bz[g] = b_[g * NH + lane];       // (in flight during the embedding and the gate sums)
-  zoo_lstm_embed(p, emb_b, filt, q.clip, xrow, Dz, eb, lane);
+  zoo_lstm_embed(p, emb_b, filt, t.clip, xrow, Dz, eb, lane);
   wave_sync();
   float z[4][1][1];
   const float* const xr[1] = {eb};
   const float* const hr[1] = {hp};
-  lstm_gates_valu<NH, 1>((const float*)wx, (const float*)wh, q.emb, xr, hr, lane, z);
+  lstm_gates_valu<NH, 1>((const float*)wx, (const float*)wh, t.emb, xr, hr, lane, z);
   // gate order i, j, f, o: z[1] is the candidate, z[2] the forget gate
-  const LstmCell cl = lstm_cell(z[0][0][0], z[2][0][0], z[3][0][0], z[1][0][0], bz[0], bz[2] + q.forget_bias, bz[3], bz[1], cp);
+  const LstmCell cl = lstm_cell(z[0][0][0], z[2][0][0], z[3][0][0], z[1][0][0], bz[0], bz[2] + t.forget_bias, bz[3], bz[1], cp);
   if constexpr (STATE) lstm_state_store<NH>(sp, lane, cl);
   hn[lane] = cl.hn;
   wave_sync();
@@ -3224,90 +3025,116 @@ __device__ __forceinline__ float zoo_lstm_mean(const ZA& q, const float PT_GAS* 
   return m[0] + (lane < A ? head_b[lane] : 0.0f);
 }
 
-// Rollout against a policy-zoo LSTM net (sumo_rollout_steps_zoo_lstm, POLICY 8; learn(opponent_mode='fix') with an LSTM file):
-// rollout_policy_phase_zoo with the zoo MLP trunk replaced by the policy branch of zoo LSTM net opp_idx[e].  The learner's policy and
-// value trunks run on the raw tile, both rows (the raw observations are in the rollout record by then) and agent 0's action is
-// sampled; the hidden tiles then become the cell's rows (r.zlr.sc_off, as in mode 6: no extra LDS).  The zoo net acts on row 1 from
-// the env's state row st1[e], masked by AGENT 1's done flag of the previous step (the Runner's M = dones[:, 1]) and updated in place;
-// it then scores agent 0's action on row 0 from a zero state, writing no state (the Runner's scoring calls feed no state).  Both rows
-// are filtered in place; the record holds the raw ones.  The launch fields travel in RolloutArgs::zlr (the lnet union: the learner
-// is an MLP), since this mode needs the six record pointers r.zl overlays.  Every recorded number equals ppo_forward (learner) /
-// ppo_lstm_step (zoo net) bit for bit.
+// Agent 1 of the matches against policy-zoo LSTM nets (POLICY 6 / 7): zoo net idx1[e] acts on xrow (agent 1's staged observation) from
+// the state row st1[e], which is zeroed first where AGENT 0's done flag of the previous step is set (policy_zoo._evaluate_against
+// resets the opponent on done[:, 0]; the rollouts mask with agent 1's flag, so zoo_lstm_mean takes `keep`); noise1, or the mean where
+// noise0 is NULL.  Lanes < A return their column of the action.
+template <class SA, class RA>
+__device__ __forceinline__ float zoo_lstm_act(const SA& a, const RA& r, int e, int s, int lane, unsigned dn, float* xrow, float* sc) {
+  const auto& t = r.zl;
+  const int A = t.A;
+  const int j1 = policy_checked_row(a, lane, pt_global(r.idx1)[e], t.n);
+  const float PT_GAS* p = pt_global(t.params) + (size_t)j1 * t.P;
+  const float keep = 1.0f - (float)(dn & 0xff);
+  const float mean = zoo_lstm_mean<true>(t, p, t.filt + (size_t)j1 * 2 * t.D, r.st1 + (size_t)e * 128, keep, xrow, sc, lane);
+  const bool ok = lane < A;
+  float act = mean;
+  if (r.noise0) {
+    const float ls = ok ? p[t.P - A + lane] : 0.0f;   // the row ends with logstd [A]
+    const float nz = ok ? pt_global(r.noise1)[policy_noise_index(a, e, s, A, lane)] : 0.0f;
+    (void)gauss_row(mean, expf(ls), 0.0f, ok, true, nz, act, A);
+  }
+  return act;
+}
+
+// MLP(64,64) checkpoints against policy-zoo LSTM nets (sumo_match_steps_zoo_lstm, POLICY 6): agent 0 through match_mlp_side0; agent 1
+// through zoo_lstm_act on row 1 of the tile, its rows in the hidden tiles' place once agent 0's trunk is done (no extra LDS).
 template <class C, class SA, class RA>
-__device__ __forceinline__ void rollout_policy_phase_zoo_lstm(C& c, const SA& a, const RA& r, int e, int s) {
+__device__ __forceinline__ void rollout_policy_phase_match_zoo_lstm(C& c, const SA& a, const RA& r, int e, int s) {
   const int lane = c.lane, i = lane & 15, kq = lane >> 4;
-  const int D = r.L.D, A = r.L.A, XS = r.XS;
-  const auto& q = r.zlr;
   float* xbuf = (float*)(c.sm + r.lds_off);        // [2][XS] | h1 [2][PT_HS] | h2 [2][PT_HS]
-  float* h1 = xbuf + 2 * XS;
-  float* h2 = h1 + 2 * PT_HS;
-  const size_t col = (size_t)r.env_offset + e;
-  const size_t slot0 = ((size_t)0 * r.T + s) * r.Ntot + col, slot1 = ((size_t)1 * r.T + s) * r.Ntot + col;
-  policy_load_obs<false, true>(a, r, e, lane, xbuf, D, XS, slot0, slot1);
+  policy_load_obs<false, false>(a, r, e, lane, xbuf, r.L.D, r.XS);
   const unsigned dn = policy_prev_done(a, e);
-  if (lane < 2) policy_record_done(r, lane, slot0, slot1, dn);
   wave_sync();
-  const int jz = policy_checked_row(a, lane, r.opp_idx ? pt_global(r.opp_idx)[e] : 0, q.nzoo);
-  const float PT_GAS* lp = pt_global(r.learner);
-  const f32x4 mL4 = trunk_forward<false, 2>(pi_net((const float*)lp, r.L), xbuf, XS, D, h1, h2, lane);
-  const float mL0 = mL4[0], mL1 = mL4[1];
-  wave_sync();
-  const f32x4 vL4 = trunk_forward<false, 2>(vf_net((const float*)lp, r.L), xbuf, XS, D, h1, h2, lane);
-  const float vL0 = vL4[0], vL1 = vL4[1];
-  // heads: row 0 = agent 0 (learner acts, zoo net scores), row 1 = agent 1 (zoo net acts, learner scores and values)
-  const bool colk = i < A;
-  const bool ok = colk && kq == 0;                  // rows 0 and 1 live in the first 16 lanes (D layout: rows 4 kq + r)
-  const float lsL = colk ? lp[r.L.logstd + i] : 0.0f;
-  const float stdL = expf(lsL), sumL = row16_sum(lsL);
-  const size_t nz = policy_noise_index(a, e, s, A, i);
-  float act0 = 0.0f, act1 = 0.0f;
-  const float nlp0 = gauss_row(mL0, stdL, sumL, ok, true, ok ? pt_global(r.noise0)[nz] : 0.0f, act0, A);   // learner samples for agent 0
+  const bool ok = i < r.L.A && kq == 0;             // row 0 lives in the first 16 lanes (D layout: rows 4 kq + r)
+  const float act0 = match_mlp_side0(a, r, e, s, lane, i, ok, xbuf);
   wave_sync();   // the hidden tiles become the cell's rows
-  const float PT_GAS* zp = pt_global(q.params) + (size_t)jz * q.Pz;
-  const float* zf = q.filt + (size_t)jz * 2 * q.Dz;
-  float* sc = xbuf + q.sc_off;
-  const float lsO = ok ? zp[q.Pz - A + i] : 0.0f;   // the row ends with logstd [A]
-  const float stdO = expf(lsO), sumO = row16_sum(lsO);
-  const float keep1 = 1.0f - (float)((dn >> 8) & 0xff);
-  const float mO1 = zoo_lstm_mean<true>(q, zp, zf, r.st1 + (size_t)e * 128, keep1, xbuf + XS, sc, lane);
-  const float onlp1 = gauss_row(mO1, stdO, sumO, ok, true, ok ? pt_global(r.noise1)[nz] : 0.0f, act1, A);   // zoo net samples for agent 1 ...
-  const float nlp1 = gauss_row(mL1, stdL, sumL, ok, false, 0.0f, act1, A);                                  // ... the learner scores it
-  wave_sync();   // the cell's rows are rewritten by the scoring pass
-  const float mO0 = zoo_lstm_mean<false>(q, zp, zf, nullptr, 0.0f, xbuf, sc, lane);
-  const float onlp0 = gauss_row(mO0, stdO, sumO, ok, false, 0.0f, act0, A);                                 // the zoo net scores agent 0's action
-  if (ok) policy_commit_actions<true>(c, a, r, e, i, act0, act1, A, slot0, slot1);
-  if (lane == 0) policy_record_scalars(r, slot0, slot1, nlp0, nlp1, onlp0, onlp1, vL0, vL1);
+  const float act1 = zoo_lstm_act(a, r, e, s, lane, dn, xbuf + r.XS, xbuf + r.zl.sc_off);
+  if (ok) policy_commit_actions<false>(c, a, r, e, i, act0, act1);
   wave_sync();   // the action buffer is read back by the env step (other lanes), the scratch region becomes the mass matrix again
 }
 
-// ---- rollout of a recurrent learner against policy-zoo nets (POLICY 9 / 10) ----
-// learn(network='lstm', opponent_mode='fix') inside the launch (sumo_rollout_steps_lstm_zoo: ZLSTM false, a zoo MLP net;
-// sumo_rollout_steps_lstm_zoo_lstm: ZLSTM true, a zoo LSTM net).  Four evaluations per step, the learner's two in one pass over its
-// weights:
-//   learner: row C = (obs 0, agent 0's state)  -> action 0, neglogp, value, agent 0's new state   (row C of rollout_policy_phase_lstm)
-//            row E = (obs 1, zero state)       -> the learner's likelihood AND value of action 1  (its row E; there is no row D: a
-//                                                 zoo net's state is not the learner's, so the zero-state evaluation also values)
-//   zoo net: on obs 0 scores action 0 (LSTM: from a zero state, nothing written); on obs 1 acts (LSTM: from its row of st1, masked by
-//            AGENT 1's done flag of the previous step and advanced in place), as modes 4 / 8.
-// The learner reads the raw tile first (it is in the record by then); only then the zoo net filters the rows in place, its hidden
-// tiles (MLP: [2][PT_HS] twice) or cell rows (LSTM: zt.sc_off, three rows of 64) in the place of the learner's latent rows.  The
-// zoo row comes from tile_net per 16-env tile of the whole env set, as the snapshot of mode 1.  Every number equals the
-// ppo_lstm_step (learner, zoo LSTM net) / ppo_forward_filtered (zoo MLP net) launches of the step-by-step path bit for bit.
-// LDS (floats, from lds_off): x [2][XS] | zero row [NH] | agent 0's previous latent [NH] | new latents [2][NH].
-template <int NH, bool ZLSTM, class C, class SA, class RA>
-__device__ __forceinline__ void rollout_policy_phase_lstm_zoo(C& c, const SA& a, const RA& r, int e, int s) {
+// LSTM(128) checkpoints against policy-zoo LSTM nets (sumo_match_steps_lstm_zoo_lstm, POLICY 7): agent 0 is side 0 of mode 3
+// (match_lstm_side: net idx0[e] of onets); agent 1 through zoo_lstm_act on row 1 of the tile, its rows in the latent rows' place once
+// agent 0's head is done.
+template <int NH, class C, class SA, class RA>
+__device__ __forceinline__ void rollout_policy_phase_match_lstm_zoo_lstm(C& c, const SA& a, const RA& r, int e, int s) {
   const int lane = c.lane;
-  const auto& NL = r.lnet;
-  const auto& q = r.zt;
-  const int D = NL.ob_dim, A = NL.ac_dim, XS = r.XS;
   float* xo = (float*)(c.sm + r.lds_off);
+  float* hp = xo + 2 * r.XS;
+  policy_load_obs<true, false>(a, r, e, lane, xo, r.lnet.ob_dim, r.XS);
+  const unsigned dn = policy_prev_done(a, e);
+  const int jn = policy_checked_row(a, lane, pt_global(r.idx0)[e], r.nsnap);
+  float act0;
+  match_lstm_side<NH>(a, r, e, s, lane, 0, jn, dn, xo, hp, hp + NH, act0);
+  const float act1 = zoo_lstm_act(a, r, e, s, lane, dn, xo + r.XS, xo + r.zl.sc_off);
+  if (lane < r.lnet.ac_dim) policy_commit_actions<false>(c, a, r, e, lane, act0, act1);
+  wave_sync();
+}
+
+// ---- rollouts against policy-zoo nets (POLICY 4, 8 .. 12): a learner front, then a zoo pass ----
+// What a learner front leaves for the zoo pass and the record: agent 0's sampled action (column of the lane) and its neglogp, the
+// learner's mean on row 1 (to score agent 1's action), exp(logstd) / sum(logstd), the values of both rows.
+struct LearnerFront { float nlp0, mL1, stdL, sumL, v0, v1, act0; };
+
+// MLP(64,64) learner (POLICY 4, 8, 11): the raw tile (no padding) into LDS and the record, the done flags (returned in dn) into the
+// record, policy and value trunks on both rows, agent 0's action sampled.  Heads are indexed by i = lane & 15: rows 0 and 1 live in
+// the first 16 lanes (D layout: rows 4 kq + r).  xbuf: [2][XS] | h1 [2][PT_HS] | h2 [2][PT_HS].  Every number equals ppo_forward.
+template <class SA, class RA>
+__device__ __forceinline__ LearnerFront mlp_learner_front(const SA& a, const RA& r, int e, int s, int lane, float* xbuf, size_t slot0,
+                                                          size_t slot1, unsigned& dn) {
+  const int i = lane & 15, kq = lane >> 4;
+  const int D = r.L.D, A = r.L.A, XS = r.XS;
+  float* h1 = xbuf + 2 * XS;
+  float* h2 = h1 + 2 * PT_HS;
+  policy_load_obs<false, true>(a, r, e, lane, xbuf, D, XS, slot0, slot1);
+  dn = policy_prev_done(a, e);
+  if (lane < 2) policy_record_done(r, lane, slot0, slot1, dn);
+  wave_sync();
+  const float PT_GAS* lp = pt_global(r.learner);
+  LearnerFront f;
+  const f32x4 mL4 = trunk_forward<false, 2>(pi_net((const float*)lp, r.L), xbuf, XS, D, h1, h2, lane);
+  const float mL0 = mL4[0];
+  f.mL1 = mL4[1];
+  wave_sync();
+  const f32x4 vL4 = trunk_forward<false, 2>(vf_net((const float*)lp, r.L), xbuf, XS, D, h1, h2, lane);
+  f.v0 = vL4[0]; f.v1 = vL4[1];
+  const bool colk = i < A;
+  const bool ok = colk && kq == 0;
+  const float lsL = colk ? lp[r.L.logstd + i] : 0.0f;
+  f.stdL = expf(lsL); f.sumL = row16_sum(lsL);
+  f.act0 = 0.0f;
+  f.nlp0 = gauss_row(mL0, f.stdL, f.sumL, ok, true, ok ? pt_global(r.noise0)[policy_noise_index(a, e, s, A, i)] : 0.0f, f.act0, A);
+  return f;
+}
+
+// LSTM(128) learner (POLICY 9, 10, 12): the zero-padded tile and the done flags as above, then two evaluations in one pass over the
+// learner's weights:
+//   row C = (obs 0, agent 0's state)  -> action 0, neglogp, value, agent 0's new state   (row C of rollout_policy_phase_lstm)
+//   row E = (obs 1, zero state)       -> the learner's likelihood AND value of action 1  (its row E; there is no row D: a zoo net's
+//                                        state is not the learner's, so the zero-state evaluation also values)
+// Heads are indexed by the lane (lanes < A).  xo: x [2][XS] | zero row [NH] | agent 0's previous latent [NH] | new latents [2][NH].
+// Every number equals ppo_lstm_step.
+template <int NH, class SA, class RA>
+__device__ __forceinline__ LearnerFront lstm_learner_front(const SA& a, const RA& r, int e, int s, int lane, float* xo, size_t slot0,
+                                                           size_t slot1, unsigned& dn) {
+  const auto& NL = r.lnet;
+  const int D = NL.ob_dim, A = NL.ac_dim, XS = r.XS;
   float* hz = xo + 2 * XS;
   float* hp = hz + NH;
   float* hn = hp + NH;
-  const size_t col = (size_t)r.env_offset + e;
-  const size_t slot0 = ((size_t)0 * r.T + s) * r.Ntot + col, slot1 = ((size_t)1 * r.T + s) * r.Ntot + col;
   policy_load_obs<true, true>(a, r, e, lane, xo, D, XS, slot0, slot1);
-  const unsigned dn = policy_prev_done(a, e);
+  dn = policy_prev_done(a, e);
   if (lane < 2) policy_record_done(r, lane, slot0, slot1, dn);
   const float keep0 = 1.0f - (float)(dn & 0xff);
   float* s0p = r.st0 + (size_t)e * 2 * NH;
@@ -3317,220 +3144,131 @@ __device__ __forceinline__ void rollout_policy_phase_lstm_zoo(C& c, const SA& a,
   lstm_state_pair(s0p + NH + j0, keep0, hp + j0);
   hz[j0] = 0.0f; hz[j0 + 1] = 0.0f;
   wave_sync();
-  const int jz = policy_checked_row(a, lane, r.tile_net ? pt_global(r.tile_net)[col >> 4] : 0, q.nzoo);
   const bool ok = lane < A;
-  const size_t nz = policy_noise_index(a, e, s, A, lane);
-  float act0 = 0.0f, act1 = 0.0f;
-  float nlp0, mL1, stdL, sumL, v0, v1;
-  {  // ---- learner net: rows C, E
-    const float fb = NL.forget_bias;
-    float z[4][2][2], bz[4][2];
-    lstm_bias_pair<NH>(pt_global(NL.b), j0, bz);   // (in flight during the gate sums)
-    const float* const xr[2] = {xo, xo + XS};
-    const float* const hr[2] = {hp, hz};
-    lstm_gates_valu<NH, 2>(NL.wx, NL.wh, D, xr, hr, lane, z);
+  const float fb = NL.forget_bias;
+  float z[4][2][2], bz[4][2];
+  lstm_bias_pair<NH>(pt_global(NL.b), j0, bz);   // (in flight during the gate sums)
+  const float* const xr[2] = {xo, xo + XS};
+  const float* const hr[2] = {hp, hz};
+  lstm_gates_valu<NH, 2>(NL.wx, NL.wh, D, xr, hr, lane, z);
 #pragma unroll
-    for (int u = 0; u < 2; u++) {
-      const int j = j0 + u;
-      const float bi = bz[0][u], bf = bz[1][u] + fb, bo = bz[2][u], bu = bz[3][u];   // gate order i, f, o, u
-      const LstmCell cc = lstm_cell(z[0][u][0], z[1][u][0], z[2][u][0], z[3][u][0], bi, bf, bo, bu, c0[u]);
-      const LstmCell ce = lstm_cell(z[0][u][1], z[1][u][1], z[2][u][1], z[3][u][1], bi, bf, bo, bu, hz[j]);
-      lstm_state_store<NH>(s0p, j, cc);                                              // agent 0's state after the learner's step
-      hn[j] = cc.hn; hn[NH + j] = ce.hn;
-    }
-    wave_sync();
-    float m[2];
-    lstm_heads_valu<NH, 2>(NL.head_w, NL.vf_w, A, hn, lane, m);
-    const float hb = ok ? pt_global(NL.head_b)[lane] : 0.0f, ls = ok ? pt_global(NL.logstd)[lane] : 0.0f;
-    stdL = expf(ls); sumL = row16_sum(ls);
-    const float vb = pt_global(NL.vf_b)[0];
-    v0 = __shfl(m[0], 16) + vb; v1 = __shfl(m[1], 16) + vb;
-    mL1 = m[1] + hb;
-    const float n0 = ok ? pt_global(r.noise0)[nz] : 0.0f;
-    nlp0 = gauss_row(m[0] + hb, stdL, sumL, ok, true, n0, act0, A);      // the learner samples for agent 0
-    wave_sync();   // the raw tile is filtered in place and the latent rows are rewritten by the zoo net's pass
+  for (int u = 0; u < 2; u++) {
+    const int j = j0 + u;
+    const float bi = bz[0][u], bf = bz[1][u] + fb, bo = bz[2][u], bu = bz[3][u];   // gate order i, f, o, u
+    const LstmCell cc = lstm_cell(z[0][u][0], z[1][u][0], z[2][u][0], z[3][u][0], bi, bf, bo, bu, c0[u]);
+    const LstmCell ce = lstm_cell(z[0][u][1], z[1][u][1], z[2][u][1], z[3][u][1], bi, bf, bo, bu, hz[j]);
+    lstm_state_store<NH>(s0p, j, cc);                                              // agent 0's state after the learner's step
+    hn[j] = cc.hn; hn[NH + j] = ce.hn;
   }
-  const float n1 = ok ? pt_global(r.noise1)[nz] : 0.0f;
-  const float PT_GAS* zp = pt_global(r.opponent) + (size_t)jz * q.Pz;
-  const float* zf = q.filt + (size_t)jz * 2 * q.Dz;
-  float onlp0, onlp1, nlp1;
-  if constexpr (ZLSTM) {
-    float* sc = xo + q.sc_off;
-    const float lsO = ok ? zp[q.Pz - A + lane] : 0.0f;   // the row ends with logstd [A]
-    const float stdO = expf(lsO), sumO = row16_sum(lsO);
-    const float keep1 = 1.0f - (float)((dn >> 8) & 0xff);
-    const float mO1 = zoo_lstm_mean<true>(q, zp, zf, r.st1 + (size_t)e * 128, keep1, xo + XS, sc, lane);
-    onlp1 = gauss_row(mO1, stdO, sumO, ok, true, n1, act1, A);           // the zoo net samples for agent 1 ...
-    nlp1 = gauss_row(mL1, stdL, sumL, ok, false, 0.0f, act1, A);         // ... the learner (zero state) scores it
-    wave_sync();   // the cell's rows are rewritten by the scoring pass
-    const float mO0 = zoo_lstm_mean<false>(q, zp, zf, nullptr, 0.0f, xo, sc, lane);
-    onlp0 = gauss_row(mO0, stdO, sumO, ok, false, 0.0f, act0, A);        // the zoo net (zero state) scores agent 0's action
-  } else {
-    float* h1 = xo + 2 * XS;                         // [2][PT_HS] | h2 [2][PT_HS]
-    float* h2 = h1 + 2 * PT_HS;
-    const f32x4 mO = zoo_trunk_forward<2>(pi_net((const float*)zp, r.L), zf, q.clip, xo, XS, q.Dz, h1, h2, lane);
-    const float lsO = ok ? zp[r.L.logstd + lane] : 0.0f;
-    const float stdO = expf(lsO), sumO = row16_sum(lsO);
-    onlp0 = gauss_row(mO[0], stdO, sumO, ok, false, 0.0f, act0, A);      // the zoo net scores agent 0's action
-    onlp1 = gauss_row(mO[1], stdO, sumO, ok, true, n1, act1, A);         // the zoo net samples for agent 1 ...
-    nlp1 = gauss_row(mL1, stdL, sumL, ok, false, 0.0f, act1, A);         // ... the learner (zero state) scores it
-  }
-  if (ok) policy_commit_actions<true>(c, a, r, e, lane, act0, act1, A, slot0, slot1);
-  if (lane == 0) policy_record_scalars(r, slot0, slot1, nlp0, nlp1, onlp0, onlp1, v0, v1);
-  wave_sync();   // the action buffer is read back by the env step (other lanes), the scratch region is the step's again
+  wave_sync();
+  float m[2];
+  lstm_heads_valu<NH, 2>(NL.head_w, NL.vf_w, A, hn, lane, m);
+  const float hb = ok ? pt_global(NL.head_b)[lane] : 0.0f, ls = ok ? pt_global(NL.logstd)[lane] : 0.0f;
+  LearnerFront f;
+  f.stdL = expf(ls); f.sumL = row16_sum(ls);
+  const float vb = pt_global(NL.vf_b)[0];
+  f.v0 = __shfl(m[0], 16) + vb; f.v1 = __shfl(m[1], 16) + vb;
+  f.mL1 = m[1] + hb;
+  f.act0 = 0.0f;
+  f.nlp0 = gauss_row(m[0] + hb, f.stdL, f.sumL, ok, true, ok ? pt_global(r.noise0)[policy_noise_index(a, e, s, A, lane)] : 0.0f, f.act0, A);
+  return f;
 }
 
-// ---- rollout against a league of policy-zoo nets, MLP and LSTM mixed (POLICY 11 / 12) ----
+// The zoo side of a rollout step, once the learner has read the raw tile and sampled act0 (and a wave_sync has passed): the zoo net
+// scores agent 0's action on row 0 (onlp0), samples agent 1's on row 1 (act1, onlp1), and the learner scores that one (nlp1).  Column
+// i where ok, from the caller's front (ok implies i == lane).  xbuf: x [2][XS] followed by the scratch the pass needs.
+// zoo_mlp_pass: row jz of the MLP table -- its tanh trunk of input width zm.D on both rows of the tile, filtered in place
+// (zoo_trunk_forward: no second tile; the hidden tiles [2][PT_HS] twice behind the tile); the zoo net's value trunk is not
+// evaluated.  Every number equals ppo_forward_filtered.
+template <class SA, class RA>
+__device__ __forceinline__ void zoo_mlp_pass(const SA& a, const RA& r, int e, int s, int lane, int i, bool ok, int jz, float* xbuf, int A,
+                                             const LearnerFront& f, float& act1, float& onlp0, float& onlp1, float& nlp1) {
+  const auto& t = r.zm;
+  const int XS = r.XS;
+  float* h1 = xbuf + 2 * XS;
+  float* h2 = h1 + 2 * PT_HS;
+  const float PT_GAS* zp = pt_global(t.params) + (size_t)jz * t.L.P;
+  const f32x4 mO = zoo_trunk_forward<2>(pi_net((const float*)zp, t.L), t.filt + (size_t)jz * 2 * t.D, t.clip, xbuf, XS, t.D, h1, h2, lane);
+  const float lsO = ok ? zp[t.L.logstd + i] : 0.0f;
+  const float stdO = expf(lsO), sumO = row16_sum(lsO);
+  const float n1 = ok ? pt_global(r.noise1)[policy_noise_index(a, e, s, A, i)] : 0.0f;
+  float act0 = f.act0;
+  onlp0 = gauss_row(mO[0], stdO, sumO, ok, false, 0.0f, act0, A);        // the zoo net scores agent 0's action
+  onlp1 = gauss_row(mO[1], stdO, sumO, ok, true, n1, act1, A);           // the zoo net samples for agent 1 ...
+  nlp1 = gauss_row(f.mL1, f.stdL, f.sumL, ok, false, 0.0f, act1, A);     // ... the learner scores it
+}
+
+// zoo_lstm_pass: row jz of the LSTM table -- zoo_lstm_mean on row 1 from the env's state row st1[e], masked by AGENT 1's done flag of
+// the previous step (the Runner's M = dones[:, 1]) and advanced in place, then on row 0 from a zero state, writing no state (the
+// Runner's scoring calls feed no state); cell rows at zl.sc_off, in the place of the learner's hidden tiles / latent rows.  Every
+// number equals ppo_lstm_step.
+template <class SA, class RA>
+__device__ __forceinline__ void zoo_lstm_pass(const SA& a, const RA& r, int e, int s, int lane, int i, bool ok, int jz, unsigned dn,
+                                              float* xbuf, int A, const LearnerFront& f, float& act1, float& onlp0, float& onlp1, float& nlp1) {
+  const auto& t = r.zl;
+  const float PT_GAS* zp = pt_global(t.params) + (size_t)jz * t.P;
+  const float* zf = t.filt + (size_t)jz * 2 * t.D;
+  float* sc = xbuf + t.sc_off;
+  const float lsO = ok ? zp[t.P - A + i] : 0.0f;     // the row ends with logstd [A]
+  const float stdO = expf(lsO), sumO = row16_sum(lsO);
+  const float n1 = ok ? pt_global(r.noise1)[policy_noise_index(a, e, s, A, i)] : 0.0f;
+  const float keep1 = 1.0f - (float)((dn >> 8) & 0xff);
+  const float mO1 = zoo_lstm_mean<true>(t, zp, zf, r.st1 + (size_t)e * 128, keep1, xbuf + r.XS, sc, lane);
+  onlp1 = gauss_row(mO1, stdO, sumO, ok, true, n1, act1, A);             // the zoo net samples for agent 1 ...
+  nlp1 = gauss_row(f.mL1, f.stdL, f.sumL, ok, false, 0.0f, act1, A);     // ... the learner scores it
+  wave_sync();   // the cell's rows are rewritten by the scoring pass
+  const float mO0 = zoo_lstm_mean<false>(t, zp, zf, nullptr, 0.0f, xbuf, sc, lane);
+  float act0 = f.act0;
+  onlp0 = gauss_row(mO0, stdO, sumO, ok, false, 0.0f, act0, A);          // the zoo net (zero state) scores agent 0's action
+}
+
 // The league entry of env column `col` (r.tile_net per 16-env tile of the whole env set, NULL = entry 0), checked against the two
-// tables' sizes like every table row (policy_checked_row).  One value per wave: the branch on it is a scalar branch.
+// tables' sizes like every table row.  One value per wave, so league_zoo_pass branches on it with a scalar branch: entry je is row
+// je of the MLP table or row je - zm.n of the LSTM table.
 template <class SA, class RA>
 __device__ __forceinline__ int league_entry(const SA& a, const RA& r, int lane, size_t col) {
-  const int je = policy_checked_row(a, lane, r.tile_net ? pt_global(r.tile_net)[col >> 4] : 0, r.lg.nmlp + r.lg.l.nzoo);
+  const int je = policy_checked_row(a, lane, r.tile_net ? pt_global(r.tile_net)[col >> 4] : 0, r.zm.n + r.zl.n);
   return __builtin_amdgcn_readfirstlane(je);
 }
-
-// The zoo side of a league step, once the learner has read the raw tile and sampled act0: entry je < nmlp plays the zoo pass of
-// modes 4 / 9 (zoo_trunk_forward on both rows of the tile, filtered in place, hidden tiles behind it), any other entry the zoo pass
-// of modes 8 / 10 (zoo_lstm_mean on row 1 from the env's state row masked by AGENT 1's done flag, then on row 0 from a zero state;
-// cell rows at l.sc_off).  xbuf: x [2][XS] followed by the scratch either pass needs; mL1 / stdL / sumL: the learner's head on row 1.
-// Lanes < A hold their action column.  Every number equals ppo_forward_filtered / ppo_lstm_step, as in those modes.
 template <class SA, class RA>
-__device__ __forceinline__ void league_zoo_pass(const SA& a, const RA& r, int e, int lane, int je, unsigned dn, float* xbuf, int XS, int A,
-                                                float n1, float mL1, float stdL, float sumL, float act0, float& act1, float& onlp0,
-                                                float& onlp1, float& nlp1) {
-  const auto& g = r.lg;
-  const bool ok = lane < A;
-  if (je < g.nmlp) {
-    float* h1 = xbuf + 2 * XS;                       // [2][PT_HS] | h2 [2][PT_HS]
-    float* h2 = h1 + 2 * PT_HS;
-    const float PT_GAS* zp = pt_global(g.mparams) + (size_t)je * g.Lz.P;
-    const f32x4 mO = zoo_trunk_forward<2>(pi_net((const float*)zp, g.Lz), g.mfilt + (size_t)je * 2 * g.Dm, g.mclip, xbuf, XS, g.Dm, h1, h2, lane);
-    const float lsO = ok ? zp[g.Lz.logstd + lane] : 0.0f;
-    const float stdO = expf(lsO), sumO = row16_sum(lsO);
-    onlp0 = gauss_row(mO[0], stdO, sumO, ok, false, 0.0f, act0, A);      // the zoo net scores agent 0's action
-    onlp1 = gauss_row(mO[1], stdO, sumO, ok, true, n1, act1, A);         // the zoo net samples for agent 1 ...
-    nlp1 = gauss_row(mL1, stdL, sumL, ok, false, 0.0f, act1, A);         // ... the learner scores it
-  } else {
-    const auto& q = g.l;
-    const int jz = je - g.nmlp;
-    const float PT_GAS* zp = pt_global(r.opponent) + (size_t)jz * q.Pz;
-    const float* zf = q.filt + (size_t)jz * 2 * q.Dz;
-    float* sc = xbuf + q.sc_off;
-    const float lsO = ok ? zp[q.Pz - A + lane] : 0.0f;   // the row ends with logstd [A]
-    const float stdO = expf(lsO), sumO = row16_sum(lsO);
-    const float keep1 = 1.0f - (float)((dn >> 8) & 0xff);
-    const float mO1 = zoo_lstm_mean<true>(q, zp, zf, r.st1 + (size_t)e * 128, keep1, xbuf + XS, sc, lane);
-    onlp1 = gauss_row(mO1, stdO, sumO, ok, true, n1, act1, A);           // the zoo net samples for agent 1 ...
-    nlp1 = gauss_row(mL1, stdL, sumL, ok, false, 0.0f, act1, A);         // ... the learner scores it
-    wave_sync();   // the cell's rows are rewritten by the scoring pass
-    const float mO0 = zoo_lstm_mean<false>(q, zp, zf, nullptr, 0.0f, xbuf, sc, lane);
-    onlp0 = gauss_row(mO0, stdO, sumO, ok, false, 0.0f, act0, A);        // the zoo net (zero state) scores agent 0's action
-  }
+__device__ __forceinline__ void league_zoo_pass(const SA& a, const RA& r, int e, int s, int lane, int i, bool ok, int je, unsigned dn,
+                                                float* xbuf, int A, const LearnerFront& f, float& act1, float& onlp0, float& onlp1, float& nlp1) {
+  if (je < r.zm.n) zoo_mlp_pass(a, r, e, s, lane, i, ok, je, xbuf, A, f, act1, onlp0, onlp1, nlp1);
+  else zoo_lstm_pass(a, r, e, s, lane, i, ok, je - r.zm.n, dn, xbuf, A, f, act1, onlp0, onlp1, nlp1);
 }
 
-// MLP(64,64) learner against a league (sumo_rollout_steps_zoo_league, POLICY 11): the learner's part of modes 4 / 8 -- policy and
-// value trunks on the raw tile, agent 0's action sampled -- then league_zoo_pass for the tile's entry.
-template <class C, class SA, class RA>
-__device__ __forceinline__ void rollout_policy_phase_zoo_league(C& c, const SA& a, const RA& r, int e, int s) {
-  const int lane = c.lane, i = lane & 15, kq = lane >> 4;
-  const int D = r.L.D, A = r.L.A, XS = r.XS;
-  float* xbuf = (float*)(c.sm + r.lds_off);        // [2][XS] | h1 [2][PT_HS] | h2 [2][PT_HS]
-  float* h1 = xbuf + 2 * XS;
-  float* h2 = h1 + 2 * PT_HS;
-  const size_t col = (size_t)r.env_offset + e;
-  const size_t slot0 = ((size_t)0 * r.T + s) * r.Ntot + col, slot1 = ((size_t)1 * r.T + s) * r.Ntot + col;
-  policy_load_obs<false, true>(a, r, e, lane, xbuf, D, XS, slot0, slot1);
-  const unsigned dn = policy_prev_done(a, e);
-  if (lane < 2) policy_record_done(r, lane, slot0, slot1, dn);
-  wave_sync();
-  const int je = league_entry(a, r, lane, col);
-  const float PT_GAS* lp = pt_global(r.learner);
-  const f32x4 mL4 = trunk_forward<false, 2>(pi_net((const float*)lp, r.L), xbuf, XS, D, h1, h2, lane);
-  const float mL0 = mL4[0], mL1 = mL4[1];
-  wave_sync();
-  const f32x4 vL4 = trunk_forward<false, 2>(vf_net((const float*)lp, r.L), xbuf, XS, D, h1, h2, lane);
-  const float vL0 = vL4[0], vL1 = vL4[1];
-  const bool colk = i < A;
-  const bool ok = colk && kq == 0;                  // rows 0 and 1 live in the first 16 lanes (D layout: rows 4 kq + r)
-  const float lsL = colk ? lp[r.L.logstd + i] : 0.0f;
-  const float stdL = expf(lsL), sumL = row16_sum(lsL);
-  const size_t nz = policy_noise_index(a, e, s, A, i);
-  const float n1 = ok ? pt_global(r.noise1)[nz] : 0.0f;
-  float act0 = 0.0f, act1 = 0.0f;
-  const float nlp0 = gauss_row(mL0, stdL, sumL, ok, true, ok ? pt_global(r.noise0)[nz] : 0.0f, act0, A);   // learner samples for agent 0
-  wave_sync();   // the tile is filtered in place, the hidden tiles are the zoo net's
-  float onlp0, onlp1, nlp1;
-  league_zoo_pass(a, r, e, lane, je, dn, xbuf, XS, A, n1, mL1, stdL, sumL, act0, act1, onlp0, onlp1, nlp1);
-  if (ok) policy_commit_actions<true>(c, a, r, e, i, act0, act1, A, slot0, slot1);
-  if (lane == 0) policy_record_scalars(r, slot0, slot1, nlp0, nlp1, onlp0, onlp1, vL0, vL1);
-  wave_sync();   // the action buffer is read back by the env step (other lanes), the scratch region becomes the mass matrix again
-}
-
-// LSTM(128) learner against a league (sumo_rollout_steps_lstm_zoo_league, POLICY 12): the learner's rows C and E of
-// rollout_policy_phase_lstm_zoo, then league_zoo_pass for the tile's entry.  The learner's block is that function's written out, not
-// a helper both call: moving it into a function is a source change to modes 9 / 10, whose code objects have to stay as they are.
-// Any change to one of the two goes into the other; tests/test_gpu_zoo_league.py compares this mode with the launches
-// tests/test_gpu_lstm_zoo_rollout.py compares modes 9 / 10 with.
-template <int NH, class C, class SA, class RA>
-__device__ __forceinline__ void rollout_policy_phase_lstm_zoo_league(C& c, const SA& a, const RA& r, int e, int s) {
+// Rollout policy phase of a learner against policy-zoo nets (learn(opponent_mode='fix'), reference alg_ppo.py:194-206):
+//   LSTM_LEARNER false: sumo_rollout_steps_zoo / _zoo_lstm / _zoo_league           (POLICY 4 / 8 / 11), zoo row opp_idx[e]
+//   LSTM_LEARNER true:  sumo_rollout_steps_lstm_zoo / _lstm_zoo_lstm / _lstm_zoo_league (POLICY 9 / 10 / 12), zoo row tile_net[col >> 4]
+//                       per 16-env tile of the whole env set, as the snapshot of mode 1
+// A league (ZOO_LEAGUE) takes its entry from tile_net for either learner (league_entry).  The learner
+// reads the raw tile first (it is in the record by then); only then the zoo net filters the rows in place and takes over the scratch
+// behind the tile.  Heads and record as rollout_policy_phase.
+enum { ZOO_MLP, ZOO_LSTM, ZOO_LEAGUE };
+template <bool LSTM_LEARNER, int ZOO_KIND, class C, class SA, class RA>
+__device__ __forceinline__ void rollout_policy_phase_vs_zoo(C& c, const SA& a, const RA& r, int e, int s) {
   const int lane = c.lane;
-  const auto& NL = r.lnet;
-  const int D = NL.ob_dim, A = NL.ac_dim, XS = r.XS;
-  float* xo = (float*)(c.sm + r.lds_off);
-  float* hz = xo + 2 * XS;
-  float* hp = hz + NH;
-  float* hn = hp + NH;
+  const int i = LSTM_LEARNER ? lane : lane & 15;
+  const int A = LSTM_LEARNER ? r.lnet.ac_dim : r.L.A;
+  const bool ok = i < A && (LSTM_LEARNER || (lane >> 4) == 0);
+  float* xbuf = (float*)(c.sm + r.lds_off);
   const size_t col = (size_t)r.env_offset + e;
   const size_t slot0 = ((size_t)0 * r.T + s) * r.Ntot + col, slot1 = ((size_t)1 * r.T + s) * r.Ntot + col;
-  policy_load_obs<true, true>(a, r, e, lane, xo, D, XS, slot0, slot1);
-  const unsigned dn = policy_prev_done(a, e);
-  if (lane < 2) policy_record_done(r, lane, slot0, slot1, dn);
-  const float keep0 = 1.0f - (float)(dn & 0xff);
-  float* s0p = r.st0 + (size_t)e * 2 * NH;
-  const int j0 = 2 * lane;                           // lane owns the units 2 lane, 2 lane + 1
-  float c0[2];
-  lstm_state_pair(s0p + j0, keep0, c0);
-  lstm_state_pair(s0p + NH + j0, keep0, hp + j0);
-  hz[j0] = 0.0f; hz[j0 + 1] = 0.0f;
-  wave_sync();
-  const int je = league_entry(a, r, lane, col);
-  const bool ok = lane < A;
-  const size_t nz = policy_noise_index(a, e, s, A, lane);
-  float act0 = 0.0f, act1 = 0.0f;
-  float nlp0, mL1, stdL, sumL, v0, v1;
-  {  // ---- learner net: rows C, E
-    const float fb = NL.forget_bias;
-    float z[4][2][2], bz[4][2];
-    lstm_bias_pair<NH>(pt_global(NL.b), j0, bz);   // (in flight during the gate sums)
-    const float* const xr[2] = {xo, xo + XS};
-    const float* const hr[2] = {hp, hz};
-    lstm_gates_valu<NH, 2>(NL.wx, NL.wh, D, xr, hr, lane, z);
-#pragma unroll
-    for (int u = 0; u < 2; u++) {
-      const int j = j0 + u;
-      const float bi = bz[0][u], bf = bz[1][u] + fb, bo = bz[2][u], bu = bz[3][u];   // gate order i, f, o, u
-      const LstmCell cc = lstm_cell(z[0][u][0], z[1][u][0], z[2][u][0], z[3][u][0], bi, bf, bo, bu, c0[u]);
-      const LstmCell ce = lstm_cell(z[0][u][1], z[1][u][1], z[2][u][1], z[3][u][1], bi, bf, bo, bu, hz[j]);
-      lstm_state_store<NH>(s0p, j, cc);                                              // agent 0's state after the learner's step
-      hn[j] = cc.hn; hn[NH + j] = ce.hn;
-    }
-    wave_sync();
-    float m[2];
-    lstm_heads_valu<NH, 2>(NL.head_w, NL.vf_w, A, hn, lane, m);
-    const float hb = ok ? pt_global(NL.head_b)[lane] : 0.0f, ls = ok ? pt_global(NL.logstd)[lane] : 0.0f;
-    stdL = expf(ls); sumL = row16_sum(ls);
-    const float vb = pt_global(NL.vf_b)[0];
-    v0 = __shfl(m[0], 16) + vb; v1 = __shfl(m[1], 16) + vb;
-    mL1 = m[1] + hb;
-    const float n0 = ok ? pt_global(r.noise0)[nz] : 0.0f;
-    nlp0 = gauss_row(m[0] + hb, stdL, sumL, ok, true, n0, act0, A);      // the learner samples for agent 0
-    wave_sync();   // the raw tile is filtered in place and the latent rows are rewritten by the zoo net's pass
-  }
-  const float n1 = ok ? pt_global(r.noise1)[nz] : 0.0f;
-  float onlp0, onlp1, nlp1;
-  league_zoo_pass(a, r, e, lane, je, dn, xo, XS, A, n1, mL1, stdL, sumL, act0, act1, onlp0, onlp1, nlp1);
-  if (ok) policy_commit_actions<true>(c, a, r, e, lane, act0, act1, A, slot0, slot1);
-  if (lane == 0) policy_record_scalars(r, slot0, slot1, nlp0, nlp1, onlp0, onlp1, v0, v1);
+  int jz;   // the zoo net of the step: a row of the mode's table, or a league entry
+  if constexpr (ZOO_KIND == ZOO_LEAGUE) jz = league_entry(a, r, lane, col);
+  else if constexpr (LSTM_LEARNER) jz = policy_checked_row(a, lane, r.tile_net ? pt_global(r.tile_net)[col >> 4] : 0, ZOO_KIND == ZOO_MLP ? r.zm.n : r.zl.n);
+  else jz = policy_checked_row(a, lane, r.opp_idx ? pt_global(r.opp_idx)[e] : 0, ZOO_KIND == ZOO_MLP ? r.zm.n : r.zl.n);
+  unsigned dn;
+  LearnerFront f;
+  if constexpr (LSTM_LEARNER) f = lstm_learner_front<128>(a, r, e, s, lane, xbuf, slot0, slot1, dn);
+  else f = mlp_learner_front(a, r, e, s, lane, xbuf, slot0, slot1, dn);
+  wave_sync();   // the raw tile is filtered in place, the hidden tiles / latent rows become the zoo net's
+  float act1 = 0.0f, onlp0, onlp1, nlp1;
+  if constexpr (ZOO_KIND == ZOO_MLP) zoo_mlp_pass(a, r, e, s, lane, i, ok, jz, xbuf, A, f, act1, onlp0, onlp1, nlp1);
+  else if constexpr (ZOO_KIND == ZOO_LSTM) zoo_lstm_pass(a, r, e, s, lane, i, ok, jz, dn, xbuf, A, f, act1, onlp0, onlp1, nlp1);
+  else league_zoo_pass(a, r, e, s, lane, i, ok, jz, dn, xbuf, A, f, act1, onlp0, onlp1, nlp1);
+  if (ok) policy_commit_actions<true>(c, a, r, e, i, f.act0, act1, A, slot0, slot1);
+  if (lane == 0) policy_record_scalars(r, slot0, slot1, f.nlp0, nlp1, onlp0, onlp1, f.v0, f.v1);
   wave_sync();   // the action buffer is read back by the env step (other lanes), the scratch region is the step's again
 }
 
@@ -3573,17 +3311,7 @@ __device__ __forceinline__ void rollout_post_phase(C& c, const SA& a, const RA& 
 // evaluations of every step (the kernel sits exactly at its 256-register budget).  The pointer addresses the kernel-argument
 // segment itself, where the runtime has placed the struct at launch (no separate copy to keep alive).
 struct RolloutLaunch { StepArgs a; RolloutArgs r; };
-static_assert(sizeof(ZooArgs) <= sizeof(ppo_lstm_net), "ZooArgs overlays RolloutArgs::lnet");
-static_assert(sizeof(ZooLstmArgs) <= sizeof(ppo_lstm_net) && offsetof(RolloutArgs, zlr) == offsetof(RolloutArgs, lnet),
-              "ZooLstmArgs (POLICY 8) overlays RolloutArgs::lnet");
-static_assert(sizeof(ZooLstmArgs) <= 6 * sizeof(float*) && offsetof(RolloutArgs, obs) == offsetof(RolloutArgs, zl) &&
-                  offsetof(RolloutArgs, obs) == offsetof(RolloutArgs, noise1) + sizeof(float*) &&
-                  offsetof(RolloutArgs, onlp) == offsetof(RolloutArgs, obs) + 5 * sizeof(float*) &&
-                  offsetof(RolloutArgs, done) == offsetof(RolloutArgs, obs) + 6 * sizeof(float*),
-              "ZooLstmArgs overlays the six rollout-record pointers of RolloutArgs: no field moves");
-static_assert(sizeof(ZooTailArgs) <= 4 * sizeof(void*) + 2 * sizeof(int) && offsetof(RolloutArgs, zt) == offsetof(RolloutArgs, snaps) &&
-                  offsetof(RolloutArgs, quota) + sizeof(int) == offsetof(RolloutArgs, lg),
-              "ZooTailArgs (POLICY 9 / 10) overlays the match fields of RolloutArgs; the league fields (POLICY 11 / 12) follow them");
+static_assert(sizeof(const Params*) + sizeof(RolloutLaunch) <= 4096, "the launch arguments fit the 4 KB kernel-argument segment");
 
 // Scheduling: the launch is a set of persistent waves (one per wave slot of the chip) that draw TICKETS from a global counter;
 // ticket t is step t / N of env t % N.  Env steps differ in cost by 3x (contacts, Newton iterations, agents wrestling), so
@@ -3598,18 +3326,23 @@ static_assert(sizeof(ZooTailArgs) <= 4 * sizeof(void*) + 2 * sizeof(int) && offs
 // launch's abort flag (counted in sumo_stats[9]) and every wave drains.
 #define ROLLOUT_SPIN_LIMIT (1u << 22)   /* polls of ~0.5 us each */
 
-template <int NV, int POLICY, int SL = 0>   // POLICY 0: MLP(64,64) policy / value nets; 1: LSTM(128) with shared value head; 2: MLP matches
-                                            // (sumo_match_steps: score counters instead of rollout buffers); 3: LSTM(128) matches
-                                            // (sumo_match_steps_lstm); 4: MLP learner against policy-zoo MLP nets
-                                            // (sumo_rollout_steps_zoo); 5: MLP checkpoints against policy-zoo MLP nets
-                                            // (sumo_match_steps_zoo); 6: MLP checkpoints against policy-zoo LSTM nets
-                                            // (sumo_match_steps_zoo_lstm); 7: LSTM(128) checkpoints against policy-zoo LSTM
-                                            // nets (sumo_match_steps_lstm_zoo_lstm); 8: MLP learner against policy-zoo LSTM
-                                            // nets (sumo_rollout_steps_zoo_lstm); 9 / 10: LSTM(128) learner against policy-zoo
-                                            // MLP / LSTM nets (sumo_rollout_steps_lstm_zoo / sumo_rollout_steps_lstm_zoo_lstm);
-                                            // 11 / 12: MLP(64,64) / LSTM(128) learner against a league of policy-zoo nets of
-                                            // both families (sumo_rollout_steps_zoo_league / sumo_rollout_steps_lstm_zoo_league);
-                                            // SL 1: static Layout
+// POLICY selects the policy phase (and with it the post phase: rollout record, or the score counters of the match modes 2, 3, 5-7):
+//    0  sumo_rollout_steps                  MLP(64,64) self-play                      rollout_policy_phase
+//    1  sumo_rollout_steps_lstm             LSTM(128) self-play, shared value head    rollout_policy_phase_lstm
+//    2  sumo_match_steps                    MLP checkpoint matches                    rollout_policy_phase_match
+//    3  sumo_match_steps_lstm               LSTM(128) checkpoint matches              match_lstm_side for both agents
+//    4  sumo_rollout_steps_zoo              MLP learner  vs zoo MLP nets              mlp_learner_front  + zoo_mlp_pass
+//    5  sumo_match_steps_zoo                MLP checkpoints vs zoo MLP nets           match_mlp_side0    + the zoo trunk on row 1
+//    6  sumo_match_steps_zoo_lstm           MLP checkpoints vs zoo LSTM nets          match_mlp_side0    + zoo_lstm_act
+//    7  sumo_match_steps_lstm_zoo_lstm      LSTM(128) checkpoints vs zoo LSTM nets    match_lstm_side(0) + zoo_lstm_act
+//    8  sumo_rollout_steps_zoo_lstm         MLP learner  vs zoo LSTM nets             mlp_learner_front  + zoo_lstm_pass
+//    9  sumo_rollout_steps_lstm_zoo         LSTM learner vs zoo MLP nets              lstm_learner_front + zoo_mlp_pass
+//   10  sumo_rollout_steps_lstm_zoo_lstm    LSTM learner vs zoo LSTM nets             lstm_learner_front + zoo_lstm_pass
+//   11  sumo_rollout_steps_zoo_league       MLP learner  vs a league of both families mlp_learner_front  + league_zoo_pass
+//   12  sumo_rollout_steps_lstm_zoo_league  LSTM learner vs a league of both families lstm_learner_front + league_zoo_pass
+// (4, 8 .. 12 are rollout_policy_phase_vs_zoo<LSTM_LEARNER, ZOO_KIND>.)  The integers are part of the kernels' mangled names, which
+// profiles/ and tools/ refer to.  SL 1 / 2: static Layout.
+template <int NV, int POLICY, int SL = 0>
 __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(SUMO_WPE_OF(NV), SUMO_WPE_OF(NV))))
 sumo_rollout_kernel(const Params* P, RolloutLaunch launch_args) {
   // `launch_args` is read in place from the kernel-argument segment (second argument, 8-byte aligned right behind P) through a
@@ -3665,15 +3398,15 @@ sumo_rollout_kernel(const Params* P, RolloutLaunch launch_args) {
     if constexpr (POLICY == 1) rollout_policy_phase_lstm<128>(c, lp->a, lp->r, e, s);
     else if constexpr (POLICY == 2) rollout_policy_phase_match(c, lp->a, lp->r, e, s);
     else if constexpr (POLICY == 3) rollout_policy_phase_match_lstm<128>(c, lp->a, lp->r, e, s);
-    else if constexpr (POLICY == 4) rollout_policy_phase_zoo(c, lp->a, lp->r, e, s);
+    else if constexpr (POLICY == 4) rollout_policy_phase_vs_zoo<false, ZOO_MLP>(c, lp->a, lp->r, e, s);
     else if constexpr (POLICY == 5) rollout_policy_phase_match_zoo(c, lp->a, lp->r, e, s);
     else if constexpr (POLICY == 6) rollout_policy_phase_match_zoo_lstm(c, lp->a, lp->r, e, s);
     else if constexpr (POLICY == 7) rollout_policy_phase_match_lstm_zoo_lstm<128>(c, lp->a, lp->r, e, s);
-    else if constexpr (POLICY == 8) rollout_policy_phase_zoo_lstm(c, lp->a, lp->r, e, s);
-    else if constexpr (POLICY == 9) rollout_policy_phase_lstm_zoo<128, false>(c, lp->a, lp->r, e, s);
-    else if constexpr (POLICY == 10) rollout_policy_phase_lstm_zoo<128, true>(c, lp->a, lp->r, e, s);
-    else if constexpr (POLICY == 11) rollout_policy_phase_zoo_league(c, lp->a, lp->r, e, s);
-    else if constexpr (POLICY == 12) rollout_policy_phase_lstm_zoo_league<128>(c, lp->a, lp->r, e, s);
+    else if constexpr (POLICY == 8) rollout_policy_phase_vs_zoo<false, ZOO_LSTM>(c, lp->a, lp->r, e, s);
+    else if constexpr (POLICY == 9) rollout_policy_phase_vs_zoo<true, ZOO_MLP>(c, lp->a, lp->r, e, s);
+    else if constexpr (POLICY == 10) rollout_policy_phase_vs_zoo<true, ZOO_LSTM>(c, lp->a, lp->r, e, s);
+    else if constexpr (POLICY == 11) rollout_policy_phase_vs_zoo<false, ZOO_LEAGUE>(c, lp->a, lp->r, e, s);
+    else if constexpr (POLICY == 12) rollout_policy_phase_vs_zoo<true, ZOO_LEAGUE>(c, lp->a, lp->r, e, s);
     else rollout_policy_phase(c, lp->a, lp->r, e, s);
 #ifdef SUMO_DBG_HARD_BARRIER
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -4498,6 +4231,14 @@ static int check_launch_args(sumo_engine* E, const void* launch, const EnvBuffer
   return 0;
 }
 
+// the instantiation of sumo_rollout_kernel for `policy`, from a table of all of them
+typedef void (*RolloutKernel)(const Params*, RolloutLaunch);
+template <int NV, int SL, int... POLICY>
+static RolloutKernel rollout_kernel(int policy, std::integer_sequence<int, POLICY...>) {
+  static const RolloutKernel table[] = {sumo_rollout_kernel<NV, POLICY, SL>...};
+  return table[policy];
+}
+
 // common tail of the fused entry points: scheduler state, persistent grid, launch
 static int rollout_launch(sumo_engine* E, const RolloutArgs& r, int policy, const EnvBuffers& b, void* stream) {
   RolloutLaunch rl;
@@ -4532,19 +4273,7 @@ static int rollout_launch(sumo_engine* E, const RolloutArgs& r, int policy, cons
   size_t lds_ = (size_t)E->L.total_bytes;
   if (!for_engine_variant(E, [&](auto nvc_, auto slc_) {
         constexpr int NV = decltype(nvc_)::value, SL = decltype(slc_)::value;
-        void (*kernel)(const Params*, RolloutLaunch) = policy == 1   ? sumo_rollout_kernel<NV, 1, SL>
-                                                       : policy == 2 ? sumo_rollout_kernel<NV, 2, SL>
-                                                       : policy == 3 ? sumo_rollout_kernel<NV, 3, SL>
-                                                       : policy == 4 ? sumo_rollout_kernel<NV, 4, SL>
-                                                       : policy == 5 ? sumo_rollout_kernel<NV, 5, SL>
-                                                       : policy == 6 ? sumo_rollout_kernel<NV, 6, SL>
-                                                       : policy == 7 ? sumo_rollout_kernel<NV, 7, SL>
-                                                       : policy == 8 ? sumo_rollout_kernel<NV, 8, SL>
-                                                       : policy == 9 ? sumo_rollout_kernel<NV, 9, SL>
-                                                       : policy == 10 ? sumo_rollout_kernel<NV, 10, SL>
-                                                       : policy == 11 ? sumo_rollout_kernel<NV, 11, SL>
-                                                       : policy == 12 ? sumo_rollout_kernel<NV, 12, SL>
-                                                                     : sumo_rollout_kernel<NV, 0, SL>;
+        const RolloutKernel kernel = rollout_kernel<NV, SL>(policy, std::make_integer_sequence<int, 13>{});
         hipLaunchKernelGGL(kernel, g_, b_, lds_, st_, E->d_params, rl);
       }))
     FAIL(-19, "no kernel variant for nv=%d", E->hm.nv);
@@ -4636,155 +4365,98 @@ static void copy_match_fields(RolloutArgs& r, const MO* mo, int N) {
   r.T = mo->T; r.Ntot = N; r.s0 = mo->s0; r.K = mo->K;
 }
 
-extern "C" int sumo_rollout_steps(sumo_handle_t E, const sumo_rollout* ro, float* actions_dev, float* obs_dev, double* info_dev,
-                                  uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
-  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
-  if (int rc = check_launch_args(E, ro, b)) return rc;
-  if (!ro->learner_params || !ro->opponent_params || rollout_buffer_missing(ro)) FAIL(-2, "sumo_rollout: missing buffer");
-  int od = 0, ad = 0;
-  if (int rc = rollout_scene(E, ro->T, ro->Ntot, ro->env_offset, ro->s0, ro->K, &od, &ad)) return rc;
-  if (int rc = check_dims(ro->ob_dim, ro->ac_dim, od, ad)) return rc;
-  if (ro->npool < 1) FAIL(-7, "npool %d", ro->npool);
+// ---- what the fused entry points share.  check_*: a family's buffer, scene and dimension checks, in the order every mode of the
+// family reports them (a zoo mode's own count checks follow in the entry point); begin_*: device and the family's fields, into a
+// zeroed RolloutArgs.  `zoo`: the entry point's name in a zoo mode (which refuses the fields that only play without a zoo), else NULL ----
+// MLP(64,64) learner (modes 0, 4, 8, 11)
+static int check_mlp_rollout(sumo_engine* E, const sumo_rollout* ro, const char* zoo, bool league, int* od, int* ad) {
+  if (!ro->learner_params || (!zoo && !ro->opponent_params) || rollout_buffer_missing(ro)) FAIL(-2, "sumo_rollout: missing buffer");
+  if (zoo && !league && ro->opponent_params) FAIL(-2, "%s: opponent_params must be NULL (the opponents are the zoo table's nets)", zoo);
+  if (league && (ro->opponent_params || ro->opponent_index))
+    FAIL(-2, "%s: opponent_params and opponent_index must be NULL (the opponents are the league's nets, selected per tile by tile_entry_dev)", zoo);
+  if (int rc = rollout_scene(E, ro->T, ro->Ntot, ro->env_offset, ro->s0, ro->K, od, ad)) return rc;
+  return check_dims(ro->ob_dim, ro->ac_dim, *od, *ad);
+}
+static int begin_mlp_rollout(sumo_engine* E, const sumo_rollout* ro, RolloutArgs& r) {
   HIPCHK(hipSetDevice(E->device));
-  RolloutArgs r;
-  memset(&r, 0, sizeof r);
   r.learner = ro->learner_params; r.opponent = ro->opponent_params; r.opp_idx = ro->opponent_index;
   copy_rollout_fields(r, ro);
-  if (int rc = place_mlp_scratch(E, ro->ob_dim, ro->ac_dim, r, 3)) return rc;
-  return rollout_launch(E, r, 0, b, stream);
+  return 0;
 }
 
-extern "C" int sumo_rollout_steps_lstm(sumo_handle_t E, const sumo_rollout_lstm* ro, float* actions_dev, float* obs_dev, double* info_dev,
-                                       uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
-  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
-  if (int rc = check_launch_args(E, ro, b)) return rc;
-  if (!ro->learner || !ro->opponents_dev || !ro->state0 || !ro->state1 || rollout_buffer_missing(ro)) FAIL(-2, "sumo_rollout_lstm: missing buffer");
-  int od = 0, ad = 0;
-  if (int rc = rollout_scene(E, ro->T, ro->Ntot, ro->env_offset, ro->s0, ro->K, &od, &ad)) return rc;
+// LSTM(128) learner (modes 1, 9, 10, 12).  nzoo: the size of the zoo mode's table or league.  begin_lstm_rollout also places the
+// scratch: x [2][XS] and `rows` rows of 128 floats
+static int check_lstm_rollout(sumo_engine* E, const sumo_rollout_lstm* ro, const char* zoo, int nzoo, int* od, int* ad) {
+  if (!ro->learner || !ro->state0 || (!zoo && (!ro->opponents_dev || !ro->state1)) || rollout_buffer_missing(ro)) FAIL(-2, "sumo_rollout_lstm: missing buffer");
+  if (zoo && (ro->opponents_dev || ro->state1))
+    FAIL(-2, "%s: opponents_dev and state1 must be NULL (the opponents are the zoo table's nets, agent 1's state is the table's)", zoo);
+  if (int rc = rollout_scene(E, ro->T, ro->Ntot, ro->env_offset, ro->s0, ro->K, od, ad)) return rc;
   const ppo_lstm_net& n = *ro->learner;
-  if (int rc = check_dims(n.ob_dim, n.ac_dim, od, ad)) return rc;
+  if (int rc = check_dims(n.ob_dim, n.ac_dim, *od, *ad)) return rc;
   if (int rc = check_lstm_shape(n, "rollout")) return rc;
   if (!n.wx || !n.wh || !n.b || !n.head_w || !n.head_b || !n.logstd || !n.vf_w || !n.vf_b) FAIL(-10, "learner net: missing weights");
-  if (ro->npool < 1) FAIL(-7, "npool %d", ro->npool);
-  if (ro->tile_net_dev && ((ro->env_offset & 15) || (E->N & 15))) FAIL(-11, "a snapshot per 16-env tile needs env_offset (%d) and the env count (%d) to be multiples of 16", ro->env_offset, E->N);
-  HIPCHK(hipSetDevice(E->device));
-  RolloutArgs r;
-  memset(&r, 0, sizeof r);
-  r.lnet = n; r.onets = ro->opponents_dev; r.tile_net = ro->tile_net_dev; r.st0 = ro->state0; r.st1 = ro->state1;
-  copy_rollout_fields(r, ro);
-  if (int rc = place_lstm_scratch(E, od, 7, r)) return rc;   // zero row, previous latents [3], new latents [3]
-  return rollout_launch(E, r, 1, b, stream);
+  if (!zoo && ro->npool < 1) FAIL(-7, "npool %d", ro->npool);
+  if (zoo && ro->npool != nzoo) FAIL(-7, "npool %d must equal the zoo table's nzoo %d", ro->npool, nzoo);
+  if (ro->tile_net_dev && ((ro->env_offset & 15) || (E->N & 15)))
+    FAIL(-11, "a %s per 16-env tile needs env_offset (%d) and the env count (%d) to be multiples of 16", zoo ? "zoo net" : "snapshot", ro->env_offset, E->N);
+  return 0;
 }
+static int begin_lstm_rollout(sumo_engine* E, const sumo_rollout_lstm* ro, int od, int rows, RolloutArgs& r) {
+  HIPCHK(hipSetDevice(E->device));
+  r.lnet = *ro->learner; r.onets = ro->opponents_dev; r.tile_net = ro->tile_net_dev; r.st0 = ro->state0; r.st1 = ro->state1;
+  copy_rollout_fields(r, ro);
+  return place_lstm_scratch(E, od, rows, r);
+}
+// the rows of a recurrent learner's zoo modes: zero row, agent 0's previous latent, two new latents, which the zoo net's hidden
+// tiles / cell rows reuse
+constexpr int LSTM_ZOO_ROWS = 4;
+static_assert(4 * PT_HS <= LSTM_ZOO_ROWS * 128, "modes 9 / 12: the zoo trunk's two hidden tiles [2][PT_HS] go where the learner's latent rows were");
 
-extern "C" int sumo_match_steps(sumo_handle_t E, const sumo_match* mo, float* actions_dev, float* obs_dev, double* info_dev,
-                                uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
-  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
-  if (int rc = check_launch_args(E, mo, b)) return rc;
+// MLP(64,64) checkpoints as agent 0, or on both sides (modes 2, 5, 6): nothing of a mode's own comes between checks and fields
+static int begin_mlp_match(sumo_engine* E, const sumo_match* mo, int* od, int* ad, RolloutArgs& r) {
   if (!mo->params) FAIL(-2, "sumo_match: missing buffer");
   if (int rc = check_match_buffers(mo, "sumo_match")) return rc;
-  int od = 0, ad = 0;
-  if (int rc = rollout_scene(E, mo->T, E->N, 0, mo->s0, mo->K, &od, &ad)) return rc;
-  if (int rc = check_dims(mo->ob_dim, mo->ac_dim, od, ad)) return rc;
+  if (int rc = rollout_scene(E, mo->T, E->N, 0, mo->s0, mo->K, od, ad)) return rc;
+  if (int rc = check_dims(mo->ob_dim, mo->ac_dim, *od, *ad)) return rc;
   if (int rc = check_match_counts(mo)) return rc;
   HIPCHK(hipSetDevice(E->device));
-  RolloutArgs r;
-  memset(&r, 0, sizeof r);
   r.snaps = mo->params;
   copy_match_fields(r, mo, E->N);
-  if (int rc = place_mlp_scratch(E, mo->ob_dim, mo->ac_dim, r, 2)) return rc;
-  return rollout_launch(E, r, 2, b, stream);
+  return 0;
 }
 
-extern "C" int sumo_match_steps_lstm(sumo_handle_t E, const sumo_match_lstm* mo, float* actions_dev, float* obs_dev, double* info_dev,
-                                     uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
-  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
-  if (int rc = check_launch_args(E, mo, b)) return rc;
+// LSTM(128) checkpoints (modes 3, 7), with the scratch: x [2][XS] | previous latent | new latent
+static int begin_lstm_match(sumo_engine* E, const sumo_match_lstm* mo, const char* zoo, int* od, int* ad, RolloutArgs& r) {
   if (!mo->proto || !mo->nets_dev) FAIL(-2, "sumo_match_lstm: missing buffer");
-  if (!mo->state0 || !mo->state1) FAIL(-2, "sumo_match_lstm: missing state buffer (state0 / state1)");
+  if (!mo->state0 || (!zoo && !mo->state1)) FAIL(-2, "sumo_match_lstm: missing state buffer (%s)", zoo ? "state0" : "state0 / state1");
+  if (zoo && mo->state1) FAIL(-2, "%s: state1 must be NULL (agent 1's state is the zoo table's state)", zoo);
   if (int rc = check_match_buffers(mo, "sumo_match_lstm")) return rc;
-  int od = 0, ad = 0;
-  if (int rc = rollout_scene(E, mo->T, E->N, 0, mo->s0, mo->K, &od, &ad)) return rc;
+  if (int rc = rollout_scene(E, mo->T, E->N, 0, mo->s0, mo->K, od, ad)) return rc;
   const ppo_lstm_net& n = *mo->proto;
-  if (int rc = check_dims(n.ob_dim, n.ac_dim, od, ad)) return rc;
+  if (int rc = check_dims(n.ob_dim, n.ac_dim, *od, *ad)) return rc;
   if (int rc = check_lstm_shape(n, "matches")) return rc;   // the nets sumo_rollout_steps_lstm plays
   if (!n.wx || !n.wh || !n.b || !n.head_w || !n.head_b || !n.logstd) FAIL(-10, "prototype net: missing weights");
   if (int rc = check_match_counts(mo)) return rc;
   HIPCHK(hipSetDevice(E->device));
-  RolloutArgs r;
-  memset(&r, 0, sizeof r);
   r.lnet = n; r.onets = mo->nets_dev; r.st0 = mo->state0; r.st1 = mo->state1;
   copy_match_fields(r, mo, E->N);
-  if (int rc = place_lstm_scratch(E, od, 2, r)) return rc;   // previous latent, new latent
-  return rollout_launch(E, r, 3, b, stream);
+  return place_lstm_scratch(E, *od, 2, r);
 }
 
-// the zoo table of sumo_rollout_steps_zoo / sumo_match_steps_zoo: checks, then the fields of RolloutArgs it fills
-static int check_zoo_table(const sumo_zoo_mlp* z, int od) {
+// ---- the zoo tables: checks, then RolloutArgs::zm / zl ----
+static int place_zoo_mlp_table(RolloutArgs& r, const sumo_zoo_mlp* z, int od, int ad) {
   if (!z->params || !z->filt) FAIL(-2, "sumo_zoo_mlp: missing buffer (params / filt)");
   if (z->nzoo < 1) FAIL(-7, "nzoo %d: the zoo table needs at least one entry", z->nzoo);
   if (z->ob_dim < 1 || z->ob_dim > od)
     FAIL(-4, "zoo ob_dim %d outside [1, %d]: a policy-zoo MLP net reads the first ob_dim columns of the scene's observation", z->ob_dim, od);
   if (!(z->obs_clip > 0.0f)) FAIL(-9, "obs_clip %g must be positive", (double)z->obs_clip);
+  r.zm.params = z->params; r.zm.filt = z->filt; r.zm.clip = z->obs_clip; r.zm.n = z->nzoo; r.zm.D = z->ob_dim;
+  r.zm.L = make_layout(z->ob_dim, ad);
   return 0;
 }
-static int place_zoo_table(RolloutArgs& r, const sumo_zoo_mlp* z, int od, int ad) {
-  if (int rc = check_zoo_table(z, od)) return rc;
-  r.opponent = z->params;
-  r.zoo.filt = z->filt; r.zoo.clip = z->obs_clip; r.zoo.nzoo = z->nzoo; r.zoo.Dz = z->ob_dim; r.zoo.Lz = make_layout(z->ob_dim, ad);
-  return 0;
-}
-
-extern "C" int sumo_rollout_steps_zoo(sumo_handle_t E, const sumo_rollout* ro, const sumo_zoo_mlp* z, float* actions_dev, float* obs_dev,
-                                      double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
-  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
-  if (int rc = check_launch_args(E, ro, b)) return rc;
-  if (!z) FAIL(-1, "bad arguments");
-  if (!ro->learner_params || rollout_buffer_missing(ro)) FAIL(-2, "sumo_rollout: missing buffer");
-  if (ro->opponent_params) FAIL(-2, "sumo_rollout_steps_zoo: opponent_params must be NULL (the opponents are the zoo table's nets)");
-  int od = 0, ad = 0;
-  if (int rc = rollout_scene(E, ro->T, ro->Ntot, ro->env_offset, ro->s0, ro->K, &od, &ad)) return rc;
-  if (int rc = check_dims(ro->ob_dim, ro->ac_dim, od, ad)) return rc;
-  if (ro->npool != z->nzoo) FAIL(-7, "npool %d must equal the zoo table's nzoo %d", ro->npool, z->nzoo);
-  HIPCHK(hipSetDevice(E->device));
-  RolloutArgs r;
-  memset(&r, 0, sizeof r);
-  if (int rc = place_zoo_table(r, z, od, ad)) return rc;
-  r.learner = ro->learner_params; r.opp_idx = ro->opponent_index;
-  copy_rollout_fields(r, ro);
-  if (int rc = place_mlp_scratch(E, ro->ob_dim, ro->ac_dim, r)) return rc;
-  return rollout_launch(E, r, 4, b, stream);
-}
-
-extern "C" int sumo_match_steps_zoo(sumo_handle_t E, const sumo_match* mo, const sumo_zoo_mlp* z, float* actions_dev, float* obs_dev,
-                                    double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
-  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
-  if (int rc = check_launch_args(E, mo, b)) return rc;
-  if (!z) FAIL(-1, "bad arguments");
-  if (!mo->params) FAIL(-2, "sumo_match: missing buffer");
-  if (int rc = check_match_buffers(mo, "sumo_match")) return rc;
-  int od = 0, ad = 0;
-  if (int rc = rollout_scene(E, mo->T, E->N, 0, mo->s0, mo->K, &od, &ad)) return rc;
-  if (int rc = check_dims(mo->ob_dim, mo->ac_dim, od, ad)) return rc;
-  if (int rc = check_match_counts(mo)) return rc;
-  HIPCHK(hipSetDevice(E->device));
-  RolloutArgs r;
-  memset(&r, 0, sizeof r);
-  if (int rc = place_zoo_table(r, z, od, ad)) return rc;
-  r.snaps = mo->params;
-  copy_match_fields(r, mo, E->N);
-  if (int rc = place_mlp_scratch(E, mo->ob_dim, mo->ac_dim, r)) return rc;
-  return rollout_launch(E, r, 5, b, stream);
-}
-
-// the zoo LSTM table of sumo_match_steps_zoo_lstm / sumo_match_steps_lstm_zoo_lstm / sumo_rollout_steps_zoo_lstm: checks, then the
-// fields of RolloutArgs it fills -- st1 and the launch's ZooLstmArgs q (r.zl in the match modes, r.zlr in the rollout mode)
-// (after place_*_scratch: the cell's rows -- embedding | previous latent | new latent, 64 floats each -- go behind the observation
-// tile, 16-byte aligned, into the `rows_floats` floats the placed scratch holds there)
-// (Q: ZooLstmArgs, or the ZooTailArgs of mode 10, whose parameter rows travel in r.opponent)
-static void zoo_lstm_params(RolloutArgs&, ZooLstmArgs& q, const float* p) { q.params = p; }
-static void zoo_lstm_params(RolloutArgs& r, ZooTailArgs&, const float* p) { r.opponent = p; }
-template <class Q>
-static int place_zoo_lstm_table(RolloutArgs& r, Q& q, const sumo_zoo_lstm* z, int od, int ad, int rows_floats) {
+// (after the scratch is placed: the cell's rows -- embedding | previous latent | new latent, 64 floats each -- go behind the
+// observation tile, 16-byte aligned, into the `rows_floats` floats the placed scratch holds there.  The table's state is agent 1's.)
+static int place_zoo_lstm_table(RolloutArgs& r, const sumo_zoo_lstm* z, int od, int ad, int rows_floats) {
   if (!z->params || !z->filt) FAIL(-2, "sumo_zoo_lstm: missing buffer (params / filt)");
   if (!z->state) FAIL(-2, "sumo_zoo_lstm: missing state buffer (state)");
   if (z->nzoo < 1) FAIL(-7, "nzoo %d: the zoo table needs at least one entry", z->nzoo);
@@ -4792,9 +4464,10 @@ static int place_zoo_lstm_table(RolloutArgs& r, Q& q, const sumo_zoo_lstm* z, in
     FAIL(-4, "zoo ob_dim %d outside [1, %d]: a policy-zoo LSTM net reads the first ob_dim columns of the scene's observation", z->ob_dim, od);
   if (z->emb_dim != PT_H || z->hidden != 64) FAIL(-4, "zoo LSTM emb_dim %d / hidden %d: the fused launch is built for 64 / 64", z->emb_dim, z->hidden);
   if (!(z->obs_clip > 0.0f)) FAIL(-9, "obs_clip %g must be positive", (double)z->obs_clip);
-  zoo_lstm_params(r, q, z->params);
-  q.filt = z->filt; q.clip = z->obs_clip; q.forget_bias = z->forget_bias; q.nzoo = z->nzoo; q.Dz = z->ob_dim; q.A = ad; q.emb = z->emb_dim;
-  q.Pz = z->ob_dim * PT_H + PT_H + 2 * 64 * 256 + 256 + 64 * ad + 2 * ad;
+  ZooLstmTable& q = r.zl;
+  q.params = z->params; q.filt = z->filt; q.clip = z->obs_clip; q.forget_bias = z->forget_bias; q.n = z->nzoo; q.D = z->ob_dim; q.A = ad;
+  q.emb = z->emb_dim;
+  q.P = z->ob_dim * PT_H + PT_H + 2 * 64 * 256 + 256 + 64 * ad + 2 * ad;
   r.st1 = z->state;
   const int tile = 2 * r.XS;
   q.sc_off = tile;
@@ -4804,135 +4477,8 @@ static int place_zoo_lstm_table(RolloutArgs& r, Q& q, const sumo_zoo_lstm* z, in
          (size_t)(q.sc_off + 3 * 64) * sizeof(float), (size_t)(tile + rows_floats) * sizeof(float));
   return 0;
 }
-
-extern "C" int sumo_match_steps_zoo_lstm(sumo_handle_t E, const sumo_match* mo, const sumo_zoo_lstm* z, float* actions_dev, float* obs_dev,
-                                         double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
-  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
-  if (int rc = check_launch_args(E, mo, b)) return rc;
-  if (!z) FAIL(-1, "bad arguments");
-  if (!mo->params) FAIL(-2, "sumo_match: missing buffer");
-  if (int rc = check_match_buffers(mo, "sumo_match")) return rc;
-  int od = 0, ad = 0;
-  if (int rc = rollout_scene(E, mo->T, E->N, 0, mo->s0, mo->K, &od, &ad)) return rc;
-  if (int rc = check_dims(mo->ob_dim, mo->ac_dim, od, ad)) return rc;
-  if (int rc = check_match_counts(mo)) return rc;
-  HIPCHK(hipSetDevice(E->device));
-  RolloutArgs r;
-  memset(&r, 0, sizeof r);
-  r.snaps = mo->params;
-  copy_match_fields(r, mo, E->N);
-  if (int rc = place_mlp_scratch(E, mo->ob_dim, mo->ac_dim, r)) return rc;
-  if (int rc = place_zoo_lstm_table(r, r.zl, z, od, ad, 4 * PT_HS)) return rc;   // the two hidden tiles of agent 0's trunk
-  return rollout_launch(E, r, 6, b, stream);
-}
-
-extern "C" int sumo_match_steps_lstm_zoo_lstm(sumo_handle_t E, const sumo_match_lstm* mo, const sumo_zoo_lstm* z, float* actions_dev,
-                                              float* obs_dev, double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev,
-                                              int32_t* ep_l_dev, void* stream) {
-  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
-  if (int rc = check_launch_args(E, mo, b)) return rc;
-  if (!z) FAIL(-1, "bad arguments");
-  if (!mo->proto || !mo->nets_dev) FAIL(-2, "sumo_match_lstm: missing buffer");
-  if (!mo->state0) FAIL(-2, "sumo_match_lstm: missing state buffer (state0)");
-  if (mo->state1) FAIL(-2, "sumo_match_steps_lstm_zoo_lstm: state1 must be NULL (agent 1's state is the zoo table's state)");
-  if (int rc = check_match_buffers(mo, "sumo_match_lstm")) return rc;
-  int od = 0, ad = 0;
-  if (int rc = rollout_scene(E, mo->T, E->N, 0, mo->s0, mo->K, &od, &ad)) return rc;
-  const ppo_lstm_net& n = *mo->proto;
-  if (int rc = check_dims(n.ob_dim, n.ac_dim, od, ad)) return rc;
-  if (int rc = check_lstm_shape(n, "matches")) return rc;
-  if (!n.wx || !n.wh || !n.b || !n.head_w || !n.head_b || !n.logstd) FAIL(-10, "prototype net: missing weights");
-  if (int rc = check_match_counts(mo)) return rc;
-  HIPCHK(hipSetDevice(E->device));
-  RolloutArgs r;
-  memset(&r, 0, sizeof r);
-  r.lnet = n; r.onets = mo->nets_dev; r.st0 = mo->state0;
-  copy_match_fields(r, mo, E->N);
-  if (int rc = place_lstm_scratch(E, od, 2, r)) return rc;   // agent 0's previous and new latent
-  if (int rc = place_zoo_lstm_table(r, r.zl, z, od, ad, 2 * 128)) return rc;
-  return rollout_launch(E, r, 7, b, stream);
-}
-
-extern "C" int sumo_rollout_steps_zoo_lstm(sumo_handle_t E, const sumo_rollout* ro, const sumo_zoo_lstm* z, float* actions_dev, float* obs_dev,
-                                           double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
-  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
-  if (int rc = check_launch_args(E, ro, b)) return rc;
-  if (!z) FAIL(-1, "bad arguments");
-  if (!ro->learner_params || rollout_buffer_missing(ro)) FAIL(-2, "sumo_rollout: missing buffer");
-  if (ro->opponent_params) FAIL(-2, "sumo_rollout_steps_zoo_lstm: opponent_params must be NULL (the opponents are the zoo table's nets)");
-  int od = 0, ad = 0;
-  if (int rc = rollout_scene(E, ro->T, ro->Ntot, ro->env_offset, ro->s0, ro->K, &od, &ad)) return rc;
-  if (int rc = check_dims(ro->ob_dim, ro->ac_dim, od, ad)) return rc;
-  if (ro->npool != z->nzoo) FAIL(-7, "npool %d must equal the zoo table's nzoo %d", ro->npool, z->nzoo);
-  HIPCHK(hipSetDevice(E->device));
-  RolloutArgs r;
-  memset(&r, 0, sizeof r);
-  r.learner = ro->learner_params; r.opp_idx = ro->opponent_index;
-  copy_rollout_fields(r, ro);
-  if (int rc = place_mlp_scratch(E, ro->ob_dim, ro->ac_dim, r)) return rc;
-  if (int rc = place_zoo_lstm_table(r, r.zlr, z, od, ad, 4 * PT_HS)) return rc;   // the two hidden tiles of the learner's trunks
-  return rollout_launch(E, r, 8, b, stream);
-}
-
-// what sumo_rollout_steps_lstm_zoo and sumo_rollout_steps_lstm_zoo_lstm share.  check_lstm_zoo_rollout: the checks of
-// sumo_rollout_steps_lstm on a launch without opponent nets; place_lstm_zoo_rollout: the learner's fields and the scratch -- x [2][XS]
-// and LSTM_ZOO_ROWS rows of 128 floats (zero row, agent 0's previous latent, two new latents), which the zoo net's hidden tiles /
-// cell rows reuse
-constexpr int LSTM_ZOO_ROWS = 4;
-static_assert(4 * PT_HS <= LSTM_ZOO_ROWS * 128, "mode 9: the zoo trunk's two hidden tiles [2][PT_HS] go where the learner's latent rows were");
-static int check_lstm_zoo_rollout(sumo_engine* E, const sumo_rollout_lstm* ro, int nzoo, const char* name, int* od, int* ad) {
-  if (!ro->learner || !ro->state0 || rollout_buffer_missing(ro)) FAIL(-2, "sumo_rollout_lstm: missing buffer");
-  if (ro->opponents_dev || ro->state1)
-    FAIL(-2, "%s: opponents_dev and state1 must be NULL (the opponents are the zoo table's nets, agent 1's state is the table's)", name);
-  if (int rc = rollout_scene(E, ro->T, ro->Ntot, ro->env_offset, ro->s0, ro->K, od, ad)) return rc;
-  const ppo_lstm_net& n = *ro->learner;
-  if (int rc = check_dims(n.ob_dim, n.ac_dim, *od, *ad)) return rc;
-  if (int rc = check_lstm_shape(n, "rollout")) return rc;
-  if (!n.wx || !n.wh || !n.b || !n.head_w || !n.head_b || !n.logstd || !n.vf_w || !n.vf_b) FAIL(-10, "learner net: missing weights");
-  if (ro->npool != nzoo) FAIL(-7, "npool %d must equal the zoo table's nzoo %d", ro->npool, nzoo);
-  if (ro->tile_net_dev && ((ro->env_offset & 15) || (E->N & 15))) FAIL(-11, "a zoo net per 16-env tile needs env_offset (%d) and the env count (%d) to be multiples of 16", ro->env_offset, E->N);
-  return 0;
-}
-static int place_lstm_zoo_rollout(sumo_engine* E, const sumo_rollout_lstm* ro, int od, RolloutArgs& r) {
-  HIPCHK(hipSetDevice(E->device));
-  memset(&r, 0, sizeof r);
-  r.lnet = *ro->learner; r.tile_net = ro->tile_net_dev; r.st0 = ro->state0;
-  copy_rollout_fields(r, ro);
-  return place_lstm_scratch(E, od, LSTM_ZOO_ROWS, r);
-}
-
-extern "C" int sumo_rollout_steps_lstm_zoo(sumo_handle_t E, const sumo_rollout_lstm* ro, const sumo_zoo_mlp* z, float* actions_dev, float* obs_dev,
-                                           double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
-  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
-  if (int rc = check_launch_args(E, ro, b)) return rc;
-  if (!z) FAIL(-1, "bad arguments");
-  RolloutArgs r;
-  int od = 0, ad = 0;
-  if (int rc = check_lstm_zoo_rollout(E, ro, z->nzoo, "sumo_rollout_steps_lstm_zoo", &od, &ad)) return rc;
-  if (int rc = check_zoo_table(z, od)) return rc;
-  if (int rc = place_lstm_zoo_rollout(E, ro, od, r)) return rc;
-  r.opponent = z->params;
-  r.L = make_layout(z->ob_dim, ad);
-  r.zt.filt = z->filt; r.zt.clip = z->obs_clip; r.zt.nzoo = z->nzoo; r.zt.Dz = z->ob_dim; r.zt.A = ad; r.zt.Pz = r.L.P;
-  return rollout_launch(E, r, 9, b, stream);
-}
-
-extern "C" int sumo_rollout_steps_lstm_zoo_lstm(sumo_handle_t E, const sumo_rollout_lstm* ro, const sumo_zoo_lstm* z, float* actions_dev,
-                                                float* obs_dev, double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev,
-                                                int32_t* ep_l_dev, void* stream) {
-  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
-  if (int rc = check_launch_args(E, ro, b)) return rc;
-  if (!z) FAIL(-1, "bad arguments");
-  RolloutArgs r;
-  int od = 0, ad = 0;
-  if (int rc = check_lstm_zoo_rollout(E, ro, z->nzoo, "sumo_rollout_steps_lstm_zoo_lstm", &od, &ad)) return rc;
-  if (int rc = place_lstm_zoo_rollout(E, ro, od, r)) return rc;   // (the table's checks need the placed scratch: as modes 6-8)
-  if (int rc = place_zoo_lstm_table(r, r.zt, z, od, ad, LSTM_ZOO_ROWS * 128)) return rc;   // the cell's rows go where the learner's latent rows were
-  return rollout_launch(E, r, 10, b, stream);
-}
-
-// the league of sumo_rollout_steps_zoo_league / sumo_rollout_steps_lstm_zoo_league: the launch's checks of the struct, then -- after
-// the scratch is placed -- both tables into r.lg (the LSTM table as mode 10 travels: place_zoo_lstm_table with the ZooTailArgs)
+// a league: the launch's checks of the struct (before the device is touched), then -- after the scratch is placed -- both tables
+// and the entry of every tile
 static int check_zoo_league(sumo_engine* E, const sumo_zoo_league* z, int npool, int env_offset) {
   if (z->mlp.nzoo < 1 || z->lstm.nzoo < 1)
     FAIL(-7, "sumo_zoo_league: nzoo %d (MLP table) / %d (LSTM table): a mixed league needs at least one net of each family (a league of one family plays through that family's launch)", z->mlp.nzoo, z->lstm.nzoo);
@@ -4941,31 +4487,166 @@ static int check_zoo_league(sumo_engine* E, const sumo_zoo_league* z, int npool,
   return 0;
 }
 static int place_zoo_league(RolloutArgs& r, const sumo_zoo_league* z, int od, int ad, int rows_floats) {
-  if (int rc = check_zoo_table(&z->mlp, od)) return rc;
-  if (int rc = place_zoo_lstm_table(r, r.lg.l, &z->lstm, od, ad, rows_floats)) return rc;
-  r.lg.mparams = z->mlp.params; r.lg.mfilt = z->mlp.filt; r.lg.mclip = z->mlp.obs_clip; r.lg.nmlp = z->mlp.nzoo; r.lg.Dm = z->mlp.ob_dim;
-  r.lg.Lz = make_layout(z->mlp.ob_dim, ad);
+  if (int rc = place_zoo_mlp_table(r, &z->mlp, od, ad)) return rc;
+  if (int rc = place_zoo_lstm_table(r, &z->lstm, od, ad, rows_floats)) return rc;
   r.tile_net = z->tile_entry_dev;
   return 0;
+}
+
+// ---- the thirteen entry points: env buffers, the family's checks (and the mode's), begin_*, the scratch of the learner's /
+// checkpoints' side, the opponent table, launch.  Where a zoo MLP table comes before the scratch and a zoo LSTM table after it, that
+// is the order in which the mode reports their errors. ----
+extern "C" int sumo_rollout_steps(sumo_handle_t E, const sumo_rollout* ro, float* actions_dev, float* obs_dev, double* info_dev,
+                                  uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
+  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
+  RolloutArgs r = {};
+  int od = 0, ad = 0;
+  if (int rc = check_launch_args(E, ro, b)) return rc;
+  if (int rc = check_mlp_rollout(E, ro, NULL, false, &od, &ad)) return rc;
+  if (ro->npool < 1) FAIL(-7, "npool %d", ro->npool);
+  if (int rc = begin_mlp_rollout(E, ro, r)) return rc;
+  if (int rc = place_mlp_scratch(E, ro->ob_dim, ro->ac_dim, r, 3)) return rc;
+  return rollout_launch(E, r, 0, b, stream);
+}
+
+extern "C" int sumo_rollout_steps_lstm(sumo_handle_t E, const sumo_rollout_lstm* ro, float* actions_dev, float* obs_dev, double* info_dev,
+                                       uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
+  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
+  RolloutArgs r = {};
+  int od = 0, ad = 0;
+  if (int rc = check_launch_args(E, ro, b)) return rc;
+  if (int rc = check_lstm_rollout(E, ro, NULL, 0, &od, &ad)) return rc;
+  if (int rc = begin_lstm_rollout(E, ro, od, 7, r)) return rc;   // zero row, previous latents [3], new latents [3]
+  return rollout_launch(E, r, 1, b, stream);
+}
+
+extern "C" int sumo_match_steps(sumo_handle_t E, const sumo_match* mo, float* actions_dev, float* obs_dev, double* info_dev,
+                                uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
+  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
+  RolloutArgs r = {};
+  int od = 0, ad = 0;
+  if (int rc = check_launch_args(E, mo, b)) return rc;
+  if (int rc = begin_mlp_match(E, mo, &od, &ad, r)) return rc;
+  if (int rc = place_mlp_scratch(E, mo->ob_dim, mo->ac_dim, r, 2)) return rc;
+  return rollout_launch(E, r, 2, b, stream);
+}
+
+extern "C" int sumo_match_steps_lstm(sumo_handle_t E, const sumo_match_lstm* mo, float* actions_dev, float* obs_dev, double* info_dev,
+                                     uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
+  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
+  RolloutArgs r = {};
+  int od = 0, ad = 0;
+  if (int rc = check_launch_args(E, mo, b)) return rc;
+  if (int rc = begin_lstm_match(E, mo, NULL, &od, &ad, r)) return rc;
+  return rollout_launch(E, r, 3, b, stream);
+}
+
+extern "C" int sumo_rollout_steps_zoo(sumo_handle_t E, const sumo_rollout* ro, const sumo_zoo_mlp* z, float* actions_dev, float* obs_dev,
+                                      double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
+  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
+  RolloutArgs r = {};
+  int od = 0, ad = 0;
+  if (int rc = check_launch_args(E, ro, b)) return rc;
+  if (!z) FAIL(-1, "bad arguments");
+  if (int rc = check_mlp_rollout(E, ro, "sumo_rollout_steps_zoo", false, &od, &ad)) return rc;
+  if (ro->npool != z->nzoo) FAIL(-7, "npool %d must equal the zoo table's nzoo %d", ro->npool, z->nzoo);
+  if (int rc = begin_mlp_rollout(E, ro, r)) return rc;
+  if (int rc = place_zoo_mlp_table(r, z, od, ad)) return rc;
+  if (int rc = place_mlp_scratch(E, ro->ob_dim, ro->ac_dim, r)) return rc;
+  return rollout_launch(E, r, 4, b, stream);
+}
+
+extern "C" int sumo_match_steps_zoo(sumo_handle_t E, const sumo_match* mo, const sumo_zoo_mlp* z, float* actions_dev, float* obs_dev,
+                                    double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
+  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
+  RolloutArgs r = {};
+  int od = 0, ad = 0;
+  if (int rc = check_launch_args(E, mo, b)) return rc;
+  if (!z) FAIL(-1, "bad arguments");
+  if (int rc = begin_mlp_match(E, mo, &od, &ad, r)) return rc;
+  if (int rc = place_zoo_mlp_table(r, z, od, ad)) return rc;
+  if (int rc = place_mlp_scratch(E, mo->ob_dim, mo->ac_dim, r)) return rc;
+  return rollout_launch(E, r, 5, b, stream);
+}
+
+extern "C" int sumo_match_steps_zoo_lstm(sumo_handle_t E, const sumo_match* mo, const sumo_zoo_lstm* z, float* actions_dev, float* obs_dev,
+                                         double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
+  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
+  RolloutArgs r = {};
+  int od = 0, ad = 0;
+  if (int rc = check_launch_args(E, mo, b)) return rc;
+  if (!z) FAIL(-1, "bad arguments");
+  if (int rc = begin_mlp_match(E, mo, &od, &ad, r)) return rc;
+  if (int rc = place_mlp_scratch(E, mo->ob_dim, mo->ac_dim, r)) return rc;
+  if (int rc = place_zoo_lstm_table(r, z, od, ad, 4 * PT_HS)) return rc;   // the two hidden tiles of agent 0's trunk
+  return rollout_launch(E, r, 6, b, stream);
+}
+
+extern "C" int sumo_match_steps_lstm_zoo_lstm(sumo_handle_t E, const sumo_match_lstm* mo, const sumo_zoo_lstm* z, float* actions_dev,
+                                              float* obs_dev, double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev,
+                                              int32_t* ep_l_dev, void* stream) {
+  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
+  RolloutArgs r = {};
+  int od = 0, ad = 0;
+  if (int rc = check_launch_args(E, mo, b)) return rc;
+  if (!z) FAIL(-1, "bad arguments");
+  if (int rc = begin_lstm_match(E, mo, "sumo_match_steps_lstm_zoo_lstm", &od, &ad, r)) return rc;
+  if (int rc = place_zoo_lstm_table(r, z, od, ad, 2 * 128)) return rc;   // agent 0's previous and new latent
+  return rollout_launch(E, r, 7, b, stream);
+}
+
+extern "C" int sumo_rollout_steps_zoo_lstm(sumo_handle_t E, const sumo_rollout* ro, const sumo_zoo_lstm* z, float* actions_dev, float* obs_dev,
+                                           double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
+  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
+  RolloutArgs r = {};
+  int od = 0, ad = 0;
+  if (int rc = check_launch_args(E, ro, b)) return rc;
+  if (!z) FAIL(-1, "bad arguments");
+  if (int rc = check_mlp_rollout(E, ro, "sumo_rollout_steps_zoo_lstm", false, &od, &ad)) return rc;
+  if (ro->npool != z->nzoo) FAIL(-7, "npool %d must equal the zoo table's nzoo %d", ro->npool, z->nzoo);
+  if (int rc = begin_mlp_rollout(E, ro, r)) return rc;
+  if (int rc = place_mlp_scratch(E, ro->ob_dim, ro->ac_dim, r)) return rc;
+  if (int rc = place_zoo_lstm_table(r, z, od, ad, 4 * PT_HS)) return rc;   // the two hidden tiles of the learner's trunks
+  return rollout_launch(E, r, 8, b, stream);
+}
+
+extern "C" int sumo_rollout_steps_lstm_zoo(sumo_handle_t E, const sumo_rollout_lstm* ro, const sumo_zoo_mlp* z, float* actions_dev, float* obs_dev,
+                                           double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
+  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
+  RolloutArgs r = {};
+  int od = 0, ad = 0;
+  if (int rc = check_launch_args(E, ro, b)) return rc;
+  if (!z) FAIL(-1, "bad arguments");
+  if (int rc = check_lstm_rollout(E, ro, "sumo_rollout_steps_lstm_zoo", z->nzoo, &od, &ad)) return rc;
+  if (int rc = place_zoo_mlp_table(r, z, od, ad)) return rc;                      // (needs no scratch: its errors come first)
+  if (int rc = begin_lstm_rollout(E, ro, od, LSTM_ZOO_ROWS, r)) return rc;
+  return rollout_launch(E, r, 9, b, stream);
+}
+
+extern "C" int sumo_rollout_steps_lstm_zoo_lstm(sumo_handle_t E, const sumo_rollout_lstm* ro, const sumo_zoo_lstm* z, float* actions_dev,
+                                                float* obs_dev, double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev,
+                                                int32_t* ep_l_dev, void* stream) {
+  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
+  RolloutArgs r = {};
+  int od = 0, ad = 0;
+  if (int rc = check_launch_args(E, ro, b)) return rc;
+  if (!z) FAIL(-1, "bad arguments");
+  if (int rc = check_lstm_rollout(E, ro, "sumo_rollout_steps_lstm_zoo_lstm", z->nzoo, &od, &ad)) return rc;
+  if (int rc = begin_lstm_rollout(E, ro, od, LSTM_ZOO_ROWS, r)) return rc;
+  if (int rc = place_zoo_lstm_table(r, z, od, ad, LSTM_ZOO_ROWS * 128)) return rc;   // the cell's rows go where the learner's latent rows were
+  return rollout_launch(E, r, 10, b, stream);
 }
 
 extern "C" int sumo_rollout_steps_zoo_league(sumo_handle_t E, const sumo_rollout* ro, const sumo_zoo_league* z, float* actions_dev, float* obs_dev,
                                              double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
   const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
+  RolloutArgs r = {};
+  int od = 0, ad = 0;
   if (int rc = check_launch_args(E, ro, b)) return rc;
   if (!z) FAIL(-1, "bad arguments");
-  if (!ro->learner_params || rollout_buffer_missing(ro)) FAIL(-2, "sumo_rollout: missing buffer");
-  if (ro->opponent_params || ro->opponent_index)
-    FAIL(-2, "sumo_rollout_steps_zoo_league: opponent_params and opponent_index must be NULL (the opponents are the league's nets, selected per tile by tile_entry_dev)");
-  int od = 0, ad = 0;
-  if (int rc = rollout_scene(E, ro->T, ro->Ntot, ro->env_offset, ro->s0, ro->K, &od, &ad)) return rc;
-  if (int rc = check_dims(ro->ob_dim, ro->ac_dim, od, ad)) return rc;
+  if (int rc = check_mlp_rollout(E, ro, "sumo_rollout_steps_zoo_league", true, &od, &ad)) return rc;
   if (int rc = check_zoo_league(E, z, ro->npool, ro->env_offset)) return rc;
-  HIPCHK(hipSetDevice(E->device));
-  RolloutArgs r;
-  memset(&r, 0, sizeof r);
-  r.learner = ro->learner_params;
-  copy_rollout_fields(r, ro);
+  if (int rc = begin_mlp_rollout(E, ro, r)) return rc;
   if (int rc = place_mlp_scratch(E, ro->ob_dim, ro->ac_dim, r)) return rc;   // the zoo trunk's hidden tiles are the learner's ...
   if (int rc = place_zoo_league(r, z, od, ad, 4 * PT_HS)) return rc;         // ... and the cell's rows go there too, as in mode 8
   return rollout_launch(E, r, 11, b, stream);
@@ -4975,14 +4656,14 @@ extern "C" int sumo_rollout_steps_lstm_zoo_league(sumo_handle_t E, const sumo_ro
                                                   float* obs_dev, double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev,
                                                   int32_t* ep_l_dev, void* stream) {
   const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
+  RolloutArgs r = {};
+  int od = 0, ad = 0;
   if (int rc = check_launch_args(E, ro, b)) return rc;
   if (!z) FAIL(-1, "bad arguments");
-  RolloutArgs r;
-  int od = 0, ad = 0;
   if (ro->tile_net_dev) FAIL(-2, "sumo_rollout_steps_lstm_zoo_league: tile_net_dev must be NULL (the league's tile_entry_dev selects the nets)");
-  if (int rc = check_lstm_zoo_rollout(E, ro, z->mlp.nzoo + z->lstm.nzoo, "sumo_rollout_steps_lstm_zoo_league", &od, &ad)) return rc;
+  if (int rc = check_lstm_rollout(E, ro, "sumo_rollout_steps_lstm_zoo_league", z->mlp.nzoo + z->lstm.nzoo, &od, &ad)) return rc;
   if (int rc = check_zoo_league(E, z, ro->npool, ro->env_offset)) return rc;
-  if (int rc = place_lstm_zoo_rollout(E, ro, od, r)) return rc;   // LSTM_ZOO_ROWS rows hold the larger of the two zoo passes (static_assert above)
+  if (int rc = begin_lstm_rollout(E, ro, od, LSTM_ZOO_ROWS, r)) return rc;   // the rows hold the larger of the two zoo passes (static_assert above)
   if (int rc = place_zoo_league(r, z, od, ad, LSTM_ZOO_ROWS * 128)) return rc;
   return rollout_launch(E, r, 12, b, stream);
 }

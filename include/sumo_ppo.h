@@ -205,7 +205,8 @@ int ppo_selection_scores(const float* ref_params, const float* table, int table_
  * is pre-divided by inv_count = 1/global_count (so summing grads over ranks gives the gradient of the global mean loss).
  * stats double[PPO_NSTATS] accumulate the un-normalised sums.  log_ratio_out [n] (minibatch order) may be NULL.
  * workspace: ppo_grad_workspace_bytes(ob_dim, ac_dim) bytes of scratch, ZERO-INITIALISED once by the caller (its tail holds the arrival
- * counters of the in-launch slab reduction, which every call leaves at zero); one ppo_grad in flight per workspace. */
+ * counters of the in-launch slab reduction, which every call leaves at zero); one ppo_grad in flight per workspace.
+ * Environment PPO_GRAD_BLOCKS (1..1024, default 256; read on every call): workgroups per net, i.e. how many 16-row tiles a workgroup walks. */
 size_t ppo_grad_workspace_bytes(int ob_dim, int ac_dim);
 int ppo_grad(const float* params, const float* obs, int obs_stride, int ob_dim, int ac_dim, const float* actions,
              const float* adv_mb, const float* returns, const float* old_neglogp, const float* is_weight,

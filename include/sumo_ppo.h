@@ -121,13 +121,16 @@ int ppo_lstm_seq_backward(const ppo_lstm_net* net, int T, int n, const float* dl
 /* PPO loss heads on stored latents (rows = all (time, env) pairs of the minibatch): forward of the Gaussian / value heads,
  * loss terms of model.py:65-111 and their gradients.  Outputs: dlatent [rows][hidden], dmean [rows][ac_dim], dvalue [rows],
  * dlogstd_rows [rows][ac_dim] (sum over rows - ent_coef = d loss / d logstd), stats double[PPO_NSTATS] (+= un-normalised sums
- * as ppo_grad; stats[2] is not touched).  inv_count = 1 / (global number of rows). */
+ * as ppo_grad; stats[2] is not touched).  inv_count = 1 / (global number of rows).  A row whose old neglogp is NaN gets ratio 2 and
+ * zero dmean / dlogstd_rows (model.py:96) and is counted in stats[4], but its nlp - old still enters stats[3]: stats[3] is left NaN, as
+ * the reference's approxkl is. */
 int ppo_lstm_head_grad(const ppo_lstm_net* net, const float* latent, int rows, const float* actions, const float* adv,
                        const float* returns, const float* old_neglogp, const float* is_weight, double inv_count, float cliprange,
                        float vf_coef, float* dlatent, float* dmean, float* dvalue, float* dlogstd_rows, double* stats, void* stream);
 /* One step of BPTT (gate order i,f,o,u): dh_carry / dc_carry [n][hidden] hold d loss / d (h_t, c_t) flowing from later steps and
  * are replaced by the values for step t-1 (already multiplied by 1 - mask_t); dz_out [n][4*hidden] receives d loss / d
- * (pre-activation gates), whose products with the inputs give the weight gradients (plain GEMMs, done by the caller). */
+ * (pre-activation gates), whose products with the inputs give the weight gradients (plain GEMMs, done by the caller).
+ * net->wh is read with 16-byte vector loads: it must be 16-byte aligned (the model's flat parameter layout guarantees it). */
 int ppo_lstm_bwd_step(const ppo_lstm_net* net, int n, const float* dlatent_t, const float* mask_t, const float* gates_t,
                       const float* cprev_t, const float* tanhc_t, float* dh_carry, float* dc_carry, float* dz_out, void* stream);
 
@@ -137,7 +140,8 @@ int ppo_lstm_bwd_step(const ppo_lstm_net* net, int n, const float* dlatent_t, co
  * written into `grads` in checkpoint order (wx | wh | b | pi/w | pi/b | logstd | vf/w | vf/b); logstd_shift is added to the
  * logstd gradient (the entropy term - ent_coef / world).  x [rows][ob_dim], hprev / latent [rows][hidden], dz [rows][4 hidden],
  * dmean / dlogstd_rows [rows][ac_dim], dvalue [rows].  Split-K MFMA kernel + fixed-order slab reduction (deterministic).
- * workspace: ppo_lstm_wgrad_workspace_bytes(ob_dim, hidden, ac_dim) bytes. */
+ * workspace: ppo_lstm_wgrad_workspace_bytes(ob_dim, hidden, ac_dim) bytes, sized for hidden 64 / 128, ob_dim 1..512, ac_dim 1..16:
+ * anything else is an argument error (negative code, nothing launched). */
 size_t ppo_lstm_wgrad_workspace_bytes(int ob_dim, int hidden, int ac_dim);
 int ppo_lstm_wgrad(const ppo_lstm_net* net, int rows, const float* x, const float* hprev, const float* dz, const float* latent,
                    const float* dmean, const float* dvalue, const float* dlogstd_rows, float logstd_shift, float* grads, void* workspace,

@@ -1196,6 +1196,10 @@ extern "C" int ppo_lstm_wgrad(const ppo_lstm_net* net, int rows, const float* x,
                               void* workspace, void* stream) {
   if (!net || !x || !hprev || !dz || !latent || !dmean || !dvalue || !dlogstd_rows || !grads || !workspace || rows <= 0) FAIL(-1, "bad arguments");
   if (net->emb_w) FAIL(-2, "the baselines LSTM has no embedding layer");
+  // (ppo_lstm_wgrad_workspace_bytes sizes the slabs for these ranges: 64 chunks of ceil64(ob_dim + hidden + 1) x 4 hidden floats)
+  if (net->hidden != 64 && net->hidden != 128) FAIL(-3, "hidden %d: only 64 and 128 are built", net->hidden);
+  if (net->ob_dim < 1 || net->ob_dim > 512) FAIL(-4, "ob_dim %d not in [1,512]", net->ob_dim);
+  if (net->ac_dim < 1 || net->ac_dim > MAXA) FAIL(-5, "ac_dim %d not in [1,%d]", net->ac_dim, MAXA);
   const int D = net->ob_dim, Hh = net->hidden, Aa = net->ac_dim;
   hipStream_t st = (hipStream_t)stream;
   int chunks = (rows + 255) / 256;

@@ -8,7 +8,10 @@
 
 Play is stochastic (model.step samples, as in the reference script) unless --deterministic is given; every agent reports its
 height with adjust_z = -0.5 (compare_history_version.py:73-74).  MLP(64,64) and LSTM runs (learn(network='lstm')) are both
-accepted: the network is read from the checkpoints and recorded in the JSON output; both runs must use the same one.
+accepted: the network is read from the checkpoints and recorded in the JSON output; both runs must use the same one, unless
+--cross_family is given: then an MLP(64,64) run and an LSTM run play each other, P1 as agent 0.
+
+    python compare_versions.py --p1 results/mlp/RoboSumo-Ant-vs-Ant-v0-0 --p2 results/lstm/RoboSumo-Ant-vs-Ant-v0-0 --cross_family
 """
 import argparse
 import json
@@ -32,6 +35,7 @@ def parse_args(argv):
     ap.add_argument("--adjust_z", type=float, default=-0.5, help="Agent._adjust_z of every agent (compare_history_version.py:73-74)")
     ap.add_argument("--env", default="RoboSumo-Ant-vs-Ant-v0")
     ap.add_argument("--chunk", type=int, default=64, help="env steps per fused launch")
+    ap.add_argument("--cross_family", action="store_true", help="paired mode: let an MLP(64,64) run play an LSTM run (refused otherwise)")
     ap.add_argument("--out", help="JSON output path (default: next to the run)")
     args = ap.parse_args(argv)
     if args.round_robin:
@@ -64,13 +68,15 @@ def main(argv):
                    loss=[[None if i == j else float(r["loss"][i, j]) for j in range(V)] for i in range(V)])
         out = args.out or os.path.join(args.path, "round_robin.json")
     else:
-        r = matches.compare_history_versions(args.p1, args.p2, args.trials, **kw)
+        r = matches.compare_history_versions(args.p1, args.p2, args.trials, cross_family=args.cross_family, **kw)
         for (a, b), w, res in zip(r["versions"], r["win_rate"], r["results"]):
             print("-----P1 %s vs P2 %s: P1 win rate %.2f (%d wins, %d losses, %d draws)-----" % (a, b, w, res["wins"], res["losses"],
                                                                                              res["draws"]))
         rec = dict(mode="paired", p1=args.p1, p2=args.p2, trials=args.trials, deterministic=args.deterministic,
                    network=r["network"], nlstm=r["nlstm"], versions=[list(v) for v in r["versions"]], win_rate=r["win_rate"],
-                   results=r["results"])
+                   results=r["results"], cross_family=args.cross_family)
+        if "networks" in r:
+            rec["networks"] = r["networks"]
         out = args.out or os.path.join(args.p1, "compare_versions_vs_%s.json" % os.path.basename(os.path.normpath(args.p2)))
     with open(out, "w") as f:
         json.dump(rec, f, indent=1)

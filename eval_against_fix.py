@@ -6,7 +6,8 @@ fixed policy-zoo opponent (MLP or LSTM net) on the GPU and print / save win, dra
         --num_env 256 --rounds 512 --interval 10
     python eval_against_fix.py --path results/RoboSumo-Ant-vs-Ant-v0-0 --opponent_path <zoo v1>.npy --opponent_path <zoo v3>.npy \
         --fused --trials 512 --interval 10      (all checkpoints x opponents batched over the envs, one fused launch per 64 steps;
-                                                 MLP and LSTM opponent files may be mixed: each family plays in launches of its own)
+                                                 MLP and LSTM opponent files may be mixed: each family plays in launches of its own;
+                                                 an LSTM run plays zoo MLP files with --cross_family)
 """
 import argparse
 import json
@@ -34,6 +35,7 @@ def main(argv):
     ap.add_argument("--fused", action="store_true", help="play every selected checkpoint against every opponent in fused match launches "
                     "(matches.evaluate_history_against_zoo): zoo MLP and LSTM opponents, exactly --trials games per checkpoint and opponent")
     ap.add_argument("--trials", type=int, default=None, help="games per checkpoint and opponent with --fused (default: --rounds)")
+    ap.add_argument("--cross_family", action="store_true", help="with --fused: let an LSTM run play zoo MLP files too (refused otherwise)")
     args = ap.parse_args(argv)
     import numpy as np
     if args.fused:
@@ -75,7 +77,7 @@ def main_fused(args):
     trials = args.trials if args.trials is not None else args.rounds
     r = matches.evaluate_history_against_zoo(args.path, args.opponent_path, trials, start=args.start, interval=args.interval,
                                              num_env=args.num_env, deterministic=not args.stochastic, fused=True, seed=args.seed,
-                                             adjust_z=args.adjust_z, env_id=args.env)
+                                             adjust_z=args.adjust_z, env_id=args.env, cross_family=args.cross_family)
     table = []
     for cid in r["checkpoints"]:
         row = [cid]
@@ -87,6 +89,9 @@ def main_fused(args):
         table.append(row)
     with open(os.path.join(args.path, "eval_against_fix.json"), "w") as f:
         json.dump(table, f)
+    with open(os.path.join(args.path, "eval_against_fix_networks.json"), "w") as f:   # which families met (the table above is rates only)
+        json.dump(dict(cross_family=args.cross_family, networks=[dict(network=r["network"], nlstm=r["nlstm"]), r["opponent_networks"]],
+                       checkpoints=r["checkpoints"], opponents=r["opponents"]), f, indent=1)
     return np.array(table)
 
 

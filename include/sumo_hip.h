@@ -234,6 +234,45 @@ int sumo_match_steps_zoo_lstm(sumo_handle_t h, const sumo_match* m, const sumo_z
 int sumo_match_steps_lstm_zoo_lstm(sumo_handle_t h, const sumo_match_lstm* m, const sumo_zoo_lstm* z, float* actions_dev, float* obs_dev,
                                    double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev,
                                    void* stream);
+/* CROSS-FAMILY checkpoint matches: an MLP(64,64) run against an LSTM(128) run (which of `run.py --network mlp` and `--network lstm`
+ * wins?).  Agent lstm_side acts as that agent of sumo_match_steps_lstm does -- net nets_dev[idx_g[e]] on (obs g, state[e]), the state
+ * row zeroed first where ITS done flag of the previous step is set, LstmPPOModel.step(obs, S, M) -- and the other agent as that agent
+ * of sumo_match_steps does (checkpoint idx_g[e] of params, PPOModel.step); every number of a side equals ppo_lstm_step / ppo_forward
+ * bit for bit.
+ *   params, nsnap_mlp, ob_dim, ac_dim   the MLP side's table [nsnap_mlp][P], as sumo_match
+ *   proto, nets_dev, nsnap_lstm         the LSTM side's table, as sumo_match_lstm
+ *   state      DEVICE float32 [E][256] (c | h) of the recurrent agent, read at step s0 and left at the state after step s0 + K - 1
+ *   lstm_side  0 or 1: the agent the LSTM table plays, for every env of the launch; idx0 / idx1 [E] index the table of THEIR agent,
+ *              and each is checked against its own table's size (an index outside it raises the abort flag: sumo_rollout_status
+ *              returns -20, row 0 plays)
+ *   noise0 / noise1, score, quota, T / s0 / K  as sumo_match
+ * Refused: whatever sumo_match_steps and sumo_match_steps_lstm refuse for their halves (cfrc_mode rne_post, mixed match-ups, ob_dim
+ * / ac_dim other than the scene's, a proto of another shape, missing buffers, one noise pointer without the other), lstm_side
+ * outside {0, 1}, a missing state, nsnap_mlp or nsnap_lstm below 1, a scene whose per-step LDS area cannot hold the observation tile
+ * plus the larger of the latent rows and the MLP trunk's hidden tiles. */
+typedef struct sumo_match_cross {
+  const float* params;
+  int nsnap_mlp, ob_dim, ac_dim;
+  const ppo_lstm_net* proto;
+  const ppo_lstm_net* nets_dev;
+  int nsnap_lstm;
+  float* state;
+  int lstm_side;
+  const int32_t *idx0, *idx1;
+  int T, s0, K, quota;
+  const float *noise0, *noise1;
+  int32_t* score;
+} sumo_match_cross;
+int sumo_match_steps_cross(sumo_handle_t h, const sumo_match_cross* m, float* actions_dev, float* obs_dev, double* info_dev,
+                           uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream);
+/* sumo_match_steps_lstm_zoo: LSTM(128) checkpoints (agent 0) against policy-zoo MLP nets (agent 1) -- eval_robosumo_against_fix.py's
+ *   games for a recurrent run against the reference's default opponent.  Agent 0 is agent 0 of sumo_match_steps_lstm (net m->idx0[e]
+ *   of m->nets_dev on its state m->state0) and reads the raw observation first; agent 1 is agent 1 of sumo_match_steps_zoo (zoo net
+ *   m->idx1[e] of z on the tile filtered in place, ppo_forward_filtered bit for bit).  m->state1 must be NULL (a zoo MLP net has no
+ *   state).  Noise, score, quota and the abort on a bad index (idx0 against nsnap, idx1 against nzoo) as sumo_match_steps.  Refused:
+ *   whatever sumo_match_steps_lstm refuses, state1 given, and the table z exactly as sumo_match_steps_zoo refuses it. */
+int sumo_match_steps_lstm_zoo(sumo_handle_t h, const sumo_match_lstm* m, const sumo_zoo_mlp* z, float* actions_dev, float* obs_dev,
+                              double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream);
 /* sumo_rollout_steps_zoo_lstm: sumo_rollout_steps_zoo with agent 1 played by a zoo LSTM net (learn(opponent_mode='fix') with an
  *   LSTM file): per step and env the learner's MLP(64,64) policy and value nets on both observations; the learner samples action 0;
  *   zoo net r->opponent_index[e] of z (NULL = net 0) acts on agent 1's observation from the env's row of z->state, which is zeroed

@@ -49,6 +49,13 @@ class MatchLstm(C.Structure):
     _fields_ = [("proto", _P), ("nets_dev", _P), ("idx0", _P), ("idx1", _P), ("nsnap", _I), ("state0", _P), ("state1", _P)] + _MATCH_TAIL
 
 
+class MatchCross(C.Structure):
+    """``sumo_match_cross`` of include/sumo_hip.h: an MLP(64,64) table and an LSTM(128) table, one per agent (``proto`` a host pointer
+    to a ``ppo_capi.LstmNet``, the rest device pointers; ``lstm_side``: the agent the LSTM table plays)."""
+    _fields_ = [("params", _P), ("nsnap_mlp", _I), ("ob_dim", _I), ("ac_dim", _I), ("proto", _P), ("nets_dev", _P), ("nsnap_lstm", _I),
+                ("state", _P), ("lstm_side", _I), ("idx0", _P), ("idx1", _P)] + _MATCH_TAIL
+
+
 class ZooMlp(C.Structure):
     """``sumo_zoo_mlp`` of include/sumo_hip.h: a device table of frozen policy-zoo MLP nets (device pointers as integers)."""
     _fields_ = [("params", _P), ("filt", _P), ("obs_clip", C.c_float), ("nzoo", _I), ("ob_dim", _I)]
@@ -95,6 +102,8 @@ def lib():
         L.sumo_rollout_steps_lstm_zoo_lstm.argtypes = [vp, C.POINTER(RolloutLstm), C.POINTER(ZooLstm)] + [vp] * 8
         L.sumo_rollout_steps_zoo_league.argtypes = [vp, C.POINTER(Rollout), C.POINTER(ZooLeague)] + [vp] * 8
         L.sumo_rollout_steps_lstm_zoo_league.argtypes = [vp, C.POINTER(RolloutLstm), C.POINTER(ZooLeague)] + [vp] * 8
+        L.sumo_match_steps_cross.argtypes = [vp, C.POINTER(MatchCross)] + [vp] * 8
+        L.sumo_match_steps_lstm_zoo.argtypes = [vp, C.POINTER(MatchLstm), C.POINTER(ZooMlp)] + [vp] * 8
         L.sumo_get_state.argtypes = [vp] * 5
         L.sumo_set_cfrc_mode.argtypes = [vp, i32]
         L.sumo_get_cfrc_ext.argtypes = [vp, vp]
@@ -114,7 +123,7 @@ def lib():
         L.sumo_profile.restype = i32
         for n in ("sumo_create", "sumo_destroy", "sumo_dims", "sumo_reset", "sumo_step", "sumo_rollout_steps", "sumo_rollout_steps_lstm", "sumo_match_steps", "sumo_match_steps_lstm",
                   "sumo_rollout_steps_zoo", "sumo_match_steps_zoo", "sumo_match_steps_zoo_lstm", "sumo_match_steps_lstm_zoo_lstm", "sumo_rollout_steps_zoo_lstm", "sumo_rollout_steps_lstm_zoo", "sumo_rollout_steps_lstm_zoo_lstm",
-                  "sumo_rollout_steps_zoo_league", "sumo_rollout_steps_lstm_zoo_league", "sumo_get_state", "sumo_set_cfrc_mode", "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_set_state", "sumo_debug_forward", "sumo_stats"):
+                  "sumo_rollout_steps_zoo_league", "sumo_rollout_steps_lstm_zoo_league", "sumo_match_steps_cross", "sumo_match_steps_lstm_zoo", "sumo_get_state", "sumo_set_cfrc_mode", "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_set_state", "sumo_debug_forward", "sumo_stats"):
             getattr(L, n).restype = i32
         _LIB = L
     return _LIB
@@ -122,7 +131,7 @@ def lib():
 
 EXPORTS = ("sumo_last_error", "sumo_create", "sumo_destroy", "sumo_dims", "sumo_reset", "sumo_step", "sumo_rollout_steps",
            "sumo_rollout_steps_lstm", "sumo_match_steps", "sumo_match_steps_lstm", "sumo_rollout_steps_zoo", "sumo_match_steps_zoo", "sumo_match_steps_zoo_lstm", "sumo_match_steps_lstm_zoo_lstm", "sumo_rollout_steps_zoo_lstm", "sumo_rollout_steps_lstm_zoo", "sumo_rollout_steps_lstm_zoo_lstm",
-           "sumo_rollout_steps_zoo_league", "sumo_rollout_steps_lstm_zoo_league", "sumo_set_cfrc_mode", "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_get_state", "sumo_set_state", "sumo_debug_forward", "sumo_stats", "sumo_profile", "sumo_debug_trace",
+           "sumo_rollout_steps_zoo_league", "sumo_rollout_steps_lstm_zoo_league", "sumo_match_steps_cross", "sumo_match_steps_lstm_zoo", "sumo_set_cfrc_mode", "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_get_state", "sumo_set_state", "sumo_debug_forward", "sumo_stats", "sumo_profile", "sumo_debug_trace",
            "sumo_rollout_status", "sumo_debug_fault", "sumo_static_layout", "sumo_debug_layout", "sumo_debug_model_ints", "sumo_debug_dump")
 
 
@@ -243,6 +252,17 @@ class Engine:
         """The same for a recurrent learner (``sumo_rollout_steps_lstm_zoo_league``); ``ro`` is a filled :class:`RolloutLstm`
         (``opponents_dev`` / ``tile_net_dev`` / ``state1`` None, ``npool`` = the league's size)."""
         self._fused("sumo_rollout_steps_lstm_zoo_league", ro, env_ptrs, stream, league)
+
+    def match_steps_cross(self, mo, *env_ptrs, stream=None):
+        """K fused match steps of MLP(64,64) checkpoints against LSTM(128) checkpoints (``sumo_match_steps_cross``); ``mo`` is a
+        filled :class:`MatchCross` (``lstm_side``: the agent the LSTM table plays, ``state``: that agent's rows)."""
+        self._fused("sumo_match_steps_cross", mo, env_ptrs, stream)
+
+    def match_steps_lstm_zoo(self, mo, zoo, *env_ptrs, stream=None):
+        """K fused match steps of LSTM(128) checkpoints (agent 0) against policy-zoo MLP nets (agent 1)
+        (``sumo_match_steps_lstm_zoo``); ``mo`` is a filled :class:`MatchLstm` with ``state1`` left None, ``zoo`` a filled
+        :class:`ZooMlp` that ``idx1`` indexes."""
+        self._fused("sumo_match_steps_lstm_zoo", mo, env_ptrs, stream, zoo)
 
     def set_cfrc_mode(self, mode):
         """'zero' (default, the reference's behaviour) or 'rne_post' (include/sumo_hip.h: cfrc_mode)."""

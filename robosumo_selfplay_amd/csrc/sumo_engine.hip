@@ -2593,6 +2593,9 @@ struct RolloutArgs {
   // policy-zoo opponents (POLICY 4 .. 12); appended, so every field above keeps the offset the modes 0 .. 3 read it at
   ZooMlpTable zm;
   ZooLstmTable zl;
+  // cross-family matches (POLICY 13): the agent the LSTM(128) checkpoints play (the other one plays the MLP(64,64) checkpoints) and
+  // the size of their table onets (nsnap is the size of snaps); appended like the zoo tables
+  int lstm_side, nsnap_lstm;
 };
 
 // ---- pieces shared by the four policy phases (each reads a / r through the references its phase received) ----
@@ -2856,7 +2859,7 @@ __device__ __forceinline__ void rollout_policy_phase_match(C& c, const SA& a, co
   wave_sync();   // the action buffer is read back by the env step (other lanes), the scratch region becomes the mass matrix again
 }
 
-// ---- pieces of the match modes 3, 5, 6, 7 and of the zoo rollouts 4, 8 .. 12 (each exists once; the phases below compose them) ----
+// ---- pieces of the match modes 3, 5, 6, 7, 13, 14 and of the zoo rollouts 4, 8 .. 12 (each exists once; the phases below compose them) ----
 // Row j of a table of n entries, checked: an index outside [0, n) raises the launch's abort flag and plays row 0.
 template <class SA>
 __device__ __forceinline__ int policy_checked_row(const SA& a, int lane, int j, int n) {
@@ -2932,42 +2935,36 @@ __device__ __forceinline__ void rollout_policy_phase_match_lstm(C& c, const SA& 
   wave_sync();
 }
 
-// Agent 0 of the MLP matches against policy-zoo nets (POLICY 5 / 6): checkpoint idx0[e] of snaps [nsnap][P] on the raw tile (row 0
-// acts), mean or mean + exp(logstd) * noise0 as rollout_policy_phase_match.  xbuf: [2][XS] | h1 [2][PT_HS] | h2 [2][PT_HS]; column i
-// where ok.
+// One side of a match played by MLP(64,64) checkpoints: agent g in {0, 1} acts with checkpoint idx_g[e] of snaps [nsnap][P] on the raw
+// tile (row g acts), mean or mean + exp(logstd) * noise_g as rollout_policy_phase_match.  g = 0 (a literal) is agent 0 of the matches
+// against policy-zoo nets (POLICY 5 / 6); the cross-family matches (POLICY 13) pass the seat the launch gives the MLP checkpoints, a
+// scalar.  xbuf: [2][XS] | h1 [2][PT_HS] | h2 [2][PT_HS]; column i where ok.
 template <class SA, class RA>
-__device__ __forceinline__ float match_mlp_side0(const SA& a, const RA& r, int e, int s, int lane, int i, bool ok, float* xbuf) {
+__device__ __forceinline__ float match_mlp_side(const SA& a, const RA& r, int e, int s, int lane, int g, int i, bool ok, float* xbuf) {
   const int D = r.L.D, A = r.L.A, XS = r.XS;
   float* h1 = xbuf + 2 * XS;
   float* h2 = h1 + 2 * PT_HS;
-  const int j0 = policy_checked_row(a, lane, pt_global(r.idx0)[e], r.nsnap);
+  const int j0 = policy_checked_row(a, lane, pt_global(g ? r.idx1 : r.idx0)[e], r.nsnap);
   const float PT_GAS* p0 = pt_global(r.snaps) + (size_t)j0 * r.L.P;
   const f32x4 m0 = trunk_forward<false, 2>(pi_net((const float*)p0, r.L), xbuf, XS, D, h1, h2, lane);
-  float act0 = m0[0];
+  const float mean = g ? m0[1] : m0[0];
+  float act0 = mean;
   if (r.noise0) {
     const float ls0 = ok ? p0[r.L.logstd + i] : 0.0f;
-    const float n0 = ok ? pt_global(r.noise0)[policy_noise_index(a, e, s, A, i)] : 0.0f;
-    (void)gauss_row(m0[0], expf(ls0), 0.0f, ok, true, n0, act0, A);
+    const float n0 = ok ? pt_global(g ? r.noise1 : r.noise0)[policy_noise_index(a, e, s, A, i)] : 0.0f;
+    (void)gauss_row(mean, expf(ls0), 0.0f, ok, true, n0, act0, A);
   }
   return act0;
 }
 
-// Matches against policy-zoo MLP nets (sumo_match_steps_zoo, POLICY 5; the reference's eval_robosumo_against_fix.py:196-230):
-// agent 0 through match_mlp_side0, agent 1 with zoo net idx1[e] on the tile filtered in place afterwards.  Noise, score counters and
-// quota as sumo_match_steps.
-template <class C, class SA, class RA>
-__device__ __forceinline__ void rollout_policy_phase_match_zoo(C& c, const SA& a, const RA& r, int e, int s) {
-  const int lane = c.lane, i = lane & 15, kq = lane >> 4;
-  const int D = r.L.D, A = r.L.A, XS = r.XS;
+// Agent 1 played by policy-zoo MLP nets (POLICY 5 / 14): zoo net idx1[e] of the table zm on the tile, which is filtered in place (the
+// caller has finished every read of the raw rows); noise1, or the mean where noise0 is NULL.  xbuf as match_mlp_side; column i where ok.
+template <class SA, class RA>
+__device__ __forceinline__ float zoo_mlp_act(const SA& a, const RA& r, int e, int s, int lane, int i, bool ok, float* xbuf, int A) {
   const auto& t = r.zm;
-  float* xbuf = (float*)(c.sm + r.lds_off);        // [2][XS] | h1 [2][PT_HS] | h2 [2][PT_HS]
+  const int XS = r.XS;
   float* h1 = xbuf + 2 * XS;
   float* h2 = h1 + 2 * PT_HS;
-  policy_load_obs<false, false>(a, r, e, lane, xbuf, D, XS);
-  wave_sync();
-  const bool ok = i < A && kq == 0;                 // rows 0 and 1 live in the first 16 lanes (D layout: rows 4 kq + r)
-  const float act0 = match_mlp_side0(a, r, e, s, lane, i, ok, xbuf);
-  wave_sync();   // the raw tile is filtered in place
   const int j1 = policy_checked_row(a, lane, pt_global(r.idx1)[e], t.n);
   const float PT_GAS* p1 = pt_global(t.params) + (size_t)j1 * t.L.P;
   const f32x4 m1 = zoo_trunk_forward<2>(pi_net((const float*)p1, t.L), t.filt + (size_t)j1 * 2 * t.D, t.clip, xbuf, XS, t.D, h1, h2, lane);
@@ -2977,6 +2974,23 @@ __device__ __forceinline__ void rollout_policy_phase_match_zoo(C& c, const SA& a
     const float n1 = ok ? pt_global(r.noise1)[policy_noise_index(a, e, s, A, i)] : 0.0f;
     (void)gauss_row(m1[1], expf(ls1), 0.0f, ok, true, n1, act1, A);
   }
+  return act1;
+}
+
+// Matches against policy-zoo MLP nets (sumo_match_steps_zoo, POLICY 5; the reference's eval_robosumo_against_fix.py:196-230):
+// agent 0 through match_mlp_side, agent 1 through zoo_mlp_act (zoo net idx1[e] on the tile filtered in place afterwards).  Noise, score
+// counters and quota as sumo_match_steps.
+template <class C, class SA, class RA>
+__device__ __forceinline__ void rollout_policy_phase_match_zoo(C& c, const SA& a, const RA& r, int e, int s) {
+  const int lane = c.lane, i = lane & 15, kq = lane >> 4;
+  const int D = r.L.D, A = r.L.A, XS = r.XS;
+  float* xbuf = (float*)(c.sm + r.lds_off);        // [2][XS] | h1 [2][PT_HS] | h2 [2][PT_HS]
+  policy_load_obs<false, false>(a, r, e, lane, xbuf, D, XS);
+  wave_sync();
+  const bool ok = i < A && kq == 0;                 // rows 0 and 1 live in the first 16 lanes (D layout: rows 4 kq + r)
+  const float act0 = match_mlp_side(a, r, e, s, lane, 0, i, ok, xbuf);
+  wave_sync();   // the raw tile is filtered in place
+  const float act1 = zoo_mlp_act(a, r, e, s, lane, i, ok, xbuf, A);
   if (ok) policy_commit_actions<false>(c, a, r, e, i, act0, act1);
   wave_sync();   // the action buffer is read back by the env step (other lanes), the scratch region becomes the mass matrix again
 }
@@ -3047,7 +3061,7 @@ __device__ __forceinline__ float zoo_lstm_act(const SA& a, const RA& r, int e, i
   return act;
 }
 
-// MLP(64,64) checkpoints against policy-zoo LSTM nets (sumo_match_steps_zoo_lstm, POLICY 6): agent 0 through match_mlp_side0; agent 1
+// MLP(64,64) checkpoints against policy-zoo LSTM nets (sumo_match_steps_zoo_lstm, POLICY 6): agent 0 through match_mlp_side; agent 1
 // through zoo_lstm_act on row 1 of the tile, its rows in the hidden tiles' place once agent 0's trunk is done (no extra LDS).
 template <class C, class SA, class RA>
 __device__ __forceinline__ void rollout_policy_phase_match_zoo_lstm(C& c, const SA& a, const RA& r, int e, int s) {
@@ -3057,7 +3071,7 @@ __device__ __forceinline__ void rollout_policy_phase_match_zoo_lstm(C& c, const 
   const unsigned dn = policy_prev_done(a, e);
   wave_sync();
   const bool ok = i < r.L.A && kq == 0;             // row 0 lives in the first 16 lanes (D layout: rows 4 kq + r)
-  const float act0 = match_mlp_side0(a, r, e, s, lane, i, ok, xbuf);
+  const float act0 = match_mlp_side(a, r, e, s, lane, 0, i, ok, xbuf);
   wave_sync();   // the hidden tiles become the cell's rows
   const float act1 = zoo_lstm_act(a, r, e, s, lane, dn, xbuf + r.XS, xbuf + r.zl.sc_off);
   if (ok) policy_commit_actions<false>(c, a, r, e, i, act0, act1);
@@ -3079,6 +3093,50 @@ __device__ __forceinline__ void rollout_policy_phase_match_lstm_zoo_lstm(C& c, c
   match_lstm_side<NH>(a, r, e, s, lane, 0, jn, dn, xo, hp, hp + NH, act0);
   const float act1 = zoo_lstm_act(a, r, e, s, lane, dn, xo + r.XS, xo + r.zl.sc_off);
   if (lane < r.lnet.ac_dim) policy_commit_actions<false>(c, a, r, e, lane, act0, act1);
+  wave_sync();
+}
+
+// Cross-family checkpoint matches (sumo_match_steps_cross, POLICY 13): agent lstm_side is one side of mode 3 (match_lstm_side: net
+// idx_g[e] of onets [nsnap_lstm] on its state row, masked by that agent's done flag of the previous step; st0 == st1 == the one state
+// buffer of the launch), the other agent one side of the MLP matches (match_mlp_side: checkpoint idx_g[e] of snaps [nsnap]).  The seat
+// is a launch field, read as a scalar: the side functions take it as a value (row of the tile, index / noise / state pointers are
+// scalar selects), so there is one body per kernel variant and no branch around the sides.  Each index is checked against its own
+// table.  LDS (floats, from lds_off): x [2][XS], zero-padded | previous latent [NH] | new latent [NH], then -- after the wave_sync
+// that ends match_lstm_side -- h1 [2][PT_HS] | h2 [2][PT_HS] of the MLP trunk in the same place.
+template <int NH, class C, class SA, class RA>
+__device__ __forceinline__ void rollout_policy_phase_match_cross(C& c, const SA& a, const RA& r, int e, int s) {
+  const int lane = c.lane, i = lane & 15, kq = lane >> 4;
+  float* xo = (float*)(c.sm + r.lds_off);
+  float* hp = xo + 2 * r.XS;
+  policy_load_obs<true, false>(a, r, e, lane, xo, r.lnet.ob_dim, r.XS);
+  const unsigned dn = policy_prev_done(a, e);
+  const int gl = r.lstm_side;
+  const int jn = policy_checked_row(a, lane, pt_global(gl ? r.idx1 : r.idx0)[e], r.nsnap_lstm);
+  float actl;
+  match_lstm_side<NH>(a, r, e, s, lane, gl, jn, dn, xo, hp, hp + NH, actl);
+  const bool ok = i < r.L.A && kq == 0;             // both sides leave their columns in the lanes < A
+  const float actm = match_mlp_side(a, r, e, s, lane, 1 - gl, i, ok, xo);
+  if (ok) policy_commit_actions<false>(c, a, r, e, i, gl ? actm : actl, gl ? actl : actm);
+  wave_sync();   // the action buffer is read back by the env step (other lanes), the scratch region is the step's again
+}
+
+// LSTM(128) checkpoints against policy-zoo MLP nets (sumo_match_steps_lstm_zoo, POLICY 14): agent 0 is side 0 of mode 3
+// (match_lstm_side: net idx0[e] of onets) on the raw tile; only then agent 1's zoo net filters the tile in place (zoo_mlp_act, agent
+// 1 of mode 5), its hidden tiles in the latent rows' place -- the order of mode 9.
+template <int NH, class C, class SA, class RA>
+__device__ __forceinline__ void rollout_policy_phase_match_lstm_zoo(C& c, const SA& a, const RA& r, int e, int s) {
+  const int lane = c.lane, i = lane & 15, kq = lane >> 4;
+  const int A = r.lnet.ac_dim;
+  float* xo = (float*)(c.sm + r.lds_off);
+  float* hp = xo + 2 * r.XS;
+  policy_load_obs<true, false>(a, r, e, lane, xo, r.lnet.ob_dim, r.XS);
+  const unsigned dn = policy_prev_done(a, e);
+  const int jn = policy_checked_row(a, lane, pt_global(r.idx0)[e], r.nsnap);
+  float act0;
+  match_lstm_side<NH>(a, r, e, s, lane, 0, jn, dn, xo, hp, hp + NH, act0);   // (its last wave_sync: the raw tile is filtered in place)
+  const bool ok = i < A && kq == 0;
+  const float act1 = zoo_mlp_act(a, r, e, s, lane, i, ok, xo, A);
+  if (ok) policy_commit_actions<false>(c, a, r, e, i, act0, act1);
   wave_sync();
 }
 
@@ -3326,20 +3384,22 @@ static_assert(sizeof(const Params*) + sizeof(RolloutLaunch) <= 4096, "the launch
 // launch's abort flag (counted in sumo_stats[9]) and every wave drains.
 #define ROLLOUT_SPIN_LIMIT (1u << 22)   /* polls of ~0.5 us each */
 
-// POLICY selects the policy phase (and with it the post phase: rollout record, or the score counters of the match modes 2, 3, 5-7):
+// POLICY selects the policy phase (and with it the post phase: rollout record, or the score counters of the match modes 2, 3, 5-7, 13, 14):
 //    0  sumo_rollout_steps                  MLP(64,64) self-play                      rollout_policy_phase
 //    1  sumo_rollout_steps_lstm             LSTM(128) self-play, shared value head    rollout_policy_phase_lstm
 //    2  sumo_match_steps                    MLP checkpoint matches                    rollout_policy_phase_match
 //    3  sumo_match_steps_lstm               LSTM(128) checkpoint matches              match_lstm_side for both agents
 //    4  sumo_rollout_steps_zoo              MLP learner  vs zoo MLP nets              mlp_learner_front  + zoo_mlp_pass
-//    5  sumo_match_steps_zoo                MLP checkpoints vs zoo MLP nets           match_mlp_side0    + the zoo trunk on row 1
-//    6  sumo_match_steps_zoo_lstm           MLP checkpoints vs zoo LSTM nets          match_mlp_side0    + zoo_lstm_act
+//    5  sumo_match_steps_zoo                MLP checkpoints vs zoo MLP nets           match_mlp_side(0)  + zoo_mlp_act
+//    6  sumo_match_steps_zoo_lstm           MLP checkpoints vs zoo LSTM nets          match_mlp_side(0)  + zoo_lstm_act
 //    7  sumo_match_steps_lstm_zoo_lstm      LSTM(128) checkpoints vs zoo LSTM nets    match_lstm_side(0) + zoo_lstm_act
 //    8  sumo_rollout_steps_zoo_lstm         MLP learner  vs zoo LSTM nets             mlp_learner_front  + zoo_lstm_pass
 //    9  sumo_rollout_steps_lstm_zoo         LSTM learner vs zoo MLP nets              lstm_learner_front + zoo_mlp_pass
 //   10  sumo_rollout_steps_lstm_zoo_lstm    LSTM learner vs zoo LSTM nets             lstm_learner_front + zoo_lstm_pass
 //   11  sumo_rollout_steps_zoo_league       MLP learner  vs a league of both families mlp_learner_front  + league_zoo_pass
 //   12  sumo_rollout_steps_lstm_zoo_league  LSTM learner vs a league of both families lstm_learner_front + league_zoo_pass
+//   13  sumo_match_steps_cross              MLP checkpoints vs LSTM(128) checkpoints  match_lstm_side(g) + match_mlp_side(1 - g)
+//   14  sumo_match_steps_lstm_zoo           LSTM(128) checkpoints vs zoo MLP nets     match_lstm_side(0) + zoo_mlp_act
 // (4, 8 .. 12 are rollout_policy_phase_vs_zoo<LSTM_LEARNER, ZOO_KIND>.)  The integers are part of the kernels' mangled names, which
 // profiles/ and tools/ refer to.  SL 1 / 2: static Layout.
 template <int NV, int POLICY, int SL = 0>
@@ -3407,6 +3467,8 @@ sumo_rollout_kernel(const Params* P, RolloutLaunch launch_args) {
     else if constexpr (POLICY == 10) rollout_policy_phase_vs_zoo<true, ZOO_LSTM>(c, lp->a, lp->r, e, s);
     else if constexpr (POLICY == 11) rollout_policy_phase_vs_zoo<false, ZOO_LEAGUE>(c, lp->a, lp->r, e, s);
     else if constexpr (POLICY == 12) rollout_policy_phase_vs_zoo<true, ZOO_LEAGUE>(c, lp->a, lp->r, e, s);
+    else if constexpr (POLICY == 13) rollout_policy_phase_match_cross<128>(c, lp->a, lp->r, e, s);
+    else if constexpr (POLICY == 14) rollout_policy_phase_match_lstm_zoo<128>(c, lp->a, lp->r, e, s);
     else rollout_policy_phase(c, lp->a, lp->r, e, s);
 #ifdef SUMO_DBG_HARD_BARRIER
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -3419,7 +3481,7 @@ sumo_rollout_kernel(const Params* P, RolloutLaunch launch_args) {
     asm volatile("" : "+s"(e), "+s"(k));
     lp = launder_sptr(LP);
     s = lp->r.s0 + k;
-    if constexpr (POLICY == 2 || POLICY == 3 || (POLICY >= 5 && POLICY <= 7)) rollout_post_phase_match(c, lp->a, lp->r, e);
+    if constexpr (POLICY == 2 || POLICY == 3 || (POLICY >= 5 && POLICY <= 7) || POLICY == 13 || POLICY == 14) rollout_post_phase_match(c, lp->a, lp->r, e);
     else rollout_post_phase(c, lp->a, lp->r, e, s);
     prof = lp->r.prof;
     if (prof && c.lane == 0) {
@@ -4273,7 +4335,7 @@ static int rollout_launch(sumo_engine* E, const RolloutArgs& r, int policy, cons
   size_t lds_ = (size_t)E->L.total_bytes;
   if (!for_engine_variant(E, [&](auto nvc_, auto slc_) {
         constexpr int NV = decltype(nvc_)::value, SL = decltype(slc_)::value;
-        const RolloutKernel kernel = rollout_kernel<NV, SL>(policy, std::make_integer_sequence<int, 13>{});
+        const RolloutKernel kernel = rollout_kernel<NV, SL>(policy, std::make_integer_sequence<int, 15>{});
         hipLaunchKernelGGL(kernel, g_, b_, lds_, st_, E->d_params, rl);
       }))
     FAIL(-19, "no kernel variant for nv=%d", E->hm.nv);
@@ -4425,8 +4487,8 @@ static int begin_mlp_match(sumo_engine* E, const sumo_match* mo, int* od, int* a
   return 0;
 }
 
-// LSTM(128) checkpoints (modes 3, 7), with the scratch: x [2][XS] | previous latent | new latent
-static int begin_lstm_match(sumo_engine* E, const sumo_match_lstm* mo, const char* zoo, int* od, int* ad, RolloutArgs& r) {
+// LSTM(128) checkpoints (modes 3, 7, 13, 14), with the scratch: x [2][XS] | `rows` rows of 128 floats (previous latent | new latent)
+static int begin_lstm_match(sumo_engine* E, const sumo_match_lstm* mo, const char* zoo, int* od, int* ad, RolloutArgs& r, int rows = 2) {
   if (!mo->proto || !mo->nets_dev) FAIL(-2, "sumo_match_lstm: missing buffer");
   if (!mo->state0 || (!zoo && !mo->state1)) FAIL(-2, "sumo_match_lstm: missing state buffer (%s)", zoo ? "state0" : "state0 / state1");
   if (zoo && mo->state1) FAIL(-2, "%s: state1 must be NULL (agent 1's state is the zoo table's state)", zoo);
@@ -4440,8 +4502,11 @@ static int begin_lstm_match(sumo_engine* E, const sumo_match_lstm* mo, const cha
   HIPCHK(hipSetDevice(E->device));
   r.lnet = n; r.onets = mo->nets_dev; r.st0 = mo->state0; r.st1 = mo->state1;
   copy_match_fields(r, mo, E->N);
-  return place_lstm_scratch(E, *od, 2, r);
+  return place_lstm_scratch(E, *od, rows, r);
 }
+// the rows of modes 13 / 14: the recurrent side's two latent rows, then the two hidden tiles of the MLP / zoo trunk in their place
+constexpr int LSTM_MLP_MATCH_ROWS = 3;
+static_assert(4 * PT_HS <= LSTM_MLP_MATCH_ROWS * 128 && 2 * 128 <= LSTM_MLP_MATCH_ROWS * 128, "modes 13 / 14: the larger of the latent rows and the hidden tiles [2][PT_HS] twice");
 
 // ---- the zoo tables: checks, then RolloutArgs::zm / zl ----
 static int place_zoo_mlp_table(RolloutArgs& r, const sumo_zoo_mlp* z, int od, int ad) {
@@ -4493,7 +4558,7 @@ static int place_zoo_league(RolloutArgs& r, const sumo_zoo_league* z, int od, in
   return 0;
 }
 
-// ---- the thirteen entry points: env buffers, the family's checks (and the mode's), begin_*, the scratch of the learner's /
+// ---- the fifteen entry points: env buffers, the family's checks (and the mode's), begin_*, the scratch of the learner's /
 // checkpoints' side, the opponent table, launch.  Where a zoo MLP table comes before the scratch and a zoo LSTM table after it, that
 // is the order in which the mode reports their errors. ----
 extern "C" int sumo_rollout_steps(sumo_handle_t E, const sumo_rollout* ro, float* actions_dev, float* obs_dev, double* info_dev,
@@ -4666,6 +4731,37 @@ extern "C" int sumo_rollout_steps_lstm_zoo_league(sumo_handle_t E, const sumo_ro
   if (int rc = begin_lstm_rollout(E, ro, od, LSTM_ZOO_ROWS, r)) return rc;   // the rows hold the larger of the two zoo passes (static_assert above)
   if (int rc = place_zoo_league(r, z, od, ad, LSTM_ZOO_ROWS * 128)) return rc;
   return rollout_launch(E, r, 12, b, stream);
+}
+
+extern "C" int sumo_match_steps_cross(sumo_handle_t E, const sumo_match_cross* mo, float* actions_dev, float* obs_dev, double* info_dev,
+                                      uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
+  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
+  RolloutArgs r = {};
+  int od = 0, ad = 0;
+  if (int rc = check_launch_args(E, mo, b)) return rc;
+  if (mo->lstm_side != 0 && mo->lstm_side != 1) FAIL(-9, "lstm_side %d: 0 (agent 0 plays the LSTM checkpoints) or 1", mo->lstm_side);
+  // each family's half of the struct goes through that family's checks: the one state buffer stands for both of sumo_match_lstm's
+  const sumo_match_lstm ml = {mo->proto, mo->nets_dev, mo->idx0, mo->idx1, mo->nsnap_lstm, mo->state, mo->state,
+                              mo->T, mo->s0, mo->K, mo->quota, mo->noise0, mo->noise1, mo->score};
+  const sumo_match mm = {mo->params, mo->idx0, mo->idx1, mo->nsnap_mlp, mo->ob_dim, mo->ac_dim,
+                         mo->T, mo->s0, mo->K, mo->quota, mo->noise0, mo->noise1, mo->score};
+  if (int rc = begin_lstm_match(E, &ml, NULL, &od, &ad, r, LSTM_MLP_MATCH_ROWS)) return rc;
+  r.nsnap_lstm = r.nsnap; r.lstm_side = mo->lstm_side;
+  if (int rc = begin_mlp_match(E, &mm, &od, &ad, r)) return rc;   // (leaves nsnap at the MLP table's size)
+  r.L = make_layout(mo->ob_dim, mo->ac_dim);
+  return rollout_launch(E, r, 13, b, stream);
+}
+
+extern "C" int sumo_match_steps_lstm_zoo(sumo_handle_t E, const sumo_match_lstm* mo, const sumo_zoo_mlp* z, float* actions_dev, float* obs_dev,
+                                         double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
+  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
+  RolloutArgs r = {};
+  int od = 0, ad = 0;
+  if (int rc = check_launch_args(E, mo, b)) return rc;
+  if (!z) FAIL(-1, "bad arguments");
+  if (int rc = begin_lstm_match(E, mo, "sumo_match_steps_lstm_zoo", &od, &ad, r, LSTM_MLP_MATCH_ROWS)) return rc;
+  if (int rc = place_zoo_mlp_table(r, z, od, ad)) return rc;
+  return rollout_launch(E, r, 14, b, stream);
 }
 
 #ifdef SUMO_POLICY_PROBE

@@ -18,12 +18,16 @@ Recurrent checkpoints (``LstmPPOModel.save``, ``learn(network='lstm')``) go into
 same drivers detect the kind from the checkpoint files (:func:`checkpoint_kind`), and each side carries its own recurrent state
 per env, zeroed where a batch starts and masked by that side's done flag of the previous step (``LstmPPOModel.step(obs, S, M)``).
 The fused path is ``sumo_match_steps_lstm`` (LSTM(128)); ``fused=False`` makes one ``ppo_lstm_step`` launch per side and run of
-envs sharing a snapshot, bit-identical again.  MLP-vs-LSTM match-ups are refused.
+envs sharing a snapshot, bit-identical again.
+
+An MLP(64,64) run against an LSTM run plays through :func:`play_cross_matches` (one table per agent, either seating;
+``sumo_match_steps_cross`` for LSTM(128), any width step by step); the version drivers take it with ``cross_family=True`` and
+refuse it otherwise.
 
 Policy-zoo opponents sit in a :class:`policy_zoo.ZooTable` (MLP nets) or a :class:`policy_zoo.ZooLstmTable` (LSTM nets) and play
 agent 1 (:func:`play_against_zoo`, :func:`evaluate_history_against_zoo`): MLP checkpoints face either family, LSTM(128)
 checkpoints face zoo LSTM nets (``sumo_match_steps_zoo`` / ``sumo_match_steps_zoo_lstm`` / ``sumo_match_steps_lstm_zoo_lstm``);
-LSTM checkpoints against zoo MLP nets are refused.
+LSTM checkpoints against zoo MLP nets play with ``cross_family=True`` (``sumo_match_steps_lstm_zoo``) and are refused otherwise.
 """
 import ctypes as C
 import os
@@ -343,12 +347,11 @@ def _stepwise(env, table, idx0, idx1, score, quota, K, noise, forward, masked, c
         _score_step(score, info, done, quota)
 
 
-def match_steps_stepwise(env, table, idx0, idx1, score, quota, K, noise=None):
-    """The same K steps on the step-by-step path: per step and side one ``ppo_forward`` launch (``PPOModel.step``'s kernel) for
-    every run of envs that share a snapshot, then ``step_device`` and the score update.  idx0 / idx1 are host arrays."""
+def _mlp_side(env, table):
+    """``forward`` of :func:`_stepwise` for a side played by a :class:`SnapshotTable`: one ``ppo_forward`` launch
+    (``PPOModel.step``'s kernel) on the rows' observations of that side."""
     import torch
     from . import ppo_capi
-    _check_env(env, table)
     D, A = table.spec.ob_dim, table.spec.ac_dim
     L, st, obs = ppo_capi.lib(), env._stream(), env.obs_dev
     nlp = torch.empty(env.num_envs, dtype=torch.float32, device=env.device)
@@ -356,8 +359,51 @@ def match_steps_stepwise(env, table, idx0, idx1, score, quota, K, noise=None):
     def forward(k, side, rows, nz, out, _mask):
         ppo_capi.chk(L.ppo_forward(table.params[k].data_ptr(), obs[rows, side].data_ptr(), rows.stop - rows.start, obs.stride(0), D, A,
                                    ppo_capi.FWD_PI, ppo_capi.ptr(nz), None, out.data_ptr(), nlp[rows].data_ptr(), None, None, st))
+    return forward
 
-    _stepwise(env, table, idx0, idx1, score, quota, K, noise, forward, masked=False)
+
+def _lstm_side(env, table, state_of):
+    """The same for a side played by an :class:`LstmSnapshotTable`: one ``ppo_lstm_step`` launch (the kernel
+    ``LstmPPOModel.step`` runs) on the rows of ``state_of(side)``, masked by that side's done flags of the previous step."""
+    from . import ppo_capi
+    H = table.spec.nlstm
+    L, st, obs = ppo_capi.lib(), env._stream(), env.obs_dev
+
+    def forward(k, side, rows, nz, out, mask):
+        S = state_of(side)[rows]
+        ppo_capi.chk(L.ppo_lstm_step(C.byref(table.nets[k]), obs[rows, side].data_ptr(), rows.stop - rows.start, obs.stride(0),
+                                     mask.data_ptr(), S.data_ptr(), S.data_ptr() + 4 * H, 2 * H, ppo_capi.ptr(nz), None,
+                                     out.data_ptr(), None, None, None, st))
+    return forward
+
+
+def _zoo_mlp_side(env, zoo_table, A):
+    """The same for a side played by a :class:`policy_zoo.ZooTable`: one ``ppo_forward_filtered`` launch (what
+    ``ZooMLPPolicy.act`` runs)."""
+    import torch
+    from . import ppo_capi
+    Dz = zoo_table.ob_dim
+    L, st, obs = ppo_capi.lib(), env._stream(), env.obs_dev
+    nlp = torch.empty(env.num_envs, dtype=torch.float32, device=env.device)
+
+    def forward(k, side, rows, nz, out, _mask):
+        f = zoo_table.filt[k]
+        ppo_capi.chk(L.ppo_forward_filtered(zoo_table.params[k].data_ptr(), obs[rows, side].data_ptr(), rows.stop - rows.start,
+                                            obs.stride(0), Dz, A, ppo_capi.FWD_PI | ppo_capi.FWD_TANH, f[0].data_ptr(), f[1].data_ptr(),
+                                            zoo_table.obs_clip, ppo_capi.ptr(nz), None, out.data_ptr(), nlp[rows].data_ptr(), None, None, st))
+    return forward
+
+
+def _by_side(forward0, forward1):
+    """``forward`` of :func:`_stepwise` from one function per side."""
+    return lambda k, side, *rest: (forward1 if side else forward0)(k, side, *rest)
+
+
+def match_steps_stepwise(env, table, idx0, idx1, score, quota, K, noise=None):
+    """The same K steps on the step-by-step path: per step and side one ``ppo_forward`` launch (``PPOModel.step``'s kernel) for
+    every run of envs that share a snapshot, then ``step_device`` and the score update.  idx0 / idx1 are host arrays."""
+    _check_env(env, table)
+    _stepwise(env, table, idx0, idx1, score, quota, K, noise, _mlp_side(env, table), masked=False)
 
 
 def _check_lstm(table, states, N):
@@ -389,19 +435,9 @@ def match_steps_stepwise_lstm(env, table, idx0, idx1, states, score, quota, K, n
     """The same K steps of an :class:`LstmSnapshotTable` step by step: per step and side one ``ppo_lstm_step`` launch (the kernel
     ``LstmPPOModel.step`` runs) for every run of envs that share a snapshot, masked by that side's done flags of the previous step,
     then ``step_device`` and the score update.  idx0 / idx1 are host arrays; any LSTM width the step kernel is built for."""
-    from . import ppo_capi
     _check_env(env, table)
     _check_lstm(table, states, env.num_envs)
-    H = table.spec.nlstm
-    L, st, obs = ppo_capi.lib(), env._stream(), env.obs_dev
-
-    def forward(k, side, rows, nz, out, mask):
-        S = states[side][rows]
-        ppo_capi.chk(L.ppo_lstm_step(C.byref(table.nets[k]), obs[rows, side].data_ptr(), rows.stop - rows.start, obs.stride(0),
-                                     mask.data_ptr(), S.data_ptr(), S.data_ptr() + 4 * H, 2 * H, ppo_capi.ptr(nz), None,
-                                     out.data_ptr(), None, None, None, st))
-
-    _stepwise(env, table, idx0, idx1, score, quota, K, noise, forward, masked=True)
+    _stepwise(env, table, idx0, idx1, score, quota, K, noise, _lstm_side(env, table, lambda side: states[side]), masked=True)
 
 
 def _check_zoo(env, table, zoo_table):
@@ -409,6 +445,10 @@ def _check_zoo(env, table, zoo_table):
     if getattr(table, "recurrent", False) and not getattr(zoo_table, "recurrent", False):
         raise ValueError("LSTM checkpoints do not play against zoo MLP nets in the fused launch (MLP(64,64) checkpoints only; LSTM "
                          "checkpoints play against zoo LSTM nets, a ZooLstmTable)")
+    _check_zoo_dims(table, zoo_table)
+
+
+def _check_zoo_dims(table, zoo_table):
     if zoo_table.ac_dim != table.spec.ac_dim or not 1 <= zoo_table.ob_dim <= table.spec.ob_dim:
         raise ValueError("zoo table (ob_dim %d, ac_dim %d) does not fit the env (%d, %d): a zoo MLP net reads the first ob_dim "
                          "observation columns" % (zoo_table.ob_dim, zoo_table.ac_dim, table.spec.ob_dim, table.spec.ac_dim))
@@ -432,24 +472,8 @@ def zoo_match_steps_stepwise(env, table, zoo_table, idx0, idx1, score, quota, K,
     """The same K steps step by step: per step one ``ppo_forward`` launch for every run of envs that share a checkpoint, one
     ``ppo_forward_filtered`` launch (what ``ZooMLPPolicy.act`` runs) for every run that shares a zoo net, then ``step_device`` and
     the score update.  idx0 / idx1 are host arrays."""
-    import torch
-    from . import ppo_capi
     _check_zoo(env, table, zoo_table)
-    D, A, Dz = table.spec.ob_dim, table.spec.ac_dim, zoo_table.ob_dim
-    L, st, obs = ppo_capi.lib(), env._stream(), env.obs_dev
-    nlp = torch.empty(env.num_envs, dtype=torch.float32, device=env.device)
-
-    def forward(k, side, rows, nz, out, _mask):
-        n, ob = rows.stop - rows.start, obs[rows, side].data_ptr()
-        if side == 0:
-            ppo_capi.chk(L.ppo_forward(table.params[k].data_ptr(), ob, n, obs.stride(0), D, A, ppo_capi.FWD_PI, ppo_capi.ptr(nz), None,
-                                       out.data_ptr(), nlp[rows].data_ptr(), None, None, st))
-        else:
-            f = zoo_table.filt[k]
-            ppo_capi.chk(L.ppo_forward_filtered(zoo_table.params[k].data_ptr(), ob, n, obs.stride(0), Dz, A,
-                                                ppo_capi.FWD_PI | ppo_capi.FWD_TANH, f[0].data_ptr(), f[1].data_ptr(), zoo_table.obs_clip,
-                                                ppo_capi.ptr(nz), None, out.data_ptr(), nlp[rows].data_ptr(), None, None, st))
-
+    forward = _by_side(_mlp_side(env, table), _zoo_mlp_side(env, zoo_table, table.spec.ac_dim))
     _stepwise(env, table, idx0, idx1, score, quota, K, noise, forward, masked=False, capacity1=zoo_table.capacity)
 
 
@@ -527,6 +551,82 @@ def zoo_lstm_match_steps_stepwise(env, table, zoo_table, idx0, idx1, states, sco
     _stepwise(env, table, idx0, idx1, score, quota, K, noise, forward, masked=True, capacity1=zoo_table.capacity)
 
 
+def _check_cross(env, mlp_table, lstm_table, lstm_side, state):
+    if getattr(mlp_table, "recurrent", False) or not getattr(lstm_table, "recurrent", False):
+        raise ValueError("cross-family matches take a SnapshotTable (MLP(64,64)) and an LstmSnapshotTable, in this order")
+    if lstm_side not in (0, 1):
+        raise ValueError("lstm_side %r: 0 (agent 0 plays the LSTM table) or 1" % (lstm_side,))
+    _check_env(env, mlp_table)
+    _check_env(env, lstm_table)
+    _check_lstm(lstm_table, (state,), env.num_envs)
+
+
+def cross_match_steps_fused(env, mlp_table, lstm_table, lstm_side, idx0, idx1, state, score, quota, K, noise=None):
+    """K match steps of MLP(64,64) checkpoints against LSTM(128) checkpoints in one ``sumo_match_steps_cross`` launch per env
+    group: agent ``lstm_side`` plays row idx_g[e] of ``lstm_table`` on ``state`` (float32 CUDA [N][256], c | h, read and updated
+    in place), the other agent row idx_g[e] of ``mlp_table``.  The other arguments as :func:`match_steps_fused`."""
+    from . import capi
+    _check_cross(env, mlp_table, lstm_table, lstm_side, state)
+    if lstm_table.spec.nlstm != 128:
+        raise ValueError("the fused match launch plays LSTM(128) policies only (got LSTM(%d)): use fused=False" % lstm_table.spec.nlstm)
+
+    def fill(mo, sl):
+        mo.params = mlp_table.params.data_ptr()
+        mo.nsnap_mlp, mo.ob_dim, mo.ac_dim = mlp_table.capacity, mlp_table.spec.ob_dim, mlp_table.spec.ac_dim
+        mo.proto = C.addressof(lstm_table.proto)
+        mo.nets_dev = lstm_table.nets_dev.data_ptr()
+        mo.nsnap_lstm = lstm_table.capacity
+        mo.state = state[sl].data_ptr()
+        mo.lstm_side = int(lstm_side)
+
+    _fused_groups(env, "match_steps_cross", capi.MatchCross, fill, idx0, idx1, score, quota, K, noise)
+
+
+def cross_match_steps_stepwise(env, mlp_table, lstm_table, lstm_side, idx0, idx1, state, score, quota, K, noise=None):
+    """The same K steps step by step: the launches of :func:`match_steps_stepwise` for the MLP side and of
+    :func:`match_steps_stepwise_lstm` for agent ``lstm_side`` (any LSTM width the step kernel is built for).  idx0 / idx1 are
+    host arrays."""
+    _check_cross(env, mlp_table, lstm_table, lstm_side, state)
+    seats = [(mlp_table, _mlp_side(env, mlp_table)), (lstm_table, _lstm_side(env, lstm_table, lambda side: state))]
+    (table0, forward0), (table1, forward1) = seats[::-1] if lstm_side == 0 else seats
+    _stepwise(env, table0, idx0, idx1, score, quota, K, noise, _by_side(forward0, forward1), masked=True, capacity1=table1.capacity)
+
+
+def _check_lstm_zoo(env, lstm_table, zoo_table, state0):
+    if not getattr(lstm_table, "recurrent", False) or getattr(zoo_table, "recurrent", False):
+        raise ValueError("lstm_zoo_match_steps_* take an LstmSnapshotTable and a policy_zoo.ZooTable (zoo MLP nets)")
+    _check_env(env, lstm_table)
+    _check_zoo_dims(lstm_table, zoo_table)
+    _check_lstm(lstm_table, (state0,), env.num_envs)
+
+
+def lstm_zoo_match_steps_fused(env, lstm_table, zoo_table, idx0, idx1, state0, score, quota, K, noise=None):
+    """K match steps of LSTM(128) checkpoints (agent 0: row idx0[e] of ``lstm_table`` on ``state0``, float32 CUDA [N][256], read
+    and updated in place) against policy-zoo MLP nets (agent 1: row idx1[e] of ``zoo_table``) in one
+    ``sumo_match_steps_lstm_zoo`` launch per env group; the other arguments as :func:`match_steps_fused`."""
+    from . import capi
+    _check_lstm_zoo(env, lstm_table, zoo_table, state0)
+    if lstm_table.spec.nlstm != 128:
+        raise ValueError("the fused match launch plays LSTM(128) policies only (got LSTM(%d)): use fused=False" % lstm_table.spec.nlstm)
+
+    def fill(mo, sl):
+        mo.proto = C.addressof(lstm_table.proto)
+        mo.nets_dev = lstm_table.nets_dev.data_ptr()
+        mo.nsnap = lstm_table.capacity
+        mo.state0 = state0[sl].data_ptr()
+
+    _fused_groups(env, "match_steps_lstm_zoo", capi.MatchLstm, fill, idx0, idx1, score, quota, K, noise, extra=(zoo_table.struct(),))
+
+
+def lstm_zoo_match_steps_stepwise(env, lstm_table, zoo_table, idx0, idx1, state0, score, quota, K, noise=None):
+    """The same K steps step by step: per step one ``ppo_lstm_step`` launch masked by agent 0's done flags for every run of envs
+    that share a checkpoint, one ``ppo_forward_filtered`` launch for every run that shares a zoo net, then ``step_device`` and the
+    score update.  idx0 / idx1 are host arrays."""
+    _check_lstm_zoo(env, lstm_table, zoo_table, state0)
+    forward = _by_side(_lstm_side(env, lstm_table, lambda side: state0), _zoo_mlp_side(env, zoo_table, lstm_table.spec.ac_dim))
+    _stepwise(env, lstm_table, idx0, idx1, score, quota, K, noise, forward, masked=True, capacity1=zoo_table.capacity)
+
+
 def match_steps(env, table, idx0, idx1, states, score, quota, K, noise=None, fused=True):
     """K match steps of either table kind on either path: ``states`` is the pair of recurrent state tensors of an
     :class:`LstmSnapshotTable` (ignored for MLP tables); idx0 / idx1 are CUDA tensors (fused) or host arrays (step by step)."""
@@ -576,6 +676,42 @@ def play_matches(env, table, pairs, rounds_per_env, envs_per_pair, deterministic
                                                                  fused=fused)
     return _play_batches(env, table.spec.ac_dim, pairs, rounds_per_env, envs_per_pair, deterministic, seed, adjust_z, chunk, fused,
                          new_states, steps)
+
+
+def play_cross_matches(env, table0, table1, pairs, rounds_per_env, envs_per_pair, deterministic=False, seed=0, adjust_z=EVAL_ADJUST_Z,
+                       chunk=64, fused=True):
+    """:func:`play_matches` across the families: ``pairs[p] = (i, j)`` is row i of ``table0`` as agent 0 against row j of
+    ``table1`` as agent 1, where exactly one of the two tables is an :class:`LstmSnapshotTable` and the other a
+    :class:`SnapshotTable` (either seating).  The recurrent agent's state is zeroed per batch.  Same batching, seeding, quota
+    and return value as :func:`play_matches`; ``fused=False`` plays the same games step by step (any LSTM width)."""
+    rec = [bool(getattr(t, "recurrent", False)) for t in (table0, table1)]
+    if rec[0] == rec[1]:
+        raise ValueError("play_cross_matches takes one SnapshotTable (MLP(64,64)) and one LstmSnapshotTable; two tables of one "
+                         "family play through play_matches")
+    lstm_side = 0 if rec[0] else 1
+    lstm_table, mlp_table = (table0, table1) if rec[0] else (table1, table0)
+    _check_env(env, table0)
+    _check_env(env, table1)
+    pairs = [(int(i), int(j)) for i, j in pairs]
+    for i, j in pairs:
+        if not (0 <= i < table0.capacity and 0 <= j < table1.capacity) or not (table0.filled[i] and table1.filled[j]):
+            raise ValueError("pair (%d, %d) refers to an empty or non-existent snapshot row" % (i, j))
+    rounds_per_env, envs_per_pair, chunk = int(rounds_per_env), int(envs_per_pair), int(chunk)
+    if rounds_per_env < 1 or chunk < 1:
+        raise ValueError("rounds_per_env and chunk must be >= 1")
+    if fused and lstm_table.spec.nlstm != 128:
+        raise ValueError("the fused match launch plays LSTM(128) policies only (got LSTM(%d)): use fused=False" % lstm_table.spec.nlstm)
+
+    def new_state():
+        import torch
+        return torch.zeros((env.num_envs, 2 * lstm_table.spec.nlstm), dtype=torch.float32, device=env.device)
+
+    def steps(idx0, idx1, state, score, noise):
+        fn = cross_match_steps_fused if fused else cross_match_steps_stepwise
+        fn(env, mlp_table, lstm_table, lstm_side, idx0, idx1, state, score, rounds_per_env, chunk, noise)
+
+    return _play_batches(env, mlp_table.spec.ac_dim, pairs, rounds_per_env, envs_per_pair, deterministic, seed, adjust_z, chunk, fused,
+                         new_state, steps)
 
 
 def _play_batches(env, A, pairs, rounds_per_env, envs_per_pair, deterministic, seed, adjust_z, chunk, fused, new_states, steps):
@@ -628,14 +764,20 @@ def _play_batches(env, A, pairs, rounds_per_env, envs_per_pair, deterministic, s
 
 
 def play_against_zoo(env, table, zoo_table, pairs, rounds_per_env, envs_per_pair, deterministic=True, seed=0, adjust_z=EVAL_ADJUST_Z,
-                     chunk=64, fused=True):
+                     chunk=64, fused=True, cross_family=False):
     """:func:`play_matches` with agent 1 played by policy-zoo nets: ``pairs[p] = (i, j)`` is checkpoint row i of ``table`` (a
     :class:`SnapshotTable`, or an :class:`LstmSnapshotTable` against zoo LSTM nets) as agent 0 against net j of ``zoo_table`` (a
     :class:`policy_zoo.ZooTable` or :class:`policy_zoo.ZooLstmTable`) as agent 1 -- the games of the reference's
     eval_robosumo_against_fix.py:196-230 (deterministic by default, as there).  Recurrent states (the zoo LSTM nets', the LSTM
     checkpoints') are allocated and zeroed per batch.  Same batching, seeding, quota and return value as :func:`play_matches`;
-    ``fused=False`` plays the same games step by step (bit-identical envs and scores)."""
-    _check_zoo(env, table, zoo_table)
+    ``fused=False`` plays the same games step by step (bit-identical envs and scores).  ``cross_family=True`` also plays an
+    :class:`LstmSnapshotTable` against a :class:`policy_zoo.ZooTable` (``sumo_match_steps_lstm_zoo``); the default refuses it."""
+    lstm_vs_mlp = bool(cross_family) and getattr(table, "recurrent", False) and not getattr(zoo_table, "recurrent", False)
+    if lstm_vs_mlp:
+        _check_env(env, table)
+        _check_zoo_dims(table, zoo_table)
+    else:
+        _check_zoo(env, table, zoo_table)
     pairs = [(int(i), int(j)) for i, j in pairs]
     for i, j in pairs:
         if not (0 <= i < table.capacity and table.filled[i]) or not 0 <= j < zoo_table.capacity:
@@ -644,7 +786,14 @@ def play_against_zoo(env, table, zoo_table, pairs, rounds_per_env, envs_per_pair
     if rounds_per_env < 1 or chunk < 1:
         raise ValueError("rounds_per_env and chunk must be >= 1")
     new_states = None
-    if getattr(zoo_table, "recurrent", False):
+    if lstm_vs_mlp:
+        import torch
+        if fused and table.spec.nlstm != 128:
+            raise ValueError("the fused match launch plays LSTM(128) policies only (got LSTM(%d)): use fused=False" % table.spec.nlstm)
+        new_states = lambda: torch.zeros((env.num_envs, 2 * table.spec.nlstm), dtype=torch.float32, device=env.device)
+        fn = lstm_zoo_match_steps_fused if fused else lstm_zoo_match_steps_stepwise
+        steps = lambda idx0, idx1, state0, score, noise: fn(env, table, zoo_table, idx0, idx1, state0, score, rounds_per_env, chunk, noise)
+    elif getattr(zoo_table, "recurrent", False):
         import torch
         rec0 = bool(getattr(table, "recurrent", False))
         if rec0 and fused and table.spec.nlstm != 128:
@@ -689,30 +838,43 @@ def _network(kind):
 
 
 def compare_history_versions(path1, path2, trials, num_env=256, deterministic=False, seed=0, adjust_z=EVAL_ADJUST_Z,
-                             env_id="RoboSumo-Ant-vs-Ant-v0", chunk=64, env=None, fused=True):
+                             env_id="RoboSumo-Ant-vs-Ant-v0", chunk=64, env=None, fused=True, cross_family=False):
     """compare_history_version.py on the GPU: version i of run ``path1`` (agent 0) against version i of ``path2`` (agent 1),
-    ``trials`` games each.  MLP and LSTM runs are told apart by their first checkpoint; both runs must hold the same kind.
+    ``trials`` games each.  MLP and LSTM runs are told apart by their first checkpoint; both runs must hold the same kind, unless
+    ``cross_family`` is set: then an MLP(64,64) run and an LSTM run play each other in the seating given
+    (:func:`play_cross_matches`; mixed LSTM widths stay refused).
     Returns dict(versions=[(id1, id2)], win_rate=[P1 wins / trials], results=[play_matches dicts], network='mlp' | 'lstm',
-    nlstm=LSTM width or None)."""
+    nlstm=LSTM width or None); a cross-family comparison returns network='cross', nlstm of the recurrent run and
+    networks=[dict(network, nlstm) of P1, of P2]."""
     pv = pair_versions(list_checkpoints(path1), list_checkpoints(path2))
     if not pv:
         raise ValueError("no checkpoints to compare")
     paths = [os.path.join(checkpoint_dir(path1), a) for a, _ in pv] + [os.path.join(checkpoint_dir(path2), b) for _, b in pv]
     k1, k2 = checkpoint_kind(paths[0]), checkpoint_kind(paths[len(pv)])
-    if k1 != k2:
+    cross = bool(cross_family) and {k1[0], k2[0]} == {"mlp", "lstm"}
+    if k1 != k2 and not cross:
         raise ValueError("P1 holds %s checkpoints and P2 %s checkpoints: both runs must use the same network (MLP-vs-LSTM and "
                          "mixed LSTM widths are not supported)" % (_kind_name(k1), _kind_name(k2)))
+    nlstm = k1[1] if k1[0] == "lstm" else k2[1]
+    if cross and fused and nlstm != 128:
+        raise ValueError("the fused match launch plays LSTM(128) policies only (got LSTM(%d)): use fused=False" % nlstm)
     env, own = _make_env(env_id, num_env, seed, env)
     try:
-        table = _table_of(k1, env, paths)
         n = len(pv)
         epp, rpe = split_trials(trials, env.num_envs)
-        res = play_matches(env, table, [(k, n + k) for k in range(n)], rpe, epp, deterministic=deterministic, seed=seed,
-                           adjust_z=adjust_z, chunk=chunk, fused=fused)
+        kw = dict(deterministic=deterministic, seed=seed, adjust_z=adjust_z, chunk=chunk, fused=fused)
+        if cross:
+            res = play_cross_matches(env, _table_of(k1, env, paths[:n]), _table_of(k2, env, paths[n:]), [(k, k) for k in range(n)],
+                                     rpe, epp, **kw)
+        else:
+            res = play_matches(env, _table_of(k1, env, paths), [(k, n + k) for k in range(n)], rpe, epp, **kw)
     finally:
         if own:
             env.close()
-    return dict(versions=pv, win_rate=[r["wins"] / float(trials) for r in res], results=res, **_network(k1))
+    out = dict(versions=pv, win_rate=[r["wins"] / float(trials) for r in res], results=res)
+    if cross:
+        return dict(out, network="cross", nlstm=nlstm, networks=[_network(k1), _network(k2)])
+    return dict(out, **_network(k1))
 
 
 def round_robin(path, interval, trials, num_env=256, deterministic=False, seed=0, adjust_z=EVAL_ADJUST_Z,
@@ -801,15 +963,17 @@ def merge_zoo_results(ids, groups, group_results):
 
 
 def evaluate_history_against_zoo(path, opponent_paths, trials, start=0, interval=1, num_env=256, deterministic=True, fused=True, seed=0,
-                                 adjust_z=EVAL_ADJUST_Z, env_id="RoboSumo-Ant-vs-Ant-v0", chunk=64, env=None):
+                                 adjust_z=EVAL_ADJUST_Z, env_id="RoboSumo-Ant-vs-Ant-v0", chunk=64, env=None, cross_family=False):
     """eval_robosumo_against_fix.py on the fused launch: every selected checkpoint of run ``path`` (:func:`select_checkpoints` of
     all of its saved versions) as agent 0 against every policy-zoo file of ``opponent_paths`` as agent 1, exactly ``trials``
     games per (checkpoint, opponent), all match-ups batched over the envs (:func:`plan_zoo_evaluation`) instead of one checkpoint
     after the other.  Each opponent file's family (MLP / LSTM) is read from its length; the MLP files and the LSTM files play in
     launches of their own (:func:`plan_mixed_zoo_evaluation`) and the results come back in the caller's opponent order.  The run's
-    checkpoint kind is read with :func:`checkpoint_kind`: MLP(64,64) runs face both families, LSTM runs zoo LSTM files only.
+    checkpoint kind is read with :func:`checkpoint_kind`: MLP(64,64) runs face both families, LSTM runs zoo LSTM files only
+    unless ``cross_family`` is set (then their MLP files play too, :func:`play_against_zoo`).
     Returns dict(checkpoints=[ids], opponents=[paths], results={(id, k): dict(win, draw, lose, rounds, env_steps)}) with rates
-    over ``rounds == trials`` games against opponent k."""
+    over ``rounds == trials`` games against opponent k, plus the families that met: network / nlstm of the run and
+    opponent_networks=['mlp' | 'lstm' per opponent]."""
     from .policy_zoo import ZooLstmTable, ZooTable, zoo_file_kind
     if isinstance(opponent_paths, (str, os.PathLike)):
         opponent_paths = [opponent_paths]
@@ -825,14 +989,17 @@ def evaluate_history_against_zoo(path, opponent_paths, trials, start=0, interval
         table = _table_of(kind, env, ck_paths)
         A = table.spec.ac_dim
         flats = [np.load(os.path.expanduser(p), allow_pickle=False) for p in opponent_paths]
-        groups = plan_mixed_zoo_evaluation(len(ids), [zoo_file_kind(f.size, A) for f in flats], trials, env.num_envs)
+        opp_kinds = [zoo_file_kind(f.size, A) for f in flats]
+        groups = plan_mixed_zoo_evaluation(len(ids), opp_kinds, trials, env.num_envs)
         res = []
         for grp in groups:
             zoo_table = (ZooLstmTable if grp["kind"] == "lstm" else ZooTable)([flats[k] for k in grp["opponents"]], A, env.device)
             plan = grp["plan"]
             res.append(play_against_zoo(env, table, zoo_table, plan["pairs"], plan["rounds_per_env"], plan["envs_per_pair"],
-                                        deterministic=deterministic, seed=seed, adjust_z=adjust_z, chunk=chunk, fused=fused))
+                                        deterministic=deterministic, seed=seed, adjust_z=adjust_z, chunk=chunk, fused=fused,
+                                        cross_family=cross_family))
     finally:
         if own:
             env.close()
-    return dict(checkpoints=ids, opponents=opponent_paths, results=merge_zoo_results(ids, groups, res))
+    return dict(checkpoints=ids, opponents=opponent_paths, results=merge_zoo_results(ids, groups, res), opponent_networks=opp_kinds,
+                **_network(kind))

@@ -9,6 +9,10 @@
     python tools/match_bench.py --opponent zoo_lstm [--network lstm]   # checkpoints against policy-zoo LSTM nets:
                                                    # sumo_match_steps_zoo_lstm / sumo_match_steps_lstm_zoo_lstm against ppo_forward
                                                    # (or ppo_lstm_step) + ppo_lstm_step per step
+    python tools/match_bench.py --network cross [--lstm_side 1]   # MLP(64,64) against LSTM(128) checkpoints, the LSTM table as agent
+                                                   # --lstm_side: sumo_match_steps_cross against ppo_forward + ppo_lstm_step per step
+    python tools/match_bench.py --network lstm --opponent zoo     # LSTM(128) checkpoints against policy-zoo MLP nets:
+                                                   # sumo_match_steps_lstm_zoo against ppo_lstm_step + ppo_forward_filtered per step
 
 Prints one JSON line: env-steps/s and finished matches per second of both paths (stochastic play, Ant-vs-Ant by default)."""
 import argparse
@@ -57,14 +61,16 @@ def main(argv):
     ap.add_argument("--chunk", type=int, default=64, help="steps per fused launch (and per counter read on both paths)")
     ap.add_argument("--warmup", type=int, default=64)
     ap.add_argument("--skip_stepwise", action="store_true")
-    ap.add_argument("--network", choices=("mlp", "lstm"), default="mlp", help="MLP(64,64) or LSTM(128) snapshots")
+    ap.add_argument("--network", choices=("mlp", "lstm", "cross"), default="mlp", help="MLP(64,64) or LSTM(128) snapshots, or an MLP "
+                    "table against an LSTM(128) table (cross)")
+    ap.add_argument("--lstm_side", type=int, choices=(0, 1), default=0, help="--network cross: the agent the LSTM table plays")
     ap.add_argument("--opponent", choices=("checkpoint", "zoo", "zoo_lstm"), default="checkpoint", help="agent 1: checkpoints of the same "
                     "table, synthetic policy-zoo MLP nets (one per pair) in a ZooTable, or synthetic policy-zoo LSTM nets in a ZooLstmTable")
     ap.add_argument("--repeats", type=int, default=1, help="timed runs per path, interleaved fused / step by step; the JSON line then "
                     "carries every run and the spread (max - min) of each path")
     args = ap.parse_args(argv)
-    if args.opponent == "zoo" and args.network != "mlp":
-        raise SystemExit("--opponent zoo plays MLP(64,64) checkpoints against zoo MLP nets")
+    if args.network == "cross" and args.opponent != "checkpoint":
+        raise SystemExit("--network cross plays checkpoints against checkpoints")
     import numpy as np
     import torch
     from robosumo_selfplay_amd import matches, policies
@@ -74,17 +80,21 @@ def main(argv):
     D, A = env.observation_space[0].shape[0], env.action_space[0].shape[0]
     nsnap = 2 * args.pairs
     rng = np.random.default_rng(0)
-    if args.network == "lstm":
+    table = ltable = None
+    if args.network in ("lstm", "cross"):
         from robosumo_selfplay_amd.lstm_model import LstmSpec
-        table = matches.LstmSnapshotTable(LstmSpec(D, A, 128), nsnap, env.device)
+        ltable = matches.LstmSnapshotTable(LstmSpec(D, A, 128), nsnap, env.device)
         for j in range(nsnap):
-            table.set(j, [p + 0.1 * rng.standard_normal(p.shape).astype(np.float32)
-                          for p in policies.init_lstm_param_list(D, A, 128, np.random.RandomState(j))])
-    else:
+            ltable.set(j, [p + 0.1 * rng.standard_normal(p.shape).astype(np.float32)
+                           for p in policies.init_lstm_param_list(D, A, 128, np.random.RandomState(j))])
+    if args.network in ("mlp", "cross"):
         table = matches.SnapshotTable(policies.PolicySpec(D, A, value_network="copy", activation="relu"), nsnap, env.device)
         for j in range(nsnap):
             table.set(j, policies.flatten_params([p + 0.1 * rng.standard_normal(p.shape).astype(np.float32)
                                                   for p in policies.init_param_list(D, A)]))
+    mlp_table = table
+    if args.network == "lstm":
+        table = ltable
     epp = N // args.pairs
     zoo_table = None
     if args.opponent == "zoo":
@@ -100,6 +110,8 @@ def main(argv):
     gen.manual_seed(0)
     noise = tuple(torch.randn((K, N, A), generator=gen, device="cuda") for _ in range(2))
     out = dict(env=args.env, network=args.network, opponent=args.opponent, num_env=N, pairs=args.pairs, chunk=K)
+    if args.network == "cross":
+        out["lstm_side"] = args.lstm_side
     quota = 1 << 30
     states = tuple(torch.zeros((N, 128 if args.opponent == "zoo_lstm" and g == 1 else 256), dtype=torch.float32, device="cuda") for g in range(2))
 
@@ -108,6 +120,12 @@ def main(argv):
         if args.opponent == "zoo_lstm":
             (matches.zoo_lstm_match_steps_fused if fused else matches.zoo_lstm_match_steps_stepwise)(
                 env, table, zoo_table, i0, i1, states if args.network == "lstm" else states[1], score, quota, K, noise)
+        elif args.network == "cross":
+            (matches.cross_match_steps_fused if fused else matches.cross_match_steps_stepwise)(
+                env, mlp_table, ltable, args.lstm_side, i0, i1, states[0], score, quota, K, noise)
+        elif zoo_table is not None and args.network == "lstm":
+            (matches.lstm_zoo_match_steps_fused if fused else matches.lstm_zoo_match_steps_stepwise)(
+                env, table, zoo_table, i0, i1, states[0], score, quota, K, noise)
         elif zoo_table is not None:
             (matches.zoo_match_steps_fused if fused else matches.zoo_match_steps_stepwise)(env, table, zoo_table, i0, i1, score, quota, K, noise)
         elif args.network == "lstm":

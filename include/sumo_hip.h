@@ -114,6 +114,23 @@ typedef struct sumo_rollout_lstm {
 } sumo_rollout_lstm;
 int sumo_rollout_steps_lstm(sumo_handle_t h, const sumo_rollout_lstm* r, float* actions_dev, float* obs_dev, double* info_dev,
                             uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream);
+/* sumo_rollout_steps_lstm for OPPONENT-DATA REUSE by a recurrent learner (learn(network='lstm', use_opponent_data=...)): agent 1's
+ * samples join the update batch, and BPTT re-evaluates them along agent 1's sequence with the LEARNER's net.  So the learner carries a
+ * state of its own along agent 1's stream, the shadow state, and the launch records agent 1's value and the learner's neglogp of
+ * action 1 from it: learner(obs 1, state2 masked by agent 1's done flag of the previous step) -> val[1], nlp[1], new state2.  That one
+ * evaluation replaces the last two of sumo_rollout_steps_lstm (value from agent 1's NEW opponent state, neglogp from a zero state);
+ * every other number of the launch -- actions, agent 0's record, onlp, state0, state1, the env -- is that launch's, bit for bit.
+ *   ro       the launch struct of sumo_rollout_steps_lstm, every field as there
+ *   state2   DEVICE float32 [E][256] (c | h): the shadow state, rows of THIS engine's envs; read at step s0, left at the state after
+ *            step s0 + K - 1
+ * Numbers equal the step-by-step path (Runner._step_group with reuse_opponent) bit for bit.  Refused: whatever sumo_rollout_steps_lstm
+ * refuses (hidden other than 128, a window outside the rollout buffers, ...), a missing state2.  Ordering contract as there. */
+typedef struct sumo_rollout_lstm_reuse {
+  sumo_rollout_lstm ro;
+  float* state2;
+} sumo_rollout_lstm_reuse;
+int sumo_rollout_steps_lstm_reuse(sumo_handle_t h, const sumo_rollout_lstm_reuse* r, float* actions_dev, float* obs_dev, double* info_dev,
+                                  uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream);
 /* K consecutive steps of checkpoint-vs-checkpoint MATCHES of every env of the engine in ONE launch: replaces the step loop of the
  * reference's compare_history_version.py:16-47 / play_evaluation.py (model[0].step on obs 0, model[1].step on obs 1, env.step, the
  * winner bookkeeping) for MLP(64,64) policies, on the fused launch of sumo_rollout_steps (same scheduler, hand-over and env step).

@@ -127,6 +127,16 @@ int ppo_lstm_seq_backward(const ppo_lstm_net* net, int T, int n, const float* dl
 int ppo_lstm_head_grad(const ppo_lstm_net* net, const float* latent, int rows, const float* actions, const float* adv,
                        const float* returns, const float* old_neglogp, const float* is_weight, double inv_count, float cliprange,
                        float vf_coef, float* dlatent, float* dmean, float* dvalue, float* dlogstd_rows, double* stats, void* stream);
+/* ppo_lstm_head_grad with a ROW MASK (opponent-data reuse for recurrent learners: an unusable row cannot be cut out of a sequence,
+ * it stays in the recurrence and leaves the loss).  valid float32 [rows] holds 0 or 1.  A row with valid = 0 writes exact zeros to
+ * dlatent, dmean, dvalue and dlogstd_rows and adds nothing to any stats entry (stats[6] counts valid rows only; a NaN on such a row
+ * reaches nothing); a valid row runs the arithmetic of ppo_lstm_head_grad unchanged (the value term stays unweighted by is_weight).
+ * inv_count = (float)(1 / max(*count_dev, 1)) is read on the DEVICE (count_dev: the third moment of ppo_adv_moments_masked_ws), so a
+ * captured graph replays with another number of valid rows. */
+int ppo_lstm_head_grad_masked(const ppo_lstm_net* net, const float* latent, int rows, const float* actions, const float* adv,
+                              const float* returns, const float* old_neglogp, const float* is_weight, const float* valid,
+                              const double* count_dev, float cliprange, float vf_coef, float* dlatent, float* dmean, float* dvalue,
+                              float* dlogstd_rows, double* stats, void* stream);
 /* One step of BPTT (gate order i,f,o,u): dh_carry / dc_carry [n][hidden] hold d loss / d (h_t, c_t) flowing from later steps and
  * are replaced by the values for step t-1 (already multiplied by 1 - mask_t); dz_out [n][4*hidden] receives d loss / d
  * (pre-activation gates), whose products with the inputs give the weight gradients (plain GEMMs, done by the caller).
@@ -187,6 +197,15 @@ int ppo_adv_moments_ws(const float* returns, const float* values, const int32_t*
 int ppo_adv_moments(const float* returns, const float* values, const int32_t* idx, int n, double* moments, void* stream);
 int ppo_adv_normalize(const float* returns, const float* values, const int32_t* idx, int n, const double* moments,
                       float* adv_out, void* stream);
+/* The same with a row mask, valid float32 [n] of 0 / 1 (rows are data rows 0 .. n-1): moments = {sum valid adv, sum valid adv^2,
+ * sum valid}.  Same 4096-row chunks, fixed summation order and workspace protocol as ppo_adv_moments_ws (one workspace serves both);
+ * every chunk's valid rows are moved to its front before they are summed, so all-ones gives the bits of ppo_adv_moments_ws and a
+ * minibatch of one chunk gives the bits of ppo_adv_moments_ws on its valid rows alone.  ppo_adv_normalize_masked: invalid rows get 0;
+ * a count of 0 gives all zeros, without a division. */
+int ppo_adv_moments_masked_ws(const float* returns, const float* values, const float* valid, int n, double* moments, void* workspace,
+                              void* stream);
+int ppo_adv_normalize_masked(const float* returns, const float* values, const float* valid, int n, const double* moments, float* adv_out,
+                             void* stream);
 
 /* Scores of the 'ours' opponent selector (alg_ppo.py:227-244) for ncand (1..32) candidates in ONE launch.  obs [n][obs_stride] and
  * actions [n][ac_dim] are the opponent's samples of the last rollout; ref_params is the net that produced them, table holds frozen

@@ -78,6 +78,55 @@ def assemble_update_batch(obs, returns, masks, actions, values, neglogpacs, rewa
     return out
 
 
+def assemble_recurrent_update_batch(obs, returns, masks, actions, values, neglogpacs, rewards, off_policy_ratio, total_ratio, states0,
+                                    shadow_state0, *, nenv, neglogp_threshold, use_opponent_data, vgap=None, version_gap=None):
+    """``assemble_update_batch`` for a recurrent learner (pure torch, any device).  A row cannot be cut out of a sequence, so the batch
+    is made of whole SEQUENCES -- agent 0's ``nenv`` first, then (when the ``vgap`` rule of the MLP path allows reuse) agent 1's
+    ``nenv`` -- and agent 1's unusable rows (learner neglogp at or above the threshold, NaN included) stay in the recurrence and leave
+    the loss: ``valid`` is 0 there, and so is the weight.  Every array is env-major ([nseq * nsteps, ...], ``sf01`` order); a
+    sequence starts from its own state (``states0`` | ``shadow_state0``: the learner's state along agent 1's stream), runs on its
+    own masks and carries its own old neglogp, values and returns.  ``weights`` on valid agent-1 rows: 1 (``direct``), the CLEANED
+    ``off_policy_ratio`` (``off_policy``) or ``total_ratio`` (``both``).  Returns the dict of ``assemble_update_batch`` plus
+    ``states``, ``valid`` and ``nseq``."""
+    import torch
+    if use_opponent_data not in ("direct", "off_policy", "both"):
+        raise ValueError("use_opponent_data %r" % (use_opponent_data,))
+    dev = returns.device
+    usable_mask = neglogpacs[1] < neglogp_threshold
+    usable = torch.nonzero(usable_mask).flatten()
+    names = ("obs", "returns", "masks", "actions", "values", "neglogpacs", "rewards")
+    arrs = (obs, returns, masks, actions, values, neglogpacs, rewards)
+    use_opp = not (vgap is not None and version_gap is not None and version_gap > vgap)
+    rows0 = returns[0].shape[0]
+    ones = torch.ones(rows0, dtype=torch.float32, device=dev)
+    if not use_opp:
+        out = {k: x[0] for k, x in zip(names, arrs)}
+        out.update(states=states0, valid=ones, weights=ones.clone(), nseq=int(nenv))
+    else:
+        out = {k: torch.cat([x[0], x[1]], dim=0) for k, x in zip(names, arrs)}
+        v1 = usable_mask.to(torch.float32)
+        if use_opponent_data == "direct":
+            w1 = v1.clone()
+        else:
+            ratio = (off_policy_ratio if use_opponent_data == "off_policy" else total_ratio).to(torch.float32)
+            w1 = torch.where(usable_mask, ratio, torch.zeros_like(ratio))
+        out.update(states=torch.cat([states0, shadow_state0], dim=0), valid=torch.cat([ones, v1]), weights=torch.cat([ones, w1]),
+                   nseq=2 * int(nenv))
+    out.update(usable_index=usable, useful_ratio=float(usable.numel()) / float(neglogpacs[1].numel()))
+    return out
+
+
+def check_recurrent_reuse(opponent_mode, comm, device_mode=True):
+    """What opponent-data reuse refuses for a recurrent learner, checked before the first rollout (``device_mode``: the Runner's)."""
+    if opponent_mode == "fix":
+        raise NotImplementedError("recurrent policies: opponent-data reuse needs a self-play opponent (the learner carries a shadow state "
+                                  "along agent 1's stream); opponent_mode='fix' (policy-zoo nets, leagues) is not supported with it")
+    if comm is not None:
+        raise NotImplementedError("recurrent policies: opponent-data reuse runs on a single GPU (no comm)")
+    if not device_mode:
+        raise NotImplementedError("recurrent policies: opponent-data reuse needs a device-mode Runner (SumoVecEnv and LstmPPOModel)")
+
+
 def selection_probs(action_prob, new_action_probs):
     """alg_ppo.py:237-242: mean |new/old - 1| of the candidates' ``action_probability`` outputs on the last rollout's opponent
     samples, normalised to sampling probabilities (uniform when every candidate equals the current opponent)."""
@@ -200,7 +249,9 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
     if recurrent:
         from .lstm_model import LstmPPOModel
         if use_opponent_data is not None:
-            raise NotImplementedError("recurrent policies: no opponent-data reuse")
+            if use_opponent_data not in ("direct", "off_policy", "both"):
+                raise ValueError("use_opponent_data %r" % (use_opponent_data,))
+            check_recurrent_reuse(opponent_mode, comm)
         assert nenvs % nminibatches == 0, "recurrent minibatches are whole env sequences: nenvs %% nminibatches must be 0"
     model_fn = model_fn or (LstmPPOModel if recurrent else PPOModel)
     dev = getattr(env, "device", torch.device("cuda", 0))
@@ -248,6 +299,10 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
                     anneal_bound=anneal_bound)
     # opt-in: in opponent_mode='fix' the zoo net (MLP or LSTM) plays inside the fused rollout launch (Runner.fused_fix_opponent: another noise stream)
     runner.fused_fix_opponent = bool(fused_fix_opponent)
+    reuse_rec = recurrent and use_opponent_data is not None
+    if reuse_rec:       # the learner carries a shadow state along agent 1's stream (Runner.reuse_opponent)
+        check_recurrent_reuse(opponent_mode, comm, runner.device_mode)
+        runner.reuse_opponent = True
     # opponent_pool = K > 1 (extension, BASELINE config 5): K frozen snapshots stay resident in HBM and every env plays against its own
     # one (opponent_pool.py); each update draws K snapshots by the selection law of ``opponent_mode`` instead of one.  K = 1 is the
     # reference: one snapshot for all parallel envs (alg_ppo.py:213-214).
@@ -353,9 +408,15 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
         total_ratio, m, f = clean_ratio(total_ratio, rho_bar)
         history["total_ratio_mean"].append(m); history["total_ratio_clip_frac"].append(f)
         # ---- usable opponent samples, batch assembly, weights (alg_ppo.py:286-344)
-        ub = assemble_update_batch(obs, returns, masks, actions, values, neglogpacs, rewards, off_policy_ratio, total_ratio,
-                                   nbatch=nbatch, neglogp_threshold=neglogp_threshold, use_opponent_data=use_opponent_data, vgap=vgap,
-                                   version_gap=history["version_gap"][-1] if history["version_gap"] else None)
+        if reuse_rec:       # whole sequences of both agents, unusable rows masked instead of dropped
+            ub = assemble_recurrent_update_batch(obs, returns, masks, actions, values, neglogpacs, rewards, off_policy_ratio, total_ratio,
+                                                 states, runner.shadow_state0, nenv=nenvs, neglogp_threshold=neglogp_threshold,
+                                                 use_opponent_data=use_opponent_data, vgap=vgap,
+                                                 version_gap=history["version_gap"][-1] if history["version_gap"] else None)
+        else:
+            ub = assemble_update_batch(obs, returns, masks, actions, values, neglogpacs, rewards, off_policy_ratio, total_ratio,
+                                       nbatch=nbatch, neglogp_threshold=neglogp_threshold, use_opponent_data=use_opponent_data, vgap=vgap,
+                                       version_gap=history["version_gap"][-1] if history["version_gap"] else None)
         b_obs, b_ret, b_act, b_val, b_nlp, weights = ub["obs"], ub["returns"], ub["actions"], ub["values"], ub["neglogpacs"], ub["weights"]
         history["useful_ratio"].append(ub["useful_ratio"])
         b_obs = b_obs.contiguous()
@@ -364,18 +425,25 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
         nsamp = b_obs.shape[0]
         mblossvals, early_stop, stop_info = [], False, None
         if recurrent:                          # baselines ppo2 recurrent convention: minibatches of whole env sequences
-            envsperbatch = nenvs // nminibatches
-            envinds = np.arange(nenvs)
-            flatinds = np.arange(nenvs * nsteps).reshape(nenvs, nsteps)
-            st0 = states if torch.is_tensor(states) else torch.as_tensor(np.asarray(states, np.float32)).to(dev)
-            b_masks = masks[0]
+            # (opponent-data reuse: agent 1's nenvs sequences follow agent 0's, each with its own start state and masks, and the row
+            # mask ``valid`` goes along; a minibatch that draws no valid row steps on a zero gradient, LstmPPOModel.train)
+            nseq = ub["nseq"] if reuse_rec else nenvs
+            envsperbatch = nseq // nminibatches
+            envinds = np.arange(nseq)
+            flatinds = np.arange(nseq * nsteps).reshape(nseq, nsteps)
+            if reuse_rec:
+                st0, b_masks, b_valid = ub["states"], ub["masks"], ub["valid"]
+            else:
+                st0 = states if torch.is_tensor(states) else torch.as_tensor(np.asarray(states, np.float32)).to(dev)
+                b_masks = masks[0]
             for epoch in range(noptepochs):
                 np.random.shuffle(envinds)
-                for start in range(0, nenvs, envsperbatch):
+                for start in range(0, nseq, envsperbatch):
                     mbenv = envinds[start:start + envsperbatch]
                     mbflat = torch.from_numpy(flatinds[mbenv].ravel()).to(dev)
+                    kw = dict(valid=b_valid[mbflat]) if reuse_rec else {}
                     out = model.train(lrnow, cliprangenow, b_obs[mbflat], b_ret[mbflat], b_masks[mbflat], b_act[mbflat], b_val[mbflat],
-                                      b_nlp[mbflat], None, weights[mbflat], st0[torch.from_numpy(mbenv).to(dev)], nsteps=nsteps)
+                                      b_nlp[mbflat], None, weights[mbflat], st0[torch.from_numpy(mbenv).to(dev)], nsteps=nsteps, **kw)
                     mblossvals.append(torch.tensor([float(x) for x in out[:5]], dtype=torch.float64))
         if not recurrent and hasattr(model, "begin_update"):
             model.begin_update(b_obs, b_ret, b_act, b_val, b_nlp, weights)   # the update's batch, handed over once (model.py)

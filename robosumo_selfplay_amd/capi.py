@@ -39,6 +39,12 @@ class RolloutLstm(C.Structure):
     _fields_ = [("learner", _P), ("opponents_dev", _P), ("tile_net_dev", _P), ("npool", _I), ("state0", _P), ("state1", _P)] + _ROLLOUT_TAIL
 
 
+class RolloutLstmReuse(C.Structure):
+    """``sumo_rollout_lstm_reuse`` of include/sumo_hip.h: the fields of :class:`RolloutLstm` (the header nests that struct: same
+    layout) and ``state2``, the learner's shadow state along agent 1's stream."""
+    _fields_ = RolloutLstm._fields_ + [("state2", _P)]
+
+
 class Match(C.Structure):
     """``sumo_match`` of include/sumo_hip.h (device pointers as integers)."""
     _fields_ = [("params", _P), ("idx0", _P), ("idx1", _P), ("nsnap", _I), ("ob_dim", _I), ("ac_dim", _I)] + _MATCH_TAIL
@@ -91,6 +97,7 @@ def lib():
         L.sumo_step.argtypes = [vp] * 9
         L.sumo_rollout_steps.argtypes = [vp, C.POINTER(Rollout)] + [vp] * 8
         L.sumo_rollout_steps_lstm.argtypes = [vp, C.POINTER(RolloutLstm)] + [vp] * 8
+        L.sumo_rollout_steps_lstm_reuse.argtypes = [vp, C.POINTER(RolloutLstmReuse)] + [vp] * 8
         L.sumo_match_steps.argtypes = [vp, C.POINTER(Match)] + [vp] * 8
         L.sumo_match_steps_lstm.argtypes = [vp, C.POINTER(MatchLstm)] + [vp] * 8
         L.sumo_rollout_steps_zoo.argtypes = [vp, C.POINTER(Rollout), C.POINTER(ZooMlp)] + [vp] * 8
@@ -123,7 +130,7 @@ def lib():
         L.sumo_profile.restype = i32
         for n in ("sumo_create", "sumo_destroy", "sumo_dims", "sumo_reset", "sumo_step", "sumo_rollout_steps", "sumo_rollout_steps_lstm", "sumo_match_steps", "sumo_match_steps_lstm",
                   "sumo_rollout_steps_zoo", "sumo_match_steps_zoo", "sumo_match_steps_zoo_lstm", "sumo_match_steps_lstm_zoo_lstm", "sumo_rollout_steps_zoo_lstm", "sumo_rollout_steps_lstm_zoo", "sumo_rollout_steps_lstm_zoo_lstm",
-                  "sumo_rollout_steps_zoo_league", "sumo_rollout_steps_lstm_zoo_league", "sumo_match_steps_cross", "sumo_match_steps_lstm_zoo", "sumo_get_state", "sumo_set_cfrc_mode", "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_set_state", "sumo_debug_forward", "sumo_stats"):
+                  "sumo_rollout_steps_zoo_league", "sumo_rollout_steps_lstm_zoo_league", "sumo_match_steps_cross", "sumo_match_steps_lstm_zoo", "sumo_rollout_steps_lstm_reuse", "sumo_get_state", "sumo_set_cfrc_mode", "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_set_state", "sumo_debug_forward", "sumo_stats"):
             getattr(L, n).restype = i32
         _LIB = L
     return _LIB
@@ -131,7 +138,7 @@ def lib():
 
 EXPORTS = ("sumo_last_error", "sumo_create", "sumo_destroy", "sumo_dims", "sumo_reset", "sumo_step", "sumo_rollout_steps",
            "sumo_rollout_steps_lstm", "sumo_match_steps", "sumo_match_steps_lstm", "sumo_rollout_steps_zoo", "sumo_match_steps_zoo", "sumo_match_steps_zoo_lstm", "sumo_match_steps_lstm_zoo_lstm", "sumo_rollout_steps_zoo_lstm", "sumo_rollout_steps_lstm_zoo", "sumo_rollout_steps_lstm_zoo_lstm",
-           "sumo_rollout_steps_zoo_league", "sumo_rollout_steps_lstm_zoo_league", "sumo_match_steps_cross", "sumo_match_steps_lstm_zoo", "sumo_set_cfrc_mode", "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_get_state", "sumo_set_state", "sumo_debug_forward", "sumo_stats", "sumo_profile", "sumo_debug_trace",
+           "sumo_rollout_steps_zoo_league", "sumo_rollout_steps_lstm_zoo_league", "sumo_match_steps_cross", "sumo_match_steps_lstm_zoo", "sumo_rollout_steps_lstm_reuse", "sumo_set_cfrc_mode", "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_get_state", "sumo_set_state", "sumo_debug_forward", "sumo_stats", "sumo_profile", "sumo_debug_trace",
            "sumo_rollout_status", "sumo_debug_fault", "sumo_static_layout", "sumo_debug_layout", "sumo_debug_model_ints", "sumo_debug_dump")
 
 
@@ -195,6 +202,11 @@ class Engine:
     def rollout_steps_lstm(self, ro, *env_ptrs, stream=None):
         """The same for recurrent policies (``sumo_rollout_steps_lstm``); ``ro`` is a filled :class:`RolloutLstm`."""
         self._fused("sumo_rollout_steps_lstm", ro, env_ptrs, stream)
+
+    def rollout_steps_lstm_reuse(self, ro, *env_ptrs, stream=None):
+        """The recurrent launch under opponent-data reuse (``sumo_rollout_steps_lstm_reuse``); ``ro`` is a filled
+        :class:`RolloutLstmReuse` (``state2``: the learner's shadow state rows of the launch's envs, read and updated in place)."""
+        self._fused("sumo_rollout_steps_lstm_reuse", ro, env_ptrs, stream)
 
     def match_steps(self, mo, *env_ptrs, stream=None):
         """K fused checkpoint-vs-checkpoint match steps (``sumo_match_steps``); ``mo`` is a filled :class:`Match`.  The outcome is

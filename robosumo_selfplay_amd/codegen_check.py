@@ -16,13 +16,28 @@ import tempfile
 
 LLVM = "/opt/rocm/lib/llvm/bin"
 
-def disassemble(lib):
+def code_objects(lib):
+    """-> paths of the gfx950 code objects embedded in `lib`: one offload bundle per translation unit linked into it (build.py compiles
+    sumo_engine.hip in several), back to back in .hip_fatbin."""
     d = tempfile.mkdtemp()
-    fat, co = os.path.join(d, "fat.bin"), os.path.join(d, "dev.co")
+    fat = os.path.join(d, "fat.bin")
     subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib, fat])
-    subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fat,
-                           "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
-    return subprocess.check_output([os.path.join(LLVM, "llvm-objdump"), "-d", co], text=True)
+    with open(fat, "rb") as f:
+        blob = f.read()
+    starts = [m.start() for m in re.finditer(b"__CLANG_OFFLOAD_BUNDLE__", blob)]
+    out = []
+    for k, s in enumerate(starts):
+        part, co = os.path.join(d, "fat%d.bin" % k), os.path.join(d, "dev%d.co" % k)
+        with open(part, "wb") as f:
+            f.write(blob[s:starts[k + 1] if k + 1 < len(starts) else len(blob)])
+        subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + part,
+                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
+        out.append(co)
+    return out
+
+
+def disassemble(lib):
+    return "\n".join(subprocess.check_output([os.path.join(LLVM, "llvm-objdump"), "-d", co], text=True) for co in code_objects(lib))
 
 
 def vregs(tok):

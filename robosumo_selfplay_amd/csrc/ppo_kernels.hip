@@ -645,11 +645,16 @@ extern "C" int ppo_lstm_step_save_z(const ppo_lstm_net* net, const float* z_t, i
 }
 
 // ---- loss heads on stored latents: one thread per row (rows x hidden x (ac_dim + 1) MACs: small next to the recurrence)
+// MASKED (ppo_lstm_head_grad_masked): a row with valid[r] == 0 stays in the recurrence and leaves the loss -- it writes exact zeros to
+// its four outputs and enters no statistic; inv_count is read on the device as 1 / max(*count_dev, 1), so that a captured graph
+// replays with another number of usable rows.  The two arguments come last: the unmasked instantiation reads every other one at
+// the offset it always had and keeps its instruction stream.
+template <bool MASKED>
 __global__ void __launch_bounds__(128) ppo_lstm_head_grad_kernel(ppo_lstm_net N, const float* latent, int rows, const float* actions,
                                                                  const float* adv, const float* returns, const float* oldnlp,
                                                                  const float* weight, float inv_count, float cliprange, float vf_coef,
                                                                  float* dlatent, float* dmean_o, float* dvalue_o, float* dlogstd_rows,
-                                                                 double* stats) {
+                                                                 double* stats, const float* valid, const double* count_dev) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   // (loops over the action dimensions are unrolled to MAXA with guards: with a runtime trip count the per-row arrays are indexed
   // dynamically and live in scratch memory -- 1 500 cycles per unit of the latent)
@@ -663,7 +668,18 @@ __global__ void __launch_bounds__(128) ppo_lstm_head_grad_kernel(ppo_lstm_net N,
   }
   __syncthreads();
   double s_pg = 0, s_vf = 0, s_kl = 0, s_cf = 0, s_n = 0;
-  if (r < rows) {
+  bool live = r < rows;
+  if constexpr (MASKED) {
+    if (live && valid[r] == 0.0f) {
+      live = false;
+      for (int q = 0; q < A; q++) { dmean_o[(size_t)r * A + q] = 0.0f; dlogstd_rows[(size_t)r * A + q] = 0.0f; }
+      dvalue_o[r] = 0.0f;
+      for (int k = 0; k < Hh; k++) dlatent[(size_t)r * Hh + k] = 0.0f;
+    }
+    const double cnt = *count_dev;
+    inv_count = (float)(1.0 / (cnt > 1.0 ? cnt : 1.0));
+  }
+  if (live) {
     const float* L = latent + (size_t)r * Hh;
     float mean[MAXA], value = N.vf_b[0];
 #pragma unroll
@@ -721,7 +737,7 @@ __global__ void __launch_bounds__(128) ppo_lstm_head_grad_kernel(ppo_lstm_net N,
     if ((int)threadIdx.x < o) for (int q = 0; q < 5; q++) red[q][threadIdx.x] += red[q][threadIdx.x + o];
     __syncthreads();
   }
-  if (threadIdx.x == 0) {
+  if (threadIdx.x == 0 && (!MASKED || red[4][0] > 0.0)) {   // (a workgroup without a valid row adds nothing)
     atomicAdd(stats + 0, red[0][0]); atomicAdd(stats + 1, red[1][0]); atomicAdd(stats + 3, red[2][0]); atomicAdd(stats + 4, red[3][0]);
     atomicAdd(stats + 6, red[4][0]);
   }
@@ -735,8 +751,24 @@ extern "C" int ppo_lstm_head_grad(const ppo_lstm_net* net, const float* latent, 
     FAIL(-1, "bad arguments");
   if (!net->head_w || !net->head_b || !net->logstd || !net->vf_w || !net->vf_b || net->ac_dim < 1 || net->ac_dim > MAXA)
     FAIL(-2, "both heads are needed");
-  hipLaunchKernelGGL(ppo_lstm_head_grad_kernel, dim3((rows + 127) / 128), dim3(128), 0, (hipStream_t)stream, *net, latent, rows, actions,
-                     adv, returns, old_neglogp, is_weight, (float)inv_count, cliprange, vf_coef, dlatent, dmean, dvalue, dlogstd_rows, stats);
+  hipLaunchKernelGGL(ppo_lstm_head_grad_kernel<false>, dim3((rows + 127) / 128), dim3(128), 0, (hipStream_t)stream, *net, latent, rows, actions,
+                     adv, returns, old_neglogp, is_weight, (float)inv_count, cliprange, vf_coef, dlatent, dmean, dvalue, dlogstd_rows, stats,
+                     (const float*)nullptr, (const double*)nullptr);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+extern "C" int ppo_lstm_head_grad_masked(const ppo_lstm_net* net, const float* latent, int rows, const float* actions, const float* adv,
+                                         const float* returns, const float* old_neglogp, const float* is_weight, const float* valid,
+                                         const double* count_dev, float cliprange, float vf_coef, float* dlatent, float* dmean,
+                                         float* dvalue, float* dlogstd_rows, double* stats, void* stream) {
+  if (!net || !latent || !actions || !adv || !returns || !old_neglogp || !is_weight || !valid || !count_dev || !dlatent || !dmean ||
+      !dvalue || !dlogstd_rows || !stats || rows <= 0)
+    FAIL(-1, "bad arguments");
+  if (!net->head_w || !net->head_b || !net->logstd || !net->vf_w || !net->vf_b || net->ac_dim < 1 || net->ac_dim > MAXA)
+    FAIL(-2, "both heads are needed");
+  hipLaunchKernelGGL(ppo_lstm_head_grad_kernel<true>, dim3((rows + 127) / 128), dim3(128), 0, (hipStream_t)stream, *net, latent, rows, actions,
+                     adv, returns, old_neglogp, is_weight, 0.0f, cliprange, vf_coef, dlatent, dmean, dvalue, dlogstd_rows, stats, valid,
+                     count_dev);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -1321,11 +1353,53 @@ extern "C" int ppo_vtrace(const float* rewards, const float* values, const float
 // caller -- one model, one stream -- so two models stepping on different streams do not share state (round 2 kept it in module-level
 // device memory).  Any n: a block takes the chunks blockIdx.x, blockIdx.x + gridDim.x, ...
 #define ADV_MAX_BLOCKS 256
-struct AdvWs { double part[2 * ADV_MAX_BLOCKS]; unsigned int arrived; unsigned int pad; };
-__global__ void __launch_bounds__(1024) ppo_adv_moments_kernel(const float* ret, const float* val, const int32_t* idx, int n, double* mom, AdvWs* ws) {
+// MASKED (ppo_adv_moments_masked_ws): rows with valid[k] == 0 leave the sums and the count.  Every 4096-row chunk is compacted in LDS
+// first -- its valid rows, in row order, move to the front and zeros follow -- and then summed exactly as the unmasked kernel sums a
+// chunk: with every row valid that is the unmasked order, and a minibatch of one chunk gives the bits of the unmasked kernel run on
+// its valid rows alone.  The count is an integer (ws->count, added by every block, read and zeroed by the last one): any order.
+struct AdvWs { double part[2 * ADV_MAX_BLOCKS]; unsigned int arrived; unsigned int count; };
+template <bool MASKED>
+__global__ void __launch_bounds__(1024) ppo_adv_moments_kernel(const float* ret, const float* val, const int32_t* idx, int n, double* mom, AdvWs* ws,
+                                                               const float* valid) {
   __shared__ double s1[16], s2[16];
   __shared__ int last;
   double a = 0, b = 0;
+  unsigned int nvalid = 0;
+  if constexpr (MASKED) {
+    __shared__ float dsh[4096];
+    __shared__ int wcount[4][16];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int base = blockIdx.x * 4096; base < n; base += gridDim.x * 4096) {
+      float d[4];
+      int pre[4];
+      bool v[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const int k = base + threadIdx.x + 1024 * u;
+        v[u] = k < n && valid[k] != 0.0f;
+        d[u] = v[u] ? ret[k] - val[k] : 0.0f;      // float32 subtraction first, as numpy does
+        const unsigned long long m = __ballot(v[u]);
+        pre[u] = __popcll(m & ((1ull << lane) - 1ull));
+        if (lane == 0) wcount[u][wv] = __popcll(m);
+        dsh[threadIdx.x + 1024 * u] = 0.0f;
+      }
+      __syncthreads();
+      int run = 0, off[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++)
+        for (int w2 = 0; w2 < 16; w2++) { if (w2 == wv) off[u] = run; run += wcount[u][w2]; }
+#pragma unroll
+      for (int u = 0; u < 4; u++) if (v[u]) dsh[off[u] + pre[u]] = d[u];
+      __syncthreads();
+      nvalid += (unsigned int)run;
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        double dd = (double)dsh[threadIdx.x + 1024 * u];
+        a += dd; b += dd * dd;
+      }
+      __syncthreads();   // the next chunk rewrites dsh / wcount
+    }
+  } else {
   for (int base = blockIdx.x * 4096; base < n; base += gridDim.x * 4096) {
     int r[4];
     float x[4], y[4];
@@ -1345,6 +1419,7 @@ __global__ void __launch_bounds__(1024) ppo_adv_moments_kernel(const float* ret,
       a += d; b += d * d;
     }
   }
+  }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o); b += __shfl_xor(b, o); }
   const int w = threadIdx.x >> 6;
@@ -1355,6 +1430,7 @@ __global__ void __launch_bounds__(1024) ppo_adv_moments_kernel(const float* ret,
     for (int i = 0; i < 16; i++) { ta += s1[i]; tb += s2[i]; }
     __hip_atomic_store(&ws->part[2 * blockIdx.x], ta, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);       // sc1: visible to every XCD
     __hip_atomic_store(&ws->part[2 * blockIdx.x + 1], tb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if constexpr (MASKED) (void)__hip_atomic_fetch_add(&ws->count, nvalid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const unsigned int arrived = __hip_atomic_fetch_add(&ws->arrived, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     last = (arrived == gridDim.x - 1);
@@ -1372,7 +1448,13 @@ __global__ void __launch_bounds__(1024) ppo_adv_moments_kernel(const float* ret,
         for (unsigned int k = 0; k < 8; k++)
           if (i0 + k < gridDim.x) { sa += va[k]; sb += vb[k]; }
       }
-      mom[0] = sa; mom[1] = sb; mom[2] = (double)n;
+      mom[0] = sa; mom[1] = sb;
+      if constexpr (MASKED) {
+        mom[2] = (double)__hip_atomic_load(&ws->count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&ws->count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      } else {
+        mom[2] = (double)n;
+      }
       __hip_atomic_store(&ws->arrived, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);                    // ready for the next call
     }
   }
@@ -1386,13 +1468,43 @@ __global__ void ppo_adv_normalize_kernel(const float* ret, const float* val, con
   int r = idx ? idx[k] : k;
   out[k] = ((ret[r] - val[r]) - m32) / (s32 + 1e-8f);
 }
+// Invalid rows get 0; a count of 0 gives all zeros (no division).  Valid rows: the expression of ppo_adv_normalize_kernel.
+__global__ void ppo_adv_normalize_masked_kernel(const float* ret, const float* val, const float* valid, int n, const double* mom, float* out) {
+  int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const double cnt = mom[2];
+  if (!(cnt > 0) || valid[k] == 0.0f) { out[k] = 0.0f; return; }
+  double mean = mom[0] / cnt, var = mom[1] / cnt - mean * mean;
+  if (var < 0) var = 0;
+  float m32 = (float)mean, s32 = (float)sqrt(var);
+  out[k] = ((ret[k] - val[k]) - m32) / (s32 + 1e-8f);
+}
 extern "C" size_t ppo_adv_moments_workspace_bytes(void) { return sizeof(AdvWs); }
 extern "C" int ppo_adv_moments_ws(const float* returns, const float* values, const int32_t* idx, int n, double* moments, void* workspace,
                                   void* stream) {
   if (!returns || !values || !moments || !workspace || n <= 0) FAIL(-1, "bad arguments");
   int nb = (n + 4095) / 4096;
   if (nb > ADV_MAX_BLOCKS) nb = ADV_MAX_BLOCKS;     // larger minibatches: the blocks stride over the chunks
-  hipLaunchKernelGGL(ppo_adv_moments_kernel, dim3(nb), dim3(1024), 0, (hipStream_t)stream, returns, values, idx, n, moments, (AdvWs*)workspace);
+  hipLaunchKernelGGL(ppo_adv_moments_kernel<false>, dim3(nb), dim3(1024), 0, (hipStream_t)stream, returns, values, idx, n, moments, (AdvWs*)workspace,
+                     (const float*)nullptr);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+extern "C" int ppo_adv_moments_masked_ws(const float* returns, const float* values, const float* valid, int n, double* moments, void* workspace,
+                                         void* stream) {
+  if (!returns || !values || !valid || !moments || !workspace || n <= 0) FAIL(-1, "bad arguments");
+  int nb = (n + 4095) / 4096;
+  if (nb > ADV_MAX_BLOCKS) nb = ADV_MAX_BLOCKS;
+  hipLaunchKernelGGL(ppo_adv_moments_kernel<true>, dim3(nb), dim3(1024), 0, (hipStream_t)stream, returns, values, (const int32_t*)nullptr, n, moments,
+                     (AdvWs*)workspace, valid);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+extern "C" int ppo_adv_normalize_masked(const float* returns, const float* values, const float* valid, int n, const double* moments,
+                                        float* adv_out, void* stream) {
+  if (!returns || !values || !valid || !moments || !adv_out || n <= 0) FAIL(-1, "bad arguments");
+  hipLaunchKernelGGL(ppo_adv_normalize_masked_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, returns, values, valid, n, moments,
+                     adv_out);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -51,7 +51,9 @@ static ParamLayout make_layout(int D, int A) {
   L.P = o;
   return L;
 }
+#ifndef SUMO_ROLLOUT_SHARD   // sumo_engine.hip's shard objects hold device code only; its main object defines the symbol
 extern "C" int ppo_param_count(int ob_dim, int ac_dim) { return make_layout(ob_dim, ac_dim).P; }
+#endif
 
 static int x_stride(int D) {  // LDS row stride of the staged observation tile: >= 16*ceil(D/16), == 2 mod 32
   int cols = ((D + 15) / 16) * 16;

@@ -2596,6 +2596,8 @@ struct RolloutArgs {
   // cross-family matches (POLICY 13): the agent the LSTM(128) checkpoints play (the other one plays the MLP(64,64) checkpoints) and
   // the size of their table onets (nsnap is the size of snaps); appended like the zoo tables
   int lstm_side, nsnap_lstm;
+  // opponent-data reuse for a recurrent learner (POLICY 15): the learner's shadow state along agent 1's stream [N][2 hidden]; appended
+  float* st2;
 };
 
 // ---- pieces shared by the four policy phases (each reads a / r through the references its phase received) ----
@@ -2730,7 +2732,14 @@ __device__ __forceinline__ void rollout_policy_phase(C& c, const SA& a, const RA
 // Gate pre-activations run on the vector ALU in the MFMA tiles' accumulation order (lstm_gates_valu), cell update and heads
 // through the functions ppo_lstm_step_kernel uses: every number equals the launch-per-evaluation path bit for bit.
 // LDS (floats, from lds_off): x [2][XS] | zero row [NH] | previous latents [3][NH] | new latents [3][NH].
-template <int NH, class C, class SA, class RA>
+//
+// REUSE (POLICY 15, sumo_rollout_steps_lstm_reuse: opponent-data reuse for a recurrent learner).  The opponent's pass is the one
+// above; the learner's pass has TWO rows, and rows D and E give way to
+//                 row D' = (obs 1, the learner's SHADOW state along agent 1's stream r.st2, masked by agent 1's done flag)
+//                          -> the value AND the neglogp of action 1 recorded for agent 1, the new shadow state
+// -- what BPTT re-evaluates along agent 1's sequence, so the recorded "old" numbers belong to the function that is trained.  The
+// shadow state crosses waves like the other two.  Same LDS region (one new latent row stays unused).
+template <int NH, bool REUSE = false, class C, class SA, class RA>
 __device__ __forceinline__ void rollout_policy_phase_lstm(C& c, const SA& a, const RA& r, int e, int s) {
   const int lane = c.lane;
   const auto& NL = r.lnet;
@@ -2754,6 +2763,12 @@ __device__ __forceinline__ void rollout_policy_phase_lstm(C& c, const SA& a, con
   lstm_state_pair(s1p + j0, keep1, c1);
   lstm_state_pair(s0p + NH + j0, keep0, hp + NH + j0);
   lstm_state_pair(s1p + NH + j0, keep1, hp + j0);
+  float* s2p = nullptr;
+  if constexpr (REUSE) {
+    s2p = r.st2 + (size_t)e * 2 * NH;
+    lstm_state_pair(s2p + j0, keep1, cD);
+    lstm_state_pair(s2p + NH + j0, keep1, hp + 2 * NH + j0);
+  }
   hz[j0] = 0.0f; hz[j0 + 1] = 0.0f;
   wave_sync();
   const ppo_lstm_net PT_GAS* NOp = pt_global(r.onets) + (r.tile_net ? pt_global(r.tile_net)[col >> 4] : 0);
@@ -2777,7 +2792,7 @@ __device__ __forceinline__ void rollout_policy_phase_lstm(C& c, const SA& a, con
       const LstmCell cb = lstm_cell(z[0][u][1], z[1][u][1], z[2][u][1], z[3][u][1], bi, bf, bo, bu, hz[j]);
       lstm_state_store<NH>(s1p, j, ca);                                              // agent 1's state after the opponent's step
       hn[j] = ca.hn; hn[NH + j] = cb.hn;
-      cD[u] = ca.cn * keep1; hp[2 * NH + j] = ca.hn * keep1;                         // row D: masked once more by the same flag
+      if constexpr (!REUSE) { cD[u] = ca.cn * keep1; hp[2 * NH + j] = ca.hn * keep1; }   // row D: masked once more by the same flag
     }
     wave_sync();
     float m[2];
@@ -2790,7 +2805,40 @@ __device__ __forceinline__ void rollout_policy_phase_lstm(C& c, const SA& a, con
     wave_sync();   // the latent rows are rewritten by the learner's pass
   }
   float nlp0, nlp1, onlp0, v0, v1;
-  {  // ---- learner net: rows C, D, E
+  if constexpr (REUSE) {  // ---- learner net: rows C, D'
+    // A two-row learner pass like lstm_learner_front's (POLICY 9, 10, 12), with row 2's (c, h) from the shadow state and one more
+    // state store.  It is written out here and not drawn from a helper shared with that function and the branch below: a helper
+    // would rewrite the source of modes 1, 9, 10 and 12, whose static-layout code objects this change keeps the parent's line for
+    // line (DESIGN.md sections 18, 19), and whether they survive that has not been tried.  The pieces inside (lstm_bias_pair,
+    // lstm_gates_valu, lstm_cell, lstm_state_store, lstm_heads_valu, gauss_row) exist once.
+    const float fb = NL.forget_bias;
+    float z[4][2][2], bz[4][2];
+    lstm_bias_pair<NH>(pt_global(NL.b), j0, bz);
+    const float* const xr[2] = {xo, xo + XS};
+    const float* const hr[2] = {hp + NH, hp + 2 * NH};
+    lstm_gates_valu<NH, 2>(NL.wx, NL.wh, D, xr, hr, lane, z);
+#pragma unroll
+    for (int u = 0; u < 2; u++) {
+      const int j = j0 + u;
+      const float bi = bz[0][u], bf = bz[1][u] + fb, bo = bz[2][u], bu = bz[3][u];
+      const LstmCell cc = lstm_cell(z[0][u][0], z[1][u][0], z[2][u][0], z[3][u][0], bi, bf, bo, bu, c0[u]);
+      const LstmCell cd = lstm_cell(z[0][u][1], z[1][u][1], z[2][u][1], z[3][u][1], bi, bf, bo, bu, cD[u]);
+      lstm_state_store<NH>(s0p, j, cc);                                              // agent 0's state after the learner's step
+      lstm_state_store<NH>(s2p, j, cd);                                              // the shadow state after agent 1's row
+      hn[j] = cc.hn; hn[NH + j] = cd.hn;
+    }
+    wave_sync();
+    float m[2];
+    lstm_heads_valu<NH, 2>(NL.head_w, NL.vf_w, A, hn, lane, m);
+    const float hb = ok ? pt_global(NL.head_b)[lane] : 0.0f, ls = ok ? pt_global(NL.logstd)[lane] : 0.0f;
+    const float stdL = expf(ls), sumL = row16_sum(ls);
+    const float vb = pt_global(NL.vf_b)[0];
+    v0 = __shfl(m[0], 16) + vb; v1 = __shfl(m[1], 16) + vb;
+    const float n0 = ok ? pt_global(r.noise0)[nz] : 0.0f;
+    nlp0 = gauss_row(m[0] + hb, stdL, sumL, ok, true, n0, act0, A);      // the learner samples for agent 0 ...
+    onlp0 = gauss_row(mOB, stdO, sumO, ok, false, 0.0f, act0, A);        // ... the opponent net (zero state) scores that action
+    nlp1 = gauss_row(m[1] + hb, stdL, sumL, ok, false, 0.0f, act1, A);   // the learner (shadow state) scores the opponent's action
+  } else {  // ---- learner net: rows C, D, E
     const float fb = NL.forget_bias;
     float z[4][2][3], bz[4][2];
     lstm_bias_pair<NH>(pt_global(NL.b), j0, bz);
@@ -3400,6 +3448,8 @@ static_assert(sizeof(const Params*) + sizeof(RolloutLaunch) <= 4096, "the launch
 //   12  sumo_rollout_steps_lstm_zoo_league  LSTM learner vs a league of both families lstm_learner_front + league_zoo_pass
 //   13  sumo_match_steps_cross              MLP checkpoints vs LSTM(128) checkpoints  match_lstm_side(g) + match_mlp_side(1 - g)
 //   14  sumo_match_steps_lstm_zoo           LSTM(128) checkpoints vs zoo MLP nets     match_lstm_side(0) + zoo_mlp_act
+//   15  sumo_rollout_steps_lstm_reuse       LSTM(128) self-play, agent 1 scored and   rollout_policy_phase_lstm<128, true>
+//                                           valued from the learner's shadow state
 // (4, 8 .. 12 are rollout_policy_phase_vs_zoo<LSTM_LEARNER, ZOO_KIND>.)  The integers are part of the kernels' mangled names, which
 // profiles/ and tools/ refer to.  SL 1 / 2: static Layout.
 template <int NV, int POLICY, int SL = 0>
@@ -3469,6 +3519,7 @@ sumo_rollout_kernel(const Params* P, RolloutLaunch launch_args) {
     else if constexpr (POLICY == 12) rollout_policy_phase_vs_zoo<true, ZOO_LEAGUE>(c, lp->a, lp->r, e, s);
     else if constexpr (POLICY == 13) rollout_policy_phase_match_cross<128>(c, lp->a, lp->r, e, s);
     else if constexpr (POLICY == 14) rollout_policy_phase_match_lstm_zoo<128>(c, lp->a, lp->r, e, s);
+    else if constexpr (POLICY == 15) rollout_policy_phase_lstm<128, true>(c, lp->a, lp->r, e, s);
     else rollout_policy_phase(c, lp->a, lp->r, e, s);
 #ifdef SUMO_DBG_HARD_BARRIER
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -3495,6 +3546,45 @@ sumo_rollout_kernel(const Params* P, RolloutLaunch launch_args) {
   flush_stats(c, launder_sptr(LP)->a.stats);
 }
 
+// Number of POLICY values above; rollout_launch's table and the instantiation lists below cover 0 .. SUMO_N_POLICY - 1.
+#define SUMO_N_POLICY 16
+// ---- building in parallel.  The instantiations of sumo_rollout_kernel (7 variants x SUMO_N_POLICY) are most of this file's compile
+// time, and one translation unit compiles on one core.  build.py therefore compiles this file several times side by side and links
+// the objects into one library:
+//   -DSUMO_ROLLOUT_SHARD=k (k = 0 .. 4)  device code of the dynamic-layout rollout kernels <28 + 4 k, *, 0> only (explicit
+//                                        instantiations, no host side)
+//   -DSUMO_ROLLOUT_EXTERN                everything else; those rollout kernels are declared `extern template`
+// The static-layout rollout kernels <28, *, 1> and <44, *, 2> stay in the main object: compiled apart from the step kernels
+// of their layout they come out with a different register allocation and schedule (the out-of-line device functions they share
+// are specialised per module), and <28, 0, 1> is the benchmark's kernel.  The dynamic-layout ones are the same text in a shard as
+// in one translation unit but for PC-relative immediates.
+// With neither macro the file is one self-contained translation unit, as the development tools compile it. ----
+#if defined(SUMO_ROLLOUT_SHARD) || defined(SUMO_ROLLOUT_EXTERN)
+#define SUMO_RK(KW, NV, SL, P) KW template __global__ void sumo_rollout_kernel<NV, P, SL>(const Params*, RolloutLaunch);
+#define SUMO_RK_ALL(KW, NV, SL)                                                                                                   \
+  SUMO_RK(KW, NV, SL, 0) SUMO_RK(KW, NV, SL, 1) SUMO_RK(KW, NV, SL, 2) SUMO_RK(KW, NV, SL, 3) SUMO_RK(KW, NV, SL, 4)              \
+  SUMO_RK(KW, NV, SL, 5) SUMO_RK(KW, NV, SL, 6) SUMO_RK(KW, NV, SL, 7) SUMO_RK(KW, NV, SL, 8) SUMO_RK(KW, NV, SL, 9)              \
+  SUMO_RK(KW, NV, SL, 10) SUMO_RK(KW, NV, SL, 11) SUMO_RK(KW, NV, SL, 12) SUMO_RK(KW, NV, SL, 13) SUMO_RK(KW, NV, SL, 14)         \
+  SUMO_RK(KW, NV, SL, 15)
+static_assert(SUMO_N_POLICY == 16, "extend SUMO_RK_ALL");
+#ifdef SUMO_ROLLOUT_EXTERN
+SUMO_RK_ALL(extern, 28, 0) SUMO_RK_ALL(extern, 32, 0) SUMO_RK_ALL(extern, 36, 0) SUMO_RK_ALL(extern, 40, 0) SUMO_RK_ALL(extern, 44, 0)
+#elif SUMO_ROLLOUT_SHARD == 0
+SUMO_RK_ALL(, 28, 0)
+#elif SUMO_ROLLOUT_SHARD == 1
+SUMO_RK_ALL(, 32, 0)
+#elif SUMO_ROLLOUT_SHARD == 2
+SUMO_RK_ALL(, 36, 0)
+#elif SUMO_ROLLOUT_SHARD == 3
+SUMO_RK_ALL(, 40, 0)
+#elif SUMO_ROLLOUT_SHARD == 4
+SUMO_RK_ALL(, 44, 0)
+#else
+#error "SUMO_ROLLOUT_SHARD: 0 .. 4"
+#endif
+#endif
+
+#ifndef SUMO_ROLLOUT_SHARD   // to the end of the file: the other kernels and the host side
 template <int NV>
 __global__ void __launch_bounds__(WAVE) sumo_reset_kernel(const Params* P, StepArgs a) {
   Ctx<NV> c;
@@ -4335,7 +4425,7 @@ static int rollout_launch(sumo_engine* E, const RolloutArgs& r, int policy, cons
   size_t lds_ = (size_t)E->L.total_bytes;
   if (!for_engine_variant(E, [&](auto nvc_, auto slc_) {
         constexpr int NV = decltype(nvc_)::value, SL = decltype(slc_)::value;
-        const RolloutKernel kernel = rollout_kernel<NV, SL>(policy, std::make_integer_sequence<int, 15>{});
+        const RolloutKernel kernel = rollout_kernel<NV, SL>(policy, std::make_integer_sequence<int, SUMO_N_POLICY>{});
         hipLaunchKernelGGL(kernel, g_, b_, lds_, st_, E->d_params, rl);
       }))
     FAIL(-19, "no kernel variant for nv=%d", E->hm.nv);
@@ -4558,7 +4648,7 @@ static int place_zoo_league(RolloutArgs& r, const sumo_zoo_league* z, int od, in
   return 0;
 }
 
-// ---- the fifteen entry points: env buffers, the family's checks (and the mode's), begin_*, the scratch of the learner's /
+// ---- the sixteen entry points: env buffers, the family's checks (and the mode's), begin_*, the scratch of the learner's /
 // checkpoints' side, the opponent table, launch.  Where a zoo MLP table comes before the scratch and a zoo LSTM table after it, that
 // is the order in which the mode reports their errors. ----
 extern "C" int sumo_rollout_steps(sumo_handle_t E, const sumo_rollout* ro, float* actions_dev, float* obs_dev, double* info_dev,
@@ -4583,6 +4673,20 @@ extern "C" int sumo_rollout_steps_lstm(sumo_handle_t E, const sumo_rollout_lstm*
   if (int rc = check_lstm_rollout(E, ro, NULL, 0, &od, &ad)) return rc;
   if (int rc = begin_lstm_rollout(E, ro, od, 7, r)) return rc;   // zero row, previous latents [3], new latents [3]
   return rollout_launch(E, r, 1, b, stream);
+}
+
+extern "C" int sumo_rollout_steps_lstm_reuse(sumo_handle_t E, const sumo_rollout_lstm_reuse* rr, float* actions_dev, float* obs_dev, double* info_dev,
+                                             uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
+  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
+  RolloutArgs r = {};
+  int od = 0, ad = 0;
+  if (int rc = check_launch_args(E, rr, b)) return rc;
+  const sumo_rollout_lstm* ro = &rr->ro;
+  if (!rr->state2) FAIL(-2, "sumo_rollout_lstm_reuse: missing buffer (state2)");
+  if (int rc = check_lstm_rollout(E, ro, NULL, 0, &od, &ad)) return rc;
+  if (int rc = begin_lstm_rollout(E, ro, od, 7, r)) return rc;   // the region of sumo_rollout_steps_lstm (one new latent row unused)
+  r.st2 = rr->state2;
+  return rollout_launch(E, r, 15, b, stream);
 }
 
 extern "C" int sumo_match_steps(sumo_handle_t E, const sumo_match* mo, float* actions_dev, float* obs_dev, double* info_dev,
@@ -4964,3 +5068,4 @@ extern "C" int sumo_stats(sumo_handle_t E, double* out) {
   for (int i = 0; i < SUMO_NSTATS; i++) out[i] = (double)h[i];
   return 0;
 }
+#endif   // !SUMO_ROLLOUT_SHARD

@@ -145,11 +145,20 @@ class LstmPPOModel(Learner):
         r = self._run(observation, None, None, given_action=given_action)
         return r[1], r[3]
 
+    def score_value_advance(self, observation, S, M, given_action):
+        """(value, neglogp of ``given_action``, new state) from the state ``S`` masked by ``M`` in ONE evaluation: how the Runner
+        scores and values agent 1's action along the learner's shadow state under opponent-data reuse (``Runner.reuse_opponent``)."""
+        r = self._run(observation, S, M, given_action=given_action)
+        return r[1], r[3], r[2]
+
     # ---- training ---------------------------------------------------------------------------------------------------
-    def loss_and_grads(self, cliprange, obs, returns, masks, actions, advs, neglogpacs, IS_weight, states, nsteps, world=1):
+    def loss_and_grads(self, cliprange, obs, returns, masks, actions, advs, neglogpacs, IS_weight, states, nsteps, world=1, valid=None):
         """Forward over ``nsteps`` + BPTT for a minibatch of whole env sequences.  Flat inputs are env-major
         ([nenv_mb * nsteps, ...], baselines' ``sf01`` order); ``states`` [nenv_mb, 2H] is the state at the start of the
-        sequences.  Leaves d(mean loss)/d(theta) in ``self.grads``, the un-normalised loss sums in ``self.stats``."""
+        sequences.  Leaves d(mean loss)/d(theta) in ``self.grads``, the un-normalised loss sums in ``self.stats``.
+        ``valid`` (0 / 1 per row, opponent-data reuse): rows with 0 stay in the recurrence and leave the loss
+        (``ppo_lstm_head_grad_masked``); the mean is then over the valid rows, whose number the kernel reads from ``self.moments[2]``
+        -- the caller (``_loss_step``) has run ``ppo_adv_moments_masked_ws`` on the same ``valid``."""
         t = self._t
         L = ppo_capi.lib()
         D, A, H = self.spec.ob_dim, self.spec.ac_dim, self.spec.nlstm
@@ -189,9 +198,15 @@ class LstmPPOModel(Learner):
         dvalue = t.empty(rows, dtype=f32, device=dev)
         dls = t.empty((rows, A), dtype=f32, device=dev)
         self.stats.zero_()
-        ppo_capi.chk(L.ppo_lstm_head_grad(net, lat.data_ptr(), rows, Ac.data_ptr(), Ad.data_ptr(), R.data_ptr(), Old.data_ptr(), W.data_ptr(),
-                                          1.0 / (rows * world), float(cliprange), self.vf_coef, dlat.data_ptr(), dmean.data_ptr(), dvalue.data_ptr(),
-                                          dls.data_ptr(), self.stats.data_ptr(), st))
+        if valid is None:
+            ppo_capi.chk(L.ppo_lstm_head_grad(net, lat.data_ptr(), rows, Ac.data_ptr(), Ad.data_ptr(), R.data_ptr(), Old.data_ptr(), W.data_ptr(),
+                                              1.0 / (rows * world), float(cliprange), self.vf_coef, dlat.data_ptr(), dmean.data_ptr(), dvalue.data_ptr(),
+                                              dls.data_ptr(), self.stats.data_ptr(), st))
+        else:
+            Vd = tm(valid)
+            ppo_capi.chk(L.ppo_lstm_head_grad_masked(net, lat.data_ptr(), rows, Ac.data_ptr(), Ad.data_ptr(), R.data_ptr(), Old.data_ptr(),
+                                                     W.data_ptr(), Vd.data_ptr(), self.moments.data_ptr() + 16, float(cliprange), self.vf_coef,
+                                                     dlat.data_ptr(), dmean.data_ptr(), dvalue.data_ptr(), dls.data_ptr(), self.stats.data_ptr(), st))
         if seq:
             ppo_capi.chk(L.ppo_lstm_seq_backward(net, T, n, dlat.data_ptr(), Mk.data_ptr(), gates.data_ptr(), cprev.data_ptr(), tanhc.data_ptr(),
                                                  dz.data_ptr(), st))
@@ -219,13 +234,22 @@ class LstmPPOModel(Learner):
             g[7].copy_(dvalue.sum().view(1))
         return state
 
-    def _loss_step(self, cliprange, obs, ret, val, masks, actions, neglogpacs, IS_weight, states, T, world):
-        """Advantage normalisation (model.py:180-185) + loss_and_grads: everything of a minibatch step before the optimiser."""
+    def _loss_step(self, cliprange, obs, ret, val, masks, actions, neglogpacs, IS_weight, states, T, world, valid=None):
+        """Advantage normalisation (model.py:180-185) + loss_and_grads: everything of a minibatch step before the optimiser.
+        ``valid``: the masked entries (moments and normalisation over the valid rows, 0 elsewhere; single-GPU)."""
         t = self._t
         L = ppo_capi.lib()
         nrow = ret.numel()
         st = t.cuda.current_stream(self.device).cuda_stream
         adv = t.empty(nrow, dtype=t.float32, device=self.device)
+        if valid is not None:
+            if self.comm is not None:
+                raise NotImplementedError("a row mask (opponent-data reuse for recurrent learners) is single-GPU")
+            vd = self._dev(valid).to(t.float32).contiguous()
+            ppo_capi.chk(L.ppo_adv_moments_masked_ws(ret.data_ptr(), val.data_ptr(), vd.data_ptr(), nrow, self.moments.data_ptr(), self.adv_ws.data_ptr(), st))
+            ppo_capi.chk(L.ppo_adv_normalize_masked(ret.data_ptr(), val.data_ptr(), vd.data_ptr(), nrow, self.moments.data_ptr(), adv.data_ptr(), st))
+            self.loss_and_grads(cliprange, obs, ret, masks, actions, adv, neglogpacs, IS_weight, states, T, world=world, valid=vd)
+            return
         ppo_capi.chk(L.ppo_adv_moments_ws(ret.data_ptr(), val.data_ptr(), None, nrow, self.moments.data_ptr(), self.adv_ws.data_ptr(), st))
         sdist.allreduce_moments(self.moments, self.comm)                                # global advantage normalisation
         ppo_capi.chk(L.ppo_adv_normalize(ret.data_ptr(), val.data_ptr(), None, nrow, self.moments.data_ptr(), adv.data_ptr(), st))
@@ -234,6 +258,8 @@ class LstmPPOModel(Learner):
     def _graph_step(self, cliprange, tensors, T):
         """Replay ``_loss_step`` from a HIP graph captured once per (minibatch shape, cliprange): the inputs are copied into
         buffers owned by the graph, the 2T+12 kernel launches and GEMMs of the step then cost one launch on the host.
+        A ninth tensor is the row mask ``valid``: one more static buffer, and (through the shapes) part of the key; the number of
+        valid rows is read on the device, so one graph serves every mask.
         Returns False (after switching the graph path off) if capture is not possible here."""
         t = self._t
         key = (tuple(tuple(x.shape) for x in tensors), tuple(x.dtype for x in tensors), int(T), float(cliprange))
@@ -246,8 +272,9 @@ class LstmPPOModel(Learner):
                 return dict(static=static)
 
             def body(ent):
-                obs, returns, masks, actions, values, neglogpacs, IS_weight, states = ent["static"]
-                self._loss_step(cliprange, obs, returns.contiguous(), values.contiguous(), masks, actions, neglogpacs, IS_weight, states, T, 1)
+                obs, returns, masks, actions, values, neglogpacs, IS_weight, states = ent["static"][:8]
+                self._loss_step(cliprange, obs, returns.contiguous(), values.contiguous(), masks, actions, neglogpacs, IS_weight, states, T, 1,
+                                valid=ent["static"][8] if len(ent["static"]) > 8 else None)
             ent = self._graphs.capture(key, make_record, body, lambda: setattr(type(self), "use_graph", False))
             if ent is None:
                 return False
@@ -257,7 +284,12 @@ class LstmPPOModel(Learner):
         ent["graph"].replay()
         return True
 
-    def train(self, lr, cliprange, obs, returns, masks, actions, values, neglogpacs, rewards, IS_weight, states=None, nsteps=None):
+    def train(self, lr, cliprange, obs, returns, masks, actions, values, neglogpacs, rewards, IS_weight, states=None, nsteps=None, valid=None):
+        """``valid`` (0 / 1 per row; None: every row counts, the unmasked entries call for call): rows with 0 stay in the recurrence and
+        leave the loss, the advantage moments and the statistics, which are means over the valid rows.  A minibatch without a valid
+        row (possible when only agent-1 sequences are drawn) has a zero gradient (but for the entropy term's constant on logstd,
+        which no row carries): the optimiser still takes its step on it -- Adam's moments decay, the step counter advances -- and
+        the statistics come back as 0."""
         if not self.trainable:
             raise RuntimeError("model built with trainable=False")
         if states is None:
@@ -267,16 +299,18 @@ class LstmPPOModel(Learner):
         T = int(nsteps or self.nsteps)
         world = 1 if self.comm is None else t.distributed.get_world_size(self.comm)
         tensors = (obs, returns, masks, actions, values, neglogpacs, IS_weight, states)
+        if valid is not None:
+            tensors += (valid.to(t.float32) if t.is_tensor(valid) else valid,)
         if not (self.use_graph and self.comm is None and all(t.is_tensor(x) for x in tensors)
                 and self._graph_step(cliprange, tensors, T)):
             ret, val = self._dev(returns).contiguous(), self._dev(values).contiguous()
-            self._loss_step(cliprange, obs, ret, val, masks, actions, neglogpacs, IS_weight, states, T, world)
+            self._loss_step(cliprange, obs, ret, val, masks, actions, neglogpacs, IS_weight, states, T, world, valid=valid)
         st = t.cuda.current_stream(self.device).cuda_stream
         if self.comm is not None:            # equal shards per rank
             self._allreduce_grad_and_stats()
         entropy = float((self.views[5].double() + 0.5 * np.log(2.0 * np.pi * np.e)).sum().item())
         self._adam_step(lr, st)
         s = self.stats.cpu().numpy()
-        cnt = s[6]
+        cnt = s[6] if valid is None else max(s[6], 1.0)
         out = [s[0] / cnt, s[1] / cnt, entropy, s[3] / cnt, s[4] / cnt]
         return [np.float32(x) for x in out] + [None, None] if np_in else out + [None, None]

@@ -11,7 +11,8 @@ _LIB = None
 
 EXPORTS = ("ppo_last_error", "ppo_param_count", "ppo_forward", "ppo_forward_filtered", "ppo_lstm_step", "ppo_lstm_step_pool", "ppo_lstm_step_save", "ppo_lstm_xproj", "ppo_lstm_step_save_z", "ppo_lstm_seq_forward", "ppo_lstm_seq_backward", "ppo_lstm_head_grad", "ppo_lstm_bwd_step", "ppo_lstm_wgrad_workspace_bytes", "ppo_lstm_wgrad", "ppo_selfplay_forward", "ppo_post_step", "ppo_reward_mix", "ppo_vtrace", "ppo_adv_moments", "ppo_adv_moments_ws", "ppo_adv_moments_workspace_bytes",
            "ppo_adv_normalize", "ppo_grad_workspace_bytes", "ppo_grad", "ppo_loss_stats", "ppo_clip_adam",
-           "ppo_a2c_grad", "ppo_a2c_loss_stats", "ppo_selection_scores_workspace_bytes", "ppo_selection_scores")
+           "ppo_a2c_grad", "ppo_a2c_loss_stats", "ppo_selection_scores_workspace_bytes", "ppo_selection_scores",
+           "ppo_adv_moments_masked_ws", "ppo_adv_normalize_masked", "ppo_lstm_head_grad_masked")
 
 
 class PpoHipError(RuntimeError):
@@ -55,6 +56,7 @@ def lib():
         L.ppo_lstm_seq_forward.argtypes = [C.POINTER(LstmNet), vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
         L.ppo_lstm_seq_backward.argtypes = [C.POINTER(LstmNet), i32, i32, vp, vp, vp, vp, vp, vp, vp]
         L.ppo_lstm_head_grad.argtypes = [C.POINTER(LstmNet), vp, i32, vp, vp, vp, vp, vp, f64, f32, f32, vp, vp, vp, vp, vp, vp]
+        L.ppo_lstm_head_grad_masked.argtypes = [C.POINTER(LstmNet), vp, i32, vp, vp, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp]
         L.ppo_lstm_bwd_step.argtypes = [C.POINTER(LstmNet), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.ppo_lstm_wgrad_workspace_bytes.argtypes = [i32, i32, i32]
         L.ppo_lstm_wgrad_workspace_bytes.restype = C.c_size_t
@@ -68,6 +70,8 @@ def lib():
         L.ppo_adv_moments_workspace_bytes.argtypes = []
         L.ppo_adv_moments_workspace_bytes.restype = C.c_size_t
         L.ppo_adv_normalize.argtypes = [vp, vp, vp, i32, vp, vp, vp]
+        L.ppo_adv_moments_masked_ws.argtypes = [vp, vp, vp, i32, vp, vp, vp]
+        L.ppo_adv_normalize_masked.argtypes = [vp, vp, vp, i32, vp, vp, vp]
         L.ppo_grad_workspace_bytes.argtypes = [i32, i32]
         L.ppo_grad_workspace_bytes.restype = C.c_size_t
         L.ppo_grad.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, f64, f32, f32, f32, vp, vp, vp, vp, vp]

@@ -112,6 +112,12 @@ class Runner(AbstractEnvRunner):
         self.zoo_state = None         # device mode: agent 1's recurrent state [nenv][128] (c | h) when a zoo LSTM net plays it
         self.league_scores = None     # a league on agent 1: int64 [members][4] of the last rollout (policy_zoo.league_scores)
         self.recurrent = all(getattr(m, "recurrent", False) for m in models)
+        # opt-in (learn(network='lstm', use_opponent_data=...)): opponent-data reuse for a recurrent learner.  BPTT re-evaluates agent 1's
+        # rows along agent 1's sequence, so the learner carries a state of its own along that stream -- ``shadow_state`` -- and the
+        # rollout records agent 1's value and neglogp from it (one evaluation) instead of the value from the opponent's state and the
+        # neglogp from a zero state.  Everything else of the rollout is untouched.  Set before the first ``run``.
+        self.reuse_opponent = False
+        self.shadow_state = self.shadow_state0 = None
         self.device_mode = hasattr(env, "step_device") and (self.recurrent or all(
             hasattr(m, "act_model") and hasattr(m.act_model, "evaluate") for m in models))
         self.device = getattr(env, "device", None) or device or torch.device("cuda", 0)
@@ -131,6 +137,8 @@ class Runner(AbstractEnvRunner):
             # a zoo LSTM opponent (installed after construction, opponent_mode='fix') acts from these rows on either path; they
             # persist across run() calls and across the K-step launches of one rollout
             self.zoo_state = torch.zeros((self.nenv, 128), dtype=torch.float32, device=self.device)
+            if self.recurrent:    # [nenv, 2 nlstm], persists across run() calls like ``states`` (read only with ``reuse_opponent``)
+                self.shadow_state = torch.zeros_like(self.states[0])
         else:
             self.obs = np.zeros((self.nenv, len(env.observation_space)) + ob_shape,
                                 dtype=models[0].train_model.X.dtype.name)
@@ -258,7 +266,7 @@ class Runner(AbstractEnvRunner):
                 launch(g, ro)
         self.obs, self.dones = env.obs_dev, env.done_dev
 
-    def _steps_fused_lstm(self, B, s0, K, alpha):
+    def _steps_fused_lstm(self, B, s0, K, alpha, reuse=False):
         """``_steps_fused`` for recurrent policies: one ``sumo_rollout_steps_lstm`` launch per env group; the recurrent states
         ``self.states`` are advanced in place.  Same numbers as the step-by-step recurrent branch of ``_step_group``: the noise is
         drawn step by step (``_draw_steps``), as that branch consumes the generators."""
@@ -275,9 +283,17 @@ class Runner(AbstractEnvRunner):
             else:
                 ro.opponents_dev, ro.tile_net_dev, ro.npool = m1.net_dev().data_ptr(), None, 1
             ro.state0, ro.state1 = self.states[0][sl].data_ptr(), self.states[1][sl].data_ptr()
+            if reuse:
+                ro.state2 = self.shadow_state[sl].data_ptr()
 
-        self._fused_groups(B, s0, K, alpha, capi.RolloutLstm, lambda n: (self._draw_steps(m0.gen, T, n, A), self._draw_steps(m1.gen, T, n, A)),
-                           fill, self.env.rollout_steps_lstm_group)
+        self._fused_groups(B, s0, K, alpha, capi.RolloutLstmReuse if reuse else capi.RolloutLstm,
+                           lambda n: (self._draw_steps(m0.gen, T, n, A), self._draw_steps(m1.gen, T, n, A)), fill,
+                           self.env.rollout_steps_lstm_reuse_group if reuse else self.env.rollout_steps_lstm_group)
+
+    def _steps_fused_lstm_reuse(self, B, s0, K, alpha):
+        """``_steps_fused_lstm`` under ``reuse_opponent``: one ``sumo_rollout_steps_lstm_reuse`` launch per env group, which also
+        advances ``self.shadow_state`` in place.  Same numbers as the step-by-step branch of ``_step_group``, bit for bit."""
+        self._steps_fused_lstm(B, s0, K, alpha, reuse=True)
 
     def fused_ok(self):
         """The fused rollout launch applies to device mode with two plain MLP policies of the env's own observation / action shape."""
@@ -674,8 +690,14 @@ class Runner(AbstractEnvRunner):
             a1, _, S1, on1 = m1.step(o1, S=self.states[1][sl], M=dn[:, 1], **pk, **nk1)
             self.states[1][sl] = S1
             act1.copy_(a1); B["onlp"][1, s, sl].copy_(on1)
-            B["val"][1, s, sl].copy_(m0.value(o1, S=S1, M=dn[:, 1]))
-            B["nlp"][1, s, sl].copy_(m0.act_model.action_probability(o1, given_action=a1))
+            if self.reuse_opponent:
+                # ONE learner evaluation on agent 1's row from the shadow state: its value, its neglogp of a1, the new shadow rows
+                v1, n1, S2 = m0.score_value_advance(o1, self.shadow_state[sl], dn[:, 1], a1)
+                self.shadow_state[sl] = S2
+                B["val"][1, s, sl].copy_(v1); B["nlp"][1, s, sl].copy_(n1)
+            else:
+                B["val"][1, s, sl].copy_(m0.value(o1, S=S1, M=dn[:, 1]))
+                B["nlp"][1, s, sl].copy_(m0.act_model.action_probability(o1, given_action=a1))
         elif self.zoo_opponent() is not None:
             # opt-in fix mode, step by step: the noise rows the fused launch (``_steps_fused_zoo`` / ``_steps_fused_zoo_lstm``) would read
             key = ("noise", sl.start)
@@ -778,6 +800,11 @@ class Runner(AbstractEnvRunner):
         B = self._alloc_device(T)
         alpha = anneal_alpha(update, self.anneal_bound)
         states0 = self.states[0].clone() if self.recurrent else None     # BPTT starts from the rollout's initial state
+        reuse = self.reuse_opponent and self.recurrent and not self._lstm_vs_zoo()
+        if self.reuse_opponent and not reuse:
+            raise NotImplementedError("reuse_opponent: recurrent self-play only (no policy-zoo opponent)")
+        if reuse:
+            self.shadow_state0 = self.shadow_state.clone()               # ... and agent 1's sequences from the shadow state's
         if self._gstreams is not None:                                   # the group streams see the parameter update that preceded this rollout
             cur = t.cuda.current_stream(self.device)
             for st in self._gstreams:
@@ -790,7 +817,7 @@ class Runner(AbstractEnvRunner):
             elif self.fused_lstm_zoo_ok():
                 steps = self._steps_fused_lstm_zoo
             elif self.recurrent:
-                steps = self._steps_fused_lstm
+                steps = self._steps_fused_lstm_reuse if reuse else self._steps_fused_lstm
             elif self.fused_zoo_ok():
                 steps = self._steps_fused_zoo_lstm if getattr(self.zoo_opponent(), "recurrent", False) else self._steps_fused_zoo
             chunk = self.rollout_chunk if self.rollout_chunk > 0 else T
@@ -810,7 +837,8 @@ class Runner(AbstractEnvRunner):
             last_values[1].copy_(self.models[0].value(self.obs[:, 1, :]))
         elif self.recurrent:
             for g in range(2):
-                last_values[g].copy_(self.models[0].value(self.obs[:, g, :], S=self.states[g], M=self.dones[:, g]))
+                Sg = self.shadow_state if (reuse and g == 1) else self.states[g]
+                last_values[g].copy_(self.models[0].value(self.obs[:, g, :], S=Sg, M=self.dones[:, g]))
         else:
             learner.evaluate(self.obs[:, 0, :], ppo_capi.FWD_VF, out=dict(value=last_values[0]))   # runner.py:184: always models[0]
             learner.evaluate(self.obs[:, 1, :], ppo_capi.FWD_VF, out=dict(value=last_values[1]))

@@ -160,6 +160,11 @@ class SumoVecEnv(VecEnv):
         """The same for recurrent policies (``capi.Engine.rollout_steps_lstm``, ``ro`` a ``capi.RolloutLstm``)."""
         self.engines[g].rollout_steps_lstm(ro, *self.env_ptrs(g), stream=self._stream())
 
+    def rollout_steps_lstm_reuse_group(self, g, ro):
+        """The recurrent launch under opponent-data reuse (``capi.Engine.rollout_steps_lstm_reuse``, ``ro`` a
+        ``capi.RolloutLstmReuse``)."""
+        self.engines[g].rollout_steps_lstm_reuse(ro, *self.env_ptrs(g), stream=self._stream())
+
     def rollout_steps_zoo_group(self, g, ro, zoo):
         """The same against policy-zoo MLP nets (``capi.Engine.rollout_steps_zoo``, ``zoo`` a ``capi.ZooMlp``)."""
         self.engines[g].rollout_steps_zoo(ro, zoo, *self.env_ptrs(g), stream=self._stream())

@@ -13,19 +13,16 @@ import re
 import shutil
 import subprocess
 import sys
-import tempfile
 
-LLVM = "/opt/rocm/lib/llvm/bin"
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from robosumo_selfplay_amd.codegen_check import LLVM, code_objects  # noqa: E402
+
 FIELDS = (".vgpr_count", ".sgpr_count", ".sgpr_spill_count", ".vgpr_spill_count", ".private_segment_fixed_size")
 
 
 def table(lib):
-    d = tempfile.mkdtemp()
-    fat, co = os.path.join(d, "fat.bin"), os.path.join(d, "dev.co")
-    subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib, fat])
-    subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fat,
-                           "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
-    notes = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", co], text=True)
+    # every code object of the library: build.py links sumo_engine.hip from several translation units, each with its own
+    notes = "\n".join(subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", co], text=True) for co in code_objects(lib))
     out, cur = {}, {}
     for ln in notes.splitlines():
         m = re.match(r"\s*(?:- )?(\.[a-z_]+):\s*(.*)$", ln)

@@ -5,12 +5,24 @@ Two modes, same arithmetic (csrc/ppo_kernels.hip: reward curriculum, IS ratios, 
     dones never leave HBM between the env step kernel and the policy kernels; ``run`` returns CUDA tensors.
   * host mode    -- any duck-typed VecEnv / models like the reference's: numpy per step (their API), then the collected
     buffers go through the same kernels; ``run`` returns numpy arrays (this is what the golden-vector tests drive).
+
+Device mode is the product of two axes -- who the learner is (an MLP(64,64) ``PolicyWithValue`` or an ``LstmPPOModel``) and who
+plays agent 1 (the other self-play net or a pool of its snapshots, one policy-zoo net, a league of them).  ``Runner.rollout_mode``
+resolves the pair once per call into a :class:`RolloutMode`; the fused driver (``_launch_steps``), the step-by-step evaluator
+(``_evaluate_step``) and the noise draw (``_noise_rows``) are each written once against the two sides.
 """
+import ctypes as C
+import functools
 import os
+from collections import namedtuple
 
 import numpy as np
 
-from . import ppo_capi
+from . import capi, ppo_capi
+from .lstm_model import LstmPPOModel
+from .opponent_pool import LstmOpponentPool
+from .policies import PolicyWithValue
+from .policy_zoo import FixedOpponentModel, ZooLeague, ZooLSTMPolicy, ZooLstmTable, ZooMLPPolicy, ZooTable, league_scores
 
 
 def sf01(arr):
@@ -70,6 +82,51 @@ class _nullctx(object):
 
     def __exit__(self, *a):
         return False
+
+
+# ---- the rollout mode: (learner, who plays agent 1) ---------------------------------------------------------------------------
+Launch = namedtuple("Launch", "entry struct selector family")
+RolloutMode = namedtuple("RolloutMode", "learner opponent zoo reuse noise_rows fused entry launch one_launch")
+RolloutMode.__doc__ = """What a device-mode rollout plays, resolved from the runner's state by ``Runner.rollout_mode``.
+
+``learner``: 'mlp' or 'lstm'.  ``opponent``: 'self' (the other self-play net, or a pool of snapshots), 'zoo' (one policy-zoo net) or
+'league'.  ``zoo``: the ``ZooMLPPolicy`` / ``ZooLSTMPolicy`` / ``ZooLeague`` on agent 1, else None.  ``reuse``: recurrent
+opponent-data reuse.  ``noise_rows``: the action noise is drawn per group for the whole buffer (``Runner._noise_rows``), the rows a
+fused launch reads; otherwise every net draws per step from its own generator.  ``fused``: a fused launch applies, and ``entry`` is
+its ``SumoVecEnv`` method (else None).  ``launch``: the pair's :func:`rollout_launch`, whether it applies or not.  ``one_launch``:
+the step-by-step path evaluates both nets in one ``ppo_selfplay_forward`` (MLP self-play of the env's shape)."""
+
+REUSE_REFUSED = "reuse_opponent: recurrent self-play only (no policy-zoo opponent)"
+
+
+def rollout_launch(learner, opponent, family=None, reuse=False):
+    """The fused launch of a (learner, opponent) pair -- the engine's ``sumo_rollout_steps[_lstm][_zoo|_zoo_lstm|_zoo_league|_reuse]``;
+    needs no GPU, env or model.  ``learner``: 'mlp' / 'lstm'; ``opponent``: 'self' / 'zoo' / 'league'; ``family``: 'mlp' / 'lstm' for a
+    zoo net, the composition (nmlp, nlstm) for a league (of one family: that family's launch with its index array filled).
+    Returns ``Launch(entry, struct, selector, family)``: the ``SumoVecEnv`` method (``sumo_`` + the name without ``_group`` is the
+    library's symbol), the ``capi`` launch struct, the struct's field that selects agent 1's net -- ``opponent_index`` per env,
+    ``tile_net_dev`` per 16-env tile; None for a mixed league, whose own struct carries the per-tile entries -- and the family
+    ('mlp' / 'lstm' / 'league'; None in self-play).  None where the pair has no launch; reuse against a zoo net or a league raises."""
+    if reuse and opponent != "self":
+        raise NotImplementedError(REUSE_REFUSED)
+    if reuse and learner != "lstm":
+        return None
+    lstm = learner == "lstm"
+    if opponent == "self":
+        family, suffix = None, "_reuse" if reuse else ""
+    else:
+        if not isinstance(family, str):
+            nmlp, nlstm = family
+            family = "league" if nmlp and nlstm else "lstm" if nlstm else "mlp"
+        suffix = {"mlp": "_zoo", "lstm": "_zoo_lstm", "league": "_zoo_league"}[family]
+    return Launch("rollout_steps" + ("_lstm" if lstm else "") + suffix + "_group",
+                  ("RolloutLstmReuse" if reuse else "RolloutLstm") if lstm else "Rollout",
+                  None if family == "league" else "tile_net_dev" if lstm else "opponent_index", family)
+
+
+def _self_play(learner, reuse=False):
+    la = rollout_launch(learner, "self", None, reuse)
+    return RolloutMode(learner, "self", None, reuse, True, True, la.entry, la, False)
 
 
 class AbstractEnvRunner(object):
@@ -163,6 +220,118 @@ class Runner(AbstractEnvRunner):
     def run(self, update):
         return self._run_device(update) if self.device_mode else self._run_host(update)
 
+    # ---- device mode: which rollout this is ---------------------------------------------------------------------
+    def rollout_mode(self):
+        """The :class:`RolloutMode` of the runner's state now -- ``models[1]`` is swapped after construction (a fixed opponent, an LSTM
+        pool) and the opt-ins are set afterwards, so nothing here is cached.  No side effects."""
+        env, (m0, m1), lstm = self.env, self.models, self.recurrent
+        learner = "lstm" if lstm else "mlp"
+        fixed = isinstance(m1, FixedOpponentModel)
+        zoo = m1.act_model if fixed else None
+        if not fixed:
+            opponent, family = "self", None
+        elif self.device_mode and type(zoo) is ZooLeague:
+            opponent, family = "league", (zoo.nmlp, zoo.nlstm)
+        else:
+            opponent, family = "zoo", "lstm" if getattr(zoo, "recurrent", False) else "mlp"
+        reuse = bool(self.reuse_opponent and lstm and not fixed)
+        la = rollout_launch(learner, opponent, family, reuse)
+        if not self.device_mode:
+            return RolloutMode(learner, opponent, zoo, reuse, False, False, None, la, False)
+        # the learner's net as the launches are built for it ...
+        if lstm:
+            sp = m0.spec if type(m0) is LstmPPOModel and m0.spec.nlstm == 128 else None
+        else:
+            a0 = getattr(m0, "act_model", None)
+            sp = a0.spec if type(a0) is PolicyWithValue else None
+        # ... and what plays agent 1: its kind, where it may stand, the widths it reads
+        grid = lambda: not any(env._gs(g).start % 16 or env._gs(g).stop % 16 for g in range(getattr(env, "groups", 1)))
+        if opponent == "self":
+            a1 = m1 if lstm else getattr(m1, "act_model", None)
+            if lstm:    # an LSTM pool is indexed per 16-env tile of the runner's own envs
+                ok = (type(m1) in (LstmPPOModel, LstmOpponentPool) and m1.spec.nlstm == 128
+                      and (type(m1) is LstmPPOModel or (m1.num_envs == self.nenv and grid())))
+            else:
+                ok = type(a1) is PolicyWithValue
+            ob1, ac1 = (a1.spec.ob_dim, a1.spec.ac_dim) if ok else (None, None)
+        else:
+            if opponent == "league":    # dealt over this env set, per tile
+                ok = zoo.num_envs == self.nenv and grid()
+            else:                       # the recurrent learner's launches index the table per tile, the MLP learner's per env
+                ok = type(zoo) in (ZooMLPPolicy, ZooLSTMPolicy) and (family == "mlp" or zoo.emb == zoo.hidden == 64) and (not lstm or grid())
+            ok = ok and self.opponent_pool is None
+            ob1, ac1 = (zoo.ob_dim, zoo.ac_dim) if ok else (None, None)
+        # fits: the nets and their shapes; applies: the launch can play them (with cfrc_mode 'rne_post' a second launch per step fills
+        # the force entries); the opt-in is asked of zoo opponents only
+        fits = bool(sp is not None and ok and sp.ob_dim == self.ob_dim
+                    and (ob1 == self.ob_dim if opponent == "self" else ob1 <= self.ob_dim)
+                    and sp.ac_dim == ac1 == env.act_dev.shape[2] and env.obs_dev.stride(2) == 1)
+        applies = fits and getattr(env, "cfrc_mode", "zero") == "zero" and hasattr(env, la.entry)
+        optin = opponent == "self" or bool(self.fused_fix_opponent)
+        fused = bool(applies and optin and self.fused_rollout)
+        one_launch = fits and not lstm and opponent == "self"
+        if opponent == "league":
+            noise_rows = True
+        elif opponent == "zoo":
+            noise_rows = applies and optin
+        else:
+            noise_rows = bool(getattr(m0, "accepts_noise", False) and getattr(m1, "accepts_noise", False)) if lstm else one_launch
+        return RolloutMode(learner, opponent, zoo, reuse, noise_rows, fused, la.entry if fused else None, la, one_launch)
+
+    def fused_ok(self):
+        """The fused rollout launch applies to device mode with two plain MLP policies of the env's own observation / action shape."""
+        m = self.rollout_mode()
+        return m.fused and (m.learner, m.opponent) == ("mlp", "self")
+
+    def fused_lstm_ok(self):
+        """The fused recurrent launch (``sumo_rollout_steps_lstm``) applies to device mode with the nets ``learn(network='lstm')``
+        trains on both sides -- an ``LstmPPOModel`` learner against an ``LstmPPOModel`` or an ``LstmOpponentPool`` -- with
+        nlstm = 128 and the env's own observation / action shape."""
+        m = self.rollout_mode()
+        return m.fused and (m.learner, m.opponent) == ("lstm", "self")
+
+    def zoo_opponent(self):
+        """The ``ZooMLPPolicy`` or ``ZooLSTMPolicy`` behind ``models[1]`` when the run opted into the fused fix-mode rollout
+        (``fused_fix_opponent``) and the launch applies -- device mode, a plain MLP learner of the env's shape, a zoo net of either
+        family (an LSTM net: embedding and cell of 64), cfrc_mode 'zero', no opponent pool -- else None.  ``fused_rollout`` is not
+        asked: with it off the step-by-step path plays the noise rows the launch would read."""
+        m = self.rollout_mode()
+        return m.zoo if (m.learner, m.opponent, m.noise_rows) == ("mlp", "zoo", True) else None
+
+    def lstm_zoo_opponent(self):
+        """:meth:`zoo_opponent` for a recurrent learner: an ``LstmPPOModel`` with nlstm = 128 of the env's shape, and env groups that
+        start and end on multiples of 16 (the launch indexes the table per 16-env tile)."""
+        m = self.rollout_mode()
+        return m.zoo if (m.learner, m.opponent, m.noise_rows) == ("lstm", "zoo", True) else None
+
+    def league_opponent(self):
+        """The :class:`policy_zoo.ZooLeague` behind ``models[1]`` (device mode), else None.  A league always plays on noise rows
+        drawn for the whole buffer -- one stream per generator, the learner's and the league's -- with or without the opt-in."""
+        m = self.rollout_mode()
+        return m.zoo if m.opponent == "league" else None
+
+    def fused_zoo_ok(self):
+        """The fused launch against a policy-zoo net (``sumo_rollout_steps_zoo`` / ``sumo_rollout_steps_zoo_lstm``) applies: see
+        :meth:`zoo_opponent`."""
+        return self.fused_rollout and self.zoo_opponent() is not None
+
+    def fused_lstm_zoo_ok(self):
+        """The fused launch of a recurrent learner against a policy-zoo net (``sumo_rollout_steps_lstm_zoo`` /
+        ``sumo_rollout_steps_lstm_zoo_lstm``) applies: see :meth:`lstm_zoo_opponent`."""
+        return self.fused_rollout and self.lstm_zoo_opponent() is not None
+
+    def fused_league_ok(self):
+        """The league plays inside the fused launches: the opt-in (``fused_fix_opponent``), ``fused_rollout``, cfrc_mode 'zero', no
+        opponent pool, a plain MLP learner or an ``LstmPPOModel`` with nlstm = 128 of the env's shape, the league dealt over this
+        env set, env groups that start and end on multiples of 16.  Otherwise the step-by-step path plays the same noise rows."""
+        m = self.rollout_mode()
+        return m.fused and m.opponent == "league"
+
+    def fused_steps(self, mode=None):
+        """The bound ``steps(B, s0, K, alpha)`` of the current mode's fused launch, or None when no fused launch applies."""
+        mode = mode or self.rollout_mode()
+        return functools.partial(self._launch_steps, mode) if mode.fused else None
+
     # ---- device mode ------------------------------------------------------------------------------------------
     def _alloc_device(self, T):
         """Rollout buffers [agent, time, env, ...] in HBM."""
@@ -183,26 +352,21 @@ class Runner(AbstractEnvRunner):
         B["scratch_b"] = t.empty((N, A), dtype=f32, device=dev)
         return B
 
-    def _step_device(self, B, s, alpha, env_events=None):
+    def _step_device(self, B, s, alpha, env_events=None, mode=None):
         """One rollout step (runner.py:62-151): 4 fused policy launches (the reference's 5 evaluations), env step, reward mix.
         With env groups (``SumoVecEnv(groups=G)``) every group runs this sequence on its own stream: a group's next step only
         waits for that group's envs, not for the slowest env of the whole batch (``join_groups`` before reading the buffers)."""
-        t = self._t
-        G = getattr(self.env, "groups", 1)
-        if G == 1:
-            self._step_group(B, s, alpha, None, slice(0, self.nenv), env_events)
+        mode = mode or self.rollout_mode()
+        streams = self._group_streams()
+        if streams is None:
+            self._step_group(B, s, alpha, None, slice(0, self.nenv), env_events, mode)
             return
-        if self._gstreams is None:
-            cur = t.cuda.current_stream(self.device)
-            self._gstreams = [t.cuda.Stream(device=self.device) for _ in range(G)]
-            self._gsides = [None] * G
-            for st in self._gstreams:
-                st.wait_stream(cur)
-        for g in range(G):
-            with t.cuda.stream(self._gstreams[g]):
-                self._step_group(B, s, alpha, g, self.env._gs(g), env_events if g == 0 else None)
+        for g, st in enumerate(streams):
+            with self._t.cuda.stream(st):
+                self._step_group(B, s, alpha, g, self.env._gs(g), env_events if g == 0 else None, mode)
 
     def _group_streams(self):
+        """One stream per env group (None without groups), created at the first use."""
         t = self._t
         G = getattr(self.env, "groups", 1)
         if G > 1 and self._gstreams is None:
@@ -213,6 +377,13 @@ class Runner(AbstractEnvRunner):
                 st.wait_stream(cur)
         return self._gstreams
 
+    def join_groups(self):
+        """Make the current stream wait for every env group's stream (no-op without groups)."""
+        if self._gstreams is not None:
+            cur = self._t.cuda.current_stream(self.device)
+            for st in self._gstreams:
+                cur.wait_stream(st)
+
     def _draw_steps(self, gen, T, n, A):
         """Action noise [T, n, A] as T consecutive [n, A] draws of ``gen``: what ``step`` would draw call by call (so a one-group
         device rollout consumes the generator exactly like the reference-order host rollout)."""
@@ -222,498 +393,108 @@ class Runner(AbstractEnvRunner):
             t.randn((n, A), generator=gen, device=self.device, dtype=t.float32, out=buf[k])
         return buf
 
-    def fused_lstm_ok(self):
-        """The fused recurrent launch (``sumo_rollout_steps_lstm``) applies to device mode with the nets ``learn(network='lstm')``
-        trains on both sides -- an ``LstmPPOModel`` learner against an ``LstmPPOModel`` or an ``LstmOpponentPool`` -- with
-        nlstm = 128 and the env's own observation / action shape."""
-        from .lstm_model import LstmPPOModel
-        from .opponent_pool import LstmOpponentPool
-        env = self.env
-        if not (self.device_mode and self.fused_rollout and self.recurrent and hasattr(env, "rollout_steps_lstm_group")):
-            return False
-        if getattr(env, "cfrc_mode", "zero") != "zero":      # the force entries are filled in by a second launch per step
-            return False
-        m0, m1 = self.models[0], self.models[1]
-        if type(m0) is not LstmPPOModel or type(m1) not in (LstmPPOModel, LstmOpponentPool):
-            return False
-        sp0, sp1 = m0.spec, m1.spec
-        if isinstance(m1, LstmOpponentPool) and (m1.num_envs != self.nenv or any((env._gs(g).start % 16 or env._gs(g).stop % 16)
-                                                                                 for g in range(getattr(env, "groups", 1)))):
-            return False
-        return (sp0.nlstm == sp1.nlstm == 128 and sp0.ob_dim == sp1.ob_dim == self.ob_dim and sp0.ac_dim == sp1.ac_dim
-                and env.act_dev.shape[2] == sp0.ac_dim and env.obs_dev.stride(2) == 1)
+    def _noise_rows(self, B, s, sl, mode):
+        """The action noise pair ([T, n, A] for agent 0, for agent 1) of the group of envs ``sl`` for the whole buffer, drawn when the
+        group's first step is written and kept in ``B``: what the fused launch reads and the step-by-step path plays row by row.
+        The learner's rows as its family draws them -- MLP: one call on its generator; LSTM: ``_draw_steps`` -- and agent 1's
+        likewise in self-play, in one call on the zoo net's / the league's generator otherwise."""
+        key = ("noise", sl.start)
+        if s == 0 or key not in B:
+            t, (m0, m1) = self._t, self.models
+            T, n, A = B["T"], sl.stop - sl.start, B["A"]
+            once = lambda gen: t.randn((T, n, A), generator=gen, device=self.device, dtype=t.float32)
+            own = (lambda m: self._draw_steps(m.gen, T, n, A)) if mode.learner == "lstm" else (lambda m: once(m.act_model.gen))
+            B[key] = (own(m0), own(m1) if mode.zoo is None else once(mode.zoo.gen))
+        return B[key]
 
-    def _fused_groups(self, B, s0, K, alpha, ro_type, draw, fill, launch):
-        """The per-group loop of the fused rollouts.  On group g's stream: the group's noise pair, drawn by ``draw(n)`` for the
-        whole buffer when its first step is written and cached as ``B[("noise", first env)]``; a ``ro_type`` launch struct whose
-        own fields ``fill(ro, sl)`` sets and whose shared fields (window, noise, rollout buffers) are set here; ``launch(g, ro)``."""
-        t, env = self._t, self.env
+    # ---- the fused launches -----------------------------------------------------------------------------------
+    def _opponent_side(self, mode):
+        """Agent 1's part of a fused launch: (parameter pointer, selector tensor or None, npool, extra) -- the selector per env for an
+        MLP learner and per 16-env tile for a recurrent one; ``extra(sl)`` the struct that follows the launch struct (a zoo table's,
+        with the group's state rows where LSTM nets play) or None.  A single zoo net sits in a cached one-row table."""
+        lstm, zoo, fam, m1 = mode.learner == "lstm", mode.zoo, mode.launch.family, self.models[1]
+        if zoo is None and lstm:
+            if hasattr(m1, "tile_net"):
+                return m1._nets_dev.data_ptr(), m1.tile_net, m1.capacity, None
+            return m1.net_dev().data_ptr(), None, 1, None
+        if zoo is None:
+            pool = self.opponent_pool
+            if pool is not None:
+                return pool.params.data_ptr(), pool.index, pool.capacity, None
+            return m1.act_model.params.data_ptr(), None, 1, None
+        if mode.opponent == "league":
+            table = zoo if fam == "league" else zoo.lstm_table if fam == "lstm" else zoo.mlp_table
+            sel = None if fam == "league" else zoo.tile_entry if lstm else zoo.env_entry
+            npool, state = len(zoo.members), zoo.state
+        else:
+            if self._zoo_table is None or self._zoo_table[0] is not zoo:
+                self._zoo_table = (zoo, (ZooLstmTable if fam == "lstm" else ZooTable)([zoo], zoo.ac_dim, self.device))
+            table = self._zoo_table[1]
+            sel, npool, state = None, table.capacity, self.zoo_state
+        if fam == "mlp":
+            zs = table.struct()
+            return None, sel, npool, lambda sl: zs
+        return None, sel, npool, lambda sl: table.struct(state[sl])
+
+    def _launch_steps(self, mode, B, s0, K, alpha):
+        """Rollout steps s0 .. s0+K-1 of every env group, one launch of ``mode.launch`` per group on the group's stream: the five
+        evaluations of runner.py:62-96, env.step, the reward curriculum and the appends to ``B`` all happen inside the env engine;
+        the recurrent states (``states``, ``shadow_state``, ``zoo_state`` / the league's) are advanced in place.  The launch reads
+        the group's ``_noise_rows`` -- the draws of the step-by-step path, hence the same rollout bit for bit."""
+        t, env, la, m0 = self._t, self.env, mode.launch, self.models[0]
+        lstm = mode.learner == "lstm"
+        ro_type, entry = getattr(capi, la.struct), getattr(env, la.entry)
+        params, sel, npool, extra = self._opponent_side(mode)
         G = getattr(env, "groups", 1)
         streams = self._group_streams() if G > 1 else [None]
         for g in range(G):
             sl = env._gs(g)
-            ctx = t.cuda.stream(streams[g]) if streams[g] is not None else _nullctx()
-            with ctx:
-                key = ("noise", sl.start)
-                if s0 == 0 or key not in B:
-                    B[key] = draw(sl.stop - sl.start)
+            with (t.cuda.stream(streams[g]) if streams[g] is not None else _nullctx()):
+                noise = self._noise_rows(B, s0, sl, mode)
                 ro = ro_type()
-                fill(ro, sl)
+                if lstm:
+                    ro.learner, ro.opponents_dev, ro.state0 = C.addressof(m0._net), params, self.states[0][sl].data_ptr()
+                    if mode.opponent == "self":
+                        ro.state1 = self.states[1][sl].data_ptr()
+                    if mode.reuse:
+                        ro.state2 = self.shadow_state[sl].data_ptr()
+                    if sel is not None:
+                        ro.tile_net_dev = sel.data_ptr()
+                else:
+                    pi = m0.act_model
+                    ro.learner_params, ro.opponent_params, ro.ob_dim, ro.ac_dim = pi.params.data_ptr(), params, pi.spec.ob_dim, pi.spec.ac_dim
+                    if sel is not None:
+                        ro.opponent_index = sel[sl].data_ptr()
+                ro.npool = npool
                 ro.T, ro.Ntot, ro.env_offset, ro.s0, ro.K, ro.alpha = B["T"], self.nenv, sl.start, int(s0), int(K), float(alpha)
-                ro.noise0, ro.noise1 = B[key][0].data_ptr(), B[key][1].data_ptr()
+                ro.noise0, ro.noise1 = noise[0].data_ptr(), noise[1].data_ptr()
                 for f in ("obs", "act", "rew", "val", "nlp", "onlp", "done", "ep_done", "ep_r", "ep_l"):
                     setattr(ro, f, B[f].data_ptr())
-                launch(g, ro)
+                entry(g, ro) if extra is None else entry(g, ro, extra(sl))
         self.obs, self.dones = env.obs_dev, env.done_dev
 
-    def _steps_fused_lstm(self, B, s0, K, alpha, reuse=False):
-        """``_steps_fused`` for recurrent policies: one ``sumo_rollout_steps_lstm`` launch per env group; the recurrent states
-        ``self.states`` are advanced in place.  Same numbers as the step-by-step recurrent branch of ``_step_group``: the noise is
-        drawn step by step (``_draw_steps``), as that branch consumes the generators."""
-        import ctypes as C
-        from . import capi
-        from .opponent_pool import LstmOpponentPool
-        m0, m1 = self.models
-        A, T = m0.spec.ac_dim, B["T"]
-
-        def fill(ro, sl):
-            ro.learner = C.addressof(m0._net)
-            if isinstance(m1, LstmOpponentPool):
-                ro.opponents_dev, ro.tile_net_dev, ro.npool = m1._nets_dev.data_ptr(), m1.tile_net.data_ptr(), m1.capacity
-            else:
-                ro.opponents_dev, ro.tile_net_dev, ro.npool = m1.net_dev().data_ptr(), None, 1
-            ro.state0, ro.state1 = self.states[0][sl].data_ptr(), self.states[1][sl].data_ptr()
-            if reuse:
-                ro.state2 = self.shadow_state[sl].data_ptr()
-
-        self._fused_groups(B, s0, K, alpha, capi.RolloutLstmReuse if reuse else capi.RolloutLstm,
-                           lambda n: (self._draw_steps(m0.gen, T, n, A), self._draw_steps(m1.gen, T, n, A)), fill,
-                           self.env.rollout_steps_lstm_reuse_group if reuse else self.env.rollout_steps_lstm_group)
-
-    def _steps_fused_lstm_reuse(self, B, s0, K, alpha):
-        """``_steps_fused_lstm`` under ``reuse_opponent``: one ``sumo_rollout_steps_lstm_reuse`` launch per env group, which also
-        advances ``self.shadow_state`` in place.  Same numbers as the step-by-step branch of ``_step_group``, bit for bit."""
-        self._steps_fused_lstm(B, s0, K, alpha, reuse=True)
-
-    def fused_ok(self):
-        """The fused rollout launch applies to device mode with two plain MLP policies of the env's own observation / action shape."""
-        if not (self.device_mode and self.fused_rollout and not self.recurrent and hasattr(self.env, "rollout_steps_group")):
-            return False
-        if getattr(self.env, "cfrc_mode", "zero") != "zero":
-            return False
-        m0, m1 = self.models[0], self.models[1]
-        if not (hasattr(m0, "act_model") and hasattr(m1, "act_model")):
-            return False
-        return self._fused_ok(m0.act_model, m1.act_model)
-
     def _steps_fused(self, B, s0, K, alpha):
-        """Rollout steps s0 .. s0+K-1 of every env group, one launch per group (``sumo_rollout_steps``): the five evaluations of
-        runner.py:62-96, env.step, the reward curriculum and the appends to ``B`` all happen inside the env engine.  Noise comes
-        from each acting model's own generator, drawn per group for the whole buffer when its first step is written -- the same
-        draws as the step-by-step path, hence the same rollout bit for bit."""
-        from . import capi
-        t = self._t
-        learner, opp = self.models[0].act_model, self.models[1].act_model
-        pool = self.opponent_pool
-        D, A, T = learner.spec.ob_dim, learner.spec.ac_dim, B["T"]
+        """``_launch_steps`` of MLP self-play (``sumo_rollout_steps``; an ``opponent_pool`` plays through its per-env index)."""
+        self._launch_steps(_self_play("mlp"), B, s0, K, alpha)
 
-        def draw(n):   # one call per generator for the whole buffer, as the step-by-step MLP path draws
-            return (t.randn((T, n, A), generator=learner.gen, device=self.device, dtype=t.float32),
-                    t.randn((T, n, A), generator=opp.gen, device=self.device, dtype=t.float32))
+    def _steps_fused_lstm(self, B, s0, K, alpha, reuse=False):
+        """``_launch_steps`` of recurrent self-play (``sumo_rollout_steps_lstm``; ``reuse``: ``sumo_rollout_steps_lstm_reuse``)."""
+        self._launch_steps(_self_play("lstm", reuse), B, s0, K, alpha)
 
-        def fill(ro, sl):
-            ro.learner_params = learner.params.data_ptr()
-            if pool is None:
-                ro.opponent_params, ro.opponent_index, ro.npool = opp.params.data_ptr(), None, 1
-            else:
-                ro.opponent_params, ro.opponent_index, ro.npool = pool.params.data_ptr(), pool.index[sl].data_ptr(), pool.capacity
-            ro.ob_dim, ro.ac_dim = D, A
-
-        self._fused_groups(B, s0, K, alpha, capi.Rollout, draw, fill, self.env.rollout_steps_group)
-
-    def zoo_opponent(self):
-        """The ``ZooMLPPolicy`` or ``ZooLSTMPolicy`` behind ``models[1]`` when the run opted into the fused fix-mode rollout
-        (``fused_fix_opponent``) and the launch applies -- device mode, a plain MLP learner of the env's shape, a zoo net of either
-        family (an LSTM net: embedding and cell of 64), cfrc_mode 'zero', no opponent pool -- else None."""
-        env = self.env
-        if not (self.fused_fix_opponent and self.device_mode and not self.recurrent and hasattr(env, "rollout_steps_zoo_group")):
-            return None
-        from .policies import PolicyWithValue
-        from .policy_zoo import FixedOpponentModel, ZooLSTMPolicy, ZooMLPPolicy
-        if getattr(env, "cfrc_mode", "zero") != "zero" or self.opponent_pool is not None:
-            return None
-        m0, m1 = self.models[0], self.models[1]
-        if not isinstance(m1, FixedOpponentModel) or type(m1.act_model) not in (ZooMLPPolicy, ZooLSTMPolicy) or not hasattr(m0, "act_model"):
-            return None
-        learner, zoo = m0.act_model, m1.act_model
-        if type(zoo) is ZooLSTMPolicy and not (zoo.emb == zoo.hidden == 64 and hasattr(env, "rollout_steps_zoo_lstm_group")):
-            return None
-        if not (type(learner) is PolicyWithValue and learner.spec.ob_dim == self.ob_dim and zoo.ob_dim <= self.ob_dim
-                and learner.spec.ac_dim == zoo.ac_dim == env.act_dev.shape[2] and env.obs_dev.stride(2) == 1):
-            return None
-        return zoo
-
-    def fused_zoo_ok(self):
-        """The fused launch against a policy-zoo net (``sumo_rollout_steps_zoo`` / ``sumo_rollout_steps_zoo_lstm``) applies: see
-        :meth:`zoo_opponent`."""
-        return self.fused_rollout and self.zoo_opponent() is not None
-
-    def _draw_zoo(self, B, n, learner, zoo):
-        """A group's noise pair for the whole buffer: one call per generator, as the MLP self-play path draws."""
-        t = self._t
-        A, T = learner.spec.ac_dim, B["T"]
-        return (t.randn((T, n, A), generator=learner.gen, device=self.device, dtype=t.float32),
-                t.randn((T, n, A), generator=zoo.gen, device=self.device, dtype=t.float32))
-
-    def _steps_fused_zoo(self, B, s0, K, alpha):
-        """``_steps_fused`` against a policy-zoo MLP net: one ``sumo_rollout_steps_zoo`` launch per env group.  The zoo net sits in a
-        one-row :class:`policy_zoo.ZooTable`; same numbers as the step-by-step launches under the opt-in (``_policy_evals`` with the
-        same noise rows), bit for bit."""
-        from . import capi
-        from .policy_zoo import ZooTable
-        learner, zoo = self.models[0].act_model, self.zoo_opponent()
-        if self._zoo_table is None or self._zoo_table[0] is not zoo:
-            self._zoo_table = (zoo, ZooTable([zoo], zoo.ac_dim, self.device))
-        table = self._zoo_table[1]
-        zs = table.struct()
-        D, A = learner.spec.ob_dim, learner.spec.ac_dim
-
-        def fill(ro, sl):
-            ro.learner_params = learner.params.data_ptr()
-            ro.opponent_params, ro.opponent_index, ro.npool = None, None, table.capacity
-            ro.ob_dim, ro.ac_dim = D, A
-
-        self._fused_groups(B, s0, K, alpha, capi.Rollout, lambda n: self._draw_zoo(B, n, learner, zoo), fill,
-                           lambda g, ro: self.env.rollout_steps_zoo_group(g, ro, zs))
-
-    def _steps_fused_zoo_lstm(self, B, s0, K, alpha):
-        """``_steps_fused_zoo`` against a policy-zoo LSTM net: one ``sumo_rollout_steps_zoo_lstm`` launch per env group.  The net
-        sits in a one-row :class:`policy_zoo.ZooLstmTable`; agent 1's state rows ``self.zoo_state`` are advanced in place.  Same
-        numbers as the step-by-step launches under the opt-in (``_zoo_lstm_evals`` with the same noise rows), bit for bit."""
-        from . import capi
-        from .policy_zoo import ZooLstmTable
-        learner, zoo = self.models[0].act_model, self.zoo_opponent()
-        if self._zoo_table is None or self._zoo_table[0] is not zoo:
-            self._zoo_table = (zoo, ZooLstmTable([zoo], zoo.ac_dim, self.device))
-        table = self._zoo_table[1]
-        D, A = learner.spec.ob_dim, learner.spec.ac_dim
-
-        def fill(ro, sl):
-            ro.learner_params = learner.params.data_ptr()
-            ro.opponent_params, ro.opponent_index, ro.npool = None, None, table.capacity
-            ro.ob_dim, ro.ac_dim = D, A
-
-        self._fused_groups(B, s0, K, alpha, capi.Rollout, lambda n: self._draw_zoo(B, n, learner, zoo), fill,
-                           lambda g, ro: self.env.rollout_steps_zoo_lstm_group(g, ro, table.struct(self.zoo_state[self.env._gs(g)])))
-
-    def _zoo_lstm_evals(self, B, s, learner, zoo, o0, o1, dn, sl, nk0=None, nk1=None):
-        """The step's evaluations against a zoo LSTM net, step by step: the learner acts on agent 0 and the zoo net scores that
-        action from a zero state; the zoo net acts on agent 1 from its rows of ``self.zoo_state`` (masked by agent 1's done flags
-        of the previous step, advanced in place) and the learner scores and values that action.  ``nk0`` / ``nk1`` as in
-        ``_policy_evals``."""
-        PI, VF = ppo_capi.FWD_PI, ppo_capi.FWD_VF
-        act0, act1 = B["act"][0, s, sl], B["act"][1, s, sl]
-        learner.evaluate(o0, PI | VF, out=dict(action=act0, neglogp=B["nlp"][0, s, sl], value=B["val"][0, s, sl]), **(nk0 or {}))
-        zoo.evaluate(o0, given_action=act0, out=dict(neglogp=B["onlp"][0, s, sl], action=B["scratch_a"][sl]))
-        zoo.evaluate(o1, state=self.zoo_state[sl], mask=dn[:, 1], out=dict(action=act1, neglogp=B["onlp"][1, s, sl]), **(nk1 or {}))
-        learner.evaluate(o1, PI | VF, given_action=act1, out=dict(neglogp=B["nlp"][1, s, sl], value=B["val"][1, s, sl], action=B["scratch_b"][sl]))
-
-    # ---- a recurrent learner against a policy-zoo net (learn(network='lstm', opponent_mode='fix')) ----------------------------
-    def _lstm_vs_zoo(self):
-        """``models[1]`` is a fixed policy-zoo opponent of a recurrent learner (``recurrent`` is computed at construction, before
-        ``install_fixed_opponent`` swaps the second model)."""
-        from .policy_zoo import FixedOpponentModel
-        return self.recurrent and isinstance(self.models[1], FixedOpponentModel)
-
-    def lstm_zoo_opponent(self):
-        """:meth:`zoo_opponent` for a recurrent learner: the ``ZooMLPPolicy`` or ``ZooLSTMPolicy`` behind ``models[1]`` when the run
-        opted into the fused fix-mode rollout (``fused_fix_opponent``) and the launch applies -- device mode, cfrc_mode 'zero', an
-        ``LstmPPOModel`` learner with nlstm = 128 of the env's shape, a zoo net of either family (an LSTM net: embedding and cell
-        of 64), env groups that start and end on multiples of 16 (the launch indexes the table per 16-env tile) -- else None."""
-        env = self.env
-        if not (self.fused_fix_opponent and self.device_mode and self._lstm_vs_zoo() and hasattr(env, "rollout_steps_lstm_zoo_group")):
-            return None
-        from .lstm_model import LstmPPOModel
-        from .policy_zoo import ZooLSTMPolicy, ZooMLPPolicy
-        if getattr(env, "cfrc_mode", "zero") != "zero" or self.opponent_pool is not None:
-            return None
-        m0, zoo = self.models[0], self.models[1].act_model
-        if type(m0) is not LstmPPOModel or type(zoo) not in (ZooMLPPolicy, ZooLSTMPolicy):
-            return None
-        if type(zoo) is ZooLSTMPolicy and not (zoo.emb == zoo.hidden == 64 and hasattr(env, "rollout_steps_lstm_zoo_lstm_group")):
-            return None
-        if any((env._gs(g).start % 16 or env._gs(g).stop % 16) for g in range(getattr(env, "groups", 1))):
-            return None
-        sp = m0.spec
-        if not (sp.nlstm == 128 and sp.ob_dim == self.ob_dim and zoo.ob_dim <= self.ob_dim
-                and sp.ac_dim == zoo.ac_dim == env.act_dev.shape[2] and env.obs_dev.stride(2) == 1):
-            return None
-        return zoo
-
-    def fused_lstm_zoo_ok(self):
-        """The fused launch of a recurrent learner against a policy-zoo net (``sumo_rollout_steps_lstm_zoo`` /
-        ``sumo_rollout_steps_lstm_zoo_lstm``) applies: see :meth:`lstm_zoo_opponent`."""
-        return self.fused_rollout and self.lstm_zoo_opponent() is not None
-
-    def _draw_lstm_zoo(self, B, n, m0, zoo):
-        """A group's noise pair for the whole buffer under the opt-in: the learner's rows step by step (``_draw_steps``, as the
-        recurrent self-play path draws), the zoo net's in one call (as ``_draw_zoo`` draws)."""
-        t = self._t
-        A, T = m0.spec.ac_dim, B["T"]
-        return (self._draw_steps(m0.gen, T, n, A), t.randn((T, n, A), generator=zoo.gen, device=self.device, dtype=t.float32))
-
-    def _steps_fused_lstm_zoo(self, B, s0, K, alpha):
-        """``_steps_fused_lstm`` against a policy-zoo net: one ``sumo_rollout_steps_lstm_zoo`` (MLP net) or
-        ``sumo_rollout_steps_lstm_zoo_lstm`` (LSTM net) launch per env group.  The net sits in a cached one-row
-        :class:`policy_zoo.ZooTable` / :class:`policy_zoo.ZooLstmTable`; ``self.states[0]`` and, for an LSTM net, ``self.zoo_state``
-        are advanced in place.  Same numbers as ``_lstm_zoo_evals`` on the same noise rows, bit for bit."""
-        import ctypes as C
-        from . import capi
-        from .policy_zoo import ZooLstmTable, ZooTable
-        m0, zoo = self.models[0], self.lstm_zoo_opponent()
-        rec = getattr(zoo, "recurrent", False)
-        if self._zoo_table is None or self._zoo_table[0] is not zoo:
-            self._zoo_table = (zoo, (ZooLstmTable if rec else ZooTable)([zoo], zoo.ac_dim, self.device))
-        table = self._zoo_table[1]
-        env = self.env
-
-        def fill(ro, sl):
-            ro.learner = C.addressof(m0._net)
-            ro.opponents_dev, ro.tile_net_dev, ro.npool = None, None, table.capacity
-            ro.state0, ro.state1 = self.states[0][sl].data_ptr(), None
-
-        if rec:
-            launch = lambda g, ro: env.rollout_steps_lstm_zoo_lstm_group(g, ro, table.struct(self.zoo_state[env._gs(g)]))
-        else:
-            zs = table.struct()
-            launch = lambda g, ro: env.rollout_steps_lstm_zoo_group(g, ro, zs)
-        self._fused_groups(B, s0, K, alpha, capi.RolloutLstm, lambda n: self._draw_lstm_zoo(B, n, m0, zoo), fill, launch)
-
-    def _lstm_zoo_evals(self, B, s, m0, zoo, o0, o1, dn, sl, nk0=None, nk1=None):
-        """The step's four evaluations of a recurrent learner against a zoo net, step by step: the learner acts on agent 0 from its
-        rows of ``self.states[0]`` (masked by agent 0's done flags of the previous step, advanced); the zoo net scores that action
-        (an LSTM net: from a zero state); the zoo net acts on agent 1 (an LSTM net: from its rows of ``self.zoo_state``, masked by
-        agent 1's done flags, advanced in place); the learner scores AND values that action in one evaluation from a zero state --
-        a zoo net's state is not the learner's, so the self-play rule (value from agent 1's new state) has nothing to feed.
-        ``self.states[1]`` is neither read nor advanced.  ``nk0`` / ``nk1`` as in ``_policy_evals``."""
-        act0, act1 = B["act"][0, s, sl], B["act"][1, s, sl]
-        a0, v0, S0, n0 = m0.step(o0, S=self.states[0][sl], M=dn[:, 0], **(nk0 or {}))
-        self.states[0][sl] = S0
-        act0.copy_(a0); B["val"][0, s, sl].copy_(v0); B["nlp"][0, s, sl].copy_(n0)
-        if getattr(zoo, "recurrent", False):
-            zoo.evaluate(o0, given_action=act0, out=dict(neglogp=B["onlp"][0, s, sl], action=B["scratch_a"][sl]))
-            zoo.evaluate(o1, state=self.zoo_state[sl], mask=dn[:, 1], out=dict(action=act1, neglogp=B["onlp"][1, s, sl]), **(nk1 or {}))
-        else:
-            PI = ppo_capi.FWD_PI
-            zoo.evaluate(o0, PI, given_action=act0, out=dict(neglogp=B["onlp"][0, s, sl], action=B["scratch_a"][sl]))
-            zoo.evaluate(o1, PI, out=dict(action=act1, neglogp=B["onlp"][1, s, sl]), **(nk1 or {}))
-        v1, n1 = m0.score_and_value(o1, act1)
-        B["val"][1, s, sl].copy_(v1); B["nlp"][1, s, sl].copy_(n1)
-
-    # ---- a league of policy-zoo nets on agent 1 (learn(opponent_mode='fix', fix_opponent_path=[files])) -------------------------
-    def league_opponent(self):
-        """The :class:`policy_zoo.ZooLeague` behind ``models[1]`` (device mode), else None.  A league always plays on noise rows
-        drawn for the whole buffer -- one stream per generator, the learner's and the league's -- with or without the opt-in."""
-        from .policy_zoo import FixedOpponentModel, ZooLeague
-        m1 = self.models[1]
-        if self.device_mode and isinstance(m1, FixedOpponentModel) and type(m1.act_model) is ZooLeague:
-            return m1.act_model
-        return None
-
-    def fused_league_ok(self):
-        """The league plays inside the fused launches: the opt-in (``fused_fix_opponent``), ``fused_rollout``, cfrc_mode 'zero', no
-        opponent pool, a plain MLP learner or an ``LstmPPOModel`` with nlstm = 128 of the env's shape, the league dealt over this env set, env groups that start and end on multiples of 16.  A league of one
-        family goes through that family's launch with the index arrays filled, a mixed one through ``sumo_rollout_steps_zoo_league``
-        / ``sumo_rollout_steps_lstm_zoo_league``.  Otherwise the step-by-step league path plays the same noise rows."""
-        league, env = self.league_opponent(), self.env
-        if league is None or not (self.fused_fix_opponent and self.fused_rollout and hasattr(env, "rollout_steps_zoo_league_group")):
-            return False
-        if getattr(env, "cfrc_mode", "zero") != "zero" or self.opponent_pool is not None:
-            return False
-        if league.num_envs != self.nenv:
-            return False
-        if any((env._gs(g).start % 16 or env._gs(g).stop % 16) for g in range(getattr(env, "groups", 1))):
-            return False
-        m0 = self.models[0]
-        if self.recurrent:
-            from .lstm_model import LstmPPOModel
-            sp = m0.spec if type(m0) is LstmPPOModel else None
-            if sp is None or sp.nlstm != 128:
-                return False
-        else:
-            from .policies import PolicyWithValue
-            sp = m0.act_model.spec if type(getattr(m0, "act_model", None)) is PolicyWithValue else None
-            if sp is None:
-                return False
-        return (sp.ob_dim == self.ob_dim and league.ob_dim <= self.ob_dim and sp.ac_dim == league.ac_dim == env.act_dev.shape[2]
-                and env.obs_dev.stride(2) == 1)
-
-    def _draw_league(self, B, n, league):
-        """A group's noise pair for the whole buffer: the learner's rows as its opt-in single-net path draws them (``_draw_zoo`` /
-        ``_draw_lstm_zoo``), agent 1's in one call from the league's generator."""
-        if self.recurrent:
-            return self._draw_lstm_zoo(B, n, self.models[0], league)
-        return self._draw_zoo(B, n, self.models[0].act_model, league)
-
-    def _league_evals(self, B, s, learner, league, o0, o1, dn, sl, nk0, nk1):
-        """The step's evaluations of an MLP learner against a league, step by step: the learner's as in ``_policy_evals`` /
-        ``_zoo_lstm_evals``; every member acts on and scores its own tiles' rows (``ZooLeague.act`` / ``score``)."""
-        PI, VF = ppo_capi.FWD_PI, ppo_capi.FWD_VF
-        act0, act1 = B["act"][0, s, sl], B["act"][1, s, sl]
-        learner.evaluate(o0, PI | VF, out=dict(action=act0, neglogp=B["nlp"][0, s, sl], value=B["val"][0, s, sl]), **nk0)
-        league.score(o0, act0, sl.start, B["onlp"][0, s, sl])
-        league.act(o1, dn[:, 1], sl.start, nk1["noise"], act1, B["onlp"][1, s, sl])
-        learner.evaluate(o1, PI | VF, given_action=act1, out=dict(neglogp=B["nlp"][1, s, sl], value=B["val"][1, s, sl], action=B["scratch_b"][sl]))
-
-    def _lstm_league_evals(self, B, s, m0, league, o0, o1, dn, sl, nk0, nk1):
-        """The same for a recurrent learner: its two evaluations as in ``_lstm_zoo_evals`` (acts from ``self.states[0]``; scores
-        and values agent 1's action from a zero state)."""
-        act0, act1 = B["act"][0, s, sl], B["act"][1, s, sl]
-        a0, v0, S0, n0 = m0.step(o0, S=self.states[0][sl], M=dn[:, 0], **nk0)
-        self.states[0][sl] = S0
-        act0.copy_(a0); B["val"][0, s, sl].copy_(v0); B["nlp"][0, s, sl].copy_(n0)
-        league.score(o0, act0, sl.start, B["onlp"][0, s, sl])
-        league.act(o1, dn[:, 1], sl.start, nk1["noise"], act1, B["onlp"][1, s, sl])
-        v1, n1 = m0.score_and_value(o1, act1)
-        B["val"][1, s, sl].copy_(v1); B["nlp"][1, s, sl].copy_(n1)
-
-    def _steps_fused_league(self, B, s0, K, alpha):
-        """``_steps_fused_zoo`` against a league, MLP learner: one launch per env group -- ``sumo_rollout_steps_zoo_league`` for a
-        mixed league, ``sumo_rollout_steps_zoo`` / ``sumo_rollout_steps_zoo_lstm`` with the per-env ``opponent_index`` for a league
-        of one family.  Same numbers as ``_league_evals`` on the same noise rows, bit for bit."""
-        from . import capi
-        learner, league, env = self.models[0].act_model, self.league_opponent(), self.env
-        D, A = learner.spec.ob_dim, learner.spec.ac_dim
-        mixed = league.nmlp > 0 and league.nlstm > 0
-
-        def fill(ro, sl):
-            ro.learner_params = learner.params.data_ptr()
-            ro.opponent_params, ro.npool = None, len(league.members)
-            ro.opponent_index = None if mixed else league.env_entry[sl].data_ptr()
-            ro.ob_dim, ro.ac_dim = D, A
-
-        if mixed:
-            launch = lambda g, ro: env.rollout_steps_zoo_league_group(g, ro, league.struct(league.state[env._gs(g)]))
-        elif league.nlstm:
-            launch = lambda g, ro: env.rollout_steps_zoo_lstm_group(g, ro, league.lstm_table.struct(league.state[env._gs(g)]))
-        else:
-            zs = league.mlp_table.struct()
-            launch = lambda g, ro: env.rollout_steps_zoo_group(g, ro, zs)
-        self._fused_groups(B, s0, K, alpha, capi.Rollout, lambda n: self._draw_league(B, n, league), fill, launch)
-
-    def _steps_fused_lstm_league(self, B, s0, K, alpha):
-        """``_steps_fused_lstm_zoo`` against a league: ``sumo_rollout_steps_lstm_zoo_league`` for a mixed league,
-        ``sumo_rollout_steps_lstm_zoo`` / ``sumo_rollout_steps_lstm_zoo_lstm`` with ``tile_net_dev`` for a league of one family.
-        Same numbers as ``_lstm_league_evals`` on the same noise rows, bit for bit."""
-        import ctypes as C
-        from . import capi
-        m0, league, env = self.models[0], self.league_opponent(), self.env
-        mixed = league.nmlp > 0 and league.nlstm > 0
-
-        def fill(ro, sl):
-            ro.learner = C.addressof(m0._net)
-            ro.opponents_dev, ro.npool = None, len(league.members)
-            ro.tile_net_dev = None if mixed else league.tile_entry.data_ptr()
-            ro.state0, ro.state1 = self.states[0][sl].data_ptr(), None
-
-        if mixed:
-            launch = lambda g, ro: env.rollout_steps_lstm_zoo_league_group(g, ro, league.struct(league.state[env._gs(g)]))
-        elif league.nlstm:
-            launch = lambda g, ro: env.rollout_steps_lstm_zoo_lstm_group(g, ro, league.lstm_table.struct(league.state[env._gs(g)]))
-        else:
-            zs = league.mlp_table.struct()
-            launch = lambda g, ro: env.rollout_steps_lstm_zoo_group(g, ro, zs)
-        self._fused_groups(B, s0, K, alpha, capi.RolloutLstm, lambda n: self._draw_league(B, n, league), fill, launch)
-
-    def join_groups(self):
-        """Make the current stream wait for every env group's stream (no-op without groups)."""
-        if self._gstreams is not None:
-            cur = self._t.cuda.current_stream(self.device)
-            for st in self._gstreams:
-                cur.wait_stream(st)
-
-    def _step_group(self, B, s, alpha, g, sl, env_events):
+    # ---- the step-by-step launches ----------------------------------------------------------------------------
+    def _step_group(self, B, s, alpha, g, sl, env_events, mode):
         t = self._t
         env = self.env
         n = sl.stop - sl.start
-        learner, opp = self.models[0].act_model, self.models[1].act_model
         ob, dn = env.obs_dev[sl], env.done_dev[sl]                      # [n, 2, D] / [n, 2]: the env's own buffers
-        fused = self._fused_ok(learner, opp)
-        if fused:
-            self._selfplay_forward(B, s, learner, opp, ob, dn, sl)      # records obs / dones, evaluates, fills env.act_dev
+        noise = self._noise_rows(B, s, sl, mode) if mode.noise_rows else None
+        act = env.act_dev
+        if mode.one_launch:                                             # records obs / dones, evaluates, fills env.act_dev
+            self._selfplay_forward(B, s, self.models[0].act_model, self.models[1].act_model, ob, dn, sl, noise)
         else:
             B["obs"][:, s, sl].copy_(ob.permute(1, 0, 2))               # one strided copy per array instead of one per agent
             B["done"][:, s, sl].copy_(dn.t())
-        o0, o1 = B["obs"][0, s, sl], B["obs"][1, s, sl]
-        act0, act1 = B["act"][0, s, sl], B["act"][1, s, sl]
-        league = self.league_opponent()
-        if fused:
-            pass
-        elif league is not None:
-            # a league of zoo nets: the noise rows the fused launches (``_steps_fused_league`` / ``_steps_fused_lstm_league``) would
-            # read, drawn for the whole buffer at the group's first step
-            key = ("noise", sl.start)
-            if s == 0 or key not in B:
-                B[key] = self._draw_league(B, n, league)
-            nk0, nk1 = dict(noise=B[key][0][s]), dict(noise=B[key][1][s])
-            if self.recurrent:
-                self._lstm_league_evals(B, s, self.models[0], league, o0, o1, dn, sl, nk0, nk1)
-            else:
-                self._league_evals(B, s, learner, league, o0, o1, dn, sl, nk0, nk1)
-        elif self._lstm_vs_zoo():
-            # a recurrent learner in fix mode.  Under the opt-in: the noise rows the fused launch (``_steps_fused_lstm_zoo``) would
-            # read, drawn for the whole buffer at the group's first step; otherwise each net draws per step from its own generator
-            nk0 = nk1 = None
-            if self.lstm_zoo_opponent() is not None:
-                key = ("noise", sl.start)
-                if s == 0 or key not in B:
-                    B[key] = self._draw_lstm_zoo(B, n, self.models[0], opp)
-                nk0, nk1 = dict(noise=B[key][0][s]), dict(noise=B[key][1][s])
-            self._lstm_zoo_evals(B, s, self.models[0], opp, o0, o1, dn, sl, nk0, nk1)
-        elif self.recurrent:
-            # same five evaluations through the recurrent nets (runner.py:62-96 with the S / M feeds): each stream carries its
-            # acting model's state; the scoring calls without a state feed start from zeros, as the reference's calls do
-            m0, m1 = self.models
-            nk0, nk1 = {}, {}
-            if getattr(m0, "accepts_noise", False) and getattr(m1, "accepts_noise", False):
-                # action noise of this group for the whole buffer, drawn at its first step from each acting model's generator
-                # (as the MLP path does): the fused recurrent launch consumes the same draws
-                key = ("noise", sl.start)
-                if s == 0 or key not in B:
-                    B[key] = (self._draw_steps(m0.gen, B["T"], n, act0.shape[-1]), self._draw_steps(m1.gen, B["T"], n, act0.shape[-1]))
-                nk0, nk1 = dict(noise=B[key][0][s]), dict(noise=B[key][1][s])
-            a0, v0, S0, n0 = m0.step(o0, S=self.states[0][sl], M=dn[:, 0], **nk0)
-            self.states[0][sl] = S0
-            act0.copy_(a0); B["val"][0, s, sl].copy_(v0); B["nlp"][0, s, sl].copy_(n0)
-            pk = dict(first_env=sl.start) if hasattr(m1, "tile_net") else {}      # opponent pool: snapshots are indexed per env tile
-            B["onlp"][0, s, sl].copy_(m1.act_model.action_probability(o0, given_action=a0, **pk))
-            a1, _, S1, on1 = m1.step(o1, S=self.states[1][sl], M=dn[:, 1], **pk, **nk1)
-            self.states[1][sl] = S1
-            act1.copy_(a1); B["onlp"][1, s, sl].copy_(on1)
-            if self.reuse_opponent:
-                # ONE learner evaluation on agent 1's row from the shadow state: its value, its neglogp of a1, the new shadow rows
-                v1, n1, S2 = m0.score_value_advance(o1, self.shadow_state[sl], dn[:, 1], a1)
-                self.shadow_state[sl] = S2
-                B["val"][1, s, sl].copy_(v1); B["nlp"][1, s, sl].copy_(n1)
-            else:
-                B["val"][1, s, sl].copy_(m0.value(o1, S=S1, M=dn[:, 1]))
-                B["nlp"][1, s, sl].copy_(m0.act_model.action_probability(o1, given_action=a1))
-        elif self.zoo_opponent() is not None:
-            # opt-in fix mode, step by step: the noise rows the fused launch (``_steps_fused_zoo`` / ``_steps_fused_zoo_lstm``) would read
-            key = ("noise", sl.start)
-            if s == 0 or key not in B:
-                B[key] = self._draw_zoo(B, n, learner, opp)
-            if getattr(opp, "recurrent", False):
-                self._zoo_lstm_evals(B, s, learner, opp, o0, o1, dn, sl, dict(noise=B[key][0][s]), dict(noise=B[key][1][s]))
-            else:
-                self._policy_evals(B, s, learner, opp, o0, o1, sl, g, dict(noise=B[key][0][s]), dict(noise=B[key][1][s]))
-        elif getattr(opp, "recurrent", False):
-            # fix mode against a zoo LSTM net without the opt-in: each net draws its noise per step from its own generator
-            self._zoo_lstm_evals(B, s, learner, opp, o0, o1, dn, sl)
-        else:
-            self._policy_evals(B, s, learner, opp, o0, o1, sl, g)
-        act = env.act_dev
-        if not fused:
+            self._evaluate_step(B, s, g, sl, dn, mode, noise)
             act[sl].copy_(B["act"][:, s, sl].permute(1, 0, 2))
         if env_events is not None:
             env_events[0].record()
@@ -731,29 +512,66 @@ class Runner(AbstractEnvRunner):
                                                   B["ep_l"][s, sl].data_ptr(), st))
         self.obs, self.dones = env.obs_dev, env.done_dev
 
-    def _fused_ok(self, learner, opp):
-        """One-launch evaluation (``ppo_selfplay_forward``) applies when both sides are plain MLP policies of the same shape."""
-        from .policies import PolicyWithValue
-        env = self.env
-        return (not self.recurrent and type(learner) is PolicyWithValue and type(opp) is PolicyWithValue
-                and learner.spec.ob_dim == opp.spec.ob_dim == self.ob_dim and learner.spec.ac_dim == opp.spec.ac_dim
-                and env.act_dev.shape[2] == learner.spec.ac_dim and env.obs_dev.stride(2) == 1)
+    def _evaluate_step(self, B, s, g, sl, dn, mode, noise):
+        """The step's evaluations (runner.py:62-96), always in this order: the learner acts on agent 0, the opponent scores that
+        action, the opponent acts on agent 1, the learner scores and values that action -- without ``noise`` (the group's
+        ``_noise_rows``) each net draws inside these calls from its own generator.  A scoring call without a state starts from
+        zeros, as the reference's calls do; a recurrent net acts from its rows of the state it carries (``states``, ``zoo_state``,
+        the league's), masked by its agent's done flags of the previous step, and advances them."""
+        PI, VF = ppo_capi.FWD_PI, ppo_capi.FWD_VF
+        m0, m1 = self.models
+        opp, lstm = m1.act_model, mode.learner == "lstm"
+        o0, o1 = B["obs"][0, s, sl], B["obs"][1, s, sl]
+        nk0, nk1 = ({}, {}) if noise is None else (dict(noise=noise[0][s]), dict(noise=noise[1][s]))
+        zoo_lstm = mode.opponent != "league" and getattr(opp, "recurrent", False) and not (lstm and mode.opponent == "self")
+        if not lstm and not zoo_lstm and mode.opponent != "league":
+            return self._policy_evals(B, s, m0.act_model, opp, o0, o1, sl, g, nk0, nk1)
+        act0, act1 = B["act"][0, s, sl], B["act"][1, s, sl]
+        val, nlp, onlp = B["val"][:, s, sl], B["nlp"][:, s, sl], B["onlp"][:, s, sl]
+        # the learner acts on agent 0
+        if lstm:
+            a0, v0, S0, n0 = m0.step(o0, S=self.states[0][sl], M=dn[:, 0], **nk0)
+            self.states[0][sl] = S0
+            act0.copy_(a0); val[0].copy_(v0); nlp[0].copy_(n0)
+        else:
+            m0.act_model.evaluate(o0, PI | VF, out=dict(action=act0, neglogp=nlp[0], value=val[0]), **nk0)
+        # the opponent scores that action, then acts on agent 1
+        if mode.opponent == "league":
+            opp.score(o0, act0, sl.start, onlp[0])
+            opp.act(o1, dn[:, 1], sl.start, nk1["noise"], act1, onlp[1])
+        elif zoo_lstm:
+            opp.evaluate(o0, given_action=act0, out=dict(neglogp=onlp[0], action=B["scratch_a"][sl]))
+            opp.evaluate(o1, state=self.zoo_state[sl], mask=dn[:, 1], out=dict(action=act1, neglogp=onlp[1]), **nk1)
+        elif mode.opponent == "self":
+            pk = dict(first_env=sl.start) if hasattr(m1, "tile_net") else {}      # opponent pool: snapshots are indexed per env tile
+            onlp[0].copy_(opp.action_probability(o0, given_action=act0, **pk))
+            a1, _, S1, on1 = m1.step(o1, S=self.states[1][sl], M=dn[:, 1], **pk, **nk1)
+            self.states[1][sl] = S1
+            act1.copy_(a1); onlp[1].copy_(on1)
+        else:
+            opp.evaluate(o0, PI, given_action=act0, out=dict(neglogp=onlp[0], action=B["scratch_a"][sl]))
+            opp.evaluate(o1, PI, out=dict(action=act1, neglogp=onlp[1]), **nk1)
+        # the learner scores and values agent 1's action
+        if not lstm:
+            return m0.act_model.evaluate(o1, PI | VF, given_action=act1, out=dict(neglogp=nlp[1], value=val[1], action=B["scratch_b"][sl]))
+        if mode.reuse:              # ONE evaluation from the shadow state: its value, its neglogp of the action, the new shadow rows
+            v1, n1, S2 = m0.score_value_advance(o1, self.shadow_state[sl], dn[:, 1], act1)
+            self.shadow_state[sl] = S2
+        elif mode.opponent == "self":   # the value from agent 1's new state, the neglogp from a zero state
+            v1, n1 = m0.value(o1, S=S1, M=dn[:, 1]), m0.act_model.action_probability(o1, given_action=act1)
+        else:                       # a zoo net's state is not the learner's: both from a zero state, in one evaluation
+            v1, n1 = m0.score_and_value(o1, act1)
+        val[1].copy_(v1); nlp[1].copy_(n1)
 
-    def _selfplay_forward(self, B, s, learner, opp, ob, dn, sl):
+    def _selfplay_forward(self, B, s, learner, opp, ob, dn, sl, noise):
         """runner.py:62-96 in one launch: learner acts on agent 0 (opponent scores it), opponent acts on agent 1 (learner scores
         it and evaluates the value); the kernel also records the observations / done flags and writes the env's action buffer.
-        Noise comes from each acting model's own generator, as in ``PolicyWithValue.evaluate``."""
-        import ctypes as C
+        ``noise``: the group's ``_noise_rows`` -- each acting model's own generator, as in ``PolicyWithValue.evaluate``, drawn for
+        the whole buffer (two launches per rollout instead of two per step between the env steps)."""
         t = self._t
         n = sl.stop - sl.start
         D, A = learner.spec.ob_dim, learner.spec.ac_dim
-        # action noise of this group for the whole buffer, drawn at its first step (two launches per rollout instead of two per
-        # step between the env steps); each acting model's own generator, as in ``PolicyWithValue.evaluate``
-        key = ("noise", sl.start)
-        if s == 0 or key not in B:
-            B[key] = (t.randn((B["T"], n, A), generator=learner.gen, device=self.device, dtype=t.float32),
-                      t.randn((B["T"], n, A), generator=opp.gen, device=self.device, dtype=t.float32))
-        noise0, noise1 = B[key][0][s], B[key][1][s]
+        noise0, noise1 = noise[0][s], noise[1][s]
         outs = [B["obs"][0, s, sl], B["obs"][1, s, sl], B["act"][0, s, sl], B["act"][1, s, sl], B["nlp"][0, s, sl], B["nlp"][1, s, sl],
                 B["onlp"][0, s, sl], B["onlp"][1, s, sl], B["val"][0, s, sl], B["val"][1, s, sl]]
         fp = (C.c_void_p * 10)(*[x.data_ptr() for x in outs])
@@ -799,27 +617,19 @@ class Runner(AbstractEnvRunner):
         T, N = self.nsteps, self.nenv
         B = self._alloc_device(T)
         alpha = anneal_alpha(update, self.anneal_bound)
-        states0 = self.states[0].clone() if self.recurrent else None     # BPTT starts from the rollout's initial state
-        reuse = self.reuse_opponent and self.recurrent and not self._lstm_vs_zoo()
-        if self.reuse_opponent and not reuse:
-            raise NotImplementedError("reuse_opponent: recurrent self-play only (no policy-zoo opponent)")
-        if reuse:
+        mode = self.rollout_mode()
+        lstm, m0 = mode.learner == "lstm", self.models[0]
+        states0 = self.states[0].clone() if lstm else None               # BPTT starts from the rollout's initial state
+        if self.reuse_opponent and not mode.reuse:
+            raise NotImplementedError(REUSE_REFUSED)
+        if mode.reuse:
             self.shadow_state0 = self.shadow_state.clone()               # ... and agent 1's sequences from the shadow state's
         if self._gstreams is not None:                                   # the group streams see the parameter update that preceded this rollout
             cur = t.cuda.current_stream(self.device)
             for st in self._gstreams:
                 st.wait_stream(cur)
-        fused = self.fused_ok() or self.fused_lstm_ok() or self.fused_zoo_ok() or self.fused_lstm_zoo_ok() or self.fused_league_ok()
-        if fused:
-            steps = self._steps_fused
-            if self.fused_league_ok():
-                steps = self._steps_fused_lstm_league if self.recurrent else self._steps_fused_league
-            elif self.fused_lstm_zoo_ok():
-                steps = self._steps_fused_lstm_zoo
-            elif self.recurrent:
-                steps = self._steps_fused_lstm_reuse if reuse else self._steps_fused_lstm
-            elif self.fused_zoo_ok():
-                steps = self._steps_fused_zoo_lstm if getattr(self.zoo_opponent(), "recurrent", False) else self._steps_fused_zoo
+        steps = self.fused_steps(mode)
+        if steps is not None:
             chunk = self.rollout_chunk if self.rollout_chunk > 0 else T
             for s0 in range(0, T, chunk):
                 steps(B, s0, min(chunk, T - s0), alpha)
@@ -827,36 +637,32 @@ class Runner(AbstractEnvRunner):
             if self.opponent_pool is not None:
                 raise NotImplementedError("a per-env opponent pool needs the fused rollout path (MLP policies, SUMO_FUSED_ROLLOUT != 0)")
             for s in range(T):
-                self._step_device(B, s, alpha)
+                self._step_device(B, s, alpha, mode=mode)
         self.join_groups()
-        learner = self.models[0].act_model
         last_values = t.empty((2, N), dtype=t.float32, device=self.device)
-        if self._lstm_vs_zoo():
-            # agent 1 carries no state of the learner's (``_lstm_zoo_evals``): its last value is the learner's from a zero state
-            last_values[0].copy_(self.models[0].value(self.obs[:, 0, :], S=self.states[0], M=self.dones[:, 0]))
-            last_values[1].copy_(self.models[0].value(self.obs[:, 1, :]))
-        elif self.recurrent:
-            for g in range(2):
-                Sg = self.shadow_state if (reuse and g == 1) else self.states[g]
-                last_values[g].copy_(self.models[0].value(self.obs[:, g, :], S=Sg, M=self.dones[:, g]))
+        if not lstm:
+            m0.act_model.evaluate(self.obs[:, 0, :], ppo_capi.FWD_VF, out=dict(value=last_values[0]))   # runner.py:184: always models[0]
+            m0.act_model.evaluate(self.obs[:, 1, :], ppo_capi.FWD_VF, out=dict(value=last_values[1]))
         else:
-            learner.evaluate(self.obs[:, 0, :], ppo_capi.FWD_VF, out=dict(value=last_values[0]))   # runner.py:184: always models[0]
-            learner.evaluate(self.obs[:, 1, :], ppo_capi.FWD_VF, out=dict(value=last_values[1]))
+            last_values[0].copy_(m0.value(self.obs[:, 0, :], S=self.states[0], M=self.dones[:, 0]))
+            if mode.opponent == "self":     # from the state the learner's values of agent 1 ran on: the opponent's, or the shadow state
+                S1 = self.shadow_state if mode.reuse else self.states[1]
+                last_values[1].copy_(m0.value(self.obs[:, 1, :], S=S1, M=self.dones[:, 1]))
+            else:                           # a zoo net carries no state of the learner's (``_evaluate_step``): from a zero state
+                last_values[1].copy_(m0.value(self.obs[:, 1, :]))
         returns, opr, oer, ratio = self._vtrace(B["rew"], B["val"], B["nlp"], B["onlp"], B["done"], self.dones.contiguous(), last_values)
         # A fused launch that was cut short (expired hand-over wait, hand-over tag / checksum mismatch) leaves unwritten rollout rows:
         # fail as loudly as a MuJoCo fault does in the reference (mujoco-py builder.py:351-369 raises out of env.step) instead of
         # training on them.  The call waits for the launch; this function synchronises right below anyway.
-        if fused:
+        if steps is not None:
             for E in self.env.engines:
                 E.rollout_status()
         # episode infos of agent 0 (monitor.py:63-78), harvested with one host sync per rollout
         d = B["ep_done"].cpu().numpy().astype(bool)
         rr, ll = B["ep_r"].cpu().numpy(), B["ep_l"].cpu().numpy()
         epinfos = EpInfoList(rr[d], ll[d])          # (step, env) order of np.nonzero, dicts built on demand
-        league = self.league_opponent()
-        if league is not None:                      # per member: episodes, learner wins, losses, draws (policy_zoo.league_scores)
-            from .policy_zoo import league_scores
-            self.league_scores = league_scores(d, rr, ll, league.tile_member, len(league.members),
+        if mode.opponent == "league":               # per member: episodes, learner wins, losses, draws (policy_zoo.league_scores)
+            self.league_scores = league_scores(d, rr, ll, mode.zoo.tile_member, len(mode.zoo.members),
                                                getattr(getattr(self.env, "model", None), "timestep_limit", 500))
         return (sf01(B["obs"]), sf01(returns), sf01(B["done"].bool()), sf01(B["act"]), sf01(B["val"]), sf01(B["nlp"]), sf01(B["rew"]),
                 sf01(B["onlp"]), sf01(B["obs"][1]), sf01(B["act"][1]), states0, epinfos, sf0(opr), sf0(oer), sf0(ratio))

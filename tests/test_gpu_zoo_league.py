@@ -1,7 +1,7 @@
 """Training against a league of policy-zoo nets, MLP and LSTM mixed (learn(opponent_mode='fix', fix_opponent_path=[files]);
 include/sumo_hip.h sumo_rollout_steps_zoo_league / sumo_rollout_steps_lstm_zoo_league) on the GPU: the fused launches against the
-step-by-step league path (Runner._league_evals / _lstm_league_evals) bit for bit, each tile against a single-net run of its member,
-leagues of one family through the existing launches' index arrays, the bad-entry status path, the refusals, learn() end to end.
+step-by-step league path (Runner._evaluate_step: ZooLeague.score / act) bit for bit, each tile against a single-net run of its
+member, leagues of one family through the existing launches' index arrays, the bad-entry status path, the refusals, learn() end to end.
 
 Every rollout: Ant-vs-Ant, 64 envs (4 tiles of 16), T = 6 steps in two launches of 3 (SUMO_ROLLOUT_CHUNK), episodes that end
 inside the window."""

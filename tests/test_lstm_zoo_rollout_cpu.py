@@ -44,6 +44,10 @@ def test_launch_struct_mirrors_are_unchanged():
 
 
 def test_runner_has_the_lstm_zoo_paths():
-    for name in ("lstm_zoo_opponent", "fused_lstm_zoo_ok", "_steps_fused_lstm_zoo", "_lstm_zoo_evals"):
+    for name in ("lstm_zoo_opponent", "fused_lstm_zoo_ok", "rollout_mode", "fused_steps", "_launch_steps", "_evaluate_step"):
         assert callable(getattr(runner.Runner, name, None)), name
+    # the pairs (LSTM learner, zoo net of either family) resolve to the two launches
+    for family, entry in zip(("mlp", "lstm"), ENTRIES):
+        la = runner.rollout_launch("lstm", "zoo", family)
+        assert (la.entry, la.struct, la.selector) == (entry[len("sumo_"):] + "_group", "RolloutLstm", "tile_net_dev")
     assert callable(getattr(lstm_model.LstmPPOModel, "score_and_value", None))

@@ -211,7 +211,10 @@ def test_bindings_list_the_new_entry_points():
     assert "sumo_rollout_steps_lstm_reuse" in capi.EXPORTS
     assert callable(getattr(capi.Engine, "rollout_steps_lstm_reuse", None))
     assert callable(getattr(vec_env.SumoVecEnv, "rollout_steps_lstm_reuse_group", None))
-    for name in ("_steps_fused_lstm_reuse",):
+    la = runner.rollout_launch("lstm", "self", None, True)      # what the Runner launches under ``reuse_opponent``
+    assert (la.entry, la.struct) == ("rollout_steps_lstm_reuse_group", "RolloutLstmReuse")
+    assert "reuse" in runner.RolloutMode._fields
+    for name in ("rollout_mode", "fused_steps", "_steps_fused_lstm"):
         assert callable(getattr(runner.Runner, name, None)), name
     assert callable(getattr(lstm_model.LstmPPOModel, "score_value_advance", None))
     build.build_all()

@@ -30,5 +30,8 @@ def test_zoo_lstm_policy_has_the_model_surface():
         for f in feeds:
             assert f in params, (name, f)
     assert P.recurrent and P.initial_state is None
-    for name in ("_steps_fused_zoo_lstm", "_zoo_lstm_evals"):
+    # the Runner's side: the pair (MLP learner, zoo LSTM net) resolves to this launch, and the one driver / evaluator play it
+    la = runner.rollout_launch("mlp", "zoo", "lstm")
+    assert (la.entry, la.struct, la.selector) == ("rollout_steps_zoo_lstm_group", "Rollout", "opponent_index")
+    for name in ("rollout_mode", "fused_steps", "_launch_steps", "_evaluate_step", "zoo_opponent", "fused_zoo_ok"):
         assert callable(getattr(runner.Runner, name, None)), name

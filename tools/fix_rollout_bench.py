@@ -82,14 +82,7 @@ def main(argv):
 
     def window(r, B, fused):
         if fused:
-            steps = r._steps_fused
-            if r.fused_league_ok():
-                steps = r._steps_fused_lstm_league if args.network == "lstm" else r._steps_fused_league
-            elif r.fused_lstm_zoo_ok():
-                steps = r._steps_fused_lstm_zoo
-            elif r.fused_zoo_ok():
-                steps = r._steps_fused_zoo_lstm if args.opponent == "zoo_lstm" else r._steps_fused_zoo
-            steps(B, 0, args.K, 0.5)
+            r.fused_steps()(B, 0, args.K, 0.5)
         else:
             for s in range(args.K):
                 r._step_device(B, s, 0.5)
@@ -98,7 +91,7 @@ def main(argv):
     rs = {f: runner() for f in paths}
     for f, r in rs.items():
         r.fused_rollout = f
-        assert (r.fused_ok() or r.fused_zoo_ok() or r.fused_lstm_zoo_ok() or r.fused_league_ok()) == f, "the fused launch does not apply"
+        assert (r.fused_steps() is not None) == f, "the fused launch does not apply"
     Bs = {f: r._alloc_device(args.K) for f, r in rs.items()}
     rates = {f: [] for f in paths}
     for rep in range(args.repeats + 1):                      # repeat 0 is the warm-up

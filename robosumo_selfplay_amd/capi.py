@@ -80,6 +80,20 @@ class ZooLeague(C.Structure):
     _fields_ = [("mlp", ZooMlp), ("lstm", ZooLstm), ("tile_entry_dev", _P)]
 
 
+# every fused launch of the C ABI: name -> (launch struct, the struct that follows it or None); their argtypes, their restype and
+# their place in EXPORTS come from here
+FUSED_ENTRIES = {
+    "sumo_rollout_steps": (Rollout, None), "sumo_rollout_steps_lstm": (RolloutLstm, None),
+    "sumo_match_steps": (Match, None), "sumo_match_steps_lstm": (MatchLstm, None),
+    "sumo_rollout_steps_zoo": (Rollout, ZooMlp), "sumo_match_steps_zoo": (Match, ZooMlp),
+    "sumo_match_steps_zoo_lstm": (Match, ZooLstm), "sumo_match_steps_lstm_zoo_lstm": (MatchLstm, ZooLstm),
+    "sumo_rollout_steps_zoo_lstm": (Rollout, ZooLstm), "sumo_rollout_steps_lstm_zoo": (RolloutLstm, ZooMlp),
+    "sumo_rollout_steps_lstm_zoo_lstm": (RolloutLstm, ZooLstm), "sumo_rollout_steps_zoo_league": (Rollout, ZooLeague),
+    "sumo_rollout_steps_lstm_zoo_league": (RolloutLstm, ZooLeague), "sumo_match_steps_cross": (MatchCross, None),
+    "sumo_match_steps_lstm_zoo": (MatchLstm, ZooMlp), "sumo_rollout_steps_lstm_reuse": (RolloutLstmReuse, None),
+}
+
+
 def lib():
     global _LIB
     if _LIB is None:
@@ -95,22 +109,9 @@ def lib():
         L.sumo_dims.argtypes = [vp, vp]
         L.sumo_reset.argtypes = [vp, vp, vp, vp, vp]
         L.sumo_step.argtypes = [vp] * 9
-        L.sumo_rollout_steps.argtypes = [vp, C.POINTER(Rollout)] + [vp] * 8
-        L.sumo_rollout_steps_lstm.argtypes = [vp, C.POINTER(RolloutLstm)] + [vp] * 8
-        L.sumo_rollout_steps_lstm_reuse.argtypes = [vp, C.POINTER(RolloutLstmReuse)] + [vp] * 8
-        L.sumo_match_steps.argtypes = [vp, C.POINTER(Match)] + [vp] * 8
-        L.sumo_match_steps_lstm.argtypes = [vp, C.POINTER(MatchLstm)] + [vp] * 8
-        L.sumo_rollout_steps_zoo.argtypes = [vp, C.POINTER(Rollout), C.POINTER(ZooMlp)] + [vp] * 8
-        L.sumo_match_steps_zoo.argtypes = [vp, C.POINTER(Match), C.POINTER(ZooMlp)] + [vp] * 8
-        L.sumo_match_steps_zoo_lstm.argtypes = [vp, C.POINTER(Match), C.POINTER(ZooLstm)] + [vp] * 8
-        L.sumo_match_steps_lstm_zoo_lstm.argtypes = [vp, C.POINTER(MatchLstm), C.POINTER(ZooLstm)] + [vp] * 8
-        L.sumo_rollout_steps_zoo_lstm.argtypes = [vp, C.POINTER(Rollout), C.POINTER(ZooLstm)] + [vp] * 8
-        L.sumo_rollout_steps_lstm_zoo.argtypes = [vp, C.POINTER(RolloutLstm), C.POINTER(ZooMlp)] + [vp] * 8
-        L.sumo_rollout_steps_lstm_zoo_lstm.argtypes = [vp, C.POINTER(RolloutLstm), C.POINTER(ZooLstm)] + [vp] * 8
-        L.sumo_rollout_steps_zoo_league.argtypes = [vp, C.POINTER(Rollout), C.POINTER(ZooLeague)] + [vp] * 8
-        L.sumo_rollout_steps_lstm_zoo_league.argtypes = [vp, C.POINTER(RolloutLstm), C.POINTER(ZooLeague)] + [vp] * 8
-        L.sumo_match_steps_cross.argtypes = [vp, C.POINTER(MatchCross)] + [vp] * 8
-        L.sumo_match_steps_lstm_zoo.argtypes = [vp, C.POINTER(MatchLstm), C.POINTER(ZooMlp)] + [vp] * 8
+        for n, (launch, second) in FUSED_ENTRIES.items():
+            getattr(L, n).argtypes = [vp] + [C.POINTER(t) for t in (launch, second) if t is not None] + [vp] * 8
+            getattr(L, n).restype = i32
         L.sumo_get_state.argtypes = [vp] * 5
         L.sumo_set_cfrc_mode.argtypes = [vp, i32]
         L.sumo_get_cfrc_ext.argtypes = [vp, vp]
@@ -128,18 +129,17 @@ def lib():
         L.sumo_static_layout.argtypes = [vp]
         L.sumo_static_layout.restype = i32
         L.sumo_profile.restype = i32
-        for n in ("sumo_create", "sumo_destroy", "sumo_dims", "sumo_reset", "sumo_step", "sumo_rollout_steps", "sumo_rollout_steps_lstm", "sumo_match_steps", "sumo_match_steps_lstm",
-                  "sumo_rollout_steps_zoo", "sumo_match_steps_zoo", "sumo_match_steps_zoo_lstm", "sumo_match_steps_lstm_zoo_lstm", "sumo_rollout_steps_zoo_lstm", "sumo_rollout_steps_lstm_zoo", "sumo_rollout_steps_lstm_zoo_lstm",
-                  "sumo_rollout_steps_zoo_league", "sumo_rollout_steps_lstm_zoo_league", "sumo_match_steps_cross", "sumo_match_steps_lstm_zoo", "sumo_rollout_steps_lstm_reuse", "sumo_get_state", "sumo_set_cfrc_mode", "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_set_state", "sumo_debug_forward", "sumo_stats"):
+        for n in ("sumo_create", "sumo_destroy", "sumo_dims", "sumo_reset", "sumo_step", "sumo_get_state", "sumo_set_cfrc_mode",
+                  "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_set_state", "sumo_debug_forward", "sumo_stats"):
             getattr(L, n).restype = i32
         _LIB = L
     return _LIB
 
 
-EXPORTS = ("sumo_last_error", "sumo_create", "sumo_destroy", "sumo_dims", "sumo_reset", "sumo_step", "sumo_rollout_steps",
-           "sumo_rollout_steps_lstm", "sumo_match_steps", "sumo_match_steps_lstm", "sumo_rollout_steps_zoo", "sumo_match_steps_zoo", "sumo_match_steps_zoo_lstm", "sumo_match_steps_lstm_zoo_lstm", "sumo_rollout_steps_zoo_lstm", "sumo_rollout_steps_lstm_zoo", "sumo_rollout_steps_lstm_zoo_lstm",
-           "sumo_rollout_steps_zoo_league", "sumo_rollout_steps_lstm_zoo_league", "sumo_match_steps_cross", "sumo_match_steps_lstm_zoo", "sumo_rollout_steps_lstm_reuse", "sumo_set_cfrc_mode", "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_get_state", "sumo_set_state", "sumo_debug_forward", "sumo_stats", "sumo_profile", "sumo_debug_trace",
-           "sumo_rollout_status", "sumo_debug_fault", "sumo_static_layout", "sumo_debug_layout", "sumo_debug_model_ints", "sumo_debug_dump")
+EXPORTS = (("sumo_last_error", "sumo_create", "sumo_destroy", "sumo_dims", "sumo_reset", "sumo_step") + tuple(FUSED_ENTRIES)
+           + ("sumo_set_cfrc_mode", "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_get_state", "sumo_set_state", "sumo_debug_forward",
+              "sumo_stats", "sumo_profile", "sumo_debug_trace", "sumo_rollout_status", "sumo_debug_fault", "sumo_static_layout",
+              "sumo_debug_layout", "sumo_debug_model_ints", "sumo_debug_dump"))
 
 
 def _np(a):
@@ -191,7 +191,6 @@ class Engine:
         """One fused launch: ``env_ptrs`` are the seven env-side pointers of :meth:`step`, in its order; ``zoo``: the
         :class:`ZooMlp` / :class:`ZooLstm` table (or :class:`ZooLeague`) the ``*_zoo`` / ``*_zoo_lstm`` / ``*_zoo_league`` entry points take after
         the launch struct."""
-        actions_ptr, obs_ptr, info_ptr, done_ptr, ep_r_ptr, ep_dr_ptr, ep_l_ptr = env_ptrs
         structs = (C.byref(launch),) if zoo is None else (C.byref(launch), C.byref(zoo))
         _chk(getattr(lib(), entry)(self.h, *structs, *env_ptrs, stream))
 

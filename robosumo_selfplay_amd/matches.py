@@ -29,13 +29,14 @@ agent 1 (:func:`play_against_zoo`, :func:`evaluate_history_against_zoo`): MLP ch
 checkpoints face zoo LSTM nets (``sumo_match_steps_zoo`` / ``sumo_match_steps_zoo_lstm`` / ``sumo_match_steps_lstm_zoo_lstm``);
 LSTM checkpoints against zoo MLP nets play with ``cross_family=True`` (``sumo_match_steps_lstm_zoo``) and are refused otherwise.
 """
+import collections
 import ctypes as C
 import os
 import warnings
 
 import numpy as np
 
-from . import policies
+from . import capi, policies
 
 EVAL_ADJUST_Z = -0.5      # compare_history_version.py:73-74
 
@@ -277,15 +278,107 @@ def _check_env(env, table):
         raise ValueError("matches run on the fused launch, which refuses cfrc_mode 'rne_post'")
 
 
-def _fused_groups(env, entry, struct, fill, idx0, idx1, score, quota, K, noise, extra=()):
-    """The per-group loop of the fused match launches: a ``struct`` (capi.Match / capi.MatchLstm) whose own fields
-    ``fill(mo, sl)`` sets and whose shared fields (indices, window, quota, noise, score) are set here, passed to the engine's
-    ``entry`` method (followed by ``extra``: the zoo table's struct, or a function of the group's env slice that returns it) with
-    the group's env-side pointers; raises if the launch was cut short (``rollout_status``)."""
+def _refuse_fused_width(nlstm):
+    """The fused match launches hold LSTM(128) checkpoints only; ``nlstm`` None: no recurrent checkpoint plays."""
+    if nlstm is not None and nlstm != 128:
+        raise ValueError("the fused match launch plays LSTM(128) policies only (got LSTM(%d)): use fused=False" % nlstm)
+
+
+# What plays one agent: ``family`` 'ckpt_mlp' (SnapshotTable), 'ckpt_lstm' (LstmSnapshotTable), 'zoo_mlp' (policy_zoo.ZooTable) or
+# 'zoo_lstm' (policy_zoo.ZooLstmTable), its ``table`` and ``width``, the columns of its recurrent state per env (c | h) or None.
+Seat = collections.namedtuple("Seat", "family table width")
+
+# Two seats resolved to their fused launch (DESIGN.md section 21): the ``capi.Engine`` method ``entry``, its launch struct, the
+# class of the struct that follows it (agent 1's zoo table) or None, the agent the LSTM table of a cross-family pairing plays
+# (else None) and the width of the LSTM checkpoints that play (else None).
+Pairing = collections.namedtuple("Pairing", "seats entry struct second lstm_side nlstm")
+
+_ENTRY = {("ckpt_mlp", "ckpt_mlp"): "match_steps", ("ckpt_lstm", "ckpt_lstm"): "match_steps_lstm",
+          ("ckpt_mlp", "zoo_mlp"): "match_steps_zoo", ("ckpt_mlp", "zoo_lstm"): "match_steps_zoo_lstm",
+          ("ckpt_lstm", "zoo_lstm"): "match_steps_lstm_zoo_lstm", ("ckpt_mlp", "ckpt_lstm"): "match_steps_cross",
+          ("ckpt_lstm", "ckpt_mlp"): "match_steps_cross", ("ckpt_lstm", "zoo_mlp"): "match_steps_lstm_zoo"}
+
+
+def _seat(table):
+    rec = bool(getattr(table, "recurrent", False))
+    if hasattr(table, "spec"):
+        return Seat("ckpt_lstm" if rec else "ckpt_mlp", table, 2 * table.spec.nlstm if rec else None)
+    return Seat("zoo_lstm" if rec else "zoo_mlp", table, 2 * table.hidden if rec else None)
+
+
+def match_pairing(table0, table1):
+    """The :class:`Pairing` of agent 0 playing rows of ``table0`` against agent 1 playing rows of ``table1``; needs no env and no
+    GPU.  Checkpoints of one family play from ONE table, zoo nets play agent 1 only; every other pair of tables is refused."""
+    s0, s1 = _seat(table0), _seat(table1)
+    if s0.family.startswith("zoo"):
+        raise ValueError("policy-zoo nets play agent 1 only: agent 0 plays a SnapshotTable or an LstmSnapshotTable")
+    if s0.family == s1.family and table0 is not table1:
+        if s0.width != s1.width:
+            raise ValueError("mixed LSTM widths are not supported (LSTM(%d) against LSTM(%d))" % (s0.width // 2, s1.width // 2))
+        raise ValueError("two tables of one family do not play each other: both agents play rows of one table (play_matches)")
+    entry = _ENTRY[s0.family, s1.family]
+    struct, second = capi.FUSED_ENTRIES["sumo_" + entry]
+    recurrent = [side for side, s in enumerate((s0, s1)) if s.family == "ckpt_lstm"]
+    return Pairing((s0, s1), entry, struct, second, recurrent[0] if struct is capi.MatchCross else None,
+                   (s0, s1)[recurrent[0]].table.spec.nlstm if recurrent else None)
+
+
+def _check_state(seat, state, N):
+    """Shape of ``state``, the recurrent state of the envs' agents that ``seat`` plays (None for an MLP seat)."""
+    if seat.width is not None and (tuple(state.shape) != (N, seat.width) or not state.is_contiguous()):
+        if seat.family == "zoo_lstm":
+            raise ValueError("the zoo nets' recurrent state must be a contiguous float32 [%d][%d] tensor (c | h)" % (N, seat.width))
+        raise ValueError("recurrent states must be two contiguous float32 [%d][%d] tensors (c | h)" % (N, seat.width))
+
+
+def pairing_steps(env, pairing, states, idx0, idx1, score, quota, K, noise=None, fused=True):
+    """K match steps of a :func:`match_pairing` on either path: what every step function below and the play drivers end in (the
+    drivers look this name up per launch).  ``states``: the pair (agent 0's recurrent state or None, agent 1's or None), float32
+    [N][seat width], read and updated in place; idx0 / idx1 are CUDA tensors (fused) or host arrays (step by step); the other
+    arguments as :func:`match_steps_fused`.  The env is checked by the callers (:func:`_check_env`)."""
+    for seat, state in zip(pairing.seats, states):
+        _check_state(seat, state, env.num_envs)
+    if fused:
+        _refuse_fused_width(pairing.nlstm)
+    (_steps_fused if fused else _steps_stepwise)(env, pairing, idx0, idx1, states, score, quota, K, noise)
+
+
+def _fill_match(mo, pairing, states, sl):
+    t = pairing.seats[0].table
+    mo.params = t.params.data_ptr()
+    mo.nsnap, mo.ob_dim, mo.ac_dim = t.capacity, t.spec.ob_dim, t.spec.ac_dim
+
+
+def _fill_match_lstm(mo, pairing, states, sl):
+    t = pairing.seats[0].table
+    mo.proto, mo.nets_dev, mo.nsnap = C.addressof(t.proto), t.nets_dev.data_ptr(), t.capacity
+    mo.state0 = states[0][sl].data_ptr()
+    if pairing.second is None:                  # agent 1 plays the same table; a zoo net's state travels in the zoo struct
+        mo.state1 = states[1][sl].data_ptr()
+
+
+def _fill_match_cross(mo, pairing, states, sl):
+    g = pairing.lstm_side
+    lt, mt = pairing.seats[g].table, pairing.seats[1 - g].table
+    mo.params = mt.params.data_ptr()
+    mo.nsnap_mlp, mo.ob_dim, mo.ac_dim = mt.capacity, mt.spec.ob_dim, mt.spec.ac_dim
+    mo.proto, mo.nets_dev, mo.nsnap_lstm = C.addressof(lt.proto), lt.nets_dev.data_ptr(), lt.capacity
+    mo.state, mo.lstm_side = states[g][sl].data_ptr(), g
+
+
+_FILL = {capi.Match: _fill_match, capi.MatchLstm: _fill_match_lstm, capi.MatchCross: _fill_match_cross}
+
+
+def _steps_fused(env, pairing, idx0, idx1, states, score, quota, K, noise):
+    """One fused match launch per env group: the pairing's launch struct, its own fields set by the filler of its class and the
+    shared ones (indices, window, quota, noise, score) here, passed to the engine's ``pairing.entry`` (followed by agent 1's zoo
+    table struct, with its state rows for zoo LSTM nets) with the group's env-side pointers; raises if the launch was cut short
+    (``rollout_status``)."""
+    zoo = pairing.seats[1]
     for g in range(env.groups):
         sl = env._gs(g)
-        mo = struct()
-        fill(mo, sl)
+        mo = pairing.struct()
+        _FILL[pairing.struct](mo, pairing, states, sl)
         mo.idx0, mo.idx1 = idx0[sl].data_ptr(), idx1[sl].data_ptr()
         mo.T, mo.s0, mo.K, mo.quota = int(K), 0, int(K), int(quota)
         keep = None
@@ -293,8 +386,11 @@ def _fused_groups(env, entry, struct, fill, idx0, idx1, score, quota, K, noise, 
             keep = [n[:, sl].contiguous() if env.groups > 1 else n for n in noise]
             mo.noise0, mo.noise1 = keep[0].data_ptr(), keep[1].data_ptr()
         mo.score = score[sl].data_ptr()
+        second = ()
+        if pairing.second is not None:
+            second = (zoo.table.struct() if zoo.width is None else zoo.table.struct(states[1][sl]),)
         E = env.engines[g]
-        getattr(E, entry)(mo, *(extra(sl) if callable(extra) else extra), *env.env_ptrs(g), stream=env._stream())
+        getattr(E, pairing.entry)(mo, *second, *env.env_ptrs(g), stream=env._stream())
         E.rollout_status()
         del keep
 
@@ -303,14 +399,8 @@ def match_steps_fused(env, table, idx0, idx1, score, quota, K, noise=None):
     """K match steps of every env in one ``sumo_match_steps`` launch per env group.  idx0 / idx1 int32 CUDA tensors [N],
     score int32 CUDA [N][3] (updated in place), noise None (deterministic) or a pair of float32 CUDA [K][N][A] tensors.  Raises
     if the launch was cut short (``rollout_status``)."""
-    from . import capi
     _check_env(env, table)
-
-    def fill(mo, sl):
-        mo.params = table.params.data_ptr()
-        mo.nsnap, mo.ob_dim, mo.ac_dim = table.capacity, table.spec.ob_dim, table.spec.ac_dim
-
-    _fused_groups(env, "match_steps", capi.Match, fill, idx0, idx1, score, quota, K, noise)
+    pairing_steps(env, match_pairing(table, table), (None, None), idx0, idx1, score, quota, K, noise, True)
 
 
 def _runs(idx):
@@ -321,17 +411,21 @@ def _runs(idx):
     return [(int(s), int(e), int(idx[s])) for s, e in zip(starts, ends)]
 
 
-def _stepwise(env, table, idx0, idx1, score, quota, K, noise, forward, masked, capacity1=None):
-    """The step-by-step loop of every kind: per step and side, ``forward(k, side, rows, noise rows or None, action rows, mask
-    rows or None)`` for every run ``rows = slice(s, e)`` of envs that share snapshot ``k``, then ``step_device`` and the score
-    update.  ``masked``: the previous step's done flags of each side are passed as float32 masks.  idx0 / idx1 are host arrays;
-    ``capacity1``: size of the table idx1 indexes where that is not ``table`` (zoo opponents)."""
+def _steps_stepwise(env, pairing, idx0, idx1, states, score, quota, K, noise):
+    """The step-by-step loop of every pairing: per step and side, that seat's ``forward(k, side, rows, noise rows or None, action
+    rows, mask rows or None)`` for every run ``rows = slice(s, e)`` of envs that share row ``k`` of its table, then ``step_device``
+    and the score update.  With a recurrent seat the previous step's done flags become float32 masks: a checkpoint LSTM is
+    masked by its own side's, a zoo LSTM net by AGENT 0's (``policy_zoo._evaluate_against`` resets the opponent on them).  idx0 /
+    idx1 are host arrays, each checked against its own seat's table."""
     import torch
+    s0, s1 = pairing.seats
     idx0, idx1 = np.asarray(idx0, np.int64), np.asarray(idx1, np.int64)
-    cap1 = table.capacity if capacity1 is None else int(capacity1)
-    if min(idx0.min(), idx1.min()) < 0 or idx0.max() >= table.capacity or idx1.max() >= cap1:
-        raise ValueError("snapshot index outside [0, %d) / [0, %d)" % (table.capacity, cap1))
-    A, N = table.spec.ac_dim, env.num_envs
+    if min(idx0.min(), idx1.min()) < 0 or idx0.max() >= s0.table.capacity or idx1.max() >= s1.table.capacity:
+        raise ValueError("snapshot index outside [0, %d) / [0, %d)" % (s0.table.capacity, s1.table.capacity))
+    A, N = s0.table.spec.ac_dim, env.num_envs
+    forward = [_FORWARD[s.family](env, s, state, A) for s, state in zip(pairing.seats, states)]
+    masked = s0.width is not None or s1.width is not None
+    mask_side = [0 if s.family == "zoo_lstm" else side for side, s in enumerate(pairing.seats)]
     acts = env.act_dev                          # the env's action buffer receives both actions, as in the fused launch
     act = [torch.empty((N, A), dtype=torch.float32, device=env.device) for _ in range(2)]
     runs = [_runs(idx0), _runs(idx1)]
@@ -340,18 +434,19 @@ def _stepwise(env, table, idx0, idx1, score, quota, K, noise, forward, masked, c
         for side in range(2):
             for s, e, k in runs[side]:
                 rows = slice(s, e)
-                forward(k, side, rows, None if noise is None else noise[side][t, rows], act[side][rows],
-                        masks[side][rows] if masked else None)
+                forward[side](k, side, rows, None if noise is None else noise[side][t, rows], act[side][rows],
+                              masks[mask_side[side]][rows] if masked else None)
             acts[:, side, :A] = act[side]
         _, info, done, _, _, _ = env.step_device(acts)
         _score_step(score, info, done, quota)
 
 
-def _mlp_side(env, table):
-    """``forward`` of :func:`_stepwise` for a side played by a :class:`SnapshotTable`: one ``ppo_forward`` launch
+def _mlp_side(env, seat, _state, _A):
+    """``forward`` of :func:`_steps_stepwise` for a side played by a :class:`SnapshotTable`: one ``ppo_forward`` launch
     (``PPOModel.step``'s kernel) on the rows' observations of that side."""
     import torch
     from . import ppo_capi
+    table = seat.table
     D, A = table.spec.ob_dim, table.spec.ac_dim
     L, st, obs = ppo_capi.lib(), env._stream(), env.obs_dev
     nlp = torch.empty(env.num_envs, dtype=torch.float32, device=env.device)
@@ -362,26 +457,28 @@ def _mlp_side(env, table):
     return forward
 
 
-def _lstm_side(env, table, state_of):
-    """The same for a side played by an :class:`LstmSnapshotTable`: one ``ppo_lstm_step`` launch (the kernel
-    ``LstmPPOModel.step`` runs) on the rows of ``state_of(side)``, masked by that side's done flags of the previous step."""
+def _lstm_side(env, seat, state, _A):
+    """The same for a side played by an :class:`LstmSnapshotTable` or a :class:`policy_zoo.ZooLstmTable` (its nets' policy branch,
+    what ``ZooLSTMPolicy.act`` runs): one ``ppo_lstm_step`` launch (the kernel ``LstmPPOModel.step`` runs) on the rows of
+    ``state``, masked by the done flags :func:`_steps_stepwise` hands over."""
     from . import ppo_capi
-    H = table.spec.nlstm
+    nets, H = seat.table.nets, seat.width // 2
     L, st, obs = ppo_capi.lib(), env._stream(), env.obs_dev
 
     def forward(k, side, rows, nz, out, mask):
-        S = state_of(side)[rows]
-        ppo_capi.chk(L.ppo_lstm_step(C.byref(table.nets[k]), obs[rows, side].data_ptr(), rows.stop - rows.start, obs.stride(0),
+        S = state[rows]
+        ppo_capi.chk(L.ppo_lstm_step(C.byref(nets[k]), obs[rows, side].data_ptr(), rows.stop - rows.start, obs.stride(0),
                                      mask.data_ptr(), S.data_ptr(), S.data_ptr() + 4 * H, 2 * H, ppo_capi.ptr(nz), None,
                                      out.data_ptr(), None, None, None, st))
     return forward
 
 
-def _zoo_mlp_side(env, zoo_table, A):
+def _zoo_mlp_side(env, seat, _state, A):
     """The same for a side played by a :class:`policy_zoo.ZooTable`: one ``ppo_forward_filtered`` launch (what
     ``ZooMLPPolicy.act`` runs)."""
     import torch
     from . import ppo_capi
+    zoo_table = seat.table
     Dz = zoo_table.ob_dim
     L, st, obs = ppo_capi.lib(), env._stream(), env.obs_dev
     nlp = torch.empty(env.num_envs, dtype=torch.float32, device=env.device)
@@ -394,41 +491,21 @@ def _zoo_mlp_side(env, zoo_table, A):
     return forward
 
 
-def _by_side(forward0, forward1):
-    """``forward`` of :func:`_stepwise` from one function per side."""
-    return lambda k, side, *rest: (forward1 if side else forward0)(k, side, *rest)
+_FORWARD = {"ckpt_mlp": _mlp_side, "ckpt_lstm": _lstm_side, "zoo_mlp": _zoo_mlp_side, "zoo_lstm": _lstm_side}
 
 
 def match_steps_stepwise(env, table, idx0, idx1, score, quota, K, noise=None):
     """The same K steps on the step-by-step path: per step and side one ``ppo_forward`` launch (``PPOModel.step``'s kernel) for
     every run of envs that share a snapshot, then ``step_device`` and the score update.  idx0 / idx1 are host arrays."""
     _check_env(env, table)
-    _stepwise(env, table, idx0, idx1, score, quota, K, noise, _mlp_side(env, table), masked=False)
-
-
-def _check_lstm(table, states, N):
-    H = table.spec.nlstm
-    for st in states:
-        if tuple(st.shape) != (N, 2 * H) or not st.is_contiguous():
-            raise ValueError("recurrent states must be two contiguous float32 [%d][%d] tensors (c | h)" % (N, 2 * H))
+    pairing_steps(env, match_pairing(table, table), (None, None), idx0, idx1, score, quota, K, noise, False)
 
 
 def match_steps_fused_lstm(env, table, idx0, idx1, states, score, quota, K, noise=None):
     """:func:`match_steps_fused` for an :class:`LstmSnapshotTable`: one ``sumo_match_steps_lstm`` launch per env group.  ``states``
     is a pair of float32 CUDA [N][2 nlstm] tensors (c | h) per agent, read and updated in place.  LSTM(128) only."""
-    from . import capi
     _check_env(env, table)
-    _check_lstm(table, states, env.num_envs)
-    if table.spec.nlstm != 128:
-        raise ValueError("the fused match launch plays LSTM(128) policies only (got LSTM(%d)): use fused=False" % table.spec.nlstm)
-
-    def fill(mo, sl):
-        mo.proto = C.addressof(table.proto)
-        mo.nets_dev = table.nets_dev.data_ptr()
-        mo.nsnap = table.capacity
-        mo.state0, mo.state1 = states[0][sl].data_ptr(), states[1][sl].data_ptr()
-
-    _fused_groups(env, "match_steps_lstm", capi.MatchLstm, fill, idx0, idx1, score, quota, K, noise)
+    pairing_steps(env, match_pairing(table, table), states, idx0, idx1, score, quota, K, noise, True)
 
 
 def match_steps_stepwise_lstm(env, table, idx0, idx1, states, score, quota, K, noise=None):
@@ -436,8 +513,7 @@ def match_steps_stepwise_lstm(env, table, idx0, idx1, states, score, quota, K, n
     ``LstmPPOModel.step`` runs) for every run of envs that share a snapshot, masked by that side's done flags of the previous step,
     then ``step_device`` and the score update.  idx0 / idx1 are host arrays; any LSTM width the step kernel is built for."""
     _check_env(env, table)
-    _check_lstm(table, states, env.num_envs)
-    _stepwise(env, table, idx0, idx1, score, quota, K, noise, _lstm_side(env, table, lambda side: states[side]), masked=True)
+    pairing_steps(env, match_pairing(table, table), states, idx0, idx1, score, quota, K, noise, False)
 
 
 def _check_zoo(env, table, zoo_table):
@@ -458,14 +534,8 @@ def zoo_match_steps_fused(env, table, zoo_table, idx0, idx1, score, quota, K, no
     """K match steps of MLP checkpoints (agent 0: row idx0[e] of ``table``) against policy-zoo MLP nets (agent 1: row idx1[e] of
     ``zoo_table``, a :class:`policy_zoo.ZooTable`) in one ``sumo_match_steps_zoo`` launch per env group; arguments as
     :func:`match_steps_fused`."""
-    from . import capi
     _check_zoo(env, table, zoo_table)
-
-    def fill(mo, sl):
-        mo.params = table.params.data_ptr()
-        mo.nsnap, mo.ob_dim, mo.ac_dim = table.capacity, table.spec.ob_dim, table.spec.ac_dim
-
-    _fused_groups(env, "match_steps_zoo", capi.Match, fill, idx0, idx1, score, quota, K, noise, extra=(zoo_table.struct(),))
+    pairing_steps(env, match_pairing(table, zoo_table), (None, None), idx0, idx1, score, quota, K, noise, True)
 
 
 def zoo_match_steps_stepwise(env, table, zoo_table, idx0, idx1, score, quota, K, noise=None):
@@ -473,23 +543,16 @@ def zoo_match_steps_stepwise(env, table, zoo_table, idx0, idx1, score, quota, K,
     ``ppo_forward_filtered`` launch (what ``ZooMLPPolicy.act`` runs) for every run that shares a zoo net, then ``step_device`` and
     the score update.  idx0 / idx1 are host arrays."""
     _check_zoo(env, table, zoo_table)
-    forward = _by_side(_mlp_side(env, table), _zoo_mlp_side(env, zoo_table, table.spec.ac_dim))
-    _stepwise(env, table, idx0, idx1, score, quota, K, noise, forward, masked=False, capacity1=zoo_table.capacity)
+    pairing_steps(env, match_pairing(table, zoo_table), (None, None), idx0, idx1, score, quota, K, noise, False)
 
 
-def _check_zoo_lstm(env, table, zoo_table, states):
-    """Checks of the zoo LSTM match steps; returns (agent 0's state or None, agent 1's state) from ``states``: agent 1's tensor
-    [N][2 * 64] for an MLP table, the pair (agent 0 [N][2 nlstm], agent 1 [N][2 * 64]) for an :class:`LstmSnapshotTable`."""
+def _zoo_lstm_pairing(env, table, zoo_table, states):
+    """Checks of the zoo LSTM match steps; returns the pairing and the state pair from ``states``: agent 1's tensor [N][2 * 64]
+    for an MLP table, the pair (agent 0 [N][2 nlstm], agent 1 [N][2 * 64]) for an :class:`LstmSnapshotTable`."""
     _check_zoo(env, table, zoo_table)
     if not getattr(zoo_table, "recurrent", False):
         raise ValueError("zoo_lstm_match_steps_* need a policy_zoo.ZooLstmTable (zoo MLP nets play through zoo_match_steps_*)")
-    N, Hz = env.num_envs, zoo_table.hidden
-    st0, st1 = states if getattr(table, "recurrent", False) else (None, states)
-    if st0 is not None:
-        _check_lstm(table, (st0,), N)
-    if tuple(st1.shape) != (N, 2 * Hz) or not st1.is_contiguous():
-        raise ValueError("the zoo nets' recurrent state must be a contiguous float32 [%d][%d] tensor (c | h)" % (N, 2 * Hz))
-    return st0, st1
+    return match_pairing(table, zoo_table), tuple(states) if getattr(table, "recurrent", False) else (None, states)
 
 
 def zoo_lstm_match_steps_fused(env, table, zoo_table, idx0, idx1, states, score, quota, K, noise=None):
@@ -498,26 +561,7 @@ def zoo_lstm_match_steps_fused(env, table, zoo_table, idx0, idx1, states, score,
     :class:`SnapshotTable` (``states``: agent 1's float32 CUDA [N][128] tensor, c | h), ``sumo_match_steps_lstm_zoo_lstm`` for an
     :class:`LstmSnapshotTable` of LSTM(128) policies (``states``: the pair agent 0 [N][256], agent 1 [N][128]).  The states are
     read and updated in place; the other arguments as :func:`match_steps_fused`."""
-    from . import capi
-    st0, st1 = _check_zoo_lstm(env, table, zoo_table, states)
-    extra = lambda sl: (zoo_table.struct(st1[sl]),)
-    if st0 is None:
-        def fill(mo, sl):
-            mo.params = table.params.data_ptr()
-            mo.nsnap, mo.ob_dim, mo.ac_dim = table.capacity, table.spec.ob_dim, table.spec.ac_dim
-
-        _fused_groups(env, "match_steps_zoo_lstm", capi.Match, fill, idx0, idx1, score, quota, K, noise, extra=extra)
-        return
-    if table.spec.nlstm != 128:
-        raise ValueError("the fused match launch plays LSTM(128) policies only (got LSTM(%d)): use fused=False" % table.spec.nlstm)
-
-    def fill(mo, sl):
-        mo.proto = C.addressof(table.proto)
-        mo.nets_dev = table.nets_dev.data_ptr()
-        mo.nsnap = table.capacity
-        mo.state0 = st0[sl].data_ptr()
-
-    _fused_groups(env, "match_steps_lstm_zoo_lstm", capi.MatchLstm, fill, idx0, idx1, score, quota, K, noise, extra=extra)
+    pairing_steps(env, *_zoo_lstm_pairing(env, table, zoo_table, states), idx0, idx1, score, quota, K, noise, True)
 
 
 def zoo_lstm_match_steps_stepwise(env, table, zoo_table, idx0, idx1, states, score, quota, K, noise=None):
@@ -526,114 +570,64 @@ def zoo_lstm_match_steps_stepwise(env, table, zoo_table, idx0, idx1, states, sco
     ``ppo_lstm_step`` launch on its policy branch (what ``ZooLSTMPolicy.act`` runs), its state rows masked by AGENT 0's done flags
     of the previous step (``policy_zoo._evaluate_against`` resets the opponent on them); then ``step_device`` and the score
     update.  idx0 / idx1 are host arrays."""
-    import torch
-    from . import ppo_capi
-    st0, st1 = _check_zoo_lstm(env, table, zoo_table, states)
-    D, A, Hz = table.spec.ob_dim, table.spec.ac_dim, zoo_table.hidden
-    L, st, obs = ppo_capi.lib(), env._stream(), env.obs_dev
-    nlp = torch.empty(env.num_envs, dtype=torch.float32, device=env.device)
-
-    def lstm_step(net, ob, n, mask, S, H, nz, out):
-        ppo_capi.chk(L.ppo_lstm_step(C.byref(net), ob, n, obs.stride(0), mask.data_ptr(), S.data_ptr(), S.data_ptr() + 4 * H, 2 * H,
-                                     ppo_capi.ptr(nz), None, out.data_ptr(), None, None, None, st))
-
-    def forward(k, side, rows, nz, out, mask):
-        n, ob = rows.stop - rows.start, obs[rows, side].data_ptr()
-        if side == 0:
-            if st0 is None:
-                ppo_capi.chk(L.ppo_forward(table.params[k].data_ptr(), ob, n, obs.stride(0), D, A, ppo_capi.FWD_PI, ppo_capi.ptr(nz), None,
-                                           out.data_ptr(), nlp[rows].data_ptr(), None, None, st))
-            else:
-                lstm_step(table.nets[k], ob, n, mask, st0[rows], table.spec.nlstm, nz, out)
-        else:
-            lstm_step(zoo_table.nets[k], ob, n, env.done_dev[rows, 0].to(torch.float32), st1[rows], Hz, nz, out)
-
-    _stepwise(env, table, idx0, idx1, score, quota, K, noise, forward, masked=True, capacity1=zoo_table.capacity)
+    pairing_steps(env, *_zoo_lstm_pairing(env, table, zoo_table, states), idx0, idx1, score, quota, K, noise, False)
 
 
-def _check_cross(env, mlp_table, lstm_table, lstm_side, state):
+def _cross_pairing(env, mlp_table, lstm_table, lstm_side, state):
+    """Checks of the cross-family match steps; returns the pairing of the seating and its state pair."""
     if getattr(mlp_table, "recurrent", False) or not getattr(lstm_table, "recurrent", False):
         raise ValueError("cross-family matches take a SnapshotTable (MLP(64,64)) and an LstmSnapshotTable, in this order")
     if lstm_side not in (0, 1):
         raise ValueError("lstm_side %r: 0 (agent 0 plays the LSTM table) or 1" % (lstm_side,))
     _check_env(env, mlp_table)
     _check_env(env, lstm_table)
-    _check_lstm(lstm_table, (state,), env.num_envs)
+    if lstm_side == 0:
+        return match_pairing(lstm_table, mlp_table), (state, None)
+    return match_pairing(mlp_table, lstm_table), (None, state)
 
 
 def cross_match_steps_fused(env, mlp_table, lstm_table, lstm_side, idx0, idx1, state, score, quota, K, noise=None):
     """K match steps of MLP(64,64) checkpoints against LSTM(128) checkpoints in one ``sumo_match_steps_cross`` launch per env
     group: agent ``lstm_side`` plays row idx_g[e] of ``lstm_table`` on ``state`` (float32 CUDA [N][256], c | h, read and updated
     in place), the other agent row idx_g[e] of ``mlp_table``.  The other arguments as :func:`match_steps_fused`."""
-    from . import capi
-    _check_cross(env, mlp_table, lstm_table, lstm_side, state)
-    if lstm_table.spec.nlstm != 128:
-        raise ValueError("the fused match launch plays LSTM(128) policies only (got LSTM(%d)): use fused=False" % lstm_table.spec.nlstm)
-
-    def fill(mo, sl):
-        mo.params = mlp_table.params.data_ptr()
-        mo.nsnap_mlp, mo.ob_dim, mo.ac_dim = mlp_table.capacity, mlp_table.spec.ob_dim, mlp_table.spec.ac_dim
-        mo.proto = C.addressof(lstm_table.proto)
-        mo.nets_dev = lstm_table.nets_dev.data_ptr()
-        mo.nsnap_lstm = lstm_table.capacity
-        mo.state = state[sl].data_ptr()
-        mo.lstm_side = int(lstm_side)
-
-    _fused_groups(env, "match_steps_cross", capi.MatchCross, fill, idx0, idx1, score, quota, K, noise)
+    pairing_steps(env, *_cross_pairing(env, mlp_table, lstm_table, lstm_side, state), idx0, idx1, score, quota, K, noise, True)
 
 
 def cross_match_steps_stepwise(env, mlp_table, lstm_table, lstm_side, idx0, idx1, state, score, quota, K, noise=None):
     """The same K steps step by step: the launches of :func:`match_steps_stepwise` for the MLP side and of
     :func:`match_steps_stepwise_lstm` for agent ``lstm_side`` (any LSTM width the step kernel is built for).  idx0 / idx1 are
     host arrays."""
-    _check_cross(env, mlp_table, lstm_table, lstm_side, state)
-    seats = [(mlp_table, _mlp_side(env, mlp_table)), (lstm_table, _lstm_side(env, lstm_table, lambda side: state))]
-    (table0, forward0), (table1, forward1) = seats[::-1] if lstm_side == 0 else seats
-    _stepwise(env, table0, idx0, idx1, score, quota, K, noise, _by_side(forward0, forward1), masked=True, capacity1=table1.capacity)
+    pairing_steps(env, *_cross_pairing(env, mlp_table, lstm_table, lstm_side, state), idx0, idx1, score, quota, K, noise, False)
 
 
-def _check_lstm_zoo(env, lstm_table, zoo_table, state0):
+def _lstm_zoo_pairing(env, lstm_table, zoo_table, state0):
     if not getattr(lstm_table, "recurrent", False) or getattr(zoo_table, "recurrent", False):
         raise ValueError("lstm_zoo_match_steps_* take an LstmSnapshotTable and a policy_zoo.ZooTable (zoo MLP nets)")
     _check_env(env, lstm_table)
     _check_zoo_dims(lstm_table, zoo_table)
-    _check_lstm(lstm_table, (state0,), env.num_envs)
+    return match_pairing(lstm_table, zoo_table), (state0, None)
 
 
 def lstm_zoo_match_steps_fused(env, lstm_table, zoo_table, idx0, idx1, state0, score, quota, K, noise=None):
     """K match steps of LSTM(128) checkpoints (agent 0: row idx0[e] of ``lstm_table`` on ``state0``, float32 CUDA [N][256], read
     and updated in place) against policy-zoo MLP nets (agent 1: row idx1[e] of ``zoo_table``) in one
     ``sumo_match_steps_lstm_zoo`` launch per env group; the other arguments as :func:`match_steps_fused`."""
-    from . import capi
-    _check_lstm_zoo(env, lstm_table, zoo_table, state0)
-    if lstm_table.spec.nlstm != 128:
-        raise ValueError("the fused match launch plays LSTM(128) policies only (got LSTM(%d)): use fused=False" % lstm_table.spec.nlstm)
-
-    def fill(mo, sl):
-        mo.proto = C.addressof(lstm_table.proto)
-        mo.nets_dev = lstm_table.nets_dev.data_ptr()
-        mo.nsnap = lstm_table.capacity
-        mo.state0 = state0[sl].data_ptr()
-
-    _fused_groups(env, "match_steps_lstm_zoo", capi.MatchLstm, fill, idx0, idx1, score, quota, K, noise, extra=(zoo_table.struct(),))
+    pairing_steps(env, *_lstm_zoo_pairing(env, lstm_table, zoo_table, state0), idx0, idx1, score, quota, K, noise, True)
 
 
 def lstm_zoo_match_steps_stepwise(env, lstm_table, zoo_table, idx0, idx1, state0, score, quota, K, noise=None):
     """The same K steps step by step: per step one ``ppo_lstm_step`` launch masked by agent 0's done flags for every run of envs
     that share a checkpoint, one ``ppo_forward_filtered`` launch for every run that shares a zoo net, then ``step_device`` and the
     score update.  idx0 / idx1 are host arrays."""
-    _check_lstm_zoo(env, lstm_table, zoo_table, state0)
-    forward = _by_side(_lstm_side(env, lstm_table, lambda side: state0), _zoo_mlp_side(env, zoo_table, lstm_table.spec.ac_dim))
-    _stepwise(env, lstm_table, idx0, idx1, score, quota, K, noise, forward, masked=True, capacity1=zoo_table.capacity)
+    pairing_steps(env, *_lstm_zoo_pairing(env, lstm_table, zoo_table, state0), idx0, idx1, score, quota, K, noise, False)
 
 
 def match_steps(env, table, idx0, idx1, states, score, quota, K, noise=None, fused=True):
     """K match steps of either table kind on either path: ``states`` is the pair of recurrent state tensors of an
     :class:`LstmSnapshotTable` (ignored for MLP tables); idx0 / idx1 are CUDA tensors (fused) or host arrays (step by step)."""
-    if getattr(table, "recurrent", False):
-        (match_steps_fused_lstm if fused else match_steps_stepwise_lstm)(env, table, idx0, idx1, states, score, quota, K, noise)
-    else:
-        (match_steps_fused if fused else match_steps_stepwise)(env, table, idx0, idx1, score, quota, K, noise)
+    _check_env(env, table)
+    pairing_steps(env, match_pairing(table, table), states if getattr(table, "recurrent", False) else (None, None), idx0, idx1, score,
+                 quota, K, noise, fused)
 
 
 def _score_step(score, info, done, quota):
@@ -648,6 +642,31 @@ def _score_step(score, info, done, quota):
 
 
 # ---- match-ups -------------------------------------------------------------------------------------------------------------
+def _play(env, pairing, pairs, rounds_per_env, envs_per_pair, deterministic, seed, adjust_z, chunk, fused):
+    """What the play drivers share once their pairing is resolved: the rows of every pair checked against the table of their own
+    seat, the quota and the chunk, the fused launch's LSTM width, and :func:`_play_batches` on :func:`pairing_steps` with fresh
+    all-zero recurrent states per batch (``LstmPPOModel.initial_state``)."""
+    import torch
+    s0, s1 = pairing.seats
+    row_ok = lambda seat, k: 0 <= k < seat.table.capacity and (seat.family.startswith("zoo") or bool(seat.table.filled[k]))
+    pairs = [(int(i), int(j)) for i, j in pairs]
+    for i, j in pairs:
+        if not (row_ok(s0, i) and row_ok(s1, j)):
+            raise ValueError("pair (%d, %d) refers to an empty or non-existent %s" %
+                             (i, j, "checkpoint / zoo row" if s1.family.startswith("zoo") else "snapshot row"))
+    rounds_per_env, envs_per_pair, chunk = int(rounds_per_env), int(envs_per_pair), int(chunk)
+    if rounds_per_env < 1 or chunk < 1:
+        raise ValueError("rounds_per_env and chunk must be >= 1")
+    if fused:
+        _refuse_fused_width(pairing.nlstm)
+    new_states = lambda: tuple(None if s.width is None else torch.zeros((env.num_envs, s.width), dtype=torch.float32, device=env.device)
+                               for s in pairing.seats)
+    steps = lambda idx0, idx1, states, score, noise: pairing_steps(env, pairing, states, idx0, idx1, score, rounds_per_env, chunk, noise,
+                                                                  fused)
+    return _play_batches(env, s0.table.spec.ac_dim, pairs, rounds_per_env, envs_per_pair, deterministic, seed, adjust_z, chunk, fused,
+                         new_states, steps)
+
+
 def play_matches(env, table, pairs, rounds_per_env, envs_per_pair, deterministic=False, seed=0, adjust_z=EVAL_ADJUST_Z, chunk=64,
                  fused=True):
     """Plays every match-up ``pairs[p] = (i, j)`` (snapshot i as agent 0 against snapshot j as agent 1 of ``table``, a
@@ -656,26 +675,8 @@ def play_matches(env, table, pairs, rounds_per_env, envs_per_pair, deterministic
     env), zeroes both sides' recurrent states (LSTM tables) and runs ``chunk``-step launches until every env of the batch has its
     quota.  ``adjust_z`` is imposed on every agent for the games and the env's value restored afterwards (None:
     leave it).  Returns one dict per pair: wins, losses, draws, rounds (== envs_per_pair * rounds_per_env), env_steps."""
-    import torch
     _check_env(env, table)
-    pairs = [(int(i), int(j)) for i, j in pairs]
-    for i, j in pairs:
-        if not (0 <= i < table.capacity and 0 <= j < table.capacity) or not (table.filled[i] and table.filled[j]):
-            raise ValueError("pair (%d, %d) refers to an empty or non-existent snapshot row" % (i, j))
-    rounds_per_env, envs_per_pair, chunk = int(rounds_per_env), int(envs_per_pair), int(chunk)
-    if rounds_per_env < 1 or chunk < 1:
-        raise ValueError("rounds_per_env and chunk must be >= 1")
-    recurrent = bool(getattr(table, "recurrent", False))
-    if recurrent and fused and table.spec.nlstm != 128:
-        raise ValueError("the fused match launch plays LSTM(128) policies only (got LSTM(%d)): use fused=False" % table.spec.nlstm)
-    new_states = None
-    if recurrent:                     # every match-up starts from the zero state (LstmPPOModel.initial_state)
-        import torch
-        new_states = lambda: tuple(torch.zeros((env.num_envs, 2 * table.spec.nlstm), dtype=torch.float32, device=env.device) for _ in range(2))
-    steps = lambda idx0, idx1, states, score, noise: match_steps(env, table, idx0, idx1, states, score, rounds_per_env, chunk, noise,
-                                                                 fused=fused)
-    return _play_batches(env, table.spec.ac_dim, pairs, rounds_per_env, envs_per_pair, deterministic, seed, adjust_z, chunk, fused,
-                         new_states, steps)
+    return _play(env, match_pairing(table, table), pairs, rounds_per_env, envs_per_pair, deterministic, seed, adjust_z, chunk, fused)
 
 
 def play_cross_matches(env, table0, table1, pairs, rounds_per_env, envs_per_pair, deterministic=False, seed=0, adjust_z=EVAL_ADJUST_Z,
@@ -684,39 +685,17 @@ def play_cross_matches(env, table0, table1, pairs, rounds_per_env, envs_per_pair
     ``table1`` as agent 1, where exactly one of the two tables is an :class:`LstmSnapshotTable` and the other a
     :class:`SnapshotTable` (either seating).  The recurrent agent's state is zeroed per batch.  Same batching, seeding, quota
     and return value as :func:`play_matches`; ``fused=False`` plays the same games step by step (any LSTM width)."""
-    rec = [bool(getattr(t, "recurrent", False)) for t in (table0, table1)]
-    if rec[0] == rec[1]:
+    if bool(getattr(table0, "recurrent", False)) == bool(getattr(table1, "recurrent", False)):
         raise ValueError("play_cross_matches takes one SnapshotTable (MLP(64,64)) and one LstmSnapshotTable; two tables of one "
                          "family play through play_matches")
-    lstm_side = 0 if rec[0] else 1
-    lstm_table, mlp_table = (table0, table1) if rec[0] else (table1, table0)
     _check_env(env, table0)
     _check_env(env, table1)
-    pairs = [(int(i), int(j)) for i, j in pairs]
-    for i, j in pairs:
-        if not (0 <= i < table0.capacity and 0 <= j < table1.capacity) or not (table0.filled[i] and table1.filled[j]):
-            raise ValueError("pair (%d, %d) refers to an empty or non-existent snapshot row" % (i, j))
-    rounds_per_env, envs_per_pair, chunk = int(rounds_per_env), int(envs_per_pair), int(chunk)
-    if rounds_per_env < 1 or chunk < 1:
-        raise ValueError("rounds_per_env and chunk must be >= 1")
-    if fused and lstm_table.spec.nlstm != 128:
-        raise ValueError("the fused match launch plays LSTM(128) policies only (got LSTM(%d)): use fused=False" % lstm_table.spec.nlstm)
-
-    def new_state():
-        import torch
-        return torch.zeros((env.num_envs, 2 * lstm_table.spec.nlstm), dtype=torch.float32, device=env.device)
-
-    def steps(idx0, idx1, state, score, noise):
-        fn = cross_match_steps_fused if fused else cross_match_steps_stepwise
-        fn(env, mlp_table, lstm_table, lstm_side, idx0, idx1, state, score, rounds_per_env, chunk, noise)
-
-    return _play_batches(env, mlp_table.spec.ac_dim, pairs, rounds_per_env, envs_per_pair, deterministic, seed, adjust_z, chunk, fused,
-                         new_state, steps)
+    return _play(env, match_pairing(table0, table1), pairs, rounds_per_env, envs_per_pair, deterministic, seed, adjust_z, chunk, fused)
 
 
 def _play_batches(env, A, pairs, rounds_per_env, envs_per_pair, deterministic, seed, adjust_z, chunk, fused, new_states, steps):
-    """The batching behind :func:`play_matches` / :func:`play_against_zoo`: pairs in batches of contiguous env blocks
-    (:func:`plan_batches`, :func:`env_assignment`); per batch a seeded reset, fresh recurrent states (``new_states()`` or None) and
+    """The batching behind :func:`_play`: pairs in batches of contiguous env blocks (:func:`plan_batches`,
+    :func:`env_assignment`); per batch a seeded reset, fresh recurrent states (``new_states()``) and
     ``steps(idx0, idx1, states, score, noise)`` launches of ``chunk`` steps -- indices as CUDA tensors when ``fused``, else host
     arrays -- until every env of the batch has its quota."""
     import torch
@@ -740,7 +719,7 @@ def _play_batches(env, A, pairs, rounds_per_env, envs_per_pair, deterministic, s
             env.seeds = np.uint64(seed) + np.uint64(bn * N) + np.arange(N, dtype=np.uint64)
             env._needs_seed = True
             env.reset_device()
-            states = new_states() if new_states is not None else None
+            states = new_states()
             launches = 0
             while True:
                 noise = None if deterministic else tuple(torch.randn((chunk, N, A), generator=gen, device=env.device) for _ in range(2))
@@ -772,41 +751,12 @@ def play_against_zoo(env, table, zoo_table, pairs, rounds_per_env, envs_per_pair
     checkpoints') are allocated and zeroed per batch.  Same batching, seeding, quota and return value as :func:`play_matches`;
     ``fused=False`` plays the same games step by step (bit-identical envs and scores).  ``cross_family=True`` also plays an
     :class:`LstmSnapshotTable` against a :class:`policy_zoo.ZooTable` (``sumo_match_steps_lstm_zoo``); the default refuses it."""
-    lstm_vs_mlp = bool(cross_family) and getattr(table, "recurrent", False) and not getattr(zoo_table, "recurrent", False)
-    if lstm_vs_mlp:
+    if cross_family:
         _check_env(env, table)
         _check_zoo_dims(table, zoo_table)
     else:
         _check_zoo(env, table, zoo_table)
-    pairs = [(int(i), int(j)) for i, j in pairs]
-    for i, j in pairs:
-        if not (0 <= i < table.capacity and table.filled[i]) or not 0 <= j < zoo_table.capacity:
-            raise ValueError("pair (%d, %d) refers to an empty or non-existent checkpoint / zoo row" % (i, j))
-    rounds_per_env, envs_per_pair, chunk = int(rounds_per_env), int(envs_per_pair), int(chunk)
-    if rounds_per_env < 1 or chunk < 1:
-        raise ValueError("rounds_per_env and chunk must be >= 1")
-    new_states = None
-    if lstm_vs_mlp:
-        import torch
-        if fused and table.spec.nlstm != 128:
-            raise ValueError("the fused match launch plays LSTM(128) policies only (got LSTM(%d)): use fused=False" % table.spec.nlstm)
-        new_states = lambda: torch.zeros((env.num_envs, 2 * table.spec.nlstm), dtype=torch.float32, device=env.device)
-        fn = lstm_zoo_match_steps_fused if fused else lstm_zoo_match_steps_stepwise
-        steps = lambda idx0, idx1, state0, score, noise: fn(env, table, zoo_table, idx0, idx1, state0, score, rounds_per_env, chunk, noise)
-    elif getattr(zoo_table, "recurrent", False):
-        import torch
-        rec0 = bool(getattr(table, "recurrent", False))
-        if rec0 and fused and table.spec.nlstm != 128:
-            raise ValueError("the fused match launch plays LSTM(128) policies only (got LSTM(%d)): use fused=False" % table.spec.nlstm)
-        zeros = lambda width: torch.zeros((env.num_envs, width), dtype=torch.float32, device=env.device)
-        new_states = (lambda: (zeros(2 * table.spec.nlstm), zeros(2 * zoo_table.hidden))) if rec0 else (lambda: zeros(2 * zoo_table.hidden))
-        fn = zoo_lstm_match_steps_fused if fused else zoo_lstm_match_steps_stepwise
-        steps = lambda idx0, idx1, states, score, noise: fn(env, table, zoo_table, idx0, idx1, states, score, rounds_per_env, chunk, noise)
-    else:
-        fn = zoo_match_steps_fused if fused else zoo_match_steps_stepwise
-        steps = lambda idx0, idx1, _states, score, noise: fn(env, table, zoo_table, idx0, idx1, score, rounds_per_env, chunk, noise)
-    return _play_batches(env, table.spec.ac_dim, pairs, rounds_per_env, envs_per_pair, deterministic, seed, adjust_z, chunk, fused,
-                         new_states, steps)
+    return _play(env, match_pairing(table, zoo_table), pairs, rounds_per_env, envs_per_pair, deterministic, seed, adjust_z, chunk, fused)
 
 
 def _make_env(env_id, num_env, seed, env):
@@ -856,8 +806,8 @@ def compare_history_versions(path1, path2, trials, num_env=256, deterministic=Fa
         raise ValueError("P1 holds %s checkpoints and P2 %s checkpoints: both runs must use the same network (MLP-vs-LSTM and "
                          "mixed LSTM widths are not supported)" % (_kind_name(k1), _kind_name(k2)))
     nlstm = k1[1] if k1[0] == "lstm" else k2[1]
-    if cross and fused and nlstm != 128:
-        raise ValueError("the fused match launch plays LSTM(128) policies only (got LSTM(%d)): use fused=False" % nlstm)
+    if cross and fused:
+        _refuse_fused_width(nlstm)
     env, own = _make_env(env_id, num_env, seed, env)
     try:
         n = len(pv)

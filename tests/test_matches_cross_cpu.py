@@ -190,7 +190,7 @@ def test_play_cross_matches_refusals():
 
 @pytest.mark.parametrize("lstm_first", [False, True])
 def test_play_cross_matches_assigns_env_blocks_as_env_assignment(monkeypatch, lstm_first):
-    """Pure planning: with the step function replaced by a recorder, every batch hands over env_assignment's (idx0, idx1) for its
+    """Pure planning: with the step driver replaced by a recorder, every batch hands over env_assignment's (idx0, idx1) for its
     pairs, the seat of the recurrent table, and a fresh zero state."""
     mt, lt = _tables(np.random.default_rng(5))
     N, epp = 10, 4                                               # two blocks per batch, two envs left over
@@ -199,13 +199,16 @@ def test_play_cross_matches_assigns_env_blocks_as_env_assignment(monkeypatch, ls
     pairs = [(1, 2), (0, 1), (1, 0)] if lstm_first else [(2, 1), (1, 0), (0, 1)]
     calls = []
 
-    def record(env_, mlp_table, lstm_table, lstm_side, idx0, idx1, state, score, quota, K, noise=None):
-        assert mlp_table is mt and lstm_table is lt and quota == 2 and K == 16 and noise is None
-        assert tuple(state.shape) == (N, 256) and float(state.abs().sum()) == 0.0
+    def record(env_, pairing, states, idx0, idx1, score, quota, K, noise, fused):
+        lstm_side = pairing.lstm_side
+        assert pairing.seats[1 - lstm_side].table is mt and pairing.seats[lstm_side].table is lt
+        assert quota == 2 and K == 16 and noise is None and fused is False
+        state = states[lstm_side]
+        assert states[1 - lstm_side] is None and tuple(state.shape) == (N, 256) and float(state.abs().sum()) == 0.0
         calls.append((lstm_side, np.array(idx0), np.array(idx1)))
         state.fill_(1.0)                                         # the next batch must not see it
         score[:, 0] = quota
-    monkeypatch.setattr(matches, "cross_match_steps_stepwise", record)
+    monkeypatch.setattr(matches, "pairing_steps", record)         # the one seam between the play drivers and the step paths
     res = matches.play_cross_matches(env, t0, t1, pairs, 2, epp, deterministic=True, chunk=16, fused=False)
     batches = matches.plan_batches(len(pairs), epp, N)
     assert [len(b) for b in batches] == [2, 1] and len(calls) == 2 and env.resets == 2

@@ -113,32 +113,24 @@ def main(argv):
     if args.network == "cross":
         out["lstm_side"] = args.lstm_side
     quota = 1 << 30
-    states = tuple(torch.zeros((N, 128 if args.opponent == "zoo_lstm" and g == 1 else 256), dtype=torch.float32, device="cuda") for g in range(2))
+    if args.network == "cross":
+        tables = (ltable, mlp_table) if args.lstm_side == 0 else (mlp_table, ltable)
+    else:
+        tables = (table, zoo_table if zoo_table is not None else table)
+    pairing = matches.match_pairing(*tables)
+    states = tuple(None if s.width is None else torch.zeros((N, s.width), dtype=torch.float32, device="cuda") for s in pairing.seats)
 
     def launch(fused, score):
         i0, i1 = (idx0, idx1) if fused else (idx0_h, idx1_h)
-        if args.opponent == "zoo_lstm":
-            (matches.zoo_lstm_match_steps_fused if fused else matches.zoo_lstm_match_steps_stepwise)(
-                env, table, zoo_table, i0, i1, states if args.network == "lstm" else states[1], score, quota, K, noise)
-        elif args.network == "cross":
-            (matches.cross_match_steps_fused if fused else matches.cross_match_steps_stepwise)(
-                env, mlp_table, ltable, args.lstm_side, i0, i1, states[0], score, quota, K, noise)
-        elif zoo_table is not None and args.network == "lstm":
-            (matches.lstm_zoo_match_steps_fused if fused else matches.lstm_zoo_match_steps_stepwise)(
-                env, table, zoo_table, i0, i1, states[0], score, quota, K, noise)
-        elif zoo_table is not None:
-            (matches.zoo_match_steps_fused if fused else matches.zoo_match_steps_stepwise)(env, table, zoo_table, i0, i1, score, quota, K, noise)
-        elif args.network == "lstm":
-            (matches.match_steps_fused_lstm if fused else matches.match_steps_stepwise_lstm)(env, table, i0, i1, states, score, quota, K, noise)
-        else:
-            (matches.match_steps_fused if fused else matches.match_steps_stepwise)(env, table, i0, i1, score, quota, K, noise)
+        matches.pairing_steps(env, pairing, states, i0, i1, score, quota, K, noise, fused)
 
     def run(fused, steps):
         score = torch.zeros((N, 3), dtype=torch.int32, device="cuda")
         env._needs_seed = True
         env.reset_device()
         for st in states:
-            st.zero_()
+            if st is not None:
+                st.zero_()
         for _ in range(-(-args.warmup // K)):
             launch(fused, score)
         score.zero_()

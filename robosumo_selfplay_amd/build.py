@@ -44,6 +44,7 @@ def build_all(force=False, verbose=False):
     jobs = [
         ("libsumo_hip.so", "sumo_engine.hip", [["-DSUMO_ROLLOUT_EXTERN"]] + [["-DSUMO_ROLLOUT_SHARD=%d" % k] for k in range(ROLLOUT_SHARDS)]),
         ("libsumo_ppo.so", "ppo_kernels.hip", [[]]),
+        ("libsumo_render.so", "sumo_render.hip", [[]]),
     ]
     out, links, compiles = [], [], []
     with tempfile.TemporaryDirectory(prefix="sumo_build_") as tmp:

@@ -283,7 +283,44 @@ class SumoVecEnv(VecEnv):
             infos.append(tuple(per_agent))
         return obs, rews, done, tuple(infos)
 
+    # ---- pictures ------------------------------------------------------------------------------------------------
+    def get_images(self, envs=None, width=320, height=240, camera="arena"):
+        """RGB images uint8 [k][H][W][3] (host) of the chosen envs, default the first min(N, 16), rendered on the GPU from each
+        group's ``get_state()`` qpos (render.py).  ``camera``: 'arena' (one fixed view), 'track' (follows the two torsos, one camera
+        per env) or a ``render.Camera``.  The renderer is created on first use."""
+        from . import render
+        if getattr(self, "_renderer", None) is None:
+            self._renderer = render.Renderer(self.model, device=self.device.index or 0)
+        self._assert_not_closed()
+        envs = np.arange(min(self.num_envs, 16)) if envs is None else np.atleast_1d(np.asarray(envs, np.int64))
+        if envs.size == 0 or envs.min() < 0 or envs.max() >= self.num_envs:
+            raise ValueError("envs must name some of the %d envs" % self.num_envs)
+        self._torch.cuda.synchronize(self.device)
+        qpos = np.concatenate([E.get_state()[0] for E in self.engines])[envs]
+        if camera == "arena":
+            cams = render.arena_camera()
+        elif camera == "track":
+            cams = render.track_camera(self.model, qpos)
+        elif isinstance(camera, render.Camera):
+            cams = camera
+        else:
+            raise ValueError("camera must be 'arena', 'track' or a render.Camera")
+        return self._renderer.frames(qpos, cams, width, height)["rgb"].cpu().numpy()
+
+    def render(self, mode="rgb_array", **kw):
+        """``mode='rgb_array'``: the images of :meth:`get_images` (its keywords) tiled into one picture, as baselines'
+        ``VecEnv.render`` returns it.  There is no window: ``mode='human'`` is not implemented."""
+        if mode == "rgb_array":
+            from . import render
+            return render.tile_images(self.get_images(**kw))
+        if mode == "human":
+            raise NotImplementedError("render(mode='human'): there is no display path; use mode='rgb_array' or play.py")
+        raise NotImplementedError("unknown render mode %r" % (mode,))
+
     def close_extras(self):
+        if getattr(self, "_renderer", None) is not None:
+            self._renderer.close()
+            self._renderer = None
         for E in self.engines:
             E.close()
 

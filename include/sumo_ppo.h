@@ -91,6 +91,31 @@ int ppo_lstm_step_pool(const ppo_lstm_net* proto, const ppo_lstm_net* nets_dev, 
                        const float* given_action, float* action_out, float* neglogp_out, float* value_out, float* mean_out,
                        void* stream);
 
+/* One seat of a zoo-vs-zoo match: the actions of one agent of n envs in ONE launch, every 16-env tile played by its own policy-zoo
+ * net, MLP nets and LSTM(64) nets mixed (robosumo/demos/play.py puts one zoo net on each side of any of the nine scenes).
+ *   obs          row e at obs + e * obs_stride (the seat's slice of the env's observation buffer); ob_dim columns are read
+ *   done         the previous step's flag of env e at done[e * done_stride] (uint8; NULL = none): an LSTM tile's state rows are
+ *                zeroed where it is set, before the cell runs; MLP tiles do not touch `state`
+ *   noise        contiguous [n][ac_dim] standard-normal rows; NULL = the action is the mean
+ *   action_out   row e at action_out + e * act_stride (the seat's slice of the env's action buffer); ac_dim columns are written
+ * An MLP tile yields the bits of ppo_forward_filtered(flags = PPO_FWD_PI | PPO_FWD_TANH, that row's filter, noise) on its 16 rows, an
+ * LSTM tile the actions and the new state of ppo_lstm_step with that row's net (PPO_LSTM_GATES_IJFO, embedding and hidden 64): the
+ * kernels share one copy of each body.  A tile whose entry is outside [0, n_mlp + n_lstm) writes neither actions nor state and reads
+ * no table; 1 + tile is stored to status_dev (DEVICE int32, may be NULL; the caller zeroes it).  Argument errors (NULL seat / obs /
+ * action_out / tile_entry, n < 16 or off the tile grid, ob_dim outside [1, 512], ac_dim outside [1, 16], strides below the widths,
+ * no rows, rows without a table, LSTM rows without a state) return before anything is launched. */
+typedef struct ppo_zoo_seat {
+  const float *mlp_params, *mlp_filt;    /* [n_mlp][Pm] in policy_zoo.zoo_kernel_flat order; [n_mlp][2][ob_dim] mean | 1/std */
+  const float *lstm_params, *lstm_filt;  /* [n_lstm][Pl] in policy_zoo._ZOO_LSTM_ROW order; [n_lstm][2][ob_dim] */
+  const int32_t* tile_entry;             /* DEVICE [n / 16]: e < n_mlp -> MLP row e; n_mlp <= e < n_mlp + n_lstm -> LSTM row e - n_mlp
+                                            (the encoding of policy_zoo.league_entries) */
+  float* state;                          /* DEVICE [n][128] c | h of the LSTM tiles; NULL allowed only when n_lstm == 0 */
+  int n_mlp, n_lstm, ob_dim, ac_dim;
+  float obs_clip, forget_bias;
+} ppo_zoo_seat;
+int ppo_zoo_seat_act(const ppo_zoo_seat* seat, const float* obs, int n, int obs_stride, const uint8_t* done, int done_stride,
+                     const float* noise, float* action_out, int act_stride, int32_t* status_dev, void* stream);
+
 /* --- recurrent training (back-propagation through time over the baselines LSTM; the reference builds the unrolled graph in
  * a2c/utils.py:82-103 + model.py:65-139, its own recurrent minibatch loop alg_ppo.py:408-421 is dead code) ---------------
  * ppo_lstm_step_save: ppo_lstm_step that also records what the backward pass needs for this time step:

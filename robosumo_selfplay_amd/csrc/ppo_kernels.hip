@@ -81,6 +81,36 @@ struct FwdArgs {
 
 extern __shared__ float smem_f[];
 
+// The policy branch of ppo_forward_kernel on one wave's staged tile (rows r0 .. r0 + 15 in xbuf): trunk, Gaussian head, action /
+// mean / neglogp rows.  ONE copy for ppo_forward_kernel (act_stride = A) and ppo_zoo_seat_kernel (rows of the env's action buffer), so
+// the two cannot drift apart.
+__device__ __forceinline__ void fwd_pi_tile(const float* params, const ParamLayout& L, bool use_tanh, const float* xbuf, int XS, float* h1,
+                                            float* h2, int lane, int r0, int n, const float* given, const float* noise, float* action,
+                                            int act_stride, float* mean_out, float* neglogp) {
+  const int i = lane & 15, kq = lane >> 4, D = L.D, A = L.A;
+  Net net = pi_net(params, L);
+  f32x4 mean = use_tanh ? trunk_forward<true>(net, xbuf, XS, D, h1, h2, lane) : trunk_forward<false>(net, xbuf, XS, D, h1, h2, lane);
+  const bool col = i < A;
+  float logstd = col ? params[L.logstd + i] : 0.0f;
+  float std = expf(logstd);
+  float sum_logstd = row16_sum(logstd);
+#pragma unroll
+  for (int r = 0; r < 4; r++) {
+    int row = r0 + 4 * kq + r;
+    bool ok = col && row < n;
+    float m = mean[r], act = m;
+    if (ok) {
+      if (given) act = given[(size_t)row * A + i];
+      else if (noise) act = m + std * noise[(size_t)row * A + i];
+      if (action) action[(size_t)row * act_stride + i] = act;
+      if (mean_out) mean_out[(size_t)row * A + i] = m;
+    }
+    float z = ok ? (act - m) / std : 0.0f;
+    float ss = row16_sum(z * z);
+    if (neglogp && i == 0 && row < n) neglogp[row] = 0.5f * ss + 0.5f * LOG2PI_F * (float)A + sum_logstd;
+  }
+}
+
 __global__ void __launch_bounds__(256) ppo_forward_kernel(FwdArgs a) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int tile = blockIdx.x * (blockDim.x >> 6) + wid, r0 = tile * 16;
@@ -93,27 +123,7 @@ __global__ void __launch_bounds__(256) ppo_forward_kernel(FwdArgs a) {
   wave_sync();
   const bool use_tanh = (a.flags & PPO_FWD_TANH) != 0;
   if (a.flags & PPO_FWD_PI) {
-    Net net = pi_net(a.params, a.L);
-    f32x4 mean = use_tanh ? trunk_forward<true>(net, xbuf, XS, D, h1, h2, lane) : trunk_forward<false>(net, xbuf, XS, D, h1, h2, lane);
-    const bool col = i < A;
-    float logstd = col ? a.params[a.L.logstd + i] : 0.0f;
-    float std = expf(logstd);
-    float sum_logstd = row16_sum(logstd);
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      int row = r0 + 4 * kq + r;
-      bool ok = col && row < a.n;
-      float m = mean[r], act = m;
-      if (ok) {
-        if (a.given) act = a.given[(size_t)row * A + i];
-        else if (a.noise) act = m + std * a.noise[(size_t)row * A + i];
-        if (a.action) a.action[(size_t)row * A + i] = act;
-        if (a.mean) a.mean[(size_t)row * A + i] = m;
-      }
-      float z = ok ? (act - m) / std : 0.0f;
-      float ss = row16_sum(z * z);
-      if (a.neglogp && i == 0 && row < a.n) a.neglogp[row] = 0.5f * ss + 0.5f * LOG2PI_F * (float)A + sum_logstd;
-    }
+    fwd_pi_tile(a.params, a.L, use_tanh, xbuf, XS, h1, h2, lane, r0, a.n, a.given, a.noise, a.action, A, a.mean, a.neglogp);
     wave_sync();
   }
   if (a.flags & PPO_FWD_VF) {
@@ -296,14 +306,27 @@ struct LstmArgs {
 
 // NH hidden units: 64 or 128; gate order (static so the gate tiles are static registers); ZIN: gate sums start from LstmArgs::zinit;
 // NW waves per tile: 4, or 8 for NH = 128 (one unit tile per wave: half the products and half the transcendentals on a wave's chain)
-template <int NH, int ORDER, bool ZIN = false, int NW = 4>
-__global__ void __launch_bounds__(64 * NW) ppo_lstm_step_kernel(LstmArgs a) {
+// The done mask of a step: LstmArgs::mask (float32 [n], NULL = none) for ppo_lstm_step_kernel, the env's uint8 done flags read in place
+// for ppo_zoo_seat_kernel (set = 1.0f, clear = 0.0f: the values the float mask of the step-by-step path holds).
+struct LstmMaskF32 {
+  const float* p;
+  __device__ __forceinline__ bool on() const { return p != nullptr; }
+  __device__ __forceinline__ float at(int row) const { return p[row]; }
+};
+struct LstmMaskDone {
+  const uint8_t* p; int stride;
+  __device__ __forceinline__ bool on() const { return p != nullptr; }
+  __device__ __forceinline__ float at(int row) const { return p[(size_t)row * stride] ? 1.0f : 0.0f; }
+};
+// The body of ppo_lstm_step_kernel for the 16-row tile blockIdx.x with net N.  ONE copy for ppo_lstm_step_kernel (its float mask, act_stride
+// = ac_dim) and ppo_zoo_seat_kernel (done flags, rows of the env's action buffer), so the two cannot drift apart.
+template <int NH, int ORDER, bool ZIN, int NW, class MASK>
+__device__ __forceinline__ void lstm_step_tile(const LstmArgs& a, const ppo_lstm_net& N, const MASK mask, int act_stride) {
   constexpr int NT = 64 * NW;
   // FOUR waves per 16-row tile: wave w owns the units [w NH/4, (w+1) NH/4) -- all four gates of those units, their cell
   // update and their slice of the new latent -- so the serial chain per wave is a quarter of the tile's (one wave per tile
   // took 150 us for H = 128 whatever the batch: 63 dependent k-steps of 32 products, then 128 units of transcendentals).
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, r0 = blockIdx.x * 16;
-  const ppo_lstm_net N = a.pool ? a.pool[a.tile_net[blockIdx.x]] : a.net;
   const int D = N.ob_dim, E = N.emb_dim, A = N.ac_dim, XS = a.XS, HP = a.HP;
   float* xbuf = smem_f;
   float* ebuf = xbuf + 16 * XS;
@@ -370,7 +393,7 @@ __global__ void __launch_bounds__(64 * NW) ppo_lstm_step_kernel(LstmArgs a) {
       const bool in = e < 16 * NH && row < a.n;
       const int rowc = row < a.n ? row : a.n - 1, kc = k < NH ? k : 0;     // plain loads at clamped indices, selects afterwards
       const float hv = a.h[(size_t)rowc * a.state_stride + kc];
-      const float mv = a.mask ? a.mask[rowc] : 0.0f;
+      const float mv = mask.on() ? mask.at(rowc) : 0.0f;
       v[u] = in ? hv : 0.0f;
       keep[u] = in ? 1.0f - mv : 1.0f;
     }
@@ -378,7 +401,7 @@ __global__ void __launch_bounds__(64 * NW) ppo_lstm_step_kernel(LstmArgs a) {
     for (int u = 0; u < 8; u++) {
       const int e = e0 + NT * u + tid, r = e / NH, k = e - r * NH, row = r0 + r;
       if (e < 16 * NH) {
-        const float hv = a.mask ? v[u] * keep[u] : v[u];
+        const float hv = mask.on() ? v[u] * keep[u] : v[u];
         hprev[r * HP + k] = hv;
         if (a.sv_hprev && row < a.n) a.sv_hprev[(size_t)row * NH + k] = hv;
       }
@@ -450,7 +473,7 @@ __global__ void __launch_bounds__(64 * NW) ppo_lstm_step_kernel(LstmArgs a) {
     for (int r = 0; r < 4; r++) {
       const int row = r0 + 4 * kq + r;
       float cp = 0.0f;
-      if (row < a.n) { cp = a.c[(size_t)row * a.state_stride + j]; if (a.mask) cp *= 1.0f - a.mask[row]; }
+      if (row < a.n) { cp = a.c[(size_t)row * a.state_stride + j]; if (mask.on()) cp *= 1.0f - mask.at(row); }
       const LstmCell cell = lstm_cell(zi[r], zf[r], zo[r], zu[r], bi, bf, bo, bu, cp);   // shared with the fused rollout kernel (ppo_tile.h)
       const float ig = cell.ig, fg = cell.fg, og = cell.og, ug = cell.ug, cn = cell.cn, tcn = cell.tcn, hn = cell.hn;
       if (row < a.n) {
@@ -489,7 +512,7 @@ __global__ void __launch_bounds__(64 * NW) ppo_lstm_step_kernel(LstmArgs a) {
       if (ok && a.given) act = a.given[(size_t)row * A + i];
       const float nlp = gauss_row(m, std, sum_logstd, ok, sample, (ok && sample) ? a.noise[(size_t)row * A + i] : 0.0f, act, A);
       if (ok) {
-        if (a.action) a.action[(size_t)row * A + i] = act;
+        if (a.action) a.action[(size_t)row * act_stride + i] = act;
         if (a.mean) a.mean[(size_t)row * A + i] = m;
       }
       if (a.neglogp && i == 0 && row < a.n) a.neglogp[row] = nlp;
@@ -509,6 +532,12 @@ __global__ void __launch_bounds__(64 * NW) ppo_lstm_step_kernel(LstmArgs a) {
       for (int r = 0; r < 4; r++) { int row = r0 + 4 * kq + r; if (row < a.n) a.value[row] = v4[r] + N.vf_b[0]; }
     }
   }
+}
+
+template <int NH, int ORDER, bool ZIN = false, int NW = 4>
+__global__ void __launch_bounds__(64 * NW) ppo_lstm_step_kernel(LstmArgs a) {
+  const ppo_lstm_net N = a.pool ? a.pool[a.tile_net[blockIdx.x]] : a.net;
+  lstm_step_tile<NH, ORDER, ZIN, NW>(a, N, LstmMaskF32{a.mask}, N.ac_dim);
 }
 
 // x * wx for ALL time steps of a training minibatch at once (rows = time x env): the input block of the gate sums does not
@@ -642,6 +671,90 @@ extern "C" int ppo_lstm_step_save_z(const ppo_lstm_net* net, const float* z_t, i
   if (!z_t || !save_gates || !save_cprev || !save_hprev || !save_tanhc) FAIL(-1, "bad arguments");
   return lstm_launch(net, nullptr, n, net ? net->ob_dim : 0, mask, c, h, state_stride, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, save_gates,
                      save_cprev, save_hprev, save_tanhc, stream, nullptr, nullptr, z_t, latent_out);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// One seat of a zoo-vs-zoo match (ppo_zoo_seat_act, sumo_ppo.h): one workgroup of four waves per 16-env tile, every tile with the
+// zoo net its entry names -- an MLP row (wave 0 runs fwd_pi_tile as ppo_forward_kernel's one-wave workgroup does; waves 1 to 3
+// leave) or an LSTM(64) row (all four waves run lstm_step_tile as ppo_lstm_step_kernel<64, IJFO> does).  The family branch is
+// uniform over the workgroup and comes before any barrier.  Observations, done flags and actions are read / written in place in the
+// env's buffers; an entry outside the tables writes nothing but the status word.  LDS: the LSTM layout (the larger of the two).
+// ---------------------------------------------------------------------------------------------------------
+struct ZooSeatArgs {
+  ppo_zoo_seat s;
+  const float *obs, *noise;
+  const uint8_t* done;
+  float* action;
+  int32_t* status;
+  int n, obs_stride, done_stride, act_stride, XS, Pl;
+  ParamLayout L;   // of the MLP rows
+};
+
+__global__ void __launch_bounds__(256) ppo_zoo_seat_kernel(ZooSeatArgs a) {
+  const int tile = blockIdx.x, e = a.s.tile_entry[tile];
+  const int n_mlp = a.s.n_mlp, D = a.s.ob_dim, A = a.s.ac_dim;
+  if (e < 0 || e >= n_mlp + a.s.n_lstm) {   // no table row: nothing is read through e, nothing written but the status word
+    if (threadIdx.x == 0 && a.status) *a.status = 1 + tile;
+    return;
+  }
+  if (e < n_mlp) {
+    if (threadIdx.x >= WAVE) return;
+    const int lane = threadIdx.x, r0 = tile * 16, XS = a.XS;
+    float *xbuf = smem_f, *h1 = xbuf + 16 * XS, *h2 = h1 + 16 * HS;
+    const float* filt = a.s.mlp_filt + (size_t)e * 2 * D;
+    stage_x(xbuf, XS, a.obs, a.obs_stride, D, nullptr, r0, a.n, lane, filt, filt + D, a.s.obs_clip);
+    wave_sync();
+    fwd_pi_tile(a.s.mlp_params + (size_t)e * a.L.P, a.L, true, xbuf, XS, h1, h2, lane, r0, a.n, nullptr, a.noise, a.action, a.act_stride,
+                nullptr, nullptr);
+    return;
+  }
+  const int k = e - n_mlp;
+  const float* row = a.s.lstm_params + (size_t)k * a.Pl;   // p/emb/w | p/emb/b | lstmp/kernel | lstmp/bias | p/out/w | p/out/b | logstd
+  const float* filt = a.s.lstm_filt + (size_t)k * 2 * D;
+  ppo_lstm_net N;
+  N.ob_dim = D; N.emb_dim = H; N.hidden = H; N.ac_dim = A; N.gate_order = PPO_LSTM_GATES_IJFO; N.forget_bias = a.s.forget_bias;
+  N.obs_mean = filt; N.obs_invstd = filt + D; N.obs_clip = a.s.obs_clip;
+  N.emb_w = row; N.emb_b = N.emb_w + (size_t)D * H;
+  N.wx = N.emb_b + H; N.wh = N.wx + H * 4 * H; N.b = N.wh + H * 4 * H;
+  N.head_w = N.b + 4 * H; N.head_b = N.head_w + H * A; N.logstd = N.head_b + A;
+  N.vf_w = nullptr; N.vf_b = nullptr;
+  LstmArgs la;
+  la.pool = nullptr; la.tile_net = nullptr;
+  la.obs = a.obs; la.mask = nullptr; la.noise = a.noise; la.given = nullptr;
+  la.c = a.s.state; la.h = a.s.state + H; la.action = a.action; la.neglogp = nullptr; la.value = nullptr; la.mean = nullptr;
+  la.sv_gates = nullptr; la.sv_cprev = nullptr; la.sv_hprev = nullptr; la.sv_tanhc = nullptr; la.zinit = nullptr; la.sv_latent = nullptr;
+  la.n = a.n; la.obs_stride = a.obs_stride; la.state_stride = 2 * H; la.XS = a.XS; la.HP = H + 2;
+  lstm_step_tile<H, PPO_LSTM_GATES_IJFO, false, 4>(la, N, LstmMaskDone{a.done, a.done_stride}, a.act_stride);
+}
+
+extern "C" int ppo_zoo_seat_act(const ppo_zoo_seat* seat, const float* obs, int n, int obs_stride, const uint8_t* done, int done_stride,
+                                const float* noise, float* action_out, int act_stride, int32_t* status_dev, void* stream) {
+  if (!seat || !obs || !action_out) FAIL(-1, "bad arguments");
+  if (n < 16 || n % 16 != 0) FAIL(-2, "n = %d: a seat acts on whole tiles of 16 envs", n);
+  if (seat->ob_dim < 1 || seat->ob_dim > 512 || obs_stride < seat->ob_dim) FAIL(-3, "bad ob_dim/obs_stride");
+  if (seat->ac_dim < 1 || seat->ac_dim > MAXA || act_stride < seat->ac_dim) FAIL(-4, "ac_dim %d not in [1,%d], or act_stride below it", seat->ac_dim, MAXA);
+  if (seat->n_mlp < 0 || seat->n_lstm < 0 || seat->n_mlp + seat->n_lstm < 1) FAIL(-5, "a seat needs at least one zoo net");
+  if (seat->n_mlp > 0 && (!seat->mlp_params || !seat->mlp_filt)) FAIL(-6, "%d MLP rows without a table", seat->n_mlp);
+  if (seat->n_lstm > 0 && (!seat->lstm_params || !seat->lstm_filt)) FAIL(-6, "%d LSTM rows without a table", seat->n_lstm);
+  if (seat->n_lstm > 0 && !seat->state) FAIL(-7, "LSTM rows need a state");
+  if (!seat->tile_entry) FAIL(-8, "missing tile entries");
+  if (done && done_stride < 1) FAIL(-9, "done_stride %d", done_stride);
+  ZooSeatArgs a;
+  a.s = *seat; a.obs = obs; a.noise = noise; a.done = done; a.action = action_out; a.status = status_dev;
+  a.n = n; a.obs_stride = obs_stride; a.done_stride = done_stride; a.act_stride = act_stride;
+  a.XS = x_stride(seat->ob_dim);
+  a.L = make_layout(seat->ob_dim, seat->ac_dim);
+  a.Pl = seat->ob_dim * H + H + 2 * H * 4 * H + 4 * H + H * seat->ac_dim + 2 * seat->ac_dim;
+  // the LSTM layout x | emb | h_prev | h_new holds the MLP layout x | h1 | h2 (HP = H + 2 == HS)
+  const size_t lds = (size_t)(16 * a.XS + 16 * HS + 2 * 16 * (H + 2)) * sizeof(float);
+  static thread_local size_t lds_set = 0;
+  if (lds > 64 * 1024 && lds > lds_set) {
+    HIPCHK(hipFuncSetAttribute((const void*)ppo_zoo_seat_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    lds_set = lds;
+  }
+  hipLaunchKernelGGL(ppo_zoo_seat_kernel, dim3(n / 16), dim3(256), lds, (hipStream_t)stream, a);
+  HIPCHK(hipGetLastError());
+  return 0;
 }
 
 // ---- loss heads on stored latents: one thread per row (rows x hidden x (ac_dim + 1) MACs: small next to the recurrence)

@@ -12,7 +12,7 @@ _LIB = None
 EXPORTS = ("ppo_last_error", "ppo_param_count", "ppo_forward", "ppo_forward_filtered", "ppo_lstm_step", "ppo_lstm_step_pool", "ppo_lstm_step_save", "ppo_lstm_xproj", "ppo_lstm_step_save_z", "ppo_lstm_seq_forward", "ppo_lstm_seq_backward", "ppo_lstm_head_grad", "ppo_lstm_bwd_step", "ppo_lstm_wgrad_workspace_bytes", "ppo_lstm_wgrad", "ppo_selfplay_forward", "ppo_post_step", "ppo_reward_mix", "ppo_vtrace", "ppo_adv_moments", "ppo_adv_moments_ws", "ppo_adv_moments_workspace_bytes",
            "ppo_adv_normalize", "ppo_grad_workspace_bytes", "ppo_grad", "ppo_loss_stats", "ppo_clip_adam",
            "ppo_a2c_grad", "ppo_a2c_loss_stats", "ppo_selection_scores_workspace_bytes", "ppo_selection_scores",
-           "ppo_adv_moments_masked_ws", "ppo_adv_normalize_masked", "ppo_lstm_head_grad_masked")
+           "ppo_adv_moments_masked_ws", "ppo_adv_normalize_masked", "ppo_lstm_head_grad_masked", "ppo_zoo_seat_act")
 
 
 class PpoHipError(RuntimeError):
@@ -25,6 +25,13 @@ class LstmNet(C.Structure):
                 ("forget_bias", C.c_float), ("obs_mean", C.c_void_p), ("obs_invstd", C.c_void_p), ("obs_clip", C.c_float),
                 ("emb_w", C.c_void_p), ("emb_b", C.c_void_p), ("wx", C.c_void_p), ("wh", C.c_void_p), ("b", C.c_void_p),
                 ("head_w", C.c_void_p), ("head_b", C.c_void_p), ("logstd", C.c_void_p), ("vf_w", C.c_void_p), ("vf_b", C.c_void_p)]
+
+
+class ZooSeat(C.Structure):
+    """``ppo_zoo_seat`` of include/sumo_ppo.h: the zoo nets of one seat of a zoo-vs-zoo match (device pointers as integers)."""
+    _fields_ = [("mlp_params", C.c_void_p), ("mlp_filt", C.c_void_p), ("lstm_params", C.c_void_p), ("lstm_filt", C.c_void_p),
+                ("tile_entry", C.c_void_p), ("state", C.c_void_p), ("n_mlp", C.c_int), ("n_lstm", C.c_int), ("ob_dim", C.c_int),
+                ("ac_dim", C.c_int), ("obs_clip", C.c_float), ("forget_bias", C.c_float)]
 
 
 def fill_lstm_net_ifou(n, ob_dim, ac_dim, nlstm, addrs):
@@ -61,6 +68,7 @@ def lib():
         L.ppo_lstm_wgrad_workspace_bytes.argtypes = [i32, i32, i32]
         L.ppo_lstm_wgrad_workspace_bytes.restype = C.c_size_t
         L.ppo_lstm_wgrad.argtypes = [C.POINTER(LstmNet), i32, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp]
+        L.ppo_zoo_seat_act.argtypes = [C.POINTER(ZooSeat), vp, i32, i32, vp, i32, vp, vp, i32, vp, vp]
         L.ppo_reward_mix.argtypes = [vp, i32, f64, vp, i32, vp]
         L.ppo_selfplay_forward.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, C.POINTER(vp), C.POINTER(vp), vp]
         L.ppo_post_step.argtypes = [vp, i32, f64, vp, i32, vp, vp, vp, vp, vp, vp, vp]

@@ -3,7 +3,8 @@
 Per update: opponent selection from the checkpoint directory, one rollout of ``nsteps`` steps (``runner.run(update)``: the fused
 ``sumo_rollout_steps`` launch with MLP policies), optional reuse of the opponent's samples, then ONE optimiser step of
 ``ActorCriticModel`` on the whole batch (no minibatches, no epochs: nbatch_train = nbatch, alg_ac.py:110-111).  Rollout buffers
-stay in HBM.  Not reproduced: TF summaries, the eval runner, matplotlib histograms.
+stay in HBM.  Not reproduced: TF summaries, matplotlib histograms; the reference's ``eval_env`` runner is replaced by the
+evaluation of train_eval.py (``eval_interval`` / ``eval_opponents``).
 
 Decisions on the reference's A2C path:
   1. alg_ac.py:153 builds its Runner without ``rho_bar`` / ``c_bar``, which runner.py:36 requires (TypeError before the first step).
@@ -45,10 +46,17 @@ def check_config(network, use_opponent_data, comm):
 def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_data=None, eval_env=None, seed=None, nsteps=2048,
           ent_coef=0.0, lr=3e-4, vf_coef=0.5, max_grad_norm=0.5, gamma=0.99, lam=0.95, log_interval=10, save_interval=1,
           load_path=None, model_fn=None, update_fn=None, init_fn=None, mpi_rank_weight=1, comm=None, nagent=1, anneal_bound=500,
-          fix_opponent_path=None, rho_bar=10.0, c_bar=1.0, log_dir=None, verbose=True, opponent_pool=1, fused_fix_opponent=False, **network_kwargs):
+          fix_opponent_path=None, rho_bar=10.0, c_bar=1.0, log_dir=None, verbose=True, opponent_pool=1, fused_fix_opponent=False,
+          run_log=False, eval_interval=0, eval_opponents=None, eval_trials=64, eval_num_env=64, eval_deterministic=True, eval_seed=0,
+          eval_cross_family=False, **network_kwargs):
+    """``run_log`` and the ``eval_*`` arguments as in ``alg_ppo.learn``: the run's files (runlog.py) and the evaluation of the live
+    learner against fixed opponents (train_eval.py), on ``eval_env`` or an env of its own; off by default."""
     check_config(network, use_opponent_data, comm)
     if opponent_mode not in ("ours", "random", "latest", "fix"):
         raise ValueError("opponent_mode %r" % (opponent_mode,))
+    from . import train_eval
+    eval_plan = train_eval.plan_for(env, network, network_kwargs, eval_env=eval_env, eval_interval=eval_interval, eval_opponents=eval_opponents,
+                                    eval_trials=eval_trials, eval_num_env=eval_num_env, eval_cross_family=eval_cross_family)
     import torch
     from .a2c_model import ActorCriticModel
     from .policies import build_policy
@@ -96,6 +104,9 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
                    league_scores=[], league_tiles=[])       # fix mode with a list of files: per update and member (alg_ppo.league_note)
     env_stats_prev = env.stats() if hasattr(env, "stats") else None
     nupdates = total_timesteps // nbatch
+    report = train_eval.Report(run_log=run_log, plan=eval_plan, log_dir=log_dir, env=env, model=model, history=history, eval_env=eval_env,
+                               deterministic=eval_deterministic, seed=eval_seed, first_checkpoint=osp.join(checkdir, "00000"),
+                               log_interval=log_interval, verbose=verbose, opponent_mode=opponent_mode)
     loaded = None        # the checkpoint(s) the opponent holds: re-read from disk only when the selection changes
     league = None        # fix mode with a list of files: the policy_zoo.ZooLeague on agent 1
     for update in range(1, nupdates + 1):
@@ -158,8 +169,14 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
         lg_note = league_note(history, runner, league)
         if update_fn is not None:
             update_fn(update)
-        if verbose and (update % log_interval == 0 or update == 1):
+        log_now = update % log_interval == 0 or update == 1
+        logged = report.update(update, nupdates, update * nbatch, epinfos)       # evaluates where due; is a row of the run log due?
+        if logged or (verbose and log_now):
             ev = explained_variance(b_val.cpu().numpy(), b_ret.cpu().numpy())
+        if logged:
+            report.log(update=update, nsteps=nsteps, nbatch=nbatch, explained_variance=ev, epinfobuf=epinfobuf,
+                       time_elapsed=tnow - tfirststart, lossvals=lossvals, league=league)
+        if verbose and log_now:
             opp = history["opponent_versions"][-1]
             print("update %d/%d  opponent %s  fps %.0f  rollout %.2fms  update %.2fms  ev %.3f  eprewmean %.2f  eplenmean %.1f  %s" % (
                 update, nupdates, opp[0] if opp else "fix", history["fps"][-1], 1e3 * t_roll, 1e3 * history["update_s"][-1], ev,
@@ -169,6 +186,7 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
             print("update %d/%d%s" % (update, nupdates, env_note), flush=True)
         if save_interval and (update % save_interval == 0 or update == 1):
             model.save(osp.join(checkdir, "%.5i" % update))               # alg_ac.py:333-339
+    report.close()
     model.history = history
     model.time_elapsed = time.perf_counter() - tfirststart
     return model

@@ -16,6 +16,7 @@ from collections import deque
 import numpy as np
 
 from . import dist as sdist
+from . import train_eval
 from .model import PPOModel
 from .policies import build_policy, init_param_list
 from .policy_selector import selection_probs_from_scores
@@ -228,9 +229,16 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
           nminibatches=4, noptepochs=4, cliprange=0.2, save_interval=1, load_path=None, model_fn=None, update_fn=None, init_fn=None,
           nagent=1, anneal_bound=500, vgap=None, kl_threshold=None, neglogp_threshold=10000.0, log_dir=None, comm=None,
           verbose=True, fix_opponent_path=None, opponent_pool=1, fused_fix_opponent=False, fused_selector=False, selector_table_mb=1024,
-          **network_kwargs):
+          run_log=False, eval_interval=0, eval_opponents=None, eval_trials=64, eval_num_env=64, eval_deterministic=True, eval_seed=0,
+          eval_cross_family=False, **network_kwargs):
+    """``run_log=True`` writes the run's files into ``log_dir`` (runlog.py); ``eval_interval`` / ``eval_opponents`` make rank 0 play the
+    live learner against fixed opponents every so many updates (train_eval.py), on ``eval_env`` (the reference's parameter) or on
+    an env of its own.  With the defaults neither happens and the run writes and draws exactly what it did without them."""
     if fused_selector:
         check_fused_selector(network, opponent_mode, model_fn)
+    # evaluation: everything unsupported is refused here, before anything touches the device (None: evaluation is off)
+    eval_plan = train_eval.plan_for(env, network, network_kwargs, eval_env=eval_env, eval_interval=eval_interval, eval_opponents=eval_opponents,
+                                    eval_trials=eval_trials, eval_num_env=eval_num_env, eval_cross_family=eval_cross_family)
     import torch
     if seed is not None:                                                # set_global_seeds (misc_util.py:48-62)
         np.random.seed(seed)
@@ -329,6 +337,10 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
                    env_diverged=[], env_dropped_contacts=[], env_rollout_aborts=[],     # per update, from the engine's counters
                    league_scores=[], league_tiles=[])       # fix mode with a list of files: per update and member (league_note)
     env_stats_prev = env.stats() if hasattr(env, "stats") else None
+    # rank 0 reports: the evaluator loads its opponents here, once (the other ranks meet it at the loop's barrier)
+    report = train_eval.Report(run_log=run_log, plan=eval_plan, log_dir=log_dir, env=env, model=model, history=history, eval_env=eval_env,
+                               deterministic=eval_deterministic, seed=eval_seed, first_checkpoint=osp.join(checkdir, "00000"),
+                               log_interval=log_interval, verbose=verbose, opponent_mode=opponent_mode) if rank == 0 else None
     idx_choice = 0
     opponent_obs = opponent_actions = None
     league = None
@@ -488,8 +500,14 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
         lg_note = league_note(history, runner, league)
         if update_fn is not None:
             update_fn(update)
-        if verbose and rank == 0 and (update % log_interval == 0 or update == 1):
+        log_now = update % log_interval == 0 or update == 1
+        logged = report is not None and report.update(update, nupdates, update * nbatch * world, epinfos)       # evaluates where due; is a row of the run log due?
+        if rank == 0 and (logged or (verbose and log_now)):
             ev = explained_variance(b_val.cpu().numpy(), b_ret.cpu().numpy())
+        if logged:
+            report.log(update=update, nsteps=nsteps, nbatch=nbatch * world, explained_variance=ev, epinfobuf=epinfobuf,
+                       time_elapsed=tnow - tfirststart, lossvals=lossvals, league=league)
+        if verbose and rank == 0 and log_now:
             print("update %d/%d  fps %.0f  rollout %.2fs  sgd %.2fs  ev %.3f  eprewmean %.2f  eplenmean %.1f  %s" % (
                 update, nupdates, history["fps"][-1], t_roll, tnow - tstart - t_roll, ev, safemean([e["r"] for e in epinfobuf]),
                 safemean([e["l"] for e in epinfobuf]), " ".join("%s %.4g" % (n, v) for n, v in zip(model.loss_names, lossvals))) + lg_note + env_note,
@@ -501,6 +519,8 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
         if comm is not None:
             sdist.assert_synced(model.params, comm)                       # MpiAdamOptimizer.check_synced (mpi_adam_optimizer.py:54-67)
             torch.distributed.barrier(comm)
+    if report is not None:
+        report.close()
     model.history = history
     model.time_elapsed = time.perf_counter() - tfirststart
     return model

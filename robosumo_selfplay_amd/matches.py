@@ -274,7 +274,11 @@ def _check_env(env, table):
                          "ac_dim %d / %d" % (D0, D1, A0, A1))
     if (table.spec.ob_dim, table.spec.ac_dim) != (D0, A0):
         raise ValueError("snapshot table's policy (%d, %d) does not match the env (%d, %d)" % (table.spec.ob_dim, table.spec.ac_dim, D0, A0))
-    if getattr(env, "cfrc_mode", "zero") != "zero":
+    _check_cfrc_mode(getattr(env, "cfrc_mode", "zero"))
+
+
+def _check_cfrc_mode(cfrc_mode):
+    if cfrc_mode != "zero":
         raise ValueError("matches run on the fused launch, which refuses cfrc_mode 'rne_post'")
 
 
@@ -518,10 +522,14 @@ def match_steps_stepwise_lstm(env, table, idx0, idx1, states, score, quota, K, n
 
 def _check_zoo(env, table, zoo_table):
     _check_env(env, table)
+    _check_zoo_family(table, zoo_table)
+    _check_zoo_dims(table, zoo_table)
+
+
+def _check_zoo_family(table, zoo_table):
     if getattr(table, "recurrent", False) and not getattr(zoo_table, "recurrent", False):
         raise ValueError("LSTM checkpoints do not play against zoo MLP nets in the fused launch (MLP(64,64) checkpoints only; LSTM "
                          "checkpoints play against zoo LSTM nets, a ZooLstmTable)")
-    _check_zoo_dims(table, zoo_table)
 
 
 def _check_zoo_dims(table, zoo_table):

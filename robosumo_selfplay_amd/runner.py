@@ -59,6 +59,10 @@ class EpInfoList(object):
     def _make(self, i):
         return {"r": float(self._r[i]), "l": int(self._l[i]), "t": 0.0}
 
+    def arrays(self):
+        """The episodes' returns and lengths as two arrays (what the run log's monitor file writes without building the dicts)."""
+        return self._r, self._l
+
     def __getitem__(self, i):
         if isinstance(i, slice):
             return EpInfoList(self._r[i], self._l[i])

@@ -2,6 +2,9 @@
 """CLI counterpart of the reference's run.py (run.py:211-251) for the hot path:
     python run.py --env RoboSumo-Ant-vs-Ant-v0 --num_env 4096 --num_timesteps 2097152 --nsteps=128
     python run.py --env RoboSumo-Ant-vs-Ant-v0 --algo ac --num_env 1024 --num_timesteps 512000      (A2C learner, one GPU)
+    python run.py --env RoboSumo-Ant-vs-Ant-v0 --num_env 1024 --nsteps=128 --eval_interval 5 --eval_opponent 00000 \\
+        --eval_opponent <zoo>/ant/mlp/agent-params-v1.npy      (play the live learner against fixed opponents every 5 updates)
+The run directory gets the reference's run files (log.txt, progress.csv, 0.0.monitor.csv, its pickles; ``--no_run_log``: none).
 Unknown ``--key=value`` flags are forwarded to ``learn`` like the reference does (run.py:29-63), but parsed with
 ``ast.literal_eval`` instead of ``eval``.  Under ``torchrun`` every rank takes an equal shard of ``--num_env``.
 """
@@ -58,7 +61,35 @@ def build_parser():
     ap.add_argument("--selector_table_mb", type=float, default=None, help="--fused_selector: device memory the checkpoint table may take, in MiB "
                     "(default 1024).  A run whose checkpoints fit gets one row per checkpoint, allocated before the first update; a longer run, "
                     "or a smaller value here, gets the 32-row staging table (3 MiB on Ant) refilled from the sampled files each update")
+    ap.add_argument("--no_run_log", action="store_true", help="do not write the run's files (log.txt, progress.csv, 0.0.monitor.csv, history.json, "
+                    "the reference's pickles; robosumo_selfplay_amd/runlog.py).  They are written by default, as the reference's run.py always "
+                    "configures its logger on the run directory")
+    ap.add_argument("--eval_interval", type=int, default=0, help="evaluate the live learner against the --eval_opponent list every so many "
+                    "updates (and at the first and the last), inside the training process (robosumo_selfplay_amd/train_eval.py); 0 = never")
+    ap.add_argument("--eval_opponent", action="append", default=None, help="an evaluation opponent, repeatable: a policy-zoo .npy file (MLP or "
+                    "LSTM), 00000 (the run's own first checkpoint) or a checkpoint path of the learner's family")
+    ap.add_argument("--eval_trials", type=int, default=None, help="games per evaluation and opponent (default 64)")
+    ap.add_argument("--eval_num_env", type=int, default=None, help="envs of the evaluation env (default 64)")
+    ap.add_argument("--eval_stochastic", action="store_true", help="sample the evaluated actions (default: the mode, as the reference's evaluator)")
+    ap.add_argument("--eval_cross_family", action="store_true", help="let an LSTM learner play zoo MLP files in its evaluation (refused otherwise)")
     return ap
+
+
+def eval_kwargs(args):
+    """The ``learn`` keywords of the run-log and evaluation flags; the evaluation ones only where they were given."""
+    kw = dict(run_log=not args.no_run_log)
+    if args.eval_interval:
+        kw["eval_interval"] = args.eval_interval
+    if args.eval_opponent:
+        kw["eval_opponents"] = list(args.eval_opponent)
+    for k in ("eval_trials", "eval_num_env"):
+        if getattr(args, k) is not None:
+            kw[k] = getattr(args, k)
+    if args.eval_stochastic:
+        kw["eval_deterministic"] = False
+    if args.eval_cross_family:
+        kw["eval_cross_family"] = True
+    return kw
 
 
 def main(argv):
@@ -69,6 +100,7 @@ def main(argv):
     learn = {"ppo": alg_ppo.learn, "ac": alg_ac.learn}.get(args.algo)
     kw = defaults.get_default_params(args.env, args.algo)       # (td3 / unknown algorithms stop here)
     kw.update(extra)
+    kw.update(eval_kwargs(args))
     if args.fused_fix_opponent:
         kw["fused_fix_opponent"] = True
     if args.fused_selector:

@@ -410,6 +410,11 @@ int sumo_static_layout(sumo_handle_t h);
  * (tools/gen_static_layout.py) */
 int sumo_debug_layout(const void* model_blob, size_t nbytes, int32_t* out, int cap);
 int sumo_debug_model_ints(const void* model_blob, size_t nbytes, int32_t* out, int cap, int32_t* aux_out, int aux_cap);
+/* development / tests, host only (no device): the two packed role words of each of the 64 lanes, out[2 * lane] and out[2 * lane + 1]
+ * (cap >= 128) -- the small integers of a lane's body, dof and joint roles that the kernels keep in registers (bit fields: ROLE0_* /
+ * ROLE1_* in csrc/sumo_engine.hip; tests/test_lane_roles_cpu.py unpacks them).  Returns 128, or the error sumo_create gives for a scene
+ * in which a value does not fit its field. */
+int sumo_debug_lane_roles(const void* model_blob, size_t nbytes, uint32_t* out, int cap);
 /* development (-DSUMO_DBG_DUMP builds): device buffer [20][8][64] float64 that receives intermediate vectors of env 0's forward
  * evaluations (tools/dump_diff.py); NULL = off */
 int sumo_debug_dump(sumo_handle_t h, double* dev_buf);

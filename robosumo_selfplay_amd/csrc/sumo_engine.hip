@@ -440,7 +440,36 @@ struct LaneRec {
   // actuator role
   double a_gear, a_lo, a_hi;
   int a_dof, pad_;
+  // the lane's small integers of all roles, packed (build_lane_roles; ROLE0_* / ROLE1_* below): read once per launch into Ctx
+  unsigned role0, role1;
 };
+// Bit fields of the two role words, {first bit, width}.  A lane keeps them in two registers for the whole launch, so the address
+// arithmetic and the branches of a phase do not wait for the constant record: what a phase still reads from the record (its doubles,
+// the chain bytes) travels while the LDS reads are already in flight.  build_lane_roles refuses a scene whose field does not fit.
+//   role0  body role: level + 1 (0: lane is no body), agent, joint is free, joint is a hinge, parent, number of children, lengths of
+//          the dof chain and of the body chain, qpos address of the joint; joint role: is a hinge, limited, agent
+//   role1  dof role: hinge index + 1 (0: none), position in its body's dof chain, body; joint role: free joints before it (from
+//          which dof address = j + 5 f, qpos address = j + 6 f, hinge index = j - f follow: free joints carry 6 dofs / 7 qpos,
+//          hinges 1 / 1), body; body role: last dof of its chain
+#define ROLE0_LEVEL1 0, 3
+#define ROLE0_AGENT 3, 1
+#define ROLE0_ISFREE 4, 1
+#define ROLE0_HINGE 5, 1
+#define ROLE0_PARENT 6, 6
+#define ROLE0_NCHILD 12, 4
+#define ROLE0_CHAIN_LEN 16, 4
+#define ROLE0_BCHAIN_LEN 20, 3
+#define ROLE0_QADR 23, 6
+#define ROLE0_JT_HINGE 29, 1
+#define ROLE0_JT_LIMITED 30, 1
+#define ROLE0_JT_AGENT 31, 1
+#define ROLE1_HID1 0, 6
+#define ROLE1_DPOS 6, 4
+#define ROLE1_DBODY 10, 6
+#define ROLE1_JT_NFREE 16, 2
+#define ROLE1_JT_BODY 18, 6
+#define ROLE1_LDOF 24, 6
+__host__ __device__ __forceinline__ int role_bits(unsigned w, int lo, int n) { return (int)((w >> lo) & ((1u << n) - 1u)); }
 
 struct Params {  // lives in device memory; read through scalar / per-lane loads
   sumo_model_t mdl; Aux aux; Layout L;
@@ -464,7 +493,7 @@ struct Ctx {
   int* si;       // LDS int region
   unsigned char* sb;  // LDS byte region (slotof)
   int lane;
-  int hid, dpos;   // this lane's dof: hinge index (-1: none) and position in its body's dof chain
+  unsigned role0, role1;   // this lane's packed integer roles (LaneRec::role0 / role1), read through the role_*() accessors
   // per-forward scalars (wave-uniform)
   int ncon, nlim, nefc, ndropped, use_prev, htree;  // htree: every contact has one moving body -> H is tree-sparse like M
 #ifdef SUMO_PROFILE
@@ -517,6 +546,30 @@ __device__ __forceinline__ T load_rec(const T* p) {
   return out;
 }
 #define KCONSTS() const LaneRec K = load_rec(launder_ptr(c.kp))
+// the lane's integer roles, from the two role words in registers (no memory access)
+// The word is made opaque at every use: the words are loop invariant, and fields the compiler may extract once would each occupy a
+// register of their own for the whole launch -- the budget that the per-phase record reads and the opaque lane id protect.
+__device__ __forceinline__ int role_get(unsigned w, int lo, int n) { asm volatile("" : "+v"(w)); return role_bits(w, lo, n); }
+template <class C> __device__ __forceinline__ int role_level(const C& c) { return role_get(c.role0, ROLE0_LEVEL1) - 1; }
+template <class C> __device__ __forceinline__ int role_agent(const C& c) { return role_get(c.role0, ROLE0_AGENT); }
+template <class C> __device__ __forceinline__ bool role_isfree(const C& c) { return role_get(c.role0, ROLE0_ISFREE) != 0; }
+template <class C> __device__ __forceinline__ bool role_hinge(const C& c) { return role_get(c.role0, ROLE0_HINGE) != 0; }   // the body's joint is a hinge
+template <class C> __device__ __forceinline__ int role_parent(const C& c) { return role_get(c.role0, ROLE0_PARENT); }
+template <class C> __device__ __forceinline__ int role_nchild(const C& c) { return role_get(c.role0, ROLE0_NCHILD); }
+template <class C> __device__ __forceinline__ int role_chain_len(const C& c) { return role_get(c.role0, ROLE0_CHAIN_LEN); }
+template <class C> __device__ __forceinline__ int role_bchain_len(const C& c) { return role_get(c.role0, ROLE0_BCHAIN_LEN); }
+template <class C> __device__ __forceinline__ int role_qadr(const C& c) { return role_get(c.role0, ROLE0_QADR); }
+template <class C> __device__ __forceinline__ int role_ldof(const C& c) { return role_get(c.role1, ROLE1_LDOF); }
+template <class C> __device__ __forceinline__ int role_d_hid(const C& c) { return role_get(c.role1, ROLE1_HID1) - 1; }   // -1: free-joint dof, lane past nv
+template <class C> __device__ __forceinline__ int role_d_pos(const C& c) { return role_get(c.role1, ROLE1_DPOS); }
+template <class C> __device__ __forceinline__ int role_d_body(const C& c) { return role_get(c.role1, ROLE1_DBODY); }
+template <class C> __device__ __forceinline__ bool role_jt_hinge(const C& c) { return role_get(c.role0, ROLE0_JT_HINGE) != 0; }   // else a free joint
+template <class C> __device__ __forceinline__ bool role_jt_limited(const C& c) { return role_get(c.role0, ROLE0_JT_LIMITED) != 0; }
+template <class C> __device__ __forceinline__ int role_jt_agent(const C& c) { return role_get(c.role0, ROLE0_JT_AGENT); }
+template <class C> __device__ __forceinline__ int role_jt_body(const C& c) { return role_get(c.role1, ROLE1_JT_BODY); }
+template <class C> __device__ __forceinline__ int role_jt_dadr(const C& c) { return c.lane + 5 * role_get(c.role1, ROLE1_JT_NFREE); }
+template <class C> __device__ __forceinline__ int role_jt_qadr(const C& c) { return c.lane + 6 * role_get(c.role1, ROLE1_JT_NFREE); }
+template <class C> __device__ __forceinline__ int role_jt_hid(const C& c) { return c.lane - role_get(c.role1, ROLE1_JT_NFREE); }
 // mass matrix element (i, j) of the block-diagonal storage; valid when i and j belong to the same agent tree
 #define MIDX(i, j) ((i) * c.L.mld + ((j) >= c.L.d1 ? (j) - c.L.d1 : (j)))
 #define SAME_TREE(i, j) (((i) >= c.L.d1) == ((j) >= c.L.d1))
@@ -598,22 +651,22 @@ __device__ __forceinline__ void kin_inertial_frames(C& c) {   // every body lane
 // of a read-modify-write chain per child.
 template <int W, int NCH, class C>
 __device__ __forceinline__ void gather_up_n(C& c, double* arr) {
-  KCONSTS();
-  const int b = c.lane;
+  KCONSTS();   // the child ids (b_child) stay in the record
+  const int b = c.lane, level = role_level(c), nchild = role_nchild(c);
   for (int lvl = c.P->aux.ndepth - 2; lvl >= 1; lvl--) {
-    if (K.b_level == lvl && K.b_nchild > 0) {
+    if (level == lvl && nchild > 0) {
       double acc[W], ch[NCH][W];
 #pragma unroll
       for (int k = 0; k < W; k++) acc[k] = arr[W * b + k];
 #pragma unroll
       for (int ci = 0; ci < NCH; ci++) {
-        const int cb = BYTE_OF(K.b_child, ci < K.b_nchild ? ci : 0);
+        const int cb = BYTE_OF(K.b_child, ci < nchild ? ci : 0);
 #pragma unroll
         for (int k = 0; k < W; k++) ch[ci][k] = arr[W * cb + k];
       }
 #pragma unroll
       for (int ci = 0; ci < NCH; ci++)
-        if (ci < K.b_nchild) {
+        if (ci < nchild) {
 #pragma unroll
           for (int k = 0; k < W; k++) acc[k] += ch[ci][k];
         }
@@ -661,7 +714,7 @@ __device__ __forceinline__ void position_velocity(C& c) {
     const bool isb = lane >= 1 && lane < nb;
     double px = 0, py = 0, pz = 0;
     if (isb) { px = K.b_mass * S(xipos)[3 * lane]; py = K.b_mass * S(xipos)[3 * lane + 1]; pz = K.b_mass * S(xipos)[3 * lane + 2]; }
-    const int ag = isb ? K.b_agent : -1;
+    const int ag = isb ? role_agent(c) : -1;
     // six independent wave sums (x, y, z of both agents) issued together so their DPP chains overlap
     const double s0x = wave_sum(ag == 0 ? px : 0.0), s0y = wave_sum(ag == 0 ? py : 0.0), s0z = wave_sum(ag == 0 ? pz : 0.0);
     const double s1x = wave_sum(ag == 1 ? px : 0.0), s1y = wave_sum(ag == 1 ? py : 0.0), s1z = wave_sum(ag == 1 ? pz : 0.0);
@@ -674,7 +727,7 @@ __device__ __forceinline__ void position_velocity(C& c) {
   // cinert per body, cdof per joint
   if (lane >= 1 && lane < nb) {
     KCONSTS();
-    const int b = lane, ag = K.b_agent;
+    const int b = lane, ag = role_agent(c);
     double R[9], cp[3], dif[3], RI[9], T[6];
     quat2mat(R, S(xquat) + 4 * b);
     mulmatvec3(cp, R, K.c_ipos);
@@ -704,11 +757,10 @@ __device__ __forceinline__ void position_velocity(C& c) {
     res[9] = ms;
   }
   if (lane < mdl.njnt) {
-    KCONSTS();
-    const int j = lane, b = K.jt_body, da = K.jt_dadr, ag = K.jt_agent;
+    const int j = lane, b = role_jt_body(c), da = role_jt_dadr(c), ag = role_jt_agent(c);
     double off[3];
     for (int k = 0; k < 3; k++) off[k] = S(com)[3 * ag + k] - S(xanchor)[3 * j + k];
-    if (K.jt_type == SUMO_JNT_FREE) {
+    if (!role_jt_hinge(c)) {
       double R[9];
       quat2mat(R, S(xquat) + 4 * b);
       for (int k = 0; k < 3; k++) {
@@ -736,9 +788,12 @@ __device__ __forceinline__ void position_velocity(C& c) {
   if (c.L.tree_ok && lane >= 1 && lane < nb) {
     // every body hangs off a free joint (6 dofs) plus at most two hinges (Layout::tree_ok): fixed shape, all loads of the
     // chain's motion axes issued together instead of one round trip per chain element
-    KCONSTS();
-    const int b = lane, len = K.b_chain_len;
-    const int B = BYTE_OF(K.b_chain, 0), j6 = BYTE_OF(K.b_chain, len > 6 ? 6 : 0), j7 = BYTE_OF(K.b_chain, len > 7 ? 7 : 0);
+    // The chain needs no record read in this shape: its first six dofs are the root's (B .. B + 5), a seventh is the hip and
+    // an eighth the ankle below it, i.e. the chain's last dof and the one before it.  A body owns the root dofs if its joint
+    // is the free one and the chain's last dof if its joint is a hinge (build_lane_roles checks all of it against the chains).
+    const int b = lane, len = role_chain_len(c), ld = role_ldof(c);
+    const int B = role_agent(c) ? c.L.d1 : 0, j6 = len > 7 ? ld - 1 : (len > 6 ? ld : B), j7 = len > 7 ? ld : B;
+    const bool own_root = role_isfree(c), own_last = role_hinge(c);
     const double* qvel = S(qvel);
     double cd[8][6], qv[8], a[6] = {0, 0, 0, 0, 0, 0}, t[6];
 #pragma unroll
@@ -752,7 +807,7 @@ __device__ __forceinline__ void position_velocity(C& c) {
     for (int k = 0; k < 3; k++)
 #pragma unroll
       for (int q = 0; q < 6; q++) cvel[q] += cd[k][q] * qv[k];
-    if (K.b_chain_own & 1u) {
+    if (own_root) {
 #pragma unroll
       for (int k = 3; k < 6; k++) {
         cross_motion(t, cvel, cd[k]);
@@ -767,7 +822,7 @@ __device__ __forceinline__ void position_velocity(C& c) {
 #pragma unroll
     for (int k = 6; k < 8; k++) {
       if (k < len) {
-        if ((K.b_chain_own >> k) & 1u) {
+        if (own_last && k == len - 1) {
           cross_motion(t, cvel, cd[k]);
 #pragma unroll
           for (int q = 0; q < 6; q++) a[q] += t[q] * qv[k];
@@ -817,19 +872,20 @@ __device__ __forceinline__ void position_velocity(C& c) {
     double* f = S(cfrc) + 6 * b;
     if (b == 0) { for (int q = 0; q < 6; q++) f[q] = 0; }
     else {
-      KCONSTS();
+      KCONSTS();   // the body chain (b_bchain) stays in the record
+      const int bclen = role_bchain_len(c);
       const double* g = MF(opt) + SUMO_OPT_GRAVITY;
       double cacc[6] = {0, 0, 0, -g[0], -g[1], -g[2]}, t[6], t1[6];
       double ab[MAXBCHAIN][6];
 #pragma unroll
       for (int p = 0; p < MAXBCHAIN; p++) {   // all loads in flight; entries past the chain re-read its first body
-        const int kb = (K.b_bchain >> (8 * (p < K.b_bchain_len ? p : 0))) & 0xFFu;
+        const int kb = (K.b_bchain >> (8 * (p < bclen ? p : 0))) & 0xFFu;
 #pragma unroll
         for (int q = 0; q < 6; q++) ab[p][q] = S(abuf)[6 * kb + q];
       }
 #pragma unroll
       for (int p = 0; p < MAXBCHAIN; p++)
-        if (p < K.b_bchain_len) {
+        if (p < bclen) {
 #pragma unroll
           for (int q = 0; q < 6; q++) cacc[q] += ab[p][q];
         }
@@ -841,7 +897,7 @@ __device__ __forceinline__ void position_velocity(C& c) {
   }
   SYNC();
   gather_up<6>(c, S(cfrc));
-  if (lane < nv) S(bias)[lane] = dot6(S(cdof) + 6 * lane, S(cfrc) + 6 * pt_global(launder_ptr(c.kp))->d_body);
+  if (lane < nv) S(bias)[lane] = dot6(S(cdof) + 6 * lane, S(cfrc) + 6 * role_d_body(c));
   PROF(3);
 }
 
@@ -864,7 +920,7 @@ __device__ __forceinline__ void mass_matrix(C& c) {
 #pragma unroll
       for (int q = 0; q < 6; q++) r[k][q] = S(cdof)[6 * (j < 0 ? 0 : j) + q];
     }
-    mul_inert_vec(buf, S(cinert) + 10 * K.d_body, ci);
+    mul_inert_vec(buf, S(cinert) + 10 * role_d_body(c), ci);
     double* Mi = S(M) + i * c.L.mld;
     Mi[il] = dot6(ci, buf) + K.d_arm;
 #pragma unroll
@@ -1202,11 +1258,11 @@ __device__ __forceinline__ void make_constraint(C& c) {
   // The Jacobian of a limit row is +-e_dof: the dof's own lane evaluates its rows without touching LDS row arrays.
   int act_lo = 0, act_hi = 0;
   if (lane < nv) ((unsigned long long*)S(cmask))[lane] = 0ull;
-  if (lane < mdl.njnt && K.jt_type == SUMO_JNT_HINGE) {
-    const int dof = K.jt_dadr;
-    const double jm = K.jt_margin, value = S(qpos)[K.jt_qadr], vel = S(qvel)[dof];
+  if (lane < mdl.njnt && role_jt_hinge(c)) {
+    const int dof = role_jt_dadr(c), limited = role_jt_limited(c);
+    const double jm = K.jt_margin, value = S(qpos)[role_jt_qadr(c)], vel = S(qvel)[dof];
     const double dlo = value - K.jt_lo, dhi = K.jt_hi - value;
-    act_lo = K.jt_limited && dlo < jm; act_hi = K.jt_limited && dhi < jm;
+    act_lo = limited && dlo < jm; act_hi = limited && dhi < jm;
     double D0 = 0, A0 = 0, D1 = 0, A1 = 0;
     if (act_lo) {
       double B, kt, R = row_params(timestep, def_solref, def_solimp, dlo, jm, K.jt_invw, &B, &kt);
@@ -1216,7 +1272,7 @@ __device__ __forceinline__ void make_constraint(C& c) {
       double B, kt, R = row_params(timestep, def_solref, def_solimp, dhi, jm, K.jt_invw, &B, &kt);
       D1 = fast_rcp(R); A1 = B * vel - kt;     // row = -e_dof: efc_vel = -qvel
     }
-    const int hid = K.jt_hid, nh = c.L.nhinge;
+    const int hid = role_jt_hid(c), nh = c.L.nhinge;
     S(limD)[hid] = D0; S(limD)[nh + hid] = D1; S(limA)[hid] = A0; S(limA)[nh + hid] = A1;
   }
   const int nlim = __popcll(__ballot(act_lo)) + __popcll(__ballot(act_hi));
@@ -1333,10 +1389,10 @@ __device__ __forceinline__ double row_Jx(const C& c, int r) {
 struct LimRows { double D0, D1, A0, A1; };
 template <class C>
 __device__ __forceinline__ LimRows lim_rows(const C& c) {
-  const int nh = c.L.nhinge, h = c.hid < 0 ? 0 : c.hid;
+  const int nh = c.L.nhinge, hid = role_d_hid(c), h = hid < 0 ? 0 : hid;
   LimRows q;
   q.D0 = c.sm[c.L.limD + h]; q.D1 = c.sm[c.L.limD + nh + h]; q.A0 = c.sm[c.L.limA + h]; q.A1 = c.sm[c.L.limA + nh + h];
-  if (c.hid < 0) q.D0 = q.D1 = 0.0;     // free-joint dofs and lanes past nv carry no limit
+  if (hid < 0) q.D0 = q.D1 = 0.0;     // free-joint dofs and lanes past nv carry no limit
   return q;
 }
 
@@ -1682,7 +1738,7 @@ __device__ __forceinline__ void newton_solve(C& c) {
       if (j1 < 0) { qc += lq.D1 * j1; dl += lq.D1; }   // row -e_dof
       for (unsigned long long mk = ((const unsigned long long*)S(cmask))[lane]; mk; mk &= mk - 1) {
         int ci = __builtin_ctzll(mk);
-        const int s = SLOT_OF(ci, lane, c.dpos);
+        const int s = SLOT_OF(ci, lane, role_d_pos(c));
         const int info = (c.si + c.L.con_b)[4 * ci + 3], ns = (info >> 20) ? 16 : 8;
         const double* Jb = S(Jb) + (info & 0xFFFFF);
         const double* cp = S(cp) + 3 * ci;
@@ -1898,10 +1954,9 @@ __device__ __forceinline__ void forward(C& c) {
 // qpos '+'= h * vel  (vel in LDS), one lane per joint
 template <class C>
 __device__ __forceinline__ void integrate_pos(C& c, double* qpos, const double* vel, double h) {
-  KCONSTS();
   if (c.lane < c.P->mdl.njnt) {
-    const int qa = K.jt_qadr, da = K.jt_dadr;
-    if (K.jt_type == SUMO_JNT_FREE) {
+    const int qa = role_jt_qadr(c), da = role_jt_dadr(c);
+    if (!role_jt_hinge(c)) {
       for (int k = 0; k < 3; k++) qpos[qa + k] += h * vel[da + k];
       double ax[3] = {vel[da + 3], vel[da + 4], vel[da + 5]}, qr[4], q[4] = {qpos[qa + 3], qpos[qa + 4], qpos[qa + 5], qpos[qa + 6]};
       double ang = h * normalize3(ax);
@@ -2114,8 +2169,8 @@ __device__ __forceinline__ void ctx_init(C& c, const Params* P, double* smem) {
     const double* wpos = P->aux.af + P->aux.o_wpa;
     for (int i = c.lane; i < 3 * nw; i += WAVE) { smem[P->L.xipos + 3 * nb + i] = wpos[i]; smem[P->L.gaxis + 3 * nb + i] = wpos[3 * nw + i]; }
   }
-  c.hid = c.lane < P->mdl.nv ? P->lanes[c.lane].d_hid : -1;
-  c.dpos = P->lanes[c.lane].d_pos;
+  c.role0 = P->lanes[c.lane].role0;
+  c.role1 = P->lanes[c.lane].role1;
   __syncthreads();
   c.ncon = c.nlim = c.nefc = c.ndropped = c.use_prev = 0;
   c.st_forward = c.st_newton = c.st_ncon = c.st_nefc = c.st_maxcon = c.st_maxefc = c.st_maxnewton = c.st_dropped = c.st_dense = c.st_cross = 0;
@@ -2485,7 +2540,7 @@ sumo_cfrc_kernel(const Params* P, StepArgs a, CfrcArgs q) {
   const int nc2 = c.ncon < ncon ? c.ncon : ncon;   // (make_constraint may have cut the list to the Jacobian pool)
   KCONSTS();
   double w[6] = {0, 0, 0, 0, 0, 0};
-  const int b = lane, ag = K.b_agent;   // one body per lane: build_aux refuses scenes with nbody > WAVE at sumo_create ("scene too large for one wavefront per env")
+  const int b = lane, ag = role_agent(c);   // one body per lane: build_aux refuses scenes with nbody > WAVE at sumo_create ("scene too large for one wavefront per env")
   if (b > 0 && b < nb) {
     const double* com = S(com) + 3 * ag;
     for (int ci = 0; ci < nc2; ci++) {
@@ -4122,6 +4177,64 @@ static void build_layout(sumo_engine* E) {
   if (lds_cu / E->L.total_bytes != slots) build_layout_with(E, 0);   // (cannot happen: the growth was sized to fit)
 }
 
+// The two role words of every lane (LaneRec::role0 / role1), packed from the records build_aux filled; after build_layout, whose
+// tree_ok decides whether the kernels derive chain elements from the words.  Nothing is truncated: a value that does not fit its
+// field, or a scene in which a derived quantity differs from the model's, fails creation.
+static int build_lane_roles(sumo_engine* E) {
+  const sumo_model_t* m = &E->hm;
+  const char* bad = nullptr; int bad_lane = 0; long bad_val = 0;
+  int nfree = 0;   // free joints before joint l
+  for (int l = 0; l < WAVE; l++) {
+    LaneRec& K = E->lanes[l];
+    unsigned w[2] = {0u, 0u};
+    auto put = [&](int wi, int lo, int n, long v, const char* what) {
+      if ((v < 0 || v >= (1L << n)) && !bad) { bad = what; bad_lane = l; bad_val = v; }
+      w[wi] |= ((unsigned)v & ((1u << n) - 1u)) << lo;
+    };
+    const int hinge = l < m->nbody && K.b_jnt >= 0 && !K.b_isfree;
+    put(0, ROLE0_LEVEL1, K.b_level + 1, "b_level");
+    put(0, ROLE0_AGENT, K.b_agent, "b_agent");
+    put(0, ROLE0_ISFREE, K.b_isfree, "b_isfree");
+    put(0, ROLE0_HINGE, hinge, "b_hinge");
+    put(0, ROLE0_PARENT, l >= 1 ? K.b_parent : 0, "b_parent");
+    put(0, ROLE0_NCHILD, K.b_nchild, "b_nchild");
+    put(0, ROLE0_CHAIN_LEN, K.b_chain_len, "b_chain_len");
+    put(0, ROLE0_BCHAIN_LEN, K.b_bchain_len, "b_bchain_len");
+    put(0, ROLE0_QADR, K.b_qadr, "b_qadr");
+    put(1, ROLE1_LDOF, K.b_chain_len > 0 ? BYTE_OF(K.b_chain, K.b_chain_len - 1) : 0, "b_chain (last dof)");
+    put(1, ROLE1_HID1, l < m->nv ? K.d_hid + 1 : 0, "d_hid");
+    put(1, ROLE1_DPOS, K.d_pos, "d_pos");
+    put(1, ROLE1_DBODY, K.d_body, "d_body");
+    if (l < m->njnt) {
+      if (K.jt_type != SUMO_JNT_FREE && K.jt_type != SUMO_JNT_HINGE) FAIL(-26, "joint %d has type %d; the engine supports free joints and hinges", l, K.jt_type);
+      const int jh = K.jt_type == SUMO_JNT_HINGE;
+      put(0, ROLE0_JT_HINGE, jh, "jt_type");
+      put(0, ROLE0_JT_LIMITED, K.jt_limited, "jt_limited");
+      put(0, ROLE0_JT_AGENT, K.jt_agent, "jt_agent");
+      put(1, ROLE1_JT_NFREE, nfree, "free joints before the joint");
+      put(1, ROLE1_JT_BODY, K.jt_body, "jt_body");
+      if (K.jt_dadr != l + 5 * nfree || K.jt_qadr != l + 6 * nfree || (jh && K.jt_hid != l - nfree))
+        FAIL(-26, "joint %d: dof address %d / qpos address %d / hinge index %d do not follow from %d free joints before it", l, K.jt_dadr,
+             K.jt_qadr, K.jt_hid, nfree);
+      if (!jh) nfree++;
+    }
+    if (bad) FAIL(-26, "lane %d: %s = %ld does not fit its field of the lane role words", bad_lane, bad, bad_val);
+    if (E->L.tree_ok && l >= 1 && l < m->nbody) {   // what the tree-shaped velocity pass derives instead of reading b_chain / b_chain_own
+      const int len = K.b_chain_len, ld = len > 0 ? BYTE_OF(K.b_chain, len - 1) : 0, B = K.b_agent ? E->L.d1 : 0;
+      int ok = len >= 6 && len <= 8;
+      for (int p = 0; ok && p < len; p++) {
+        const int want = p < 6 ? B + p : (len > 7 ? ld - 7 + p : ld);
+        if (BYTE_OF(K.b_chain, p) != want) ok = 0;
+      }
+      const unsigned own = (K.b_isfree ? 0x3Fu : 0u) | (hinge && len > 6 ? 1u << (len - 1) : 0u);
+      if (!ok || K.b_chain_own != own || (hinge && len <= 6))
+        FAIL(-26, "body %d: its dof chain is not the root's six dofs, then hip and ankle, owned as its joint says", l);
+    }
+    K.role0 = w[0]; K.role1 = w[1];
+  }
+  return 0;
+}
+
 static int model_ints(const sumo_model_t* m, int32_t* out);
 extern "C" int sumo_create(const void* model_blob, size_t nbytes, int num_envs, int device, sumo_handle_t* out) {
   if (!model_blob || !out || num_envs <= 0) FAIL(-1, "bad arguments");
@@ -4138,6 +4251,8 @@ extern "C" int sumo_create(const void* model_blob, size_t nbytes, int num_envs, 
   rc = build_aux(E, ai, af, pic);
   if (rc != 0) { delete E; return rc; }
   build_layout(E);
+  rc = build_lane_roles(E);
+  if (rc != 0) { delete E; return rc; }
   {   // static kernel variants only when the runtime Layout IS the compile-time table (SUMO_STATIC_LAYOUT=0 switches them off)
     static_assert(sizeof(Layout) % sizeof(int) == 0, "Layout is all ints");
     const char* sl = getenv("SUMO_STATIC_LAYOUT");
@@ -4944,6 +5059,21 @@ extern "C" int sumo_debug_layout(const void* model_blob, size_t nbytes, int32_t*
   if (cap < n) FAIL(-2, "need room for %d ints", n);
   memcpy(out, &E.L, sizeof(Layout));
   return n;
+}
+// host only (no device is touched): the two packed role words of the 64 lanes (LaneRec::role0 / role1; the ROLE0_* / ROLE1_* fields),
+// out[2 * lane], out[2 * lane + 1]; returns the count, or the error sumo_create would give for a scene whose roles do not fit.
+extern "C" int sumo_debug_lane_roles(const void* model_blob, size_t nbytes, uint32_t* out, int cap) {
+  if (!model_blob || !out) FAIL(-1, "bad arguments");
+  sumo_engine E;
+  E.blob.assign((const char*)model_blob, (const char*)model_blob + nbytes);
+  if (int rc = sumo_model_parse(&E.hm, E.blob.data(), nbytes)) FAIL(-4, "malformed model blob (%d)", rc);
+  std::vector<int> ai; std::vector<double> af; std::vector<signed char> pic;
+  if (int rc = build_aux(&E, ai, af, pic)) return rc;
+  build_layout(&E);
+  if (int rc = build_lane_roles(&E)) return rc;
+  if (cap < 2 * WAVE) FAIL(-2, "need room for %d words", 2 * WAVE);
+  for (int l = 0; l < WAVE; l++) { out[2 * l] = E.lanes[l].role0; out[2 * l + 1] = E.lanes[l].role1; }
+  return 2 * WAVE;
 }
 // the integer members of the compiled model view (header dims, then the int / float table offsets in SUMO_*_TABLES order) and of Aux
 static int model_ints(const sumo_model_t* m, int32_t* out) {

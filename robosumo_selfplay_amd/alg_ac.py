@@ -6,16 +6,14 @@ Per update: opponent selection from the checkpoint directory, one rollout of ``n
 stay in HBM.  Not reproduced: TF summaries, matplotlib histograms; the reference's ``eval_env`` runner is replaced by the
 evaluation of train_eval.py (``eval_interval`` / ``eval_opponents``).
 
-Decisions on the reference's A2C path:
-  1. alg_ac.py:153 builds its Runner without ``rho_bar`` / ``c_bar``, which runner.py:36 requires (TypeError before the first step).
-     Here they are ``learn`` keywords with PPO's RoboSumo defaults, 10.0 / 1.0.  They enter only agent 1's V-trace returns -- agent
-     0's clips are 1 (runner.py:175-177), so the learner's own returns are plain GAE(lambda) -- i.e. they matter only with
-     opponent-data reuse.
-  2. ``use_opponent_data='off_policy'`` / ``'both'`` use ratios the reference computes in commented-out code (alg_ac.py:285-290,
-     NameError).  Supported: None and ``'direct'`` (weights 1); the other two raise NotImplementedError.
-  3. ``opponent_mode='ours'`` has no selection block in alg_ac.py:200-213: the opponent stays checkpoint 00000 for the whole run (and
-     the reference's log line reads an unset ``idx``).  That v0-forever behaviour is what the reference trains against and is kept;
-     the log line reports version 0.
+Decisions on the reference's A2C path (DESIGN.md section 8 gives the reasons):
+  1. ``rho_bar`` / ``c_bar``, which alg_ac.py:153 forgets to hand to its Runner (TypeError), are ``learn`` keywords with PPO's RoboSumo
+     defaults, 10.0 / 1.0.  They enter only agent 1's V-trace returns, i.e. they matter only with opponent-data reuse.
+  2. ``use_opponent_data``: None and ``'direct'`` (weights 1); ``'off_policy'`` / ``'both'`` read ratios of commented-out code
+     (alg_ac.py:285-290, NameError) and raise NotImplementedError.
+  3. ``opponent_mode='ours'`` has no selection block in alg_ac.py:200-213: the opponent stays checkpoint 00000 for the whole run.
+     That is what the reference trains against and is kept; the log line reports version 0.
+The stages that are the same for both learners come from ``alg_ppo`` ("The learners: one loop, named stages").
 Single GPU, MLP policies only (``comm`` / ``network='lstm'`` raise NotImplementedError)."""
 import os
 import os.path as osp
@@ -24,8 +22,8 @@ from collections import deque
 
 import numpy as np
 
-from .alg_ppo import (assemble_update_batch, assign_league, check_opponent_pool, constfn, env_fault_delta, explained_variance,
-                      install_fixed_opponent, league_note, safemean, upload)
+from .alg_ppo import (assemble_update_batch, assign_league, check_opponent_pool, choose_opponents, collect_rollout, constfn,
+                      install_fixed_opponent, install_opponents, report_update, save_checkpoint)
 
 NEGLOGP_THRESHOLD = 50.0      # alg_ac.py:241-243, hard-coded there
 
@@ -79,7 +77,7 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
     models = [model] + [mk("model_%d" % i, False) for i in range(1, nagent)]
     log_dir = log_dir or os.environ.get("OPENAI_LOGDIR") or "/tmp/robosumo_selfplay_amd"
     checkdir = osp.join(log_dir, "checkpoints")
-    model.save(osp.join(checkdir, "00000"))                              # alg_ac.py:117-118
+    save_checkpoint(model, checkdir, "00000")                            # alg_ac.py:117-118
     if load_path is not None:
         for m in models:
             m.load(load_path)
@@ -102,11 +100,14 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
     history = dict(opponent_versions=[], useful_ratio=[], lossvals=[], fps=[], select_s=[], rollout_s=[], update_s=[],
                    env_diverged=[], env_dropped_contacts=[], env_rollout_aborts=[],     # per update, from the engine's counters
                    league_scores=[], league_tiles=[])       # fix mode with a list of files: per update and member (alg_ppo.league_note)
-    env_stats_prev = env.stats() if hasattr(env, "stats") else None
+    env_stats = env.stats() if hasattr(env, "stats") else None
     nupdates = total_timesteps // nbatch
     report = train_eval.Report(run_log=run_log, plan=eval_plan, log_dir=log_dir, env=env, model=model, history=history, eval_env=eval_env,
                                deterministic=eval_deterministic, seed=eval_seed, first_checkpoint=osp.join(checkdir, "00000"),
                                log_interval=log_interval, verbose=verbose, opponent_mode=opponent_mode)
+    tail = dict(nupdates=nupdates, nsteps=nsteps, nbatch=nbatch, env=env, runner=runner, history=history, model=model, report=report,
+                epinfobuf=epinfobuf, update_fn=update_fn, log_interval=log_interval, verbose=verbose, save_interval=save_interval,
+                checkdir=checkdir)
     loaded = None        # the checkpoint(s) the opponent holds: re-read from disk only when the selection changes
     league = None        # fix mode with a list of files: the policy_zoo.ZooLeague on agent 1
     for update in range(1, nupdates + 1):
@@ -124,68 +125,39 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
                 paths, choices = [osp.join(checkdir, "00000")], [0]
             else:
                 paths = sorted(osp.join(checkdir, f) for f in os.listdir(checkdir))
-                K = pool.capacity if pool is not None else 1
-                if opponent_mode == "random":                            # alg_ac.py:203-205
-                    choices = [int(x) for x in np.random.choice(len(paths), K)]
-                else:                                                    # 'latest', alg_ac.py:206-208
-                    choices = list(range(len(paths) - 1, max(-1, len(paths) - 1 - K), -1))
+                # 'random' over the checkpoints there are (alg_ac.py:203-205), 'latest' as in alg_ppo (:206-208)
+                choices = choose_opponents(opponent_mode, len(paths), len(paths), pool.capacity if pool is not None else 1)
             sel = tuple(paths[c] for c in choices)
             if sel != loaded:
-                runner.models[1].load(sel[0])
-                if pool is not None:
-                    for k, p in enumerate(sel):
-                        pool.set_snapshot(k, p)
-                    pool.assign_round_robin(range(len(sel)))
+                install_opponents(runner.models[1], pool, sel)
                 loaded = sel
             history["opponent_versions"].append([int(osp.basename(p)) for p in sel])
         tsel = time.perf_counter()
-        # ---- rollout
-        obs, returns, masks, actions, values, neglogpacs, rewards, _onlp, _oobs, _oact, _states, epinfos, _opr, _oer, _tr = runner.run(update)
-        torch.cuda.synchronize(dev)
-        t_roll = time.perf_counter() - tsel
-        if isinstance(obs, np.ndarray):       # host-mode Runner: continue on the device
-            obs, returns, masks, actions, values, neglogpacs, rewards = upload(dev, obs, returns, masks, actions, values, neglogpacs, rewards)
+        # ---- rollout, timed from the end of the selection
+        ro, t_roll = collect_rollout(runner, update, dev, tsel)
         # ---- batch: the learner's rows, plus the opponent's usable rows under 'direct' (alg_ac.py:241-262)
         if use_opponent_data is None:
-            b_obs, b_ret, b_act, b_val = obs[0], returns[0], actions[0], values[0]
+            b_obs, b_ret, b_act, b_val = ro.obs[0], ro.returns[0], ro.actions[0], ro.values[0]
             weights = torch.ones(nbatch, dtype=torch.float32, device=dev)
             history["useful_ratio"].append(None)
         else:
-            ub = assemble_update_batch(obs, returns, masks, actions, values, neglogpacs, rewards, None, None, nbatch=nbatch,
-                                       neglogp_threshold=NEGLOGP_THRESHOLD, use_opponent_data=use_opponent_data)
+            ub = assemble_update_batch(*ro[:7], None, None, nbatch=nbatch, neglogp_threshold=NEGLOGP_THRESHOLD, use_opponent_data=use_opponent_data)
             b_obs, b_ret, b_act, b_val, weights = ub["obs"], ub["returns"], ub["actions"], ub["values"], ub["weights"]
             history["useful_ratio"].append(ub["useful_ratio"])
-        epinfobuf.extend(epinfos[-epinfobuf.maxlen:])
+        epinfobuf.extend(ro.epinfos[-epinfobuf.maxlen:])
         # ---- one optimiser step on the whole batch (alg_ac.py:273-276)
         out3 = model.train_device(lrnow, b_obs.contiguous(), b_ret.contiguous(), b_act.contiguous(), b_val.contiguous(), weights)
         lossvals = out3.cpu().numpy().astype(np.float64)                # (waits for the step)
         tnow = time.perf_counter()
-        history["lossvals"].append(lossvals)
+        history["lossvals"].append(lossvals); history["fps"].append(nbatch / (tnow - tstart))
         history["select_s"].append(tsel - tstart)                      # opponent selection (checkpoint reads)
-        history["rollout_s"].append(t_roll)
-        history["update_s"].append(tnow - tsel - t_roll)
-        history["fps"].append(nbatch / (tnow - tstart))
-        env_stats_prev, env_note = env_fault_delta(env, env_stats_prev, history)
-        lg_note = league_note(history, runner, league)
-        if update_fn is not None:
-            update_fn(update)
-        log_now = update % log_interval == 0 or update == 1
-        logged = report.update(update, nupdates, update * nbatch, epinfos)       # evaluates where due; is a row of the run log due?
-        if logged or (verbose and log_now):
-            ev = explained_variance(b_val.cpu().numpy(), b_ret.cpu().numpy())
-        if logged:
-            report.log(update=update, nsteps=nsteps, nbatch=nbatch, explained_variance=ev, epinfobuf=epinfobuf,
-                       time_elapsed=tnow - tfirststart, lossvals=lossvals, league=league)
-        if verbose and log_now:
-            opp = history["opponent_versions"][-1]
-            print("update %d/%d  opponent %s  fps %.0f  rollout %.2fms  update %.2fms  ev %.3f  eprewmean %.2f  eplenmean %.1f  %s" % (
-                update, nupdates, opp[0] if opp else "fix", history["fps"][-1], 1e3 * t_roll, 1e3 * history["update_s"][-1], ev,
-                safemean([e["r"] for e in epinfobuf]), safemean([e["l"] for e in epinfobuf]),
-                " ".join("%s %.4g" % (n, v) for n, v in zip(model.loss_names, lossvals))) + lg_note + env_note, flush=True)
-        elif env_note:
-            print("update %d/%d%s" % (update, nupdates, env_note), flush=True)
-        if save_interval and (update % save_interval == 0 or update == 1):
-            model.save(osp.join(checkdir, "%.5i" % update))               # alg_ac.py:333-339
+        history["rollout_s"].append(t_roll); history["update_s"].append(tnow - tsel - t_roll)
+        # ---- report (alg_ppo.report_update): counters, run log, evaluation, the printed line, checkpoint (alg_ac.py:333-339)
+        opp = history["opponent_versions"][-1]
+        middle = "opponent %s  fps %.0f  rollout %.2fms  update %.2fms" % (opp[0] if opp else "fix", history["fps"][-1], 1e3 * t_roll,
+                                                                           1e3 * history["update_s"][-1])
+        env_stats = report_update(update, middle, dict(values=b_val, returns=b_ret), lossvals, ro.epinfos, env_stats, tnow - tfirststart,
+                                  league=league, **tail)
     report.close()
     model.history = history
     model.time_elapsed = time.perf_counter() - tfirststart

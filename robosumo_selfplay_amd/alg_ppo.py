@@ -4,6 +4,7 @@ Same keyword surface and per-update sequence -- opponent selection from the chec
 the opponent pool, alg_ppo.py:217-244), ``runner.run(update)``, IS-ratio hygiene (:258-280), optional opponent-data reuse
 (:325-344), ``noptepochs x nminibatches`` shuffled minibatch steps with KL early stop (:355-398), checkpoint every update
 (:459-464) -- but rollout buffers stay in HBM and each minibatch is a row-index gather inside the gradient kernel.
+``learn`` is a driver over one module-level function per stage ("The learners: one loop, named stages").
 Not reproduced: matplotlib histograms per update (:292-318), TF summaries.
 Multi-GPU: every rank runs this with its own env shard; ``comm`` (torch.distributed group) makes PPOModel all-reduce the
 advantage moments and the fused gradient buffer.
@@ -11,7 +12,8 @@ advantage moments and the fused gradient buffer.
 import os
 import os.path as osp
 import time
-from collections import deque
+from collections import deque, namedtuple
+from functools import partial
 
 import numpy as np
 
@@ -224,6 +226,204 @@ def env_fault_delta(env, prev, history):
     return now, note
 
 
+def choose_opponents(opponent_mode, update, npaths, K, score_fn=None):
+    """(shared; pure) ``K`` of the ``npaths`` checkpoints for agent 1 (alg_ppo.py:217-244; 'latest': fewer where fewer exist).  Draws from numpy's
+    global stream: 'random' over ``range(update)``, 'ours' the 30-subset if there are more, then by the probabilities ``score_fn(subset)`` returns."""
+    if opponent_mode == "random":
+        return [int(x) for x in np.random.choice(update, K)]
+    if opponent_mode == "latest":
+        return list(range(npaths - 1, max(-1, npaths - 1 - K), -1))
+    if opponent_mode == "ours":                                          # ratio-divergence sampling (:227-244)
+        sub = np.sort(np.random.choice(npaths, 30, replace=False)) if npaths > 30 else np.arange(npaths)
+        rd = score_fn(sub)
+        return [int(sub[j]) for j in np.random.choice(len(rd), K, p=rd)]
+    raise ValueError("opponent_mode %r" % (opponent_mode,))
+
+
+def candidate_probs(paths, sub, *, ref, opponent_data, selector, model_util):
+    """The ``score_fn`` of 'ours': sampling probabilities of the candidates ``paths[i], i in sub`` against the opponent ``ref`` on the last
+    rollout's opponent samples -- one launch over the selector's table, or candidate by candidate through the scratch ``model_util``."""
+    obs, actions = opponent_data
+    if selector is not None:
+        selector.ensure(paths, sub)
+        return selection_probs_from_scores(selector.scores(ref.params, sub, obs, actions))
+    ap = ref.act_model.action_probability(obs, given_action=actions)
+    naps = []
+    for i in sub:
+        model_util.load(paths[i])
+        naps.append(model_util.act_model.action_probability(obs, given_action=actions))
+    return selection_probs(ap, naps)
+
+
+def install_opponents(opp_ref, pool, files):
+    """(shared) The chosen checkpoint files into place: the first into the single reference opponent (agent 1 itself without an LSTM pool),
+    file k into pool slot k, and the envs (16-env tiles) dealt over those slots round robin."""
+    opp_ref.load(files[0])
+    if pool is not None:
+        for k, f in enumerate(files):
+            pool.set_snapshot(k, f)
+        pool.assign_round_robin(range(len(files)))
+
+
+def select_opponents(update, opponent_mode, checkdir, opp_ref, pool, history, score_fn, comm, dev):
+    """Self-play selection of one update (alg_ppo.py:207-247): 00000 at update 1, then ``choose_opponents`` over the checkpoint
+    directory; rank 0 decides and everyone loads the same files.  ``version_gap`` grows at update 1 and in 'random' mode only."""
+    if update == 1:
+        paths, choices = [osp.join(checkdir, "00000")], [0]
+        history["version_gap"].append(0)
+    else:
+        paths = sorted(osp.join(checkdir, f) for f in os.listdir(checkdir))
+        K = pool.capacity if pool is not None else 1
+        choices = choose_opponents(opponent_mode, update, len(paths), K, lambda sub: score_fn(paths, sub))
+        if opponent_mode == "random":
+            history["version_gap"].append(update - 1 - choices[0])
+        if comm is not None:                                             # rank 0 decides, everyone loads the same files
+            import torch
+            c = torch.tensor(choices + [-1] * (K - len(choices)), device=dev)
+            torch.distributed.broadcast(c, 0, group=comm)
+            choices = [int(x) for x in c.tolist() if x >= 0]
+    history["opponent_versions"].append(list(choices))
+    install_opponents(opp_ref, pool, [paths[c] for c in choices])
+
+
+Rollout = namedtuple("Rollout", "obs returns masks actions values neglogpacs rewards opponent_neglogpacs opp_obs_s opp_act_s states epinfos "
+                                "off_policy_ratio off_env_ratio total_ratio")         # what Runner.run returns, in its order
+
+
+def collect_rollout(runner, update, dev, tstart):
+    """One rollout, left on the device (a host-mode Runner's arrays are moved there).  Returns (Rollout, seconds since ``tstart``)."""
+    import torch
+    ro = Rollout(*runner.run(update))
+    torch.cuda.synchronize(dev)
+    t_roll = time.perf_counter() - tstart
+    if isinstance(ro.obs, np.ndarray):       # host-mode Runner (recurrent models): continue on the device like the MLP path
+        names = [n for n in Rollout._fields if n not in ("opp_obs_s", "opp_act_s", "states", "epinfos")]
+        ro = ro._replace(**dict(zip(names, upload(dev, *[getattr(ro, n) for n in names]))))
+    return ro, t_roll
+
+
+def clean_and_assemble(ro, history, *, rho_bar, recurrent, shadow_state0, nenvs, nbatch, neglogp_threshold, use_opponent_data, vgap):
+    """Ratio hygiene (alg_ppo.py:258-280), then the usable opponent samples, the batch and its weights (:286-344); ``obs`` comes back
+    contiguous.  A recurrent learner's batch also carries ``states``, ``nseq`` and ``valid`` (None without opponent-data reuse)."""
+    import torch
+    clean = {}
+    for name in ("off_policy_ratio", "off_env_ratio", "total_ratio"):
+        clean[name], m, f = clean_ratio(getattr(ro, name), rho_bar)
+        history[name + "_mean"].append(m); history[name + "_clip_frac"].append(f)
+    kw = dict(neglogp_threshold=neglogp_threshold, use_opponent_data=use_opponent_data, vgap=vgap,
+              version_gap=history["version_gap"][-1] if history["version_gap"] else None)      # its last entry, whatever the mode
+    if recurrent and use_opponent_data is not None:
+        ub = assemble_recurrent_update_batch(*ro[:7], clean["off_policy_ratio"], clean["total_ratio"], ro.states, shadow_state0, nenv=nenvs, **kw)
+    else:
+        ub = assemble_update_batch(*ro[:7], clean["off_policy_ratio"], clean["total_ratio"], nbatch=nbatch, **kw)
+        if recurrent:
+            st0 = ro.states if torch.is_tensor(ro.states) else torch.as_tensor(np.asarray(ro.states, np.float32)).to(ro.returns.device)
+            ub.update(states=st0, nseq=nenvs, valid=None)
+    history["useful_ratio"].append(ub["useful_ratio"])
+    ub["obs"] = ub["obs"].contiguous()
+    return ub
+
+
+def optimise_recurrent(model, ub, lrnow, cliprangenow, *, nsteps, nminibatches, noptepochs, dev):
+    """Minibatch SGD of a recurrent learner, baselines ppo2 convention: minibatches of whole env sequences, each with its own start state
+    and masks; under opponent-data reuse agent 1's sequences follow agent 0's and the row mask ``valid`` goes along (a minibatch without
+    a valid row steps on a zero gradient, LstmPPOModel.train).  Returns (mean loss row, None): no KL early stop here."""
+    import torch
+    nseq, valid = ub["nseq"], ub["valid"]
+    rows = [ub[k] for k in ("obs", "returns", "masks", "actions", "values", "neglogpacs")]
+    envsperbatch = nseq // nminibatches
+    envinds = np.arange(nseq)
+    flatinds = np.arange(nseq * nsteps).reshape(nseq, nsteps)
+    mblossvals = []
+    for epoch in range(noptepochs):
+        np.random.shuffle(envinds)
+        for start in range(0, nseq, envsperbatch):
+            mbenv = envinds[start:start + envsperbatch]
+            mbflat = torch.from_numpy(flatinds[mbenv].ravel()).to(dev)
+            kw = dict(valid=valid[mbflat]) if valid is not None else {}
+            out = model.train(lrnow, cliprangenow, *[x[mbflat] for x in rows], None, ub["weights"][mbflat],
+                              ub["states"][torch.from_numpy(mbenv).to(dev)], nsteps=nsteps, **kw)
+            mblossvals.append(torch.tensor([float(x) for x in out[:5]], dtype=torch.float64))
+    return torch.stack(mblossvals).mean(dim=0).cpu().numpy().astype(np.float64), None
+
+
+def optimise_indexed(model, ub, lrnow, cliprangenow, *, nbatch_train, noptepochs, kl_threshold, shuffle_gen, comm, dev):
+    """Minibatch SGD of an MLP learner (alg_ppo.py:355-398): the batch is handed over once and every step gathers its rows by index
+    inside the gradient kernel.  Returns (mean loss row, [epoch, minibatch] of the KL early stop or None)."""
+    import torch
+    batch = [ub[k] for k in ("obs", "returns", "actions", "values", "neglogpacs", "weights")]
+    if hasattr(model, "begin_update"):
+        model.begin_update(*batch)                                       # the update's batch, handed over once (model.py)
+    # minibatch steps per epoch (alg_ppo.py:378): with opponent-data reuse the ranks hold different numbers of rows, so they
+    # agree on the largest count and short ranks finish the epoch with empty minibatches (same collectives on every rank)
+    nsamp = batch[0].shape[0]
+    nmb_steps = -(-nsamp // nbatch_train)
+    if comm is not None and not model.equal_counts:
+        nmb_steps = sdist.agree_max(nmb_steps, comm, device=dev)
+    mblossvals, stop_info = [], None
+    for epoch in range(noptepochs):
+        inds = torch.randperm(nsamp, device=dev, generator=shuffle_gen).to(torch.int32)   # np.random.shuffle (:375), on the device
+        if comm is not None and hasattr(model, "prepare_epoch"):
+            # equal shards: the advantage moments of all the epoch's minibatches in ONE all-reduce, so that every optimiser step
+            # issues exactly one collective (SURVEY.md 8(e)(ii)); a no-op with opponent-data reuse (unequal shards)
+            model.prepare_epoch(inds, nbatch_train)
+        for ii in range(nmb_steps):
+            mb = inds[ii * nbatch_train:(ii + 1) * nbatch_train]       # empty once this rank's rows are used up
+            # statistics stay on the device unless the KL early stop needs them now (alg_ppo.py:389-398)
+            out = model.train_indexed(lrnow, cliprangenow, *batch, mb, int(mb.numel()), sync=kl_threshold is not None, mb_index=ii)
+            mblossvals.append(out[:5] if kl_threshold is not None else out)
+            if kl_threshold is not None and out[3] > kl_threshold * 1.5:
+                stop_info = [epoch, ii]
+                break
+        if stop_info is not None:
+            break
+    if hasattr(model, "end_update"):
+        model.end_update()
+    if kl_threshold is None:                                             # device rows: one transfer for the update
+        return torch.stack(mblossvals).mean(dim=0).cpu().numpy().astype(np.float64), stop_info
+    return np.mean(np.array(mblossvals, dtype=np.float64), axis=0), stop_info
+
+
+def save_checkpoint(model, checkdir, name, selector=None):
+    """(shared) ``checkdir/name``, and its row of the fused selector's table where there is one."""
+    path = osp.join(checkdir, name)
+    model.save(path)
+    if selector is not None:
+        selector.note_saved(sorted(os.listdir(checkdir)).index(name), model, path)
+
+
+def report_update(update, middle, ub, lossvals, epinfos, env_stats_prev, time_elapsed, *, nupdates, nsteps, nbatch, env, runner, league,
+                  history, model, report, epinfobuf, update_fn, log_interval, verbose, save_interval, checkdir, selector=None, rank=0,
+                  comm=None):
+    """(shared) The tail of an update: the engine's fault counters and the league's tally into ``history``, ``update_fn``, the run log and
+    the evaluation (``report``, rank 0's), the printed line around the learner's own ``middle``, the checkpoint and, with ``comm``, the
+    check that all ranks hold the same weights.  ``nbatch`` counts all ranks.  Returns ``env.stats()``: the next ``env_stats_prev``."""
+    env_stats, env_note = env_fault_delta(env, env_stats_prev, history)
+    lg_note = league_note(history, runner, league)
+    if update_fn is not None:
+        update_fn(update)
+    log_now = update % log_interval == 0 or update == 1
+    logged = report is not None and report.update(update, nupdates, update * nbatch, epinfos)       # evaluates where due; is a row of the run log due?
+    if rank == 0 and (logged or (verbose and log_now)):
+        ev = explained_variance(ub["values"].cpu().numpy(), ub["returns"].cpu().numpy())
+    if logged:
+        report.log(update=update, nsteps=nsteps, nbatch=nbatch, explained_variance=ev, epinfobuf=epinfobuf, time_elapsed=time_elapsed,
+                   lossvals=lossvals, league=league)
+    if verbose and rank == 0 and log_now:
+        print("update %d/%d  %s  ev %.3f  eprewmean %.2f  eplenmean %.1f  %s" % (
+            update, nupdates, middle, ev, safemean([e["r"] for e in epinfobuf]), safemean([e["l"] for e in epinfobuf]),
+            " ".join("%s %.4g" % (n, v) for n, v in zip(model.loss_names, lossvals))) + lg_note + env_note, flush=True)
+    elif env_note and rank == 0:
+        print("update %d/%d%s" % (update, nupdates, env_note), flush=True)
+    if save_interval and (update % save_interval == 0 or update == 1) and rank == 0:
+        save_checkpoint(model, checkdir, "%.5i" % update, selector)       # alg_ppo.py:459-464
+    if comm is not None:
+        import torch
+        sdist.assert_synced(model.params, comm)                           # MpiAdamOptimizer.check_synced (mpi_adam_optimizer.py:54-67)
+        torch.distributed.barrier(comm)
+    return env_stats
+
+
 def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_data=None, eval_env=None, seed=None, nsteps=2048,
           ent_coef=0.0, lr=3e-4, vf_coef=0.5, max_grad_norm=0.5, gamma=0.99, lam=0.95, rho_bar=1.0, c_bar=1.0, log_interval=10,
           nminibatches=4, noptepochs=4, cliprange=0.2, save_interval=1, load_path=None, model_fn=None, update_fn=None, init_fn=None,
@@ -246,8 +446,7 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
     lr = constfn(lr) if isinstance(lr, float) else lr
     cliprange = constfn(cliprange) if isinstance(cliprange, float) else cliprange
     total_timesteps = int(total_timesteps)
-    rank = 0 if comm is None else torch.distributed.get_rank(comm)
-    world = 1 if comm is None else torch.distributed.get_world_size(comm)
+    rank, world = (0, 1) if comm is None else (torch.distributed.get_rank(comm), torch.distributed.get_world_size(comm))
     policy = build_policy(env, network, **network_kwargs)
     nenvs = env.num_envs
     ob_space, ac_space = env.observation_space[0], env.action_space[0]
@@ -274,7 +473,7 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
     log_dir = log_dir or os.environ.get("OPENAI_LOGDIR") or "/tmp/robosumo_selfplay_amd"
     checkdir = osp.join(log_dir, "checkpoints")
     nupdates = total_timesteps // nbatch
-    selector = None
+    selector = model_util = None
     if not fused_selector:
         model_util = mk("model_util", False)
     else:
@@ -287,15 +486,8 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
         names = set(os.listdir(checkdir)) if osp.isdir(checkdir) else set()      # a run directory may already hold checkpoints
         # history mode takes its whole table (one row per checkpoint of the run, at most selector_table_mb) here, before the first update
         selector = FusedSelector(policy, dev, len(names | set("%.5i" % u for u in range(nupdates + 1))), table_mb=selector_table_mb)
-
-    def save_checkpoint(name):
-        path = osp.join(checkdir, name)
-        model.save(path)
-        if selector is not None:
-            selector.note_saved(sorted(os.listdir(checkdir)).index(name), model, path)
-
     if rank == 0:
-        save_checkpoint("00000")                                         # alg_ppo.py:122-123
+        save_checkpoint(model, checkdir, "00000", selector)              # alg_ppo.py:122-123
     if comm is not None:
         torch.distributed.barrier(comm)
     if load_path is not None:
@@ -307,15 +499,16 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
                     anneal_bound=anneal_bound)
     # opt-in: in opponent_mode='fix' the zoo net (MLP or LSTM) plays inside the fused rollout launch (Runner.fused_fix_opponent: another noise stream)
     runner.fused_fix_opponent = bool(fused_fix_opponent)
-    reuse_rec = recurrent and use_opponent_data is not None
-    if reuse_rec:       # the learner carries a shadow state along agent 1's stream (Runner.reuse_opponent)
+    if recurrent and use_opponent_data is not None:       # the learner carries a shadow state along agent 1's stream (Runner.reuse_opponent)
         check_recurrent_reuse(opponent_mode, comm, runner.device_mode)
         runner.reuse_opponent = True
     # opponent_pool = K > 1 (extension, BASELINE config 5): K frozen snapshots stay resident in HBM and every env plays against its own
     # one (opponent_pool.py); each update draws K snapshots by the selection law of ``opponent_mode`` instead of one.  K = 1 is the
     # reference: one snapshot for all parallel envs (alg_ppo.py:213-214).
     pool = None
-    opp_ref = models[1] if nagent > 1 else None      # the single-snapshot opponent model (reference of the 'ours' selector under a pool)
+    # the single-snapshot opponent: every selection loads its first choice here and the 'ours' selector scores against it.  It is agent
+    # 1 itself unless an LSTM pool takes that seat below (alg_ppo.py:208: it holds 00000 when update 2 scores the opponent update 1 faced)
+    opp_ref = runner.models[1]
     if int(opponent_pool) > 1:
         check_opponent_pool(opponent_mode, runner, fused=not recurrent)
         from .opponent_pool import LstmOpponentPool, OpponentPool
@@ -328,6 +521,9 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
     epinfobuf = deque(maxlen=100)
     shuffle_gen = torch.Generator(device=dev)
     shuffle_gen.manual_seed((seed or 0) * 7919 + 13)          # same minibatch order on every rank (equal shards)
+    # the optimiser phase, resolved once: whole-sequence minibatches for a recurrent learner, row-indexed ones for an MLP learner
+    optimise = partial(optimise_recurrent, nsteps=nsteps, nminibatches=nminibatches, noptepochs=noptepochs, dev=dev) if recurrent else partial(
+        optimise_indexed, nbatch_train=nbatch_train, noptepochs=noptepochs, kl_threshold=kl_threshold, shuffle_gen=shuffle_gen, comm=comm, dev=dev)
     if init_fn is not None:
         init_fn()
     tfirststart = time.perf_counter()
@@ -336,189 +532,46 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
                    approxkl=[], early_stop_info=[], lossvals=[], fps=[], rollout_s=[], update_s=[],
                    env_diverged=[], env_dropped_contacts=[], env_rollout_aborts=[],     # per update, from the engine's counters
                    league_scores=[], league_tiles=[])       # fix mode with a list of files: per update and member (league_note)
-    env_stats_prev = env.stats() if hasattr(env, "stats") else None
+    env_stats = env.stats() if hasattr(env, "stats") else None
     # rank 0 reports: the evaluator loads its opponents here, once (the other ranks meet it at the loop's barrier)
     report = train_eval.Report(run_log=run_log, plan=eval_plan, log_dir=log_dir, env=env, model=model, history=history, eval_env=eval_env,
                                deterministic=eval_deterministic, seed=eval_seed, first_checkpoint=osp.join(checkdir, "00000"),
                                log_interval=log_interval, verbose=verbose, opponent_mode=opponent_mode) if rank == 0 else None
-    idx_choice = 0
-    opponent_obs = opponent_actions = None
-    league = None
+    tail = dict(nupdates=nupdates, nsteps=nsteps, nbatch=nbatch * world, env=env, runner=runner, history=history, model=model, report=report,
+                epinfobuf=epinfobuf, update_fn=update_fn, log_interval=log_interval, verbose=verbose, save_interval=save_interval,
+                checkdir=checkdir, selector=selector, rank=rank, comm=comm)
+    opponent_data = league = None
     for update in range(1, nupdates + 1):
         assert nbatch % nminibatches == 0
         tstart = time.perf_counter()
         frac = 1.0 - (update - 1.0) / nupdates
         lrnow, cliprangenow = lr(frac), cliprange(frac)
-        # ---- opponent selection (alg_ppo.py:191-247); rank 0 decides, everyone loads the same file
+        # ---- opponent selection (alg_ppo.py:191-247)
         if opponent_mode == "fix":                                       # alg_ppo.py:194-206: a policy-zoo net
             if update == 1:
                 install_fixed_opponent(runner, fix_opponent_path, ac_space.shape[0], dev, (seed or 0) * 1000 + 17 + rank)
             league = assign_league(runner, update)
-        elif update == 1:
-            if not (recurrent and pool is not None):
-                runner.models[1].load(osp.join(checkdir, "00000"))
-            else:        # alg_ppo.py:208 loads 00000 into models[1]: the 'ours' selector of update 2 scores the opponent the rollout faced
-                opp_ref.load(osp.join(checkdir, "00000"))
-            if pool is not None:
-                pool.set_snapshot(0, osp.join(checkdir, "00000"))
-                pool.assign_round_robin([0])
-            history["version_gap"].append(0)
-            history["opponent_versions"].append([0])
         else:
-            paths = sorted(osp.join(checkdir, f) for f in os.listdir(checkdir))
-            K = pool.capacity if pool is not None else 1
-            if opponent_mode == "random":
-                choices = [int(x) for x in np.random.choice(update, K)]
-                history["version_gap"].append(update - 1 - choices[0])
-            elif opponent_mode == "latest":
-                choices = list(range(len(paths) - 1, max(-1, len(paths) - 1 - K), -1))
-            elif opponent_mode == "ours":                                # ratio-divergence sampling (:227-244)
-                ref = opp_ref if (recurrent and pool is not None) else runner.models[1]
-                sub = np.sort(np.random.choice(len(paths), 30, replace=False)) if len(paths) > 30 else np.arange(len(paths))
-                if selector is not None:
-                    selector.ensure(paths, sub)
-                    rd = selection_probs_from_scores(selector.scores(ref.params, sub, opponent_obs, opponent_actions))
-                else:
-                    ap = ref.act_model.action_probability(opponent_obs, given_action=opponent_actions)
-                    naps = []
-                    for i in sub:
-                        model_util.load(paths[i])
-                        naps.append(model_util.act_model.action_probability(opponent_obs, given_action=opponent_actions))
-                    rd = selection_probs(ap, naps)
-                choices = [int(sub[j]) for j in np.random.choice(len(rd), K, p=rd)]
-            else:
-                raise ValueError("opponent_mode %r" % (opponent_mode,))
-            if comm is not None:                                         # rank 0 decides, everyone loads the same files
-                c = torch.tensor(choices + [-1] * (K - len(choices)), device=dev)
-                torch.distributed.broadcast(c, 0, group=comm)
-                choices = [int(x) for x in c.tolist() if x >= 0]
-            idx_choice = choices[0]
-            history["opponent_versions"].append(list(choices))
-            if recurrent and pool is not None:
-                opp_ref.load(paths[idx_choice])                          # reference opponent of the 'ours' selector
-            else:
-                runner.models[1].load(paths[idx_choice])
-            if pool is not None:
-                for k, ci in enumerate(choices):
-                    pool.set_snapshot(k, paths[ci])
-                pool.assign_round_robin(range(len(choices)))
-        # ---- rollout
-        obs, returns, masks, actions, values, neglogpacs, rewards, opponent_neglogpacs, opp_obs_s, opp_act_s, states, epinfos, \
-            off_policy_ratio, off_env_ratio, total_ratio = runner.run(update)
-        torch.cuda.synchronize(dev)
-        t_roll = time.perf_counter() - tstart
-        if isinstance(obs, np.ndarray):       # host-mode Runner (recurrent models): continue on the device like the MLP path
-            obs, returns, masks, actions, values, neglogpacs, rewards, opponent_neglogpacs, off_policy_ratio, off_env_ratio, total_ratio = upload(
-                dev, obs, returns, masks, actions, values, neglogpacs, rewards, opponent_neglogpacs, off_policy_ratio, off_env_ratio, total_ratio)
-        # un-scrambled opponent data for the 'ours' selector: rows = agent 1's (obs, action), env-major
-        opponent_obs, opponent_actions = obs[1], actions[1]
-        # ---- ratio hygiene (alg_ppo.py:258-280)
-        off_policy_ratio, m, f = clean_ratio(off_policy_ratio, rho_bar)
-        history["off_policy_ratio_mean"].append(m); history["off_policy_ratio_clip_frac"].append(f)
-        off_env_ratio, m, f = clean_ratio(off_env_ratio, rho_bar)
-        history["off_env_ratio_mean"].append(m); history["off_env_ratio_clip_frac"].append(f)
-        total_ratio, m, f = clean_ratio(total_ratio, rho_bar)
-        history["total_ratio_mean"].append(m); history["total_ratio_clip_frac"].append(f)
-        # ---- usable opponent samples, batch assembly, weights (alg_ppo.py:286-344)
-        if reuse_rec:       # whole sequences of both agents, unusable rows masked instead of dropped
-            ub = assemble_recurrent_update_batch(obs, returns, masks, actions, values, neglogpacs, rewards, off_policy_ratio, total_ratio,
-                                                 states, runner.shadow_state0, nenv=nenvs, neglogp_threshold=neglogp_threshold,
-                                                 use_opponent_data=use_opponent_data, vgap=vgap,
-                                                 version_gap=history["version_gap"][-1] if history["version_gap"] else None)
-        else:
-            ub = assemble_update_batch(obs, returns, masks, actions, values, neglogpacs, rewards, off_policy_ratio, total_ratio,
-                                       nbatch=nbatch, neglogp_threshold=neglogp_threshold, use_opponent_data=use_opponent_data, vgap=vgap,
-                                       version_gap=history["version_gap"][-1] if history["version_gap"] else None)
-        b_obs, b_ret, b_act, b_val, b_nlp, weights = ub["obs"], ub["returns"], ub["actions"], ub["values"], ub["neglogpacs"], ub["weights"]
-        history["useful_ratio"].append(ub["useful_ratio"])
-        b_obs = b_obs.contiguous()
-        epinfobuf.extend(epinfos[-epinfobuf.maxlen:])                    # the deque keeps the last 100 anyway (alg_ppo.py:160,347)
+            select_opponents(update, opponent_mode, checkdir, opp_ref, pool, history, partial(
+                candidate_probs, ref=opp_ref, opponent_data=opponent_data, selector=selector, model_util=model_util), comm, dev)
+        # ---- rollout; agent 1's (obs, action) rows, env-major, are the 'ours' selector's data of the next update
+        ro, t_roll = collect_rollout(runner, update, dev, tstart)
+        opponent_data = (ro.obs[1], ro.actions[1])
+        # ---- ratio hygiene, usable opponent samples, batch assembly, weights (alg_ppo.py:258-344)
+        ub = clean_and_assemble(ro, history, rho_bar=rho_bar, recurrent=recurrent, shadow_state0=runner.shadow_state0, nenvs=nenvs,
+                                nbatch=nbatch, neglogp_threshold=neglogp_threshold, use_opponent_data=use_opponent_data, vgap=vgap)
+        epinfobuf.extend(ro.epinfos[-epinfobuf.maxlen:])                 # the deque keeps the last 100 anyway (alg_ppo.py:160,347)
         # ---- minibatch SGD (alg_ppo.py:355-398)
-        nsamp = b_obs.shape[0]
-        mblossvals, early_stop, stop_info = [], False, None
-        if recurrent:                          # baselines ppo2 recurrent convention: minibatches of whole env sequences
-            # (opponent-data reuse: agent 1's nenvs sequences follow agent 0's, each with its own start state and masks, and the row
-            # mask ``valid`` goes along; a minibatch that draws no valid row steps on a zero gradient, LstmPPOModel.train)
-            nseq = ub["nseq"] if reuse_rec else nenvs
-            envsperbatch = nseq // nminibatches
-            envinds = np.arange(nseq)
-            flatinds = np.arange(nseq * nsteps).reshape(nseq, nsteps)
-            if reuse_rec:
-                st0, b_masks, b_valid = ub["states"], ub["masks"], ub["valid"]
-            else:
-                st0 = states if torch.is_tensor(states) else torch.as_tensor(np.asarray(states, np.float32)).to(dev)
-                b_masks = masks[0]
-            for epoch in range(noptepochs):
-                np.random.shuffle(envinds)
-                for start in range(0, nseq, envsperbatch):
-                    mbenv = envinds[start:start + envsperbatch]
-                    mbflat = torch.from_numpy(flatinds[mbenv].ravel()).to(dev)
-                    kw = dict(valid=b_valid[mbflat]) if reuse_rec else {}
-                    out = model.train(lrnow, cliprangenow, b_obs[mbflat], b_ret[mbflat], b_masks[mbflat], b_act[mbflat], b_val[mbflat],
-                                      b_nlp[mbflat], None, weights[mbflat], st0[torch.from_numpy(mbenv).to(dev)], nsteps=nsteps, **kw)
-                    mblossvals.append(torch.tensor([float(x) for x in out[:5]], dtype=torch.float64))
-        if not recurrent and hasattr(model, "begin_update"):
-            model.begin_update(b_obs, b_ret, b_act, b_val, b_nlp, weights)   # the update's batch, handed over once (model.py)
-        # minibatch steps per epoch (alg_ppo.py:378): with opponent-data reuse the ranks hold different numbers of rows, so they
-        # agree on the largest count and short ranks finish the epoch with empty minibatches (same collectives on every rank)
-        nmb_steps = -(-nsamp // nbatch_train)
-        if comm is not None and not model.equal_counts:
-            nmb_steps = sdist.agree_max(nmb_steps, comm, device=dev)
-        for epoch in range(noptepochs if not recurrent else 0):
-            inds = torch.randperm(nsamp, device=dev, generator=shuffle_gen).to(torch.int32)   # np.random.shuffle (:375), on the device
-            if comm is not None and hasattr(model, "prepare_epoch"):
-                # equal shards: the advantage moments of all the epoch's minibatches in ONE all-reduce, so that every optimiser step
-                # issues exactly one collective; a no-op with opponent-data reuse (unequal shards)
-                model.prepare_epoch(inds, nbatch_train)
-            for ii in range(nmb_steps):
-                mb = inds[ii * nbatch_train:(ii + 1) * nbatch_train]       # empty once this rank's rows are used up
-                # statistics stay on the device unless the KL early stop needs them now (alg_ppo.py:389-398)
-                out = model.train_indexed(lrnow, cliprangenow, b_obs, b_ret, b_act, b_val, b_nlp, weights, mb, int(mb.numel()),
-                                          sync=kl_threshold is not None, mb_index=ii)
-                mblossvals.append(out[:5] if kl_threshold is not None else out)
-                if kl_threshold is not None and out[3] > kl_threshold * 1.5:
-                    early_stop, stop_info = True, [epoch, ii]
-                    break
-            if early_stop:
-                break
-        if not recurrent and hasattr(model, "end_update"):
-            model.end_update()
-        history["early_stop_info"].append(stop_info)
-        if kl_threshold is None or recurrent:
-            lossvals = torch.stack(mblossvals).mean(dim=0).cpu().numpy().astype(np.float64)
-        else:
-            lossvals = np.mean(np.array(mblossvals, dtype=np.float64), axis=0)
-        history["lossvals"].append(lossvals)
-        history["ppo_clip_frac"].append(lossvals[-1])
-        history["approxkl"].append(lossvals[-2])
+        lossvals, stop_info = optimise(model, ub, lrnow, cliprangenow)
+        history["early_stop_info"].append(stop_info); history["lossvals"].append(lossvals)
+        history["ppo_clip_frac"].append(lossvals[-1]); history["approxkl"].append(lossvals[-2])
         torch.cuda.synchronize(dev)
         tnow = time.perf_counter()
-        history["rollout_s"].append(t_roll)
-        history["update_s"].append(tnow - tstart - t_roll)
+        history["rollout_s"].append(t_roll); history["update_s"].append(tnow - tstart - t_roll)
         history["fps"].append(nbatch * world / (tnow - tstart))
-        env_stats_prev, env_note = env_fault_delta(env, env_stats_prev, history)
-        lg_note = league_note(history, runner, league)
-        if update_fn is not None:
-            update_fn(update)
-        log_now = update % log_interval == 0 or update == 1
-        logged = report is not None and report.update(update, nupdates, update * nbatch * world, epinfos)       # evaluates where due; is a row of the run log due?
-        if rank == 0 and (logged or (verbose and log_now)):
-            ev = explained_variance(b_val.cpu().numpy(), b_ret.cpu().numpy())
-        if logged:
-            report.log(update=update, nsteps=nsteps, nbatch=nbatch * world, explained_variance=ev, epinfobuf=epinfobuf,
-                       time_elapsed=tnow - tfirststart, lossvals=lossvals, league=league)
-        if verbose and rank == 0 and log_now:
-            print("update %d/%d  fps %.0f  rollout %.2fs  sgd %.2fs  ev %.3f  eprewmean %.2f  eplenmean %.1f  %s" % (
-                update, nupdates, history["fps"][-1], t_roll, tnow - tstart - t_roll, ev, safemean([e["r"] for e in epinfobuf]),
-                safemean([e["l"] for e in epinfobuf]), " ".join("%s %.4g" % (n, v) for n, v in zip(model.loss_names, lossvals))) + lg_note + env_note,
-                flush=True)
-        elif env_note and rank == 0:
-            print("update %d/%d%s" % (update, nupdates, env_note), flush=True)
-        if save_interval and (update % save_interval == 0 or update == 1) and rank == 0:
-            save_checkpoint("%.5i" % update)                              # alg_ppo.py:459-464
-        if comm is not None:
-            sdist.assert_synced(model.params, comm)                       # MpiAdamOptimizer.check_synced (mpi_adam_optimizer.py:54-67)
-            torch.distributed.barrier(comm)
+        # ---- report: counters, run log, evaluation, the printed line, checkpoint
+        middle = "fps %.0f  rollout %.2fs  sgd %.2fs" % (history["fps"][-1], t_roll, tnow - tstart - t_roll)
+        env_stats = report_update(update, middle, ub, lossvals, ro.epinfos, env_stats, tnow - tfirststart, league=league, **tail)
     if report is not None:
         report.close()
     model.history = history

@@ -547,6 +547,37 @@ def test_learn_with_opponent_pool_matches_glue_oracle(tmp_path):
     env.close()
 
 
+@pytest.mark.parametrize("network", ["mlp", "lstm"])
+def test_learn_installs_the_chosen_checkpoints(network, tmp_path, monkeypatch):
+    """Where the last update's choices end up: pool slot k holds the checkpoint named in ``opponent_versions[-1][k]`` and the single
+    reference opponent holds the first choice -- ``runner.models[1]`` with MLP policies, with LSTM policies the model that was
+    ``models[1]`` before the pool took its place."""
+    import joblib
+    from robosumo_selfplay_amd import alg_ppo
+    made = []
+
+    class Recording(alg_ppo.Runner):
+        def __init__(self, **kw):
+            super().__init__(**kw)
+            self.first_opponent = self.models[1]
+            made.append(self)
+    monkeypatch.setattr(alg_ppo, "Runner", Recording)
+    kw = dict(nlstm=128) if network == "lstm" else dict(value_network="copy", num_hidden=64, activation="relu")
+    env = SumoVecEnv("RoboSumo-Ant-vs-Ant-v0", num_envs=32, seed=1)
+    model = alg_ppo.learn(network=network, env=env, seed=2, total_timesteps=32 * 8 * 3, nagent=2, log_dir=str(tmp_path), verbose=False, nsteps=8,
+                          nminibatches=4, noptepochs=1, opponent_mode="random", opponent_pool=2, **kw)
+    runner, = made
+    pool = runner.models[1] if network == "lstm" else runner.opponent_pool
+    assert (runner.models[1] is runner.first_opponent) == (network == "mlp")
+    choices = model.history["opponent_versions"][-1]
+    assert len(model.history["opponent_versions"]) == 3 and len(choices) == 2 and all(0 <= c < 3 for c in choices)
+    flat = lambda c: policies.flatten_params(joblib.load(os.path.join(str(tmp_path), "checkpoints", "%.5i" % c)))
+    for k, c in enumerate(choices):
+        assert np.array_equal(pool.params[k].cpu().numpy(), flat(c)), (k, c)
+    assert np.array_equal(runner.first_opponent.params.detach().reshape(-1).cpu().numpy(), flat(choices[0]))
+    env.close()
+
+
 @pytest.mark.parametrize("N,T,chunk", [(1, 3, 0), (2, 1, 0), (5, 7, 3), (40, 12, 5)])
 def test_rollout_kernel_edge_shapes_and_chunks(N, T, chunk):
     """Fused rollout launch on tiny batches (fewer envs than wave slots, one env, one step) and split into several launches per

@@ -1264,13 +1264,21 @@ __device__ __forceinline__ void make_constraint(C& c) {
     const double dlo = value - K.jt_lo, dhi = K.jt_hi - value;
     act_lo = limited && dlo < jm; act_hi = limited && dhi < jm;
     double D0 = 0, A0 = 0, D1 = 0, A1 = 0;
-    if (act_lo) {
-      double B, kt, R = row_params(timestep, def_solref, def_solimp, dlo, jm, K.jt_invw, &B, &kt);
-      D0 = fast_rcp(R); A0 = -B * vel - kt;
+    // one evaluation per lane, of the side that is active (a wave with hinges at their lower and others at their upper limit
+    // -- the usual case -- runs the body once, not once per side)
+    if (act_lo || act_hi) {
+      double B, kt, R = row_params(timestep, def_solref, def_solimp, act_lo ? dlo : dhi, jm, K.jt_invw, &B, &kt);
+      const double Dr = fast_rcp(R), Alo = -B * vel - kt, Ahi = B * vel - kt;     // upper side: row = -e_dof, efc_vel = -qvel
+      D0 = act_lo ? Dr : 0.0; A0 = act_lo ? Alo : 0.0;
+      D1 = act_lo ? 0.0 : Dr; A1 = act_lo ? 0.0 : Ahi;
     }
-    if (act_hi) {
-      double B, kt, R = row_params(timestep, def_solref, def_solimp, dhi, jm, K.jt_invw, &B, &kt);
-      D1 = fast_rcp(R); A1 = B * vel - kt;     // row = -e_dof: efc_vel = -qvel
+    // both sides of one hinge active: only where its range is narrower than twice the margin.  The test is uniform over the
+    // lanes here, so a wave without such a hinge skips the second evaluation.
+    if (__ballot(act_lo && act_hi) != 0ull) {
+      if (act_lo && act_hi) {
+        double B, kt, R = row_params(timestep, def_solref, def_solimp, dhi, jm, K.jt_invw, &B, &kt);
+        D1 = fast_rcp(R); A1 = B * vel - kt;
+      }
     }
     const int hid = role_jt_hid(c), nh = c.L.nhinge;
     S(limD)[hid] = D0; S(limD)[nh + hid] = D1; S(limA)[hid] = A0; S(limA)[nh + hid] = A1;
@@ -1377,14 +1385,45 @@ __device__ __forceinline__ void contact_Jx(C& c, const double* x) {
   }
   SYNC();
 }
-// value of contact row r (= 4 * contact + pyramid edge) of J*x given cp (after contact_Jx)
+// The same products for three vectors in one pass over the slots (the solver set-up: warm start, qacc_smooth, qvel): a
+// slot's Jb words and dof indices are loaded once, the vectors are taken in turn against that one set of jv[16], and each
+// keeps contact_Jx's a0..a3 grouping, so every cp word carries the bits the single pass gives.  cp0..cp2 are offsets in c.sm.
 template <class C>
-__device__ __forceinline__ double row_Jx(const C& c, int r) {
+__device__ __forceinline__ void contact_Jx3(C& c, const double* x0, const double* x1, const double* x2, int cp0, int cp1, int cp2) {
+  for (int idx = c.lane; idx < 3 * c.ncon; idx += WAVE) {
+    int ci = idx / 3, a = idx - 3 * ci;
+    const int info = (c.si + c.L.con_b)[4 * ci + 3], ns = (info >> 20) ? 16 : 8;
+    const double* Jb = S(Jb) + (info & 0xFFFFF) + ns * a;
+    const signed char* di = (const signed char*)c.sb + c.L.b_dofidx + 16 * ci;
+    double jv[16];
+    int dv[16];
+#pragma unroll
+    for (int s = 0; s < 16; s++) { int d = di[s]; dv[s] = d < 0 ? 0 : d; double jq = Jb[s]; jv[s] = s < ns ? jq : 0.0; }
+#pragma unroll
+    for (int v = 0; v < 3; v++) {
+      const double* x = v == 0 ? x0 : (v == 1 ? x1 : x2);
+      double xv[16];
+#pragma unroll
+      for (int s = 0; s < 16; s++) xv[s] = x[dv[s]];
+      double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+#pragma unroll
+      for (int s = 0; s < 16; s += 4) { a0 += jv[s] * xv[s]; a1 += jv[s + 1] * xv[s + 1]; a2 += jv[s + 2] * xv[s + 2]; a3 += jv[s + 3] * xv[s + 3]; }
+      c.sm[(v == 0 ? cp0 : (v == 1 ? cp1 : cp2)) + idx] = (a0 + a1) + (a2 + a3);
+    }
+  }
+  SYNC();
+}
+// value of contact row r (= 4 * contact + pyramid edge) of J*x given its cp words at offset `cpo` of c.sm
+template <class C>
+__device__ __forceinline__ double row_Jx_at(const C& c, int cpo, int r) {
   const int ci = r >> 2, k = r & 3;
   double mu = c.sm[c.L.cpar + ci];
-  const double* cp = c.sm + c.L.cp + 3 * ci;
+  const double* cp = c.sm + cpo + 3 * ci;
   return cp[0] + ((k & 1) ? -mu : mu) * cp[1 + (k >> 1)];
 }
+// ... given cp (after contact_Jx)
+template <class C>
+__device__ __forceinline__ double row_Jx(const C& c, int r) { return row_Jx_at(c, c.L.cp, r); }
 // this lane's two joint-limit slots (lower, upper): D (0 = absent) and aref
 struct LimRows { double D0, D1, A0, A1; };
 template <class C>
@@ -1666,12 +1705,18 @@ __device__ __forceinline__ void newton_solve(C& c) {
   if (!c.use_prev && lane < nv) x[lane] = S(warm)[lane];
   SYNC();
   double Ma = dense_Mx(c, x);
-  contact_Jx(c, x);
-  for (int r = lane; r < nrow; r += WAVE) S(jar)[r] = row_Jx(c, r) - S(aref)[r];
+  // one pass over the contact Jacobians for J x, J qacc_smooth and J qvel (efc_vel).  The two extra cp buffers: cW (5 maxcon words,
+  // first written by the iterations below) and the head of the Hessian region (>= 6 + 10 nbody + 6 nv >= 3 maxcon words in every
+  // layout; dead between the qacc_smooth solve and the first factorisation).
+  contact_Jx3(c, x, S(asmo), S(qvel), c.L.cp, c.L.cW, c.L.H);
+  for (int r = lane; r < nrow; r += WAVE) {
+    const double a = -S(aref)[r] * row_Jx_at(c, c.L.H, r) - S(jar)[r];   // aref = -B efc_vel - K imp (pos - margin): make_constraint parked B in aref, the K term in jar
+    S(aref)[r] = a;
+    S(jar)[r] = row_Jx(c, r) - a;
+  }
   SYNC();
   double xi = lane < nv ? x[lane] : 0.0;
   double cost_ws = solver_cost(c, Ma, xi);
-  contact_Jx(c, S(asmo));
   double jsm[RPL];
   double csm = 0;
   {
@@ -1683,7 +1728,7 @@ __device__ __forceinline__ void newton_solve(C& c) {
 #pragma unroll
   for (int q = 0; q < RPL; q++) {
     int r = lane + WAVE * q;
-    double jv = r < nrow ? row_Jx(c, r) - S(aref)[r] : 1.0;
+    double jv = r < nrow ? row_Jx_at(c, c.L.cW, r) - S(aref)[r] : 1.0;
     jsm[q] = jv;
     if (jv < 0) csm += 0.5 * S(D)[r >> 2] * jv * jv;
   }
@@ -1891,10 +1936,8 @@ __device__ __forceinline__ void forward(C& c) {
 #ifdef SUMO_DBG_DUMP
   if (c.dbg && c.st_forward <= 20 && lane < 3) c.dbg[((c.st_forward - 1) * 8 + 5) * 64 + lane] = lane == 0 ? c.ncon : (lane == 1 ? c.nefc : c.nlim);
 #endif
-  // efc_vel and aref (B and K*imp*(pos-margin) were parked in Jv / jar)
-  contact_Jx(c, S(qvel));
-  for (int r = lane; r < 4 * c.ncon; r += WAVE) S(aref)[r] = -S(aref)[r] * row_Jx(c, r) - S(jar)[r];  // B was parked in aref
-  SYNC();
+  // (efc_vel and aref: newton_solve forms them in its set-up pass; until then B and K*imp*(pos-margin) stay parked in aref / jar,
+  // and nothing in between touches them, qvel, Jb or the dof indices)
   PROF(8);
   mass_matrix(c);  // last user of the kinematic scratch; H may overwrite it from here on
   PROF(9);

@@ -302,6 +302,26 @@ __device__ __forceinline__ double wave_sum(double v) {
   v += dpp_mov_f64<0x143, 0xC>(v);  // row_bcast:31 -> rows 2,3
   return readlane_f64(v, 63);
 }
+// two / four wave sums whose inputs are ready together: wave_sum's adds per value, the stages of the chains interleaved
+template <int N>
+__device__ __forceinline__ void wave_sum_n(double (&v)[N]) {
+#define WAVE_SUM_STAGE(CTRL, MASK) _Pragma("unroll") for (int k = 0; k < N; k++) v[k] += dpp_mov_f64<CTRL, MASK>(v[k]);
+  WAVE_SUM_STAGE(0x111, 0xF) WAVE_SUM_STAGE(0x112, 0xF) WAVE_SUM_STAGE(0x114, 0xF) WAVE_SUM_STAGE(0x118, 0xF)
+  WAVE_SUM_STAGE(0x142, 0xA) WAVE_SUM_STAGE(0x143, 0xC)
+#undef WAVE_SUM_STAGE
+#pragma unroll
+  for (int k = 0; k < N; k++) v[k] = readlane_f64(v[k], 63);
+}
+__device__ __forceinline__ void wave_sum2(double& a, double& b) {
+  double v[2] = {a, b};
+  wave_sum_n(v);
+  a = v[0]; b = v[1];
+}
+__device__ __forceinline__ void wave_sum4(double& a, double& b, double& c, double& d) {
+  double v[4] = {a, b, c, d};
+  wave_sum_n(v);
+  a = v[0]; b = v[1]; c = v[2]; d = v[3];
+}
 __device__ __forceinline__ int wave_excl_scan(int v, int lane, int* total) {
   int inc = v;
   inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xF, 0xF, false);
@@ -1517,8 +1537,8 @@ __device__ __forceinline__ double ldl_solve_rows(C& c, const double* A, double* 
 // Hessian as long as every contact touches a single moving body -- is then nonzero only between a dof and its
 // ancestors: lane i keeps row i as row[p] = A[i][ancestor at chain position p] (root dof m: p <= m; hip: 0..5 root,
 // 6 diag; ankle: 0..5 root, 6 hip, 7 diag).  A x = b is solved by block elimination (MuJoCo's mj_factorM order, leaves
-// first): the 2x2 leg blocks are inverted in their own lanes, the 6x6 Schur complement of each root is accumulated by
-// the six root lanes and factorised redundantly by every lane of the agent.  No fill-in, five short phases.
+// first): the 2x2 leg blocks are inverted in their own lanes, the 6x6 Schur complement of each root is accumulated one
+// needed word per lane and factorised redundantly by every lane of the agent.  No fill-in, five short phases.
 #define DPP_SWAP_PAIR 0xB1  /* quad_perm [1,0,3,2]: exchange with the neighbouring lane (hip <-> ankle; hips sit on even lanes) */
 __device__ __forceinline__ double pair_swap_f64(double v) {
   int lo = __double2loint(v), hi = __double2hiint(v);
@@ -1558,7 +1578,6 @@ __device__ __forceinline__ double tree_factor_solve(C& c, const double (&row)[8]
   const int lane = c.lane, nv = c.P->mdl.nv, d1 = c.L.d1;
   const bool act = lane < nv;
   const int B = lane >= d1 ? d1 : 0, il = lane - B;
-  const int nvg = lane >= d1 ? nv - d1 : d1;        // dofs of this lane's agent
   const bool isleg = act && il >= 6, iship = !(il & 1);
   double* ROW = S(H);           // [nv][8] rows (root rows are overwritten by the Schur complement: [0..5] S, [6] rhs)
   double* WW = S(H) + 8 * nv;   // [nv][6] leg dofs: row of A_ll^-1 A_lr
@@ -1579,7 +1598,8 @@ __device__ __forceinline__ double tree_factor_solve(C& c, const double (&row)[8]
   const double y = (d_par * b - off * pb) * idet;
   if (act) {
 #pragma unroll
-    for (int p = 0; p < 8; p++) ROW[8 * lane + p] = row[p];
+    for (int p = 0; p < 6; p++) ROW[8 * lane + p] = row[p];
+    ROW[8 * lane + 6] = b;   // a root row's right-hand side, the start of its Schur word; nobody reads words 6 / 7 of a leg row
     if (isleg) {
 #pragma unroll
       for (int p = 0; p < 6; p++) WW[6 * lane + p] = w[p];
@@ -1587,37 +1607,38 @@ __device__ __forceinline__ double tree_factor_solve(C& c, const double (&row)[8]
     }
   }
   SYNC();
-  // ---- Schur complement of the root block: S = A_rr - A_rl A_ll^-1 A_lr, rhs' = b_r - A_rl A_ll^-1 b_l (root lane m: row m)
-  if (act && il < 6) {
-    double s[6], br = b;
-#pragma unroll
-    for (int p = 0; p < 6; p++) s[p] = row[p];
-    // leg dofs of this agent: at most MAXLD; unrolled over the bound in batches of four with the 32 loads of a batch issued
-    // before its 28 FMAs (a leg dof past the agent's own re-reads the first one and is masked out of the sums)
+  // ---- Schur complement of the root block: S = A_rr - A_rl A_ll^-1 A_lr, rhs' = b_r - A_rl A_ll^-1 b_l, one lane per word the
+  // factorisation below reads: per agent the 21 words S[i][j], j <= i, and the 6 of the right-hand side (word 6 of row i) -- lanes
+  // 0 .. 26 agent 0, 27 .. 53 agent 1.  Entry t of an agent: t = 7 r + q; r < 3 pairs row r (q <= r) with row 5 - r (7 words
+  // together), r == 3 is the right-hand side of row q.  A word starts from what phase 1 stored there and takes its leg dofs in
+  // ascending order, every product subtracted by one fma: the chain, the operands and the order of the row-per-lane form this
+  // replaces, so the bits are the same.  Each word is read and written by its own lane only; leg rows, WW and Y are only read.
+  {
+    int e = lane;
+    asm volatile("" : "+v"(e));   // opaque: the entry's integers are formed here, per call, not once per launch and kept in registers
+    const int ag = e >= 27, t = e - 27 * ag, r = (t * 37) >> 8, q = t - 7 * r;   // (t * 37) >> 8 == t / 7 for t < 28
+    const bool rhs = r == 3, lo = q <= r;
+    const int i = rhs ? q : (lo ? r : 5 - r), j = rhs ? 6 : (lo ? q : q - r - 1);
+    const int Be = ag ? d1 : 0, nld = (ag ? nv - d1 : d1) - 6, d0 = Be + 6;   // first leg dof of the entry's agent
+    // leg dofs of the agent: at most MAXLD; unrolled over the bound with every load issued before the FMAs (a leg dof past the
+    // agent's own re-reads the first one and is masked out of the sum)
     constexpr int MAXLD = C::NV == 28 ? 8 : (C::NV == 32 ? 12 : 16);
-    const int nld = nvg - 6;
+    if (e < 54) {
+      double* own = ROW + 8 * (Be + i) + j;
+      const double* pa = ROW + 8 * d0 + i;
+      const double* sm = c.sm;
+      const int wo = rhs ? c.L.tmpv + d0 : c.L.H + 8 * nv + 6 * d0 + j, ws = rhs ? 1 : 6;   // Y[d] or WW[6 d + j]
+      double s = *own, am[MAXLD], wv[MAXLD];
 #pragma unroll
-    for (int k0 = 0; k0 < MAXLD; k0 += 4) {
-      double am[4], yv[4], wv[4][6];
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const int d = B + 6 + (k0 + k < nld ? k0 + k : 0);
-        am[k] = ROW[8 * d + il];
-        yv[k] = Y[d];
-#pragma unroll
-        for (int p = 0; p < 6; p++) wv[k][p] = WW[6 * d + p];
+      for (int k = 0; k < MAXLD; k++) {
+        const int kk = k < nld ? k : 0;
+        am[k] = pa[8 * kk];
+        wv[k] = sm[wo + ws * kk];
       }
 #pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const double a_ = k0 + k < nld ? am[k] : 0.0;
-#pragma unroll
-        for (int p = 0; p < 6; p++) s[p] -= a_ * wv[k][p];
-        br -= a_ * yv[k];
-      }
+      for (int k = 0; k < MAXLD; k++) s = __builtin_fma(-(k < nld ? am[k] : 0.0), wv[k], s);
+      *own = s;
     }
-#pragma unroll
-    for (int p = 0; p < 6; p++) ROW[8 * lane + p] = s[p];
-    ROW[8 * lane + 6] = br;
   }
   SYNC();
   // ---- 6x6 LDL^T + solve, redundantly in every lane of the agent
@@ -1671,7 +1692,7 @@ __device__ __forceinline__ double tree_factor_solve(C& c, const double (&row)[8]
 // cost(x) = 1/2 (Ma - qfrc_smooth).(x - qacc_smooth) + sum_active 1/2 D jar^2   (jar of the contact rows in LDS; the
 // limit rows of a dof are evaluated by its lane: jar = +-x - aref)
 template <class C>
-__device__ __forceinline__ double solver_cost(C& c, double Ma_i, double x_i) {
+__device__ __forceinline__ double solver_cost_part(C& c, double Ma_i, double x_i) {   // this lane's share, before the wave sum
   const int lane = c.lane, nv = c.P->mdl.nv;
   double v = 0;
   if (lane < nv) v = 0.5 * (Ma_i - S(qsm)[lane]) * (x_i - S(asmo)[lane]);
@@ -1680,8 +1701,10 @@ __device__ __forceinline__ double solver_cost(C& c, double Ma_i, double x_i) {
   if (j0 < 0) v += 0.5 * q.D0 * j0 * j0;
   if (j1 < 0) v += 0.5 * q.D1 * j1 * j1;
   for (int r = lane; r < 4 * c.ncon; r += WAVE) { double j = S(jar)[r]; if (j < 0) v += 0.5 * S(D)[r >> 2] * j * j; }
-  return wave_sum(v);
+  return v;
 }
+template <class C>
+__device__ __forceinline__ double solver_cost(C& c, double Ma_i, double x_i) { return wave_sum(solver_cost_part(c, Ma_i, x_i)); }
 
 // TREE: every contact touches one moving body (c.htree) -- two instantiations so that the register-hungry general
 // factorisation does not share a loop (and its spills) with the common tree-sparse one
@@ -1716,7 +1739,7 @@ __device__ __forceinline__ void newton_solve(C& c) {
   }
   SYNC();
   double xi = lane < nv ? x[lane] : 0.0;
-  double cost_ws = solver_cost(c, Ma, xi);
+  double cost_ws = solver_cost_part(c, Ma, xi);   // both costs: the lanes' shares first, then the two wave sums together
   double jsm[RPL];
   double csm = 0;
   {
@@ -1732,7 +1755,8 @@ __device__ __forceinline__ void newton_solve(C& c) {
     jsm[q] = jv;
     if (jv < 0) csm += 0.5 * S(D)[r >> 2] * jv * jv;
   }
-  double cost_sm = wave_sum(csm);
+  double cost_sm = csm;
+  wave_sum2(cost_ws, cost_sm);
   double cost = cost_ws;
   if (cost_ws > cost_sm) {
     if (lane < nv) { xi = S(asmo)[lane]; x[lane] = xi; }
@@ -1873,24 +1897,30 @@ __device__ __forceinline__ void newton_solve(C& c) {
     }
     rj[RPL] = xi - lq.A0; rjv[RPL] = sr; rD[RPL] = lq.D0;
     rj[RPL + 1] = -xi - lq.A1; rjv[RPL + 1] = -sr; rD[RPL + 1] = lq.D1;
-    double g1 = wave_sum(lane < nv ? sr * (Ma - qsm_i) : 0.0);
-    double g2 = wave_sum(lane < nv ? sr * Mv : 0.0);
-    double alpha = 0, lo = 0, hi = -1, d0 = 0;
-    for (int ls = 0; ls < 50; ls++) {
-      double f1 = 0, f2 = 0;
+    double g1 = lane < nv ? sr * (Ma - qsm_i) : 0.0, g2 = lane < nv ? sr * Mv : 0.0;
+    double alpha = 0, lo = 0, hi = -1, d0 = 0, f1, f2;
+    auto ls_terms = [&]() {   // this lane's share of the constraint terms of the derivatives at alpha
+      f1 = 0; f2 = 0;
 #pragma unroll
       for (int q = 0; q < RPL + 2; q++) {
         double j = rj[q] + alpha * rjv[q];
         if (j < 0) { f1 += rD[q] * j * rjv[q]; f2 += rD[q] * rjv[q] * rjv[q]; }
       }
-      f1 = wave_sum(f1) + (g1 + alpha * g2);
-      f2 = wave_sum(f2) + g2;
+    };
+    ls_terms();   // the first evaluation (alpha == 0) is ready with g1 and g2: the four wave sums run together
+    wave_sum4(g1, g2, f1, f2);
+    for (int ls = 0;;) {
+      f1 += g1 + alpha * g2;
+      f2 += g2;
       if (ls == 0) d0 = fabs(f1);
       if (fabs(f1) <= 1e-10 * d0) break;
       if (f1 < 0) lo = alpha; else hi = alpha;
       double an = alpha - f1 * fast_rcp(f2);
       if (an <= lo || (hi >= 0 && an >= hi)) an = hi >= 0 ? 0.5 * (lo + hi) : 2 * (alpha > 0 ? alpha : 1.0);
       alpha = an;
+      if (++ls == 50) break;
+      ls_terms();
+      wave_sum2(f1, f2);
     }
     PROF(15);
     if (alpha == 0) break;

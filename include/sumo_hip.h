@@ -406,11 +406,15 @@ int sumo_rollout_status(sumo_handle_t h, int64_t* out4);
  * (SUMO_STATIC_LAYOUT=0 forces those) to float64 rounding -- a different compilation of the same source: literals change which multiply-add
  * pairs are contracted -- and the oracle parity tests run on the static variants; 0 otherwise. */
 int sumo_static_layout(sumo_handle_t h);
-/* development, host only (no device): the Layout / the model's and the derived tables' integer members the engine computes for a scene
- * (tools/gen_static_layout.py) */
+/* The three exports below are host only (no device, no HIP call): each runs the scene preparation of sumo_create itself (parse, derived
+ * tables and lane records, Layout, lane role words, final checks; settings from the SUMO_* environment variables read once) and stops
+ * after the stage it reports, so what they return is what sumo_create computes.  A scene that fails a later stage still reports the
+ * earlier ones; a failing stage returns the code and message sumo_create gives.
+ * development: the Layout as ints in declaration order (returns the count) / the model's and the derived tables' integer members
+ * (returns the model count | the Aux count << 16); tools/gen_static_layout.py writes csrc/layout_static.h from them */
 int sumo_debug_layout(const void* model_blob, size_t nbytes, int32_t* out, int cap);
 int sumo_debug_model_ints(const void* model_blob, size_t nbytes, int32_t* out, int cap, int32_t* aux_out, int aux_cap);
-/* development / tests, host only (no device): the two packed role words of each of the 64 lanes, out[2 * lane] and out[2 * lane + 1]
+/* development / tests: the two packed role words of each of the 64 lanes, out[2 * lane] and out[2 * lane + 1]
  * (cap >= 128) -- the small integers of a lane's body, dof and joint roles that the kernels keep in registers (bit fields: ROLE0_* /
  * ROLE1_* in csrc/sumo_engine.hip; tests/test_lane_roles_cpu.py unpacks them).  Returns 128, or the error sumo_create gives for a scene
  * in which a value does not fit its field. */

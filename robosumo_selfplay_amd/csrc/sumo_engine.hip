@@ -3759,53 +3759,101 @@ __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(SUMO_
 #else
 #define SUMO_FOR_NV(X) X(28) X(32) X(36) X(40) X(44)
 #endif
+#include <memory>
 static thread_local char g_err[512];
 extern "C" const char* sumo_last_error(void) { return g_err; }
 #define FAIL(code, ...) do { snprintf(g_err, sizeof g_err, __VA_ARGS__); return code; } while (0)
 #define HIPCHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) FAIL(-100, "%s failed: %s", #expr, hipGetErrorString(_e)); } while (0)
 
-struct sumo_engine {
-  int device, N;
+// Everything the host derives from a model blob, with one owner.  prepare_scene fills it stage by stage; it makes no HIP call (the
+// host-only exports run where there is no device), and it is not copyable: hm points into blob.
+struct Scene {
+  Scene() = default;
+  Scene(const Scene&) = delete;
+  Scene& operator=(const Scene&) = delete;
   std::vector<char> blob;
-  sumo_model_t hm;  // host view
-  sumo_model_t dm;  // device view
-  Aux aux;
-  Layout L;
-  Params* d_params = nullptr;
-  LaneRec* d_lanes = nullptr;
-  int* d_pair_rec = nullptr;
-  float* d_pair_bound = nullptr;
+  sumo_model_t hm{};                       // host view of blob
+  Aux aux{};                               // its table pointers stay null here: sumo_create points the device copy at the uploads
+  Layout L{};
+  std::vector<int> ai;                     // the tables behind aux.ai / aux.af / aux.pic
+  std::vector<double> af;
+  std::vector<signed char> pic;
   std::vector<LaneRec> lanes;
   std::vector<int> pair_rec;
   std::vector<float> pair_bound;
-  void* d_blob = nullptr;
-  int* d_ai = nullptr;
-  double* d_af = nullptr;
-  signed char* d_pic = nullptr;
-  double* d_state = nullptr;
+  int static_layout = 0;                   // 1 / 2: the scene's Layout equals a compile-time table (Ant-vs-Ant / Spider-vs-Spider): static kernel variants
+  int state_stride = 0, obs_stride = 0, act_stride = 0;
+};
+
+// What the environment says about a scene preparation, read once per preparation.
+struct SceneOptions {
+  bool true_tree;      // SUMO_TRUE_TREE != 0: the model's own body tree instead of the effective one
+  int maxcon;          // SUMO_MAXCON > 0: contact records (still capped by what the line search holds in registers)
+  int warm_mode;       // SUMO_WARM_MODE (Layout::warm_mode)
+  int force_dense;     // SUMO_FORCE_DENSE_H (Layout::force_dense)
+  bool no_tree;        // SUMO_NO_TREE != 0: never the tree solver
+  bool jbcap_set;      // SUMO_JBCAP present, whatever its value: the Jacobian pool does not grow into the spare LDS
+  int jbcap;           // SUMO_JBCAP > 0: the pool's capacity
+  bool static_layout;  // unless SUMO_STATIC_LAYOUT is 0: the static kernel variants where the scene matches a compile-time table
+  static SceneOptions from_env() {
+    auto num = [](const char* name) { const char* v = getenv(name); return v ? atoi(v) : 0; };
+    const char* sl = getenv("SUMO_STATIC_LAYOUT");
+    return {num("SUMO_TRUE_TREE") != 0, num("SUMO_MAXCON"), num("SUMO_WARM_MODE"), num("SUMO_FORCE_DENSE_H"), num("SUMO_NO_TREE") != 0,
+            getenv("SUMO_JBCAP") != nullptr, num("SUMO_JBCAP"), !(sl && atoi(sl) == 0)};
+  }
+};
+
+// Device memory that is freed with its holder.  Reads like the raw pointer it replaces; templates that deduce a pointer type take get().
+template <class T>
+struct DevBuf {
+  struct Free { void operator()(T* p) const { (void)hipFree(p); } };
+  std::unique_ptr<T, Free> p;
+  T* get() const { return p.get(); }
+  operator T*() const { return p.get(); }
+  hipError_t alloc(size_t n) {
+    void* q = nullptr;
+    const hipError_t e = hipMalloc(&q, n * sizeof(T));
+    if (e == hipSuccess) p.reset((T*)q);
+    return e;
+  }
+  hipError_t upload(const std::vector<T>& h) {
+    const hipError_t e = alloc(h.size());
+    return e != hipSuccess ? e : hipMemcpy(p.get(), h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
+  }
+};
+
+struct sumo_engine : Scene {   // a prepared scene and the device state of its N envs
+  int device = 0, N = 0;
+  DevBuf<Params> d_params;
+  DevBuf<LaneRec> d_lanes;
+  DevBuf<int> d_pair_rec;
+  DevBuf<float> d_pair_bound;
+  DevBuf<char> d_blob;
+  DevBuf<int> d_ai;
+  DevBuf<double> d_af;
+  DevBuf<signed char> d_pic;
+  DevBuf<double> d_state;
   int cfrc_mode = 0;                       // 0 zero (reference behaviour), 1 rne_post (sumo_set_cfrc_mode)
   double adjust_z = 0.0;                   // Agent._adjust_z (sumo_set_adjust_z)
-  double *d_state_prev = nullptr, *d_fbuf = nullptr, *d_cfrc = nullptr;   // rne_post: pre-step state, row-force scratch, cfrc_ext [N][nbody][6]
-  int* d_counters = nullptr;
-  uint64_t* d_seeds = nullptr;
-  unsigned long long* d_stats = nullptr;
+  DevBuf<double> d_state_prev, d_fbuf, d_cfrc;   // rne_post: pre-step state, row-force scratch, cfrc_ext [N][nbody][6] (sumo_set_cfrc_mode allocates them)
+  DevBuf<int> d_counters;
+  DevBuf<uint64_t> d_seeds;
+  DevBuf<unsigned long long> d_stats;
   // longest-first scheduling of the env steps (see sumo_step)
-  int *d_cost = nullptr, *d_cost_sorted = nullptr, *d_iota = nullptr, *d_perm = nullptr;   // d_cost / d_perm: two buffers of N each
-  unsigned long long* d_trace = nullptr;   // sumo_debug_trace
+  DevBuf<int> d_cost, d_cost_sorted, d_iota, d_perm;   // d_cost / d_perm: two buffers of N each
+  unsigned long long* d_trace = nullptr;   // sumo_debug_trace: the caller's buffer, not owned
   int num_cus = 0;                         // cached device property (sumo_rollout_steps sizes its persistent grid with it)
-  int* d_rsched = nullptr;                 // sumo_rollout_steps: ticket counter, abort flag, per-env progress [2 + N]
+  DevBuf<int> d_rsched;                    // sumo_rollout_steps: ticket counter, abort flag, per-env progress [2 + N] (allocated by the first fused launch)
   unsigned rollout_seq = 0;                // fused launches so far (hand-over tags: seq_base = (rollout_seq & 0x7FFF) << 16)
   hipStream_t rollout_stream = nullptr;    // stream of the most recent fused launch (sumo_rollout_status waits on it)
   long long rollout_tickets = -1;          // N * K of the most recent fused launch, -1: none yet
   int dbg_fault_env = -1;                  // sumo_debug_fault
-  double* dbg_dump = nullptr;              // sumo_debug_dump (SUMO_DBG_DUMP builds)
-  int static_layout = 0;                   // 1 / 2: the scene's Layout equals a compile-time table (Ant-vs-Ant / Spider-vs-Spider): static kernel variants
+  double* dbg_dump = nullptr;              // sumo_debug_dump (SUMO_DBG_DUMP builds): the caller's buffer, not owned
   unsigned long long acked_faults = 0;     // stats[9] + stats[10] already reported by sumo_rollout_status
   long long sched_t = 0;                                                                     // step launches so far (in-kernel ranking)
-  void* d_sort_tmp = nullptr;
+  DevBuf<char> d_sort_tmp;
   size_t sort_tmp_bytes = 0;
   bool sched = true, perm_valid = false;
-  int state_stride, obs_stride, act_stride;
 };
 
 static void quat2mat_h(double* m, const double* q) {
@@ -3815,19 +3863,58 @@ static void quat2mat_h(double* m, const double* q) {
   m[6] = 2 * (x * z - w * y); m[7] = 2 * (y * z + w * x); m[8] = w * w - x * x - y * y + z * z;
 }
 
-static int build_aux(sumo_engine* E, std::vector<int>& ai, std::vector<double>& af, std::vector<signed char>& pic) {
-  const sumo_model_t* m = &E->hm;
+// build_aux: the derived tables (S.ai / af / pic, the Aux offsets into them), the lane records and the pair records of a parsed
+// scene.  Its pieces run in the order they are declared in; the members are what one piece leaves for the later ones.
+namespace {
+struct AuxBuilder {
+  Scene& S;
+  const SceneOptions& opt;
+  const sumo_model_t* const m = &S.hm;
+  const int nb = m->nbody, nv = m->nv;
+  Aux& A = S.aux;
+  std::vector<int>& ai = S.ai;
+  std::vector<double>& af = S.af;
+  std::vector<signed char>& pic = S.pic;
+  const int* const tparent = SUMO_I(m, body_parentid);
+  const int* const gbody = SUMO_I(m, geom_bodyid);
+  const int* const gtype = SUMO_I(m, geom_type);
+  const int* parent = nullptr;   // tparent, or eparent: the tree the kernels walk
+  bool folded = false;           // parent is the effective tree
+  std::vector<int> eparent, depth, lvl_adr, lvl_body, is_stub, child_adr, child;
+  std::vector<double> epos, equat;
+  std::vector<int> chain_len, chain, bchain_len, bchain, body_agent, tri_i, tri_j, cen_of_geom;
+  int push_tbl(const std::vector<int>& v) { int o = (int)ai.size(); ai.insert(ai.end(), v.begin(), v.end()); return o; }
+  void effective_tree();
+  int chains_and_checks();
+  int collision_tables();
+  int lane_records();
+  void hessian_entries();
+  int pair_records();
+};
+}  // namespace
+
+static int build_aux(Scene& S, const SceneOptions& opt) {
+  const sumo_model_t* m = &S.hm;
   int nb = m->nbody, nv = m->nv;
   if (nb > WAVE || nv > WAVE || m->njnt > WAVE || m->nq > WAVE) FAIL(-10, "scene too large for one wavefront per env (nbody %d nv %d)", nb, nv);
   if (m->nagent != 2) FAIL(-11, "exactly two agents expected");
   if (nv != 28 && nv != 32 && nv != 36 && nv != 40 && nv != 44) FAIL(-18, "no kernel variant for nv=%d", nv);
-  const int* tparent = SUMO_I(m, body_parentid);
+  AuxBuilder B{S, opt};
+  B.effective_tree();
+  if (int rc = B.chains_and_checks()) return rc;
+  if (int rc = B.collision_tables()) return rc;
+  if (int rc = B.lane_records()) return rc;
+  B.hessian_entries();
+  return B.pair_records();
+}
+
+void AuxBuilder::effective_tree() {
   // "Effective" tree of the kernel's level-by-level passes: a body whose parent carries no joint is re-attached to the nearest
   // ancestor that does, with the static transforms composed (the jointless body keeps its own frame as a leaf: its frame
   // still feeds its geom and inertia, and subtree sums do not care which rigidly connected ancestor collects it).  For the
   // RoboSumo agents (torso -> jointless leg stub -> hip body -> ankle body) this removes one level from every pass.
-  std::vector<int> eparent(nb, 0);
-  std::vector<double> epos(3 * (size_t)nb, 0.0), equat(4 * (size_t)nb, 0.0);
+  eparent.assign(nb, 0);
+  epos.assign(3 * (size_t)nb, 0.0); equat.assign(4 * (size_t)nb, 0.0);
   for (int b = 0; b < nb; b++) {
     double pos[3] = {SUMO_F(m, body_pos)[3 * b], SUMO_F(m, body_pos)[3 * b + 1], SUMO_F(m, body_pos)[3 * b + 2]};
     double q[4] = {SUMO_F(m, body_quat)[4 * b], SUMO_F(m, body_quat)[4 * b + 1], SUMO_F(m, body_quat)[4 * b + 2], SUMO_F(m, body_quat)[4 * b + 3]};
@@ -3850,20 +3937,18 @@ static int build_aux(sumo_engine* E, std::vector<int>& ai, std::vector<double>& 
     for (int k = 0; k < 3; k++) epos[3 * b + k] = pos[k];
     for (int k = 0; k < 4; k++) equat[4 * b + k] = q[k];
   }
-  const int* parent = getenv("SUMO_TRUE_TREE") && atoi(getenv("SUMO_TRUE_TREE")) ? tparent : eparent.data();
-  const bool folded = parent != tparent;
-  std::vector<int> depth(nb, 0);
+  parent = opt.true_tree ? tparent : eparent.data();
+  folded = parent != tparent;
+  depth.assign(nb, 0);
   int ndepth = 1;
   for (int b = 1; b < nb; b++) { depth[b] = depth[parent[b]] + 1; if (depth[b] + 1 > ndepth) ndepth = depth[b] + 1; }
-  Aux& A = E->aux;
   A.ndepth = ndepth;
-  auto push_tbl = [&](const std::vector<int>& v) { int o = (int)ai.size(); ai.insert(ai.end(), v.begin(), v.end()); return o; };
-  std::vector<int> lvl_adr(ndepth + 1, 0), lvl_body;
+  lvl_adr.assign(ndepth + 1, 0);
   for (int d = 0; d < ndepth; d++) { lvl_adr[d] = (int)lvl_body.size(); for (int b = 0; b < nb; b++) if (depth[b] == d) lvl_body.push_back(b); }
   lvl_adr[ndepth] = (int)lvl_body.size();
   // jointless leaves of the effective tree ("stubs", e.g. the fixed upper leg segments): rigidly attached to their parent, so
   // their inertia is added to the parent's once per evaluation and they take no part in the subtree gathers
-  std::vector<int> is_stub(nb, 0);
+  is_stub.assign(nb, 0);
   if (folded)
     for (int b = 1; b < nb; b++) {
       if (SUMO_I(m, body_jntnum)[b] != 0 || parent[b] == 0) continue;
@@ -3871,13 +3956,17 @@ static int build_aux(sumo_engine* E, std::vector<int>& ai, std::vector<double>& 
       for (int ch = 1; ch < nb; ch++) if (ch != b && parent[ch] == b) leaf = false;
       is_stub[b] = leaf;
     }
-  std::vector<int> child_adr(nb + 1, 0), child;
+  child_adr.assign(nb + 1, 0);
   for (int b = 0; b < nb; b++) {
     child_adr[b] = (int)child.size();
     for (int ch = nb - 1; ch > b; ch--) if (parent[ch] == b && b != 0 && !is_stub[ch]) child.push_back(ch);
   }
   child_adr[nb] = (int)child.size();
-  std::vector<int> chain_len(nb, 0), chain(nb * MAXCHAIN, -1), bchain_len(nb, 0), bchain(nb * MAXBCHAIN, -1), body_agent(nb, -1);
+}
+
+// dof and body chains root -> body, the checks of what the kernels assume about a body, and the integer tables
+int AuxBuilder::chains_and_checks() {
+  chain_len.assign(nb, 0); chain.assign(nb * MAXCHAIN, -1); bchain_len.assign(nb, 0); bchain.assign(nb * MAXBCHAIN, -1); body_agent.assign(nb, -1);
   pic.assign((size_t)nb * nv, -1);
   const int* dofnum = SUMO_I(m, body_dofnum);
   const int* dofadr = SUMO_I(m, body_dofadr);
@@ -3911,7 +4000,6 @@ static int build_aux(sumo_engine* E, std::vector<int>& ai, std::vector<double>& 
     std::vector<int> seen(nv, 0);
     for (int u = 0; u < m->nu; u++) { int d = SUMO_I(m, actuator_dofid)[u]; if (seen[d]++) FAIL(-17, "two actuators on one dof"); }
   }
-  std::vector<int> tri_i, tri_j;
   for (int i = 0; i < nv; i++) for (int j = 0; j <= i; j++) { tri_i.push_back(i); tri_j.push_back(j); }
   A.ntri = (int)tri_i.size();
   A.o_lvl_adr = push_tbl(lvl_adr); A.o_lvl_body = push_tbl(lvl_body); A.o_child_adr = push_tbl(child_adr);
@@ -3921,15 +4009,17 @@ static int build_aux(sumo_engine* E, std::vector<int>& ai, std::vector<double>& 
   A.o_wgmat = 0;
   af.assign((size_t)9 * m->ngeom, 0.0);
   for (int g = 0; g < m->ngeom; g++) quat2mat_h(&af[9 * g], SUMO_F(m, geom_quat) + 4 * g);
+  return 0;
+}
 
-  // ---- collision centres: body ids for agent geoms, nbody + w for world geom w
-  const int* gbody = SUMO_I(m, geom_bodyid);
-  const int* gtype = SUMO_I(m, geom_type);
+// collision centres (body ids for agent geoms, nbody + w for world geom w) and the static tables the collision code reads by centre
+int AuxBuilder::collision_tables() {
   int nworld = SUMO_I(m, body_geomadr)[1] - SUMO_I(m, body_geomadr)[0];
   int nc = nb + nworld;
   if (nc > 255) FAIL(-20, "too many collision centres");
   A.nc = nc; A.nworld = nworld;
-  std::vector<int> cen_of_geom(m->ngeom, 0), geom_of_cen(nc, -1);
+  cen_of_geom.assign(m->ngeom, 0);
+  std::vector<int> geom_of_cen(nc, -1);
   for (int g = 0; g < m->ngeom; g++) {
     int ci = gbody[g] == 0 ? nb + (g - SUMO_I(m, body_geomadr)[0]) : gbody[g];
     cen_of_geom[g] = ci; geom_of_cen[ci] = g;
@@ -3989,11 +4079,15 @@ static int build_aux(sumo_engine* E, std::vector<int>& ai, std::vector<double>& 
     A.o_stat_i = push_tbl(si);
     A.n_stat_i = (int)si.size();
   }
-  // ---- per-lane constants
-  E->lanes.assign(WAVE, LaneRec());
+  return 0;
+}
+
+// per-lane constants: lane l is body l, dof l, joint l and actuator l at once
+int AuxBuilder::lane_records() {
+  S.lanes.assign(WAVE, LaneRec());
   const int* jbody = SUMO_I(m, jnt_bodyid);
   for (int l = 0; l < WAVE; l++) {
-    LaneRec& K = E->lanes[l];
+    LaneRec& K = S.lanes[l];
     memset(&K, 0, sizeof K);
     K.b_jnt = -1; K.b_level = -1; K.b_agent = 0;
     if (l < nb) {
@@ -4089,63 +4183,66 @@ static int build_aux(sumo_engine* E, std::vector<int>& ai, std::vector<double>& 
       K.a_lo = SUMO_F(m, actuator_ctrlrange)[2 * l]; K.a_hi = SUMO_F(m, actuator_ctrlrange)[2 * l + 1];
     }
   }
-  // ---- lower-triangle entry words of the dense Hessian assembly, entry t = lane + 64 m: (i << 8 | j) | chain position of dof i
-  // << 16 | of dof j << 20; 0xFFFF = none.  Read where the (rare) dense path assembles H instead of living in 7 registers of
-  // every lane for the whole launch.
-  {
-    const int epl = (A.ntri + WAVE - 1) / WAVE;
-    std::vector<int> ent((size_t)epl * WAVE, 0xFFFF);
-    for (int t = 0; t < A.ntri; t++) {
-      const int i = tri_i[t], j = tri_j[t];
-      ent[t] = (int)((unsigned)((i << 8) | j) | ((unsigned)E->lanes[i].d_pos << 16) | ((unsigned)E->lanes[j].d_pos << 20));
-    }
-    A.o_ent = push_tbl(ent);
+  return 0;
+}
+
+// lower-triangle entry words of the dense Hessian assembly, entry t = lane + 64 m: (i << 8 | j) | chain position of dof i
+// << 16 | of dof j << 20; 0xFFFF = none.  Read where the (rare) dense path assembles H instead of living in 7 registers of
+// every lane for the whole launch.
+void AuxBuilder::hessian_entries() {
+  const int epl = (A.ntri + WAVE - 1) / WAVE;
+  std::vector<int> ent((size_t)epl * WAVE, 0xFFFF);
+  for (int t = 0; t < A.ntri; t++) {
+    const int i = tri_i[t], j = tri_j[t];
+    ent[t] = (int)((unsigned)((i << 8) | j) | ((unsigned)S.lanes[i].d_pos << 16) | ((unsigned)S.lanes[j].d_pos << 20));
   }
-  // ---- packed pair records for the broad phase: pairs with a static world geom first (the model lists them first:
-  // body-pair order, world body = 0), padded to whole rounds of 64, then the pairs between moving geoms.
-  //   world pair:  moving centre | world centre << 8 | (world geom is geom1) << 16 | valid << 17
-  //                bound = margin + rbound(moving geom) [+ radius of a static capsule; + rbound of other static shapes]
-  //   moving pair: c1 | c2 << 8 | valid << 17;  bound = margin + rbound1 + rbound2
-  // bounds are rounded up in float: the broad phase may only over-include
-  {
-    int nwp = 0;
-    while (nwp < m->npair && (gbody[SUMO_I(m, pair_geom1)[nwp]] == 0 || gbody[SUMO_I(m, pair_geom2)[nwp]] == 0)) nwp++;
-    for (int p = nwp; p < m->npair; p++)
-      if (gbody[SUMO_I(m, pair_geom1)[p]] == 0 || gbody[SUMO_I(m, pair_geom2)[p]] == 0)
-        FAIL(-23, "collision pair %d: pairs with a world geom must precede the others", p);
-    const int WR = (nwp + WAVE - 1) / WAVE, AR = (m->npair - nwp + WAVE - 1) / WAVE;
-    A.nwp = nwp; A.wrounds = WR; A.arounds = AR;
-    E->pair_rec.assign((size_t)(WR + AR) * WAVE, 0);
-    E->pair_bound.assign((size_t)(WR + AR) * WAVE, 0.0f);
-    auto up = [](double bound) {
-      float bf = (float)bound;
-      while ((double)bf < bound) bf = nextafterf(bf, INFINITY);
-      return nextafterf(bf, INFINITY);
-    };
-    for (int p = 0; p < m->npair; p++) {
-      int g1 = SUMO_I(m, pair_geom1)[p], g2 = SUMO_I(m, pair_geom2)[p];
-      const double margin = SUMO_F(m, pair_margin)[p];
-      if (p < nwp) {
-        if (gbody[g1] == 0 && gbody[g2] == 0) continue;   // static-static: never collides (slot stays invalid)
-        const int w1 = gbody[g1] == 0, gw = w1 ? g1 : g2, ga = w1 ? g2 : g1, tw = gtype[gw];
-        double bound = margin + SUMO_F(m, geom_rbound)[ga];
-        if (tw == SUMO_GEOM_CAPSULE || tw == SUMO_GEOM_CYLINDER) bound += SUMO_F(m, geom_size)[3 * gw];
-        else if (tw != SUMO_GEOM_BOX && tw != SUMO_GEOM_PLANE) bound += SUMO_F(m, geom_rbound)[gw];
-        E->pair_rec[p] = cen_of_geom[ga] | (cen_of_geom[gw] << 8) | (w1 << 16) | (1 << 17);
-        E->pair_bound[p] = up(bound);
-      } else {
-        const int sl = WR * WAVE + (p - nwp);
-        E->pair_rec[sl] = cen_of_geom[g1] | (cen_of_geom[g2] << 8) | (1 << 17);
-        E->pair_bound[sl] = up(margin + SUMO_F(m, geom_rbound)[g1] + SUMO_F(m, geom_rbound)[g2]);
-      }
+  A.o_ent = push_tbl(ent);
+}
+
+// packed pair records for the broad phase: pairs with a static world geom first (the model lists them first:
+// body-pair order, world body = 0), padded to whole rounds of 64, then the pairs between moving geoms.
+//   world pair:  moving centre | world centre << 8 | (world geom is geom1) << 16 | valid << 17
+//                bound = margin + rbound(moving geom) [+ radius of a static capsule; + rbound of other static shapes]
+//   moving pair: c1 | c2 << 8 | valid << 17;  bound = margin + rbound1 + rbound2
+// bounds are rounded up in float: the broad phase may only over-include
+int AuxBuilder::pair_records() {
+  int nwp = 0;
+  while (nwp < m->npair && (gbody[SUMO_I(m, pair_geom1)[nwp]] == 0 || gbody[SUMO_I(m, pair_geom2)[nwp]] == 0)) nwp++;
+  for (int p = nwp; p < m->npair; p++)
+    if (gbody[SUMO_I(m, pair_geom1)[p]] == 0 || gbody[SUMO_I(m, pair_geom2)[p]] == 0)
+      FAIL(-23, "collision pair %d: pairs with a world geom must precede the others", p);
+  const int WR = (nwp + WAVE - 1) / WAVE, AR = (m->npair - nwp + WAVE - 1) / WAVE;
+  A.nwp = nwp; A.wrounds = WR; A.arounds = AR;
+  S.pair_rec.assign((size_t)(WR + AR) * WAVE, 0);
+  S.pair_bound.assign((size_t)(WR + AR) * WAVE, 0.0f);
+  auto up = [](double bound) {
+    float bf = (float)bound;
+    while ((double)bf < bound) bf = nextafterf(bf, INFINITY);
+    return nextafterf(bf, INFINITY);
+  };
+  for (int p = 0; p < m->npair; p++) {
+    int g1 = SUMO_I(m, pair_geom1)[p], g2 = SUMO_I(m, pair_geom2)[p];
+    const double margin = SUMO_F(m, pair_margin)[p];
+    if (p < nwp) {
+      if (gbody[g1] == 0 && gbody[g2] == 0) continue;   // static-static: never collides (slot stays invalid)
+      const int w1 = gbody[g1] == 0, gw = w1 ? g1 : g2, ga = w1 ? g2 : g1, tw = gtype[gw];
+      double bound = margin + SUMO_F(m, geom_rbound)[ga];
+      if (tw == SUMO_GEOM_CAPSULE || tw == SUMO_GEOM_CYLINDER) bound += SUMO_F(m, geom_size)[3 * gw];
+      else if (tw != SUMO_GEOM_BOX && tw != SUMO_GEOM_PLANE) bound += SUMO_F(m, geom_rbound)[gw];
+      S.pair_rec[p] = cen_of_geom[ga] | (cen_of_geom[gw] << 8) | (w1 << 16) | (1 << 17);
+      S.pair_bound[p] = up(bound);
+    } else {
+      const int sl = WR * WAVE + (p - nwp);
+      S.pair_rec[sl] = cen_of_geom[g1] | (cen_of_geom[g2] << 8) | (1 << 17);
+      S.pair_bound[sl] = up(margin + SUMO_F(m, geom_rbound)[g1] + SUMO_F(m, geom_rbound)[g2]);
     }
   }
   return 0;
 }
 
-static void build_layout_with(sumo_engine* E, int jb_extra) {
-  const sumo_model_t* m = &E->hm;
-  Layout& L = E->L;
+static void build_layout_with(Scene& S, const SceneOptions& opt, int jb_extra) {
+  const sumo_model_t* m = &S.hm;
+  Layout& L = S.L;
   int nq = m->nq, nv = m->nv, nb = m->nbody, nj = m->njnt, nu = m->nu;
   L.ld = nv | 1;
   int nhinge = 0;
@@ -4153,18 +4250,16 @@ static void build_layout_with(sumo_engine* E, int jb_extra) {
   // Ant-vs-Ant: 18 contact records (the soaks and the zoo play never saw more than 14) instead of 24: the 1 KB goes to the contact-Jacobian pool
   // (build_layout: 29 halves instead of 24 -- 14 contacts between two moving bodies fit), which is what overflowed a few times per 10^8 forwards
   L.maxcon = nv <= 28 ? 18 : (nv <= 36 ? 32 : 40);
-  const char* mc = getenv("SUMO_MAXCON");
-  if (mc && atoi(mc) > 0) L.maxcon = atoi(mc);
+  if (opt.maxcon > 0) L.maxcon = opt.maxcon;
   { int cap = 16 * (nv <= 36 ? 2 : 3); if (L.maxcon > cap) L.maxcon = cap; }  // contact rows per lane held in registers by the line search (newton_solve RPL)
   L.maxefc = 4 * L.maxcon + 2 * nhinge;
-  { const char* wm = getenv("SUMO_WARM_MODE"); L.warm_mode = wm ? atoi(wm) : 0; }
-  { const char* fd = getenv("SUMO_FORCE_DENSE_H"); L.force_dense = fd ? atoi(fd) : 0; }
+  L.warm_mode = opt.warm_mode; L.force_dense = opt.force_dense;
   int o = 0;
   auto take = [&](int n) { int r = o; o += n; return r; };
   L.qpos = take(nq); L.qvel = take(nv); L.warm = take(nv); L.ctrl = take(nu);
   L.x0 = 0; L.accv = 0; L.acca = 0; L.tmpv = take(nv);
   // kinematic data needed until the mass matrix is built (com, cinert -> crb, cdof); the packed Hessian aliases it
-  const int nc = E->aux.nc;
+  const int nc = S.aux.nc;
   const int ntri = nv * (nv + 1) / 2;
   int kin0 = o;
   L.com = take(3 * m->nagent); L.cinert = take(10 * nb); L.cdof = take(6 * nv);
@@ -4173,7 +4268,7 @@ static void build_layout_with(sumo_engine* E, int jb_extra) {
   const int hsize = o - kin0;
   // centre positions / axes: bodies (rewritten every forward) then world geoms (static)
   L.xipos = take(3 * nc); L.gaxis = take(3 * nc);
-  L.stat_d = take(SUMO_STAT_LDS ? E->aux.n_stat_d : 0);
+  L.stat_d = take(SUMO_STAT_LDS ? S.aux.n_stat_d : 0);
   {
     int nv0 = SUMO_I(m, agent_nv)[0], nv1 = SUMO_I(m, agent_nv)[1];
     int mx = nv0 > nv1 ? nv0 : nv1;
@@ -4193,8 +4288,7 @@ static void build_layout_with(sumo_engine* E, int jb_extra) {
     }
     if (14 * nv > hsize) ok = 0;   // exchange buffers of the tree solver live in the Hessian region
     L.tree_ok = ok;
-    const char* nt = getenv("SUMO_NO_TREE");
-    if (nt && atoi(nt)) L.tree_ok = 0;
+    if (opt.no_tree) L.tree_ok = 0;
   }
   L.qsm = take(nv); L.asmo = take(nv); L.Ma = 0; L.grad = 0;
   L.search = take(nv); L.bias = L.search;   // the bias force is consumed (into qsm) before the solver writes its search direction
@@ -4212,7 +4306,7 @@ static void build_layout_with(sumo_engine* E, int jb_extra) {
     L.jbcap = L.maxcon;
     if ((need - 16) / 24 > L.jbcap) L.jbcap = (need - 16) / 24;
     L.jbcap += jb_extra;
-    { const char* jc = getenv("SUMO_JBCAP"); if (jc && atoi(jc) > 0) L.jbcap = atoi(jc); }
+    if (opt.jbcap > 0) L.jbcap = opt.jbcap;
     int jb0 = o, jbsz = 24 * L.jbcap + 16;
     L.Jb = take(jbsz > need ? jbsz : need);
     int q = jb0;
@@ -4231,34 +4325,34 @@ static void build_layout_with(sumo_engine* E, int jb_extra) {
   int io = 0;
   auto itake = [&](int n) { int r = io; io += n; return r; };
   L.con_b = itake(4 * L.maxcon);
-  L.stat_i = itake(SUMO_STAT_LDS ? E->aux.n_stat_i : 0);
+  L.stat_i = itake(SUMO_STAT_LDS ? S.aux.n_stat_i : 0);
   L.b_dofidx = io * 4;
   L.total_bytes = o * 8 + io * 4 + 16 * L.maxcon;
 }
 // The LDS a wave slot leaves unused at the scene's residency (160 KB / waves per CU - the env record) goes to the contact-Jacobian
 // pool: a contact between two moving bodies takes two halves, and wrestling Spiders overflowed a pool of `maxcon` halves about twice
 // per million env steps (counted in `dropped`).  Ant-vs-Ant has 32 B to spare (8 x 20 448 B = 163 584 of 163 840): unchanged.
-static void build_layout(sumo_engine* E) {
-  build_layout_with(E, 0);
-  const int lds_cu = 160 * 1024, slots = lds_cu / E->L.total_bytes;
-  if (slots < 1 || getenv("SUMO_JBCAP")) return;
+static void build_layout(Scene& S, const SceneOptions& opt) {
+  build_layout_with(S, opt, 0);
+  const int lds_cu = 160 * 1024, slots = lds_cu / S.L.total_bytes;
+  if (slots < 1 || opt.jbcap_set) return;
   const int budget = lds_cu / slots / 1280 * 1280;   // LDS is allocated in granules of 1280 B on gfx950
-  int extra = (budget - E->L.total_bytes) / (24 * 8);
-  if (extra > E->L.maxcon) extra = E->L.maxcon;      // (a pool of 2 x maxcon halves can never overflow)
+  int extra = (budget - S.L.total_bytes) / (24 * 8);
+  if (extra > S.L.maxcon) extra = S.L.maxcon;        // (a pool of 2 x maxcon halves can never overflow)
   if (extra <= 0) return;
-  build_layout_with(E, extra);
-  if (lds_cu / E->L.total_bytes != slots) build_layout_with(E, 0);   // (cannot happen: the growth was sized to fit)
+  build_layout_with(S, opt, extra);
+  if (lds_cu / S.L.total_bytes != slots) build_layout_with(S, opt, 0);   // (cannot happen: the growth was sized to fit)
 }
 
 // The two role words of every lane (LaneRec::role0 / role1), packed from the records build_aux filled; after build_layout, whose
 // tree_ok decides whether the kernels derive chain elements from the words.  Nothing is truncated: a value that does not fit its
 // field, or a scene in which a derived quantity differs from the model's, fails creation.
-static int build_lane_roles(sumo_engine* E) {
-  const sumo_model_t* m = &E->hm;
+static int build_lane_roles(Scene& S) {
+  const sumo_model_t* m = &S.hm;
   const char* bad = nullptr; int bad_lane = 0; long bad_val = 0;
   int nfree = 0;   // free joints before joint l
   for (int l = 0; l < WAVE; l++) {
-    LaneRec& K = E->lanes[l];
+    LaneRec& K = S.lanes[l];
     unsigned w[2] = {0u, 0u};
     auto put = [&](int wi, int lo, int n, long v, const char* what) {
       if ((v < 0 || v >= (1L << n)) && !bad) { bad = what; bad_lane = l; bad_val = v; }
@@ -4292,8 +4386,8 @@ static int build_lane_roles(sumo_engine* E) {
       if (!jh) nfree++;
     }
     if (bad) FAIL(-26, "lane %d: %s = %ld does not fit its field of the lane role words", bad_lane, bad, bad_val);
-    if (E->L.tree_ok && l >= 1 && l < m->nbody) {   // what the tree-shaped velocity pass derives instead of reading b_chain / b_chain_own
-      const int len = K.b_chain_len, ld = len > 0 ? BYTE_OF(K.b_chain, len - 1) : 0, B = K.b_agent ? E->L.d1 : 0;
+    if (S.L.tree_ok && l >= 1 && l < m->nbody) {   // what the tree-shaped velocity pass derives instead of reading b_chain / b_chain_own
+      const int len = K.b_chain_len, ld = len > 0 ? BYTE_OF(K.b_chain, len - 1) : 0, B = K.b_agent ? S.L.d1 : 0;
       int ok = len >= 6 && len <= 8;
       for (int p = 0; ok && p < len; p++) {
         const int want = p < 6 ? B + p : (len > 7 ? ld - 7 + p : ld);
@@ -4308,105 +4402,140 @@ static int build_lane_roles(sumo_engine* E) {
   return 0;
 }
 
-static int model_ints(const sumo_model_t* m, int32_t* out);
-extern "C" int sumo_create(const void* model_blob, size_t nbytes, int num_envs, int device, sumo_handle_t* out) {
-  if (!model_blob || !out || num_envs <= 0) FAIL(-1, "bad arguments");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) FAIL(-2, "no HIP device available: the engine has no CPU fallback");
-  if (device < 0 || device >= ndev) FAIL(-3, "device %d out of range (%d devices)", device, ndev);
-  HIPCHK(hipSetDevice(device));
-  sumo_engine* E = new sumo_engine();
-  E->device = device; E->N = num_envs;
-  E->blob.assign((const char*)model_blob, (const char*)model_blob + nbytes);
-  int rc = sumo_model_parse(&E->hm, E->blob.data(), nbytes);
-  if (rc != 0) { delete E; FAIL(-4, "malformed model blob (%d)", rc); }
-  std::vector<int> ai; std::vector<double> af; std::vector<signed char> pic;
-  rc = build_aux(E, ai, af, pic);
-  if (rc != 0) { delete E; return rc; }
-  build_layout(E);
-  rc = build_lane_roles(E);
-  if (rc != 0) { delete E; return rc; }
+// the integer members of the compiled model view (header dims, then the int / float table offsets in SUMO_*_TABLES order)
+static int model_ints(const sumo_model_t* m, int32_t* out) {
+  int n = 0;
+  out[n++] = m->nq; out[n++] = m->nv; out[n++] = m->nu; out[n++] = m->nbody; out[n++] = m->njnt; out[n++] = m->ngeom; out[n++] = m->npair;
+  out[n++] = m->nagent; out[n++] = m->frame_skip; out[n++] = m->timestep_limit;
+#define X(name, len) out[n++] = m->o_##name;
+  SUMO_INT_TABLES(X)
+  SUMO_FLT_TABLES(X)
+#undef X
+  return n;
+}
+
+// The last stage of a preparation, what only the whole scene can answer: which kernel variants run it, whether its constraint rows
+// fit the registers, and the strides of its per-env records.
+static int finish_scene(Scene& S, const SceneOptions& opt) {
   {   // static kernel variants only when the runtime Layout IS the compile-time table (SUMO_STATIC_LAYOUT=0 switches them off)
     static_assert(sizeof(Layout) % sizeof(int) == 0, "Layout is all ints");
-    const char* sl = getenv("SUMO_STATIC_LAYOUT");
     int32_t mi[160];
-    const int nmi = model_ints(&E->hm, mi);
+    const int nmi = model_ints(&S.hm, mi);
     auto same = [&](const int* kl, size_t nl, const int* km, size_t nm_, const int* ka, size_t na) {
-      return nl == sizeof(Layout) && memcmp(&E->L, kl, nl) == 0 && nm_ == nmi * sizeof(int) && memcmp(mi, km, nm_) == 0 &&
-             na == AUX_NINTS * sizeof(int) && memcmp(&E->aux.ndepth, ka, na) == 0;
+      return nl == sizeof(Layout) && memcmp(&S.L, kl, nl) == 0 && nm_ == nmi * sizeof(int) && memcmp(mi, km, nm_) == 0 &&
+             na == AUX_NINTS * sizeof(int) && memcmp(&S.aux.ndepth, ka, na) == 0;
     };
-    E->static_layout = 0;      // 1: Ant-vs-Ant, 2: Spider-vs-Spider (the scenes of csrc/layout_static.h), 0: runtime-Layout variants
-    if (!(sl && atoi(sl) == 0)) {
-      if (same(kLayoutAntAnt, sizeof(kLayoutAntAnt), kModelAntAnt, sizeof(kModelAntAnt), kAuxAntAnt, sizeof(kAuxAntAnt))) E->static_layout = 1;
+    S.static_layout = 0;      // 1: Ant-vs-Ant, 2: Spider-vs-Spider (the scenes of csrc/layout_static.h), 0: runtime-Layout variants
+    if (opt.static_layout) {
+      if (same(kLayoutAntAnt, sizeof(kLayoutAntAnt), kModelAntAnt, sizeof(kModelAntAnt), kAuxAntAnt, sizeof(kAuxAntAnt))) S.static_layout = 1;
       else if (same(kLayoutSpiderSpider, sizeof(kLayoutSpiderSpider), kModelSpiderSpider, sizeof(kModelSpiderSpider), kAuxSpiderSpider, sizeof(kAuxSpiderSpider)))
-        E->static_layout = 2;
+        S.static_layout = 2;
     }
   }
-  if (E->L.maxefc > WAVE * (E->hm.nv <= 28 ? 2 : 4)) { int me = E->L.maxefc; delete E; FAIL(-24, "maxefc %d exceeds the rows a lane keeps in registers", me); }
-  hipDeviceProp_t prop;
-  HIPCHK(hipGetDeviceProperties(&prop, device));
-  if ((size_t)E->L.total_bytes > prop.sharedMemPerBlock && (size_t)E->L.total_bytes > 160 * 1024) {
-    delete E; FAIL(-5, "LDS need %d bytes exceeds the device limit", E->L.total_bytes);
-  }
-  const sumo_model_t* m = &E->hm;
+  if (S.L.maxefc > WAVE * (S.hm.nv <= 28 ? 2 : 4)) FAIL(-24, "maxefc %d exceeds the rows a lane keeps in registers", S.L.maxefc);
+  const sumo_model_t* m = &S.hm;
   int od = 0, ad = 0;
   for (int a = 0; a < m->nagent; a++) {
     int o = SUMO_I(m, agent_nq)[a] + SUMO_I(m, agent_nv)[a] + 6 * SUMO_I(m, agent_nbody)[a] + 14;
     if (o > od) od = o;
     if (SUMO_I(m, agent_nu)[a] > ad) ad = SUMO_I(m, agent_nu)[a];
   }
-  E->obs_stride = od; E->act_stride = ad;
-  E->state_stride = (m->nq + 2 * m->nv + 2 + 15) & ~15;
-  HIPCHK(hipMalloc(&E->d_blob, nbytes));
-  HIPCHK(hipMemcpy(E->d_blob, E->blob.data(), nbytes, hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc((void**)&E->d_ai, ai.size() * sizeof(int)));
-  HIPCHK(hipMemcpy(E->d_ai, ai.data(), ai.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc((void**)&E->d_af, af.size() * sizeof(double)));
-  HIPCHK(hipMemcpy(E->d_af, af.data(), af.size() * sizeof(double), hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc((void**)&E->d_pic, pic.size()));
-  HIPCHK(hipMemcpy(E->d_pic, pic.data(), pic.size(), hipMemcpyHostToDevice));
-  E->aux.ai = E->d_ai; E->aux.af = E->d_af; E->aux.pic = E->d_pic;
-  E->dm = E->hm;
-  E->dm.ibase = (const int32_t*)((const char*)E->d_blob + ((const char*)E->hm.ibase - E->blob.data()));
-  E->dm.fbase = (const double*)((const char*)E->d_blob + ((const char*)E->hm.fbase - E->blob.data()));
-  HIPCHK(hipMalloc((void**)&E->d_lanes, E->lanes.size() * sizeof(LaneRec)));
-  HIPCHK(hipMemcpy(E->d_lanes, E->lanes.data(), E->lanes.size() * sizeof(LaneRec), hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc((void**)&E->d_pair_rec, E->pair_rec.size() * sizeof(int)));
-  HIPCHK(hipMemcpy(E->d_pair_rec, E->pair_rec.data(), E->pair_rec.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc((void**)&E->d_pair_bound, E->pair_bound.size() * sizeof(float)));
-  HIPCHK(hipMemcpy(E->d_pair_bound, E->pair_bound.data(), E->pair_bound.size() * sizeof(float), hipMemcpyHostToDevice));
+  S.obs_stride = od; S.act_stride = ad;
+  S.state_stride = (m->nq + 2 * m->nv + 2 + 15) & ~15;
+  return 0;
+}
+
+// The one preparation of a scene from a model blob, in stages; a caller stops after the stage it needs, and a scene that fails a
+// later stage still answers for the earlier ones.  Host only.
+enum SceneStage { SCENE_AUX, SCENE_LAYOUT, SCENE_ROLES, SCENE_CHECKED };
+static int prepare_scene(Scene& S, const void* blob, size_t nbytes, SceneStage upto) {
+  const SceneOptions opt = SceneOptions::from_env();
+  S.blob.assign((const char*)blob, (const char*)blob + nbytes);
+  if (int rc = sumo_model_parse(&S.hm, S.blob.data(), nbytes)) FAIL(-4, "malformed model blob (%d)", rc);
+  if (int rc = build_aux(S, opt)) return rc;             // aux tables, lane records, pair records
+  if (upto == SCENE_AUX) return 0;
+  build_layout(S, opt);
+  if (upto == SCENE_LAYOUT) return 0;
+  if (int rc = build_lane_roles(S)) return rc;           // after the layout: its tree_ok decides what the words must carry
+  if (upto == SCENE_ROLES) return 0;
+  return finish_scene(S, opt);
+}
+
+// kernel variants by nv (the factorisation is unrolled over a compile-time nv); the nine registered scenes have
+// nv in {28, 32, 36, 40, 44}
+template <class F>
+static bool for_kernel_variant(int nv, F&& f) {
+#define X(NVV) if (nv == NVV) { f(std::integral_constant<int, NVV>()); return true; }
+  SUMO_FOR_NV(X)
+#undef X
+  return false;
+}
+
+// an env record of more than the 64 KB of LDS a launch gets without asking
+template <int NV>
+static int allow_large_lds(int bytes) {
+  HIPCHK(hipFuncSetAttribute((const void*)sumo_step_kernel<NV>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  HIPCHK(hipFuncSetAttribute((const void*)sumo_reset_kernel<NV>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  HIPCHK(hipFuncSetAttribute((const void*)sumo_forward_kernel<NV>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  return 0;
+}
+
+// Every failure below returns through the unique_ptr: the engine and whatever it had allocated on the device go with it.
+extern "C" int sumo_create(const void* model_blob, size_t nbytes, int num_envs, int device, sumo_handle_t* out) {
+  if (!model_blob || !out || num_envs <= 0) FAIL(-1, "bad arguments");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) FAIL(-2, "no HIP device available: the engine has no CPU fallback");
+  if (device < 0 || device >= ndev) FAIL(-3, "device %d out of range (%d devices)", device, ndev);
+  HIPCHK(hipSetDevice(device));
+  std::unique_ptr<sumo_engine> E(new sumo_engine());
+  E->device = device; E->N = num_envs;
+  if (int rc = prepare_scene(*E, model_blob, nbytes, SCENE_CHECKED)) return rc;
+  hipDeviceProp_t prop;
+  HIPCHK(hipGetDeviceProperties(&prop, device));
+  if ((size_t)E->L.total_bytes > prop.sharedMemPerBlock && (size_t)E->L.total_bytes > 160 * 1024)
+    FAIL(-5, "LDS need %d bytes exceeds the device limit", E->L.total_bytes);
+  const sumo_model_t* m = &E->hm;
+  HIPCHK(E->d_blob.upload(E->blob));
+  HIPCHK(E->d_ai.upload(E->ai));
+  HIPCHK(E->d_af.upload(E->af));
+  HIPCHK(E->d_pic.upload(E->pic));
+  HIPCHK(E->d_lanes.upload(E->lanes));
+  HIPCHK(E->d_pair_rec.upload(E->pair_rec));
+  HIPCHK(E->d_pair_bound.upload(E->pair_bound));
   {
     Params hp;
-    hp.mdl = E->dm; hp.aux = E->aux; hp.L = E->L;
+    hp.mdl = E->hm;   // the device view: the host view with its table bases inside the uploaded blob
+    hp.mdl.ibase = (const int32_t*)(E->d_blob.get() + ((const char*)E->hm.ibase - E->blob.data()));
+    hp.mdl.fbase = (const double*)(E->d_blob.get() + ((const char*)E->hm.fbase - E->blob.data()));
+    hp.aux = E->aux; hp.aux.ai = E->d_ai; hp.aux.af = E->d_af; hp.aux.pic = E->d_pic;
+    hp.L = E->L;
     hp.lanes = E->d_lanes; hp.pair_rec = E->d_pair_rec; hp.pair_bound = E->d_pair_bound;
     hp.adjust_z = 0.0;
-    HIPCHK(hipMalloc((void**)&E->d_params, sizeof(Params)));
+    HIPCHK(E->d_params.alloc(1));
     HIPCHK(hipMemcpy(E->d_params, &hp, sizeof(Params), hipMemcpyHostToDevice));
   }
   size_t N = (size_t)num_envs;
-  HIPCHK(hipMalloc((void**)&E->d_state, N * E->state_stride * sizeof(double)));
+  HIPCHK(E->d_state.alloc(N * E->state_stride));
   HIPCHK(hipMemset(E->d_state, 0, N * E->state_stride * sizeof(double)));
-  HIPCHK(hipMalloc((void**)&E->d_counters, N * 4 * sizeof(int)));
+  HIPCHK(E->d_counters.alloc(N * 4));
   HIPCHK(hipMemset(E->d_counters, 0, N * 4 * sizeof(int)));
-  HIPCHK(hipMalloc((void**)&E->d_seeds, N * sizeof(uint64_t)));
   std::vector<uint64_t> seeds(N);
   for (size_t i = 0; i < N; i++) seeds[i] = i;
-  HIPCHK(hipMemcpy(E->d_seeds, seeds.data(), N * sizeof(uint64_t), hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc((void**)&E->d_stats, 48 * sizeof(unsigned long long)));
+  HIPCHK(E->d_seeds.upload(seeds));
+  HIPCHK(E->d_stats.alloc(48));
   HIPCHK(hipMemset(E->d_stats, 0, 48 * sizeof(unsigned long long)));
   {
     const char* sc = getenv("SUMO_SCHED");
     E->sched = !(sc && atoi(sc) == 0);
-    HIPCHK(hipMalloc((void**)&E->d_cost, 2 * N * sizeof(int)));
-    HIPCHK(hipMalloc((void**)&E->d_cost_sorted, N * sizeof(int)));
-    HIPCHK(hipMalloc((void**)&E->d_iota, N * sizeof(int)));
-    HIPCHK(hipMalloc((void**)&E->d_perm, 2 * N * sizeof(int)));
+    HIPCHK(E->d_cost.alloc(2 * N));
+    HIPCHK(E->d_cost_sorted.alloc(N));
+    HIPCHK(E->d_perm.alloc(2 * N));
     std::vector<int> iota(N);
     for (size_t i = 0; i < N; i++) iota[i] = (int)i;
-    HIPCHK(hipMemcpy(E->d_iota, iota.data(), N * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(rocprim::radix_sort_pairs_desc(nullptr, E->sort_tmp_bytes, E->d_cost, E->d_cost_sorted, E->d_iota, E->d_perm, N, 0, 16,
-                                          (hipStream_t)0));
-    HIPCHK(hipMalloc(&E->d_sort_tmp, E->sort_tmp_bytes ? E->sort_tmp_bytes : 16));
+    HIPCHK(E->d_iota.upload(iota));
+    HIPCHK(rocprim::radix_sort_pairs_desc(nullptr, E->sort_tmp_bytes, E->d_cost.get(), E->d_cost_sorted.get(), E->d_iota.get(), E->d_perm.get(), N,
+                                          0, 16, (hipStream_t)0));
+    HIPCHK(E->d_sort_tmp.alloc(E->sort_tmp_bytes ? E->sort_tmp_bytes : 16));
   }
   // qpos = qpos0 for every env until the first reset / set_state
   {
@@ -4415,26 +4544,18 @@ extern "C" int sumo_create(const void* model_blob, size_t nbytes, int num_envs, 
     HIPCHK(hipMemcpy(E->d_state, st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice));
   }
   if (E->L.total_bytes > 64 * 1024) {
-#define X(NVV)                                                                                                         \
-    if (E->hm.nv == NVV) {                                                                                            \
-      HIPCHK(hipFuncSetAttribute((const void*)sumo_step_kernel<NVV>, hipFuncAttributeMaxDynamicSharedMemorySize, E->L.total_bytes));    \
-      HIPCHK(hipFuncSetAttribute((const void*)sumo_reset_kernel<NVV>, hipFuncAttributeMaxDynamicSharedMemorySize, E->L.total_bytes));   \
-      HIPCHK(hipFuncSetAttribute((const void*)sumo_forward_kernel<NVV>, hipFuncAttributeMaxDynamicSharedMemorySize, E->L.total_bytes)); \
-    }
-    SUMO_FOR_NV(X)
-#undef X
+    int rc = 0;
+    for_kernel_variant(E->hm.nv, [&](auto nvc_) { rc = allow_large_lds<decltype(nvc_)::value>(E->L.total_bytes); });
+    if (rc) return rc;
   }
-  *out = E;
+  *out = E.release();
   return 0;
 }
 
 extern "C" int sumo_destroy(sumo_handle_t E) {
   if (!E) return 0;
   (void)hipSetDevice(E->device);
-  (void)hipFree(E->d_params); (void)hipFree(E->d_lanes); (void)hipFree(E->d_pair_rec); (void)hipFree(E->d_pair_bound); (void)hipFree(E->d_blob); (void)hipFree(E->d_ai); (void)hipFree(E->d_af); (void)hipFree(E->d_pic); (void)hipFree(E->d_state); (void)hipFree(E->d_state_prev); (void)hipFree(E->d_fbuf); (void)hipFree(E->d_cfrc);
-  (void)hipFree(E->d_counters); (void)hipFree(E->d_seeds); (void)hipFree(E->d_stats); (void)hipFree(E->d_rsched);
-  (void)hipFree(E->d_cost); (void)hipFree(E->d_cost_sorted); (void)hipFree(E->d_iota); (void)hipFree(E->d_perm); (void)hipFree(E->d_sort_tmp);
-  delete E;
+  delete E;   // its DevBuf members free the device memory
   return 0;
 }
 
@@ -4447,15 +4568,6 @@ extern "C" int sumo_dims(sumo_handle_t E, int32_t* o) {
   return 0;
 }
 
-// kernel variants by nv (the factorisation is unrolled over a compile-time nv); the nine registered scenes have
-// nv in {28, 32, 36, 40, 44}
-template <class F>
-static bool for_kernel_variant(int nv, F&& f) {
-#define X(NVV) if (nv == NVV) { f(std::integral_constant<int, NVV>()); return true; }
-  SUMO_FOR_NV(X)
-#undef X
-  return false;
-}
 // the variant an engine's step / rollout kernels run: f(NV, SL) with the static layouts <28, 1> (Ant vs Ant) and <44, 2> (Spider
 // vs Spider) where sumo_create found one, else <nv, 0>
 template <class F>
@@ -4551,8 +4663,8 @@ extern "C" int sumo_step(sumo_handle_t E, const float* actions_dev, float* obs_d
     HIPCHK(hipGetLastError());
   }
   if (E->sched && E->N > SCHED_RANK_MAX) {   // costs stay below 2^16 (see the step kernel's epilogue)
-    HIPCHK(rocprim::radix_sort_pairs_desc(E->d_sort_tmp, E->sort_tmp_bytes, E->d_cost, E->d_cost_sorted, E->d_iota, E->d_perm,
-                                          (size_t)E->N, 0, 16, (hipStream_t)stream));
+    HIPCHK(rocprim::radix_sort_pairs_desc(E->d_sort_tmp.get(), E->sort_tmp_bytes, E->d_cost.get(), E->d_cost_sorted.get(), E->d_iota.get(),
+                                          E->d_perm.get(), (size_t)E->N, 0, 16, (hipStream_t)stream));
     E->perm_valid = true;
   }
   return 0;
@@ -4588,7 +4700,7 @@ static int rollout_launch(sumo_engine* E, const RolloutArgs& r, int policy, cons
   rl.r = r;
   rl.r.prof = E->d_trace;   // development: sumo_debug_trace(stamps) switches the per-wave phase clock on
   hipStream_t st_ = (hipStream_t)stream;
-  if (!E->d_rsched) HIPCHK(hipMalloc((void**)&E->d_rsched, (size_t)(2 + E->N) * sizeof(int)));
+  if (!E->d_rsched) HIPCHK(E->d_rsched.alloc((size_t)(2 + E->N)));
   HIPCHK(hipMemsetAsync(E->d_rsched, 0, (size_t)(2 + E->N) * sizeof(int), st_));
   rl.r.sched = E->d_rsched;
   if (r.K >= 65536) FAIL(-5, "K = %d: at most 65535 steps per fused launch", r.K);
@@ -5071,9 +5183,9 @@ extern "C" int sumo_set_cfrc_mode(sumo_handle_t E, int mode) {
   if (mode != 0 && mode != 1) FAIL(-2, "cfrc_mode %d: 0 (zero) or 1 (rne_post)", mode);
   HIPCHK(hipSetDevice(E->device));
   if (mode && !E->d_state_prev) {
-    HIPCHK(hipMalloc((void**)&E->d_state_prev, (size_t)E->N * E->state_stride * sizeof(double)));
-    HIPCHK(hipMalloc((void**)&E->d_fbuf, (size_t)E->N * 5 * E->L.maxcon * sizeof(double)));
-    HIPCHK(hipMalloc((void**)&E->d_cfrc, (size_t)E->N * 6 * E->hm.nbody * sizeof(double)));
+    HIPCHK(E->d_state_prev.alloc((size_t)E->N * E->state_stride));
+    HIPCHK(E->d_fbuf.alloc((size_t)E->N * 5 * E->L.maxcon));
+    HIPCHK(E->d_cfrc.alloc((size_t)E->N * 6 * E->hm.nbody));
     HIPCHK(hipMemset(E->d_cfrc, 0, (size_t)E->N * 6 * E->hm.nbody * sizeof(double)));
   }
   E->cfrc_mode = mode;
@@ -5084,7 +5196,7 @@ extern "C" int sumo_set_adjust_z(sumo_handle_t E, double adjust_z) {
   if (!(fabs(adjust_z) <= 1e10)) FAIL(-2, "adjust_z must be finite");
   HIPCHK(hipSetDevice(E->device));
   HIPCHK(hipDeviceSynchronize());   // no launch of this engine may be reading the parameter block
-  HIPCHK(hipMemcpy((char*)E->d_params + offsetof(Params, adjust_z), &adjust_z, sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy((char*)E->d_params.get() + offsetof(Params, adjust_z), &adjust_z, sizeof(double), hipMemcpyHostToDevice));
   E->adjust_z = adjust_z;
   return 0;
 }
@@ -5118,57 +5230,35 @@ extern "C" int sumo_rollout_status(sumo_handle_t E, int64_t* out4) {
   } else if (out4) for (int i = 0; i < 4; i++) out4[i] = o[i];
   return 0;
 }
-// host only (no device is touched): the Layout build_layout() computes for a scene, as ints in declaration order; returns the count.
-// tools/gen_static_layout.py turns it into csrc/layout_static.h.
+// The three host-only exports (no device is touched) run sumo_create's own prepare_scene, up to the stage they report.
+// The Layout of a scene, as ints in declaration order; returns the count.  tools/gen_static_layout.py turns it into csrc/layout_static.h.
 extern "C" int sumo_debug_layout(const void* model_blob, size_t nbytes, int32_t* out, int cap) {
   if (!model_blob || !out) FAIL(-1, "bad arguments");
-  sumo_engine E;
-  E.blob.assign((const char*)model_blob, (const char*)model_blob + nbytes);
-  if (int rc = sumo_model_parse(&E.hm, E.blob.data(), nbytes)) FAIL(-4, "malformed model blob (%d)", rc);
-  std::vector<int> ai; std::vector<double> af; std::vector<signed char> pic;
-  if (int rc = build_aux(&E, ai, af, pic)) return rc;
-  build_layout(&E);
+  Scene sc;
+  if (int rc = prepare_scene(sc, model_blob, nbytes, SCENE_LAYOUT)) return rc;
   const int n = (int)(sizeof(Layout) / sizeof(int));
   if (cap < n) FAIL(-2, "need room for %d ints", n);
-  memcpy(out, &E.L, sizeof(Layout));
+  memcpy(out, &sc.L, sizeof(Layout));
   return n;
 }
-// host only (no device is touched): the two packed role words of the 64 lanes (LaneRec::role0 / role1; the ROLE0_* / ROLE1_* fields),
-// out[2 * lane], out[2 * lane + 1]; returns the count, or the error sumo_create would give for a scene whose roles do not fit.
+// The two packed role words of the 64 lanes (LaneRec::role0 / role1; the ROLE0_* / ROLE1_* fields), out[2 * lane], out[2 * lane + 1];
+// returns the count, or the error sumo_create gives for a scene whose roles do not fit.
 extern "C" int sumo_debug_lane_roles(const void* model_blob, size_t nbytes, uint32_t* out, int cap) {
   if (!model_blob || !out) FAIL(-1, "bad arguments");
-  sumo_engine E;
-  E.blob.assign((const char*)model_blob, (const char*)model_blob + nbytes);
-  if (int rc = sumo_model_parse(&E.hm, E.blob.data(), nbytes)) FAIL(-4, "malformed model blob (%d)", rc);
-  std::vector<int> ai; std::vector<double> af; std::vector<signed char> pic;
-  if (int rc = build_aux(&E, ai, af, pic)) return rc;
-  build_layout(&E);
-  if (int rc = build_lane_roles(&E)) return rc;
+  Scene sc;
+  if (int rc = prepare_scene(sc, model_blob, nbytes, SCENE_ROLES)) return rc;
   if (cap < 2 * WAVE) FAIL(-2, "need room for %d words", 2 * WAVE);
-  for (int l = 0; l < WAVE; l++) { out[2 * l] = E.lanes[l].role0; out[2 * l + 1] = E.lanes[l].role1; }
+  for (int l = 0; l < WAVE; l++) { out[2 * l] = sc.lanes[l].role0; out[2 * l + 1] = sc.lanes[l].role1; }
   return 2 * WAVE;
 }
-// the integer members of the compiled model view (header dims, then the int / float table offsets in SUMO_*_TABLES order) and of Aux
-static int model_ints(const sumo_model_t* m, int32_t* out) {
-  int n = 0;
-  out[n++] = m->nq; out[n++] = m->nv; out[n++] = m->nu; out[n++] = m->nbody; out[n++] = m->njnt; out[n++] = m->ngeom; out[n++] = m->npair;
-  out[n++] = m->nagent; out[n++] = m->frame_skip; out[n++] = m->timestep_limit;
-#define X(name, len) out[n++] = m->o_##name;
-  SUMO_INT_TABLES(X)
-  SUMO_FLT_TABLES(X)
-#undef X
-  return n;
-}
+// The integer members of the compiled model view (model_ints) and of Aux; returns the two counts, the second shifted left by 16.
 extern "C" int sumo_debug_model_ints(const void* model_blob, size_t nbytes, int32_t* out, int cap, int32_t* aux_out, int aux_cap) {
   if (!model_blob || !out || !aux_out) FAIL(-1, "bad arguments");
-  sumo_engine E;
-  E.blob.assign((const char*)model_blob, (const char*)model_blob + nbytes);
-  if (int rc = sumo_model_parse(&E.hm, E.blob.data(), nbytes)) FAIL(-4, "malformed model blob (%d)", rc);
-  std::vector<int> ai; std::vector<double> af; std::vector<signed char> pic;
-  if (int rc = build_aux(&E, ai, af, pic)) return rc;
+  Scene sc;
+  if (int rc = prepare_scene(sc, model_blob, nbytes, SCENE_AUX)) return rc;
   if (cap < 128 || aux_cap < AUX_NINTS) FAIL(-2, "buffers too small");
-  const int n = model_ints(&E.hm, out);
-  memcpy(aux_out, &E.aux.ndepth, AUX_NINTS * sizeof(int));
+  const int n = model_ints(&sc.hm, out);
+  memcpy(aux_out, &sc.aux.ndepth, AUX_NINTS * sizeof(int));
   return n | (AUX_NINTS << 16);
 }
 extern "C" int sumo_static_layout(sumo_handle_t E) { return E ? E->static_layout : -1; }   // 1: this engine runs the static-Layout kernel variants
@@ -5235,11 +5325,11 @@ extern "C" int sumo_debug_forward(sumo_handle_t E, const double* ctrl, double* q
   HIPCHK(hipSetDevice(E->device));
   const sumo_model_t* m = &E->hm;
   size_t N = (size_t)E->N;
-  double *d_ctrl, *d_qacc;
-  int* d_cnt;
-  HIPCHK(hipMalloc((void**)&d_ctrl, N * m->nu * sizeof(double)));
-  HIPCHK(hipMalloc((void**)&d_qacc, N * m->nv * sizeof(double)));
-  HIPCHK(hipMalloc((void**)&d_cnt, N * 4 * sizeof(int)));
+  DevBuf<double> d_ctrl, d_qacc;
+  DevBuf<int> d_cnt;
+  HIPCHK(d_ctrl.alloc(N * m->nu));
+  HIPCHK(d_qacc.alloc(N * m->nv));
+  HIPCHK(d_cnt.alloc(N * 4));
   HIPCHK(hipMemcpy(d_ctrl, ctrl, N * m->nu * sizeof(double), hipMemcpyHostToDevice));
   StepArgs a = base_args(E);
   a.stats = nullptr; a.dbg_ctrl = d_ctrl; a.dbg_qacc = d_qacc; a.dbg_counts = d_cnt;
@@ -5248,7 +5338,6 @@ extern "C" int sumo_debug_forward(sumo_handle_t E, const double* ctrl, double* q
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy(qacc, d_qacc, N * m->nv * sizeof(double), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(counts, d_cnt, N * 4 * sizeof(int), hipMemcpyDeviceToHost));
-  (void)hipFree(d_ctrl); (void)hipFree(d_qacc); (void)hipFree(d_cnt);
   return 0;
 }
 

@@ -419,6 +419,20 @@ int sumo_debug_model_ints(const void* model_blob, size_t nbytes, int32_t* out, i
  * ROLE1_* in csrc/sumo_engine.hip; tests/test_lane_roles_cpu.py unpacks them).  Returns 128, or the error sumo_create gives for a scene
  * in which a value does not fit its field. */
 int sumo_debug_lane_roles(const void* model_blob, size_t nbytes, uint32_t* out, int cap);
+/* development / tests, host only: the Newton loop's gradient test `scale * sqrt(gn) < tol` as a threshold on gn, the squared gradient
+ * norm -- *out = the largest double G with scale * sqrt(G) < tol, so that the test is gn <= G (-1 where no gn >= 0 passes); found by
+ * bisection over the bit patterns with IEEE sqrt.  sumo_create computes it once per scene from the model's options. */
+int sumo_debug_grad_threshold(double scale, double tol, double* out);
+/* development / tests: one wave over caller-given lanes through the in-wave primitives of the engine kernels (all HOST pointers).
+ * in64x8 float64 [8][64], int_in64 int32 [64] ->
+ *   sums20 float64 [20]: the single wave sum of rows 0 .. 7, then the paired form on rows 0 .. 1, the 4-fold on rows 0 .. 3 and the
+ *                        6-fold on rows 0 .. 5;
+ *   swapped64 float64 [64]: row 0 exchanged between neighbouring lanes (lane i receives lane i ^ 1);
+ *   scan65 int32 [65]: the exclusive scan of int_in64 and, last, its total;
+ *   grad_out uint8 [ngn][2]: for each gn[i] the gradient test in its sqrt form (scale * sqrt(gn) < tol, evaluated on the device) and in
+ *                        its threshold form (gn <= sumo_debug_grad_threshold(scale, tol)).  ngn may be 0. */
+int sumo_debug_wave_ops(sumo_handle_t h, const double* in64x8, const int32_t* int_in64, double* sums20, double* swapped64,
+                        int32_t* scan65, const double* gn, int ngn, double scale, double tol, uint8_t* grad_out);
 /* development (-DSUMO_DBG_DUMP builds): device buffer [20][8][64] float64 that receives intermediate vectors of env 0's forward
  * evaluations (tools/dump_diff.py); NULL = off */
 int sumo_debug_dump(sumo_handle_t h, double* dev_buf);

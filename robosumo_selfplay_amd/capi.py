@@ -129,6 +129,11 @@ def lib():
         L.sumo_static_layout.argtypes = [vp]
         L.sumo_static_layout.restype = i32
         L.sumo_profile.restype = i32
+        if hasattr(L, "sumo_debug_wave_ops"):   # a SUMO_HIP_LIB build from before these two debug exports still runs everything else (_debug_export)
+            L.sumo_debug_grad_threshold.argtypes = [C.c_double, C.c_double, vp]
+            L.sumo_debug_grad_threshold.restype = i32
+            L.sumo_debug_wave_ops.argtypes = [vp] * 7 + [i32, C.c_double, C.c_double, vp]
+            L.sumo_debug_wave_ops.restype = i32
         for n in ("sumo_create", "sumo_destroy", "sumo_dims", "sumo_reset", "sumo_step", "sumo_get_state", "sumo_set_cfrc_mode",
                   "sumo_get_cfrc_ext", "sumo_set_adjust_z", "sumo_set_state", "sumo_debug_forward", "sumo_stats"):
             getattr(L, n).restype = i32
@@ -149,6 +154,22 @@ def _np(a):
 def _chk(rc):
     if rc != 0:
         raise SumoHipError("sumo_hip error %d: %s" % (rc, lib().sumo_last_error().decode()))
+
+
+def _debug_export(name):
+    """One of the two debug exports that an older SUMO_HIP_LIB build may lack: a clear error instead of ctypes' AttributeError."""
+    L = lib()
+    if not hasattr(L, name):
+        raise SumoHipError("%s is not exported by %s: rebuild the engine library" % (name, L._name))
+    return getattr(L, name)
+
+
+def grad_threshold(scale, tol):
+    """Development / tests (host only): the largest float64 G with scale * sqrt(G) < tol -- the Newton loop's gradient test as a
+    threshold on the squared gradient norm (sumo_debug_grad_threshold); -1 where no G >= 0 passes."""
+    out = C.c_double()
+    _chk(_debug_export("sumo_debug_grad_threshold")(float(scale), float(tol), C.byref(out)))
+    return out.value
 
 
 class Engine:
@@ -318,6 +339,21 @@ class Engine:
         counts = np.zeros((self.N, 4), np.int32)
         _chk(lib().sumo_debug_forward(self.h, _np(ctrl), _np(qacc), _np(counts)))
         return qacc, counts
+
+    def debug_wave_ops(self, rows, ints, gn=(), scale=1.0, tol=0.0):
+        """Development / tests: one wave through the kernels' in-wave primitives (sumo_debug_wave_ops).  rows float64 [8][64],
+        ints int32 [64] -> (sums [20], row 0 pair-swapped [64], exclusive scan [64], its total, gradient test [len(gn)][2]: the
+        sqrt form and the threshold form at `scale`, `tol`)."""
+        rows = np.ascontiguousarray(rows, np.float64)
+        ints = np.ascontiguousarray(ints, np.int32)
+        gn = np.ascontiguousarray(gn, np.float64)
+        if rows.shape != (8, 64) or ints.shape != (64,) or gn.ndim != 1:
+            raise ValueError("rows must be [8][64], ints [64], gn one-dimensional")
+        sums, swapped, scan = np.zeros(20), np.zeros(64), np.zeros(65, np.int32)
+        grad = np.zeros((max(len(gn), 1), 2), np.uint8)
+        _chk(_debug_export("sumo_debug_wave_ops")(self.h, _np(rows), _np(ints), _np(sums), _np(swapped), _np(scan), _np(gn) if len(gn) else None,
+                                       len(gn), float(scale), float(tol), _np(grad)))
+        return sums, swapped, scan[:64], int(scan[64]), grad[:len(gn)].astype(bool)
 
     def debug_trace(self, stamps_ptr):
         """Development: device uint64 [N][4] buffer that receives each env wave's start / end stamps and work counters (0 / None = off)."""

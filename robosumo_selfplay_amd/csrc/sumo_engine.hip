@@ -280,34 +280,35 @@ __device__ __forceinline__ void cross_force(double* r, const double* vel, const 
   r[4] = vel[2] * f[3] - vel[0] * f[5];
   r[5] = -vel[1] * f[3] + vel[0] * f[4];
 }
-// DPP move of a double (two 32-bit halves); lanes whose source is out of range / masked read 0
-template <int CTRL, int ROW_MASK>
+// DPP move of a double (two 32-bit halves), every row enabled, bound_ctrl on: a lane without a source reads 0.  (With bound_ctrl
+// off the builtin's `old` operand is live, and the compiler fills it with a v_mov 0 in front of every DPP move.)
+template <int CTRL>
 __device__ __forceinline__ double dpp_mov_f64(double v) {
   int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, ROW_MASK, 0xF, false);
-  hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, ROW_MASK, 0xF, false);
+  lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);
+  hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
   return __hiloint2double(hi, lo);
 }
 __device__ __forceinline__ double readlane_f64(double v, int l) {
   int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
   return __hiloint2double(hi, lo);
 }
-// wave-wide sum, identical bits in every lane (in-row scan with row_shr, then row_bcast 15 / 31, total in lane 63)
+// wave-wide sum, returned wave-uniform from lane 63: in-row scan with row_shr, then row_bcast 15 / 31.  The two broadcast stages
+// run with every row enabled: lane 63 takes lane 47 (its row's source) in the first and lane 31 in the second, lane 31 took lane 15
+// in the first, and each source is read before its own stage's add -- lane 63 ends as (d63 + d47) + (d31 + d15), d the row totals.
+// The lanes of rows 0 and 2 hold other (defined) numbers after these stages; nothing reads a lane but through the readlane of 63.
+#define WAVE_SUM_STAGES(X) X(0x111) X(0x112) X(0x114) X(0x118) X(0x142) X(0x143)   /* row_shr 1, 2, 4, 8; row_bcast 15, 31 */
 __device__ __forceinline__ double wave_sum(double v) {
-  v += dpp_mov_f64<0x111, 0xF>(v);  // row_shr:1
-  v += dpp_mov_f64<0x112, 0xF>(v);  // row_shr:2
-  v += dpp_mov_f64<0x114, 0xF>(v);  // row_shr:4
-  v += dpp_mov_f64<0x118, 0xF>(v);  // row_shr:8
-  v += dpp_mov_f64<0x142, 0xA>(v);  // row_bcast:15 -> rows 1,3
-  v += dpp_mov_f64<0x143, 0xC>(v);  // row_bcast:31 -> rows 2,3
+#define WAVE_SUM_STAGE(CTRL) v += dpp_mov_f64<CTRL>(v);
+  WAVE_SUM_STAGES(WAVE_SUM_STAGE)
+#undef WAVE_SUM_STAGE
   return readlane_f64(v, 63);
 }
-// two / four wave sums whose inputs are ready together: wave_sum's adds per value, the stages of the chains interleaved
+// N wave sums whose inputs are ready together: wave_sum's adds per value, the stages of the chains interleaved
 template <int N>
 __device__ __forceinline__ void wave_sum_n(double (&v)[N]) {
-#define WAVE_SUM_STAGE(CTRL, MASK) _Pragma("unroll") for (int k = 0; k < N; k++) v[k] += dpp_mov_f64<CTRL, MASK>(v[k]);
-  WAVE_SUM_STAGE(0x111, 0xF) WAVE_SUM_STAGE(0x112, 0xF) WAVE_SUM_STAGE(0x114, 0xF) WAVE_SUM_STAGE(0x118, 0xF)
-  WAVE_SUM_STAGE(0x142, 0xA) WAVE_SUM_STAGE(0x143, 0xC)
+#define WAVE_SUM_STAGE(CTRL) _Pragma("unroll") for (int k = 0; k < N; k++) v[k] += dpp_mov_f64<CTRL>(v[k]);
+  WAVE_SUM_STAGES(WAVE_SUM_STAGE)
 #undef WAVE_SUM_STAGE
 #pragma unroll
   for (int k = 0; k < N; k++) v[k] = readlane_f64(v[k], 63);
@@ -322,12 +323,14 @@ __device__ __forceinline__ void wave_sum4(double& a, double& b, double& c, doubl
   wave_sum_n(v);
   a = v[0]; b = v[1]; c = v[2]; d = v[3];
 }
+// exclusive scan over the wave + total.  Every lane's value is used: the row_shr stages read 0 where there is no source
+// (bound_ctrl), the two row_bcast stages keep their row masks and the `old` operand that the masked rows take.
 __device__ __forceinline__ int wave_excl_scan(int v, int lane, int* total) {
   int inc = v;
-  inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xF, 0xF, false);
-  inc += __builtin_amdgcn_update_dpp(0, inc, 0x112, 0xF, 0xF, false);
-  inc += __builtin_amdgcn_update_dpp(0, inc, 0x114, 0xF, 0xF, false);
-  inc += __builtin_amdgcn_update_dpp(0, inc, 0x118, 0xF, 0xF, false);
+  inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xF, 0xF, true);
+  inc += __builtin_amdgcn_update_dpp(0, inc, 0x112, 0xF, 0xF, true);
+  inc += __builtin_amdgcn_update_dpp(0, inc, 0x114, 0xF, 0xF, true);
+  inc += __builtin_amdgcn_update_dpp(0, inc, 0x118, 0xF, 0xF, true);
   inc += __builtin_amdgcn_update_dpp(0, inc, 0x142, 0xA, 0xF, false);
   inc += __builtin_amdgcn_update_dpp(0, inc, 0x143, 0xC, 0xF, false);
   *total = __builtin_amdgcn_readlane(inc, 63);
@@ -497,6 +500,7 @@ struct Params {  // lives in device memory; read through scalar / per-lane loads
   const int* pair_rec;      // [(wrounds + arounds) * 64] packed pair records (see build_aux)
   const float* pair_bound;  // conservative (rounded-up) reach of each pair
   double adjust_z;          // Agent._adjust_z (agents.py:33,155-161): added to the z an agent REPORTS -- observations and lose test; 0 in training
+  double grad_thresh;       // newton_solve's gradient test as a threshold on the squared norm (grad_threshold)
 };
 
 template <int NV_, class LT_ = Layout>
@@ -735,9 +739,10 @@ __device__ __forceinline__ void position_velocity(C& c) {
     double px = 0, py = 0, pz = 0;
     if (isb) { px = K.b_mass * S(xipos)[3 * lane]; py = K.b_mass * S(xipos)[3 * lane + 1]; pz = K.b_mass * S(xipos)[3 * lane + 2]; }
     const int ag = isb ? role_agent(c) : -1;
-    // six independent wave sums (x, y, z of both agents) issued together so their DPP chains overlap
-    const double s0x = wave_sum(ag == 0 ? px : 0.0), s0y = wave_sum(ag == 0 ? py : 0.0), s0z = wave_sum(ag == 0 ? pz : 0.0);
-    const double s1x = wave_sum(ag == 1 ? px : 0.0), s1y = wave_sum(ag == 1 ? py : 0.0), s1z = wave_sum(ag == 1 ? pz : 0.0);
+    // six independent wave sums (x, y, z of both agents), their DPP chains interleaved stage by stage
+    double cs[6] = {ag == 0 ? px : 0.0, ag == 0 ? py : 0.0, ag == 0 ? pz : 0.0, ag == 1 ? px : 0.0, ag == 1 ? py : 0.0, ag == 1 ? pz : 0.0};
+    wave_sum_n(cs);
+    const double s0x = cs[0], s0y = cs[1], s0z = cs[2], s1x = cs[3], s1y = cs[4], s1z = cs[5];
     if (lane < 2) {
       const double istm = fast_rcp(MF(body_subtreemass)[MI(agent_torso)[lane]]);
       S(com)[3 * lane] = (lane ? s1x : s0x) * istm; S(com)[3 * lane + 1] = (lane ? s1y : s0y) * istm; S(com)[3 * lane + 2] = (lane ? s1z : s0z) * istm;
@@ -1315,6 +1320,12 @@ __device__ __forceinline__ void make_constraint(C& c) {
       if (cb[0] != 0 && cb[1] != 0) { two = 1; if ((cb[0] >= b1) != (cb[1] >= b1)) cross = 1; }
     }
     c.htree = c.L.tree_ok && !c.L.force_dense && __ballot(two) == 0ull;
+#ifdef SUMO_DBG_DUMP
+    // development builds (-DSUMO_DBG_DUMP, the build tools/dump_diff.py runs): on the tree path every contact took
+    // one 3 x 8 block of the pool, so the offset of contact ci is 24 ci -- what tree_rows, contact_Jx<8> and the tree-path gradient
+    // rely on.  `ncon` is the count after the pool's capacity cut (at most maxcon, which is below 64: one contact per lane, word 4 * lane + 3).
+    assert(!(c.htree && lane < ncon && (c.si + c.L.con_b)[4 * lane + 3] != 24 * lane));
+#endif
     c.hcross = __ballot(cross) != 0ull;
   }
   // contact row parameters (same for the 4 pyramid edges of a contact)
@@ -1388,19 +1399,29 @@ __device__ __forceinline__ void make_constraint(C& c) {
 #define SLOT_OF(ci, d, p) ((((const signed char*)c.sb)[c.L.b_dofidx + 16 * (ci) + (p)] == (signed char)(d)) ? (p) : (p) + 8)
 // cp[3*c + a] = sum_s Jb[c][a][s] * x[dof(c,s)].  Branch-free and fully unrolled so all 16 slot loads are in flight at
 // once: Jb is exactly 0 in unused slots, so those may read any x.
-template <class C>
+// NS == 8 (the tree path, c.htree): every contact has one moving body, so its block is 3 x 8 at 24 * ci (make_constraint) and slots
+// 8 .. 15 do not exist.  The general form gives those slots jv = 0: each adds 0.0 * x to an accumulator that is never -0 (it starts at
+// +0, and an exact zero sum rounds to +0), so for finite x leaving them out changes no bit.  A non-finite x belongs to an env that the
+// divergence guard replaces at the end of the step.
+template <int NS = 16, class C>
 __device__ __forceinline__ void contact_Jx(C& c, const double* x) {
   for (int idx = c.lane; idx < 3 * c.ncon; idx += WAVE) {
     int ci = idx / 3, a = idx - 3 * ci;
-    const int info = (c.si + c.L.con_b)[4 * ci + 3], ns = (info >> 20) ? 16 : 8;
-    const double* Jb = S(Jb) + (info & 0xFFFFF) + ns * a;
     const signed char* di = (const signed char*)c.sb + c.L.b_dofidx + 16 * ci;
-    double xv[16], jv[16];
+    double xv[NS], jv[NS];
+    if constexpr (NS == 8) {
+      const double* Jb = S(Jb) + 24 * ci + 8 * a;
 #pragma unroll
-    for (int s = 0; s < 16; s++) { int d = di[s]; xv[s] = x[d < 0 ? 0 : d]; double jq = Jb[s]; jv[s] = s < ns ? jq : 0.0; }
+      for (int s = 0; s < 8; s++) { int d = di[s]; xv[s] = x[d < 0 ? 0 : d]; jv[s] = Jb[s]; }
+    } else {
+      const int info = (c.si + c.L.con_b)[4 * ci + 3], ns = (info >> 20) ? 16 : 8;
+      const double* Jb = S(Jb) + (info & 0xFFFFF) + ns * a;
+#pragma unroll
+      for (int s = 0; s < 16; s++) { int d = di[s]; xv[s] = x[d < 0 ? 0 : d]; double jq = Jb[s]; jv[s] = s < ns ? jq : 0.0; }
+    }
     double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
 #pragma unroll
-    for (int s = 0; s < 16; s += 4) { a0 += jv[s] * xv[s]; a1 += jv[s + 1] * xv[s + 1]; a2 += jv[s + 2] * xv[s + 2]; a3 += jv[s + 3] * xv[s + 3]; }
+    for (int s = 0; s < NS; s += 4) { a0 += jv[s] * xv[s]; a1 += jv[s + 1] * xv[s + 1]; a2 += jv[s + 2] * xv[s + 2]; a3 += jv[s + 3] * xv[s + 3]; }
     S(cp)[idx] = (a0 + a1) + (a2 + a3);
   }
   SYNC();
@@ -1408,26 +1429,32 @@ __device__ __forceinline__ void contact_Jx(C& c, const double* x) {
 // The same products for three vectors in one pass over the slots (the solver set-up: warm start, qacc_smooth, qvel): a
 // slot's Jb words and dof indices are loaded once, the vectors are taken in turn against that one set of jv[16], and each
 // keeps contact_Jx's a0..a3 grouping, so every cp word carries the bits the single pass gives.  cp0..cp2 are offsets in c.sm.
-template <class C>
+template <int NS = 16, class C>   // NS == 8: the tree path, as in contact_Jx
 __device__ __forceinline__ void contact_Jx3(C& c, const double* x0, const double* x1, const double* x2, int cp0, int cp1, int cp2) {
   for (int idx = c.lane; idx < 3 * c.ncon; idx += WAVE) {
     int ci = idx / 3, a = idx - 3 * ci;
-    const int info = (c.si + c.L.con_b)[4 * ci + 3], ns = (info >> 20) ? 16 : 8;
-    const double* Jb = S(Jb) + (info & 0xFFFFF) + ns * a;
     const signed char* di = (const signed char*)c.sb + c.L.b_dofidx + 16 * ci;
-    double jv[16];
-    int dv[16];
+    double jv[NS];
+    int dv[NS];
+    if constexpr (NS == 8) {
+      const double* Jb = S(Jb) + 24 * ci + 8 * a;
 #pragma unroll
-    for (int s = 0; s < 16; s++) { int d = di[s]; dv[s] = d < 0 ? 0 : d; double jq = Jb[s]; jv[s] = s < ns ? jq : 0.0; }
+      for (int s = 0; s < 8; s++) { int d = di[s]; dv[s] = d < 0 ? 0 : d; jv[s] = Jb[s]; }
+    } else {
+      const int info = (c.si + c.L.con_b)[4 * ci + 3], ns = (info >> 20) ? 16 : 8;
+      const double* Jb = S(Jb) + (info & 0xFFFFF) + ns * a;
+#pragma unroll
+      for (int s = 0; s < 16; s++) { int d = di[s]; dv[s] = d < 0 ? 0 : d; double jq = Jb[s]; jv[s] = s < ns ? jq : 0.0; }
+    }
 #pragma unroll
     for (int v = 0; v < 3; v++) {
       const double* x = v == 0 ? x0 : (v == 1 ? x1 : x2);
-      double xv[16];
+      double xv[NS];
 #pragma unroll
-      for (int s = 0; s < 16; s++) xv[s] = x[dv[s]];
+      for (int s = 0; s < NS; s++) xv[s] = x[dv[s]];
       double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
 #pragma unroll
-      for (int s = 0; s < 16; s += 4) { a0 += jv[s] * xv[s]; a1 += jv[s + 1] * xv[s + 1]; a2 += jv[s + 2] * xv[s + 2]; a3 += jv[s + 3] * xv[s + 3]; }
+      for (int s = 0; s < NS; s += 4) { a0 += jv[s] * xv[s]; a1 += jv[s + 1] * xv[s + 1]; a2 += jv[s + 2] * xv[s + 2]; a3 += jv[s + 3] * xv[s + 3]; }
       c.sm[(v == 0 ? cp0 : (v == 1 ? cp1 : cp2)) + idx] = (a0 + a1) + (a2 + a3);
     }
   }
@@ -1541,10 +1568,7 @@ __device__ __forceinline__ double ldl_solve_rows(C& c, const double* A, double* 
 // needed word per lane and factorised redundantly by every lane of the agent.  No fill-in, five short phases.
 #define DPP_SWAP_PAIR 0xB1  /* quad_perm [1,0,3,2]: exchange with the neighbouring lane (hip <-> ankle; hips sit on even lanes) */
 __device__ __forceinline__ double pair_swap_f64(double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_update_dpp(0, lo, DPP_SWAP_PAIR, 0xF, 0xF, false);
-  hi = __builtin_amdgcn_update_dpp(0, hi, DPP_SWAP_PAIR, 0xF, 0xF, false);
-  return __hiloint2double(hi, lo);
+  return dpp_mov_f64<DPP_SWAP_PAIR>(v);   // every lane has a source
 }
 
 // row <- tree row `lane` of M + diag_add on the diagonal (+ J^T W J of the contacts touching this dof)
@@ -1563,7 +1587,7 @@ __device__ __forceinline__ void tree_rows(C& c, double (&row)[8], double diag_ad
   if (with_contacts && lane < nv) {
     for (unsigned long long mk = ((const unsigned long long*)S(cmask))[lane]; mk; mk &= mk - 1) {
       const int ci = __builtin_ctzll(mk);
-      const double* Jb = S(Jb) + ((c.si + c.L.con_b)[4 * ci + 3] & 0xFFFFF);   // one moving body: 3 rows x 8 chain slots
+      const double* Jb = S(Jb) + 24 * ci;   // one moving body per contact: 3 rows x 8 chain slots, the pool offset is 24 ci (make_constraint)
       const double* W = S(cW) + 5 * ci;
       const double a0 = Jb[pos], a1 = Jb[8 + pos], a2 = Jb[16 + pos];
       const double u0 = W[0] * a0 + W[1] * a1 + W[2] * a2, u1 = W[1] * a0 + W[3] * a1, u2 = W[2] * a0 + W[4] * a2;
@@ -1731,7 +1755,7 @@ __device__ __forceinline__ void newton_solve(C& c) {
   // one pass over the contact Jacobians for J x, J qacc_smooth and J qvel (efc_vel).  The two extra cp buffers: cW (5 maxcon words,
   // first written by the iterations below) and the head of the Hessian region (>= 6 + 10 nbody + 6 nv >= 3 maxcon words in every
   // layout; dead between the qacc_smooth solve and the first factorisation).
-  contact_Jx3(c, x, S(asmo), S(qvel), c.L.cp, c.L.cW, c.L.H);
+  contact_Jx3<TREE ? 8 : 16>(c, x, S(asmo), S(qvel), c.L.cp, c.L.cW, c.L.H);
   for (int r = lane; r < nrow; r += WAVE) {
     const double a = -S(aref)[r] * row_Jx_at(c, c.L.H, r) - S(jar)[r];   // aref = -B efc_vel - K imp (pos - margin): make_constraint parked B in aref, the K term in jar
     S(aref)[r] = a;
@@ -1805,20 +1829,32 @@ __device__ __forceinline__ void newton_solve(C& c) {
       const double j0 = xi - lq.A0, j1 = -xi - lq.A1;
       if (j0 < 0) { qc -= lq.D0 * j0; dl += lq.D0; }   // force -D jar through the row +e_dof
       if (j1 < 0) { qc += lq.D1 * j1; dl += lq.D1; }   // row -e_dof
-      for (unsigned long long mk = ((const unsigned long long*)S(cmask))[lane]; mk; mk &= mk - 1) {
-        int ci = __builtin_ctzll(mk);
-        const int s = SLOT_OF(ci, lane, role_d_pos(c));
-        const int info = (c.si + c.L.con_b)[4 * ci + 3], ns = (info >> 20) ? 16 : 8;
-        const double* Jb = S(Jb) + (info & 0xFFFFF);
-        const double* cp = S(cp) + 3 * ci;
-        qc += Jb[s] * cp[0] + Jb[ns + s] * cp[1] + Jb[2 * ns + s] * cp[2];
+      if constexpr (TREE) {
+        // one moving body per contact: its block is 3 x 8 at 24 ci (make_constraint) and this dof's slot is its chain position -- no
+        // slot byte, no info word, no branch
+        const double* Js = S(Jb) + role_d_pos(c);
+        for (unsigned long long mk = ((const unsigned long long*)S(cmask))[lane]; mk; mk &= mk - 1) {
+          const int ci = __builtin_ctzll(mk);
+          const double* Jb = Js + 24 * ci;
+          const double* cp = S(cp) + 3 * ci;
+          qc += Jb[0] * cp[0] + Jb[8] * cp[1] + Jb[16] * cp[2];
+        }
+      } else {
+        for (unsigned long long mk = ((const unsigned long long*)S(cmask))[lane]; mk; mk &= mk - 1) {
+          int ci = __builtin_ctzll(mk);
+          const int s = SLOT_OF(ci, lane, role_d_pos(c));
+          const int info = (c.si + c.L.con_b)[4 * ci + 3], ns = (info >> 20) ? 16 : 8;
+          const double* Jb = S(Jb) + (info & 0xFFFFF);
+          const double* cp = S(cp) + 3 * ci;
+          qc += Jb[s] * cp[0] + Jb[ns + s] * cp[1] + Jb[2 * ns + s] * cp[2];
+        }
       }
       g = Ma - qsm_i - qc;
       if (!TREE) S(dlim)[lane] = dl;
     }
     double gn = wave_sum(g * g);
     PROF(12);
-    if (scale * sqrt(gn) < tol) break;
+    if (gn <= c.P->grad_thresh) break;   // scale * sqrt(gn) < tol  <=>  gn <= grad_thresh (grad_threshold on the host: the last double that passes)
     SYNC();
     // ---- Hessian H = M + J^T diag(D_active) J, lower triangle: entry-major gather (every lane a few entries).
     // All loads of the mass-matrix / mask words are issued before any store so they pipeline.
@@ -1884,7 +1920,7 @@ __device__ __forceinline__ void newton_solve(C& c) {
     PROF(14);
     // ---- exact line search
     double Mv = dense_Mx(c, S(search));
-    contact_Jx(c, S(search));
+    contact_Jx<TREE ? 8 : 16>(c, S(search));
     // each lane keeps its contact rows (r = lane + 64 q) and its dof's two limit rows (jar, Jv, D) in registers
     double rj[RPL + 2], rjv[RPL + 2], rD[RPL + 2];
 #pragma unroll
@@ -2262,14 +2298,11 @@ __device__ __forceinline__ unsigned rec_hash(double v, int i) {
   const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
   return (lo ^ (hi * 0x9E3779B1u)) * 0x85EBCA77u + (unsigned)(i + 1) * 0xC2B2AE3Du;
 }
-__device__ __forceinline__ unsigned wave_usum(unsigned v) {
+__device__ __forceinline__ unsigned wave_usum(unsigned v) {   // wave_sum's stages on an integer; only lane 63 is read
   int x = (int)v;
-  x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xF, 0xF, false);
-  x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xF, 0xF, false);
-  x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xF, 0xF, false);
-  x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xF, 0xF, false);
-  x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xA, 0xF, false);
-  x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xC, 0xF, false);
+#define WAVE_SUM_STAGE(CTRL) x += __builtin_amdgcn_update_dpp(0, x, CTRL, 0xF, 0xF, true);
+  WAVE_SUM_STAGES(WAVE_SUM_STAGE)
+#undef WAVE_SUM_STAGE
   return (unsigned)__builtin_amdgcn_readlane(x, 63);
 }
 template <bool COH = false, class C, class SA>   // SA: StepArgs by value (per-step kernel) or in the kernel-argument segment (rollout kernel)
@@ -3781,6 +3814,7 @@ struct Scene {
   std::vector<LaneRec> lanes;
   std::vector<int> pair_rec;
   std::vector<float> pair_bound;
+  double grad_thresh = -1.0;               // Params::grad_thresh
   int static_layout = 0;                   // 1 / 2: the scene's Layout equals a compile-time table (Ant-vs-Ant / Spider-vs-Spider): static kernel variants
   int state_stride = 0, obs_stride = 0, act_stride = 0;
 };
@@ -4445,6 +4479,23 @@ static int finish_scene(Scene& S, const SceneOptions& opt) {
   return 0;
 }
 
+// The Newton loop's gradient test D(gn) = (scale * sqrt(gn) < tol) as a threshold on gn, the squared gradient norm: with a correctly
+// rounded sqrt and scale >= 0, D is non-increasing over gn >= 0, so D(gn) == (gn <= G) for G the largest double with D(G) true (-1 where
+// there is none; gn is a sum of squares, never below +0).  NaN and +inf fail both forms.  Found by bisection over the bit patterns of the
+// non-negative finite doubles, which are ordered like their values.
+static double grad_threshold(double scale, double tol) {
+  auto D = [&](uint64_t bits) { double g; memcpy(&g, &bits, sizeof g); volatile double s = sqrt(g); volatile double p = scale * s; return p < tol; };
+  uint64_t lo = 0, hi = 0x7FEFFFFFFFFFFFFFull;   // +0 .. DBL_MAX
+  if (!D(lo)) return -1.0;
+  while (lo < hi) {   // invariant: D(lo) true
+    const uint64_t mid = lo + (hi - lo + 1) / 2;
+    if (D(mid)) lo = mid; else hi = mid - 1;
+  }
+  double g; memcpy(&g, &lo, sizeof g);
+  return g;
+}
+static double newton_scale(const sumo_model_t* m) { return 1.0 / (SUMO_F(m, opt)[SUMO_OPT_MEANINERTIA] * (m->nv > 1 ? m->nv : 1)); }   // newton_solve's `scale`
+
 // The one preparation of a scene from a model blob, in stages; a caller stops after the stage it needs, and a scene that fails a
 // later stage still answers for the earlier ones.  Host only.
 enum SceneStage { SCENE_AUX, SCENE_LAYOUT, SCENE_ROLES, SCENE_CHECKED };
@@ -4453,6 +4504,7 @@ static int prepare_scene(Scene& S, const void* blob, size_t nbytes, SceneStage u
   S.blob.assign((const char*)blob, (const char*)blob + nbytes);
   if (int rc = sumo_model_parse(&S.hm, S.blob.data(), nbytes)) FAIL(-4, "malformed model blob (%d)", rc);
   if (int rc = build_aux(S, opt)) return rc;             // aux tables, lane records, pair records
+  S.grad_thresh = grad_threshold(newton_scale(&S.hm), SUMO_F(&S.hm, opt)[SUMO_OPT_TOLERANCE]);
   if (upto == SCENE_AUX) return 0;
   build_layout(S, opt);
   if (upto == SCENE_LAYOUT) return 0;
@@ -4511,6 +4563,7 @@ extern "C" int sumo_create(const void* model_blob, size_t nbytes, int num_envs, 
     hp.L = E->L;
     hp.lanes = E->d_lanes; hp.pair_rec = E->d_pair_rec; hp.pair_bound = E->d_pair_bound;
     hp.adjust_z = 0.0;
+    hp.grad_thresh = E->grad_thresh;
     HIPCHK(E->d_params.alloc(1));
     HIPCHK(hipMemcpy(E->d_params, &hp, sizeof(Params), hipMemcpyHostToDevice));
   }
@@ -5338,6 +5391,65 @@ extern "C" int sumo_debug_forward(sumo_handle_t E, const double* ctrl, double* q
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy(qacc, d_qacc, N * m->nv * sizeof(double), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(counts, d_cnt, N * 4 * sizeof(int), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// One wave through the in-wave primitives of the kernels above, on caller-given lanes (sumo_debug_wave_ops).
+struct WaveOpsArgs {
+  const double* in;   // [8][64]
+  const int* iin;     // [64]
+  double* sums;       // [20]: wave_sum of rows 0 .. 7, wave_sum2 of rows 0 .. 1, wave_sum4 of rows 0 .. 3, wave_sum_n<6> of rows 0 .. 5
+  double* swapped;    // [64]: pair_swap_f64 of row 0
+  int* scan;          // [65]: wave_excl_scan of iin, then its total
+  const double* gn;   // [ngn]
+  unsigned char* grad;   // [ngn][2]: the gradient test on gn[i], sqrt form and threshold form
+  int ngn;
+  double scale, tol, thresh;
+};
+__global__ void __launch_bounds__(WAVE) sumo_wave_ops_kernel(WaveOpsArgs a) {
+  const int lane = threadIdx.x;
+  double r[8];
+  for (int k = 0; k < 8; k++) r[k] = a.in[WAVE * k + lane];
+  for (int k = 0; k < 8; k++) { const double s = wave_sum(r[k]); if (lane == 0) a.sums[k] = s; }
+  { double p = r[0], q = r[1]; wave_sum2(p, q); if (lane == 0) { a.sums[8] = p; a.sums[9] = q; } }
+  { double p = r[0], q = r[1], u = r[2], v = r[3]; wave_sum4(p, q, u, v); if (lane == 0) { a.sums[10] = p; a.sums[11] = q; a.sums[12] = u; a.sums[13] = v; } }
+  { double v[6] = {r[0], r[1], r[2], r[3], r[4], r[5]}; wave_sum_n(v); if (lane == 0) for (int k = 0; k < 6; k++) a.sums[14 + k] = v[k]; }
+  a.swapped[lane] = pair_swap_f64(r[0]);
+  int tot;
+  a.scan[lane] = wave_excl_scan(a.iin[lane], lane, &tot);
+  if (lane == 0) a.scan[WAVE] = tot;
+  for (int i = lane; i < a.ngn; i += WAVE) {
+    const double gn = a.gn[i];
+    a.grad[2 * i] = a.scale * sqrt(gn) < a.tol;
+    a.grad[2 * i + 1] = gn <= a.thresh;
+  }
+}
+extern "C" int sumo_debug_grad_threshold(double scale, double tol, double* out) {   // host only
+  if (!out) FAIL(-1, "bad arguments");
+  *out = grad_threshold(scale, tol);
+  return 0;
+}
+extern "C" int sumo_debug_wave_ops(sumo_handle_t E, const double* in64x8, const int32_t* int_in64, double* sums20, double* swapped64,
+                                   int32_t* scan65, const double* gn, int ngn, double scale, double tol, uint8_t* grad_out) {
+  if (!E || !in64x8 || !int_in64 || !sums20 || !swapped64 || !scan65 || ngn < 0 || (ngn && (!gn || !grad_out))) FAIL(-1, "bad arguments");
+  HIPCHK(hipSetDevice(E->device));
+  DevBuf<double> d_in, d_sums, d_swapped, d_gn;
+  DevBuf<int> d_iin, d_scan;
+  DevBuf<unsigned char> d_grad;
+  const size_t ng = ngn ? (size_t)ngn : 1;
+  HIPCHK(d_in.alloc(8 * WAVE)); HIPCHK(d_sums.alloc(20)); HIPCHK(d_swapped.alloc(WAVE)); HIPCHK(d_gn.alloc(ng));
+  HIPCHK(d_iin.alloc(WAVE)); HIPCHK(d_scan.alloc(WAVE + 1)); HIPCHK(d_grad.alloc(2 * ng));
+  HIPCHK(hipMemcpy(d_in, in64x8, 8 * WAVE * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d_iin, int_in64, WAVE * sizeof(int), hipMemcpyHostToDevice));
+  if (ngn) HIPCHK(hipMemcpy(d_gn, gn, ng * sizeof(double), hipMemcpyHostToDevice));
+  WaveOpsArgs a{d_in, d_iin, d_sums, d_swapped, d_scan, d_gn, d_grad, ngn, scale, tol, grad_threshold(scale, tol)};
+  hipLaunchKernelGGL(sumo_wave_ops_kernel, dim3(1), dim3(WAVE), 0, (hipStream_t)0, a);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(sums20, d_sums, 20 * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(swapped64, d_swapped, WAVE * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(scan65, d_scan, (WAVE + 1) * sizeof(int), hipMemcpyDeviceToHost));
+  if (ngn) HIPCHK(hipMemcpy(grad_out, d_grad, 2 * ng * sizeof(unsigned char), hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -19,6 +19,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <memory>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -3745,1731 +3746,9 @@ SUMO_RK_ALL(, 44, 0)
 #endif
 #endif
 
-#ifndef SUMO_ROLLOUT_SHARD   // to the end of the file: the other kernels and the host side
-template <int NV>
-__global__ void __launch_bounds__(WAVE) sumo_reset_kernel(const Params* P, StepArgs a) {
-  Ctx<NV> c;
-  ctx_init(c, P, smem_dyn);
-  const sumo_model_t& mdl = P->mdl;
-  const int e = blockIdx.x, lane = c.lane;
-  if (e >= a.N) return;
-  if (a.mask && !a.mask[e]) return;
-  int* cnt = a.counters + 4 * e;
-  int reset_count = cnt[1];
-  reset_state(c, a.seeds[e], (uint32_t)reset_count);
-  if (a.obs) write_obs(c, a.obs + (size_t)e * 2 * a.obs_stride, a.obs_stride, 0);
-  store_state(c, a, e);
-  if (lane == 0) {
-    double* st = a.state + (size_t)e * a.state_stride;
-    cnt[0] = 0; cnt[1] = reset_count + 1;
-    st[mdl.nq + 2 * mdl.nv] = 0; st[mdl.nq + 2 * mdl.nv + 1] = 0;
-  }
-}
-
-template <int NV>
-__global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(SUMO_WPE_OF(NV), SUMO_WPE_OF(NV)))) sumo_forward_kernel(const Params* P, StepArgs a) {
-  Ctx<NV> c;
-  ctx_init(c, P, smem_dyn);
-  const sumo_model_t& mdl = P->mdl;
-  const int e = blockIdx.x, lane = c.lane;
-  if (e >= a.N) return;
-  load_state(c, a, e);
-  if (lane < mdl.nu) S(ctrl)[lane] = a.dbg_ctrl[(size_t)e * mdl.nu + lane];
-  SYNC();
-  forward(c);
-  if (lane < mdl.nv) a.dbg_qacc[(size_t)e * mdl.nv + lane] = S(x)[lane];
-  if (lane == 0) {
-    int* o = a.dbg_counts + 4 * e;
-    o[0] = c.ncon; o[1] = c.nefc; o[2] = c.st_newton; o[3] = c.ndropped;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// host side
-// ---------------------------------------------------------------------------------------------------------
-#ifdef SUMO_DEV_NV  /* development builds: compile a single kernel variant */
-#define SUMO_FOR_NV(X) X(SUMO_DEV_NV)
-#else
-#define SUMO_FOR_NV(X) X(28) X(32) X(36) X(40) X(44)
-#endif
-#include <memory>
-static thread_local char g_err[512];
-extern "C" const char* sumo_last_error(void) { return g_err; }
-#define FAIL(code, ...) do { snprintf(g_err, sizeof g_err, __VA_ARGS__); return code; } while (0)
-#define HIPCHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) FAIL(-100, "%s failed: %s", #expr, hipGetErrorString(_e)); } while (0)
-
-// Everything the host derives from a model blob, with one owner.  prepare_scene fills it stage by stage; it makes no HIP call (the
-// host-only exports run where there is no device), and it is not copyable: hm points into blob.
-struct Scene {
-  Scene() = default;
-  Scene(const Scene&) = delete;
-  Scene& operator=(const Scene&) = delete;
-  std::vector<char> blob;
-  sumo_model_t hm{};                       // host view of blob
-  Aux aux{};                               // its table pointers stay null here: sumo_create points the device copy at the uploads
-  Layout L{};
-  std::vector<int> ai;                     // the tables behind aux.ai / aux.af / aux.pic
-  std::vector<double> af;
-  std::vector<signed char> pic;
-  std::vector<LaneRec> lanes;
-  std::vector<int> pair_rec;
-  std::vector<float> pair_bound;
-  double grad_thresh = -1.0;               // Params::grad_thresh
-  int static_layout = 0;                   // 1 / 2: the scene's Layout equals a compile-time table (Ant-vs-Ant / Spider-vs-Spider): static kernel variants
-  int state_stride = 0, obs_stride = 0, act_stride = 0;
-};
-
-// What the environment says about a scene preparation, read once per preparation.
-struct SceneOptions {
-  bool true_tree;      // SUMO_TRUE_TREE != 0: the model's own body tree instead of the effective one
-  int maxcon;          // SUMO_MAXCON > 0: contact records (still capped by what the line search holds in registers)
-  int warm_mode;       // SUMO_WARM_MODE (Layout::warm_mode)
-  int force_dense;     // SUMO_FORCE_DENSE_H (Layout::force_dense)
-  bool no_tree;        // SUMO_NO_TREE != 0: never the tree solver
-  bool jbcap_set;      // SUMO_JBCAP present, whatever its value: the Jacobian pool does not grow into the spare LDS
-  int jbcap;           // SUMO_JBCAP > 0: the pool's capacity
-  bool static_layout;  // unless SUMO_STATIC_LAYOUT is 0: the static kernel variants where the scene matches a compile-time table
-  static SceneOptions from_env() {
-    auto num = [](const char* name) { const char* v = getenv(name); return v ? atoi(v) : 0; };
-    const char* sl = getenv("SUMO_STATIC_LAYOUT");
-    return {num("SUMO_TRUE_TREE") != 0, num("SUMO_MAXCON"), num("SUMO_WARM_MODE"), num("SUMO_FORCE_DENSE_H"), num("SUMO_NO_TREE") != 0,
-            getenv("SUMO_JBCAP") != nullptr, num("SUMO_JBCAP"), !(sl && atoi(sl) == 0)};
-  }
-};
-
-// Device memory that is freed with its holder.  Reads like the raw pointer it replaces; templates that deduce a pointer type take get().
-template <class T>
-struct DevBuf {
-  struct Free { void operator()(T* p) const { (void)hipFree(p); } };
-  std::unique_ptr<T, Free> p;
-  T* get() const { return p.get(); }
-  operator T*() const { return p.get(); }
-  hipError_t alloc(size_t n) {
-    void* q = nullptr;
-    const hipError_t e = hipMalloc(&q, n * sizeof(T));
-    if (e == hipSuccess) p.reset((T*)q);
-    return e;
-  }
-  hipError_t upload(const std::vector<T>& h) {
-    const hipError_t e = alloc(h.size());
-    return e != hipSuccess ? e : hipMemcpy(p.get(), h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
-  }
-};
-
-struct sumo_engine : Scene {   // a prepared scene and the device state of its N envs
-  int device = 0, N = 0;
-  DevBuf<Params> d_params;
-  DevBuf<LaneRec> d_lanes;
-  DevBuf<int> d_pair_rec;
-  DevBuf<float> d_pair_bound;
-  DevBuf<char> d_blob;
-  DevBuf<int> d_ai;
-  DevBuf<double> d_af;
-  DevBuf<signed char> d_pic;
-  DevBuf<double> d_state;
-  int cfrc_mode = 0;                       // 0 zero (reference behaviour), 1 rne_post (sumo_set_cfrc_mode)
-  double adjust_z = 0.0;                   // Agent._adjust_z (sumo_set_adjust_z)
-  DevBuf<double> d_state_prev, d_fbuf, d_cfrc;   // rne_post: pre-step state, row-force scratch, cfrc_ext [N][nbody][6] (sumo_set_cfrc_mode allocates them)
-  DevBuf<int> d_counters;
-  DevBuf<uint64_t> d_seeds;
-  DevBuf<unsigned long long> d_stats;
-  // longest-first scheduling of the env steps (see sumo_step)
-  DevBuf<int> d_cost, d_cost_sorted, d_iota, d_perm;   // d_cost / d_perm: two buffers of N each
-  unsigned long long* d_trace = nullptr;   // sumo_debug_trace: the caller's buffer, not owned
-  int num_cus = 0;                         // cached device property (sumo_rollout_steps sizes its persistent grid with it)
-  DevBuf<int> d_rsched;                    // sumo_rollout_steps: ticket counter, abort flag, per-env progress [2 + N] (allocated by the first fused launch)
-  unsigned rollout_seq = 0;                // fused launches so far (hand-over tags: seq_base = (rollout_seq & 0x7FFF) << 16)
-  hipStream_t rollout_stream = nullptr;    // stream of the most recent fused launch (sumo_rollout_status waits on it)
-  long long rollout_tickets = -1;          // N * K of the most recent fused launch, -1: none yet
-  int dbg_fault_env = -1;                  // sumo_debug_fault
-  double* dbg_dump = nullptr;              // sumo_debug_dump (SUMO_DBG_DUMP builds): the caller's buffer, not owned
-  unsigned long long acked_faults = 0;     // stats[9] + stats[10] already reported by sumo_rollout_status
-  long long sched_t = 0;                                                                     // step launches so far (in-kernel ranking)
-  DevBuf<char> d_sort_tmp;
-  size_t sort_tmp_bytes = 0;
-  bool sched = true, perm_valid = false;
-};
-
-static void quat2mat_h(double* m, const double* q) {
-  double w = q[0], x = q[1], y = q[2], z = q[3];
-  m[0] = w * w + x * x - y * y - z * z; m[1] = 2 * (x * y - w * z); m[2] = 2 * (x * z + w * y);
-  m[3] = 2 * (x * y + w * z); m[4] = w * w - x * x + y * y - z * z; m[5] = 2 * (y * z - w * x);
-  m[6] = 2 * (x * z - w * y); m[7] = 2 * (y * z + w * x); m[8] = w * w - x * x - y * y + z * z;
-}
-
-// build_aux: the derived tables (S.ai / af / pic, the Aux offsets into them), the lane records and the pair records of a parsed
-// scene.  Its pieces run in the order they are declared in; the members are what one piece leaves for the later ones.
-namespace {
-struct AuxBuilder {
-  Scene& S;
-  const SceneOptions& opt;
-  const sumo_model_t* const m = &S.hm;
-  const int nb = m->nbody, nv = m->nv;
-  Aux& A = S.aux;
-  std::vector<int>& ai = S.ai;
-  std::vector<double>& af = S.af;
-  std::vector<signed char>& pic = S.pic;
-  const int* const tparent = SUMO_I(m, body_parentid);
-  const int* const gbody = SUMO_I(m, geom_bodyid);
-  const int* const gtype = SUMO_I(m, geom_type);
-  const int* parent = nullptr;   // tparent, or eparent: the tree the kernels walk
-  bool folded = false;           // parent is the effective tree
-  std::vector<int> eparent, depth, lvl_adr, lvl_body, is_stub, child_adr, child;
-  std::vector<double> epos, equat;
-  std::vector<int> chain_len, chain, bchain_len, bchain, body_agent, tri_i, tri_j, cen_of_geom;
-  int push_tbl(const std::vector<int>& v) { int o = (int)ai.size(); ai.insert(ai.end(), v.begin(), v.end()); return o; }
-  void effective_tree();
-  int chains_and_checks();
-  int collision_tables();
-  int lane_records();
-  void hessian_entries();
-  int pair_records();
-};
-}  // namespace
-
-static int build_aux(Scene& S, const SceneOptions& opt) {
-  const sumo_model_t* m = &S.hm;
-  int nb = m->nbody, nv = m->nv;
-  if (nb > WAVE || nv > WAVE || m->njnt > WAVE || m->nq > WAVE) FAIL(-10, "scene too large for one wavefront per env (nbody %d nv %d)", nb, nv);
-  if (m->nagent != 2) FAIL(-11, "exactly two agents expected");
-  if (nv != 28 && nv != 32 && nv != 36 && nv != 40 && nv != 44) FAIL(-18, "no kernel variant for nv=%d", nv);
-  AuxBuilder B{S, opt};
-  B.effective_tree();
-  if (int rc = B.chains_and_checks()) return rc;
-  if (int rc = B.collision_tables()) return rc;
-  if (int rc = B.lane_records()) return rc;
-  B.hessian_entries();
-  return B.pair_records();
-}
-
-void AuxBuilder::effective_tree() {
-  // "Effective" tree of the kernel's level-by-level passes: a body whose parent carries no joint is re-attached to the nearest
-  // ancestor that does, with the static transforms composed (the jointless body keeps its own frame as a leaf: its frame
-  // still feeds its geom and inertia, and subtree sums do not care which rigidly connected ancestor collects it).  For the
-  // RoboSumo agents (torso -> jointless leg stub -> hip body -> ankle body) this removes one level from every pass.
-  eparent.assign(nb, 0);
-  epos.assign(3 * (size_t)nb, 0.0); equat.assign(4 * (size_t)nb, 0.0);
-  for (int b = 0; b < nb; b++) {
-    double pos[3] = {SUMO_F(m, body_pos)[3 * b], SUMO_F(m, body_pos)[3 * b + 1], SUMO_F(m, body_pos)[3 * b + 2]};
-    double q[4] = {SUMO_F(m, body_quat)[4 * b], SUMO_F(m, body_quat)[4 * b + 1], SUMO_F(m, body_quat)[4 * b + 2], SUMO_F(m, body_quat)[4 * b + 3]};
-    int pp = b ? tparent[b] : 0;
-    while (pp != 0 && SUMO_I(m, body_jntnum)[pp] == 0) {
-      const double* pq = SUMO_F(m, body_quat) + 4 * pp;
-      const double* ppos = SUMO_F(m, body_pos) + 3 * pp;
-      double R[9];
-      quat2mat_h(R, pq);
-      double np_[3] = {ppos[0] + R[0] * pos[0] + R[1] * pos[1] + R[2] * pos[2], ppos[1] + R[3] * pos[0] + R[4] * pos[1] + R[5] * pos[2],
-                       ppos[2] + R[6] * pos[0] + R[7] * pos[1] + R[8] * pos[2]};
-      double nq[4] = {pq[0] * q[0] - pq[1] * q[1] - pq[2] * q[2] - pq[3] * q[3], pq[0] * q[1] + pq[1] * q[0] + pq[2] * q[3] - pq[3] * q[2],
-                      pq[0] * q[2] - pq[1] * q[3] + pq[2] * q[0] + pq[3] * q[1], pq[0] * q[3] + pq[1] * q[2] - pq[2] * q[1] + pq[3] * q[0]};
-      double nn = sqrt(nq[0] * nq[0] + nq[1] * nq[1] + nq[2] * nq[2] + nq[3] * nq[3]);
-      for (int k = 0; k < 3; k++) pos[k] = np_[k];
-      for (int k = 0; k < 4; k++) q[k] = nq[k] / nn;
-      pp = tparent[pp];
-    }
-    eparent[b] = pp;
-    for (int k = 0; k < 3; k++) epos[3 * b + k] = pos[k];
-    for (int k = 0; k < 4; k++) equat[4 * b + k] = q[k];
-  }
-  parent = opt.true_tree ? tparent : eparent.data();
-  folded = parent != tparent;
-  depth.assign(nb, 0);
-  int ndepth = 1;
-  for (int b = 1; b < nb; b++) { depth[b] = depth[parent[b]] + 1; if (depth[b] + 1 > ndepth) ndepth = depth[b] + 1; }
-  A.ndepth = ndepth;
-  lvl_adr.assign(ndepth + 1, 0);
-  for (int d = 0; d < ndepth; d++) { lvl_adr[d] = (int)lvl_body.size(); for (int b = 0; b < nb; b++) if (depth[b] == d) lvl_body.push_back(b); }
-  lvl_adr[ndepth] = (int)lvl_body.size();
-  // jointless leaves of the effective tree ("stubs", e.g. the fixed upper leg segments): rigidly attached to their parent, so
-  // their inertia is added to the parent's once per evaluation and they take no part in the subtree gathers
-  is_stub.assign(nb, 0);
-  if (folded)
-    for (int b = 1; b < nb; b++) {
-      if (SUMO_I(m, body_jntnum)[b] != 0 || parent[b] == 0) continue;
-      bool leaf = true;
-      for (int ch = 1; ch < nb; ch++) if (ch != b && parent[ch] == b) leaf = false;
-      is_stub[b] = leaf;
-    }
-  child_adr.assign(nb + 1, 0);
-  for (int b = 0; b < nb; b++) {
-    child_adr[b] = (int)child.size();
-    for (int ch = nb - 1; ch > b; ch--) if (parent[ch] == b && b != 0 && !is_stub[ch]) child.push_back(ch);
-  }
-  child_adr[nb] = (int)child.size();
-}
-
-// dof and body chains root -> body, the checks of what the kernels assume about a body, and the integer tables
-int AuxBuilder::chains_and_checks() {
-  chain_len.assign(nb, 0); chain.assign(nb * MAXCHAIN, -1); bchain_len.assign(nb, 0); bchain.assign(nb * MAXBCHAIN, -1); body_agent.assign(nb, -1);
-  pic.assign((size_t)nb * nv, -1);
-  const int* dofnum = SUMO_I(m, body_dofnum);
-  const int* dofadr = SUMO_I(m, body_dofadr);
-  const int* dpar = SUMO_I(m, dof_parentid);
-  for (int b = 1; b < nb; b++) {
-    std::vector<int> bc;
-    for (int k = b; k != 0; k = parent[k]) bc.insert(bc.begin(), k);
-    if ((int)bc.size() > MAXBCHAIN) FAIL(-12, "kinematic tree deeper than %d bodies", MAXBCHAIN);
-    bchain_len[b] = (int)bc.size();
-    for (size_t i = 0; i < bc.size(); i++) bchain[b * MAXBCHAIN + i] = bc[i];
-    int bb = b;
-    while (bb && dofnum[bb] == 0) bb = tparent[bb];
-    std::vector<int> dc;
-    if (bb) for (int d = dofadr[bb] + dofnum[bb] - 1; d >= 0; d = dpar[d]) dc.insert(dc.begin(), d);
-    if ((int)dc.size() > MAXCHAIN) FAIL(-13, "dof chain longer than %d", MAXCHAIN);
-    chain_len[b] = (int)dc.size();
-    for (size_t i = 0; i < dc.size(); i++) { chain[b * MAXCHAIN + i] = dc[i]; pic[(size_t)b * nv + dc[i]] = (signed char)i; }
-    for (int a = 0; a < m->nagent; a++) {
-      int adr = SUMO_I(m, agent_bodyadr)[a];
-      if (b >= adr && b < adr + SUMO_I(m, agent_nbody)[a]) body_agent[b] = a;
-    }
-    if (body_agent[b] < 0) FAIL(-14, "body %d belongs to no agent", b);
-    // one geom per moving body, and its frame is the inertial frame (what the kernel assumes)
-    int g0 = SUMO_I(m, body_geomadr)[b], g1 = SUMO_I(m, body_geomadr)[b + 1];
-    if (g1 - g0 != 1) FAIL(-15, "body %d has %d geoms; the engine needs exactly one per moving body", b, g1 - g0);
-    for (int k = 0; k < 3; k++) if (SUMO_F(m, geom_pos)[3 * g0 + k] != SUMO_F(m, body_ipos)[3 * b + k]) FAIL(-16, "geom/inertial frame mismatch");
-    for (int k = 0; k < 4; k++) if (SUMO_F(m, geom_quat)[4 * g0 + k] != SUMO_F(m, body_iquat)[4 * b + k]) FAIL(-16, "geom/inertial frame mismatch");
-  }
-  // one actuator per dof at most (kernel adds actuator forces without atomics)
-  {
-    std::vector<int> seen(nv, 0);
-    for (int u = 0; u < m->nu; u++) { int d = SUMO_I(m, actuator_dofid)[u]; if (seen[d]++) FAIL(-17, "two actuators on one dof"); }
-  }
-  for (int i = 0; i < nv; i++) for (int j = 0; j <= i; j++) { tri_i.push_back(i); tri_j.push_back(j); }
-  A.ntri = (int)tri_i.size();
-  A.o_lvl_adr = push_tbl(lvl_adr); A.o_lvl_body = push_tbl(lvl_body); A.o_child_adr = push_tbl(child_adr);
-  A.o_child = push_tbl(child.empty() ? std::vector<int>(1, 0) : child);
-  A.o_chain_len = push_tbl(chain_len); A.o_chain = push_tbl(chain); A.o_bchain_len = push_tbl(bchain_len);
-  A.o_bchain = push_tbl(bchain); A.o_body_agent = push_tbl(body_agent); A.o_tri_i = push_tbl(tri_i); A.o_tri_j = push_tbl(tri_j);
-  A.o_wgmat = 0;
-  af.assign((size_t)9 * m->ngeom, 0.0);
-  for (int g = 0; g < m->ngeom; g++) quat2mat_h(&af[9 * g], SUMO_F(m, geom_quat) + 4 * g);
-  return 0;
-}
-
-// collision centres (body ids for agent geoms, nbody + w for world geom w) and the static tables the collision code reads by centre
-int AuxBuilder::collision_tables() {
-  int nworld = SUMO_I(m, body_geomadr)[1] - SUMO_I(m, body_geomadr)[0];
-  int nc = nb + nworld;
-  if (nc > 255) FAIL(-20, "too many collision centres");
-  A.nc = nc; A.nworld = nworld;
-  cen_of_geom.assign(m->ngeom, 0);
-  std::vector<int> geom_of_cen(nc, -1);
-  for (int g = 0; g < m->ngeom; g++) {
-    int ci = gbody[g] == 0 ? nb + (g - SUMO_I(m, body_geomadr)[0]) : gbody[g];
-    cen_of_geom[g] = ci; geom_of_cen[ci] = g;
-  }
-  // static double tables: csize[2*nc] | cinvw[nc] | wbox[12*nworld] | wlim[6*nworld]
-  A.o_stat_d = (int)af.size();
-  {
-    std::vector<double> sd((size_t)3 * nc + 18 * nworld, 0.0), wpa((size_t)6 * nworld, 0.0);
-    for (int ci = 0; ci < nc; ci++) {
-      int g = geom_of_cen[ci];
-      if (g >= 0) { sd[2 * ci] = SUMO_F(m, geom_size)[3 * g]; sd[2 * ci + 1] = SUMO_F(m, geom_size)[3 * g + 1]; }
-      int body = ci < nb ? ci : 0;
-      sd[2 * nc + ci] = SUMO_F(m, body_invweight0)[2 * body];
-    }
-    const double BIG = 1e300;
-    for (int w = 0; w < nworld; w++) {
-      int g = SUMO_I(m, body_geomadr)[0] + w;
-      double R[9];
-      quat2mat_h(R, SUMO_F(m, geom_quat) + 4 * g);
-      double* wb = &sd[3 * nc + 12 * w];
-      for (int k = 0; k < 9; k++) wb[k] = R[k];
-      for (int k = 0; k < 3; k++) wb[9 + k] = SUMO_F(m, geom_size)[3 * g + k];
-      // broad-phase extent of the geom in its own frame, hi[3] | lo[3] (the other geom's bounding radius goes into the
-      // pair bound): box = its half sizes; capsule / border rod = its axis segment; plane = the half space z <= 0;
-      // anything else = its centre with the bounding radius
-      double* wl = &sd[3 * nc + 12 * nworld + 6 * w];
-      const double* gs = SUMO_F(m, geom_size) + 3 * g;
-      if (gtype[g] == SUMO_GEOM_BOX) { for (int k = 0; k < 3; k++) { wl[k] = gs[k]; wl[3 + k] = -gs[k]; } }
-      else if (gtype[g] == SUMO_GEOM_CAPSULE || gtype[g] == SUMO_GEOM_CYLINDER) { wl[2] = gs[1]; wl[5] = -gs[1]; }
-      else if (gtype[g] == SUMO_GEOM_PLANE) { wl[0] = wl[1] = BIG; wl[2] = 0; wl[3] = wl[4] = wl[5] = -BIG; }
-      for (int k = 0; k < 3; k++) wpa[3 * w + k] = SUMO_F(m, geom_pos)[3 * g + k];
-      wpa[3 * nworld + 3 * w + 0] = R[2]; wpa[3 * nworld + 3 * w + 1] = R[5]; wpa[3 * nworld + 3 * w + 2] = R[8];
-    }
-    A.n_stat_d = (int)sd.size();
-    af.insert(af.end(), sd.begin(), sd.end());
-    A.o_wpa = (int)af.size();   // world geom positions / axes: read once per launch, not kept in LDS
-    af.insert(af.end(), wpa.begin(), wpa.end());
-  }
-  // static int tables: ctype[nc] | cbody[nc] | chain words [2*nb] | chlen_agent[nb]
-  {
-    std::vector<int> si((size_t)2 * nc + 3 * nb, 0);
-    for (int ci = 0; ci < nc; ci++) {
-      int g = geom_of_cen[ci];
-      int t = g >= 0 ? gtype[g] : -1;
-      if (t == SUMO_GEOM_CYLINDER) t = SUMO_GEOM_CAPSULE;  // border rods collide as capsules
-      si[ci] = t; si[nc + ci] = ci < nb ? ci : 0;
-    }
-    for (int b = 0; b < nb; b++) {
-      unsigned w0 = 0, w1 = 0;
-      for (int p = 0; p < chain_len[b]; p++) {
-        unsigned d = (unsigned)chain[b * MAXCHAIN + p];
-        if (p < 4) w0 |= d << (8 * p); else w1 |= d << (8 * (p - 4));
-      }
-      si[2 * nc + 2 * b] = (int)w0; si[2 * nc + 2 * b + 1] = (int)w1;
-      si[2 * nc + 2 * nb + b] = chain_len[b] | ((body_agent[b] < 0 ? 0 : body_agent[b]) << 8);
-    }
-    A.o_stat_i = push_tbl(si);
-    A.n_stat_i = (int)si.size();
-  }
-  return 0;
-}
-
-// per-lane constants: lane l is body l, dof l, joint l and actuator l at once
-int AuxBuilder::lane_records() {
-  S.lanes.assign(WAVE, LaneRec());
-  const int* jbody = SUMO_I(m, jnt_bodyid);
-  for (int l = 0; l < WAVE; l++) {
-    LaneRec& K = S.lanes[l];
-    memset(&K, 0, sizeof K);
-    K.b_jnt = -1; K.b_level = -1; K.b_agent = 0;
-    if (l < nb) {
-      int b = l;
-      for (int k = 0; k < 3; k++) { K.b_pos[k] = folded ? epos[3 * b + k] : SUMO_F(m, body_pos)[3 * b + k]; K.b_ipos[k] = SUMO_F(m, body_ipos)[3 * b + k]; K.b_inertia[k] = SUMO_F(m, body_inertia)[3 * b + k]; }
-      for (int k = 0; k < 4; k++) { K.b_quat[k] = folded ? equat[4 * b + k] : SUMO_F(m, body_quat)[4 * b + k]; K.b_iquat[k] = SUMO_F(m, body_iquat)[4 * b + k]; }
-      K.b_mass = SUMO_F(m, body_mass)[b];
-      K.b_parent = parent[b]; K.b_level = depth[b]; K.b_agent = body_agent[b] < 0 ? 0 : body_agent[b];
-      int jn = SUMO_I(m, body_jntnum)[b], ja = SUMO_I(m, body_jntadr)[b];
-      if (jn > 1) FAIL(-21, "body %d has %d joints; the engine supports at most one per body", b, jn);
-      if (jn == 1) {
-        K.b_jnt = ja;
-        K.b_isfree = SUMO_I(m, jnt_type)[ja] == SUMO_JNT_FREE;
-        K.b_qadr = SUMO_I(m, jnt_qposadr)[ja];
-        for (int k = 0; k < 3; k++) { K.j_pos[k] = SUMO_F(m, jnt_pos)[3 * ja + k]; K.j_axis[k] = SUMO_F(m, jnt_axis)[3 * ja + k]; }
-        K.j_qpos0 = SUMO_F(m, qpos0)[K.b_qadr];
-      }
-      int c0 = child_adr[b], c1 = child_adr[b + 1];
-      K.b_nchild = c1 - c0;
-      if (K.b_nchild > 8) FAIL(-22, "body %d has more than 8 children", b);
-      if (b > 0 && K.b_nchild > A.maxchild) A.maxchild = K.b_nchild;
-      {  // inertial constants for cinert: own, merged with the rigidly attached leaves, or zero for such a leaf
-        auto add_part = [&](double* I6, double* mc, double& M, double mass, const double* cpos, const double* Rb, const double* diag) {
-          // accumulates mass, mass * centre and the inertia about the ORIGIN of the body frame (shifted to the centre below)
-          double Ip[9];
-          for (int r = 0; r < 3; r++) for (int cc = 0; cc < 3; cc++)
-            Ip[3 * r + cc] = Rb[3 * r] * diag[0] * Rb[3 * cc] + Rb[3 * r + 1] * diag[1] * Rb[3 * cc + 1] + Rb[3 * r + 2] * diag[2] * Rb[3 * cc + 2];
-          double d2 = cpos[0] * cpos[0] + cpos[1] * cpos[1] + cpos[2] * cpos[2];
-          I6[0] += Ip[0] + mass * (d2 - cpos[0] * cpos[0]); I6[1] += Ip[4] + mass * (d2 - cpos[1] * cpos[1]); I6[2] += Ip[8] + mass * (d2 - cpos[2] * cpos[2]);
-          I6[3] += Ip[1] - mass * cpos[0] * cpos[1]; I6[4] += Ip[2] - mass * cpos[0] * cpos[2]; I6[5] += Ip[5] - mass * cpos[1] * cpos[2];
-          for (int k = 0; k < 3; k++) mc[k] += mass * cpos[k];
-          M += mass;
-        };
-        double I6[6] = {0, 0, 0, 0, 0, 0}, mc[3] = {0, 0, 0}, M = 0, Rb[9];
-        if (!is_stub[b]) {
-          quat2mat_h(Rb, SUMO_F(m, body_iquat) + 4 * b);
-          add_part(I6, mc, M, SUMO_F(m, body_mass)[b], SUMO_F(m, body_ipos) + 3 * b, Rb, SUMO_F(m, body_inertia) + 3 * b);
-          for (int sb = 1; sb < nb; sb++)
-            if (is_stub[sb] && parent[sb] == b) {
-              double Rs[9], Ri[9], Rsi[9], cs[3];
-              quat2mat_h(Rs, &equat[4 * sb]);
-              quat2mat_h(Ri, SUMO_F(m, body_iquat) + 4 * sb);
-              for (int r = 0; r < 3; r++) for (int cc = 0; cc < 3; cc++)
-                Rsi[3 * r + cc] = Rs[3 * r] * Ri[cc] + Rs[3 * r + 1] * Ri[3 + cc] + Rs[3 * r + 2] * Ri[6 + cc];
-              const double* ip = SUMO_F(m, body_ipos) + 3 * sb;
-              for (int k = 0; k < 3; k++) cs[k] = epos[3 * sb + k] + Rs[3 * k] * ip[0] + Rs[3 * k + 1] * ip[1] + Rs[3 * k + 2] * ip[2];
-              add_part(I6, mc, M, SUMO_F(m, body_mass)[sb], cs, Rsi, SUMO_F(m, body_inertia) + 3 * sb);
-              A.nstub++;
-            }
-          double cm[3] = {0, 0, 0};
-          if (M > 0) for (int k = 0; k < 3; k++) cm[k] = mc[k] / M;
-          // shift from the frame origin to the (merged) centre of mass
-          double d2 = cm[0] * cm[0] + cm[1] * cm[1] + cm[2] * cm[2];
-          I6[0] -= M * (d2 - cm[0] * cm[0]); I6[1] -= M * (d2 - cm[1] * cm[1]); I6[2] -= M * (d2 - cm[2] * cm[2]);
-          I6[3] += M * cm[0] * cm[1]; I6[4] += M * cm[0] * cm[2]; I6[5] += M * cm[1] * cm[2];
-          for (int k = 0; k < 6; k++) K.c_I[k] = I6[k];
-          for (int k = 0; k < 3; k++) K.c_ipos[k] = cm[k];
-          K.c_mass = M;
-        }
-      }
-      for (int q = 0; q < K.b_nchild; q++) K.b_child |= (unsigned long long)child[c0 + q] << (8 * q);
-      K.b_bchain_len = bchain_len[b];
-      for (int q = 0; q < bchain_len[b]; q++) K.b_bchain |= (unsigned)bchain[b * MAXBCHAIN + q] << (8 * q);
-      K.b_chain_len = chain_len[b];
-      for (int q = 0; q < chain_len[b]; q++) {
-        int d = chain[b * MAXCHAIN + q];
-        K.b_chain |= (unsigned long long)d << (8 * q);
-        if (SUMO_I(m, dof_bodyid)[d] == b) K.b_chain_own |= 1u << q;
-        int jt = SUMO_I(m, dof_jntid)[d];
-        if (SUMO_I(m, jnt_type)[jt] == SUMO_JNT_FREE && SUMO_I(m, jnt_dofadr)[jt] == d) K.b_chain_free |= 1u << q;
-      }
-    }
-    if (l < nv) {
-      int d = l, b = SUMO_I(m, dof_bodyid)[d];
-      K.d_arm = SUMO_F(m, dof_armature)[d]; K.d_damp = SUMO_F(m, dof_damping)[d]; K.d_body = b;
-      K.d_pos = pic[(size_t)b * nv + d];
-      K.d_hid = -1;
-      { int jt = SUMO_I(m, dof_jntid)[d];
-        if (SUMO_I(m, jnt_type)[jt] == SUMO_JNT_HINGE) { int h = 0; for (int jj = 0; jj < jt; jj++) if (SUMO_I(m, jnt_type)[jj] == SUMO_JNT_HINGE) h++; K.d_hid = h; } }
-      for (int q = 0; q < chain_len[b]; q++) K.d_chain |= (unsigned long long)chain[b * MAXCHAIN + q] << (8 * q);
-    }
-    if (l < m->njnt) {
-      int j = l;
-      K.jt_type = SUMO_I(m, jnt_type)[j]; K.jt_qadr = SUMO_I(m, jnt_qposadr)[j]; K.jt_dadr = SUMO_I(m, jnt_dofadr)[j];
-      K.jt_limited = SUMO_I(m, jnt_limited)[j]; K.jt_body = jbody[j]; K.jt_agent = body_agent[jbody[j]] < 0 ? 0 : body_agent[jbody[j]];
-      K.jt_lo = SUMO_F(m, jnt_range)[2 * j]; K.jt_hi = SUMO_F(m, jnt_range)[2 * j + 1]; K.jt_margin = SUMO_F(m, jnt_margin)[j];
-      K.jt_invw = SUMO_F(m, dof_invweight0)[K.jt_dadr];
-      K.jt_hid = -1;
-      if (K.jt_type == SUMO_JNT_HINGE) { int h = 0; for (int jj = 0; jj < j; jj++) if (SUMO_I(m, jnt_type)[jj] == SUMO_JNT_HINGE) h++; K.jt_hid = h; }
-    }
-    if (l < m->nu) {
-      K.a_dof = SUMO_I(m, actuator_dofid)[l]; K.a_gear = SUMO_F(m, actuator_gear)[l];
-      K.a_lo = SUMO_F(m, actuator_ctrlrange)[2 * l]; K.a_hi = SUMO_F(m, actuator_ctrlrange)[2 * l + 1];
-    }
-  }
-  return 0;
-}
-
-// lower-triangle entry words of the dense Hessian assembly, entry t = lane + 64 m: (i << 8 | j) | chain position of dof i
-// << 16 | of dof j << 20; 0xFFFF = none.  Read where the (rare) dense path assembles H instead of living in 7 registers of
-// every lane for the whole launch.
-void AuxBuilder::hessian_entries() {
-  const int epl = (A.ntri + WAVE - 1) / WAVE;
-  std::vector<int> ent((size_t)epl * WAVE, 0xFFFF);
-  for (int t = 0; t < A.ntri; t++) {
-    const int i = tri_i[t], j = tri_j[t];
-    ent[t] = (int)((unsigned)((i << 8) | j) | ((unsigned)S.lanes[i].d_pos << 16) | ((unsigned)S.lanes[j].d_pos << 20));
-  }
-  A.o_ent = push_tbl(ent);
-}
-
-// packed pair records for the broad phase: pairs with a static world geom first (the model lists them first:
-// body-pair order, world body = 0), padded to whole rounds of 64, then the pairs between moving geoms.
-//   world pair:  moving centre | world centre << 8 | (world geom is geom1) << 16 | valid << 17
-//                bound = margin + rbound(moving geom) [+ radius of a static capsule; + rbound of other static shapes]
-//   moving pair: c1 | c2 << 8 | valid << 17;  bound = margin + rbound1 + rbound2
-// bounds are rounded up in float: the broad phase may only over-include
-int AuxBuilder::pair_records() {
-  int nwp = 0;
-  while (nwp < m->npair && (gbody[SUMO_I(m, pair_geom1)[nwp]] == 0 || gbody[SUMO_I(m, pair_geom2)[nwp]] == 0)) nwp++;
-  for (int p = nwp; p < m->npair; p++)
-    if (gbody[SUMO_I(m, pair_geom1)[p]] == 0 || gbody[SUMO_I(m, pair_geom2)[p]] == 0)
-      FAIL(-23, "collision pair %d: pairs with a world geom must precede the others", p);
-  const int WR = (nwp + WAVE - 1) / WAVE, AR = (m->npair - nwp + WAVE - 1) / WAVE;
-  A.nwp = nwp; A.wrounds = WR; A.arounds = AR;
-  S.pair_rec.assign((size_t)(WR + AR) * WAVE, 0);
-  S.pair_bound.assign((size_t)(WR + AR) * WAVE, 0.0f);
-  auto up = [](double bound) {
-    float bf = (float)bound;
-    while ((double)bf < bound) bf = nextafterf(bf, INFINITY);
-    return nextafterf(bf, INFINITY);
-  };
-  for (int p = 0; p < m->npair; p++) {
-    int g1 = SUMO_I(m, pair_geom1)[p], g2 = SUMO_I(m, pair_geom2)[p];
-    const double margin = SUMO_F(m, pair_margin)[p];
-    if (p < nwp) {
-      if (gbody[g1] == 0 && gbody[g2] == 0) continue;   // static-static: never collides (slot stays invalid)
-      const int w1 = gbody[g1] == 0, gw = w1 ? g1 : g2, ga = w1 ? g2 : g1, tw = gtype[gw];
-      double bound = margin + SUMO_F(m, geom_rbound)[ga];
-      if (tw == SUMO_GEOM_CAPSULE || tw == SUMO_GEOM_CYLINDER) bound += SUMO_F(m, geom_size)[3 * gw];
-      else if (tw != SUMO_GEOM_BOX && tw != SUMO_GEOM_PLANE) bound += SUMO_F(m, geom_rbound)[gw];
-      S.pair_rec[p] = cen_of_geom[ga] | (cen_of_geom[gw] << 8) | (w1 << 16) | (1 << 17);
-      S.pair_bound[p] = up(bound);
-    } else {
-      const int sl = WR * WAVE + (p - nwp);
-      S.pair_rec[sl] = cen_of_geom[g1] | (cen_of_geom[g2] << 8) | (1 << 17);
-      S.pair_bound[sl] = up(margin + SUMO_F(m, geom_rbound)[g1] + SUMO_F(m, geom_rbound)[g2]);
-    }
-  }
-  return 0;
-}
-
-static void build_layout_with(Scene& S, const SceneOptions& opt, int jb_extra) {
-  const sumo_model_t* m = &S.hm;
-  Layout& L = S.L;
-  int nq = m->nq, nv = m->nv, nb = m->nbody, nj = m->njnt, nu = m->nu;
-  L.ld = nv | 1;
-  int nhinge = 0;
-  for (int j = 0; j < nj; j++) if (SUMO_I(m, jnt_type)[j] == SUMO_JNT_HINGE) nhinge++;
-  // Ant-vs-Ant: 18 contact records (the soaks and the zoo play never saw more than 14) instead of 24: the 1 KB goes to the contact-Jacobian pool
-  // (build_layout: 29 halves instead of 24 -- 14 contacts between two moving bodies fit), which is what overflowed a few times per 10^8 forwards
-  L.maxcon = nv <= 28 ? 18 : (nv <= 36 ? 32 : 40);
-  if (opt.maxcon > 0) L.maxcon = opt.maxcon;
-  { int cap = 16 * (nv <= 36 ? 2 : 3); if (L.maxcon > cap) L.maxcon = cap; }  // contact rows per lane held in registers by the line search (newton_solve RPL)
-  L.maxefc = 4 * L.maxcon + 2 * nhinge;
-  L.warm_mode = opt.warm_mode; L.force_dense = opt.force_dense;
-  int o = 0;
-  auto take = [&](int n) { int r = o; o += n; return r; };
-  L.qpos = take(nq); L.qvel = take(nv); L.warm = take(nv); L.ctrl = take(nu);
-  L.x0 = 0; L.accv = 0; L.acca = 0; L.tmpv = take(nv);
-  // kinematic data needed until the mass matrix is built (com, cinert -> crb, cdof); the packed Hessian aliases it
-  const int nc = S.aux.nc;
-  const int ntri = nv * (nv + 1) / 2;
-  int kin0 = o;
-  L.com = take(3 * m->nagent); L.cinert = take(10 * nb); L.cdof = take(6 * nv);
-  L.H = kin0;
-  if (o - kin0 < ntri) o = kin0 + ntri;
-  const int hsize = o - kin0;
-  // centre positions / axes: bodies (rewritten every forward) then world geoms (static)
-  L.xipos = take(3 * nc); L.gaxis = take(3 * nc);
-  L.stat_d = take(SUMO_STAT_LDS ? S.aux.n_stat_d : 0);
-  {
-    int nv0 = SUMO_I(m, agent_nv)[0], nv1 = SUMO_I(m, agent_nv)[1];
-    int mx = nv0 > nv1 ? nv0 : nv1;
-    L.mld = mx | 1;
-    L.d1 = SUMO_I(m, agent_dofadr)[1];
-    L.msize = (nv0 + nv1) * L.mld;
-  }
-  {  // shape tree_factor_solve relies on: two agents, each a free joint (6 dofs) + legs of (hip, ankle), bases even
-    const int* dpar = SUMO_I(m, dof_parentid);
-    int ok = m->nagent == 2 && SUMO_I(m, agent_dofadr)[0] == 0 && SUMO_I(m, agent_nv)[0] + SUMO_I(m, agent_nv)[1] == nv;
-    for (int g = 0; ok && g < 2; g++) {
-      int B = SUMO_I(m, agent_dofadr)[g], n = SUMO_I(m, agent_nv)[g];
-      if ((B & 1) || n < 6 || ((n - 6) & 1)) { ok = 0; break; }
-      if (dpar[B] != -1) ok = 0;
-      for (int k = 1; ok && k < 6; k++) if (dpar[B + k] != B + k - 1) ok = 0;
-      for (int d = B + 6; ok && d < B + n; d += 2) if (dpar[d] != B + 5 || dpar[d + 1] != d) ok = 0;
-    }
-    if (14 * nv > hsize) ok = 0;   // exchange buffers of the tree solver live in the Hessian region
-    L.tree_ok = ok;
-    if (opt.no_tree) L.tree_ok = 0;
-  }
-  L.qsm = take(nv); L.asmo = take(nv); L.Ma = 0; L.grad = 0;
-  L.search = take(nv); L.bias = L.search;   // the bias force is consumed (into qsm) before the solver writes its search direction
-  L.Mv = 0; L.x = take(nv); L.dlim = take(nv); L.cmask = take(nv); L.stash = take(12);   // + the fused rollout's ticket (env, step) and the step's reward inputs / episode record for its post phase
-  // contact records live from the narrow phase to the Jacobian build only: they borrow the mass matrix's storage
-  if (L.msize < 14 * L.maxcon) L.msize = 14 * L.maxcon;
-  if (L.msize < 12 * nb) L.msize = 12 * nb;      // ... and so do the velocity-pass temporaries (abuf, cfrc), see below
-  L.M = take(L.msize);
-  L.cond = L.M;
-  // body frames / joint anchors / RNE temporaries are dead before the contact Jacobians are written: same storage
-  {
-    // pool of Jacobian halves (3 rows x 8 slots, one half per moving body of a contact): room for maxcon contacts with the
-    // world, or half as many between two moving bodies -- more where the frames' storage leaves space anyway
-    int need = 7 * nb + 6 * nj;
-    L.jbcap = L.maxcon;
-    if ((need - 16) / 24 > L.jbcap) L.jbcap = (need - 16) / 24;
-    L.jbcap += jb_extra;
-    if (opt.jbcap > 0) L.jbcap = opt.jbcap;
-    int jb0 = o, jbsz = 24 * L.jbcap + 16;
-    L.Jb = take(jbsz > need ? jbsz : need);
-    int q = jb0;
-    L.xpos = q; q += 3 * nb; L.xquat = q; q += 4 * nb; L.xanchor = q; q += 3 * nj; L.xaxis = q; q += 3 * nj;
-    // velocity-pass temporaries (dead before the narrow phase writes contact records there): the mass matrix's storage
-    L.abuf = L.M; L.cfrc = L.M + 6 * nb;
-  }
-  L.cpar = take(L.maxcon); L.cW = take(5 * L.maxcon);
-  L.cp = take(3 * L.maxcon);
-  // row arrays hold the contact rows only (4 per contact); the limit rows live in the dof-indexed slots limD / limA
-  L.jar = take(4 * L.maxcon); L.D = take(L.maxcon); L.aref = take(4 * L.maxcon);
-  L.nhinge = nhinge; L.limD = take(2 * nhinge); L.limA = take(2 * nhinge);
-  // queue of broad-phase survivors (ints, inside jar / aref); drained by the narrow phase before it can overflow
-  L.maxcand = 8 * L.maxcon >= 192 ? 192 : (8 * L.maxcon) / WAVE * WAVE;
-  L.i_base = o;
-  int io = 0;
-  auto itake = [&](int n) { int r = io; io += n; return r; };
-  L.con_b = itake(4 * L.maxcon);
-  L.stat_i = itake(SUMO_STAT_LDS ? S.aux.n_stat_i : 0);
-  L.b_dofidx = io * 4;
-  L.total_bytes = o * 8 + io * 4 + 16 * L.maxcon;
-}
-// The LDS a wave slot leaves unused at the scene's residency (160 KB / waves per CU - the env record) goes to the contact-Jacobian
-// pool: a contact between two moving bodies takes two halves, and wrestling Spiders overflowed a pool of `maxcon` halves about twice
-// per million env steps (counted in `dropped`).  Ant-vs-Ant has 32 B to spare (8 x 20 448 B = 163 584 of 163 840): unchanged.
-static void build_layout(Scene& S, const SceneOptions& opt) {
-  build_layout_with(S, opt, 0);
-  const int lds_cu = 160 * 1024, slots = lds_cu / S.L.total_bytes;
-  if (slots < 1 || opt.jbcap_set) return;
-  const int budget = lds_cu / slots / 1280 * 1280;   // LDS is allocated in granules of 1280 B on gfx950
-  int extra = (budget - S.L.total_bytes) / (24 * 8);
-  if (extra > S.L.maxcon) extra = S.L.maxcon;        // (a pool of 2 x maxcon halves can never overflow)
-  if (extra <= 0) return;
-  build_layout_with(S, opt, extra);
-  if (lds_cu / S.L.total_bytes != slots) build_layout_with(S, opt, 0);   // (cannot happen: the growth was sized to fit)
-}
-
-// The two role words of every lane (LaneRec::role0 / role1), packed from the records build_aux filled; after build_layout, whose
-// tree_ok decides whether the kernels derive chain elements from the words.  Nothing is truncated: a value that does not fit its
-// field, or a scene in which a derived quantity differs from the model's, fails creation.
-static int build_lane_roles(Scene& S) {
-  const sumo_model_t* m = &S.hm;
-  const char* bad = nullptr; int bad_lane = 0; long bad_val = 0;
-  int nfree = 0;   // free joints before joint l
-  for (int l = 0; l < WAVE; l++) {
-    LaneRec& K = S.lanes[l];
-    unsigned w[2] = {0u, 0u};
-    auto put = [&](int wi, int lo, int n, long v, const char* what) {
-      if ((v < 0 || v >= (1L << n)) && !bad) { bad = what; bad_lane = l; bad_val = v; }
-      w[wi] |= ((unsigned)v & ((1u << n) - 1u)) << lo;
-    };
-    const int hinge = l < m->nbody && K.b_jnt >= 0 && !K.b_isfree;
-    put(0, ROLE0_LEVEL1, K.b_level + 1, "b_level");
-    put(0, ROLE0_AGENT, K.b_agent, "b_agent");
-    put(0, ROLE0_ISFREE, K.b_isfree, "b_isfree");
-    put(0, ROLE0_HINGE, hinge, "b_hinge");
-    put(0, ROLE0_PARENT, l >= 1 ? K.b_parent : 0, "b_parent");
-    put(0, ROLE0_NCHILD, K.b_nchild, "b_nchild");
-    put(0, ROLE0_CHAIN_LEN, K.b_chain_len, "b_chain_len");
-    put(0, ROLE0_BCHAIN_LEN, K.b_bchain_len, "b_bchain_len");
-    put(0, ROLE0_QADR, K.b_qadr, "b_qadr");
-    put(1, ROLE1_LDOF, K.b_chain_len > 0 ? BYTE_OF(K.b_chain, K.b_chain_len - 1) : 0, "b_chain (last dof)");
-    put(1, ROLE1_HID1, l < m->nv ? K.d_hid + 1 : 0, "d_hid");
-    put(1, ROLE1_DPOS, K.d_pos, "d_pos");
-    put(1, ROLE1_DBODY, K.d_body, "d_body");
-    if (l < m->njnt) {
-      if (K.jt_type != SUMO_JNT_FREE && K.jt_type != SUMO_JNT_HINGE) FAIL(-26, "joint %d has type %d; the engine supports free joints and hinges", l, K.jt_type);
-      const int jh = K.jt_type == SUMO_JNT_HINGE;
-      put(0, ROLE0_JT_HINGE, jh, "jt_type");
-      put(0, ROLE0_JT_LIMITED, K.jt_limited, "jt_limited");
-      put(0, ROLE0_JT_AGENT, K.jt_agent, "jt_agent");
-      put(1, ROLE1_JT_NFREE, nfree, "free joints before the joint");
-      put(1, ROLE1_JT_BODY, K.jt_body, "jt_body");
-      if (K.jt_dadr != l + 5 * nfree || K.jt_qadr != l + 6 * nfree || (jh && K.jt_hid != l - nfree))
-        FAIL(-26, "joint %d: dof address %d / qpos address %d / hinge index %d do not follow from %d free joints before it", l, K.jt_dadr,
-             K.jt_qadr, K.jt_hid, nfree);
-      if (!jh) nfree++;
-    }
-    if (bad) FAIL(-26, "lane %d: %s = %ld does not fit its field of the lane role words", bad_lane, bad, bad_val);
-    if (S.L.tree_ok && l >= 1 && l < m->nbody) {   // what the tree-shaped velocity pass derives instead of reading b_chain / b_chain_own
-      const int len = K.b_chain_len, ld = len > 0 ? BYTE_OF(K.b_chain, len - 1) : 0, B = K.b_agent ? S.L.d1 : 0;
-      int ok = len >= 6 && len <= 8;
-      for (int p = 0; ok && p < len; p++) {
-        const int want = p < 6 ? B + p : (len > 7 ? ld - 7 + p : ld);
-        if (BYTE_OF(K.b_chain, p) != want) ok = 0;
-      }
-      const unsigned own = (K.b_isfree ? 0x3Fu : 0u) | (hinge && len > 6 ? 1u << (len - 1) : 0u);
-      if (!ok || K.b_chain_own != own || (hinge && len <= 6))
-        FAIL(-26, "body %d: its dof chain is not the root's six dofs, then hip and ankle, owned as its joint says", l);
-    }
-    K.role0 = w[0]; K.role1 = w[1];
-  }
-  return 0;
-}
-
-// the integer members of the compiled model view (header dims, then the int / float table offsets in SUMO_*_TABLES order)
-static int model_ints(const sumo_model_t* m, int32_t* out) {
-  int n = 0;
-  out[n++] = m->nq; out[n++] = m->nv; out[n++] = m->nu; out[n++] = m->nbody; out[n++] = m->njnt; out[n++] = m->ngeom; out[n++] = m->npair;
-  out[n++] = m->nagent; out[n++] = m->frame_skip; out[n++] = m->timestep_limit;
-#define X(name, len) out[n++] = m->o_##name;
-  SUMO_INT_TABLES(X)
-  SUMO_FLT_TABLES(X)
-#undef X
-  return n;
-}
-
-// The last stage of a preparation, what only the whole scene can answer: which kernel variants run it, whether its constraint rows
-// fit the registers, and the strides of its per-env records.
-static int finish_scene(Scene& S, const SceneOptions& opt) {
-  {   // static kernel variants only when the runtime Layout IS the compile-time table (SUMO_STATIC_LAYOUT=0 switches them off)
-    static_assert(sizeof(Layout) % sizeof(int) == 0, "Layout is all ints");
-    int32_t mi[160];
-    const int nmi = model_ints(&S.hm, mi);
-    auto same = [&](const int* kl, size_t nl, const int* km, size_t nm_, const int* ka, size_t na) {
-      return nl == sizeof(Layout) && memcmp(&S.L, kl, nl) == 0 && nm_ == nmi * sizeof(int) && memcmp(mi, km, nm_) == 0 &&
-             na == AUX_NINTS * sizeof(int) && memcmp(&S.aux.ndepth, ka, na) == 0;
-    };
-    S.static_layout = 0;      // 1: Ant-vs-Ant, 2: Spider-vs-Spider (the scenes of csrc/layout_static.h), 0: runtime-Layout variants
-    if (opt.static_layout) {
-      if (same(kLayoutAntAnt, sizeof(kLayoutAntAnt), kModelAntAnt, sizeof(kModelAntAnt), kAuxAntAnt, sizeof(kAuxAntAnt))) S.static_layout = 1;
-      else if (same(kLayoutSpiderSpider, sizeof(kLayoutSpiderSpider), kModelSpiderSpider, sizeof(kModelSpiderSpider), kAuxSpiderSpider, sizeof(kAuxSpiderSpider)))
-        S.static_layout = 2;
-    }
-  }
-  if (S.L.maxefc > WAVE * (S.hm.nv <= 28 ? 2 : 4)) FAIL(-24, "maxefc %d exceeds the rows a lane keeps in registers", S.L.maxefc);
-  const sumo_model_t* m = &S.hm;
-  int od = 0, ad = 0;
-  for (int a = 0; a < m->nagent; a++) {
-    int o = SUMO_I(m, agent_nq)[a] + SUMO_I(m, agent_nv)[a] + 6 * SUMO_I(m, agent_nbody)[a] + 14;
-    if (o > od) od = o;
-    if (SUMO_I(m, agent_nu)[a] > ad) ad = SUMO_I(m, agent_nu)[a];
-  }
-  S.obs_stride = od; S.act_stride = ad;
-  S.state_stride = (m->nq + 2 * m->nv + 2 + 15) & ~15;
-  return 0;
-}
-
-// The Newton loop's gradient test D(gn) = (scale * sqrt(gn) < tol) as a threshold on gn, the squared gradient norm: with a correctly
-// rounded sqrt and scale >= 0, D is non-increasing over gn >= 0, so D(gn) == (gn <= G) for G the largest double with D(G) true (-1 where
-// there is none; gn is a sum of squares, never below +0).  NaN and +inf fail both forms.  Found by bisection over the bit patterns of the
-// non-negative finite doubles, which are ordered like their values.
-static double grad_threshold(double scale, double tol) {
-  auto D = [&](uint64_t bits) { double g; memcpy(&g, &bits, sizeof g); volatile double s = sqrt(g); volatile double p = scale * s; return p < tol; };
-  uint64_t lo = 0, hi = 0x7FEFFFFFFFFFFFFFull;   // +0 .. DBL_MAX
-  if (!D(lo)) return -1.0;
-  while (lo < hi) {   // invariant: D(lo) true
-    const uint64_t mid = lo + (hi - lo + 1) / 2;
-    if (D(mid)) lo = mid; else hi = mid - 1;
-  }
-  double g; memcpy(&g, &lo, sizeof g);
-  return g;
-}
-static double newton_scale(const sumo_model_t* m) { return 1.0 / (SUMO_F(m, opt)[SUMO_OPT_MEANINERTIA] * (m->nv > 1 ? m->nv : 1)); }   // newton_solve's `scale`
-
-// The one preparation of a scene from a model blob, in stages; a caller stops after the stage it needs, and a scene that fails a
-// later stage still answers for the earlier ones.  Host only.
-enum SceneStage { SCENE_AUX, SCENE_LAYOUT, SCENE_ROLES, SCENE_CHECKED };
-static int prepare_scene(Scene& S, const void* blob, size_t nbytes, SceneStage upto) {
-  const SceneOptions opt = SceneOptions::from_env();
-  S.blob.assign((const char*)blob, (const char*)blob + nbytes);
-  if (int rc = sumo_model_parse(&S.hm, S.blob.data(), nbytes)) FAIL(-4, "malformed model blob (%d)", rc);
-  if (int rc = build_aux(S, opt)) return rc;             // aux tables, lane records, pair records
-  S.grad_thresh = grad_threshold(newton_scale(&S.hm), SUMO_F(&S.hm, opt)[SUMO_OPT_TOLERANCE]);
-  if (upto == SCENE_AUX) return 0;
-  build_layout(S, opt);
-  if (upto == SCENE_LAYOUT) return 0;
-  if (int rc = build_lane_roles(S)) return rc;           // after the layout: its tree_ok decides what the words must carry
-  if (upto == SCENE_ROLES) return 0;
-  return finish_scene(S, opt);
-}
-
-// kernel variants by nv (the factorisation is unrolled over a compile-time nv); the nine registered scenes have
-// nv in {28, 32, 36, 40, 44}
-template <class F>
-static bool for_kernel_variant(int nv, F&& f) {
-#define X(NVV) if (nv == NVV) { f(std::integral_constant<int, NVV>()); return true; }
-  SUMO_FOR_NV(X)
-#undef X
-  return false;
-}
-
-// an env record of more than the 64 KB of LDS a launch gets without asking
-template <int NV>
-static int allow_large_lds(int bytes) {
-  HIPCHK(hipFuncSetAttribute((const void*)sumo_step_kernel<NV>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-  HIPCHK(hipFuncSetAttribute((const void*)sumo_reset_kernel<NV>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-  HIPCHK(hipFuncSetAttribute((const void*)sumo_forward_kernel<NV>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-  return 0;
-}
-
-// Every failure below returns through the unique_ptr: the engine and whatever it had allocated on the device go with it.
-extern "C" int sumo_create(const void* model_blob, size_t nbytes, int num_envs, int device, sumo_handle_t* out) {
-  if (!model_blob || !out || num_envs <= 0) FAIL(-1, "bad arguments");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) FAIL(-2, "no HIP device available: the engine has no CPU fallback");
-  if (device < 0 || device >= ndev) FAIL(-3, "device %d out of range (%d devices)", device, ndev);
-  HIPCHK(hipSetDevice(device));
-  std::unique_ptr<sumo_engine> E(new sumo_engine());
-  E->device = device; E->N = num_envs;
-  if (int rc = prepare_scene(*E, model_blob, nbytes, SCENE_CHECKED)) return rc;
-  hipDeviceProp_t prop;
-  HIPCHK(hipGetDeviceProperties(&prop, device));
-  if ((size_t)E->L.total_bytes > prop.sharedMemPerBlock && (size_t)E->L.total_bytes > 160 * 1024)
-    FAIL(-5, "LDS need %d bytes exceeds the device limit", E->L.total_bytes);
-  const sumo_model_t* m = &E->hm;
-  HIPCHK(E->d_blob.upload(E->blob));
-  HIPCHK(E->d_ai.upload(E->ai));
-  HIPCHK(E->d_af.upload(E->af));
-  HIPCHK(E->d_pic.upload(E->pic));
-  HIPCHK(E->d_lanes.upload(E->lanes));
-  HIPCHK(E->d_pair_rec.upload(E->pair_rec));
-  HIPCHK(E->d_pair_bound.upload(E->pair_bound));
-  {
-    Params hp;
-    hp.mdl = E->hm;   // the device view: the host view with its table bases inside the uploaded blob
-    hp.mdl.ibase = (const int32_t*)(E->d_blob.get() + ((const char*)E->hm.ibase - E->blob.data()));
-    hp.mdl.fbase = (const double*)(E->d_blob.get() + ((const char*)E->hm.fbase - E->blob.data()));
-    hp.aux = E->aux; hp.aux.ai = E->d_ai; hp.aux.af = E->d_af; hp.aux.pic = E->d_pic;
-    hp.L = E->L;
-    hp.lanes = E->d_lanes; hp.pair_rec = E->d_pair_rec; hp.pair_bound = E->d_pair_bound;
-    hp.adjust_z = 0.0;
-    hp.grad_thresh = E->grad_thresh;
-    HIPCHK(E->d_params.alloc(1));
-    HIPCHK(hipMemcpy(E->d_params, &hp, sizeof(Params), hipMemcpyHostToDevice));
-  }
-  size_t N = (size_t)num_envs;
-  HIPCHK(E->d_state.alloc(N * E->state_stride));
-  HIPCHK(hipMemset(E->d_state, 0, N * E->state_stride * sizeof(double)));
-  HIPCHK(E->d_counters.alloc(N * 4));
-  HIPCHK(hipMemset(E->d_counters, 0, N * 4 * sizeof(int)));
-  std::vector<uint64_t> seeds(N);
-  for (size_t i = 0; i < N; i++) seeds[i] = i;
-  HIPCHK(E->d_seeds.upload(seeds));
-  HIPCHK(E->d_stats.alloc(48));
-  HIPCHK(hipMemset(E->d_stats, 0, 48 * sizeof(unsigned long long)));
-  {
-    const char* sc = getenv("SUMO_SCHED");
-    E->sched = !(sc && atoi(sc) == 0);
-    HIPCHK(E->d_cost.alloc(2 * N));
-    HIPCHK(E->d_cost_sorted.alloc(N));
-    HIPCHK(E->d_perm.alloc(2 * N));
-    std::vector<int> iota(N);
-    for (size_t i = 0; i < N; i++) iota[i] = (int)i;
-    HIPCHK(E->d_iota.upload(iota));
-    HIPCHK(rocprim::radix_sort_pairs_desc(nullptr, E->sort_tmp_bytes, E->d_cost.get(), E->d_cost_sorted.get(), E->d_iota.get(), E->d_perm.get(), N,
-                                          0, 16, (hipStream_t)0));
-    HIPCHK(E->d_sort_tmp.alloc(E->sort_tmp_bytes ? E->sort_tmp_bytes : 16));
-  }
-  // qpos = qpos0 for every env until the first reset / set_state
-  {
-    std::vector<double> st(N * E->state_stride, 0.0);
-    for (size_t e = 0; e < N; e++) memcpy(&st[e * E->state_stride], SUMO_F(m, qpos0), m->nq * sizeof(double));
-    HIPCHK(hipMemcpy(E->d_state, st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice));
-  }
-  if (E->L.total_bytes > 64 * 1024) {
-    int rc = 0;
-    for_kernel_variant(E->hm.nv, [&](auto nvc_) { rc = allow_large_lds<decltype(nvc_)::value>(E->L.total_bytes); });
-    if (rc) return rc;
-  }
-  *out = E.release();
-  return 0;
-}
-
-extern "C" int sumo_destroy(sumo_handle_t E) {
-  if (!E) return 0;
-  (void)hipSetDevice(E->device);
-  delete E;   // its DevBuf members free the device memory
-  return 0;
-}
-
-extern "C" int sumo_dims(sumo_handle_t E, int32_t* o) {
-  if (!E || !o) FAIL(-1, "bad arguments");
-  const sumo_model_t* m = &E->hm;
-  int v[SUMO_NDIMS] = {m->nq, m->nv, m->nu, m->nbody, m->njnt, m->ngeom, m->npair, m->nagent, E->obs_stride, E->act_stride,
-                       E->L.maxcon, E->L.maxefc, E->L.total_bytes, E->state_stride, E->L.jbcap, 0};
-  memcpy(o, v, sizeof v);
-  return 0;
-}
-
-// the variant an engine's step / rollout kernels run: f(NV, SL) with the static layouts <28, 1> (Ant vs Ant) and <44, 2> (Spider
-// vs Spider) where sumo_create found one, else <nv, 0>
-template <class F>
-static bool for_engine_variant(const sumo_engine* E, F&& f) {
-  if (E->static_layout == 1) { f(std::integral_constant<int, 28>(), std::integral_constant<int, 1>()); return true; }
-  if (E->static_layout == 2) { f(std::integral_constant<int, 44>(), std::integral_constant<int, 2>()); return true; }
-  return for_kernel_variant(E->hm.nv, [&](auto nvc_) { f(nvc_, std::integral_constant<int, 0>()); });
-}
-#define SUMO_DISPATCH(KERNEL, E, stream, args) SUMO_DISPATCH_N(KERNEL, E, stream, args, (E)->N)
-#define SUMO_DISPATCH_N(KERNEL, E, stream, args, nblocks)                                                   \
-  do {                                                                                                       \
-    dim3 g_(nblocks), b_(WAVE);                                                                              \
-    size_t lds_ = (size_t)(E)->L.total_bytes;                                                                \
-    if (!for_kernel_variant((E)->hm.nv, [&](auto nvc_) {                                                     \
-          hipLaunchKernelGGL(KERNEL<decltype(nvc_)::value>, g_, b_, lds_, stream, (E)->d_params, args);      \
-        }))                                                                                                  \
-      FAIL(-19, "no kernel variant for nv=%d", (E)->hm.nv);                                                  \
-  } while (0)
-
-static StepArgs base_args(sumo_engine* E) {
-  StepArgs a;
-  memset(&a, 0, sizeof a);
-  a.state = E->d_state; a.counters = E->d_counters; a.seeds = E->d_seeds; a.state_stride = E->state_stride;
-  a.stats = E->d_stats; a.obs_stride = E->obs_stride; a.act_stride = E->act_stride; a.N = E->N;
-  a.dbg_fault_env = -1;
-  a.dbg_qacc = E->dbg_dump;
-  return a;
-}
-
-extern "C" int sumo_reset(sumo_handle_t E, const uint64_t* seeds_host, const uint8_t* mask_dev, float* obs_dev, void* stream) {
-  if (!E) FAIL(-1, "bad handle");
-  HIPCHK(hipSetDevice(E->device));
-  hipStream_t s = (hipStream_t)stream;
-  if (seeds_host) {
-    HIPCHK(hipMemcpyAsync(E->d_seeds, seeds_host, (size_t)E->N * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(E->d_counters, 0, (size_t)E->N * 4 * sizeof(int), s));
-  }
-  StepArgs a = base_args(E);
-  a.mask = mask_dev; a.obs = obs_dev;
-  SUMO_DISPATCH(sumo_reset_kernel, E, s, a);
-  HIPCHK(hipGetLastError());
-  if (seeds_host) HIPCHK(hipStreamSynchronize(s));  // seeds_host may be freed by the caller after return
-  return 0;
-}
-
-extern "C" int sumo_step(sumo_handle_t E, const float* actions_dev, float* obs_dev, double* info_dev, uint8_t* done_dev,
-                         double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
-  if (!E || !actions_dev || !obs_dev || !info_dev || !done_dev || !ep_r_dev || !ep_dr_dev || !ep_l_dev) FAIL(-1, "bad arguments");
-  HIPCHK(hipSetDevice(E->device));
-  StepArgs a = base_args(E);
-  a.actions = actions_dev; a.obs = obs_dev; a.info = info_dev; a.done = done_dev; a.ep_r = ep_r_dev; a.ep_dr = ep_dr_dev;
-  a.ep_l = ep_l_dev;
-  // Env steps differ in cost (Newton iterations, contacts) by up to ~1.6x and a launch is only N / (6 * 256) rounds deep, so
-  // the slowest workgroups of the last round set the launch time.  Workgroups are dispatched in index order: hand the
-  // envs out longest-first, using the work each env reported in its previous step (results do not depend on the order).
-  a.trace = E->d_trace;
-  int nblocks = E->N;
-  if (E->sched && E->N <= SCHED_RANK_MAX) {
-    // in-kernel ranking (sched_rank): launch t writes its estimates to cost[t & 1]; its first workgroups rank cost[(t-1) & 1]
-    // into perm[(t+1) & 1]; it is itself scheduled by perm[t & 1], ranked during launch t-1 from the estimates of launch t-2
-    const long long t = E->sched_t++;
-    a.cost = E->d_cost + (size_t)(t & 1) * E->N;
-    a.perm = t >= 2 ? E->d_perm + (size_t)(t & 1) * E->N : nullptr;
-    if (t >= 1) {
-      a.rank_cost = E->d_cost + (size_t)((t - 1) & 1) * E->N;
-      a.rank_perm = E->d_perm + (size_t)((t + 1) & 1) * E->N;
-      a.rank_blocks = (E->N + WAVE - 1) / WAVE;
-      nblocks += a.rank_blocks;
-    }
-  } else if (E->sched) {
-    a.cost = E->d_cost; a.perm = E->perm_valid ? E->d_perm : nullptr;
-  }
-  if (E->cfrc_mode)   // rne_post: the state this step starts from, for the second launch below
-    HIPCHK(hipMemcpyAsync(E->d_state_prev, E->d_state, (size_t)E->N * E->state_stride * sizeof(double), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  if (!for_engine_variant(E, [&](auto nvc_, auto slc_) {
-        hipLaunchKernelGGL((sumo_step_kernel<decltype(nvc_)::value, decltype(slc_)::value>), dim3(nblocks), dim3(WAVE), (size_t)E->L.total_bytes,
-                           (hipStream_t)stream, E->d_params, a);
-      }))
-    FAIL(-19, "no kernel variant for nv=%d", E->hm.nv);
-  HIPCHK(hipGetLastError());
-  if (E->cfrc_mode) {
-    CfrcArgs q;
-    q.prev_state = E->d_state_prev; q.fbuf = E->d_fbuf; q.cfrc_out = E->d_cfrc;
-    StepArgs ac = base_args(E);
-    ac.actions = actions_dev; ac.obs = obs_dev; ac.done = done_dev;
-    dim3 g_(E->N), b_(WAVE);
-    size_t lds_ = (size_t)E->L.total_bytes;
-    hipStream_t st_ = (hipStream_t)stream;
-    if (!for_kernel_variant(E->hm.nv, [&](auto nvc_) {
-          hipLaunchKernelGGL(sumo_cfrc_kernel<decltype(nvc_)::value>, g_, b_, lds_, st_, E->d_params, ac, q);
-        }))
-      FAIL(-19, "no kernel variant for nv=%d", E->hm.nv);
-    HIPCHK(hipGetLastError());
-  }
-  if (E->sched && E->N > SCHED_RANK_MAX) {   // costs stay below 2^16 (see the step kernel's epilogue)
-    HIPCHK(rocprim::radix_sort_pairs_desc(E->d_sort_tmp.get(), E->sort_tmp_bytes, E->d_cost.get(), E->d_cost_sorted.get(), E->d_iota.get(),
-                                          E->d_perm.get(), (size_t)E->N, 0, 16, (hipStream_t)stream));
-    E->perm_valid = true;
-  }
-  return 0;
-}
-
-// the env-side buffers of sumo_step, as every fused entry point receives them
-struct EnvBuffers {
-  float *actions, *obs;
-  double* info;
-  uint8_t* done;
-  double *ep_r, *ep_dr;
-  int32_t* ep_l;
-};
-static int check_launch_args(sumo_engine* E, const void* launch, const EnvBuffers& b) {
-  if (!E || !launch || !b.actions || !b.obs || !b.info || !b.done || !b.ep_r || !b.ep_dr || !b.ep_l) FAIL(-1, "bad arguments");
-  return 0;
-}
-
-// the instantiation of sumo_rollout_kernel for `policy`, from a table of all of them
-typedef void (*RolloutKernel)(const Params*, RolloutLaunch);
-template <int NV, int SL, int... POLICY>
-static RolloutKernel rollout_kernel(int policy, std::integer_sequence<int, POLICY...>) {
-  static const RolloutKernel table[] = {sumo_rollout_kernel<NV, POLICY, SL>...};
-  return table[policy];
-}
-
-// common tail of the fused entry points: scheduler state, persistent grid, launch
-static int rollout_launch(sumo_engine* E, const RolloutArgs& r, int policy, const EnvBuffers& b, void* stream) {
-  RolloutLaunch rl;
-  rl.a = base_args(E);
-  StepArgs& a = rl.a;
-  a.actions = b.actions; a.obs = b.obs; a.info = b.info; a.done = b.done; a.ep_r = b.ep_r; a.ep_dr = b.ep_dr; a.ep_l = b.ep_l;
-  rl.r = r;
-  rl.r.prof = E->d_trace;   // development: sumo_debug_trace(stamps) switches the per-wave phase clock on
-  hipStream_t st_ = (hipStream_t)stream;
-  if (!E->d_rsched) HIPCHK(E->d_rsched.alloc((size_t)(2 + E->N)));
-  HIPCHK(hipMemsetAsync(E->d_rsched, 0, (size_t)(2 + E->N) * sizeof(int), st_));
-  rl.r.sched = E->d_rsched;
-  if (r.K >= 65536) FAIL(-5, "K = %d: at most 65535 steps per fused launch", r.K);
-  E->rollout_seq++;
-  a.seq_base = (int)((E->rollout_seq & 0x7FFFu) << 16);
-  a.abort_flag = E->d_rsched + 1;
-  a.dbg_fault_env = E->dbg_fault_env;
-  E->rollout_stream = st_;
-  E->rollout_tickets = (long long)E->N * r.K;
-  // persistent waves: as many as the chip holds at this kernel's LDS footprint (8 per CU at most: two per SIMD)
-  int slots = (int)((size_t)160 * 1024 / (size_t)E->L.total_bytes);
-  if (slots > 4 * SUMO_WPE_OF(E->hm.nv)) slots = 4 * SUMO_WPE_OF(E->hm.nv);
-  if (slots < 1) slots = 1;
-  if (E->num_cus <= 0) {
-    hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, E->device));
-    E->num_cus = prop.multiProcessorCount;
-  }
-  long long nw = (long long)slots * E->num_cus;
-  if (nw > (long long)E->N) nw = E->N;   // more waves than envs would only wait on each other's steps
-  dim3 g_((unsigned)nw), b_(WAVE);
-  size_t lds_ = (size_t)E->L.total_bytes;
-  if (!for_engine_variant(E, [&](auto nvc_, auto slc_) {
-        constexpr int NV = decltype(nvc_)::value, SL = decltype(slc_)::value;
-        const RolloutKernel kernel = rollout_kernel<NV, SL>(policy, std::make_integer_sequence<int, SUMO_N_POLICY>{});
-        hipLaunchKernelGGL(kernel, g_, b_, lds_, st_, E->d_params, rl);
-      }))
-    FAIL(-19, "no kernel variant for nv=%d", E->hm.nv);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-// scene checks shared by the entry points; returns the observation / action width through od / ad
-static int rollout_scene(sumo_engine* E, int T, int Ntot, int env_offset, int s0, int K, int* od, int* ad) {
-  const sumo_model_t* m = &E->hm;
-  if (E->cfrc_mode) FAIL(-12, "cfrc_mode rne_post fills the observations in a second launch per step: use sumo_step (the fused rollout evaluates the policies inside its launch)");
-  const int* anq = SUMO_I(m, agent_nq); const int* anv = SUMO_I(m, agent_nv); const int* anb = SUMO_I(m, agent_nbody);
-  const int* anu = SUMO_I(m, agent_nu);
-  const int od0 = anq[0] + anv[0] + 6 * anb[0] + 14, od1 = anq[1] + anv[1] + 6 * anb[1] + 14;
-  if (od0 != od1 || anu[0] != anu[1]) FAIL(-3, "fused rollout needs a homogeneous match-up (one observation / action space for both sides, runner.py:14-16)");
-  if (T < 1 || K < 1 || s0 < 0 || s0 + K > T) FAIL(-5, "steps [%d, %d) outside the rollout buffers (T = %d)", s0, s0 + K, T);
-  if (env_offset < 0 || env_offset + E->N > Ntot) FAIL(-6, "envs [%d, %d) outside the rollout buffers (N = %d)", env_offset, env_offset + E->N, Ntot);
-  *od = od0; *ad = anu[0];
-  return 0;
-}
-
-static int check_dims(int ob_dim, int ac_dim, int od, int ad) {
-  if (ob_dim != od || ac_dim != ad || ac_dim > PT_MAXA) FAIL(-4, "ob_dim %d / ac_dim %d do not match the scene (%d / %d)", ob_dim, ac_dim, od, ad);
-  return 0;
-}
-
-// what the in-wave recurrent evaluation is built for: the nets `learn(network='lstm')` trains (policy-zoo LSTM nets carry an
-// observation filter, an embedding and the other gate order: they play as agent 1 of the match modes 6 / 7, zoo_lstm_act)
-static int check_lstm_shape(const ppo_lstm_net& n, const char* what) {
-  if (n.hidden != 128 || n.gate_order != PPO_LSTM_GATES_IFOU || n.emb_w || n.emb_dim != 0 || n.obs_mean || n.obs_invstd)
-    FAIL(-9, "fused recurrent %s: hidden 128, gate order i,f,o,u, no embedding, no observation filter (got hidden %d, order %d, emb %d)", what, n.hidden, n.gate_order, n.emb_dim);
-  return 0;
-}
-
-// MLP phases: x [2][XS] and the two hidden tiles go where the mass matrix lives between two steps.  valu_nets > 0 (modes 0 and 2:
-// that many trunks in one pass of mlp_rows_valu): x rows and the activation rows [valu_nets][2][PT_VS] 16-byte aligned for the
-// 128-bit LDS reads, the x rows zero-padded to a multiple of four columns
-static int place_mlp_scratch(sumo_engine* E, int ob_dim, int ac_dim, RolloutArgs& r, int valu_nets = 0) {
-  r.XS = valu_nets ? (ob_dim + 3) & ~3 : x_stride(ob_dim); r.L = make_layout(ob_dim, ac_dim);
-  r.lds_off = valu_nets ? (E->L.M + 1) & ~1 : E->L.M;
-  const size_t need = (size_t)(2 * r.XS + (valu_nets ? valu_nets * 2 * PT_VS : 4 * PT_HS)) * sizeof(float);
-  const size_t have = (size_t)(E->L.M + E->L.msize - r.lds_off) * sizeof(double);
-  if (need > have) FAIL(-8, "policy scratch (%zu B) does not fit the mass-matrix region (%zu B)", need, have);
-  return 0;
-}
-
-// LSTM phases: x [2][XS] and `rows` rows of 128 floats.  Between two steps of an env nothing from the mass matrix to the end of the
-// float64 area is live (contact records, Jacobian pool and row arrays are rebuilt by every forward): the rows go there, 16-byte
-// aligned for the 128-bit LDS reads
-static int place_lstm_scratch(sumo_engine* E, int od, int rows, RolloutArgs& r) {
-  r.XS = (od + 3) & ~3;
-  r.lds_off = (E->L.M + 1) & ~1;
-  const size_t need = (size_t)(2 * r.XS + rows * 128) * sizeof(float), have = (size_t)(E->L.i_base - r.lds_off) * sizeof(double);
-  if (E->L.ctrl >= E->L.M || E->L.stash >= E->L.M || need > have) FAIL(-8, "policy scratch (%zu B) does not fit the per-step LDS area (%zu B)", need, have);
-  return 0;
-}
-
-// the fields sumo_rollout and sumo_rollout_lstm share
-template <class RO>
-static bool rollout_buffer_missing(const RO* ro) {
-  return !ro->noise0 || !ro->noise1 || !ro->obs || !ro->act || !ro->rew || !ro->val || !ro->nlp || !ro->onlp || !ro->done || !ro->ep_done ||
-         !ro->ep_r || !ro->ep_l;
-}
-template <class RO>
-static void copy_rollout_fields(RolloutArgs& r, const RO* ro) {
-  r.noise0 = ro->noise0; r.noise1 = ro->noise1;
-  r.obs = ro->obs; r.act = ro->act; r.rew = ro->rew; r.val = ro->val; r.nlp = ro->nlp; r.onlp = ro->onlp; r.done = ro->done;
-  r.ep_done = ro->ep_done; r.ep_r = ro->ep_r; r.ep_l = ro->ep_l; r.alpha = ro->alpha;
-  r.T = ro->T; r.Ntot = ro->Ntot; r.env_offset = ro->env_offset; r.s0 = ro->s0; r.K = ro->K;
-}
-
-// the fields sumo_match and sumo_match_lstm share: their checks (`name`: the struct in the messages) and the copy
-template <class MO>
-static int check_match_buffers(const MO* mo, const char* name) {
-  if (!mo->idx0 || !mo->idx1 || !mo->score) FAIL(-2, "%s: missing buffer", name);
-  if (!mo->noise0 != !mo->noise1) FAIL(-2, "%s: noise0 and noise1 are both given (stochastic play) or both NULL (deterministic)", name);
-  return 0;
-}
-template <class MO>
-static int check_match_counts(const MO* mo) {
-  if (mo->nsnap < 1) FAIL(-7, "nsnap %d: the snapshot table needs at least one entry", mo->nsnap);
-  if (mo->quota < 0) FAIL(-9, "quota %d", mo->quota);
-  return 0;
-}
-template <class MO>
-static void copy_match_fields(RolloutArgs& r, const MO* mo, int N) {
-  r.idx0 = mo->idx0; r.idx1 = mo->idx1; r.score = mo->score; r.nsnap = mo->nsnap; r.quota = mo->quota;
-  r.noise0 = mo->noise0; r.noise1 = mo->noise1;
-  r.T = mo->T; r.Ntot = N; r.s0 = mo->s0; r.K = mo->K;
-}
-
-// ---- what the fused entry points share.  check_*: a family's buffer, scene and dimension checks, in the order every mode of the
-// family reports them (a zoo mode's own count checks follow in the entry point); begin_*: device and the family's fields, into a
-// zeroed RolloutArgs.  `zoo`: the entry point's name in a zoo mode (which refuses the fields that only play without a zoo), else NULL ----
-// MLP(64,64) learner (modes 0, 4, 8, 11)
-static int check_mlp_rollout(sumo_engine* E, const sumo_rollout* ro, const char* zoo, bool league, int* od, int* ad) {
-  if (!ro->learner_params || (!zoo && !ro->opponent_params) || rollout_buffer_missing(ro)) FAIL(-2, "sumo_rollout: missing buffer");
-  if (zoo && !league && ro->opponent_params) FAIL(-2, "%s: opponent_params must be NULL (the opponents are the zoo table's nets)", zoo);
-  if (league && (ro->opponent_params || ro->opponent_index))
-    FAIL(-2, "%s: opponent_params and opponent_index must be NULL (the opponents are the league's nets, selected per tile by tile_entry_dev)", zoo);
-  if (int rc = rollout_scene(E, ro->T, ro->Ntot, ro->env_offset, ro->s0, ro->K, od, ad)) return rc;
-  return check_dims(ro->ob_dim, ro->ac_dim, *od, *ad);
-}
-static int begin_mlp_rollout(sumo_engine* E, const sumo_rollout* ro, RolloutArgs& r) {
-  HIPCHK(hipSetDevice(E->device));
-  r.learner = ro->learner_params; r.opponent = ro->opponent_params; r.opp_idx = ro->opponent_index;
-  copy_rollout_fields(r, ro);
-  return 0;
-}
-
-// LSTM(128) learner (modes 1, 9, 10, 12).  nzoo: the size of the zoo mode's table or league.  begin_lstm_rollout also places the
-// scratch: x [2][XS] and `rows` rows of 128 floats
-static int check_lstm_rollout(sumo_engine* E, const sumo_rollout_lstm* ro, const char* zoo, int nzoo, int* od, int* ad) {
-  if (!ro->learner || !ro->state0 || (!zoo && (!ro->opponents_dev || !ro->state1)) || rollout_buffer_missing(ro)) FAIL(-2, "sumo_rollout_lstm: missing buffer");
-  if (zoo && (ro->opponents_dev || ro->state1))
-    FAIL(-2, "%s: opponents_dev and state1 must be NULL (the opponents are the zoo table's nets, agent 1's state is the table's)", zoo);
-  if (int rc = rollout_scene(E, ro->T, ro->Ntot, ro->env_offset, ro->s0, ro->K, od, ad)) return rc;
-  const ppo_lstm_net& n = *ro->learner;
-  if (int rc = check_dims(n.ob_dim, n.ac_dim, *od, *ad)) return rc;
-  if (int rc = check_lstm_shape(n, "rollout")) return rc;
-  if (!n.wx || !n.wh || !n.b || !n.head_w || !n.head_b || !n.logstd || !n.vf_w || !n.vf_b) FAIL(-10, "learner net: missing weights");
-  if (!zoo && ro->npool < 1) FAIL(-7, "npool %d", ro->npool);
-  if (zoo && ro->npool != nzoo) FAIL(-7, "npool %d must equal the zoo table's nzoo %d", ro->npool, nzoo);
-  if (ro->tile_net_dev && ((ro->env_offset & 15) || (E->N & 15)))
-    FAIL(-11, "a %s per 16-env tile needs env_offset (%d) and the env count (%d) to be multiples of 16", zoo ? "zoo net" : "snapshot", ro->env_offset, E->N);
-  return 0;
-}
-static int begin_lstm_rollout(sumo_engine* E, const sumo_rollout_lstm* ro, int od, int rows, RolloutArgs& r) {
-  HIPCHK(hipSetDevice(E->device));
-  r.lnet = *ro->learner; r.onets = ro->opponents_dev; r.tile_net = ro->tile_net_dev; r.st0 = ro->state0; r.st1 = ro->state1;
-  copy_rollout_fields(r, ro);
-  return place_lstm_scratch(E, od, rows, r);
-}
-// the rows of a recurrent learner's zoo modes: zero row, agent 0's previous latent, two new latents, which the zoo net's hidden
-// tiles / cell rows reuse
-constexpr int LSTM_ZOO_ROWS = 4;
-static_assert(4 * PT_HS <= LSTM_ZOO_ROWS * 128, "modes 9 / 12: the zoo trunk's two hidden tiles [2][PT_HS] go where the learner's latent rows were");
-
-// MLP(64,64) checkpoints as agent 0, or on both sides (modes 2, 5, 6): nothing of a mode's own comes between checks and fields
-static int begin_mlp_match(sumo_engine* E, const sumo_match* mo, int* od, int* ad, RolloutArgs& r) {
-  if (!mo->params) FAIL(-2, "sumo_match: missing buffer");
-  if (int rc = check_match_buffers(mo, "sumo_match")) return rc;
-  if (int rc = rollout_scene(E, mo->T, E->N, 0, mo->s0, mo->K, od, ad)) return rc;
-  if (int rc = check_dims(mo->ob_dim, mo->ac_dim, *od, *ad)) return rc;
-  if (int rc = check_match_counts(mo)) return rc;
-  HIPCHK(hipSetDevice(E->device));
-  r.snaps = mo->params;
-  copy_match_fields(r, mo, E->N);
-  return 0;
-}
-
-// LSTM(128) checkpoints (modes 3, 7, 13, 14), with the scratch: x [2][XS] | `rows` rows of 128 floats (previous latent | new latent)
-static int begin_lstm_match(sumo_engine* E, const sumo_match_lstm* mo, const char* zoo, int* od, int* ad, RolloutArgs& r, int rows = 2) {
-  if (!mo->proto || !mo->nets_dev) FAIL(-2, "sumo_match_lstm: missing buffer");
-  if (!mo->state0 || (!zoo && !mo->state1)) FAIL(-2, "sumo_match_lstm: missing state buffer (%s)", zoo ? "state0" : "state0 / state1");
-  if (zoo && mo->state1) FAIL(-2, "%s: state1 must be NULL (agent 1's state is the zoo table's state)", zoo);
-  if (int rc = check_match_buffers(mo, "sumo_match_lstm")) return rc;
-  if (int rc = rollout_scene(E, mo->T, E->N, 0, mo->s0, mo->K, od, ad)) return rc;
-  const ppo_lstm_net& n = *mo->proto;
-  if (int rc = check_dims(n.ob_dim, n.ac_dim, *od, *ad)) return rc;
-  if (int rc = check_lstm_shape(n, "matches")) return rc;   // the nets sumo_rollout_steps_lstm plays
-  if (!n.wx || !n.wh || !n.b || !n.head_w || !n.head_b || !n.logstd) FAIL(-10, "prototype net: missing weights");
-  if (int rc = check_match_counts(mo)) return rc;
-  HIPCHK(hipSetDevice(E->device));
-  r.lnet = n; r.onets = mo->nets_dev; r.st0 = mo->state0; r.st1 = mo->state1;
-  copy_match_fields(r, mo, E->N);
-  return place_lstm_scratch(E, *od, rows, r);
-}
-// the rows of modes 13 / 14: the recurrent side's two latent rows, then the two hidden tiles of the MLP / zoo trunk in their place
-constexpr int LSTM_MLP_MATCH_ROWS = 3;
-static_assert(4 * PT_HS <= LSTM_MLP_MATCH_ROWS * 128 && 2 * 128 <= LSTM_MLP_MATCH_ROWS * 128, "modes 13 / 14: the larger of the latent rows and the hidden tiles [2][PT_HS] twice");
-
-// ---- the zoo tables: checks, then RolloutArgs::zm / zl ----
-static int place_zoo_mlp_table(RolloutArgs& r, const sumo_zoo_mlp* z, int od, int ad) {
-  if (!z->params || !z->filt) FAIL(-2, "sumo_zoo_mlp: missing buffer (params / filt)");
-  if (z->nzoo < 1) FAIL(-7, "nzoo %d: the zoo table needs at least one entry", z->nzoo);
-  if (z->ob_dim < 1 || z->ob_dim > od)
-    FAIL(-4, "zoo ob_dim %d outside [1, %d]: a policy-zoo MLP net reads the first ob_dim columns of the scene's observation", z->ob_dim, od);
-  if (!(z->obs_clip > 0.0f)) FAIL(-9, "obs_clip %g must be positive", (double)z->obs_clip);
-  r.zm.params = z->params; r.zm.filt = z->filt; r.zm.clip = z->obs_clip; r.zm.n = z->nzoo; r.zm.D = z->ob_dim;
-  r.zm.L = make_layout(z->ob_dim, ad);
-  return 0;
-}
-// (after the scratch is placed: the cell's rows -- embedding | previous latent | new latent, 64 floats each -- go behind the
-// observation tile, 16-byte aligned, into the `rows_floats` floats the placed scratch holds there.  The table's state is agent 1's.)
-static int place_zoo_lstm_table(RolloutArgs& r, const sumo_zoo_lstm* z, int od, int ad, int rows_floats) {
-  if (!z->params || !z->filt) FAIL(-2, "sumo_zoo_lstm: missing buffer (params / filt)");
-  if (!z->state) FAIL(-2, "sumo_zoo_lstm: missing state buffer (state)");
-  if (z->nzoo < 1) FAIL(-7, "nzoo %d: the zoo table needs at least one entry", z->nzoo);
-  if (z->ob_dim < 1 || z->ob_dim > od)
-    FAIL(-4, "zoo ob_dim %d outside [1, %d]: a policy-zoo LSTM net reads the first ob_dim columns of the scene's observation", z->ob_dim, od);
-  if (z->emb_dim != PT_H || z->hidden != 64) FAIL(-4, "zoo LSTM emb_dim %d / hidden %d: the fused launch is built for 64 / 64", z->emb_dim, z->hidden);
-  if (!(z->obs_clip > 0.0f)) FAIL(-9, "obs_clip %g must be positive", (double)z->obs_clip);
-  ZooLstmTable& q = r.zl;
-  q.params = z->params; q.filt = z->filt; q.clip = z->obs_clip; q.forget_bias = z->forget_bias; q.n = z->nzoo; q.D = z->ob_dim; q.A = ad;
-  q.emb = z->emb_dim;
-  q.P = z->ob_dim * PT_H + PT_H + 2 * 64 * 256 + 256 + 64 * ad + 2 * ad;
-  r.st1 = z->state;
-  const int tile = 2 * r.XS;
-  q.sc_off = tile;
-  while ((2 * r.lds_off + q.sc_off) & 3) q.sc_off++;   // lds_off counts doubles from the 16-byte aligned LDS base
-  if (q.sc_off + 3 * 64 > tile + rows_floats)
-    FAIL(-8, "zoo LSTM scratch (observation tile + embedding and latent rows, %zu B) does not fit the policy scratch (%zu B)",
-         (size_t)(q.sc_off + 3 * 64) * sizeof(float), (size_t)(tile + rows_floats) * sizeof(float));
-  return 0;
-}
-// a league: the launch's checks of the struct (before the device is touched), then -- after the scratch is placed -- both tables
-// and the entry of every tile
-static int check_zoo_league(sumo_engine* E, const sumo_zoo_league* z, int npool, int env_offset) {
-  if (z->mlp.nzoo < 1 || z->lstm.nzoo < 1)
-    FAIL(-7, "sumo_zoo_league: nzoo %d (MLP table) / %d (LSTM table): a mixed league needs at least one net of each family (a league of one family plays through that family's launch)", z->mlp.nzoo, z->lstm.nzoo);
-  if (npool != z->mlp.nzoo + z->lstm.nzoo) FAIL(-7, "npool %d must equal the league's size %d + %d", npool, z->mlp.nzoo, z->lstm.nzoo);
-  if (z->tile_entry_dev && ((env_offset & 15) || (E->N & 15))) FAIL(-11, "a league entry per 16-env tile needs env_offset (%d) and the env count (%d) to be multiples of 16", env_offset, E->N);
-  return 0;
-}
-static int place_zoo_league(RolloutArgs& r, const sumo_zoo_league* z, int od, int ad, int rows_floats) {
-  if (int rc = place_zoo_mlp_table(r, &z->mlp, od, ad)) return rc;
-  if (int rc = place_zoo_lstm_table(r, &z->lstm, od, ad, rows_floats)) return rc;
-  r.tile_net = z->tile_entry_dev;
-  return 0;
-}
-
-// ---- the sixteen entry points: env buffers, the family's checks (and the mode's), begin_*, the scratch of the learner's /
-// checkpoints' side, the opponent table, launch.  Where a zoo MLP table comes before the scratch and a zoo LSTM table after it, that
-// is the order in which the mode reports their errors. ----
-extern "C" int sumo_rollout_steps(sumo_handle_t E, const sumo_rollout* ro, float* actions_dev, float* obs_dev, double* info_dev,
-                                  uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
-  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
-  RolloutArgs r = {};
-  int od = 0, ad = 0;
-  if (int rc = check_launch_args(E, ro, b)) return rc;
-  if (int rc = check_mlp_rollout(E, ro, NULL, false, &od, &ad)) return rc;
-  if (ro->npool < 1) FAIL(-7, "npool %d", ro->npool);
-  if (int rc = begin_mlp_rollout(E, ro, r)) return rc;
-  if (int rc = place_mlp_scratch(E, ro->ob_dim, ro->ac_dim, r, 3)) return rc;
-  return rollout_launch(E, r, 0, b, stream);
-}
-
-extern "C" int sumo_rollout_steps_lstm(sumo_handle_t E, const sumo_rollout_lstm* ro, float* actions_dev, float* obs_dev, double* info_dev,
-                                       uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
-  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
-  RolloutArgs r = {};
-  int od = 0, ad = 0;
-  if (int rc = check_launch_args(E, ro, b)) return rc;
-  if (int rc = check_lstm_rollout(E, ro, NULL, 0, &od, &ad)) return rc;
-  if (int rc = begin_lstm_rollout(E, ro, od, 7, r)) return rc;   // zero row, previous latents [3], new latents [3]
-  return rollout_launch(E, r, 1, b, stream);
-}
-
-extern "C" int sumo_rollout_steps_lstm_reuse(sumo_handle_t E, const sumo_rollout_lstm_reuse* rr, float* actions_dev, float* obs_dev, double* info_dev,
-                                             uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
-  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
-  RolloutArgs r = {};
-  int od = 0, ad = 0;
-  if (int rc = check_launch_args(E, rr, b)) return rc;
-  const sumo_rollout_lstm* ro = &rr->ro;
-  if (!rr->state2) FAIL(-2, "sumo_rollout_lstm_reuse: missing buffer (state2)");
-  if (int rc = check_lstm_rollout(E, ro, NULL, 0, &od, &ad)) return rc;
-  if (int rc = begin_lstm_rollout(E, ro, od, 7, r)) return rc;   // the region of sumo_rollout_steps_lstm (one new latent row unused)
-  r.st2 = rr->state2;
-  return rollout_launch(E, r, 15, b, stream);
-}
-
-extern "C" int sumo_match_steps(sumo_handle_t E, const sumo_match* mo, float* actions_dev, float* obs_dev, double* info_dev,
-                                uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
-  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
-  RolloutArgs r = {};
-  int od = 0, ad = 0;
-  if (int rc = check_launch_args(E, mo, b)) return rc;
-  if (int rc = begin_mlp_match(E, mo, &od, &ad, r)) return rc;
-  if (int rc = place_mlp_scratch(E, mo->ob_dim, mo->ac_dim, r, 2)) return rc;
-  return rollout_launch(E, r, 2, b, stream);
-}
-
-extern "C" int sumo_match_steps_lstm(sumo_handle_t E, const sumo_match_lstm* mo, float* actions_dev, float* obs_dev, double* info_dev,
-                                     uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
-  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
-  RolloutArgs r = {};
-  int od = 0, ad = 0;
-  if (int rc = check_launch_args(E, mo, b)) return rc;
-  if (int rc = begin_lstm_match(E, mo, NULL, &od, &ad, r)) return rc;
-  return rollout_launch(E, r, 3, b, stream);
-}
-
-extern "C" int sumo_rollout_steps_zoo(sumo_handle_t E, const sumo_rollout* ro, const sumo_zoo_mlp* z, float* actions_dev, float* obs_dev,
-                                      double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
-  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
-  RolloutArgs r = {};
-  int od = 0, ad = 0;
-  if (int rc = check_launch_args(E, ro, b)) return rc;
-  if (!z) FAIL(-1, "bad arguments");
-  if (int rc = check_mlp_rollout(E, ro, "sumo_rollout_steps_zoo", false, &od, &ad)) return rc;
-  if (ro->npool != z->nzoo) FAIL(-7, "npool %d must equal the zoo table's nzoo %d", ro->npool, z->nzoo);
-  if (int rc = begin_mlp_rollout(E, ro, r)) return rc;
-  if (int rc = place_zoo_mlp_table(r, z, od, ad)) return rc;
-  if (int rc = place_mlp_scratch(E, ro->ob_dim, ro->ac_dim, r)) return rc;
-  return rollout_launch(E, r, 4, b, stream);
-}
-
-extern "C" int sumo_match_steps_zoo(sumo_handle_t E, const sumo_match* mo, const sumo_zoo_mlp* z, float* actions_dev, float* obs_dev,
-                                    double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
-  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
-  RolloutArgs r = {};
-  int od = 0, ad = 0;
-  if (int rc = check_launch_args(E, mo, b)) return rc;
-  if (!z) FAIL(-1, "bad arguments");
-  if (int rc = begin_mlp_match(E, mo, &od, &ad, r)) return rc;
-  if (int rc = place_zoo_mlp_table(r, z, od, ad)) return rc;
-  if (int rc = place_mlp_scratch(E, mo->ob_dim, mo->ac_dim, r)) return rc;
-  return rollout_launch(E, r, 5, b, stream);
-}
-
-extern "C" int sumo_match_steps_zoo_lstm(sumo_handle_t E, const sumo_match* mo, const sumo_zoo_lstm* z, float* actions_dev, float* obs_dev,
-                                         double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
-  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
-  RolloutArgs r = {};
-  int od = 0, ad = 0;
-  if (int rc = check_launch_args(E, mo, b)) return rc;
-  if (!z) FAIL(-1, "bad arguments");
-  if (int rc = begin_mlp_match(E, mo, &od, &ad, r)) return rc;
-  if (int rc = place_mlp_scratch(E, mo->ob_dim, mo->ac_dim, r)) return rc;
-  if (int rc = place_zoo_lstm_table(r, z, od, ad, 4 * PT_HS)) return rc;   // the two hidden tiles of agent 0's trunk
-  return rollout_launch(E, r, 6, b, stream);
-}
-
-extern "C" int sumo_match_steps_lstm_zoo_lstm(sumo_handle_t E, const sumo_match_lstm* mo, const sumo_zoo_lstm* z, float* actions_dev,
-                                              float* obs_dev, double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev,
-                                              int32_t* ep_l_dev, void* stream) {
-  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
-  RolloutArgs r = {};
-  int od = 0, ad = 0;
-  if (int rc = check_launch_args(E, mo, b)) return rc;
-  if (!z) FAIL(-1, "bad arguments");
-  if (int rc = begin_lstm_match(E, mo, "sumo_match_steps_lstm_zoo_lstm", &od, &ad, r)) return rc;
-  if (int rc = place_zoo_lstm_table(r, z, od, ad, 2 * 128)) return rc;   // agent 0's previous and new latent
-  return rollout_launch(E, r, 7, b, stream);
-}
-
-extern "C" int sumo_rollout_steps_zoo_lstm(sumo_handle_t E, const sumo_rollout* ro, const sumo_zoo_lstm* z, float* actions_dev, float* obs_dev,
-                                           double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
-  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
-  RolloutArgs r = {};
-  int od = 0, ad = 0;
-  if (int rc = check_launch_args(E, ro, b)) return rc;
-  if (!z) FAIL(-1, "bad arguments");
-  if (int rc = check_mlp_rollout(E, ro, "sumo_rollout_steps_zoo_lstm", false, &od, &ad)) return rc;
-  if (ro->npool != z->nzoo) FAIL(-7, "npool %d must equal the zoo table's nzoo %d", ro->npool, z->nzoo);
-  if (int rc = begin_mlp_rollout(E, ro, r)) return rc;
-  if (int rc = place_mlp_scratch(E, ro->ob_dim, ro->ac_dim, r)) return rc;
-  if (int rc = place_zoo_lstm_table(r, z, od, ad, 4 * PT_HS)) return rc;   // the two hidden tiles of the learner's trunks
-  return rollout_launch(E, r, 8, b, stream);
-}
-
-extern "C" int sumo_rollout_steps_lstm_zoo(sumo_handle_t E, const sumo_rollout_lstm* ro, const sumo_zoo_mlp* z, float* actions_dev, float* obs_dev,
-                                           double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
-  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
-  RolloutArgs r = {};
-  int od = 0, ad = 0;
-  if (int rc = check_launch_args(E, ro, b)) return rc;
-  if (!z) FAIL(-1, "bad arguments");
-  if (int rc = check_lstm_rollout(E, ro, "sumo_rollout_steps_lstm_zoo", z->nzoo, &od, &ad)) return rc;
-  if (int rc = place_zoo_mlp_table(r, z, od, ad)) return rc;                      // (needs no scratch: its errors come first)
-  if (int rc = begin_lstm_rollout(E, ro, od, LSTM_ZOO_ROWS, r)) return rc;
-  return rollout_launch(E, r, 9, b, stream);
-}
-
-extern "C" int sumo_rollout_steps_lstm_zoo_lstm(sumo_handle_t E, const sumo_rollout_lstm* ro, const sumo_zoo_lstm* z, float* actions_dev,
-                                                float* obs_dev, double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev,
-                                                int32_t* ep_l_dev, void* stream) {
-  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
-  RolloutArgs r = {};
-  int od = 0, ad = 0;
-  if (int rc = check_launch_args(E, ro, b)) return rc;
-  if (!z) FAIL(-1, "bad arguments");
-  if (int rc = check_lstm_rollout(E, ro, "sumo_rollout_steps_lstm_zoo_lstm", z->nzoo, &od, &ad)) return rc;
-  if (int rc = begin_lstm_rollout(E, ro, od, LSTM_ZOO_ROWS, r)) return rc;
-  if (int rc = place_zoo_lstm_table(r, z, od, ad, LSTM_ZOO_ROWS * 128)) return rc;   // the cell's rows go where the learner's latent rows were
-  return rollout_launch(E, r, 10, b, stream);
-}
-
-extern "C" int sumo_rollout_steps_zoo_league(sumo_handle_t E, const sumo_rollout* ro, const sumo_zoo_league* z, float* actions_dev, float* obs_dev,
-                                             double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
-  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
-  RolloutArgs r = {};
-  int od = 0, ad = 0;
-  if (int rc = check_launch_args(E, ro, b)) return rc;
-  if (!z) FAIL(-1, "bad arguments");
-  if (int rc = check_mlp_rollout(E, ro, "sumo_rollout_steps_zoo_league", true, &od, &ad)) return rc;
-  if (int rc = check_zoo_league(E, z, ro->npool, ro->env_offset)) return rc;
-  if (int rc = begin_mlp_rollout(E, ro, r)) return rc;
-  if (int rc = place_mlp_scratch(E, ro->ob_dim, ro->ac_dim, r)) return rc;   // the zoo trunk's hidden tiles are the learner's ...
-  if (int rc = place_zoo_league(r, z, od, ad, 4 * PT_HS)) return rc;         // ... and the cell's rows go there too, as in mode 8
-  return rollout_launch(E, r, 11, b, stream);
-}
-
-extern "C" int sumo_rollout_steps_lstm_zoo_league(sumo_handle_t E, const sumo_rollout_lstm* ro, const sumo_zoo_league* z, float* actions_dev,
-                                                  float* obs_dev, double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev,
-                                                  int32_t* ep_l_dev, void* stream) {
-  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
-  RolloutArgs r = {};
-  int od = 0, ad = 0;
-  if (int rc = check_launch_args(E, ro, b)) return rc;
-  if (!z) FAIL(-1, "bad arguments");
-  if (ro->tile_net_dev) FAIL(-2, "sumo_rollout_steps_lstm_zoo_league: tile_net_dev must be NULL (the league's tile_entry_dev selects the nets)");
-  if (int rc = check_lstm_rollout(E, ro, "sumo_rollout_steps_lstm_zoo_league", z->mlp.nzoo + z->lstm.nzoo, &od, &ad)) return rc;
-  if (int rc = check_zoo_league(E, z, ro->npool, ro->env_offset)) return rc;
-  if (int rc = begin_lstm_rollout(E, ro, od, LSTM_ZOO_ROWS, r)) return rc;   // the rows hold the larger of the two zoo passes (static_assert above)
-  if (int rc = place_zoo_league(r, z, od, ad, LSTM_ZOO_ROWS * 128)) return rc;
-  return rollout_launch(E, r, 12, b, stream);
-}
-
-extern "C" int sumo_match_steps_cross(sumo_handle_t E, const sumo_match_cross* mo, float* actions_dev, float* obs_dev, double* info_dev,
-                                      uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
-  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
-  RolloutArgs r = {};
-  int od = 0, ad = 0;
-  if (int rc = check_launch_args(E, mo, b)) return rc;
-  if (mo->lstm_side != 0 && mo->lstm_side != 1) FAIL(-9, "lstm_side %d: 0 (agent 0 plays the LSTM checkpoints) or 1", mo->lstm_side);
-  // each family's half of the struct goes through that family's checks: the one state buffer stands for both of sumo_match_lstm's
-  const sumo_match_lstm ml = {mo->proto, mo->nets_dev, mo->idx0, mo->idx1, mo->nsnap_lstm, mo->state, mo->state,
-                              mo->T, mo->s0, mo->K, mo->quota, mo->noise0, mo->noise1, mo->score};
-  const sumo_match mm = {mo->params, mo->idx0, mo->idx1, mo->nsnap_mlp, mo->ob_dim, mo->ac_dim,
-                         mo->T, mo->s0, mo->K, mo->quota, mo->noise0, mo->noise1, mo->score};
-  if (int rc = begin_lstm_match(E, &ml, NULL, &od, &ad, r, LSTM_MLP_MATCH_ROWS)) return rc;
-  r.nsnap_lstm = r.nsnap; r.lstm_side = mo->lstm_side;
-  if (int rc = begin_mlp_match(E, &mm, &od, &ad, r)) return rc;   // (leaves nsnap at the MLP table's size)
-  r.L = make_layout(mo->ob_dim, mo->ac_dim);
-  return rollout_launch(E, r, 13, b, stream);
-}
-
-extern "C" int sumo_match_steps_lstm_zoo(sumo_handle_t E, const sumo_match_lstm* mo, const sumo_zoo_mlp* z, float* actions_dev, float* obs_dev,
-                                         double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
-  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
-  RolloutArgs r = {};
-  int od = 0, ad = 0;
-  if (int rc = check_launch_args(E, mo, b)) return rc;
-  if (!z) FAIL(-1, "bad arguments");
-  if (int rc = begin_lstm_match(E, mo, "sumo_match_steps_lstm_zoo", &od, &ad, r, LSTM_MLP_MATCH_ROWS)) return rc;
-  if (int rc = place_zoo_mlp_table(r, z, od, ad)) return rc;
-  return rollout_launch(E, r, 14, b, stream);
-}
-
-#ifdef SUMO_POLICY_PROBE
-extern "C" int sumo_debug_tprobe(double* out8, int reset) {   // development: ticks (100 MHz) inside the five sections of trunk_forward
-  unsigned long long h[8];
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_tprobe), sizeof h));
-  for (int k = 0; k < 8; k++) out8[k] = (double)h[k];
-  if (reset) { memset(h, 0, sizeof h); HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_tprobe), h, sizeof h)); }
-  return 0;
-}
-#endif
-extern "C" int sumo_set_cfrc_mode(sumo_handle_t E, int mode) {
-  if (!E) FAIL(-1, "bad handle");
-  if (mode != 0 && mode != 1) FAIL(-2, "cfrc_mode %d: 0 (zero) or 1 (rne_post)", mode);
-  HIPCHK(hipSetDevice(E->device));
-  if (mode && !E->d_state_prev) {
-    HIPCHK(E->d_state_prev.alloc((size_t)E->N * E->state_stride));
-    HIPCHK(E->d_fbuf.alloc((size_t)E->N * 5 * E->L.maxcon));
-    HIPCHK(E->d_cfrc.alloc((size_t)E->N * 6 * E->hm.nbody));
-    HIPCHK(hipMemset(E->d_cfrc, 0, (size_t)E->N * 6 * E->hm.nbody * sizeof(double)));
-  }
-  E->cfrc_mode = mode;
-  return 0;
-}
-extern "C" int sumo_set_adjust_z(sumo_handle_t E, double adjust_z) {
-  if (!E) FAIL(-1, "bad handle");
-  if (!(fabs(adjust_z) <= 1e10)) FAIL(-2, "adjust_z must be finite");
-  HIPCHK(hipSetDevice(E->device));
-  HIPCHK(hipDeviceSynchronize());   // no launch of this engine may be reading the parameter block
-  HIPCHK(hipMemcpy((char*)E->d_params.get() + offsetof(Params, adjust_z), &adjust_z, sizeof(double), hipMemcpyHostToDevice));
-  E->adjust_z = adjust_z;
-  return 0;
-}
-extern "C" int sumo_get_cfrc_ext(sumo_handle_t E, double* out) {   // HOST float64 [E][nbody][6] of the last step (rne_post mode)
-  if (!E || !out) FAIL(-1, "bad arguments");
-  if (!E->d_cfrc) FAIL(-2, "cfrc_mode is zero: nothing was computed");
-  HIPCHK(hipSetDevice(E->device));
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(out, E->d_cfrc, (size_t)E->N * 6 * E->hm.nbody * sizeof(double), hipMemcpyDeviceToHost));
-  return 0;
-}
-extern "C" int sumo_rollout_status(sumo_handle_t E, int64_t* out4) {
-  if (!E) FAIL(-1, "bad handle");
-  long long o[4] = {0, 0, E->rollout_tickets < 0 ? 0 : E->rollout_tickets, 0};
-  if (E->rollout_tickets >= 0) {
-    HIPCHK(hipSetDevice(E->device));
-    HIPCHK(hipStreamSynchronize(E->rollout_stream));
-    int sc[2];
-    unsigned long long st[2];
-    HIPCHK(hipMemcpy(sc, E->d_rsched, sizeof sc, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(st, E->d_stats + 9, sizeof st, hipMemcpyDeviceToHost));
-    // the counters accumulate over launches: an earlier chunk's abort (whose flag the next launch's memset has cleared) still shows
-    const bool cut = sc[1] != 0 || st[0] + st[1] != E->acked_faults;
-    E->acked_faults = st[0] + st[1];
-    o[0] = cut; o[1] = sc[0]; o[3] = (long long)st[1];
-    if (out4) for (int i = 0; i < 4; i++) out4[i] = o[i];
-    if (cut)
-      FAIL(-20, "fused rollout launch was cut short (abort flag set: %llu expired hand-over waits, %llu hand-over tag / checksum mismatches "
-                "since creation; %d of %lld tickets were drawn): the rollout buffers hold unwritten rows and the env states are "
-                "partly advanced -- reset the envs before continuing", st[0], st[1], sc[0], E->rollout_tickets);
-  } else if (out4) for (int i = 0; i < 4; i++) out4[i] = o[i];
-  return 0;
-}
-// The three host-only exports (no device is touched) run sumo_create's own prepare_scene, up to the stage they report.
-// The Layout of a scene, as ints in declaration order; returns the count.  tools/gen_static_layout.py turns it into csrc/layout_static.h.
-extern "C" int sumo_debug_layout(const void* model_blob, size_t nbytes, int32_t* out, int cap) {
-  if (!model_blob || !out) FAIL(-1, "bad arguments");
-  Scene sc;
-  if (int rc = prepare_scene(sc, model_blob, nbytes, SCENE_LAYOUT)) return rc;
-  const int n = (int)(sizeof(Layout) / sizeof(int));
-  if (cap < n) FAIL(-2, "need room for %d ints", n);
-  memcpy(out, &sc.L, sizeof(Layout));
-  return n;
-}
-// The two packed role words of the 64 lanes (LaneRec::role0 / role1; the ROLE0_* / ROLE1_* fields), out[2 * lane], out[2 * lane + 1];
-// returns the count, or the error sumo_create gives for a scene whose roles do not fit.
-extern "C" int sumo_debug_lane_roles(const void* model_blob, size_t nbytes, uint32_t* out, int cap) {
-  if (!model_blob || !out) FAIL(-1, "bad arguments");
-  Scene sc;
-  if (int rc = prepare_scene(sc, model_blob, nbytes, SCENE_ROLES)) return rc;
-  if (cap < 2 * WAVE) FAIL(-2, "need room for %d words", 2 * WAVE);
-  for (int l = 0; l < WAVE; l++) { out[2 * l] = sc.lanes[l].role0; out[2 * l + 1] = sc.lanes[l].role1; }
-  return 2 * WAVE;
-}
-// The integer members of the compiled model view (model_ints) and of Aux; returns the two counts, the second shifted left by 16.
-extern "C" int sumo_debug_model_ints(const void* model_blob, size_t nbytes, int32_t* out, int cap, int32_t* aux_out, int aux_cap) {
-  if (!model_blob || !out || !aux_out) FAIL(-1, "bad arguments");
-  Scene sc;
-  if (int rc = prepare_scene(sc, model_blob, nbytes, SCENE_AUX)) return rc;
-  if (cap < 128 || aux_cap < AUX_NINTS) FAIL(-2, "buffers too small");
-  const int n = model_ints(&sc.hm, out);
-  memcpy(aux_out, &sc.aux.ndepth, AUX_NINTS * sizeof(int));
-  return n | (AUX_NINTS << 16);
-}
-extern "C" int sumo_static_layout(sumo_handle_t E) { return E ? E->static_layout : -1; }   // 1: this engine runs the static-Layout kernel variants
-extern "C" int sumo_debug_dump(sumo_handle_t E, double* dev_buf /* [2][8][64] or NULL */) {   // development (-DSUMO_DBG_DUMP builds)
-  if (!E) FAIL(-1, "bad handle");
-  E->dbg_dump = dev_buf;
-  return 0;
-}
-extern "C" int sumo_debug_fault(sumo_handle_t E, int env) {
-  if (!E) FAIL(-1, "bad handle");
-  E->dbg_fault_env = env;
-  return 0;
-}
-extern "C" int sumo_debug_trace(sumo_handle_t E, uint64_t* stamps_dev) {
-  if (!E) FAIL(-1, "bad handle");
-  E->d_trace = (unsigned long long*)stamps_dev;
-  return 0;
-}
-
-extern "C" int sumo_get_state(sumo_handle_t E, double* qpos, double* qvel, double* warm, int32_t* counters) {
-  if (!E) FAIL(-1, "bad handle");
-  HIPCHK(hipSetDevice(E->device));
-  HIPCHK(hipDeviceSynchronize());
-  const sumo_model_t* m = &E->hm;
-  size_t N = (size_t)E->N;
-  std::vector<double> st(N * E->state_stride);
-  std::vector<int> cn(N * 4);
-  HIPCHK(hipMemcpy(st.data(), E->d_state, st.size() * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(cn.data(), E->d_counters, cn.size() * sizeof(int), hipMemcpyDeviceToHost));
-  for (size_t e = 0; e < N; e++) {
-    const double* s = &st[e * E->state_stride];
-    if (qpos) memcpy(qpos + e * m->nq, s, m->nq * sizeof(double));
-    if (qvel) memcpy(qvel + e * m->nv, s + m->nq, m->nv * sizeof(double));
-    if (warm) memcpy(warm + e * m->nv, s + m->nq + m->nv, m->nv * sizeof(double));
-    if (counters) { counters[2 * e] = cn[4 * e]; counters[2 * e + 1] = cn[4 * e + 1]; }
-  }
-  return 0;
-}
-
-extern "C" int sumo_set_state(sumo_handle_t E, const double* qpos, const double* qvel, const double* warm, const int32_t* counters) {
-  if (!E) FAIL(-1, "bad handle");
-  HIPCHK(hipSetDevice(E->device));
-  HIPCHK(hipDeviceSynchronize());
-  const sumo_model_t* m = &E->hm;
-  size_t N = (size_t)E->N;
-  std::vector<double> st(N * E->state_stride);
-  std::vector<int> cn(N * 4);
-  HIPCHK(hipMemcpy(st.data(), E->d_state, st.size() * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(cn.data(), E->d_counters, cn.size() * sizeof(int), hipMemcpyDeviceToHost));
-  for (size_t e = 0; e < N; e++) {
-    double* s = &st[e * E->state_stride];
-    if (qpos) memcpy(s, qpos + e * m->nq, m->nq * sizeof(double));
-    if (qvel) memcpy(s + m->nq, qvel + e * m->nv, m->nv * sizeof(double));
-    if (warm) memcpy(s + m->nq + m->nv, warm + e * m->nv, m->nv * sizeof(double));
-    if (counters) { cn[4 * e] = counters[2 * e]; cn[4 * e + 1] = counters[2 * e + 1]; }
-  }
-  HIPCHK(hipMemcpy(E->d_state, st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(E->d_counters, cn.data(), cn.size() * sizeof(int), hipMemcpyHostToDevice));
-  return 0;
-}
-
-extern "C" int sumo_debug_forward(sumo_handle_t E, const double* ctrl, double* qacc, int32_t* counts) {
-  if (!E || !ctrl || !qacc || !counts) FAIL(-1, "bad arguments");
-  HIPCHK(hipSetDevice(E->device));
-  const sumo_model_t* m = &E->hm;
-  size_t N = (size_t)E->N;
-  DevBuf<double> d_ctrl, d_qacc;
-  DevBuf<int> d_cnt;
-  HIPCHK(d_ctrl.alloc(N * m->nu));
-  HIPCHK(d_qacc.alloc(N * m->nv));
-  HIPCHK(d_cnt.alloc(N * 4));
-  HIPCHK(hipMemcpy(d_ctrl, ctrl, N * m->nu * sizeof(double), hipMemcpyHostToDevice));
-  StepArgs a = base_args(E);
-  a.stats = nullptr; a.dbg_ctrl = d_ctrl; a.dbg_qacc = d_qacc; a.dbg_counts = d_cnt;
-  SUMO_DISPATCH(sumo_forward_kernel, E, (hipStream_t)0, a);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(qacc, d_qacc, N * m->nv * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(counts, d_cnt, N * 4 * sizeof(int), hipMemcpyDeviceToHost));
-  return 0;
-}
-
-// One wave through the in-wave primitives of the kernels above, on caller-given lanes (sumo_debug_wave_ops).
-struct WaveOpsArgs {
-  const double* in;   // [8][64]
-  const int* iin;     // [64]
-  double* sums;       // [20]: wave_sum of rows 0 .. 7, wave_sum2 of rows 0 .. 1, wave_sum4 of rows 0 .. 3, wave_sum_n<6> of rows 0 .. 5
-  double* swapped;    // [64]: pair_swap_f64 of row 0
-  int* scan;          // [65]: wave_excl_scan of iin, then its total
-  const double* gn;   // [ngn]
-  unsigned char* grad;   // [ngn][2]: the gradient test on gn[i], sqrt form and threshold form
-  int ngn;
-  double scale, tol, thresh;
-};
-__global__ void __launch_bounds__(WAVE) sumo_wave_ops_kernel(WaveOpsArgs a) {
-  const int lane = threadIdx.x;
-  double r[8];
-  for (int k = 0; k < 8; k++) r[k] = a.in[WAVE * k + lane];
-  for (int k = 0; k < 8; k++) { const double s = wave_sum(r[k]); if (lane == 0) a.sums[k] = s; }
-  { double p = r[0], q = r[1]; wave_sum2(p, q); if (lane == 0) { a.sums[8] = p; a.sums[9] = q; } }
-  { double p = r[0], q = r[1], u = r[2], v = r[3]; wave_sum4(p, q, u, v); if (lane == 0) { a.sums[10] = p; a.sums[11] = q; a.sums[12] = u; a.sums[13] = v; } }
-  { double v[6] = {r[0], r[1], r[2], r[3], r[4], r[5]}; wave_sum_n(v); if (lane == 0) for (int k = 0; k < 6; k++) a.sums[14 + k] = v[k]; }
-  a.swapped[lane] = pair_swap_f64(r[0]);
-  int tot;
-  a.scan[lane] = wave_excl_scan(a.iin[lane], lane, &tot);
-  if (lane == 0) a.scan[WAVE] = tot;
-  for (int i = lane; i < a.ngn; i += WAVE) {
-    const double gn = a.gn[i];
-    a.grad[2 * i] = a.scale * sqrt(gn) < a.tol;
-    a.grad[2 * i + 1] = gn <= a.thresh;
-  }
-}
-extern "C" int sumo_debug_grad_threshold(double scale, double tol, double* out) {   // host only
-  if (!out) FAIL(-1, "bad arguments");
-  *out = grad_threshold(scale, tol);
-  return 0;
-}
-extern "C" int sumo_debug_wave_ops(sumo_handle_t E, const double* in64x8, const int32_t* int_in64, double* sums20, double* swapped64,
-                                   int32_t* scan65, const double* gn, int ngn, double scale, double tol, uint8_t* grad_out) {
-  if (!E || !in64x8 || !int_in64 || !sums20 || !swapped64 || !scan65 || ngn < 0 || (ngn && (!gn || !grad_out))) FAIL(-1, "bad arguments");
-  HIPCHK(hipSetDevice(E->device));
-  DevBuf<double> d_in, d_sums, d_swapped, d_gn;
-  DevBuf<int> d_iin, d_scan;
-  DevBuf<unsigned char> d_grad;
-  const size_t ng = ngn ? (size_t)ngn : 1;
-  HIPCHK(d_in.alloc(8 * WAVE)); HIPCHK(d_sums.alloc(20)); HIPCHK(d_swapped.alloc(WAVE)); HIPCHK(d_gn.alloc(ng));
-  HIPCHK(d_iin.alloc(WAVE)); HIPCHK(d_scan.alloc(WAVE + 1)); HIPCHK(d_grad.alloc(2 * ng));
-  HIPCHK(hipMemcpy(d_in, in64x8, 8 * WAVE * sizeof(double), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d_iin, int_in64, WAVE * sizeof(int), hipMemcpyHostToDevice));
-  if (ngn) HIPCHK(hipMemcpy(d_gn, gn, ng * sizeof(double), hipMemcpyHostToDevice));
-  WaveOpsArgs a{d_in, d_iin, d_sums, d_swapped, d_scan, d_gn, d_grad, ngn, scale, tol, grad_threshold(scale, tol)};
-  hipLaunchKernelGGL(sumo_wave_ops_kernel, dim3(1), dim3(WAVE), 0, (hipStream_t)0, a);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(sums20, d_sums, 20 * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(swapped64, d_swapped, WAVE * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(scan65, d_scan, (WAVE + 1) * sizeof(int), hipMemcpyDeviceToHost));
-  if (ngn) HIPCHK(hipMemcpy(grad_out, d_grad, 2 * ng * sizeof(unsigned char), hipMemcpyDeviceToHost));
-  return 0;
-}
-
-extern "C" int sumo_profile(sumo_handle_t E, double* out24) {  // cycle totals per phase (SUMO_PROFILE builds only)
-  if (!E || !out24) FAIL(-1, "bad arguments");
-  HIPCHK(hipSetDevice(E->device));
-  HIPCHK(hipDeviceSynchronize());
-  unsigned long long h[48];
-  HIPCHK(hipMemcpy(h, E->d_stats, sizeof h, hipMemcpyDeviceToHost));
-  for (int i = 0; i < 24; i++) out24[i] = (double)h[16 + i];
-  return 0;
-}
-
-extern "C" int sumo_stats(sumo_handle_t E, double* out) {
-  if (!E || !out) FAIL(-1, "bad arguments");
-  HIPCHK(hipSetDevice(E->device));
-  HIPCHK(hipDeviceSynchronize());
-  unsigned long long h[SUMO_NSTATS];
-  HIPCHK(hipMemcpy(h, E->d_stats, sizeof h, hipMemcpyDeviceToHost));
-  for (int i = 0; i < SUMO_NSTATS; i++) out[i] = (double)h[i];
-  return 0;
-}
+#ifndef SUMO_ROLLOUT_SHARD   // a shard object is the device code above and nothing else (DESIGN.md sections 19, 27)
+#include "engine_host_scene.h"
+#include "engine_host_api.h"
+#include "engine_host_fused.h"
+#include "engine_host_debug.h"
 #endif   // !SUMO_ROLLOUT_SHARD

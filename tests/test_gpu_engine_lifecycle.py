@@ -1,4 +1,4 @@
-"""Creation and destruction of engines (csrc/sumo_engine.hip: sumo_create / sumo_destroy; every device buffer of an engine is owned by
+"""Creation and destruction of engines (csrc/engine_host_api.h: sumo_create / sumo_destroy; every device buffer of an engine is owned by
 it and goes with it): two engines alive on one device do not share anything, destroying one leaves the other's results bit for bit
 what a fresh engine gives, destroying nothing or twice is harmless, and a creation that fails on the host (a scene whose lane roles do
 not fit, -26) leaves nothing behind that changes the next engine.  16 envs, three env steps at a time; Ant-vs-Ant runs the static-layout

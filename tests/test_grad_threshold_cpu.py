@@ -1,4 +1,4 @@
-"""The Newton loop's gradient test as a threshold (csrc/sumo_engine.hip: grad_threshold, exported as sumo_debug_grad_threshold).  The
+"""The Newton loop's gradient test as a threshold (csrc/engine_host_scene.h: grad_threshold, exported as sumo_debug_grad_threshold).  The
 kernel breaks on ``scale * sqrt(gn) < tol``, gn the squared gradient norm; sumo_create bisects once per scene for the largest float64 G
 for which that holds and the kernel tests ``gn <= G``.  Here, for the options of the nine scenes and two further tolerances, with the
 test D evaluated in numpy float64: D(G) holds, D(nextafter(G, inf)) does not, and D is non-increasing over the 512 doubles on either

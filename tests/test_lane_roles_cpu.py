@@ -1,7 +1,8 @@
-"""The two packed role words a lane keeps in registers (csrc/sumo_engine.hip: LaneRec::role0 / role1, built by build_lane_roles):
-every field, for all 64 lanes of all nine scenes, against the same quantity recomputed here from the compiled model; the chain
-elements the tree-shaped velocity pass derives from the words against the model's dof_parentid walk; and a value that does not fit
-its field must fail creation instead of being truncated.  Host only: sumo_debug_lane_roles touches no device."""
+"""The two packed role words a lane keeps in registers (csrc/sumo_engine.hip: LaneRec::role0 / role1, built by build_lane_roles of
+csrc/engine_host_scene.h): every field, for all 64 lanes of all nine scenes, against the same quantity recomputed here from the
+compiled model; the chain elements the tree-shaped velocity pass derives from the words against the model's dof_parentid walk; and
+a value that does not fit its field must fail creation instead of being truncated.  Host only: sumo_debug_lane_roles touches no
+device."""
 import copy
 import ctypes as C
 import os

@@ -8,6 +8,9 @@ fixed policy-zoo opponent (MLP or LSTM net) on the GPU and print / save win, dra
         --fused --trials 512 --interval 10      (all checkpoints x opponents batched over the envs, one fused launch per 64 steps;
                                                  MLP and LSTM opponent files may be mixed: each family plays in launches of its own;
                                                  an LSTM run plays zoo MLP files with --cross_family)
+    python eval_against_fix.py --path results/RoboSumo-Ant-vs-Bug-v0-0 --env RoboSumo-Ant-vs-Bug-v0 --fused --trials 512 \
+        --opponent_path <zoo>/bug/mlp/agent-params-v3.npy --opponent_path <zoo>/bug/lstm/agent-params-v3.npy
+                                                (a run on a mixed match-up: mixed.evaluate_history_against_zoo, --trials a multiple of 16)
 """
 import argparse
 import json
@@ -75,9 +78,20 @@ def main_fused(args):
     if args.cfrc_mode != "zero":
         raise SystemExit("--fused runs on the fused match launch, which refuses --cfrc_mode rne_post")
     trials = args.trials if args.trials is not None else args.rounds
-    r = matches.evaluate_history_against_zoo(args.path, args.opponent_path, trials, start=args.start, interval=args.interval,
-                                             num_env=args.num_env, deterministic=not args.stochastic, fused=True, seed=args.seed,
-                                             adjust_z=args.adjust_z, env_id=args.env, cross_family=args.cross_family)
+    from robosumo_selfplay_amd import mjcf
+    scene = mjcf.load_model(args.env)
+    if scene.obs_dims[0] != scene.obs_dims[1] or scene.act_dims[0] != scene.act_dims[1]:
+        # a mixed match-up: the learner's seat against a zoo seat on the per-step env launch (--trials a multiple of 16)
+        from robosumo_selfplay_amd import mixed
+        if args.cross_family:
+            raise SystemExit("--cross_family is about LSTM runs; mixed match-ups evaluate MLP(64,64) runs")
+        r = mixed.evaluate_history_against_zoo(args.path, args.opponent_path, trials, start=args.start, interval=args.interval,
+                                               num_env=args.num_env, deterministic=not args.stochastic, fused=True, seed=args.seed,
+                                               adjust_z=args.adjust_z, env_id=args.env)
+    else:
+        r = matches.evaluate_history_against_zoo(args.path, args.opponent_path, trials, start=args.start, interval=args.interval,
+                                                 num_env=args.num_env, deterministic=not args.stochastic, fused=True, seed=args.seed,
+                                                 adjust_z=args.adjust_z, env_id=args.env, cross_family=args.cross_family)
     table = []
     for cid in r["checkpoints"]:
         row = [cid]

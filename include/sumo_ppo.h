@@ -116,6 +116,37 @@ typedef struct ppo_zoo_seat {
 int ppo_zoo_seat_act(const ppo_zoo_seat* seat, const float* obs, int n, int obs_stride, const uint8_t* done, int done_stride,
                      const float* noise, float* action_out, int act_stride, int32_t* status_dev, void* stream);
 
+/* One step of a MIXED match-up (RoboSumo-Ant-vs-Bug-v0, ...: the two sides differ in observation and action width) for both seats in
+ * ONE launch, grid (n / 16 tiles, 2 sides): agent 0 is played by a learner's MLP(64,64) net, agent 1 by a zoo seat.
+ *   side 0  tile t is evaluated with row tile_row[t] (NULL = row 0 for every tile) of `table`, nrows rows of row_stride floats, each an
+ *           MLP(64,64) + copy-value parameter vector in ppo_forward's flat order (ppo_param_count(ob_dim, ac_dim) floats).  obs0 row e at
+ *           obs0 + e * obs_stride, action0 row e at action0 + e * act_stride (ac_dim columns written), noise0 contiguous [n][ac_dim] or
+ *           NULL (= the action is the mean).  Action, neglogp and value are the bits of ppo_forward(row, obs0, PPO_FWD_PI | PPO_FWD_VF,
+ *           noise0).  `record` (NULL or any member NULL = skip it) receives the step's rollout record: obs [n][ob_dim] an exact copy of
+ *           the rows read, action [n][ac_dim], neglogp [n], value [n] and done [n] = done[e * done_stride], agent 0's flag of the
+ *           previous step.  With record->value NULL the value trunk is not evaluated.
+ *   side 1  ppo_zoo_seat_act(seat, obs1, ..., noise1, action1, ...) bit for bit, the same device function: an LSTM tile's state rows
+ *           are reset on done[e * done_stride] -- agent 0's flag, the one side 0 records.
+ * n, the strides and `done` are shared by the two sides (the env's buffers).  A tile whose learner row is outside [0, nrows), or whose
+ * zoo entry names no net, reads no table and writes neither actions, record nor state for that side; it stores
+ *   status = 1 + 2 * tile + side            (tile = (status - 1) >> 1, side = (status - 1) & 1)
+ * to status_dev (DEVICE int32, may be NULL; the caller zeroes it; of several such tiles one is reported).  Argument errors return
+ * before anything is launched: NULL learner / table / obs0 / action0, nrows < 1, learner ob_dim outside [1, 512] or ac_dim outside
+ * [1, 16], strides below the learner's widths, row_stride below the parameter count, and everything ppo_zoo_seat_act refuses of its
+ * seat, n and strides. */
+typedef struct ppo_learner_seat {
+  const float* table;        /* DEVICE [nrows][row_stride] */
+  const int32_t* tile_row;   /* DEVICE [n / 16], or NULL: row 0 for every tile */
+  int nrows, row_stride, ob_dim, ac_dim;
+} ppo_learner_seat;
+typedef struct ppo_mixed_record {
+  float *obs, *action, *neglogp, *value;
+  uint8_t* done;
+} ppo_mixed_record;
+int ppo_mixed_step(const ppo_learner_seat* learner, const ppo_zoo_seat* seat, const float* obs0, const float* obs1, int n,
+                   int obs_stride, const uint8_t* done, int done_stride, const float* noise0, const float* noise1, float* action0,
+                   float* action1, int act_stride, const ppo_mixed_record* record, int32_t* status_dev, void* stream);
+
 /* --- recurrent training (back-propagation through time over the baselines LSTM; the reference builds the unrolled graph in
  * a2c/utils.py:82-103 + model.py:65-139, its own recurrent minibatch loop alg_ppo.py:408-421 is dead code) ---------------
  * ppo_lstm_step_save: ppo_lstm_step that also records what the backward pass needs for this time step:

@@ -434,6 +434,15 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
     """``run_log=True`` writes the run's files into ``log_dir`` (runlog.py); ``eval_interval`` / ``eval_opponents`` make rank 0 play the
     live learner against fixed opponents every so many updates (train_eval.py), on ``eval_env`` (the reference's parameter) or on
     an env of its own.  With the defaults neither happens and the run writes and draws exactly what it did without them."""
+    # a mixed match-up (the two sides differ) trains in fix mode only, through mixed.MixedRunner; the other modes meet the Runner's refusal
+    from . import mixed
+    mixed_env = mixed.is_mixed(env) and opponent_mode == "fix"
+    if mixed_env:
+        mixed.check_learn(env, network=network, opponent_mode=opponent_mode, use_opponent_data=use_opponent_data, opponent_pool=opponent_pool,
+                          fused_fix_opponent=fused_fix_opponent, fused_selector=fused_selector, eval_interval=eval_interval,
+                          eval_opponents=eval_opponents, comm=comm)
+        from . import zoo_pairs
+        zoo_seat = zoo_pairs.seat_for(env, 1, mixed.fix_paths(fix_opponent_path))     # a file of another species is refused here
     if fused_selector:
         check_fused_selector(network, opponent_mode, model_fn)
     # evaluation: everything unsupported is refused here, before anything touches the device (None: evaluation is off)
@@ -469,12 +478,14 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
     model = mk("model_0", True)
     model.equal_counts = use_opponent_data is None      # opponent-data reuse makes per-rank minibatch sizes differ
     sdist.broadcast_params(model.params, comm)                          # sync_from_root (ppo2/model.py:129-131)
-    models = [model] + [mk("model_%d" % i, False) for i in range(1, nagent)]
+    models = [model] + [mk("model_%d" % i, False) for i in range(1, 1 if mixed_env else nagent)]   # a mixed match-up has no second net of the learner's shape
     log_dir = log_dir or os.environ.get("OPENAI_LOGDIR") or "/tmp/robosumo_selfplay_amd"
     checkdir = osp.join(log_dir, "checkpoints")
     nupdates = total_timesteps // nbatch
     selector = model_util = None
-    if not fused_selector:
+    if mixed_env:
+        pass                                                             # no candidates to score
+    elif not fused_selector:
         model_util = mk("model_util", False)
     else:
         # the candidates live in a device table and are scored in one launch (policy_selector.py); no scratch model is built, but the
@@ -495,8 +506,11 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
             m.load(load_path)
     for i, m in enumerate(models):
         m.act_model.seed((seed or 0) * 1000 + 17 * i + rank)
-    runner = Runner(env=env, models=models, nsteps=nsteps, nagent=nagent, gamma=gamma, lam=lam, rho_bar=rho_bar, c_bar=c_bar,
-                    anneal_bound=anneal_bound)
+    if mixed_env:     # agent 1's noise generator is seeded as install_fixed_opponent seeds a zoo net
+        runner = mixed.MixedRunner(env, model, zoo_seat, nsteps, gamma, lam, anneal_bound, seat_seed=(seed or 0) * 1000 + 17 + rank)
+    else:
+        runner = Runner(env=env, models=models, nsteps=nsteps, nagent=nagent, gamma=gamma, lam=lam, rho_bar=rho_bar, c_bar=c_bar,
+                        anneal_bound=anneal_bound)
     # opt-in: in opponent_mode='fix' the zoo net (MLP or LSTM) plays inside the fused rollout launch (Runner.fused_fix_opponent: another noise stream)
     runner.fused_fix_opponent = bool(fused_fix_opponent)
     if recurrent and use_opponent_data is not None:       # the learner carries a shadow state along agent 1's stream (Runner.reuse_opponent)
@@ -508,7 +522,7 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
     pool = None
     # the single-snapshot opponent: every selection loads its first choice here and the 'ours' selector scores against it.  It is agent
     # 1 itself unless an LSTM pool takes that seat below (alg_ppo.py:208: it holds 00000 when update 2 scores the opponent update 1 faced)
-    opp_ref = runner.models[1]
+    opp_ref = None if mixed_env else runner.models[1]
     if int(opponent_pool) > 1:
         check_opponent_pool(opponent_mode, runner, fused=not recurrent)
         from .opponent_pool import LstmOpponentPool, OpponentPool
@@ -547,7 +561,10 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
         frac = 1.0 - (update - 1.0) / nupdates
         lrnow, cliprangenow = lr(frac), cliprange(frac)
         # ---- opponent selection (alg_ppo.py:191-247)
-        if opponent_mode == "fix":                                       # alg_ppo.py:194-206: a policy-zoo net
+        if mixed_env:                                                    # the seat's nets re-dealt over the tiles; there is no version to choose
+            league = runner.assign(update)
+            history["version_gap"].append(0); history["opponent_versions"].append(list(range(len(zoo_seat))))
+        elif opponent_mode == "fix":                                     # alg_ppo.py:194-206: a policy-zoo net
             if update == 1:
                 install_fixed_opponent(runner, fix_opponent_path, ac_space.shape[0], dev, (seed or 0) * 1000 + 17 + rank)
             league = assign_league(runner, update)

@@ -690,11 +690,13 @@ struct ZooSeatArgs {
   ParamLayout L;   // of the MLP rows
 };
 
-__global__ void __launch_bounds__(256) ppo_zoo_seat_kernel(ZooSeatArgs a) {
+// The seat's tile blockIdx.x: ONE copy for ppo_zoo_seat_kernel and side 1 of ppo_mixed_step_kernel.  `bad`: the status word of a tile whose
+// entry names no net (1 + tile for the seat launch, the (tile, side) code for the mixed one).
+__device__ __forceinline__ void zoo_seat_tile(const ZooSeatArgs& a, int bad) {
   const int tile = blockIdx.x, e = a.s.tile_entry[tile];
   const int n_mlp = a.s.n_mlp, D = a.s.ob_dim, A = a.s.ac_dim;
   if (e < 0 || e >= n_mlp + a.s.n_lstm) {   // no table row: nothing is read through e, nothing written but the status word
-    if (threadIdx.x == 0 && a.status) *a.status = 1 + tile;
+    if (threadIdx.x == 0 && a.status) *a.status = bad;
     return;
   }
   if (e < n_mlp) {
@@ -727,8 +729,11 @@ __global__ void __launch_bounds__(256) ppo_zoo_seat_kernel(ZooSeatArgs a) {
   lstm_step_tile<H, PPO_LSTM_GATES_IJFO, false, 4>(la, N, LstmMaskDone{a.done, a.done_stride}, a.act_stride);
 }
 
-extern "C" int ppo_zoo_seat_act(const ppo_zoo_seat* seat, const float* obs, int n, int obs_stride, const uint8_t* done, int done_stride,
-                                const float* noise, float* action_out, int act_stride, int32_t* status_dev, void* stream) {
+__global__ void __launch_bounds__(256) ppo_zoo_seat_kernel(ZooSeatArgs a) { zoo_seat_tile(a, 1 + (int)blockIdx.x); }
+
+// the seat's own checks and launch arguments, shared by ppo_zoo_seat_act and ppo_mixed_step; `lds` receives the seat layout's bytes
+static int zoo_seat_args(ZooSeatArgs& a, size_t& lds, const ppo_zoo_seat* seat, const float* obs, int n, int obs_stride, const uint8_t* done,
+                         int done_stride, const float* noise, float* action_out, int act_stride, int32_t* status_dev) {
   if (!seat || !obs || !action_out) FAIL(-1, "bad arguments");
   if (n < 16 || n % 16 != 0) FAIL(-2, "n = %d: a seat acts on whole tiles of 16 envs", n);
   if (seat->ob_dim < 1 || seat->ob_dim > 512 || obs_stride < seat->ob_dim) FAIL(-3, "bad ob_dim/obs_stride");
@@ -739,20 +744,123 @@ extern "C" int ppo_zoo_seat_act(const ppo_zoo_seat* seat, const float* obs, int 
   if (seat->n_lstm > 0 && !seat->state) FAIL(-7, "LSTM rows need a state");
   if (!seat->tile_entry) FAIL(-8, "missing tile entries");
   if (done && done_stride < 1) FAIL(-9, "done_stride %d", done_stride);
-  ZooSeatArgs a;
   a.s = *seat; a.obs = obs; a.noise = noise; a.done = done; a.action = action_out; a.status = status_dev;
   a.n = n; a.obs_stride = obs_stride; a.done_stride = done_stride; a.act_stride = act_stride;
   a.XS = x_stride(seat->ob_dim);
   a.L = make_layout(seat->ob_dim, seat->ac_dim);
   a.Pl = seat->ob_dim * H + H + 2 * H * 4 * H + 4 * H + H * seat->ac_dim + 2 * seat->ac_dim;
   // the LSTM layout x | emb | h_prev | h_new holds the MLP layout x | h1 | h2 (HP = H + 2 == HS)
-  const size_t lds = (size_t)(16 * a.XS + 16 * HS + 2 * 16 * (H + 2)) * sizeof(float);
+  lds = (size_t)(16 * a.XS + 16 * HS + 2 * 16 * (H + 2)) * sizeof(float);
+  return 0;
+}
+
+extern "C" int ppo_zoo_seat_act(const ppo_zoo_seat* seat, const float* obs, int n, int obs_stride, const uint8_t* done, int done_stride,
+                                const float* noise, float* action_out, int act_stride, int32_t* status_dev, void* stream) {
+  ZooSeatArgs a;
+  size_t lds;
+  if (int rc = zoo_seat_args(a, lds, seat, obs, n, obs_stride, done, done_stride, noise, action_out, act_stride, status_dev)) return rc;
   static thread_local size_t lds_set = 0;
   if (lds > 64 * 1024 && lds > lds_set) {
     HIPCHK(hipFuncSetAttribute((const void*)ppo_zoo_seat_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     lds_set = lds;
   }
   hipLaunchKernelGGL(ppo_zoo_seat_kernel, dim3(n / 16), dim3(256), lds, (hipStream_t)stream, a);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// One rollout / evaluation step of a mixed match-up (ppo_mixed_step, sumo_ppo.h): grid (tile, side), four waves.  Side 1 is the zoo
+// seat above (zoo_seat_tile).  Side 0 is the learner's seat: the tile's parameter row from a device table, the observations staged once
+// (no filter), wave 0 the policy trunk and Gaussian head (fwd_pi_tile: the bits of ppo_forward_kernel) into the env's action buffer
+// and the record, wave 1 the value trunk on the same staged tile, waves 2 and 3 the observation and done records.  The side branch is
+// uniform over the workgroup and comes before any barrier.  LDS: the larger of x [16][XS] + two waves' activation tile pairs and the
+// seat's layout.
+// ---------------------------------------------------------------------------------------------------------
+struct MixedStepArgs {
+  ZooSeatArgs z;           // side 1 (n, done / done_stride, strides and status are shared with side 0)
+  const float *table, *obs0, *noise0;
+  const int32_t* tile_row;
+  float *action0, *rec_obs, *rec_act, *rec_nlp, *rec_val;
+  uint8_t* rec_done;
+  int nrows, row_stride, XS0;
+  ParamLayout L0;
+};
+
+__global__ void __launch_bounds__(256) ppo_mixed_step_kernel(MixedStepArgs a) {
+  const int tile = blockIdx.x;
+  if (blockIdx.y == 1) { zoo_seat_tile(a.z, 2 + 2 * tile); return; }
+  const int row_id = a.tile_row ? a.tile_row[tile] : 0;
+  if (row_id < 0 || row_id >= a.nrows) {   // no table row: nothing is read through it, nothing written but the status word
+    if (threadIdx.x == 0 && a.z.status) *a.z.status = 1 + 2 * tile;
+    return;
+  }
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, r0 = tile * 16, n = a.z.n;
+  const int XS = a.XS0, D = a.L0.D, A = a.L0.A;
+  const float* params = a.table + (size_t)row_id * a.row_stride;
+  float* xbuf = smem_f;
+  float* h1 = xbuf + 16 * XS + (wid & 1) * (2 * 16 * HS);   // waves 0 and 1: an activation tile pair each
+  float* h2 = h1 + 16 * HS;
+  stage_x(xbuf, XS, a.obs0, a.z.obs_stride, D, nullptr, r0, n, tid, nullptr, nullptr, 0.0f, 256);
+  __syncthreads();
+  const int i = lane & 15, kq = lane >> 4;
+  if (wid == 0) {
+    fwd_pi_tile(params, a.L0, false, xbuf, XS, h1, h2, lane, r0, n, nullptr, a.noise0, a.action0, a.z.act_stride, nullptr, a.rec_nlp);
+    if (a.rec_act && i < A) {   // every lane copies the action elements it has just written itself
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const int row = r0 + 4 * kq + r;
+        if (row < n) a.rec_act[(size_t)row * A + i] = a.action0[(size_t)row * a.z.act_stride + i];
+      }
+    }
+  } else if (wid == 1) {
+    if (a.rec_val) {
+      f32x4 v = trunk_forward<false>(vf_net(params, a.L0), xbuf, XS, D, h1, h2, lane);
+      if (i == 0) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) { const int row = r0 + 4 * kq + r; if (row < n) a.rec_val[row] = v[r]; }
+      }
+    }
+  } else {
+    const int t2 = tid - 128;
+    if (a.rec_obs) {
+      for (int r = 0; r < 16 && r0 + r < n; r++)
+        for (int c = t2; c < D; c += 128) a.rec_obs[(size_t)(r0 + r) * D + c] = xbuf[r * XS + c];
+    }
+    if (a.rec_done && t2 < 16 && r0 + t2 < n) a.rec_done[r0 + t2] = a.z.done ? a.z.done[(size_t)(r0 + t2) * a.z.done_stride] : 0;
+  }
+}
+
+extern "C" int ppo_mixed_step(const ppo_learner_seat* learner, const ppo_zoo_seat* seat, const float* obs0, const float* obs1, int n,
+                              int obs_stride, const uint8_t* done, int done_stride, const float* noise0, const float* noise1,
+                              float* action0, float* action1, int act_stride, const ppo_mixed_record* record, int32_t* status_dev,
+                              void* stream) {
+  if (!learner) FAIL(-20, "missing learner seat");
+  if (!learner->table) FAIL(-21, "the learner seat has no parameter table");
+  if (!obs0 || !action0) FAIL(-22, "missing observation or action buffer of agent 0");
+  if (learner->nrows < 1) FAIL(-23, "the learner seat needs at least one parameter row, got %d", learner->nrows);
+  if (learner->ob_dim < 1 || learner->ob_dim > 512) FAIL(-24, "learner ob_dim %d not in [1,512]", learner->ob_dim);
+  if (learner->ac_dim < 1 || learner->ac_dim > MAXA) FAIL(-25, "learner ac_dim %d not in [1,%d]", learner->ac_dim, MAXA);
+  if (obs_stride < learner->ob_dim) FAIL(-26, "obs_stride %d below the learner's ob_dim %d", obs_stride, learner->ob_dim);
+  if (act_stride < learner->ac_dim) FAIL(-27, "act_stride %d below the learner's ac_dim %d", act_stride, learner->ac_dim);
+  MixedStepArgs a;
+  a.L0 = make_layout(learner->ob_dim, learner->ac_dim);
+  if (learner->row_stride < a.L0.P) FAIL(-28, "row_stride %d below the %d parameters of a row", learner->row_stride, a.L0.P);
+  size_t lds1;
+  if (int rc = zoo_seat_args(a.z, lds1, seat, obs1, n, obs_stride, done, done_stride, noise1, action1, act_stride, status_dev)) return rc;
+  a.table = learner->table; a.tile_row = learner->tile_row; a.nrows = learner->nrows; a.row_stride = learner->row_stride;
+  a.obs0 = obs0; a.noise0 = noise0; a.action0 = action0;
+  a.rec_obs = record ? record->obs : nullptr; a.rec_act = record ? record->action : nullptr; a.rec_nlp = record ? record->neglogp : nullptr;
+  a.rec_val = record ? record->value : nullptr; a.rec_done = record ? record->done : nullptr;
+  a.XS0 = x_stride(learner->ob_dim);
+  const size_t lds0 = (size_t)(16 * a.XS0 + 2 * 2 * 16 * HS) * sizeof(float);
+  const size_t lds = lds0 > lds1 ? lds0 : lds1;
+  static thread_local size_t lds_set = 0;
+  if (lds > 64 * 1024 && lds > lds_set) {
+    HIPCHK(hipFuncSetAttribute((const void*)ppo_mixed_step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    lds_set = lds;
+  }
+  hipLaunchKernelGGL(ppo_mixed_step_kernel, dim3(n / 16, 2), dim3(256), lds, (hipStream_t)stream, a);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -12,7 +12,7 @@ _LIB = None
 EXPORTS = ("ppo_last_error", "ppo_param_count", "ppo_forward", "ppo_forward_filtered", "ppo_lstm_step", "ppo_lstm_step_pool", "ppo_lstm_step_save", "ppo_lstm_xproj", "ppo_lstm_step_save_z", "ppo_lstm_seq_forward", "ppo_lstm_seq_backward", "ppo_lstm_head_grad", "ppo_lstm_bwd_step", "ppo_lstm_wgrad_workspace_bytes", "ppo_lstm_wgrad", "ppo_selfplay_forward", "ppo_post_step", "ppo_reward_mix", "ppo_vtrace", "ppo_adv_moments", "ppo_adv_moments_ws", "ppo_adv_moments_workspace_bytes",
            "ppo_adv_normalize", "ppo_grad_workspace_bytes", "ppo_grad", "ppo_loss_stats", "ppo_clip_adam",
            "ppo_a2c_grad", "ppo_a2c_loss_stats", "ppo_selection_scores_workspace_bytes", "ppo_selection_scores",
-           "ppo_adv_moments_masked_ws", "ppo_adv_normalize_masked", "ppo_lstm_head_grad_masked", "ppo_zoo_seat_act")
+           "ppo_adv_moments_masked_ws", "ppo_adv_normalize_masked", "ppo_lstm_head_grad_masked", "ppo_zoo_seat_act", "ppo_mixed_step")
 
 
 class PpoHipError(RuntimeError):
@@ -32,6 +32,30 @@ class ZooSeat(C.Structure):
     _fields_ = [("mlp_params", C.c_void_p), ("mlp_filt", C.c_void_p), ("lstm_params", C.c_void_p), ("lstm_filt", C.c_void_p),
                 ("tile_entry", C.c_void_p), ("state", C.c_void_p), ("n_mlp", C.c_int), ("n_lstm", C.c_int), ("ob_dim", C.c_int),
                 ("ac_dim", C.c_int), ("obs_clip", C.c_float), ("forget_bias", C.c_float)]
+
+
+class LearnerSeat(C.Structure):
+    """``ppo_learner_seat`` of include/sumo_ppo.h: the parameter rows that may play agent 0 of a mixed match-up."""
+    _fields_ = [("table", C.c_void_p), ("tile_row", C.c_void_p), ("nrows", C.c_int), ("row_stride", C.c_int), ("ob_dim", C.c_int),
+                ("ac_dim", C.c_int)]
+
+
+class MixedRecord(C.Structure):
+    """``ppo_mixed_record`` of include/sumo_ppo.h: where ``ppo_mixed_step`` writes agent 0's rollout record (0 / None = skip)."""
+    _fields_ = [("obs", C.c_void_p), ("action", C.c_void_p), ("neglogp", C.c_void_p), ("value", C.c_void_p), ("done", C.c_void_p)]
+
+
+def mixed_status(tile, side):
+    """The status word ``ppo_mixed_step`` leaves for a tile whose side names no table row."""
+    return 1 + 2 * int(tile) + int(side)
+
+
+def mixed_status_decode(status):
+    """(tile, side) of a non-zero ``ppo_mixed_step`` status word."""
+    status = int(status)
+    if status < 1:
+        raise ValueError("status %d reports no tile" % status)
+    return (status - 1) >> 1, (status - 1) & 1
 
 
 def fill_lstm_net_ifou(n, ob_dim, ac_dim, nlstm, addrs):
@@ -69,6 +93,8 @@ def lib():
         L.ppo_lstm_wgrad_workspace_bytes.restype = C.c_size_t
         L.ppo_lstm_wgrad.argtypes = [C.POINTER(LstmNet), i32, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp]
         L.ppo_zoo_seat_act.argtypes = [C.POINTER(ZooSeat), vp, i32, i32, vp, i32, vp, vp, i32, vp, vp]
+        L.ppo_mixed_step.argtypes = [C.POINTER(LearnerSeat), C.POINTER(ZooSeat), vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, i32,
+                                     C.POINTER(MixedRecord), vp, vp]
         L.ppo_reward_mix.argtypes = [vp, i32, f64, vp, i32, vp]
         L.ppo_selfplay_forward.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, C.POINTER(vp), C.POINTER(vp), vp]
         L.ppo_post_step.argtypes = [vp, i32, f64, vp, i32, vp, vp, vp, vp, vp, vp, vp]

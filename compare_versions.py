@@ -68,7 +68,15 @@ def main(argv):
                    loss=[[None if i == j else float(r["loss"][i, j]) for j in range(V)] for i in range(V)])
         out = args.out or os.path.join(args.path, "round_robin.json")
     else:
-        r = matches.compare_history_versions(args.p1, args.p2, args.trials, cross_family=args.cross_family, **kw)
+        from robosumo_selfplay_amd import mjcf
+        m = mjcf.load_model(args.env)
+        if m.obs_dims[0] != m.obs_dims[1] or m.act_dims[0] != m.act_dims[1]:      # the two sides of a co-trained run (run.py --co_train)
+            from robosumo_selfplay_amd import co_train
+            if args.cross_family:
+                raise SystemExit("--cross_family is about LSTM runs; mixed match-ups compare MLP(64,64) runs")
+            r = co_train.compare_history_versions(args.p1, args.p2, args.trials, interval=args.interval, **kw)
+        else:
+            r = matches.compare_history_versions(args.p1, args.p2, args.trials, cross_family=args.cross_family, **kw)
         for (a, b), w, res in zip(r["versions"], r["win_rate"], r["results"]):
             print("-----P1 %s vs P2 %s: P1 win rate %.2f (%d wins, %d losses, %d draws)-----" % (a, b, w, res["wins"], res["losses"],
                                                                                              res["draws"]))

@@ -147,6 +147,25 @@ int ppo_mixed_step(const ppo_learner_seat* learner, const ppo_zoo_seat* seat, co
                    int obs_stride, const uint8_t* done, int done_stride, const float* noise0, const float* noise1, float* action0,
                    float* action1, int act_stride, const ppo_mixed_record* record, int32_t* status_dev, void* stream);
 
+/* One step of a mixed match-up with a LEARNER seat on BOTH sides (two species trained against each other), ONE launch, grid (n / 16
+ * tiles, 2 sides).  Each side is side 0 of ppo_mixed_step, the same device function, with its own widths, table, buffers and record:
+ * per side, action, neglogp and value are the bits of ppo_forward(row, obs, PPO_FWD_PI | PPO_FWD_VF, noise), the obs record is an exact
+ * copy of the rows read and the done record is that side's own flag done[e * done_stride] (NULL = 0).  n and the three strides are
+ * shared (the env's buffers).  A tile whose row is outside [0, nrows) reads no table and writes nothing for that side; it stores
+ * status = 1 + 2 * tile + side to status_dev (DEVICE int32, may be NULL; the caller zeroes it), the encoding of ppo_mixed_step.
+ * Argument errors return before anything is launched, the message naming the side: NULL sides / table / obs / action, nrows < 1,
+ * ob_dim outside [1, 512] or ac_dim outside [1, 16], strides below a side's widths, row_stride below the parameter count, n < 16 or
+ * off the 16 grid, done given with done_stride < 1. */
+typedef struct ppo_pair_side {
+  ppo_learner_seat seat;      /* table, tile_row (NULL = row 0), nrows, row_stride, ob_dim, ac_dim */
+  const float *obs, *noise;   /* obs row e at obs + e*obs_stride; noise contiguous [n][ac_dim] or NULL = means */
+  const uint8_t* done;        /* this agent's previous-step flag at done[e*done_stride]; NULL = 0 */
+  float* action;              /* row e at action + e*act_stride */
+  ppo_mixed_record record;    /* any member NULL = skip; value NULL = value trunk not evaluated */
+} ppo_pair_side;
+int ppo_mixed_pair_step(const ppo_pair_side sides[2], int n, int obs_stride, int done_stride, int act_stride,
+                        int32_t* status_dev, void* stream);
+
 /* --- recurrent training (back-propagation through time over the baselines LSTM; the reference builds the unrolled graph in
  * a2c/utils.py:82-103 + model.py:65-139, its own recurrent minibatch loop alg_ppo.py:408-421 is dead code) ---------------
  * ppo_lstm_step_save: ppo_lstm_step that also records what the backward pass needs for this time step:

@@ -777,45 +777,53 @@ extern "C" int ppo_zoo_seat_act(const ppo_zoo_seat* seat, const float* obs, int 
 // uniform over the workgroup and comes before any barrier.  LDS: the larger of x [16][XS] + two waves' activation tile pairs and the
 // seat's layout.
 // ---------------------------------------------------------------------------------------------------------
-struct MixedStepArgs {
-  ZooSeatArgs z;           // side 1 (n, done / done_stride, strides and status are shared with side 0)
-  const float *table, *obs0, *noise0;
+// One learner seat's side of a launch: its table, buffers, record and layout.  n, the strides, the done flags and the status word
+// travel beside it.
+struct LearnerSideArgs {
+  const float *table, *obs, *noise;
   const int32_t* tile_row;
-  float *action0, *rec_obs, *rec_act, *rec_nlp, *rec_val;
+  float *action, *rec_obs, *rec_act, *rec_nlp, *rec_val;
   uint8_t* rec_done;
-  int nrows, row_stride, XS0;
-  ParamLayout L0;
+  int nrows, row_stride, XS;
+  ParamLayout L;
 };
 
-__global__ void __launch_bounds__(256) ppo_mixed_step_kernel(MixedStepArgs a) {
+struct MixedStepArgs {
+  ZooSeatArgs z;           // side 1 (n, the strides and status are shared with side 0)
+  LearnerSideArgs l;       // side 0 (it records z.done)
+};
+
+// The learner seat's tile blockIdx.x: ONE copy for side 0 of ppo_mixed_step_kernel and both sides of ppo_mixed_pair_step_kernel.  `bad`: the
+// status word of a tile whose row names no table row.
+__device__ __forceinline__ void learner_seat_tile(const LearnerSideArgs& a, int n, int obs_stride, const uint8_t* done, int done_stride,
+                                                  int act_stride, int32_t* status, int bad) {
   const int tile = blockIdx.x;
-  if (blockIdx.y == 1) { zoo_seat_tile(a.z, 2 + 2 * tile); return; }
   const int row_id = a.tile_row ? a.tile_row[tile] : 0;
   if (row_id < 0 || row_id >= a.nrows) {   // no table row: nothing is read through it, nothing written but the status word
-    if (threadIdx.x == 0 && a.z.status) *a.z.status = 1 + 2 * tile;
+    if (threadIdx.x == 0 && status) *status = bad;
     return;
   }
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, r0 = tile * 16, n = a.z.n;
-  const int XS = a.XS0, D = a.L0.D, A = a.L0.A;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, r0 = tile * 16;
+  const int XS = a.XS, D = a.L.D, A = a.L.A;
   const float* params = a.table + (size_t)row_id * a.row_stride;
   float* xbuf = smem_f;
   float* h1 = xbuf + 16 * XS + (wid & 1) * (2 * 16 * HS);   // waves 0 and 1: an activation tile pair each
   float* h2 = h1 + 16 * HS;
-  stage_x(xbuf, XS, a.obs0, a.z.obs_stride, D, nullptr, r0, n, tid, nullptr, nullptr, 0.0f, 256);
+  stage_x(xbuf, XS, a.obs, obs_stride, D, nullptr, r0, n, tid, nullptr, nullptr, 0.0f, 256);
   __syncthreads();
   const int i = lane & 15, kq = lane >> 4;
   if (wid == 0) {
-    fwd_pi_tile(params, a.L0, false, xbuf, XS, h1, h2, lane, r0, n, nullptr, a.noise0, a.action0, a.z.act_stride, nullptr, a.rec_nlp);
+    fwd_pi_tile(params, a.L, false, xbuf, XS, h1, h2, lane, r0, n, nullptr, a.noise, a.action, act_stride, nullptr, a.rec_nlp);
     if (a.rec_act && i < A) {   // every lane copies the action elements it has just written itself
 #pragma unroll
       for (int r = 0; r < 4; r++) {
         const int row = r0 + 4 * kq + r;
-        if (row < n) a.rec_act[(size_t)row * A + i] = a.action0[(size_t)row * a.z.act_stride + i];
+        if (row < n) a.rec_act[(size_t)row * A + i] = a.action[(size_t)row * act_stride + i];
       }
     }
   } else if (wid == 1) {
     if (a.rec_val) {
-      f32x4 v = trunk_forward<false>(vf_net(params, a.L0), xbuf, XS, D, h1, h2, lane);
+      f32x4 v = trunk_forward<false>(vf_net(params, a.L), xbuf, XS, D, h1, h2, lane);
       if (i == 0) {
 #pragma unroll
         for (int r = 0; r < 4; r++) { const int row = r0 + 4 * kq + r; if (row < n) a.rec_val[row] = v[r]; }
@@ -827,8 +835,19 @@ __global__ void __launch_bounds__(256) ppo_mixed_step_kernel(MixedStepArgs a) {
       for (int r = 0; r < 16 && r0 + r < n; r++)
         for (int c = t2; c < D; c += 128) a.rec_obs[(size_t)(r0 + r) * D + c] = xbuf[r * XS + c];
     }
-    if (a.rec_done && t2 < 16 && r0 + t2 < n) a.rec_done[r0 + t2] = a.z.done ? a.z.done[(size_t)(r0 + t2) * a.z.done_stride] : 0;
+    if (a.rec_done && t2 < 16 && r0 + t2 < n) a.rec_done[r0 + t2] = done ? done[(size_t)(r0 + t2) * done_stride] : 0;
   }
+}
+
+__global__ void __launch_bounds__(256) ppo_mixed_step_kernel(MixedStepArgs a) {
+  const int tile = blockIdx.x;
+  if (blockIdx.y == 1) { zoo_seat_tile(a.z, 2 + 2 * tile); return; }
+  learner_seat_tile(a.l, a.z.n, a.z.obs_stride, a.z.done, a.z.done_stride, a.z.act_stride, a.z.status, 1 + 2 * tile);
+}
+
+static void learner_side_record(LearnerSideArgs& s, const ppo_mixed_record* record) {
+  s.rec_obs = record ? record->obs : nullptr; s.rec_act = record ? record->action : nullptr; s.rec_nlp = record ? record->neglogp : nullptr;
+  s.rec_val = record ? record->value : nullptr; s.rec_done = record ? record->done : nullptr;
 }
 
 extern "C" int ppo_mixed_step(const ppo_learner_seat* learner, const ppo_zoo_seat* seat, const float* obs0, const float* obs1, int n,
@@ -844,16 +863,15 @@ extern "C" int ppo_mixed_step(const ppo_learner_seat* learner, const ppo_zoo_sea
   if (obs_stride < learner->ob_dim) FAIL(-26, "obs_stride %d below the learner's ob_dim %d", obs_stride, learner->ob_dim);
   if (act_stride < learner->ac_dim) FAIL(-27, "act_stride %d below the learner's ac_dim %d", act_stride, learner->ac_dim);
   MixedStepArgs a;
-  a.L0 = make_layout(learner->ob_dim, learner->ac_dim);
-  if (learner->row_stride < a.L0.P) FAIL(-28, "row_stride %d below the %d parameters of a row", learner->row_stride, a.L0.P);
+  a.l.L = make_layout(learner->ob_dim, learner->ac_dim);
+  if (learner->row_stride < a.l.L.P) FAIL(-28, "row_stride %d below the %d parameters of a row", learner->row_stride, a.l.L.P);
   size_t lds1;
   if (int rc = zoo_seat_args(a.z, lds1, seat, obs1, n, obs_stride, done, done_stride, noise1, action1, act_stride, status_dev)) return rc;
-  a.table = learner->table; a.tile_row = learner->tile_row; a.nrows = learner->nrows; a.row_stride = learner->row_stride;
-  a.obs0 = obs0; a.noise0 = noise0; a.action0 = action0;
-  a.rec_obs = record ? record->obs : nullptr; a.rec_act = record ? record->action : nullptr; a.rec_nlp = record ? record->neglogp : nullptr;
-  a.rec_val = record ? record->value : nullptr; a.rec_done = record ? record->done : nullptr;
-  a.XS0 = x_stride(learner->ob_dim);
-  const size_t lds0 = (size_t)(16 * a.XS0 + 2 * 2 * 16 * HS) * sizeof(float);
+  a.l.table = learner->table; a.l.tile_row = learner->tile_row; a.l.nrows = learner->nrows; a.l.row_stride = learner->row_stride;
+  a.l.obs = obs0; a.l.noise = noise0; a.l.action = action0;
+  learner_side_record(a.l, record);
+  a.l.XS = x_stride(learner->ob_dim);
+  const size_t lds0 = (size_t)(16 * a.l.XS + 2 * 2 * 16 * HS) * sizeof(float);
   const size_t lds = lds0 > lds1 ? lds0 : lds1;
   static thread_local size_t lds_set = 0;
   if (lds > 64 * 1024 && lds > lds_set) {
@@ -861,6 +879,61 @@ extern "C" int ppo_mixed_step(const ppo_learner_seat* learner, const ppo_zoo_sea
     lds_set = lds;
   }
   hipLaunchKernelGGL(ppo_mixed_step_kernel, dim3(n / 16, 2), dim3(256), lds, (hipStream_t)stream, a);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// One step of a mixed match-up with a LEARNER seat on both sides (ppo_mixed_pair_step, sumo_ppo.h): grid (tile, side), four waves, both
+// sides the body above, each with its own layout, buffers and record.  The side branch is uniform over the workgroup and comes before
+// any barrier.  LDS: the larger of the two sides' x [16][XS] + two waves' activation tile pairs.
+// ---------------------------------------------------------------------------------------------------------
+struct MixedPairArgs {
+  LearnerSideArgs s[2];
+  const uint8_t* done[2];  // each side's own flags
+  int32_t* status;
+  int n, obs_stride, done_stride, act_stride;
+};
+
+__global__ void __launch_bounds__(256) ppo_mixed_pair_step_kernel(MixedPairArgs a) {
+  const int bad = 1 + 2 * (int)blockIdx.x;
+  if (blockIdx.y == 0) learner_seat_tile(a.s[0], a.n, a.obs_stride, a.done[0], a.done_stride, a.act_stride, a.status, bad);
+  else learner_seat_tile(a.s[1], a.n, a.obs_stride, a.done[1], a.done_stride, a.act_stride, a.status, bad + 1);
+}
+
+extern "C" int ppo_mixed_pair_step(const ppo_pair_side sides[2], int n, int obs_stride, int done_stride, int act_stride, int32_t* status_dev,
+                                   void* stream) {
+  if (!sides) FAIL(-40, "missing sides");
+  if (n < 16 || n % 16 != 0) FAIL(-41, "n = %d: the seats act on whole tiles of 16 envs", n);
+  MixedPairArgs a;
+  size_t lds = 0;
+  for (int k = 0; k < 2; k++) {
+    const ppo_pair_side& p = sides[k];
+    LearnerSideArgs& s = a.s[k];
+    if (!p.seat.table) FAIL(-42, "side %d: the seat has no parameter table", k);
+    if (!p.obs || !p.action) FAIL(-43, "side %d: missing observation or action buffer", k);
+    if (p.seat.nrows < 1) FAIL(-44, "side %d: the seat needs at least one parameter row, got %d", k, p.seat.nrows);
+    if (p.seat.ob_dim < 1 || p.seat.ob_dim > 512) FAIL(-45, "side %d: ob_dim %d not in [1,512]", k, p.seat.ob_dim);
+    if (p.seat.ac_dim < 1 || p.seat.ac_dim > MAXA) FAIL(-46, "side %d: ac_dim %d not in [1,%d]", k, p.seat.ac_dim, MAXA);
+    if (obs_stride < p.seat.ob_dim) FAIL(-47, "side %d: obs_stride %d below ob_dim %d", k, obs_stride, p.seat.ob_dim);
+    if (act_stride < p.seat.ac_dim) FAIL(-48, "side %d: act_stride %d below ac_dim %d", k, act_stride, p.seat.ac_dim);
+    s.L = make_layout(p.seat.ob_dim, p.seat.ac_dim);
+    if (p.seat.row_stride < s.L.P) FAIL(-49, "side %d: row_stride %d below the %d parameters of a row", k, p.seat.row_stride, s.L.P);
+    if (p.done && done_stride < 1) FAIL(-50, "side %d: done_stride %d", k, done_stride);
+    s.table = p.seat.table; s.tile_row = p.seat.tile_row; s.nrows = p.seat.nrows; s.row_stride = p.seat.row_stride;
+    s.obs = p.obs; s.noise = p.noise; a.done[k] = p.done; s.action = p.action;
+    learner_side_record(s, &p.record);
+    s.XS = x_stride(p.seat.ob_dim);
+    const size_t l = (size_t)(16 * s.XS + 2 * 2 * 16 * HS) * sizeof(float);
+    if (l > lds) lds = l;
+  }
+  a.status = status_dev; a.n = n; a.obs_stride = obs_stride; a.done_stride = done_stride; a.act_stride = act_stride;
+  static thread_local size_t lds_set = 0;
+  if (lds > 64 * 1024 && lds > lds_set) {
+    HIPCHK(hipFuncSetAttribute((const void*)ppo_mixed_pair_step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    lds_set = lds;
+  }
+  hipLaunchKernelGGL(ppo_mixed_pair_step_kernel, dim3(n / 16, 2), dim3(256), lds, (hipStream_t)stream, a);
   HIPCHK(hipGetLastError());
   return 0;
 }

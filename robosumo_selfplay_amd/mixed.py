@@ -131,17 +131,18 @@ class EnvRows(object):
 RECORD_KEYS = ("obs", "act", "nlp", "val", "done")
 
 
-def _check_mixed_step(lseat, env, tile_row, noise0, record):
+def _check_mixed_step(lseat, env, tile_row, noise0, record, side=0):
+    """The arguments of a learner seat on ``side`` of one step (``noise0`` / ``record``: that side's)."""
     import torch
     N, D0, A0 = env.num_envs, lseat.ob_dim, lseat.ac_dim
-    if (D0, A0) != (env.model.obs_dims[0], env.model.act_dims[0]):
-        raise ValueError("the learner seat (%d observations, %d actions) does not fit agent 0 of %s (%d, %d)"
-                         % (D0, A0, env.spec.id, env.model.obs_dims[0], env.model.act_dims[0]))
+    if (D0, A0) != (env.model.obs_dims[side], env.model.act_dims[side]):
+        raise ValueError("the learner seat (%d observations, %d actions) does not fit agent %d of %s (%d, %d)"
+                         % (D0, A0, side, env.spec.id, env.model.obs_dims[side], env.model.act_dims[side]))
     if tile_row is not None and (not torch.is_tensor(tile_row) or tile_row.dtype != torch.int32 or not tile_row.is_contiguous()
                                  or tuple(tile_row.shape) != (N // LEAGUE_TILE,) or tile_row.device != env.device):
         raise ValueError("tile_row must be a contiguous int32 tensor [%d] on the env's device" % (N // LEAGUE_TILE))
     if noise0 is not None and (tuple(noise0.shape) != (N, A0) or noise0.dtype != torch.float32 or not noise0.is_contiguous()):
-        raise ValueError("noise0 must be a contiguous float32 tensor [%d][%d]" % (N, A0))
+        raise ValueError("noise%d must be a contiguous float32 tensor [%d][%d]" % (side, N, A0))
     shapes = dict(obs=((N, D0), torch.float32), act=((N, A0), torch.float32), nlp=((N,), torch.float32), val=((N,), torch.float32),
                   done=((N,), torch.uint8))
     for k, x in (record or {}).items():
@@ -165,14 +166,12 @@ def mixed_step(env, learner_seat, zoo_seat, tile_entry, state, noise0=None, nois
     definition: ``ppo_forward`` (PI, and VF with ``val``) per run of tiles sharing a row (``runs0``, default the runs of
     ``tile_row``, a device read), torch copies into the action buffer and the record, then ``zoo_pairs.seat_act(fused=False)``
     (``runs1``); runs whose row names no net are skipped."""
-    import torch
     _check_mixed_step(learner_seat, env, tile_row, noise0, record)
     zoo_pairs._check_step(zoo_seat, env, 1, tile_entry, state, noise1)
     rec = dict.fromkeys(RECORD_KEYS)
     rec.update(record or {})
-    N, D0, A0 = env.num_envs, learner_seat.ob_dim, learner_seat.ac_dim
-    L, st, obs, act, done = ppo_capi.lib(), env._stream(), env.obs_dev, env.act_dev, env.done_dev
     if fused:
+        N, L, st, obs, act, done = env.num_envs, ppo_capi.lib(), env._stream(), env.obs_dev, env.act_dev, env.done_dev
         ls, zs = learner_seat.struct(tile_row), zoo_seat.struct(tile_entry, state)
         r = ppo_capi.MixedRecord()
         r.obs, r.action, r.neglogp, r.value, r.done = (ppo_capi.ptr(rec[k]) for k in RECORD_KEYS)
@@ -180,6 +179,17 @@ def mixed_step(env, learner_seat, zoo_seat, tile_entry, state, noise0=None, nois
                                       done.data_ptr(), done.stride(0), ppo_capi.ptr(noise0), ppo_capi.ptr(noise1), act[:, 0].data_ptr(),
                                       act[:, 1].data_ptr(), act.stride(0), C.byref(r), ppo_capi.ptr(status), st))
         return
+    learner_side_definition(env, learner_seat, 0, tile_row, noise0, rec, runs0)
+    zoo_pairs.seat_act(zoo_seat, env, 1, tile_entry, state, noise1, fused=False, runs=runs1)
+
+
+def learner_side_definition(env, learner_seat, side, tile_row, noise0, rec, runs0=None):
+    """The definition of a learner seat's step on ``side``: ``ppo_forward`` (PI, and VF with ``rec['val']``) per run of tiles sharing a
+    row (``runs0``, default the runs of ``tile_row``, a device read), torch copies into ``act_dev[:, side, :A]`` and the record
+    ``rec`` (every key of ``RECORD_KEYS`` present, None = skip); runs whose row names no net are skipped."""
+    import torch
+    N, D0, A0 = env.num_envs, learner_seat.ob_dim, learner_seat.ac_dim
+    L, st, obs, act, done = ppo_capi.lib(), env._stream(), env.obs_dev, env.act_dev, env.done_dev
     if runs0 is None:
         runs0 = [(0, N // LEAGUE_TILE, 0)] if tile_row is None else matches._runs(tile_row.cpu().numpy())
     out = torch.empty((N, A0), dtype=torch.float32, device=env.device) if rec["act"] is None else rec["act"]
@@ -190,22 +200,21 @@ def mixed_step(env, learner_seat, zoo_seat, tile_entry, state, noise0=None, nois
         rows = slice(LEAGUE_TILE * t0, LEAGUE_TILE * t1)
         n = rows.stop - rows.start
         sub = lambda x: None if x is None else x[rows].data_ptr()
-        ppo_capi.chk(L.ppo_forward(learner_seat.table[row].data_ptr(), obs[rows, 0].data_ptr(), n, obs.stride(0), D0, A0, flags,
+        ppo_capi.chk(L.ppo_forward(learner_seat.table[row].data_ptr(), obs[rows, side].data_ptr(), n, obs.stride(0), D0, A0, flags,
                                    sub(noise0), None, out[rows].data_ptr(), sub(rec["nlp"]), sub(rec["val"]), None, st))
-        act[rows, 0, :A0] = out[rows]
+        act[rows, side, :A0] = out[rows]
         if rec["obs"] is not None:
-            rec["obs"][rows] = obs[rows, 0, :D0]
+            rec["obs"][rows] = obs[rows, side, :D0]
         if rec["done"] is not None:
-            rec["done"][rows] = done[rows, 0]
-    zoo_pairs.seat_act(zoo_seat, env, 1, tile_entry, state, noise1, fused=False, runs=runs1)
+            rec["done"][rows] = done[rows, side]
 
 
-def raise_status(status):
+def raise_status(status, sides=("learner row", "zoo entry")):
     """``ValueError`` naming tile and side if a ``ppo_mixed_step`` status word is set (a device read)."""
     bad = int(status.item())
     if bad:
         tile, side = ppo_capi.mixed_status_decode(bad)
-        raise ValueError("tile %d: its %s names no table row of the seat" % (tile, "zoo entry" if side else "learner row"))
+        raise ValueError("tile %d: its %s names no table row of the seat" % (tile, sides[side]))
 
 
 # ---- training -------------------------------------------------------------------------------------------------------------
@@ -437,31 +446,28 @@ def _seat_steps(env, seats, tiles, state, score, quota, K, noise, fused):
         raise_status(status)
 
 
-def play_checkpoints_against_seat(env, learner_seat, zoo_seat, pairs, rounds_per_env, envs_per_pair, deterministic=True, seed=0,
-                                  adjust_z=EVAL_ADJUST_Z, chunk=64, fused=True, record=None, every=1):
-    """:func:`zoo_pairs.play_zoo_pairs` with a :class:`LearnerSeat` on side 0: every match-up ``pairs[p] = (i, j)`` -- row i of
-    ``learner_seat`` as agent 0 against net j of ``zoo_seat`` as agent 1 -- on ``envs_per_pair`` envs (a multiple of 16),
-    ``rounds_per_env`` finished episodes per env, with the same batching (:func:`matches.plan_batches`,
-    :func:`matches.env_assignment` over whole tiles), seeded reset (``seed`` + batch number * N + env), per-env quota, score update
-    and ``adjust_z`` imposed and restored.  Deterministic by default, as the reference's evaluator plays.  ``record``: a directory
-    that receives ``traj.npz`` of the first batch (every ``every``-th step), which ``play.py --replay`` renders.  Returns one dict
-    per pair: wins, losses, draws, rounds, env_steps."""
-    import torch
-    N = env.num_envs
+def check_batch_args(env, rounds_per_env, envs_per_pair, chunk, every=1):
+    """The four counts of a seat match as ints; ``ValueError`` where a pair would not play whole tiles or a count is below 1."""
     rounds_per_env, envs_per_pair, chunk, every = int(rounds_per_env), int(envs_per_pair), int(chunk), int(every)
     if envs_per_pair < LEAGUE_TILE or envs_per_pair % LEAGUE_TILE:
         raise ValueError("envs_per_pair = %d: a pair plays whole tiles of %d envs" % (envs_per_pair, LEAGUE_TILE))
-    if N % LEAGUE_TILE:
-        raise ValueError("num_envs = %d is not a multiple of %d" % (N, LEAGUE_TILE))
+    if env.num_envs % LEAGUE_TILE:
+        raise ValueError("num_envs = %d is not a multiple of %d" % (env.num_envs, LEAGUE_TILE))
     if rounds_per_env < 1 or chunk < 1 or every < 1:
         raise ValueError("rounds_per_env, chunk and every must be >= 1")
-    pairs = [(int(i), int(j)) for i, j in pairs]
-    for i, j in pairs:
-        if not (0 <= i < len(learner_seat) and 0 <= j < len(zoo_seat)):
-            raise ValueError("pair (%d, %d) refers to a non-existent net (%d learner rows / %d zoo nets)" % (i, j, len(learner_seat), len(zoo_seat)))
-    if getattr(env, "cfrc_mode", "zero") != "zero":
-        raise ValueError("the zoo nets were trained on cfrc_mode 'zero' observations")
-    seats = (learner_seat, zoo_seat)
+    return rounds_per_env, envs_per_pair, chunk, every
+
+
+def play_seat_batches(env, seats, pairs, rounds_per_env, envs_per_pair, deterministic, seed, adjust_z, chunk, tiles_of, new_state, steps,
+                      record=None, every=1):
+    """The batch loop of :func:`play_checkpoints_against_seat` and ``co_train.play_checkpoint_pairs``: the pairs in batches of contiguous
+    env blocks (:func:`matches.plan_batches`, :func:`matches.env_assignment` over whole tiles); per batch a seeded reset (``seed`` +
+    batch number * N + env), ``tiles_of(idx0, idx1)`` (the two seats' int32 tile arrays), a fresh ``new_state()`` and
+    ``steps(tiles, state, score, K, noise)`` calls of ``chunk`` steps until every env of the batch has its quota; ``adjust_z``
+    imposed and restored.  ``record``: see :func:`play_checkpoints_against_seat`.  Returns one dict per pair."""
+    import torch
+    N = env.num_envs
+    rounds_per_env, envs_per_pair, chunk, every = check_batch_args(env, rounds_per_env, envs_per_pair, chunk, every)
     batches = matches.plan_batches(len(pairs), envs_per_pair, N)
     max_calls = -(-rounds_per_env * (env.model.timestep_limit + 1) // chunk) + 1      # every episode ends by the time limit
     gen = torch.Generator(device=env.device)
@@ -474,27 +480,27 @@ def play_checkpoints_against_seat(env, learner_seat, zoo_seat, pairs, rounds_per
     try:
         for bn, batch in enumerate(batches):
             idx0, idx1, active = matches.env_assignment(pairs, batch, envs_per_pair, N)
-            tiles = (torch.from_numpy(learner_seat.tile_rows(idx0)).to(env.device), torch.from_numpy(zoo_seat.tile_entries(idx1)).to(env.device))
+            tiles = tuple(torch.from_numpy(x).to(env.device) for x in tiles_of(idx0, idx1))
             act_t = torch.from_numpy(active).to(env.device)
             score = torch.zeros((N, 3), dtype=torch.int32, device=env.device)
             env.seeds = np.uint64(seed) + np.uint64(bn * N) + np.arange(N, dtype=np.uint64)
             env._needs_seed = True
             env.reset_device()
             env.act_dev.zero_()
-            state = zoo_seat.new_state(N)
+            state = new_state()
             rec = record is not None and bn == 0
             qpos, dones, calls = [], [], 0
             while True:
                 noise = None if deterministic else tuple(torch.randn((chunk, N, s.ac_dim), generator=gen, device=env.device) for s in seats)
                 if rec:                  # the same steps one at a time, the joint positions read in between
                     for k in range(chunk):
-                        _seat_steps(env, seats, tiles, state, score, rounds_per_env, 1, None if noise is None else tuple(z[k:k + 1] for z in noise), fused)
+                        steps(tiles, state, score, 1, None if noise is None else tuple(z[k:k + 1] for z in noise))
                         if (calls * chunk + k + 1) % every == 0:
                             torch.cuda.synchronize(env.device)
                             qpos.append(np.concatenate([E.get_state()[0] for E in env.engines]))
                             dones.append(env.done_dev[:, 0].cpu().numpy())
                 else:
-                    _seat_steps(env, seats, tiles, state, score, rounds_per_env, chunk, noise, fused)
+                    steps(tiles, state, score, chunk, noise)
                 calls += 1
                 if not bool((score.sum(1)[act_t] < rounds_per_env).any()):
                     break
@@ -518,6 +524,30 @@ def play_checkpoints_against_seat(env, learner_seat, zoo_seat, pairs, rounds_per
             torch.cuda.synchronize(env.device)
             env.set_adjust_z(prev_adjust)
     return out
+
+
+def play_checkpoints_against_seat(env, learner_seat, zoo_seat, pairs, rounds_per_env, envs_per_pair, deterministic=True, seed=0,
+                                  adjust_z=EVAL_ADJUST_Z, chunk=64, fused=True, record=None, every=1):
+    """:func:`zoo_pairs.play_zoo_pairs` with a :class:`LearnerSeat` on side 0: every match-up ``pairs[p] = (i, j)`` -- row i of
+    ``learner_seat`` as agent 0 against net j of ``zoo_seat`` as agent 1 -- on ``envs_per_pair`` envs (a multiple of 16),
+    ``rounds_per_env`` finished episodes per env, with the same batching (:func:`matches.plan_batches`,
+    :func:`matches.env_assignment` over whole tiles), seeded reset (``seed`` + batch number * N + env), per-env quota, score update
+    and ``adjust_z`` imposed and restored (:func:`play_seat_batches`).  Deterministic by default, as the reference's evaluator plays.
+    ``record``: a directory that receives ``traj.npz`` of the first batch (every ``every``-th step), which ``play.py --replay``
+    renders.  Returns one dict per pair: wins, losses, draws, rounds, env_steps."""
+    check_batch_args(env, rounds_per_env, envs_per_pair, chunk, every)
+    pairs = [(int(i), int(j)) for i, j in pairs]
+    for i, j in pairs:
+        if not (0 <= i < len(learner_seat) and 0 <= j < len(zoo_seat)):
+            raise ValueError("pair (%d, %d) refers to a non-existent net (%d learner rows / %d zoo nets)" % (i, j, len(learner_seat), len(zoo_seat)))
+    if getattr(env, "cfrc_mode", "zero") != "zero":
+        raise ValueError("the zoo nets were trained on cfrc_mode 'zero' observations")
+    seats = (learner_seat, zoo_seat)
+    return play_seat_batches(env, seats, pairs, rounds_per_env, envs_per_pair, deterministic, seed, adjust_z, chunk,
+                             lambda idx0, idx1: (learner_seat.tile_rows(idx0), zoo_seat.tile_entries(idx1)),
+                             lambda: zoo_seat.new_state(env.num_envs),
+                             lambda tiles, state, score, K, noise: _seat_steps(env, seats, tiles, state, score, int(rounds_per_env), K, noise, fused),
+                             record, every)
 
 
 def evaluate_history_against_zoo(path, opponent_paths, trials, start=0, interval=1, num_env=256, deterministic=True, fused=True, seed=0,

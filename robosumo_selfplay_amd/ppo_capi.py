@@ -12,7 +12,8 @@ _LIB = None
 EXPORTS = ("ppo_last_error", "ppo_param_count", "ppo_forward", "ppo_forward_filtered", "ppo_lstm_step", "ppo_lstm_step_pool", "ppo_lstm_step_save", "ppo_lstm_xproj", "ppo_lstm_step_save_z", "ppo_lstm_seq_forward", "ppo_lstm_seq_backward", "ppo_lstm_head_grad", "ppo_lstm_bwd_step", "ppo_lstm_wgrad_workspace_bytes", "ppo_lstm_wgrad", "ppo_selfplay_forward", "ppo_post_step", "ppo_reward_mix", "ppo_vtrace", "ppo_adv_moments", "ppo_adv_moments_ws", "ppo_adv_moments_workspace_bytes",
            "ppo_adv_normalize", "ppo_grad_workspace_bytes", "ppo_grad", "ppo_loss_stats", "ppo_clip_adam",
            "ppo_a2c_grad", "ppo_a2c_loss_stats", "ppo_selection_scores_workspace_bytes", "ppo_selection_scores",
-           "ppo_adv_moments_masked_ws", "ppo_adv_normalize_masked", "ppo_lstm_head_grad_masked", "ppo_zoo_seat_act", "ppo_mixed_step")
+           "ppo_adv_moments_masked_ws", "ppo_adv_normalize_masked", "ppo_lstm_head_grad_masked", "ppo_zoo_seat_act", "ppo_mixed_step",
+           "ppo_mixed_pair_step")
 
 
 class PpoHipError(RuntimeError):
@@ -43,6 +44,12 @@ class LearnerSeat(C.Structure):
 class MixedRecord(C.Structure):
     """``ppo_mixed_record`` of include/sumo_ppo.h: where ``ppo_mixed_step`` writes agent 0's rollout record (0 / None = skip)."""
     _fields_ = [("obs", C.c_void_p), ("action", C.c_void_p), ("neglogp", C.c_void_p), ("value", C.c_void_p), ("done", C.c_void_p)]
+
+
+class PairSide(C.Structure):
+    """``ppo_pair_side`` of include/sumo_ppo.h: one learner seat of ``ppo_mixed_pair_step`` with its buffers and record."""
+    _fields_ = [("seat", LearnerSeat), ("obs", C.c_void_p), ("noise", C.c_void_p), ("done", C.c_void_p), ("action", C.c_void_p),
+                ("record", MixedRecord)]
 
 
 def mixed_status(tile, side):
@@ -95,6 +102,7 @@ def lib():
         L.ppo_zoo_seat_act.argtypes = [C.POINTER(ZooSeat), vp, i32, i32, vp, i32, vp, vp, i32, vp, vp]
         L.ppo_mixed_step.argtypes = [C.POINTER(LearnerSeat), C.POINTER(ZooSeat), vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, i32,
                                      C.POINTER(MixedRecord), vp, vp]
+        L.ppo_mixed_pair_step.argtypes = [C.POINTER(PairSide), i32, i32, i32, i32, vp, vp]
         L.ppo_reward_mix.argtypes = [vp, i32, f64, vp, i32, vp]
         L.ppo_selfplay_forward.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, C.POINTER(vp), C.POINTER(vp), vp]
         L.ppo_post_step.argtypes = [vp, i32, f64, vp, i32, vp, vp, vp, vp, vp, vp, vp]

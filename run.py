@@ -4,6 +4,7 @@
     python run.py --env RoboSumo-Ant-vs-Ant-v0 --algo ac --num_env 1024 --num_timesteps 512000      (A2C learner, one GPU)
     python run.py --env RoboSumo-Ant-vs-Ant-v0 --num_env 1024 --nsteps=128 --eval_interval 5 --eval_opponent 00000 \\
         --eval_opponent <zoo>/ant/mlp/agent-params-v1.npy      (play the live learner against fixed opponents every 5 updates)
+    python run.py --co_train --env RoboSumo-Ant-vs-Bug-v0 --num_env 4096 --nsteps=128      (two species against each other, co_train.learn)
 The run directory gets the reference's run files (log.txt, progress.csv, 0.0.monitor.csv, its pickles; ``--no_run_log``: none).
 Unknown ``--key=value`` flags are forwarded to ``learn`` like the reference does (run.py:29-63), but parsed with
 ``ast.literal_eval`` instead of ``eval``.  Under ``torchrun`` every rank takes an equal shard of ``--num_env``.
@@ -72,7 +73,59 @@ def build_parser():
     ap.add_argument("--eval_num_env", type=int, default=None, help="envs of the evaluation env (default 64)")
     ap.add_argument("--eval_stochastic", action="store_true", help="sample the evaluated actions (default: the mode, as the reference's evaluator)")
     ap.add_argument("--eval_cross_family", action="store_true", help="let an LSTM learner play zoo MLP files in its evaluation (refused otherwise)")
+    ap.add_argument("--co_train", action="store_true", help="a MIXED match-up (RoboSumo-Ant-vs-Bug-v0, ...): train one MLP learner per side against "
+                    "the other side's checkpoints (co_train.learn; --opponent_mode=latest, the default here, or =random).  The run directory "
+                    "gets agent0/ and agent1/, each a run directory of its own")
     return ap
+
+
+def check_co_train(args, extra, world):
+    """What --co_train refuses, before an env is built: each combination with its own message."""
+    if args.algo != "ppo":
+        raise SystemExit("--co_train trains two PPO learners: --algo %s is not available with it" % args.algo)
+    if args.network != "mlp":
+        raise SystemExit("--co_train: both seats hold MLP(64,64) policies, --network %s is not available" % args.network)
+    mode = extra.get("opponent_mode", "latest")
+    if mode == "fix":
+        raise SystemExit("--co_train with --opponent_mode=fix: a learner against policy-zoo nets is a plain run (leave --co_train out)")
+    if mode == "ours":
+        raise SystemExit("--co_train with --opponent_mode=ours: the selector would have to score another species' samples; use latest or random")
+    if extra.get("use_opponent_data") is not None:
+        raise SystemExit("--co_train: --use_opponent_data is not available, a learner cannot score another species' action")
+    if int(extra.get("opponent_pool", 1)) > 1:
+        raise SystemExit("--co_train: --opponent_pool is not available, each side keeps one frozen checkpoint")
+    if args.fused_selector:
+        raise SystemExit("--co_train: --fused_selector serves opponent_mode=ours, which co-training cannot run")
+    if args.eval_interval or args.eval_opponent:
+        raise SystemExit("--co_train: evaluation while training (--eval_interval / --eval_opponent) is out of scope; evaluate agent0/ and "
+                         "agent1/ afterwards with eval_against_fix.py --fused and compare_versions.py")
+    if world > 1:
+        raise SystemExit("--co_train runs on a single GPU: launch it without torchrun / with WORLD_SIZE=1")
+
+
+def co_train_main(args, extra):
+    """--co_train: ``co_train.learn`` on a mixed env, the run directory prepared as ``main`` prepares it."""
+    from robosumo_selfplay_amd import co_train, defaults, dist as sdist
+    check_co_train(args, extra, sdist.env_rank_world()[2])
+    from robosumo_selfplay_amd.vec_env import make_vec_env
+    kw = defaults.get_default_params(args.env, "ppo")
+    for k in ("rho_bar", "c_bar"):          # the importance clips of opponent-data reuse: no such samples here
+        kw.pop(k)
+    kw.update(extra)
+    kw.setdefault("opponent_mode", "latest")
+    log_path = os.path.join(args.log_path, "%s-%s" % (args.env, args.suffix))
+    groups = max(1, args.env_groups or 2)      # the step-by-step env launches, on two streams by default
+    env = make_vec_env(args.env, args.num_env, args.seed, device=0, groups=groups if args.num_env % (16 * groups) == 0 else 1,
+                       cfrc_mode=args.cfrc_mode, adjust_z=args.adjust_z)
+    try:
+        co_train.check_learn(env, network=args.network, opponent_mode=kw["opponent_mode"], nsteps=kw["nsteps"], nminibatches=kw["nminibatches"])
+        shutil.rmtree(log_path, ignore_errors=True)
+        os.makedirs(log_path, exist_ok=True)
+        with open(os.path.join(log_path, "config.pkl"), "wb") as f:
+            pickle.dump(dict(vars(args), **kw), f)
+        return co_train.learn(network=args.network, env=env, seed=args.seed, total_timesteps=int(args.num_timesteps), log_dir=log_path, **kw)
+    finally:
+        env.close()
 
 
 def eval_kwargs(args):
@@ -95,6 +148,8 @@ def eval_kwargs(args):
 def main(argv):
     args, unknown = build_parser().parse_known_args(argv)
     extra = parse_unknown(unknown)
+    if args.co_train:
+        return co_train_main(args, extra)
     from robosumo_selfplay_amd import alg_ac, alg_ppo, defaults, dist as sdist
     from robosumo_selfplay_amd.vec_env import make_vec_env
     learn = {"ppo": alg_ppo.learn, "ac": alg_ac.learn}.get(args.algo)

@@ -364,6 +364,41 @@ int sumo_rollout_steps_zoo_league(sumo_handle_t h, const sumo_rollout* r, const 
 int sumo_rollout_steps_lstm_zoo_league(sumo_handle_t h, const sumo_rollout_lstm* r, const sumo_zoo_league* z, float* actions_dev,
                                        float* obs_dev, double* info_dev, uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev,
                                        int32_t* ep_l_dev, void* stream);
+/* K consecutive CO-TRAINING rollout steps on a match-up whose two sides may be different species (RoboSumo-Ant-vs-Bug-v0, ...: two
+ * observation widths, two action widths) in ONE launch: what co_train.PairRunner runs per step as ppo_mixed_pair_step + sumo_step +
+ * ppo_post_step.  Each side is a seat: a device table of MLP(64,64) + copy-value rows, one row per 16-env tile.  The wave that owns an
+ * env evaluates both seats on their own observation, samples both actions (action = mean + exp(logstd) * noise), steps the env and
+ * writes rewards and agent 0's episode record as sumo_rollout_steps does.
+ *   Side s RECORDS on the tiles whose row equals record_row (-1: on every tile): there its value net runs too and obs / act / nlp / val
+ *   and done (that agent's OWN flag before the step) are written at [step][env_offset + e]; on every other tile only its policy net runs
+ *   and nothing of the side is written -- the co-training runner lets each learner record on the half of the tiles its live row plays.
+ *   A tile_row entry outside [0, nrows) raises the launch's abort flag (sumo_rollout_status returns -20) and row 0 plays.
+ * Per env and step each side's action, neglogp and value are the bits of ppo_forward(row, obs_s, PPO_FWD_PI | PPO_FWD_VF, noise_s); env,
+ * rewards and episode record are sumo_step's and ppo_post_step's.  Ordering contract and env-side buffers as sumo_rollout_steps.
+ * Refused, each with its own code, before anything is launched: cfrc_mode rne_post (-12), steps (-5) or envs (-6) outside the buffers,
+ * ob_dim / ac_dim that are not that agent's of the scene (-4), ac_dim above 16 (-16), nrows < 1 (-7), row_stride below
+ * ppo_param_count (-17), a missing table (-13), noise (-14), record (-15) or shared buffer (-2), tile_row with env_offset or the env
+ * count off the 16-env grid (-11), a scene whose mass-matrix region cannot hold the scratch (-8).  A homogeneous scene is valid. */
+typedef struct sumo_pair_side {
+  const float* table;          /* DEVICE [nrows][row_stride]: MLP(64,64) + copy-value rows, ppo_forward's flat order */
+  const int32_t* tile_row;     /* DEVICE [Ntot / 16]: the row of every 16-env tile of the WHOLE env set; NULL = row 0 */
+  int nrows, row_stride, ob_dim, ac_dim;
+  int record_row;              /* record (and value) on tiles whose row equals it; -1 = on every tile */
+  const float* noise;          /* DEVICE [T][Ntot][ac_dim] */
+  float *obs, *act, *val, *nlp; /* DEVICE [T][Ntot][ob_dim], [T][Ntot][ac_dim], [T][Ntot], [T][Ntot] */
+  uint8_t* done;               /* DEVICE [T][Ntot] */
+} sumo_pair_side;
+typedef struct sumo_rollout_pair {
+  sumo_pair_side side[2];
+  int T, Ntot, env_offset, s0, K;
+  double alpha;
+  float* rew;                  /* DEVICE [2][T][Ntot] */
+  uint8_t* ep_done;            /* DEVICE [T][Ntot], as ep_r (float64) and ep_l (int32) */
+  double* ep_r;
+  int32_t* ep_l;
+} sumo_rollout_pair;
+int sumo_rollout_steps_pair(sumo_handle_t h, const sumo_rollout_pair* r, float* actions_dev, float* obs_dev, double* info_dev,
+                            uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream);
 /* cfrc_mode (reference agents.py:190-214 reads sim.data.cfrc_ext into 84 of the 121 observation entries):
  *   0 = zero (default): what the reference produces -- its MuJoCo 2.1 scenes declare no force / torque / accelerometer sensor, so
  *       mj_rnePostConstraint never runs and cfrc_ext stays at its reset value 0;

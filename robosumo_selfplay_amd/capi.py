@@ -80,6 +80,18 @@ class ZooLeague(C.Structure):
     _fields_ = [("mlp", ZooMlp), ("lstm", ZooLstm), ("tile_entry_dev", _P)]
 
 
+class PairSideRollout(C.Structure):
+    """``sumo_pair_side`` of include/sumo_hip.h: one seat of the co-training launch (device pointers as integers)."""
+    _fields_ = [("table", _P), ("tile_row", _P), ("nrows", _I), ("row_stride", _I), ("ob_dim", _I), ("ac_dim", _I), ("record_row", _I),
+                ("noise", _P), ("obs", _P), ("act", _P), ("val", _P), ("nlp", _P), ("done", _P)]
+
+
+class RolloutPair(C.Structure):
+    """``sumo_rollout_pair`` of include/sumo_hip.h: the two seats and what the launch shares."""
+    _fields_ = [("side", PairSideRollout * 2), ("T", _I), ("Ntot", _I), ("env_offset", _I), ("s0", _I), ("K", _I), ("alpha", C.c_double),
+                ("rew", _P), ("ep_done", _P), ("ep_r", _P), ("ep_l", _P)]
+
+
 # every fused launch of the C ABI: name -> (launch struct, the struct that follows it or None); their argtypes, their restype and
 # their place in EXPORTS come from here
 FUSED_ENTRIES = {
@@ -92,6 +104,9 @@ FUSED_ENTRIES = {
     "sumo_rollout_steps_lstm_zoo_league": (RolloutLstm, ZooLeague), "sumo_match_steps_cross": (MatchCross, None),
     "sumo_match_steps_lstm_zoo": (MatchLstm, ZooMlp), "sumo_rollout_steps_lstm_reuse": (RolloutLstmReuse, None),
 }
+# the fused launches of mixed match-ups, bound like the ones above (a table of its own: FUSED_ENTRIES and EXPORTS list the launches of
+# homogeneous scenes, which matches.py and the runner's rollout modes index)
+PAIR_ENTRIES = {"sumo_rollout_steps_pair": (RolloutPair, None)}
 
 
 def lib():
@@ -109,7 +124,7 @@ def lib():
         L.sumo_dims.argtypes = [vp, vp]
         L.sumo_reset.argtypes = [vp, vp, vp, vp, vp]
         L.sumo_step.argtypes = [vp] * 9
-        for n, (launch, second) in FUSED_ENTRIES.items():
+        for n, (launch, second) in list(FUSED_ENTRIES.items()) + list(PAIR_ENTRIES.items()):
             getattr(L, n).argtypes = [vp] + [C.POINTER(t) for t in (launch, second) if t is not None] + [vp] * 8
             getattr(L, n).restype = i32
         L.sumo_get_state.argtypes = [vp] * 5
@@ -295,6 +310,11 @@ class Engine:
         (``sumo_match_steps_lstm_zoo``); ``mo`` is a filled :class:`MatchLstm` with ``state1`` left None, ``zoo`` a filled
         :class:`ZooMlp` that ``idx1`` indexes."""
         self._fused("sumo_match_steps_lstm_zoo", mo, env_ptrs, stream, zoo)
+
+    def rollout_steps_pair(self, ro, *env_ptrs, stream=None):
+        """K fused co-training rollout steps of a match-up of two species (``sumo_rollout_steps_pair``); ``ro`` is a filled
+        :class:`RolloutPair`: per side a table of MLP rows, the row of every 16-env tile, the row whose tiles record, and its own record."""
+        self._fused("sumo_rollout_steps_pair", ro, env_ptrs, stream)
 
     def set_cfrc_mode(self, mode):
         """'zero' (default, the reference's behaviour) or 'rne_post' (include/sumo_hip.h: cfrc_mode)."""

@@ -16,7 +16,7 @@ from collections import deque
 
 import numpy as np
 
-from . import matches, mixed, ppo_capi, zoo_pairs
+from . import capi, matches, mixed, ppo_capi, zoo_pairs
 from .mixed import LearnerSeat, RECORD_KEYS
 from .policy_zoo import EVAL_ADJUST_Z, LEAGUE_TILE
 
@@ -40,6 +40,14 @@ def own_envs(nenvs, side):
     """The envs that train learner ``side``: the half in which its live row plays."""
     h = int(nenvs) // 2
     return slice(side * h, (side + 1) * h)
+
+
+def check_engine_fused(env, engine_fused, what, instead):
+    """The fused launch evaluates the policies inside its launch, ``cfrc_mode='rne_post'`` fills the observations in a second launch per
+    step: ``what`` on such an env is refused, before the device is touched, with a pointer to ``instead``."""
+    if engine_fused and getattr(env, "cfrc_mode", "zero") != "zero":
+        raise ValueError("%s is not available on an env with cfrc_mode=%r (its observations are completed by a second launch per step, "
+                         "the fused launch reads them inside its own): use %s" % (what, env.cfrc_mode, instead))
 
 
 def pair_step(env, seats, tile_rows, noise, records, fused=True, status=None, runs=None):
@@ -109,9 +117,16 @@ class PairRunner(object):
     Agent 0's episode records are ``ppo_post_step``'s (the env's monitor figure).  Agent 1's side has no monitor: its episode return
     is the running per-env sum of its ANNEALED reward ``rew[1]`` (what it is trained on, not the monitor's figure), carried
     across rollouts and closed where ``ep_done`` is set; the lengths are ``ep_l``.  ``fused``: the one-launch step; default from the
-    environment, ``SUMO_MIXED_STEP=0`` selects the definition (same numbers, bit for bit)."""
+    environment, ``SUMO_MIXED_STEP=0`` selects the definition (same numbers, bit for bit).
 
-    def __init__(self, env, models, nsteps, gamma, lam, anneal_bound=500, fused=None):
+    ``engine_fused``: the steps of a rollout run inside the engine's fused launch (``sumo_rollout_steps_pair``):
+    per env group ONE launch of all ``nsteps`` steps on the group's stream, or launches of ``rollout_chunk`` steps each where that
+    is > 0.  Both seats act in the wave that owns the env; each side records (and evaluates its value net) only on the half of the
+    tiles its live row plays, so the other half of every side's record stays zero -- the halves a learner trains on, the env, the
+    rewards and the episode records are the step-by-step path's, bit for bit.  Not available with ``cfrc_mode='rne_post'``."""
+
+    def __init__(self, env, models, nsteps, gamma, lam, anneal_bound=500, fused=None, engine_fused=False, rollout_chunk=0):
+        check_engine_fused(env, engine_fused, "PairRunner(engine_fused=True)", "engine_fused=False")
         import torch
         self._t = torch
         if not hasattr(env, "step_device"):
@@ -134,6 +149,9 @@ class PairRunner(object):
             table = torch.stack([m.params, m.params]).contiguous()
             self.seats.append(LearnerSeat(D[s], A[s], device=self.device, table=table))
         self.fused = os.environ.get("SUMO_MIXED_STEP", "1") != "0" if fused is None else bool(fused)
+        self.engine_fused, self.rollout_chunk = bool(engine_fused), int(rollout_chunk)
+        if self.rollout_chunk < 0:
+            raise ValueError("rollout_chunk = %d: the steps per fused launch, or 0 for the whole rollout in one" % self.rollout_chunk)
         self.tile_rows = tuple(torch.from_numpy(r).to(self.device) for r in rows)
         self._runs = tuple(matches._runs(r) for r in rows)
         self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -158,13 +176,14 @@ class PairRunner(object):
     def _alloc(self, T):
         t, N, dev = self._t, self.nenv, self.device
         f32 = t.float32
+        new = t.zeros if self.engine_fused else t.empty      # the fused launch leaves the halves nobody trains on unwritten: zeros there
         B = dict(rew=t.empty((2, T, N), dtype=f32, device=dev), ep_done=t.empty((T, N), dtype=t.uint8, device=dev),
                  ep_r=t.empty((T, N), dtype=t.float64, device=dev), ep_l=t.empty((T, N), dtype=t.int32, device=dev), side=[])
         for s, seat in enumerate(self.seats):
             D, A = seat.ob_dim, seat.ac_dim
-            B["side"].append(dict(obs=t.empty((T, N, D), dtype=f32, device=dev), act=t.empty((T, N, A), dtype=f32, device=dev),
-                                  val=t.empty((T, N), dtype=f32, device=dev), nlp=t.empty((T, N), dtype=f32, device=dev),
-                                  done=t.empty((T, N), dtype=t.uint8, device=dev),
+            B["side"].append(dict(obs=new((T, N, D), dtype=f32, device=dev), act=new((T, N, A), dtype=f32, device=dev),
+                                  val=new((T, N), dtype=f32, device=dev), nlp=new((T, N), dtype=f32, device=dev),
+                                  done=new((T, N), dtype=t.uint8, device=dev),
                                   noise=t.randn((T, N, A), generator=self.models[s].act_model.gen, device=dev, dtype=f32)))
         return B
 
@@ -185,6 +204,23 @@ class PairRunner(object):
         ppo_capi.chk(ppo_capi.lib().ppo_post_step(env.info_dev[sl].data_ptr(), n, alpha, B["rew"][0, s, sl].data_ptr(), T * N,
                                                   env.done_dev[sl].data_ptr(), env.ep_r_dev[sl].data_ptr(), env.ep_l_dev[sl].data_ptr(),
                                                   B["ep_done"][s, sl].data_ptr(), B["ep_r"][s, sl].data_ptr(), B["ep_l"][s, sl].data_ptr(), st))
+
+    def _launch_group(self, B, alpha, g, sl):
+        """The rollout's steps of env group ``g`` (envs ``sl``) in fused launches on the current stream."""
+        T, N = self.nsteps, self.nenv
+        K = self.rollout_chunk or T
+        ro = capi.RolloutPair()
+        for s, (seat, b) in enumerate(zip(self.seats, B["side"])):
+            p = ro.side[s]
+            p.table, p.tile_row = seat.table.data_ptr(), self.tile_rows[s].data_ptr()
+            p.nrows, p.row_stride, p.ob_dim, p.ac_dim = len(seat), int(seat.table.stride(0)), seat.ob_dim, seat.ac_dim
+            p.record_row = 0                                            # the live row: each learner records its own half of the tiles
+            p.noise, p.obs, p.act, p.val, p.nlp, p.done = (b[k].data_ptr() for k in ("noise", "obs", "act", "val", "nlp", "done"))
+        ro.T, ro.Ntot, ro.env_offset, ro.alpha = T, N, sl.start, float(alpha)
+        ro.rew, ro.ep_done, ro.ep_r, ro.ep_l = (B[k].data_ptr() for k in ("rew", "ep_done", "ep_r", "ep_l"))
+        for s0 in range(0, T, K):
+            ro.s0, ro.K = s0, min(K, T - s0)
+            self.env.rollout_steps_pair_group(g, ro)
 
     def _side_rollout(self, B, side, cur):
         """The 15 fields of learner ``side`` over its own half of the envs, in ``MixedRunner.run``'s placeholder form."""
@@ -245,18 +281,26 @@ class PairRunner(object):
         self.status.zero_()
         streams = self._group_streams()
         cur = t.cuda.current_stream(self.device)
-        if streams is None:
-            for s in range(T):
-                self._step_group(B, s, alpha, None, slice(0, N))
+
+        def on_groups(fn):                                              # fn(group, its envs) for every env group, on its stream
+            if streams is None:
+                return fn(None, slice(0, N))
+            for g, st in enumerate(streams):
+                with t.cuda.stream(st):
+                    fn(g, env._gs(g))
+
+        for st in streams or ():
+            st.wait_stream(cur)
+        if self.engine_fused:
+            on_groups(lambda g, sl: self._launch_group(B, alpha, g or 0, sl))
         else:
-            for st in streams:
-                st.wait_stream(cur)
             for s in range(T):
-                for g, st in enumerate(streams):
-                    with t.cuda.stream(st):
-                        self._step_group(B, s, alpha, g, env._gs(g))
-            for st in streams:
-                cur.wait_stream(st)
+                on_groups(lambda g, sl: self._step_group(B, s, alpha, g, sl))
+        for st in streams or ():
+            cur.wait_stream(st)
+        if self.engine_fused:
+            for E in env.engines:                                       # waits for the group's launches; raises if one was cut short
+                E.rollout_status()
         self.obs, self.dones = env.obs_dev, env.done_dev
         out = [self._side_rollout(B, side, cur) for side in range(2)]
         mixed.raise_status(self.status, ROW_SIDES)
@@ -266,7 +310,7 @@ class PairRunner(object):
 
 
 # ---- training -------------------------------------------------------------------------------------------------------------
-def check_learn(env, *, network, opponent_mode, nsteps, nminibatches):
+def check_learn(env, *, network, opponent_mode, nsteps, nminibatches, fused_rollout=False):
     """What :func:`learn` refuses, each with its own message, before anything touches the device or a file is written."""
     if not mixed.is_mixed(env):
         raise ValueError("co_train.learn grows two species against each other: %s is a homogeneous match-up, which alg_ppo.learn trains "
@@ -285,6 +329,7 @@ def check_learn(env, *, network, opponent_mode, nsteps, nminibatches):
     if nbatch % int(nminibatches):
         raise ValueError("%s: each learner's batch of num_envs / 2 * nsteps = %d rows does not split into nminibatches = %d"
                          % (where, nbatch, int(nminibatches)))
+    check_engine_fused(env, fused_rollout, "%s: fused_rollout=True (--fused_rollout)" % where, "fused_rollout=False")
 
 
 def choose_frozen(update, opponent_mode, checkdirs, histories):
@@ -320,18 +365,19 @@ def _new_history():
 
 def learn(*, env, total_timesteps, network="mlp", opponent_mode="latest", seed=None, nsteps=2048, nminibatches=4, noptepochs=4, lr=3e-4,
           cliprange=0.2, gamma=0.99, lam=0.95, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, kl_threshold=None, anneal_bound=500,
-          save_interval=1, log_interval=10, log_dir=None, verbose=True, **network_kwargs):
+          save_interval=1, log_interval=10, log_dir=None, verbose=True, fused_rollout=False, **network_kwargs):
     """Train one MLP(64,64) learner per side of a mixed match-up against the other side's checkpoints.  Per update: selection
     (:func:`choose_frozen`), one :meth:`PairRunner.run`, then per side (0, then 1) ``alg_ppo.clean_and_assemble`` and
     ``alg_ppo.optimise_indexed`` on that side's half of the envs (``num_envs / 2 * nsteps`` rows), its printed line and its
     checkpoint ``log_dir/agentS/checkpoints/NNNNN`` (``00000`` before the first update).  ``total_timesteps`` counts each learner's
     own rows.  Each ``log_dir/agentS`` is a run directory of its own for ``eval_against_fix.py`` and ``compare_versions.py``.
-    Returns ``(model0, model1)``, ``model_s.history`` that side's history.  Agent 1's ``eprewmean`` is the mean of its ANNEALED
+    ``fused_rollout``: the rollouts run in the engine's fused launch (``PairRunner(engine_fused=True)``): the same checkpoints, bit for
+    bit.  Returns ``(model0, model1)``, ``model_s.history`` that side's history.  Agent 1's ``eprewmean`` is the mean of its ANNEALED
     episode reward sums (``PairRunner``), not the monitor's figure."""
     from . import alg_ppo
     from .model import PPOModel
     from .policies import PolicySpec
-    check_learn(env, network=network, opponent_mode=opponent_mode, nsteps=nsteps, nminibatches=nminibatches)
+    check_learn(env, network=network, opponent_mode=opponent_mode, nsteps=nsteps, nminibatches=nminibatches, fused_rollout=fused_rollout)
     import torch
     if seed is not None:                                                # as alg_ppo.learn (set_global_seeds)
         np.random.seed(seed)
@@ -356,7 +402,7 @@ def learn(*, env, total_timesteps, network="mlp", opponent_mode="latest", seed=N
     for s in range(2):
         alg_ppo.save_checkpoint(models[s], checkdirs[s], "00000")
         models[s].act_model.seed((seed or 0) * 1000 + 17 * s)
-    runner = PairRunner(env, models, nsteps, gamma, lam, anneal_bound)
+    runner = PairRunner(env, models, nsteps, gamma, lam, anneal_bound, engine_fused=bool(fused_rollout))
     shuffle_gens = []
     for s in range(2):
         g = torch.Generator(device=dev)

@@ -1,4 +1,4 @@
-// engine_host_fused.h -- the fused launches: EnvBuffers .. rollout_launch, the family checks, the zoo tables, the sixteen fused entry points.
+// engine_host_fused.h -- the fused launches: EnvBuffers .. rollout_launch, the family checks, the zoo tables, the seventeen fused entry points.
 // Not in a shard object.
 // A part of the sumo_engine.hip translation unit, not a stand-alone header: no includes of its own.
 
@@ -280,7 +280,7 @@ static int place_zoo_league(RolloutArgs& r, const sumo_zoo_league* z, int od, in
   return 0;
 }
 
-// ---- the sixteen entry points: env buffers, the family's checks (and the mode's), begin_*, the scratch of the learner's /
+// ---- the seventeen entry points: env buffers, the family's checks (and the mode's), begin_*, the scratch of the learner's /
 // checkpoints' side, the opponent table, launch.  Where a zoo MLP table comes before the scratch and a zoo LSTM table after it, that
 // is the order in which the mode reports their errors. ----
 extern "C" int sumo_rollout_steps(sumo_handle_t E, const sumo_rollout* ro, float* actions_dev, float* obs_dev, double* info_dev,
@@ -500,3 +500,52 @@ extern "C" int sumo_match_steps_lstm_zoo(sumo_handle_t E, const sumo_match_lstm*
   return rollout_launch(E, r, 14, b, stream);
 }
 
+// Co-training on a match-up of two species (mode 16).  The entry has its own scene check: rollout_scene keeps refusing mixed scenes for
+// the other entries, here each side is held against ITS agent of the scene (a homogeneous scene is simply a valid one).
+static int check_pair_rollout(sumo_engine* E, const sumo_rollout_pair* ro) {
+  const sumo_model_t* m = &E->hm;
+  if (E->cfrc_mode) FAIL(-12, "cfrc_mode rne_post fills the observations in a second launch per step: use sumo_step (the fused rollout evaluates the policies inside its launch)");
+  if (ro->T < 1 || ro->K < 1 || ro->s0 < 0 || ro->s0 + ro->K > ro->T) FAIL(-5, "steps [%d, %d) outside the rollout buffers (T = %d)", ro->s0, ro->s0 + ro->K, ro->T);
+  if (ro->env_offset < 0 || ro->env_offset + E->N > ro->Ntot) FAIL(-6, "envs [%d, %d) outside the rollout buffers (N = %d)", ro->env_offset, ro->env_offset + E->N, ro->Ntot);
+  const int* anq = SUMO_I(m, agent_nq); const int* anv = SUMO_I(m, agent_nv); const int* anb = SUMO_I(m, agent_nbody);
+  const int* anu = SUMO_I(m, agent_nu);
+  for (int g = 0; g < 2; g++) {
+    const sumo_pair_side& p = ro->side[g];
+    const int od = anq[g] + anv[g] + 6 * anb[g] + 14, ad = anu[g];
+    if (p.ob_dim != od || p.ac_dim != ad) FAIL(-4, "side %d: ob_dim %d / ac_dim %d do not match agent %d of the scene (%d / %d)", g, p.ob_dim, p.ac_dim, g, od, ad);
+    if (p.ac_dim > PT_MAXA) FAIL(-16, "side %d: ac_dim %d above the %d columns of a head", g, p.ac_dim, PT_MAXA);
+    if (p.nrows < 1) FAIL(-7, "side %d: nrows %d: the table needs at least one row", g, p.nrows);
+    const int P = make_layout(p.ob_dim, p.ac_dim).P;
+    if (p.row_stride < P) FAIL(-17, "side %d: row_stride %d below the %d parameters of a row", g, p.row_stride, P);
+    if (!p.table) FAIL(-13, "side %d: missing parameter table", g);
+    if (!p.noise) FAIL(-14, "side %d: missing noise", g);
+    if (!p.obs || !p.act || !p.val || !p.nlp || !p.done) FAIL(-15, "side %d: missing record buffer (obs / act / val / nlp / done)", g);
+    if (p.tile_row && ((ro->env_offset & 15) || (E->N & 15)))
+      FAIL(-11, "side %d: a table row per 16-env tile needs env_offset (%d) and the env count (%d) to be multiples of 16", g, ro->env_offset, E->N);
+  }
+  if (!ro->rew || !ro->ep_done || !ro->ep_r || !ro->ep_l) FAIL(-2, "sumo_rollout_pair: missing buffer (rew / ep_done / ep_r / ep_l)");
+  return 0;
+}
+
+extern "C" int sumo_rollout_steps_pair(sumo_handle_t E, const sumo_rollout_pair* ro, float* actions_dev, float* obs_dev, double* info_dev,
+                                       uint8_t* done_dev, double* ep_r_dev, double* ep_dr_dev, int32_t* ep_l_dev, void* stream) {
+  const EnvBuffers b = {actions_dev, obs_dev, info_dev, done_dev, ep_r_dev, ep_dr_dev, ep_l_dev};
+  RolloutArgs r = {};
+  if (int rc = check_launch_args(E, ro, b)) return rc;
+  if (int rc = check_pair_rollout(E, ro)) return rc;
+  HIPCHK(hipSetDevice(E->device));
+  for (int g = 0; g < 2; g++) {
+    const sumo_pair_side& p = ro->side[g];
+    PairSideArgs& q = r.pair[g];
+    q.table = p.table; q.tile_row = p.tile_row; q.obs = p.obs; q.act = p.act; q.val = p.val; q.nlp = p.nlp; q.done = p.done;
+    q.nrows = p.nrows; q.row_stride = p.row_stride; q.record_row = p.record_row; q.L = make_layout(p.ob_dim, p.ac_dim);
+  }
+  r.noise0 = ro->side[0].noise; r.noise1 = ro->side[1].noise;
+  r.rew = ro->rew; r.ep_done = ro->ep_done; r.ep_r = ro->ep_r; r.ep_l = ro->ep_l; r.alpha = ro->alpha;
+  r.T = ro->T; r.Ntot = ro->Ntot; r.env_offset = ro->env_offset; r.s0 = ro->s0; r.K = ro->K;
+  // x [2][XS], XS the wider side's padded width, and one pass's activation rows [2][PT_VS] (policy and value trunk of a recording side)
+  const int dmax = ro->side[0].ob_dim > ro->side[1].ob_dim ? ro->side[0].ob_dim : ro->side[1].ob_dim;
+  const int amax = ro->side[0].ac_dim > ro->side[1].ac_dim ? ro->side[0].ac_dim : ro->side[1].ac_dim;
+  if (int rc = place_mlp_scratch(E, dmax, amax, r, 1)) return rc;
+  return rollout_launch(E, r, 16, b, stream);
+}

@@ -2723,6 +2723,17 @@ struct ZooLstmTable {
                                      // nets (their D is a launch field too).  The loop is shared with modes 1 and 3, so it
                                      // carries no unroll pragma of its own.
 };
+// One side of the co-training launch (POLICY 16): agent g of a match-up whose two sides may differ in observation and action width
+// acts with row tile_row[tile] of its own table of MLP(64,64) rows and keeps its own record [T][Ntot][...] (noise: RolloutArgs::noise0 / 1).
+struct PairSideArgs {
+  const float* table;                // [nrows][row_stride], a row in ppo_forward's flat order
+  const int32_t* tile_row;           // [Ntot / 16]: the row of every 16-env tile of the whole env set, or NULL (row 0)
+  float *obs, *act, *val, *nlp;      // written on the side's recording tiles only
+  uint8_t* done;
+  int nrows, row_stride;
+  int record_row;                    // the side records (and evaluates its value net) on the tiles that play this row; < 0: on every tile
+  ParamLayout L;                     // make_layout(D_g, A_g)
+};
 struct RolloutArgs {
   const float *learner, *opponent;   // flat parameter vectors; opponent: the self-play snapshot pool [npool][P]
   const int32_t* opp_idx;            // [N] snapshot (zoo modes: table row) per env or NULL
@@ -2760,6 +2771,9 @@ struct RolloutArgs {
   int lstm_side, nsnap_lstm;
   // opponent-data reuse for a recurrent learner (POLICY 15): the learner's shadow state along agent 1's stream [N][2 hidden]; appended
   float* st2;
+  // co-training on a match-up of two species (POLICY 16): the two sides; appended.  It reuses noise0 / noise1 (here [T][Ntot][A_g], the
+  // columns of the whole env set), rew, ep_*, T .. K, alpha, XS (one row stride for both x rows) and lds_off
+  PairSideArgs pair[2];
 };
 
 // ---- pieces shared by the four policy phases (each reads a / r through the references its phase received) ----
@@ -3540,6 +3554,102 @@ __device__ __forceinline__ void rollout_policy_phase_vs_zoo(C& c, const SA& a, c
   wave_sync();   // the action buffer is read back by the env step (other lanes), the scratch region is the step's again
 }
 
+// ---- co-training on a match-up of two species (POLICY 16, sumo_rollout_steps_pair) ----
+// policy_load_obs for two widths: observation g into x row g, zero from D_g to XS; where side g records, its D_g columns also go into
+// its record (an exact copy of what was read).
+template <class SA, class RA>
+__device__ __forceinline__ void policy_load_obs_pair(const SA& a, const RA& r, int e, int lane, float* x, int XS, bool rec0, bool rec1, size_t slot) {
+  const float* ob = a.obs + (size_t)e * 2 * a.obs_stride;
+  const int D0 = r.pair[0].L.D, D1 = r.pair[1].L.D;
+  for (int k = lane; k < XS; k += WAVE) {
+    float o0 = 0.0f, o1 = 0.0f;
+    if (k < D0) { o0 = hand_load<true>(ob + k); if (rec0) pt_global(r.pair[0].obs)[slot * D0 + k] = o0; }
+    if (k < D1) { o1 = hand_load<true>(ob + a.obs_stride + k); if (rec1) pt_global(r.pair[1].obs)[slot * D1 + k] = o1; }
+    x[k] = o0; x[XS + k] = o1;
+  }
+}
+// policy_commit_actions for one side of its own width: column i < A_g of agent g's action into the env's action buffer and the step's
+// control vector.
+template <class C, class SA>
+__device__ __forceinline__ void policy_commit_action_side(C& c, const SA& a, int e, int g, int i, float act) {
+  float* ae = const_cast<float*>(a.actions) + ((size_t)e * 2 + g) * a.act_stride;
+  hand_store<true>(ae + i, act);
+  const auto& mdl = model_view(c);
+  S(ctrl)[MI(agent_uadr)[g] + i] = (double)act;
+}
+
+// gauss_row's neglogp of `act` with its three roundings in the order ppo_forward's kernels have them: c A = 0.5 log(2 pi) * A rounded on
+// its own, fma(0.5, ss, c A), then + sum_logstd.  The source expression `0.5f * ss + c * A + sum_logstd` leaves the contraction to the
+// compiler, which forms that fma wherever the product c A has several uses (gauss_row called for two or four rows) and
+// fma(c, A, 0.5 ss) where it has one -- as in the loop over the sides below, whose neglogp then differed from ppo_forward's in the last bit.
+__device__ __forceinline__ float gauss_neglogp_pinned(float m, float std, float sum_logstd, bool ok, float act, int A) {
+  const float z = ok ? (act - m) / std : 0.0f;
+  const float ss = row16_sum(z * z);
+  float cA = 0.5f * PT_LOG2PI_F * (float)A;
+  asm volatile("" : "+v"(cA));   // (a value of its own: nothing is contracted into or out of it)
+  return __builtin_fmaf(0.5f, ss, cA) + sum_logstd;
+}
+
+// Both seats of a co-training step.  Side g plays row tile_row_g[tile] of its table (tile = (env_offset + e) >> 4; a row outside the
+// table raises the launch's abort flag and plays row 0, as policy_checked_row does for the zoo modes).  On a RECORDING tile of side g
+// (record_row_g < 0, or the tile plays that row: wave-uniform) policy and value trunk run in one pass of mlp_rows_valu<2, 1> on x row g
+// and the side's observation, action, neglogp, value and own previous-step done flag go to its record at [s][env_offset + e]; on any
+// other tile only the policy trunk runs (mlp_rows_valu<1, 1>) and nothing of the side is recorded.  Every number is ppo_forward's on
+// that row and observation, bit for bit (mlp_rows_valu, gauss_row).  LDS (floats, from lds_off): x [2][XS] | activation rows [2][PT_VS].
+template <class C, class SA, class RA>
+__device__ __forceinline__ void rollout_policy_phase_pair(C& c, const SA& a, const RA& r, int e, int s) {
+  const int lane = c.lane, i = lane & 15, kq = lane >> 4;
+  const int XS = r.XS;
+  float* xbuf = (float*)(c.sm + r.lds_off);
+  float* hb = xbuf + 2 * XS;
+  const size_t col = (size_t)r.env_offset + e;
+  const size_t slot = (size_t)s * r.Ntot + col;
+  const int tile = (int)(col >> 4);
+  // (scalars, not arrays: the loop over the sides below selects them with its wave-uniform counter)
+  const int j0 = r.pair[0].tile_row ? pt_global(r.pair[0].tile_row)[tile] : 0, j1 = r.pair[1].tile_row ? pt_global(r.pair[1].tile_row)[tile] : 0;
+  const int row0 = __builtin_amdgcn_readfirstlane(policy_checked_row(a, lane, j0, r.pair[0].nrows));
+  const int row1 = __builtin_amdgcn_readfirstlane(policy_checked_row(a, lane, j1, r.pair[1].nrows));
+  const bool rec0 = r.pair[0].record_row < 0 || row0 == r.pair[0].record_row, rec1 = r.pair[1].record_row < 0 || row1 == r.pair[1].record_row;
+  policy_load_obs_pair(a, r, e, lane, xbuf, XS, rec0, rec1, slot);
+  const unsigned dn = policy_prev_done(a, e);
+  if (lane == 0 && rec0) pt_global(r.pair[0].done)[slot] = (uint8_t)dn;
+  if (lane == 1 && rec1) pt_global(r.pair[1].done)[slot] = (uint8_t)(dn >> 8);
+  wave_sync();
+#pragma unroll 1
+  for (int g = 0; g < 2; g++) {   // (one copy of the two trunk passes: the sides differ in launch fields only)
+    const auto& ps = r.pair[g];
+    const int D = ps.L.D, A = ps.L.A;
+    const bool recg = g ? rec1 : rec0;
+    const float PT_GAS* p = pt_global(ps.table) + (size_t)(g ? row1 : row0) * ps.row_stride;
+    const bool colk = i < A, ok = colk && kq == 0;   // a head's row lives in the first 16 lanes
+    const float ls = colk ? p[ps.L.logstd + i] : 0.0f;   // (requested with the first weight rows)
+    const float nz = ok ? pt_global(g ? r.noise1 : r.noise0)[slot * A + i] : 0.0f;
+    float mean, value = 0.0f;
+    if (recg) {
+      const Net nets[2] = {pi_net((const float*)p, ps.L), vf_net((const float*)p, ps.L)};
+      float m[2][1];
+      mlp_rows_valu<2, 1>(nets, xbuf + g * XS, XS, D, hb, lane, m);
+      mean = m[0][0]; value = m[1][0];
+    } else {
+      const Net nets[1] = {pi_net((const float*)p, ps.L)};
+      float m[1][1];
+      mlp_rows_valu<1, 1>(nets, xbuf + g * XS, XS, D, hb, lane, m);
+      mean = m[0][0];
+    }
+    float act = 0.0f;
+    const float std = expf(ls);
+    (void)gauss_row(mean, std, 0.0f, ok, true, nz, act, A);   // the sample; its neglogp follows with the roundings pinned
+    const float nlp = gauss_neglogp_pinned(mean, std, row16_sum(ls), ok, act, A);
+    if (ok) {
+      if (recg) pt_global(ps.act)[slot * A + i] = act;
+      policy_commit_action_side(c, a, e, g, i, act);
+    }
+    if (lane == 0 && recg) { pt_global(ps.nlp)[slot] = nlp; pt_global(ps.val)[slot] = value; }
+    wave_sync();   // the activation rows are the next side's; after the second side: the action buffer is read back by the env step (other
+                   // lanes), the scratch region becomes the mass matrix again
+  }
+}
+
 // Match post phase: where agent 0's episode ended in the step, score it from the step's winner flags (info[.][7] bit 0, just
 // written by this lane): a win if agent 0 carries the flag, a loss if only agent 1 does, a draw otherwise (timeouts, diverged states)
 // -- policy_zoo._evaluate_against's rule.  Counted while wins + losses + draws < quota.
@@ -3612,6 +3722,8 @@ static_assert(sizeof(const Params*) + sizeof(RolloutLaunch) <= 4096, "the launch
 //   14  sumo_match_steps_lstm_zoo           LSTM(128) checkpoints vs zoo MLP nets     match_lstm_side(0) + zoo_mlp_act
 //   15  sumo_rollout_steps_lstm_reuse       LSTM(128) self-play, agent 1 scored and   rollout_policy_phase_lstm<128, true>
 //                                           valued from the learner's shadow state
+//   16  sumo_rollout_steps_pair             two MLP seats of their own widths (mixed  rollout_policy_phase_pair
+//                                           match-ups), each recording on its tiles
 // (4, 8 .. 12 are rollout_policy_phase_vs_zoo<LSTM_LEARNER, ZOO_KIND>.)  The integers are part of the kernels' mangled names, which
 // profiles/ and tools/ refer to.  SL 1 / 2: static Layout.
 template <int NV, int POLICY, int SL = 0>
@@ -3682,6 +3794,7 @@ sumo_rollout_kernel(const Params* P, RolloutLaunch launch_args) {
     else if constexpr (POLICY == 13) rollout_policy_phase_match_cross<128>(c, lp->a, lp->r, e, s);
     else if constexpr (POLICY == 14) rollout_policy_phase_match_lstm_zoo<128>(c, lp->a, lp->r, e, s);
     else if constexpr (POLICY == 15) rollout_policy_phase_lstm<128, true>(c, lp->a, lp->r, e, s);
+    else if constexpr (POLICY == 16) rollout_policy_phase_pair(c, lp->a, lp->r, e, s);
     else rollout_policy_phase(c, lp->a, lp->r, e, s);
 #ifdef SUMO_DBG_HARD_BARRIER
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -3709,7 +3822,7 @@ sumo_rollout_kernel(const Params* P, RolloutLaunch launch_args) {
 }
 
 // Number of POLICY values above; rollout_launch's table and the instantiation lists below cover 0 .. SUMO_N_POLICY - 1.
-#define SUMO_N_POLICY 16
+#define SUMO_N_POLICY 17
 // ---- building in parallel.  The instantiations of sumo_rollout_kernel (7 variants x SUMO_N_POLICY) are most of this file's compile
 // time, and one translation unit compiles on one core.  build.py therefore compiles this file several times side by side and links
 // the objects into one library:
@@ -3727,8 +3840,8 @@ sumo_rollout_kernel(const Params* P, RolloutLaunch launch_args) {
   SUMO_RK(KW, NV, SL, 0) SUMO_RK(KW, NV, SL, 1) SUMO_RK(KW, NV, SL, 2) SUMO_RK(KW, NV, SL, 3) SUMO_RK(KW, NV, SL, 4)              \
   SUMO_RK(KW, NV, SL, 5) SUMO_RK(KW, NV, SL, 6) SUMO_RK(KW, NV, SL, 7) SUMO_RK(KW, NV, SL, 8) SUMO_RK(KW, NV, SL, 9)              \
   SUMO_RK(KW, NV, SL, 10) SUMO_RK(KW, NV, SL, 11) SUMO_RK(KW, NV, SL, 12) SUMO_RK(KW, NV, SL, 13) SUMO_RK(KW, NV, SL, 14)         \
-  SUMO_RK(KW, NV, SL, 15)
-static_assert(SUMO_N_POLICY == 16, "extend SUMO_RK_ALL");
+  SUMO_RK(KW, NV, SL, 15) SUMO_RK(KW, NV, SL, 16)
+static_assert(SUMO_N_POLICY == 17, "extend SUMO_RK_ALL");
 #ifdef SUMO_ROLLOUT_EXTERN
 SUMO_RK_ALL(extern, 28, 0) SUMO_RK_ALL(extern, 32, 0) SUMO_RK_ALL(extern, 36, 0) SUMO_RK_ALL(extern, 40, 0) SUMO_RK_ALL(extern, 44, 0)
 #elif SUMO_ROLLOUT_SHARD == 0

@@ -194,6 +194,11 @@ class SumoVecEnv(VecEnv):
         ``capi.RolloutLstm``)."""
         self.engines[g].rollout_steps_lstm_zoo_league(ro, league, *self.env_ptrs(g), stream=self._stream())
 
+    def rollout_steps_pair_group(self, g, ro):
+        """K fused co-training steps of group ``g`` of a mixed match-up on the current stream (``capi.Engine.rollout_steps_pair``,
+        ``ro`` a ``capi.RolloutPair`` whose ``env_offset`` is the group's first env)."""
+        self.engines[g].rollout_steps_pair(ro, *self.env_ptrs(g), stream=self._stream())
+
     def step_device(self, actions):
         """actions: float32 CUDA tensor [N, 2, act_stride]. Returns (obs, info, done, ep_r, ep_dr, ep_l) tensors that
         are overwritten by the next call."""

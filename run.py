@@ -5,6 +5,7 @@
     python run.py --env RoboSumo-Ant-vs-Ant-v0 --num_env 1024 --nsteps=128 --eval_interval 5 --eval_opponent 00000 \\
         --eval_opponent <zoo>/ant/mlp/agent-params-v1.npy      (play the live learner against fixed opponents every 5 updates)
     python run.py --co_train --env RoboSumo-Ant-vs-Bug-v0 --num_env 4096 --nsteps=128      (two species against each other, co_train.learn)
+    python run.py --co_train --fused_rollout --env RoboSumo-Ant-vs-Bug-v0 --num_env 4096 --nsteps=128      (its rollouts in the fused launch)
 The run directory gets the reference's run files (log.txt, progress.csv, 0.0.monitor.csv, its pickles; ``--no_run_log``: none).
 Unknown ``--key=value`` flags are forwarded to ``learn`` like the reference does (run.py:29-63), but parsed with
 ``ast.literal_eval`` instead of ``eval``.  Under ``torchrun`` every rank takes an equal shard of ``--num_env``.
@@ -76,6 +77,9 @@ def build_parser():
     ap.add_argument("--co_train", action="store_true", help="a MIXED match-up (RoboSumo-Ant-vs-Bug-v0, ...): train one MLP learner per side against "
                     "the other side's checkpoints (co_train.learn; --opponent_mode=latest, the default here, or =random).  The run directory "
                     "gets agent0/ and agent1/, each a run directory of its own")
+    ap.add_argument("--fused_rollout", action="store_true", help="--co_train: run each rollout's steps inside the engine's fused launch "
+                    "(sumo_rollout_steps_pair: both seats act in the wave that owns the env) instead of three launches per step.  Opt-in; "
+                    "the same checkpoints bit for bit; not with --cfrc_mode rne_post")
     return ap
 
 
@@ -101,6 +105,9 @@ def check_co_train(args, extra, world):
                          "agent1/ afterwards with eval_against_fix.py --fused and compare_versions.py")
     if world > 1:
         raise SystemExit("--co_train runs on a single GPU: launch it without torchrun / with WORLD_SIZE=1")
+    if args.fused_rollout and args.cfrc_mode != "zero":
+        raise SystemExit("--co_train --fused_rollout: not with --cfrc_mode %s, whose observations a second launch per step completes (leave "
+                         "--fused_rollout out)" % args.cfrc_mode)
 
 
 def co_train_main(args, extra):
@@ -113,12 +120,16 @@ def co_train_main(args, extra):
         kw.pop(k)
     kw.update(extra)
     kw.setdefault("opponent_mode", "latest")
+    if args.fused_rollout:
+        kw["fused_rollout"] = True
     log_path = os.path.join(args.log_path, "%s-%s" % (args.env, args.suffix))
-    groups = max(1, args.env_groups or 2)      # the step-by-step env launches, on two streams by default
+    # the step-by-step env launches run on two streams by default; a fused launch balances its envs itself
+    groups = max(1, args.env_groups or (1 if args.fused_rollout else 2))
     env = make_vec_env(args.env, args.num_env, args.seed, device=0, groups=groups if args.num_env % (16 * groups) == 0 else 1,
                        cfrc_mode=args.cfrc_mode, adjust_z=args.adjust_z)
     try:
-        co_train.check_learn(env, network=args.network, opponent_mode=kw["opponent_mode"], nsteps=kw["nsteps"], nminibatches=kw["nminibatches"])
+        co_train.check_learn(env, network=args.network, opponent_mode=kw["opponent_mode"], nsteps=kw["nsteps"], nminibatches=kw["nminibatches"],
+                             fused_rollout=args.fused_rollout)
         shutil.rmtree(log_path, ignore_errors=True)
         os.makedirs(log_path, exist_ok=True)
         with open(os.path.join(log_path, "config.pkl"), "wb") as f:
@@ -150,6 +161,8 @@ def main(argv):
     extra = parse_unknown(unknown)
     if args.co_train:
         return co_train_main(args, extra)
+    if args.fused_rollout:
+        raise SystemExit("--fused_rollout belongs to --co_train (a homogeneous match-up's rollouts run in the fused launch by default)")
     from robosumo_selfplay_amd import alg_ac, alg_ppo, defaults, dist as sdist
     from robosumo_selfplay_amd.vec_env import make_vec_env
     learn = {"ppo": alg_ppo.learn, "ac": alg_ac.learn}.get(args.algo)

@@ -8,7 +8,10 @@ a few env steps per 10^4 diverged, run-to-run nondeterministically (tools/determ
 
 The signature looked for: inside a branch-free predicated region, a plain VGPR move whose destination (a) is not consumed inside the region,
 (b) has NO other write in the whole kernel (a conditional assignment `if (c) x = v` always has one: x's earlier value) and (c) is read
-somewhere.  `scan_library` lists such copies per kernel; the build warns about them and tests/test_codegen_check.py fails on them."""
+somewhere.  `scan_library` lists such copies per kernel; the build warns about them and tests/test_codegen_check.py fails on them.
+
+A second form of the same placement, found by tests/test_gpu_fused_matrix.py: the save copy goes to an AGPR (`v_accvgpr_write_b32`) and
+sits behind the exit of a lane-strided loop, where EXEC is empty (`check_drained_exit`)."""
 import os
 import re
 import subprocess
@@ -131,6 +134,29 @@ def check_spills(body):
     return [(k, body[k]) for a, b in regions(body) for k in range(a, b) if body[k].startswith("scratch_store")]
 
 
+def _writes_exec(t):
+    return bool(re.match(r"s_\w+ exec\b", t)) or "saveexec" in t
+
+
+def check_drained_exit(body):
+    """-> list of (index, text): AGPR save copies `v_accvgpr_write_b32 aN, vM` between the back edge of a lane-strided loop
+    (`s_andn2_b64 exec, exec, sX` / `s_cbranch_execnz`: the fall-through runs with NO lane active) and the instruction that restores
+    EXEC.  The copy writes nothing; its restore `v_accvgpr_read_b32 vM, aN` hands every lane what aN held before.  Found in
+    sumo_rollout_kernel<44, 11, 2> behind the filter loop of zoo_lstm_embed (agent 0's sampled action of the league launch, Spider's
+    static-layout variant; tests/test_gpu_fused_matrix.py): the only such copy in either library."""
+    bad = []
+    for i, t in enumerate(body):
+        if not t.startswith("s_cbranch_execnz"):
+            continue
+        for j in range(i + 1, min(len(body), i + 16)):
+            u = body[j]
+            if _writes_exec(u) or u.startswith(("s_cbranch", "s_branch", "s_endpgm", "s_setpc", "s_swappc")):
+                break
+            if u.startswith("v_accvgpr_write_b32"):
+                bad.append((j, u))
+    return bad
+
+
 _STORES = ("ds_write", "global_store", "scratch_store", "flat_store", "buffer_store", "global_atomic", "ds_add")
 _NO_VDST = ("s_", "v_cmp", "v_cmpx")
 
@@ -161,6 +187,7 @@ def scan_kernel(body):
             if writes.get(dst, 0) == 1 and reads.get(dst, 0) >= 1:
                 out.append((idx, t, reads[dst]))
     out += [(idx, t, 0) for idx, t in check_spills(body)]
+    out += [(idx, t, 0) for idx, t in check_drained_exit(body)]
     return out
 
 

@@ -478,7 +478,16 @@ __device__ __forceinline__ void zoo_lstm_embed(const float PT_GAS* emb_w, const 
                                                int Dz, float* erow, int lane) {
   const float PT_GAS* filt = pt_global(filt_);
   const float bias = emb_b[lane];
-  for (int k = lane; k < Dz; k += PT_WAVE) xrow[k] = fminf(fmaxf((xrow[k] - filt[k]) * filt[Dz + k], -clip), clip);
+  // Wave-uniform trips and a clamped column instead of `for (k = lane; k < Dz; k += PT_WAVE)`: a lane-strided loop drains EXEC, and in
+  // sumo_rollout_kernel<44, 11, 2> the register allocator parked a live value (agent 0's sampled action) in an AGPR right behind that
+  // loop's exit, where no lane is active -- the copy wrote nothing and the restore handed back a stale register (DESIGN.md sections 4,
+  // 31).  The lanes past Dz recompute column Dz - 1 and store the same value to the same word.
+  for (int k0 = 0; k0 < Dz; k0 += PT_WAVE) {
+    const int k = k0 + lane < Dz ? k0 + lane : Dz - 1;
+    const float y = fminf(fmaxf((xrow[k] - filt[k]) * filt[Dz + k], -clip), clip);
+    wave_sync();   // every lane has read its column before column Dz - 1 is rewritten
+    xrow[k] = y;
+  }
   wave_sync();
   float acc = 0.0f;
   for (int k0 = 0; k0 < Dz; k0 += 16) {   // sixteen 256-byte weight rows in flight per trip to the L2

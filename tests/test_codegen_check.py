@@ -42,3 +42,21 @@ def test_checker_recognises_the_pattern():
     ]
     hits = codegen_check.scan_kernel(body)
     assert [t for _, t, _ in hits] == ["v_mov_b32_e32 v140, v237"]
+
+
+def test_checker_recognises_a_save_copy_behind_a_drained_loop():
+    """The instructions of sumo_rollout_kernel<44, 11, 2> that tests/test_gpu_fused_matrix.py exposed: the AGPR save of a live VGPR
+    behind the back edge of a lane-strided loop, where no lane is active (flagged); the same copy after EXEC is restored, and an AGPR
+    write inside the loop body, are fine."""
+    loop = ["s_and_saveexec_b64 s[16:17], vcc",
+            "v_cmp_le_i32_e32 vcc, s67, v0",
+            "s_or_b64 s[18:19], vcc, s[18:19]",
+            "v_accvgpr_write_b32 a9, v3",                # inside the loop body: its lanes are active
+            "ds_write_b32 v1, v9",
+            "s_andn2_b64 exec, exec, s[18:19]",
+            "s_cbranch_execnz 65507"]
+    tail = ["v_accvgpr_read_b32 v81, a7", "global_store_dword v72, v81, s[6:7]", "s_endpgm"]
+    bad = loop + ["v_accvgpr_write_b32 a7, v81", "s_mov_b64 s[18:19], 0x100", "s_or_b64 exec, exec, s[16:17]"] + tail
+    good = loop + ["s_mov_b64 s[18:19], 0x100", "s_or_b64 exec, exec, s[16:17]", "v_accvgpr_write_b32 a7, v81"] + tail
+    assert [t for _, t, _ in codegen_check.scan_kernel(bad)] == ["v_accvgpr_write_b32 a7, v81"]
+    assert codegen_check.scan_kernel(good) == []

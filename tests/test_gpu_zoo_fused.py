@@ -202,11 +202,13 @@ def test_learn_fused_fix_opponent_equals_stepwise(tmp_path, monkeypatch):
 
 
 # ---- 7. against numpy -------------------------------------------------------------------------------------------------------
-def test_zoo_rollout_matches_numpy_nets():
+def _assert_rollout_matches_numpy_nets(env_id, zoo_flat):
+    """One fused rollout against ``zoo_flat`` (None: a synthetic net of the scene's width); both nets re-evaluated in numpy on the
+    recorded observations, within the tolerances of the module docstring."""
     N, T = 32, 16
-    env = SumoVecEnv("RoboSumo-Ant-vs-Ant-v0", num_envs=N, seed=5)
+    env = SumoVecEnv(env_id, num_envs=N, seed=5)
     D, A = _dims(env)
-    flat = _synthetic_flat(D - 1, A, 9)
+    flat = _synthetic_flat(D - 1, A, 9) if zoo_flat is None else zoo_flat
     r, pl = _fix_runner(env, T, flat)
     assert r.fused_zoo_ok()
     out = r.run(250)
@@ -234,6 +236,22 @@ def test_zoo_rollout_matches_numpy_nets():
             print("zoo mean err %.3g" % e_mean)
             assert e_mean < 2e-5
     env.close()
+
+
+def test_zoo_rollout_matches_numpy_nets():
+    _assert_rollout_matches_numpy_nets("RoboSumo-Ant-vs-Ant-v0", None)
+
+
+@pytest.mark.parametrize("species", ["ant", "bug", "spider"])
+def test_zoo_rollout_matches_numpy_nets_of_every_species(species):
+    """The same with the golden ``<species>-mlp-v3`` net on ``<Species>-vs-<Species>``: Bug is the dynamic-layout kernel, Spider the
+    widest one -- A = 16 fills the head's 16-column tile, D = 209 is the widest filter stage -- and here both meet a plain numpy
+    restatement instead of another path of the same code.  The tolerances are the module's, unchanged for every species.  Measured
+    worst errors (ant / bug / spider): value 2.8e-6 / 2.0e-6 / 2.4e-6 against 2e-5 * (1 + max |v|), learner neglogp 6.0e-6 / 6.0e-6 /
+    1.2e-5 and zoo neglogp 1.1e-3 / 1.7e-3 / 2.6e-3 against 1e-3 * (1 + max |neglogp|) with neglogps of 10 to 500, zoo mean 5.5e-7 /
+    3.9e-7 / 4.2e-7 against 2e-5: Spider needs no wider bound."""
+    from zoo_lstm_helpers import golden
+    _assert_rollout_matches_numpy_nets("RoboSumo-%s-vs-%s-v0" % (species.title(), species.title()), golden("%s-mlp-v3" % species))
 
 
 # ---- 8. loud failures ---------------------------------------------------------------------------------------------------------

@@ -423,6 +423,24 @@ int sumo_get_cfrc_ext(sumo_handle_t h, double* out);
 int sumo_get_state(sumo_handle_t h, double* qpos, double* qvel, double* warm, int32_t* counters /* [E][2] */);
 int sumo_set_state(sumo_handle_t h, const double* qpos, const double* qvel, const double* warm,
                    const int32_t* counters);
+/* A complete snapshot of the envs: everything a later sumo_step / sumo_rollout_steps* output depends on, as one versioned HOST blob
+ * (DESIGN.md section 32).  Header (SUMO_SNAPSHOT_HEADER_BYTES): magic, version, E, state_stride, nq, nv, cfrc_mode, the fused-launch
+ * count (the hand-over tags in the counters derive from it), adjust_z, a 64-bit FNV-1a hash of the model blob, the payload size.
+ * Payload: the state rows [E][state_stride] float64 whole (qpos, qvel, warm start, the episode accumulators), all four counter words
+ * [E][4] int32, the per-env seeds [E] uint64 and, in cfrc_mode 1, the pre-step state [E][state_stride] and cfrc_ext [E][nbody][6].
+ * Not in it: the fault counters of sumo_stats (a restored engine keeps its own) and what only orders the work (the longest-first
+ * schedule, the ticket counters).  Both calls take HOST pointers and synchronise like sumo_get_state / sumo_set_state.
+ * sumo_snapshot_load checks everything before it writes anything to the device, each mismatch with its own code and message:
+ * -1 NULL pointer, -30 fewer bytes than a header, -31 bad magic, -32 unknown version, -33 another E, -34 another state_stride / nq /
+ * nv, -35 another model (hash), -36 another cfrc_mode, -37 fewer bytes than header + payload, -38 a header whose adjust_z is not
+ * finite (sumo_snapshot_save: -30 where `bytes` is below sumo_snapshot_bytes).  It applies the header's adjust_z as sumo_set_adjust_z
+ * does. */
+#define SUMO_SNAPSHOT_MAGIC 0x50414E534F4D5553ull /* "SUMOSNAP" */
+#define SUMO_SNAPSHOT_VERSION 1
+#define SUMO_SNAPSHOT_HEADER_BYTES 64
+size_t sumo_snapshot_bytes(sumo_handle_t h);
+int sumo_snapshot_save(sumo_handle_t h, void* dst_host, size_t bytes);
+int sumo_snapshot_load(sumo_handle_t h, const void* src_host, size_t bytes);
 /* debug / parity hook: run mj_forward once per env at its current state with ctrl (HOST float64 [E][nu]) and return
  * qacc (HOST float64 [E][nv]) plus per-env {ncon, nefc, newton iterations, dropped contacts} (HOST int32 [E][4]). */
 int sumo_debug_forward(sumo_handle_t h, const double* ctrl, double* qacc, int32_t* counts);

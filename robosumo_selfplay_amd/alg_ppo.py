@@ -18,6 +18,7 @@ from functools import partial
 import numpy as np
 
 from . import dist as sdist
+from . import resume as resume_state
 from . import train_eval
 from .model import PPOModel
 from .policies import build_policy, init_param_list
@@ -394,10 +395,11 @@ def save_checkpoint(model, checkdir, name, selector=None):
 
 def report_update(update, middle, ub, lossvals, epinfos, env_stats_prev, time_elapsed, *, nupdates, nsteps, nbatch, env, runner, league,
                   history, model, report, epinfobuf, update_fn, log_interval, verbose, save_interval, checkdir, selector=None, rank=0,
-                  comm=None):
+                  comm=None, resume_save=None):
     """(shared) The tail of an update: the engine's fault counters and the league's tally into ``history``, ``update_fn``, the run log and
     the evaluation (``report``, rank 0's), the printed line around the learner's own ``middle``, the checkpoint and, with ``comm``, the
-    check that all ranks hold the same weights.  ``nbatch`` counts all ranks.  Returns ``env.stats()``: the next ``env_stats_prev``."""
+    check that all ranks hold the same weights; last of all ``resume_save(update)``, which writes the resume state where one is due
+    (resume.py).  ``nbatch`` counts all ranks.  Returns ``env.stats()``: the next ``env_stats_prev``."""
     env_stats, env_note = env_fault_delta(env, env_stats_prev, history)
     lg_note = league_note(history, runner, league)
     if update_fn is not None:
@@ -421,6 +423,8 @@ def report_update(update, middle, ub, lossvals, epinfos, env_stats_prev, time_el
         import torch
         sdist.assert_synced(model.params, comm)                           # MpiAdamOptimizer.check_synced (mpi_adam_optimizer.py:54-67)
         torch.distributed.barrier(comm)
+    if resume_save is not None:
+        resume_save(update)
     return env_stats
 
 
@@ -430,12 +434,22 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
           nagent=1, anneal_bound=500, vgap=None, kl_threshold=None, neglogp_threshold=10000.0, log_dir=None, comm=None,
           verbose=True, fix_opponent_path=None, opponent_pool=1, fused_fix_opponent=False, fused_selector=False, selector_table_mb=1024,
           run_log=False, eval_interval=0, eval_opponents=None, eval_trials=64, eval_num_env=64, eval_deterministic=True, eval_seed=0,
-          eval_cross_family=False, **network_kwargs):
-    """``run_log=True`` writes the run's files into ``log_dir`` (runlog.py); ``eval_interval`` / ``eval_opponents`` make rank 0 play the
+          eval_cross_family=False, resume_interval=0, resume=False, **network_kwargs):
+    """``resume_interval=k`` writes the run's whole state into ``log_dir/resume/state.pt`` after every k-th update and after the last;
+    ``resume=True`` continues from that file -- the same checkpoints, history and run-log rows as the uninterrupted run, bit for bit --
+    or starts from update 1 where there is none (resume.py).  Single GPU, no ``opponent_pool`` / ``fused_selector`` /
+    mixed match-up; a custom ``model_fn`` must be a ``learner.Learner`` subclass (or a ``functools.partial`` of one).
+    ``run_log=True`` writes the run's files into ``log_dir`` (runlog.py); ``eval_interval`` / ``eval_opponents`` make rank 0 play the
     live learner against fixed opponents every so many updates (train_eval.py), on ``eval_env`` (the reference's parameter) or on
     an env of its own.  With the defaults neither happens and the run writes and draws exactly what it did without them."""
     # a mixed match-up (the two sides differ) trains in fix mode only, through mixed.MixedRunner; the other modes meet the Runner's refusal
     from . import mixed
+    resume_interval = int(resume_interval or 0)
+    if resume or resume_interval:                                        # refused before anything touches the device
+        if resume_interval < 0:
+            raise ValueError("resume_interval must be >= 0 (0: no resume state is written), got %d" % resume_interval)
+        resume_state.check_supported(env=env, opponent_mode=opponent_mode, comm=comm, opponent_pool=opponent_pool,
+                                     fused_selector=fused_selector, model_fn=model_fn)
     mixed_env = mixed.is_mixed(env) and opponent_mode == "fix"
     if mixed_env:
         mixed.check_learn(env, network=network, opponent_mode=opponent_mode, use_opponent_data=use_opponent_data, opponent_pool=opponent_pool,
@@ -456,6 +470,19 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
     cliprange = constfn(cliprange) if isinstance(cliprange, float) else cliprange
     total_timesteps = int(total_timesteps)
     rank, world = (0, 1) if comm is None else (torch.distributed.get_rank(comm), torch.distributed.get_world_size(comm))
+    log_dir = log_dir or os.environ.get("OPENAI_LOGDIR") or "/tmp/robosumo_selfplay_amd"
+    saved = fingerprint = None          # resume.py: the state to continue from; what a state file of this run opens with
+    if resume or resume_interval:
+        fingerprint = resume_state.fingerprint(env=env, nsteps=nsteps, total_timesteps=total_timesteps, network=network,
+                                               network_kwargs=network_kwargs, opponent_mode=opponent_mode, use_opponent_data=use_opponent_data,
+                                               seed=seed, nminibatches=nminibatches, noptepochs=noptepochs, lr=lr, cliprange=cliprange,
+                                               fix_opponent_path=fix_opponent_path)
+    if resume:
+        saved = resume_state.read_state(log_dir)                         # a file that does not load is refused by name
+        if saved is None:
+            print("resume: no state file %s, starting from update 1" % resume_state.state_path(log_dir), flush=True)
+        else:
+            resume_state.check_fingerprint(saved["fingerprint"], fingerprint, resume_state.state_path(log_dir))
     policy = build_policy(env, network, **network_kwargs)
     nenvs = env.num_envs
     ob_space, ac_space = env.observation_space[0], env.action_space[0]
@@ -479,7 +506,6 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
     model.equal_counts = use_opponent_data is None      # opponent-data reuse makes per-rank minibatch sizes differ
     sdist.broadcast_params(model.params, comm)                          # sync_from_root (ppo2/model.py:129-131)
     models = [model] + [mk("model_%d" % i, False) for i in range(1, 1 if mixed_env else nagent)]   # a mixed match-up has no second net of the learner's shape
-    log_dir = log_dir or os.environ.get("OPENAI_LOGDIR") or "/tmp/robosumo_selfplay_amd"
     checkdir = osp.join(log_dir, "checkpoints")
     nupdates = total_timesteps // nbatch
     selector = model_util = None
@@ -497,7 +523,7 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
         names = set(os.listdir(checkdir)) if osp.isdir(checkdir) else set()      # a run directory may already hold checkpoints
         # history mode takes its whole table (one row per checkpoint of the run, at most selector_table_mb) here, before the first update
         selector = FusedSelector(policy, dev, len(names | set("%.5i" % u for u in range(nupdates + 1))), table_mb=selector_table_mb)
-    if rank == 0:
+    if rank == 0 and saved is None:                                     # (a resumed run keeps the 00000 it wrote)
         save_checkpoint(model, checkdir, "00000", selector)              # alg_ppo.py:122-123
     if comm is not None:
         torch.distributed.barrier(comm)
@@ -550,12 +576,37 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
     # rank 0 reports: the evaluator loads its opponents here, once (the other ranks meet it at the loop's barrier)
     report = train_eval.Report(run_log=run_log, plan=eval_plan, log_dir=log_dir, env=env, model=model, history=history, eval_env=eval_env,
                                deterministic=eval_deterministic, seed=eval_seed, first_checkpoint=osp.join(checkdir, "00000"),
-                               log_interval=log_interval, verbose=verbose, opponent_mode=opponent_mode) if rank == 0 else None
+                               log_interval=log_interval, verbose=verbose, opponent_mode=opponent_mode,
+                               resume_log=saved["run_log"] if saved is not None else None) if rank == 0 else None
     tail = dict(nupdates=nupdates, nsteps=nsteps, nbatch=nbatch * world, env=env, runner=runner, history=history, model=model, report=report,
                 epinfobuf=epinfobuf, update_fn=update_fn, log_interval=log_interval, verbose=verbose, save_interval=save_interval,
                 checkdir=checkdir, selector=selector, rank=rank, comm=comm)
     opponent_data = league = None
-    for update in range(1, nupdates + 1):
+    first_update = 1
+    if saved is not None:
+        # set-up has built the same objects as ever; the saved state now overwrites what it drew, and the loop goes on after the saved update
+        if opponent_mode == "fix":                                       # what update 1 installs
+            install_fixed_opponent(runner, fix_opponent_path, ac_space.shape[0], dev, (seed or 0) * 1000 + 17 + rank)
+        resume_state.drop_later_checkpoints(checkdir, saved["update"])
+        done, opponent_data = resume_state.apply(saved, runner=runner, env=env, shuffle_gen=shuffle_gen, epinfobuf=epinfobuf, history=history,
+                                                 device=dev)
+        env_stats = env.stats()                                          # the restored engines count their own faults, from here
+        report.resumed()
+        tfirststart = time.perf_counter() - saved["time_elapsed"]
+        first_update = done + 1
+        if verbose:
+            print("resume: continuing after update %d/%d from %s" % (done, nupdates, resume_state.state_path(log_dir)), flush=True)
+
+    def resume_save(update):
+        """The state after ``update`` into log_dir/resume/state.pt, where one is due; agent 1's rows only where the next selection reads them."""
+        if update % resume_interval == 0 or update == nupdates:
+            resume_state.write_state(log_dir, resume_state.capture(
+                fingerprint=fingerprint, update=update, runner=runner, env=env, shuffle_gen=shuffle_gen,
+                opponent_data=opponent_data if opponent_mode == "ours" else None, epinfobuf=epinfobuf, history=history,
+                time_elapsed=time.perf_counter() - tfirststart, run_log=report.log_state(), device=dev))
+    if resume_interval:
+        tail["resume_save"] = resume_save
+    for update in range(first_update, nupdates + 1):
         assert nbatch % nminibatches == 0
         tstart = time.perf_counter()
         frac = 1.0 - (update - 1.0) / nupdates

@@ -107,6 +107,10 @@ FUSED_ENTRIES = {
 # the fused launches of mixed match-ups, bound like the ones above (a table of its own: FUSED_ENTRIES and EXPORTS list the launches of
 # homogeneous scenes, which matches.py and the runner's rollout modes index)
 PAIR_ENTRIES = {"sumo_rollout_steps_pair": (RolloutPair, None)}
+# the env snapshot of Engine.snapshot / Engine.restore, a table of its own like the one above (EXPORTS is the tuple that the pairing
+# tests pin entry by entry)
+SNAPSHOT_EXPORTS = ("sumo_snapshot_bytes", "sumo_snapshot_save", "sumo_snapshot_load")
+SNAPSHOT_HEADER_BYTES = 64
 
 
 def lib():
@@ -144,6 +148,12 @@ def lib():
         L.sumo_static_layout.argtypes = [vp]
         L.sumo_static_layout.restype = i32
         L.sumo_profile.restype = i32
+        if hasattr(L, "sumo_snapshot_bytes"):   # a SUMO_HIP_LIB build from before the snapshot exports runs everything but snapshot / restore
+            L.sumo_snapshot_bytes.argtypes = [vp]
+            L.sumo_snapshot_bytes.restype = C.c_size_t
+            for n in SNAPSHOT_EXPORTS[1:]:
+                getattr(L, n).argtypes = [vp, vp, C.c_size_t]
+                getattr(L, n).restype = i32
         if hasattr(L, "sumo_debug_wave_ops"):   # a SUMO_HIP_LIB build from before these two debug exports still runs everything else (_debug_export)
             L.sumo_debug_grad_threshold.argtypes = [C.c_double, C.c_double, vp]
             L.sumo_debug_grad_threshold.restype = i32
@@ -172,7 +182,8 @@ def _chk(rc):
 
 
 def _debug_export(name):
-    """One of the two debug exports that an older SUMO_HIP_LIB build may lack: a clear error instead of ctypes' AttributeError."""
+    """One of the exports that an older SUMO_HIP_LIB build may lack (the two debug ones, the snapshot ones): a clear error instead of
+    ctypes' AttributeError."""
     L = lib()
     if not hasattr(L, name):
         raise SumoHipError("%s is not exported by %s: rebuild the engine library" % (name, L._name))
@@ -350,6 +361,22 @@ class Engine:
         warm = f(warm, np.float64, (self.N, self.nv))
         counters = f(counters, np.int32, (self.N, 2))
         _chk(lib().sumo_set_state(self.h, _np(qpos), _np(qvel), _np(warm), _np(counters)))
+
+    def snapshot(self):
+        """Everything a later step's outputs depend on as one versioned blob (uint8 array; ``sumo_snapshot_save``): a 64-byte header,
+        then the state rows whole, all four counter words, the seeds and, in cfrc_mode 'rne_post', the pre-step state and cfrc_ext."""
+        n = int(_debug_export("sumo_snapshot_bytes")(self.h))
+        blob = np.zeros(n, np.uint8)
+        _chk(lib().sumo_snapshot_save(self.h, _np(blob), n))
+        return blob
+
+    def restore(self, blob):
+        """Put a :meth:`snapshot` back (``sumo_snapshot_load``).  A blob of another engine shape, model, cfrc_mode or format raises
+        before anything is written; the fault counters of :meth:`stats` stay this engine's own."""
+        if hasattr(blob, "numpy"):
+            blob = blob.numpy()
+        blob = np.ascontiguousarray(np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray)) else blob, np.uint8).ravel()
+        _chk(_debug_export("sumo_snapshot_load")(self.h, _np(blob), blob.size))
 
     def debug_forward(self, ctrl):
         ctrl = np.ascontiguousarray(ctrl, np.float64)

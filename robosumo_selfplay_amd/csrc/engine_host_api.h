@@ -308,6 +308,102 @@ extern "C" int sumo_set_state(sumo_handle_t E, const double* qpos, const double*
   return 0;
 }
 
+// ---- snapshots (include/sumo_hip.h): host-side copies of the buffers that are state, no kernel
+struct SnapshotHeader {
+  uint64_t magic;
+  uint32_t version;
+  int32_t N, state_stride, nq, nv, cfrc_mode;
+  uint32_t rollout_seq;      // fused launches so far: the hand-over tags in counters[2] derive from it
+  uint32_t pad;
+  double adjust_z;
+  uint64_t model_hash;       // FNV-1a over the model blob
+  uint64_t payload_bytes;
+};
+static_assert(sizeof(SnapshotHeader) == SUMO_SNAPSHOT_HEADER_BYTES, "snapshot header layout");
+
+static uint64_t blob_hash(const std::vector<char>& b) {
+  uint64_t h = 0xCBF29CE484222325ull;
+  for (char ch : b) { h ^= (unsigned char)ch; h *= 0x100000001B3ull; }
+  return h;
+}
+// the payload's parts in order: (device pointer, bytes); the cfrc parts only where rne_post has allocated them
+struct SnapshotPart { void* dev; size_t bytes; };
+static int snapshot_parts(const sumo_engine* E, SnapshotPart* out) {
+  const size_t N = (size_t)E->N;
+  int n = 0;
+  out[n++] = {E->d_state.get(), N * E->state_stride * sizeof(double)};
+  out[n++] = {E->d_counters.get(), N * 4 * sizeof(int)};
+  out[n++] = {E->d_seeds.get(), N * sizeof(uint64_t)};
+  if (E->cfrc_mode && E->d_state_prev) {
+    out[n++] = {E->d_state_prev.get(), N * E->state_stride * sizeof(double)};
+    out[n++] = {E->d_cfrc.get(), N * 6 * E->hm.nbody * sizeof(double)};
+  }
+  return n;
+}
+static size_t snapshot_payload_bytes(const sumo_engine* E) {
+  SnapshotPart p[5];
+  size_t total = 0;
+  for (int i = 0, n = snapshot_parts(E, p); i < n; i++) total += p[i].bytes;
+  return total;
+}
+
+extern "C" size_t sumo_snapshot_bytes(sumo_handle_t E) { return E ? sizeof(SnapshotHeader) + snapshot_payload_bytes(E) : 0; }
+
+extern "C" int sumo_snapshot_save(sumo_handle_t E, void* dst_host, size_t bytes) {
+  if (!E || !dst_host) FAIL(-1, "snapshot: NULL handle or buffer");
+  const size_t payload = snapshot_payload_bytes(E);
+  if (bytes < sizeof(SnapshotHeader) + payload) FAIL(-30, "snapshot: buffer of %zu bytes, %zu needed (sumo_snapshot_bytes)", bytes, sizeof(SnapshotHeader) + payload);
+  HIPCHK(hipSetDevice(E->device));
+  HIPCHK(hipDeviceSynchronize());
+  SnapshotHeader hd;
+  memset(&hd, 0, sizeof hd);
+  hd.magic = SUMO_SNAPSHOT_MAGIC; hd.version = SUMO_SNAPSHOT_VERSION;
+  hd.N = E->N; hd.state_stride = E->state_stride; hd.nq = E->hm.nq; hd.nv = E->hm.nv; hd.cfrc_mode = E->cfrc_mode;
+  hd.rollout_seq = E->rollout_seq; hd.adjust_z = E->adjust_z; hd.model_hash = blob_hash(E->blob); hd.payload_bytes = payload;
+  memcpy(dst_host, &hd, sizeof hd);
+  char* dst = (char*)dst_host + sizeof hd;
+  SnapshotPart p[5];
+  for (int i = 0, n = snapshot_parts(E, p); i < n; i++) {
+    HIPCHK(hipMemcpy(dst, p[i].dev, p[i].bytes, hipMemcpyDeviceToHost));
+    dst += p[i].bytes;
+  }
+  return 0;
+}
+
+extern "C" int sumo_snapshot_load(sumo_handle_t E, const void* src_host, size_t bytes) {
+  if (!E || !src_host) FAIL(-1, "snapshot: NULL handle or buffer");
+  if (bytes < sizeof(SnapshotHeader)) FAIL(-30, "snapshot: %zu bytes are fewer than a header (%zu)", bytes, sizeof(SnapshotHeader));
+  SnapshotHeader hd;
+  memcpy(&hd, src_host, sizeof hd);
+  if (hd.magic != SUMO_SNAPSHOT_MAGIC) FAIL(-31, "snapshot: bad magic %016llx (not an env snapshot)", (unsigned long long)hd.magic);
+  if (hd.version != SUMO_SNAPSHOT_VERSION) FAIL(-32, "snapshot: version %u, this library reads version %d", hd.version, SUMO_SNAPSHOT_VERSION);
+  if (hd.N != E->N) FAIL(-33, "snapshot: taken of %d envs, this engine has %d", hd.N, E->N);
+  if (hd.state_stride != E->state_stride || hd.nq != E->hm.nq || hd.nv != E->hm.nv)
+    FAIL(-34, "snapshot: state rows of another scene (stride %d nq %d nv %d; this engine: stride %d nq %d nv %d)", hd.state_stride, hd.nq, hd.nv,
+         E->state_stride, E->hm.nq, E->hm.nv);
+  if (hd.model_hash != blob_hash(E->blob)) FAIL(-35, "snapshot: taken with another model (blob hash %016llx, this engine %016llx)",
+                                                (unsigned long long)hd.model_hash, (unsigned long long)blob_hash(E->blob));
+  if (hd.cfrc_mode != E->cfrc_mode) FAIL(-36, "snapshot: taken in cfrc_mode %d, this engine is in cfrc_mode %d", hd.cfrc_mode, E->cfrc_mode);
+  const size_t payload = snapshot_payload_bytes(E);
+  if (hd.payload_bytes != payload || bytes < sizeof(SnapshotHeader) + payload)
+    FAIL(-37, "snapshot: %zu bytes with a payload of %llu, %zu + %zu needed", bytes, (unsigned long long)hd.payload_bytes, sizeof(SnapshotHeader), payload);
+  if (!(fabs(hd.adjust_z) <= 1e10)) FAIL(-38, "snapshot: adjust_z is not finite");
+  HIPCHK(hipSetDevice(E->device));
+  HIPCHK(hipDeviceSynchronize());   // no launch of this engine may be reading the state or the parameter block
+  const char* src = (const char*)src_host + sizeof hd;
+  SnapshotPart p[5];
+  for (int i = 0, n = snapshot_parts(E, p); i < n; i++) {
+    HIPCHK(hipMemcpy(p[i].dev, src, p[i].bytes, hipMemcpyHostToDevice));
+    src += p[i].bytes;
+  }
+  if (hd.adjust_z != E->adjust_z) {
+    HIPCHK(hipMemcpy((char*)E->d_params.get() + offsetof(Params, adjust_z), &hd.adjust_z, sizeof(double), hipMemcpyHostToDevice));
+    E->adjust_z = hd.adjust_z;
+  }
+  E->rollout_seq = hd.rollout_seq;
+  return 0;
+}
+
 extern "C" int sumo_stats(sumo_handle_t E, double* out) {
   if (!E || !out) FAIL(-1, "bad arguments");
   HIPCHK(hipSetDevice(E->device));

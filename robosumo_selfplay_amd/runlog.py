@@ -100,15 +100,20 @@ def _csv_line(fields):
 
 # ---- the run's files ---------------------------------------------------------------------------------------------------------
 class RunLog(object):
-    """Writes the files of one run into ``log_dir`` (created if missing; files of an earlier run there are overwritten).
+    """Writes the files of one run into ``log_dir`` (created if missing; files of an earlier run there are overwritten, unless
+    ``resume`` -- a :meth:`state` of the interrupted run -- says to continue them).
 
     ``row(kvs)`` logs one update to ``log.txt`` and ``progress.csv``; ``episodes(epinfos)`` appends a rollout's finished episodes
     to the monitor file; ``history(h)``, ``early_stop_info(l)``, ``ratio_summary(h)`` and ``evaluation(entries)`` rewrite their
     files.  ``header``: extra entries of the monitor file's JSON header (the evaluation opponents' names)."""
 
-    def __init__(self, log_dir, env_id, header=None):
+    def __init__(self, log_dir, env_id, header=None, resume=None):
         self.dir = str(log_dir)
         os.makedirs(self.dir, exist_ok=True)
+        self.monitor_rows = 0
+        if resume is not None:
+            self._continue(resume)
+            return
         self.t_start = time.time()
         self.keys, self.rows = [], []
         for name in ("log.txt", "progress.csv"):
@@ -118,6 +123,31 @@ class RunLog(object):
         with open(os.path.join(self.dir, MONITOR_FILE), "w") as f:
             f.write("# %s\n" % json.dumps(head))
             f.write("r,l,t\n")
+
+    def state(self):
+        """What :meth:`_continue` needs to take the files up where they stand now: the logged rows (exact values), the header of
+        progress.csv, the number of monitor rows and ``t_start``.  Small: one dict per logged update."""
+        return dict(keys=list(self.keys), rows=[dict(r) for r in self.rows], monitor_rows=int(self.monitor_rows), t_start=self.t_start)
+
+    def _continue(self, st):
+        """Continue the files of an interrupted run from ``st`` (a :meth:`state` of it) instead of truncating them: whatever the
+        interrupted process wrote after ``st`` was taken is cut off first -- ``log.txt`` and ``progress.csv`` are rewritten from the
+        saved rows, byte for byte what they held then, and the monitor file keeps its header and its first ``monitor_rows`` episodes --
+        so no update appears twice.  The caller rewrites ``history.json`` and the pickles from the restored history."""
+        self.t_start = st["t_start"]
+        self.keys, self.rows = list(st["keys"]), [dict(r) for r in st["rows"]]
+        self.monitor_rows = int(st["monitor_rows"])
+        mon = self.path(MONITOR_FILE)
+        if not os.path.exists(mon):
+            raise FileNotFoundError("cannot continue the run log: %s is missing" % mon)
+        with open(mon) as f:
+            lines = f.readlines()
+        if len(lines) < 2 + self.monitor_rows:
+            raise ValueError("cannot continue the run log: %s holds %d episodes, the saved state %d" % (mon, len(lines) - 2, self.monitor_rows))
+        _replace(mon, "".join(lines[:2 + self.monitor_rows]))
+        _replace(self.path("log.txt"), "".join(format_table(r) for r in self.rows))
+        line = lambda r: _csv_line(["" if k not in r else str(r[k]) for k in self.keys])
+        _replace(self.path("progress.csv"), (_csv_line(self.keys) if self.keys else "") + "".join(line(r) for r in self.rows))
 
     def path(self, name):
         return os.path.join(self.dir, name)
@@ -155,6 +185,7 @@ class RunLog(object):
         if len(r):
             with open(self.path(MONITOR_FILE), "a") as f:
                 f.write("".join("%r,%d,%r\n" % (float(a), int(b), t) for a, b in zip(r, l)))
+        self.monitor_rows += len(r)
         return len(r)
 
     def history(self, history, **extra):

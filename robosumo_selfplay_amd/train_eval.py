@@ -194,7 +194,8 @@ class Report(object):
     rollout's episodes) and :meth:`log` (one row of the run log).  ``run_log`` False and ``plan`` None: both do nothing."""
 
     def __init__(self, *, run_log, plan, log_dir, env, model, history, first_checkpoint, eval_env=None, deterministic=True, seed=0,
-                 log_interval=10, verbose=False, opponent_mode=None):
+                 log_interval=10, verbose=False, opponent_mode=None, resume_log=None):
+        """``resume_log``: the :meth:`log_state` of an interrupted run, whose files are continued instead of truncated (resume.py)."""
         from . import runlog
         self.model, self.hist, self.plan, self.log_interval, self.verbose = model, history, plan, log_interval, verbose
         self.opponent_mode = opponent_mode
@@ -204,8 +205,21 @@ class Report(object):
             history["eval"] = []
         if run_log:
             names = self.evaluator.names() if self.evaluator is not None else []
-            self.files = runlog.RunLog(log_dir, env.spec.id, header=dict(eval_opponents=names))
+            self.files = runlog.RunLog(log_dir, env.spec.id, header=dict(eval_opponents=names), resume=resume_log)
             self.extra = dict(eval_opponents=names, loss_names=list(model.loss_names))
+
+    def log_state(self):
+        """The run log's position (``RunLog.state``) for the resume state; None without a run log."""
+        return self.files.state() if self.files is not None else None
+
+    def resumed(self):
+        """After the restored ``history`` is in place: the files that are rewritten from it hold it again."""
+        if self.files is not None:
+            self.files.history(self.hist, **self.extra)
+            if "early_stop_info" in self.hist:
+                self.files.early_stop_info(self.hist["early_stop_info"])
+            if self.evaluator is not None and self.hist.get("eval"):
+                self.files.evaluation(self.hist["eval"])
 
     def update(self, update, nupdates, timesteps, epinfos):
         """After an update's optimiser steps (and outside its timing): evaluate if due -- the entry goes to ``history['eval']`` --

@@ -217,6 +217,53 @@ class SumoVecEnv(VecEnv):
         for E_ in self.engines:
             E_.set_adjust_z(self.adjust_z)
 
+    # ---- snapshots ---------------------------------------------------------------------------------------------------
+    _SNAP_BUFFERS = ("obs_dev", "act_dev", "info_dev", "done_dev", "ep_r_dev", "ep_dr_dev", "ep_l_dev")
+
+    def snapshot(self):
+        """The whole env set as a dict: one engine blob per group (``capi.Engine.snapshot``), clones of the seven step buffers, the
+        seeds and whether the next reset still uploads them, ``adjust_z`` / ``cfrc_mode``, and what :meth:`restore` checks (env id,
+        ``num_envs``, ``groups``).  Synchronises.  A later :meth:`restore` -- on this env or on a freshly built one of the same shape --
+        makes every following step, fused rollout launch and reset return what it returned after the snapshot, bit for bit."""
+        self._assert_not_closed()
+        self._torch.cuda.synchronize(self.device)
+        snap = dict(env_id=self.spec.id, num_envs=int(self.num_envs), groups=int(self.groups), adjust_z=float(self.adjust_z),
+                    cfrc_mode=self.cfrc_mode, seeds=np.array(self.seeds, copy=True), _needs_seed=bool(self._needs_seed),
+                    blobs=[E.snapshot() for E in self.engines])
+        for k in self._SNAP_BUFFERS:
+            snap[k] = getattr(self, k).clone()
+        return snap
+
+    def restore(self, snap):
+        """Put a :meth:`snapshot` back (its tensors may live on the host).  Another env id, ``num_envs`` or ``groups`` is refused here,
+        another ``cfrc_mode`` or a damaged blob by the engine, which checks a blob before it writes anything; with several groups the groups
+        already loaded are put back to what they held when a later group's blob is refused.  The engines' fault counters (:meth:`stats`) are not part of a snapshot."""
+        self._assert_not_closed()
+        for k, mine in (("env_id", self.spec.id), ("num_envs", int(self.num_envs)), ("groups", int(self.groups))):
+            if snap[k] != mine:
+                raise ValueError("snapshot of an env with %s=%r cannot be restored into one with %s=%r" % (k, snap[k], k, mine))
+        if snap["cfrc_mode"] != self.cfrc_mode:
+            raise ValueError("snapshot of an env with cfrc_mode=%r cannot be restored into one with cfrc_mode=%r" % (snap["cfrc_mode"], self.cfrc_mode))
+        if len(snap["blobs"]) != len(self.engines):
+            raise ValueError("snapshot holds %d engine blobs, this env has %d groups" % (len(snap["blobs"]), len(self.engines)))
+        self._torch.cuda.synchronize(self.device)
+        done = []
+        try:
+            for E, blob in zip(self.engines, snap["blobs"]):
+                before = E.snapshot() if len(self.engines) > 1 else None      # several groups: a later group's refusal undoes the earlier ones
+                E.restore(blob)
+                done.append((E, before))
+        except Exception:
+            for E, before in done:
+                E.restore(before)
+            raise
+        for k in self._SNAP_BUFFERS:
+            getattr(self, k).copy_(snap[k])
+        self.seeds = np.array(snap["seeds"], dtype=np.uint64, copy=True)
+        self._needs_seed = bool(snap["_needs_seed"])
+        self.adjust_z = float(snap["adjust_z"])
+        self._torch.cuda.synchronize(self.device)
+
     def stats(self):
         """Solver / contact statistics summed over the groups' engines (maxima for the ``max_*`` entries)."""
         out = None

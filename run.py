@@ -6,6 +6,8 @@
         --eval_opponent <zoo>/ant/mlp/agent-params-v1.npy      (play the live learner against fixed opponents every 5 updates)
     python run.py --co_train --env RoboSumo-Ant-vs-Bug-v0 --num_env 4096 --nsteps=128      (two species against each other, co_train.learn)
     python run.py --co_train --fused_rollout --env RoboSumo-Ant-vs-Bug-v0 --num_env 4096 --nsteps=128      (its rollouts in the fused launch)
+    python run.py --env RoboSumo-Ant-vs-Ant-v0 --num_env 4096 --nsteps=128 --resume_interval 10 --resume      (write a resume state every
+        10 updates; started again after a kill, the same command continues the run bit for bit)
 The run directory gets the reference's run files (log.txt, progress.csv, 0.0.monitor.csv, its pickles; ``--no_run_log``: none).
 Unknown ``--key=value`` flags are forwarded to ``learn`` like the reference does (run.py:29-63), but parsed with
 ``ast.literal_eval`` instead of ``eval``.  Under ``torchrun`` every rank takes an equal shard of ``--num_env``.
@@ -80,7 +82,28 @@ def build_parser():
     ap.add_argument("--fused_rollout", action="store_true", help="--co_train: run each rollout's steps inside the engine's fused launch "
                     "(sumo_rollout_steps_pair: both seats act in the wave that owns the env) instead of three launches per step.  Opt-in; "
                     "the same checkpoints bit for bit; not with --cfrc_mode rne_post")
+    ap.add_argument("--resume_interval", type=int, default=0, help="write the run's whole state (learner, optimiser, generators, Runner, envs) "
+                    "into <run dir>/resume/state.pt after every K-th update and after the last (robosumo_selfplay_amd/resume.py); 0 = never")
+    ap.add_argument("--resume", action="store_true", help="continue the run in the run directory from its resume state, bit for bit; the "
+                    "directory is kept.  Without a state file the run starts from update 1, so a job script can always pass it")
     return ap
+
+
+def check_resume(args, world):
+    """What --resume / --resume_interval refuse, before an env is built: each combination with its own message."""
+    if not (args.resume or args.resume_interval):
+        return
+    if args.resume_interval < 0:
+        raise SystemExit("--resume_interval is a number of updates, 0 or more")
+    if args.algo != "ppo":
+        raise SystemExit("--resume / --resume_interval belong to --algo ppo: the %s learner keeps no resume state" % args.algo)
+    if args.co_train:
+        raise SystemExit("--resume / --resume_interval are not available with --co_train (co_train.learn keeps no resume state)")
+    if world > 1:
+        raise SystemExit("--resume / --resume_interval run on a single GPU: launch without torchrun / with WORLD_SIZE=1")
+    sides = args.env.replace("RoboSumo-", "").rsplit("-v", 1)[0].split("-vs-")
+    if len(sides) == 2 and sides[0] != sides[1]:
+        raise SystemExit("--resume / --resume_interval are not available on a mixed match-up (%s): only homogeneous scenes are resumed" % args.env)
 
 
 def check_co_train(args, extra, world):
@@ -159,6 +182,9 @@ def eval_kwargs(args):
 def main(argv):
     args, unknown = build_parser().parse_known_args(argv)
     extra = parse_unknown(unknown)
+    if args.resume or args.resume_interval:
+        from robosumo_selfplay_amd import dist as sdist
+        check_resume(args, sdist.env_rank_world()[2])
     if args.co_train:
         return co_train_main(args, extra)
     if args.fused_rollout:
@@ -186,8 +212,14 @@ def main(argv):
     comm = sdist.init_process_group()
     rank, local_rank, world = sdist.env_rank_world()
     log_path = os.path.join(args.log_path, "%s-%s" % (args.env, args.suffix))
+    resuming = False
+    if args.resume or args.resume_interval:
+        from robosumo_selfplay_amd import resume as resume_state
+        kw.update(resume=args.resume, resume_interval=args.resume_interval)
+        resuming = args.resume and os.path.exists(resume_state.state_path(log_path))
     if rank == 0:
-        shutil.rmtree(log_path, ignore_errors=True)                        # run.py:233-234
+        if not resuming:                                                   # a run that continues keeps its directory
+            shutil.rmtree(log_path, ignore_errors=True)                    # run.py:233-234
         os.makedirs(log_path, exist_ok=True)
     start, per = sdist.shard_envs(args.num_env, rank, world)
     if args.env_groups <= 0:

@@ -311,6 +311,29 @@ int ppo_grad(const float* params, const float* obs, int obs_stride, int ob_dim, 
              const int32_t* idx, int n, double inv_count, float cliprange, float ent_coef, float vf_coef, float* grads,
              double* stats, float* log_ratio_out, void* workspace, void* stream);
 
+/* ppo_grad for the net the zoo forward evaluates (ppo_forward_filtered with PPO_FWD_TANH on rows that are already filtered): the same
+ * objective, row gather, PPO_GRAD_BLOCKS grid, slab reduction, statistics slots, log-ratio output and NaN rules, on the same workspace
+ * (ppo_grad_workspace_bytes serves both entries; one gradient launch in flight per workspace).
+ *   flags    PPO_GRAD_TANH: tanh hidden units in both trunks (the tanhf of the forward kernel; the backward factor is 1 - h*h of the
+ *            stored activation).  0: relu, as ppo_grad.
+ *   value    v = v_scale * head + v_shift, the zoo's return-filter de-normalisation (robosumo/robosumo/policy_zoo/policy.py:58-60); the
+ *            value loss stays 0.5 (v - R)^2, so the head's delta carries v_scale.
+ * With flags = 0, v_scale = 1, v_shift = 0 the call runs ppo_grad's own kernel: gradients, statistics and log-ratios bit for bit.
+ * `obs` holds FILTERED rows (ppo_obs_filter, once per update).  Refused before any launch: an unknown flag bit, v_scale not finite or
+ * <= 0, v_shift not finite, and whatever ppo_grad refuses. */
+#define PPO_GRAD_TANH 1
+int ppo_grad_act(const float* params, const float* obs, int obs_stride, int ob_dim, int ac_dim, const float* actions,
+                 const float* adv_mb, const float* returns, const float* old_neglogp, const float* is_weight,
+                 const int32_t* idx, int n, double inv_count, float cliprange, float ent_coef, float vf_coef, int flags, float v_scale,
+                 float v_shift, float* grads, double* stats, float* log_ratio_out, void* workspace, void* stream);
+
+/* out[r][c] = clip((obs[r][c] - mean[c]) * invstd[c], -clip, clip) for r < n, c < ob_dim: the observation filter of the zoo nets with
+ * the forward kernel's own expression, for a learner that filters its batch copy once per update.  Columns behind ob_dim are neither
+ * read nor written.  out may equal obs when the strides agree.  Refused: n < 1, NULL pointers, clip <= 0, a stride below ob_dim,
+ * out == obs with different strides. */
+int ppo_obs_filter(const float* obs, int n, int obs_stride, int ob_dim, const float* mean, const float* invstd, float clip,
+                   float* out, int out_stride, void* stream);
+
 /* The statistics PPOModel.train returns (model.py:138,205-213) from the sums ppo_grad accumulated: out5 = {policy loss, value loss,
  * entropy, approxkl, clipfrac}; entropy = sum(logstd + 0.5 log(2 pi e)) of the policy the loss was evaluated with
  * (baselines distributions.py:246-247).  logstd float32 [ac_dim] (inside the flat parameter vector), stats double[PPO_NSTATS]. */

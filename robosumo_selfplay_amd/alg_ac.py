@@ -32,6 +32,8 @@ def check_config(network, use_opponent_data, comm):
     """The scope of this learner, checked before anything touches the GPU."""
     if network == "lstm":
         raise NotImplementedError("the A2C learner (--algo ac) supports MLP policies only; recurrent (lstm) policies train with --algo ppo")
+    if network == "zoo_mlp":
+        raise NotImplementedError("the A2C learner (--algo ac) does not take network='zoo_mlp': policy-zoo nets are fine-tuned with --algo ppo")
     if use_opponent_data in ("off_policy", "both"):
         raise NotImplementedError("use_opponent_data=%r: the reference's A2C computes these importance ratios in commented-out code "
                                   "(alg_ac.py:285-290) and fails with NameError; supported here: None and 'direct'" % (use_opponent_data,))

@@ -445,6 +445,12 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
     # a mixed match-up (the two sides differ) trains in fix mode only, through mixed.MixedRunner; the other modes meet the Runner's refusal
     from . import mixed
     resume_interval = int(resume_interval or 0)
+    zoo_net = network == "zoo_mlp"      # fine-tune a policy-zoo MLP net (zoo_learner.py); everything it cannot do is refused here, before the device
+    if zoo_net:
+        from . import zoo_learner
+        zoo_learner.check_learn(env, opponent_mode=opponent_mode, opponent_pool=opponent_pool, fused_selector=fused_selector,
+                                fused_fix_opponent=fused_fix_opponent, eval_interval=eval_interval, eval_opponents=eval_opponents, comm=comm,
+                                resume=resume, resume_interval=resume_interval, load_path=load_path, zoo_init=network_kwargs.get("zoo_init"))
     if resume or resume_interval:                                        # refused before anything touches the device
         if resume_interval < 0:
             raise ValueError("resume_interval must be >= 0 (0: no resume state is written), got %d" % resume_interval)
@@ -496,7 +502,7 @@ def learn(*, network, env, total_timesteps, opponent_mode="ours", use_opponent_d
                 raise ValueError("use_opponent_data %r" % (use_opponent_data,))
             check_recurrent_reuse(opponent_mode, comm)
         assert nenvs % nminibatches == 0, "recurrent minibatches are whole env sequences: nenvs %% nminibatches must be 0"
-    model_fn = model_fn or (LstmPPOModel if recurrent else PPOModel)
+    model_fn = model_fn or (LstmPPOModel if recurrent else zoo_learner.ZooPPOModel if zoo_net else PPOModel)
     dev = getattr(env, "device", torch.device("cuda", 0))
     mk = lambda scope, trainable: model_fn(policy=policy, ob_space=ob_space, ac_space=ac_space, nbatch_act=nenvs,
                                            nbatch_train=nbatch_train, nsteps=nsteps, ent_coef=ent_coef, vf_coef=vf_coef,

@@ -3,7 +3,7 @@
 // Dense layers run on the f32-input matrix cores (v_mfma_f32_16x16x4_f32: exact f32, so results stay comparable with
 // the reference's float32 TF graph).  Inference: one wavefront owns a 16-row tile of the batch, activations of the tile live in
 // LDS (row stride == 2 mod 32 floats -> conflict-free A-operand reads), weights are read straight from L2 as B
-// operands (24.5 k parameters, resident).  Training (ppo_grad_kernel): four waves share a tile, each owning 16 hidden units with
+// operands (24.5 k parameters, resident).  Training (ppo_grad_kernel, ppo_grad_act_kernel): four waves share a tile, each owning 16 hidden units with
 // its weight slices resident in registers; weight gradients accumulate in MFMA accumulator registers across all tiles of a
 // workgroup and are written once as a per-workgroup slab that a second kernel reduces in a fixed order (deterministic, no float
 // atomics).
@@ -2008,6 +2008,12 @@ struct GradArgs {
   float inv_count, cliprange, ent_coef, vf_coef;
   ParamLayout L;
 };
+// ppo_grad_act's kernels take the value affine behind the same arguments (GradArgs itself keeps its size: the kernels of ppo_grad and
+// ppo_a2c_grad read their implicit arguments where they always did)
+struct GradActArgs {
+  GradArgs g;
+  float v_scale, v_shift;   // value = v_scale * head + v_shift
+};
 
 // ---------------------------------------------------------------------------------------------------------
 // Gradient kernel: FOUR waves share a 16-row tile; wave w owns the hidden units 16w .. 16w+15 of both hidden layers.
@@ -2045,8 +2051,12 @@ __device__ __forceinline__ float quad_bcast(float v) {   // the value of lane R 
 //   GRAD_A2C  ActorCriticModel's loss, model.py:257-310 (ppo_a2c_grad): pg = w adv neglogp, no ratio / clip; the value term is
 //             0.5 w (v - R)^2, i.e. weighted too; stats slot 5 receives sum w, slots 3 / 4 (approxkl, clipfrac) stay 0
 enum GradObjective { GRAD_PPO = 0, GRAD_A2C = 1 };
-template <int KT, bool PI, int OBJ>
-__device__ __forceinline__ void grad_net_coop(const GradArgs& a, float* lds, int lane, int w) {
+// TANH (ppo_grad_act, PPO_GRAD_TANH): tanh hidden units in both trunks, the policy-zoo MLP (policy_zoo MLPPolicy, policy.py:23-91) -- the
+//   forward is the tanhf of trunk_forward<true>, the backward factor 1 - h * h comes from the activations the lane still holds.
+// VAFF (ppo_grad_act): the value is v_scale * head + v_shift (the zoo's return-filter de-normalisation, policy.py:58-60); the loss stays
+//   0.5 (v - R)^2, so the head's delta carries v_scale.
+template <int KT, bool PI, int OBJ, bool TANH = false, bool VAFF = false>
+__device__ __forceinline__ void grad_net_coop(const GradArgs& a, float* lds, int lane, int w, float v_scale = 1.0f, float v_shift = 0.0f) {
   const ParamLayout& L = a.L;
   const int XS = a.XS, D = L.D, A = L.A;
   const int i = lane & 15, kq = lane >> 4, tid = threadIdx.x;
@@ -2159,7 +2169,7 @@ __device__ __forceinline__ void grad_net_coop(const GradArgs& a, float* lds, int
     }
     float h1v[4], h2v[4];
 #pragma unroll
-    for (int r = 0; r < 4; r++) { h1v[r] = fmaxf(acc[r] + acc2[r] + bias0, 0.0f); h1[(4 * kq + r) * GHS + cw] = h1v[r]; }
+    for (int r = 0; r < 4; r++) { const float z = acc[r] + acc2[r] + bias0; h1v[r] = TANH ? tanhf(z) : fmaxf(z, 0.0f); h1[(4 * kq + r) * GHS + cw] = h1v[r]; }
     __syncthreads();
     GP(1);
     // ---- second layer
@@ -2174,7 +2184,7 @@ __device__ __forceinline__ void grad_net_coop(const GradArgs& a, float* lds, int
       }
     }
 #pragma unroll
-    for (int r = 0; r < 4; r++) { h2v[r] = fmaxf(acc[r] + acc2[r] + bias1, 0.0f); h2[(4 * kq + r) * GHS + cw] = h2v[r]; }
+    for (int r = 0; r < 4; r++) { const float z = acc[r] + acc2[r] + bias1; h2v[r] = TANH ? tanhf(z) : fmaxf(z, 0.0f); h2[(4 * kq + r) * GHS + cw] = h2v[r]; }
     __syncthreads();
     GP(2);
     request(tile + gridDim.x, src_next);   // the next tile's rows travel during the head and the backward half
@@ -2261,7 +2271,7 @@ __device__ __forceinline__ void grad_net_coop(const GradArgs& a, float* lds, int
 #pragma unroll
       for (int r = 0; r < 4; r++) {
         const bool rok = r0 + 4 * kq + r < a.n;
-        const float v = out[r] + bias2;
+        const float v = VAFF ? v_scale * (out[r] + bias2) + v_shift : out[r] + bias2;
         const float R = rok ? rd[(4 * kq + r) * RDS + 16] : v;
         const float dv = v - R;
         if (OBJ == GRAD_A2C) {   // weighted value loss (model.py:275): the weight rides in side-tile slot 18
@@ -2272,7 +2282,7 @@ __device__ __forceinline__ void grad_net_coop(const GradArgs& a, float* lds, int
           gb2 += dhead;
           continue;
         }
-        const float dhead = (rok && col) ? a.vf_coef * a.inv_count * dv : 0.0f;
+        const float dhead = (rok && col) ? (VAFF ? a.vf_coef * a.inv_count * dv * v_scale : a.vf_coef * a.inv_count * dv) : 0.0f;
         if (w == 0 && rok && i == 0) { st_vf += 0.5 * (double)dv * (double)dv; st_cnt += 1.0; }
         mydout[(4 * kq + r) * 18 + i] = dhead;
         gb2 += dhead;
@@ -2283,7 +2293,7 @@ __device__ __forceinline__ void grad_net_coop(const GradArgs& a, float* lds, int
     // ---- head weight gradient, rows 16w .. 16w+15: gW2 += h2[:, slice]^T dhead
 #pragma unroll
     for (int s_ = 0; s_ < 4; s_++) { const int row = 4 * s_ + kq; gW2 = MFMA(h2[row * GHS + cw], mydout[row * 18 + i], gW2); }
-    // ---- dh2[:, slice] = dhead W2[slice, :]^T, masked by h2 > 0
+    // ---- dh2[:, slice] = dhead W2[slice, :]^T, masked by h2 > 0 (TANH: times 1 - h2^2)
     acc = (f32x4){0, 0, 0, 0};
     {
       const int nk = (net.nout + 3) >> 2;
@@ -2292,7 +2302,10 @@ __device__ __forceinline__ void grad_net_coop(const GradArgs& a, float* lds, int
         if (u < nk) acc = MFMA(mydout[i * 18 + 4 * u + kq], bW2T[u], acc);
     }
 #pragma unroll
-    for (int r = 0; r < 4; r++) { const float d = h2v[r] > 0.0f ? acc[r] : 0.0f; d2[(4 * kq + r) * GHS + cw] = d; gb1 += d; }
+    for (int r = 0; r < 4; r++) {
+      const float d = TANH ? acc[r] * (1.0f - h2v[r] * h2v[r]) : (h2v[r] > 0.0f ? acc[r] : 0.0f);
+      d2[(4 * kq + r) * GHS + cw] = d; gb1 += d;
+    }
     __syncthreads();
     GP(4);
     // ---- gW1[:, slice] += h1^T d2[:, slice]
@@ -2303,7 +2316,7 @@ __device__ __forceinline__ void grad_net_coop(const GradArgs& a, float* lds, int
 #pragma unroll
       for (int ft = 0; ft < 4; ft++) gW1[ft] = MFMA(h1[row * GHS + ft * 16 + i], b, gW1[ft]);
     }
-    // ---- dh1[:, slice] = d2 W1[slice, :]^T, masked by h1 > 0 (only this wave reads its slice of d1 back)
+    // ---- dh1[:, slice] = d2 W1[slice, :]^T, masked by h1 > 0 / times 1 - h1^2 (only this wave reads its slice of d1 back)
     acc = (f32x4){0, 0, 0, 0}; acc2 = (f32x4){0, 0, 0, 0};
     {
       const float4* da = (const float4*)(d2 + i * GHS + kq * 16);
@@ -2315,7 +2328,10 @@ __device__ __forceinline__ void grad_net_coop(const GradArgs& a, float* lds, int
       }
     }
 #pragma unroll
-    for (int r = 0; r < 4; r++) { const float d = h1v[r] > 0.0f ? acc[r] + acc2[r] : 0.0f; d1[(4 * kq + r) * GHS + cw] = d; gb0 += d; }
+    for (int r = 0; r < 4; r++) {
+      const float d = TANH ? (acc[r] + acc2[r]) * (1.0f - h1v[r] * h1v[r]) : (h1v[r] > 0.0f ? acc[r] + acc2[r] : 0.0f);
+      d1[(4 * kq + r) * GHS + cw] = d; gb0 += d;
+    }
     wave_sync();
     GP(5);
     // ---- gW0[:, slice] += x^T d1[:, slice]
@@ -2391,6 +2407,15 @@ __global__ void __launch_bounds__(256, (KT <= 8 ? 2 : 1)) ppo_grad_kernel(GradAr
   if (blockIdx.y == 0) grad_net_coop<KT, true, OBJ>(a, smem_f, lane, wid);
   else grad_net_coop<KT, false, OBJ>(a, smem_f, lane, wid);
 }
+// ppo_grad_act's kernels: the PPO objective with the value affine, relu (TANH = false: flags 0 with a scale or shift) or tanh trunks.
+// tanhf's temporaries do not fit next to the Ant variant's 255 registers at two workgroups per CU: every tanh variant gets a SIMD's
+// whole register file (one workgroup per CU), like the wide relu variants.
+template <int KT, bool TANH>
+__global__ void __launch_bounds__(256, ((TANH || KT > 8) ? 1 : 2)) ppo_grad_act_kernel(GradActArgs a) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  if (blockIdx.y == 0) grad_net_coop<KT, true, GRAD_PPO, TANH, true>(a.g, smem_f, lane, wid, a.v_scale, a.v_shift);
+  else grad_net_coop<KT, false, GRAD_PPO, TANH, true>(a.g, smem_f, lane, wid, a.v_scale, a.v_shift);
+}
 
 // grads[p] = sum over workgroups of the slab of the net that owns p; stats += per-workgroup stats.  ONE launch, two levels, fixed
 // association (deterministic, no float atomics): workgroup (chunk, g) sums the RED_GROUP consecutive slabs of group g for its 256
@@ -2460,12 +2485,19 @@ extern "C" size_t ppo_grad_workspace_bytes(int ob_dim, int ac_dim) {
          (size_t)((L.P + 255) / 256) * sizeof(unsigned int);              // | arrival counter per 256-parameter chunk (zero between calls)
 }
 
-// ppo_grad and ppo_a2c_grad: the same launches (gradient kernel of objective OBJ, then the slab reduction) on the same workspace layout
-template <int OBJ>
+// ppo_grad, ppo_a2c_grad and ppo_grad_act: the same launches (a gradient kernel, then the slab reduction) on the same workspace layout.
+// VAR selects the kernel: GRAD_PLAIN ppo_grad_kernel<KT, OBJ>; GRAD_AFFINE / GRAD_TANH ppo_grad_act_kernel<KT, false / true> (OBJ = GRAD_PPO)
+enum GradVariant { GRAD_PLAIN = 0, GRAD_AFFINE = 1, GRAD_TANH = 2 };
+template <int KT, int OBJ, int VAR>
+static auto grad_kernel_fn() {
+  if constexpr (VAR == GRAD_PLAIN) return ppo_grad_kernel<KT, OBJ>;
+  else return ppo_grad_act_kernel<KT, VAR == GRAD_TANH>;
+}
+template <int OBJ, int VAR = GRAD_PLAIN>
 static int grad_launch(const float* params, const float* obs, int obs_stride, int ob_dim, int ac_dim, const float* actions,
                        const float* adv_mb, const float* returns, const float* old_neglogp, const float* is_weight, const int32_t* idx,
                        int n, double inv_count, float cliprange, float ent_coef, float vf_coef, float* grads, double* stats,
-                       float* log_ratio_out, void* workspace, void* stream) {
+                       float* log_ratio_out, void* workspace, void* stream, float v_scale = 1.0f, float v_shift = 0.0f) {
   if (ac_dim < 1 || ac_dim > MAXA) FAIL(-2, "ac_dim %d not in [1,%d]", ac_dim, MAXA);
   int KT = (ob_dim + 15) / 16;
   if (KT > 14) FAIL(-3, "ob_dim %d too large (max 224)", ob_dim);
@@ -2494,10 +2526,11 @@ static int grad_launch(const float* params, const float* obs, int obs_stride, in
   do {                                                                                                                  \
     static thread_local size_t lds_set_##KTV = 0;                                                                       \
     if (lds > 64 * 1024 && lds > lds_set_##KTV) {                                                                       \
-      HIPCHK(hipFuncSetAttribute((const void*)ppo_grad_kernel<KTV, OBJ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+      HIPCHK(hipFuncSetAttribute((const void*)grad_kernel_fn<KTV, OBJ, VAR>(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
       lds_set_##KTV = lds;                                                                                              \
     }                                                                                                                   \
-    hipLaunchKernelGGL((ppo_grad_kernel<KTV, OBJ>), dim3(nblocks, 2), dim3(256), lds, s, a);                           \
+    if constexpr (VAR == GRAD_PLAIN) hipLaunchKernelGGL((ppo_grad_kernel<KTV, OBJ>), dim3(nblocks, 2), dim3(256), lds, s, a);                          \
+    else hipLaunchKernelGGL((ppo_grad_act_kernel<KTV, VAR == GRAD_TANH>), dim3(nblocks, 2), dim3(256), lds, s, GradActArgs{a, v_scale, v_shift}); \
   } while (0)
   if (KT <= 8) LAUNCH(8);
   else if (KT <= 11) LAUNCH(11);
@@ -2534,6 +2567,53 @@ extern "C" int ppo_a2c_grad(const float* params, const float* obs, int obs_strid
     FAIL(-1, "bad arguments");
   return grad_launch<GRAD_A2C>(params, obs, obs_stride, ob_dim, ac_dim, actions, adv, returns, returns, is_weight, idx, n, inv_count, 0.0f,
                                ent_coef, vf_coef, grads, stats, nullptr, workspace, stream);
+}
+
+// ppo_grad_act: ppo_grad's objective for the net the zoo forward evaluates.  flags 0 with v_scale 1 and v_shift 0 IS ppo_grad (the same
+// kernel, hence the same bits); otherwise the value affine is compiled in, with relu or (PPO_GRAD_TANH) tanh trunks.
+extern "C" int ppo_grad_act(const float* params, const float* obs, int obs_stride, int ob_dim, int ac_dim, const float* actions,
+                            const float* adv_mb, const float* returns, const float* old_neglogp, const float* is_weight, const int32_t* idx,
+                            int n, double inv_count, float cliprange, float ent_coef, float vf_coef, int flags, float v_scale, float v_shift,
+                            float* grads, double* stats, float* log_ratio_out, void* workspace, void* stream) {
+  if (flags & ~PPO_GRAD_TANH) FAIL(-4, "unknown ppo_grad_act flags 0x%x", flags);
+  if (!isfinite(v_scale) || !(v_scale > 0.0f)) FAIL(-5, "v_scale must be finite and > 0");
+  if (!isfinite(v_shift)) FAIL(-6, "v_shift must be finite");
+  if (!params || !obs || !actions || !adv_mb || !returns || !old_neglogp || !is_weight || !grads || !stats || !workspace || n <= 0)
+    FAIL(-1, "bad arguments");
+  if (flags & PPO_GRAD_TANH)
+    return grad_launch<GRAD_PPO, GRAD_TANH>(params, obs, obs_stride, ob_dim, ac_dim, actions, adv_mb, returns, old_neglogp, is_weight, idx, n,
+                                            inv_count, cliprange, ent_coef, vf_coef, grads, stats, log_ratio_out, workspace, stream, v_scale, v_shift);
+  if (v_scale != 1.0f || v_shift != 0.0f)
+    return grad_launch<GRAD_PPO, GRAD_AFFINE>(params, obs, obs_stride, ob_dim, ac_dim, actions, adv_mb, returns, old_neglogp, is_weight, idx, n,
+                                              inv_count, cliprange, ent_coef, vf_coef, grads, stats, log_ratio_out, workspace, stream, v_scale, v_shift);
+  return grad_launch<GRAD_PPO>(params, obs, obs_stride, ob_dim, ac_dim, actions, adv_mb, returns, old_neglogp, is_weight, idx, n, inv_count,
+                               cliprange, ent_coef, vf_coef, grads, stats, log_ratio_out, workspace, stream);
+}
+
+// The zoo nets' observation filter on a whole batch, once per update (the optimiser steps re-read every row noptepochs times): stage_x's
+// expression, element by element; out == obs filters in place.
+__global__ void __launch_bounds__(256) ppo_obs_filter_kernel(const float* obs, int n, int obs_stride, int D, const float* mean, const float* invstd,
+                                                             float clip, float* out, int out_stride) {
+  const size_t total = (size_t)n * D;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+    const size_t row = e / D;
+    const int c = (int)(e - row * D);
+    out[row * out_stride + c] = fminf(fmaxf((obs[row * obs_stride + c] - mean[c]) * invstd[c], -clip), clip);
+  }
+}
+extern "C" int ppo_obs_filter(const float* obs, int n, int obs_stride, int ob_dim, const float* mean, const float* invstd, float clip,
+                              float* out, int out_stride, void* stream) {
+  if (!obs || !mean || !invstd || !out) FAIL(-1, "ppo_obs_filter: NULL pointer");
+  if (n < 1) FAIL(-2, "ppo_obs_filter: n %d < 1", n);
+  if (ob_dim < 1 || obs_stride < ob_dim || out_stride < ob_dim) FAIL(-3, "ppo_obs_filter: strides %d / %d below ob_dim %d", obs_stride, out_stride, ob_dim);
+  if (!(clip > 0.0f)) FAIL(-4, "ppo_obs_filter: clip must be > 0");
+  if (out == obs && out_stride != obs_stride) FAIL(-5, "ppo_obs_filter: in place needs out_stride == obs_stride");
+  const size_t total = (size_t)n * ob_dim;
+  const size_t want = (total + 255) / 256;
+  hipLaunchKernelGGL(ppo_obs_filter_kernel, dim3((unsigned)(want < 65536 ? want : 65536)), dim3(256), 0, (hipStream_t)stream, obs, n, obs_stride,
+                     ob_dim, mean, invstd, clip, out, out_stride);
+  HIPCHK(hipGetLastError());
+  return 0;
 }
 
 #ifdef PPO_GRAD_PROBE

@@ -77,6 +77,9 @@ def build_policy(env, policy_network="mlp", value_network=None, normalize_observ
         if value_network not in (None, "shared"):
             raise NotImplementedError("recurrent architectures are not supported with value_network=copy (reference policies.py:179)")
         return LstmSpec(env.observation_space[0].shape[0], env.action_space[0].shape[0], nlstm=policy_kwargs.get("nlstm", 128))
+    if policy_network == "zoo_mlp":                   # a policy-zoo MLP net to fine-tune (zoo_learner.py); the file fixes the architecture
+        from .zoo_learner import ZooMlpSpec
+        return ZooMlpSpec(env.observation_space[0].shape[0], env.action_space[0].shape[0], policy_kwargs.get("zoo_init"))
     return PolicySpec(env.observation_space[0].shape[0], env.action_space[0].shape[0], policy_network,
                       value_network if value_network is not None else "shared", **policy_kwargs)
 

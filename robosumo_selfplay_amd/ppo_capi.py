@@ -6,6 +6,7 @@ from . import build as _build
 
 NSTATS = 8
 FWD_PI, FWD_VF, FWD_TANH = 1, 2, 4
+GRAD_TANH = 1
 LSTM_GATES_IFOU, LSTM_GATES_IJFO = 0, 1
 _LIB = None
 
@@ -13,7 +14,7 @@ EXPORTS = ("ppo_last_error", "ppo_param_count", "ppo_forward", "ppo_forward_filt
            "ppo_adv_normalize", "ppo_grad_workspace_bytes", "ppo_grad", "ppo_loss_stats", "ppo_clip_adam",
            "ppo_a2c_grad", "ppo_a2c_loss_stats", "ppo_selection_scores_workspace_bytes", "ppo_selection_scores",
            "ppo_adv_moments_masked_ws", "ppo_adv_normalize_masked", "ppo_lstm_head_grad_masked", "ppo_zoo_seat_act", "ppo_mixed_step",
-           "ppo_mixed_pair_step")
+           "ppo_mixed_pair_step", "ppo_grad_act", "ppo_obs_filter")
 
 
 class PpoHipError(RuntimeError):
@@ -117,6 +118,8 @@ def lib():
         L.ppo_grad_workspace_bytes.argtypes = [i32, i32]
         L.ppo_grad_workspace_bytes.restype = C.c_size_t
         L.ppo_grad.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, f64, f32, f32, f32, vp, vp, vp, vp, vp]
+        L.ppo_grad_act.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, f64, f32, f32, f32, i32, f32, f32, vp, vp, vp, vp, vp]
+        L.ppo_obs_filter.argtypes = [vp, i32, i32, i32, vp, vp, f32, vp, i32, vp]
         L.ppo_loss_stats.argtypes = [vp, vp, i32, vp, vp]
         L.ppo_a2c_grad.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, f64, f32, f32, vp, vp, vp, vp]
         L.ppo_a2c_loss_stats.argtypes = [vp, vp, i32, vp, vp]

@@ -44,7 +44,9 @@ def build_parser():
     ap.add_argument("--env", default="RoboSumo-Ant-vs-Ant-v0")
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--num_timesteps", type=float, default=1e8)
-    ap.add_argument("--network", default="mlp")
+    ap.add_argument("--network", default="mlp", help="mlp (relu 64-64, the default), lstm, or zoo_mlp: fine-tune the policy-zoo MLP net given by "
+                    "--zoo_init (--algo ppo; the checkpoints are zoo files)")
+    ap.add_argument("--zoo_init", default=None, help="--network zoo_mlp: the policy-zoo MLP .npy file to start from")
     ap.add_argument("--num_env", type=int, default=1)
     ap.add_argument("--algo", default="ppo", help="ppo (PPO2, alg_ppo.learn) or ac (A2C, alg_ac.learn); the reference's td3 is not ported")
     ap.add_argument("--log_path", default="results")
@@ -104,6 +106,38 @@ def check_resume(args, world):
     sides = args.env.replace("RoboSumo-", "").rsplit("-v", 1)[0].split("-vs-")
     if len(sides) == 2 and sides[0] != sides[1]:
         raise SystemExit("--resume / --resume_interval are not available on a mixed match-up (%s): only homogeneous scenes are resumed" % args.env)
+
+
+def check_zoo_mlp(args, extra, world):
+    """What --network zoo_mlp / --zoo_init refuse, before an env is built: each combination with its own message."""
+    if args.network != "zoo_mlp":
+        if args.zoo_init is not None:
+            raise SystemExit("--zoo_init belongs to --network zoo_mlp")
+        return
+    if args.zoo_init is None:
+        raise SystemExit("--network zoo_mlp needs --zoo_init <policy-zoo MLP .npy file>")
+    if args.algo != "ppo":
+        raise SystemExit("--network zoo_mlp belongs to --algo ppo: the %s learner does not take it" % args.algo)
+    if args.co_train:
+        raise SystemExit("--network zoo_mlp is not available with --co_train (both seats hold MLP(64,64) policies)")
+    if extra.get("opponent_mode", "ours") == "ours":
+        raise SystemExit("--network zoo_mlp: --opponent_mode=ours (the default) is not available; give --opponent_mode=latest, random or fix")
+    if int(extra.get("opponent_pool", 1)) > 1:
+        raise SystemExit("--network zoo_mlp: --opponent_pool is not available")
+    if args.fused_selector:
+        raise SystemExit("--network zoo_mlp: --fused_selector serves opponent_mode=ours, which this learner does not run")
+    if args.fused_fix_opponent:
+        raise SystemExit("--network zoo_mlp: --fused_fix_opponent is not available, the zoo-architecture learner plays step by step")
+    if args.eval_interval or args.eval_opponent:
+        raise SystemExit("--network zoo_mlp: --eval_interval / --eval_opponent are not available; the checkpoints are zoo files, play them "
+                         "with zoo_tournament.py")
+    if args.resume or args.resume_interval:
+        raise SystemExit("--network zoo_mlp: --resume / --resume_interval are not available")
+    if world > 1:
+        raise SystemExit("--network zoo_mlp runs on a single GPU: launch without torchrun / with WORLD_SIZE=1")
+    sides = args.env.replace("RoboSumo-", "").rsplit("-v", 1)[0].split("-vs-")
+    if len(sides) == 2 and sides[0] != sides[1]:
+        raise SystemExit("--network zoo_mlp is not available on a mixed match-up (%s): homogeneous scenes only" % args.env)
 
 
 def check_co_train(args, extra, world):
@@ -182,6 +216,9 @@ def eval_kwargs(args):
 def main(argv):
     args, unknown = build_parser().parse_known_args(argv)
     extra = parse_unknown(unknown)
+    if args.network == "zoo_mlp" or args.zoo_init is not None:
+        from robosumo_selfplay_amd import dist as sdist
+        check_zoo_mlp(args, extra, sdist.env_rank_world()[2])
     if args.resume or args.resume_interval:
         from robosumo_selfplay_amd import dist as sdist
         check_resume(args, sdist.env_rank_world()[2])
@@ -223,16 +260,18 @@ def main(argv):
         os.makedirs(log_path, exist_ok=True)
     start, per = sdist.shard_envs(args.num_env, rank, world)
     if args.env_groups <= 0:
-        stepwise = (os.environ.get("SUMO_FUSED_ROLLOUT", "1") == "0" or args.cfrc_mode != "zero"
+        stepwise = (os.environ.get("SUMO_FUSED_ROLLOUT", "1") == "0" or args.cfrc_mode != "zero" or args.network == "zoo_mlp"
                     or (args.network == "lstm" and int(extra.get("nlstm", 128)) != 128))
         args.env_groups = 2 if stepwise else 1
     groups = args.env_groups if per % max(1, args.env_groups) == 0 else 1
     import torch
     local_rank = local_rank % max(1, torch.cuda.device_count())        # gloo rehearsal of N ranks on fewer GPUs
     env = make_vec_env(args.env, per, args.seed + start, device=local_rank, groups=groups, cfrc_mode=args.cfrc_mode, adjust_z=args.adjust_z)  # run.py:144: env i gets seed + i
-    if args.network == "lstm":       # the RoboSumo defaults describe the MLP (defaults.py:8-26); recurrent nets share the latent
+    if args.network in ("lstm", "zoo_mlp"):   # the RoboSumo defaults describe the MLP (defaults.py:8-26); recurrent nets share the latent, a zoo file fixes its own architecture
         for k in ("value_network", "num_hidden", "num_layers", "activation"):
             kw.pop(k, None)
+    if args.network == "zoo_mlp":
+        kw["zoo_init"] = args.zoo_init
     if rank == 0:
         with open(os.path.join(log_path, "config.pkl"), "wb") as f:        # run.py:176-177
             pickle.dump(dict(vars(args), **kw), f)
